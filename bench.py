@@ -19,7 +19,11 @@ What N > 1 measures (reference seam: hw8/src/sceneio.cpp:387-396, the pixel loop
   `--scaling weak`: every GPU keeps one base frame's worth of pixels, the frame grows by sqrt(N) per side; the
       `metric` string then names the grown frame (it is NOT the headline metric).
 
-Prints ONE JSON line on rank 0 (contract in the task statement): metric/value/... plus `roofline` and `cpu_baseline`.
+Prints ONE JSON line on rank 0: metric/value/unit/ms_per_step/... and the run's `config`.  A plain run does nothing else
+after the timed steps; `--full` adds `roofline` (one untimed counting render) and `cpu_baseline` with the side
+configurations (device-built tree, cost of the exactness gate).  `--dump-outputs DIR` writes what the last timed step
+returned — `rgb` (float radiance) and `rgb8` (tonemapped bytes; at N > 1 only the gathered `rgb8` frame) — as
+DIR/<name>.npy in float32, sampled with a fixed seed past 64 MiB.
 """
 import argparse
 import importlib
@@ -68,9 +72,38 @@ def parse_args(argv=None):
                     help="N>1: strong (default) = the named workload's frame split N ways; weak = per-GPU pixel count fixed, the frame grows (labelled as such)")
     ap.add_argument("--emulate-shards", type=int, default=0, help="diagnostic: render only shard 0 of N on this one GPU (what each GPU does at --gpus N, without the gather)")
     ap.add_argument("--sample-streams", type=int, default=0, help="diagnostic: throughput mode with K random streams per pixel (NOT the reference's pixel stream, hence not the headline metric)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure roofline counters, the CPU baseline and the side configurations (off: the headline only)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and the side configurations")
     ap.add_argument("--cpu-seconds", type=float, default=15.0, help="target CPU time of the bounded baseline sample")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's frame as DIR/<name>.npy (float32)")
     return ap.parse_args(argv)
+
+
+DUMP_BYTES = 64 << 20   # --dump-outputs writes at most this much; larger frames are sampled
+DUMP_SEED = 20241223
+
+
+def dump_sample(n, keep):
+    """Sorted flat indices of the fixed, seeded sample kept of an n-element output (all of them when keep >= n)."""
+    import numpy as np
+    if keep >= n:
+        return np.arange(n)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(n, keep, replace=False))
+
+
+def dump_outputs(out_dir, arrays):
+    """arrays: name -> numpy array.  Saved as float32; when the total would exceed DUMP_BYTES each array keeps its share of the
+    budget as the flat elements dump_sample picks, so two builds given the same arguments write comparable files."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    total = sum(a.size for a in arrays.values())
+    budget = (DUMP_BYTES - 4096 * len(arrays)) // 4          # elements, leaving room for the .npy headers
+    for name, a in arrays.items():
+        a = np.asarray(a, dtype=np.float32)
+        if total > budget:
+            a = a.reshape(-1)[dump_sample(a.size, a.size * budget // total)]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def launch_ranks(args):
@@ -250,6 +283,14 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device="cpu" if rehearsal else "cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:  # before any untimed render reuses the output buffers
+        if world > 1:
+            outs = {"rgb8": frame.cpu().numpy()}                       # the gathered frame: what rank 0's caller receives
+        else:
+            outs = {"rgb8": out_rgb8.cpu().numpy()} if fake else {"rgb": out_rgb.cpu().numpy(), "rgb8": out_rgb8.cpu().numpy()}
+            if not emu:
+                outs = {k: v.reshape(H, W, 3) for k, v in outs.items()}
+        dump_outputs(args.dump_outputs, outs)
     total_samples = W * H * SPP * args.steps
     value = total_samples / elapsed / 1e6
 
@@ -291,6 +332,13 @@ def main():
         return
 
     if rank == 0:
+        base["config"] = {"workload": args.workload if (W, H) == (base_w, base_h) else f"{args.workload} grown to {W}x{H} ({world} x {base_w}x{base_h} pixels)",
+                          "scene": "synth_room_v1 (seed 20241223)", "triangles": int(info.n_triangles),
+                          "emissive_triangles": int(info.n_lights), "width": W, "height": H, "spp": SPP, "ray_depth": 6,
+                          "parallelism": f"pixel tiles {TILE}x{TILE} round-robin over {world} GPU(s)" + ((", gloo gather of u8 tiles (one-GPU rehearsal)" if rehearsal else ", RCCL gather of u8 tiles") if world > 1 else ""),
+                          "bvh_nodes": int(info.n_bvh_nodes), "bvh_depth": int(info.bvh_depth), "light_bvh_depth": int(info.light_bvh_depth), "scene_prep_ms": round(info.prep_ms, 1), "scene_upload_ms": round(info.upload_ms, 1),
+                          "scene_load_ms": round(t_load * 1e3, 1), "device_bytes": int(info.device_bytes)}
+    if rank == 0 and args.full:
         samples_per_render = st.samples  # this rank's share
         # Work counters: closest-hit / light-pdf queries per camera sample (S-bar, P-bar) come from the TIMED renders' own
         # stats when the kernel reports them without the counting variant; node visits / triangle tests (diagnostics only) from
@@ -362,13 +410,7 @@ def main():
         cpu = None
         if not args.no_cpu_baseline and world == 1:
             cpu = cpu_baseline(args, rt, np, sd, W, H, SPP)
-        base["config"] = {"workload": args.workload if (W, H) == (base_w, base_h) else f"{args.workload} grown to {W}x{H} ({world} x {base_w}x{base_h} pixels)",
-                          "scene": "synth_room_v1 (seed 20241223)", "triangles": int(info.n_triangles),
-                          "emissive_triangles": int(info.n_lights), "width": W, "height": H, "spp": SPP, "ray_depth": 6,
-                          "parallelism": f"pixel tiles {TILE}x{TILE} round-robin over {world} GPU(s)" + ((", gloo gather of u8 tiles (one-GPU rehearsal)" if rehearsal else ", RCCL gather of u8 tiles") if world > 1 else ""),
-                          "bvh_nodes": int(info.n_bvh_nodes), "bvh_depth": int(info.bvh_depth), "light_bvh_depth": int(info.light_bvh_depth), "scene_prep_ms": round(info.prep_ms, 1), "scene_upload_ms": round(info.upload_ms, 1),
-                          "scene_load_ms": round(t_load * 1e3, 1), "device_bytes": int(info.device_bytes)}
-        if world == 1 and not args.no_cpu_baseline:  # a lean run (profilers use --no-cpu-baseline) launches nothing but the timed renders and the counting render
+        if world == 1 and not args.no_cpu_baseline:  # --full --no-cpu-baseline (what profilers run) launches nothing but the timed renders and the counting render
             # Untimed side measurement: the same scene with its tree built on the GPU (RT_BUILD_DEVICE_BVH).  Not the
             # headline: the figure order becomes the load order, so these frames follow the reference's estimator, not its pixels.
             try:
@@ -414,6 +456,7 @@ def main():
                 base["config"]["without_exactness_gate"] = {"error": str(e)}
         base["roofline"] = roofline
         base["cpu_baseline"] = cpu
+    if rank == 0:
         print(json.dumps(base), flush=True)
     scene.close()
     if world > 1:

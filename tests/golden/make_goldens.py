@@ -1,4 +1,4 @@
-"""Regenerates tests/golden/pins_*.npz from the compiled reference (oracle/_ref, needs /root/reference).
+"""Regenerates tests/golden/pins_*.npz from the compiled reference (oracle/_ref, built where the reference's sources are).
 Run:  python tests/golden/make_goldens.py      (after `make -C oracle`)"""
 import ctypes as C
 import os
@@ -22,6 +22,7 @@ def main():
         out = pin_cases.eval_functions(oracle_lib.Ref8(sd), sd, seed)
         np.savez_compressed(os.path.join(HERE, f"pins_hw8_functions_{name}.npz"), **out)
         print(name, {k: v.shape for k, v in out.items()})
+    save_function_inputs()
     bi = pin_cases.brdf_inputs()
     br = np.stack([oracle_lib.brdf(L8, "ref8_", float(bi["base_metallic"][i]), bi["base_color"][i], bi["l"][i], bi["v"][i], bi["n"][i],
                                    bi["color"][i], float(bi["metallic"][i]), float(bi["alpha"][i])) for i in range(len(bi["alpha"]))])
@@ -107,6 +108,29 @@ def main():
             out[name + "_md5"] = np.frombuffer(hashlib.md5(open(ppm, "rb").read()).hexdigest().encode(), np.uint8)
         print(name, out[name + "_rgb"].shape, float(out[name + "_rgb"].mean()), bytes(out[name + "_md5"]).decode())
     np.savez_compressed(os.path.join(HERE, "pins_hw5_render.npz"), **out)
+    save_reference_crops()
+
+
+def save_function_inputs():
+    """The soup case's queries, so that tests can tell the goldens still answer the questions pin_cases asks today."""
+    out = pin_cases.function_inputs(pin_cases.random_triangle_scene(), 23)
+    np.savez_compressed(os.path.join(HERE, "pins_hw8_functions_soup_inputs.npz"), **out)
+    print("soup inputs", {k: v.shape for k, v in out.items()})
+
+
+def save_reference_crops():
+    """Crops of full-size frames through the reference's hw7 and hw6 integrators (whole frames would take the CPU hours, hence crops)."""
+    import tempfile
+    out = {}
+    with tempfile.TemporaryDirectory() as td:
+        ref7 = oracle_lib.Ref7(pin_cases.synth_room_without_textures(td))
+    for x0, y0 in pin_cases.HW7_HEADLINE_CROPS:
+        out[f"hw7_headline_{x0}_{y0}_rgb"], _, _ = ref7.render(1920, 1080, 256, rect=(x0, y0, 32, 32))
+        print("hw7 headline crop", (x0, y0), float(out[f"hw7_headline_{x0}_{y0}_rgb"].mean()))
+    x0, y0 = pin_cases.HW6_CONFIG3_REF_CROP
+    out["hw6_config3_rgb"], out["hw6_config3_rgb8"], _ = oracle_lib.Ref6(pin_cases.load_hw6("practice6_2")).render(1024, 1024, 256, rect=(x0, y0, 16, 16))
+    print("hw6 config3 crop", (x0, y0), float(out["hw6_config3_rgb"].mean()))
+    np.savez_compressed(os.path.join(HERE, "pins_reference_crops.npz"), **out)
 
 
 if __name__ == "__main__":

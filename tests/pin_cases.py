@@ -1,7 +1,7 @@
 """Deterministic input sets for pinning the CPU oracle against the compiled reference.
 
 Each case is evaluated once through the reference harnesses (tests/golden/make_goldens.py, only where
-/root/reference exists) and stored in tests/golden/pins_*.npz; tests/test_oracle_pins.py evaluates the
+the reference's sources are at hand) and stored in tests/golden/pins_*.npz; tests/test_oracle_pins.py evaluates the
 same inputs through the oracle and demands bit-identical outputs."""
 import importlib
 import os
@@ -78,18 +78,10 @@ def rays_for(sd, n, seed):
     return origin, d
 
 
-def eval_functions(impl, sd, seed):
-    """impl: Hw8Oracle or Ref8.  Returns dict of output arrays."""
+def function_inputs(sd, seed):
+    """The queries eval_functions puts to an implementation, with the scene's triangles they are put against."""
     o, d = rays_for(sd, 600, seed)
-    hit_idx = np.zeros(len(o), np.int64)
-    hit_val = np.zeros((len(o), 14), np.float32)
-    order = impl.figure_order().astype(np.int64)
-    for i in range(len(o)):
-        idx, val = impl.closest_hit(o[i], d[i])
-        hit_idx[i] = order[idx] if idx >= 0 else -1  # LOAD-order index
-        hit_val[i] = val if idx >= 0 else 0
     lo, ld = rays_for(sd, 400, seed + 1)
-    lpdf = np.array([impl.light_pdf(lo[i], ld[i]) for i in range(len(lo))], np.float32)
     rng = np.random.default_rng(seed + 2)
     k = 500
     xs = rng.uniform(-2, 2, (k, 3)).astype(np.float32)
@@ -99,7 +91,25 @@ def eval_functions(impl, sd, seed):
     vs = unit(rng.normal(0, 1, (k, 3)))
     vs = np.where((np.sum(vs * ns, axis=1, keepdims=True) > 0) & (rng.uniform(size=(k, 1)) < 0.8), -vs, vs).astype(np.float32)
     alphas = (rng.uniform(0.08, 1, k) ** 2).astype(np.float32)
-    mix = np.stack([impl.mix_sample_pdf(1000 + i, xs[i], ns[i], vs[i], float(alphas[i])) for i in range(k)])
+    return {"positions": sd.positions, "material_index": sd.material_index, "o": o, "d": d, "lo": lo, "ld": ld,
+            "xs": xs, "ns": ns, "vs": vs, "alphas": alphas}
+
+
+def eval_functions(impl, sd, seed):
+    """impl: Hw8Oracle or Ref8.  Returns dict of output arrays."""
+    q = function_inputs(sd, seed)
+    o, d = q["o"], q["d"]
+    hit_idx = np.zeros(len(o), np.int64)
+    hit_val = np.zeros((len(o), 14), np.float32)
+    order = impl.figure_order().astype(np.int64)
+    for i in range(len(o)):
+        idx, val = impl.closest_hit(o[i], d[i])
+        hit_idx[i] = order[idx] if idx >= 0 else -1  # LOAD-order index
+        hit_val[i] = val if idx >= 0 else 0
+    lo, ld = q["lo"], q["ld"]
+    lpdf = np.array([impl.light_pdf(lo[i], ld[i]) for i in range(len(lo))], np.float32)
+    xs, ns, vs, alphas = q["xs"], q["ns"], q["vs"], q["alphas"]
+    mix = np.stack([impl.mix_sample_pdf(1000 + i, xs[i], ns[i], vs[i], float(alphas[i])) for i in range(len(xs))])
     return {"figure_order": order, "hit_idx": hit_idx, "hit_val": hit_val, "light_pdf": lpdf, "mix": mix}
 
 
@@ -129,6 +139,26 @@ def hw6_soup(n=300, seed=17):
         sd.materials[i].kind = kinds[i]
         sd.materials[i].ior = 1.5
     return rt.SceneData(sd.positions, None, None, None, sd.material_index, list(sd.materials)[:sd.n_materials], camera=sd.camera, bg=(0.1, 0.2, 0.3))
+
+
+# Crops of full-size frames rendered by the reference's own integrators, stored in tests/golden/pins_reference_crops.npz:
+# the benchmark scene as hw7 sees it at 1920x1080x256, and BASELINE.json configs[2] (practice6_2) at 1024x1024x256.
+HW7_HEADLINE_CROPS = ((944, 524), (64, 900), (1700, 96), (400, 300), (1300, 700), (960, 40))
+HW6_CONFIG3_REF_CROP = (500, 560)
+
+
+def synth_room_without_textures(tmpdir):
+    """The benchmark scene (tools/gen_synth_room.py at its default size) with every texture stripped, as hw7 renders it."""
+    import sys
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import gen_synth_room
+    path, _ = gen_synth_room.generate(tmpdir, 64, 50, 43)
+    sd = rt.load_gltf(path)
+    for i in range(sd.n_materials):
+        m = sd.materials[i]
+        m.base_color_texture = m.emissive_texture = m.metallic_roughness_texture = m.normal_texture = -1
+    sd._build_desc()
+    return sd
 
 
 HW6_CASES = {"practice6_1": (lambda: load_hw6("practice6_1"), 48, 36, 4), "practice6_2": (lambda: load_hw6("practice6_2"), 20, 20, 2),

@@ -7,7 +7,11 @@ import os
 import subprocess
 import sys
 
+import numpy as np
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import bench  # noqa: E402
 
 
 def _run(extra, n):
@@ -58,3 +62,24 @@ def test_failure_of_the_ranks_is_the_parents_exit_code():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--workload", "no_such_workload"],
                          capture_output=True, text=True, timeout=300, cwd=ROOT, env=env)
     assert out.returncode != 0
+
+
+def test_dump_outputs_writes_the_gathered_frame(tmp_path):
+    """--dump-outputs at N > 1: rank 0 writes the frame its caller receives, the gathered tonemapped bytes, as float32."""
+    _run(["--workload", "synth_room_small_320x180x16", "--dump-outputs", str(tmp_path)], 2)
+    assert sorted(os.listdir(tmp_path)) == ["rgb8.npy"]
+    a = np.load(tmp_path / "rgb8.npy")
+    assert a.dtype == np.float32 and np.array_equal(a, bench.FakeScene.expected(np, 320, 180))
+
+
+def test_dump_outputs_samples_a_frame_past_64_mib(tmp_path):
+    """A gathered 3840x2160 frame as float32 is 99.5 MB: the file keeps the fixed, seeded sample dump_sample picks, within 64 MiB,
+    and a second run with the same arguments writes the same file byte for byte."""
+    for run in ("a", "b"):
+        _run(["--workload", "synth_room_v1_3840x2160x1024", "--dump-outputs", str(tmp_path / run)], 2)
+    path = tmp_path / "a" / "rgb8.npy"
+    a = np.load(path)
+    full = bench.FakeScene.expected(np, 3840, 2160).reshape(-1)
+    assert os.path.getsize(path) <= bench.DUMP_BYTES and a.dtype == np.float32 and 0.6 * full.size < a.size < full.size
+    assert np.array_equal(a, full[bench.dump_sample(full.size, a.size)])
+    assert path.read_bytes() == (tmp_path / "b" / "rgb8.npy").read_bytes()

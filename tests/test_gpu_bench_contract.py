@@ -1,10 +1,11 @@
-"""bench.py prints ONE JSON line with the driver's contract fields plus `roofline` and `cpu_baseline` (small workload here; the
-headline workload is what the driver runs)."""
+"""bench.py prints ONE JSON line with the driver's contract fields, plus `roofline` and `cpu_baseline` under --full (small workload
+here; the headline workload is what the driver runs)."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -13,7 +14,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def test_bench_json_line_contract():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "synth_room_small_320x180x16", "--steps", "2", "--warmup", "1",
-                          "--cpu-seconds", "1"], capture_output=True, text=True, timeout=600, cwd=ROOT)
+                          "--full", "--cpu-seconds", "1"], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, out.stdout
@@ -50,3 +51,27 @@ def test_bench_two_rank_rehearsal_on_one_gpu():
     assert len(lines) == 1, out.stdout
     d = json.loads(lines[0])
     assert d["n_gpus"] == 2 and d["scaling"] == "strong" and d["config"]["width"] == 320 and d["config"]["height"] == 180 and d["value"] > 0
+
+
+def test_plain_run_is_lean_and_dumps_the_frame_of_its_last_timed_step(rt, tmp_path):
+    """Without --full the line holds the headline fields and nothing measured after the timed steps; --dump-outputs writes what
+    the last timed step returned, which must be the frame the library renders for the same scene."""
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "synth_room_small_320x180x16", "--steps", "3", "--warmup", "1",
+                          "--dump-outputs", str(tmp_path / "out")], capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, out.stdout
+    d = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "config"):
+        assert k in d, k
+    assert "roofline" not in d and "cpu_baseline" not in d and d["steps"] == 3 and d["warmup"] == 1
+    assert abs(d["value"] - 320 * 180 * 16 / (d["ms_per_step"] * 1e3)) < 0.02 * d["value"]
+    rgb, rgb8 = np.load(tmp_path / "out" / "rgb.npy"), np.load(tmp_path / "out" / "rgb8.npy")
+    assert rgb.dtype == rgb8.dtype == np.float32 and rgb.shape == rgb8.shape == (180, 320, 3)
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import gen_synth_room
+    path, _ = gen_synth_room.generate(str(tmp_path / "scene"), 8, 12, 9)
+    scene = rt.Scene(rt.load_gltf(path))
+    ref, ref8, _ = scene.render(320, 180, 16)
+    scene.close()
+    assert rgb.mean() > 0.01 and np.array_equal(rgb, ref) and np.array_equal(rgb8, ref8.astype(np.float32))

@@ -1,5 +1,7 @@
 """GPU parity for the hw6 integrator (BASELINE.json configs[2]): HIP path through the C-ABI vs the CPU oracle
 (oracle/oracle_hw6.cpp, itself pinned bit-exact against the compiled hw6 reference)."""
+import os
+
 import numpy as np
 import pytest
 
@@ -81,14 +83,19 @@ def test_config3_practice6_2_1024x1024x256_crops(rt):
         cref, cref8, _ = orc.render(1024, 1024, 256, rect=(cx, cy, 16, 16))
         _cmp(f"config3 crop ({cx},{cy})", rgb[cy:cy + 16, cx:cx + 16], cref, rgb8[cy:cy + 16, cx:cx + 16], cref8)
         assert np.array_equal(rgb[cy:cy + 16, cx:cx + 16], cref, equal_nan=True) and np.array_equal(rgb8[cy:cy + 16, cx:cx + 16], cref8)
-    x0, y0 = 500, 560
+    x0, y0 = pin_cases.HW6_CONFIG3_REF_CROP
     ref, ref8, _ = orc.render(1024, 1024, 256, rect=(x0, y0, 16, 16))
     rmse, bad = _cmp("config3 crop", rgb[y0:y0 + 16, x0:x0 + 16], ref, rgb8[y0:y0 + 16, x0:x0 + 16], ref8)
     assert np.array_equal(rgb[y0:y0 + 16, x0:x0 + 16], ref, equal_nan=True) and np.array_equal(rgb8[y0:y0 + 16, x0:x0 + 16], ref8)
-    if oracle_lib.ref_path("libref_hw6.so"):  # the reference's own hw6 code on the same crop (65,536 camera samples)
-        rref, rref8, _ = oracle_lib.Ref6(sd).render(1024, 1024, 256, rect=(x0, y0, 16, 16))
-        rmse, bad = _cmp("config3 crop vs the reference itself", rgb[y0:y0 + 16, x0:x0 + 16], rref, rgb8[y0:y0 + 16, x0:x0 + 16], rref8)
-        assert np.array_equal(rgb[y0:y0 + 16, x0:x0 + 16], rref, equal_nan=True) and np.array_equal(rgb8[y0:y0 + 16, x0:x0 + 16], rref8)
+    # the reference's own hw6 code on the same crop (65,536 camera samples): stored in tests/golden/pins_reference_crops.npz,
+    # and rendered live as well where oracle/_ref/libref_hw6.so is built
+    gold = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "pins_reference_crops.npz"))
+    rref, rref8 = gold["hw6_config3_rgb"], gold["hw6_config3_rgb8"]
+    if oracle_lib.ref_path("libref_hw6.so"):
+        live, live8, _ = oracle_lib.Ref6(sd).render(1024, 1024, 256, rect=(x0, y0, 16, 16))
+        assert np.array_equal(live, rref, equal_nan=True) and np.array_equal(live8, rref8), "stored crop differs from the live reference"
+    rmse, bad = _cmp("config3 crop vs the reference itself", rgb[y0:y0 + 16, x0:x0 + 16], rref, rgb8[y0:y0 + 16, x0:x0 + 16], rref8)
+    assert np.array_equal(rgb[y0:y0 + 16, x0:x0 + 16], rref, equal_nan=True) and np.array_equal(rgb8[y0:y0 + 16, x0:x0 + 16], rref8)
     scene.close()
 
 

@@ -35,7 +35,7 @@ def main():
          "l2_hit_pct": round(100 * tot["TCC_HIT_sum"] / (tot["TCC_HIT_sum"] + tot["TCC_MISS_sum"]), 1),
          "verdict": ("VALU issue" if valu_per_wave * waves_per_simd > 0.85 else "latency x VALU issue") +
                     " on a cache-resident working set (98 MB scene in the Infinity Cache, tree tops in L2): not HBM bandwidth",
-         "source": "rocprofv3 --pmc SQ_* / TCC_* passes (counters only, --kernel-trace) of `bench.py --steps 1 --warmup 0 --spp 16 --no-cpu-baseline`, tools/profiling/profile_bench.sh"}
+         "source": "rocprofv3 --pmc SQ_* / TCC_* passes (counters only, --kernel-trace) of `bench.py --full --steps 1 --warmup 0 --spp 16 --no-cpu-baseline`, tools/profiling/profile_bench.sh"}
     json.dump(j, open(out, "w"), indent=1)
     print(json.dumps(j))
 

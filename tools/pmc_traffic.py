@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Condense two rocprofv3 PMC passes (FETCH_SIZE, WRITE_SIZE — they do not fit in one pass on gfx950) of
-`bench.py --steps 1 --spp 4 --no-cpu-baseline` into profiles/traffic_latest.json: memory-side bytes per launch of the
+`bench.py --full --steps 1 --spp 4 --no-cpu-baseline` into profiles/traffic_latest.json: memory-side bytes per launch of the
 dominant kernel, for bench.py's roofline.traffic.
 
 usage: pmc_traffic.py <dir with the counter_collection CSVs> <workload name> <out.json> [kernel name, default pt_persistent_kernel]
@@ -43,7 +43,7 @@ def main():
          "bytes_per_launch": int((2 * fetch_kb + write_kb) * 1024 / per),
          "bytes_per_launch_uncorrected": int((fetch_kb + write_kb) * 1024 / per),
          "frame_scale": scale,
-         "source": f"rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) of `bench.py --steps 1 --spp {spp_note} --no-cpu-baseline`"
+         "source": f"rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) of `bench.py --full --steps 1 --spp {spp_note} --no-cpu-baseline`"
                    + (f", scaled x{scale:g} to the frame's full sample count (the traffic of this kernel is proportional to the samples it renders)" if scale != 1 else "") + "; "
                    "FETCH_SIZE doubled per MI355X_MICROARCH.md (gfx950 counts 128-B requests at 64 B); fabric-side requests, Infinity-Cache hits included. "
                    "The doubling is calibrated for wide coalesced reads; this kernel's reads are divergent 16-byte-per-lane loads of 64-B nodes and 48-B "

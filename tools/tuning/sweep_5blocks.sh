@@ -1,4 +1,4 @@
-run() { env "$@" timeout -k 10 200 python bench.py --no-cpu-baseline 2>/dev/null | python -c "
+run() { env "$@" timeout -k 10 200 python bench.py --full --no-cpu-baseline 2>/dev/null | python -c "
 import json,sys;d=json.loads(sys.stdin.read());print(sys.argv[1:],d['value'],d['roofline']['kernel_avg_launch_ms'],flush=True)" "$@"; }
 run A=0
 run RTAMD_WF_SPLIT=8:7

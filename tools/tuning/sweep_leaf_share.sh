@@ -1,5 +1,5 @@
 # Share of a wave's active lanes that must wait at a leaf before the leaf phase starts (in 1/256), capped by the leaf batch.
-run() { env "$@" timeout -k 10 200 python bench.py --no-cpu-baseline 2>/dev/null | python -c "
+run() { env "$@" timeout -k 10 200 python bench.py --full --no-cpu-baseline 2>/dev/null | python -c "
 import json,sys;d=json.loads(sys.stdin.read());print(sys.argv[1:],d['value'],d['roofline']['kernel_avg_launch_ms'],flush=True)" "$@"; }
 run RTAMD_WF_LEAF_SHARE_256=32
 run RTAMD_WF_LEAF_SHARE_256=64
