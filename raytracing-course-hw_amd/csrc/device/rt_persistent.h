@@ -148,13 +148,21 @@ RT_DEV int pt_wide_step_nearest(const GpuNode4Q *nodes, const RayGrid &ray, floa
     cur = c0;
     return PT_WIDE_WENT;
 }
+// Which records of wide node `cur` a light sum enters: the one decision of the light walker (pt_wide_step_all) and of the shader's
+// settling of light sums (pt_light_reach), so that both take it with the same code.
+RT_DEV void pt_wide_enter_all(const GpuNode4Q *nodes, uint32_t cur, const RayGrid &ray, uint4 &b0, uint4 &b1, uint4 &b2, uint4 &b3,
+                              bool &h0, bool &h1, bool &h2, bool &h3) {
+    const uint4 *q = reinterpret_cast<const uint4 *>(nodes + cur);
+    b0 = q[0]; b1 = q[1]; b2 = q[2]; b3 = q[3];
+    float n;
+    h0 = slab_test_q(b0, ray, RT_T_MAX, n); h1 = slab_test_q(b1, ray, RT_T_MAX, n);
+    h2 = slab_test_q(b2, ray, RT_T_MAX, n); h3 = slab_test_q(b3, ray, RT_T_MAX, n);
+}
 // Light sums: every entered child is walked, in any order (the callers keep their hits sorted): the first one now, the others wait.
 RT_DEV int pt_wide_step_all(const GpuNode4Q *nodes, const RayGrid &ray, uint32_t (*stack)[64], int lane, int &sp, int cap, uint32_t &cur) {
-    const uint4 *q = reinterpret_cast<const uint4 *>(nodes + cur);
-    const uint4 b0 = q[0], b1 = q[1], b2 = q[2], b3 = q[3];
-    float n;
-    const bool h0 = slab_test_q(b0, ray, RT_T_MAX, n), h1 = slab_test_q(b1, ray, RT_T_MAX, n);
-    const bool h2 = slab_test_q(b2, ray, RT_T_MAX, n), h3 = slab_test_q(b3, ray, RT_T_MAX, n);
+    uint4 b0, b1, b2, b3;
+    bool h0, h1, h2, h3;
+    pt_wide_enter_all(nodes, cur, ray, b0, b1, b2, b3, h0, h1, h2, h3);
     const int nh = (int)h0 + (int)h1 + (int)h2 + (int)h3;
     if (nh == 0) return PT_WIDE_NONE;
     if (sp + nh - 1 > cap) return PT_WIDE_FULL;
@@ -173,6 +181,39 @@ RT_DEV PtRay pt_make_ray(const SceneView &S, F3 o, F3 d) { return make_ray_grid(
 typedef RayInv PtRay;
 #define PT_RAY_IDLE {{0.f, 0.f, 0.f}, {1.f, 1.f, 1.f}}
 RT_DEV PtRay pt_make_ray(const SceneView &, F3 o, F3 d) { return make_ray_inv(o, d); }
+#endif
+#ifndef PT_LIGHT_SETTLE
+#define PT_LIGHT_SETTLE 1      // the shader settles the light sums whose walk enters no record of the light tree's root (1), or no record
+                               // below the root's either (2), instead of handing them to the light walker; 0: every sum is walked, for A/B builds
+#endif
+#if !PT_QUANT_NODES
+#undef PT_LIGHT_SETTLE
+#define PT_LIGHT_SETTLE 0      // the two-box float path walks every sum
+#endif
+#if PT_QUANT_NODES
+// How far the light walker's walk of this ray would get before its first light test, taking the walker's own decisions
+// (pt_wide_enter_all): 0 = it enters no record of the light tree's root; 1 = it enters inner nodes there but none of their records;
+// 2 = it goes further (or LEVELS < 2 and it enters the root).  `steps`: the node steps that took.  A walk that ends at 0 or 1 tests no
+// light, so its sum is exactly the walker's sum of no hits.
+template <int LEVELS>
+RT_DEV int pt_light_reach(const SceneView &S, const RayGrid &ray, int &steps) {
+    uint4 b[4];
+    bool h[4];
+    pt_wide_enter_all(S.light_walk_nodes4, 0u, ray, b[0], b[1], b[2], b[3], h[0], h[1], h[2], h[3]);
+    steps = 1;
+    if (!(h[0] | h[1] | h[2] | h[3])) return 0;
+    if (LEVELS < 2) return 2;
+    for (int c = 0; c < 4; c++) {
+        if (!h[c]) continue;
+        if (b[c].w & RT_LEAF_BIT) return 2;                      // a leaf (or an unused record): the walker tests lights there
+        uint4 g0, g1, g2, g3;
+        bool e0, e1, e2, e3;
+        pt_wide_enter_all(S.light_walk_nodes4, b[c].w, ray, g0, g1, g2, g3, e0, e1, e2, e3);
+        steps++;
+        if (e0 | e1 | e2 | e3) return 2;
+    }
+    return 1;
+}
 #endif
 #define PT_EXACT_BATCH 16             // the exact role walks at most this many queries at once: their stacks (RT_STACK_SIZE entries each) share the wave's LDS stack area
 
@@ -204,7 +245,7 @@ struct PtParams {
     uint32_t front_first;             // 1: the queues serve the front of the workgroup's group list first (the host sorted it by cost, most expensive first)
     int prio;                         // experiment: 1 = walker stints run at raised wave priority (s_setprio 2), 2 = shader batches do
     unsigned long long deadline_ticks; // 100 MHz ticks a wave may spend in this launch before it gives up (error)
-    unsigned long long *counters;     // [0] closest-hit queries, [1] light queries, [2] node visits, [3] triangle tests, [10] discarded speculative hits, [12] exact closest hits, [13] exact light sums, [14] waves that gave up waiting for a lost path (error), [29] waves that ran into the launch deadline (error)
+    unsigned long long *counters;     // [0] closest-hit queries, [1] light queries, [2] node visits, [3] triangle tests, [10] discarded speculative hits, [12] exact closest hits, [13] exact light sums, [14] waves that gave up waiting for a lost path (error), [29] waves that ran into the launch deadline (error); counting builds: [30] / [31] light sums whose walk ends at the light tree's root / one level below it (pt_light_reach)
     unsigned long long *debug;        // nullable: per workgroup {start time, exit time of its last wave (100 MHz ticks), paths}
     // COUNT builds, RTAMD_TRACE_PIXEL: every hit record the shader consumes for pixel trace_pixel (= y * width + x) is appended as
     // four float4 (r0..r3 of the path record: ray, hit, packed word); word 0 of trace_buf counts the entries
@@ -218,6 +259,7 @@ struct PtProf {
     // where a walker's wave time goes (counting build): [0] hand-off and refill, [1] inner nodes, [2] leaves; tests / lane-tests of the leaf loops; light hits
     unsigned long long t_part[2][3] = {{0, 0, 0}, {0, 0, 0}}, leaf_iters[2] = {0, 0}, leaf_lane_iters[2] = {0, 0}, light_hits = 0, light_tests = 0; // the last two per lane
     unsigned long long t_sub[2][3] = {{0, 0, 0}, {0, 0, 0}}, refills[2] = {0, 0}; // of [0]: publish finished walks | take new ones from the bitmap | read their rays
+    unsigned long long light_reach[2] = {0, 0}; // light sums whose walk ends at the light tree's root / one level below it (pt_light_reach), per lane
 };
 template <bool COUNT> struct PtLap { // s_memtime laps of the counting build
     unsigned long long t;
@@ -1038,19 +1080,38 @@ __global__ __launch_bounds__(P8_THREADS, P8_PER_CU) void pt_persistent_kernel(Sc
             if (got != PT_NONE) { PtPark pk; pk.p = (PtLdsWord)&stack[0][lane]; todo = pt_shade_lean<FEAT>(S, R, W, pt_slot(sh, got), pk, discarded); }
 #endif
             n_discarded += __popcll(pt_ballot(discarded));
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
             const bool next = got != PT_NONE && todo != PT_SHADE_EXACT && (todo & WF_NEXT_TRACE), with_light = next && (todo & WF_NEXT_LIGHT);
-            bool wire = false; // the new ray pierces a tripwire (rt_exact.h): its closest hit is the exact role's
-            if (S.n_tripwire_groups && next) {
+            bool wire = false;    // the new ray pierces a tripwire (rt_exact.h): its closest hit is the exact role's
+            bool settled = false; // its light sum is settled here (PT_LIGHT_SETTLE): the walk would test no light
+            int settle_steps = 0; // the node steps that decision took (the cost the light walker would have booked)
+            if (next && (S.n_tripwire_groups || ((COUNT || PT_LIGHT_SETTLE) && with_light))) {
                 const float4 *nr = wf_rec(W, pt_slot(sh, got));
                 const float4 n0 = nr[0], n1 = nr[1];
-                wire = pt_tripwire(S, f3(n0.x, n0.y, n0.z), f3(n0.w, n1.x, n1.y));
+                const F3 o = f3(n0.x, n0.y, n0.z), d = f3(n0.w, n1.x, n1.y);
+                if (S.n_tripwire_groups) wire = pt_tripwire(S, o, d);
+#if PT_QUANT_NODES
+                if ((COUNT || PT_LIGHT_SETTLE) && with_light) { // the counting build classifies every sum, whatever it settles
+                    const int reach = pt_light_reach<COUNT ? 2 : PT_LIGHT_SETTLE>(S, pt_make_ray(S, o, d), settle_steps);
+                    if (COUNT) { prof.light_reach[0] += reach == 0; prof.light_reach[1] += reach == 1; }
+                    settled = reach < PT_LIGHT_SETTLE;
+                    if (settled) { // what the walker's finish() does with no hit, before the release below publishes the path
+                        const int depth = (int)(__float_as_uint(reinterpret_cast<const float *>(nr + 3)[3]) & 15u);
+                        float *pdf = reinterpret_cast<float *>(wf_entry(W, pt_slot(sh, got), depth)) + 3;
+                        *pdf = *pdf + 0.f / S.n_lights_f;                      // distributions.h:123,273 (+0.f: a -0 sum becomes +0)
+                    }
+                }
+#endif
             }
-            if (next) atomicOr(&sh.pending[got >> 4], (PT_BIT_T | (with_light ? PT_BIT_L : 0u)) << ((got & 15u) * 2u));
+            n_light += __popcll(pt_ballot(settled)); // a settled sum is still a light-pdf query of the algorithm
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+            const bool walk_light = with_light && !settled;
+            if (next) atomicOr(&sh.pending[got >> 4], (PT_BIT_T | (walk_light ? PT_BIT_L : 0u)) << ((got & 15u) * 2u));
             pt_push(sh, PT_Q_TRACE, got, next && !wire);
-            pt_push(sh, PT_Q_LIGHT, got, with_light);
+            pt_push(sh, PT_Q_LIGHT, got, walk_light);
             pt_push(sh, PT_Q_XTRACE, got, (got != PT_NONE && todo == PT_SHADE_EXACT) || wire);
-            if (got != PT_NONE && todo != PT_SHADE_EXACT) atomicAdd(&sh.cost[got >> pt_gshift(sh)], (uint32_t)PT_COST_SHADE);
+            if (got != PT_NONE && todo != PT_SHADE_EXACT)
+                atomicAdd(&sh.cost[got >> pt_gshift(sh)], (uint32_t)PT_COST_SHADE + (settled ? PT_COST_LIGHT_NODE * (uint32_t)settle_steps : 0u));
+            if (COUNT && settled) n_nodes += (unsigned long long)settle_steps;
             const unsigned long long done = pt_ballot(got != PT_NONE && (todo == 0 || todo == WF_PARKED)); // finished, or parked for the next phase
             if (done && lane == 0) atomicSub(&sh.cnt[PT_N_LIVE], (int)__popcll(done));
             idle_spins = 0;
@@ -1104,6 +1165,7 @@ __global__ __launch_bounds__(P8_THREADS, P8_PER_CU) void pt_persistent_kernel(Sc
     if (COUNT && P.counters) {
         atomicAdd(&P.counters[2], n_nodes); atomicAdd(&P.counters[3], n_tris);
         atomicAdd(&P.counters[58], prof.light_hits); atomicAdd(&P.counters[59], prof.light_tests);
+        atomicAdd(&P.counters[30], prof.light_reach[0]); atomicAdd(&P.counters[31], prof.light_reach[1]);
         if (lane == 0) { // wave-level profile, words 16..27 and 48..57
             atomicAdd(&P.counters[16], prof.t_trace); atomicAdd(&P.counters[17], prof.t_light); atomicAdd(&P.counters[18], prof.t_shade);
             atomicAdd(&P.counters[19], prof.t_exact); atomicAdd(&P.counters[20], prof.t_idle);

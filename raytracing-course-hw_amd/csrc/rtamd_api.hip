@@ -1311,6 +1311,8 @@ int rt_render(rt_scene *scene, const rt_render_params *p, float *out_rgb, uint8_
                     fprintf(stderr, "[rtamd]   light tests %llu (%.2f per light sum), hits %llu (%.2f per light sum); triangle tests of closest-hit walks %llu (%.2f per query)\n",
                             h_cnt[59], (double)h_cnt[59] / (double)(h_cnt[1] ? h_cnt[1] : 1), h_cnt[58], (double)h_cnt[58] / (double)(h_cnt[1] ? h_cnt[1] : 1),
                             h_cnt[3] - h_cnt[59], (double)(h_cnt[3] - h_cnt[59]) / (double)(h_cnt[0] ? h_cnt[0] : 1));
+                    fprintf(stderr, "[rtamd]   light sums whose walk ends at the light tree's root %llu (%.1f %%), one level below it %llu (%.1f %%); settled by the shader: level %d\n",
+                            h_cnt[30], 100.0 * h_cnt[30] / (double)(h_cnt[1] ? h_cnt[1] : 1), h_cnt[31], 100.0 * h_cnt[31] / (double)(h_cnt[1] ? h_cnt[1] : 1), PT_LIGHT_SETTLE);
                 }
                 if (const char *dump = getenv("RTAMD_DUMP_WG")) { // diagnostic: start / exit time (ms after the first start) and paths of every workgroup of the last launch
                     if (FILE *f = fopen(dump, "w")) {
