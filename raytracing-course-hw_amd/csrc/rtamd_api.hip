@@ -7,6 +7,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <functional>
 #include <memory>
 #include <stdexcept>
 #include <string>
@@ -102,14 +103,11 @@ struct rt_scene {
     std::vector<hipEvent_t> ev_pool; // brackets every launch of the dominant kernel when stats are requested
     bool device_tree = false;                 // RT_BUILD_DEVICE_BVH: figure order = LOAD order, no reference trees
     unsigned long long *d_pt_debug = nullptr; // persistent pipeline: per workgroup {start, exit time, paths} (RTAMD_DEBUG_COUNTERS)
-    float4 *pt_r0 = nullptr;         // persistent pipeline: path records of one pass
+    void *pt_records = nullptr;      // persistent pipeline: path records of one pass
     uint32_t *pt_groups = nullptr;   // [cost per group | group_ofs (n_blocks + 1) | group_ids]: the re-deal between the phases of a frame
-    size_t pt_slots = 0, pt_levels = 0, pt_group_words = 0;
+    size_t pt_record_bytes = 0, pt_group_words = 0;
     uint32_t pt_passes = 0, pt_blocks = 0, pt_launches = 0;
     double pt_rebalance_ms = 0, pt_imbalance = 0;
-    float4 *pt6_r0 = nullptr;        // hw6 persistent pipeline: path records (frames included) of one pass
-    size_t pt6_slots = 0;
-    int pipeline = 0;                // RT_PIPELINE_* of the last render
     void free_wf() {
         for (void *p : wf_allocs) (void)hipFree(p);
         wf_allocs.clear();
@@ -119,9 +117,8 @@ struct rt_scene {
     ~rt_scene() {
         free_wf();
         if (d_partial) (void)hipFree(d_partial);
-        if (pt_r0) (void)hipFree(pt_r0);
+        if (pt_records) (void)hipFree(pt_records);
         if (pt_groups) (void)hipFree(pt_groups);
-        if (pt6_r0) (void)hipFree(pt6_r0);
         if (d_pt_debug) (void)hipFree(d_pt_debug);
         for (void *p : allocations) (void)hipFree(p);
         if (ev_start) (void)hipEventDestroy(ev_start);
@@ -712,7 +709,7 @@ static void launch_wavefront(rt_scene *scene, const SceneView &V, const RenderVi
 // costs measured over the long middle phase — measured: no gain (hw6 practice6_2 191.7 vs 193.6 Msamples/s, headline 284.2 vs 284.6):
 // what remains of the spread of the workgroups' exit times after one re-deal is not the amount of work but the serial samples of the
 // slowest pixels.
-static std::vector<int> phase_stops(bool rebalance, int phase0, int samples, int default_phases, bool small_population) {
+static std::vector<int> phase_stops(bool rebalance, int phase0, int samples, bool small_population) {
     std::vector<int> stops;
     if (rebalance && getenv("RTAMD_PT_STOPS")) { // experiment: explicit sample counts at which the frame is re-dealt, e.g. "2,16"
         int last = 0;
@@ -730,7 +727,7 @@ static std::vector<int> phase_stops(bool rebalance, int phase0, int samples, int
         // first phase is the costly one there (slowest workgroup / mean 1.8 on hw6's 1024x1024 frame) — then the usual one
         if (small_population && phase0 > 2 && !getenv("RTAMD_PT_PHASE0")) stops.push_back(2);
         stops.push_back(phase0);
-        const int want = getenv("RTAMD_PT_PHASES") ? atoi(getenv("RTAMD_PT_PHASES")) : default_phases;
+        const int want = getenv("RTAMD_PT_PHASES") ? atoi(getenv("RTAMD_PT_PHASES")) : 2;
         const int mid = phase0 + (samples - phase0) * 3 / 4;
         if (want >= 3 && samples >= 64 && mid > phase0 && mid < samples) stops.push_back(mid);
     }
@@ -746,9 +743,9 @@ static std::vector<int> phase_stops(bool rebalance, int phase0, int samples, int
 // waves per SIMD, then three ...  So the deal is by speed: speed(b) = (cost of the sub-tiles b owned) / (its run time) in the phase that
 // just ended, and a sub-tile goes to the workgroup with the smallest load / speed.  `owner` (sub-tile -> workgroup of the phase that
 // just ended; empty = the kernel's round-robin deal) is updated to the new deal.  d_times: per workgroup {start, exit, -} in 100 MHz
-// ticks (PtParams::debug), nullable.
-static void redeal_groups(rt_scene *scene, const uint32_t *d_cost, uint32_t *d_ofs, uint32_t *d_ids, uint32_t groups, uint32_t blocks, uint32_t groups_per_block, hipStream_t stream,
-                          const unsigned long long *d_times = nullptr, std::vector<uint32_t> *owner = nullptr) {
+// ticks (PtParams::debug), nullable.  gamma_round / gamma_own: the kernel's speed model (below).
+static void redeal_groups(rt_scene *scene, const uint32_t *d_cost, uint32_t *d_ofs, uint32_t *d_ids, uint32_t groups, uint32_t blocks, uint32_t groups_per_block,
+                          double gamma_round, double gamma_own, hipStream_t stream, const unsigned long long *d_times, std::vector<uint32_t> *owner) {
     std::vector<uint32_t> cost(groups), ofs, ids, order(groups);
     HIP_CHECK(hipStreamSynchronize(stream));
     const double t0 = now_ms();
@@ -772,9 +769,8 @@ static void redeal_groups(rt_scene *scene, const uint32_t *d_cost, uint32_t *d_o
         // difference than an even finish will: 2.0 measured best for the hw8 kernel on the 1080p frame — its youngest workgroups
         // still left last at 1.5 (exit times by dispatch round 1,028 / 1,024 / 1,035 / 1,071 / 1,118 ms) — and 1.5 for the hw6 kernel) and the
         // workgroup's own deviation from it (most of which is gone in the next phase: damped).
-        const bool hw6_kernel = scene->flavor == RT_INTEGRATOR_HW6;
-        const double gamma_round = getenv("RTAMD_PT_SPEED_GAMMA") ? atof(getenv("RTAMD_PT_SPEED_GAMMA")) : (hw6_kernel ? 1.5 : 2.0);
-        const double gamma_own = getenv("RTAMD_PT_SPEED_GAMMA_OWN") ? atof(getenv("RTAMD_PT_SPEED_GAMMA_OWN")) : (hw6_kernel ? 0.4 : 0.3);
+        if (getenv("RTAMD_PT_SPEED_GAMMA")) gamma_round = atof(getenv("RTAMD_PT_SPEED_GAMMA"));
+        if (getenv("RTAMD_PT_SPEED_GAMMA_OWN")) gamma_own = atof(getenv("RTAMD_PT_SPEED_GAMMA_OWN"));
         const uint32_t round_size = scene->n_cus > 0 && blocks % (uint32_t)scene->n_cus == 0 ? (uint32_t)scene->n_cus : blocks;
         for (uint32_t r0 = 0; r0 < blocks; r0 += round_size) {
             double lsum = 0; uint32_t ln = 0;
@@ -832,8 +828,9 @@ static void redeal_groups(rt_scene *scene, const uint32_t *d_cost, uint32_t *d_o
     if (total) scene->pt_imbalance = (double)before_max * blocks / (double)total; // slowest workgroup / mean under the round-robin deal
 }
 
-// Persistent dataflow driver (device/rt_persistent.h): ONE launch renders up to n_cus x PT_MAX_PATHS path slots; larger frames
-// (or throughput mode with many streams) take several passes over disjoint slot ranges, each a complete render of its pixels.
+// Persistent dataflow driver (hw8 / hw7: device/rt_persistent.h, hw6: device/rt_persistent_hw6.h): ONE launch renders up to
+// n_cus x per_cu x max_paths path slots; larger frames (or throughput mode with many streams) take several passes over disjoint slot
+// ranges, each a complete render of its pixels.
 //
 // Load balance.  A workgroup owns its pixels for a whole launch, and pixels differ in cost (sky: one query per sample, a glossy
 // interior: up to 2 x depth), so with the plain round-robin deal of the 8x8 sub-tiles the slowest workgroup ends 3 % (1080p on
@@ -841,11 +838,56 @@ static void redeal_groups(rt_scene *scene, const uint32_t *d_cost, uint32_t *d_o
 // 1/16 of the samples with the round-robin deal while every workgroup counts the hits it shades per sub-tile, then the host
 // re-deals the sub-tiles (longest processing time first onto the least loaded workgroup) and the second launch resumes every
 // pixel from its record (pixel sum, random stream and the parked camera ray are all there; pixels do not depend on the deal).
+// For hw6 the cost of a pixel spans 1 to 63 walks per sample (a wall against the glass bunny), so the deal matters far more.
 // Every launch is bracketed by events when `time_trace` (ev_pool[2k], ev_pool[2k+1]).
-static void launch_persistent(rt_scene *scene, const SceneView &V, const RenderView &R, uint32_t n_work, hipStream_t stream, bool count, bool time_trace) {
+//
+// What the two kernels do not share is their PersistentKernel.
+struct PersistentKernel {
+    uint32_t max_paths;               // paths per workgroup (its LDS bitmap)
+    int per_cu;                       // workgroups per CU
+    size_t record_bytes;              // path record per slot
+    int cost_t, cost_l;               // PtParams::cost_t / cost_l
+    bool hw8_knobs;                   // RTAMD_WF_SPLIT, RTAMD_PT_PRIO and the RTAMD_TRACE_PIXEL dump apply
+    double gamma_round, gamma_own;    // the re-deal's speed model (redeal_groups)
+    // one launch of `blocks` workgroups over the path slots [slot_base, slot_base + n_slots) of `records`
+    std::function<void(uint32_t blocks, const RenderView &R, const dev::PtParams &P, float4 *records, uint32_t slot_base, uint32_t n_slots)> launch;
+};
+
+static PersistentKernel hw8_persistent(const SceneView &V, int ray_depth, hipStream_t stream, bool count) {
+    const uint32_t stride = (uint32_t)WF_REC_BASE + 2u * (uint32_t)ray_depth; // float4 per slot
+    // kernel variant by the features this render can reach (fewer features, fewer spilled registers): the hw7 integrator has no
+    // environment map; an hw8 render needs the environment lookup only when the scene has a map
+    const int feat = V.hw7 ? WF_FEAT_HW7 : (V.env_image >= 0 ? WF_FEAT_ENV : 0);
+    return {PT_MAX_PATHS, P8_PER_CU, 16u * stride, 7, 8, true, 2.0, 0.3,
+            [=, &V](uint32_t blocks, const RenderView &R, const dev::PtParams &P, float4 *records, uint32_t slot_base, uint32_t n_slots) {
+                dev::WfView W{};
+                W.r0 = records; W.stride = stride; W.n_slots = n_slots; W.slot_base = slot_base;
+                const dim3 grid(blocks), block(P8_THREADS);
+                if (count) {
+                    if (feat == WF_FEAT_HW7) hipLaunchKernelGGL((dev::pt_persistent_kernel<true, WF_FEAT_HW7>), grid, block, 0, stream, V, R, W, P);
+                    else if (feat == WF_FEAT_ENV) hipLaunchKernelGGL((dev::pt_persistent_kernel<true, WF_FEAT_ENV>), grid, block, 0, stream, V, R, W, P);
+                    else hipLaunchKernelGGL((dev::pt_persistent_kernel<true, 0>), grid, block, 0, stream, V, R, W, P);
+                } else {
+                    if (feat == WF_FEAT_HW7) hipLaunchKernelGGL((dev::pt_persistent_kernel<false, WF_FEAT_HW7>), grid, block, 0, stream, V, R, W, P);
+                    else if (feat == WF_FEAT_ENV) hipLaunchKernelGGL((dev::pt_persistent_kernel<false, WF_FEAT_ENV>), grid, block, 0, stream, V, R, W, P);
+                    else hipLaunchKernelGGL((dev::pt_persistent_kernel<false, 0>), grid, block, 0, stream, V, R, W, P);
+                }
+            }};
+}
+
+static PersistentKernel hw6_persistent(const SceneView6 &V, hipStream_t stream, bool count) {
+    return {P6_MAX_PATHS, P6_PER_CU, (size_t)P6_REC * sizeof(float4), 1, 1, false, 1.5, 0.4, // the record holds the path's frames
+            [=, &V](uint32_t blocks, const RenderView &R, const dev::PtParams &P, float4 *records, uint32_t slot_base, uint32_t) {
+                const dev::W6View W{records, slot_base};
+                if (count) hipLaunchKernelGGL(dev::p6_persistent_kernel<true>, dim3(blocks), dim3(P6_THREADS), 0, stream, V, R, W, P);
+                else hipLaunchKernelGGL(dev::p6_persistent_kernel<false>, dim3(blocks), dim3(P6_THREADS), 0, stream, V, R, W, P);
+            }};
+}
+
+static void launch_persistent(rt_scene *scene, const PersistentKernel &k, const RenderView &R, uint32_t n_work, hipStream_t stream, bool count, bool time_trace) {
     auto env_int = [](const char *n, int dflt) { const char *e = getenv(n); return e && atoi(e) > 0 ? atoi(e) : dflt; };
-    uint32_t n_blocks_max = (uint32_t)env_int("RTAMD_PT_BLOCKS", scene->n_cus * P8_PER_CU); // five 4-wave workgroups per CU (their LDS fills the CU)
-    const uint64_t pass_cap = (uint64_t)n_blocks_max * (PT_MAX_PATHS / 64);
+    const uint32_t n_blocks_max = (uint32_t)env_int("RTAMD_PT_BLOCKS", scene->n_cus * k.per_cu); // five 4-wave workgroups per CU (their LDS fills the CU)
+    const uint64_t pass_cap = (uint64_t)n_blocks_max * (k.max_paths / 64);
     const uint32_t passes = (uint32_t)((n_work + pass_cap - 1) / pass_cap);
     const uint32_t pass_groups = (n_work + passes - 1) / passes;         // 8x8 sub-tiles (64 path slots) per pass
     // The unit of the deal: an 8x8 sub-tile, or — when a workgroup would hold fewer than sixteen of those (small frames, shards) — a
@@ -853,13 +895,13 @@ static void launch_persistent(rt_scene *scene, const SceneView &V, const RenderV
     // is a few heavy pixels is bound by their serial samples.
     uint32_t group_shift = (uint64_t)pass_groups < 16ull * n_blocks_max ? 4u : 6u;
     if (const char *e = getenv("RTAMD_PT_GROUP_SHIFT")) { const int v = atoi(e); if (v == 4 || v == 5 || v == 6) group_shift = (uint32_t)v; }
-    const uint32_t sub = 6u - group_shift, groups_per_block = PT_MAX_PATHS >> group_shift;
-    const size_t n_slots = (size_t)pass_groups * 64;
-    if (scene->pt_slots < n_slots || scene->pt_levels < (size_t)R.ray_depth) {
-        if (scene->pt_r0) (void)hipFree(scene->pt_r0);
-        scene->pt_r0 = nullptr; scene->pt_slots = scene->pt_levels = 0;
-        HIP_CHECK(hipMalloc((void **)&scene->pt_r0, n_slots * (16 * WF_REC_BASE + 32 * (size_t)R.ray_depth)));
-        scene->pt_slots = n_slots; scene->pt_levels = (size_t)R.ray_depth;
+    const uint32_t sub = 6u - group_shift, groups_per_block = k.max_paths >> group_shift;
+    const size_t record_bytes = (size_t)pass_groups * 64 * k.record_bytes;
+    if (scene->pt_record_bytes < record_bytes) {
+        if (scene->pt_records) (void)hipFree(scene->pt_records);
+        scene->pt_records = nullptr; scene->pt_record_bytes = 0;
+        HIP_CHECK(hipMalloc(&scene->pt_records, record_bytes));
+        scene->pt_record_bytes = record_bytes;
     }
     const size_t group_words = 2 * ((size_t)pass_groups << sub) + n_blocks_max + 1;
     if (scene->pt_group_words < group_words) {
@@ -876,9 +918,11 @@ static void launch_persistent(rt_scene *scene, const SceneView &V, const RenderV
     P.shade_min = 0; // set per pass below
     P.shade_thr0 = env_int("RTAMD_PT_SHADE_THR0", 128);
     P.shade_thr_step = env_int("RTAMD_PT_SHADE_STEP", 512);
-    P.cost_t = 7; P.cost_l = 8;
-    if (const char *e = getenv("RTAMD_WF_SPLIT")) { int a = 0, b = 0; if (sscanf(e, "%d:%d", &a, &b) == 2 && a > 0 && b > 0 && a < 256 && b < 256) { P.cost_t = a; P.cost_l = b; } }
-    P.prio = getenv("RTAMD_PT_PRIO") ? atoi(getenv("RTAMD_PT_PRIO")) : 0;
+    P.cost_t = k.cost_t; P.cost_l = k.cost_l;
+    if (k.hw8_knobs) {
+        if (const char *e = getenv("RTAMD_WF_SPLIT")) { int a = 0, b = 0; if (sscanf(e, "%d:%d", &a, &b) == 2 && a > 0 && b > 0 && a < 256 && b < 256) { P.cost_t = a; P.cost_l = b; } }
+        P.prio = getenv("RTAMD_PT_PRIO") ? atoi(getenv("RTAMD_PT_PRIO")) : 0;
+    }
     P.counters = scene->d_counters;
     // A wave still in the launch after this long gives up (the kernel cannot hang the GPU): RTAMD_PT_TIMEOUT_S, by default ten minutes or
     // — for long renders: 4K at thousands of samples — the time the launch would take at a twentieth of the usual rate, whichever is more.
@@ -888,36 +932,29 @@ static void launch_persistent(rt_scene *scene, const SceneView &V, const RenderV
         P.deadline_ticks = (unsigned long long)(deadline_s * 1e8);
     }
     // every workgroup leaves its start and exit time (the re-deal measures the workgroups' speeds with them)
-    P.debug = nullptr;
     if (!scene->d_pt_debug) HIP_CHECK(hipMalloc((void **)&scene->d_pt_debug, (size_t)PT_DEBUG_BLOCKS * 3 * sizeof(unsigned long long)));
     if (n_blocks_max <= PT_DEBUG_BLOCKS) P.debug = scene->d_pt_debug;
     float4 *d_trace = nullptr;
     const uint32_t trace_cap = 1u << 16;
-    if (count && getenv("RTAMD_TRACE_PIXEL") && getenv("RTAMD_TRACE_OUT")) { // diagnostic: tests/diagnostics/trace_pixel.py
+    if (k.hw8_knobs && count && getenv("RTAMD_TRACE_PIXEL") && getenv("RTAMD_TRACE_OUT")) { // diagnostic: tests/diagnostics/trace_pixel.py
         int tx = 0, ty = 0;
         if (sscanf(getenv("RTAMD_TRACE_PIXEL"), "%d,%d", &tx, &ty) == 2) {
             HIP_CHECK(hipMalloc((void **)&d_trace, (size_t)trace_cap * sizeof(float4)));
             HIP_CHECK(hipMemsetAsync(d_trace, 0, sizeof(float4), stream));
             P.trace_buf = d_trace; P.trace_cap = trace_cap; P.trace_pixel = ty * R.width + tx;
         }
-
     }
     // two phases when there is something to re-deal: enough samples, and several sub-tiles per workgroup
     const int phase0 = getenv("RTAMD_PT_PHASE0") ? atoi(getenv("RTAMD_PT_PHASE0")) : R.samples / 16;
     const bool two_phase = !getenv("RTAMD_PT_NO_REBALANCE") && phase0 >= 1 && phase0 < R.samples && ((uint64_t)pass_groups << sub) >= 4ull * n_blocks_max;
-    const std::vector<int> stops = phase_stops(two_phase, phase0, R.samples, 2, group_shift < 6u);
+    const std::vector<int> stops = phase_stops(two_phase, phase0, R.samples, group_shift < 6u);
     const uint32_t phases = (uint32_t)stops.size();
     if (time_trace) while (scene->ev_pool.size() < 2 * (size_t)passes * phases) { hipEvent_t e; HIP_CHECK(hipEventCreate(&e)); scene->ev_pool.push_back(e); }
-    dev::WfView W{};
-    W.r0 = scene->pt_r0;
-    W.stride = (uint32_t)WF_REC_BASE + 2u * (uint32_t)scene->pt_levels;
     uint32_t first = 0, launch = 0;
     scene->pt_blocks = 0; scene->pt_rebalance_ms = 0; scene->pt_imbalance = 0;
     std::vector<uint32_t> owner; // sub-tile -> workgroup of the phase in flight
     for (uint32_t p = 0; p < passes; p++) {
         const uint32_t groups = n_work - first < pass_groups ? n_work - first : pass_groups;
-        W.n_slots = groups * 64u;
-        W.slot_base = first * 64u;
         const uint32_t n_units = groups << sub;   // groups of the deal
         P.n_groups = n_units; P.group_shift = group_shift;
         const uint32_t blocks = n_units < n_blocks_max ? n_units : n_blocks_max;
@@ -934,22 +971,10 @@ static void launch_persistent(rt_scene *scene, const SceneView &V, const RenderV
             P.group_ids = ph ? d_ids : nullptr;
             P.front_first = ph && !getenv("RTAMD_PT_NO_FRONT_FIRST") ? 1u : 0u;
             if (ph == 0) owner.clear(); // the kernel's round-robin deal
-            if (ph >= 1) redeal_groups(scene, d_cost, d_ofs, d_ids, n_units, blocks, groups_per_block, stream, P.debug, &owner);
+            if (ph >= 1) redeal_groups(scene, d_cost, d_ofs, d_ids, n_units, blocks, groups_per_block, k.gamma_round, k.gamma_own, stream, P.debug, &owner);
             if (P.debug) HIP_CHECK(hipMemsetAsync(scene->d_pt_debug, 0, (size_t)PT_DEBUG_BLOCKS * 3 * sizeof(unsigned long long), stream));
             if (time_trace) HIP_CHECK(hipEventRecord(scene->ev_pool[2 * launch], stream));
-            // kernel variant by the features this render can reach (fewer features, fewer spilled registers): the hw7 integrator has no
-            // environment map; an hw8 render needs the environment lookup only when the scene has a map
-            const int feat = V.hw7 ? WF_FEAT_HW7 : (V.env_image >= 0 ? WF_FEAT_ENV : 0);
-            const dim3 grid(blocks), block(P8_THREADS);
-            if (count) {
-                if (feat == WF_FEAT_HW7) hipLaunchKernelGGL((dev::pt_persistent_kernel<true, WF_FEAT_HW7>), grid, block, 0, stream, V, Rp, W, P);
-                else if (feat == WF_FEAT_ENV) hipLaunchKernelGGL((dev::pt_persistent_kernel<true, WF_FEAT_ENV>), grid, block, 0, stream, V, Rp, W, P);
-                else hipLaunchKernelGGL((dev::pt_persistent_kernel<true, 0>), grid, block, 0, stream, V, Rp, W, P);
-            } else {
-                if (feat == WF_FEAT_HW7) hipLaunchKernelGGL((dev::pt_persistent_kernel<false, WF_FEAT_HW7>), grid, block, 0, stream, V, Rp, W, P);
-                else if (feat == WF_FEAT_ENV) hipLaunchKernelGGL((dev::pt_persistent_kernel<false, WF_FEAT_ENV>), grid, block, 0, stream, V, Rp, W, P);
-                else hipLaunchKernelGGL((dev::pt_persistent_kernel<false, 0>), grid, block, 0, stream, V, Rp, W, P);
-            }
+            k.launch(blocks, Rp, P, (float4 *)scene->pt_records, first * 64u, groups * 64u);
             if (time_trace) HIP_CHECK(hipEventRecord(scene->ev_pool[2 * launch + 1], stream));
             launch++;
         }
@@ -967,97 +992,101 @@ static void launch_persistent(rt_scene *scene, const SceneView &V, const RenderV
     }
 }
 
-// hw6 in the persistent organisation (device/rt_persistent_hw6.h): passes of up to n_cus x P6_MAX_PATHS path slots, each rendered in
-// two phases with a re-deal of the sub-tiles in between like launch_persistent — here the cost of a pixel spans 1 to 63 walks per
-// sample (a wall against the glass bunny), so the deal matters far more than for hw8.
-static void launch_persistent6(rt_scene *scene, const SceneView6 &V, const RenderView &R, uint32_t n_work, hipStream_t stream, bool count, bool time_trace) {
-    auto env_int = [](const char *n, int dflt) { const char *e = getenv(n); return e && atoi(e) > 0 ? atoi(e) : dflt; };
-    const uint32_t n_blocks_max = (uint32_t)env_int("RTAMD_PT_BLOCKS", scene->n_cus * P6_PER_CU); // five 4-wave workgroups per CU
-    const uint64_t pass_cap = (uint64_t)n_blocks_max * (P6_MAX_PATHS / 64);
-    const uint32_t passes = (uint32_t)((n_work + pass_cap - 1) / pass_cap);
-    const uint32_t pass_groups = (n_work + passes - 1) / passes;         // 8x8 sub-tiles (64 path slots) per pass
-    // The unit of the deal: an 8x8 sub-tile, or — when a workgroup would hold fewer than sixteen of those (small frames, shards) — a
-    // quarter of one (two pixel rows): a single heavy sub-tile must not outweigh a workgroup's fair share, and a workgroup whose load
-    // is a few heavy pixels is bound by their serial samples.
-    uint32_t group_shift = (uint64_t)pass_groups < 16ull * n_blocks_max ? 4u : 6u;
-    if (const char *e = getenv("RTAMD_PT_GROUP_SHIFT")) { const int v = atoi(e); if (v == 4 || v == 5 || v == 6) group_shift = (uint32_t)v; }
-    const uint32_t sub = 6u - group_shift, groups_per_block = P6_MAX_PATHS >> group_shift;
-    const size_t n_slots = (size_t)pass_groups * 64;
-    if (scene->pt6_slots < n_slots) {
-        if (scene->pt6_r0) (void)hipFree(scene->pt6_r0);
-        scene->pt6_r0 = nullptr; scene->pt6_slots = 0;
-        HIP_CHECK(hipMalloc((void **)&scene->pt6_r0, n_slots * (size_t)P6_REC * sizeof(float4)));
-        scene->pt6_slots = n_slots;
+// The kernels that render a frame.  hw8 / hw7: the persistent dataflow pipeline, the round pipeline or the megakernel; hw6: its own
+// persistent pipeline or its per-lane path machine; hw1..hw5: one kernel each.
+enum class Pipeline { Persistent8, Persistent6, Rounds, Mega6, Mega8, Hw1, Hw2, Hw3, Hw4, Hw5 };
+
+// hw8 / hw7: persistent dataflow pipeline (default) | round pipeline (RTAMD_KERNEL=wavefront, and for trees deeper than the LDS stack
+// columns) | megakernel (RTAMD_KERNEL=mega, and for trees deeper than the round kernels' stacks).
+// The persistent pipeline is the default at every size: it takes reference-exact box decisions at no measurable cost for the exact
+// walks themselves (they hide behind the other waves of the workgroup), keeps a small path population — a shard of a multi-GPU
+// frame — near the full rate, and since round 3 (five waves per SIMD, four-wide grid nodes, postponed leaves) it is a third faster
+// than the round pipeline on a full 1080p frame.  The round pipeline stands in for trees deeper than the LDS stack columns, then with
+// its exact kernels on (a serial walk of the reference tree, ~1.5 ms, sits on the critical path of every round); chosen explicitly
+// (RTAMD_KERNEL=wavefront, reported in `rounds_chosen`) it keeps the padded box test's answer unless RTAMD_ROUNDS_EXACT=1.
+// RTAMD_AUTO_GROUPS_PER_CU=n: opt into the round pipeline from n sub-tiles per CU on.  RTAMD_WF_LDS_STACK (testing) takes the round
+// pipeline's spill variant.
+// hw6: the persistent pipeline (device/rt_persistent_hw6.h) when both own trees fit its stack columns; RTAMD_KERNEL=mega and
+// RTAMD_HW6_SCRATCH_STACK keep the per-lane path machine.
+static Pipeline choose_pipeline(const rt_scene *scene, int integrator, const RenderView &R, uint32_t n_work, int streams, bool &rounds_chosen) {
+    const char *ksel = getenv("RTAMD_KERNEL");
+    const bool mega = ksel && strcmp(ksel, "mega") == 0;
+    rounds_chosen = ksel && strcmp(ksel, "wavefront") == 0;
+    switch (integrator) { // the .txt scenes' integrators
+    case RT_INTEGRATOR_HW1: return Pipeline::Hw1;
+    case RT_INTEGRATOR_HW2: return Pipeline::Hw2;
+    case RT_INTEGRATOR_HW3: return Pipeline::Hw3;
+    case RT_INTEGRATOR_HW4: return Pipeline::Hw4;
+    case RT_INTEGRATOR_HW5: return Pipeline::Hw5;
     }
-    const size_t group_words = 2 * ((size_t)pass_groups << sub) + n_blocks_max + 1;
-    if (scene->pt_group_words < group_words) {
-        if (scene->pt_groups) (void)hipFree(scene->pt_groups);
-        scene->pt_groups = nullptr; scene->pt_group_words = 0;
-        HIP_CHECK(hipMalloc((void **)&scene->pt_groups, group_words * 4));
-        scene->pt_group_words = group_words;
-    }
-    uint32_t *d_cost = scene->pt_groups, *d_ofs = d_cost + ((size_t)pass_groups << sub), *d_ids = d_ofs + n_blocks_max + 1;
-    dev::PtParams P{};
-    const int leaf_share = env_int("RTAMD_WF_LEAF_SHARE_256", 112) & 0x7fff;
-    P.refill = env_int("RTAMD_TRACE_REFILL", WF_REFILL) | (env_int("RTAMD_LIGHT_REFILL", env_int("RTAMD_TRACE_REFILL", WF_REFILL)) << 16);
-    P.leaf_batch = (env_int("RTAMD_TRACE_LEAF_BATCH", 28) & 255) | (leaf_share << 16); // lanes that hold two leaves (or have nothing else left) before a leaf phase starts
-    P.shade_min = 0; // set per pass below
-    P.shade_thr0 = env_int("RTAMD_PT_SHADE_THR0", 128);
-    P.shade_thr_step = env_int("RTAMD_PT_SHADE_STEP", 512);
-    P.cost_t = 1; P.cost_l = 1;
-    P.counters = scene->d_counters;
-    // A wave still in the launch after this long gives up (the kernel cannot hang the GPU): RTAMD_PT_TIMEOUT_S, by default ten minutes or
-    // — for long renders: 4K at thousands of samples — the time the launch would take at a twentieth of the usual rate, whichever is more.
-    {
-        const double expected_s = (double)n_work * 64.0 * (double)R.samples / 15e6;
-        const double deadline_s = getenv("RTAMD_PT_TIMEOUT_S") ? (double)env_int("RTAMD_PT_TIMEOUT_S", 600) : (expected_s > 600.0 ? expected_s : 600.0);
-        P.deadline_ticks = (unsigned long long)(deadline_s * 1e8);
-    }
-    // every workgroup leaves its start and exit time (the re-deal measures the workgroups' speeds with them)
-    if (!scene->d_pt_debug) HIP_CHECK(hipMalloc((void **)&scene->d_pt_debug, (size_t)PT_DEBUG_BLOCKS * 3 * sizeof(unsigned long long)));
-    if (n_blocks_max <= PT_DEBUG_BLOCKS) P.debug = scene->d_pt_debug;
-    const int phase0 = getenv("RTAMD_PT_PHASE0") ? atoi(getenv("RTAMD_PT_PHASE0")) : R.samples / 16;
-    const bool two_phase = !getenv("RTAMD_PT_NO_REBALANCE") && phase0 >= 1 && phase0 < R.samples && ((uint64_t)pass_groups << sub) >= 4ull * n_blocks_max;
-    const std::vector<int> stops = phase_stops(two_phase, phase0, R.samples, 2, group_shift < 6u);
-    const uint32_t phases = (uint32_t)stops.size();
-    if (time_trace) while (scene->ev_pool.size() < 2 * (size_t)passes * phases) { hipEvent_t e; HIP_CHECK(hipEventCreate(&e)); scene->ev_pool.push_back(e); }
-    dev::W6View W{};
-    W.r0 = scene->pt6_r0;
-    uint32_t first = 0, launch = 0;
-    scene->pt_rebalance_ms = 0; scene->pt_imbalance = 0; scene->pt_blocks = 0;
-    std::vector<uint32_t> owner; // sub-tile -> workgroup of the phase in flight
-    for (uint32_t p = 0; p < passes; p++) {
-        const uint32_t groups = n_work - first < pass_groups ? n_work - first : pass_groups;
-        W.slot_base = first * 64u;
-        const uint32_t n_units = groups << sub;   // groups of the deal
-        P.n_groups = n_units; P.group_shift = group_shift;
-        const uint32_t blocks = n_units < n_blocks_max ? n_units : n_blocks_max;
-        if (blocks > scene->pt_blocks) scene->pt_blocks = blocks;
-        // a wave turns shader when this many paths wait: a pool of a few hundred paths cannot let its paths wait for a full wave of them
-        // (measured: 1,620 paths per workgroup 32 > 64 > 16; 820 and 200 paths per workgroup 16 > 32 > 64)
-        P.shade_min = env_int("RTAMD_PT_SHADE_MIN", ((uint64_t)groups * 64u) / blocks >= 1536u ? 32 : 16);
-        for (uint32_t ph = 0; ph < phases; ph++) {
-            RenderView Rp = R;
-            Rp.sample_stop = stops[ph];
-            P.resume = ph ? 1u : 0u;
-            P.group_cost = ph + 1 < phases ? d_cost : nullptr;   // every phase but the last measures for the next re-deal
-            P.group_ofs = ph ? d_ofs : nullptr;
-            P.group_ids = ph ? d_ids : nullptr;
-            P.front_first = ph && !getenv("RTAMD_PT_NO_FRONT_FIRST") ? 1u : 0u;
-            if (ph == 0) owner.clear(); // the kernel's round-robin deal
-            if (ph >= 1) redeal_groups(scene, d_cost, d_ofs, d_ids, n_units, blocks, groups_per_block, stream, P.debug, &owner);
-            if (P.debug) HIP_CHECK(hipMemsetAsync(scene->d_pt_debug, 0, (size_t)PT_DEBUG_BLOCKS * 3 * sizeof(unsigned long long), stream));
-            if (time_trace) HIP_CHECK(hipEventRecord(scene->ev_pool[2 * launch], stream));
-            if (count) hipLaunchKernelGGL(dev::p6_persistent_kernel<true>, dim3(blocks), dim3(P6_THREADS), 0, stream, V, Rp, W, P);
-            else hipLaunchKernelGGL(dev::p6_persistent_kernel<false>, dim3(blocks), dim3(P6_THREADS), 0, stream, V, Rp, W, P);
-            if (time_trace) HIP_CHECK(hipEventRecord(scene->ev_pool[2 * launch + 1], stream));
-            launch++;
+    if (scene->flavor == RT_INTEGRATOR_HW6)
+        return scene->hw6_pt_stack && !mega && !getenv("RTAMD_HW6_SCRATCH_STACK") ? Pipeline::Persistent6 : Pipeline::Mega6;
+    const rt_scene_info &I = scene->info;
+    if (mega || I.bvh_depth > WF_STACK + WF_OVF || I.light_bvh_depth > 64 || I.n_triangles >= 0x40000000u // light depth: 64-bit frame mask
+        || R.samples / streams >= (1 << 25)) // the path record keeps the sample index in 25 bits
+        return Pipeline::Mega8;
+    if (rounds_chosen || I.bvh_depth > P8_STACK || scene->light_walk_depth > P8_STACK || getenv("RTAMD_WF_LDS_STACK")) return Pipeline::Rounds;
+    const uint64_t auto_groups = (uint64_t)(getenv("RTAMD_AUTO_GROUPS_PER_CU") ? atoi(getenv("RTAMD_AUTO_GROUPS_PER_CU")) : 0);
+    if (!ksel && auto_groups && (uint64_t)n_work * (uint64_t)streams >= auto_groups * (uint64_t)scene->n_cus) return Pipeline::Rounds;
+    return Pipeline::Persistent8;
+}
+
+// RTAMD_DEBUG_COUNTERS after a persistent render: launches and re-deal, where the waves' time went (counting renders) and when the
+// workgroups of the last launch left; RTAMD_DUMP_WG=file: start / exit time (ms after the first start) and paths of each of them
+// (tools/tuning/wg_balance.py).
+static void report_persistent(rt_scene *scene, bool hw6, const char *kernel, bool count, const unsigned long long *h_cnt) {
+    const bool times = scene->d_pt_debug && scene->pt_blocks <= PT_DEBUG_BLOCKS;
+    if (hw6) {
+        fprintf(stderr, "[rtamd] persistent hw6 pipeline: %u launches; re-deal %.2f ms on the host (slowest workgroup / mean under the round-robin deal: %.3f); light sums through the slow role %llu of %llu; exact closest-hit walks %llu of %llu, exact light sums %llu\n",
+                scene->pt_launches, scene->pt_rebalance_ms, scene->pt_imbalance, h_cnt[13], h_cnt[1], h_cnt[12], h_cnt[0], h_cnt[11]);
+        if (count) {
+            fprintf(stderr, "[rtamd] persistent hw6 kernel, light sums in the slow role by number of hits (0..14, 15+):");
+            for (int b = 0; b < 16; b++) fprintf(stderr, " %llu", h_cnt[32 + b]);
+            fprintf(stderr, "\n");
+            const double tt = (double)(h_cnt[16] + h_cnt[17] + h_cnt[18] + h_cnt[19] + h_cnt[20]);
+            fprintf(stderr, "[rtamd] persistent hw6 kernel, wave time by role: closest-hit walks %.1f %%, light walks %.1f %%, shading %.1f %%, slow light sums %.1f %%, idle %.1f %%\n",
+                    100 * h_cnt[16] / tt, 100 * h_cnt[17] / tt, 100 * h_cnt[18] / tt, 100 * h_cnt[19] / tt, 100 * h_cnt[20] / tt);
         }
-        first += groups;
+    } else if (times && count) {
+        const double tt = (double)(h_cnt[16] + h_cnt[17] + h_cnt[18] + h_cnt[19] + h_cnt[20]);
+        fprintf(stderr, "[rtamd] persistent kernel, wave time by role: closest-hit walks %.1f %%, light walks %.1f %%, shading %.1f %%, exact walks %.2f %%, idle %.1f %%; "
+                        "walker lane utilisation: closest hit %.1f of 64 (%llu wave iterations), light %.1f of 64 (%llu); %llu stints, %llu shade batches of %.1f paths\n",
+                100 * h_cnt[16] / tt, 100 * h_cnt[17] / tt, 100 * h_cnt[18] / tt, 100 * h_cnt[19] / tt, 100 * h_cnt[20] / tt,
+                (double)h_cnt[22] / (double)(h_cnt[21] ? h_cnt[21] : 1), h_cnt[21], (double)h_cnt[24] / (double)(h_cnt[23] ? h_cnt[23] : 1), h_cnt[23],
+                h_cnt[25], h_cnt[26], (double)h_cnt[27] / (double)(h_cnt[26] ? h_cnt[26] : 1));
+        for (int w = 0; w < 2; w++) {
+            const double tw = (double)(h_cnt[48 + 3 * w] + h_cnt[49 + 3 * w] + h_cnt[50 + 3 * w]);
+            fprintf(stderr, "[rtamd]   %s walker's wave time: hand-off and refill %.1f %%, inner nodes %.1f %%, leaves %.1f %%; leaf passes %llu with %.1f of 64 lanes\n",
+                    w ? "light" : "closest-hit", 100 * h_cnt[48 + 3 * w] / tw, 100 * h_cnt[49 + 3 * w] / tw, 100 * h_cnt[50 + 3 * w] / tw,
+                    h_cnt[54 + 2 * w], (double)h_cnt[55 + 2 * w] / (double)(h_cnt[54 + 2 * w] ? h_cnt[54 + 2 * w] : 1));
+        }
+        fprintf(stderr, "[rtamd]   closest-hit walker's hand-off points: %llu; of their time: publishing finished walks %.1f %%, taking new ones from the bitmap %.1f %%, reading their rays %.1f %% (the rest: the test itself)\n",
+                h_cnt[63], 100.0 * h_cnt[60] / (double)(h_cnt[48] ? h_cnt[48] : 1), 100.0 * h_cnt[61] / (double)(h_cnt[48] ? h_cnt[48] : 1), 100.0 * h_cnt[62] / (double)(h_cnt[48] ? h_cnt[48] : 1));
+        fprintf(stderr, "[rtamd]   light tests %llu (%.2f per light sum), hits %llu (%.2f per light sum); triangle tests of closest-hit walks %llu (%.2f per query)\n",
+                h_cnt[59], (double)h_cnt[59] / (double)(h_cnt[1] ? h_cnt[1] : 1), h_cnt[58], (double)h_cnt[58] / (double)(h_cnt[1] ? h_cnt[1] : 1),
+                h_cnt[3] - h_cnt[59], (double)(h_cnt[3] - h_cnt[59]) / (double)(h_cnt[0] ? h_cnt[0] : 1));
+        fprintf(stderr, "[rtamd]   light sums whose walk ends at the light tree's root %llu (%.1f %%), one level below it %llu (%.1f %%); settled by the shader: level %d\n",
+                h_cnt[30], 100.0 * h_cnt[30] / (double)(h_cnt[1] ? h_cnt[1] : 1), h_cnt[31], 100.0 * h_cnt[31] / (double)(h_cnt[1] ? h_cnt[1] : 1), PT_LIGHT_SETTLE);
     }
-    HIP_CHECK(hipGetLastError());
-    scene->pt_passes = passes;
-    scene->pt_launches = launch;
+    if (!times) return;
+    std::vector<unsigned long long> dbg((size_t)scene->pt_blocks * 3);
+    HIP_CHECK(hipMemcpy(dbg.data(), scene->d_pt_debug, dbg.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    unsigned long long t0 = ~0ull, tmin = ~0ull, tmax = 0; double tsum = 0;
+    for (uint32_t b = 0; b < scene->pt_blocks; b++) if (dbg[3 * b] && dbg[3 * b] < t0) t0 = dbg[3 * b];
+    for (uint32_t b = 0; b < scene->pt_blocks; b++) { unsigned long long e = dbg[3 * b + 1] - t0; tmin = e < tmin ? e : tmin; tmax = e > tmax ? e : tmax; tsum += (double)e; }
+    if (const char *dump = getenv("RTAMD_DUMP_WG")) {
+        if (FILE *f = fopen(dump, "w")) {
+            for (uint32_t b = 0; b < scene->pt_blocks; b++) fprintf(f, "%u %.4f %.4f %llu\n", b, (dbg[3 * b] - t0) * 1e-5, (dbg[3 * b + 1] - t0) * 1e-5, dbg[3 * b + 2]);
+            fclose(f);
+        }
+    }
+    if (!hw6)
+        fprintf(stderr, "[rtamd] persistent pipeline: %u launches; re-deal of the sub-tiles took %.2f ms on the host (slowest workgroup / mean under the round-robin deal: %.3f)\n",
+                scene->pt_launches, scene->pt_rebalance_ms, scene->pt_imbalance);
+    fprintf(stderr, "[rtamd] %s (last launch): %u workgroups, exit times min / mean / max = %.3f / %.3f / %.3f ms after the first start",
+            kernel, scene->pt_blocks, tmin * 1e-5, tsum / scene->pt_blocks * 1e-5, tmax * 1e-5);
+    if (!hw6) fprintf(stderr, "; exact closest hits %llu, exact light sums %llu of %llu + %llu queries", h_cnt[12], h_cnt[13], h_cnt[0], h_cnt[1]);
+    fprintf(stderr, "\n");
 }
 
 int rt_render(rt_scene *scene, const rt_render_params *p, float *out_rgb, uint8_t *out_rgb8, rt_stats *stats) {
@@ -1120,46 +1149,9 @@ int rt_render(rt_scene *scene, const rt_render_params *p, float *out_rgb, uint8_
         }
         uint32_t blocks = (uint32_t)scene->n_cus * 16u;
         if (blocks > n_work) blocks = n_work;
-        // Kernel organisation: "wavefront" (default) or the single persistent "megakernel" (RTAMD_KERNEL=mega,
-        // also the fallback when a BVH is deeper than the wavefront kernels' LDS stacks).
-        const char *ksel = getenv("RTAMD_KERNEL");
-        bool use_wavefront = !(ksel && strcmp(ksel, "mega") == 0);
-        if (scene->info.bvh_depth > WF_STACK + WF_OVF || scene->info.light_bvh_depth > 64 || scene->info.n_triangles >= 0x40000000u) use_wavefront = false; // light depth: 64-bit frame mask
-        if (scene->flavor == RT_INTEGRATOR_HW6 || txt_scene) use_wavefront = false;
-        if (R.samples / streams >= (1 << 25)) use_wavefront = false; // the path record keeps the sample index in 25 bits
-        // persistent dataflow pipeline (default) | round pipeline (RTAMD_KERNEL=wavefront, and for trees deeper than the LDS stack columns)
-        // The persistent pipeline is the default at every size: it takes reference-exact box decisions at no measurable cost for the exact
-        // walks themselves (they hide behind the other waves of the workgroup), keeps a small path population — a shard of a multi-GPU
-        // frame — near the full rate, and since round 3 (five waves per SIMD, four-wide grid nodes, postponed leaves) it is a third faster
-        // than the round pipeline on a full 1080p frame.  The round pipeline stands in for trees deeper than the LDS stack columns, then with
-        // its exact kernels on (a serial walk of the reference tree, ~1.5 ms, sits on the critical path of every round); chosen explicitly
-        // (RTAMD_KERNEL=wavefront) it keeps the padded box test's answer unless RTAMD_ROUNDS_EXACT=1.  RTAMD_AUTO_GROUPS_PER_CU=n: opt
-        // into the round pipeline from n sub-tiles per CU on.
-        bool use_persistent = use_wavefront && !(ksel && strcmp(ksel, "wavefront") == 0) &&
-                              scene->info.bvh_depth <= P8_STACK && scene->light_walk_depth <= P8_STACK && !getenv("RTAMD_WF_LDS_STACK");
-        if (use_persistent && !ksel) {
-            const uint64_t auto_groups = (uint64_t)(getenv("RTAMD_AUTO_GROUPS_PER_CU") ? atoi(getenv("RTAMD_AUTO_GROUPS_PER_CU")) : 0);
-            if (auto_groups && (uint64_t)n_work * (uint64_t)streams >= auto_groups * (uint64_t)scene->n_cus) use_persistent = false;
-        }
-        const bool hw6_persistent = scene->flavor == RT_INTEGRATOR_HW6 && scene->hw6_pt_stack && !(ksel && strcmp(ksel, "mega") == 0) && !getenv("RTAMD_HW6_SCRATCH_STACK");
-        if (streams > 1 && !use_wavefront && !hw6_persistent) return fail(RT_ERR_UNSUPPORTED, "rt_render: sample_streams > 1 needs the persistent / round kernels (RTAMD_KERNEL=mega or a tree beyond their limits is in effect)");
-        // throughput mode (include/rtamd.h: sample_streams): K path slots per pixel, `samples` per stream, a partial-sum buffer and a final reduction
-        auto setup_streams = [&]() {
-            R.streams = streams; R.n_pixslots = n_work * 64u; R.seed_stride = (uint32_t)R.width * (uint32_t)R.height;
-            R.total_samples = (uint32_t)R.samples;
-            R.sample_seeds = (p->flags & RT_FLAG_SAMPLE_SEEDS) ? 1u : 0u;
-            R.rr_depth = (p->flags & RT_FLAG_RUSSIAN_ROULETTE) ? 2 : 0;
-            R.samples /= streams;                           // per stream; inv_samples stays 1 / (all samples of the pixel)
-            R.sample_stop = R.samples;
-            const size_t need = (size_t)streams * R.n_pixslots * 3 * sizeof(float);
-            if (scene->partial_bytes < need) {
-                if (scene->d_partial) (void)hipFree(scene->d_partial);
-                scene->d_partial = nullptr; scene->partial_bytes = 0;
-                HIP_CHECK(hipMalloc((void **)&scene->d_partial, need));
-                scene->partial_bytes = need;
-            }
-            R.partial = scene->d_partial;
-        };
+        bool rounds_chosen = false;
+        const Pipeline pipe = choose_pipeline(scene, p->integrator, R, n_work, streams, rounds_chosen);
+        if (streams > 1 && pipe != Pipeline::Persistent8 && pipe != Pipeline::Rounds && pipe != Pipeline::Persistent6) return fail(RT_ERR_UNSUPPORTED, "rt_render: sample_streams > 1 needs the persistent / round kernels (RTAMD_KERNEL=mega or a tree beyond their limits is in effect)");
         if (txt_scene && p->integrator == RT_INTEGRATOR_HW3 && R.ray_depth > RT3_MAX_DEPTH) return fail(RT_ERR_LIMIT, "rt_render: hw3 ray_depth above 8");
         if (txt_scene && scene->txt_has_triangles && p->integrator != RT_INTEGRATOR_HW5) return fail(RT_ERR_INVALID_ARG, "rt_render: a .txt scene with TRIANGLE figures renders with RT_INTEGRATOR_HW5 only");
         if (p->integrator == RT_INTEGRATOR_HW5 && R.ray_depth > RT4_MAX_DEPTH) return fail(RT_ERR_LIMIT, "rt_render: hw5 ray_depth above 8");
@@ -1177,73 +1169,67 @@ int rt_render(rt_scene *scene, const rt_render_params *p, float *out_rgb, uint8_
         // stack columns), the round pipeline runs with its exact kernels on.  Only an explicit RTAMD_KERNEL=wavefront (the yardstick
         // of the benchmarks; RTAMD_ROUNDS_EXACT=1 switches the exact kernels on there too) and the megakernel, which has no gate,
         // keep the padded boxes' answer — and say so in rt_stats.reference_exact.
-        const bool rounds_chosen = ksel && strcmp(ksel, "wavefront") == 0;
-        if (!use_persistent && (!use_wavefront || (rounds_chosen && !getenv("RTAMD_ROUNDS_EXACT")))) V8.exact_boxes = 0;
+        if (pipe != Pipeline::Persistent8 && (pipe != Pipeline::Rounds || (rounds_chosen && !getenv("RTAMD_ROUNDS_EXACT")))) V8.exact_boxes = 0;
         if (!V8.exact_boxes) V8.cull_k = 4.8e-7f; // no exact walks to feed: the walkers look behind the best hit by the tie tolerance only
         uint32_t launches = 0;
-        bool time_trace = false, use_persistent6 = false;
+        bool time_trace = false;
         HIP_CHECK(hipEventRecord(scene->ev_start, stream));
         if (blocks) {
-            if (use_wavefront) {
-                if (streams > 1) setup_streams();
-                // every traverse launch is bracketed by events when stats are wanted -- up to 64 k rounds (e.g. 10,922 spp at depth 6)
-                if (use_persistent) {
-                    time_trace = stats != nullptr;
-                    launch_persistent(scene, V8, R, n_work * (uint32_t)streams, stream, count, time_trace);
-                    launches = scene->pt_launches;
-                } else {
-                time_trace = stats != nullptr && wavefront_rounds(V8, R) * (size_t)wavefront_pipelines(n_work * (uint32_t)streams) <= 65536;
-                launch_wavefront(scene, V8, R, n_work * (uint32_t)streams, stream, count, time_trace);
-                launches = (uint32_t)scene->wf_pipes * (1 + 2 * (uint32_t)wavefront_rounds(V8, R));
+            if (streams > 1) { // throughput mode (include/rtamd.h: sample_streams): K path slots per pixel, `samples` per stream, a partial-sum buffer and a final reduction
+                R.streams = streams; R.n_pixslots = n_work * 64u; R.seed_stride = (uint32_t)R.width * (uint32_t)R.height;
+                R.total_samples = (uint32_t)R.samples;
+                R.sample_seeds = (p->flags & RT_FLAG_SAMPLE_SEEDS) ? 1u : 0u;
+                R.rr_depth = (p->flags & RT_FLAG_RUSSIAN_ROULETTE) ? 2 : 0;
+                R.samples /= streams;                           // per stream; inv_samples stays 1 / (all samples of the pixel)
+                R.sample_stop = R.samples;
+                const size_t need = (size_t)streams * R.n_pixslots * 3 * sizeof(float);
+                if (scene->partial_bytes < need) {
+                    if (scene->d_partial) (void)hipFree(scene->d_partial);
+                    scene->d_partial = nullptr; scene->partial_bytes = 0;
+                    HIP_CHECK(hipMalloc((void **)&scene->d_partial, need));
+                    scene->partial_bytes = need;
                 }
-                if (streams > 1) {
-                    hipLaunchKernelGGL(dev::wf_reduce_streams_kernel, dim3((R.n_pixslots + 255u) / 256u), dim3(256), 0, stream, R);
-                    HIP_CHECK(hipGetLastError());
-                    launches++;
-                }
-            } else if (p->integrator == RT_INTEGRATOR_HW1) {
-                uint32_t npx = (uint32_t)R.width * (uint32_t)R.height;
-                hipLaunchKernelGGL(dev::render_hw1_kernel, dim3((npx + 255) / 256), dim3(256), 0, stream, scene->viewt, R.width, R.height, txt_tan_fov_y, d_rgb, d_rgb8);
-                HIP_CHECK(hipGetLastError());
-                launches = 1;
-            } else if (p->integrator == RT_INTEGRATOR_HW5) {
-                hipLaunchKernelGGL(dev::render_hw5_kernel, dim3(blocks), dim3(64), 0, stream, scene->view5, R, txt_tan_fov_y, n_work);
-                HIP_CHECK(hipGetLastError());
-                launches = 1;
-            } else if (p->integrator == RT_INTEGRATOR_HW4) {
-                hipLaunchKernelGGL(dev::render_hw4_kernel, dim3(blocks), dim3(64), 0, stream, scene->viewt, R, txt_tan_fov_y, n_work);
-                HIP_CHECK(hipGetLastError());
-                launches = 1;
-            } else if (p->integrator == RT_INTEGRATOR_HW2) {
-                hipLaunchKernelGGL(dev::render_hw2_kernel, dim3(blocks), dim3(64), 0, stream, scene->viewt, R, txt_tan_fov_y, n_work);
-                HIP_CHECK(hipGetLastError());
-                launches = 1;
-            } else if (txt_scene) {
-                hipLaunchKernelGGL(dev::render_hw3_kernel, dim3(blocks), dim3(64), 0, stream, scene->viewt, R, txt_tan_fov_y, n_work);
-                HIP_CHECK(hipGetLastError());
-                launches = 1;
-            } else if (hw6_persistent) {
-                // persistent dataflow organisation (device/rt_persistent_hw6.h); RTAMD_KERNEL=mega keeps the per-lane path machine
-                use_persistent6 = true;
+                R.partial = scene->d_partial;
+            }
+            const uint32_t n_slot_groups = n_work * (uint32_t)streams; // 64-slot groups of all streams
+            launches = 1;
+            switch (pipe) {
+            case Pipeline::Persistent8:
+            case Pipeline::Persistent6:
                 time_trace = stats != nullptr;
-                if (streams > 1) setup_streams();
-                launch_persistent6(scene, scene->view6, R, n_work * (uint32_t)streams, stream, count, time_trace);
+                launch_persistent(scene, pipe == Pipeline::Persistent8 ? hw8_persistent(V8, R.ray_depth, stream, count) : hw6_persistent(scene->view6, stream, count),
+                                  R, n_slot_groups, stream, count, time_trace);
                 launches = scene->pt_launches;
-                if (streams > 1) {
-                    hipLaunchKernelGGL(dev::wf_reduce_streams_kernel, dim3((R.n_pixslots + 255u) / 256u), dim3(256), 0, stream, R);
-                    HIP_CHECK(hipGetLastError());
-                    launches++;
-                }
-            } else if (scene->flavor == RT_INTEGRATOR_HW6) {
+                break;
+            case Pipeline::Rounds:
+                // every traverse launch is bracketed by events when stats are wanted -- up to 64 k rounds (e.g. 10,922 spp at depth 6)
+                time_trace = stats != nullptr && wavefront_rounds(V8, R) * (size_t)wavefront_pipelines(n_slot_groups) <= 65536;
+                launch_wavefront(scene, V8, R, n_slot_groups, stream, count, time_trace);
+                launches = (uint32_t)scene->wf_pipes * (1 + 2 * (uint32_t)wavefront_rounds(V8, R));
+                break;
+            case Pipeline::Mega6:
                 if (scene->hw6_lds_stack && !getenv("RTAMD_HW6_SCRATCH_STACK")) hipLaunchKernelGGL(dev::render_hw6_kernel<true>, dim3(blocks), dim3(64), 0, stream, scene->view6, R, n_work);
                 else hipLaunchKernelGGL(dev::render_hw6_kernel<false>, dim3(blocks), dim3(64), 0, stream, scene->view6, R, n_work);
-                HIP_CHECK(hipGetLastError());
-                launches = 1;
-            } else {
+                break;
+            case Pipeline::Mega8:
                 if (count) hipLaunchKernelGGL(dev::render_hw8_kernel<true>, dim3(blocks), dim3(64), 0, stream, V8, R, n_work);
                 else hipLaunchKernelGGL(dev::render_hw8_kernel<false>, dim3(blocks), dim3(64), 0, stream, V8, R, n_work);
+                break;
+            case Pipeline::Hw1: {
+                uint32_t npx = (uint32_t)R.width * (uint32_t)R.height;
+                hipLaunchKernelGGL(dev::render_hw1_kernel, dim3((npx + 255) / 256), dim3(256), 0, stream, scene->viewt, R.width, R.height, txt_tan_fov_y, d_rgb, d_rgb8);
+                break;
+            }
+            case Pipeline::Hw2: hipLaunchKernelGGL(dev::render_hw2_kernel, dim3(blocks), dim3(64), 0, stream, scene->viewt, R, txt_tan_fov_y, n_work); break;
+            case Pipeline::Hw3: hipLaunchKernelGGL(dev::render_hw3_kernel, dim3(blocks), dim3(64), 0, stream, scene->viewt, R, txt_tan_fov_y, n_work); break;
+            case Pipeline::Hw4: hipLaunchKernelGGL(dev::render_hw4_kernel, dim3(blocks), dim3(64), 0, stream, scene->viewt, R, txt_tan_fov_y, n_work); break;
+            case Pipeline::Hw5: hipLaunchKernelGGL(dev::render_hw5_kernel, dim3(blocks), dim3(64), 0, stream, scene->view5, R, txt_tan_fov_y, n_work); break;
+            }
+            HIP_CHECK(hipGetLastError());
+            if (streams > 1) {
+                hipLaunchKernelGGL(dev::wf_reduce_streams_kernel, dim3((R.n_pixslots + 255u) / 256u), dim3(256), 0, stream, R);
                 HIP_CHECK(hipGetLastError());
-                launches = 1;
+                launches++;
             }
         }
         HIP_CHECK(hipEventRecord(scene->ev_stop, stream));
@@ -1252,81 +1238,17 @@ int rt_render(rt_scene *scene, const rt_render_params *p, float *out_rgb, uint8_
         unsigned long long h_cnt[64] = {0};
         HIP_CHECK(hipMemcpyAsync(h_cnt, scene->d_counters, 512, hipMemcpyDeviceToHost, stream));
         HIP_CHECK(hipStreamSynchronize(stream)); // render is synchronous on return
-        use_persistent = use_persistent && use_wavefront && blocks;
-        if (use_persistent6 && getenv("RTAMD_DEBUG_COUNTERS")) {
-            fprintf(stderr, "[rtamd] persistent hw6 pipeline: %u launches; re-deal %.2f ms on the host (slowest workgroup / mean under the round-robin deal: %.3f); light sums through the slow role %llu of %llu; exact closest-hit walks %llu of %llu, exact light sums %llu\n",
-                    scene->pt_launches, scene->pt_rebalance_ms, scene->pt_imbalance, h_cnt[13], h_cnt[1], h_cnt[12], h_cnt[0], h_cnt[11]);
-            if (count) {
-                fprintf(stderr, "[rtamd] persistent hw6 kernel, light sums in the slow role by number of hits (0..14, 15+):");
-                for (int b = 0; b < 16; b++) fprintf(stderr, " %llu", h_cnt[32 + b]);
-                fprintf(stderr, "\n");
-                const double tt = (double)(h_cnt[16] + h_cnt[17] + h_cnt[18] + h_cnt[19] + h_cnt[20]);
-                fprintf(stderr, "[rtamd] persistent hw6 kernel, wave time by role: closest-hit walks %.1f %%, light walks %.1f %%, shading %.1f %%, slow light sums %.1f %%, idle %.1f %%\n",
-                        100 * h_cnt[16] / tt, 100 * h_cnt[17] / tt, 100 * h_cnt[18] / tt, 100 * h_cnt[19] / tt, 100 * h_cnt[20] / tt);
-            }
-            if (scene->d_pt_debug && scene->pt_blocks <= PT_DEBUG_BLOCKS) {
-                std::vector<unsigned long long> dbg((size_t)scene->pt_blocks * 3);
-                HIP_CHECK(hipMemcpy(dbg.data(), scene->d_pt_debug, dbg.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-                unsigned long long t0 = ~0ull, tmin = ~0ull, tmax = 0; double tsum = 0;
-                for (uint32_t b = 0; b < scene->pt_blocks; b++) if (dbg[3 * b] && dbg[3 * b] < t0) t0 = dbg[3 * b];
-                for (uint32_t b = 0; b < scene->pt_blocks; b++) { unsigned long long e = dbg[3 * b + 1] - t0; tmin = e < tmin ? e : tmin; tmax = e > tmax ? e : tmax; tsum += (double)e; }
-                fprintf(stderr, "[rtamd] persistent hw6 kernel (last launch): %u workgroups, exit times min / mean / max = %.3f / %.3f / %.3f ms after the first start\n",
-                        scene->pt_blocks, tmin * 1e-5, tsum / scene->pt_blocks * 1e-5, tmax * 1e-5);
-                if (const char *dump = getenv("RTAMD_DUMP_WG")) { // diagnostic, as for hw8 (tools/tuning/wg_balance.py)
-                    if (FILE *f = fopen(dump, "w")) {
-                        for (uint32_t b = 0; b < scene->pt_blocks; b++) fprintf(f, "%u %.4f %.4f %llu\n", b, (dbg[3 * b] - t0) * 1e-5, (dbg[3 * b + 1] - t0) * 1e-5, dbg[3 * b + 2]);
-                        fclose(f);
-                    }
-                }
-            }
+        const bool ran_persistent = blocks && (pipe == Pipeline::Persistent8 || pipe == Pipeline::Persistent6);
+        const bool ran_rounds = blocks && pipe == Pipeline::Rounds;
+        if (ran_persistent) {
+            const bool hw6 = pipe == Pipeline::Persistent6;
+            const char *kernel = hw6 ? "persistent hw6 kernel" : "persistent kernel";
+            if (!hw6) h_cnt[0] -= h_cnt[10] < h_cnt[0] ? h_cnt[10] : h_cnt[0]; // speculative closest-hit queries that the clamp step discarded are not part of the algorithm
+            if (getenv("RTAMD_DEBUG_COUNTERS")) report_persistent(scene, hw6, kernel, count, h_cnt);
+            if (h_cnt[29]) return fail(RT_ERR_LIMIT, std::string("rt_render: the ") + kernel + " ran into its launch deadline (" + std::to_string(h_cnt[29]) + " waves; RTAMD_PT_TIMEOUT_S raises it); the frame is incomplete");
+            if (h_cnt[14]) return fail(RT_ERR_HIP, std::string("rt_render: the ") + kernel + " lost a path (" + std::to_string(h_cnt[14]) + " waves gave up waiting); the frame is incomplete");
         }
-        if (use_persistent6 && h_cnt[29]) return fail(RT_ERR_LIMIT, "rt_render: the persistent hw6 kernel ran into its launch deadline (" + std::to_string(h_cnt[29]) + " waves; RTAMD_PT_TIMEOUT_S raises it); the frame is incomplete");
-        if (use_persistent6 && h_cnt[14]) return fail(RT_ERR_HIP, "rt_render: the persistent hw6 kernel lost a path (" + std::to_string(h_cnt[14]) + " waves gave up waiting); the frame is incomplete");
-        scene->pipeline = (use_persistent || use_persistent6) ? RT_PIPELINE_PERSISTENT : (use_wavefront && blocks ? RT_PIPELINE_ROUNDS : RT_PIPELINE_SINGLE);
-        if (use_persistent) {
-            if (h_cnt[29]) return fail(RT_ERR_LIMIT, "rt_render: the persistent kernel ran into its launch deadline (" + std::to_string(h_cnt[29]) + " waves; RTAMD_PT_TIMEOUT_S raises it); the frame is incomplete");
-            if (h_cnt[14]) return fail(RT_ERR_HIP, "rt_render: the persistent kernel lost a path (" + std::to_string(h_cnt[14]) + " waves gave up waiting); the frame is incomplete");
-            h_cnt[0] -= h_cnt[10] < h_cnt[0] ? h_cnt[10] : h_cnt[0]; // speculative closest-hit queries that the clamp step discarded are not part of the algorithm
-            if (getenv("RTAMD_DEBUG_COUNTERS") && scene->d_pt_debug && scene->pt_blocks <= PT_DEBUG_BLOCKS) {
-                std::vector<unsigned long long> dbg((size_t)scene->pt_blocks * 3);
-                HIP_CHECK(hipMemcpy(dbg.data(), scene->d_pt_debug, dbg.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-                unsigned long long t0 = ~0ull, tmin = ~0ull, tmax = 0; double tsum = 0;
-                for (uint32_t b = 0; b < scene->pt_blocks; b++) if (dbg[3 * b] && dbg[3 * b] < t0) t0 = dbg[3 * b];
-                for (uint32_t b = 0; b < scene->pt_blocks; b++) { unsigned long long e = dbg[3 * b + 1] - t0; tmin = e < tmin ? e : tmin; tmax = e > tmax ? e : tmax; tsum += (double)e; }
-                if (count) {
-                    const double tt = (double)(h_cnt[16] + h_cnt[17] + h_cnt[18] + h_cnt[19] + h_cnt[20]);
-                    fprintf(stderr, "[rtamd] persistent kernel, wave time by role: closest-hit walks %.1f %%, light walks %.1f %%, shading %.1f %%, exact walks %.2f %%, idle %.1f %%; "
-                                    "walker lane utilisation: closest hit %.1f of 64 (%llu wave iterations), light %.1f of 64 (%llu); %llu stints, %llu shade batches of %.1f paths\n",
-                            100 * h_cnt[16] / tt, 100 * h_cnt[17] / tt, 100 * h_cnt[18] / tt, 100 * h_cnt[19] / tt, 100 * h_cnt[20] / tt,
-                            (double)h_cnt[22] / (double)(h_cnt[21] ? h_cnt[21] : 1), h_cnt[21], (double)h_cnt[24] / (double)(h_cnt[23] ? h_cnt[23] : 1), h_cnt[23],
-                            h_cnt[25], h_cnt[26], (double)h_cnt[27] / (double)(h_cnt[26] ? h_cnt[26] : 1));
-                    for (int w = 0; w < 2; w++) {
-                        const double tw = (double)(h_cnt[48 + 3 * w] + h_cnt[49 + 3 * w] + h_cnt[50 + 3 * w]);
-                        fprintf(stderr, "[rtamd]   %s walker's wave time: hand-off and refill %.1f %%, inner nodes %.1f %%, leaves %.1f %%; leaf passes %llu with %.1f of 64 lanes\n",
-                                w ? "light" : "closest-hit", 100 * h_cnt[48 + 3 * w] / tw, 100 * h_cnt[49 + 3 * w] / tw, 100 * h_cnt[50 + 3 * w] / tw,
-                                h_cnt[54 + 2 * w], (double)h_cnt[55 + 2 * w] / (double)(h_cnt[54 + 2 * w] ? h_cnt[54 + 2 * w] : 1));
-                    }
-                    fprintf(stderr, "[rtamd]   closest-hit walker's hand-off points: %llu; of their time: publishing finished walks %.1f %%, taking new ones from the bitmap %.1f %%, reading their rays %.1f %% (the rest: the test itself)\n",
-                            h_cnt[63], 100.0 * h_cnt[60] / (double)(h_cnt[48] ? h_cnt[48] : 1), 100.0 * h_cnt[61] / (double)(h_cnt[48] ? h_cnt[48] : 1), 100.0 * h_cnt[62] / (double)(h_cnt[48] ? h_cnt[48] : 1));
-                    fprintf(stderr, "[rtamd]   light tests %llu (%.2f per light sum), hits %llu (%.2f per light sum); triangle tests of closest-hit walks %llu (%.2f per query)\n",
-                            h_cnt[59], (double)h_cnt[59] / (double)(h_cnt[1] ? h_cnt[1] : 1), h_cnt[58], (double)h_cnt[58] / (double)(h_cnt[1] ? h_cnt[1] : 1),
-                            h_cnt[3] - h_cnt[59], (double)(h_cnt[3] - h_cnt[59]) / (double)(h_cnt[0] ? h_cnt[0] : 1));
-                    fprintf(stderr, "[rtamd]   light sums whose walk ends at the light tree's root %llu (%.1f %%), one level below it %llu (%.1f %%); settled by the shader: level %d\n",
-                            h_cnt[30], 100.0 * h_cnt[30] / (double)(h_cnt[1] ? h_cnt[1] : 1), h_cnt[31], 100.0 * h_cnt[31] / (double)(h_cnt[1] ? h_cnt[1] : 1), PT_LIGHT_SETTLE);
-                }
-                if (const char *dump = getenv("RTAMD_DUMP_WG")) { // diagnostic: start / exit time (ms after the first start) and paths of every workgroup of the last launch
-                    if (FILE *f = fopen(dump, "w")) {
-                        for (uint32_t b = 0; b < scene->pt_blocks; b++) fprintf(f, "%u %.4f %.4f %llu\n", b, (dbg[3 * b] - t0) * 1e-5, (dbg[3 * b + 1] - t0) * 1e-5, dbg[3 * b + 2]);
-                        fclose(f);
-                    }
-                }
-                fprintf(stderr, "[rtamd] persistent pipeline: %u launches; re-deal of the sub-tiles took %.2f ms on the host (slowest workgroup / mean under the round-robin deal: %.3f)\n",
-                        scene->pt_launches, scene->pt_rebalance_ms, scene->pt_imbalance);
-                fprintf(stderr, "[rtamd] persistent kernel (last launch): %u workgroups, exit times min / mean / max = %.3f / %.3f / %.3f ms after the first start; exact closest hits %llu, exact light sums %llu of %llu + %llu queries\n",
-                        scene->pt_blocks, tmin * 1e-5, tsum / scene->pt_blocks * 1e-5, tmax * 1e-5, h_cnt[12], h_cnt[13], h_cnt[0], h_cnt[1]);
-            }
-        }
-        if (count && use_wavefront && blocks && !use_persistent) { // queries = lengths of the per-round queues
+        if (count && ran_rounds) { // queries = lengths of the per-round queues
             size_t rounds = wavefront_rounds(V8, R);
             std::vector<uint32_t> ctr(scene->wf_ctr_block * scene->wf_pipes);
             HIP_CHECK(hipMemcpy(ctr.data(), scene->wf.ctr, ctr.size() * 4, hipMemcpyDeviceToHost));
@@ -1339,7 +1261,7 @@ int rt_render(rt_scene *scene, const rt_render_params *p, float *out_rgb, uint8_
             h_cnt[0] -= h_cnt[10]; // speculative closest-hit queries that the clamp step discarded are not part of the algorithm
             h_cnt[13] = h_cnt[11];  // light sums finished by the exact kernel
         }
-        if (count && use_wavefront && getenv("RTAMD_DEBUG_COUNTERS")) { // wave iterations a query stays in flight, buckets of 32
+        if (count && (pipe == Pipeline::Persistent8 || pipe == Pipeline::Rounds) && getenv("RTAMD_DEBUG_COUNTERS")) { // wave iterations a query stays in flight, buckets of 32
             fprintf(stderr, "[rtamd] closest-hit queries by in-flight wave iterations (x32):");
             for (int b = 0; b < 16; b++) fprintf(stderr, " %llu", h_cnt[16 + b]);
             fprintf(stderr, "\n[rtamd] light queries by in-flight wave iterations (x32):");
@@ -1356,15 +1278,15 @@ int rt_render(rt_scene *scene, const rt_render_params *p, float *out_rgb, uint8_
             stats->kernel_ms = ms;
             stats->total_ms = now_ms() - t0;
             stats->launches = launches;
-            stats->pipeline = (uint32_t)scene->pipeline;
-            stats->reference_exact = p->integrator == RT_INTEGRATOR_HW5 ? 1u : use_persistent6 ? (scene->view6.exact_boxes ? 1u : 0u)
-                                     : ((scene->flavor == RT_INTEGRATOR_HW8 && (use_persistent || (use_wavefront && blocks)) && V8.exact_boxes == 1u) ? 1u : 0u);
-            if (use_persistent || use_persistent6) {
+            stats->pipeline = ran_persistent ? RT_PIPELINE_PERSISTENT : ran_rounds ? RT_PIPELINE_ROUNDS : RT_PIPELINE_SINGLE;
+            stats->reference_exact = pipe == Pipeline::Hw5 ? 1u : pipe == Pipeline::Persistent6 ? (blocks && scene->view6.exact_boxes ? 1u : 0u)
+                                     : ((ran_persistent || ran_rounds) && V8.exact_boxes == 1u ? 1u : 0u);
+            if (ran_persistent) {
                 double sum = 0;
                 for (uint32_t pp = 0; time_trace && pp < scene->pt_launches; pp++) { float e = 0; HIP_CHECK(hipEventElapsedTime(&e, scene->ev_pool[2 * pp], scene->ev_pool[2 * pp + 1])); sum += e; }
                 stats->dominant_kernel_ms = time_trace ? sum : ms; stats->dominant_kernel_launches = scene->pt_launches;
-                stats->exact_closest_hits = h_cnt[12]; stats->exact_light_sums = use_persistent6 ? h_cnt[11] : h_cnt[13];
-            } else if (use_wavefront && blocks && time_trace) {
+                stats->exact_closest_hits = h_cnt[12]; stats->exact_light_sums = pipe == Pipeline::Persistent6 ? h_cnt[11] : h_cnt[13];
+            } else if (ran_rounds && time_trace) {
                 stats->exact_closest_hits = h_cnt[12]; stats->exact_light_sums = h_cnt[13]; // counting renders only
                 size_t rounds = wavefront_rounds(V8, R);
                 double sum = 0;

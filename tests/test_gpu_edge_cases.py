@@ -256,6 +256,31 @@ def test_persistent_pipeline_phases_and_deals_do_not_change_pixels(rt, monkeypat
         thr2, _, stt = scene.render(w, h, 12, sample_streams=3)
         assert np.array_equal(thr2, thr1, equal_nan=True)
     scene.close()
+    # the hw6 kernel under the same host scheme: 36 sub-tiles per workgroup, so three workgroups take the 187 sub-tiles in two passes
+    monkeypatch.delenv("RTAMD_PT_BLOCKS")
+    monkeypatch.delenv("RTAMD_PT_PHASE0")
+    sd6 = pin_cases.hw6_soup()
+    hw6 = dict(integrator=rt.RT_INTEGRATOR_HW6)
+    scene = rt.Scene(sd6)
+    monkeypatch.setenv("RTAMD_PT_NO_REBALANCE", "1")
+    one, one8, st1 = scene.render(w, h, spp, **hw6)
+    shard1, _, _ = scene.render(w, h, spp, shard_index=1, shard_count=2, tile=16, **hw6)
+    thr1, _, _ = scene.render(w, h, 12, sample_streams=3, **hw6)
+    monkeypatch.delenv("RTAMD_PT_NO_REBALANCE")
+    assert st1.pipeline == rt.RT_PIPELINE_PERSISTENT and st1.launches == 1
+    for (blocks, phase0), launches in zip(((8, 2), (3, 1), (16, 6)), (2, 4, 2)):
+        monkeypatch.setenv("RTAMD_PT_BLOCKS", str(blocks))
+        monkeypatch.setenv("RTAMD_PT_PHASE0", str(phase0))
+        two, two8, st2 = scene.render(w, h, spp, **hw6)
+        assert st2.launches == launches and st2.dominant_kernel_launches == launches
+        assert np.array_equal(two, one, equal_nan=True) and np.array_equal(two8, one8)
+        shard2, _, _ = scene.render(w, h, spp, shard_index=1, shard_count=2, tile=16, **hw6)
+        assert np.array_equal(shard2, shard1, equal_nan=True)
+        thr2, _, _ = scene.render(w, h, 12, sample_streams=3, **hw6)
+        assert np.array_equal(thr2, thr1, equal_nan=True)
+    scene.close()
+    crop_ref, _, _ = oracle_lib.Hw6Oracle(sd6).render(w, h, spp, rect=(48, 32, 40, 24))
+    assert np.array_equal(one[32:56, 48:88], crop_ref, equal_nan=True)
 
 
 def test_persistent_pipeline_in_several_passes(rt, monkeypatch):
@@ -280,4 +305,24 @@ def test_persistent_pipeline_in_several_passes(rt, monkeypatch):
     assert np.array_equal(thr2, thr1, equal_nan=True) and np.array_equal(shard2, shard1, equal_nan=True)
     assert (st2.closest_hit_queries, st2.light_pdf_queries) == (st1.closest_hit_queries, st1.light_pdf_queries)
     crop_ref, _, _ = oracle_lib.Hw8Oracle(sd).render(w, h, spp, rect=(180, 130, 40, 40))
+    assert np.array_equal(two[130:170, 180:220], crop_ref, equal_nan=True)
+    # the hw6 kernel (36 sub-tiles per workgroup): 1,900 sub-tiles on 14 workgroups take four passes
+    monkeypatch.delenv("RTAMD_PT_BLOCKS")
+    monkeypatch.delenv("RTAMD_PT_PHASE0")
+    sd6 = pin_cases.hw6_soup()
+    hw6 = dict(integrator=rt.RT_INTEGRATOR_HW6)
+    scene = rt.Scene(sd6)
+    one, one8, st1 = scene.render(w, h, spp, **hw6)
+    thr1, _, _ = scene.render(w, h, 8, sample_streams=2, **hw6)
+    shard1, _, _ = scene.render(w, h, spp, shard_index=2, shard_count=3, tile=32, **hw6)
+    monkeypatch.setenv("RTAMD_PT_BLOCKS", "14")
+    monkeypatch.setenv("RTAMD_PT_PHASE0", "1")
+    two, two8, st2 = scene.render(w, h, spp, **hw6)
+    thr2, _, stt = scene.render(w, h, 8, sample_streams=2, **hw6)
+    shard2, _, _ = scene.render(w, h, spp, shard_index=2, shard_count=3, tile=32, **hw6)
+    scene.close()
+    assert st1.pipeline == rt.RT_PIPELINE_PERSISTENT and st1.launches == 1 and st2.launches == 8 and stt.launches >= 8 + 1   # 4 passes x 2 phases
+    assert np.array_equal(two, one, equal_nan=True) and np.array_equal(two8, one8)
+    assert np.array_equal(thr2, thr1, equal_nan=True) and np.array_equal(shard2, shard1, equal_nan=True)
+    crop_ref, _, _ = oracle_lib.Hw6Oracle(sd6).render(w, h, spp, rect=(180, 130, 40, 40))
     assert np.array_equal(two[130:170, 180:220], crop_ref, equal_nan=True)
