@@ -447,6 +447,12 @@ static V3 load_texel(int ix, int iy, const Tex &tex, bool srgb) {
     if (srgb) return V3{std::pow(res.x, 2.2f), std::pow(res.y, 2.2f), std::pow(res.z, 2.2f)};
     return res;
 }
+// scene.cpp:94-95.  Vec3's members are float: std::atan2 / std::asin resolve to atan2f / asinf, and only their results are
+// widened to double for the rest of each expression.
+static void env_uv(V3 d, float &tx, float &ty) {
+    tx = 0.5 + 0.5 * std::atan2(d.z, d.x) / M_PI;
+    ty = 0.5 - std::asin(d.y) / M_PI;
+}
 // scene.cpp:18-35
 static V3 sample_texture(float tx, float ty, const Tex &tex, bool srgb) {
     tx -= std::floor(tx);
@@ -539,8 +545,8 @@ struct Scene {
         }
         if (!found) {
             if (!has_env) return bg;
-            float tx = 0.5 + 0.5 * std::atan2((double)rd.z, (double)rd.x) / M_PI;
-            float ty = 0.5 - std::asin((double)rd.y) / M_PI;
+            float tx, ty;
+            env_uv(rd, tx, ty);
             return sample_texture(tx, ty, env, true);
         }
         const Fig &f = figs[idx];
@@ -740,6 +746,13 @@ void rto_rng_kat(uint32_t seed, int n_u, int n_n, float *out) {
 }
 // Host libm logf (what the reference's normal_distribution calls) on an array.
 void rto_logf_array(const float *in, float *out, size_t n) { for (size_t i = 0; i < n; i++) out[i] = std::log(in[i]); }
+// Host libm atan2f / asinf (what the reference's environment lookup calls on floats) on arrays.
+void rto_atan2f_array(const float *y, const float *x, float *out, size_t n) { for (size_t i = 0; i < n; i++) out[i] = std::atan2(y[i], x[i]); }
+void rto_asinf_array(const float *in, float *out, size_t n) { for (size_t i = 0; i < n; i++) out[i] = std::asin(in[i]); }
+// The oracle's environment-map uv for n directions (d: n x 3, uv: n x 2).
+void rto_hw8_env_uv(const float *d, float *uv, size_t n) {
+    for (size_t i = 0; i < n; i++) env_uv(V3{d[3 * i], d[3 * i + 1], d[3 * i + 2]}, uv[2 * i], uv[2 * i + 1]);
+}
 // Same engine, normals drawn first, then uniforms.
 void rto_rng_kat_normals_first(uint32_t seed, int n_n, int n_u, float *out) {
     rng_t rng(seed); U01 u01(0.0, 1.0); N01 n01(0.0, 1.0);

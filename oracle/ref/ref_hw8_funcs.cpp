@@ -116,6 +116,17 @@ void ref8_transform_chain(int n_levels, const float *chain, const float *matrix1
         out_tan[3 * i] = tt.x; out_tan[3 * i + 1] = tt.y; out_tan[3 * i + 2] = tt.z;
     }
 }
+// The environment-map uv of a miss, hw8/src/scene.cpp:94-95 evaluated on the reference's own Ray / Vec3, so that the libm
+// overloads are the ones its types select.  d: n x 3 directions, uv: n x 2.
+void ref8_env_uv(const float *d, float *uv, size_t n) {
+    for (size_t i = 0; i < n; i++) {
+        Ray ray(Vec3(0, 0, 0), v3(d + 3 * i));
+        float texcoordX = 0.5 + 0.5 * std::atan2(ray.d.z, ray.d.x) / M_PI;
+        float texcoordY = 0.5 - std::asin(ray.d.y) / M_PI;
+        uv[2 * i] = texcoordX;
+        uv[2 * i + 1] = texcoordY;
+    }
+}
 void ref8_tonemap(const float *rgb, uint8_t *out3) {
     auto a = toExternColorFormat(gamma_corrected(aces_tonemap(v3(rgb))));
     out3[0] = a[0]; out3[1] = a[1]; out3[2] = a[2];

@@ -99,6 +99,100 @@ RT_DEV float rt_logf(float x) {
     return (float)y;
 }
 
+// glibc 2.35 atanf, atan2f and asinf (sysdeps/ieee754/flt-32/s_atanf.c, e_atan2f.c, e_asinf.c): the float overloads
+// that std::atan2(float, float) and std::asin(float) select in the reference's environment-map lookup (scene.cpp:94-95).
+// fdlibm's float algorithms, restated in float arithmetic only: no FMA (x86-64 glibc builds these without the multiarch
+// ifunc that logf has, so the host CPU does not matter), correctly rounded division and sqrtf, atanf's atanhi / atanlo
+// picked by selects instead of a runtime-indexed table.  Bit-identical to the host libm of an x86-64 glibc 2.35 host: asinf on
+// every float in [-1, 1], atanf on every float, atan2f on 6e7 pairs and the special values; tests/test_gpu_device_math.py
+// checks the device against the host libm.
+RT_DEV float rt_atanf(float x) {
+    const uint32_t hx = __float_as_uint(x), ix = hx & 0x7fffffffu;
+    if (ix >= 0x4c000000u) {                                   // |x| >= 2^25 (or NaN)
+        if (ix > 0x7f800000u) return x + x;
+        const float r = 1.5707962513e+00f + 7.5497894159e-08f; // atanhi[3] + atanlo[3]
+        return (hx >> 31) ? -r : r;
+    }
+    int id = -1;
+    if (ix < 0x3ee00000u) {                                    // |x| < 7/16
+        if (ix < 0x31000000u) return x;                        // |x| < 2^-29
+    } else {
+        x = fabsf(x);
+        if (ix < 0x3f980000u) {                                // |x| < 19/16
+            if (ix < 0x3f300000u) { id = 0; x = (2.0f * x - 1.0f) / (2.0f + x); }   // 7/16 <= |x| < 11/16
+            else { id = 1; x = (x - 1.0f) / (x + 1.0f); }                        // 11/16 <= |x| < 19/16
+        } else {
+            if (ix < 0x401c0000u) { id = 2; x = (x - 1.5f) / (1.0f + 1.5f * x); } // 19/16 <= |x| < 39/16
+            else { id = 3; x = -1.0f / x; }                                        // 39/16 <= |x| < 2^26
+        }
+    }
+    const float z = x * x, w = z * z;
+    const float s1 = z * (3.3333334327e-01f + w * (1.4285714924e-01f + w * (9.0908870101e-02f + w * (6.6610731184e-02f + w * (4.9768779427e-02f + w * 1.6285819933e-02f)))));
+    const float s2 = w * (-2.0000000298e-01f + w * (-1.1111110449e-01f + w * (-7.6918758452e-02f + w * (-5.8335702866e-02f + w * -3.6531571299e-02f))));
+    if (id < 0) return x - x * (s1 + s2);
+    // atanhi[id], atanlo[id] by selects: a table indexed by a runtime id would live in scratch
+    const float hi = id == 0 ? 4.6364760399e-01f : id == 1 ? 7.8539812565e-01f : id == 2 ? 9.8279368877e-01f : 1.5707962513e+00f;
+    const float lo = id == 0 ? 5.0121582440e-09f : id == 1 ? 3.7748947079e-08f : id == 2 ? 3.4473217170e-08f : 7.5497894159e-08f;
+    const float r = hi - ((x * (s1 + s2) - lo) - x);
+    return (hx >> 31) ? -r : r;
+}
+
+RT_DEV float rt_atan2f(float y, float x) {
+    const float pi_o_4 = 7.8539818525e-01f, pi_o_2 = 1.5707963705e+00f, pi = 3.1415927410e+00f, pi_lo = -8.7422776573e-08f;
+    const uint32_t hx = __float_as_uint(x), hy = __float_as_uint(y);
+    const uint32_t ix = hx & 0x7fffffffu, iy = hy & 0x7fffffffu;
+    if (ix > 0x7f800000u || iy > 0x7f800000u) return x + y;   // NaN
+    if (hx == 0x3f800000u) return rt_atanf(y);                 // x = 1
+    const uint32_t m = ((hy >> 31) & 1u) | ((hx >> 30) & 2u);  // 2 sign(x) + sign(y)
+    if (iy == 0) return m < 2 ? y : m == 2 ? pi : -pi;        // atan(+-0, +x) = +-0, atan(+-0, -x) = +-pi
+    if (ix == 0) return (hy >> 31) ? -pi_o_2 : pi_o_2;
+    if (ix == 0x7f800000u) {
+        if (iy == 0x7f800000u) return m == 0 ? pi_o_4 : m == 1 ? -pi_o_4 : m == 2 ? 3.0f * pi_o_4 : -3.0f * pi_o_4;
+        return m == 0 ? 0.0f : m == 1 ? -0.0f : m == 2 ? pi : -pi;
+    }
+    if (iy == 0x7f800000u) return (hy >> 31) ? -pi_o_2 : pi_o_2;
+    const int k = ((int)iy - (int)ix) >> 23;
+    float z;
+    if (k > 26) z = pi_o_2 + 0.5f * pi_lo;                     // |y/x| > 2^26
+    else if ((hx >> 31) && k < -26) z = 0.0f;                  // |y|/x < -2^26
+    else z = rt_atanf(fabsf(y / x));
+    switch (m) {
+    case 0: return z;
+    case 1: return -z;
+    case 2: return pi - (z - pi_lo);
+    default: return (z - pi_lo) - pi;
+    }
+}
+
+RT_DEV float rt_asinf(float x) {
+    const float pio2_hi = 1.57079637050628662109375f, pio2_lo = -4.37113900018624283e-8f, pio4_hi = 0.785398185253143310546875f;
+    const float p0 = 1.666675248e-1f, p1 = 7.495297643e-2f, p2 = 4.547037598e-2f, p3 = 2.417951451e-2f, p4 = 4.216630880e-2f;
+    const uint32_t hx = __float_as_uint(x), ix = hx & 0x7fffffffu;
+    if (ix == 0x3f800000u) return x * pio2_hi + x * pio2_lo;  // asin(+-1) = +-pi/2
+    if (ix > 0x3f800000u) return (x - x) / (x - x);            // |x| > 1 (and NaN): NaN
+    if (ix < 0x3f000000u) {                                    // |x| < 0.5
+        if (ix < 0x32000000u) return x;                        // |x| < 2^-27
+        const float t = x * x;
+        const float w = t * (p0 + t * (p1 + t * (p2 + t * (p3 + t * p4))));
+        return x + x * w;
+    }
+    const float w = 1.0f - fabsf(x);                           // 0.5 <= |x| < 1
+    float t = w * 0.5f;
+    float p = t * (p0 + t * (p1 + t * (p2 + t * (p3 + t * p4))));
+    const float s = sqrtf(t);
+    if (ix >= 0x3f79999au) {                                   // |x| > 0.975
+        t = pio2_hi - (2.0f * (s + s * p) - pio2_lo);
+    } else {
+        const float wh = __uint_as_float(__float_as_uint(s) & 0xfffff000u);
+        const float c = (t - wh * wh) / (s + wh);
+        const float r = p;
+        p = 2.0f * s * r - (pio2_lo - 2.0f * c);
+        const float q = pio4_hi - 2.0f * wh;
+        t = pio4_hi - (p - q);
+    }
+    return (hx >> 31) ? -t : t;
+}
+
 // normal_distribution<float>(0,1): Marsaglia polar with the saved second value
 // (bits/random.tcc:1802-1838).
 RT_DEV float rng_n01(Rng &r) {

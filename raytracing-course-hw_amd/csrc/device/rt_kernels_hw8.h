@@ -118,13 +118,20 @@ RT_DEV F3 emission_fetch(const SceneView &S, const HitRec &h) {
     return emission;
 }
 
-// ENV = false compiles the environment-map lookup out: its inlined double-precision atan2 / asin are the largest register users of
-// the shading code, and a kernel that can never reach them (scene without an environment map) spills half as many registers.
+// scene.cpp:94-95.  Vec3's members are float, so the reference's std::atan2 / std::asin are the float overloads (atan2f, asinf);
+// only their results are widened, and the rest of each expression is double as written.
+RT_DEV void env_uv(F3 d, float &tx, float &ty) {
+    tx = (float)(0.5 + 0.5 * (double)rt_atan2f(d.z, d.x) / RT_PI);
+    ty = (float)(0.5 - (double)rt_asinf(d.y) / RT_PI);
+}
+
+// ENV = false compiles the environment-map lookup out: a kernel that can never reach it (scene without an environment map) carries
+// neither the two libm restatements nor the texture fetch.
 template <bool ENV = true>
 RT_DEV F3 miss_color(const SceneView &S, F3 d) { // scene.cpp:90-97
     if (!ENV || S.env_image < 0) return f3(S.bg);
-    float tx = (float)(0.5 + 0.5 * atan2((double)d.z, (double)d.x) / RT_PI);
-    float ty = (float)(0.5 - asin((double)d.y) / RT_PI);
+    float tx, ty;
+    env_uv(d, tx, ty);
     return sample_texture(S, S.env_image, tx, ty, true);
 }
 

@@ -646,8 +646,8 @@ __global__ __launch_bounds__(64) void wf_light_exact_kernel(SceneView S, WfView 
 // ray), | WF_NEXT_LIGHT (that ray is also a bounce's light-pdf query), WF_PARKED (the next sample's camera ray is in the
 // record but belongs to the frame's next phase), or 0 (the pixel is finished and written).
 // FEAT: which optional features the shading code is compiled with (WF_FEAT_ENV: environment-map lookup on a miss; WF_FEAT_HW7: the
-// hw7 material model).  A kernel variant without a feature the render cannot use carries less register pressure: the inlined
-// double-precision atan2 / asin of the environment lookup alone double the spills of the persistent kernel.
+// hw7 material model).  A kernel variant without a feature the render cannot use carries less register pressure and less code: the
+// environment lookup inlines float atan2f / asinf (rt_device.h) and a texture fetch.
 #define WF_FEAT_ENV 1
 #define WF_FEAT_HW7 2
 template <int FEAT = WF_FEAT_ENV | WF_FEAT_HW7>

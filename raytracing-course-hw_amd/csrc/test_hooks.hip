@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include "device/rt_device.h"
 #include "device/rt_exact.h"
+#include "device/rt_kernels_hw8.h"
 #include "device/rt_node_grid.h"
 #include "host/fold_nodes.h"
 #include <cstring>
@@ -13,6 +14,18 @@ using namespace rtamd::dev;
 __global__ void k_logf(const float *in, float *out, size_t n) {
     size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
     if (i < n) out[i] = rt_logf(in[i]);
+}
+__global__ void k_asinf(const float *in, float *out, size_t n) {
+    size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (i < n) out[i] = rt_asinf(in[i]);
+}
+__global__ void k_atan2f(const float *y, const float *x, float *out, size_t n) {
+    size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (i < n) out[i] = rt_atan2f(y[i], x[i]);
+}
+__global__ void k_env_uv(const float *d, float *uv, size_t n) { // d: n x 3 directions, uv: n x 2
+    size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (i < n) env_uv(f3(d + 3 * i), uv[2 * i], uv[2 * i + 1]);
 }
 __global__ void k_rng(uint32_t seed0, int n_seeds, int n_u, int n_n, float *out) {
     int s = blockIdx.x * blockDim.x + threadIdx.x;
@@ -112,6 +125,37 @@ int rtt_logf(const float *in, float *out, size_t n) {
     hipLaunchKernelGGL(k_logf, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, d_in, d_out, n);
     int rc = hipMemcpy(out, d_out, n * 4, hipMemcpyDeviceToHost) == hipSuccess ? 0 : -2;
     (void)hipFree(d_in); (void)hipFree(d_out);
+    return rc;
+}
+int rtt_asinf(const float *in, float *out, size_t n) {
+    float *d_in = nullptr, *d_out = nullptr;
+    if (hipMalloc((void **)&d_in, n * 4) != hipSuccess || hipMalloc((void **)&d_out, n * 4) != hipSuccess) return -1;
+    if (hipMemcpy(d_in, in, n * 4, hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(d_in); (void)hipFree(d_out); return -2; }
+    hipLaunchKernelGGL(k_asinf, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, d_in, d_out, n);
+    int rc = hipMemcpy(out, d_out, n * 4, hipMemcpyDeviceToHost) == hipSuccess ? 0 : -2;
+    (void)hipFree(d_in); (void)hipFree(d_out);
+    return rc;
+}
+int rtt_atan2f(const float *y, const float *x, float *out, size_t n) {
+    float *d_y = nullptr, *d_x = nullptr, *d_out = nullptr;
+    if (hipMalloc((void **)&d_y, n * 4) != hipSuccess || hipMalloc((void **)&d_x, n * 4) != hipSuccess ||
+        hipMalloc((void **)&d_out, n * 4) != hipSuccess) { (void)hipFree(d_y); (void)hipFree(d_x); return -1; }
+    if (hipMemcpy(d_y, y, n * 4, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(d_x, x, n * 4, hipMemcpyHostToDevice) != hipSuccess) {
+        (void)hipFree(d_y); (void)hipFree(d_x); (void)hipFree(d_out); return -2;
+    }
+    hipLaunchKernelGGL(k_atan2f, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, d_y, d_x, d_out, n);
+    int rc = hipMemcpy(out, d_out, n * 4, hipMemcpyDeviceToHost) == hipSuccess ? 0 : -2;
+    (void)hipFree(d_y); (void)hipFree(d_x); (void)hipFree(d_out);
+    return rc;
+}
+// the miss shader's environment-map uv (rt_kernels_hw8.h env_uv) for n directions: d n x 3, uv n x 2
+int rtt_env_uv(const float *d, float *uv, size_t n) {
+    float *d_d = nullptr, *d_uv = nullptr;
+    if (hipMalloc((void **)&d_d, n * 12) != hipSuccess || hipMalloc((void **)&d_uv, n * 8) != hipSuccess) return -1;
+    if (hipMemcpy(d_d, d, n * 12, hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(d_d); (void)hipFree(d_uv); return -2; }
+    hipLaunchKernelGGL(k_env_uv, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, d_d, d_uv, n);
+    int rc = hipMemcpy(uv, d_uv, n * 8, hipMemcpyDeviceToHost) == hipSuccess ? 0 : -2;
+    (void)hipFree(d_d); (void)hipFree(d_uv);
     return rc;
 }
 // streams for seeds seed0 .. seed0+n_seeds-1: n_u uniforms then n_n normals each

@@ -109,6 +109,15 @@ def main():
         print(name, out[name + "_rgb"].shape, float(out[name + "_rgb"].mean()), bytes(out[name + "_md5"]).decode())
     np.savez_compressed(os.path.join(HERE, "pins_hw5_render.npz"), **out)
     save_reference_crops()
+    save_env_uv()
+
+
+def save_env_uv():
+    """The environment-map uv of a miss (hw8/src/scene.cpp:94-95) evaluated on the reference's own Ray / Vec3."""
+    d = pin_cases.env_uv_directions()
+    uv = oracle_lib.env_uv(C.CDLL(oracle_lib.ref_path("libref_hw8.so")), "ref8_env_uv", d)
+    np.savez_compressed(os.path.join(HERE, "pins_env_uv.npz"), d=d, uv=uv)
+    print("env uv", d.shape)
 
 
 def save_function_inputs():

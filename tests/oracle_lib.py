@@ -196,6 +196,19 @@ def tonemap(impl_lib, name, rgb):
     return out
 
 
+def env_uv(impl_lib, name, d):
+    """The environment-map uv (n x 2 float32) of directions d (n x 3) through impl_lib's `name`(d, uv, n): rto_hw8_env_uv (the
+    oracle), ref8_env_uv (the reference's scene.cpp:94-95 on its own types) or rtt_env_uv (the device)."""
+    d = np.ascontiguousarray(d, np.float32)
+    uv = np.zeros((d.shape[0], 2), np.float32)
+    fn = getattr(impl_lib, name)
+    fn.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+    fn.restype = C.c_int if name.startswith("rtt_") else None     # the test hooks report hip errors
+    rc = fn(d.ctypes.data, uv.ctypes.data, d.shape[0])
+    assert not rc, rc
+    return uv
+
+
 def _setup_hw6(L):
     if getattr(L, "_hw6_ready", False):
         return

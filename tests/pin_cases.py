@@ -127,6 +127,53 @@ def tonemap_inputs(seed=6, k=3000):
     return x.astype(np.float32)
 
 
+def env_uv_directions(seed=29, k=20000):
+    """Directions for the environment-map uv (hw8/src/scene.cpp:94-95): k random unit vectors, then the edges of atan2f / asinf
+    (float32, n x 3).  The edges: the six axes with both signs of zero beside them; the seam (d.z = +-0 with d.x < 0); the poles and
+    the floats just below 1 in magnitude; asinf's branch points (|d.y| = 0.5, 0x3F79999A, 2^-27); atanf's reduction boundaries
+    (|d.z / d.x| at 7/16, 11/16, 19/16, 39/16, 2^25, 2^26 and beyond) and denormal components."""
+    rng = np.random.default_rng(seed)
+    v = rng.normal(size=(k, 3))
+    dirs = [(v / np.linalg.norm(v, axis=1, keepdims=True)).astype(np.float32)]
+    f = lambda bits: np.array(bits, np.uint32).view(np.float32)
+    near = lambda x, m=4: f(np.float32(x).view(np.uint32) + np.arange(-m, m + 1))     # x and its m float neighbours on either side
+    edge = []
+    for a in range(3):                                            # the axes, with both signs of zero in the other two components
+        for s in (1.0, -1.0):
+            for z1 in (0.0, -0.0):
+                for z2 in (0.0, -0.0):
+                    p = [z1, z2]
+                    p.insert(a, s)
+                    edge.append(p)
+    for zs in (0.0, -0.0):                                        # the seam: d.z = +-0, d.x < 0
+        for y in (0.0, -0.0, 0.25, -0.6, 0.999, -0.999999):
+            edge.append([-np.sqrt(1 - y * y), y, zs])
+        for x in (-1e-30, -1e-45, -0.5, -2.0 ** -130):
+            edge.append([x, 0.5, zs])
+    ys = np.concatenate([near(1.0, 64), near(0.5, 8), f([0x3F79999A + i for i in range(-8, 9)]), near(2.0 ** -27, 4), f([0x32000000]),
+                         np.float32([2.0 ** -28, 2.0 ** -126, 2.0 ** -140, 1e-45, 0.975, 0.9749999])])
+    ys = ys[(ys <= 1) & (ys > 0)]
+    for y in ys:                                                  # poles and asinf's branch points, both signs, x / z around the ring
+        for sy in (1.0, -1.0):
+            r = np.sqrt(max(0.0, 1.0 - float(y) ** 2))
+            for phi in (0.0, 2.1, -2.7):
+                edge.append([r * np.cos(phi), sy * float(y), r * np.sin(phi)])
+    ratios = np.concatenate([near(7 / 16), near(11 / 16), near(19 / 16), near(39 / 16), near(2.0 ** 25), near(2.0 ** 26), near(2.0 ** 27),
+                             np.float32([2.0 ** 40, 2.0 ** 100, 2.0 ** -27, 2.0 ** -29, 2.0 ** -30, 1.0])])
+    for r in ratios:                                              # atanf's reduction boundaries: |d.z / d.x| = r in all four quadrants
+        for sx in (1.0, -1.0):
+            for sz in (1.0, -1.0):
+                x = np.float32(sx / np.sqrt(1.0 + float(r) ** 2))
+                edge.append([x, 0.1, np.float32(sz * abs(x) * r)])
+                edge.append([np.float32(sx * 0.3), 0.2, np.float32(sz * 0.3 * r)])
+    for dn in (1e-45, 3e-39, 2.0 ** -127, 2.0 ** -149 * 12345):      # denormal components
+        for s in (1.0, -1.0):
+            edge += [[s * dn, 0.3, -0.9], [-0.9, 0.3, s * dn], [0.6, s * dn, 0.8], [s * dn, 1.0, s * dn], [s * dn, -1.0, -s * dn],
+                     [s * dn, 0.0, -dn], [-dn, 0.0, s * dn], [s * dn, s * dn, s * dn], [-1.0, 0.0, s * dn]]
+    dirs.append(np.array(edge, np.float64).astype(np.float32))
+    return np.ascontiguousarray(np.concatenate(dirs))
+
+
 def load_hw6(name):
     return rt.load_gltf(os.path.join(SCENES, "hw6", name + ".gltf"), rt.RT_INTEGRATOR_HW6)
 

@@ -1,5 +1,6 @@
 """Device building blocks against the host libraries the reference links: rt_logf vs glibc logf (the reference's
-normal_distribution calls std::log(float)), and the device minstd/uniform/normal streams vs libstdc++."""
+normal_distribution calls std::log(float)), rt_asinf / rt_atan2f vs glibc asinf / atan2f and the miss shader's environment-map uv
+vs the reference's (scene.cpp:94-95 on float Vec3), and the device minstd/uniform/normal streams vs libstdc++."""
 import ctypes as C
 import os
 
@@ -7,6 +8,7 @@ import numpy as np
 import pytest
 
 import oracle_lib
+import pin_cases
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -17,7 +19,88 @@ def hooks():
     L = C.CDLL(os.path.join(ROOT, "raytracing-course-hw_amd", "librtamd_testhooks.so"))
     L.rtt_logf.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
     L.rtt_rng_streams.argtypes = [C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_void_p]
+    L.rtt_asinf.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+    L.rtt_atan2f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
     return L
+
+
+def _same_bits_or_both_nan(a, b):
+    """Per element: identical bits, or both NaN (libm's NaN payloads are not part of the contract)."""
+    return (a.view(np.uint32) == b.view(np.uint32)) | (np.isnan(a) & np.isnan(b))
+
+
+def _report_diff(name, args, dev, host):
+    ok = _same_bits_or_both_nan(dev, host)
+    bad = np.flatnonzero(~ok)
+    print(f"{name}: {dev.size} inputs, {bad.size} differ from the host libm")
+    for i in bad[:5]:
+        print(f"  {name}({', '.join(float(a[i]).hex() for a in args)}) = device {float(dev[i]).hex()} host {float(host[i]).hex()}")
+    return bad.size
+
+
+# Special values of atan2f: zeros, infinities, NaN, denormals, 1 (atan2f's x == 1 shortcut) and atanf's thresholds with a neighbour.
+_SPECIAL_BITS = [0, 1, 2, 0x007FFFFF, 0x00800000, 0x3F800000, 0x3F7FFFFF, 0x3F800001, 0x7F7FFFFF, 0x7F800000, 0x7FC00000,
+                 0x4C000000, 0x4BFFFFFF, 0x4C800000, 0x31000000, 0x30FFFFFF, 0x3EE00000, 0x3EDFFFFF, 0x3F300000, 0x3F2FFFFF,
+                 0x3F980000, 0x3F97FFFF, 0x401C0000, 0x401BFFFF, 0x40490FDB, 0x0D000000, 0x1A000000, 0x33000000]
+
+
+def test_device_asinf_is_bit_identical_to_host_libm(hooks):
+    """rt_asinf vs the host's asinf (what std::asin(float) calls in scene.cpp:95): every float in [-1, 1] at a stride of 61 bit
+    patterns (odd, so every low-bit residue occurs), the branch points 0.5, 0x3F79999A and 2^-27 with their neighbours, +-1, and 10^6
+    random bit patterns (mostly |x| > 1 and NaN, where only NaN-ness is compared)."""
+    pos = np.concatenate([np.arange(0, 0x3F800001, 61, dtype=np.uint32), np.uint32([0x3F800000, 0x3F7FFFFF])])
+    for b in (0x3F000000, 0x3F79999A, 0x32000000):
+        pos = np.concatenate([pos, np.arange(b - 64, b + 65, dtype=np.uint32)])
+    rnd = np.random.default_rng(41).integers(0, 1 << 32, 1_000_000, dtype=np.uint64).astype(np.uint32)
+    bits = np.concatenate([pos, pos | np.uint32(0x80000000), rnd])
+    x = bits.view(np.float32)
+    dev = np.zeros_like(x)
+    assert hooks.rtt_asinf(x.ctypes.data, dev.ctypes.data, x.size) == 0
+    host = np.zeros_like(x)
+    L = oracle_lib.lib()
+    L.rto_asinf_array.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+    L.rto_asinf_array(x.ctypes.data, host.ctypes.data, x.size)
+    assert np.isnan(host).sum() > 500_000 and (np.abs(x) <= 1).sum() > 30_000_000     # the sets cover what they claim
+    assert _report_diff("asinf", [x], dev, host) == 0
+
+
+def test_device_atan2f_is_bit_identical_to_host_libm(hooks):
+    """rt_atan2f vs the host's atan2f (what std::atan2(float, float) calls in scene.cpp:94) on 4.4 million pairs: random bit patterns,
+    components of random unit vectors (what the miss shader passes), the env-uv edge directions (seam, poles, atanf's reduction
+    boundaries, denormals) and every pairing of the special values with each other and with random floats of every exponent."""
+    rng = np.random.default_rng(43)
+    n = 2_000_000
+    rb = rng.integers(0, 1 << 32, (n, 2), dtype=np.uint64).astype(np.uint32).view(np.float32)
+    v = rng.normal(size=(n, 3))
+    v = (v / np.linalg.norm(v, axis=1, keepdims=True)).astype(np.float32)
+    d = pin_cases.env_uv_directions()
+    special = np.uint32(_SPECIAL_BITS)
+    special = np.concatenate([special, special | np.uint32(0x80000000)]).view(np.float32)
+    expo = rng.integers(0, 255, 4000).astype(np.uint32)
+    anyexp = ((expo << 23) | (rng.integers(0, 1 << 32, 4000, dtype=np.uint64).astype(np.uint32) & np.uint32(0x807FFFFF))).view(np.float32)
+    pool = np.concatenate([special, anyexp])
+    sy, sx = np.meshgrid(special, pool, indexing="ij")
+    ys = np.concatenate([rb[:, 0], v[:, 2], d[:, 2], sy.ravel(), sx.ravel()])
+    xs = np.concatenate([rb[:, 1], v[:, 0], d[:, 0], sx.ravel(), sy.ravel()])
+    ys, xs = np.ascontiguousarray(ys, np.float32), np.ascontiguousarray(xs, np.float32)
+    assert ys.size >= 4_000_000
+    dev = np.zeros_like(ys)
+    assert hooks.rtt_atan2f(ys.ctypes.data, xs.ctypes.data, dev.ctypes.data, ys.size) == 0
+    host = np.zeros_like(ys)
+    L = oracle_lib.lib()
+    L.rto_atan2f_array.argtypes = [C.c_void_p] * 3 + [C.c_size_t]
+    L.rto_atan2f_array(ys.ctypes.data, xs.ctypes.data, host.ctypes.data, ys.size)
+    assert _report_diff("atan2f", [ys, xs], dev, host) == 0
+
+
+def test_device_env_uv_matches_reference_golden(hooks):
+    """The miss shader's uv (rt_kernels_hw8.h env_uv) against tests/golden/pins_env_uv.npz: the reference's scene.cpp:94-95 on its
+    own Ray / Vec3, bit for bit, random directions and the edge set."""
+    g = np.load(os.path.join(ROOT, "tests", "golden", "pins_env_uv.npz"))
+    uv = oracle_lib.env_uv(hooks, "rtt_env_uv", g["d"])
+    bad = np.flatnonzero((uv.view(np.uint32) != g["uv"].view(np.uint32)).any(axis=1))
+    print(f"env uv: {g['d'].shape[0]} directions, {bad.size} differ from the reference")
+    assert bad.size == 0, (g["d"][bad[:5]].tolist(), uv[bad[:5]].tolist(), g["uv"][bad[:5]].tolist())
 
 
 def test_device_logf_is_bit_identical_to_host_libm(hooks):

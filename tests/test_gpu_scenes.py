@@ -139,6 +139,50 @@ def test_environment_map_miss_shader(rt, sphere_scene, kernel):
     scene.close()
 
 
+# Cameras for the all-miss scene: (name, forward, right, up, fov_y).  The 2^-149 axes (the smallest denormal) make cx * right and
+# cy * up round to +-0 wherever |cx|, |cy| < 0.5 and to +-2^-149 beyond, so whole blocks of pixels look exactly along the seam
+# (d.z = +-0 with d.x < 0, both signs of zero) or exactly at a pole (d.y = +-1), with denormal components beside them.
+_TINY = float(np.float32(2.0 ** -149))
+_MISS_CAMERAS = [
+    ("seam -x", (-1.0, 0.0, -0.0), (0.0, 0.0, _TINY), (0.0, 1.0, 0.0), 1.2),
+    ("pole +y", (0.0, 1.0, 0.0), (_TINY, 0.0, 0.0), (0.0, 0.0, _TINY), 1.2),
+    ("pole -y", (-0.0, -1.0, -0.0), (_TINY, 0.0, 0.0), (0.0, 0.0, _TINY), 1.2),
+    ("near seam -x", (-1.0, 0.0, 0.0), (0.0, 0.0, 1.0), (0.0, 1.0, 0.0), 2.6),
+    ("near pole +y", (0.0, 1.0, 0.0), (1.0, 0.0, 0.0), (0.0, 0.0, 1.0), 1.0),
+]
+
+
+@pytest.mark.parametrize("cam", _MISS_CAMERAS, ids=[c[0].replace(" ", "_") for c in _MISS_CAMERAS])
+def test_all_miss_environment_lookup_is_bit_exact(rt, kernel, cam):
+    """Every primary ray misses (one small triangle behind the camera), so each pixel is the environment map at the reference's uv
+    (scene.cpp:94-95: atan2f / asinf of float components) and no pipeline has a box decision to make: bit-exact floats and bytes on
+    all three.  The map is 512x256 random bytes, so a 1-ulp change of a coordinate moves the bilinear weights.  At the seam with
+    d.z = -0 and at d.y = +1 the float overloads give a coordinate just below 0 that wraps to 1.0f: the texel index is then the
+    image's width or height, where the reference reads past its image on the last row (undefined); the product and the oracle read 0."""
+    name, fwd, right, up, fov = cam
+    rng = np.random.default_rng(8)
+    env = rng.integers(0, 256, (256, 512, 3)).astype(np.uint8)
+    tri = (-10.0 * np.array(fwd, np.float64) + np.array([[0.1, 0.0, 0.0], [0.0, 0.1, 0.0], [0.0, 0.0, 0.1]])).astype(np.float32)
+    m = rt.rt_material()
+    m.base_color, m.roughness_factor = (0.8, 0.8, 0.8), 0.5
+    m.base_color_texture = m.emissive_texture = m.metallic_roughness_texture = m.normal_texture = -1
+    c = rt.rt_camera()
+    c.position, c.forward, c.right, c.up, c.fov_y = (0.0, 0.0, 0.0), fwd, right, up, fov
+    tan = np.array([1, 0, 0, 1] * 3, np.float32)
+    sd = rt.SceneData(tri.reshape(1, 9), np.zeros(6, np.float32), np.tile(np.float32([0, 0, 1]), 3), tan, np.zeros(1, np.uint32), [m],
+                      camera=c, environment=env)
+    scene = rt.Scene(sd)
+    rgb, rgb8, _ = scene.render(40, 32, 3)
+    ref, ref8, _ = oracle_lib.Hw8Oracle(sd).render(40, 32, 3)
+    _report(f"all-miss {name}[{kernel}] 40x32x3", rgb, ref, rgb8, ref8)
+    if name == "pole +y":
+        assert not ref.any()           # every ray straight up: the row past the image, read as 0
+    else:
+        assert len(np.unique(ref.reshape(-1, 3), axis=0)) > 20
+    assert _exact(rgb, ref, rgb8, ref8)
+    scene.close()
+
+
 @pytest.mark.parametrize("world", [2, 3])
 def test_sharded_render_is_bit_identical(rt, small_room, world):
     """Multi-GPU layout on one GPU: every shard rendered separately, assembled, compared with the unsharded frame."""

@@ -195,9 +195,19 @@ def test_goldens_are_current_with_live_reference():
     asked = np.load(os.path.join(GOLD, "pins_hw8_functions_soup_inputs.npz"))
     for k, v in pin_cases.function_inputs(sd, 23).items():
         assert same(v, asked[k]), k
+    env = np.load(os.path.join(GOLD, "pins_env_uv.npz"))
+    assert same(env["d"], pin_cases.env_uv_directions()), "pins_env_uv.npz"
     if oracle_lib.ref_path("libref_hw8.so") is None:
         return
     live = pin_cases.eval_functions(oracle_lib.Ref8(sd), sd, 23)
     gold = np.load(os.path.join(GOLD, "pins_hw8_functions_soup.npz"))
     for k in live:
         assert same(live[k], gold[k]), k
+    L8 = C.CDLL(oracle_lib.ref_path("libref_hw8.so"))
+    if not hasattr(L8, "ref8_env_uv"):
+        # a harness prebuilt from an older oracle/ref/ref_hw8_funcs.cpp (no reference sources here to rebuild it) cannot answer the
+        # env-uv case; the oracle is still held to the golden by tests/test_env_uv.py
+        print("oracle/_ref/libref_hw8.so predates ref8_env_uv: pins_env_uv.npz not re-evaluated live")
+        return
+    live_uv = oracle_lib.env_uv(L8, "ref8_env_uv", env["d"])
+    assert same(live_uv, env["uv"]), "pins_env_uv.npz"
