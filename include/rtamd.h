@@ -240,6 +240,54 @@ int rt_render(rt_scene *scene, const rt_render_params *params,
 int rt_unshard(const rt_render_params *params, const void *shard_buf, size_t elem_size,
                void *full_image);
 
+/* ---- resumable renders: advance a frame in slices of samples --------------------------------------------------------------
+ * A pixel is the sum of its samples, drawn in order from its one engine, times (float)(1.0 / samples).  An rt_accum keeps that
+ * sum and the engine per pixel on the scene's GPU between calls, so a frame can be shown while it converges, continued later
+ * ("64 more samples") and checkpointed.  A frame rendered in ANY number of slices is bit for bit the frame of one
+ * rt_render call, floats and bytes, and the picture after d samples is bit for bit rt_render(samples = d): the same additions
+ * in the same order, the factor applied once at the end.
+ *
+ * Replay mode only (sample_streams 0 or 1), RT_INTEGRATOR_HW8 / HW7 / HW6 on the pipelines they use by default (both
+ * persistent kernels and the round pipeline).  The megakernels (RTAMD_KERNEL=mega, trees beyond the other pipelines' limits),
+ * hw1 .. hw5 and throughput mode answer RT_ERR_UNSUPPORTED; there is no fallback.  Several rt_accum may exist per scene, and
+ * rt_render on the scene between two slices disturbs none of them; like all calls on one rt_scene they are serialised by the
+ * caller.  Destroy every rt_accum before its scene.
+ *
+ * rt_accum_create   params as for rt_render (width, height, ray_depth, integrator, tile_w/h, shard_index/count, stream);
+ *                   params->samples is ignored; flags other than RT_FLAG_COUNTERS -> RT_ERR_UNSUPPORTED.
+ * rt_accum_render   every pixel draws n_samples more samples.  rt_stats as rt_render reports them, samples = pixels x
+ *                   n_samples.  The total per pixel stays below 2^25 (hw6: 2^24), the sample index field of a path record:
+ *                   a slice that would cross it is RT_ERR_LIMIT and leaves the state as it was.  A slice that fails under
+ *                   way (launch deadline, HIP error) leaves the rt_accum broken: every later call fails with that first
+ *                   error's message.  Cost of slicing: every slice pays its launches, the kernels' init blocks and the exit
+ *                   spread of the workgroups, and reads and writes the state once (2 x 24 bytes per pixel slot); the first
+ *                   sixteenth of every slice runs under the round-robin deal.  Measured on one MI355X, 1920x1080x256 on
+ *                   synth_room_v1, one resolve to the host per slice included: 4 slices of 64 samples take 2.9 % longer than the
+ *                   one-shot rt_render (290 ms of kernels per slice), 16 slices of 16 take 15.5 % longer (80 ms per slice);
+ *                   DESIGN.md section 4, profiles/r05_sliced_render.txt.
+ * rt_accum_samples  samples per pixel so far.
+ * rt_accum_resolve  the picture of the state: (float)(1.0 / d) * sum and its tonemapped bytes, in rt_render's output layout
+ *                   (sharded or not, padding of border tiles zeroed).  flags: RT_FLAG_OUT_DEVICE.  d == 0 is
+ *                   RT_ERR_INVALID_ARG.  The state is only read.
+ * rt_accum_state_bytes / rt_accum_save / rt_accum_load   a checkpoint in host memory.  The blob is little-endian: a 128-byte
+ *                   header of 32-bit words {magic "RTAC", format version, header bytes, bytes per pixel slot, width, height,
+ *                   integrator, effective ray depth, tile_w, tile_h, shard_index, shard_count, pixel slots, samples so far,
+ *                   triangle count, light count, FNV-1a hash of the scene's light order, zeros}, then per pixel slot of the
+ *                   shard (64 per 8x8 sub-tile, border padding included) {sum r, g, b as float, engine state x}, then per
+ *                   pixel slot {the normal distribution's saved value as float, 1 if it is available else 0}: 24 bytes per
+ *                   slot.  The engine is the one BEFORE the camera ray of the next sample is drawn.  rt_accum_load rejects
+ *                   a blob whose header differs from the rt_accum's in anything but the samples, and a truncated one, with
+ *                   RT_ERR_INVALID_ARG and a message naming the field.  rt_accum_state_bytes needs no GPU; 0 = bad params. */
+typedef struct rt_accum rt_accum;
+int rt_accum_create(rt_scene *scene, const rt_render_params *params, rt_accum **out);
+int rt_accum_render(rt_accum *accum, int32_t n_samples, rt_stats *stats /* nullable */);
+int rt_accum_samples(const rt_accum *accum);
+int rt_accum_resolve(rt_accum *accum, uint32_t flags, float *out_rgb_linear /* nullable */, uint8_t *out_rgb8 /* nullable */);
+size_t rt_accum_state_bytes(const rt_render_params *params);
+int rt_accum_save(rt_accum *accum, void *blob, size_t capacity);
+int rt_accum_load(rt_accum *accum, const void *blob, size_t size);
+void rt_accum_destroy(rt_accum *accum);
+
 /* ---- several GPUs in one process ---------------------------------------------------------------------------------------
  * The reference shards nothing (one OpenMP loop over the pixels, hw8/src/sceneio.cpp:387-396, driven from main,
  * hw8/src/main.cpp:7-18); pixels are independent and seeded by their global index, so the frame's 32x32 tiles are dealt

@@ -9,6 +9,7 @@ The package directory name contains a hyphen, so import it with
 """
 import ctypes as C
 import os
+import weakref
 
 import numpy as np
 
@@ -21,7 +22,7 @@ RT_FLAG_OUT_DEVICE, RT_FLAG_COUNTERS, RT_FLAG_SAMPLE_SEEDS, RT_FLAG_RUSSIAN_ROUL
 RT_BUILD_DEVICE_BVH = 1
 RT_PIPELINE_SINGLE, RT_PIPELINE_ROUNDS, RT_PIPELINE_PERSISTENT = 0, 1, 2
 RT_OK = 0
-RT_ERR_NO_DEVICE = -2
+RT_ERR_INVALID_ARG, RT_ERR_NO_DEVICE, RT_ERR_HIP, RT_ERR_UNSUPPORTED, RT_ERR_LIMIT = -1, -2, -3, -4, -7
 
 
 class RtError(RuntimeError):
@@ -99,7 +100,8 @@ ABI_SYMBOLS = ["rt_abi_version", "rt_last_error", "rt_scene_create", "rt_scene_d
                "rt_unshard", "rt_scene_get_info", "rt_scene_get_light_order", "rt_load_gltf", "rt_load_txt",
                "rt_host_scene_set_environment", "rt_host_scene_desc", "rt_host_scene_free", "rt_write_ppm",
                "rt_decode_png", "rt_free", "rt_host_prepare_orders", "rt_device_count", "rt_multi_create", "rt_multi_render",
-               "rt_multi_destroy"]
+               "rt_multi_destroy", "rt_accum_create", "rt_accum_render", "rt_accum_samples", "rt_accum_resolve",
+               "rt_accum_state_bytes", "rt_accum_save", "rt_accum_load", "rt_accum_destroy"]
 
 if not os.path.exists(LIB_PATH):
     raise ImportError(f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
@@ -131,6 +133,16 @@ lib.rt_multi_create.argtypes = [C.POINTER(rt_scene_desc), C.POINTER(C.c_int), C.
 lib.rt_multi_render.argtypes = [C.c_void_p, C.POINTER(rt_render_params), C.c_void_p, C.c_void_p, C.POINTER(rt_stats)]
 lib.rt_multi_destroy.argtypes = [C.c_void_p]
 lib.rt_multi_destroy.restype = None
+lib.rt_accum_create.argtypes = [C.c_void_p, C.POINTER(rt_render_params), C.POINTER(C.c_void_p)]
+lib.rt_accum_render.argtypes = [C.c_void_p, C.c_int32, C.POINTER(rt_stats)]
+lib.rt_accum_samples.argtypes = [C.c_void_p]
+lib.rt_accum_resolve.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
+lib.rt_accum_state_bytes.argtypes = [C.POINTER(rt_render_params)]
+lib.rt_accum_state_bytes.restype = C.c_size_t
+lib.rt_accum_save.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+lib.rt_accum_load.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
+lib.rt_accum_destroy.argtypes = [C.c_void_p]
+lib.rt_accum_destroy.restype = None
 
 
 def _check(code):
@@ -326,17 +338,73 @@ class MultiScene:
         return rgb, rgb8, st
 
 
+class Accumulator:
+    """A frame in progress on a Scene (rt_accum): render(n) draws n more samples per pixel, resolve() is the picture so far,
+    bit for bit Scene.render(width, height, samples); save() / load() move the state through host memory."""
+
+    def __init__(self, scene, width, height, **kw):
+        self.scene = scene  # keeps the scene alive: an rt_accum is destroyed before its scene
+        self.params = make_params(width, height, 0, **kw)
+        self._h = C.c_void_p()
+        _check(lib.rt_accum_create(scene._h, C.byref(self.params), C.byref(self._h)))
+        scene._accums.add(self)
+
+    def close(self):
+        if self._h:
+            lib.rt_accum_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def samples(self):
+        return _check(lib.rt_accum_samples(self._h))
+
+    def render(self, n_samples):
+        st = rt_stats()
+        _check(lib.rt_accum_render(self._h, n_samples, C.byref(st)))
+        return st
+
+    def resolve(self, want_float=True, want_rgb8=True):
+        """(rgb float32, rgb8) in Scene.render's layout: (H, W, 3), or the compact shard buffers."""
+        p = rt_render_params.from_buffer_copy(self.params)
+        p.samples = 1
+        n = lib.rt_output_elems(C.byref(p))
+        rgb = np.zeros(n, dtype=np.float32) if want_float else None
+        rgb8 = np.zeros(n, dtype=np.uint8) if want_rgb8 else None
+        _check(lib.rt_accum_resolve(self._h, 0, rgb.ctypes.data if want_float else None, rgb8.ctypes.data if want_rgb8 else None))
+        if p.shard_count <= 1:
+            rgb = None if rgb is None else rgb.reshape(p.height, p.width, 3)
+            rgb8 = None if rgb8 is None else rgb8.reshape(p.height, p.width, 3)
+        return rgb, rgb8
+
+    def save(self):
+        buf = C.create_string_buffer(lib.rt_accum_state_bytes(C.byref(self.params)))
+        _check(lib.rt_accum_save(self._h, buf, len(buf)))
+        return buf.raw
+
+    def load(self, blob):
+        _check(lib.rt_accum_load(self._h, blob, len(blob)))
+
+
 class Scene:
     """A prepared scene resident in HBM on the current HIP device (rt_scene)."""
 
     def __init__(self, data, build_flags=0):
         self.data = data
         self._h = C.c_void_p()
+        self._accums = weakref.WeakSet()
         desc = rt_scene_desc.from_buffer_copy(data.desc)   # the arrays stay owned by `data`
         desc.build_flags = build_flags
         _check(lib.rt_scene_create(C.byref(desc), C.byref(self._h)))
 
     def close(self):
+        for a in list(self._accums):  # an rt_accum goes before its scene
+            a.close()
         if self._h:
             lib.rt_scene_destroy(self._h)
             self._h = C.c_void_p()
@@ -373,6 +441,10 @@ class Scene:
             rgb = None if rgb is None else rgb.reshape(height, width, 3)
             rgb8 = None if rgb8 is None else rgb8.reshape(height, width, 3)
         return rgb, rgb8, st
+
+    def accumulator(self, width, height, **kw):
+        """A resumable render of this scene (Accumulator); keywords as make_params."""
+        return Accumulator(self, width, height, **kw)
 
     def render_device(self, params, out_rgb_ptr, out_rgb8_ptr):
         """Render into device buffers (raw pointers, e.g. torch tensor data_ptr())."""

@@ -6,6 +6,9 @@
 // The host only parses, prepares and writes the PPM; the render loop runs on the GPU through the C-ABI — on EVERY visible GPU
 // when there are several (rt_multi_*: tiles dealt round-robin, one exchange step to the first device; RTAMD_DEVICES=n limits
 // the count, RTAMD_DEVICES=1 forces the single-device path).
+// Progressive renders of the glTF surface (rt_accum_*, one device): RTAMD_SLICE=n renders in slices of n samples and rewrites the PPM
+// after every slice; RTAMD_CHECKPOINT=path carries on from that file when it exists and writes it after every slice (both files are
+// written under a temporary name and renamed, so a reader never sees half a file); RTAMD_SLICE_LIMIT=k stops after k slices.
 #include "../../../include/rtamd.h"
 #include <cstdio>
 #include <cstdlib>
@@ -16,6 +19,66 @@
 static int die() {
     fprintf(stderr, "error: %s\n", rt_last_error());
     return 1;
+}
+
+static bool write_file_atomically(const std::string &path, const void *data, size_t size) {
+    const std::string tmp = path + ".part";
+    FILE *f = fopen(tmp.c_str(), "wb");
+    if (!f) return false;
+    const bool ok = fwrite(data, 1, size, f) == size;
+    if (fclose(f) != 0 || !ok || rename(tmp.c_str(), path.c_str()) != 0) { remove(tmp.c_str()); return false; }
+    return true;
+}
+
+// The frame in slices: the picture after every slice is the frame of that many samples, the last one the frame of the plain run.
+static int render_in_slices(rt_scene *scene, const rt_render_params &p, int slice, const char *checkpoint, const char *out_path, std::vector<uint8_t> &rgb8) {
+    rt_accum *acc = nullptr;
+    if (rt_accum_create(scene, &p, &acc) != RT_OK) return die();
+    std::vector<uint8_t> blob(checkpoint ? rt_accum_state_bytes(&p) : 0);
+    if (checkpoint) {
+        if (FILE *f = fopen(checkpoint, "rb")) {
+            std::vector<uint8_t> in(blob.size() + 1);
+            const size_t got = fread(in.data(), 1, in.size(), f);
+            fclose(f);
+            if (rt_accum_load(acc, in.data(), got) != RT_OK) { fprintf(stderr, "error: checkpoint %s does not match this command line: %s\n", checkpoint, rt_last_error()); return 1; }
+            if (got != blob.size()) { fprintf(stderr, "error: checkpoint %s has %zu bytes where this frame's has %zu\n", checkpoint, got, blob.size()); return 1; }
+            if (rt_accum_samples(acc) > p.samples) { fprintf(stderr, "error: checkpoint %s holds %d samples, more than the %d asked for\n", checkpoint, rt_accum_samples(acc), p.samples); return 1; }
+            fprintf(stderr, "checkpoint: %s loaded, %d of %d samples done\n", checkpoint, rt_accum_samples(acc), p.samples);
+        }
+    }
+    const int limit = getenv("RTAMD_SLICE_LIMIT") ? atoi(getenv("RTAMD_SLICE_LIMIT")) : 0;
+    const std::string tmp_ppm = std::string(out_path) + ".part";
+    double kernel_ms = 0;
+    uint64_t samples = 0;
+    uint32_t exact = 1;
+    for (int k = 0;; k++) {
+        const int done = rt_accum_samples(acc);
+        if (k > 0 || done == p.samples) { // the picture so far (a checkpoint that already holds the frame just resolves)
+            if (rt_accum_resolve(acc, 0, nullptr, rgb8.data()) != RT_OK) return die();
+            if (rt_write_ppm(tmp_ppm.c_str(), p.width, p.height, rgb8.data()) != RT_OK) return die();
+            if (rename(tmp_ppm.c_str(), out_path) != 0) { fprintf(stderr, "error: cannot rename %s to %s\n", tmp_ppm.c_str(), out_path); return 1; }
+        }
+        if (done == p.samples) break;
+        if (limit > 0 && k >= limit) {
+            fprintf(stderr, "STOPPED after %d slices at %d of %d samples\n", k, done, p.samples);
+            rt_accum_destroy(acc);
+            return -1;
+        }
+        const int n = slice > 0 && slice < p.samples - done ? slice : p.samples - done;
+        rt_stats st;
+        if (rt_accum_render(acc, n, &st) != RT_OK) return die();
+        kernel_ms += st.kernel_ms; samples += st.samples; exact &= st.reference_exact;
+        fprintf(stderr, "slice %d: %d samples (%d of %d), %.3f ms on the GPU\n", k + 1, n, done + n, p.samples, st.kernel_ms);
+        if (checkpoint) {
+            if (rt_accum_save(acc, blob.data(), blob.size()) != RT_OK) return die();
+            if (!write_file_atomically(checkpoint, blob.data(), blob.size())) { fprintf(stderr, "error: cannot write checkpoint %s\n", checkpoint); return 1; }
+        }
+    }
+    if (samples) fprintf(stderr, "render: %.3f ms on the GPU, %.2f Msamples/s\n", kernel_ms, samples / (kernel_ms * 1e3));
+    if (samples && !exact)
+        fprintf(stderr, "note: this render kept the answers of the walkers' padded boxes (no exactness gate on this path: see rt_stats.reference_exact in rtamd.h); about one pixel in 1e5 may differ from the reference's\n");
+    rt_accum_destroy(acc);
+    return 0;
 }
 
 int main(int argc, const char *argv[]) {
@@ -56,6 +119,14 @@ int main(int argc, const char *argv[]) {
     rt_stats st;
     int n_dev = rt_device_count();
     if (const char *e = getenv("RTAMD_DEVICES")) { int v = atoi(e); if (v >= 1 && v < n_dev) n_dev = v; }
+    const int slice = getenv("RTAMD_SLICE") ? atoi(getenv("RTAMD_SLICE")) : 0;
+    const char *checkpoint = getenv("RTAMD_CHECKPOINT");
+    const bool sliced = argc >= 6 && (getenv("RTAMD_SLICE") || checkpoint);
+    if (sliced && slice <= 0 && getenv("RTAMD_SLICE")) { fprintf(stderr, "error: RTAMD_SLICE must be a positive number of samples\n"); return 1; }
+    if (sliced && n_dev > 1) {
+        fprintf(stderr, "note: RTAMD_SLICE / RTAMD_CHECKPOINT render on one device (%d are visible)\n", n_dev);
+        n_dev = 1;
+    }
     if (n_dev > 1 && p.integrator != RT_INTEGRATOR_HW1) {
         rt_multi *multi = nullptr;
         if (rt_multi_create(&desc, nullptr, n_dev, &multi) != RT_OK) return die();
@@ -65,6 +136,13 @@ int main(int argc, const char *argv[]) {
     } else {
         rt_scene *scene = nullptr;
         if (rt_scene_create(&desc, &scene) != RT_OK) return die();
+        if (sliced) {
+            const int rc = render_in_slices(scene, p, slice, checkpoint, out_path, rgb8);
+            rt_scene_destroy(scene);
+            rt_host_scene_free(hs);
+            if (rc == 0) fprintf(stderr, "FINISH\n");
+            return rc < 0 ? 0 : rc; // < 0: stopped by RTAMD_SLICE_LIMIT, the checkpoint and the picture so far are written
+        }
         if (rt_render(scene, &p, nullptr, rgb8.data(), &st) != RT_OK) return die();
         fprintf(stderr, "render: %.3f ms on the GPU, %.2f Msamples/s\n", st.kernel_ms, st.samples / (st.kernel_ms * 1e3));
         if ((p.integrator == RT_INTEGRATOR_HW8 || p.integrator == RT_INTEGRATOR_HW7 || p.integrator == RT_INTEGRATOR_HW6) && !st.reference_exact)

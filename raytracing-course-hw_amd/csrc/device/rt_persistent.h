@@ -1008,7 +1008,9 @@ __global__ __launch_bounds__(P8_THREADS, P8_PER_CU) void pt_persistent_kernel(Sc
                 if (started) atomicOr(&sh.pending[l >> 4], PT_BIT_T << ((l & 15u) * 2u));
             } else {
                 Rng rng;
-                rng_seed(rng, (uint32_t)(y * R.width + x) + (R.streams > 1 ? (gslot / R.n_pixslots) * R.seed_stride : 0u)); // sceneio.cpp:389-391
+                F3 sum = f3(0.f, 0.f, 0.f);
+                if (R.accum) accum_enter(R, gslot, rng, sum);   // a slice of a resumable render: carry on at sample R.sample_first
+                else rng_seed(rng, (uint32_t)(y * R.width + x) + (R.streams > 1 ? (gslot / R.n_pixslots) * R.seed_stride : 0u)); // sceneio.cpp:389-391
                 if (R.sample_seeds) wf_sample_seed(R, rng, gslot, x, y, 0u);
                 F3 o, d;
                 wf_camera_ray(S, R, rng, x, y, o, d);
@@ -1016,7 +1018,7 @@ __global__ __launch_bounds__(P8_THREADS, P8_PER_CU) void pt_persistent_kernel(Sc
                 r[0] = make_float4(o.x, o.y, o.z, d.x);
                 r[1] = make_float4(d.y, d.z, __uint_as_float(rng.x), rng.saved);
                 r[2] = make_float4(0.f, 0.f, 0.f, 0.f);
-                r[3] = make_float4(0.f, 0.f, 0.f, __uint_as_float(wf_pack(0, rng.has_saved, 0)));
+                r[3] = make_float4(sum.x, sum.y, sum.z, __uint_as_float(wf_pack(0, rng.has_saved, R.accum ? (uint32_t)R.sample_first : 0u)));
                 atomicOr(&sh.pending[l >> 4], PT_BIT_T << ((l & 15u) * 2u));
                 started = true;
             }

@@ -235,6 +235,10 @@ RT_DEV int p6_advance(const SceneView6 &S, const RenderView &R, const W6View &W,
                 r[3] = make_float4(accum.x, accum.y, accum.z, __uint_as_float(p6_pack(0, rng.has_saved, sample, 0u)));
                 return sample < (uint32_t)R.sample_stop ? P6_TRACE : P6_PARKED;
             }
+            if (R.accum) { // a slice of a resumable render ends here (rt_wavefront.h): sum and engine go back to the state
+                accum_leave(R, slot + W.slot_base, rng, accum);
+                return 0;
+            }
             if (R.streams > 1) { // throughput mode (rt_wavefront.h): this stream's unnormalised sum; wf_reduce_streams_kernel adds a pixel's streams
                 float *ps = R.partial + 3 * (size_t)(slot + W.slot_base);
                 ps[0] = accum.x; ps[1] = accum.y; ps[2] = accum.z;
@@ -890,14 +894,16 @@ __global__ __launch_bounds__(P6_THREADS, P6_PER_CU) void p6_persistent_kernel(Sc
                 if (started) atomicOr(&sh.pending[l >> 4], PT_BIT_T << ((l & 15u) * 2u));
             } else {
                 Rng rng;
-                rng_seed(rng, (uint32_t)(y * R.width + x) + (R.streams > 1 ? (gslot / R.n_pixslots) * R.seed_stride : 0u)); // hw6/src/sceneio.cpp:280-284; throughput mode: stream k offset by k * W * H
+                F3 sum = f3(0.f, 0.f, 0.f);
+                if (R.accum) accum_enter(R, gslot, rng, sum);   // a slice of a resumable render: carry on at sample R.sample_first
+                else rng_seed(rng, (uint32_t)(y * R.width + x) + (R.streams > 1 ? (gslot / R.n_pixslots) * R.seed_stride : 0u)); // hw6/src/sceneio.cpp:280-284; throughput mode: stream k offset by k * W * H
                 F3 o, d;
                 p6_camera_ray(S, R, rng, x, y, o, d);
                 float4 *r = p6_rec(W, slot);
                 r[0] = make_float4(o.x, o.y, o.z, d.x);
                 r[1] = make_float4(d.y, d.z, __uint_as_float(rng.x), rng.saved);
                 r[2] = make_float4(0.f, 0.f, 0.f, 0.f);
-                r[3] = make_float4(0.f, 0.f, 0.f, __uint_as_float(p6_pack(0, rng.has_saved, 0u, 0u)));
+                r[3] = make_float4(sum.x, sum.y, sum.z, __uint_as_float(p6_pack(0, rng.has_saved, R.accum ? (uint32_t)R.sample_first : 0u, 0u)));
                 atomicOr(&sh.pending[l >> 4], PT_BIT_T << ((l & 15u) * 2u));
                 started = true;
             }

@@ -158,6 +158,12 @@ struct RenderView {
     uint32_t sample_seeds;         // throughput mode, RT_FLAG_SAMPLE_SEEDS: every sample seeds its own engine (hash of pixel and sample)
     uint32_t total_samples;        // samples per pixel over all its streams
     int32_t rr_depth;              // throughput mode, RT_FLAG_RUSSIAN_ROULETTE: first bounce index that plays roulette (0 = off)
+    // Resumable renders (rt_accum_*, replay mode): a launch advances every pixel from sample `sample_first` to sample `samples`
+    // (both absolute, as the indices in the path records are).  Paths start from the per-pixel-slot state instead of a seed
+    // and a path that reaches `samples` leaves its sum and engine there instead of writing a pixel.  Layout (rt_wavefront.h
+    // accum_enter / accum_leave): n_pixslots x {sum.x, sum.y, sum.z, Rng::x}, then n_pixslots x {Rng::saved, Rng::has_saved}.
+    uint32_t *accum;               // nullable: null = a one-shot frame
+    int32_t sample_first;
 };
 
 } // namespace rtamd

@@ -132,6 +132,19 @@ RT_DEV float wf_roulette_q(const WfView &W, uint32_t slot, int depth, F3 mult) {
     return fminf(1.f, fmaxf(0.25f, fmaxf(beta.x, fmaxf(beta.y, beta.z))));
 }
 
+// Resumable renders (RenderView::accum): the state of pixel slot `pslot` is its sum and its engine BEFORE the camera ray of the next
+// sample is drawn; 24 bytes in two arrays, so that a wave reads and writes whole 16- and 8-byte words side by side.
+RT_DEV void accum_enter(const RenderView &R, uint32_t pslot, Rng &rng, F3 &sum) {
+    const uint4 a = reinterpret_cast<const uint4 *>(R.accum)[pslot];
+    const uint2 b = reinterpret_cast<const uint2 *>(R.accum + 4 * (size_t)R.n_pixslots)[pslot];
+    sum = f3(__uint_as_float(a.x), __uint_as_float(a.y), __uint_as_float(a.z));
+    rng.x = a.w; rng.saved = __uint_as_float(b.x); rng.has_saved = b.y != 0u;
+}
+RT_DEV void accum_leave(const RenderView &R, uint32_t pslot, const Rng &rng, F3 sum) {
+    reinterpret_cast<uint4 *>(R.accum)[pslot] = make_uint4(__float_as_uint(sum.x), __float_as_uint(sum.y), __float_as_uint(sum.z), rng.x);
+    reinterpret_cast<uint2 *>(R.accum + 4 * (size_t)R.n_pixslots)[pslot] = make_uint2(__float_as_uint(rng.saved), rng.has_saved ? 1u : 0u);
+}
+
 // End of one camera sample: fold e + m*(inner) backwards (scene.cpp:164), add to the pixel sum
 // (scene.cpp:174), then either start the next sample (returns WF_NEXT_TRACE: the slot holds a new camera ray that wants
 // tracing; WF_PARKED instead when that sample belongs to the next phase of the frame, R.sample_stop) or write the finished
@@ -162,7 +175,9 @@ RT_DEV int wf_finish_path(const SceneView &S, const RenderView &R, const WfView 
         r[3] = make_float4(accum.x, accum.y, accum.z, __uint_as_float(wf_pack(0, rng.has_saved, sample)));
         return sample < (uint32_t)R.sample_stop ? WF_NEXT_TRACE : WF_PARKED;
     }
-    if (R.streams > 1) {                                             // throughput mode: this stream's unnormalised sum
+    if (R.accum) {                                                   // a slice of a resumable render ends here: sum and engine go back to the state
+        accum_leave(R, slot + W.slot_base, rng, accum);
+    } else if (R.streams > 1) {                                      // throughput mode: this stream's unnormalised sum
         float *o = R.partial + 3 * (size_t)(slot + W.slot_base);
         o[0] = accum.x; o[1] = accum.y; o[2] = accum.z;
     } else {
@@ -195,7 +210,9 @@ __global__ __launch_bounds__(256) void wf_init_kernel(SceneView S, RenderView R,
                 }
             } else {
                 Rng rng;
-                rng_seed(rng, (uint32_t)(y * R.width + x) + (R.streams > 1 ? (gslot / R.n_pixslots) * R.seed_stride : 0u)); // sceneio.cpp:389-391
+                F3 sum = f3(0.f, 0.f, 0.f);
+                if (R.accum) accum_enter(R, gslot, rng, sum);   // a slice of a resumable render: carry on at sample R.sample_first
+                else rng_seed(rng, (uint32_t)(y * R.width + x) + (R.streams > 1 ? (gslot / R.n_pixslots) * R.seed_stride : 0u)); // sceneio.cpp:389-391
                 if (R.sample_seeds) wf_sample_seed(R, rng, gslot, x, y, 0u);
                 F3 o, d;
                 wf_camera_ray(S, R, rng, x, y, o, d);
@@ -203,7 +220,7 @@ __global__ __launch_bounds__(256) void wf_init_kernel(SceneView S, RenderView R,
                 r[0] = make_float4(o.x, o.y, o.z, d.x);
                 r[1] = make_float4(d.y, d.z, __uint_as_float(rng.x), rng.saved);
                 r[2] = make_float4(0.f, 0.f, 0.f, 0.f);
-                r[3] = make_float4(0.f, 0.f, 0.f, __uint_as_float(wf_pack(0, rng.has_saved, 0)));
+                r[3] = make_float4(sum.x, sum.y, sum.z, __uint_as_float(wf_pack(0, rng.has_saved, R.accum ? (uint32_t)R.sample_first : 0u)));
                 wf_push(q, slot);
             }
         }
@@ -801,6 +818,37 @@ __global__ __launch_bounds__(256) void wf_reduce_streams_kernel(RenderView R) {
         F3 px = R.inv_samples * sum;
         if (R.out_rgb) { R.out_rgb[3 * out_index] = px.x; R.out_rgb[3 * out_index + 1] = px.y; R.out_rgb[3 * out_index + 2] = px.z; }
         if (R.out_rgb8) { R.out_rgb8[3 * out_index] = tonemap1(px.x); R.out_rgb8[3 * out_index + 1] = tonemap1(px.y); R.out_rgb8[3 * out_index + 2] = tonemap1(px.z); }
+    }
+}
+
+// Resumable renders: a fresh state (every pixel's engine as sceneio.cpp:389-391 seeds it, sums zero; padding slots zero) ...
+__global__ __launch_bounds__(256) void accum_seed_kernel(RenderView R) {
+    for (uint32_t p = blockIdx.x * 256u + threadIdx.x; p < R.n_pixslots; p += gridDim.x * 256u) {
+        int x, y; bool inside; size_t out_index;
+        slot_to_pixel(R, p, x, y, inside, out_index);
+        Rng rng;
+        rng_seed(rng, inside ? (uint32_t)(y * R.width + x) : 0u);
+        if (!inside) rng.x = 0u;
+        accum_leave(R, p, rng, f3(0.f, 0.f, 0.f));
+    }
+}
+// ... and the picture of a state: pixel = inv_samples * sum and the tonemap, exactly as wf_finish_path ends a one-shot frame;
+// the padding of border tiles in the compact shard layout is zeroed as the init blocks do.  The state is only read.
+__global__ __launch_bounds__(256) void accum_resolve_kernel(RenderView R) {
+    for (uint32_t p = blockIdx.x * 256u + threadIdx.x; p < R.n_pixslots; p += gridDim.x * 256u) {
+        int x, y; bool inside; size_t out_index;
+        slot_to_pixel(R, p, x, y, inside, out_index);
+        if (!inside && R.shard_count <= 1) continue;
+        F3 px = f3(0.f, 0.f, 0.f);
+        uint8_t b0 = 0, b1 = 0, b2 = 0;
+        if (inside) {
+            Rng rng; F3 sum;
+            accum_enter(R, p, rng, sum);
+            px = R.inv_samples * sum;                                // scene.cpp:176
+            b0 = tonemap1(px.x); b1 = tonemap1(px.y); b2 = tonemap1(px.z); // sceneio.cpp:393-395
+        }
+        if (R.out_rgb) { R.out_rgb[3 * out_index] = px.x; R.out_rgb[3 * out_index + 1] = px.y; R.out_rgb[3 * out_index + 2] = px.z; }
+        if (R.out_rgb8) { R.out_rgb8[3 * out_index] = b0; R.out_rgb8[3 * out_index + 1] = b1; R.out_rgb8[3 * out_index + 2] = b2; }
     }
 }
 

@@ -572,7 +572,7 @@ size_t rt_output_elems(const rt_render_params *p) {
 // Rounds a pixel needs per camera sample: one per bounce; without the deepest-level shortcut the last bounce's pdf / clamp
 // step takes one more.
 static size_t wavefront_rounds(const SceneView &V, const RenderView &R) {
-    return (size_t)R.samples * ((size_t)R.ray_depth + (V.last_level_emission_only ? 0u : 1u));
+    return (size_t)(R.samples - R.sample_first) * ((size_t)R.ray_depth + (V.last_level_emission_only ? 0u : 1u));
 }
 
 // Wavefront driver: per round one traverse launch and one shade launch (device/rt_wavefront.h).
@@ -886,6 +886,7 @@ static PersistentKernel hw6_persistent(const SceneView6 &V, hipStream_t stream, 
 
 static void launch_persistent(rt_scene *scene, const PersistentKernel &k, const RenderView &R, uint32_t n_work, hipStream_t stream, bool count, bool time_trace) {
     auto env_int = [](const char *n, int dflt) { const char *e = getenv(n); return e && atoi(e) > 0 ? atoi(e) : dflt; };
+    const int n_samples = R.samples - R.sample_first; // of this launch sequence: a frame, or one slice of a resumable render (sample_first > 0)
     const uint32_t n_blocks_max = (uint32_t)env_int("RTAMD_PT_BLOCKS", scene->n_cus * k.per_cu); // five 4-wave workgroups per CU (their LDS fills the CU)
     const uint64_t pass_cap = (uint64_t)n_blocks_max * (k.max_paths / 64);
     const uint32_t passes = (uint32_t)((n_work + pass_cap - 1) / pass_cap);
@@ -927,7 +928,7 @@ static void launch_persistent(rt_scene *scene, const PersistentKernel &k, const 
     // A wave still in the launch after this long gives up (the kernel cannot hang the GPU): RTAMD_PT_TIMEOUT_S, by default ten minutes or
     // — for long renders: 4K at thousands of samples — the time the launch would take at a twentieth of the usual rate, whichever is more.
     {
-        const double expected_s = (double)n_work * 64.0 * (double)R.samples / 15e6;
+        const double expected_s = (double)n_work * 64.0 * (double)n_samples / 15e6;
         const double deadline_s = getenv("RTAMD_PT_TIMEOUT_S") ? (double)env_int("RTAMD_PT_TIMEOUT_S", 600) : (expected_s > 600.0 ? expected_s : 600.0);
         P.deadline_ticks = (unsigned long long)(deadline_s * 1e8);
     }
@@ -945,9 +946,10 @@ static void launch_persistent(rt_scene *scene, const PersistentKernel &k, const 
         }
     }
     // two phases when there is something to re-deal: enough samples, and several sub-tiles per workgroup
-    const int phase0 = getenv("RTAMD_PT_PHASE0") ? atoi(getenv("RTAMD_PT_PHASE0")) : R.samples / 16;
-    const bool two_phase = !getenv("RTAMD_PT_NO_REBALANCE") && phase0 >= 1 && phase0 < R.samples && ((uint64_t)pass_groups << sub) >= 4ull * n_blocks_max;
-    const std::vector<int> stops = phase_stops(two_phase, phase0, R.samples, group_shift < 6u);
+    const int phase0 = getenv("RTAMD_PT_PHASE0") ? atoi(getenv("RTAMD_PT_PHASE0")) : n_samples / 16;
+    const bool two_phase = !getenv("RTAMD_PT_NO_REBALANCE") && phase0 >= 1 && phase0 < n_samples && ((uint64_t)pass_groups << sub) >= 4ull * n_blocks_max;
+    std::vector<int> stops = phase_stops(two_phase, phase0, n_samples, group_shift < 6u);
+    for (int &stop : stops) stop += R.sample_first; // the records count a pixel's samples from the start of its frame
     const uint32_t phases = (uint32_t)stops.size();
     if (time_trace) while (scene->ev_pool.size() < 2 * (size_t)passes * phases) { hipEvent_t e; HIP_CHECK(hipEventCreate(&e)); scene->ev_pool.push_back(e); }
     uint32_t first = 0, launch = 0;
@@ -1089,21 +1091,40 @@ static void report_persistent(rt_scene *scene, bool hw6, const char *kernel, boo
     fprintf(stderr, "\n");
 }
 
-int rt_render(rt_scene *scene, const rt_render_params *p, float *out_rgb, uint8_t *out_rgb8, rt_stats *stats) {
-    if (!scene || !p) return fail(RT_ERR_INVALID_ARG, "rt_render: null argument");
-    if (p->struct_size != sizeof(rt_render_params)) return fail(RT_ERR_INVALID_ARG, "rt_render: struct_size mismatch (ABI skew)");
+// Resumable renders advance the kernels that can park and resume a path: both persistent pipelines and the round pipeline.
+// Returns what stands in the way, or null.
+static const char *accum_unsupported(Pipeline pipe, const rt_render_params *p) {
+    if (p->sample_streams > 1) return "throughput mode (sample_streams > 1) has no resumable state";
+    if (p->flags & ~RT_FLAG_COUNTERS) return "flags other than RT_FLAG_COUNTERS do not apply to a resumable render (the outputs are named at rt_accum_resolve)";
+    switch (pipe) {
+    case Pipeline::Persistent8: case Pipeline::Persistent6: case Pipeline::Rounds: return nullptr;
+    case Pipeline::Mega8: return "the hw8 / hw7 megakernel is in effect (RTAMD_KERNEL=mega, or a tree beyond the persistent and round kernels' limits): a resumable render needs the persistent or the round pipeline";
+    case Pipeline::Mega6: return "the hw6 per-lane path machine is in effect (RTAMD_KERNEL=mega, RTAMD_HW6_SCRATCH_STACK, or a tree beyond the persistent hw6 kernel's stacks): a resumable render needs the persistent hw6 pipeline";
+    default: return "the hw1 .. hw5 integrators have no resumable state (RT_INTEGRATOR_HW6 / HW7 / HW8 only)";
+    }
+}
+
+// One slice of a resumable render (rt_accum_render): every pixel goes from sample `first` to `first + p->samples` of its stream,
+// from and to `state` (RenderView::accum) instead of from a seed and to a pixel.
+struct AccumSlice { uint32_t *state; int32_t first; };
+
+// rt_render, and with `slice` rt_accum_render: the same checks, pipelines, launches and statistics.
+static int render_frame(rt_scene *scene, const rt_render_params *p, float *out_rgb, uint8_t *out_rgb8, rt_stats *stats, const AccumSlice *slice) {
+    const std::string who = slice ? "rt_accum_render: " : "rt_render: ";
+    if (!scene || !p) return fail(RT_ERR_INVALID_ARG, who + "null argument");
+    if (p->struct_size != sizeof(rt_render_params)) return fail(RT_ERR_INVALID_ARG, who + "struct_size mismatch (ABI skew)");
     if (p->integrator != RT_INTEGRATOR_HW8 && p->integrator != RT_INTEGRATOR_HW6 && p->integrator != RT_INTEGRATOR_HW3 && p->integrator != RT_INTEGRATOR_HW1 &&
         p->integrator != RT_INTEGRATOR_HW2 && p->integrator != RT_INTEGRATOR_HW4 && p->integrator != RT_INTEGRATOR_HW5 && p->integrator != RT_INTEGRATOR_HW7)
-        return fail(RT_ERR_UNSUPPORTED, "rt_render: unknown integrator");
+        return fail(RT_ERR_UNSUPPORTED, who + "unknown integrator");
     const bool txt_scene = scene->flavor == RT_INTEGRATOR_HW3;
     const bool txt_integrator = p->integrator >= RT_INTEGRATOR_HW1 && p->integrator <= RT_INTEGRATOR_HW5;
     const bool hw7 = p->integrator == RT_INTEGRATOR_HW7; // renders a scene prepared for hw8 with hw7's material model (no textures)
     if (txt_scene != txt_integrator || (!txt_scene && p->integrator != scene->flavor && !(hw7 && scene->flavor == RT_INTEGRATOR_HW8)))
-        return fail(RT_ERR_INVALID_ARG, "rt_render: this scene was prepared for integrator " + std::to_string(scene->flavor) +
+        return fail(RT_ERR_INVALID_ARG, who + "this scene was prepared for integrator " + std::to_string(scene->flavor) +
                                             " (hw6 scenes carry no vertex normals, hw8 scenes do)");
     RenderView R{};
     std::string err;
-    if (!resolve_tiles(p, R, err)) return fail(RT_ERR_INVALID_ARG, "rt_render: " + err);
+    if (!resolve_tiles(p, R, err)) return fail(RT_ERR_INVALID_ARG, who + "" + err);
     double t0 = now_ms();
     float *d_rgb = nullptr;
     uint8_t *d_rgb8 = nullptr;
@@ -1129,18 +1150,22 @@ int rt_render(rt_scene *scene, const rt_render_params *p, float *out_rgb, uint8_
         // scene.cpp:181,176 — evaluated on the host in float exactly like the reference
         R.tan_fov_x = scene->view.tan_fov_y * R.width / R.height;
         R.inv_samples = (float)(1.0 / R.samples);
-        R.sample_stop = R.samples;
         uint32_t n_work = R.n_shard_tiles * (uint32_t)((R.tile_w >> 3) * (R.tile_h >> 3));
         const int streams = p->sample_streams > 1 ? p->sample_streams : 1;
-        if (p->reserved != 0) return fail(RT_ERR_INVALID_ARG, "rt_render: reserved must be 0");
+        if (slice) { // sample indices are absolute, in the records as in RenderView
+            R.accum = slice->state; R.sample_first = slice->first; R.samples += slice->first;
+            R.n_pixslots = n_work * 64u;
+        }
+        R.sample_stop = R.samples;
+        if (p->reserved != 0) return fail(RT_ERR_INVALID_ARG, who + "reserved must be 0");
         if ((p->flags & (RT_FLAG_SAMPLE_SEEDS | RT_FLAG_RUSSIAN_ROULETTE)) && streams <= 1)
-            return fail(RT_ERR_INVALID_ARG, "rt_render: RT_FLAG_SAMPLE_SEEDS / RT_FLAG_RUSSIAN_ROULETTE change the estimator and belong to throughput mode (sample_streams > 1)");
+            return fail(RT_ERR_INVALID_ARG, who + "RT_FLAG_SAMPLE_SEEDS / RT_FLAG_RUSSIAN_ROULETTE change the estimator and belong to throughput mode (sample_streams > 1)");
         if (streams > 1) { // throughput mode (include/rtamd.h: sample_streams)
-            if (p->integrator != RT_INTEGRATOR_HW8 && p->integrator != RT_INTEGRATOR_HW7 && p->integrator != RT_INTEGRATOR_HW6) return fail(RT_ERR_UNSUPPORTED, "rt_render: sample_streams > 1 is implemented for RT_INTEGRATOR_HW6 / HW7 / HW8 only");
-            if (p->integrator == RT_INTEGRATOR_HW6 && (p->flags & (RT_FLAG_SAMPLE_SEEDS | RT_FLAG_RUSSIAN_ROULETTE))) return fail(RT_ERR_UNSUPPORTED, "rt_render: RT_FLAG_SAMPLE_SEEDS / RT_FLAG_RUSSIAN_ROULETTE are implemented for RT_INTEGRATOR_HW7 / HW8 only");
-            if (streams > 256 || R.samples % streams != 0) return fail(RT_ERR_INVALID_ARG, "rt_render: samples must be a multiple of sample_streams (at most 256 streams)");
-            if ((int64_t)R.width * R.height * streams >= 2147483647LL) return fail(RT_ERR_INVALID_ARG, "rt_render: width*height*sample_streams must stay below 2^31-1 (stream seeds)");
-            if ((uint64_t)n_work * 64u * (uint64_t)streams >= 0x40000000ull) return fail(RT_ERR_LIMIT, "rt_render: too many path slots (pixels of this shard x sample_streams)");
+            if (p->integrator != RT_INTEGRATOR_HW8 && p->integrator != RT_INTEGRATOR_HW7 && p->integrator != RT_INTEGRATOR_HW6) return fail(RT_ERR_UNSUPPORTED, who + "sample_streams > 1 is implemented for RT_INTEGRATOR_HW6 / HW7 / HW8 only");
+            if (p->integrator == RT_INTEGRATOR_HW6 && (p->flags & (RT_FLAG_SAMPLE_SEEDS | RT_FLAG_RUSSIAN_ROULETTE))) return fail(RT_ERR_UNSUPPORTED, who + "RT_FLAG_SAMPLE_SEEDS / RT_FLAG_RUSSIAN_ROULETTE are implemented for RT_INTEGRATOR_HW7 / HW8 only");
+            if (streams > 256 || R.samples % streams != 0) return fail(RT_ERR_INVALID_ARG, who + "samples must be a multiple of sample_streams (at most 256 streams)");
+            if ((int64_t)R.width * R.height * streams >= 2147483647LL) return fail(RT_ERR_INVALID_ARG, who + "width*height*sample_streams must stay below 2^31-1 (stream seeds)");
+            if ((uint64_t)n_work * 64u * (uint64_t)streams >= 0x40000000ull) return fail(RT_ERR_LIMIT, who + "too many path slots (pixels of this shard x sample_streams)");
         }
         HIP_CHECK(hipMemsetAsync(scene->d_work_counter, 0, 4, stream));
         HIP_CHECK(hipMemsetAsync(scene->d_counters, 0, 512, stream));
@@ -1151,18 +1176,19 @@ int rt_render(rt_scene *scene, const rt_render_params *p, float *out_rgb, uint8_
         if (blocks > n_work) blocks = n_work;
         bool rounds_chosen = false;
         const Pipeline pipe = choose_pipeline(scene, p->integrator, R, n_work, streams, rounds_chosen);
-        if (streams > 1 && pipe != Pipeline::Persistent8 && pipe != Pipeline::Rounds && pipe != Pipeline::Persistent6) return fail(RT_ERR_UNSUPPORTED, "rt_render: sample_streams > 1 needs the persistent / round kernels (RTAMD_KERNEL=mega or a tree beyond their limits is in effect)");
-        if (txt_scene && p->integrator == RT_INTEGRATOR_HW3 && R.ray_depth > RT3_MAX_DEPTH) return fail(RT_ERR_LIMIT, "rt_render: hw3 ray_depth above 8");
-        if (txt_scene && scene->txt_has_triangles && p->integrator != RT_INTEGRATOR_HW5) return fail(RT_ERR_INVALID_ARG, "rt_render: a .txt scene with TRIANGLE figures renders with RT_INTEGRATOR_HW5 only");
-        if (p->integrator == RT_INTEGRATOR_HW5 && R.ray_depth > RT4_MAX_DEPTH) return fail(RT_ERR_LIMIT, "rt_render: hw5 ray_depth above 8");
-        if (p->integrator == RT_INTEGRATOR_HW5 && (scene->info.bvh_depth > RT5_STACK || scene->info.light_bvh_depth > RT5_STACK)) return fail(RT_ERR_LIMIT, "rt_render: hw5 BVH deeper than 64");
-        if (p->integrator == RT_INTEGRATOR_HW4 && R.ray_depth > RT4_MAX_DEPTH) return fail(RT_ERR_LIMIT, "rt_render: hw4 ray_depth above 8");
-        if (p->integrator == RT_INTEGRATOR_HW4 && scene->viewt.n_light_prims > RT4_MAX_LIGHTS) return fail(RT_ERR_LIMIT, "rt_render: hw4 supports at most 32 emissive box/ellipsoid lights");
-        if (p->integrator == RT_INTEGRATOR_HW2 && R.ray_depth > RT2_MAX_DEPTH) return fail(RT_ERR_LIMIT, "rt_render: hw2 ray_depth above 16");
-        if (p->integrator == RT_INTEGRATOR_HW1 && R.shard_count > 1) return fail(RT_ERR_UNSUPPORTED, "rt_render: the hw1 caster renders unsharded frames only");
+        if (slice) if (const char *why = accum_unsupported(pipe, p)) return fail(RT_ERR_UNSUPPORTED, who + why);
+        if (streams > 1 && pipe != Pipeline::Persistent8 && pipe != Pipeline::Rounds && pipe != Pipeline::Persistent6) return fail(RT_ERR_UNSUPPORTED, who + "sample_streams > 1 needs the persistent / round kernels (RTAMD_KERNEL=mega or a tree beyond their limits is in effect)");
+        if (txt_scene && p->integrator == RT_INTEGRATOR_HW3 && R.ray_depth > RT3_MAX_DEPTH) return fail(RT_ERR_LIMIT, who + "hw3 ray_depth above 8");
+        if (txt_scene && scene->txt_has_triangles && p->integrator != RT_INTEGRATOR_HW5) return fail(RT_ERR_INVALID_ARG, who + "a .txt scene with TRIANGLE figures renders with RT_INTEGRATOR_HW5 only");
+        if (p->integrator == RT_INTEGRATOR_HW5 && R.ray_depth > RT4_MAX_DEPTH) return fail(RT_ERR_LIMIT, who + "hw5 ray_depth above 8");
+        if (p->integrator == RT_INTEGRATOR_HW5 && (scene->info.bvh_depth > RT5_STACK || scene->info.light_bvh_depth > RT5_STACK)) return fail(RT_ERR_LIMIT, who + "hw5 BVH deeper than 64");
+        if (p->integrator == RT_INTEGRATOR_HW4 && R.ray_depth > RT4_MAX_DEPTH) return fail(RT_ERR_LIMIT, who + "hw4 ray_depth above 8");
+        if (p->integrator == RT_INTEGRATOR_HW4 && scene->viewt.n_light_prims > RT4_MAX_LIGHTS) return fail(RT_ERR_LIMIT, who + "hw4 supports at most 32 emissive box/ellipsoid lights");
+        if (p->integrator == RT_INTEGRATOR_HW2 && R.ray_depth > RT2_MAX_DEPTH) return fail(RT_ERR_LIMIT, who + "hw2 ray_depth above 16");
+        if (p->integrator == RT_INTEGRATOR_HW1 && R.shard_count > 1) return fail(RT_ERR_UNSUPPORTED, who + "the hw1 caster renders unsharded frames only");
         const bool float_tan = p->integrator == RT_INTEGRATOR_HW1 || p->integrator == RT_INTEGRATOR_HW2;
         const float txt_tan_fov_y = (float_tan ? scene->viewt.tan_fov_x_f : scene->viewt.tan_fov_x) * R.height / R.width; // hw3/src/scene.cpp:101
-        if (scene->flavor == RT_INTEGRATOR_HW6 && R.ray_depth > RT6_MAX_DEPTH) return fail(RT_ERR_LIMIT, "rt_render: hw6 ray_depth above 8");
+        if (scene->flavor == RT_INTEGRATOR_HW6 && R.ray_depth > RT6_MAX_DEPTH) return fail(RT_ERR_LIMIT, who + "hw6 ray_depth above 8");
         SceneView V8 = scene->view; // per-render copy: the hw7 replay switches are render parameters, not scene state
         if (hw7) { V8.hw7 = 1; V8.last_level_emission_only = 0; V8.env_image = -1; }
         // Exactness follows the scene, not the pipeline: when the persistent pipeline cannot take the scene (a tree deeper than its
@@ -1245,8 +1271,8 @@ int rt_render(rt_scene *scene, const rt_render_params *p, float *out_rgb, uint8_
             const char *kernel = hw6 ? "persistent hw6 kernel" : "persistent kernel";
             if (!hw6) h_cnt[0] -= h_cnt[10] < h_cnt[0] ? h_cnt[10] : h_cnt[0]; // speculative closest-hit queries that the clamp step discarded are not part of the algorithm
             if (getenv("RTAMD_DEBUG_COUNTERS")) report_persistent(scene, hw6, kernel, count, h_cnt);
-            if (h_cnt[29]) return fail(RT_ERR_LIMIT, std::string("rt_render: the ") + kernel + " ran into its launch deadline (" + std::to_string(h_cnt[29]) + " waves; RTAMD_PT_TIMEOUT_S raises it); the frame is incomplete");
-            if (h_cnt[14]) return fail(RT_ERR_HIP, std::string("rt_render: the ") + kernel + " lost a path (" + std::to_string(h_cnt[14]) + " waves gave up waiting); the frame is incomplete");
+            if (h_cnt[29]) return fail(RT_ERR_LIMIT, who + "the " + kernel + " ran into its launch deadline (" + std::to_string(h_cnt[29]) + " waves; RTAMD_PT_TIMEOUT_S raises it); the frame is incomplete");
+            if (h_cnt[14]) return fail(RT_ERR_HIP, who + "the " + kernel + " lost a path (" + std::to_string(h_cnt[14]) + " waves gave up waiting); the frame is incomplete");
         }
         if (count && ran_rounds) { // queries = lengths of the per-round queues
             size_t rounds = wavefront_rounds(V8, R);
@@ -1316,7 +1342,7 @@ int rt_render(rt_scene *scene, const rt_render_params *p, float *out_rgb, uint8_
                 int w = R.width - tx0 < R.tile_w ? R.width - tx0 : R.tile_w, h = R.height - ty0 < R.tile_h ? R.height - ty0 : R.tile_h;
                 px += (uint64_t)w * h;
             }
-            stats->samples = px * (uint64_t)R.samples * (uint64_t)streams;
+            stats->samples = px * (uint64_t)(R.samples - R.sample_first) * (uint64_t)streams;
             stats->closest_hit_queries = h_cnt[0]; stats->light_pdf_queries = h_cnt[1];
             stats->node_visits = h_cnt[2]; stats->triangle_tests = h_cnt[3];
         }
@@ -1324,7 +1350,218 @@ int rt_render(rt_scene *scene, const rt_render_params *p, float *out_rgb, uint8_
     } catch (const HipError &e) {
         return fail(RT_ERR_HIP, e.what());
     } catch (const std::exception &e) { // e.g. std::bad_alloc from the host-side vectors: nothing crosses the C boundary
-        return fail(RT_ERR_INVALID_ARG, std::string("rt_render: ") + e.what());
+        return fail(RT_ERR_INVALID_ARG, who + e.what());
+    }
+}
+
+int rt_render(rt_scene *scene, const rt_render_params *p, float *out_rgb, uint8_t *out_rgb8, rt_stats *stats) {
+    return render_frame(scene, p, out_rgb, out_rgb8, stats, nullptr);
+}
+
+// ---- resumable renders (include/rtamd.h: rt_accum_*) ---------------------------------------------------------------------
+// The state lives in one device allocation indexed by pixel slot of the shard (RenderView::accum, device/rt_wavefront.h
+// accum_enter / accum_leave): it belongs to the rt_accum, not to the scene's path records, so passes, phases, re-deals and
+// other renders on the scene do not touch it.  The blob of rt_accum_save is a 128-byte header and that allocation, verbatim.
+#define ACCUM_MAGIC 0x43415452u   // "RTAC" read as a little-endian word
+#define ACCUM_VERSION 1u
+#define ACCUM_HEADER_BYTES 128u
+#define ACCUM_SLOT_BYTES 24u
+enum { AH_MAGIC, AH_VERSION, AH_HEADER_BYTES, AH_SLOT_BYTES, AH_WIDTH, AH_HEIGHT, AH_INTEGRATOR, AH_RAY_DEPTH, AH_TILE_W, AH_TILE_H,
+       AH_SHARD_INDEX, AH_SHARD_COUNT, AH_PIXSLOTS, AH_SAMPLES, AH_TRIANGLES, AH_LIGHTS, AH_LIGHT_HASH, AH_WORDS };
+static const char *const accum_field_names[AH_WORDS] = {"magic", "format version", "header size", "bytes per pixel slot", "width", "height", "integrator",
+    "ray depth", "tile width", "tile height", "shard index", "shard count", "pixel slots", "samples", "triangle count of the scene", "light count of the scene",
+    "light order of the scene (hash)"};
+
+struct rt_accum {
+    rt_scene *scene = nullptr;
+    rt_render_params params{};      // as given to rt_accum_create; samples is set per slice
+    RenderView view{};              // the frame's geometry (resolve_tiles)
+    uint32_t n_pixslots = 0;
+    uint32_t *d_state = nullptr;
+    int32_t samples = 0;            // per pixel so far
+    int32_t sample_limit = 0;       // the path records' sample index field (choose_pipeline)
+    std::string broken;             // first error of a slice that failed under way: the state is half advanced
+    ~rt_accum() { if (d_state) (void)hipFree(d_state); }
+};
+
+// Geometry of a resumable frame from its params (host only); false with `err` set for params no rt_accum can be made of.
+static bool accum_geometry(const rt_render_params *p, RenderView &R, uint32_t &n_pixslots, std::string &err) {
+    if (!p) { err = "null params"; return false; }
+    if (p->struct_size != sizeof(rt_render_params)) { err = "struct_size mismatch (ABI skew)"; return false; }
+    if (p->reserved != 0) { err = "reserved must be 0"; return false; }
+    if (p->integrator != RT_INTEGRATOR_HW8 && p->integrator != RT_INTEGRATOR_HW7 && p->integrator != RT_INTEGRATOR_HW6) { err = "resumable renders exist for RT_INTEGRATOR_HW6 / HW7 / HW8 only"; return false; }
+    rt_render_params q = *p;
+    q.samples = 1; // ignored here
+    if (!resolve_tiles(&q, R, err)) return false;
+    if (R.ray_depth > (p->integrator == RT_INTEGRATOR_HW6 ? RT6_MAX_DEPTH : RT_MAX_DEPTH)) { err = "ray_depth above the integrator's limit"; return false; }
+    const uint64_t slots = (uint64_t)R.n_shard_tiles * (uint64_t)((R.tile_w >> 3) * (R.tile_h >> 3)) * 64u;
+    if (slots >= 0x40000000ull) { err = "too many pixel slots"; return false; }
+    n_pixslots = (uint32_t)slots;
+    return true;
+}
+
+static void accum_header(const rt_accum *a, uint32_t *h) {
+    memset(h, 0, ACCUM_HEADER_BYTES);
+    const RenderView &R = a->view;
+    h[AH_MAGIC] = ACCUM_MAGIC; h[AH_VERSION] = ACCUM_VERSION; h[AH_HEADER_BYTES] = ACCUM_HEADER_BYTES; h[AH_SLOT_BYTES] = ACCUM_SLOT_BYTES;
+    h[AH_WIDTH] = (uint32_t)R.width; h[AH_HEIGHT] = (uint32_t)R.height; h[AH_INTEGRATOR] = (uint32_t)a->params.integrator; h[AH_RAY_DEPTH] = (uint32_t)R.ray_depth;
+    h[AH_TILE_W] = (uint32_t)R.tile_w; h[AH_TILE_H] = (uint32_t)R.tile_h; h[AH_SHARD_INDEX] = (uint32_t)R.shard_index; h[AH_SHARD_COUNT] = (uint32_t)R.shard_count;
+    h[AH_PIXSLOTS] = a->n_pixslots; h[AH_SAMPLES] = (uint32_t)a->samples;
+    h[AH_TRIANGLES] = a->scene->info.n_triangles; h[AH_LIGHTS] = a->scene->info.n_lights;
+    uint32_t hash = 2166136261u; // FNV-1a over the bytes of the light order, least significant first
+    for (uint32_t v : a->scene->light_order) for (int b = 0; b < 4; b++) { hash ^= (v >> (8 * b)) & 255u; hash *= 16777619u; }
+    h[AH_LIGHT_HASH] = hash;
+}
+
+size_t rt_accum_state_bytes(const rt_render_params *p) {
+    RenderView R{};
+    uint32_t n = 0;
+    std::string err;
+    if (!accum_geometry(p, R, n, err)) { set_error("rt_accum_state_bytes: " + err); return 0; }
+    return (size_t)ACCUM_HEADER_BYTES + (size_t)n * ACCUM_SLOT_BYTES;
+}
+
+int rt_accum_create(rt_scene *scene, const rt_render_params *p, rt_accum **out) {
+    if (!scene || !p || !out) return fail(RT_ERR_INVALID_ARG, "rt_accum_create: null argument");
+    *out = nullptr;
+    if (p->struct_size == sizeof(rt_render_params)) {
+        if (p->sample_streams > 1) return fail(RT_ERR_UNSUPPORTED, std::string("rt_accum_create: ") + accum_unsupported(Pipeline::Persistent8, p));
+        if (p->integrator >= RT_INTEGRATOR_HW1 && p->integrator <= RT_INTEGRATOR_HW5) return fail(RT_ERR_UNSUPPORTED, std::string("rt_accum_create: ") + accum_unsupported(Pipeline::Hw1, p));
+    }
+    std::unique_ptr<rt_accum> a(new rt_accum);
+    std::string err;
+    if (!accum_geometry(p, a->view, a->n_pixslots, err)) return fail(RT_ERR_INVALID_ARG, "rt_accum_create: " + err);
+    const bool hw7 = p->integrator == RT_INTEGRATOR_HW7;
+    if (scene->flavor == RT_INTEGRATOR_HW3 || (p->integrator != scene->flavor && !(hw7 && scene->flavor == RT_INTEGRATOR_HW8)))
+        return fail(RT_ERR_INVALID_ARG, "rt_accum_create: this scene was prepared for integrator " + std::to_string(scene->flavor));
+    bool rounds_chosen = false;
+    a->view.samples = 1;
+    const Pipeline pipe = choose_pipeline(scene, p->integrator, a->view, a->n_pixslots / 64u, 1, rounds_chosen);
+    if (const char *why = accum_unsupported(pipe, p)) return fail(RT_ERR_UNSUPPORTED, std::string("rt_accum_create: ") + why);
+    a->scene = scene; a->params = *p; a->params.samples = 0;
+    a->sample_limit = pipe == Pipeline::Persistent6 ? 1 << 24 : 1 << 25; // sample index bits of p6_pack / wf_pack
+    try {
+        HIP_CHECK(hipSetDevice(scene->device));
+        hipStream_t stream = (hipStream_t)p->stream;
+        HIP_CHECK(hipMalloc((void **)&a->d_state, (size_t)(a->n_pixslots ? a->n_pixslots : 1u) * ACCUM_SLOT_BYTES));
+        if (a->n_pixslots) {
+            RenderView R = a->view;
+            R.accum = a->d_state; R.n_pixslots = a->n_pixslots;
+            hipLaunchKernelGGL(dev::accum_seed_kernel, dim3((a->n_pixslots + 255u) / 256u), dim3(256), 0, stream, R);
+            HIP_CHECK(hipGetLastError());
+            HIP_CHECK(hipStreamSynchronize(stream));
+        }
+    } catch (const HipError &e) {
+        return fail(RT_ERR_HIP, e.what());
+    }
+    *out = a.release();
+    return RT_OK;
+}
+
+void rt_accum_destroy(rt_accum *a) {
+    if (a) (void)hipSetDevice(a->scene->device);
+    delete a;
+}
+
+int rt_accum_samples(const rt_accum *a) {
+    if (!a) return fail(RT_ERR_INVALID_ARG, "rt_accum_samples: null argument");
+    return a->samples;
+}
+
+int rt_accum_render(rt_accum *a, int32_t n_samples, rt_stats *stats) {
+    if (!a) return fail(RT_ERR_INVALID_ARG, "rt_accum_render: null argument");
+    if (!a->broken.empty()) return fail(RT_ERR_INVALID_ARG, "rt_accum_render: an earlier slice failed and left the state half advanced (" + a->broken + ")");
+    if (n_samples <= 0) return fail(RT_ERR_INVALID_ARG, "rt_accum_render: n_samples must be positive");
+    if ((int64_t)a->samples + n_samples >= (int64_t)a->sample_limit)
+        return fail(RT_ERR_LIMIT, "rt_accum_render: " + std::to_string(a->samples) + " + " + std::to_string(n_samples) + " samples per pixel do not fit the path records' sample index (below " + std::to_string(a->sample_limit) + ")");
+    rt_render_params p = a->params;
+    p.samples = n_samples;
+    { // what can be refused is refused before anything is launched: the state stays as it was
+        RenderView R = a->view;
+        R.samples = a->samples + n_samples;
+        bool rounds_chosen = false;
+        if (const char *why = accum_unsupported(choose_pipeline(a->scene, p.integrator, R, a->n_pixslots / 64u, 1, rounds_chosen), &p)) return fail(RT_ERR_UNSUPPORTED, std::string("rt_accum_render: ") + why);
+    }
+    const AccumSlice slice{a->d_state, a->samples};
+    const int rc = render_frame(a->scene, &p, nullptr, nullptr, stats, &slice);
+    if (rc != RT_OK) { a->broken = rt_last_error(); return rc; }
+    a->samples += n_samples;
+    return RT_OK;
+}
+
+int rt_accum_resolve(rt_accum *a, uint32_t flags, float *out_rgb, uint8_t *out_rgb8) {
+    if (!a) return fail(RT_ERR_INVALID_ARG, "rt_accum_resolve: null argument");
+    if (!a->broken.empty()) return fail(RT_ERR_INVALID_ARG, "rt_accum_resolve: an earlier slice failed and left the state half advanced (" + a->broken + ")");
+    if (flags & ~RT_FLAG_OUT_DEVICE) return fail(RT_ERR_INVALID_ARG, "rt_accum_resolve: flags other than RT_FLAG_OUT_DEVICE");
+    if (a->samples <= 0) return fail(RT_ERR_INVALID_ARG, "rt_accum_resolve: no samples yet (a picture needs at least one)");
+    OwnedDev rgb_buf, rgb8_buf;
+    try {
+        HIP_CHECK(hipSetDevice(a->scene->device));
+        hipStream_t stream = (hipStream_t)a->params.stream;
+        const bool out_dev = (flags & RT_FLAG_OUT_DEVICE) != 0;
+        RenderView R = a->view;
+        const size_t elems = R.shard_count > 1 ? (size_t)R.n_shard_tiles * R.tile_w * R.tile_h * 3 : (size_t)R.width * R.height * 3;
+        R.out_rgb = out_rgb; R.out_rgb8 = out_rgb8;
+        if (out_rgb && !out_dev) { HIP_CHECK(hipMalloc(&rgb_buf.p, elems * sizeof(float))); R.out_rgb = (float *)rgb_buf.p; }
+        if (out_rgb8 && !out_dev) { HIP_CHECK(hipMalloc(&rgb8_buf.p, elems)); R.out_rgb8 = (uint8_t *)rgb8_buf.p; }
+        R.accum = a->d_state; R.n_pixslots = a->n_pixslots;
+        R.samples = a->samples;
+        R.inv_samples = (float)(1.0 / a->samples); // scene.cpp:176, as rt_render(samples = d) evaluates it
+        if (a->n_pixslots && (out_rgb || out_rgb8)) {
+            hipLaunchKernelGGL(dev::accum_resolve_kernel, dim3((a->n_pixslots + 255u) / 256u), dim3(256), 0, stream, R);
+            HIP_CHECK(hipGetLastError());
+        }
+        if (rgb_buf.p) HIP_CHECK(hipMemcpyAsync(out_rgb, rgb_buf.p, elems * sizeof(float), hipMemcpyDeviceToHost, stream));
+        if (rgb8_buf.p) HIP_CHECK(hipMemcpyAsync(out_rgb8, rgb8_buf.p, elems, hipMemcpyDeviceToHost, stream));
+        HIP_CHECK(hipStreamSynchronize(stream));
+        return RT_OK;
+    } catch (const HipError &e) {
+        return fail(RT_ERR_HIP, e.what());
+    }
+}
+
+int rt_accum_save(rt_accum *a, void *blob, size_t capacity) {
+    if (!a || !blob) return fail(RT_ERR_INVALID_ARG, "rt_accum_save: null argument");
+    if (!a->broken.empty()) return fail(RT_ERR_INVALID_ARG, "rt_accum_save: an earlier slice failed and left the state half advanced (" + a->broken + ")");
+    const size_t state = (size_t)a->n_pixslots * ACCUM_SLOT_BYTES;
+    if (capacity < ACCUM_HEADER_BYTES + state) return fail(RT_ERR_INVALID_ARG, "rt_accum_save: buffer smaller than rt_accum_state_bytes");
+    try {
+        HIP_CHECK(hipSetDevice(a->scene->device));
+        hipStream_t stream = (hipStream_t)a->params.stream;
+        uint32_t h[ACCUM_HEADER_BYTES / 4];
+        accum_header(a, h);
+        memcpy(blob, h, ACCUM_HEADER_BYTES);
+        if (state) HIP_CHECK(hipMemcpyAsync((uint8_t *)blob + ACCUM_HEADER_BYTES, a->d_state, state, hipMemcpyDeviceToHost, stream));
+        HIP_CHECK(hipStreamSynchronize(stream));
+        return RT_OK;
+    } catch (const HipError &e) {
+        return fail(RT_ERR_HIP, e.what());
+    }
+}
+
+int rt_accum_load(rt_accum *a, const void *blob, size_t size) {
+    if (!a || !blob) return fail(RT_ERR_INVALID_ARG, "rt_accum_load: null argument");
+    if (!a->broken.empty()) return fail(RT_ERR_INVALID_ARG, "rt_accum_load: an earlier slice failed and left the state half advanced (" + a->broken + ")");
+    if (size < ACCUM_HEADER_BYTES) return fail(RT_ERR_INVALID_ARG, "rt_accum_load: truncated blob (shorter than its header)");
+    uint32_t want[ACCUM_HEADER_BYTES / 4], got[ACCUM_HEADER_BYTES / 4];
+    accum_header(a, want);
+    memcpy(got, blob, ACCUM_HEADER_BYTES);
+    for (int f = 0; f < AH_WORDS; f++)
+        if (f != AH_SAMPLES && got[f] != want[f])
+            return fail(RT_ERR_INVALID_ARG, std::string("rt_accum_load: the blob does not belong to this frame: ") + accum_field_names[f] + " is " + std::to_string(got[f]) +
+                                                ", expected " + std::to_string(want[f]));
+    if (got[AH_SAMPLES] >= (uint32_t)a->sample_limit) return fail(RT_ERR_INVALID_ARG, "rt_accum_load: samples beyond the path records' sample index");
+    const size_t state = (size_t)a->n_pixslots * ACCUM_SLOT_BYTES;
+    if (size < ACCUM_HEADER_BYTES + state) return fail(RT_ERR_INVALID_ARG, "rt_accum_load: truncated blob (" + std::to_string(size) + " bytes, " + std::to_string(ACCUM_HEADER_BYTES + state) + " expected)");
+    try {
+        HIP_CHECK(hipSetDevice(a->scene->device));
+        hipStream_t stream = (hipStream_t)a->params.stream;
+        if (state) HIP_CHECK(hipMemcpyAsync(a->d_state, (const uint8_t *)blob + ACCUM_HEADER_BYTES, state, hipMemcpyHostToDevice, stream));
+        HIP_CHECK(hipStreamSynchronize(stream));
+        a->samples = (int32_t)got[AH_SAMPLES];
+        return RT_OK;
+    } catch (const HipError &e) {
+        return fail(RT_ERR_HIP, e.what());
     }
 }
 
