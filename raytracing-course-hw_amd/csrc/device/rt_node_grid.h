@@ -25,7 +25,7 @@ inline NodeGrid make_node_grid(const float lo[3], const float hi[3]) {
 }
 
 // One axis of a child box as lo | hi << 16: each bound goes to the cell below / above it and one further — the margin that covers the
-// rounding of the walkers' grid-space ray (rt_device.h make_ray_grid: at most 0.02 cells for an origin inside the grid).
+// rounding of the walkers' grid-space ray and of their FMA slabs (rt_device.h, the budget above RayGrid: at most 0.03 cells for an origin inside the grid).
 // `fits` is cleared when the box does not lie on the grid (the word then spans the whole axis).
 __host__ __device__ inline uint32_t grid_axis_word(float lo, float hi, float grid_lo, float step, bool &fits) {
     const double a = floor(((double)lo - (double)grid_lo) / (double)step) - 1.0;

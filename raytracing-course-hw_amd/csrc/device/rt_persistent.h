@@ -105,8 +105,8 @@ namespace dev {
 #define PT_WIDE_NONE 0                // no child entered: the caller pops its stack
 #define PT_WIDE_WENT 1                // `cur` is the child to visit next, the others wait in the lane's stack column
 #define PT_WIDE_FULL 2                // the column cannot take the children that would wait (nothing was pushed, `cur` unchanged)
-// sort key of a child's entry distance: the bits of max(t, 0) (a negative float, -0 included, is a negative integer)
-RT_DEV uint32_t pt_near_key(float t) { const int b = (int)__float_as_uint(t); return (uint32_t)(b > 0 ? b : 0); }
+// sort key of a child: its entry distance's (rt_device.h slab_enter_q), or the last of all for one that is not entered
+RT_DEV uint32_t pt_near_key(bool entered, uint32_t key) { return entered ? key : 0xFFFFFFFFu; }
 // compare-exchange of (key, child word) pairs: the smaller key first
 RT_DEV void pt_order(uint32_t &ka, uint32_t &ca, uint32_t &kb, uint32_t &cb) {
     const bool s = kb < ka;
@@ -119,11 +119,10 @@ RT_DEV void pt_order(uint32_t &ka, uint32_t &ca, uint32_t &kb, uint32_t &cb) {
 RT_DEV int pt_wide_step_nearest(const GpuNode4Q *nodes, const RayGrid &ray, float cull_t, uint32_t (*stack)[64], int lane, int &sp, int cap, uint32_t &cur) {
     const uint4 *q = reinterpret_cast<const uint4 *>(nodes + cur);
     const uint4 b0 = q[0], b1 = q[1], b2 = q[2], b3 = q[3];
-    float n0, n1, n2, n3;
-    const bool h0 = slab_test_q(b0, ray, cull_t, n0), h1 = slab_test_q(b1, ray, cull_t, n1);
-    const bool h2 = slab_test_q(b2, ray, cull_t, n2), h3 = slab_test_q(b3, ray, cull_t, n3);
-    uint32_t k0 = h0 ? pt_near_key(n0) : 0xFFFFFFFFu, k1 = h1 ? pt_near_key(n1) : 0xFFFFFFFFu;
-    uint32_t k2 = h2 ? pt_near_key(n2) : 0xFFFFFFFFu, k3 = h3 ? pt_near_key(n3) : 0xFFFFFFFFu;
+    uint32_t k0, k1, k2, k3;
+    const bool h0 = slab_enter_q(b0, ray, cull_t, k0), h1 = slab_enter_q(b1, ray, cull_t, k1);
+    const bool h2 = slab_enter_q(b2, ray, cull_t, k2), h3 = slab_enter_q(b3, ray, cull_t, k3);
+    k0 = pt_near_key(h0, k0); k1 = pt_near_key(h1, k1); k2 = pt_near_key(h2, k2); k3 = pt_near_key(h3, k3);
     uint32_t c0 = b0.w, c1 = b1.w, c2 = b2.w, c3 = b3.w;
 #ifndef PT_WIDE_SORT
 #define PT_WIDE_SORT 1
@@ -154,9 +153,7 @@ RT_DEV void pt_wide_enter_all(const GpuNode4Q *nodes, uint32_t cur, const RayGri
                               bool &h0, bool &h1, bool &h2, bool &h3) {
     const uint4 *q = reinterpret_cast<const uint4 *>(nodes + cur);
     b0 = q[0]; b1 = q[1]; b2 = q[2]; b3 = q[3];
-    float n;
-    h0 = slab_test_q(b0, ray, RT_T_MAX, n); h1 = slab_test_q(b1, ray, RT_T_MAX, n);
-    h2 = slab_test_q(b2, ray, RT_T_MAX, n); h3 = slab_test_q(b3, ray, RT_T_MAX, n);
+    h0 = slab_test_q(b0, ray); h1 = slab_test_q(b1, ray); h2 = slab_test_q(b2, ray); h3 = slab_test_q(b3, ray); // no entry distance: every entered child is walked
 }
 // Light sums: every entered child is walked, in any order (the callers keep their hits sorted): the first one now, the others wait.
 RT_DEV int pt_wide_step_all(const GpuNode4Q *nodes, const RayGrid &ray, uint32_t (*stack)[64], int lane, int &sp, int cap, uint32_t &cur) {
@@ -325,9 +322,8 @@ RT_DEV uint32_t pt_pop(uint32_t *bm, int *cnt, const uint32_t nw, uint32_t &curs
     int have = 0;                                                 // wave-uniform, like everything below that is not per word (= per lane) or `got`
     for (uint32_t swept = 0; swept < nw && have < need; swept += 64u) {
         uint32_t w = cursor + lane;
-        bool valid = true;
-        if (nw >= 64u) { if (w >= nw) w -= nw; }
-        else { valid = lane < nw; w = w % nw; }
+        const bool valid = lane < nw;                                 // fewer than 64 words: the wave sees the whole ring at once
+        if (w >= nw) w -= nw;                                         // cursor < nw, and lane < nw where the word is read: no division
         const uint32_t v = valid ? bm[w] : 0u;
         // Every word claims for itself, all in ONE LDS atomic of the wave: word i may take what the words before it leave of the request
         // (a prefix sum of the words' bit counts).  A claim can come back short (another wave was faster); the sweep then goes on.
@@ -369,7 +365,7 @@ RT_DEV uint32_t pt_pop(uint32_t *bm, int *cnt, const uint32_t nw, uint32_t &curs
             }
         }
         cursor = (uint32_t)__builtin_amdgcn_readfirstlane((int)next_cursor);
-        if (cursor >= nw) cursor %= nw;
+        while (cursor >= nw) cursor -= nw;                            // cursor % nw on SGPRs; one round, but for a ring of under 64 words swept without finding enough
     }
     if (have && lane == 0) atomicSub(cnt, have);
     return got;

@@ -69,6 +69,23 @@ __global__ void k_slab_q(const float *in, rtamd::NodeGrid G, uint32_t *out, size
     const bool hq = slab_test_q(b, make_ray_grid(G, o, d), p[12], tq);
     out[i] = (hf ? 1u : 0u) | (hq ? 2u : 0u) | (fits ? 4u : 0u) | (tq <= tn ? 8u : 0u);
 }
+// what the model of slab_test_q (tests/slab_fma_model.py) takes from the device: the reciprocals make_ray_grid forms its 1/d' from, and
+// the grid test's entry distance as it is, for a bit-for-bit comparison
+__global__ void k_slab_q_entry(const float *in, rtamd::NodeGrid G, float *rcp, float *entry, size_t n) {
+    size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float *p = in + 13 * i;
+    for (int k = 0; k < 3; k++) { const float d = p[9 + k]; rcp[3 * i + k] = __builtin_amdgcn_rcpf(fabsf(d) > 1e-30f ? d : copysignf(1e-30f, d)); }
+    bool fits = true;
+    uint4 b;
+    b.x = rtamd::grid_axis_word(p[0], p[3], G.lo[0], G.step[0], fits);
+    b.y = rtamd::grid_axis_word(p[1], p[4], G.lo[1], G.step[1], fits);
+    b.z = rtamd::grid_axis_word(p[2], p[5], G.lo[2], G.step[2], fits);
+    b.w = 0u;
+    float tq = 0.f;
+    (void)slab_test_q(b, make_ray_grid(G, f3(p[6], p[7], p[8]), f3(p[9], p[10], p[11])), p[12], tq);
+    entry[i] = tq;
+}
 
 extern "C" {
 // host/fold_nodes.h on host memory (no GPU needed): nodes = n two-box nodes of 64 bytes, grid_box = lo.xyz hi.xyz of what the grid must hold,
@@ -98,6 +115,20 @@ int rtt_slab_q(const float *cases, const float *grid_box, uint32_t *out, size_t 
         if (hipDeviceSynchronize() == hipSuccess && hipMemcpy(out, d_out, n * 4, hipMemcpyDeviceToHost) == hipSuccess) rc = 0;
     }
     (void)hipFree(d_in); (void)hipFree(d_out);
+    return rc;
+}
+// the same cases: rcp = n x 3 reciprocals of the (clamped) direction components as the device forms them, entry = n unclamped grid entry distances
+int rtt_slab_q_entry(const float *cases, const float *grid_box, float *rcp, float *entry, size_t n) {
+    const rtamd::NodeGrid G = rtamd::make_node_grid(grid_box, grid_box + 3);
+    float *d_in = nullptr, *d_rcp = nullptr, *d_entry = nullptr;
+    int rc = -1;
+    if (hipMalloc((void **)&d_in, n * 13 * 4) == hipSuccess && hipMalloc((void **)&d_rcp, n * 12) == hipSuccess && hipMalloc((void **)&d_entry, n * 4) == hipSuccess &&
+        hipMemcpy(d_in, cases, n * 13 * 4, hipMemcpyHostToDevice) == hipSuccess) {
+        hipLaunchKernelGGL(k_slab_q_entry, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, d_in, G, d_rcp, d_entry, n);
+        if (hipDeviceSynchronize() == hipSuccess && hipMemcpy(rcp, d_rcp, n * 12, hipMemcpyDeviceToHost) == hipSuccess &&
+            hipMemcpy(entry, d_entry, n * 4, hipMemcpyDeviceToHost) == hipSuccess) rc = 0;
+    }
+    (void)hipFree(d_in); (void)hipFree(d_rcp); (void)hipFree(d_entry);
     return rc;
 }
 int rtt_gap_code(const float *t, const float *t2, float *floor_out, uint32_t *code_out, size_t n) {
