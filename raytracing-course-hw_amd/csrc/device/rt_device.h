@@ -311,10 +311,6 @@ RT_DEV bool slab_test(float4 lo, float4 hi, const RayInv &r, float tbest, float 
 }
 
 typedef float rt_f2 __attribute__((ext_vector_type(2)));
-#ifndef PT_SLAB_FMA
-#define PT_SLAB_FMA 1          // a slab of the grid walkers' box test is one FMA, cell * (1/d') + c (1: plain FMAs, 2: packed pairs); 0: the earlier
-                               // (cell - o') * (1/d') with its three-compare test, for A/B builds
-#endif
 // The walk nodes on the 16-bit grid (rt_types.h GpuNode4Q).  The ray moves into grid coordinates once per walk,
 //     o' = (o - grid.lo) / step,   1/d' = step / d      (t keeps its meaning: x = o + t d  <=>  x' = o' + t d'),
 // and a child's slabs are t = cell * (1/d') + c with c = -o' * (1/d') formed once per walk: one FMA per slab.  Cells are small integers,
@@ -330,8 +326,8 @@ typedef float rt_f2 __attribute__((ext_vector_type(2)));
 // A point of the float box lies at least one whole cell inside the grid box on every axis (rt_node_grid.h grid_axis_word), so every t at
 // which the real ray is in the float box stays inside all three computed intervals, and the interval needs no widening of its own.
 // Overflow: |cell * (1/d')| and |c| stay finite while step < 2^127 / (65,536 * 1e30), a scene under 1e8 across; beyond that a NaN slab is
-// ignored by v_max / v_min, which only lets more boxes in.  PT_SLAB_FMA=0 budgets 0.012 + 6 * 2^-8 = 0.035 cells for (cell - o') * (1/d').
-// cx, cy, cz: c (PT_SLAB_FMA=0: o').  sx, sy, sz: byte selectors (v_perm_b32) that put the slab the ray meets first into the low half of
+// ignored by v_max / v_min, which only lets more boxes in.
+// cx, cy, cz: c.  sx, sy, sz: byte selectors (v_perm_b32) that put the slab the ray meets first into the low half of
 // a record's axis word — lo | hi << 16 as stored for a direction component >= 0, the halves swapped for a negative one — so that the test
 // needs no min / max per axis.
 struct RayGrid { float cx, cy, cz, ix, iy, iz; uint32_t sx, sy, sz; };
@@ -348,9 +344,7 @@ RT_DEV RayGrid make_ray_grid(const NodeGrid &G, F3 o, F3 d) {
     RayGrid g;
     g.cx = (o.x - G.lo[0]) * G.istep[0]; g.cy = (o.y - G.lo[1]) * G.istep[1]; g.cz = (o.z - G.lo[2]) * G.istep[2];
     g.ix = G.step[0] * __builtin_amdgcn_rcpf(dx); g.iy = G.step[1] * __builtin_amdgcn_rcpf(dy); g.iz = G.step[2] * __builtin_amdgcn_rcpf(dz);
-#if PT_SLAB_FMA
     g.cx = -g.cx * g.ix; g.cy = -g.cy * g.iy; g.cz = -g.cz * g.iz;
-#endif
     g.sx = g.ix < 0.f ? 0x01000302u : 0x03020100u; g.sy = g.iy < 0.f ? 0x01000302u : 0x03020100u; g.sz = g.iz < 0.f ? 0x01000302u : 0x03020100u;
     return g;
 }
@@ -358,19 +352,9 @@ RT_DEV RayGrid make_ray_grid(const NodeGrid &G, F3 o, F3 d) {
 // pairs of slabs (tmin unclamped: negative for an origin inside).
 RT_DEV void slab_span_q(uint4 b, const RayGrid &r, float &tmin, float &tmax) {
     const uint32_t wx = __builtin_amdgcn_perm(b.x, b.x, r.sx), wy = __builtin_amdgcn_perm(b.y, b.y, r.sy), wz = __builtin_amdgcn_perm(b.z, b.z, r.sz);
-#if PT_SLAB_FMA == 2
-    const rt_f2 x = __builtin_elementwise_fma(rt_f2{(float)(wx & 0xFFFFu), (float)(wx >> 16)}, rt_f2{r.ix, r.ix}, rt_f2{r.cx, r.cx}); // (entry, exit) along x
-    const rt_f2 y = __builtin_elementwise_fma(rt_f2{(float)(wy & 0xFFFFu), (float)(wy >> 16)}, rt_f2{r.iy, r.iy}, rt_f2{r.cy, r.cy});
-    const rt_f2 z = __builtin_elementwise_fma(rt_f2{(float)(wz & 0xFFFFu), (float)(wz >> 16)}, rt_f2{r.iz, r.iz}, rt_f2{r.cz, r.cz});
-#elif PT_SLAB_FMA
     const rt_f2 x = {__builtin_fmaf((float)(wx & 0xFFFFu), r.ix, r.cx), __builtin_fmaf((float)(wx >> 16), r.ix, r.cx)}; // (entry, exit) along x
     const rt_f2 y = {__builtin_fmaf((float)(wy & 0xFFFFu), r.iy, r.cy), __builtin_fmaf((float)(wy >> 16), r.iy, r.cy)};
     const rt_f2 z = {__builtin_fmaf((float)(wz & 0xFFFFu), r.iz, r.cz), __builtin_fmaf((float)(wz >> 16), r.iz, r.cz)};
-#else
-    const rt_f2 x = (rt_f2{(float)(wx & 0xFFFFu), (float)(wx >> 16)} - r.cx) * r.ix; // (entry, exit) along x: the products keep that order
-    const rt_f2 y = (rt_f2{(float)(wy & 0xFFFFu), (float)(wy >> 16)} - r.cy) * r.iy;
-    const rt_f2 z = (rt_f2{(float)(wz & 0xFFFFu), (float)(wz >> 16)} - r.cz) * r.iz;
-#endif
     tmin = fmaxf(fmaxf(x.x, y.x), z.x);
     tmax = fminf(fminf(x.y, y.y), z.y);
 }
@@ -379,35 +363,21 @@ RT_DEV void slab_span_q(uint4 b, const RayGrid &r, float &tmin, float &tmax) {
 RT_DEV bool slab_enter_q(uint4 b, const RayGrid &r, float tbest, uint32_t &key) {
     float tmin, tmax;
     slab_span_q(b, r, tmin, tmax);
-#if PT_SLAB_FMA
     const float t0 = fmaxf(tmin, 0.f);
     key = __float_as_uint(t0);
     return t0 <= fminf(tmax, tbest);
-#else
-    const int kb = (int)__float_as_uint(tmin);       // a negative float, -0 included, is a negative integer
-    key = (uint32_t)(kb > 0 ? kb : 0);
-    return (tmin <= tmax) & (tmax >= 0.f) & (tmin <= tbest);
-#endif
 }
 // The same decision; tnear = tmin as it is, unclamped.
 RT_DEV bool slab_test_q(uint4 b, const RayGrid &r, float tbest, float &tnear) {
     float tmax;
     slab_span_q(b, r, tnear, tmax);
-#if PT_SLAB_FMA
     return fmaxf(tnear, 0.f) <= fminf(tmax, tbest);
-#else
-    return (tnear <= tmax) & (tmax >= 0.f) & (tnear <= tbest);
-#endif
 }
 // With no bound on t (the light sums enter every box on the ray): slab_test_q at tbest = inf.
 RT_DEV bool slab_test_q(uint4 b, const RayGrid &r) {
     float tmin, tmax;
     slab_span_q(b, r, tmin, tmax);
-#if PT_SLAB_FMA
     return fmaxf(tmin, 0.f) <= tmax;
-#else
-    return (tmin <= tmax) & (tmax >= 0.f) & (tmin <= RT_T_MAX);
-#endif
 }
 
 #define RT_LEAF_BIT 0x80000000u

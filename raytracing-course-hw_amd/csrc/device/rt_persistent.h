@@ -46,14 +46,9 @@ namespace dev {
 // workgroup, five of which fill the CU's 160 KB (handed out in 1,280-byte granules: 25 granules each).
 #define P8_WAVES 4
 #define P8_THREADS (64 * P8_WAVES)
-#ifndef P8_PER_CU
 #define P8_PER_CU 5
-#endif
 #define P8_STACK 24                   // LDS traversal stack entries per lane; the walkers' tree is built at most this deep (rt_bvh_build.h)
-#ifndef PT_MAX_PATHS
-#define PT_MAX_PATHS 5120
-#endif
-#define PT_MAX_PATHS_NOTE             // paths per workgroup (bitmap capacity in LDS): x 1,280 workgroups = 6.5 M (a 3840x2160 frame on one GPU: two passes)
+#define PT_MAX_PATHS 5120             // paths per workgroup (bitmap capacity in LDS): x 1,280 workgroups = 6.5 M (a 3840x2160 frame on one GPU: two passes)
 #define PT_MIN_GROUP 16               // smallest group of the deal (group_shift 4): the LDS tables are sized for it
 #define PT_NW (PT_MAX_PATHS / 32)
 #define PT_BIT_T 1u                   // pending: closest-hit walk outstanding
@@ -71,34 +66,12 @@ namespace dev {
 #define PT_GSHIFT 15                  // cnt only: PtParams::group_shift (constant during the launch)
 // What a sub-tile costs its workgroup, in units of one closest-hit node step (wave time by role over steps by role on the benchmark
 // scene): the measure the frame is re-dealt by after its first phase.  Counting shaded hits alone misses the rays that hit nothing.
-#ifndef PT_COST_TRACE_NODE
 #define PT_COST_TRACE_NODE 1u     // a node visit of a closest-hit walk
-#endif
 #define PT_COST_TRACE_TRI 1u      // a triangle test of a closest-hit walk
-#ifndef PT_COST_LIGHT_NODE
 #define PT_COST_LIGHT_NODE 2u     // a node visit of a light-sum walk
-#endif
 #define PT_COST_LIGHT_TEST 2u     // a light test of a light-sum walk
 #define PT_COST_SHADE 14u
 #define PT_DEBUG_BLOCKS 2048           // RTAMD_DEBUG_COUNTERS: workgroups whose start / exit times are recorded (>= 256 CUs x 5)
-#ifndef PT_QUANT_NODES
-#define PT_QUANT_NODES 1       // the walkers read the four-wide grid nodes (rt_types.h GpuNode4Q: two levels per fetch); 0 = the two-box float nodes, for A/B builds
-#endif
-#ifndef PT_POSTPONE
-#define PT_POSTPONE 1          // walkers keep a leaf they meet for the next leaf phase and walk on (0: they wait at it), for A/B builds
-#endif
-#if !PT_QUANT_NODES
-#undef PT_POSTPONE
-#define PT_POSTPONE 0          // the two-box float path keeps the plain loop
-#endif
-#ifndef PT_PEND_SLOTS
-#define PT_PEND_SLOTS 3        // leaves a lane may hold for the next leaf phase (2 or 3)
-#endif
-#if PT_PEND_SLOTS == 3
-#define PT_LAST_SLOT pend3
-#else
-#define PT_LAST_SLOT pend2
-#endif
 #define PT_DRAINED 0xFFFFFFFEu        // `cur` of a lane whose stack is empty and whose last leaf is still to be tested (reads as a leaf: the lane waits)
 #define PT_T_OVERFLOW (-1.f)          // t of a closest-hit record whose walk ran out of stack: the exact role redoes the query
 // ---- one step of a walk over the four-wide grid nodes (rt_types.h GpuNode4Q), shared with rt_persistent_hw6.h ------------------------
@@ -124,26 +97,13 @@ RT_DEV int pt_wide_step_nearest(const GpuNode4Q *nodes, const RayGrid &ray, floa
     const bool h2 = slab_enter_q(b2, ray, cull_t, k2), h3 = slab_enter_q(b3, ray, cull_t, k3);
     k0 = pt_near_key(h0, k0); k1 = pt_near_key(h1, k1); k2 = pt_near_key(h2, k2); k3 = pt_near_key(h3, k3);
     uint32_t c0 = b0.w, c1 = b1.w, c2 = b2.w, c3 = b3.w;
-#ifndef PT_WIDE_SORT
-#define PT_WIDE_SORT 1
-#endif
-#if PT_WIDE_SORT
     pt_order(k0, c0, k1, c1); pt_order(k2, c2, k3, c3); pt_order(k0, c0, k2, c2); pt_order(k1, c1, k3, c3); pt_order(k1, c1, k2, c2);
-#else
-    pt_order(k0, c0, k1, c1); pt_order(k2, c2, k3, c3); pt_order(k0, c0, k2, c2); // only the nearest is singled out; the others wait in any order
-#endif
     const int nh = (int)h0 + (int)h1 + (int)h2 + (int)h3;
     if (nh == 0) return PT_WIDE_NONE;
     if (sp + nh - 1 > cap) return PT_WIDE_FULL;
-#if PT_WIDE_SORT
     if (nh > 3) stack[sp++][lane] = c3;
     if (nh > 2) stack[sp++][lane] = c2;
     if (nh > 1) stack[sp++][lane] = c1;
-#else
-    if (k3 != 0xFFFFFFFFu) stack[sp++][lane] = c3;
-    if (k2 != 0xFFFFFFFFu) stack[sp++][lane] = c2;
-    if (k1 != 0xFFFFFFFFu) stack[sp++][lane] = c1;
-#endif
     cur = c0;
     return PT_WIDE_WENT;
 }
@@ -170,24 +130,9 @@ RT_DEV int pt_wide_step_all(const GpuNode4Q *nodes, const RayGrid &ray, uint32_t
     cur = first == 0 ? b0.w : first == 1 ? b1.w : first == 2 ? b2.w : b3.w;
     return PT_WIDE_WENT;
 }
-#if PT_QUANT_NODES
-typedef RayGrid PtRay;
-#define PT_RAY_IDLE RT_GRID_RAY_IDLE
-RT_DEV PtRay pt_make_ray(const SceneView &S, F3 o, F3 d) { return make_ray_grid(S.grid, o, d); }
-#else
-typedef RayInv PtRay;
-#define PT_RAY_IDLE {{0.f, 0.f, 0.f}, {1.f, 1.f, 1.f}}
-RT_DEV PtRay pt_make_ray(const SceneView &, F3 o, F3 d) { return make_ray_inv(o, d); }
-#endif
-#ifndef PT_LIGHT_SETTLE
-#define PT_LIGHT_SETTLE 1      // the shader settles the light sums whose walk enters no record of the light tree's root (1), or no record
-                               // below the root's either (2), instead of handing them to the light walker; 0: every sum is walked, for A/B builds
-#endif
-#if !PT_QUANT_NODES
-#undef PT_LIGHT_SETTLE
-#define PT_LIGHT_SETTLE 0      // the two-box float path walks every sum
-#endif
-#if PT_QUANT_NODES
+// The shader settles the light sums whose walk enters no record of the light tree's root (pt_light_reach < PT_LIGHT_SETTLE) instead of
+// handing them to the light walker.
+#define PT_LIGHT_SETTLE 1
 // How far the light walker's walk of this ray would get before its first light test, taking the walker's own decisions
 // (pt_wide_enter_all): 0 = it enters no record of the light tree's root; 1 = it enters inner nodes there but none of their records;
 // 2 = it goes further (or LEVELS < 2 and it enters the root).  `steps`: the node steps that took.  A walk that ends at 0 or 1 tests no
@@ -211,7 +156,6 @@ RT_DEV int pt_light_reach(const SceneView &S, const RayGrid &ray, int &steps) {
     }
     return 1;
 }
-#endif
 #define PT_EXACT_BATCH 16             // the exact role walks at most this many queries at once: their stacks (RT_STACK_SIZE entries each) share the wave's LDS stack area
 
 struct PtShared {
@@ -249,10 +193,10 @@ struct PtParams {
     float4 *trace_buf; uint32_t trace_cap; int32_t trace_pixel;
 };
 
-// COUNT builds only: where a wave's time goes (shader-clock cycles per role) and how full its walker iterations are
+// COUNT builds only: where a wave's time goes (shader-clock cycles per role) and how full its walker iterations are ([2]: closest-hit | light walker)
 struct PtProf {
     unsigned long long t_trace = 0, t_light = 0, t_shade = 0, t_exact = 0, t_idle = 0;
-    unsigned long long trace_iters = 0, trace_lane_iters = 0, light_iters = 0, light_lane_iters = 0, stints = 0, shade_batches = 0, shade_items = 0;
+    unsigned long long iters[2] = {0, 0}, lane_iters[2] = {0, 0}, stints = 0, shade_batches = 0, shade_items = 0;
     // where a walker's wave time goes (counting build): [0] hand-off and refill, [1] inner nodes, [2] leaves; tests / lane-tests of the leaf loops; light hits
     unsigned long long t_part[2][3] = {{0, 0, 0}, {0, 0, 0}}, leaf_iters[2] = {0, 0}, leaf_lane_iters[2] = {0, 0}, light_hits = 0, light_tests = 0; // the last two per lane
     unsigned long long t_sub[2][3] = {{0, 0, 0}, {0, 0, 0}}, refills[2] = {0, 0}; // of [0]: publish finished walks | take new ones from the bitmap | read their rays
@@ -390,190 +334,248 @@ template <class SH> RT_DEV void pt_complete(SH &sh, uint32_t l, uint32_t bit, bo
     pt_push(sh, PT_Q_SHADE, l, ready);
 }
 
-// ---- closest-hit walker ------------------------------------------------------------------------------------------------
-// The traversal loop of rt_wavefront.h (while-while, near-first, tie -> lowest figure index) fed from the need_trace bitmap.
-// A finished lane keeps its path index in `fin` until the next refill point, where the wave orders its record stores before
-// the LDS hand-off with one workgroup-scope release.
-template <bool COUNT>
-RT_DEV void pt_trace_stint(const SceneView &S, const WfView &W, PtShared &sh, const PtParams &P, PtWave &wv, uint32_t (*stack)[64],
-                           const int shade_thr, uint32_t &n_queries, unsigned long long &n_nodes, unsigned long long &n_tris, PtProf &prof) {
+// ---- the walker loop -----------------------------------------------------------------------------------------------------------
+// The traversal loop of rt_wavefront.h (while-while) with its lanes refilled from a `need` bitmap: the one loop of the closest-hit and
+// the light-sum walkers of this file and of rt_persistent_hw6.h.  A walker is a policy WK, a struct that holds the per-walk state of a
+// lane and says what differs between the four:
+//   Queue                           which queue it serves and how a finished lane is published (PtTraceQueue, PtLightQueue)
+//   COST_NODE, COST_TEST            what a node step / a leaf test adds to the walk's `steps`, the cost measure of the re-deal (PT_COST_*)
+//   begin(slot)                     read the ray from the path's record, reset the walk's state
+//   step(cur, sp)                   one wide step (PT_WIDE_*); full(): what a full stack column means for the walk
+//   Leaf, test(i, sp, lf)           the state of one leaf phase and its per-triangle body: tests record i, returns whether it was its leaf's last
+//   leaves_done(lf, sp)             after a lane's leaf loop; returns whether the walk is over whatever its stack holds
+//   end(l, slot, steps)             the end of a walk: writes its result, returns the lane's `fin` word (path l, bit 31 for the queue's use)
+// Two measured tuning choices are parameters (DESIGN.md, section 3 "leaf phases"); nothing else depends on who is served:
+//   SLOTS  leaves a lane may park for the next leaf phase: 3 for hw8 (one slot 380, two 396 -> 414 Msamples/s, the third +0.6 %), 2 for hw6
+//   DEFER  the end of a walk runs once per pass for all lanes that ended in it (hw8: +1.2 %), or at once where the walk ends (the hw6
+//          kernel lost 3 % with the deferred form and keeps the immediate one)
+struct PtTraceQueue {
+    static constexpr int ID = PT_Q_TRACE;
+    static RT_DEV int refill_at(const PtParams &P) { return P.refill & 0xFFFF; }
+    template <class SH> static RT_DEV void publish(SH &sh, uint32_t fin) { pt_complete(sh, fin, PT_BIT_T, fin != PT_NONE); }
+};
+// bit 31 of `fin`: the sum is left to a rare role (queue RARE: PT_Q_XLIGHT, P6_Q_SLOW), which completes the path's light bit in its turn
+template <int RARE> struct PtLightQueue {
+    static constexpr int ID = PT_Q_LIGHT;
+    static RT_DEV int refill_at(const PtParams &P) { return P.refill >> 16; }
+    template <class SH> static RT_DEV void publish(SH &sh, uint32_t fin) {
+        const bool slow = (fin >> 31) != 0u && fin != PT_NONE;
+        pt_complete(sh, fin, PT_BIT_L, fin != PT_NONE && !slow);
+        pt_push(sh, RARE, fin & 0x7FFFFFFFu, slow);
+    }
+};
+// the work of a finished walk, booked to its path's group (PtShared::cost)
+template <class SH> RT_DEV void pt_book_cost(SH &sh, const PtParams &P, uint32_t l, uint32_t steps) {
+    if (P.group_cost) atomicAdd(&sh.cost[l >> pt_gshift(sh)], steps);
+}
+
+template <int SLOTS, bool DEFER, bool COUNT, class WK, class SH>
+RT_DEV void pt_walk_stint(WK &w, SH &sh, const PtParams &P, PtWave &wv, uint32_t (*stack)[64], const int shade_thr,
+                          uint32_t &n_queries, unsigned long long &n_nodes, unsigned long long &n_tris, PtProf &prof) {
+    static_assert(SLOTS == 2 || SLOTS == 3, "a lane parks two or three leaves");
+    typedef typename WK::Queue Q;
+    constexpr int K = Q::ID; // PtProf's index of the walker
     const int lane = threadIdx.x & 63;
-    bool active = false, refill_ok = true, ending = false; // ending: the walk is over, its record is written at the next hand-off test
-    uint32_t l = 0, slot = 0, cur = 0, hit = WF_MISS, fin = PT_NONE;
+    bool active = false, refill_ok = true, ending = false; // ending (DEFER): the walk is over, its end() runs at the top of the next pass
+    uint32_t l = 0, slot = 0, cur = 0, fin = PT_NONE;      // fin: the lane's finished, unpublished path
     int sp = 0;
-    uint32_t pend = RT_EMPTY_LEAF, pend2 = RT_EMPTY_LEAF, pend3 = RT_EMPTY_LEAF; (void)pend; (void)pend2; (void)pend3; // PT_POSTPONE: the leaves this lane has met and not yet tested (pend first)
-    uint32_t steps = 0;   // node steps + triangle tests of the lane's current walk: the cost measure of the re-deal (PT_COST_*)
+    uint32_t pend = RT_EMPTY_LEAF, pend2 = RT_EMPTY_LEAF, pend3 = RT_EMPTY_LEAF; // the leaves this lane has met and not yet tested (pend first)
+    uint32_t steps = 0;   // node steps + leaf tests of the lane's current walk, weighted
+    auto end_walk = [&]() {
+        active = false;
+        if (DEFER) ending = true; else fin = w.end(l, slot, steps);
+    };
+    PtLap<COUNT> clk;
+    for (;;) {
+        // Walks that ended since the last pass write their results here, together: in the loops below a lane only marks itself, so the
+        // code of an ending (gap code or sum, record store, cost counter) runs once per pass and not in every step in which some lane ends.
+        if (DEFER && pt_ballot(ending)) {
+            if (ending) { fin = w.end(l, slot, steps); ending = false; }
+        }
+        const unsigned long long idle = pt_ballot(!active);
+        if (idle && (__popcll(idle) >= Q::refill_at(P) || idle == ~0ull)) {
+            // Hand-off point.  Finished lanes are published here and not the moment they finish: the release (a wait for the
+            // wave's outstanding record stores) is paid once per refill, when the stores have long landed, not once per walk.
+            PtLap<COUNT> sub;
+            if (COUNT) prof.refills[K]++;
+            if (pt_ballot(fin != PT_NONE)) {
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+                Q::publish(sh, fin);
+                fin = PT_NONE;
+            }
+            sub.lap(prof.t_sub[K][0]);
+            if (!refill_ok) {}
+            else if (pt_count(&sh.cnt[PT_Q_SHADE]) >= shade_thr) refill_ok = false;      // shaders are behind: drain, then help them
+            else if (pt_count(&sh.cnt[Q::ID]) > 0) {
+                const uint32_t got = pt_pop(sh.need[Q::ID], &sh.cnt[Q::ID], wv.nw, wv.cur[Q::ID], !active, wv.front_first);
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+                sub.lap(prof.t_sub[K][1]);
+                n_queries += __popcll(pt_ballot(got != PT_NONE));
+                if (got != PT_NONE) {
+                    l = got; slot = pt_slot(sh, l);
+                    w.begin(slot);
+                    steps = 0;
+                    cur = 0; sp = 0; pend = RT_EMPTY_LEAF; pend2 = RT_EMPTY_LEAF; pend3 = RT_EMPTY_LEAF;
+                    active = true;
+                }
+                sub.lap(prof.t_sub[K][2]);
+            }
+        }
+        const unsigned long long m_active = pt_ballot(active);
+        clk.lap(prof.t_part[K][0]);
+        if (!m_active) break;
+        const int lb = pt_leaf_batch(P.leaf_batch, m_active);
+        for (;;) { // phase 1: inner nodes
+            // A lane that meets a leaf keeps it for the next leaf phase and walks on with what its stack holds (a leaf beyond its slots stops
+            // it): more lanes stay in the node loop, and more of them bring a leaf to each leaf phase.
+            if (active && (cur & RT_LEAF_BIT) && (SLOTS == 3 ? pend3 : pend2) == RT_EMPTY_LEAF && cur != PT_DRAINED) {
+                if (pend == RT_EMPTY_LEAF) pend = cur; else if (SLOTS == 2 || pend2 == RT_EMPTY_LEAF) pend2 = cur; else pend3 = cur; // (an empty leaf leaves the slot as it was)
+                cur = sp == 0 ? PT_DRAINED : stack[--sp][lane];
+                if (cur == PT_DRAINED && pend == RT_EMPTY_LEAF) end_walk(); // an empty leaf was all that was left
+            }
+            const bool inner = active && !(cur & RT_LEAF_BIT);
+            if (!pt_ballot(inner) || __popcll(pt_ballot(active && (cur & RT_LEAF_BIT))) >= lb) break;
+            if (COUNT) { prof.iters[K]++; prof.lane_iters[K] += __popcll(pt_ballot(inner)); }
+            if (inner) {
+                if (COUNT) n_nodes++;
+                steps += WK::COST_NODE;
+                const int went = w.step(cur, sp);
+                if (went == PT_WIDE_NONE) {
+                    if (sp != 0) cur = stack[--sp][lane];
+                    else if (pend != RT_EMPTY_LEAF) cur = PT_DRAINED;
+                    else end_walk();
+                } else if (went == PT_WIDE_FULL) { // the walk ends here, the parked leaves untested: a rare role redoes the query
+                    w.full();
+                    pend = RT_EMPTY_LEAF; pend2 = RT_EMPTY_LEAF; pend3 = RT_EMPTY_LEAF;
+                    end_walk();
+                }
+            }
+        }
+        clk.lap(prof.t_part[K][1]);
+        const bool at_leaf = active && pend != RT_EMPTY_LEAF;
+        if (COUNT) { prof.leaf_iters[K]++; prof.leaf_lane_iters[K] += __popcll(pt_ballot(at_leaf)); }
+        if (at_leaf) { // phase 2: the lane's parked leaves, in the order it met them
+            uint32_t i = pend & ~RT_LEAF_BIT, more = pend2, more2 = pend3;
+            typename WK::Leaf lf;
+            for (;;) { // ONE loop over all of them: a lane goes on to its next leaf while its neighbours are still in their first
+                const bool last = w.test(i, sp, lf);
+                if (COUNT) n_tris++;
+                steps += WK::COST_TEST;
+                if (!last) i++;
+                else if (more == RT_EMPTY_LEAF) break;
+                else { i = more & ~RT_LEAF_BIT; more = more2; more2 = RT_EMPTY_LEAF; } // the lane's next leaf
+            }
+            const bool over = w.leaves_done(lf, sp);
+            pend = RT_EMPTY_LEAF; pend2 = RT_EMPTY_LEAF; pend3 = RT_EMPTY_LEAF;
+            if (cur == PT_DRAINED || over) end_walk(); // a lane that stopped at a leaf beyond its slots keeps that for the next round
+        }
+        clk.lap(prof.t_part[K][2]);
+    }
+}
+
+// ---- closest-hit walker: near-first, tie -> lowest figure index ---------------------------------------------------------------------
+struct PtTraceWalk {
+    typedef PtTraceQueue Queue;
+    static constexpr uint32_t COST_NODE = PT_COST_TRACE_NODE, COST_TEST = PT_COST_TRACE_TRI;
+    const SceneView &S; const WfView &W; PtShared &sh; const PtParams &P; uint32_t (*stack)[64];
+    const int lane = threadIdx.x & 63;
     F3 o = f3(0.f, 0.f, 0.f), d = f3(0.f, 0.f, 1.f);
-    PtRay ray = PT_RAY_IDLE; // idle lanes: never used
+    RayGrid ray = RT_GRID_RAY_IDLE; // idle lanes: never used
+    uint32_t hit = WF_MISS;
     float best_t = RT_T_MAX, best_u = 0.f, best_v = 0.f;
     // Boxes are pruned, and farther hits dropped, only beyond cull_t = best_t + the look-behind of rt_exact.h: the runner-up of the
     // best hit must be SEEN, whatever tree the walk uses, to decide at the end of the walk whether the exact walk is needed.
     float cull_t = RT_T_MAX, t2 = 2.f * RT_T_MAX, h_ray = 0.f; // h_ray: absolute part of the look-behind (pt_look_behind)
-    auto store_hit = [&]() { // the gate (pt_shade_item) decides with the runner-up's t whether this hit needs the exact walk
-        wf_rec(W, slot)[2] = make_float4(best_t, best_u, best_v, __uint_as_float(S.exact_boxes && hit != WF_MISS ? hit | pt_gap_code(best_t, t2) : hit));
-        if (P.group_cost) atomicAdd(&sh.cost[l >> pt_gshift(sh)], steps);
-    };
-    PtLap<COUNT> clk;
-    for (;;) {
-        // Walks that ended since the last pass write their records here, together: in the loops below a lane only marks itself, so the
-        // code of an ending (gap code, record store, cost counter) runs once per pass and not in every step in which some lane ends.
-        if (pt_ballot(ending)) {
-            if (ending) { store_hit(); fin = l; ending = false; }
-        }
-        const unsigned long long idle = pt_ballot(!active);
-        if (idle && (__popcll(idle) >= (P.refill & 0xFFFF) || idle == ~0ull)) {
-            // Hand-off point.  Finished lanes are published here and not the moment they finish: the release (a wait for the
-            // wave's outstanding record stores) is paid once per refill, when the stores have long landed, not once per walk.
-            PtLap<COUNT> sub;
-            if (COUNT) prof.refills[0]++;
-            if (pt_ballot(fin != PT_NONE)) {
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-                pt_complete(sh, fin, PT_BIT_T, fin != PT_NONE);
-                fin = PT_NONE;
-            }
-            sub.lap(prof.t_sub[0][0]);
-            if (!refill_ok) {}
-            else if (pt_count(&sh.cnt[PT_Q_SHADE]) >= shade_thr) refill_ok = false;      // shaders are behind: drain, then help them
-            else if (pt_count(&sh.cnt[PT_Q_TRACE]) > 0) {
-                const uint32_t got = pt_pop(sh.need[PT_Q_TRACE], &sh.cnt[PT_Q_TRACE], wv.nw, wv.cur[PT_Q_TRACE], !active, wv.front_first);
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-                sub.lap(prof.t_sub[0][1]);
-                n_queries += __popcll(pt_ballot(got != PT_NONE));
-                if (got != PT_NONE) {
-                    l = got; slot = pt_slot(sh, l);
-                    const float4 *r = wf_rec(W, slot);
-                    float4 q0 = r[0], q1 = r[1];
-                    o = f3(q0.x, q0.y, q0.z); d = f3(q0.w, q1.x, q1.y);
-                    ray = pt_make_ray(S, o, d);
-                    h_ray = S.exact_boxes ? pt_look_behind_abs(d, S.box_c2x) : 0.f;
-                    steps = 0;
-                    cur = 0; sp = 0; pend = RT_EMPTY_LEAF; pend2 = RT_EMPTY_LEAF; pend3 = RT_EMPTY_LEAF; hit = WF_MISS; best_t = RT_T_MAX; cull_t = RT_T_MAX; t2 = 2.f * RT_T_MAX; best_u = 0.f; best_v = 0.f;
-                    active = true;
-                }
-                if (COUNT) { asm volatile("" : "+v"(cull_t)); sub.lap(prof.t_sub[0][2]); }
-            }
-        }
-        const unsigned long long m_active = pt_ballot(active);
-        clk.lap(prof.t_part[0][0]);
-        if (!m_active) break;
-        const int lb = pt_leaf_batch(P.leaf_batch, m_active);
-        for (;;) { // phase 1: inner nodes
-#if PT_POSTPONE
-            // A lane that meets a leaf keeps it for the next leaf phase and walks on with what its stack holds (a second leaf stops it):
-            // more lanes stay in the node loop, and more of them bring a leaf to each leaf phase.
-            if (active && (cur & RT_LEAF_BIT) && PT_LAST_SLOT == RT_EMPTY_LEAF && cur != PT_DRAINED) {
-                if (pend == RT_EMPTY_LEAF) pend = cur; else if (pend2 == RT_EMPTY_LEAF) pend2 = cur; else pend3 = cur; // (an empty leaf leaves the slot as it was)
-                cur = sp == 0 ? PT_DRAINED : stack[--sp][lane];
-                if (cur == PT_DRAINED && pend == RT_EMPTY_LEAF) { active = false; ending = true; } // an empty leaf was all that was left
-            }
-#endif
-            const bool inner = active && !(cur & RT_LEAF_BIT);
-            if (!pt_ballot(inner) || __popcll(pt_ballot(active && (cur & RT_LEAF_BIT))) >= lb) break;
-            if (COUNT) { prof.trace_iters++; prof.trace_lane_iters += __popcll(pt_ballot(inner)); }
-            if (inner) {
-                if (COUNT) n_nodes++;
-                steps += PT_COST_TRACE_NODE;
-#if PT_QUANT_NODES
-                const int went = pt_wide_step_nearest(S.nodes4, ray, cull_t, stack, lane, sp, P8_STACK, cur);
-                if (went == PT_WIDE_NONE) {
-#if PT_POSTPONE
-                    if (sp != 0) cur = stack[--sp][lane];
-                    else if (pend != RT_EMPTY_LEAF) cur = PT_DRAINED;
-                    else { active = false; ending = true; }
-#else
-                    if (sp == 0) { active = false; ending = true; }
-                    else cur = stack[--sp][lane];
-#endif
-                } else if (went == PT_WIDE_FULL) {
-                    // The column is full (a walk holds up to three entries per level of a tree of up to P8_STACK / 2 levels; this takes a
-                    // ray that grazes many boxes: triangle soups).  The walk ends here and says so — no hit has a negative t — and the
-                    // exact role walks the query with a stack of its own (pt_exact_batch).
-                    best_t = PT_T_OVERFLOW; best_u = 0.f; best_v = 0.f; hit = 0u; t2 = PT_T_OVERFLOW;
-                    active = false; ending = true; pend = RT_EMPTY_LEAF; pend2 = RT_EMPTY_LEAF; pend3 = RT_EMPTY_LEAF;
-                }
-#else
-                float n0, n1;
-                const float4 *q = reinterpret_cast<const float4 *>(S.nodes + cur);
-                float4 lo0 = q[0], hi0 = q[1], lo1 = q[2], hi1 = q[3];
-                bool h0 = slab_test(lo0, hi0, ray, cull_t, n0);
-                bool h1 = slab_test(lo1, hi1, ray, cull_t, n1);
-                uint32_t c0 = __float_as_uint(lo0.w), c1 = __float_as_uint(lo1.w);
-                if (h0 & h1) {
-                    bool swap = n1 < n0;
-                    stack[sp++][lane] = swap ? c0 : c1;
-                    cur = swap ? c1 : c0;
-                } else if (h0) cur = c0;
-                else if (h1) cur = c1;
-                else if (sp == 0) {
-                    store_hit();
-                    active = false; fin = l;
-                } else cur = stack[--sp][lane];
-#endif
-            }
-        }
-        clk.lap(prof.t_part[0][1]);
-#if PT_POSTPONE
-        const bool at_leaf = active && pend != RT_EMPTY_LEAF;
-        const uint32_t leaf = pend;
-        uint32_t more = pend2, more2 = pend3;
-#else
-        const bool at_leaf = active && (cur & RT_LEAF_BIT);
-        const uint32_t leaf = cur;
-        uint32_t more = RT_EMPTY_LEAF, more2 = RT_EMPTY_LEAF;
-#endif
-        if (COUNT) { prof.leaf_iters[0]++; prof.leaf_lane_iters[0] += __popcll(pt_ballot(at_leaf)); }
-        if (at_leaf) { // phase 2: leaves
-            if (leaf != RT_EMPTY_LEAF) {
-                uint32_t i = leaf & ~RT_LEAF_BIT;
-                for (;;) {
-                    TriIsect T = load_isect(S.tri_walk + i);
-                    if (COUNT) n_tris++;
-                    steps += PT_COST_TRACE_TRI;
-                    float t, u, v; bool inside;
-                    const uint32_t fi = T.pad >> 1; // index in the figure order
-                    if (tri_test_closer(T, o, d, cull_t, t, u, v, inside)) {
-                        const uint32_t best_i = hit & WF_INDEX_MASK;
-                        if (t < best_t || (t == best_t && fi < best_i)) { // reference tie rule: smallest t, equal t -> lowest figure index
-                            t2 = fminf(t2, best_t);
-                            best_t = t; best_u = u; best_v = v; hit = fi | (inside ? WF_INSIDE_BIT : 0u);
-                            cull_t = t + fmaxf(S.cull_k * t, h_ray);
-                        } else t2 = fminf(t2, t);
-                    }
-                    if (!(T.pad & 1u)) i++;
-                    else if (more == RT_EMPTY_LEAF) break;
-                    else { i = more & ~RT_LEAF_BIT; more = more2; more2 = RT_EMPTY_LEAF; } // the lane's next leaf
-                }
-            }
-#if PT_POSTPONE
-            pend = RT_EMPTY_LEAF; pend2 = RT_EMPTY_LEAF; pend3 = RT_EMPTY_LEAF;
-            if (cur == PT_DRAINED) { active = false; ending = true; } // a lane that stopped at a second leaf keeps that for the next round
-#else
-            if (sp == 0) {
-                store_hit();
-                active = false; fin = l;
-            } else cur = stack[--sp][lane];
-#endif
-        }
-        clk.lap(prof.t_part[0][2]);
+    struct Leaf {};
+    RT_DEV void begin(uint32_t slot) {
+        const float4 *r = wf_rec(W, slot);
+        float4 q0 = r[0], q1 = r[1];
+        o = f3(q0.x, q0.y, q0.z); d = f3(q0.w, q1.x, q1.y);
+        ray = make_ray_grid(S.grid, o, d);
+        h_ray = S.exact_boxes ? pt_look_behind_abs(d, S.box_c2x) : 0.f;
+        hit = WF_MISS; best_t = RT_T_MAX; cull_t = RT_T_MAX; t2 = 2.f * RT_T_MAX; best_u = 0.f; best_v = 0.f;
     }
-}
+    RT_DEV int step(uint32_t &cur, int &sp) { return pt_wide_step_nearest(S.nodes4, ray, cull_t, stack, lane, sp, P8_STACK, cur); }
+    // The column is full (a walk holds up to three entries per level of a tree of up to P8_STACK / 2 levels; this takes a ray that
+    // grazes many boxes: triangle soups).  The walk says so — no hit has a negative t — and the exact role walks the query with a
+    // stack of its own (pt_exact_batch).
+    RT_DEV void full() { best_t = PT_T_OVERFLOW; best_u = 0.f; best_v = 0.f; hit = 0u; t2 = PT_T_OVERFLOW; }
+    RT_DEV bool test(uint32_t i, int, Leaf &) {
+        TriIsect T = load_isect(S.tri_walk + i);
+        float t, u, v; bool inside;
+        const uint32_t fi = T.pad >> 1; // index in the figure order
+        if (tri_test_closer(T, o, d, cull_t, t, u, v, inside)) {
+            const uint32_t best_i = hit & WF_INDEX_MASK;
+            if (t < best_t || (t == best_t && fi < best_i)) { // reference tie rule: smallest t, equal t -> lowest figure index
+                t2 = fminf(t2, best_t);
+                best_t = t; best_u = u; best_v = v; hit = fi | (inside ? WF_INSIDE_BIT : 0u);
+                cull_t = t + fmaxf(S.cull_k * t, h_ray);
+            } else t2 = fminf(t2, t);
+        }
+        return (T.pad & 1u) != 0u;
+    }
+    RT_DEV bool leaves_done(Leaf &, int) { return false; }
+    RT_DEV uint32_t end(uint32_t l, uint32_t slot, uint32_t steps) { // the gate (pt_shade_item) decides with the runner-up's t whether this hit needs the exact walk
+        wf_rec(W, slot)[2] = make_float4(best_t, best_u, best_v, __uint_as_float(S.exact_boxes && hit != WF_MISS ? hit | pt_gap_code(best_t, t2) : hit));
+        pt_book_cost(sh, P, l, steps);
+        return l;
+    }
+};
 
-// ---- light-sum walker (wf_light_loop_lean of rt_wavefront.h fed from the need_light bitmap) ----------------------------------
-template <bool COUNT>
-RT_DEV void pt_light_stint(const SceneView &S, const WfView &W, PtShared &sh, const PtParams &P, PtWave &wv, uint32_t (*stack)[64],
-                           const int shade_thr, uint32_t &n_queries, unsigned long long &n_nodes, unsigned long long &n_tris, PtProf &prof) {
+// ---- light-sum walker (wf_light_loop_lean of rt_wavefront.h): every light on the ray, the hits kept sorted at the top of the lane's column --
+template <bool COUNT> struct PtLightWalk {
+    typedef PtLightQueue<PT_Q_XLIGHT> Queue;
+    static constexpr uint32_t COST_NODE = PT_COST_LIGHT_NODE, COST_TEST = PT_COST_LIGHT_TEST;
+    const SceneView &S; const WfView &W; PtShared &sh; const PtParams &P; uint32_t (*stack)[64]; PtProf &prof;
     const int lane = threadIdx.x & 63;
-    bool active = false, overflow = false, refill_ok = true, ending = false; // ending: see pt_trace_stint
-    uint32_t l = 0, slot = 0, cur = 0, fin = PT_NONE; // fin: the lane's finished, unpublished path; bit 31 = it needs the exact role instead
-    int sp = 0, k = 0;
-    uint32_t pend = RT_EMPTY_LEAF, pend2 = RT_EMPTY_LEAF, pend3 = RT_EMPTY_LEAF; (void)pend; (void)pend2; (void)pend3; // PT_POSTPONE: the leaves this lane has met and not yet tested (pend first)
-    uint32_t steps = 0;
+    bool overflow = false; // the exact role sums this query
+    int k = 0;             // hits so far
     F3 o = f3(0.f, 0.f, 0.f), d = f3(0.f, 0.f, 1.f);
-    PtRay ray = PT_RAY_IDLE; // idle lanes: never used
-    auto finish = [&]() {
-        active = false;
-        if (P.group_cost) atomicAdd(&sh.cost[l >> pt_gshift(sh)], steps);
-        if (overflow) { fin = l | 0x80000000u; return; }
+    RayGrid ray = RT_GRID_RAY_IDLE; // idle lanes: never used
+    // The leaf loop only tests; what a hit needs beyond the test (the rest of the light's record, the pdf term, the robustness test, the
+    // sorted insertion) waits until after the loop — a lane rarely hits twice in one leaf phase, and the long hit code then runs once
+    // per phase instead of once per tested light.
+    struct Leaf { bool held = false; uint32_t h_i = 0u, h_li = 0u; float h_t = 0.f, h_u = 0.f, h_v = 0.f; bool h_in = false; };
+    RT_DEV void begin(uint32_t slot) {
+        const float4 *r = wf_rec(W, slot);
+        float4 q0 = r[0], q1 = r[1];
+        o = f3(q0.x, q0.y, q0.z); d = f3(q0.w, q1.x, q1.y);
+        ray = make_ray_grid(S.grid, o, d);
+        k = 0; overflow = false;
+    }
+    RT_DEV int step(uint32_t &cur, int &sp) { return pt_wide_step_all(S.light_walk_nodes4, ray, stack, lane, sp, P8_STACK - 2 * k - 1, cur); } // the hits sit at the column's top
+    RT_DEV void full() { overflow = true; } // no room beside the hits
+    RT_DEV void take(Leaf &lf, int sp) { // the held hit joins the lane's hits
+        bool robust;
+        const float term = pt_light_pdf_hit(S, S.lights_walk + lf.h_i, o, d, lf.h_t, lf.h_u, lf.h_v, lf.h_in, robust);
+        if (COUNT && term != 0.f) prof.light_hits++;
+        if (term != 0.f) { // (a hit whose term is exactly 0 adds nothing, like a miss)
+            if (!robust || k >= WF_MAX_LIGHT_HITS || sp + 2 * k + 2 >= P8_STACK) overflow = true;
+            else { // kept sorted by light index (this tree's leaf order is not the light order): hit j at words P8_STACK-1-2j (index), -2-2j (term)
+                int j = k;
+                while (j > 0 && stack[P8_STACK - 1 - 2 * (j - 1)][lane] > lf.h_li) {
+                    stack[P8_STACK - 1 - 2 * j][lane] = stack[P8_STACK - 1 - 2 * (j - 1)][lane];
+                    stack[P8_STACK - 2 - 2 * j][lane] = stack[P8_STACK - 2 - 2 * (j - 1)][lane];
+                    j--;
+                }
+                stack[P8_STACK - 1 - 2 * j][lane] = lf.h_li; stack[P8_STACK - 2 - 2 * j][lane] = __float_as_uint(term); k++;
+            }
+        }
+        lf.held = false;
+    }
+    RT_DEV bool test(uint32_t i, int sp, Leaf &lf) {
+        bool last, inside; uint32_t li; float t, u, v;
+        if (COUNT) prof.light_tests++;
+        if (pt_light_test(S.lights_walk + i, o, d, last, li, t, u, v, inside)) {
+            if (lf.held) take(lf, sp); // a second hit in this phase
+            lf.held = true; lf.h_i = i; lf.h_li = li; lf.h_t = t; lf.h_u = u; lf.h_v = v; lf.h_in = inside;
+        }
+        return last;
+    }
+    RT_DEV bool leaves_done(Leaf &lf, int sp) { if (lf.held) take(lf, sp); return false; }
+    RT_DEV uint32_t end(uint32_t l, uint32_t slot, uint32_t steps) {
+        pt_book_cost(sh, P, l, steps);
+        if (overflow) return l | 0x80000000u;
         float v = 0.f;
         if (k == 1) v = __uint_as_float(stack[P8_STACK - 2][lane]);
         else if (k == 2) v = __uint_as_float(stack[P8_STACK - 2][lane]) + __uint_as_float(stack[P8_STACK - 4][lane]);
@@ -602,145 +604,9 @@ RT_DEV void pt_light_stint(const SceneView &S, const WfView &W, PtShared &sh, co
         int depth = (int)(__float_as_uint(reinterpret_cast<const float *>(wf_rec(W, slot) + 3)[3]) & 15u);
         float *pdf = reinterpret_cast<float *>(wf_entry(W, slot, depth)) + 3;
         *pdf = *pdf + v / S.n_lights_f;                                  // distributions.h:123,273
-        fin = l;
-    };
-    PtLap<COUNT> clk;
-    for (;;) {
-        if (pt_ballot(ending)) { // the sums of the walks that ended since the last pass (pt_trace_stint)
-            if (ending) { finish(); ending = false; }
-        }
-        const unsigned long long idle = pt_ballot(!active);
-        if (idle && (__popcll(idle) >= (P.refill >> 16) || idle == ~0ull)) {
-            if (pt_ballot(fin != PT_NONE)) { // hand-off point, see pt_trace_stint
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-                const bool slow = (fin >> 31) != 0u && fin != PT_NONE;
-                pt_complete(sh, fin, PT_BIT_L, fin != PT_NONE && !slow);
-                pt_push(sh, PT_Q_XLIGHT, fin & 0x7FFFFFFFu, slow);
-                fin = PT_NONE;
-            }
-            if (!refill_ok) {}
-            else if (pt_count(&sh.cnt[PT_Q_SHADE]) >= shade_thr) refill_ok = false;
-            else if (pt_count(&sh.cnt[PT_Q_LIGHT]) > 0) {
-                const uint32_t got = pt_pop(sh.need[PT_Q_LIGHT], &sh.cnt[PT_Q_LIGHT], wv.nw, wv.cur[PT_Q_LIGHT], !active, wv.front_first);
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-                n_queries += __popcll(pt_ballot(got != PT_NONE));
-                if (got != PT_NONE) {
-                    l = got; slot = pt_slot(sh, l);
-                    const float4 *r = wf_rec(W, slot);
-                    float4 q0 = r[0], q1 = r[1];
-                    o = f3(q0.x, q0.y, q0.z); d = f3(q0.w, q1.x, q1.y);
-                    ray = pt_make_ray(S, o, d);
-                    cur = 0; sp = 0; pend = RT_EMPTY_LEAF; pend2 = RT_EMPTY_LEAF; pend3 = RT_EMPTY_LEAF; k = 0; overflow = false; steps = 0;
-                    active = true;
-                }
-            }
-        }
-        const unsigned long long m_active = pt_ballot(active);
-        clk.lap(prof.t_part[1][0]);
-        if (!m_active) break;
-        const int lb = pt_leaf_batch(P.leaf_batch, m_active);
-        for (;;) { // phase 1: inner nodes
-#if PT_POSTPONE
-            if (active && (cur & RT_LEAF_BIT) && PT_LAST_SLOT == RT_EMPTY_LEAF && cur != PT_DRAINED) { // the leaf waits for the next leaf phase (pt_trace_stint)
-                if (pend == RT_EMPTY_LEAF) pend = cur; else if (pend2 == RT_EMPTY_LEAF) pend2 = cur; else pend3 = cur;
-                cur = sp == 0 ? PT_DRAINED : stack[--sp][lane];
-                if (cur == PT_DRAINED && pend == RT_EMPTY_LEAF) { active = false; ending = true; }
-            }
-#endif
-            const bool inner = active && !(cur & RT_LEAF_BIT);
-            if (!pt_ballot(inner) || __popcll(pt_ballot(active && (cur & RT_LEAF_BIT))) >= lb) break;
-            if (COUNT) { prof.light_iters++; prof.light_lane_iters += __popcll(pt_ballot(inner)); }
-            if (inner) {
-                if (COUNT) n_nodes++;
-                steps += PT_COST_LIGHT_NODE;
-#if PT_QUANT_NODES
-                const int went = pt_wide_step_all(S.light_walk_nodes4, ray, stack, lane, sp, P8_STACK - 2 * k - 1, cur); // the hits sit at the column's top
-                if (went == PT_WIDE_NONE) {
-#if PT_POSTPONE
-                    if (sp != 0) cur = stack[--sp][lane];
-                    else if (pend != RT_EMPTY_LEAF) cur = PT_DRAINED;
-                    else { active = false; ending = true; }
-#else
-                    if (sp == 0) { active = false; ending = true; }
-                    else cur = stack[--sp][lane];
-#endif
-                } else if (went == PT_WIDE_FULL) { overflow = true; pend = RT_EMPTY_LEAF; pend2 = RT_EMPTY_LEAF; pend3 = RT_EMPTY_LEAF; { active = false; ending = true; } } // no room beside the hits: the slow role sums this query
-#else
-                float n0, n1;
-                const float4 *q = reinterpret_cast<const float4 *>(S.light_walk_nodes + cur);
-                float4 lo0 = q[0], hi0 = q[1], lo1 = q[2], hi1 = q[3];
-                bool h0 = slab_test(lo0, hi0, ray, RT_T_MAX, n0);
-                bool h1 = slab_test(lo1, hi1, ray, RT_T_MAX, n1);
-                uint32_t c0 = __float_as_uint(lo0.w), c1 = __float_as_uint(lo1.w);
-                if (h0 & h1) { stack[sp++][lane] = c1; cur = c0; if (sp + 2 * k >= P8_STACK) overflow = true; }
-                else if (h0) cur = c0;
-                else if (h1) cur = c1;
-                else if (sp == 0) { active = false; ending = true; }
-                else cur = stack[--sp][lane];
-#endif
-            }
-        }
-        clk.lap(prof.t_part[1][1]);
-#if PT_POSTPONE
-        const bool at_leaf = active && pend != RT_EMPTY_LEAF;
-        const uint32_t leaf = pend;
-        uint32_t more = pend2, more2 = pend3;
-#else
-        const bool at_leaf = active && (cur & RT_LEAF_BIT);
-        const uint32_t leaf = cur;
-        uint32_t more = RT_EMPTY_LEAF, more2 = RT_EMPTY_LEAF;
-#endif
-        if (COUNT) { prof.leaf_iters[1]++; prof.leaf_lane_iters[1] += __popcll(pt_ballot(at_leaf)); }
-        if (at_leaf) { // phase 2: leaves
-            if (leaf != RT_EMPTY_LEAF) {
-                uint32_t i = leaf & ~RT_LEAF_BIT;
-                // The loop only tests; what a hit needs beyond the test (the rest of the light's record, the pdf term, the robustness test, the
-                // sorted insertion) waits until after the loop — a lane rarely hits twice in one leaf phase, and the long hit code then runs once
-                // per phase instead of once per tested light.
-                bool held = false; uint32_t h_i = 0u, h_li = 0u; float h_t = 0.f, h_u = 0.f, h_v = 0.f; bool h_in = false;
-                auto take = [&]() { // the held hit joins the lane's hits
-                    bool robust;
-                    const float term = pt_light_pdf_hit(S, S.lights_walk + h_i, o, d, h_t, h_u, h_v, h_in, robust);
-                    if (COUNT && term != 0.f) prof.light_hits++;
-                    if (term != 0.f) { // (a hit whose term is exactly 0 adds nothing, like a miss)
-                        if (!robust || k >= WF_MAX_LIGHT_HITS || sp + 2 * k + 2 >= P8_STACK) overflow = true;
-                        else { // kept sorted by light index (this tree's leaf order is not the light order): hit j at words P8_STACK-1-2j (index), -2-2j (term)
-                            int j = k;
-                            while (j > 0 && stack[P8_STACK - 1 - 2 * (j - 1)][lane] > h_li) {
-                                stack[P8_STACK - 1 - 2 * j][lane] = stack[P8_STACK - 1 - 2 * (j - 1)][lane];
-                                stack[P8_STACK - 2 - 2 * j][lane] = stack[P8_STACK - 2 - 2 * (j - 1)][lane];
-                                j--;
-                            }
-                            stack[P8_STACK - 1 - 2 * j][lane] = h_li; stack[P8_STACK - 2 - 2 * j][lane] = __float_as_uint(term); k++;
-                        }
-                    }
-                    held = false;
-                };
-                for (;;) {
-                    bool last, inside; uint32_t li; float t, u, v;
-                    if (COUNT) { n_tris++; prof.light_tests++; }
-                    steps += PT_COST_LIGHT_TEST;
-                    if (pt_light_test(S.lights_walk + i, o, d, last, li, t, u, v, inside)) {
-                        if (held) take(); // a second hit in this phase
-                        held = true; h_i = i; h_li = li; h_t = t; h_u = u; h_v = v; h_in = inside;
-                    }
-                    if (!last) i++;
-                    else if (more == RT_EMPTY_LEAF) break;
-                    else { i = more & ~RT_LEAF_BIT; more = more2; more2 = RT_EMPTY_LEAF; } // the lane's next leaf
-                }
-                if (held) take();
-            }
-#if PT_POSTPONE
-            pend = RT_EMPTY_LEAF; pend2 = RT_EMPTY_LEAF; pend3 = RT_EMPTY_LEAF;
-            if (cur == PT_DRAINED) { active = false; ending = true; }
-#else
-            if (sp == 0) { active = false; ending = true; }
-            else cur = stack[--sp][lane];
-#endif
-        }
-        clk.lap(prof.t_part[1][2]);
+        return l;
     }
-}
+};
 
 // ---- the shader role: wf_shade_item / pt_shade_item of rt_wavefront.h laid out for a 96-VGPR budget -----------------------------------
 // Same arithmetic, same order of random draws, same record writes.  What differs is where values wait: the shading code is a chain of
@@ -789,7 +655,7 @@ RT_DEV int pt_shade_lean(const SceneView &S, const RenderView &R, const WfView &
     float4 pe0, pe1;
     { const float4 *e = wf_entry(W, slot, depth); pe0 = e[0]; pe1 = e[1]; }
     // the exactness gate (pt_shade_item): a hit that does not stand as the reference's answer goes to the exact walk first, untouched
-    if (q2.x == PT_T_OVERFLOW && !(packed & WF_VERIFIED_BIT)) return PT_SHADE_EXACT; // the walk ran out of stack (pt_trace_stint)
+    if (q2.x == PT_T_OVERFLOW && !(packed & WF_VERIFIED_BIT)) return PT_SHADE_EXACT; // the walk ran out of stack (PtTraceWalk::full)
     if (S.exact_boxes == 1u && hit != WF_MISS && !(packed & WF_VERIFIED_BIT) &&
         !pt_hit_stands(f3(blo.x, blo.y, blo.z), f3(bhi.x, bhi.y, bhi.z), f3(q0.x, q0.y, q0.z), f3(q0.w, q1.x, q1.y), q2.x, pt_gap_floor(hit, q2.x), S.box_c2, S.box_c2x, S.cull_k))
         return PT_SHADE_EXACT;
@@ -960,6 +826,38 @@ RT_DEV void pt_exact_batch(const SceneView &S, const WfView &W, SH &sh, PtWave &
 }
 
 // ---- the kernel -----------------------------------------------------------------------------------------------------------
+// What a workgroup of THREADS threads does first, in this kernel and in rt_persistent_hw6.h's: its share of the pass's groups, the wave's
+// state, cleared queues and tables in LDS (SH: PtShared, P6Shared), the debug stamp.  False: the workgroup owns no path and leaves.
+template <int THREADS, class SH>
+RT_DEV bool pt_enter(SH &sh, const PtParams &P, PtWave &wv, uint32_t &n_local_groups) {
+    const uint32_t tid = threadIdx.x;
+    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6));
+    wv.n_blocks = gridDim.x; wv.block = blockIdx.x;
+    wv.front_first = P.front_first != 0u;
+    const uint32_t first_group = P.group_ofs ? P.group_ofs[wv.block] : 0u;
+    n_local_groups = P.group_ofs ? P.group_ofs[wv.block + 1u] - first_group
+                                 : (P.n_groups > wv.block ? (P.n_groups - wv.block + wv.n_blocks - 1u) / wv.n_blocks : 0u);
+    wv.n_local = n_local_groups << P.group_shift;
+    wv.nw = (wv.n_local + 31u) >> 5;
+    if (wv.n_local == 0u) return false;
+    if (P.debug && tid == 0) { P.debug[3 * blockIdx.x] = __builtin_amdgcn_s_memrealtime(); P.debug[3 * blockIdx.x + 2] = wv.n_local; }
+    for (int q = 0; q < 5; q++) wv.cur[q] = (wave * 64u) % wv.nw;
+    for (uint32_t i = tid; i < wv.nw; i += THREADS) { sh.need[0][i] = 0; sh.need[1][i] = 0; sh.need[2][i] = 0; sh.need[3][i] = 0; sh.need[4][i] = 0; }
+    for (uint32_t i = tid; i < 2u * wv.nw; i += THREADS) sh.pending[i] = 0;
+    for (uint32_t i = tid; i < n_local_groups; i += THREADS) { sh.groups[i] = P.group_ofs ? P.group_ids[first_group + i] : i * wv.n_blocks + wv.block; sh.cost[i] = 0; }
+    if (tid < 16u) sh.cnt[tid] = tid == PT_GSHIFT ? (int)P.group_shift : 0;
+    __syncthreads();
+    return true;
+}
+// ... and last: the work booked for each of its groups goes back to the host (every wave leaves the scheduler loop once the workgroup's
+// pixels are done, or at the deadline)
+template <int THREADS, class SH>
+RT_DEV void pt_leave(SH &sh, const PtParams &P, uint32_t n_local_groups) {
+    if (!P.group_cost) return;
+    __syncthreads();
+    for (uint32_t i = threadIdx.x; i < n_local_groups; i += THREADS) P.group_cost[sh.groups[i]] = sh.cost[i];
+}
+
 // __launch_bounds__(256, 5): five waves per SIMD, i.e. a budget of 96 VGPRs.  Every role fits it without scratch; the scheduler's own
 // state is wave-uniform and lives in SGPRs (pt_count / readfirstlane).
 template <bool COUNT, int FEAT>
@@ -968,23 +866,10 @@ __global__ __launch_bounds__(P8_THREADS, P8_PER_CU) void pt_persistent_kernel(Sc
     const uint32_t tid = threadIdx.x, lane = tid & 63u;
     const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6));
     PtWave wv;
-    wv.n_blocks = gridDim.x; wv.block = blockIdx.x;
-    wv.front_first = P.front_first != 0u;
-    const uint32_t first_group = P.group_ofs ? P.group_ofs[wv.block] : 0u;
-    const uint32_t n_local_groups = P.group_ofs ? P.group_ofs[wv.block + 1u] - first_group
-                                                : (P.n_groups > wv.block ? (P.n_groups - wv.block + wv.n_blocks - 1u) / wv.n_blocks : 0u);
-    wv.n_local = n_local_groups << P.group_shift;
-    wv.nw = (wv.n_local + 31u) >> 5;
-    if (wv.n_local == 0u) return;
-    if (P.debug && tid == 0) { P.debug[3 * blockIdx.x] = __builtin_amdgcn_s_memrealtime(); P.debug[3 * blockIdx.x + 2] = wv.n_local; }
-    for (int q = 0; q < 5; q++) wv.cur[q] = (wave * 64u) % wv.nw;
+    uint32_t n_local_groups;
+    if (!pt_enter<P8_THREADS>(sh, P, wv, n_local_groups)) return;
 
     // ---- init: seed every pixel of this workgroup, first camera ray (wf_init_kernel of rt_wavefront.h) -----------------------
-    for (uint32_t i = tid; i < wv.nw; i += P8_THREADS) { sh.need[0][i] = 0; sh.need[1][i] = 0; sh.need[2][i] = 0; sh.need[3][i] = 0; sh.need[4][i] = 0; }
-    for (uint32_t i = tid; i < 2u * wv.nw; i += P8_THREADS) sh.pending[i] = 0;
-    for (uint32_t i = tid; i < n_local_groups; i += P8_THREADS) { sh.groups[i] = P.group_ofs ? P.group_ids[first_group + i] : i * wv.n_blocks + wv.block; sh.cost[i] = 0; }
-    if (tid < 16u) sh.cnt[tid] = tid == PT_GSHIFT ? (int)P.group_shift : 0;
-    __syncthreads();
     for (uint32_t base = 0; base < wv.n_local; base += P8_THREADS) {
         const uint32_t l = base + tid;
         bool started = false;
@@ -1050,9 +935,7 @@ __global__ __launch_bounds__(P8_THREADS, P8_PER_CU) void pt_persistent_kernel(Sc
         const int ns = pt_count(&sh.cnt[PT_Q_SHADE]), nt = pt_count(&sh.cnt[PT_Q_TRACE]), nl = pt_count(&sh.cnt[PT_Q_LIGHT]);
         const int nx = pt_count(&sh.cnt[PT_Q_XLIGHT]) + pt_count(&sh.cnt[PT_Q_XTRACE]);
         if (nx > 0) {
-#ifndef DBG_NO_EXACT
             pt_exact_batch(S, W, sh, wv, &stack[0][0], n_xlight, n_xtrace);
-#endif
             idle_spins = 0;
             lap(prof.t_exact);
             continue;
@@ -1074,9 +957,7 @@ __global__ __launch_bounds__(P8_THREADS, P8_PER_CU) void pt_persistent_kernel(Sc
                     if (4u * k + 5u <= P.trace_cap) for (int q = 0; q < 4; q++) P.trace_buf[1 + 4 * k + q] = tr[q];
                 }
             }
-#ifndef DBG_NO_SHADE
             if (got != PT_NONE) { PtPark pk; pk.p = (PtLdsWord)&stack[0][lane]; todo = pt_shade_lean<FEAT>(S, R, W, pt_slot(sh, got), pk, discarded); }
-#endif
             n_discarded += __popcll(pt_ballot(discarded));
             const bool next = got != PT_NONE && todo != PT_SHADE_EXACT && (todo & WF_NEXT_TRACE), with_light = next && (todo & WF_NEXT_LIGHT);
             bool wire = false;    // the new ray pierces a tripwire (rt_exact.h): its closest hit is the exact role's
@@ -1087,18 +968,16 @@ __global__ __launch_bounds__(P8_THREADS, P8_PER_CU) void pt_persistent_kernel(Sc
                 const float4 n0 = nr[0], n1 = nr[1];
                 const F3 o = f3(n0.x, n0.y, n0.z), d = f3(n0.w, n1.x, n1.y);
                 if (S.n_tripwire_groups) wire = pt_tripwire(S, o, d);
-#if PT_QUANT_NODES
                 if ((COUNT || PT_LIGHT_SETTLE) && with_light) { // the counting build classifies every sum, whatever it settles
-                    const int reach = pt_light_reach<COUNT ? 2 : PT_LIGHT_SETTLE>(S, pt_make_ray(S, o, d), settle_steps);
+                    const int reach = pt_light_reach<COUNT ? 2 : PT_LIGHT_SETTLE>(S, make_ray_grid(S.grid, o, d), settle_steps);
                     if (COUNT) { prof.light_reach[0] += reach == 0; prof.light_reach[1] += reach == 1; }
                     settled = reach < PT_LIGHT_SETTLE;
-                    if (settled) { // what the walker's finish() does with no hit, before the release below publishes the path
+                    if (settled) { // what the walker's end() does with no hit, before the release below publishes the path
                         const int depth = (int)(__float_as_uint(reinterpret_cast<const float *>(nr + 3)[3]) & 15u);
                         float *pdf = reinterpret_cast<float *>(wf_entry(W, pt_slot(sh, got), depth)) + 3;
                         *pdf = *pdf + 0.f / S.n_lights_f;                      // distributions.h:123,273 (+0.f: a -0 sum becomes +0)
                     }
                 }
-#endif
             }
             n_light += __popcll(pt_ballot(settled)); // a settled sum is still a light-pdf query of the algorithm
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
@@ -1124,16 +1003,14 @@ __global__ __launch_bounds__(P8_THREADS, P8_PER_CU) void pt_persistent_kernel(Sc
             if (P.prio == 1) __builtin_amdgcn_s_setprio(2);
             if (nl == 0 || (nt > 0 && wt >= wl)) {
                 if (lane == 0) atomicAdd(&sh.cnt[PT_W_TRACE], 1);
-#ifndef DBG_NO_TRACE
-                pt_trace_stint<COUNT>(S, W, sh, P, wv, stack, shade_thr, n_closest, n_nodes, n_tris, prof);
-#endif
+                PtTraceWalk walk{S, W, sh, P, stack}; // hw8 / hw7: three parked leaves, deferred endings (pt_walk_stint)
+                pt_walk_stint<3, true, COUNT>(walk, sh, P, wv, stack, shade_thr, n_closest, n_nodes, n_tris, prof);
                 if (lane == 0) atomicSub(&sh.cnt[PT_W_TRACE], 1);
                 lap(prof.t_trace);
             } else {
                 if (lane == 0) atomicAdd(&sh.cnt[PT_W_LIGHT], 1);
-#ifndef DBG_NO_LIGHT
-                pt_light_stint<COUNT>(S, W, sh, P, wv, stack, shade_thr, n_light, n_nodes, n_tris, prof);
-#endif
+                PtLightWalk<COUNT> walk{S, W, sh, P, stack, prof};
+                pt_walk_stint<3, true, COUNT>(walk, sh, P, wv, stack, shade_thr, n_light, n_nodes, n_tris, prof);
                 if (lane == 0) atomicSub(&sh.cnt[PT_W_LIGHT], 1);
                 lap(prof.t_light);
             }
@@ -1149,10 +1026,7 @@ __global__ __launch_bounds__(P8_THREADS, P8_PER_CU) void pt_persistent_kernel(Sc
         if (++idle_spins > (1u << 24)) { gave_up = 2; break; } // safety net (seconds): never hang the GPU on a lost path; the host reports it
     }
     if (gave_up && lane == 0 && P.counters) atomicAdd(&P.counters[gave_up == 1 ? 29 : 14], 1ull);
-    if (P.group_cost) { // every wave leaves the loop once the workgroup's pixels are done (or at the deadline)
-        __syncthreads();
-        for (uint32_t i = tid; i < n_local_groups; i += P8_THREADS) P.group_cost[sh.groups[i]] = sh.cost[i];
-    }
+    pt_leave<P8_THREADS>(sh, P, n_local_groups);
     if (lane == 0 && P.counters) {
         if (n_closest) atomicAdd(&P.counters[0], (unsigned long long)n_closest);
         if (n_light) atomicAdd(&P.counters[1], (unsigned long long)n_light);
@@ -1167,8 +1041,8 @@ __global__ __launch_bounds__(P8_THREADS, P8_PER_CU) void pt_persistent_kernel(Sc
         if (lane == 0) { // wave-level profile, words 16..27 and 48..57
             atomicAdd(&P.counters[16], prof.t_trace); atomicAdd(&P.counters[17], prof.t_light); atomicAdd(&P.counters[18], prof.t_shade);
             atomicAdd(&P.counters[19], prof.t_exact); atomicAdd(&P.counters[20], prof.t_idle);
-            atomicAdd(&P.counters[21], prof.trace_iters); atomicAdd(&P.counters[22], prof.trace_lane_iters);
-            atomicAdd(&P.counters[23], prof.light_iters); atomicAdd(&P.counters[24], prof.light_lane_iters);
+            atomicAdd(&P.counters[21], prof.iters[0]); atomicAdd(&P.counters[22], prof.lane_iters[0]);
+            atomicAdd(&P.counters[23], prof.iters[1]); atomicAdd(&P.counters[24], prof.lane_iters[1]);
             atomicAdd(&P.counters[25], prof.stints); atomicAdd(&P.counters[26], prof.shade_batches); atomicAdd(&P.counters[27], prof.shade_items);
             for (int k = 0; k < 3; k++) atomicAdd(&P.counters[60 + k], prof.t_sub[0][k]);
             atomicAdd(&P.counters[63], prof.refills[0]);

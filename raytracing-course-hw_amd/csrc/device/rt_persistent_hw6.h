@@ -38,9 +38,7 @@ namespace dev {
 #define P6_COST_TRACE_STEP 1u        // what a sub-tile costs its workgroup, in closest-hit node steps (the measure of the re-deal, as PT_COST_*)
 #define P6_COST_LIGHT_STEP 2u
 #define P6_COST_SHADE 10u
-#ifndef P6_LIGHT_PRETEST
 #define P6_LIGHT_PRETEST false   // the deep-inside shortcut of pt_box_robust in the light walker: its few extra live values are exactly what tips this kernel (at 96 VGPRs) into spilling
-#endif
 #define P6_MERGE_HITS 13             // p6_merge_hits works in the lane's own 28-word column: 13 terms + 14 index / depth words
 #define P6_Q_SLOW 3                  // light sums with more than two hits: the complete per-lane light_pdf_sum6_fast
 #define P6_REC 56u                   // float4 per path record: 8 + 5 per frame x RT6_MAX_DEPTH + 8 for the hits of a light sum
@@ -104,7 +102,7 @@ RT_DEV int p6_advance(const SceneView6 &S, const RenderView &R, const W6View &W,
     int fp = (int)(packed & 15u);
     rng.has_saved = (packed & 16u) != 0;
     uint32_t sample = packed >> 8;
-    if (!(packed & (P6_LIGHT_ONLY | P6_VERIFIED)) && r[2].x == PT_T_OVERFLOW) return P6_EXACT; // the walk ran out of stack (p6_trace_stint)
+    if (!(packed & (P6_LIGHT_ONLY | P6_VERIFIED)) && r[2].x == PT_T_OVERFLOW) return P6_EXACT; // the walk ran out of stack (P6TraceWalk::full)
     if (S.exact_boxes && !(packed & (P6_LIGHT_ONLY | P6_VERIFIED))) {
         // the gate of rt_exact.h (pt_hit_stands), before anything of the path's state changes
         const float4 g0 = r[0], g2 = r[2];
@@ -290,134 +288,127 @@ RT_DEV int p6_advance(const SceneView6 &S, const RenderView &R, const W6View &W,
     }
 }
 
-// ---- closest-hit walker over hw6's own tree (closest_hit6 with lane refill) -------------------------------------------------------
-template <bool COUNT>
-RT_DEV void p6_trace_stint(const SceneView6 &S, const W6View &W, P6Shared &sh, const PtParams &P, PtWave &wv, uint32_t (*stack)[64],
-                           const int shade_thr, uint32_t &n_queries, unsigned long long &n_nodes, unsigned long long &n_tris) {
+// ---- closest-hit walker over hw6's own tree (closest_hit6): a policy of rt_persistent.h's pt_walk_stint --------------------------------
+struct P6TraceWalk {
+    typedef PtTraceQueue Queue;
+    static constexpr uint32_t COST_NODE = P6_COST_TRACE_STEP, COST_TEST = P6_COST_TRACE_STEP;
+    const SceneView6 &S; const W6View &W; P6Shared &sh; const PtParams &P; uint32_t (*stack)[64];
     const int lane = threadIdx.x & 63;
-    bool active = false, refill_ok = true;
-    uint32_t l = 0, slot = 0, cur = 0, hit = 0xFFFFFFFFu, best_ref = 0xFFFFFFFFu, fin = PT_NONE;
+    uint32_t hit = 0xFFFFFFFFu, best_ref = 0xFFFFFFFFu;
     bool best_inside = false;
-    int sp = 0;
-    uint32_t steps = 0; // node steps + triangle tests of the lane's walk: the cost measure of the re-deal
-    uint32_t pend = RT_EMPTY_LEAF, pend2 = RT_EMPTY_LEAF; // the leaves this lane has met and not yet tested (pend first)
     F3 o = f3(0.f, 0.f, 0.f), d = f3(0.f, 0.f, 1.f);
     RayGrid ray = RT_GRID_RAY_IDLE; // idle lanes: never used
     float best_t = RT_T_MAX, cull_t = RT_T_MAX, t2 = 2.f * RT_T_MAX, h_ray = 0.f; // look-behind and runner-up: rt_exact.h
-    for (;;) {
-        const unsigned long long idle = pt_ballot(!active);
-        if (idle && (__popcll(idle) >= (P.refill & 0xFFFF) || idle == ~0ull)) {
-            if (pt_ballot(fin != PT_NONE)) { // hand-off point (rt_persistent.h)
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-                pt_complete(sh, fin, PT_BIT_T, fin != PT_NONE);
-                fin = PT_NONE;
-            }
-            if (!refill_ok) {}
-            else if (pt_count(&sh.cnt[PT_Q_SHADE]) >= shade_thr) refill_ok = false;
-            else if (pt_count(&sh.cnt[PT_Q_TRACE]) > 0) {
-                const uint32_t got = pt_pop(sh.need[PT_Q_TRACE], &sh.cnt[PT_Q_TRACE], wv.nw, wv.cur[PT_Q_TRACE], !active, wv.front_first);
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-                n_queries += __popcll(pt_ballot(got != PT_NONE));
-                if (got != PT_NONE) {
-                    l = got; slot = pt_slot(sh, l);
-                    const float4 *r = p6_rec(W, slot);
-                    float4 q0 = r[0], q1 = r[1];
-                    o = f3(q0.x, q0.y, q0.z); d = f3(q0.w, q1.x, q1.y);
-                    ray = make_ray_grid(S.grid, o, d);
-                    h_ray = S.exact_boxes ? pt_look_behind_abs(d, S.box_c2x) : 0.f;
-                    steps = 0;
-                    cur = 0; sp = 0; pend = RT_EMPTY_LEAF; pend2 = RT_EMPTY_LEAF; hit = 0xFFFFFFFFu; best_ref = 0xFFFFFFFFu; best_t = RT_T_MAX; cull_t = RT_T_MAX; t2 = 2.f * RT_T_MAX; best_inside = false;
-                    active = true;
-                }
-            }
-        }
-        const unsigned long long m_active = pt_ballot(active);
-        if (!m_active) break;
-        const int lb = pt_leaf_batch(P.leaf_batch, m_active);
-        auto done = [&]() {
-            p6_rec(W, slot)[2] = make_float4(best_t, __uint_as_float(hit), __uint_as_float(best_inside ? 1u : 0u), t2);
-            if (P.group_cost) atomicAdd(&sh.cost[l >> pt_gshift(sh)], steps * P6_COST_TRACE_STEP);
-            active = false; fin = l;
-        };
-        for (;;) { // phase 1: inner nodes; a leaf waits in `pend` for the next leaf phase while the lane walks on (rt_persistent.h, pt_trace_stint)
-            if (active && (cur & RT_LEAF_BIT) && pend2 == RT_EMPTY_LEAF && cur != PT_DRAINED) {
-                if (pend == RT_EMPTY_LEAF) pend = cur; else pend2 = cur;
-                cur = sp == 0 ? PT_DRAINED : stack[--sp][lane];
-                if (cur == PT_DRAINED && pend == RT_EMPTY_LEAF) done();
-            }
-            const bool inner = active && !(cur & RT_LEAF_BIT);
-            if (!pt_ballot(inner) || __popcll(pt_ballot(active && (cur & RT_LEAF_BIT))) >= lb) break;
-            if (inner) {
-                if (COUNT) n_nodes++;
-                steps++;
-                const int went = pt_wide_step_nearest(S.nodes4, ray, cull_t, stack, lane, sp, P6_STACK, cur);
-                if (went == PT_WIDE_FULL) { best_t = PT_T_OVERFLOW; hit = 0u; t2 = PT_T_OVERFLOW; best_inside = false; pend = RT_EMPTY_LEAF; pend2 = RT_EMPTY_LEAF; done(); } // the exact role redoes the query (rt_persistent.h)
-                else if (went == PT_WIDE_NONE) {
-                    if (sp != 0) cur = stack[--sp][lane];
-                    else if (pend != RT_EMPTY_LEAF) cur = PT_DRAINED;
-                    else done();
-                }
-            }
-        }
-        if (active && pend != RT_EMPTY_LEAF) { // phase 2: leaves
-            {
-                uint32_t i = pend & ~RT_LEAF_BIT, more = pend2;
-                for (;;) {
-                    Tri6Regs T = load_tri6(S.tris + i);
-                    if (COUNT) n_tris++;
-                    steps++;
-                    float t; bool inside;
-                    // reference tie rule: smallest t, equal t -> lowest index in the reference's figure order
-                    if (tri6_test_closer(T, o, d, cull_t, t, inside)) {
-                        if (t < best_t || (t == best_t && T.ref_index < best_ref)) {
-                            t2 = fminf(t2, best_t);
-                            best_t = t; best_inside = inside; hit = i; best_ref = T.ref_index;
-                            cull_t = S.exact_boxes ? t + fmaxf(S.cull_k * t, h_ray) : t;
-                        } else t2 = fminf(t2, t);
-                    }
-                    if (!T.last) i++;
-                    else if (more == RT_EMPTY_LEAF) break;
-                    else { i = more & ~RT_LEAF_BIT; more = RT_EMPTY_LEAF; } // the lane's second leaf
-                }
-            }
-            pend = RT_EMPTY_LEAF; pend2 = RT_EMPTY_LEAF;
-            if (cur == PT_DRAINED) done();
-        }
+    struct Leaf {};
+    RT_DEV void begin(uint32_t slot) {
+        const float4 *r = p6_rec(W, slot);
+        float4 q0 = r[0], q1 = r[1];
+        o = f3(q0.x, q0.y, q0.z); d = f3(q0.w, q1.x, q1.y);
+        ray = make_ray_grid(S.grid, o, d);
+        h_ray = S.exact_boxes ? pt_look_behind_abs(d, S.box_c2x) : 0.f;
+        hit = 0xFFFFFFFFu; best_ref = 0xFFFFFFFFu; best_t = RT_T_MAX; cull_t = RT_T_MAX; t2 = 2.f * RT_T_MAX; best_inside = false;
     }
-}
+    RT_DEV int step(uint32_t &cur, int &sp) { return pt_wide_step_nearest(S.nodes4, ray, cull_t, stack, lane, sp, P6_STACK, cur); }
+    RT_DEV void full() { best_t = PT_T_OVERFLOW; hit = 0u; t2 = PT_T_OVERFLOW; best_inside = false; } // the exact role redoes the query (rt_persistent.h)
+    RT_DEV bool test(uint32_t i, int, Leaf &) {
+        Tri6Regs T = load_tri6(S.tris + i);
+        float t; bool inside;
+        // reference tie rule: smallest t, equal t -> lowest index in the reference's figure order
+        if (tri6_test_closer(T, o, d, cull_t, t, inside)) {
+            if (t < best_t || (t == best_t && T.ref_index < best_ref)) {
+                t2 = fminf(t2, best_t);
+                best_t = t; best_inside = inside; hit = i; best_ref = T.ref_index;
+                cull_t = S.exact_boxes ? t + fmaxf(S.cull_k * t, h_ray) : t;
+            } else t2 = fminf(t2, t);
+        }
+        return T.last;
+    }
+    RT_DEV bool leaves_done(Leaf &, int) { return false; }
+    RT_DEV uint32_t end(uint32_t l, uint32_t slot, uint32_t steps) {
+        p6_rec(W, slot)[2] = make_float4(best_t, __uint_as_float(hit), __uint_as_float(best_inside ? 1u : 0u), t2);
+        pt_book_cost(sh, P, l, steps);
+        return l;
+    }
+};
 
 // ---- light-sum walker over the own tree of the lights: no, one or two hits need no order (x + 0 = x, a + b = b + a); more are
 // left in the record and added in the reference's association (light_sum6_associate) by the slow role -----------------------------
-template <bool COUNT>
-RT_DEV void p6_light_stint(const SceneView6 &S, const W6View &W, P6Shared &sh, const PtParams &P, PtWave &wv, uint32_t (*stack)[64],
-                           const int shade_thr, uint32_t &n_queries, unsigned long long &n_nodes, unsigned long long &n_tris) {
+struct P6LightWalk {
+    typedef PtLightQueue<P6_Q_SLOW> Queue;
+    static constexpr uint32_t COST_NODE = P6_COST_LIGHT_STEP, COST_TEST = P6_COST_LIGHT_STEP;
+    const SceneView6 &S; const W6View &W; P6Shared &sh; const PtParams &P; uint32_t (*stack)[64];
     const int lane = threadIdx.x & 63;
-    bool active = false, refill_ok = true, many = false, fragile = false; // fragile: a hit at a box boundary, the sum goes to the exact walk
-    uint32_t l = 0, slot = 0, cur = 0, fin = PT_NONE, idx0 = 0, idx1 = 0, idx2 = 0, idx3 = 0; // fin: the lane's finished, unpublished path; bit 31 = it goes to the slow role
-    int sp = 0, k = 0;
-    uint32_t steps = 0, pend = RT_EMPTY_LEAF, pend2 = RT_EMPTY_LEAF; // pend, pend2: the leaves this lane has met and not yet tested
+    bool many = false, fragile = false; // fragile: a hit at a box boundary, the sum goes to the exact walk
+    uint32_t idx0 = 0, idx1 = 0, idx2 = 0, idx3 = 0;
+    uint32_t slot = 0; // the path's record: a fifth hit goes there
+    int k = 0;
     float term0 = 0.f, term1 = 0.f, term2 = 0.f, term3 = 0.f;
     F3 o = f3(0.f, 0.f, 0.f), d = f3(0.f, 0.f, 1.f);
     RayGrid ray = RT_GRID_RAY_IDLE; // idle lanes: never used
+    struct Leaf { bool held = false; uint32_t h_i = 0u; float h_t = 0.f; bool h_in = false; }; // the leaf loop only tests (rt_persistent.h, PtLightWalk)
+    RT_DEV void begin(uint32_t s) {
+        slot = s;
+        const float4 *r = p6_rec(W, slot);
+        float4 q0 = r[0], q1 = r[1], q4 = r[4];
+        o = f3(q4.x, q4.y, q4.z); d = f3(q0.w, q1.x, q1.y);                        // the pdf's ray: x + eps*n towards the sampled direction
+        ray = make_ray_grid(S.grid, o, d);
+        k = 0; many = false; fragile = false; term0 = 0.f; term1 = 0.f;
+    }
+    RT_DEV int step(uint32_t &cur, int &sp) { return pt_wide_step_all(S.fast_light_nodes4, ray, stack, lane, sp, P6_STACK, cur); }
+    RT_DEV void full() { many = true; fragile = false; k = RT6_MAX_LIGHT_HITS + 1; } // the slow role walks the sum in the reference's order
+    RT_DEV void take(Leaf &lf) { // the held hit's pdf term, robustness test and bookkeeping
+        const Tri6Regs T = load_tri6(S.fast_lights + lf.h_i);
+        const float t = lf.h_t; const bool inside = lf.h_in;
+        F3 yn = normalize(inside ? neg(T.n) : T.n);                          // primitives.cpp:31
+        F3 y = o + t * d;
+        const float term = T.point_prob * len2(o - y) / fabsf(dot(d, yn));    // distributions.h:116-118
+        if (S.exact_boxes) { // is every box of the reference's light tree above this hit passed whatever the rounding? (rt_exact.h)
+            const F3 pb = T.a + T.b, pc = T.a + T.c;
+            const F3 blo = f3(fminf(T.a.x, fminf(pb.x, pc.x)), fminf(T.a.y, fminf(pb.y, pc.y)), fminf(T.a.z, fminf(pb.z, pc.z)));
+            const F3 bhi = f3(fmaxf(T.a.x, fmaxf(pb.x, pc.x)), fmaxf(T.a.y, fmaxf(pb.y, pc.y)), fmaxf(T.a.z, fmaxf(pb.z, pc.z)));
+            if (!pt_box_robust<P6_LIGHT_PRETEST>(blo, bhi, y, d, t, S.box_c2)) fragile = true;
+        }
+        if (k == 0) { term0 = term; idx0 = T.ref_index; }
+        else if (k == 1) { term1 = term; idx1 = T.ref_index; }
+        else if (k == 2) { term2 = term; idx2 = T.ref_index; }
+        else if (k == 3) { term3 = term; idx3 = T.ref_index; }
+        else { // five or more: the hits go to the record for the slow role
+            float2 *h = reinterpret_cast<float2 *>(p6_rec(W, slot) + 48);
+            if (k == 4) { h[0] = make_float2(__uint_as_float(idx0), term0); h[1] = make_float2(__uint_as_float(idx1), term1); h[2] = make_float2(__uint_as_float(idx2), term2); h[3] = make_float2(__uint_as_float(idx3), term3); }
+            if (k < RT6_MAX_LIGHT_HITS) h[k] = make_float2(__uint_as_float(T.ref_index), term);
+            many = true;
+        }
+        k++;
+        lf.held = false;
+    }
+    RT_DEV bool test(uint32_t i, int, Leaf &lf) {
+        Tri6Regs T = load_tri6(S.fast_lights + i);
+        float t; bool inside;
+        if (tri6_test(T, o, d, t, inside)) {
+            if (lf.held) take(lf); // another hit in this phase
+            lf.held = true; lf.h_i = i; lf.h_t = t; lf.h_in = inside;
+        }
+        return T.last;
+    }
+    RT_DEV bool leaves_done(Leaf &lf, int) { if (lf.held) take(lf); return k > RT6_MAX_LIGHT_HITS; } // more hits than the record holds: the walk is over
     // where the lights x < y of the reference order separate in the reference's light tree (SceneView6::light_sep, see p6_merge_hits)
-    auto sep = [&](uint32_t x, uint32_t y) {
+    RT_DEV uint32_t sep(uint32_t x, uint32_t y) const {
         const uint32_t lv = 31u - (uint32_t)__clz((int)(y - x));
         const uint32_t row = lv * S.n_lights; // 32-bit: the table has fewer than 2^32 entries (levels x lights)
         const uint16_t m0 = S.light_sep[row + x], m1 = S.light_sep[row + (y - (1u << lv))];
         return (uint32_t)(m0 < m1 ? m0 : m1);
-    };
-    auto finish = [&]() {
-        active = false;
-        if (P.group_cost) atomicAdd(&sh.cost[l >> pt_gshift(sh)], steps * P6_COST_LIGHT_STEP);
+    }
+    RT_DEV uint32_t end(uint32_t l, uint32_t, uint32_t steps) {
+        pt_book_cost(sh, P, l, steps);
         if (fragile) { // the hits go along (also when there are fewer than five), the slow role adds them with the reference's box tests
             float2 *h = reinterpret_cast<float2 *>(p6_rec(W, slot) + 48);
             if (k >= 1 && k <= 4) h[0] = make_float2(__uint_as_float(idx0), term0);
             if (k >= 2 && k <= 4) h[1] = make_float2(__uint_as_float(idx1), term1);
             if (k >= 3 && k <= 4) h[2] = make_float2(__uint_as_float(idx2), term2);
             if (k == 4) h[3] = make_float2(__uint_as_float(idx3), term3);
-            reinterpret_cast<uint32_t *>(p6_rec(W, slot) + 7)[0] = (uint32_t)k | 0x80000000u; fin = l | 0x80000000u; return;
+            reinterpret_cast<uint32_t *>(p6_rec(W, slot) + 7)[0] = (uint32_t)k | 0x80000000u; return l | 0x80000000u;
         }
-        if (many) { reinterpret_cast<uint32_t *>(p6_rec(W, slot) + 7)[0] = (uint32_t)k; fin = l | 0x80000000u; return; }
+        if (many) { reinterpret_cast<uint32_t *>(p6_rec(W, slot) + 7)[0] = (uint32_t)k; return l | 0x80000000u; }
         float v = k == 0 ? 0.f : (k == 1 ? term0 : term0 + term1);
         if (k == 3) {
             // three hits (the commonest case beyond two) are added here and now, in the reference's association: sorted by reference index
@@ -443,109 +434,9 @@ RT_DEV void p6_light_stint(const SceneView6 &S, const W6View &W, P6Shared &sh, c
             else v = t0 + (t1 + (t2 + t3));
         }
         reinterpret_cast<float *>(p6_rec(W, slot) + 4)[3] = v;
-        fin = l;
-    };
-    for (;;) {
-        const unsigned long long idle = pt_ballot(!active);
-        if (idle && (__popcll(idle) >= (P.refill >> 16) || idle == ~0ull)) {
-            if (pt_ballot(fin != PT_NONE)) {
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-                const bool slow = fin != PT_NONE && (fin >> 31) != 0u;
-                pt_complete(sh, fin, PT_BIT_L, fin != PT_NONE && !slow);
-                pt_push(sh, P6_Q_SLOW, fin & 0x7FFFFFFFu, slow);
-                fin = PT_NONE;
-            }
-            if (!refill_ok) {}
-            else if (pt_count(&sh.cnt[PT_Q_SHADE]) >= shade_thr) refill_ok = false;
-            else if (pt_count(&sh.cnt[PT_Q_LIGHT]) > 0) {
-                const uint32_t got = pt_pop(sh.need[PT_Q_LIGHT], &sh.cnt[PT_Q_LIGHT], wv.nw, wv.cur[PT_Q_LIGHT], !active, wv.front_first);
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-                n_queries += __popcll(pt_ballot(got != PT_NONE));
-                if (got != PT_NONE) {
-                    l = got; slot = pt_slot(sh, l);
-                    const float4 *r = p6_rec(W, slot);
-                    float4 q0 = r[0], q1 = r[1], q4 = r[4];
-                    o = f3(q4.x, q4.y, q4.z); d = f3(q0.w, q1.x, q1.y);                        // the pdf's ray: x + eps*n towards the sampled direction
-                    ray = make_ray_grid(S.grid, o, d);
-                    steps = 0;
-                    cur = 0; sp = 0; pend = RT_EMPTY_LEAF; pend2 = RT_EMPTY_LEAF; k = 0; many = false; fragile = false; term0 = 0.f; term1 = 0.f;
-                    active = true;
-                }
-            }
-        }
-        const unsigned long long m_active = pt_ballot(active);
-        if (!m_active) break;
-        const int lb = pt_leaf_batch(P.leaf_batch, m_active);
-        for (;;) { // phase 1: inner nodes; a leaf waits in `pend` for the next leaf phase (rt_persistent.h, pt_trace_stint)
-            if (active && (cur & RT_LEAF_BIT) && pend2 == RT_EMPTY_LEAF && cur != PT_DRAINED) {
-                if (pend == RT_EMPTY_LEAF) pend = cur; else pend2 = cur;
-                cur = sp == 0 ? PT_DRAINED : stack[--sp][lane];
-                if (cur == PT_DRAINED && pend == RT_EMPTY_LEAF) finish();
-            }
-            const bool inner = active && !(cur & RT_LEAF_BIT);
-            if (!pt_ballot(inner) || __popcll(pt_ballot(active && (cur & RT_LEAF_BIT))) >= lb) break;
-            if (inner) {
-                if (COUNT) n_nodes++;
-                steps++;
-                const int went = pt_wide_step_all(S.fast_light_nodes4, ray, stack, lane, sp, P6_STACK, cur);
-                if (went == PT_WIDE_FULL) { many = true; fragile = false; k = RT6_MAX_LIGHT_HITS + 1; pend = RT_EMPTY_LEAF; pend2 = RT_EMPTY_LEAF; finish(); } // the slow role walks the sum in the reference's order
-                else if (went == PT_WIDE_NONE) {
-                    if (sp != 0) cur = stack[--sp][lane];
-                    else if (pend != RT_EMPTY_LEAF) cur = PT_DRAINED;
-                    else finish();
-                }
-            }
-        }
-        if (active && pend != RT_EMPTY_LEAF) { // phase 2: leaves
-            {
-                uint32_t i = pend & ~RT_LEAF_BIT, more = pend2;
-                // the loop only tests; a hit's pdf term, robustness test and bookkeeping wait until after it (rt_persistent.h, pt_light_stint)
-                bool held = false; uint32_t h_i = 0u; float h_t = 0.f; bool h_in = false;
-                auto take = [&]() {
-                    const Tri6Regs T = load_tri6(S.fast_lights + h_i);
-                    const float t = h_t; const bool inside = h_in;
-                    F3 yn = normalize(inside ? neg(T.n) : T.n);                          // primitives.cpp:31
-                    F3 y = o + t * d;
-                    const float term = T.point_prob * len2(o - y) / fabsf(dot(d, yn));    // distributions.h:116-118
-                    if (S.exact_boxes) { // is every box of the reference's light tree above this hit passed whatever the rounding? (rt_exact.h)
-                        const F3 pb = T.a + T.b, pc = T.a + T.c;
-                        const F3 blo = f3(fminf(T.a.x, fminf(pb.x, pc.x)), fminf(T.a.y, fminf(pb.y, pc.y)), fminf(T.a.z, fminf(pb.z, pc.z)));
-                        const F3 bhi = f3(fmaxf(T.a.x, fmaxf(pb.x, pc.x)), fmaxf(T.a.y, fmaxf(pb.y, pc.y)), fmaxf(T.a.z, fmaxf(pb.z, pc.z)));
-                        if (!pt_box_robust<P6_LIGHT_PRETEST>(blo, bhi, y, d, t, S.box_c2)) fragile = true;
-                    }
-                    if (k == 0) { term0 = term; idx0 = T.ref_index; }
-                    else if (k == 1) { term1 = term; idx1 = T.ref_index; }
-                    else if (k == 2) { term2 = term; idx2 = T.ref_index; }
-                    else if (k == 3) { term3 = term; idx3 = T.ref_index; }
-                    else { // five or more: the hits go to the record for the slow role
-                        float2 *h = reinterpret_cast<float2 *>(p6_rec(W, slot) + 48);
-                        if (k == 4) { h[0] = make_float2(__uint_as_float(idx0), term0); h[1] = make_float2(__uint_as_float(idx1), term1); h[2] = make_float2(__uint_as_float(idx2), term2); h[3] = make_float2(__uint_as_float(idx3), term3); }
-                        if (k < RT6_MAX_LIGHT_HITS) h[k] = make_float2(__uint_as_float(T.ref_index), term);
-                        many = true;
-                    }
-                    k++;
-                    held = false;
-                };
-                for (;;) {
-                    Tri6Regs T = load_tri6(S.fast_lights + i);
-                    if (COUNT) n_tris++;
-                    steps++;
-                    float t; bool inside;
-                    if (tri6_test(T, o, d, t, inside)) {
-                        if (held) take(); // another hit in this phase
-                        held = true; h_i = i; h_t = t; h_in = inside;
-                    }
-                    if (!T.last) i++;
-                    else if (more == RT_EMPTY_LEAF) break;
-                    else { i = more & ~RT_LEAF_BIT; more = RT_EMPTY_LEAF; } // the lane's second leaf
-                }
-                if (held) take();
-            }
-            pend = RT_EMPTY_LEAF; pend2 = RT_EMPTY_LEAF;
-            if (cur == PT_DRAINED || k > RT6_MAX_LIGHT_HITS) finish();
-        }
+        return l;
     }
-}
+};
 
 // ---- slow role: three or more hits, added in the reference's association.  sum(node) = sum(left) + sum(right) with a side without
 // hits as the additive identity means: of the hits sorted by reference light index, those two neighbouring groups are added first
@@ -860,21 +751,8 @@ __global__ __launch_bounds__(P6_THREADS, P6_PER_CU) void p6_persistent_kernel(Sc
     const uint32_t tid = threadIdx.x, lane = tid & 63u;
     const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6));
     PtWave wv;
-    wv.n_blocks = gridDim.x; wv.block = blockIdx.x;
-    wv.front_first = P.front_first != 0u;
-    const uint32_t first_group = P.group_ofs ? P.group_ofs[wv.block] : 0u;
-    const uint32_t n_local_groups = P.group_ofs ? P.group_ofs[wv.block + 1u] - first_group
-                                                : (P.n_groups > wv.block ? (P.n_groups - wv.block + wv.n_blocks - 1u) / wv.n_blocks : 0u);
-    wv.n_local = n_local_groups << P.group_shift;
-    wv.nw = (wv.n_local + 31u) >> 5;
-    if (wv.n_local == 0u) return;
-    for (int q = 0; q < 5; q++) wv.cur[q] = (wave * 64u) % wv.nw;
-    for (uint32_t i = tid; i < wv.nw; i += P6_THREADS) { sh.need[0][i] = 0; sh.need[1][i] = 0; sh.need[2][i] = 0; sh.need[3][i] = 0; sh.need[4][i] = 0; }
-    for (uint32_t i = tid; i < 2u * wv.nw; i += P6_THREADS) sh.pending[i] = 0;
-    for (uint32_t i = tid; i < n_local_groups; i += P6_THREADS) { sh.groups[i] = P.group_ofs ? P.group_ids[first_group + i] : i * wv.n_blocks + wv.block; sh.cost[i] = 0; }
-    if (tid < 16u) sh.cnt[tid] = tid == PT_GSHIFT ? (int)P.group_shift : 0;
-    if (P.debug && tid == 0) { P.debug[3 * blockIdx.x] = __builtin_amdgcn_s_memrealtime(); P.debug[3 * blockIdx.x + 2] = wv.n_local; }
-    __syncthreads();
+    uint32_t n_local_groups;
+    if (!pt_enter<P6_THREADS>(sh, P, wv, n_local_groups)) return;
     for (uint32_t base = 0; base < wv.n_local; base += P6_THREADS) { // seed every pixel, first camera ray (hw6/src/sceneio.cpp:281-284)
         const uint32_t l = base + tid;
         bool started = false;
@@ -924,6 +802,7 @@ __global__ __launch_bounds__(P6_THREADS, P6_PER_CU) void p6_persistent_kernel(Sc
     int gave_up = 0; // 1: the launch ran into its deadline; 2: the workgroup waited in vain for a path to come back (a lost path: a bug)
     const unsigned long long t_start = __builtin_amdgcn_s_memrealtime();
     unsigned long long t_role[5] = {0, 0, 0, 0, 0}, t_mark = t_start; // COUNT: wave time as closest-hit walker, light walker, shader, slow light sums, idle
+    PtProf prof; // the shared walker loop's laps (counting build): not reported for hw6
     auto clock_role = [&](int role) { if (COUNT) { const unsigned long long now = __builtin_amdgcn_s_memrealtime(); t_role[role] += now - t_mark; t_mark = now; } };
     for (;;) {
         if (__builtin_amdgcn_s_memrealtime() - t_start > P.deadline_ticks) { gave_up = 1; break; } // safety net: never hang the GPU; the host reports the error
@@ -974,15 +853,19 @@ __global__ __launch_bounds__(P6_THREADS, P6_PER_CU) void p6_persistent_kernel(Sc
             continue;
         }
         if (nt + nl > 0) {
+            // pt_walk_stint<2, false>: two parked leaves and immediate endings — deferred to once per pass as in hw8, this kernel lost 3 %
+            // (DESIGN.md, section 3 "leaf phases")
             const long long wt = (long long)nt * P.cost_t * (pt_count(&sh.cnt[PT_W_LIGHT]) + 1), wl = (long long)nl * P.cost_l * (pt_count(&sh.cnt[PT_W_TRACE]) + 1);
             if (nl == 0 || (nt > 0 && wt >= wl)) {
                 if (lane == 0) atomicAdd(&sh.cnt[PT_W_TRACE], 1);
-                p6_trace_stint<COUNT>(S, W, sh, P, wv, stack, shade_thr, n_closest, n_nodes, n_tris);
+                P6TraceWalk walk{S, W, sh, P, stack};
+                pt_walk_stint<2, false, COUNT>(walk, sh, P, wv, stack, shade_thr, n_closest, n_nodes, n_tris, prof);
                 if (lane == 0) atomicSub(&sh.cnt[PT_W_TRACE], 1);
                 clock_role(0);
             } else {
                 if (lane == 0) atomicAdd(&sh.cnt[PT_W_LIGHT], 1);
-                p6_light_stint<COUNT>(S, W, sh, P, wv, stack, shade_thr, n_light, n_nodes, n_tris);
+                P6LightWalk walk{S, W, sh, P, stack};
+                pt_walk_stint<2, false, COUNT>(walk, sh, P, wv, stack, shade_thr, n_light, n_nodes, n_tris, prof);
                 if (lane == 0) atomicSub(&sh.cnt[PT_W_LIGHT], 1);
                 clock_role(1);
             }
@@ -995,10 +878,7 @@ __global__ __launch_bounds__(P6_THREADS, P6_PER_CU) void p6_persistent_kernel(Sc
         if (++idle_spins > (1u << 24)) { gave_up = 2; break; }
     }
     if (gave_up && lane == 0 && P.counters) atomicAdd(&P.counters[gave_up == 1 ? 29 : 14], 1ull);
-    if (P.group_cost) { // every wave leaves the loop once the workgroup's pixels are done (or at the deadline)
-        __syncthreads();
-        for (uint32_t i = tid; i < n_local_groups; i += P6_THREADS) P.group_cost[sh.groups[i]] = sh.cost[i];
-    }
+    pt_leave<P6_THREADS>(sh, P, n_local_groups);
     if (lane == 0 && P.counters) {
         if (n_closest) atomicAdd(&P.counters[0], (unsigned long long)n_closest);
         if (n_light) atomicAdd(&P.counters[1], (unsigned long long)n_light);
