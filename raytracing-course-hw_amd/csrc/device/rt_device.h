@@ -382,7 +382,6 @@ RT_DEV bool slab_test_q(uint4 b, const RayGrid &r) {
 
 #define RT_LEAF_BIT 0x80000000u
 #define RT_EMPTY_LEAF 0xFFFFFFFFu
-#define RT_STACK_SIZE 64
 
 struct HitRec {
     int idx;       // BVH-order triangle index or -1

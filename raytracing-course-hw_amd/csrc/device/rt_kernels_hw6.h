@@ -16,7 +16,6 @@ namespace rtamd {
 namespace dev {
 
 #define RT6_MAX_DEPTH 8
-#define RT6_STACK_SIZE 128 // hw6's light tree is built on a constant sort key and can be very deep (practice6_2: 85)
 #define RT_PI_F 3.14159274101257324219f // const float PI = acos(-1), hw6/src/include/distributions.h:11
 
 struct Tri6Regs { F3 a, b, c, n; uint32_t ref_index, last, material; float point_prob; };
@@ -383,9 +382,6 @@ RT_DEV bool machine6_step(const SceneView6 &S, int ray_depth, Rng &rng, Machine6
 // LDS_STACK: the traversal stacks of the closest-hit walk and of the fast light walk live in LDS (one column of RT6_LDS_STACK
 // entries per lane, odd stride: conflict-free) instead of scratch memory; the host selects it when both of the library's own
 // trees are at most that deep.  The reference-order light walk (only after more than 16 hits) keeps its deep private stack.
-#ifndef RT6_LDS_STACK
-#define RT6_LDS_STACK 36   // 9.5 KB per wave: 16 waves per CU; measured on config 3 (stack entries / waves per SIMD): 36/4 61.6, 32/5 58.7, 40/4 57.6, 28/6 55.1, 48/3 55.5 Msamples/s
-#endif
 #define RT6_LDS_STRIDE (RT6_LDS_STACK + 1)
 #ifndef RT6_MIN_WAVES
 #define RT6_MIN_WAVES 4    // waves per SIMD the register allocation aims at (128 VGPR, some spills)
@@ -449,7 +445,7 @@ __global__ __launch_bounds__(64, RT6_MIN_WAVES) void render_hw6_kernel(SceneView
             }
         }
     }
-    if (R.counters) { atomicAdd(&R.counters[0], (unsigned long long)M.n_closest); atomicAdd(&R.counters[1], (unsigned long long)M.n_light); }
+    if (R.counters) { atomicAdd(&R.counters[CNT_CLOSEST], (unsigned long long)M.n_closest); atomicAdd(&R.counters[CNT_LIGHT], (unsigned long long)M.n_light); }
 }
 
 } // namespace dev

@@ -9,7 +9,6 @@
 namespace rtamd {
 namespace dev {
 
-#define RT_MAX_DEPTH 16
 
 struct Shaded {
     F3 emission, color, sn;
@@ -224,8 +223,8 @@ __global__ __launch_bounds__(64) void render_hw8_kernel(SceneView S, RenderView 
         }
     }
     if (COUNT && R.counters) {
-        atomicAdd(&R.counters[0], cnt.closest); atomicAdd(&R.counters[1], cnt.lightq);
-        atomicAdd(&R.counters[2], cnt.nodes); atomicAdd(&R.counters[3], cnt.tris);
+        atomicAdd(&R.counters[CNT_CLOSEST], cnt.closest); atomicAdd(&R.counters[CNT_LIGHT], cnt.lightq);
+        atomicAdd(&R.counters[CNT_NODE_VISITS], cnt.nodes); atomicAdd(&R.counters[CNT_TRI_TESTS], cnt.tris);
     }
 }
 

@@ -1,5 +1,5 @@
 // The 16-bit grid of the persistent pipeline's walk nodes (rt_types.h GpuNode4Q / NodeGrid): how the grid is laid over the scene and how a
-// box bound becomes a cell.  Shared by the host (rtamd_api.hip), the fold of the walk trees (rtamd_build.hip widen_nodes) and the test hooks.
+// box bound becomes a cell.  Shared by scene creation (rtamd_scene.hip), the fold of the walk trees (rtamd_build.hip widen_nodes) and the test hooks.
 #pragma once
 #include <math.h>
 #include <hip/hip_runtime.h>

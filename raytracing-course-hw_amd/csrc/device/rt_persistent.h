@@ -47,7 +47,6 @@ namespace dev {
 #define P8_WAVES 4
 #define P8_THREADS (64 * P8_WAVES)
 #define P8_PER_CU 5
-#define P8_STACK 24                   // LDS traversal stack entries per lane; the walkers' tree is built at most this deep (rt_bvh_build.h)
 #define PT_MAX_PATHS 5120             // paths per workgroup (bitmap capacity in LDS): x 1,280 workgroups = 6.5 M (a 3840x2160 frame on one GPU: two passes)
 #define PT_MIN_GROUP 16               // smallest group of the deal (group_shift 4): the LDS tables are sized for it
 #define PT_NW (PT_MAX_PATHS / 32)
@@ -186,7 +185,7 @@ struct PtParams {
     uint32_t front_first;             // 1: the queues serve the front of the workgroup's group list first (the host sorted it by cost, most expensive first)
     int prio;                         // experiment: 1 = walker stints run at raised wave priority (s_setprio 2), 2 = shader batches do
     unsigned long long deadline_ticks; // 100 MHz ticks a wave may spend in this launch before it gives up (error)
-    unsigned long long *counters;     // [0] closest-hit queries, [1] light queries, [2] node visits, [3] triangle tests, [10] discarded speculative hits, [12] exact closest hits, [13] exact light sums, [14] waves that gave up waiting for a lost path (error), [29] waves that ran into the launch deadline (error); counting builds: [30] / [31] light sums whose walk ends at the light tree's root / one level below it (pt_light_reach)
+    unsigned long long *counters;     // rt_types.h CounterSlot
     unsigned long long *debug;        // nullable: per workgroup {start time, exit time of its last wave (100 MHz ticks), paths}
     // COUNT builds, RTAMD_TRACE_PIXEL: every hit record the shader consumes for pixel trace_pixel (= y * width + x) is appended as
     // four float4 (r0..r3 of the path record: ray, hit, packed word); word 0 of trace_buf counts the entries
@@ -1025,30 +1024,30 @@ __global__ __launch_bounds__(P8_THREADS, P8_PER_CU) void pt_persistent_kernel(Sc
         lap(prof.t_idle);
         if (++idle_spins > (1u << 24)) { gave_up = 2; break; } // safety net (seconds): never hang the GPU on a lost path; the host reports it
     }
-    if (gave_up && lane == 0 && P.counters) atomicAdd(&P.counters[gave_up == 1 ? 29 : 14], 1ull);
+    if (gave_up && lane == 0 && P.counters) atomicAdd(&P.counters[gave_up == 1 ? CNT_DEADLINE : CNT_LOST_PATH], 1ull);
     pt_leave<P8_THREADS>(sh, P, n_local_groups);
     if (lane == 0 && P.counters) {
-        if (n_closest) atomicAdd(&P.counters[0], (unsigned long long)n_closest);
-        if (n_light) atomicAdd(&P.counters[1], (unsigned long long)n_light);
-        if (n_discarded) atomicAdd(&P.counters[10], (unsigned long long)n_discarded);
-        if (n_xtrace) atomicAdd(&P.counters[12], (unsigned long long)n_xtrace);
-        if (n_xlight) atomicAdd(&P.counters[13], (unsigned long long)n_xlight);
+        if (n_closest) atomicAdd(&P.counters[CNT_CLOSEST], (unsigned long long)n_closest);
+        if (n_light) atomicAdd(&P.counters[CNT_LIGHT], (unsigned long long)n_light);
+        if (n_discarded) atomicAdd(&P.counters[CNT_DISCARDED], (unsigned long long)n_discarded);
+        if (n_xtrace) atomicAdd(&P.counters[CNT_EXACT_CLOSEST], (unsigned long long)n_xtrace);
+        if (n_xlight) atomicAdd(&P.counters[CNT_EXACT_LIGHT], (unsigned long long)n_xlight);
     }
     if (COUNT && P.counters) {
-        atomicAdd(&P.counters[2], n_nodes); atomicAdd(&P.counters[3], n_tris);
-        atomicAdd(&P.counters[58], prof.light_hits); atomicAdd(&P.counters[59], prof.light_tests);
-        atomicAdd(&P.counters[30], prof.light_reach[0]); atomicAdd(&P.counters[31], prof.light_reach[1]);
+        atomicAdd(&P.counters[CNT_NODE_VISITS], n_nodes); atomicAdd(&P.counters[CNT_TRI_TESTS], n_tris);
+        atomicAdd(&P.counters[CNT_P8_LIGHT_HITS], prof.light_hits); atomicAdd(&P.counters[CNT_P8_LIGHT_TESTS], prof.light_tests);
+        atomicAdd(&P.counters[CNT_P8_LIGHT_REACH], prof.light_reach[0]); atomicAdd(&P.counters[CNT_P8_LIGHT_REACH + 1], prof.light_reach[1]);
         if (lane == 0) { // wave-level profile, words 16..27 and 48..57
-            atomicAdd(&P.counters[16], prof.t_trace); atomicAdd(&P.counters[17], prof.t_light); atomicAdd(&P.counters[18], prof.t_shade);
-            atomicAdd(&P.counters[19], prof.t_exact); atomicAdd(&P.counters[20], prof.t_idle);
-            atomicAdd(&P.counters[21], prof.iters[0]); atomicAdd(&P.counters[22], prof.lane_iters[0]);
-            atomicAdd(&P.counters[23], prof.iters[1]); atomicAdd(&P.counters[24], prof.lane_iters[1]);
-            atomicAdd(&P.counters[25], prof.stints); atomicAdd(&P.counters[26], prof.shade_batches); atomicAdd(&P.counters[27], prof.shade_items);
-            for (int k = 0; k < 3; k++) atomicAdd(&P.counters[60 + k], prof.t_sub[0][k]);
-            atomicAdd(&P.counters[63], prof.refills[0]);
+            atomicAdd(&P.counters[CNT_ROLE_TIME], prof.t_trace); atomicAdd(&P.counters[CNT_ROLE_TIME + 1], prof.t_light); atomicAdd(&P.counters[CNT_ROLE_TIME + 2], prof.t_shade);
+            atomicAdd(&P.counters[CNT_ROLE_TIME + 3], prof.t_exact); atomicAdd(&P.counters[CNT_ROLE_TIME + 4], prof.t_idle);
+            atomicAdd(&P.counters[CNT_P8_WALK_ITERS], prof.iters[0]); atomicAdd(&P.counters[CNT_P8_WALK_ITERS + 1], prof.lane_iters[0]);
+            atomicAdd(&P.counters[CNT_P8_WALK_ITERS + 2], prof.iters[1]); atomicAdd(&P.counters[CNT_P8_WALK_ITERS + 3], prof.lane_iters[1]);
+            atomicAdd(&P.counters[CNT_P8_STINTS], prof.stints); atomicAdd(&P.counters[CNT_P8_SHADE_BATCHES], prof.shade_batches); atomicAdd(&P.counters[CNT_P8_SHADE_ITEMS], prof.shade_items);
+            for (int k = 0; k < 3; k++) atomicAdd(&P.counters[CNT_P8_HANDOFF_TIME + k], prof.t_sub[0][k]);
+            atomicAdd(&P.counters[CNT_P8_HANDOFFS], prof.refills[0]);
             for (int w = 0; w < 2; w++) {
-                for (int k = 0; k < 3; k++) atomicAdd(&P.counters[48 + 3 * w + k], prof.t_part[w][k]);
-                atomicAdd(&P.counters[54 + 2 * w], prof.leaf_iters[w]); atomicAdd(&P.counters[55 + 2 * w], prof.leaf_lane_iters[w]);
+                for (int k = 0; k < 3; k++) atomicAdd(&P.counters[CNT_P8_WALK_TIME + 3 * w + k], prof.t_part[w][k]);
+                atomicAdd(&P.counters[CNT_P8_LEAF_ITERS + 2 * w], prof.leaf_iters[w]); atomicAdd(&P.counters[CNT_P8_LEAF_ITERS + 2 * w + 1], prof.leaf_lane_iters[w]);
             }
         }
     }

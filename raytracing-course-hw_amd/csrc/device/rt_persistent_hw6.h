@@ -27,7 +27,6 @@ namespace dev {
 #define P6_WAVES 4
 #define P6_THREADS (64 * P6_WAVES)
 #define P6_PER_CU 5
-#define P6_STACK 28                  // LDS stack entries per lane: the scene tree (GPU-built, depth <= 28) and the own tree over the lights must fit
 #define P6_MAX_PATHS 2304            // paths per workgroup: 4 x 28 x 256 B of stacks + 1.4 B per path = 31.9 KB, five workgroups per CU
 #define P6_NW (P6_MAX_PATHS / 32)
 // The rare roles that need work arrays per query (exact walks, light sums at a box boundary or with many hits) run P6_XBATCH queries at
@@ -816,7 +815,7 @@ __global__ __launch_bounds__(P6_THREADS, P6_PER_CU) void p6_persistent_kernel(Sc
             if (got != PT_NONE) {
                 float4 *r = p6_rec(W, pt_slot(sh, got));
                 const uint32_t kw = reinterpret_cast<const uint32_t *>(r + 7)[0];
-                if (COUNT && P.counters) atomicAdd(&P.counters[32 + ((kw & 0x7FFFFFFFu) < 15u ? (kw & 0x7FFFFFFFu) : 15u)], 1ull); // histogram of the hit counts that reach the slow role
+                if (COUNT && P.counters) atomicAdd(&P.counters[CNT_P6_SLOW_HITS + ((kw & 0x7FFFFFFFu) < 15u ? (kw & 0x7FFFFFFFu) : 15u)], 1ull); // histogram of the hit counts that reach the slow role
                 if ((kw >> 31) || kw > (uint32_t)P6_MERGE_HITS) batch = true;
                 else reinterpret_cast<float *>(r + 4)[3] = p6_merge_hits(S, reinterpret_cast<const float2 *>(r + 48), (int)kw, stack);
             }
@@ -877,18 +876,18 @@ __global__ __launch_bounds__(P6_THREADS, P6_PER_CU) void p6_persistent_kernel(Sc
         clock_role(4);
         if (++idle_spins > (1u << 24)) { gave_up = 2; break; }
     }
-    if (gave_up && lane == 0 && P.counters) atomicAdd(&P.counters[gave_up == 1 ? 29 : 14], 1ull);
+    if (gave_up && lane == 0 && P.counters) atomicAdd(&P.counters[gave_up == 1 ? CNT_DEADLINE : CNT_LOST_PATH], 1ull);
     pt_leave<P6_THREADS>(sh, P, n_local_groups);
     if (lane == 0 && P.counters) {
-        if (n_closest) atomicAdd(&P.counters[0], (unsigned long long)n_closest);
-        if (n_light) atomicAdd(&P.counters[1], (unsigned long long)n_light);
-        if (n_slow) atomicAdd(&P.counters[13], (unsigned long long)n_slow);
-        if (n_exact) atomicAdd(&P.counters[12], (unsigned long long)n_exact);
+        if (n_closest) atomicAdd(&P.counters[CNT_CLOSEST], (unsigned long long)n_closest);
+        if (n_light) atomicAdd(&P.counters[CNT_LIGHT], (unsigned long long)n_light);
+        if (n_slow) atomicAdd(&P.counters[CNT_P6_SLOW_LIGHT], (unsigned long long)n_slow);
+        if (n_exact) atomicAdd(&P.counters[CNT_EXACT_CLOSEST], (unsigned long long)n_exact);
     }
-    if (lane == 0 && n_xlight && P.counters) atomicAdd(&P.counters[11], (unsigned long long)n_xlight);
+    if (lane == 0 && n_xlight && P.counters) atomicAdd(&P.counters[CNT_P6_EXACT_LIGHT], (unsigned long long)n_xlight);
     if (COUNT && P.counters) {
-        atomicAdd(&P.counters[2], n_nodes); atomicAdd(&P.counters[3], n_tris);
-        if (lane == 0) for (int i = 0; i < 5; i++) atomicAdd(&P.counters[16 + i], t_role[i]);
+        atomicAdd(&P.counters[CNT_NODE_VISITS], n_nodes); atomicAdd(&P.counters[CNT_TRI_TESTS], n_tris);
+        if (lane == 0) for (int i = 0; i < 5; i++) atomicAdd(&P.counters[CNT_ROLE_TIME + i], t_role[i]);
     }
     if (P.debug && lane == 0) atomicMax(&P.debug[3 * blockIdx.x + 1], __builtin_amdgcn_s_memrealtime());
 }

@@ -6,6 +6,54 @@
 
 namespace rtamd {
 
+// Limits that scene creation and the frame geometry check and the kernels size their stacks by.
+#define RT_MAX_DEPTH 16               // ray_depth of the hw8 / hw7 integrators
+#define RT_STACK_SIZE 64              // private traversal stack of the megakernel and of the exact walks over the reference's own tree
+#define P8_STACK 24                   // rt_persistent.h: LDS traversal stack entries per lane; the walkers' tree is built at most this deep (rt_bvh_build.h)
+
+// The 64 counters of a render (8 bytes each; RenderView::counters / PtParams::counters), zeroed before every frame and read back after
+// it for rt_stats, the error checks and the RTAMD_DEBUG_COUNTERS report (render_frame, report_persistent).  One name per meaning: where
+// two kernels use a slot differently it has two names, and the comment says who writes it (P8 = pt_persistent_kernel, P6 =
+// p6_persistent_kernel, WF = the round pipeline's kernels, mega = render_hw8_kernel / render_hw6_kernel).
+enum CounterSlot {
+    CNT_CLOSEST = 0,            // closest-hit queries: P8, P6, mega; WF: summed by the host from the rounds' queue lengths
+    CNT_LIGHT = 1,              // light-pdf queries: likewise
+    CNT_NODE_VISITS = 2,        // counting variants of P8, P6, WF, render_hw8_kernel
+    CNT_TRI_TESTS = 3,
+    CNT_WF_NODE_ITERS = 4,      // WF wf_trace_loop: wave node-iterations, ...
+    CNT_WF_LEAF_PHASES = 5,
+    CNT_WF_LEAF_LANES = 6,
+    CNT_WF_REFILLS = 7,
+    CNT_WF_LANE_NODES = 8,      // ... and its own share of CNT_NODE_VISITS / CNT_TRI_TESTS
+    CNT_WF_LANE_TRIS = 9,
+    CNT_DISCARDED = 10,         // speculative closest hits that the clamp step discarded: P8, WF wf_shade_item
+    CNT_WF_SLOW_LIGHT = 11,     // WF: light sums finished by wf_light_exact_kernel (summed by the host from the rounds' counters)
+    CNT_P6_EXACT_LIGHT = 11,    // P6: exact light sums
+    CNT_EXACT_CLOSEST = 12,     // exact closest hits: P8, P6, WF wf_trace_exact_kernel
+    CNT_EXACT_LIGHT = 13,       // exact light sums: P8; WF: the host's copy of CNT_WF_SLOW_LIGHT
+    CNT_P6_SLOW_LIGHT = 13,     // P6: light sums through the slow role
+    CNT_LOST_PATH = 14,         // P8, P6: waves that gave up waiting for a lost path (an error)
+    CNT_WANT_HISTOGRAMS = 15,   // request, set by the host (RTAMD_DEBUG_COUNTERS): WF's counting kernels fill the two histograms
+    CNT_WF_HIST_CLOSEST = 16,   // WF, 16 slots: closest-hit queries by in-flight wave iterations / 32
+    CNT_ROLE_TIME = 16,         // P8, P6, 5 slots: wave time by role (closest-hit walks, light walks, shading, exact | slow light sums, idle)
+    CNT_P8_WALK_ITERS = 21,     // P8, 2 slots per walker (closest hit, light): wave iterations, lane iterations
+    CNT_P8_STINTS = 25,
+    CNT_P8_SHADE_BATCHES = 26,
+    CNT_P8_SHADE_ITEMS = 27,
+    CNT_DEADLINE = 29,          // P8, P6: waves that ran into the launch deadline (an error)
+    CNT_P8_LIGHT_REACH = 30,    // P8, 2 slots: light sums whose walk ends at the light tree's root / one level below it (pt_light_reach)
+    CNT_WF_HIST_LIGHT = 32,     // WF, 16 slots: light queries by in-flight wave iterations / 32
+    CNT_P6_SLOW_HITS = 32,      // P6, 16 slots: light sums in the slow role by number of hits
+    CNT_P8_WALK_TIME = 48,      // P8, 3 slots per walker: hand-off and refill, inner nodes, leaves
+    CNT_P8_LEAF_ITERS = 54,     // P8, 2 slots per walker: leaf passes, their lanes
+    CNT_P8_LIGHT_HITS = 58,
+    CNT_P8_LIGHT_TESTS = 59,
+    CNT_P8_HANDOFF_TIME = 60,   // P8, 3 slots: the closest-hit walker's hand-off time by part (publish, take, read rays)
+    CNT_P8_HANDOFFS = 63,       // P8: the closest-hit walker's hand-off points
+    CNT_SLOTS = 64
+};
+#define CNT_BYTES (CNT_SLOTS * sizeof(unsigned long long)) // the 512-byte block
+
 // Binary BVH node with BOTH child boxes inline (one 64-byte fetch decides both children).
 // child = index of an inner node, or 0x80000000|first for a leaf whose primitives run from `first`
 // up to the record whose `pad` word is 1 (cnt repeats the count for diagnostics), or 0xFFFFFFFF (empty).
@@ -147,7 +195,7 @@ struct RenderView {
     float *out_rgb;                // nullable
     uint8_t *out_rgb8;             // nullable
     uint32_t *work_counter;        // dynamic tile queue head
-    unsigned long long *counters;  // nullable: [closest, lightq, node_visits, tri_tests]
+    unsigned long long *counters;  // nullable: CNT_SLOTS counters (CounterSlot)
     // Throughput mode (rt_render_params.sample_streams = K > 1, wavefront path only): K independent random streams per pixel,
     // `samples` is then the count PER STREAM, path slot = stream * n_pixslots + pixel slot, every slot leaves its unnormalised
     // sum in `partial` and wf_reduce_streams_kernel adds the K sums of a pixel in stream order.

@@ -3,6 +3,13 @@
 #include <stdint.h>
 #include "rt_types.h"
 
+// Depth limits that scene creation checks and the kernels size their stacks by.
+#define RT6_STACK_SIZE 128 // rt_kernels_hw6.h: hw6's light tree is built on a constant sort key and can be very deep (practice6_2: 85)
+#ifndef RT6_LDS_STACK
+#define RT6_LDS_STACK 36   // rt_kernels_hw6.h: 9.5 KB per wave: 16 waves per CU; measured on config 3 (stack entries / waves per SIMD): 36/4 61.6, 32/5 58.7, 40/4 57.6, 28/6 55.1, 48/3 55.5 Msamples/s
+#endif
+#define P6_STACK 28        // rt_persistent_hw6.h: LDS stack entries per lane: the scene tree (GPU-built, depth <= 28) and the own tree over the lights must fit
+
 namespace rtamd {
 
 // 64-byte figure record for the hw6 triangle test (hw6/src/primitives.cpp:143-164).

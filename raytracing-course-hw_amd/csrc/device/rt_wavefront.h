@@ -27,6 +27,7 @@
 // lines and the backward fold at the end of a path reads one contiguous run.
 #pragma once
 #include "rt_exact.h"
+#include "rt_types_wf.h"
 
 namespace rtamd {
 namespace dev {
@@ -38,18 +39,6 @@ namespace dev {
 // Mix::pdf / clamp step (its stack entry is filled, the ray in q0/q1 is the one it sampled).
 // Stack entry (2 x float4): E0 = emission.xyz, pdf (cosine + vndf terms; the light loop adds its term)
 //                           E1 = brdf (then mult).xyz, dot(d, n_s)
-struct WfView {
-    float4 *r0;             // per slot: `stride` float4 = WF_REC_BASE (R0 record) + 2 per stack level, contiguous
-    uint32_t stride;
-    uint32_t *q_trace[2];
-    uint32_t *q_light;
-    uint32_t *ctr;          // per round r, WF_CTR words: +0 trace count, +1 light count, +2 trace head, +3 light head, +4 slow-light count
-    uint32_t *q_slow;       // light queries of this round that the lean loop hands to wf_light_exact_kernel
-    uint32_t n_slots;
-    uint32_t *ovf;          // SPILL variant only: WF_OVF stack entries per persistent thread beyond the WF_STACK entries in LDS
-    uint32_t slot_base;     // this pipeline's first path slot (the frame's slots are cut into independent pipelines, one per stream)
-};
-
 RT_DEV float4 *wf_rec(const WfView &W, uint32_t slot) { return W.r0 + (size_t)slot * W.stride; }
 #define WF_REC_BASE 4          // float4 in front of the per-level entries: q0..q3 (16 float4 = two 128-byte lines per path at depth 6)
 RT_DEV float4 *wf_entry(const WfView &W, uint32_t slot, int level) { return W.r0 + ((size_t)slot * W.stride + (uint32_t)(WF_REC_BASE + 2 * level)); } // one 64-bit multiply-add of 32-bit operands
@@ -319,8 +308,8 @@ RT_DEV void wf_trace_loop(const SceneView &S, const WfView &W, uint32_t (*stack)
     };
     unsigned long long n_nodes = 0, n_tris = 0;
     unsigned long long w_node_iters = 0, w_leaf_phases = 0, w_leaf_lanes = 0, w_refills = 0; // wave-level (lane 0 reports)
-    uint32_t w_iter = 0, ray_start = 0; // COUNT: wave iterations a ray stays in flight -> histogram counters[16 + min(15, iterations / 32)]
-    const bool hist = COUNT && counters && counters[15] != 0; // the host sets counters[15] when the histogram is wanted (one global atomic per query)
+    uint32_t w_iter = 0, ray_start = 0; // COUNT: wave iterations a ray stays in flight -> histogram counters[CNT_WF_HIST_CLOSEST + min(15, iterations / 32)]
+    const bool hist = COUNT && counters && counters[CNT_WANT_HISTOGRAMS] != 0; // the host sets it when the histogram is wanted (one global atomic per query)
     for (;;) {
         unsigned long long idle = __ballot(!active);
         if (idle && (slice.pos < slice.end || !slice.done) && (__popcll(idle) >= refill || idle == ~0ull)) {
@@ -367,7 +356,7 @@ RT_DEV void wf_trace_loop(const SceneView &S, const WfView &W, uint32_t (*stack)
                 else if (sp == 0) { // traversal finished: publish the hit
                     store_hit();
                     active = false;
-                    if (COUNT && hist) { uint32_t b = (w_iter - ray_start) >> 5; atomicAdd(&counters[16 + (b > 15u ? 15u : b)], 1ull); }
+                    if (COUNT && hist) { uint32_t b = (w_iter - ray_start) >> 5; atomicAdd(&counters[CNT_WF_HIST_CLOSEST + (b > 15u ? 15u : b)], 1ull); }
                 } else cur = wf_spop<SPILL>(stack, ovf, lds_limit, lane, sp);
             }
         }
@@ -397,14 +386,14 @@ RT_DEV void wf_trace_loop(const SceneView &S, const WfView &W, uint32_t (*stack)
             if (sp == 0) {
                 store_hit();
                 active = false;
-                if (COUNT && hist) { uint32_t b = (w_iter - ray_start) >> 5; atomicAdd(&counters[16 + (b > 15u ? 15u : b)], 1ull); }
+                if (COUNT && hist) { uint32_t b = (w_iter - ray_start) >> 5; atomicAdd(&counters[CNT_WF_HIST_CLOSEST + (b > 15u ? 15u : b)], 1ull); }
             } else cur = wf_spop<SPILL>(stack, ovf, lds_limit, lane, sp);
         }
     }
     if (COUNT && counters) {
-        atomicAdd(&counters[2], n_nodes); atomicAdd(&counters[3], n_tris);
-        atomicAdd(&counters[8], n_nodes); atomicAdd(&counters[9], n_tris);
-        if (lane == 0) { atomicAdd(&counters[4], w_node_iters); atomicAdd(&counters[5], w_leaf_phases); atomicAdd(&counters[6], w_leaf_lanes); atomicAdd(&counters[7], w_refills); }
+        atomicAdd(&counters[CNT_NODE_VISITS], n_nodes); atomicAdd(&counters[CNT_TRI_TESTS], n_tris);
+        atomicAdd(&counters[CNT_WF_LANE_NODES], n_nodes); atomicAdd(&counters[CNT_WF_LANE_TRIS], n_tris);
+        if (lane == 0) { atomicAdd(&counters[CNT_WF_NODE_ITERS], w_node_iters); atomicAdd(&counters[CNT_WF_LEAF_PHASES], w_leaf_phases); atomicAdd(&counters[CNT_WF_LEAF_LANES], w_leaf_lanes); atomicAdd(&counters[CNT_WF_REFILLS], w_refills); }
     }
 }
 
@@ -488,7 +477,7 @@ RT_DEV void wf_light_loop(const SceneView &S, const WfView &W, uint32_t (*stack)
             descending = false;
         }
     }
-    if (COUNT && counters) { atomicAdd(&counters[2], n_nodes); atomicAdd(&counters[3], n_tris); }
+    if (COUNT && counters) { atomicAdd(&counters[CNT_NODE_VISITS], n_nodes); atomicAdd(&counters[CNT_TRI_TESTS], n_tris); }
 }
 
 // The same sum, decoupled: WHICH lights the ray hits is found by a plain all-hits walk (no frames, left child first, so the
@@ -509,8 +498,8 @@ RT_DEV void wf_light_loop_lean(const SceneView &S, const WfView &W, uint32_t (*s
     F3 o = f3(0.f, 0.f, 0.f), d = f3(0.f, 0.f, 1.f);
     RayInv ray = make_ray_inv(o, d);
     unsigned long long n_nodes = 0, n_tris = 0;
-    uint32_t w_iter = 0, ray_start = 0; // COUNT: histogram of in-flight wave iterations per query, counters[32 + ...]
-    const bool hist = COUNT && counters && counters[15] != 0;
+    uint32_t w_iter = 0, ray_start = 0; // COUNT: histogram of in-flight wave iterations per query, counters[CNT_WF_HIST_LIGHT + ...]
+    const bool hist = COUNT && counters && counters[CNT_WANT_HISTOGRAMS] != 0;
     // Hit j of the finished walk: light index in stack[31-2j], term in stack[30-2j] (ascending indices); the bottom of the
     // column is free by then and holds the separation depths while the terms are merged.
     auto finish = [&]() {
@@ -583,7 +572,7 @@ RT_DEV void wf_light_loop_lean(const SceneView &S, const WfView &W, uint32_t (*s
                 if (h0 & h1) { stack[sp++][lane] = c1; cur = c0; if (sp + 2 * k >= WF_STACK) overflow = true; }
                 else if (h0) cur = c0;
                 else if (h1) cur = c1;
-                else if (sp == 0) { finish(); if (COUNT && hist) { uint32_t b = (w_iter - ray_start) >> 5; atomicAdd(&counters[32 + (b > 15u ? 15u : b)], 1ull); } }
+                else if (sp == 0) { finish(); if (COUNT && hist) { uint32_t b = (w_iter - ray_start) >> 5; atomicAdd(&counters[CNT_WF_HIST_LIGHT + (b > 15u ? 15u : b)], 1ull); } }
                 else cur = stack[--sp][lane];
             }
         }
@@ -603,11 +592,11 @@ RT_DEV void wf_light_loop_lean(const SceneView &S, const WfView &W, uint32_t (*s
                     i++;
                 }
             }
-            if (sp == 0) { finish(); if (COUNT && hist) { uint32_t b = (w_iter - ray_start) >> 5; atomicAdd(&counters[32 + (b > 15u ? 15u : b)], 1ull); } }
+            if (sp == 0) { finish(); if (COUNT && hist) { uint32_t b = (w_iter - ray_start) >> 5; atomicAdd(&counters[CNT_WF_HIST_LIGHT + (b > 15u ? 15u : b)], 1ull); } }
             else cur = stack[--sp][lane];
         }
     }
-    if (COUNT && counters) { atomicAdd(&counters[2], n_nodes); atomicAdd(&counters[3], n_tris); }
+    if (COUNT && counters) { atomicAdd(&counters[CNT_NODE_VISITS], n_nodes); atomicAdd(&counters[CNT_TRI_TESTS], n_tris); }
 }
 
 // ---- traverse: both loops in one persistent launch -------------------------------------------------------------------
@@ -693,7 +682,7 @@ RT_DEV int wf_shade_item(const SceneView &S, const RenderView &R, const WfView &
         if (clamp || depth + 1 >= R.ray_depth) {
             // clamp hack (scene.cpp:161-163): the path returns the emission and the speculative hit is dropped; at the
             // last level the inner call returns 0, i.e. emission + mult * 0 evaluated literally.
-            if (counters) atomicAdd(&counters[10], 1ull);
+            if (counters) atomicAdd(&counters[CNT_DISCARDED], 1ull);
             if (discarded) *discarded = true;
             ended = true;
             tail = f3(e0.x, e0.y, e0.z);
@@ -711,7 +700,7 @@ RT_DEV int wf_shade_item(const SceneView &S, const RenderView &R, const WfView &
             e[1] = make_float4(mult.x, mult.y, mult.z, e1.w);
             if (survives) depth++;
             else {
-                if (counters) atomicAdd(&counters[10], 1ull);
+                if (counters) atomicAdd(&counters[CNT_DISCARDED], 1ull);
                 if (discarded) *discarded = true;
                 ended = true; tail = f3(0.f, 0.f, 0.f); levels = depth + 1;
             }
@@ -902,7 +891,7 @@ __global__ __launch_bounds__(64) void wf_trace_exact_kernel(SceneView S, RenderV
         r[2] = make_float4(bt, bu, bv, __uint_as_float(hit));
         float *pk = reinterpret_cast<float *>(r + 3) + 3;
         *pk = __uint_as_float(__float_as_uint(*pk) | WF_VERIFIED_BIT);
-        if (counters) atomicAdd(&counters[12], 1ull);
+        if (counters) atomicAdd(&counters[CNT_EXACT_CLOSEST], 1ull);
         const int todo = wf_shade_item(S, R, W, slot, counters);
         if (todo & WF_NEXT_TRACE) next_queue[atomicAdd(next_count, 1u)] = slot;
         if (todo & WF_NEXT_LIGHT) W.q_light[atomicAdd(light_count, 1u)] = slot;

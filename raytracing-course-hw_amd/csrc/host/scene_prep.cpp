@@ -14,6 +14,7 @@
 //
 // Build with -ffp-contract=off (reference float semantics for the precomputed sub-expressions).
 #include "scene_prep.h"
+#include "knobs.h"
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -152,8 +153,7 @@ inline float scene_abs_pad(const std::vector<Box3> &boxes, const rt_camera &cam)
     float m = 0.f;
     for (int k = 0; k < 3; k++) m = smax(m, std::fabs(cam.position[k]));
     for (const Box3 &b : boxes) for (int k = 0; k < 3; k++) m = smax(m, smax(std::fabs(b.lo[k]), std::fabs(b.hi[k])));
-    float scale = 1.f;
-    if (const char *e = getenv("RTAMD_BOX_PAD_SCALE")) scale = (float)atof(e); // experiments
+    const float scale = (float)env_float("RTAMD_BOX_PAD_SCALE", 1.0); // experiments
     return m * 3.814697265625e-06f * scale; // 2^-18
 }
 
@@ -414,7 +414,7 @@ void prepare_scene(const rt_scene_desc &d, PreparedScene &out, bool tree_on_devi
         const double m1[3] = {0.239f, 0.419f, 0.533f}, m2[3] = {0.35743f, 0.66682f, 0.69695f};
         const double kx = m1[1] * m2[2] - m1[2] * m2[1], ky = m1[2] * m2[0] - m1[0] * m2[2], kz = m1[0] * m2[1] - m1[1] * m2[0];
         const double kn = std::sqrt(kx * kx + ky * ky + kz * kz);
-        const double tripwire_cos = getenv("RTAMD_TRIPWIRE_COS") ? atof(getenv("RTAMD_TRIPWIRE_COS")) : 6.103515625e-05; // 2^-14
+        const double tripwire_cos = env_float("RTAMD_TRIPWIRE_COS", 6.103515625e-05); // 2^-14
         struct Wire { uint64_t key; float lo[3], hi[3]; uint32_t figure; };
         std::vector<Wire> wires;
         float slo[3] = {3e38f, 3e38f, 3e38f}, shi[3] = {-3e38f, -3e38f, -3e38f};
@@ -459,7 +459,7 @@ void prepare_scene(const rt_scene_desc &d, PreparedScene &out, bool tree_on_devi
         }
         const size_t n_groups = runs.size();
         out.n_tripwire_groups = (uint32_t)n_groups;
-        if (getenv("RTAMD_DUMP_TRIPWIRES")) // diagnostic
+        if (env_flag("RTAMD_DUMP_TRIPWIRES")) // diagnostic
             for (const Run &r : runs) fprintf(stderr, "[rtamd] tripwire group: %zu wires, box %.3f %.3f %.3f .. %.3f %.3f %.3f\n", r.last - r.first, r.lo[0], r.lo[1], r.lo[2], r.hi[0], r.hi[1], r.hi[2]);
         out.tripwires.assign((n_groups + wires.size()) * 8, 0.f);
         for (size_t g = 0; g < n_groups; g++) {

@@ -1,25 +1,19 @@
-// C-ABI of the render path (include/rtamd.h): scene upload, render launch, output handling.
+// C-ABI of the render path (include/rtamd.h): every kernel that renders, the launch drivers, the statistics and the resumable renders.
+// Scene creation and the file front-end are in rtamd_scene.hip.
 // No CPU fallback exists: every entry point that needs the GPU fails with RT_ERR_NO_DEVICE / RT_ERR_HIP
 // when HIP is unusable.
 #include <hip/hip_runtime.h>
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <functional>
 #include <memory>
-#include <stdexcept>
 #include <string>
 #include <vector>
 #include "../../include/rtamd.h"
-#include "host/host_scene.h"
-#include "host/png.h"
-#include "host/scene_prep.h"
-#include "host/shared_prep.h"
-#include "host/hip_check.h"
-#include "device/rt_node_grid.h"
-#include "host/device_build.h"
+#include "host/knobs.h"
+#include "host/rt_scene.h"
 #include "device/rt_kernels_hw8.h"
 #include "device/rt_wavefront.h"
 #include "device/rt_persistent.h"
@@ -29,536 +23,12 @@
 #include "device/rt_kernels_hw2.h"
 #include "device/rt_kernels_hw4.h"
 #include "device/rt_kernels_hw5.h"
-#include <cstdlib>
 
-namespace rtamd {
-static thread_local std::string g_last_error;
-void set_error(const std::string &msg) { g_last_error = msg; }
-}
 using namespace rtamd;
-
-namespace {
-
-template <class T> T *upload(const std::vector<T> &v, uint64_t &bytes) {
-    if (v.empty()) { // keep pointers valid: one dummy element
-        void *p = nullptr;
-        HIP_CHECK(hipMalloc(&p, sizeof(T) > 16 ? sizeof(T) : 16));
-        HIP_CHECK(hipMemset(p, 0, sizeof(T) > 16 ? sizeof(T) : 16));
-        return (T *)p;
-    }
-    void *p = nullptr;
-    size_t n = v.size() * sizeof(T);
-    HIP_CHECK(hipMalloc(&p, n));
-    HIP_CHECK(hipMemcpy(p, v.data(), n, hipMemcpyHostToDevice));
-    bytes += n;
-    return (T *)p;
-}
-
-double now_ms() {
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
-
-// Device buffer owned by one rt_render call (host-output renders): freed on every way out of the call.
-struct OwnedDev {
-    void *p = nullptr;
-    ~OwnedDev() { if (p) (void)hipFree(p); }
-};
-
-int fail(int code, const std::string &msg) {
-    set_error(msg);
-    return code;
-}
-
-} // namespace
-
-struct rt_scene {
-    int device = 0;
-    SceneView view{};
-    SceneView6 view6{};
-    SceneViewTxt viewt{};
-    SceneView5 view5{};
-    bool txt_has_triangles = false; // TRIANGLE figures exist only in the hw5 grammar: such a scene renders with RT_INTEGRATOR_HW5 only
-    int flavor = RT_INTEGRATOR_HW8; // which integrator this scene was prepared for
-    bool hw6_lds_stack = false, hw6_pt_stack = false;
-    uint32_t light_walk_depth = 0;   // hw8: depth of the tree the persistent kernel's light walker uses
-    uint32_t wide_depth = 0, wide_light_depth = 0; // levels of the four-wide forms of the two walk trees (rt_types.h GpuNode4Q)
-    std::vector<void *> allocations;
-    rt_scene_info info{};
-    std::vector<uint32_t> light_order;
-    float fov_y = 0;
-    uint32_t *d_work_counter = nullptr;
-    unsigned long long *d_counters = nullptr;
-    hipEvent_t ev_start = nullptr, ev_stop = nullptr;
-    int n_cus = 256;
-    // wavefront path state (grown on demand, reused across renders)
-    dev::WfView wf{};
-    size_t wf_slots = 0, wf_levels = 0, wf_ctr_words = 0, wf_ovf_words = 0;
-    int wf_pipes = 1;                // pipelines of the last wavefront render and the counter words of each
-    size_t wf_ctr_block = 0;
-    hipStream_t wf_streams[4] = {nullptr, nullptr, nullptr, nullptr}; // one per pipeline when a render uses more than one
-    hipEvent_t ev_fork = nullptr, ev_join[4] = {nullptr, nullptr, nullptr, nullptr};
-    std::vector<void *> wf_allocs;
-    float *d_partial = nullptr;      // throughput mode: per-stream pixel sums
-    size_t partial_bytes = 0;
-    std::vector<hipEvent_t> ev_pool; // brackets every launch of the dominant kernel when stats are requested
-    bool device_tree = false;                 // RT_BUILD_DEVICE_BVH: figure order = LOAD order, no reference trees
-    unsigned long long *d_pt_debug = nullptr; // persistent pipeline: per workgroup {start, exit time, paths} (RTAMD_DEBUG_COUNTERS)
-    void *pt_records = nullptr;      // persistent pipeline: path records of one pass
-    uint32_t *pt_groups = nullptr;   // [cost per group | group_ofs (n_blocks + 1) | group_ids]: the re-deal between the phases of a frame
-    size_t pt_record_bytes = 0, pt_group_words = 0;
-    uint32_t pt_passes = 0, pt_blocks = 0, pt_launches = 0;
-    double pt_rebalance_ms = 0, pt_imbalance = 0;
-    void free_wf() {
-        for (void *p : wf_allocs) (void)hipFree(p);
-        wf_allocs.clear();
-        wf = dev::WfView{};
-        wf_slots = wf_levels = wf_ctr_words = wf_ovf_words = 0;
-    }
-    ~rt_scene() {
-        free_wf();
-        if (d_partial) (void)hipFree(d_partial);
-        if (pt_records) (void)hipFree(pt_records);
-        if (pt_groups) (void)hipFree(pt_groups);
-        if (d_pt_debug) (void)hipFree(d_pt_debug);
-        for (void *p : allocations) (void)hipFree(p);
-        if (ev_start) (void)hipEventDestroy(ev_start);
-        if (ev_stop) (void)hipEventDestroy(ev_stop);
-        for (hipEvent_t e : ev_pool) (void)hipEventDestroy(e);
-        for (int h = 0; h < 4; h++) { if (wf_streams[h]) (void)hipStreamDestroy(wf_streams[h]); if (ev_join[h]) (void)hipEventDestroy(ev_join[h]); }
-        if (ev_fork) (void)hipEventDestroy(ev_fork);
-    }
-};
 
 extern "C" {
 
 int rt_abi_version(void) { return RTAMD_ABI_VERSION; }
-const char *rt_last_error(void) { return g_last_error.c_str(); }
-
-int rt_scene_create(const rt_scene_desc *desc, rt_scene **out) { return rtamd::scene_create_shared(desc, out, nullptr); }
-
-} // extern "C"
-
-// rt_scene_create with the host-side preparation of an hw8 / hw7 scene (the replay of the reference's figure and light order:
-// ~0.4 s for the benchmark scene) optionally taken from `shared`: the first caller fills it, the others wait for it and only upload.
-// rt_multi_create gives all its devices the same one (rtamd_multi.hip); the plain C entry point passes none.
-int rtamd::scene_create_shared(const rt_scene_desc *desc, rt_scene **out, rtamd::SharedPrep *shared) {
-    if (!desc || !out) return fail(RT_ERR_INVALID_ARG, "rt_scene_create: null argument");
-    if (desc->struct_size != sizeof(rt_scene_desc)) return fail(RT_ERR_INVALID_ARG, "rt_scene_create: struct_size mismatch (ABI skew)");
-    *out = nullptr;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-        return fail(RT_ERR_NO_DEVICE, "rt_scene_create: no HIP device available (this library has no CPU fallback)");
-    try {
-        std::unique_ptr<rt_scene> s(new rt_scene());
-        HIP_CHECK(hipGetDevice(&s->device));
-        hipDeviceProp_t prop;
-        HIP_CHECK(hipGetDeviceProperties(&prop, s->device));
-        s->n_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-        double t0 = now_ms();
-        // Analytic primitives only: a .txt scene (hw1 / hw3).
-        // (A scene without any figure counts as a .txt scene when its camera carries only CAMERA_FOV_X, as the .txt loader leaves it.)
-        if (desc->n_triangles == 0 && (desc->n_primitives > 0 || (desc->camera.fov_x != 0.f && desc->camera.fov_y == 0.f))) {
-            std::vector<GpuPrim> prims(desc->n_primitives);
-            for (uint32_t i = 0; i < desc->n_primitives; i++) {
-                const rt_primitive &p = desc->primitives[i];
-                GpuPrim &g = prims[i];
-                memset(&g, 0, sizeof g);
-                if (p.type < RT_PRIM_ELLIPSOID || p.type > RT_PRIM_TRIANGLE) return fail(RT_ERR_INVALID_ARG, "rt_scene_create: bad primitive type");
-                if (p.type == RT_PRIM_TRIANGLE) s->txt_has_triangles = true;
-                for (int k = 0; k < 3; k++) { g.data[k] = p.data[k]; g.position[k] = p.position[k]; g.color[k] = p.color[k]; g.emission[k] = p.emission[k]; }
-                for (int k = 0; k < 4; k++) g.rotation[k] = p.rotation[k];
-                g.type = p.type; g.kind = p.kind; g.ior = p.ior;
-            }
-            uint64_t bytes = 0;
-            SceneViewTxt &V = s->viewt;
-            V.prims = upload(prims, bytes);
-            s->allocations.push_back((void *)V.prims);
-            V.n_prims = desc->n_primitives;
-            for (int k = 0; k < 3; k++) {
-                V.cam_pos[k] = desc->camera.position[k]; V.cam_right[k] = desc->camera.right[k];
-                V.cam_up[k] = desc->camera.up[k]; V.cam_fwd[k] = desc->camera.forward[k];
-                V.bg[k] = desc->bg_color[k];
-            }
-            V.tan_fov_x = (float)std::tan((double)(desc->camera.fov_x / 2)); // hw3/src/scene.cpp:100
-            V.tan_fov_x_f = tanf(desc->camera.fov_x / 2);                    // hw1/src/scene.cpp:23, hw2/src/scene.cpp:91 (<math.h>: float overload)
-            std::vector<GpuLight> lights(desc->n_lights);
-            for (uint32_t i = 0; i < desc->n_lights; i++) {
-                const rt_light &L = desc->lights[i];
-                GpuLight &g = lights[i];
-                memset(&g, 0, sizeof g);
-                if (L.type != RT_LIGHT_POINT && L.type != RT_LIGHT_DIRECTIONAL) return fail(RT_ERR_INVALID_ARG, "rt_scene_create: bad light type");
-                g.type = L.type;
-                for (int k = 0; k < 3; k++) { g.intensity[k] = L.intensity[k]; g.position[k] = L.position[k]; g.attenuation[k] = L.attenuation[k]; g.direction[k] = L.direction[k]; }
-            }
-            V.n_lights = desc->n_lights;
-            if (desc->n_lights) { V.lights = upload(lights, bytes); s->allocations.push_back((void *)V.lights); }
-            for (int k = 0; k < 3; k++) V.ambient[k] = desc->ambient_light[k];
-            std::vector<uint32_t> light_prims; // hw4/src/scene.cpp:12-21
-            for (uint32_t i = 0; i < desc->n_primitives; i++) {
-                const rt_primitive &p = desc->primitives[i];
-                if ((p.emission[0] > 0 || p.emission[1] > 0 || p.emission[2] > 0) && (p.type == RT_PRIM_BOX || p.type == RT_PRIM_ELLIPSOID)) light_prims.push_back(i);
-            }
-            V.n_light_prims = (uint32_t)light_prims.size();
-            if (!light_prims.empty()) { V.light_prims = upload(light_prims, bytes); s->allocations.push_back((void *)V.light_prims); }
-            { // hw5 structures: reference figure order, BVH over the non-planes, light list + light BVH
-                PreparedScene5 P5;
-                prepare_scene_hw5(*desc, P5);
-                SceneView5 &V5 = s->view5;
-                V5.nodes = upload(P5.nodes, bytes); s->allocations.push_back((void *)V5.nodes);
-                V5.figs = upload(P5.figs, bytes); s->allocations.push_back((void *)V5.figs);
-                V5.light_nodes = upload(P5.light_nodes, bytes); s->allocations.push_back((void *)V5.light_nodes);
-                V5.ref_nodes = upload(P5.ref_nodes, bytes); s->allocations.push_back((void *)V5.ref_nodes);
-                V5.ref_light_nodes = upload(P5.ref_light_nodes, bytes); s->allocations.push_back((void *)V5.ref_light_nodes);
-                if (!P5.lights.empty()) { V5.lights = upload(P5.lights, bytes); s->allocations.push_back((void *)V5.lights); }
-                V5.n_figs = (uint32_t)P5.figs.size(); V5.n_nonplanes = P5.n_nonplanes; V5.n_lights = (uint32_t)P5.lights.size();
-                for (int k = 0; k < 3; k++) {
-                    V5.cam_pos[k] = V.cam_pos[k]; V5.cam_right[k] = V.cam_right[k]; V5.cam_up[k] = V.cam_up[k]; V5.cam_fwd[k] = V.cam_fwd[k]; V5.bg[k] = V.bg[k];
-                }
-                V5.tan_fov_x = V.tan_fov_x;
-                s->light_order = P5.light_order;
-                s->info.n_lights = V5.n_lights; s->info.n_bvh_nodes = (uint32_t)P5.nodes.size(); s->info.n_light_bvh_nodes = (uint32_t)P5.light_nodes.size();
-                s->info.bvh_depth = P5.bvh_depth; s->info.light_bvh_depth = P5.light_bvh_depth;
-            }
-            s->flavor = RT_INTEGRATOR_HW3;
-            HIP_CHECK(hipMalloc((void **)&s->d_work_counter, 64));
-            s->allocations.push_back(s->d_work_counter);
-            HIP_CHECK(hipMalloc((void **)&s->d_counters, 512));
-            s->allocations.push_back(s->d_counters);
-            HIP_CHECK(hipEventCreate(&s->ev_start));
-            HIP_CHECK(hipEventCreate(&s->ev_stop));
-            HIP_CHECK(hipDeviceSynchronize());
-            s->info.device_bytes = bytes;
-            s->info.prep_ms = 0; s->info.upload_ms = now_ms() - t0;
-            *out = s.release();
-            return RT_OK;
-        }
-        // A scene without per-vertex normals can only be an hw6 scene (flat shading, hw6/src/sceneio.cpp:186-225).
-        if (desc->n_triangles && !desc->normals) {
-            // hw6's scene tree is the library's own (the reference's is degenerate, rt_kernels_hw6.h), so it can be built on the GPU
-            // without touching the replay: the tie rule reads the reference's figure index from the record.
-            const bool tree_on_device = desc->n_triangles >= 64 && !getenv("RTAMD_HOST_BVH");
-            PreparedScene6 P6;
-            prepare_scene_hw6(*desc, P6, tree_on_device);
-            double t1 = now_ms();
-            uint64_t bytes = 0;
-            SceneView6 &V = s->view6;
-            auto keep = [&](auto *p) { s->allocations.push_back((void *)p); return p; };
-            if (tree_on_device) {
-                uint64_t scratch = 0;
-                Tri6 *d_load = upload(P6.tris, bytes);
-                float *d_boxes = upload(P6.boxes8, scratch);
-                DeviceTree t;
-                Tri6 *d_tris = nullptr;
-                try {
-                    t = build_tree_on_device(d_boxes, desc->n_triangles, P6.box_pad, 28); // hw6 walkers: 36-entry stack columns
-                    HIP_CHECK(hipMalloc((void **)&d_tris, (size_t)desc->n_triangles * sizeof(Tri6)));
-                    gather_records(d_load, d_tris, t, desc->n_triangles, sizeof(Tri6), 13); // word 13 = Tri6::last
-                    HIP_CHECK(hipDeviceSynchronize());
-                } catch (...) {
-                    (void)hipFree(d_load); (void)hipFree(d_boxes); if (d_tris) (void)hipFree(d_tris);
-                    free_device_tree(t);
-                    throw;
-                }
-                (void)hipFree(d_load); (void)hipFree(d_boxes);
-                (void)hipFree(t.order); (void)hipFree(t.last); t.order = nullptr; t.last = nullptr;
-                V.nodes = keep(t.nodes);
-                V.tris = keep(d_tris);
-                bytes += (uint64_t)t.n_nodes * sizeof(GpuNode);
-                P6.bvh_depth = t.depth;
-                P6.nodes.resize(t.n_nodes); // node count for rt_scene_info
-                s->info.bvh_build_ms = t.build_ms; s->info.bvh_on_device = 1;
-            } else {
-                V.nodes = keep(upload(P6.nodes, bytes));
-                V.tris = keep(upload(P6.tris, bytes));
-            }
-            if (P6.bvh_depth > RT6_STACK_SIZE - 2 || P6.light_bvh_depth > RT6_STACK_SIZE - 2 || P6.fast_light_bvh_depth > RT6_STACK_SIZE - 2)
-                return fail(RT_ERR_LIMIT, "scene BVH deeper than the kernel's traversal stack (" + std::to_string(P6.bvh_depth) + "/" +
-                                              std::to_string(P6.light_bvh_depth) + ")");
-            s->hw6_lds_stack = P6.bvh_depth <= RT6_LDS_STACK && P6.fast_light_bvh_depth <= RT6_LDS_STACK; // both own trees fit the LDS stack columns
-            s->hw6_pt_stack = P6.bvh_depth <= P6_STACK && P6.fast_light_bvh_depth <= P6_STACK;           // ... of the persistent pipeline
-            V.light_nodes = keep(upload(P6.light_nodes, bytes));
-            V.lights = keep(upload(P6.lights, bytes));
-            V.fast_light_nodes = keep(upload(P6.fast_light_nodes, bytes));
-            V.fast_lights = keep(upload(P6.fast_lights, bytes));
-            V.light_ref = keep(upload(P6.light_ref, bytes));
-            V.ref_nodes = keep(upload(P6.ref_nodes, bytes));
-            V.ref_light_nodes = keep(upload(P6.ref_light_nodes, bytes));
-            V.ref_tris = keep(upload(P6.ref_tris, bytes));
-            V.tri_box = keep(upload(P6.tri_box, bytes));
-            V.box_c2 = P6.box_c2; V.box_c2x = 1.25f * P6.box_c2;
-            V.cull_k = getenv("RTAMD_CULL_K") ? (float)atof(getenv("RTAMD_CULL_K")) : 0.0078125f;
-            V.exact_boxes = getenv("RTAMD_NO_EXACT_BOXES") ? 0u : 1u;
-            V.light_sep = keep(upload(P6.light_sep, bytes));
-            V.materials = keep(upload(P6.materials, bytes));
-            V.n_tris = desc->n_triangles;
-            V.n_lights = (uint32_t)P6.lights.size();
-            V.n_components = P6.lights.empty() ? 1u : 2u; // hw6/src/scene.cpp:8-16
-            V.n_lights_f = (float)V.n_lights; V.n_components_f = (float)V.n_components;
-            for (int k = 0; k < 3; k++) {
-                V.cam_pos[k] = desc->camera.position[k]; V.cam_right[k] = desc->camera.right[k];
-                V.cam_up[k] = desc->camera.up[k]; V.cam_fwd[k] = desc->camera.forward[k];
-                V.bg[k] = desc->bg_color[k];
-            }
-            V.tan_fov_y = (float)std::tan((double)(desc->camera.fov_y / 2));
-            s->view.tan_fov_y = V.tan_fov_y;
-            s->flavor = RT_INTEGRATOR_HW6;
-            {   // the walk nodes of the persistent pipeline (rt_types.h GpuNode4Q), as for hw8
-                float glo[3], ghi[3];
-                for (int k = 0; k < 3; k++) glo[k] = ghi[k] = V.cam_pos[k];
-                join_root_box(V.nodes, glo, ghi);
-                join_root_box(V.fast_light_nodes, glo, ghi);
-                V.grid = make_node_grid(glo, ghi);
-                uint32_t n4 = 0, n4l = 0, d4 = 0, d4l = 0;
-                V.nodes4 = keep(widen_nodes(V.nodes, (uint32_t)P6.nodes.size(), V.grid, n4, d4));
-                V.fast_light_nodes4 = keep(widen_nodes(V.fast_light_nodes, (uint32_t)P6.fast_light_nodes.size(), V.grid, n4l, d4l));
-                bytes += ((uint64_t)n4 + n4l) * sizeof(GpuNode4Q);
-                s->wide_depth = d4; s->wide_light_depth = d4l;
-            }
-            HIP_CHECK(hipMalloc((void **)&s->d_work_counter, 64));
-            s->allocations.push_back(s->d_work_counter);
-            HIP_CHECK(hipMalloc((void **)&s->d_counters, 512));
-            s->allocations.push_back(s->d_counters);
-            HIP_CHECK(hipEventCreate(&s->ev_start));
-            HIP_CHECK(hipEventCreate(&s->ev_stop));
-            HIP_CHECK(hipDeviceSynchronize());
-            double t2 = now_ms();
-            s->light_order = P6.light_order;
-            s->info.n_triangles = desc->n_triangles; s->info.n_lights = V.n_lights;
-            s->info.n_bvh_nodes = (uint32_t)P6.nodes.size(); s->info.n_light_bvh_nodes = (uint32_t)P6.light_nodes.size();
-            s->info.bvh_depth = P6.bvh_depth; s->info.light_bvh_depth = P6.light_bvh_depth;
-            s->info.device_bytes = bytes; s->info.prep_ms = t1 - t0; s->info.upload_ms = t2 - t1;
-            *out = s.release();
-            return RT_OK;
-        }
-        if (desc->build_flags & ~RT_BUILD_DEVICE_BVH) return fail(RT_ERR_INVALID_ARG, "rt_scene_create: unknown build_flags");
-        // Two things a scene tree is needed for.  The replay needs the reference's FIGURE ORDER (tie rule, light numbering) and, for the
-        // rare hits at a box boundary, the reference's own tree (exact walks): the host replays the reference's builder for those
-        // (prepare_scene) unless RT_BUILD_DEVICE_BVH gives the order up.  The walkers need a good tree of bounded depth, and a closest
-        // hit does not depend on which: that one is built on the GPU (device/rt_bvh_build.h) over the records in figure order, each of
-        // which carries its figure index (RTAMD_HOST_BVH=1, or a handful of triangles: the walkers use the reference topology).
-        const bool fast_build = (desc->build_flags & RT_BUILD_DEVICE_BVH) && desc->n_triangles >= 64;
-        const bool walk_tree_on_device = desc->n_triangles >= 64 && (fast_build || !getenv("RTAMD_HOST_BVH"));
-        PreparedScene P_local;
-        if (shared) std::call_once(shared->once, [&] { try { prepare_scene(*desc, shared->P, fast_build); } catch (...) { shared->error = std::current_exception(); } });
-        else prepare_scene(*desc, P_local, fast_build);
-        if (shared && shared->error) std::rethrow_exception(shared->error);
-        const PreparedScene &P = shared ? shared->P : P_local; // read-only from here on (several devices may be uploading from it)
-        uint32_t bvh_depth = P.bvh_depth, n_nodes = (uint32_t)P.nodes.size();
-        double t1 = now_ms();
-        uint64_t bytes = 0;
-        SceneView &V = s->view;
-        auto keep = [&](auto *p) { s->allocations.push_back((void *)p); return p; };
-        V.tri_isect = keep(upload(P.isect, bytes));
-        V.tri_shade = keep(upload(P.shade, bytes));
-        V.tri_box = keep(upload(P.tri_box, bytes));
-        uint32_t ref_depth = P.bvh_depth;
-        if (walk_tree_on_device) {
-            const uint32_t n = desc->n_triangles;
-            // The persistent kernel's walkers take two levels per step (GpuNode4Q) and hold up to three entries per step in a stack column
-            // of P8_STACK entries; a walk that runs out of room is redone by the exact role with a stack of its own (rt_persistent.h).
-            const uint32_t walk_depth_cap = P8_STACK;
-            DeviceTree t;
-            TriIsect *d_walk = nullptr;
-            try {
-                if (!P.walk_box.empty()) { // reference leaf boxes (scene_prep.h)
-                    uint64_t scratch = 0;
-                    float *d_walk_box = upload(P.walk_box, scratch);
-                    try { t = build_tree_on_device(d_walk_box, n, P.box_pad, walk_depth_cap); } catch (...) { (void)hipFree(d_walk_box); throw; }
-                    (void)hipFree(d_walk_box);
-                } else t = build_tree_on_device(V.tri_box, n, P.box_pad, walk_depth_cap);
-                HIP_CHECK(hipMalloc((void **)&d_walk, (size_t)n * sizeof(TriIsect)));
-                gather_records(V.tri_isect, d_walk, t, n, sizeof(TriIsect), 11, true); // word 11 = TriIsect::pad: figure index << 1 | leaf mark
-                HIP_CHECK(hipDeviceSynchronize());
-            } catch (...) {
-                if (d_walk) (void)hipFree(d_walk);
-                free_device_tree(t);
-                throw;
-            }
-            (void)hipFree(t.order); (void)hipFree(t.last); t.order = nullptr; t.last = nullptr;
-            V.nodes = keep(t.nodes); V.tri_walk = keep(d_walk);
-            bytes += (uint64_t)t.n_nodes * sizeof(GpuNode) + (uint64_t)n * sizeof(TriIsect);
-            bvh_depth = t.depth;
-            n_nodes = t.n_nodes;
-            s->info.bvh_build_ms = t.build_ms; s->info.bvh_on_device = 1;
-            s->device_tree = fast_build;
-        } else {
-            V.nodes = keep(upload(P.nodes, bytes));
-            V.tri_walk = V.tri_isect;
-        }
-        if (ref_depth > RT_STACK_SIZE - 2) // the exact walks keep a private stack over the reference's own tree
-            return fail(RT_ERR_LIMIT, "the reference's scene BVH is deeper than the exact walk's stack (" + std::to_string(ref_depth) + ")");
-        if (bvh_depth > RT_STACK_SIZE - 2 || P.light_bvh_depth > RT_STACK_SIZE - 2)
-            return fail(RT_ERR_LIMIT, "scene BVH deeper than the kernel's traversal stack (" + std::to_string(bvh_depth) + "/" +
-                                          std::to_string(P.light_bvh_depth) + ")");
-        V.light_nodes = keep(upload(P.light_nodes, bytes));
-        V.light_sep = keep(upload(P.light_sep, bytes));
-        V.ref_nodes = keep(upload(P.ref_nodes, bytes));
-        V.ref_light_nodes = keep(upload(P.ref_light_nodes, bytes));
-        V.box_c2 = P.box_c2; V.box_c2x = 1.25f * P.box_c2;
-        if (const char *e = getenv("RTAMD_C2X_SCALE")) V.box_c2x *= (float)atof(e); // experiment: the walkers' absolute look-behind (the gate's `seen` follows)
-        // how far behind the best hit the walkers still look, relative to t (rt_exact.h)
-        V.cull_k = getenv("RTAMD_CULL_K") ? (float)atof(getenv("RTAMD_CULL_K")) : 0.0078125f;
-        V.exact_boxes = (getenv("RTAMD_NO_EXACT_BOXES") || fast_build) ? 0u : 1u; // RT_BUILD_DEVICE_BVH: there is no reference tree to be exact about
-        if (getenv("RTAMD_DIAG_LOOKBEHIND_ONLY")) V.exact_boxes = 2u; // diagnostic (timing only, pixels NOT exact): the walkers look behind as with the gate, every hit stands
-        V.n_tripwire_groups = (V.exact_boxes != 1u || getenv("RTAMD_NO_TRIPWIRES")) ? 0u : P.n_tripwire_groups; // part of the exactness machinery
-        V.tripwires = V.n_tripwire_groups ? keep(upload(P.tripwires, bytes)) : nullptr;
-        V.lights = keep(upload(P.lights, bytes));
-        uint32_t n_light_walk_nodes = 0;
-        {   // the light walker's own tree (rt_types.h: light_walk_nodes / lights_walk)
-            const uint32_t nl = (uint32_t)P.lights.size();
-            std::vector<LightRec> tagged = P.lights; // pad = light index << 1 | last-of-leaf (of the REFERENCE topology for now)
-            for (uint32_t i = 0; i < nl; i++) tagged[i].isect.pad = (i << 1) | (tagged[i].isect.pad ? 1u : 0u);
-            bool own_tree = nl >= 64 && !getenv("RTAMD_HOST_LIGHT_BVH");
-            if (own_tree) {
-                LightRec *d_tagged = upload(tagged, bytes);
-                uint64_t scratch = 0;
-                float *d_lbox = upload(P.light_walk_box, scratch);
-                DeviceTree lt;
-                LightRec *d_walk = nullptr;
-                try {
-                    lt = build_tree_on_device(d_lbox, nl, P.box_pad, 16); // the hits of a walk share its 24-entry column with the node stack
-                    HIP_CHECK(hipMalloc((void **)&d_walk, (size_t)nl * sizeof(LightRec)));
-                    gather_records(d_tagged, d_walk, lt, nl, sizeof(LightRec), 11, true); // word 11 = TriIsect::pad
-                    HIP_CHECK(hipDeviceSynchronize());
-                } catch (...) {
-                    (void)hipFree(d_lbox); (void)hipFree(d_tagged); if (d_walk) (void)hipFree(d_walk);
-                    free_device_tree(lt);
-                    throw;
-                }
-                (void)hipFree(d_lbox); (void)hipFree(d_tagged);
-                (void)hipFree(lt.order); (void)hipFree(lt.last); lt.order = nullptr; lt.last = nullptr;
-                V.light_walk_nodes = keep(lt.nodes); V.lights_walk = keep(d_walk);
-                bytes += (uint64_t)lt.n_nodes * sizeof(GpuNode);
-                s->light_walk_depth = lt.depth;
-                n_light_walk_nodes = lt.n_nodes;
-            } else {
-                V.light_walk_nodes = V.light_nodes;
-                n_light_walk_nodes = (uint32_t)P.light_nodes.size();
-                V.lights_walk = keep(upload(tagged, bytes));
-                s->light_walk_depth = P.light_bvh_depth;
-            }
-        }
-        V.materials = keep(upload(P.materials, bytes));
-        V.images = keep(upload(P.images, bytes));
-        V.texels = keep(upload(P.texels, bytes));
-        std::vector<float> lut(P.srgb_lut, P.srgb_lut + 256);
-        V.srgb_lut = keep(upload(lut, bytes));
-        V.n_tris = desc->n_triangles;
-        V.n_nodes = n_nodes;
-        V.n_lights = (uint32_t)P.lights.size();
-        V.n_components = P.lights.empty() ? 2u : 3u; // scene.cpp:65-74
-        V.n_lights_f = (float)V.n_lights; V.n_components_f = (float)V.n_components;
-        V.last_level_emission_only = 1;
-        for (uint32_t i = 0; i < desc->n_materials; i++) {
-            const rt_material &m = desc->materials[i];
-            if (!(m.metallic_factor >= 0 && m.metallic_factor <= 1 && m.base_color[0] >= 0 && m.base_color[1] >= 0 && m.base_color[2] >= 0))
-                V.last_level_emission_only = 0;
-        }
-        if (getenv("RTAMD_NO_LAST_LEVEL_SHORTCUT")) V.last_level_emission_only = 0;
-        V.env_image = P.env_image;
-        for (int k = 0; k < 3; k++) {
-            V.cam_pos[k] = desc->camera.position[k]; V.cam_right[k] = desc->camera.right[k];
-            V.cam_up[k] = desc->camera.up[k]; V.cam_fwd[k] = desc->camera.forward[k];
-            V.bg[k] = desc->bg_color[k];
-        }
-        s->fov_y = desc->camera.fov_y;
-        V.tan_fov_y = (float)std::tan((double)(desc->camera.fov_y / 2)); // scene.cpp:180 (host libm, like the reference)
-        {   // the walk nodes of the persistent pipeline: both trees four wide on one 16-bit grid that also holds the camera (rt_types.h GpuNode4Q)
-            float glo[3], ghi[3];
-            for (int k = 0; k < 3; k++) glo[k] = ghi[k] = V.cam_pos[k];
-            join_root_box(V.nodes, glo, ghi);
-            if (n_light_walk_nodes) join_root_box(V.light_walk_nodes, glo, ghi);
-            V.grid = make_node_grid(glo, ghi);
-            uint32_t n4 = 0, n4l = 0, d4 = 0, d4l = 0;
-            V.nodes4 = keep(widen_nodes(V.nodes, n_nodes, V.grid, n4, d4));
-            V.light_walk_nodes4 = keep(widen_nodes(V.light_walk_nodes, n_light_walk_nodes, V.grid, n4l, d4l));
-            bytes += ((uint64_t)n4 + n4l) * sizeof(GpuNode4Q);
-            s->wide_depth = d4; s->wide_light_depth = d4l;
-        }
-        HIP_CHECK(hipMalloc((void **)&s->d_work_counter, 64));
-        s->allocations.push_back(s->d_work_counter);
-        HIP_CHECK(hipMalloc((void **)&s->d_counters, 512));
-        s->allocations.push_back(s->d_counters);
-        HIP_CHECK(hipEventCreate(&s->ev_start));
-        HIP_CHECK(hipEventCreate(&s->ev_stop));
-        HIP_CHECK(hipDeviceSynchronize());
-        double t2 = now_ms();
-        s->light_order = P.light_order;
-        s->info.n_triangles = desc->n_triangles;
-        s->info.n_lights = V.n_lights;
-        s->info.n_bvh_nodes = n_nodes;
-        s->info.n_light_bvh_nodes = (uint32_t)P.light_nodes.size();
-        s->info.bvh_depth = bvh_depth;
-        s->info.light_bvh_depth = P.light_bvh_depth;
-        s->info.device_bytes = bytes;
-        s->info.prep_ms = t1 - t0;
-        s->info.upload_ms = t2 - t1;
-        *out = s.release();
-        return RT_OK;
-    } catch (const HipError &e) {
-        return fail(RT_ERR_HIP, e.what());
-    } catch (const std::exception &e) {
-        return fail(RT_ERR_INVALID_ARG, e.what());
-    }
-}
-
-extern "C" {
-
-void rt_scene_destroy(rt_scene *scene) { delete scene; }
-
-int rt_scene_get_info(const rt_scene *scene, rt_scene_info *info) {
-    if (!scene || !info) return fail(RT_ERR_INVALID_ARG, "rt_scene_get_info: null argument");
-    *info = scene->info;
-    return RT_OK;
-}
-
-int rt_scene_get_light_order(const rt_scene *scene, uint32_t *out, uint32_t capacity) {
-    if (!scene || (!out && capacity)) return fail(RT_ERR_INVALID_ARG, "rt_scene_get_light_order: null argument");
-    if (capacity < scene->light_order.size()) return fail(RT_ERR_INVALID_ARG, "rt_scene_get_light_order: buffer too small");
-    memcpy(out, scene->light_order.data(), scene->light_order.size() * sizeof(uint32_t));
-    return (int)scene->light_order.size();
-}
-
-int rt_host_prepare_orders(const rt_scene_desc *desc, int integrator, uint32_t *figure_order, uint32_t figure_capacity,
-                           uint32_t *light_order, uint32_t light_capacity) {
-    if (!desc || desc->struct_size != sizeof(rt_scene_desc)) return fail(RT_ERR_INVALID_ARG, "rt_host_prepare_orders: bad desc");
-    try {
-        std::vector<uint32_t> fo, lo;
-        if (integrator == RT_INTEGRATOR_HW8 || integrator == RT_INTEGRATOR_HW7) { PreparedScene P; prepare_scene(*desc, P); fo = P.figure_order; lo = P.light_order; }
-        else if (integrator == RT_INTEGRATOR_HW6) { PreparedScene6 P; prepare_scene_hw6(*desc, P); fo = P.figure_order; lo = P.light_order; }
-        else if (integrator == RT_INTEGRATOR_HW5) { PreparedScene5 P; prepare_scene_hw5(*desc, P); fo = P.figure_order; lo = P.light_order; }
-        else return fail(RT_ERR_UNSUPPORTED, "rt_host_prepare_orders: integrator must be HW5, HW6, HW7 or HW8");
-        if ((figure_order && figure_capacity < fo.size()) || (light_order && light_capacity < lo.size())) return fail(RT_ERR_INVALID_ARG, "rt_host_prepare_orders: buffer too small");
-        if (figure_order) memcpy(figure_order, fo.data(), fo.size() * sizeof(uint32_t));
-        if (light_order) memcpy(light_order, lo.data(), lo.size() * sizeof(uint32_t));
-        return (int)lo.size();
-    } catch (const std::exception &e) {
-        return fail(RT_ERR_INVALID_ARG, std::string("rt_host_prepare_orders: ") + e.what());
-    }
-}
-
-static bool resolve_tiles(const rt_render_params *p, RenderView &R, std::string &err) {
-    if (p->width <= 0 || p->height <= 0 || p->samples <= 0) { err = "width, height and samples must be positive"; return false; }
-    if ((int64_t)p->width * p->height >= 2147483647LL) { err = "image too large for the per-pixel seed (y*W+x must stay below 2^31-1)"; return false; }
-    R.width = p->width; R.height = p->height; R.samples = p->samples;
-    R.ray_depth = p->ray_depth > 0 ? p->ray_depth : 6;
-    if (R.ray_depth > RT_MAX_DEPTH) { err = "ray_depth above RT_MAX_DEPTH (16)"; return false; }
-    R.shard_count = p->shard_count > 1 ? p->shard_count : 1;
-    R.shard_index = p->shard_count > 1 ? p->shard_index : 0;
-    if (R.shard_index < 0 || R.shard_index >= R.shard_count) { err = "shard_index out of range"; return false; }
-    if (R.shard_count > 1) {
-        R.tile_w = p->tile_w > 0 ? p->tile_w : 32;
-        R.tile_h = p->tile_h > 0 ? p->tile_h : 32;
-        if ((R.tile_w & 7) || (R.tile_h & 7)) { err = "tile_w and tile_h must be multiples of 8"; return false; }
-    } else {
-        R.tile_w = R.tile_h = 8;
-    }
-    R.tiles_x = (R.width + R.tile_w - 1) / R.tile_w;
-    R.tiles_y = (R.height + R.tile_h - 1) / R.tile_h;
-    uint32_t total = (uint32_t)R.tiles_x * (uint32_t)R.tiles_y;
-    R.n_shard_tiles = total > (uint32_t)R.shard_index ? (total - (uint32_t)R.shard_index + (uint32_t)R.shard_count - 1) / (uint32_t)R.shard_count : 0;
-    return true;
-}
 
 size_t rt_output_elems(const rt_render_params *p) {
     if (!p) return 0;
@@ -567,6 +37,15 @@ size_t rt_output_elems(const rt_render_params *p) {
     if (!resolve_tiles(p, R, err)) return 0;
     if (R.shard_count > 1) return (size_t)R.n_shard_tiles * R.tile_w * R.tile_h * 3;
     return (size_t)R.width * R.height * 3;
+}
+
+// A buffer of the scene that a render needs `need` bytes of: kept when it is large enough, else freed and allocated anew.
+static void grow(void **p, size_t &have, size_t need) {
+    if (have >= need) return;
+    if (*p) (void)hipFree(*p);
+    *p = nullptr; have = 0;
+    HIP_CHECK(hipMalloc(p, need));
+    have = need;
 }
 
 // Rounds a pixel needs per camera sample: one per bounce; without the deepest-level shortcut the last bounce's pdf / clamp
@@ -584,10 +63,17 @@ static size_t wavefront_rounds(const SceneView &V, const RenderView &R) {
 // more to ramp-up and drain than the overlap returns -- so one pipeline stays the default.
 #define WF_MAX_PIPES 4
 static int wavefront_pipelines(uint32_t n_work) {
-    int p = 1;
-    if (const char *e = getenv("RTAMD_WF_PIPELINES")) { int v = atoi(e); if (v >= 1 && v <= WF_MAX_PIPES) p = v; }
+    const int v = env_int("RTAMD_WF_PIPELINES", 1);
+    int p = v >= 1 && v <= WF_MAX_PIPES ? v : 1;
     while (p > 1 && n_work < (uint32_t)p) p--;
     return p;
+}
+
+// RTAMD_WF_SPLIT=a:b replaces the cost weights closest-hit : light query (the round pipeline's block split, the hw8 persistent kernel's
+// choice of role); anything but two numbers in 1..255 leaves them alone.
+static void env_cost_split(int &cost_t, int &cost_l) {
+    int a = 0, b = 0;
+    if (const char *e = env_str("RTAMD_WF_SPLIT")) if (sscanf(e, "%d:%d", &a, &b) == 2 && a > 0 && b > 0 && a < 256 && b < 256) { cost_t = a; cost_l = b; }
 }
 
 static void launch_wavefront(rt_scene *scene, const SceneView &V, const RenderView &R, uint32_t n_work, hipStream_t stream, bool count, bool time_trace) {
@@ -609,8 +95,8 @@ static void launch_wavefront(rt_scene *scene, const SceneView &V, const RenderVi
     scene->wf_pipes = pipes; scene->wf_ctr_block = ctr_block;
     // Trees deeper than the LDS stacks use the SPILL kernel variant (bounds-checked stack with a global overflow area).
     // RTAMD_WF_LDS_STACK=n (testing): pretend the LDS stacks hold only n entries, which forces the SPILL variant and its overflow area.
-    int lds_limit = WF_STACK;
-    if (const char *e = getenv("RTAMD_WF_LDS_STACK")) { int v = atoi(e); if (v >= 1 && v < WF_STACK) lds_limit = v; }
+    int lds_limit = env_int("RTAMD_WF_LDS_STACK", WF_STACK);
+    if (lds_limit < 1 || lds_limit >= WF_STACK) lds_limit = WF_STACK;
     const bool spill = scene->info.bvh_depth > (uint32_t)lds_limit || scene->info.light_bvh_depth > (uint32_t)lds_limit;
     const size_t ovf_block = (size_t)scene->n_cus * 8u * 256u * WF_OVF; // words per pipeline: up to 8 persistent blocks per CU
     if (spill && scene->wf_ovf_words < ovf_block * pipes) {
@@ -621,23 +107,21 @@ static void launch_wavefront(rt_scene *scene, const SceneView &V, const RenderVi
         scene->wf_ovf_words = ovf_block * pipes;
     }
     HIP_CHECK(hipMemsetAsync(scene->wf.ctr, 0, ctr_block * pipes * 4, stream));
-    uint32_t blocks_per_cu = 5u;                                      // 5 x 30 KB of stacks fit the 160 KB LDS (which is handed out in 1280-byte granules: 32 KB blocks fit only 4 times)
-    if (const char *e = getenv("RTAMD_WF_BLOCKS_PER_CU")) blocks_per_cu = (uint32_t)atoi(e) > 0 ? (uint32_t)atoi(e) : blocks_per_cu;
-    if (blocks_per_cu > 8u) blocks_per_cu = 8u;
+    uint32_t blocks_per_cu = (uint32_t)env_int("RTAMD_WF_BLOCKS_PER_CU", 5);  // 5 x 30 KB of stacks fit the 160 KB LDS (which is handed out in 1280-byte granules: 32 KB blocks fit only 4 times)
+    if (blocks_per_cu == 0u) blocks_per_cu = 5u;
+    if (blocks_per_cu > 8u) blocks_per_cu = 8u;                               // a negative value ends here too
     const uint32_t persistent_blocks = (uint32_t)scene->n_cus * blocks_per_cu;
-    int dyn256 = 64;                                                   // share of each queue (of 256) handed out dynamically at the tail
-    if (const char *e = getenv("RTAMD_WF_DYNAMIC_256")) dyn256 = atoi(e) < 0 ? 0 : (atoi(e) > 255 ? 255 : atoi(e));
-    if (const char *e = getenv("RTAMD_WF_STEAL_CHUNK")) dyn256 |= ((atoi(e) > 0 ? atoi(e) : 64) & 255) << 8; // tuning: items per dynamic chunk (default 64)
+    int dyn256 = std::min(255, std::max(0, env_int("RTAMD_WF_DYNAMIC_256", 64))); // share of each queue (of 256) handed out dynamically at the tail
+    if (env_flag("RTAMD_WF_STEAL_CHUNK")) dyn256 |= (env_positive("RTAMD_WF_STEAL_CHUNK", 64) & 255) << 8; // tuning: items per dynamic chunk (default 64)
     int split_a = 7, split_b = 8; // cost weights closest-hit : light query for the block split (two sweeps: 7:8 is ~1 % ahead of 1:1 and 8:7)
-    if (const char *e = getenv("RTAMD_WF_SPLIT")) { int a = 0, b = 0; if (sscanf(e, "%d:%d", &a, &b) == 2 && a > 0 && b > 0 && a < 256 && b < 256) { split_a = a; split_b = b; } }
+    env_cost_split(split_a, split_b);
     dyn256 |= (split_a << 16) | (split_b << 24);
-    auto env_int = [](const char *n, int dflt) { const char *e = getenv(n); return e && atoi(e) > 0 ? atoi(e) : dflt; };
     // leaf batch: lanes waiting at a leaf start their triangle tests when 20 of them wait -- or, in a thinly populated wave, a share
     // of the active lanes (RTAMD_WF_LEAF_SHARE_256, default 112/256; sweep: tools/tuning/sweep_leaf_share.sh); packed as batch | share << 16
-    const int leaf_share = env_int("RTAMD_WF_LEAF_SHARE_256", 112) & 0x7fff;
-    const int t_refill = env_int("RTAMD_TRACE_REFILL", WF_REFILL), t_batch = (env_int("RTAMD_TRACE_LEAF_BATCH", WF_LEAF_BATCH) & 255) | (leaf_share << 16);
-    const int l_refill = env_int("RTAMD_LIGHT_REFILL", WF_REFILL), l_batch = (env_int("RTAMD_LIGHT_LEAF_BATCH", WF_LEAF_BATCH) & 255) | (leaf_share << 16);
-    const uint32_t shade_per_cu = (uint32_t)env_int("RTAMD_WF_SHADE_BLOCKS_PER_CU", 16); // grid cap of wf_shade_kernel (grid-stride beyond it)
+    const int leaf_share = env_positive("RTAMD_WF_LEAF_SHARE_256", 112) & 0x7fff;
+    const int t_refill = env_positive("RTAMD_TRACE_REFILL", WF_REFILL), t_batch = (env_positive("RTAMD_TRACE_LEAF_BATCH", WF_LEAF_BATCH) & 255) | (leaf_share << 16);
+    const int l_refill = env_positive("RTAMD_LIGHT_REFILL", WF_REFILL), l_batch = (env_positive("RTAMD_LIGHT_LEAF_BATCH", WF_LEAF_BATCH) & 255) | (leaf_share << 16);
+    const uint32_t shade_per_cu = (uint32_t)env_positive("RTAMD_WF_SHADE_BLOCKS_PER_CU", 16); // grid cap of wf_shade_kernel (grid-stride beyond it)
     unsigned long long *ctrs = count ? scene->d_counters : nullptr;
     if (time_trace) while (scene->ev_pool.size() < 2 * rounds * pipes) { hipEvent_t e; HIP_CHECK(hipEventCreate(&e)); scene->ev_pool.push_back(e); }
 
@@ -711,9 +195,10 @@ static void launch_wavefront(rt_scene *scene, const SceneView &V, const RenderVi
 // slowest pixels.
 static std::vector<int> phase_stops(bool rebalance, int phase0, int samples, bool small_population) {
     std::vector<int> stops;
-    if (rebalance && getenv("RTAMD_PT_STOPS")) { // experiment: explicit sample counts at which the frame is re-dealt, e.g. "2,16"
+    const char *explicit_stops = env_str("RTAMD_PT_STOPS"); // experiment: explicit sample counts at which the frame is re-dealt, e.g. "2,16"
+    if (rebalance && explicit_stops) {
         int last = 0;
-        for (const char *c = getenv("RTAMD_PT_STOPS"); *c;) {
+        for (const char *c = explicit_stops; *c;) {
             const int v = atoi(c);
             if (v > last && v < samples) { stops.push_back(v); last = v; }
             while (*c && *c != ',') c++;
@@ -725,9 +210,9 @@ static std::vector<int> phase_stops(bool rebalance, int phase0, int samples, boo
     if (rebalance) {
         // small populations (the deal is in quarter sub-tiles): a first re-deal after two samples already — the round-robin deal of the
         // first phase is the costly one there (slowest workgroup / mean 1.8 on hw6's 1024x1024 frame) — then the usual one
-        if (small_population && phase0 > 2 && !getenv("RTAMD_PT_PHASE0")) stops.push_back(2);
+        if (small_population && phase0 > 2 && !env_flag("RTAMD_PT_PHASE0")) stops.push_back(2);
         stops.push_back(phase0);
-        const int want = getenv("RTAMD_PT_PHASES") ? atoi(getenv("RTAMD_PT_PHASES")) : 2;
+        const int want = env_int("RTAMD_PT_PHASES", 2);
         const int mid = phase0 + (samples - phase0) * 3 / 4;
         if (want >= 3 && samples >= 64 && mid > phase0 && mid < samples) stops.push_back(mid);
     }
@@ -751,7 +236,7 @@ static void redeal_groups(rt_scene *scene, const uint32_t *d_cost, uint32_t *d_o
     const double t0 = now_ms();
     HIP_CHECK(hipMemcpy(cost.data(), d_cost, (size_t)groups * 4, hipMemcpyDeviceToHost));
     std::vector<double> slowness(blocks, 1.0); // time per unit of cost, relative to the mean
-    if (d_times && owner && !getenv("RTAMD_PT_NO_SPEEDS")) {
+    if (d_times && owner && !env_flag("RTAMD_PT_NO_SPEEDS")) {
         std::vector<unsigned long long> times((size_t)blocks * 3);
         HIP_CHECK(hipMemcpy(times.data(), d_times, times.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
         std::vector<double> had(blocks, 0.0);
@@ -769,8 +254,8 @@ static void redeal_groups(rt_scene *scene, const uint32_t *d_cost, uint32_t *d_o
         // difference than an even finish will: 2.0 measured best for the hw8 kernel on the 1080p frame — its youngest workgroups
         // still left last at 1.5 (exit times by dispatch round 1,028 / 1,024 / 1,035 / 1,071 / 1,118 ms) — and 1.5 for the hw6 kernel) and the
         // workgroup's own deviation from it (most of which is gone in the next phase: damped).
-        if (getenv("RTAMD_PT_SPEED_GAMMA")) gamma_round = atof(getenv("RTAMD_PT_SPEED_GAMMA"));
-        if (getenv("RTAMD_PT_SPEED_GAMMA_OWN")) gamma_own = atof(getenv("RTAMD_PT_SPEED_GAMMA_OWN"));
+        gamma_round = env_float("RTAMD_PT_SPEED_GAMMA", gamma_round);
+        gamma_own = env_float("RTAMD_PT_SPEED_GAMMA_OWN", gamma_own);
         const uint32_t round_size = scene->n_cus > 0 && blocks % (uint32_t)scene->n_cus == 0 ? (uint32_t)scene->n_cus : blocks;
         for (uint32_t r0 = 0; r0 < blocks; r0 += round_size) {
             double lsum = 0; uint32_t ln = 0;
@@ -802,7 +287,7 @@ static void redeal_groups(rt_scene *scene, const uint32_t *d_cost, uint32_t *d_o
     }
     ofs.assign(blocks + 1, 0);
     if (owner) owner->assign(groups, 0);
-    const bool by_cost = !getenv("RTAMD_PT_NO_FRONT_FIRST"); // most expensive group first: the kernel's queues serve the front of the list first (PtParams::front_first)
+    const bool by_cost = !env_flag("RTAMD_PT_NO_FRONT_FIRST"); // most expensive group first: the kernel's queues serve the front of the list first (PtParams::front_first)
     for (uint32_t b = 0; b < blocks; b++) {
         if (by_cost) std::sort(mine[b].begin(), mine[b].end(), [&](uint32_t x, uint32_t y) { return cost[x] != cost[y] ? cost[x] > cost[y] : x < y; });
         else std::sort(mine[b].begin(), mine[b].end());
@@ -811,7 +296,7 @@ static void redeal_groups(rt_scene *scene, const uint32_t *d_cost, uint32_t *d_o
         if (owner) for (uint32_t g : mine[b]) (*owner)[g] = b;
     }
     ofs[blocks] = (uint32_t)ids.size();
-    if (const char *dump = getenv("RTAMD_DUMP_DEAL")) { // diagnostic: what the re-deal gave every workgroup (tools/tuning/wg_balance.py)
+    if (const char *dump = env_str("RTAMD_DUMP_DEAL")) { // diagnostic: what the re-deal gave every workgroup (tools/tuning/wg_balance.py)
         if (FILE *f = fopen(dump, "w")) {
             for (uint32_t b = 0; b < blocks; b++) {
                 uint64_t load = 0;
@@ -885,9 +370,8 @@ static PersistentKernel hw6_persistent(const SceneView6 &V, hipStream_t stream, 
 }
 
 static void launch_persistent(rt_scene *scene, const PersistentKernel &k, const RenderView &R, uint32_t n_work, hipStream_t stream, bool count, bool time_trace) {
-    auto env_int = [](const char *n, int dflt) { const char *e = getenv(n); return e && atoi(e) > 0 ? atoi(e) : dflt; };
     const int n_samples = R.samples - R.sample_first; // of this launch sequence: a frame, or one slice of a resumable render (sample_first > 0)
-    const uint32_t n_blocks_max = (uint32_t)env_int("RTAMD_PT_BLOCKS", scene->n_cus * k.per_cu); // five 4-wave workgroups per CU (their LDS fills the CU)
+    const uint32_t n_blocks_max = (uint32_t)env_positive("RTAMD_PT_BLOCKS", scene->n_cus * k.per_cu); // five 4-wave workgroups per CU (their LDS fills the CU)
     const uint64_t pass_cap = (uint64_t)n_blocks_max * (k.max_paths / 64);
     const uint32_t passes = (uint32_t)((n_work + pass_cap - 1) / pass_cap);
     const uint32_t pass_groups = (n_work + passes - 1) / passes;         // 8x8 sub-tiles (64 path slots) per pass
@@ -895,41 +379,29 @@ static void launch_persistent(rt_scene *scene, const PersistentKernel &k, const 
     // quarter of one (two pixel rows): a single heavy sub-tile must not outweigh a workgroup's fair share, and a workgroup whose load
     // is a few heavy pixels is bound by their serial samples.
     uint32_t group_shift = (uint64_t)pass_groups < 16ull * n_blocks_max ? 4u : 6u;
-    if (const char *e = getenv("RTAMD_PT_GROUP_SHIFT")) { const int v = atoi(e); if (v == 4 || v == 5 || v == 6) group_shift = (uint32_t)v; }
+    if (const int v = env_int("RTAMD_PT_GROUP_SHIFT", 0); v == 4 || v == 5 || v == 6) group_shift = (uint32_t)v;
     const uint32_t sub = 6u - group_shift, groups_per_block = k.max_paths >> group_shift;
-    const size_t record_bytes = (size_t)pass_groups * 64 * k.record_bytes;
-    if (scene->pt_record_bytes < record_bytes) {
-        if (scene->pt_records) (void)hipFree(scene->pt_records);
-        scene->pt_records = nullptr; scene->pt_record_bytes = 0;
-        HIP_CHECK(hipMalloc(&scene->pt_records, record_bytes));
-        scene->pt_record_bytes = record_bytes;
-    }
-    const size_t group_words = 2 * ((size_t)pass_groups << sub) + n_blocks_max + 1;
-    if (scene->pt_group_words < group_words) {
-        if (scene->pt_groups) (void)hipFree(scene->pt_groups);
-        scene->pt_groups = nullptr; scene->pt_group_words = 0;
-        HIP_CHECK(hipMalloc((void **)&scene->pt_groups, group_words * 4));
-        scene->pt_group_words = group_words;
-    }
+    grow(&scene->pt_records, scene->pt_record_bytes, (size_t)pass_groups * 64 * k.record_bytes);
+    grow((void **)&scene->pt_groups, scene->pt_group_bytes, (2 * ((size_t)pass_groups << sub) + n_blocks_max + 1) * 4);
     uint32_t *d_cost = scene->pt_groups, *d_ofs = d_cost + ((size_t)pass_groups << sub), *d_ids = d_ofs + n_blocks_max + 1;
     dev::PtParams P{};
-    const int leaf_share = env_int("RTAMD_WF_LEAF_SHARE_256", 112) & 0x7fff;
-    P.refill = env_int("RTAMD_TRACE_REFILL", WF_REFILL) | (env_int("RTAMD_LIGHT_REFILL", env_int("RTAMD_TRACE_REFILL", WF_REFILL)) << 16);
-    P.leaf_batch = (env_int("RTAMD_TRACE_LEAF_BATCH", 28) & 255) | (leaf_share << 16); // lanes that hold two leaves (or have nothing else left) before a leaf phase starts
+    const int leaf_share = env_positive("RTAMD_WF_LEAF_SHARE_256", 112) & 0x7fff;
+    P.refill = env_positive("RTAMD_TRACE_REFILL", WF_REFILL) | (env_positive("RTAMD_LIGHT_REFILL", env_positive("RTAMD_TRACE_REFILL", WF_REFILL)) << 16);
+    P.leaf_batch = (env_positive("RTAMD_TRACE_LEAF_BATCH", 28) & 255) | (leaf_share << 16); // lanes that hold two leaves (or have nothing else left) before a leaf phase starts
     P.shade_min = 0; // set per pass below
-    P.shade_thr0 = env_int("RTAMD_PT_SHADE_THR0", 128);
-    P.shade_thr_step = env_int("RTAMD_PT_SHADE_STEP", 512);
+    P.shade_thr0 = env_positive("RTAMD_PT_SHADE_THR0", 128);
+    P.shade_thr_step = env_positive("RTAMD_PT_SHADE_STEP", 512);
     P.cost_t = k.cost_t; P.cost_l = k.cost_l;
     if (k.hw8_knobs) {
-        if (const char *e = getenv("RTAMD_WF_SPLIT")) { int a = 0, b = 0; if (sscanf(e, "%d:%d", &a, &b) == 2 && a > 0 && b > 0 && a < 256 && b < 256) { P.cost_t = a; P.cost_l = b; } }
-        P.prio = getenv("RTAMD_PT_PRIO") ? atoi(getenv("RTAMD_PT_PRIO")) : 0;
+        env_cost_split(P.cost_t, P.cost_l);
+        P.prio = env_int("RTAMD_PT_PRIO", 0);
     }
     P.counters = scene->d_counters;
     // A wave still in the launch after this long gives up (the kernel cannot hang the GPU): RTAMD_PT_TIMEOUT_S, by default ten minutes or
     // — for long renders: 4K at thousands of samples — the time the launch would take at a twentieth of the usual rate, whichever is more.
     {
         const double expected_s = (double)n_work * 64.0 * (double)n_samples / 15e6;
-        const double deadline_s = getenv("RTAMD_PT_TIMEOUT_S") ? (double)env_int("RTAMD_PT_TIMEOUT_S", 600) : (expected_s > 600.0 ? expected_s : 600.0);
+        const double deadline_s = env_flag("RTAMD_PT_TIMEOUT_S") ? (double)env_positive("RTAMD_PT_TIMEOUT_S", 600) : (expected_s > 600.0 ? expected_s : 600.0);
         P.deadline_ticks = (unsigned long long)(deadline_s * 1e8);
     }
     // every workgroup leaves its start and exit time (the re-deal measures the workgroups' speeds with them)
@@ -937,17 +409,17 @@ static void launch_persistent(rt_scene *scene, const PersistentKernel &k, const 
     if (n_blocks_max <= PT_DEBUG_BLOCKS) P.debug = scene->d_pt_debug;
     float4 *d_trace = nullptr;
     const uint32_t trace_cap = 1u << 16;
-    if (k.hw8_knobs && count && getenv("RTAMD_TRACE_PIXEL") && getenv("RTAMD_TRACE_OUT")) { // diagnostic: tests/diagnostics/trace_pixel.py
+    if (k.hw8_knobs && count && env_str("RTAMD_TRACE_PIXEL") && env_str("RTAMD_TRACE_OUT")) { // diagnostic: tests/diagnostics/trace_pixel.py
         int tx = 0, ty = 0;
-        if (sscanf(getenv("RTAMD_TRACE_PIXEL"), "%d,%d", &tx, &ty) == 2) {
+        if (sscanf(env_str("RTAMD_TRACE_PIXEL"), "%d,%d", &tx, &ty) == 2) {
             HIP_CHECK(hipMalloc((void **)&d_trace, (size_t)trace_cap * sizeof(float4)));
             HIP_CHECK(hipMemsetAsync(d_trace, 0, sizeof(float4), stream));
             P.trace_buf = d_trace; P.trace_cap = trace_cap; P.trace_pixel = ty * R.width + tx;
         }
     }
     // two phases when there is something to re-deal: enough samples, and several sub-tiles per workgroup
-    const int phase0 = getenv("RTAMD_PT_PHASE0") ? atoi(getenv("RTAMD_PT_PHASE0")) : n_samples / 16;
-    const bool two_phase = !getenv("RTAMD_PT_NO_REBALANCE") && phase0 >= 1 && phase0 < n_samples && ((uint64_t)pass_groups << sub) >= 4ull * n_blocks_max;
+    const int phase0 = env_int("RTAMD_PT_PHASE0", n_samples / 16);
+    const bool two_phase = !env_flag("RTAMD_PT_NO_REBALANCE") && phase0 >= 1 && phase0 < n_samples && ((uint64_t)pass_groups << sub) >= 4ull * n_blocks_max;
     std::vector<int> stops = phase_stops(two_phase, phase0, n_samples, group_shift < 6u);
     for (int &stop : stops) stop += R.sample_first; // the records count a pixel's samples from the start of its frame
     const uint32_t phases = (uint32_t)stops.size();
@@ -963,7 +435,7 @@ static void launch_persistent(rt_scene *scene, const PersistentKernel &k, const 
         if (blocks > scene->pt_blocks) scene->pt_blocks = blocks;
         // a wave turns shader when this many paths wait: a pool of a few hundred paths cannot let its paths wait for a full wave of them
         // (measured: 1,620 paths per workgroup 32 > 64 > 16; 820 and 200 paths per workgroup 16 > 32 > 64)
-        P.shade_min = env_int("RTAMD_PT_SHADE_MIN", ((uint64_t)groups * 64u) / blocks >= 1536u ? 32 : 16);
+        P.shade_min = env_positive("RTAMD_PT_SHADE_MIN", ((uint64_t)groups * 64u) / blocks >= 1536u ? 32 : 16);
         for (uint32_t ph = 0; ph < phases; ph++) {
             RenderView Rp = R;
             Rp.sample_stop = stops[ph];
@@ -971,7 +443,7 @@ static void launch_persistent(rt_scene *scene, const PersistentKernel &k, const 
             P.group_cost = ph + 1 < phases ? d_cost : nullptr;   // every phase but the last measures for the next re-deal
             P.group_ofs = ph ? d_ofs : nullptr;
             P.group_ids = ph ? d_ids : nullptr;
-            P.front_first = ph && !getenv("RTAMD_PT_NO_FRONT_FIRST") ? 1u : 0u;
+            P.front_first = ph && !env_flag("RTAMD_PT_NO_FRONT_FIRST") ? 1u : 0u;
             if (ph == 0) owner.clear(); // the kernel's round-robin deal
             if (ph >= 1) redeal_groups(scene, d_cost, d_ofs, d_ids, n_units, blocks, groups_per_block, k.gamma_round, k.gamma_own, stream, P.debug, &owner);
             if (P.debug) HIP_CHECK(hipMemsetAsync(scene->d_pt_debug, 0, (size_t)PT_DEBUG_BLOCKS * 3 * sizeof(unsigned long long), stream));
@@ -983,14 +455,13 @@ static void launch_persistent(rt_scene *scene, const PersistentKernel &k, const 
         first += groups;
     }
     HIP_CHECK(hipGetLastError());
-    scene->pt_passes = passes;
     scene->pt_launches = launch;
     if (d_trace) { // diagnostic dump: raw float32, 4 words header (count first), then 16 words per consumed hit record
         std::vector<float4> h(trace_cap);
         HIP_CHECK(hipStreamSynchronize(stream));
         HIP_CHECK(hipMemcpy(h.data(), d_trace, (size_t)trace_cap * sizeof(float4), hipMemcpyDeviceToHost));
         (void)hipFree(d_trace);
-        if (FILE *f = fopen(getenv("RTAMD_TRACE_OUT"), "wb")) { fwrite(h.data(), sizeof(float4), trace_cap, f); fclose(f); }
+        if (FILE *f = fopen(env_str("RTAMD_TRACE_OUT"), "wb")) { fwrite(h.data(), sizeof(float4), trace_cap, f); fclose(f); }
     }
 }
 
@@ -1011,7 +482,7 @@ enum class Pipeline { Persistent8, Persistent6, Rounds, Mega6, Mega8, Hw1, Hw2, 
 // hw6: the persistent pipeline (device/rt_persistent_hw6.h) when both own trees fit its stack columns; RTAMD_KERNEL=mega and
 // RTAMD_HW6_SCRATCH_STACK keep the per-lane path machine.
 static Pipeline choose_pipeline(const rt_scene *scene, int integrator, const RenderView &R, uint32_t n_work, int streams, bool &rounds_chosen) {
-    const char *ksel = getenv("RTAMD_KERNEL");
+    const char *ksel = env_str("RTAMD_KERNEL");
     const bool mega = ksel && strcmp(ksel, "mega") == 0;
     rounds_chosen = ksel && strcmp(ksel, "wavefront") == 0;
     switch (integrator) { // the .txt scenes' integrators
@@ -1022,13 +493,13 @@ static Pipeline choose_pipeline(const rt_scene *scene, int integrator, const Ren
     case RT_INTEGRATOR_HW5: return Pipeline::Hw5;
     }
     if (scene->flavor == RT_INTEGRATOR_HW6)
-        return scene->hw6_pt_stack && !mega && !getenv("RTAMD_HW6_SCRATCH_STACK") ? Pipeline::Persistent6 : Pipeline::Mega6;
+        return scene->hw6_pt_stack && !mega && !env_flag("RTAMD_HW6_SCRATCH_STACK") ? Pipeline::Persistent6 : Pipeline::Mega6;
     const rt_scene_info &I = scene->info;
     if (mega || I.bvh_depth > WF_STACK + WF_OVF || I.light_bvh_depth > 64 || I.n_triangles >= 0x40000000u // light depth: 64-bit frame mask
         || R.samples / streams >= (1 << 25)) // the path record keeps the sample index in 25 bits
         return Pipeline::Mega8;
-    if (rounds_chosen || I.bvh_depth > P8_STACK || scene->light_walk_depth > P8_STACK || getenv("RTAMD_WF_LDS_STACK")) return Pipeline::Rounds;
-    const uint64_t auto_groups = (uint64_t)(getenv("RTAMD_AUTO_GROUPS_PER_CU") ? atoi(getenv("RTAMD_AUTO_GROUPS_PER_CU")) : 0);
+    if (rounds_chosen || I.bvh_depth > P8_STACK || scene->light_walk_depth > P8_STACK || env_flag("RTAMD_WF_LDS_STACK")) return Pipeline::Rounds;
+    const uint64_t auto_groups = (uint64_t)env_int("RTAMD_AUTO_GROUPS_PER_CU", 0);
     if (!ksel && auto_groups && (uint64_t)n_work * (uint64_t)streams >= auto_groups * (uint64_t)scene->n_cus) return Pipeline::Rounds;
     return Pipeline::Persistent8;
 }
@@ -1038,37 +509,39 @@ static Pipeline choose_pipeline(const rt_scene *scene, int integrator, const Ren
 // (tools/tuning/wg_balance.py).
 static void report_persistent(rt_scene *scene, bool hw6, const char *kernel, bool count, const unsigned long long *h_cnt) {
     const bool times = scene->d_pt_debug && scene->pt_blocks <= PT_DEBUG_BLOCKS;
+    const unsigned long long *role = h_cnt + CNT_ROLE_TIME;
+    const double tt = (double)(role[0] + role[1] + role[2] + role[3] + role[4]);
+    auto nz = [](unsigned long long d) { return (double)(d ? d : 1); }; // a denominator that may be zero
     if (hw6) {
         fprintf(stderr, "[rtamd] persistent hw6 pipeline: %u launches; re-deal %.2f ms on the host (slowest workgroup / mean under the round-robin deal: %.3f); light sums through the slow role %llu of %llu; exact closest-hit walks %llu of %llu, exact light sums %llu\n",
-                scene->pt_launches, scene->pt_rebalance_ms, scene->pt_imbalance, h_cnt[13], h_cnt[1], h_cnt[12], h_cnt[0], h_cnt[11]);
+                scene->pt_launches, scene->pt_rebalance_ms, scene->pt_imbalance, h_cnt[CNT_P6_SLOW_LIGHT], h_cnt[CNT_LIGHT], h_cnt[CNT_EXACT_CLOSEST], h_cnt[CNT_CLOSEST], h_cnt[CNT_P6_EXACT_LIGHT]);
         if (count) {
             fprintf(stderr, "[rtamd] persistent hw6 kernel, light sums in the slow role by number of hits (0..14, 15+):");
-            for (int b = 0; b < 16; b++) fprintf(stderr, " %llu", h_cnt[32 + b]);
+            for (int b = 0; b < 16; b++) fprintf(stderr, " %llu", h_cnt[CNT_P6_SLOW_HITS + b]);
             fprintf(stderr, "\n");
-            const double tt = (double)(h_cnt[16] + h_cnt[17] + h_cnt[18] + h_cnt[19] + h_cnt[20]);
             fprintf(stderr, "[rtamd] persistent hw6 kernel, wave time by role: closest-hit walks %.1f %%, light walks %.1f %%, shading %.1f %%, slow light sums %.1f %%, idle %.1f %%\n",
-                    100 * h_cnt[16] / tt, 100 * h_cnt[17] / tt, 100 * h_cnt[18] / tt, 100 * h_cnt[19] / tt, 100 * h_cnt[20] / tt);
+                    100 * role[0] / tt, 100 * role[1] / tt, 100 * role[2] / tt, 100 * role[3] / tt, 100 * role[4] / tt);
         }
     } else if (times && count) {
-        const double tt = (double)(h_cnt[16] + h_cnt[17] + h_cnt[18] + h_cnt[19] + h_cnt[20]);
+        const unsigned long long *iters = h_cnt + CNT_P8_WALK_ITERS, n_light = h_cnt[CNT_LIGHT];
         fprintf(stderr, "[rtamd] persistent kernel, wave time by role: closest-hit walks %.1f %%, light walks %.1f %%, shading %.1f %%, exact walks %.2f %%, idle %.1f %%; "
                         "walker lane utilisation: closest hit %.1f of 64 (%llu wave iterations), light %.1f of 64 (%llu); %llu stints, %llu shade batches of %.1f paths\n",
-                100 * h_cnt[16] / tt, 100 * h_cnt[17] / tt, 100 * h_cnt[18] / tt, 100 * h_cnt[19] / tt, 100 * h_cnt[20] / tt,
-                (double)h_cnt[22] / (double)(h_cnt[21] ? h_cnt[21] : 1), h_cnt[21], (double)h_cnt[24] / (double)(h_cnt[23] ? h_cnt[23] : 1), h_cnt[23],
-                h_cnt[25], h_cnt[26], (double)h_cnt[27] / (double)(h_cnt[26] ? h_cnt[26] : 1));
+                100 * role[0] / tt, 100 * role[1] / tt, 100 * role[2] / tt, 100 * role[3] / tt, 100 * role[4] / tt,
+                (double)iters[1] / nz(iters[0]), iters[0], (double)iters[3] / nz(iters[2]), iters[2],
+                h_cnt[CNT_P8_STINTS], h_cnt[CNT_P8_SHADE_BATCHES], (double)h_cnt[CNT_P8_SHADE_ITEMS] / nz(h_cnt[CNT_P8_SHADE_BATCHES]));
         for (int w = 0; w < 2; w++) {
-            const double tw = (double)(h_cnt[48 + 3 * w] + h_cnt[49 + 3 * w] + h_cnt[50 + 3 * w]);
+            const unsigned long long *part = h_cnt + CNT_P8_WALK_TIME + 3 * w, *leaf = h_cnt + CNT_P8_LEAF_ITERS + 2 * w;
+            const double tw = (double)(part[0] + part[1] + part[2]);
             fprintf(stderr, "[rtamd]   %s walker's wave time: hand-off and refill %.1f %%, inner nodes %.1f %%, leaves %.1f %%; leaf passes %llu with %.1f of 64 lanes\n",
-                    w ? "light" : "closest-hit", 100 * h_cnt[48 + 3 * w] / tw, 100 * h_cnt[49 + 3 * w] / tw, 100 * h_cnt[50 + 3 * w] / tw,
-                    h_cnt[54 + 2 * w], (double)h_cnt[55 + 2 * w] / (double)(h_cnt[54 + 2 * w] ? h_cnt[54 + 2 * w] : 1));
+                    w ? "light" : "closest-hit", 100 * part[0] / tw, 100 * part[1] / tw, 100 * part[2] / tw, leaf[0], (double)leaf[1] / nz(leaf[0]));
         }
+        const unsigned long long *handoff = h_cnt + CNT_P8_HANDOFF_TIME, tests = h_cnt[CNT_P8_LIGHT_TESTS], hits = h_cnt[CNT_P8_LIGHT_HITS], *reach = h_cnt + CNT_P8_LIGHT_REACH;
         fprintf(stderr, "[rtamd]   closest-hit walker's hand-off points: %llu; of their time: publishing finished walks %.1f %%, taking new ones from the bitmap %.1f %%, reading their rays %.1f %% (the rest: the test itself)\n",
-                h_cnt[63], 100.0 * h_cnt[60] / (double)(h_cnt[48] ? h_cnt[48] : 1), 100.0 * h_cnt[61] / (double)(h_cnt[48] ? h_cnt[48] : 1), 100.0 * h_cnt[62] / (double)(h_cnt[48] ? h_cnt[48] : 1));
+                h_cnt[CNT_P8_HANDOFFS], 100.0 * handoff[0] / nz(h_cnt[CNT_P8_WALK_TIME]), 100.0 * handoff[1] / nz(h_cnt[CNT_P8_WALK_TIME]), 100.0 * handoff[2] / nz(h_cnt[CNT_P8_WALK_TIME]));
         fprintf(stderr, "[rtamd]   light tests %llu (%.2f per light sum), hits %llu (%.2f per light sum); triangle tests of closest-hit walks %llu (%.2f per query)\n",
-                h_cnt[59], (double)h_cnt[59] / (double)(h_cnt[1] ? h_cnt[1] : 1), h_cnt[58], (double)h_cnt[58] / (double)(h_cnt[1] ? h_cnt[1] : 1),
-                h_cnt[3] - h_cnt[59], (double)(h_cnt[3] - h_cnt[59]) / (double)(h_cnt[0] ? h_cnt[0] : 1));
+                tests, (double)tests / nz(n_light), hits, (double)hits / nz(n_light), h_cnt[CNT_TRI_TESTS] - tests, (double)(h_cnt[CNT_TRI_TESTS] - tests) / nz(h_cnt[CNT_CLOSEST]));
         fprintf(stderr, "[rtamd]   light sums whose walk ends at the light tree's root %llu (%.1f %%), one level below it %llu (%.1f %%); settled by the shader: level %d\n",
-                h_cnt[30], 100.0 * h_cnt[30] / (double)(h_cnt[1] ? h_cnt[1] : 1), h_cnt[31], 100.0 * h_cnt[31] / (double)(h_cnt[1] ? h_cnt[1] : 1), PT_LIGHT_SETTLE);
+                reach[0], 100.0 * reach[0] / nz(n_light), reach[1], 100.0 * reach[1] / nz(n_light), PT_LIGHT_SETTLE);
     }
     if (!times) return;
     std::vector<unsigned long long> dbg((size_t)scene->pt_blocks * 3);
@@ -1076,7 +549,7 @@ static void report_persistent(rt_scene *scene, bool hw6, const char *kernel, boo
     unsigned long long t0 = ~0ull, tmin = ~0ull, tmax = 0; double tsum = 0;
     for (uint32_t b = 0; b < scene->pt_blocks; b++) if (dbg[3 * b] && dbg[3 * b] < t0) t0 = dbg[3 * b];
     for (uint32_t b = 0; b < scene->pt_blocks; b++) { unsigned long long e = dbg[3 * b + 1] - t0; tmin = e < tmin ? e : tmin; tmax = e > tmax ? e : tmax; tsum += (double)e; }
-    if (const char *dump = getenv("RTAMD_DUMP_WG")) {
+    if (const char *dump = env_str("RTAMD_DUMP_WG")) {
         if (FILE *f = fopen(dump, "w")) {
             for (uint32_t b = 0; b < scene->pt_blocks; b++) fprintf(f, "%u %.4f %.4f %llu\n", b, (dbg[3 * b] - t0) * 1e-5, (dbg[3 * b + 1] - t0) * 1e-5, dbg[3 * b + 2]);
             fclose(f);
@@ -1087,7 +560,7 @@ static void report_persistent(rt_scene *scene, bool hw6, const char *kernel, boo
                 scene->pt_launches, scene->pt_rebalance_ms, scene->pt_imbalance);
     fprintf(stderr, "[rtamd] %s (last launch): %u workgroups, exit times min / mean / max = %.3f / %.3f / %.3f ms after the first start",
             kernel, scene->pt_blocks, tmin * 1e-5, tsum / scene->pt_blocks * 1e-5, tmax * 1e-5);
-    if (!hw6) fprintf(stderr, "; exact closest hits %llu, exact light sums %llu of %llu + %llu queries", h_cnt[12], h_cnt[13], h_cnt[0], h_cnt[1]);
+    if (!hw6) fprintf(stderr, "; exact closest hits %llu, exact light sums %llu of %llu + %llu queries", h_cnt[CNT_EXACT_CLOSEST], h_cnt[CNT_EXACT_LIGHT], h_cnt[CNT_CLOSEST], h_cnt[CNT_LIGHT]);
     fprintf(stderr, "\n");
 }
 
@@ -1108,245 +581,271 @@ static const char *accum_unsupported(Pipeline pipe, const rt_render_params *p) {
 // from and to `state` (RenderView::accum) instead of from a seed and to a pixel.
 struct AccumSlice { uint32_t *state; int32_t first; };
 
-// rt_render, and with `slice` rt_accum_render: the same checks, pipelines, launches and statistics.
-static int render_frame(rt_scene *scene, const rt_render_params *p, float *out_rgb, uint8_t *out_rgb8, rt_stats *stats, const AccumSlice *slice) {
-    const std::string who = slice ? "rt_accum_render: " : "rt_render: ";
+// What the checks of a frame settle for its launch and its statistics.
+struct Frame {
+    RenderView R{};
+    SceneView V8{};            // per-render copy of the hw8 view: the hw7 replay switches and the exactness are render parameters, not scene state
+    Pipeline pipe = Pipeline::Persistent8;
+    bool rounds_chosen = false, count = false, time_trace = false;
+    uint32_t n_work = 0;       // 8x8 sub-tiles of this shard
+    uint32_t blocks = 0;       // workgroups of the one-kernel pipelines; 0 = nothing to render
+    int streams = 1;
+    float txt_tan_fov_y = 0;
+    uint32_t launches = 0;
+};
+
+// ray_depth a render may ask of RT_INTEGRATOR_HWn (hw1 has none of its own; for it, hw7 and hw8 resolve_tiles has checked RT_MAX_DEPTH).
+static const int max_ray_depth[RT_INTEGRATOR_HW8 + 1] = {0, RT_MAX_DEPTH, RT2_MAX_DEPTH, RT3_MAX_DEPTH, RT4_MAX_DEPTH, RT4_MAX_DEPTH, RT6_MAX_DEPTH, RT_MAX_DEPTH, RT_MAX_DEPTH};
+
+// Part one of a render: argument and limit checks, in the order in which each error has always won; fills `F`.  Host only.
+static int check_frame(const rt_scene *scene, const rt_render_params *p, const AccumSlice *slice, const std::string &who, Frame &F) {
     if (!scene || !p) return fail(RT_ERR_INVALID_ARG, who + "null argument");
     if (p->struct_size != sizeof(rt_render_params)) return fail(RT_ERR_INVALID_ARG, who + "struct_size mismatch (ABI skew)");
-    if (p->integrator != RT_INTEGRATOR_HW8 && p->integrator != RT_INTEGRATOR_HW6 && p->integrator != RT_INTEGRATOR_HW3 && p->integrator != RT_INTEGRATOR_HW1 &&
-        p->integrator != RT_INTEGRATOR_HW2 && p->integrator != RT_INTEGRATOR_HW4 && p->integrator != RT_INTEGRATOR_HW5 && p->integrator != RT_INTEGRATOR_HW7)
-        return fail(RT_ERR_UNSUPPORTED, who + "unknown integrator");
+    if (p->integrator < RT_INTEGRATOR_HW1 || p->integrator > RT_INTEGRATOR_HW8) return fail(RT_ERR_UNSUPPORTED, who + "unknown integrator");
     const bool txt_scene = scene->flavor == RT_INTEGRATOR_HW3;
     const bool txt_integrator = p->integrator >= RT_INTEGRATOR_HW1 && p->integrator <= RT_INTEGRATOR_HW5;
     const bool hw7 = p->integrator == RT_INTEGRATOR_HW7; // renders a scene prepared for hw8 with hw7's material model (no textures)
     if (txt_scene != txt_integrator || (!txt_scene && p->integrator != scene->flavor && !(hw7 && scene->flavor == RT_INTEGRATOR_HW8)))
         return fail(RT_ERR_INVALID_ARG, who + "this scene was prepared for integrator " + std::to_string(scene->flavor) +
                                             " (hw6 scenes carry no vertex normals, hw8 scenes do)");
-    RenderView R{};
+    RenderView &R = F.R;
     std::string err;
     if (!resolve_tiles(p, R, err)) return fail(RT_ERR_INVALID_ARG, who + "" + err);
-    double t0 = now_ms();
-    float *d_rgb = nullptr;
-    uint8_t *d_rgb8 = nullptr;
-    bool own_rgb = false, own_rgb8 = false;
-    OwnedDev rgb_buf, rgb8_buf;
+    F.count = (p->flags & RT_FLAG_COUNTERS) != 0;
+    R.work_counter = scene->d_work_counter;
+    R.counters = F.count ? scene->d_counters : nullptr;
+    // scene.cpp:181,176 — evaluated on the host in float exactly like the reference
+    R.tan_fov_x = scene->view.tan_fov_y * R.width / R.height;
+    R.inv_samples = (float)(1.0 / R.samples);
+    const uint32_t n_work = F.n_work = R.n_shard_tiles * (uint32_t)((R.tile_w >> 3) * (R.tile_h >> 3));
+    const int streams = F.streams = p->sample_streams > 1 ? p->sample_streams : 1;
+    if (slice) { // sample indices are absolute, in the records as in RenderView
+        R.accum = slice->state; R.sample_first = slice->first; R.samples += slice->first;
+        R.n_pixslots = n_work * 64u;
+    }
+    R.sample_stop = R.samples;
+    if (p->reserved != 0) return fail(RT_ERR_INVALID_ARG, who + "reserved must be 0");
+    if ((p->flags & (RT_FLAG_SAMPLE_SEEDS | RT_FLAG_RUSSIAN_ROULETTE)) && streams <= 1)
+        return fail(RT_ERR_INVALID_ARG, who + "RT_FLAG_SAMPLE_SEEDS / RT_FLAG_RUSSIAN_ROULETTE change the estimator and belong to throughput mode (sample_streams > 1)");
+    if (streams > 1) { // throughput mode (include/rtamd.h: sample_streams)
+        if (p->integrator != RT_INTEGRATOR_HW8 && p->integrator != RT_INTEGRATOR_HW7 && p->integrator != RT_INTEGRATOR_HW6) return fail(RT_ERR_UNSUPPORTED, who + "sample_streams > 1 is implemented for RT_INTEGRATOR_HW6 / HW7 / HW8 only");
+        if (p->integrator == RT_INTEGRATOR_HW6 && (p->flags & (RT_FLAG_SAMPLE_SEEDS | RT_FLAG_RUSSIAN_ROULETTE))) return fail(RT_ERR_UNSUPPORTED, who + "RT_FLAG_SAMPLE_SEEDS / RT_FLAG_RUSSIAN_ROULETTE are implemented for RT_INTEGRATOR_HW7 / HW8 only");
+        if (streams > 256 || R.samples % streams != 0) return fail(RT_ERR_INVALID_ARG, who + "samples must be a multiple of sample_streams (at most 256 streams)");
+        if ((int64_t)R.width * R.height * streams >= 2147483647LL) return fail(RT_ERR_INVALID_ARG, who + "width*height*sample_streams must stay below 2^31-1 (stream seeds)");
+        if ((uint64_t)n_work * 64u * (uint64_t)streams >= 0x40000000ull) return fail(RT_ERR_LIMIT, who + "too many path slots (pixels of this shard x sample_streams)");
+    }
+    F.blocks = std::min((uint32_t)scene->n_cus * 16u, n_work);
+    F.pipe = choose_pipeline(scene, p->integrator, R, n_work, streams, F.rounds_chosen);
+    if (slice) if (const char *why = accum_unsupported(F.pipe, p)) return fail(RT_ERR_UNSUPPORTED, who + why);
+    if (streams > 1 && F.pipe != Pipeline::Persistent8 && F.pipe != Pipeline::Rounds && F.pipe != Pipeline::Persistent6) return fail(RT_ERR_UNSUPPORTED, who + "sample_streams > 1 needs the persistent / round kernels (RTAMD_KERNEL=mega or a tree beyond their limits is in effect)");
+    // the integrators' own limits; hw3's ray_depth has always been looked at before the TRIANGLE figures, the others' after them
+    const int max_depth = max_ray_depth[p->integrator];
+    const bool too_deep = R.ray_depth > max_depth;
+    auto deep = [&] { return fail(RT_ERR_LIMIT, who + "hw" + std::to_string(p->integrator) + " ray_depth above " + std::to_string(max_depth)); }; // RT_INTEGRATOR_HWn = n
+    if (too_deep && p->integrator == RT_INTEGRATOR_HW3) return deep();
+    if (txt_scene && scene->txt_has_triangles && p->integrator != RT_INTEGRATOR_HW5) return fail(RT_ERR_INVALID_ARG, who + "a .txt scene with TRIANGLE figures renders with RT_INTEGRATOR_HW5 only");
+    if (too_deep) return deep();
+    if (p->integrator == RT_INTEGRATOR_HW5 && (scene->info.bvh_depth > RT5_STACK || scene->info.light_bvh_depth > RT5_STACK)) return fail(RT_ERR_LIMIT, who + "hw5 BVH deeper than 64");
+    if (p->integrator == RT_INTEGRATOR_HW4 && scene->viewt.n_light_prims > RT4_MAX_LIGHTS) return fail(RT_ERR_LIMIT, who + "hw4 supports at most 32 emissive box/ellipsoid lights");
+    if (p->integrator == RT_INTEGRATOR_HW1 && R.shard_count > 1) return fail(RT_ERR_UNSUPPORTED, who + "the hw1 caster renders unsharded frames only");
+    const bool float_tan = p->integrator == RT_INTEGRATOR_HW1 || p->integrator == RT_INTEGRATOR_HW2;
+    F.txt_tan_fov_y = (float_tan ? scene->viewt.tan_fov_x_f : scene->viewt.tan_fov_x) * R.height / R.width; // hw3/src/scene.cpp:101
+    F.V8 = scene->view;
+    if (hw7) { F.V8.hw7 = 1; F.V8.last_level_emission_only = 0; F.V8.env_image = -1; }
+    // Exactness follows the scene, not the pipeline: when the persistent pipeline cannot take the scene (a tree deeper than its
+    // stack columns), the round pipeline runs with its exact kernels on.  Only an explicit RTAMD_KERNEL=wavefront (the yardstick
+    // of the benchmarks; RTAMD_ROUNDS_EXACT=1 switches the exact kernels on there too) and the megakernel, which has no gate,
+    // keep the padded boxes' answer — and say so in rt_stats.reference_exact.
+    if (F.pipe != Pipeline::Persistent8 && (F.pipe != Pipeline::Rounds || (F.rounds_chosen && !env_flag("RTAMD_ROUNDS_EXACT")))) F.V8.exact_boxes = 0;
+    if (!F.V8.exact_boxes) F.V8.cull_k = 4.8e-7f; // no exact walks to feed: the walkers look behind the best hit by the tie tolerance only
+    return RT_OK;
+}
+
+// Part two: the launches of the frame on `stream`, between the scene's two events.  want_times: rt_stats are asked for.
+static void launch_frame(rt_scene *scene, const rt_render_params *p, Frame &F, hipStream_t stream, bool want_times) {
+    RenderView &R = F.R;
+    const SceneView &V8 = F.V8;
+    const uint32_t n_work = F.n_work, blocks = F.blocks;
+    const int streams = F.streams;
+    const bool count = F.count;
+    HIP_CHECK(hipMemsetAsync(scene->d_work_counter, 0, 4, stream));
+    HIP_CHECK(hipMemsetAsync(scene->d_counters, 0, CNT_BYTES, stream));
+    if (count && env_flag("RTAMD_DEBUG_COUNTERS")) HIP_CHECK(hipMemsetAsync(scene->d_counters + CNT_WANT_HISTOGRAMS, 1, 1, stream)); // asks the counting kernels for the in-flight histograms
+    HIP_CHECK(hipEventRecord(scene->ev_start, stream));
+    if (blocks) {
+        if (streams > 1) { // throughput mode (include/rtamd.h: sample_streams): K path slots per pixel, `samples` per stream, a partial-sum buffer and a final reduction
+            R.streams = streams; R.n_pixslots = n_work * 64u; R.seed_stride = (uint32_t)R.width * (uint32_t)R.height;
+            R.total_samples = (uint32_t)R.samples;
+            R.sample_seeds = (p->flags & RT_FLAG_SAMPLE_SEEDS) ? 1u : 0u;
+            R.rr_depth = (p->flags & RT_FLAG_RUSSIAN_ROULETTE) ? 2 : 0;
+            R.samples /= streams;                           // per stream; inv_samples stays 1 / (all samples of the pixel)
+            R.sample_stop = R.samples;
+            grow((void **)&scene->d_partial, scene->partial_bytes, (size_t)streams * R.n_pixslots * 3 * sizeof(float));
+            R.partial = scene->d_partial;
+        }
+        const uint32_t n_slot_groups = n_work * (uint32_t)streams; // 64-slot groups of all streams
+        F.launches = 1;
+        switch (F.pipe) {
+        case Pipeline::Persistent8:
+        case Pipeline::Persistent6:
+            F.time_trace = want_times;
+            launch_persistent(scene, F.pipe == Pipeline::Persistent8 ? hw8_persistent(V8, R.ray_depth, stream, count) : hw6_persistent(scene->view6, stream, count),
+                              R, n_slot_groups, stream, count, F.time_trace);
+            F.launches = scene->pt_launches;
+            break;
+        case Pipeline::Rounds:
+            // every traverse launch is bracketed by events when stats are wanted -- up to 64 k rounds (e.g. 10,922 spp at depth 6)
+            F.time_trace = want_times && wavefront_rounds(V8, R) * (size_t)wavefront_pipelines(n_slot_groups) <= 65536;
+            launch_wavefront(scene, V8, R, n_slot_groups, stream, count, F.time_trace);
+            F.launches = (uint32_t)scene->wf_pipes * (1 + 2 * (uint32_t)wavefront_rounds(V8, R));
+            break;
+        case Pipeline::Mega6:
+            if (scene->hw6_lds_stack && !env_flag("RTAMD_HW6_SCRATCH_STACK")) hipLaunchKernelGGL(dev::render_hw6_kernel<true>, dim3(blocks), dim3(64), 0, stream, scene->view6, R, n_work);
+            else hipLaunchKernelGGL(dev::render_hw6_kernel<false>, dim3(blocks), dim3(64), 0, stream, scene->view6, R, n_work);
+            break;
+        case Pipeline::Mega8:
+            if (count) hipLaunchKernelGGL(dev::render_hw8_kernel<true>, dim3(blocks), dim3(64), 0, stream, V8, R, n_work);
+            else hipLaunchKernelGGL(dev::render_hw8_kernel<false>, dim3(blocks), dim3(64), 0, stream, V8, R, n_work);
+            break;
+        case Pipeline::Hw1: {
+            uint32_t npx = (uint32_t)R.width * (uint32_t)R.height;
+            hipLaunchKernelGGL(dev::render_hw1_kernel, dim3((npx + 255) / 256), dim3(256), 0, stream, scene->viewt, R.width, R.height, F.txt_tan_fov_y, R.out_rgb, R.out_rgb8);
+            break;
+        }
+        case Pipeline::Hw2: hipLaunchKernelGGL(dev::render_hw2_kernel, dim3(blocks), dim3(64), 0, stream, scene->viewt, R, F.txt_tan_fov_y, n_work); break;
+        case Pipeline::Hw3: hipLaunchKernelGGL(dev::render_hw3_kernel, dim3(blocks), dim3(64), 0, stream, scene->viewt, R, F.txt_tan_fov_y, n_work); break;
+        case Pipeline::Hw4: hipLaunchKernelGGL(dev::render_hw4_kernel, dim3(blocks), dim3(64), 0, stream, scene->viewt, R, F.txt_tan_fov_y, n_work); break;
+        case Pipeline::Hw5: hipLaunchKernelGGL(dev::render_hw5_kernel, dim3(blocks), dim3(64), 0, stream, scene->view5, R, F.txt_tan_fov_y, n_work); break;
+        }
+        HIP_CHECK(hipGetLastError());
+        if (streams > 1) {
+            hipLaunchKernelGGL(dev::wf_reduce_streams_kernel, dim3((R.n_pixslots + 255u) / 256u), dim3(256), 0, stream, R);
+            HIP_CHECK(hipGetLastError());
+            F.launches++;
+        }
+    }
+    HIP_CHECK(hipEventRecord(scene->ev_stop, stream));
+}
+
+// Part three: wait for the frame, read its counters (rt_types.h CounterSlot), report what the kernels gave up on, print the
+// RTAMD_DEBUG_COUNTERS report and fill `stats` (nullable).  t0: when the render began.
+static int collect_frame(rt_scene *scene, const Frame &F, hipStream_t stream, rt_stats *stats, double t0, const std::string &who) {
+    const RenderView &R = F.R;
+    const SceneView &V8 = F.V8;
+    const Pipeline pipe = F.pipe;
+    const bool count = F.count, time_trace = F.time_trace, debug = env_flag("RTAMD_DEBUG_COUNTERS");
+    unsigned long long h_cnt[CNT_SLOTS] = {0};
+    HIP_CHECK(hipMemcpyAsync(h_cnt, scene->d_counters, CNT_BYTES, hipMemcpyDeviceToHost, stream));
+    HIP_CHECK(hipStreamSynchronize(stream)); // render is synchronous on return
+    const bool ran_persistent = F.blocks && (pipe == Pipeline::Persistent8 || pipe == Pipeline::Persistent6);
+    const bool ran_rounds = F.blocks && pipe == Pipeline::Rounds;
+    if (ran_persistent) {
+        const bool hw6 = pipe == Pipeline::Persistent6;
+        const char *kernel = hw6 ? "persistent hw6 kernel" : "persistent kernel";
+        if (!hw6) h_cnt[CNT_CLOSEST] -= std::min(h_cnt[CNT_DISCARDED], h_cnt[CNT_CLOSEST]); // speculative closest-hit queries that the clamp step discarded are not part of the algorithm
+        if (debug) report_persistent(scene, hw6, kernel, count, h_cnt);
+        if (h_cnt[CNT_DEADLINE]) return fail(RT_ERR_LIMIT, who + "the " + kernel + " ran into its launch deadline (" + std::to_string(h_cnt[CNT_DEADLINE]) + " waves; RTAMD_PT_TIMEOUT_S raises it); the frame is incomplete");
+        if (h_cnt[CNT_LOST_PATH]) return fail(RT_ERR_HIP, who + "the " + kernel + " lost a path (" + std::to_string(h_cnt[CNT_LOST_PATH]) + " waves gave up waiting); the frame is incomplete");
+    }
+    auto round_counters = [&] { // of the round pipeline: WF_CTR words per round and pipeline
+        std::vector<uint32_t> ctr(scene->wf_ctr_block * scene->wf_pipes);
+        HIP_CHECK(hipMemcpy(ctr.data(), scene->wf.ctr, ctr.size() * 4, hipMemcpyDeviceToHost));
+        return ctr;
+    };
+    if (count && ran_rounds) { // queries = lengths of the per-round queues
+        size_t rounds = wavefront_rounds(V8, R);
+        const std::vector<uint32_t> ctr = round_counters();
+        for (int h = 0; h < scene->wf_pipes; h++)
+            for (size_t r = 0; r < rounds; r++) {
+                const uint32_t *c = ctr.data() + (size_t)h * scene->wf_ctr_block + WF_CTR * r;
+                h_cnt[CNT_CLOSEST] += c[0];
+                if (scene->info.n_lights) { h_cnt[CNT_LIGHT] += c[1]; h_cnt[CNT_WF_SLOW_LIGHT] += c[4]; }
+            }
+        h_cnt[CNT_CLOSEST] -= h_cnt[CNT_DISCARDED]; // speculative closest-hit queries that the clamp step discarded are not part of the algorithm
+        h_cnt[CNT_EXACT_LIGHT] = h_cnt[CNT_WF_SLOW_LIGHT]; // light sums finished by the exact kernel
+    }
+    // The two histograms are the round pipeline's (CNT_WF_HIST_*).  After a persistent hw8 render the same lines print what that kernel
+    // keeps in those slots (CNT_ROLE_TIME .. CNT_P8_LIGHT_REACH, then zeros), and the last line's CNT_WF_* slots are the round pipeline's
+    // too (after a persistent hw6 render slot 11 is CNT_P6_EXACT_LIGHT): kept as they are, see profiles/r08_api_split.txt.
+    if (count && debug && (pipe == Pipeline::Persistent8 || pipe == Pipeline::Rounds)) { // wave iterations a query stays in flight, buckets of 32
+        fprintf(stderr, "[rtamd] closest-hit queries by in-flight wave iterations (x32):");
+        for (int b = 0; b < 16; b++) fprintf(stderr, " %llu", h_cnt[CNT_WF_HIST_CLOSEST + b]);
+        fprintf(stderr, "\n[rtamd] light queries by in-flight wave iterations (x32):");
+        for (int b = 0; b < 16; b++) fprintf(stderr, " %llu", h_cnt[CNT_WF_HIST_LIGHT + b]);
+        fprintf(stderr, "\n");
+    }
+    if (count && debug)
+        fprintf(stderr, "[rtamd] light queries finished by the exact kernel: %llu of %llu; trace kernel: wave node-iterations %llu, leaf phases %llu (lanes %llu), refills %llu; lane node visits %llu, tri tests %llu\n",
+                h_cnt[CNT_WF_SLOW_LIGHT], h_cnt[CNT_LIGHT], h_cnt[CNT_WF_NODE_ITERS], h_cnt[CNT_WF_LEAF_PHASES], h_cnt[CNT_WF_LEAF_LANES], h_cnt[CNT_WF_REFILLS],
+                h_cnt[CNT_WF_LANE_NODES], h_cnt[CNT_WF_LANE_TRIS]);
+    if (!stats) return RT_OK;
+    float ms = 0;
+    HIP_CHECK(hipEventElapsedTime(&ms, scene->ev_start, scene->ev_stop));
+    memset(stats, 0, sizeof *stats);
+    stats->kernel_ms = ms;
+    stats->total_ms = now_ms() - t0;
+    stats->launches = F.launches;
+    stats->pipeline = ran_persistent ? RT_PIPELINE_PERSISTENT : ran_rounds ? RT_PIPELINE_ROUNDS : RT_PIPELINE_SINGLE;
+    stats->reference_exact = pipe == Pipeline::Hw5 ? 1u : pipe == Pipeline::Persistent6 ? (F.blocks && scene->view6.exact_boxes ? 1u : 0u)
+                             : ((ran_persistent || ran_rounds) && V8.exact_boxes == 1u ? 1u : 0u);
+    if (ran_persistent) {
+        double sum = 0;
+        for (uint32_t pp = 0; time_trace && pp < scene->pt_launches; pp++) { float e = 0; HIP_CHECK(hipEventElapsedTime(&e, scene->ev_pool[2 * pp], scene->ev_pool[2 * pp + 1])); sum += e; }
+        stats->dominant_kernel_ms = time_trace ? sum : ms; stats->dominant_kernel_launches = scene->pt_launches;
+        stats->exact_closest_hits = h_cnt[CNT_EXACT_CLOSEST];
+        stats->exact_light_sums = pipe == Pipeline::Persistent6 ? h_cnt[CNT_P6_EXACT_LIGHT] : h_cnt[CNT_EXACT_LIGHT];
+    } else if (ran_rounds && time_trace) {
+        stats->exact_closest_hits = h_cnt[CNT_EXACT_CLOSEST]; stats->exact_light_sums = h_cnt[CNT_EXACT_LIGHT]; // counting renders only
+        size_t rounds = wavefront_rounds(V8, R);
+        double sum = 0;
+        const size_t n_launch = rounds * (size_t)scene->wf_pipes; // with more than one pipeline a launch shares the GPU with the other pipelines' kernels
+        for (size_t r = 0; r < n_launch; r++) { float e = 0; HIP_CHECK(hipEventElapsedTime(&e, scene->ev_pool[2 * r], scene->ev_pool[2 * r + 1])); sum += e; }
+        stats->dominant_kernel_ms = sum; stats->dominant_kernel_launches = (uint32_t)n_launch;
+        if (const char *path = env_str("RTAMD_DUMP_ROUNDS")) { // diagnostic: per launch of the traverse kernel its queue lengths and duration
+            const std::vector<uint32_t> ctr = round_counters();
+            if (FILE *f = fopen(path, "a")) { // appended: one block per render
+                fprintf(f, "round,pipeline,closest_hit_queries,light_queries,traverse_ms\n");
+                for (size_t r = 0; r < rounds; r++)
+                    for (int h = 0; h < scene->wf_pipes; h++) {
+                        float e = 0; (void)hipEventElapsedTime(&e, scene->ev_pool[2 * (r * scene->wf_pipes + h)], scene->ev_pool[2 * (r * scene->wf_pipes + h) + 1]);
+                        const uint32_t *c = ctr.data() + (size_t)h * scene->wf_ctr_block + WF_CTR * r;
+                        fprintf(f, "%zu,%d,%u,%u,%.4f\n", r, h, c[0], c[1], e);
+                    }
+                fclose(f);
+            }
+        }
+    } else { stats->dominant_kernel_ms = ms; stats->dominant_kernel_launches = F.launches; }
+    uint64_t px = 0; // pixels of this shard that lie inside the image
+    for (uint32_t st = 0; st < R.n_shard_tiles; st++) {
+        int x0, y0, w, h;
+        shard_tile_rect(R, st, x0, y0, w, h);
+        px += (uint64_t)w * h;
+    }
+    stats->samples = px * (uint64_t)(R.samples - R.sample_first) * (uint64_t)F.streams;
+    stats->closest_hit_queries = h_cnt[CNT_CLOSEST]; stats->light_pdf_queries = h_cnt[CNT_LIGHT];
+    stats->node_visits = h_cnt[CNT_NODE_VISITS]; stats->triangle_tests = h_cnt[CNT_TRI_TESTS];
+    return RT_OK;
+}
+
+// rt_render, and with `slice` rt_accum_render: the same checks, pipelines, launches and statistics.
+static int render_frame(rt_scene *scene, const rt_render_params *p, float *out_rgb, uint8_t *out_rgb8, rt_stats *stats, const AccumSlice *slice) {
+    const std::string who = slice ? "rt_accum_render: " : "rt_render: ";
+    Frame F;
+    if (const int rc = check_frame(scene, p, slice, who, F)) return rc;
+    const double t0 = now_ms();
+    OwnedDev rgb_buf, rgb8_buf; // host-output renders: freed on every way out
     try {
         HIP_CHECK(hipSetDevice(scene->device));
         hipStream_t stream = (hipStream_t)p->stream;
         const bool out_dev = (p->flags & RT_FLAG_OUT_DEVICE) != 0;
-        const bool count = (p->flags & RT_FLAG_COUNTERS) != 0;
-        size_t elems = rt_output_elems(p);
-        if (out_rgb) {
-            if (out_dev) d_rgb = out_rgb;
-            else { HIP_CHECK(hipMalloc(&rgb_buf.p, elems * sizeof(float))); d_rgb = (float *)rgb_buf.p; own_rgb = true; }
-        }
-        if (out_rgb8) {
-            if (out_dev) d_rgb8 = out_rgb8;
-            else { HIP_CHECK(hipMalloc(&rgb8_buf.p, elems)); d_rgb8 = (uint8_t *)rgb8_buf.p; own_rgb8 = true; }
-        }
-        R.out_rgb = d_rgb; R.out_rgb8 = d_rgb8;
-        R.work_counter = scene->d_work_counter;
-        R.counters = count ? scene->d_counters : nullptr;
-        // scene.cpp:181,176 — evaluated on the host in float exactly like the reference
-        R.tan_fov_x = scene->view.tan_fov_y * R.width / R.height;
-        R.inv_samples = (float)(1.0 / R.samples);
-        uint32_t n_work = R.n_shard_tiles * (uint32_t)((R.tile_w >> 3) * (R.tile_h >> 3));
-        const int streams = p->sample_streams > 1 ? p->sample_streams : 1;
-        if (slice) { // sample indices are absolute, in the records as in RenderView
-            R.accum = slice->state; R.sample_first = slice->first; R.samples += slice->first;
-            R.n_pixslots = n_work * 64u;
-        }
-        R.sample_stop = R.samples;
-        if (p->reserved != 0) return fail(RT_ERR_INVALID_ARG, who + "reserved must be 0");
-        if ((p->flags & (RT_FLAG_SAMPLE_SEEDS | RT_FLAG_RUSSIAN_ROULETTE)) && streams <= 1)
-            return fail(RT_ERR_INVALID_ARG, who + "RT_FLAG_SAMPLE_SEEDS / RT_FLAG_RUSSIAN_ROULETTE change the estimator and belong to throughput mode (sample_streams > 1)");
-        if (streams > 1) { // throughput mode (include/rtamd.h: sample_streams)
-            if (p->integrator != RT_INTEGRATOR_HW8 && p->integrator != RT_INTEGRATOR_HW7 && p->integrator != RT_INTEGRATOR_HW6) return fail(RT_ERR_UNSUPPORTED, who + "sample_streams > 1 is implemented for RT_INTEGRATOR_HW6 / HW7 / HW8 only");
-            if (p->integrator == RT_INTEGRATOR_HW6 && (p->flags & (RT_FLAG_SAMPLE_SEEDS | RT_FLAG_RUSSIAN_ROULETTE))) return fail(RT_ERR_UNSUPPORTED, who + "RT_FLAG_SAMPLE_SEEDS / RT_FLAG_RUSSIAN_ROULETTE are implemented for RT_INTEGRATOR_HW7 / HW8 only");
-            if (streams > 256 || R.samples % streams != 0) return fail(RT_ERR_INVALID_ARG, who + "samples must be a multiple of sample_streams (at most 256 streams)");
-            if ((int64_t)R.width * R.height * streams >= 2147483647LL) return fail(RT_ERR_INVALID_ARG, who + "width*height*sample_streams must stay below 2^31-1 (stream seeds)");
-            if ((uint64_t)n_work * 64u * (uint64_t)streams >= 0x40000000ull) return fail(RT_ERR_LIMIT, who + "too many path slots (pixels of this shard x sample_streams)");
-        }
-        HIP_CHECK(hipMemsetAsync(scene->d_work_counter, 0, 4, stream));
-        HIP_CHECK(hipMemsetAsync(scene->d_counters, 0, 512, stream));
-        if (count) {
-            if (getenv("RTAMD_DEBUG_COUNTERS")) HIP_CHECK(hipMemsetAsync(scene->d_counters + 15, 1, 1, stream)); // asks the counting kernels for the in-flight histograms
-        }
-        uint32_t blocks = (uint32_t)scene->n_cus * 16u;
-        if (blocks > n_work) blocks = n_work;
-        bool rounds_chosen = false;
-        const Pipeline pipe = choose_pipeline(scene, p->integrator, R, n_work, streams, rounds_chosen);
-        if (slice) if (const char *why = accum_unsupported(pipe, p)) return fail(RT_ERR_UNSUPPORTED, who + why);
-        if (streams > 1 && pipe != Pipeline::Persistent8 && pipe != Pipeline::Rounds && pipe != Pipeline::Persistent6) return fail(RT_ERR_UNSUPPORTED, who + "sample_streams > 1 needs the persistent / round kernels (RTAMD_KERNEL=mega or a tree beyond their limits is in effect)");
-        if (txt_scene && p->integrator == RT_INTEGRATOR_HW3 && R.ray_depth > RT3_MAX_DEPTH) return fail(RT_ERR_LIMIT, who + "hw3 ray_depth above 8");
-        if (txt_scene && scene->txt_has_triangles && p->integrator != RT_INTEGRATOR_HW5) return fail(RT_ERR_INVALID_ARG, who + "a .txt scene with TRIANGLE figures renders with RT_INTEGRATOR_HW5 only");
-        if (p->integrator == RT_INTEGRATOR_HW5 && R.ray_depth > RT4_MAX_DEPTH) return fail(RT_ERR_LIMIT, who + "hw5 ray_depth above 8");
-        if (p->integrator == RT_INTEGRATOR_HW5 && (scene->info.bvh_depth > RT5_STACK || scene->info.light_bvh_depth > RT5_STACK)) return fail(RT_ERR_LIMIT, who + "hw5 BVH deeper than 64");
-        if (p->integrator == RT_INTEGRATOR_HW4 && R.ray_depth > RT4_MAX_DEPTH) return fail(RT_ERR_LIMIT, who + "hw4 ray_depth above 8");
-        if (p->integrator == RT_INTEGRATOR_HW4 && scene->viewt.n_light_prims > RT4_MAX_LIGHTS) return fail(RT_ERR_LIMIT, who + "hw4 supports at most 32 emissive box/ellipsoid lights");
-        if (p->integrator == RT_INTEGRATOR_HW2 && R.ray_depth > RT2_MAX_DEPTH) return fail(RT_ERR_LIMIT, who + "hw2 ray_depth above 16");
-        if (p->integrator == RT_INTEGRATOR_HW1 && R.shard_count > 1) return fail(RT_ERR_UNSUPPORTED, who + "the hw1 caster renders unsharded frames only");
-        const bool float_tan = p->integrator == RT_INTEGRATOR_HW1 || p->integrator == RT_INTEGRATOR_HW2;
-        const float txt_tan_fov_y = (float_tan ? scene->viewt.tan_fov_x_f : scene->viewt.tan_fov_x) * R.height / R.width; // hw3/src/scene.cpp:101
-        if (scene->flavor == RT_INTEGRATOR_HW6 && R.ray_depth > RT6_MAX_DEPTH) return fail(RT_ERR_LIMIT, who + "hw6 ray_depth above 8");
-        SceneView V8 = scene->view; // per-render copy: the hw7 replay switches are render parameters, not scene state
-        if (hw7) { V8.hw7 = 1; V8.last_level_emission_only = 0; V8.env_image = -1; }
-        // Exactness follows the scene, not the pipeline: when the persistent pipeline cannot take the scene (a tree deeper than its
-        // stack columns), the round pipeline runs with its exact kernels on.  Only an explicit RTAMD_KERNEL=wavefront (the yardstick
-        // of the benchmarks; RTAMD_ROUNDS_EXACT=1 switches the exact kernels on there too) and the megakernel, which has no gate,
-        // keep the padded boxes' answer — and say so in rt_stats.reference_exact.
-        if (pipe != Pipeline::Persistent8 && (pipe != Pipeline::Rounds || (rounds_chosen && !getenv("RTAMD_ROUNDS_EXACT")))) V8.exact_boxes = 0;
-        if (!V8.exact_boxes) V8.cull_k = 4.8e-7f; // no exact walks to feed: the walkers look behind the best hit by the tie tolerance only
-        uint32_t launches = 0;
-        bool time_trace = false;
-        HIP_CHECK(hipEventRecord(scene->ev_start, stream));
-        if (blocks) {
-            if (streams > 1) { // throughput mode (include/rtamd.h: sample_streams): K path slots per pixel, `samples` per stream, a partial-sum buffer and a final reduction
-                R.streams = streams; R.n_pixslots = n_work * 64u; R.seed_stride = (uint32_t)R.width * (uint32_t)R.height;
-                R.total_samples = (uint32_t)R.samples;
-                R.sample_seeds = (p->flags & RT_FLAG_SAMPLE_SEEDS) ? 1u : 0u;
-                R.rr_depth = (p->flags & RT_FLAG_RUSSIAN_ROULETTE) ? 2 : 0;
-                R.samples /= streams;                           // per stream; inv_samples stays 1 / (all samples of the pixel)
-                R.sample_stop = R.samples;
-                const size_t need = (size_t)streams * R.n_pixslots * 3 * sizeof(float);
-                if (scene->partial_bytes < need) {
-                    if (scene->d_partial) (void)hipFree(scene->d_partial);
-                    scene->d_partial = nullptr; scene->partial_bytes = 0;
-                    HIP_CHECK(hipMalloc((void **)&scene->d_partial, need));
-                    scene->partial_bytes = need;
-                }
-                R.partial = scene->d_partial;
-            }
-            const uint32_t n_slot_groups = n_work * (uint32_t)streams; // 64-slot groups of all streams
-            launches = 1;
-            switch (pipe) {
-            case Pipeline::Persistent8:
-            case Pipeline::Persistent6:
-                time_trace = stats != nullptr;
-                launch_persistent(scene, pipe == Pipeline::Persistent8 ? hw8_persistent(V8, R.ray_depth, stream, count) : hw6_persistent(scene->view6, stream, count),
-                                  R, n_slot_groups, stream, count, time_trace);
-                launches = scene->pt_launches;
-                break;
-            case Pipeline::Rounds:
-                // every traverse launch is bracketed by events when stats are wanted -- up to 64 k rounds (e.g. 10,922 spp at depth 6)
-                time_trace = stats != nullptr && wavefront_rounds(V8, R) * (size_t)wavefront_pipelines(n_slot_groups) <= 65536;
-                launch_wavefront(scene, V8, R, n_slot_groups, stream, count, time_trace);
-                launches = (uint32_t)scene->wf_pipes * (1 + 2 * (uint32_t)wavefront_rounds(V8, R));
-                break;
-            case Pipeline::Mega6:
-                if (scene->hw6_lds_stack && !getenv("RTAMD_HW6_SCRATCH_STACK")) hipLaunchKernelGGL(dev::render_hw6_kernel<true>, dim3(blocks), dim3(64), 0, stream, scene->view6, R, n_work);
-                else hipLaunchKernelGGL(dev::render_hw6_kernel<false>, dim3(blocks), dim3(64), 0, stream, scene->view6, R, n_work);
-                break;
-            case Pipeline::Mega8:
-                if (count) hipLaunchKernelGGL(dev::render_hw8_kernel<true>, dim3(blocks), dim3(64), 0, stream, V8, R, n_work);
-                else hipLaunchKernelGGL(dev::render_hw8_kernel<false>, dim3(blocks), dim3(64), 0, stream, V8, R, n_work);
-                break;
-            case Pipeline::Hw1: {
-                uint32_t npx = (uint32_t)R.width * (uint32_t)R.height;
-                hipLaunchKernelGGL(dev::render_hw1_kernel, dim3((npx + 255) / 256), dim3(256), 0, stream, scene->viewt, R.width, R.height, txt_tan_fov_y, d_rgb, d_rgb8);
-                break;
-            }
-            case Pipeline::Hw2: hipLaunchKernelGGL(dev::render_hw2_kernel, dim3(blocks), dim3(64), 0, stream, scene->viewt, R, txt_tan_fov_y, n_work); break;
-            case Pipeline::Hw3: hipLaunchKernelGGL(dev::render_hw3_kernel, dim3(blocks), dim3(64), 0, stream, scene->viewt, R, txt_tan_fov_y, n_work); break;
-            case Pipeline::Hw4: hipLaunchKernelGGL(dev::render_hw4_kernel, dim3(blocks), dim3(64), 0, stream, scene->viewt, R, txt_tan_fov_y, n_work); break;
-            case Pipeline::Hw5: hipLaunchKernelGGL(dev::render_hw5_kernel, dim3(blocks), dim3(64), 0, stream, scene->view5, R, txt_tan_fov_y, n_work); break;
-            }
-            HIP_CHECK(hipGetLastError());
-            if (streams > 1) {
-                hipLaunchKernelGGL(dev::wf_reduce_streams_kernel, dim3((R.n_pixslots + 255u) / 256u), dim3(256), 0, stream, R);
-                HIP_CHECK(hipGetLastError());
-                launches++;
-            }
-        }
-        HIP_CHECK(hipEventRecord(scene->ev_stop, stream));
-        if (own_rgb) HIP_CHECK(hipMemcpyAsync(out_rgb, d_rgb, elems * sizeof(float), hipMemcpyDeviceToHost, stream));
-        if (own_rgb8) HIP_CHECK(hipMemcpyAsync(out_rgb8, d_rgb8, elems, hipMemcpyDeviceToHost, stream));
-        unsigned long long h_cnt[64] = {0};
-        HIP_CHECK(hipMemcpyAsync(h_cnt, scene->d_counters, 512, hipMemcpyDeviceToHost, stream));
-        HIP_CHECK(hipStreamSynchronize(stream)); // render is synchronous on return
-        const bool ran_persistent = blocks && (pipe == Pipeline::Persistent8 || pipe == Pipeline::Persistent6);
-        const bool ran_rounds = blocks && pipe == Pipeline::Rounds;
-        if (ran_persistent) {
-            const bool hw6 = pipe == Pipeline::Persistent6;
-            const char *kernel = hw6 ? "persistent hw6 kernel" : "persistent kernel";
-            if (!hw6) h_cnt[0] -= h_cnt[10] < h_cnt[0] ? h_cnt[10] : h_cnt[0]; // speculative closest-hit queries that the clamp step discarded are not part of the algorithm
-            if (getenv("RTAMD_DEBUG_COUNTERS")) report_persistent(scene, hw6, kernel, count, h_cnt);
-            if (h_cnt[29]) return fail(RT_ERR_LIMIT, who + "the " + kernel + " ran into its launch deadline (" + std::to_string(h_cnt[29]) + " waves; RTAMD_PT_TIMEOUT_S raises it); the frame is incomplete");
-            if (h_cnt[14]) return fail(RT_ERR_HIP, who + "the " + kernel + " lost a path (" + std::to_string(h_cnt[14]) + " waves gave up waiting); the frame is incomplete");
-        }
-        if (count && ran_rounds) { // queries = lengths of the per-round queues
-            size_t rounds = wavefront_rounds(V8, R);
-            std::vector<uint32_t> ctr(scene->wf_ctr_block * scene->wf_pipes);
-            HIP_CHECK(hipMemcpy(ctr.data(), scene->wf.ctr, ctr.size() * 4, hipMemcpyDeviceToHost));
-            for (int h = 0; h < scene->wf_pipes; h++)
-                for (size_t r = 0; r < rounds; r++) {
-                    const uint32_t *c = ctr.data() + (size_t)h * scene->wf_ctr_block + WF_CTR * r;
-                    h_cnt[0] += c[0];
-                    if (scene->info.n_lights) { h_cnt[1] += c[1]; h_cnt[11] += c[4]; }
-                }
-            h_cnt[0] -= h_cnt[10]; // speculative closest-hit queries that the clamp step discarded are not part of the algorithm
-            h_cnt[13] = h_cnt[11];  // light sums finished by the exact kernel
-        }
-        if (count && (pipe == Pipeline::Persistent8 || pipe == Pipeline::Rounds) && getenv("RTAMD_DEBUG_COUNTERS")) { // wave iterations a query stays in flight, buckets of 32
-            fprintf(stderr, "[rtamd] closest-hit queries by in-flight wave iterations (x32):");
-            for (int b = 0; b < 16; b++) fprintf(stderr, " %llu", h_cnt[16 + b]);
-            fprintf(stderr, "\n[rtamd] light queries by in-flight wave iterations (x32):");
-            for (int b = 0; b < 16; b++) fprintf(stderr, " %llu", h_cnt[32 + b]);
-            fprintf(stderr, "\n");
-        }
-        if (count && getenv("RTAMD_DEBUG_COUNTERS"))
-            fprintf(stderr, "[rtamd] light queries finished by the exact kernel: %llu of %llu; trace kernel: wave node-iterations %llu, leaf phases %llu (lanes %llu), refills %llu; lane node visits %llu, tri tests %llu\n",
-                    h_cnt[11], h_cnt[1], h_cnt[4], h_cnt[5], h_cnt[6], h_cnt[7], h_cnt[8], h_cnt[9]);
-        if (stats) {
-            float ms = 0;
-            HIP_CHECK(hipEventElapsedTime(&ms, scene->ev_start, scene->ev_stop));
-            memset(stats, 0, sizeof *stats);
-            stats->kernel_ms = ms;
-            stats->total_ms = now_ms() - t0;
-            stats->launches = launches;
-            stats->pipeline = ran_persistent ? RT_PIPELINE_PERSISTENT : ran_rounds ? RT_PIPELINE_ROUNDS : RT_PIPELINE_SINGLE;
-            stats->reference_exact = pipe == Pipeline::Hw5 ? 1u : pipe == Pipeline::Persistent6 ? (blocks && scene->view6.exact_boxes ? 1u : 0u)
-                                     : ((ran_persistent || ran_rounds) && V8.exact_boxes == 1u ? 1u : 0u);
-            if (ran_persistent) {
-                double sum = 0;
-                for (uint32_t pp = 0; time_trace && pp < scene->pt_launches; pp++) { float e = 0; HIP_CHECK(hipEventElapsedTime(&e, scene->ev_pool[2 * pp], scene->ev_pool[2 * pp + 1])); sum += e; }
-                stats->dominant_kernel_ms = time_trace ? sum : ms; stats->dominant_kernel_launches = scene->pt_launches;
-                stats->exact_closest_hits = h_cnt[12]; stats->exact_light_sums = pipe == Pipeline::Persistent6 ? h_cnt[11] : h_cnt[13];
-            } else if (ran_rounds && time_trace) {
-                stats->exact_closest_hits = h_cnt[12]; stats->exact_light_sums = h_cnt[13]; // counting renders only
-                size_t rounds = wavefront_rounds(V8, R);
-                double sum = 0;
-                const size_t n_launch = rounds * (size_t)scene->wf_pipes; // with more than one pipeline a launch shares the GPU with the other pipelines' kernels
-                for (size_t r = 0; r < n_launch; r++) { float e = 0; HIP_CHECK(hipEventElapsedTime(&e, scene->ev_pool[2 * r], scene->ev_pool[2 * r + 1])); sum += e; }
-                stats->dominant_kernel_ms = sum; stats->dominant_kernel_launches = (uint32_t)n_launch;
-                if (const char *path = getenv("RTAMD_DUMP_ROUNDS")) { // diagnostic: per launch of the traverse kernel its queue lengths and duration
-                    std::vector<uint32_t> ctr(scene->wf_ctr_block * scene->wf_pipes);
-                    HIP_CHECK(hipMemcpy(ctr.data(), scene->wf.ctr, ctr.size() * 4, hipMemcpyDeviceToHost));
-                    if (FILE *f = fopen(path, "a")) { // appended: one block per render
-                        fprintf(f, "round,pipeline,closest_hit_queries,light_queries,traverse_ms\n");
-                        for (size_t r = 0; r < rounds; r++)
-                            for (int h = 0; h < scene->wf_pipes; h++) {
-                                float e = 0; (void)hipEventElapsedTime(&e, scene->ev_pool[2 * (r * scene->wf_pipes + h)], scene->ev_pool[2 * (r * scene->wf_pipes + h) + 1]);
-                                const uint32_t *c = ctr.data() + (size_t)h * scene->wf_ctr_block + WF_CTR * r;
-                                fprintf(f, "%zu,%d,%u,%u,%.4f\n", r, h, c[0], c[1], e);
-                            }
-                        fclose(f);
-                    }
-                }
-            } else { stats->dominant_kernel_ms = ms; stats->dominant_kernel_launches = launches; }
-            // pixels of this shard that lie inside the image
-            uint64_t px = 0;
-            for (uint32_t st = 0; st < R.n_shard_tiles; st++) {
-                uint32_t gt = R.shard_count > 1 ? (uint32_t)R.shard_index + st * (uint32_t)R.shard_count : st;
-                int tx0 = (int)(gt % (uint32_t)R.tiles_x) * R.tile_w, ty0 = (int)(gt / (uint32_t)R.tiles_x) * R.tile_h;
-                int w = R.width - tx0 < R.tile_w ? R.width - tx0 : R.tile_w, h = R.height - ty0 < R.tile_h ? R.height - ty0 : R.tile_h;
-                px += (uint64_t)w * h;
-            }
-            stats->samples = px * (uint64_t)(R.samples - R.sample_first) * (uint64_t)streams;
-            stats->closest_hit_queries = h_cnt[0]; stats->light_pdf_queries = h_cnt[1];
-            stats->node_visits = h_cnt[2]; stats->triangle_tests = h_cnt[3];
-        }
-        return RT_OK;
+        const size_t elems = rt_output_elems(p);
+        F.R.out_rgb = out_rgb; F.R.out_rgb8 = out_rgb8;
+        if (out_rgb && !out_dev) { HIP_CHECK(hipMalloc(&rgb_buf.p, elems * sizeof(float))); F.R.out_rgb = (float *)rgb_buf.p; }
+        if (out_rgb8 && !out_dev) { HIP_CHECK(hipMalloc(&rgb8_buf.p, elems)); F.R.out_rgb8 = (uint8_t *)rgb8_buf.p; }
+        launch_frame(scene, p, F, stream, stats != nullptr);
+        if (rgb_buf.p) HIP_CHECK(hipMemcpyAsync(out_rgb, rgb_buf.p, elems * sizeof(float), hipMemcpyDeviceToHost, stream));
+        if (rgb8_buf.p) HIP_CHECK(hipMemcpyAsync(out_rgb8, rgb8_buf.p, elems, hipMemcpyDeviceToHost, stream));
+        return collect_frame(scene, F, stream, stats, t0, who);
     } catch (const HipError &e) {
         return fail(RT_ERR_HIP, e.what());
     } catch (const std::exception &e) { // e.g. std::bad_alloc from the host-side vectors: nothing crosses the C boundary
@@ -1393,7 +892,7 @@ static bool accum_geometry(const rt_render_params *p, RenderView &R, uint32_t &n
     rt_render_params q = *p;
     q.samples = 1; // ignored here
     if (!resolve_tiles(&q, R, err)) return false;
-    if (R.ray_depth > (p->integrator == RT_INTEGRATOR_HW6 ? RT6_MAX_DEPTH : RT_MAX_DEPTH)) { err = "ray_depth above the integrator's limit"; return false; }
+    if (R.ray_depth > max_ray_depth[p->integrator]) { err = "ray_depth above the integrator's limit"; return false; }
     const uint64_t slots = (uint64_t)R.n_shard_tiles * (uint64_t)((R.tile_w >> 3) * (R.tile_h >> 3)) * 64u;
     if (slots >= 0x40000000ull) { err = "too many pixel slots"; return false; }
     n_pixslots = (uint32_t)slots;
@@ -1564,88 +1063,5 @@ int rt_accum_load(rt_accum *a, const void *blob, size_t size) {
         return fail(RT_ERR_HIP, e.what());
     }
 }
-
-int rt_unshard(const rt_render_params *p, const void *shard_buf, size_t elem_size, void *full_image) {
-    if (!p || !shard_buf || !full_image || (elem_size != 1 && elem_size != 4)) return fail(RT_ERR_INVALID_ARG, "rt_unshard: bad argument");
-    RenderView R{};
-    std::string err;
-    if (!resolve_tiles(p, R, err)) return fail(RT_ERR_INVALID_ARG, "rt_unshard: " + err);
-    const uint8_t *src = (const uint8_t *)shard_buf;
-    uint8_t *dst = (uint8_t *)full_image;
-    size_t px = 3 * elem_size;
-    if (R.shard_count <= 1) { memcpy(dst, src, (size_t)R.width * R.height * px); return RT_OK; }
-    for (uint32_t st = 0; st < R.n_shard_tiles; st++) {
-        uint32_t gt = (uint32_t)R.shard_index + st * (uint32_t)R.shard_count;
-        int tx0 = (int)(gt % (uint32_t)R.tiles_x) * R.tile_w, ty0 = (int)(gt / (uint32_t)R.tiles_x) * R.tile_h;
-        int w = R.width - tx0 < R.tile_w ? R.width - tx0 : R.tile_w, h = R.height - ty0 < R.tile_h ? R.height - ty0 : R.tile_h;
-        for (int ly = 0; ly < h; ly++)
-            memcpy(dst + ((size_t)(ty0 + ly) * R.width + tx0) * px, src + (((size_t)st * R.tile_h + ly) * R.tile_w) * px, (size_t)w * px);
-    }
-    return RT_OK;
-}
-
-// ---- host-side front-end ---------------------------------------------------------------------------
-int rt_load_gltf(const char *path, int flavor, rt_host_scene **out) {
-    if (!path || !out) return fail(RT_ERR_INVALID_ARG, "rt_load_gltf: null argument");
-    *out = nullptr;
-    try {
-        *out = load_gltf(path, flavor);
-        return RT_OK;
-    } catch (const std::exception &e) {
-        return fail(RT_ERR_PARSE, std::string("rt_load_gltf(") + path + "): " + e.what());
-    }
-}
-int rt_load_txt(const char *path, int flavor, rt_host_scene **out, int32_t *w, int32_t *h, int32_t *samples, int32_t *depth) {
-    if (!path || !out) return fail(RT_ERR_INVALID_ARG, "rt_load_txt: null argument");
-    *out = nullptr;
-    try {
-        *out = load_txt(path, flavor, w, h, samples, depth);
-        return RT_OK;
-    } catch (const std::exception &e) {
-        return fail(RT_ERR_PARSE, std::string("rt_load_txt(") + path + "): " + e.what());
-    }
-}
-int rt_host_scene_set_environment(rt_host_scene *hs, const char *image_path) {
-    if (!hs || !image_path) return fail(RT_ERR_INVALID_ARG, "rt_host_scene_set_environment: null argument");
-    try {
-        int w, h;
-        load_image_rgb8(image_path, w, h, hs->env_data);
-        hs->env = rt_image{w, h, nullptr};
-        hs->has_env = true;
-        hs->finalize();
-        return RT_OK;
-    } catch (const std::exception &e) {
-        return fail(RT_ERR_IO, e.what());
-    }
-}
-const rt_scene_desc *rt_host_scene_desc(const rt_host_scene *hs) { return hs ? &hs->desc : nullptr; }
-void rt_host_scene_free(rt_host_scene *hs) { delete hs; }
-
-int rt_write_ppm(const char *path, int32_t width, int32_t height, const uint8_t *rgb8) { // sceneio.cpp:383-385,397-401
-    if (!path || !rgb8 || width <= 0 || height <= 0) return fail(RT_ERR_INVALID_ARG, "rt_write_ppm: bad argument");
-    FILE *f = fopen(path, "wb");
-    if (!f) return fail(RT_ERR_IO, std::string("rt_write_ppm: cannot open ") + path);
-    fprintf(f, "P6\n%d %d\n255\n", width, height);
-    size_t n = (size_t)width * height * 3;
-    bool ok = fwrite(rgb8, 1, n, f) == n;
-    ok = (fclose(f) == 0) && ok;
-    return ok ? RT_OK : fail(RT_ERR_IO, std::string("rt_write_ppm: short write to ") + path);
-}
-int rt_decode_png(const char *path, int32_t *width, int32_t *height, uint8_t **rgb) {
-    if (!path || !width || !height || !rgb) return fail(RT_ERR_INVALID_ARG, "rt_decode_png: null argument");
-    try {
-        std::vector<uint8_t> px;
-        int w, h;
-        load_image_rgb8(path, w, h, px);
-        *rgb = (uint8_t *)malloc(px.size());
-        if (!*rgb) return fail(RT_ERR_IO, "rt_decode_png: out of memory");
-        memcpy(*rgb, px.data(), px.size());
-        *width = w; *height = h;
-        return RT_OK;
-    } catch (const std::exception &e) {
-        return fail(RT_ERR_IO, e.what());
-    }
-}
-void rt_free(void *p) { free(p); }
 
 } // extern "C"
