@@ -13,9 +13,10 @@
 //   * the stage a path waits for is one bit per path in an LDS bitmap (need_trace / need_light / need_shade / ...); a wave
 //     that wants work claims set bits with LDS atomics (one word per lane, rotating cursor: round-robin service, no
 //     capacity limit, no ring to overflow);
-//   * every wave picks a role when it is idle: closest-hit walker, light-sum walker or shader, by the populations of the
-//     bitmaps; walkers keep their lanes full by refilling idle lanes from the bitmap; a shader takes up to 64 paths,
-//     finishes their pending bounce, shades the new hit and sets the bits of what each path needs next;
+//   * every wave picks a role when it is idle (the scheduler loop of pt_run, the one kernel body of this file's kernel and of
+//     rt_persistent_hw6.h's): closest-hit walker, light-sum walker or shader, by the populations of the bitmaps; walkers keep
+//     their lanes full by refilling idle lanes from the bitmap; a shader takes up to 64 paths, finishes their pending bounce,
+//     shades the new hit and sets the bits of what each path needs next;
 //   * the walkers read four-wide nodes on a 16-bit grid (rt_types.h GpuNode4Q: two tree levels per 64-byte fetch, the ray in grid
 //     coordinates), park the leaves they meet for a common leaf phase, and leave what only a few lanes need (a light hit's pdf
 //     term, the record of a walk that has ended) for once per pass;
@@ -192,9 +193,10 @@ struct PtParams {
     float4 *trace_buf; uint32_t trace_cap; int32_t trace_pixel;
 };
 
-// COUNT builds only: where a wave's time goes (shader-clock cycles per role) and how full its walker iterations are ([2]: closest-hit | light walker)
+// COUNT builds only: where a wave's time goes (shader-clock cycles per role, the slots of CNT_ROLE_TIME: closest-hit walks, light walks, shading,
+// rare roles, idle) and how full its walker iterations are ([2]: closest-hit | light walker)
 struct PtProf {
-    unsigned long long t_trace = 0, t_light = 0, t_shade = 0, t_exact = 0, t_idle = 0;
+    unsigned long long t_role[5] = {0, 0, 0, 0, 0};
     unsigned long long iters[2] = {0, 0}, lane_iters[2] = {0, 0}, stints = 0, shade_batches = 0, shade_items = 0;
     // where a walker's wave time goes (counting build): [0] hand-off and refill, [1] inner nodes, [2] leaves; tests / lane-tests of the leaf loops; light hits
     unsigned long long t_part[2][3] = {{0, 0, 0}, {0, 0, 0}}, leaf_iters[2] = {0, 0}, leaf_lane_iters[2] = {0, 0}, light_hits = 0, light_tests = 0; // the last two per lane
@@ -472,11 +474,16 @@ RT_DEV void pt_walk_stint(WK &w, SH &sh, const PtParams &P, PtWave &wv, uint32_t
     }
 }
 
+// A wave-uniform pointer in a scalar register pair of its own, for what a walker reads in its innermost loops: taken straight from the kernel arguments it
+// sits in a group of four registers that the allocator keeps or spills as a whole.  Without the copies (profiles/r09_scheduler_refactor.txt) the hw8 node
+// loops reload the pointer with 4 v_readlane per step and the light leaf loop reloads 30 SGPRs per iteration instead of 15.
+template <class T> RT_DEV const T *pt_own_pointer(const T *p) { asm volatile("" : "+s"(p)); return p; }
 // ---- closest-hit walker: near-first, tie -> lowest figure index ---------------------------------------------------------------------
 struct PtTraceWalk {
     typedef PtTraceQueue Queue;
     static constexpr uint32_t COST_NODE = PT_COST_TRACE_NODE, COST_TEST = PT_COST_TRACE_TRI;
     const SceneView &S; const WfView &W; PtShared &sh; const PtParams &P; uint32_t (*stack)[64];
+    const GpuNode4Q *nodes = pt_own_pointer(S.nodes4);
     const int lane = threadIdx.x & 63;
     F3 o = f3(0.f, 0.f, 0.f), d = f3(0.f, 0.f, 1.f);
     RayGrid ray = RT_GRID_RAY_IDLE; // idle lanes: never used
@@ -494,7 +501,7 @@ struct PtTraceWalk {
         h_ray = S.exact_boxes ? pt_look_behind_abs(d, S.box_c2x) : 0.f;
         hit = WF_MISS; best_t = RT_T_MAX; cull_t = RT_T_MAX; t2 = 2.f * RT_T_MAX; best_u = 0.f; best_v = 0.f;
     }
-    RT_DEV int step(uint32_t &cur, int &sp) { return pt_wide_step_nearest(S.nodes4, ray, cull_t, stack, lane, sp, P8_STACK, cur); }
+    RT_DEV int step(uint32_t &cur, int &sp) { return pt_wide_step_nearest(nodes, ray, cull_t, stack, lane, sp, P8_STACK, cur); }
     // The column is full (a walk holds up to three entries per level of a tree of up to P8_STACK / 2 levels; this takes a ray that
     // grazes many boxes: triangle soups).  The walk says so — no hit has a negative t — and the exact role walks the query with a
     // stack of its own (pt_exact_batch).
@@ -526,6 +533,8 @@ template <bool COUNT> struct PtLightWalk {
     typedef PtLightQueue<PT_Q_XLIGHT> Queue;
     static constexpr uint32_t COST_NODE = PT_COST_LIGHT_NODE, COST_TEST = PT_COST_LIGHT_TEST;
     const SceneView &S; const WfView &W; PtShared &sh; const PtParams &P; uint32_t (*stack)[64]; PtProf &prof;
+    const GpuNode4Q *nodes = pt_own_pointer(S.light_walk_nodes4);
+    const LightRec *lights = pt_own_pointer(S.lights_walk);
     const int lane = threadIdx.x & 63;
     bool overflow = false; // the exact role sums this query
     int k = 0;             // hits so far
@@ -542,11 +551,11 @@ template <bool COUNT> struct PtLightWalk {
         ray = make_ray_grid(S.grid, o, d);
         k = 0; overflow = false;
     }
-    RT_DEV int step(uint32_t &cur, int &sp) { return pt_wide_step_all(S.light_walk_nodes4, ray, stack, lane, sp, P8_STACK - 2 * k - 1, cur); } // the hits sit at the column's top
+    RT_DEV int step(uint32_t &cur, int &sp) { return pt_wide_step_all(nodes, ray, stack, lane, sp, P8_STACK - 2 * k - 1, cur); } // the hits sit at the column's top
     RT_DEV void full() { overflow = true; } // no room beside the hits
     RT_DEV void take(Leaf &lf, int sp) { // the held hit joins the lane's hits
         bool robust;
-        const float term = pt_light_pdf_hit(S, S.lights_walk + lf.h_i, o, d, lf.h_t, lf.h_u, lf.h_v, lf.h_in, robust);
+        const float term = pt_light_pdf_hit(S, lights + lf.h_i, o, d, lf.h_t, lf.h_u, lf.h_v, lf.h_in, robust);
         if (COUNT && term != 0.f) prof.light_hits++;
         if (term != 0.f) { // (a hit whose term is exactly 0 adds nothing, like a miss)
             if (!robust || k >= WF_MAX_LIGHT_HITS || sp + 2 * k + 2 >= P8_STACK) overflow = true;
@@ -565,7 +574,7 @@ template <bool COUNT> struct PtLightWalk {
     RT_DEV bool test(uint32_t i, int sp, Leaf &lf) {
         bool last, inside; uint32_t li; float t, u, v;
         if (COUNT) prof.light_tests++;
-        if (pt_light_test(S.lights_walk + i, o, d, last, li, t, u, v, inside)) {
+        if (pt_light_test(lights + i, o, d, last, li, t, u, v, inside)) {
             if (lf.held) take(lf, sp); // a second hit in this phase
             lf.held = true; lf.h_i = i; lf.h_li = li; lf.h_t = t; lf.h_u = u; lf.h_v = v; lf.h_in = inside;
         }
@@ -828,14 +837,14 @@ RT_DEV void pt_exact_batch(const SceneView &S, const WfView &W, SH &sh, PtWave &
 // What a workgroup of THREADS threads does first, in this kernel and in rt_persistent_hw6.h's: its share of the pass's groups, the wave's
 // state, cleared queues and tables in LDS (SH: PtShared, P6Shared), the debug stamp.  False: the workgroup owns no path and leaves.
 template <int THREADS, class SH>
-RT_DEV bool pt_enter(SH &sh, const PtParams &P, PtWave &wv, uint32_t &n_local_groups) {
+RT_DEV bool pt_enter(SH &sh, const PtParams &P, PtWave &wv) {
     const uint32_t tid = threadIdx.x;
     const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6));
     wv.n_blocks = gridDim.x; wv.block = blockIdx.x;
     wv.front_first = P.front_first != 0u;
     const uint32_t first_group = P.group_ofs ? P.group_ofs[wv.block] : 0u;
-    n_local_groups = P.group_ofs ? P.group_ofs[wv.block + 1u] - first_group
-                                 : (P.n_groups > wv.block ? (P.n_groups - wv.block + wv.n_blocks - 1u) / wv.n_blocks : 0u);
+    const uint32_t n_local_groups = P.group_ofs ? P.group_ofs[wv.block + 1u] - first_group
+                                                : (P.n_groups > wv.block ? (P.n_groups - wv.block + wv.n_blocks - 1u) / wv.n_blocks : 0u);
     wv.n_local = n_local_groups << P.group_shift;
     wv.nw = (wv.n_local + 31u) >> 5;
     if (wv.n_local == 0u) return false;
@@ -851,66 +860,65 @@ RT_DEV bool pt_enter(SH &sh, const PtParams &P, PtWave &wv, uint32_t &n_local_gr
 // ... and last: the work booked for each of its groups goes back to the host (every wave leaves the scheduler loop once the workgroup's
 // pixels are done, or at the deadline)
 template <int THREADS, class SH>
-RT_DEV void pt_leave(SH &sh, const PtParams &P, uint32_t n_local_groups) {
+RT_DEV void pt_leave(SH &sh, const PtParams &P, const PtWave &wv) {
     if (!P.group_cost) return;
     __syncthreads();
+    const uint32_t n_local_groups = wv.n_local >> P.group_shift;
     for (uint32_t i = threadIdx.x; i < n_local_groups; i += THREADS) P.group_cost[sh.groups[i]] = sh.cost[i];
 }
 
-// __launch_bounds__(256, 5): five waves per SIMD, i.e. a budget of 96 VGPRs.  Every role fits it without scratch; the scheduler's own
-// state is wave-uniform and lives in SGPRs (pt_count / readfirstlane).
-template <bool COUNT, int FEAT>
-__global__ __launch_bounds__(P8_THREADS, P8_PER_CU) void pt_persistent_kernel(SceneView S, RenderView R, WfView W, PtParams P) {
-    __shared__ PtShared sh;
+// A wave-uniform kernel argument compared where it is used: hoisted out of the scheduler loop, each compare of PtParams::prio holds a register pair across
+// every role of the loop, and the walkers need them more (profiles/r09_scheduler_refactor.txt: reloads in the hw6 kernel's largest inner loop 106 -> 74).
+RT_DEV int pt_here(int v) { asm volatile("" : "+s"(v)); return v; }
+// ---- the kernel body: seeding, the scheduler loop and the epilogue, once for this file's kernel and rt_persistent_hw6.h's -----------------
+// What the shader role decided for the path of one lane (all false / 0 for a lane without a path).
+struct PtShaded {
+    bool trace = false;   // the record holds a new ray that wants its closest hit: PT_BIT_T is outstanding ...
+    bool light = false;   // ... and its light-pdf sum is walked beside it: PT_BIT_L
+    bool xtrace = false;  // the closest hit is the exact role's (PT_Q_XTRACE): the hit the gate refused, or, with `trace`, the new ray's instead of PT_Q_TRACE
+    bool done = false;    // the path is finished, or parked for the next phase of the frame
+    uint32_t cost = 0;    // what the step adds to the work booked for the path's group (PtShared::cost); 0 for a refused hit
+};
+// What differs between the two kernels is a policy RL, the kernel's roles (PtRoles below, P6Roles of rt_persistent_hw6.h): a struct that
+// holds the kernel's arguments (S, R, W, P), its LDS block `sh`, the wave's stack area `stack`, its own query counts, and says
+//   THREADS, COUNT, SLOTS, DEFER    the workgroup's size; the counting build; the two measured choices of pt_walk_stint
+//   trace_walk(), light_walk(prof)  the kernel's two walker policies
+//   seed(slot, gslot, x, y, rng, sum)  writes r0..r3 of a fresh path: its first camera ray, drawn from `rng`, and the pixel sum
+//   resumed_sample(slot)            the sample count in the packed word of a record that carries on (PtParams::resume)
+//   seed_wire(slot)                 whether the record's camera ray belongs to the exact role from the start (a tripwire)
+//   rare(wv)                        runs one batch of the kernel's rare roles if any is queued, and says whether it did
+//   shade(got, n_light, n_nodes, prof)  one shader step of path `got` (PT_NONE: none), between the loop's acquire and release: all that is the integrator's
+//   flush(lane, prof)               the kernel's own counters at the exit
+template <class RL>
+RT_DEV void pt_run(RL &rl) {
+    constexpr bool COUNT = RL::COUNT;
+    auto &sh = rl.sh;
+    const RenderView &R = rl.R;
+    const PtParams &P = rl.P;
     const uint32_t tid = threadIdx.x, lane = tid & 63u;
     const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6));
     PtWave wv;
-    uint32_t n_local_groups;
-    if (!pt_enter<P8_THREADS>(sh, P, wv, n_local_groups)) return;
+    if (!pt_enter<RL::THREADS>(sh, P, wv)) return;
 
     // ---- init: seed every pixel of this workgroup, first camera ray (wf_init_kernel of rt_wavefront.h) -----------------------
-    for (uint32_t base = 0; base < wv.n_local; base += P8_THREADS) {
+    for (uint32_t base = 0; base < wv.n_local; base += RL::THREADS) {
         const uint32_t l = base + tid;
-        bool started = false;
+        bool started = false, wire = false;
         if (l < wv.n_local) {
-            const uint32_t slot = pt_slot(sh, l), gslot = slot + W.slot_base;
-            int x, y; bool inside; size_t out_index;
-            wf_slot_to_pixel(R, gslot, x, y, inside, out_index);
-            if (!inside) { // padding of a border tile in the compact shard layout
-                if (R.shard_count > 1 && (R.streams <= 1 || gslot < R.n_pixslots)) {
-                    if (R.out_rgb) { R.out_rgb[3 * out_index] = 0.f; R.out_rgb[3 * out_index + 1] = 0.f; R.out_rgb[3 * out_index + 2] = 0.f; }
-                    if (R.out_rgb8) { R.out_rgb8[3 * out_index] = 0; R.out_rgb8[3 * out_index + 1] = 0; R.out_rgb8[3 * out_index + 2] = 0; }
-                }
-            } else if (P.resume) {
+            const uint32_t slot = pt_slot(sh, l), gslot = slot + rl.W.slot_base;
+            int x, y; Rng rng; F3 sum;
+            if (wf_seed_record(R, gslot, !P.resume, x, y, rng, sum)) {
                 // a later phase of the frame: the record holds the pixel sum, the random stream and the parked camera ray
-                const uint32_t packed = __float_as_uint(reinterpret_cast<const float *>(wf_rec(W, slot) + 3)[3]);
-                started = ((packed >> 6) & WF_SAMPLE_MASK) < (uint32_t)R.samples;
-                if (started) atomicOr(&sh.pending[l >> 4], PT_BIT_T << ((l & 15u) * 2u));
-            } else {
-                Rng rng;
-                F3 sum = f3(0.f, 0.f, 0.f);
-                if (R.accum) accum_enter(R, gslot, rng, sum);   // a slice of a resumable render: carry on at sample R.sample_first
-                else rng_seed(rng, (uint32_t)(y * R.width + x) + (R.streams > 1 ? (gslot / R.n_pixslots) * R.seed_stride : 0u)); // sceneio.cpp:389-391
-                if (R.sample_seeds) wf_sample_seed(R, rng, gslot, x, y, 0u);
-                F3 o, d;
-                wf_camera_ray(S, R, rng, x, y, o, d);
-                float4 *r = wf_rec(W, slot);
-                r[0] = make_float4(o.x, o.y, o.z, d.x);
-                r[1] = make_float4(d.y, d.z, __uint_as_float(rng.x), rng.saved);
-                r[2] = make_float4(0.f, 0.f, 0.f, 0.f);
-                r[3] = make_float4(sum.x, sum.y, sum.z, __uint_as_float(wf_pack(0, rng.has_saved, R.accum ? (uint32_t)R.sample_first : 0u)));
-                atomicOr(&sh.pending[l >> 4], PT_BIT_T << ((l & 15u) * 2u));
-                started = true;
+                if (P.resume) started = rl.resumed_sample(slot) < (uint32_t)R.samples;
+                else { rl.seed(slot, gslot, x, y, rng, sum); started = true; }
+                if (started) {
+                    atomicOr(&sh.pending[l >> 4], PT_BIT_T << ((l & 15u) * 2u));
+                    wire = rl.seed_wire(slot);
+                }
             }
         }
         const unsigned long long m = pt_ballot(started);
         if (m && lane == 0) atomicAdd(&sh.cnt[PT_N_LIVE], (int)__popcll(m));
-        bool wire = false;
-        if (S.n_tripwire_groups && started) {
-            const float4 *nr = wf_rec(W, pt_slot(sh, l));
-            const float4 n0 = nr[0], n1 = nr[1];
-            wire = pt_tripwire(S, f3(n0.x, n0.y, n0.z), f3(n0.w, n1.x, n1.y));
-        }
         pt_push(sh, PT_Q_TRACE, l, started && !wire);
         pt_push(sh, PT_Q_XTRACE, l, wire);
     }
@@ -919,101 +927,61 @@ __global__ __launch_bounds__(P8_THREADS, P8_PER_CU) void pt_persistent_kernel(Sc
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
 
     // ---- scheduler: every wave picks a role whenever it is idle ----------------------------------------------------------------
-    uint32_t(*stack)[64] = sh.stack[wave];
+    uint32_t(*stack)[64] = rl.stack;
     const int shade_thr = P.shade_thr0 + (int)wave * P.shade_thr_step;
-    uint32_t n_closest = 0, n_light = 0, n_xtrace = 0, n_xlight = 0, n_discarded = 0; // per wave and launch: well below 2^32
+    uint32_t n_closest = 0, n_light = 0; // per wave and launch: well below 2^32
     unsigned long long n_nodes = 0, n_tris = 0;
     uint32_t idle_spins = 0;
     int gave_up = 0; // 1: the launch ran into its deadline; 2: the workgroup waited in vain for a path to come back (a lost path: a bug)
     PtProf prof;
-    unsigned long long t_mark = COUNT ? __builtin_amdgcn_s_memtime() : 0ull;
-    auto lap = [&](unsigned long long &acc) { if (COUNT) { const unsigned long long t = __builtin_amdgcn_s_memtime(); acc += t - t_mark; t_mark = t; } };
-    const unsigned long long t_start = __builtin_amdgcn_s_memrealtime();
+    PtLap<COUNT> clk; // the role clock of the counting build (prof.t_role)
+    const unsigned long long t_start = __builtin_amdgcn_s_memrealtime(); // the deadline's clock: deadline_ticks are 100 MHz ticks
     for (;;) {
         if (__builtin_amdgcn_s_memrealtime() - t_start > P.deadline_ticks) { gave_up = 1; break; } // safety net: never hang the GPU; the host reports the error
         const int ns = pt_count(&sh.cnt[PT_Q_SHADE]), nt = pt_count(&sh.cnt[PT_Q_TRACE]), nl = pt_count(&sh.cnt[PT_Q_LIGHT]);
-        const int nx = pt_count(&sh.cnt[PT_Q_XLIGHT]) + pt_count(&sh.cnt[PT_Q_XTRACE]);
-        if (nx > 0) {
-            pt_exact_batch(S, W, sh, wv, &stack[0][0], n_xlight, n_xtrace);
+        if (rl.rare(wv)) {
             idle_spins = 0;
-            lap(prof.t_exact);
+            clk.lap(prof.t_role[3]);
             continue;
         }
         // shaders first when a full wave of paths waits (or when it is all there is to do)
         if (ns >= P.shade_min || (ns > 0 && nt + nl == 0)) {
             const uint32_t got = pt_pop(sh.need[PT_Q_SHADE], &sh.cnt[PT_Q_SHADE], wv.nw, wv.cur[PT_Q_SHADE], true, wv.front_first);
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-            if (P.prio == 2) __builtin_amdgcn_s_setprio(2);
-            int todo = 0;
-            bool discarded = false;
-            if (COUNT && P.trace_buf && got != PT_NONE) {
-                const uint32_t tslot = pt_slot(sh, got);
-                int tx, ty; bool tin; size_t toi;
-                wf_slot_to_pixel(R, tslot + W.slot_base, tx, ty, tin, toi);
-                if (tin && ty * R.width + tx == P.trace_pixel) {
-                    const float4 *tr = wf_rec(W, tslot);
-                    const uint32_t k = atomicAdd(reinterpret_cast<uint32_t *>(P.trace_buf), 1u);
-                    if (4u * k + 5u <= P.trace_cap) for (int q = 0; q < 4; q++) P.trace_buf[1 + 4 * k + q] = tr[q];
-                }
-            }
-            if (got != PT_NONE) { PtPark pk; pk.p = (PtLdsWord)&stack[0][lane]; todo = pt_shade_lean<FEAT>(S, R, W, pt_slot(sh, got), pk, discarded); }
-            n_discarded += __popcll(pt_ballot(discarded));
-            const bool next = got != PT_NONE && todo != PT_SHADE_EXACT && (todo & WF_NEXT_TRACE), with_light = next && (todo & WF_NEXT_LIGHT);
-            bool wire = false;    // the new ray pierces a tripwire (rt_exact.h): its closest hit is the exact role's
-            bool settled = false; // its light sum is settled here (PT_LIGHT_SETTLE): the walk would test no light
-            int settle_steps = 0; // the node steps that decision took (the cost the light walker would have booked)
-            if (next && (S.n_tripwire_groups || ((COUNT || PT_LIGHT_SETTLE) && with_light))) {
-                const float4 *nr = wf_rec(W, pt_slot(sh, got));
-                const float4 n0 = nr[0], n1 = nr[1];
-                const F3 o = f3(n0.x, n0.y, n0.z), d = f3(n0.w, n1.x, n1.y);
-                if (S.n_tripwire_groups) wire = pt_tripwire(S, o, d);
-                if ((COUNT || PT_LIGHT_SETTLE) && with_light) { // the counting build classifies every sum, whatever it settles
-                    const int reach = pt_light_reach<COUNT ? 2 : PT_LIGHT_SETTLE>(S, make_ray_grid(S.grid, o, d), settle_steps);
-                    if (COUNT) { prof.light_reach[0] += reach == 0; prof.light_reach[1] += reach == 1; }
-                    settled = reach < PT_LIGHT_SETTLE;
-                    if (settled) { // what the walker's end() does with no hit, before the release below publishes the path
-                        const int depth = (int)(__float_as_uint(reinterpret_cast<const float *>(nr + 3)[3]) & 15u);
-                        float *pdf = reinterpret_cast<float *>(wf_entry(W, pt_slot(sh, got), depth)) + 3;
-                        *pdf = *pdf + 0.f / S.n_lights_f;                      // distributions.h:123,273 (+0.f: a -0 sum becomes +0)
-                    }
-                }
-            }
-            n_light += __popcll(pt_ballot(settled)); // a settled sum is still a light-pdf query of the algorithm
+            if (pt_here(P.prio) == 2) __builtin_amdgcn_s_setprio(2);
+            const PtShaded s = rl.shade(got, n_light, n_nodes, prof);
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-            const bool walk_light = with_light && !settled;
-            if (next) atomicOr(&sh.pending[got >> 4], (PT_BIT_T | (walk_light ? PT_BIT_L : 0u)) << ((got & 15u) * 2u));
-            pt_push(sh, PT_Q_TRACE, got, next && !wire);
-            pt_push(sh, PT_Q_LIGHT, got, walk_light);
-            pt_push(sh, PT_Q_XTRACE, got, (got != PT_NONE && todo == PT_SHADE_EXACT) || wire);
-            if (got != PT_NONE && todo != PT_SHADE_EXACT)
-                atomicAdd(&sh.cost[got >> pt_gshift(sh)], (uint32_t)PT_COST_SHADE + (settled ? PT_COST_LIGHT_NODE * (uint32_t)settle_steps : 0u));
-            if (COUNT && settled) n_nodes += (unsigned long long)settle_steps;
-            const unsigned long long done = pt_ballot(got != PT_NONE && (todo == 0 || todo == WF_PARKED)); // finished, or parked for the next phase
+            if (s.trace || s.light) atomicOr(&sh.pending[got >> 4], ((s.trace ? PT_BIT_T : 0u) | (s.light ? PT_BIT_L : 0u)) << ((got & 15u) * 2u));
+            pt_push(sh, PT_Q_TRACE, got, s.trace && !s.xtrace); // (a refused hit sets no pending bit and takes no other push: where its push stands does not matter)
+            pt_push(sh, PT_Q_LIGHT, got, s.light);
+            pt_push(sh, PT_Q_XTRACE, got, s.xtrace);
+            if (s.cost) atomicAdd(&sh.cost[got >> pt_gshift(sh)], s.cost);
+            const unsigned long long done = pt_ballot(s.done);
             if (done && lane == 0) atomicSub(&sh.cnt[PT_N_LIVE], (int)__popcll(done));
             idle_spins = 0;
-            if (P.prio == 2) __builtin_amdgcn_s_setprio(0);
-            if (COUNT) { prof.shade_batches++; prof.shade_items += __popcll(pt_ballot(got != PT_NONE)); }
-            lap(prof.t_shade);
+            if (pt_here(P.prio) == 2) __builtin_amdgcn_s_setprio(0);
+            if (COUNT) { prof.shade_batches++; prof.shade_items += __popcll(pt_ballot(got != PT_NONE)); } // reported by hw8's flush only (CNT_P8_*)
+            clk.lap(prof.t_role[2]);
             continue;
         }
         if (nt + nl > 0) {
             // walkers: the kind whose backlog per walking wave (weighted by the cost of a query) is larger
             const long long wt = (long long)nt * P.cost_t * (pt_count(&sh.cnt[PT_W_LIGHT]) + 1), wl = (long long)nl * P.cost_l * (pt_count(&sh.cnt[PT_W_TRACE]) + 1);
-            if (P.prio == 1) __builtin_amdgcn_s_setprio(2);
+            if (pt_here(P.prio) == 1) __builtin_amdgcn_s_setprio(2);
             if (nl == 0 || (nt > 0 && wt >= wl)) {
                 if (lane == 0) atomicAdd(&sh.cnt[PT_W_TRACE], 1);
-                PtTraceWalk walk{S, W, sh, P, stack}; // hw8 / hw7: three parked leaves, deferred endings (pt_walk_stint)
-                pt_walk_stint<3, true, COUNT>(walk, sh, P, wv, stack, shade_thr, n_closest, n_nodes, n_tris, prof);
+                auto walk = rl.trace_walk();
+                pt_walk_stint<RL::SLOTS, RL::DEFER, COUNT>(walk, sh, P, wv, stack, shade_thr, n_closest, n_nodes, n_tris, prof);
                 if (lane == 0) atomicSub(&sh.cnt[PT_W_TRACE], 1);
-                lap(prof.t_trace);
+                clk.lap(prof.t_role[0]);
             } else {
                 if (lane == 0) atomicAdd(&sh.cnt[PT_W_LIGHT], 1);
-                PtLightWalk<COUNT> walk{S, W, sh, P, stack, prof};
-                pt_walk_stint<3, true, COUNT>(walk, sh, P, wv, stack, shade_thr, n_light, n_nodes, n_tris, prof);
+                auto walk = rl.light_walk(prof);
+                pt_walk_stint<RL::SLOTS, RL::DEFER, COUNT>(walk, sh, P, wv, stack, shade_thr, n_light, n_nodes, n_tris, prof);
                 if (lane == 0) atomicSub(&sh.cnt[PT_W_LIGHT], 1);
-                lap(prof.t_light);
+                clk.lap(prof.t_role[1]);
             }
-            if (P.prio == 1) __builtin_amdgcn_s_setprio(0);
+            if (pt_here(P.prio) == 1) __builtin_amdgcn_s_setprio(0);
             idle_spins = 0;
             if (COUNT) prof.stints++;
             continue;
@@ -1021,25 +989,114 @@ __global__ __launch_bounds__(P8_THREADS, P8_PER_CU) void pt_persistent_kernel(Sc
         if (pt_count(&sh.cnt[PT_N_LIVE]) <= 0) break;
         // paths are in flight in other waves' registers: wait for them
         __builtin_amdgcn_s_sleep(8);
-        lap(prof.t_idle);
+        clk.lap(prof.t_role[4]);
         if (++idle_spins > (1u << 24)) { gave_up = 2; break; } // safety net (seconds): never hang the GPU on a lost path; the host reports it
     }
     if (gave_up && lane == 0 && P.counters) atomicAdd(&P.counters[gave_up == 1 ? CNT_DEADLINE : CNT_LOST_PATH], 1ull);
-    pt_leave<P8_THREADS>(sh, P, n_local_groups);
-    if (lane == 0 && P.counters) {
-        if (n_closest) atomicAdd(&P.counters[CNT_CLOSEST], (unsigned long long)n_closest);
-        if (n_light) atomicAdd(&P.counters[CNT_LIGHT], (unsigned long long)n_light);
-        if (n_discarded) atomicAdd(&P.counters[CNT_DISCARDED], (unsigned long long)n_discarded);
-        if (n_xtrace) atomicAdd(&P.counters[CNT_EXACT_CLOSEST], (unsigned long long)n_xtrace);
-        if (n_xlight) atomicAdd(&P.counters[CNT_EXACT_LIGHT], (unsigned long long)n_xlight);
+    pt_leave<RL::THREADS>(sh, P, wv);
+    if (P.counters) {
+        if (lane == 0 && n_closest) atomicAdd(&P.counters[CNT_CLOSEST], (unsigned long long)n_closest);
+        if (lane == 0 && n_light) atomicAdd(&P.counters[CNT_LIGHT], (unsigned long long)n_light);
+        if (COUNT) { // node visits and tests are counted per lane, the role times per wave
+            atomicAdd(&P.counters[CNT_NODE_VISITS], n_nodes); atomicAdd(&P.counters[CNT_TRI_TESTS], n_tris);
+            if (lane == 0) for (int i = 0; i < 5; i++) atomicAdd(&P.counters[CNT_ROLE_TIME + i], prof.t_role[i]);
+        }
+        rl.flush(lane, prof);
     }
-    if (COUNT && P.counters) {
-        atomicAdd(&P.counters[CNT_NODE_VISITS], n_nodes); atomicAdd(&P.counters[CNT_TRI_TESTS], n_tris);
+    if (P.debug && lane == 0) atomicMax(&P.debug[3 * blockIdx.x + 1], __builtin_amdgcn_s_memrealtime());
+}
+
+// The roles of the hw8 / hw7 kernel.  Its rare role is the exact role (pt_exact_batch); its shader also keeps rays that cross a tripwire
+// away from the walkers and settles the light sums whose walk would test no light (PT_LIGHT_SETTLE).
+template <bool COUNT_, int FEAT>
+struct PtRoles {
+    static constexpr bool COUNT = COUNT_;
+    static constexpr int THREADS = P8_THREADS;
+    static constexpr int SLOTS = 3;      // three parked leaves, deferred endings (pt_walk_stint)
+    static constexpr bool DEFER = true;
+    const SceneView &S; const RenderView &R; const WfView &W; PtShared &sh; const PtParams &P;
+    uint32_t (*stack)[64] = sh.stack[__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6))];
+    uint32_t n_xtrace = 0, n_xlight = 0, n_discarded = 0; // per wave and launch: well below 2^32
+    RT_DEV PtTraceWalk trace_walk() { return PtTraceWalk{S, W, sh, P, stack}; }
+    RT_DEV PtLightWalk<COUNT> light_walk(PtProf &prof) { return PtLightWalk<COUNT>{S, W, sh, P, stack, prof}; }
+    RT_DEV void seed(uint32_t slot, uint32_t gslot, int x, int y, Rng &rng, F3 sum) {
+        if (R.sample_seeds) wf_sample_seed(R, rng, gslot, x, y, 0u);
+        F3 o, d;
+        wf_camera_ray(S, R, rng, x, y, o, d);
+        float4 *r = wf_rec(W, slot);
+        r[0] = make_float4(o.x, o.y, o.z, d.x);
+        r[1] = make_float4(d.y, d.z, __uint_as_float(rng.x), rng.saved);
+        r[2] = make_float4(0.f, 0.f, 0.f, 0.f);
+        r[3] = make_float4(sum.x, sum.y, sum.z, __uint_as_float(wf_pack(0, rng.has_saved, R.accum ? (uint32_t)R.sample_first : 0u)));
+    }
+    RT_DEV uint32_t resumed_sample(uint32_t slot) { return (__float_as_uint(reinterpret_cast<const float *>(wf_rec(W, slot) + 3)[3]) >> 6) & WF_SAMPLE_MASK; }
+    RT_DEV bool seed_wire(uint32_t slot) { // the record's ray pierces a tripwire (rt_exact.h): its closest hit is the exact role's
+        if (!S.n_tripwire_groups) return false;
+        const float4 *nr = wf_rec(W, slot);
+        const float4 n0 = nr[0], n1 = nr[1];
+        return pt_tripwire(S, f3(n0.x, n0.y, n0.z), f3(n0.w, n1.x, n1.y));
+    }
+    RT_DEV bool rare(PtWave &wv) {
+        const bool queued = pt_count(&sh.cnt[PT_Q_XLIGHT]) + pt_count(&sh.cnt[PT_Q_XTRACE]) > 0;
+        if (queued) pt_exact_batch(S, W, sh, wv, &stack[0][0], n_xlight, n_xtrace);
+        return queued; // decided before the batch's divergent code: the loop's branch on it stays a scalar one
+    }
+    RT_DEV PtShaded shade(uint32_t got, uint32_t &n_light, unsigned long long &n_nodes, PtProf &prof) {
+        const uint32_t lane = threadIdx.x & 63u;
+        int todo = 0;
+        bool discarded = false;
+        if (COUNT && P.trace_buf && got != PT_NONE) {
+            const uint32_t tslot = pt_slot(sh, got);
+            int tx, ty; bool tin; size_t toi;
+            wf_slot_to_pixel(R, tslot + W.slot_base, tx, ty, tin, toi);
+            if (tin && ty * R.width + tx == P.trace_pixel) {
+                const float4 *tr = wf_rec(W, tslot);
+                const uint32_t k = atomicAdd(reinterpret_cast<uint32_t *>(P.trace_buf), 1u);
+                if (4u * k + 5u <= P.trace_cap) for (int q = 0; q < 4; q++) P.trace_buf[1 + 4 * k + q] = tr[q];
+            }
+        }
+        if (got != PT_NONE) { PtPark pk; pk.p = (PtLdsWord)&stack[0][lane]; todo = pt_shade_lean<FEAT>(S, R, W, pt_slot(sh, got), pk, discarded); }
+        n_discarded += __popcll(pt_ballot(discarded));
+        const bool next = got != PT_NONE && todo != PT_SHADE_EXACT && (todo & WF_NEXT_TRACE), with_light = next && (todo & WF_NEXT_LIGHT);
+        bool wire = false;    // the new ray pierces a tripwire (rt_exact.h): its closest hit is the exact role's
+        bool settled = false; // its light sum is settled here (PT_LIGHT_SETTLE): the walk would test no light
+        int settle_steps = 0; // the node steps that decision took (the cost the light walker would have booked)
+        if (next && (S.n_tripwire_groups || ((COUNT || PT_LIGHT_SETTLE) && with_light))) {
+            const float4 *nr = wf_rec(W, pt_slot(sh, got));
+            const float4 n0 = nr[0], n1 = nr[1];
+            const F3 o = f3(n0.x, n0.y, n0.z), d = f3(n0.w, n1.x, n1.y);
+            if (S.n_tripwire_groups) wire = pt_tripwire(S, o, d);
+            if ((COUNT || PT_LIGHT_SETTLE) && with_light) { // the counting build classifies every sum, whatever it settles
+                const int reach = pt_light_reach<COUNT ? 2 : PT_LIGHT_SETTLE>(S, make_ray_grid(S.grid, o, d), settle_steps);
+                if (COUNT) { prof.light_reach[0] += reach == 0; prof.light_reach[1] += reach == 1; }
+                settled = reach < PT_LIGHT_SETTLE;
+                if (settled) { // what the walker's end() does with no hit, before the loop's release publishes the path
+                    const int depth = (int)(__float_as_uint(reinterpret_cast<const float *>(nr + 3)[3]) & 15u);
+                    float *pdf = reinterpret_cast<float *>(wf_entry(W, pt_slot(sh, got), depth)) + 3;
+                    *pdf = *pdf + 0.f / S.n_lights_f;                      // distributions.h:123,273 (+0.f: a -0 sum becomes +0)
+                }
+            }
+        }
+        n_light += __popcll(pt_ballot(settled)); // a settled sum is still a light-pdf query of the algorithm
+        if (COUNT && settled) n_nodes += (unsigned long long)settle_steps;
+        PtShaded s;
+        s.trace = next;
+        s.light = with_light && !settled;
+        s.xtrace = (got != PT_NONE && todo == PT_SHADE_EXACT) || wire;
+        s.done = got != PT_NONE && (todo == 0 || todo == WF_PARKED); // finished, or parked for the next phase
+        if (got != PT_NONE && todo != PT_SHADE_EXACT) s.cost = (uint32_t)PT_COST_SHADE + (settled ? PT_COST_LIGHT_NODE * (uint32_t)settle_steps : 0u);
+        return s;
+    }
+    RT_DEV void flush(uint32_t lane, const PtProf &prof) {
+        if (lane == 0) {
+            if (n_discarded) atomicAdd(&P.counters[CNT_DISCARDED], (unsigned long long)n_discarded);
+            if (n_xtrace) atomicAdd(&P.counters[CNT_EXACT_CLOSEST], (unsigned long long)n_xtrace);
+            if (n_xlight) atomicAdd(&P.counters[CNT_EXACT_LIGHT], (unsigned long long)n_xlight);
+        }
+        if (!COUNT) return;
         atomicAdd(&P.counters[CNT_P8_LIGHT_HITS], prof.light_hits); atomicAdd(&P.counters[CNT_P8_LIGHT_TESTS], prof.light_tests);
         atomicAdd(&P.counters[CNT_P8_LIGHT_REACH], prof.light_reach[0]); atomicAdd(&P.counters[CNT_P8_LIGHT_REACH + 1], prof.light_reach[1]);
-        if (lane == 0) { // wave-level profile, words 16..27 and 48..57
-            atomicAdd(&P.counters[CNT_ROLE_TIME], prof.t_trace); atomicAdd(&P.counters[CNT_ROLE_TIME + 1], prof.t_light); atomicAdd(&P.counters[CNT_ROLE_TIME + 2], prof.t_shade);
-            atomicAdd(&P.counters[CNT_ROLE_TIME + 3], prof.t_exact); atomicAdd(&P.counters[CNT_ROLE_TIME + 4], prof.t_idle);
+        if (lane == 0) { // wave-level profile, words 21..27 and 48..63
             atomicAdd(&P.counters[CNT_P8_WALK_ITERS], prof.iters[0]); atomicAdd(&P.counters[CNT_P8_WALK_ITERS + 1], prof.lane_iters[0]);
             atomicAdd(&P.counters[CNT_P8_WALK_ITERS + 2], prof.iters[1]); atomicAdd(&P.counters[CNT_P8_WALK_ITERS + 3], prof.lane_iters[1]);
             atomicAdd(&P.counters[CNT_P8_STINTS], prof.stints); atomicAdd(&P.counters[CNT_P8_SHADE_BATCHES], prof.shade_batches); atomicAdd(&P.counters[CNT_P8_SHADE_ITEMS], prof.shade_items);
@@ -1051,10 +1108,15 @@ __global__ __launch_bounds__(P8_THREADS, P8_PER_CU) void pt_persistent_kernel(Sc
             }
         }
     }
-    if (P.debug && lane == 0) {
-        const unsigned long long now = __builtin_amdgcn_s_memrealtime();
-        atomicMax(&P.debug[3 * blockIdx.x + 1], now);
-    }
+};
+
+// __launch_bounds__(256, 5): five waves per SIMD, i.e. a budget of 96 VGPRs.  Every role fits it without scratch; the scheduler's own
+// state is wave-uniform and lives in SGPRs (pt_count / readfirstlane).
+template <bool COUNT, int FEAT>
+__global__ __launch_bounds__(P8_THREADS, P8_PER_CU) void pt_persistent_kernel(SceneView S, RenderView R, WfView W, PtParams P) {
+    __shared__ PtShared sh;
+    PtRoles<COUNT, FEAT> roles{S, R, W, sh, P};
+    pt_run(roles);
 }
 
 } // namespace dev

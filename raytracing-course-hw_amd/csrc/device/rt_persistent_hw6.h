@@ -15,6 +15,9 @@
 // the dielectric's uniform is drawn, scene.cpp:77,92), so the replay is the one of rt_kernels_hw6.h; the arithmetic is the same code.
 // As in rt_persistent.h a DIFFUSE bounce's sampled direction is traced for the next hit while its light-pdf sum is walked (the two
 // rays share the direction but not the origin here: x + eps*d for the child, x + eps*n for the pdf, scene.cpp:63,68).
+//
+// The kernel body (seeding, scheduler loop, epilogue) is rt_persistent.h's pt_run and the walker loop its pt_walk_stint; this file holds hw6's own: the
+// record layout, the shader step (p6_advance), the two walker policies, the rare roles and the policy that hands them to pt_run (P6Roles).
 #pragma once
 #include "rt_persistent.h"
 #include "rt_kernels_hw6.h"
@@ -56,6 +59,7 @@ namespace dev {
 #define P6_LIGHT 2
 #define P6_PARKED 8
 #define P6_EXACT 16                  // the hit does not stand as the reference's answer: exact walk first, nothing of the path was touched
+static_assert(P6_TRACE == WF_NEXT_TRACE && P6_PARKED == WF_PARKED, "p6_advance returns what wf_end_sample returns at the end of a camera sample");
 
 typedef __attribute__((address_space(3))) uint32_t *P6Lds; // an LDS pointer that stays one: 32 bits, not a 64-bit generic pointer in two VGPRs
 typedef __attribute__((address_space(3))) float *P6LdsF;
@@ -218,33 +222,15 @@ RT_DEV int p6_advance(const SceneView6 &S, const RenderView &R, const W6View &W,
     }
     // unwind: `ret` is the value of the call at level fp (scene.cpp:69,73,77-103)
     for (;;) {
-        if (fp == 0) { // the camera sample is complete (scene.cpp:111-117)
-            const float4 q3 = r[3];
-            const F3 accum = f3(q3.x, q3.y, q3.z) + ret;
-            sample++;
-            int px, py; bool in_image; size_t out_index;
-            wf_slot_to_pixel(R, slot + W.slot_base, px, py, in_image, out_index);
-            if (sample < (uint32_t)R.samples) {
-                F3 o, d;
-                p6_camera_ray(S, R, rng, px, py, o, d);
-                r[0] = make_float4(o.x, o.y, o.z, d.x);
-                r[1] = make_float4(d.y, d.z, __uint_as_float(rng.x), rng.saved);
-                r[3] = make_float4(accum.x, accum.y, accum.z, __uint_as_float(p6_pack(0, rng.has_saved, sample, 0u)));
-                return sample < (uint32_t)R.sample_stop ? P6_TRACE : P6_PARKED;
-            }
-            if (R.accum) { // a slice of a resumable render ends here (rt_wavefront.h): sum and engine go back to the state
-                accum_leave(R, slot + W.slot_base, rng, accum);
-                return 0;
-            }
-            if (R.streams > 1) { // throughput mode (rt_wavefront.h): this stream's unnormalised sum; wf_reduce_streams_kernel adds a pixel's streams
-                float *ps = R.partial + 3 * (size_t)(slot + W.slot_base);
-                ps[0] = accum.x; ps[1] = accum.y; ps[2] = accum.z;
-                return 0;
-            }
-            const F3 pxl = R.inv_samples * accum;                                               // scene.cpp:115
-            if (R.out_rgb) { R.out_rgb[3 * out_index] = pxl.x; R.out_rgb[3 * out_index + 1] = pxl.y; R.out_rgb[3 * out_index + 2] = pxl.z; }
-            if (R.out_rgb8) { R.out_rgb8[3 * out_index] = tonemap1(pxl.x); R.out_rgb8[3 * out_index + 1] = tonemap1(pxl.y); R.out_rgb8[3 * out_index + 2] = tonemap1(pxl.z); }
-            return 0;
+        if (fp == 0) { // the camera sample is complete (scene.cpp:111-117): the next one, or the pixel (scene.cpp:115)
+            // The frame's dimensions pass through an opaque copy: what the pixel arithmetic derives from them (reciprocals, float copies) is
+            // formed here, once per sample, and does not wait in VGPRs across the whole scheduler loop — registers this kernel does not have
+            // (measured without the copy: 6 VGPR spills, 28 bytes of scratch per lane).  "+s": the view's fields are kernel arguments, wave-uniform.
+            RenderView Q = R;
+            asm volatile("" : "+s"(Q.tile_w), "+s"(Q.tile_h), "+s"(Q.tiles_x), "+s"(Q.width), "+s"(Q.height), "+s"(Q.n_pixslots));
+            return wf_end_sample(Q, r, slot + W.slot_base, ret, rng, sample,
+                                 [&](int px, int py, uint32_t, F3 &o, F3 &d) { p6_camera_ray(S, Q, rng, px, py, o, d); },
+                                 [](bool has_saved, uint32_t next) { return p6_pack(0, has_saved, next, 0u); });
         }
         float4 *f = r + 8 + 5 * (--fp);
         const float4 f0 = f[0], f1 = f[1];
@@ -743,70 +729,37 @@ RT_DEV void p6_exact_batch(const SceneView6 &S, const W6View &W, SH &sh, PtWave 
 static_assert(sizeof(P6Shared) <= 25 * 1280, "five workgroups per CU: 25 LDS granules of 1,280 bytes each");
 static_assert(RT6_STACK_SIZE + P6_XHITS <= P6_SLICE_WORDS && 6 * RT6_MAX_LIGHT_HITS <= P6_SLICE_WORDS, "the rare roles' work arrays must fit a slice of the wave's stack area");
 
-// ---- the kernel (scheduler of rt_persistent.h) ------------------------------------------------------------------------------------------
-template <bool COUNT>
-__global__ __launch_bounds__(P6_THREADS, P6_PER_CU) void p6_persistent_kernel(SceneView6 S, RenderView R, W6View W, PtParams P) {
-    __shared__ P6Shared sh;
-    const uint32_t tid = threadIdx.x, lane = tid & 63u;
-    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6));
-    PtWave wv;
-    uint32_t n_local_groups;
-    if (!pt_enter<P6_THREADS>(sh, P, wv, n_local_groups)) return;
-    for (uint32_t base = 0; base < wv.n_local; base += P6_THREADS) { // seed every pixel, first camera ray (hw6/src/sceneio.cpp:281-284)
-        const uint32_t l = base + tid;
-        bool started = false;
-        if (l < wv.n_local) {
-            const uint32_t slot = pt_slot(sh, l), gslot = slot + W.slot_base;
-            int x, y; bool inside; size_t out_index;
-            wf_slot_to_pixel(R, gslot, x, y, inside, out_index);
-            if (!inside) {
-                if (R.shard_count > 1 && (R.streams <= 1 || gslot < R.n_pixslots)) { // padding of a border tile in the compact shard layout
-                    if (R.out_rgb) { R.out_rgb[3 * out_index] = 0.f; R.out_rgb[3 * out_index + 1] = 0.f; R.out_rgb[3 * out_index + 2] = 0.f; }
-                    if (R.out_rgb8) { R.out_rgb8[3 * out_index] = 0; R.out_rgb8[3 * out_index + 1] = 0; R.out_rgb8[3 * out_index + 2] = 0; }
-                }
-            } else if (P.resume) {
-                // a later phase of the frame: the record holds the pixel sum, the random stream and the parked camera ray
-                const uint32_t packed = __float_as_uint(reinterpret_cast<const float *>(p6_rec(W, slot) + 3)[3]);
-                started = (packed >> 8) < (uint32_t)R.samples;
-                if (started) atomicOr(&sh.pending[l >> 4], PT_BIT_T << ((l & 15u) * 2u));
-            } else {
-                Rng rng;
-                F3 sum = f3(0.f, 0.f, 0.f);
-                if (R.accum) accum_enter(R, gslot, rng, sum);   // a slice of a resumable render: carry on at sample R.sample_first
-                else rng_seed(rng, (uint32_t)(y * R.width + x) + (R.streams > 1 ? (gslot / R.n_pixslots) * R.seed_stride : 0u)); // hw6/src/sceneio.cpp:280-284; throughput mode: stream k offset by k * W * H
-                F3 o, d;
-                p6_camera_ray(S, R, rng, x, y, o, d);
-                float4 *r = p6_rec(W, slot);
-                r[0] = make_float4(o.x, o.y, o.z, d.x);
-                r[1] = make_float4(d.y, d.z, __uint_as_float(rng.x), rng.saved);
-                r[2] = make_float4(0.f, 0.f, 0.f, 0.f);
-                r[3] = make_float4(sum.x, sum.y, sum.z, __uint_as_float(p6_pack(0, rng.has_saved, R.accum ? (uint32_t)R.sample_first : 0u, 0u)));
-                atomicOr(&sh.pending[l >> 4], PT_BIT_T << ((l & 15u) * 2u));
-                started = true;
-            }
-        }
-        const unsigned long long m = pt_ballot(started);
-        if (m && lane == 0) atomicAdd(&sh.cnt[PT_N_LIVE], (int)__popcll(m));
-        pt_push(sh, PT_Q_TRACE, l, started);
+// ---- the kernel: pt_run of rt_persistent.h with hw6's roles ------------------------------------------------------------------------------
+// Its rare roles are the slow role for light sums and the exact role for closest hits, in this order; no ray starts at the exact role
+// (no tripwires) and the shader settles no light sum.
+template <bool COUNT_>
+struct P6Roles {
+    static constexpr bool COUNT = COUNT_;
+    static constexpr int THREADS = P6_THREADS;
+    // pt_walk_stint<2, false>: two parked leaves and immediate endings — deferred to once per pass as in hw8, this kernel lost 3 %
+    // (DESIGN.md, section 3 "leaf phases")
+    static constexpr int SLOTS = 2;
+    static constexpr bool DEFER = false;
+    const SceneView6 &S; const RenderView &R; const W6View &W; P6Shared &sh; const PtParams &P;
+    uint32_t (*stack)[64] = sh.stack[__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6))];
+    uint32_t n_slow = 0, n_exact = 0, n_xlight = 0;
+    RT_DEV P6TraceWalk trace_walk() { return P6TraceWalk{S, W, sh, P, stack}; }
+    RT_DEV P6LightWalk light_walk(PtProf &) { return P6LightWalk{S, W, sh, P, stack}; }
+    RT_DEV void seed(uint32_t slot, uint32_t, int x, int y, Rng &rng, F3 sum) { // first camera ray (hw6/src/sceneio.cpp:281-284)
+        F3 o, d;
+        p6_camera_ray(S, R, rng, x, y, o, d);
+        float4 *r = p6_rec(W, slot);
+        r[0] = make_float4(o.x, o.y, o.z, d.x);
+        r[1] = make_float4(d.y, d.z, __uint_as_float(rng.x), rng.saved);
+        r[2] = make_float4(0.f, 0.f, 0.f, 0.f);
+        r[3] = make_float4(sum.x, sum.y, sum.z, __uint_as_float(p6_pack(0, rng.has_saved, R.accum ? (uint32_t)R.sample_first : 0u, 0u)));
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __syncthreads();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-
-    uint32_t(*stack)[64] = sh.stack[wave];
-    const int shade_thr = P.shade_thr0 + (int)wave * P.shade_thr_step;
-    uint32_t n_closest = 0, n_light = 0, n_slow = 0, n_exact = 0, n_xlight = 0;
-    unsigned long long n_nodes = 0, n_tris = 0;
-    uint32_t idle_spins = 0;
-    int gave_up = 0; // 1: the launch ran into its deadline; 2: the workgroup waited in vain for a path to come back (a lost path: a bug)
-    const unsigned long long t_start = __builtin_amdgcn_s_memrealtime();
-    unsigned long long t_role[5] = {0, 0, 0, 0, 0}, t_mark = t_start; // COUNT: wave time as closest-hit walker, light walker, shader, slow light sums, idle
-    PtProf prof; // the shared walker loop's laps (counting build): not reported for hw6
-    auto clock_role = [&](int role) { if (COUNT) { const unsigned long long now = __builtin_amdgcn_s_memrealtime(); t_role[role] += now - t_mark; t_mark = now; } };
-    for (;;) {
-        if (__builtin_amdgcn_s_memrealtime() - t_start > P.deadline_ticks) { gave_up = 1; break; } // safety net: never hang the GPU; the host reports the error
-        const int ns = pt_count(&sh.cnt[PT_Q_SHADE]), nt = pt_count(&sh.cnt[PT_Q_TRACE]), nl = pt_count(&sh.cnt[PT_Q_LIGHT]);
-        if (pt_count(&sh.cnt[P6_Q_SLOW]) > 0) {
+    RT_DEV uint32_t resumed_sample(uint32_t slot) { return __float_as_uint(reinterpret_cast<const float *>(p6_rec(W, slot) + 3)[3]) >> 8; }
+    RT_DEV bool seed_wire(uint32_t) { return false; }
+    RT_DEV bool rare(PtWave &wv) {
+        // which role is decided before either's divergent code, so the loop's branch on the answer stays a scalar one
+        const bool slow = pt_count(&sh.cnt[P6_Q_SLOW]) > 0, exact = !slow && pt_count(&sh.cnt[P6_Q_XTRACE]) > 0;
+        if (slow) {
             // light sums with more than two hits: the reference's association over the hits the walker left in the record, one lane per
             // query in its own stack column (up to P6_MERGE_HITS hits, not at a box boundary); the others in batches (p6_slow_batch)
             const uint32_t got = pt_pop(sh.need[P6_Q_SLOW], &sh.cnt[P6_Q_SLOW], wv.nw, wv.cur[P6_Q_SLOW], true);
@@ -823,73 +776,33 @@ __global__ __launch_bounds__(P6_THREADS, P6_PER_CU) void p6_persistent_kernel(Sc
             n_slow += __popcll(pt_ballot(got != PT_NONE));
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
             pt_complete(sh, got, PT_BIT_L, got != PT_NONE);
-            idle_spins = 0;
-            clock_role(3);
-            continue;
-        }
-        if (pt_count(&sh.cnt[P6_Q_XTRACE]) > 0) {
-            p6_exact_batch(S, W, sh, wv, (P6Lds)&stack[0][0], n_exact);
-            idle_spins = 0;
-            clock_role(3);
-            continue;
-        }
-        if (ns >= P.shade_min || (ns > 0 && nt + nl == 0)) {
-            const uint32_t got = pt_pop(sh.need[PT_Q_SHADE], &sh.cnt[PT_Q_SHADE], wv.nw, wv.cur[PT_Q_SHADE], true, wv.front_first);
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-            int todo = 0;
-            if (got != PT_NONE) todo = p6_advance(S, R, W, pt_slot(sh, got));
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-            pt_push(sh, P6_Q_XTRACE, got, got != PT_NONE && todo == P6_EXACT);
-            const bool tr = got != PT_NONE && todo != P6_EXACT && (todo & P6_TRACE), li = got != PT_NONE && todo != P6_EXACT && (todo & P6_LIGHT);
-            if (tr || li) atomicOr(&sh.pending[got >> 4], ((tr ? PT_BIT_T : 0u) | (li ? PT_BIT_L : 0u)) << ((got & 15u) * 2u));
-            pt_push(sh, PT_Q_TRACE, got, tr);
-            pt_push(sh, PT_Q_LIGHT, got, li);
-            if (got != PT_NONE && todo != P6_EXACT) atomicAdd(&sh.cost[got >> pt_gshift(sh)], (uint32_t)P6_COST_SHADE);
-            const unsigned long long done = pt_ballot(got != PT_NONE && (todo == 0 || todo == P6_PARKED));
-            if (done && lane == 0) atomicSub(&sh.cnt[PT_N_LIVE], (int)__popcll(done));
-            idle_spins = 0;
-            clock_role(2);
-            continue;
-        }
-        if (nt + nl > 0) {
-            // pt_walk_stint<2, false>: two parked leaves and immediate endings — deferred to once per pass as in hw8, this kernel lost 3 %
-            // (DESIGN.md, section 3 "leaf phases")
-            const long long wt = (long long)nt * P.cost_t * (pt_count(&sh.cnt[PT_W_LIGHT]) + 1), wl = (long long)nl * P.cost_l * (pt_count(&sh.cnt[PT_W_TRACE]) + 1);
-            if (nl == 0 || (nt > 0 && wt >= wl)) {
-                if (lane == 0) atomicAdd(&sh.cnt[PT_W_TRACE], 1);
-                P6TraceWalk walk{S, W, sh, P, stack};
-                pt_walk_stint<2, false, COUNT>(walk, sh, P, wv, stack, shade_thr, n_closest, n_nodes, n_tris, prof);
-                if (lane == 0) atomicSub(&sh.cnt[PT_W_TRACE], 1);
-                clock_role(0);
-            } else {
-                if (lane == 0) atomicAdd(&sh.cnt[PT_W_LIGHT], 1);
-                P6LightWalk walk{S, W, sh, P, stack};
-                pt_walk_stint<2, false, COUNT>(walk, sh, P, wv, stack, shade_thr, n_light, n_nodes, n_tris, prof);
-                if (lane == 0) atomicSub(&sh.cnt[PT_W_LIGHT], 1);
-                clock_role(1);
-            }
-            idle_spins = 0;
-            continue;
-        }
-        if (pt_count(&sh.cnt[PT_N_LIVE]) <= 0) break;
-        __builtin_amdgcn_s_sleep(8);
-        clock_role(4);
-        if (++idle_spins > (1u << 24)) { gave_up = 2; break; }
+        } else if (exact) p6_exact_batch(S, W, sh, wv, (P6Lds)&stack[0][0], n_exact);
+        return slow || exact;
     }
-    if (gave_up && lane == 0 && P.counters) atomicAdd(&P.counters[gave_up == 1 ? CNT_DEADLINE : CNT_LOST_PATH], 1ull);
-    pt_leave<P6_THREADS>(sh, P, n_local_groups);
-    if (lane == 0 && P.counters) {
-        if (n_closest) atomicAdd(&P.counters[CNT_CLOSEST], (unsigned long long)n_closest);
-        if (n_light) atomicAdd(&P.counters[CNT_LIGHT], (unsigned long long)n_light);
+    RT_DEV PtShaded shade(uint32_t got, uint32_t &, unsigned long long &, PtProf &) {
+        int todo = 0;
+        if (got != PT_NONE) todo = p6_advance(S, R, W, pt_slot(sh, got));
+        const bool went = got != PT_NONE && todo != P6_EXACT;
+        PtShaded s;
+        s.trace = went && (todo & P6_TRACE); s.light = went && (todo & P6_LIGHT);
+        s.xtrace = got != PT_NONE && todo == P6_EXACT;
+        s.done = got != PT_NONE && (todo == 0 || todo == P6_PARKED);
+        if (went) s.cost = P6_COST_SHADE;
+        return s;
+    }
+    RT_DEV void flush(uint32_t lane, const PtProf &) {
+        if (lane != 0) return;
         if (n_slow) atomicAdd(&P.counters[CNT_P6_SLOW_LIGHT], (unsigned long long)n_slow);
         if (n_exact) atomicAdd(&P.counters[CNT_EXACT_CLOSEST], (unsigned long long)n_exact);
+        if (n_xlight) atomicAdd(&P.counters[CNT_P6_EXACT_LIGHT], (unsigned long long)n_xlight);
     }
-    if (lane == 0 && n_xlight && P.counters) atomicAdd(&P.counters[CNT_P6_EXACT_LIGHT], (unsigned long long)n_xlight);
-    if (COUNT && P.counters) {
-        atomicAdd(&P.counters[CNT_NODE_VISITS], n_nodes); atomicAdd(&P.counters[CNT_TRI_TESTS], n_tris);
-        if (lane == 0) for (int i = 0; i < 5; i++) atomicAdd(&P.counters[CNT_ROLE_TIME + i], t_role[i]);
-    }
-    if (P.debug && lane == 0) atomicMax(&P.debug[3 * blockIdx.x + 1], __builtin_amdgcn_s_memrealtime());
+};
+
+template <bool COUNT>
+__global__ __launch_bounds__(P6_THREADS, P6_PER_CU) void p6_persistent_kernel(SceneView6 S, RenderView R, W6View W, PtParams P) {
+    __shared__ P6Shared sh;
+    P6Roles<COUNT> roles{S, R, W, sh, P};
+    pt_run(roles);
 }
 
 } // namespace dev

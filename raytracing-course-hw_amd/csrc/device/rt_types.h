@@ -35,7 +35,7 @@ enum CounterSlot {
     CNT_LOST_PATH = 14,         // P8, P6: waves that gave up waiting for a lost path (an error)
     CNT_WANT_HISTOGRAMS = 15,   // request, set by the host (RTAMD_DEBUG_COUNTERS): WF's counting kernels fill the two histograms
     CNT_WF_HIST_CLOSEST = 16,   // WF, 16 slots: closest-hit queries by in-flight wave iterations / 32
-    CNT_ROLE_TIME = 16,         // P8, P6, 5 slots: wave time by role (closest-hit walks, light walks, shading, exact | slow light sums, idle)
+    CNT_ROLE_TIME = 16,         // P8, P6, 5 slots: wave time by role in shader-clock cycles (closest-hit walks, light walks, shading, rare roles — P8: exact walks, P6: slow light sums and exact walks —, idle)
     CNT_P8_WALK_ITERS = 21,     // P8, 2 slots per walker (closest hit, light): wave iterations, lane iterations
     CNT_P8_STINTS = 25,
     CNT_P8_SHADE_BATCHES = 26,

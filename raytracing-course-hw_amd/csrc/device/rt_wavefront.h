@@ -134,40 +134,32 @@ RT_DEV void accum_leave(const RenderView &R, uint32_t pslot, const Rng &rng, F3 
     reinterpret_cast<uint2 *>(R.accum + 4 * (size_t)R.n_pixslots)[pslot] = make_uint2(__float_as_uint(rng.saved), rng.has_saved ? 1u : 0u);
 }
 
-// End of one camera sample: fold e + m*(inner) backwards (scene.cpp:164), add to the pixel sum
-// (scene.cpp:174), then either start the next sample (returns WF_NEXT_TRACE: the slot holds a new camera ray that wants
-// tracing; WF_PARKED instead when that sample belongs to the next phase of the frame, R.sample_stop) or write the finished
-// pixel (returns 0).  The pixel sum is read here, not carried through the shading code.
+// The tail of one camera sample where the record keeps the ray in r[0..1] and the pixel sum with the packed word in r[3] (wf_finish_path, p6_advance of
+// rt_persistent_hw6.h): add the sample's value L to the pixel sum (scene.cpp:174), then either start the next sample (returns WF_NEXT_TRACE: the record
+// holds a new camera ray; WF_PARKED when that sample belongs to the next phase of the frame, R.sample_stop) or write the finished pixel (returns 0).  The sum
+// is read here, not carried through the shading code.  ray(x, y, next, o, d) draws the camera ray of sample `next` from `rng`; pack(has_saved, next) packs it.
 #define WF_NEXT_TRACE 1
 #define WF_NEXT_LIGHT 2
 #define WF_PARKED 8
-RT_DEV int wf_finish_path(const SceneView &S, const RenderView &R, const WfView &W, uint32_t slot, int depth, F3 tail,
-                           Rng &rng, uint32_t sample) {
-    F3 L = tail;
-    for (int b = depth - 1; b >= 0; b--) {
-        const float4 *e = wf_entry(W, slot, b);
-        float4 e0 = e[0], e1 = e[1];
-        L = f3(e0.x, e0.y, e0.z) + f3(e1.x, e1.y, e1.z) * L;
-    }
-    float4 *r = wf_rec(W, slot);
+template <class RAY, class PACK>
+RT_DEV int wf_end_sample(const RenderView &R, float4 *r, uint32_t gslot, F3 L, Rng &rng, uint32_t sample, RAY ray, PACK pack) {
     float4 q3 = r[3];
     F3 accum = f3(q3.x, q3.y, q3.z) + L;
     sample++;
     int x, y; bool inside; size_t out_index;
-    wf_slot_to_pixel(R, slot + W.slot_base, x, y, inside, out_index);
+    wf_slot_to_pixel(R, gslot, x, y, inside, out_index);
     if (sample < (uint32_t)R.samples) {
         F3 o, d;
-        if (R.sample_seeds) wf_sample_seed(R, rng, slot + W.slot_base, x, y, sample);
-        wf_camera_ray(S, R, rng, x, y, o, d);
+        ray(x, y, sample, o, d);
         r[0] = make_float4(o.x, o.y, o.z, d.x);
         r[1] = make_float4(d.y, d.z, __uint_as_float(rng.x), rng.saved);
-        r[3] = make_float4(accum.x, accum.y, accum.z, __uint_as_float(wf_pack(0, rng.has_saved, sample)));
+        r[3] = make_float4(accum.x, accum.y, accum.z, __uint_as_float(pack(rng.has_saved, sample)));
         return sample < (uint32_t)R.sample_stop ? WF_NEXT_TRACE : WF_PARKED;
     }
     if (R.accum) {                                                   // a slice of a resumable render ends here: sum and engine go back to the state
-        accum_leave(R, slot + W.slot_base, rng, accum);
-    } else if (R.streams > 1) {                                      // throughput mode: this stream's unnormalised sum
-        float *o = R.partial + 3 * (size_t)(slot + W.slot_base);
+        accum_leave(R, gslot, rng, accum);
+    } else if (R.streams > 1) {                                      // throughput mode: this stream's unnormalised sum; wf_reduce_streams_kernel adds a pixel's streams
+        float *o = R.partial + 3 * (size_t)gslot;
         o[0] = accum.x; o[1] = accum.y; o[2] = accum.z;
     } else {
         F3 px = R.inv_samples * accum;                               // scene.cpp:176
@@ -177,6 +169,45 @@ RT_DEV int wf_finish_path(const SceneView &S, const RenderView &R, const WfView 
         }
     }
     return 0;
+}
+
+// Where a pixel slot begins, for every kernel that seeds paths (wf_init_kernel, pt_run of rt_persistent.h): its pixel, and for padding of a border
+// tile in the compact shard layout a black pixel (returns false: no path).  `fresh`: also the pixel's engine and sum before its first camera ray —
+// from the state of a resumable render (a slice carries on at sample R.sample_first), else seeded as the reference does (sceneio.cpp:389-391,
+// hw6/src/sceneio.cpp:280-284; throughput mode: stream k offset by k * seed_stride) with a sum of 0.
+RT_DEV bool wf_seed_record(const RenderView &R, uint32_t gslot, bool fresh, int &x, int &y, Rng &rng, F3 &sum) {
+    bool inside; size_t out_index;
+    wf_slot_to_pixel(R, gslot, x, y, inside, out_index);
+    if (!inside) {
+        if (R.shard_count > 1 && (R.streams <= 1 || gslot < R.n_pixslots)) {
+            if (R.out_rgb) { R.out_rgb[3 * out_index] = 0.f; R.out_rgb[3 * out_index + 1] = 0.f; R.out_rgb[3 * out_index + 2] = 0.f; }
+            if (R.out_rgb8) { R.out_rgb8[3 * out_index] = 0; R.out_rgb8[3 * out_index + 1] = 0; R.out_rgb8[3 * out_index + 2] = 0; }
+        }
+        return false;
+    }
+    if (fresh) {
+        sum = f3(0.f, 0.f, 0.f);
+        if (R.accum) accum_enter(R, gslot, rng, sum);
+        else rng_seed(rng, (uint32_t)(y * R.width + x) + (R.streams > 1 ? (gslot / R.n_pixslots) * R.seed_stride : 0u));
+    }
+    return true;
+}
+
+// End of one camera sample: fold e + m*(inner) backwards (scene.cpp:164), then wf_end_sample.
+RT_DEV int wf_finish_path(const SceneView &S, const RenderView &R, const WfView &W, uint32_t slot, int depth, F3 tail,
+                           Rng &rng, uint32_t sample) {
+    F3 L = tail;
+    for (int b = depth - 1; b >= 0; b--) {
+        const float4 *e = wf_entry(W, slot, b);
+        float4 e0 = e[0], e1 = e[1];
+        L = f3(e0.x, e0.y, e0.z) + f3(e1.x, e1.y, e1.z) * L;
+    }
+    return wf_end_sample(R, wf_rec(W, slot), slot + W.slot_base, L, rng, sample,
+                         [&](int x, int y, uint32_t next, F3 &o, F3 &d) {
+                             if (R.sample_seeds) wf_sample_seed(R, rng, slot + W.slot_base, x, y, next);
+                             wf_camera_ray(S, R, rng, x, y, o, d);
+                         },
+                         [](bool has_saved, uint32_t next) { return wf_pack(0, has_saved, next); });
 }
 
 // ---- init: seed every pixel, first camera ray, fill the round-0 trace queue ------------------------------
@@ -189,19 +220,9 @@ __global__ __launch_bounds__(256) void wf_init_kernel(SceneView S, RenderView R,
     for (uint32_t base = blockIdx.x * 256u; base < W.n_slots; base += gridDim.x * 256u) {
         uint32_t slot = base + threadIdx.x;
         if (slot < W.n_slots) {
-            int x, y; bool inside; size_t out_index;
+            int x, y; Rng rng; F3 sum;
             const uint32_t gslot = slot + W.slot_base;
-            wf_slot_to_pixel(R, gslot, x, y, inside, out_index);
-            if (!inside) { // padding of a border tile in the compact shard layout
-                if (R.shard_count > 1 && (R.streams <= 1 || gslot < R.n_pixslots)) {
-                    if (R.out_rgb) { R.out_rgb[3 * out_index] = 0.f; R.out_rgb[3 * out_index + 1] = 0.f; R.out_rgb[3 * out_index + 2] = 0.f; }
-                    if (R.out_rgb8) { R.out_rgb8[3 * out_index] = 0; R.out_rgb8[3 * out_index + 1] = 0; R.out_rgb8[3 * out_index + 2] = 0; }
-                }
-            } else {
-                Rng rng;
-                F3 sum = f3(0.f, 0.f, 0.f);
-                if (R.accum) accum_enter(R, gslot, rng, sum);   // a slice of a resumable render: carry on at sample R.sample_first
-                else rng_seed(rng, (uint32_t)(y * R.width + x) + (R.streams > 1 ? (gslot / R.n_pixslots) * R.seed_stride : 0u)); // sceneio.cpp:389-391
+            if (wf_seed_record(R, gslot, true, x, y, rng, sum)) {
                 if (R.sample_seeds) wf_sample_seed(R, rng, gslot, x, y, 0u);
                 F3 o, d;
                 wf_camera_ray(S, R, rng, x, y, o, d);

@@ -326,3 +326,23 @@ def test_persistent_pipeline_in_several_passes(rt, monkeypatch):
     assert np.array_equal(thr2, thr1, equal_nan=True) and np.array_equal(shard2, shard1, equal_nan=True)
     crop_ref, _, _ = oracle_lib.Hw6Oracle(sd6).render(w, h, spp, rect=(180, 130, 40, 40))
     assert np.array_equal(two[130:170, 180:220], crop_ref, equal_nan=True)
+
+
+@pytest.mark.parametrize("integrator", ["hw6", "hw8"])
+def test_counting_render_equals_the_plain_render(rt, sphere_scene, integrator):
+    """RT_FLAG_COUNTERS selects the counting variant of the persistent kernel (node visits, triangle tests, the role clock): the
+    frame and the two query counts are the plain variant's, for the hw6 kernel (practice6_1) and the hw8 kernel (the emissive sphere)
+    at 64x48 and 4 samples.  The five role times are not part of rt_stats, so only the frame and the counts are compared; the counting
+    render has visited nodes."""
+    if integrator == "hw6":
+        scene, kw = rt.Scene(pin_cases.load_hw6("practice6_1")), dict(integrator=rt.RT_INTEGRATOR_HW6)
+    else:
+        scene, kw = rt.Scene(sphere_scene), {}
+    plain, plain8, st = scene.render(64, 48, 4, **kw)
+    cnt, cnt8, stc = scene.render(64, 48, 4, counters=True, **kw)
+    scene.close()
+    print(f"{integrator}: {st.closest_hit_queries}+{st.light_pdf_queries} queries, counting {stc.closest_hit_queries}+{stc.light_pdf_queries}, node visits {stc.node_visits}")
+    assert st.pipeline == rt.RT_PIPELINE_PERSISTENT and stc.pipeline == rt.RT_PIPELINE_PERSISTENT
+    assert np.array_equal(cnt, plain, equal_nan=True) and np.array_equal(cnt8, plain8)
+    assert (stc.closest_hit_queries, stc.light_pdf_queries) == (st.closest_hit_queries, st.light_pdf_queries)
+    assert st.closest_hit_queries > 64 * 48 * 4 and stc.node_visits > 0
