@@ -304,6 +304,52 @@ int rt_multi_render(rt_multi *multi, const rt_render_params *params, float *out_
                     rt_stats *stats /* nullable */);
 void rt_multi_destroy(rt_multi *multi);
 
+/* ---- resumable renders on several GPUs ---------------------------------------------------------------------------------
+ * rt_multi_* and rt_accum_* composed: one sharded rt_accum per device entry of the rt_multi (shard i of N, 32x32 tiles dealt
+ * round-robin, on that entry's own stream), advanced side by side, one host thread per device.  The frame after any slicing
+ * on any number of devices is bit for bit the one rt_render call's, and the picture after d samples is rt_render(samples = d).
+ * Like everything in rt_multi the path has so far run with repeated entries of ONE physical GPU only (the peer copies are
+ * then copies within the device); two physical devices were never involved.
+ *
+ * rt_multi_accum_create   params of the UNSHARDED frame, as for rt_multi_render (shard_count 0 or 1, square tiles, default 32;
+ *                         samples ignored).  What rt_accum_create refuses is refused here with its code and its reason:
+ *                         hw1 .. hw5, throughput mode, the megakernels and flags other than RT_FLAG_COUNTERS are
+ *                         RT_ERR_UNSUPPORTED.  With more entries than tiles some shards are empty.  Several rt_multi_accum may
+ *                         live on one rt_multi, rt_multi_render between two slices disturbs none of them; destroy them before
+ *                         the rt_multi.  Calls on one rt_multi and its rt_multi_accums are serialised by the caller.
+ * rt_multi_accum_render   every device draws n_samples more samples for the pixels of its shard.  Whatever can be refused is
+ *                         refused before any device launches and leaves the state as it was; that includes the sample index
+ *                         limit (the smallest of the devices' limits, RT_ERR_LIMIT).  A device that fails under way leaves the
+ *                         whole object broken: every later call fails with that first message.  rt_stats as rt_multi_render
+ *                         sums them, samples = W*H*n_samples, reference_exact = the AND over the shards that have pixels,
+ *                         pipeline = that of a shard that has pixels.
+ * rt_multi_accum_samples  samples per pixel so far.
+ * rt_multi_accum_resolve  every device resolves its shard on the device; the shards go through rt_multi_render's exchange (push to
+ *                         the first device, tiles scattered into the frame there).  Outputs are host memory, or with
+ *                         RT_FLAG_OUT_DEVICE memory on the first device.  d == 0 is RT_ERR_INVALID_ARG.  The state is only read.
+ * rt_multi_accum_save / rt_multi_accum_load   the PORTABLE checkpoint: the blob is byte for byte the blob an unsharded
+ *                         single-device rt_accum of the same frame writes after the same samples -- the header of shard 0 of 1
+ *                         in 8x8 tiles with ceil(W/8)*ceil(H/8)*64 pixel slots, then the two per-slot arrays in the order of
+ *                         the image's 8x8 sub-tiles, row-major.  Its size is rt_accum_state_bytes(the unsharded params): there
+ *                         is no size function of its own.  So a checkpoint saved on N devices loads on M devices for any M,
+ *                         one included, and into a plain unsharded rt_accum, and an unsharded rt_accum's blob loads here; the
+ *                         continued frame is bit for bit the one-shot rt_render.  Save: every device pushes its shard's state
+ *                         to the first device, which regroups the shards into that order and copies the blob to the host once;
+ *                         load is the reverse.  rt_multi_accum_load checks every header field but the samples against the frame
+ *                         and the samples against the limit; a mismatch or a truncated blob is RT_ERR_INVALID_ARG with a
+ *                         message naming the field and leaves the state as it was.
+ * Measured on one MI355X (profiles/r10_multi_accum.txt): the 1920x1080x256 frame in 4 slices of 64 with a resolve
+ * to the host per slice takes 1,124 ms on one device entry (rt_accum: 1,131 - 1,141 ms) and 1,246 ms as two shards on that one GPU;
+ * save / load of its 49.8 MB checkpoint 14 / 25 ms through the Python binding. */
+typedef struct rt_multi_accum rt_multi_accum;
+int rt_multi_accum_create(rt_multi *multi, const rt_render_params *params, rt_multi_accum **out);
+int rt_multi_accum_render(rt_multi_accum *accum, int32_t n_samples, rt_stats *stats /* nullable */);
+int rt_multi_accum_samples(const rt_multi_accum *accum);
+int rt_multi_accum_resolve(rt_multi_accum *accum, uint32_t flags, float *out_rgb_linear /* nullable */, uint8_t *out_rgb8 /* nullable */);
+int rt_multi_accum_save(rt_multi_accum *accum, void *blob, size_t capacity);
+int rt_multi_accum_load(rt_multi_accum *accum, const void *blob, size_t size);
+void rt_multi_accum_destroy(rt_multi_accum *accum);
+
 /* Scene info the host side needs after preparation. */
 typedef struct rt_scene_info {
     uint32_t n_triangles, n_lights, n_bvh_nodes, n_light_bvh_nodes;

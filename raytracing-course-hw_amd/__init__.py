@@ -101,7 +101,9 @@ ABI_SYMBOLS = ["rt_abi_version", "rt_last_error", "rt_scene_create", "rt_scene_d
                "rt_host_scene_set_environment", "rt_host_scene_desc", "rt_host_scene_free", "rt_write_ppm",
                "rt_decode_png", "rt_free", "rt_host_prepare_orders", "rt_device_count", "rt_multi_create", "rt_multi_render",
                "rt_multi_destroy", "rt_accum_create", "rt_accum_render", "rt_accum_samples", "rt_accum_resolve",
-               "rt_accum_state_bytes", "rt_accum_save", "rt_accum_load", "rt_accum_destroy"]
+               "rt_accum_state_bytes", "rt_accum_save", "rt_accum_load", "rt_accum_destroy", "rt_multi_accum_create",
+               "rt_multi_accum_render", "rt_multi_accum_samples", "rt_multi_accum_resolve", "rt_multi_accum_save",
+               "rt_multi_accum_load", "rt_multi_accum_destroy"]
 
 if not os.path.exists(LIB_PATH):
     raise ImportError(f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
@@ -143,6 +145,14 @@ lib.rt_accum_save.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
 lib.rt_accum_load.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
 lib.rt_accum_destroy.argtypes = [C.c_void_p]
 lib.rt_accum_destroy.restype = None
+lib.rt_multi_accum_create.argtypes = [C.c_void_p, C.POINTER(rt_render_params), C.POINTER(C.c_void_p)]
+lib.rt_multi_accum_render.argtypes = [C.c_void_p, C.c_int32, C.POINTER(rt_stats)]
+lib.rt_multi_accum_samples.argtypes = [C.c_void_p]
+lib.rt_multi_accum_resolve.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
+lib.rt_multi_accum_save.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+lib.rt_multi_accum_load.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
+lib.rt_multi_accum_destroy.argtypes = [C.c_void_p]
+lib.rt_multi_accum_destroy.restype = None
 
 
 def _check(code):
@@ -313,10 +323,13 @@ class MultiScene:
     def __init__(self, data, devices):
         self.data = data
         self._h = C.c_void_p()
+        self._accums = weakref.WeakSet()
         arr = (C.c_int * len(devices))(*devices)
         _check(lib.rt_multi_create(C.byref(data.desc), arr, len(devices), C.byref(self._h)))
 
     def close(self):
+        for a in list(self._accums):  # an rt_multi_accum goes before its rt_multi
+            a.close()
         if self._h:
             lib.rt_multi_destroy(self._h)
             self._h = C.c_void_p()
@@ -336,6 +349,63 @@ class MultiScene:
         _check(lib.rt_multi_render(self._h, C.byref(p), rgb.ctypes.data if want_float else None,
                                    rgb8.ctypes.data if want_rgb8 else None, C.byref(st)))
         return rgb, rgb8, st
+
+    def accumulator(self, width, height, **kw):
+        """A resumable render of the frame on all the devices (MultiAccumulator); keywords as make_params."""
+        return MultiAccumulator(self, width, height, **kw)
+
+
+class MultiAccumulator:
+    """A frame in progress on every device of a MultiScene (rt_multi_accum), the counterpart of Accumulator: render(n) draws n more
+    samples per pixel on all devices, resolve() is the whole picture so far, bit for bit Scene.render(width, height, samples);
+    save() / load() exchange the portable checkpoint, byte for byte the blob of an unsharded Accumulator of the same frame."""
+
+    def __init__(self, multi, width, height, **kw):
+        self.multi = multi  # keeps the rt_multi alive: an rt_multi_accum is destroyed before it
+        self.params = make_params(width, height, 0, **kw)
+        if "shard_count" not in kw:
+            self.params.shard_count, self.params.shard_index = 0, 0
+        self._h = C.c_void_p()
+        _check(lib.rt_multi_accum_create(multi._h, C.byref(self.params), C.byref(self._h)))
+        multi._accums.add(self)
+
+    def close(self):
+        if self._h:
+            lib.rt_multi_accum_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def samples(self):
+        return _check(lib.rt_multi_accum_samples(self._h))
+
+    def render(self, n_samples):
+        st = rt_stats()
+        _check(lib.rt_multi_accum_render(self._h, n_samples, C.byref(st)))
+        return st
+
+    def resolve(self, want_float=True, want_rgb8=True):
+        """(rgb float32, rgb8) of the whole frame, (H, W, 3) each."""
+        h, w = self.params.height, self.params.width
+        rgb = np.zeros((h, w, 3), dtype=np.float32) if want_float else None
+        rgb8 = np.zeros((h, w, 3), dtype=np.uint8) if want_rgb8 else None
+        _check(lib.rt_multi_accum_resolve(self._h, 0, rgb.ctypes.data if want_float else None, rgb8.ctypes.data if want_rgb8 else None))
+        return rgb, rgb8
+
+    def save(self):
+        p = rt_render_params.from_buffer_copy(self.params)
+        p.shard_count, p.shard_index = 0, 0   # the checkpoint is the unsharded frame's
+        buf = C.create_string_buffer(lib.rt_accum_state_bytes(C.byref(p)))
+        _check(lib.rt_multi_accum_save(self._h, buf, len(buf)))
+        return buf.raw
+
+    def load(self, blob):
+        _check(lib.rt_multi_accum_load(self._h, blob, len(blob)))
 
 
 class Accumulator:

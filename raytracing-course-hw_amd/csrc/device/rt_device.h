@@ -754,5 +754,30 @@ RT_DEV void slot_to_pixel(const RenderView &R, uint32_t slot, int &x, int &y, bo
     out_index = R.shard_count > 1 ? ((size_t)st * R.tile_h + ly) * R.tile_w + lx : (size_t)y * R.width + x;
 }
 
+// Pixel slot of a shard -> pixel slot of the unsharded frame (its "frame order": the 8x8 sub-tiles of the image row-major, 64 slots each),
+// the order a portable checkpoint keeps the state in (rt_multi_accum_save).  `tile` = side of the shard's square tiles, tiles_x = tiles per
+// row, sub_w x sub_h = ceil(W/8) x ceil(H/8).  false: the slot lies in a sub-tile wholly outside the image (padding of a border tile),
+// which the frame order does not have.  Same divisions as slot_to_pixel on the device; the host (tests, no GPU) divides plainly.
+__host__ __device__ inline bool shard_slot_to_frame_slot(int tile, int tiles_x, int sub_w, int sub_h, uint32_t shard_index, uint32_t shard_count, uint32_t slot, uint32_t &frame_slot) {
+    const uint32_t sub_x = (uint32_t)tile >> 3, sub_per_tile = sub_x * sub_x;
+    const uint32_t w = slot >> 6, lane = slot & 63u; // w < 2^24, as in slot_to_pixel
+    uint32_t sub, st, gtx, gty, sx, sy;
+#if defined(__HIP_DEVICE_COMPILE__)
+    st = udiv24(w, sub_per_tile, __builtin_amdgcn_rcpf((float)sub_per_tile), sub);
+    const uint32_t gt = shard_index + st * shard_count;
+    if (gt < (1u << 24)) gty = udiv24(gt, (uint32_t)tiles_x, __builtin_amdgcn_rcpf((float)tiles_x), gtx);
+    else { gty = gt / (uint32_t)tiles_x; gtx = gt % (uint32_t)tiles_x; }
+    sy = udiv24(sub, sub_x, __builtin_amdgcn_rcpf((float)sub_x), sx);
+#else
+    st = w / sub_per_tile; sub = w % sub_per_tile;
+    const uint32_t gt = shard_index + st * shard_count;
+    gty = gt / (uint32_t)tiles_x; gtx = gt % (uint32_t)tiles_x;
+    sy = sub / sub_x; sx = sub % sub_x;
+#endif
+    const uint32_t gx = gtx * sub_x + sx, gy = gty * sub_x + sy;
+    frame_slot = ((gy * (uint32_t)sub_w + gx) << 6) | lane;
+    return gx < (uint32_t)sub_w && gy < (uint32_t)sub_h;
+}
+
 } // namespace dev
 } // namespace rtamd

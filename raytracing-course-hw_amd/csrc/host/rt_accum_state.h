@@ -1,0 +1,49 @@
+// struct rt_accum and the header of its checkpoint, shared by the two translation units that keep resumable state:
+// rtamd_api.hip (rt_accum_*: one frame or one shard on one device) and rtamd_multi.hip (rt_multi_accum_*: one sharded rt_accum
+// per device and the checkpoint of the whole frame, which is the unsharded rt_accum's blob byte for byte).
+#pragma once
+#include <cstring>
+#include <string>
+#include "rt_scene.h"
+
+#define ACCUM_MAGIC 0x43415452u   // "RTAC" read as a little-endian word
+#define ACCUM_VERSION 1u
+#define ACCUM_HEADER_BYTES 128u
+#define ACCUM_SLOT_BYTES 24u
+enum { AH_MAGIC, AH_VERSION, AH_HEADER_BYTES, AH_SLOT_BYTES, AH_WIDTH, AH_HEIGHT, AH_INTEGRATOR, AH_RAY_DEPTH, AH_TILE_W, AH_TILE_H,
+       AH_SHARD_INDEX, AH_SHARD_COUNT, AH_PIXSLOTS, AH_SAMPLES, AH_TRIANGLES, AH_LIGHTS, AH_LIGHT_HASH, AH_WORDS };
+static const char *const accum_field_names[AH_WORDS] = {"magic", "format version", "header size", "bytes per pixel slot", "width", "height", "integrator",
+    "ray depth", "tile width", "tile height", "shard index", "shard count", "pixel slots", "samples", "triangle count of the scene", "light count of the scene",
+    "light order of the scene (hash)"};
+
+struct rt_accum {
+    rt_scene *scene = nullptr;
+    rt_render_params params{};      // as given to rt_accum_create; samples is set per slice
+    rtamd::RenderView view{};       // the frame's geometry (resolve_tiles)
+    uint32_t n_pixslots = 0;
+    uint32_t *d_state = nullptr;
+    int32_t samples = 0;            // per pixel so far
+    int32_t sample_limit = 0;       // the path records' sample index field (choose_pipeline)
+    std::string broken;             // first error of a slice that failed under way: the state is half advanced
+    ~rt_accum() { if (d_state) (void)hipFree(d_state); }
+};
+
+// The 128-byte header of the checkpoint of a frame (or shard) of geometry `R` with `n_pixslots` pixel slots after `samples` samples.
+static inline void accum_header(const rt_scene *scene, int integrator, const rtamd::RenderView &R, uint32_t n_pixslots, int32_t samples, uint32_t *h) {
+    memset(h, 0, ACCUM_HEADER_BYTES);
+    h[AH_MAGIC] = ACCUM_MAGIC; h[AH_VERSION] = ACCUM_VERSION; h[AH_HEADER_BYTES] = ACCUM_HEADER_BYTES; h[AH_SLOT_BYTES] = ACCUM_SLOT_BYTES;
+    h[AH_WIDTH] = (uint32_t)R.width; h[AH_HEIGHT] = (uint32_t)R.height; h[AH_INTEGRATOR] = (uint32_t)integrator; h[AH_RAY_DEPTH] = (uint32_t)R.ray_depth;
+    h[AH_TILE_W] = (uint32_t)R.tile_w; h[AH_TILE_H] = (uint32_t)R.tile_h; h[AH_SHARD_INDEX] = (uint32_t)R.shard_index; h[AH_SHARD_COUNT] = (uint32_t)R.shard_count;
+    h[AH_PIXSLOTS] = n_pixslots; h[AH_SAMPLES] = (uint32_t)samples;
+    h[AH_TRIANGLES] = scene->info.n_triangles; h[AH_LIGHTS] = scene->info.n_lights;
+    uint32_t hash = 2166136261u; // FNV-1a over the bytes of the light order, least significant first
+    for (uint32_t v : scene->light_order) for (int b = 0; b < 4; b++) { hash ^= (v >> (8 * b)) & 255u; hash *= 16777619u; }
+    h[AH_LIGHT_HASH] = hash;
+}
+static inline void accum_header(const rt_accum *a, uint32_t *h) { accum_header(a->scene, a->params.integrator, a->view, a->n_pixslots, a->samples, h); }
+
+namespace rtamd {
+// What rt_accum_render refuses before it launches anything (a broken state, n_samples, the sample-index limit, a pipeline without
+// resumable state); RT_OK = the slice would be launched.  Host only; `who` prefixes the message.
+int accum_check_slice(const rt_accum *a, int32_t n_samples, const std::string &who);
+} // namespace rtamd

@@ -14,6 +14,7 @@
 #include "../../include/rtamd.h"
 #include "host/knobs.h"
 #include "host/rt_scene.h"
+#include "host/rt_accum_state.h"
 #include "device/rt_kernels_hw8.h"
 #include "device/rt_wavefront.h"
 #include "device/rt_persistent.h"
@@ -861,28 +862,7 @@ int rt_render(rt_scene *scene, const rt_render_params *p, float *out_rgb, uint8_
 // The state lives in one device allocation indexed by pixel slot of the shard (RenderView::accum, device/rt_wavefront.h
 // accum_enter / accum_leave): it belongs to the rt_accum, not to the scene's path records, so passes, phases, re-deals and
 // other renders on the scene do not touch it.  The blob of rt_accum_save is a 128-byte header and that allocation, verbatim.
-#define ACCUM_MAGIC 0x43415452u   // "RTAC" read as a little-endian word
-#define ACCUM_VERSION 1u
-#define ACCUM_HEADER_BYTES 128u
-#define ACCUM_SLOT_BYTES 24u
-enum { AH_MAGIC, AH_VERSION, AH_HEADER_BYTES, AH_SLOT_BYTES, AH_WIDTH, AH_HEIGHT, AH_INTEGRATOR, AH_RAY_DEPTH, AH_TILE_W, AH_TILE_H,
-       AH_SHARD_INDEX, AH_SHARD_COUNT, AH_PIXSLOTS, AH_SAMPLES, AH_TRIANGLES, AH_LIGHTS, AH_LIGHT_HASH, AH_WORDS };
-static const char *const accum_field_names[AH_WORDS] = {"magic", "format version", "header size", "bytes per pixel slot", "width", "height", "integrator",
-    "ray depth", "tile width", "tile height", "shard index", "shard count", "pixel slots", "samples", "triangle count of the scene", "light count of the scene",
-    "light order of the scene (hash)"};
-
-struct rt_accum {
-    rt_scene *scene = nullptr;
-    rt_render_params params{};      // as given to rt_accum_create; samples is set per slice
-    RenderView view{};              // the frame's geometry (resolve_tiles)
-    uint32_t n_pixslots = 0;
-    uint32_t *d_state = nullptr;
-    int32_t samples = 0;            // per pixel so far
-    int32_t sample_limit = 0;       // the path records' sample index field (choose_pipeline)
-    std::string broken;             // first error of a slice that failed under way: the state is half advanced
-    ~rt_accum() { if (d_state) (void)hipFree(d_state); }
-};
-
+// struct rt_accum and the header are in host/rt_accum_state.h, shared with rtamd_multi.hip (rt_multi_accum_*).
 // Geometry of a resumable frame from its params (host only); false with `err` set for params no rt_accum can be made of.
 static bool accum_geometry(const rt_render_params *p, RenderView &R, uint32_t &n_pixslots, std::string &err) {
     if (!p) { err = "null params"; return false; }
@@ -897,19 +877,6 @@ static bool accum_geometry(const rt_render_params *p, RenderView &R, uint32_t &n
     if (slots >= 0x40000000ull) { err = "too many pixel slots"; return false; }
     n_pixslots = (uint32_t)slots;
     return true;
-}
-
-static void accum_header(const rt_accum *a, uint32_t *h) {
-    memset(h, 0, ACCUM_HEADER_BYTES);
-    const RenderView &R = a->view;
-    h[AH_MAGIC] = ACCUM_MAGIC; h[AH_VERSION] = ACCUM_VERSION; h[AH_HEADER_BYTES] = ACCUM_HEADER_BYTES; h[AH_SLOT_BYTES] = ACCUM_SLOT_BYTES;
-    h[AH_WIDTH] = (uint32_t)R.width; h[AH_HEIGHT] = (uint32_t)R.height; h[AH_INTEGRATOR] = (uint32_t)a->params.integrator; h[AH_RAY_DEPTH] = (uint32_t)R.ray_depth;
-    h[AH_TILE_W] = (uint32_t)R.tile_w; h[AH_TILE_H] = (uint32_t)R.tile_h; h[AH_SHARD_INDEX] = (uint32_t)R.shard_index; h[AH_SHARD_COUNT] = (uint32_t)R.shard_count;
-    h[AH_PIXSLOTS] = a->n_pixslots; h[AH_SAMPLES] = (uint32_t)a->samples;
-    h[AH_TRIANGLES] = a->scene->info.n_triangles; h[AH_LIGHTS] = a->scene->info.n_lights;
-    uint32_t hash = 2166136261u; // FNV-1a over the bytes of the light order, least significant first
-    for (uint32_t v : a->scene->light_order) for (int b = 0; b < 4; b++) { hash ^= (v >> (8 * b)) & 255u; hash *= 16777619u; }
-    h[AH_LIGHT_HASH] = hash;
 }
 
 size_t rt_accum_state_bytes(const rt_render_params *p) {
@@ -967,20 +934,26 @@ int rt_accum_samples(const rt_accum *a) {
     return a->samples;
 }
 
-int rt_accum_render(rt_accum *a, int32_t n_samples, rt_stats *stats) {
-    if (!a) return fail(RT_ERR_INVALID_ARG, "rt_accum_render: null argument");
-    if (!a->broken.empty()) return fail(RT_ERR_INVALID_ARG, "rt_accum_render: an earlier slice failed and left the state half advanced (" + a->broken + ")");
-    if (n_samples <= 0) return fail(RT_ERR_INVALID_ARG, "rt_accum_render: n_samples must be positive");
+extern "C++" {
+// what can be refused is refused before anything is launched: the state stays as it was
+int rtamd::accum_check_slice(const rt_accum *a, int32_t n_samples, const std::string &who) {
+    if (!a) return fail(RT_ERR_INVALID_ARG, who + "null argument");
+    if (!a->broken.empty()) return fail(RT_ERR_INVALID_ARG, who + "an earlier slice failed and left the state half advanced (" + a->broken + ")");
+    if (n_samples <= 0) return fail(RT_ERR_INVALID_ARG, who + "n_samples must be positive");
     if ((int64_t)a->samples + n_samples >= (int64_t)a->sample_limit)
-        return fail(RT_ERR_LIMIT, "rt_accum_render: " + std::to_string(a->samples) + " + " + std::to_string(n_samples) + " samples per pixel do not fit the path records' sample index (below " + std::to_string(a->sample_limit) + ")");
+        return fail(RT_ERR_LIMIT, who + std::to_string(a->samples) + " + " + std::to_string(n_samples) + " samples per pixel do not fit the path records' sample index (below " + std::to_string(a->sample_limit) + ")");
+    RenderView R = a->view;
+    R.samples = a->samples + n_samples;
+    bool rounds_chosen = false;
+    if (const char *why = accum_unsupported(choose_pipeline(a->scene, a->params.integrator, R, a->n_pixslots / 64u, 1, rounds_chosen), &a->params)) return fail(RT_ERR_UNSUPPORTED, who + why);
+    return RT_OK;
+}
+}
+
+int rt_accum_render(rt_accum *a, int32_t n_samples, rt_stats *stats) {
+    if (const int rc = accum_check_slice(a, n_samples, "rt_accum_render: ")) return rc;
     rt_render_params p = a->params;
     p.samples = n_samples;
-    { // what can be refused is refused before anything is launched: the state stays as it was
-        RenderView R = a->view;
-        R.samples = a->samples + n_samples;
-        bool rounds_chosen = false;
-        if (const char *why = accum_unsupported(choose_pipeline(a->scene, p.integrator, R, a->n_pixslots / 64u, 1, rounds_chosen), &p)) return fail(RT_ERR_UNSUPPORTED, std::string("rt_accum_render: ") + why);
-    }
     const AccumSlice slice{a->d_state, a->samples};
     const int rc = render_frame(a->scene, &p, nullptr, nullptr, stats, &slice);
     if (rc != RT_OK) { a->broken = rt_last_error(); return rc; }

@@ -7,6 +7,8 @@
 // the reference's figure order) runs once and is shared by the devices' scenes (host/shared_prep.h).
 // This is what `./run.sh scene.gltf W H SPP out.ppm` (csrc/cli/main.cpp) uses when more than one GPU is visible; the
 // reference seam is the pixel loop of sceneio::renderScene driven from main (hw8/src/main.cpp:7-18).
+// Resumable renders on the same devices (rt_multi_accum_*, second half of this file): one sharded rt_accum per device, the picture through
+// the same exchange, and a checkpoint regrouped on device 0 into the unsharded rt_accum's own blob.
 #include <hip/hip_runtime.h>
 #include <chrono>
 #include <cstring>
@@ -15,9 +17,9 @@
 #include <thread>
 #include <vector>
 #include "../../include/rtamd.h"
+#include "device/rt_device.h"
+#include "host/rt_accum_state.h"
 #include "host/shared_prep.h"
-
-namespace rtamd { void set_error(const std::string &msg); }
 
 namespace {
 
@@ -38,6 +40,43 @@ __global__ void assemble_tiles_kernel(const T *shard_buf, T *frame, int width, i
         if (x < width && y < height) frame[((size_t)y * width + x) * 3 + c] = shard_buf[i];
     }
 }
+
+// Resumable state between the order of a shard (rt_accum of shard `shard` of `count`: the 8x8 sub-tiles of its tiles) and the frame order
+// of the portable checkpoint (device/rt_device.h shard_slot_to_frame_slot).  A state is n x {sum r, g, b, engine} as uint4, then n x {saved,
+// has_saved} as uint2.  One thread per slot of the shard: a wave moves one sub-tile, 1 KB + 512 B, contiguous on both sides.
+struct Regroup { int tile, tiles_x, sub_w, sub_h; uint32_t shard, count, n_slots, frame_slots; };
+__global__ __launch_bounds__(256) void shard_to_frame_kernel(const uint32_t *shard_state, uint32_t *frame_state, Regroup G) {
+    const uint4 *s4 = reinterpret_cast<const uint4 *>(shard_state);
+    const uint2 *s2 = reinterpret_cast<const uint2 *>(shard_state + 4 * (size_t)G.n_slots);
+    uint4 *f4 = reinterpret_cast<uint4 *>(frame_state);
+    uint2 *f2 = reinterpret_cast<uint2 *>(frame_state + 4 * (size_t)G.frame_slots);
+    for (uint32_t s = blockIdx.x * 256u + threadIdx.x; s < G.n_slots; s += gridDim.x * 256u) {
+        uint32_t f;
+        if (!rtamd::dev::shard_slot_to_frame_slot(G.tile, G.tiles_x, G.sub_w, G.sub_h, G.shard, G.count, s, f)) continue; // a padding sub-tile
+        f4[f] = s4[s]; f2[f] = s2[s];
+    }
+}
+// ... and back; the shard's padding sub-tiles get the zeros a fresh state has there (accum_seed_kernel)
+__global__ __launch_bounds__(256) void frame_to_shard_kernel(const uint32_t *frame_state, uint32_t *shard_state, Regroup G) {
+    const uint4 *f4 = reinterpret_cast<const uint4 *>(frame_state);
+    const uint2 *f2 = reinterpret_cast<const uint2 *>(frame_state + 4 * (size_t)G.frame_slots);
+    uint4 *s4 = reinterpret_cast<uint4 *>(shard_state);
+    uint2 *s2 = reinterpret_cast<uint2 *>(shard_state + 4 * (size_t)G.n_slots);
+    for (uint32_t s = blockIdx.x * 256u + threadIdx.x; s < G.n_slots; s += gridDim.x * 256u) {
+        uint32_t f;
+        const bool in_frame = rtamd::dev::shard_slot_to_frame_slot(G.tile, G.tiles_x, G.sub_w, G.sub_h, G.shard, G.count, s, f);
+        s4[s] = in_frame ? f4[f] : make_uint4(0u, 0u, 0u, 0u);
+        s2[s] = in_frame ? f2[f] : make_uint2(0u, 0u);
+    }
+}
+
+// The host threads of a call, one per device: joined on every way out, so that a thread that could not be started (emplace_back
+// throws std::system_error) leaves the started ones finished behind it instead of a std::terminate in their destructors.
+struct Threads {
+    std::vector<std::thread> th;
+    void join() { for (auto &t : th) if (t.joinable()) t.join(); }
+    ~Threads() { join(); }
+};
 
 struct DeviceSlot {
     int device = 0;
@@ -60,6 +99,12 @@ struct rt_multi {
     float *frame_rgb = nullptr;
     uint8_t *frame_rgb8 = nullptr;
     size_t frame_cap_rgb = 0, frame_cap_rgb8 = 0;
+    // on device 0, for the checkpoints of rt_multi_accum: landing areas of the other devices' states and the state in frame order
+    std::vector<uint32_t *> land_state;
+    std::vector<size_t> land_cap_state;
+    uint32_t *frame_state = nullptr;
+    size_t frame_cap_state = 0;
+    hipEvent_t state_ready = nullptr; // recorded on device 0's stream when a loaded state has been regrouped for every shard
     ~rt_multi() {
         for (size_t i = 0; i < dev.size(); i++) {
             if (!dev[i].scene && !dev[i].stream && !dev[i].d_rgb && !dev[i].d_rgb8) continue; // nothing was created on it (it may not even exist)
@@ -75,6 +120,9 @@ struct rt_multi {
         for (uint8_t *p : land_rgb8) if (p) (void)hipFree(p);
         if (frame_rgb) (void)hipFree(frame_rgb);
         if (frame_rgb8) (void)hipFree(frame_rgb8);
+        for (uint32_t *p : land_state) if (p) (void)hipFree(p);
+        if (frame_state) (void)hipFree(frame_state);
+        if (state_ready) (void)hipEventDestroy(state_ready);
         (void)hipGetLastError(); // a failed teardown call must not surface in somebody else's next launch check
     }
 };
@@ -92,6 +140,101 @@ template <class T> static int grow(T *&p, size_t &cap, size_t elems) {
     MHIP(hipMalloc((void **)&p, elems * sizeof(T)));
     cap = elems;
     return RT_OK;
+}
+
+// The exchange step of a frame, shared by rt_multi_render and rt_multi_accum_resolve.  Every device fills its compact shard buffers
+// from its own host thread (`produce(i, d_rgb, d_rgb8)`, an rt_status with the message left in rt_last_error; elems[i] == 0: an
+// empty shard, not called) and pushes them to its landing area on device 0 (hipMemcpyPeerAsync on its own stream, then an event);
+// device 0's stream waits for each event and scatters that shard's tiles into the frame, which is read back to the host or, with
+// out_dev, assembled in the caller's memory on device 0.  One device: its buffers hold the plain frame, which is copied out.
+template <class Produce>
+static int exchange_frame(rt_multi *m, const std::string &who, int width, int height, int tile, bool out_dev, float *out_rgb, uint8_t *out_rgb8,
+                          const std::vector<size_t> &elems, Produce produce) {
+    const int N = (int)m->dev.size();
+    // landing areas on device 0 and the frame, before any thread starts (allocations on device 0 from this thread only)
+    const int dev0 = m->dev[0].device;
+    MHIP(hipSetDevice(dev0));
+    hipStream_t s0 = m->dev[0].stream;
+    const size_t frame_elems = (size_t)width * height * 3;
+    float *frame_rgb = nullptr;
+    uint8_t *frame_rgb8 = nullptr;
+    if (N > 1) {
+        if (out_rgb) { if (out_dev) frame_rgb = out_rgb; else { int r = grow(m->frame_rgb, m->frame_cap_rgb, frame_elems); if (r != RT_OK) return r; frame_rgb = m->frame_rgb; } }
+        if (out_rgb8) { if (out_dev) frame_rgb8 = out_rgb8; else { int r = grow(m->frame_rgb8, m->frame_cap_rgb8, frame_elems); if (r != RT_OK) return r; frame_rgb8 = m->frame_rgb8; } }
+        for (int i = 1; i < N; i++) {
+            if (elems[i] == 0) continue;
+            if (out_rgb) { int r = grow(m->land_rgb[i], m->land_cap_rgb[i], elems[i]); if (r != RT_OK) return r; }
+            if (out_rgb8) { int r = grow(m->land_rgb8[i], m->land_cap_rgb8[i], elems[i]); if (r != RT_OK) return r; }
+        }
+    }
+    // every device fills its shard from its own host thread and pushes it to device 0 as soon as it is done
+    std::vector<int> rc((size_t)N, RT_OK);
+    std::vector<std::string> err((size_t)N);
+    {
+        Threads threads;
+        for (int i = 0; i < N; i++)
+            threads.th.emplace_back([&, i] {
+                DeviceSlot &d = m->dev[i];
+                if (hipSetDevice(d.device) != hipSuccess) { rc[i] = RT_ERR_HIP; err[i] = "hipSetDevice failed"; return; }
+                if (elems[i] == 0) return; // more devices than tiles
+                if (out_rgb && (rc[i] = grow(d.d_rgb, d.cap_rgb, elems[i])) != RT_OK) { err[i] = rt_last_error(); return; }
+                if (out_rgb8 && (rc[i] = grow(d.d_rgb8, d.cap_rgb8, elems[i])) != RT_OK) { err[i] = rt_last_error(); return; }
+                rc[i] = produce(i, out_rgb ? d.d_rgb : nullptr, out_rgb8 ? d.d_rgb8 : nullptr);
+                if (rc[i] != RT_OK) { err[i] = rt_last_error(); return; }
+                if (i > 0 && N > 1) { // the push: this device's stream, this device's link
+                    hipError_t e = hipSuccess;
+                    if (out_rgb) e = hipMemcpyPeerAsync(m->land_rgb[i], dev0, d.d_rgb, d.device, elems[i] * sizeof(float), d.stream);
+                    if (e == hipSuccess && out_rgb8) e = hipMemcpyPeerAsync(m->land_rgb8[i], dev0, d.d_rgb8, d.device, elems[i], d.stream);
+                    if (e == hipSuccess) e = hipEventRecord(d.done, d.stream);
+                    if (e != hipSuccess) { rc[i] = RT_ERR_HIP; err[i] = std::string("shard push: ") + hipGetErrorString(e); }
+                }
+            });
+    }
+    for (int i = 0; i < N; i++)
+        if (rc[i] != RT_OK) return fail(rc[i], who + "device " + std::to_string(m->dev[i].device) + ": " + err[i]);
+    // tiles -> frame on device 0, each shard as soon as its push has landed
+    MHIP(hipSetDevice(dev0));
+    if (N == 1) { frame_rgb = m->dev[0].d_rgb; frame_rgb8 = m->dev[0].d_rgb8; }
+    else {
+        const int tiles_x = (width + tile - 1) / tile, tiles_y = (height + tile - 1) / tile;
+        const uint32_t total_tiles = (uint32_t)tiles_x * (uint32_t)tiles_y;
+        for (int i = 0; i < N; i++) {
+            if (elems[i] == 0) continue;
+            const uint32_t n_tiles = (total_tiles - (uint32_t)i + (uint32_t)N - 1) / (uint32_t)N;
+            const float *src_rgb = i ? m->land_rgb[i] : m->dev[0].d_rgb;
+            const uint8_t *src_rgb8 = i ? m->land_rgb8[i] : m->dev[0].d_rgb8;
+            if (i > 0) MHIP(hipStreamWaitEvent(s0, m->dev[i].done, 0));
+            const unsigned blocks = (unsigned)((elems[i] + 255) / 256 < 65535 ? (elems[i] + 255) / 256 : 65535);
+            if (out_rgb) hipLaunchKernelGGL(assemble_tiles_kernel<float>, dim3(blocks), dim3(256), 0, s0, src_rgb, frame_rgb, width, height, tile, tiles_x, i, N, n_tiles);
+            if (out_rgb8) hipLaunchKernelGGL(assemble_tiles_kernel<uint8_t>, dim3(blocks), dim3(256), 0, s0, src_rgb8, frame_rgb8, width, height, tile, tiles_x, i, N, n_tiles);
+        }
+        MHIP(hipGetLastError());
+    }
+    if (!out_dev) {
+        if (out_rgb) MHIP(hipMemcpyAsync(out_rgb, frame_rgb, frame_elems * sizeof(float), hipMemcpyDeviceToHost, s0));
+        if (out_rgb8) MHIP(hipMemcpyAsync(out_rgb8, frame_rgb8, frame_elems, hipMemcpyDeviceToHost, s0));
+    } else if (N == 1) {
+        if (out_rgb) MHIP(hipMemcpyAsync(out_rgb, frame_rgb, frame_elems * sizeof(float), hipMemcpyDeviceToDevice, s0));
+        if (out_rgb8) MHIP(hipMemcpyAsync(out_rgb8, frame_rgb8, frame_elems, hipMemcpyDeviceToDevice, s0));
+    }
+    MHIP(hipStreamSynchronize(s0));
+    return RT_OK;
+}
+
+// rt_stats of a call on all devices from the shards' (empty shards left out): sums, except the times of devices that work side by side
+static void sum_stats(const std::vector<rt_stats> &st, const std::vector<size_t> &work, rt_stats *stats) {
+    memset(stats, 0, sizeof *stats);
+    for (size_t i = 0; i < st.size(); i++) {
+        if (work[i] == 0) continue;
+        stats->kernel_ms = st[i].kernel_ms > stats->kernel_ms ? st[i].kernel_ms : stats->kernel_ms;            // the devices render side by side
+        stats->dominant_kernel_ms = st[i].dominant_kernel_ms > stats->dominant_kernel_ms ? st[i].dominant_kernel_ms : stats->dominant_kernel_ms;
+        stats->samples += st[i].samples;
+        stats->closest_hit_queries += st[i].closest_hit_queries; stats->light_pdf_queries += st[i].light_pdf_queries;
+        stats->node_visits += st[i].node_visits; stats->triangle_tests += st[i].triangle_tests;
+        stats->launches += st[i].launches; stats->dominant_kernel_launches += st[i].dominant_kernel_launches;
+        stats->exact_closest_hits += st[i].exact_closest_hits; stats->exact_light_sums += st[i].exact_light_sums;
+        stats->pipeline = st[i].pipeline;
+    }
 }
 
 extern "C" {
@@ -118,9 +261,9 @@ int rt_multi_create(const rt_scene_desc *desc, const int *devices, int n_devices
     // one scene per device; the host-side preparation (BVH replay) of each runs on its own thread
     std::vector<int> rc((size_t)n_devices, RT_OK);
     std::vector<std::string> err((size_t)n_devices);
-    std::vector<std::thread> th;
+    Threads threads;
     for (int i = 0; i < n_devices; i++)
-        th.emplace_back([&, i] {
+        threads.th.emplace_back([&, i] {
             if (hipSetDevice(m->dev[i].device) != hipSuccess) { rc[i] = RT_ERR_HIP; err[i] = "hipSetDevice failed"; return; }
             rc[i] = rtamd::scene_create_shared(desc, &m->dev[i].scene, &prep);
             if (rc[i] != RT_OK) { err[i] = rt_last_error(); return; }
@@ -128,7 +271,7 @@ int rt_multi_create(const rt_scene_desc *desc, const int *devices, int n_devices
                 rc[i] = RT_ERR_HIP; err[i] = "stream / event creation failed";
             }
         });
-    for (auto &t : th) t.join();
+    threads.join();
     for (int i = 0; i < n_devices; i++)
         if (rc[i] != RT_OK) return fail(rc[i], "rt_multi_create: device " + std::to_string(m->dev[i].device) + ": " + err[i]);
     // peer access from every sender towards device 0 — the direction of its push — where the hardware offers it (hipMemcpyPeerAsync
@@ -145,6 +288,8 @@ int rt_multi_create(const rt_scene_desc *desc, const int *devices, int n_devices
     (void)hipSetDevice(m->dev[0].device);
     m->land_rgb.assign((size_t)n_devices, nullptr); m->land_rgb8.assign((size_t)n_devices, nullptr);
     m->land_cap_rgb.assign((size_t)n_devices, 0); m->land_cap_rgb8.assign((size_t)n_devices, 0);
+    m->land_state.assign((size_t)n_devices, nullptr); m->land_cap_state.assign((size_t)n_devices, 0);
+    MHIP(hipEventCreateWithFlags(&m->state_ready, hipEventDisableTiming));
     *out = m.release();
     return RT_OK;
     } catch (const std::exception &e) { // std::bad_alloc, std::system_error of a thread: nothing may cross the C boundary
@@ -178,86 +323,13 @@ int rt_multi_render(rt_multi *m, const rt_render_params *params, float *out_rgb,
     }
     if (params->width <= 0 || params->height <= 0 || params->samples <= 0) return fail(RT_ERR_INVALID_ARG, "rt_multi_render: width, height and samples must be positive");
     try {
-    // landing areas on device 0 and the frame, before any thread starts (allocations on device 0 from this thread only)
-    const int dev0 = m->dev[0].device;
-    MHIP(hipSetDevice(dev0));
-    hipStream_t s0 = m->dev[0].stream;
-    const size_t frame_elems = (size_t)params->width * params->height * 3;
-    float *frame_rgb = nullptr;
-    uint8_t *frame_rgb8 = nullptr;
-    if (N > 1) {
-        if (out_rgb) { if (out_dev) frame_rgb = out_rgb; else { int r = grow(m->frame_rgb, m->frame_cap_rgb, frame_elems); if (r != RT_OK) return r; frame_rgb = m->frame_rgb; } }
-        if (out_rgb8) { if (out_dev) frame_rgb8 = out_rgb8; else { int r = grow(m->frame_rgb8, m->frame_cap_rgb8, frame_elems); if (r != RT_OK) return r; frame_rgb8 = m->frame_rgb8; } }
-        for (int i = 1; i < N; i++) {
-            if (elems[i] == 0) continue;
-            if (out_rgb) { int r = grow(m->land_rgb[i], m->land_cap_rgb[i], elems[i]); if (r != RT_OK) return r; }
-            if (out_rgb8) { int r = grow(m->land_rgb8[i], m->land_cap_rgb8[i], elems[i]); if (r != RT_OK) return r; }
-        }
-    }
-    // every device renders its shard from its own host thread and pushes it to device 0 as soon as it is done
-    std::vector<int> rc((size_t)N, RT_OK);
-    std::vector<std::string> err((size_t)N);
     std::vector<rt_stats> st((size_t)N);
-    std::vector<std::thread> th;
-    for (int i = 0; i < N; i++)
-        th.emplace_back([&, i] {
-            DeviceSlot &d = m->dev[i];
-            if (hipSetDevice(d.device) != hipSuccess) { rc[i] = RT_ERR_HIP; err[i] = "hipSetDevice failed"; return; }
-            if (elems[i] == 0) { memset(&st[i], 0, sizeof st[i]); return; } // more devices than tiles
-            if (out_rgb && (rc[i] = grow(d.d_rgb, d.cap_rgb, elems[i])) != RT_OK) { err[i] = rt_last_error(); return; }
-            if (out_rgb8 && (rc[i] = grow(d.d_rgb8, d.cap_rgb8, elems[i])) != RT_OK) { err[i] = rt_last_error(); return; }
-            rc[i] = rt_render(d.scene, &p[i], out_rgb ? d.d_rgb : nullptr, out_rgb8 ? d.d_rgb8 : nullptr, &st[i]);
-            if (rc[i] != RT_OK) { err[i] = rt_last_error(); return; }
-            if (i > 0 && N > 1) { // the push: this device's stream, this device's link
-                hipError_t e = hipSuccess;
-                if (out_rgb) e = hipMemcpyPeerAsync(m->land_rgb[i], dev0, d.d_rgb, d.device, elems[i] * sizeof(float), d.stream);
-                if (e == hipSuccess && out_rgb8) e = hipMemcpyPeerAsync(m->land_rgb8[i], dev0, d.d_rgb8, d.device, elems[i], d.stream);
-                if (e == hipSuccess) e = hipEventRecord(d.done, d.stream);
-                if (e != hipSuccess) { rc[i] = RT_ERR_HIP; err[i] = std::string("shard push: ") + hipGetErrorString(e); }
-            }
-        });
-    for (auto &t : th) t.join();
-    for (int i = 0; i < N; i++)
-        if (rc[i] != RT_OK) return fail(rc[i], "rt_multi_render: device " + std::to_string(m->dev[i].device) + ": " + err[i]);
-    // tiles -> frame on device 0, each shard as soon as its push has landed
-    MHIP(hipSetDevice(dev0));
-    if (N == 1) { frame_rgb = m->dev[0].d_rgb; frame_rgb8 = m->dev[0].d_rgb8; }
-    else {
-        const int tiles_x = (params->width + tile - 1) / tile, tiles_y = (params->height + tile - 1) / tile;
-        const uint32_t total_tiles = (uint32_t)tiles_x * (uint32_t)tiles_y;
-        for (int i = 0; i < N; i++) {
-            if (elems[i] == 0) continue;
-            const uint32_t n_tiles = (total_tiles - (uint32_t)i + (uint32_t)N - 1) / (uint32_t)N;
-            const float *src_rgb = i ? m->land_rgb[i] : m->dev[0].d_rgb;
-            const uint8_t *src_rgb8 = i ? m->land_rgb8[i] : m->dev[0].d_rgb8;
-            if (i > 0) MHIP(hipStreamWaitEvent(s0, m->dev[i].done, 0));
-            const unsigned blocks = (unsigned)((elems[i] + 255) / 256 < 65535 ? (elems[i] + 255) / 256 : 65535);
-            if (out_rgb) hipLaunchKernelGGL(assemble_tiles_kernel<float>, dim3(blocks), dim3(256), 0, s0, src_rgb, frame_rgb, params->width, params->height, tile, tiles_x, i, N, n_tiles);
-            if (out_rgb8) hipLaunchKernelGGL(assemble_tiles_kernel<uint8_t>, dim3(blocks), dim3(256), 0, s0, src_rgb8, frame_rgb8, params->width, params->height, tile, tiles_x, i, N, n_tiles);
-        }
-        MHIP(hipGetLastError());
-    }
-    if (!out_dev) {
-        if (out_rgb) MHIP(hipMemcpyAsync(out_rgb, frame_rgb, frame_elems * sizeof(float), hipMemcpyDeviceToHost, s0));
-        if (out_rgb8) MHIP(hipMemcpyAsync(out_rgb8, frame_rgb8, frame_elems, hipMemcpyDeviceToHost, s0));
-    } else if (N == 1) {
-        if (out_rgb) MHIP(hipMemcpyAsync(out_rgb, frame_rgb, frame_elems * sizeof(float), hipMemcpyDeviceToDevice, s0));
-        if (out_rgb8) MHIP(hipMemcpyAsync(out_rgb8, frame_rgb8, frame_elems, hipMemcpyDeviceToDevice, s0));
-    }
-    MHIP(hipStreamSynchronize(s0));
+    for (auto &x : st) memset(&x, 0, sizeof x);
+    const int rc = exchange_frame(m, "rt_multi_render: ", params->width, params->height, tile, out_dev, out_rgb, out_rgb8, elems,
+                                  [&](int i, float *d_rgb, uint8_t *d_rgb8) { return rt_render(m->dev[i].scene, &p[i], d_rgb, d_rgb8, &st[i]); });
+    if (rc != RT_OK) return rc;
     if (stats) {
-        memset(stats, 0, sizeof *stats);
-        for (int i = 0; i < N; i++) {
-            if (elems[i] == 0) continue;
-            stats->kernel_ms = st[i].kernel_ms > stats->kernel_ms ? st[i].kernel_ms : stats->kernel_ms;            // the devices render side by side
-            stats->dominant_kernel_ms = st[i].dominant_kernel_ms > stats->dominant_kernel_ms ? st[i].dominant_kernel_ms : stats->dominant_kernel_ms;
-            stats->samples += st[i].samples;
-            stats->closest_hit_queries += st[i].closest_hit_queries; stats->light_pdf_queries += st[i].light_pdf_queries;
-            stats->node_visits += st[i].node_visits; stats->triangle_tests += st[i].triangle_tests;
-            stats->launches += st[i].launches; stats->dominant_kernel_launches += st[i].dominant_kernel_launches;
-            stats->exact_closest_hits += st[i].exact_closest_hits; stats->exact_light_sums += st[i].exact_light_sums;
-            stats->pipeline = st[i].pipeline;
-        }
+        sum_stats(st, elems, stats);
         stats->total_ms = now_ms() - t0; // host wall time of the whole call: renders, exchange, read-back
     }
     return RT_OK;
@@ -266,6 +338,249 @@ int rt_multi_render(rt_multi *m, const rt_render_params *params, float *out_rgb,
     } catch (...) {
         return fail(RT_ERR_INVALID_ARG, "rt_multi_render: unknown exception");
     }
+}
+
+// ---- resumable renders on all devices (include/rtamd.h: rt_multi_accum_*) ---------------------------------------------------
+// One sharded rt_accum per device entry (shard i of N on that entry's stream; none for an entry that gets no tile), advanced side
+// by side; the picture goes through the exchange of rt_multi_render; the checkpoint is regrouped on device 0 into the frame order,
+// where it is the blob of the unsharded single-device rt_accum.  With one entry the rt_accum IS that unsharded one.
+struct rt_multi_accum {
+    rt_multi *multi = nullptr;
+    rt_render_params params{};       // of the unsharded frame, as given
+    int tile = 32;
+    rtamd::RenderView frame{};       // geometry of the unsharded frame: 8x8 tiles, shard 0 of 1
+    uint32_t frame_slots = 0;        // ceil(W/8) * ceil(H/8) * 64
+    std::vector<rt_accum *> shard;   // per device entry; null = an empty shard
+    std::vector<size_t> elems;       // floats (or bytes) of each shard's compact picture
+    int32_t samples = 0, sample_limit = 0;
+    std::string broken;              // first error of a call that failed under way on some device
+    ~rt_multi_accum() { for (rt_accum *a : shard) if (a) rt_accum_destroy(a); }
+};
+
+static Regroup regroup_of(const rt_multi_accum *a, int i) {
+    Regroup G;
+    G.tile = a->tile; G.tiles_x = (a->params.width + a->tile - 1) / a->tile; G.sub_w = a->frame.tiles_x; G.sub_h = a->frame.tiles_y;
+    G.shard = (uint32_t)i; G.count = (uint32_t)a->shard.size(); G.n_slots = a->shard[i]->n_pixslots; G.frame_slots = a->frame_slots;
+    return G;
+}
+static unsigned regroup_blocks(uint32_t n_slots) { return (n_slots + 255u) / 256u < 65535u ? (n_slots + 255u) / 256u : 65535u; }
+
+int rt_multi_accum_create(rt_multi *m, const rt_render_params *params, rt_multi_accum **out) {
+    if (!m || !params || !out) return fail(RT_ERR_INVALID_ARG, "rt_multi_accum_create: null argument");
+    *out = nullptr;
+    if (params->struct_size != sizeof(rt_render_params)) return fail(RT_ERR_INVALID_ARG, "rt_multi_accum_create: struct_size mismatch (ABI skew)");
+    if (params->shard_count > 1) return fail(RT_ERR_INVALID_ARG, "rt_multi_accum_create: the frame is sharded over the devices here; shard_count must be 0 or 1");
+    const int tile = params->tile_w > 0 ? params->tile_w : 32;
+    if (params->tile_h > 0 && params->tile_h != tile) return fail(RT_ERR_INVALID_ARG, "rt_multi_accum_create: square tiles only");
+    try {
+    const int N = (int)m->dev.size();
+    std::unique_ptr<rt_multi_accum> a(new rt_multi_accum());
+    a->multi = m; a->params = *params; a->params.samples = 0; a->params.shard_index = 0; a->params.shard_count = 1; a->tile = tile;
+    a->shard.assign((size_t)N, nullptr); a->elems.assign((size_t)N, 0);
+    a->sample_limit = 0;
+    for (int i = 0; i < N; i++) {
+        rt_render_params p = a->params;
+        p.stream = m->dev[i].stream;
+        if (N > 1) { p.shard_index = i; p.shard_count = N; p.tile_w = p.tile_h = tile; }
+        p.samples = 1; // ignored by rt_accum_create, looked at by rt_output_elems
+        a->elems[i] = N > 1 ? rt_output_elems(&p) : (size_t)(params->width > 0 && params->height > 0 ? (size_t)params->width * params->height * 3 : 0);
+        if (i > 0 && a->elems[i] == 0) continue; // more devices than tiles; the first entry always has a tile, and makes every refusal
+        MHIP(hipSetDevice(m->dev[i].device));
+        const int rc = rt_accum_create(m->dev[i].scene, &p, &a->shard[i]);
+        if (rc != RT_OK) return fail(rc, "rt_multi_accum_create: device " + std::to_string(m->dev[i].device) + ": " + rt_last_error());
+        if (a->sample_limit == 0 || a->shard[i]->sample_limit < a->sample_limit) a->sample_limit = a->shard[i]->sample_limit;
+    }
+    std::string err;
+    rt_render_params q = a->params;
+    q.samples = 1;
+    if (!rtamd::resolve_tiles(&q, a->frame, err)) return fail(RT_ERR_INVALID_ARG, "rt_multi_accum_create: " + err);
+    a->frame_slots = (uint32_t)a->frame.tiles_x * (uint32_t)a->frame.tiles_y * 64u; // below 2^30: rt_accum_create has taken shard 0 of this frame
+    MHIP(hipSetDevice(m->dev[0].device));
+    *out = a.release();
+    return RT_OK;
+    } catch (const std::exception &e) {
+        return fail(RT_ERR_INVALID_ARG, std::string("rt_multi_accum_create: ") + e.what());
+    } catch (...) {
+        return fail(RT_ERR_INVALID_ARG, "rt_multi_accum_create: unknown exception");
+    }
+}
+
+void rt_multi_accum_destroy(rt_multi_accum *a) { delete a; }
+
+int rt_multi_accum_samples(const rt_multi_accum *a) {
+    if (!a) return fail(RT_ERR_INVALID_ARG, "rt_multi_accum_samples: null argument");
+    return a->samples;
+}
+
+#define MA_ENTER(name)                                                                                                                      \
+    if (!a) return fail(RT_ERR_INVALID_ARG, name ": null argument");                                                                          \
+    if (!a->broken.empty()) return fail(RT_ERR_INVALID_ARG, name ": an earlier call failed under way and left the state half advanced (" + a->broken + ")")
+// a failure after the devices have started: the object is broken from here on
+#define MA_BREAK(rc_) do { a->broken = rt_last_error(); return (rc_); } while (0)
+
+int rt_multi_accum_render(rt_multi_accum *a, int32_t n_samples, rt_stats *stats) {
+    MA_ENTER("rt_multi_accum_render");
+    rt_multi *m = a->multi;
+    const int N = (int)a->shard.size();
+    const double t0 = now_ms();
+    if (n_samples <= 0) return fail(RT_ERR_INVALID_ARG, "rt_multi_accum_render: n_samples must be positive");
+    if ((int64_t)a->samples + n_samples >= (int64_t)a->sample_limit)
+        return fail(RT_ERR_LIMIT, "rt_multi_accum_render: " + std::to_string(a->samples) + " + " + std::to_string(n_samples) + " samples per pixel do not fit the path records' sample index (below " + std::to_string(a->sample_limit) + " on some device)");
+    for (int i = 0; i < N; i++) // every refusal before any device launches: the state stays as it was
+        if (a->shard[i]) if (const int rc = rtamd::accum_check_slice(a->shard[i], n_samples, "rt_multi_accum_render: device " + std::to_string(m->dev[i].device) + ": ")) return rc;
+    try {
+    std::vector<int> rc((size_t)N, RT_OK);
+    std::vector<std::string> err((size_t)N);
+    std::vector<rt_stats> st((size_t)N);
+    for (auto &x : st) memset(&x, 0, sizeof x);
+    {
+        Threads threads;
+        for (int i = 0; i < N; i++)
+            if (a->shard[i])
+                threads.th.emplace_back([&, i] {
+                    if (hipSetDevice(m->dev[i].device) != hipSuccess) { rc[i] = RT_ERR_HIP; err[i] = "hipSetDevice failed"; return; }
+                    rc[i] = rt_accum_render(a->shard[i], n_samples, &st[i]);
+                    if (rc[i] != RT_OK) err[i] = rt_last_error();
+                });
+    }
+    (void)hipSetDevice(m->dev[0].device);
+    for (int i = 0; i < N; i++)
+        if (rc[i] != RT_OK) { fail(rc[i], "rt_multi_accum_render: device " + std::to_string(m->dev[i].device) + ": " + err[i]); MA_BREAK(rc[i]); }
+    a->samples += n_samples;
+    if (stats) {
+        sum_stats(st, a->elems, stats);
+        stats->samples = (uint64_t)a->params.width * (uint64_t)a->params.height * (uint64_t)n_samples;
+        stats->reference_exact = 1;
+        for (int i = 0; i < N; i++) if (a->shard[i]) stats->reference_exact &= st[i].reference_exact;
+        stats->total_ms = now_ms() - t0;
+    }
+    return RT_OK;
+    } catch (const std::exception &e) { // a thread that could not be started: the others have run
+        fail(RT_ERR_INVALID_ARG, std::string("rt_multi_accum_render: ") + e.what());
+        MA_BREAK(RT_ERR_INVALID_ARG);
+    } catch (...) {
+        fail(RT_ERR_INVALID_ARG, "rt_multi_accum_render: unknown exception");
+        MA_BREAK(RT_ERR_INVALID_ARG);
+    }
+}
+
+int rt_multi_accum_resolve(rt_multi_accum *a, uint32_t flags, float *out_rgb, uint8_t *out_rgb8) {
+    MA_ENTER("rt_multi_accum_resolve");
+    if (flags & ~RT_FLAG_OUT_DEVICE) return fail(RT_ERR_INVALID_ARG, "rt_multi_accum_resolve: flags other than RT_FLAG_OUT_DEVICE");
+    if (a->samples <= 0) return fail(RT_ERR_INVALID_ARG, "rt_multi_accum_resolve: no samples yet (a picture needs at least one)");
+    if (!out_rgb && !out_rgb8) return RT_OK;
+    try {
+        // the state is only read; each device resolves its shard on device in the compact layout (accum_resolve_kernel)
+        return exchange_frame(a->multi, "rt_multi_accum_resolve: ", a->params.width, a->params.height, a->tile, (flags & RT_FLAG_OUT_DEVICE) != 0, out_rgb, out_rgb8, a->elems,
+                              [&](int i, float *d_rgb, uint8_t *d_rgb8) { return rt_accum_resolve(a->shard[i], RT_FLAG_OUT_DEVICE, d_rgb, d_rgb8); });
+    } catch (const std::exception &e) {
+        return fail(RT_ERR_INVALID_ARG, std::string("rt_multi_accum_resolve: ") + e.what());
+    } catch (...) {
+        return fail(RT_ERR_INVALID_ARG, "rt_multi_accum_resolve: unknown exception");
+    }
+}
+
+// Save: every device pushes its shard's state to its landing area on device 0 (its own stream, an event), device 0 scatters each
+// landed shard into the frame-order buffer and copies header + buffer to the host once.
+int rt_multi_accum_save(rt_multi_accum *a, void *blob, size_t capacity) {
+    MA_ENTER("rt_multi_accum_save");
+    if (!blob) return fail(RT_ERR_INVALID_ARG, "rt_multi_accum_save: null argument");
+    const size_t state = (size_t)a->frame_slots * ACCUM_SLOT_BYTES;
+    if (capacity < ACCUM_HEADER_BYTES + state) return fail(RT_ERR_INVALID_ARG, "rt_multi_accum_save: buffer smaller than rt_accum_state_bytes of the unsharded frame");
+    rt_multi *m = a->multi;
+    const int N = (int)a->shard.size();
+    if (N == 1) { // the unsharded rt_accum itself
+        MHIP(hipSetDevice(m->dev[0].device));
+        const int rc = rt_accum_save(a->shard[0], blob, capacity);
+        return rc == RT_OK ? rc : fail(rc, std::string("rt_multi_accum_save: ") + rt_last_error());
+    }
+    const int dev0 = m->dev[0].device;
+    hipStream_t s0 = m->dev[0].stream;
+    MHIP(hipSetDevice(dev0));
+    { int r = grow(m->frame_state, m->frame_cap_state, (size_t)a->frame_slots * (ACCUM_SLOT_BYTES / 4)); if (r != RT_OK) return r; }
+    for (int i = 1; i < N; i++)
+        if (a->shard[i]) { int r = grow(m->land_state[i], m->land_cap_state[i], (size_t)a->shard[i]->n_pixslots * (ACCUM_SLOT_BYTES / 4)); if (r != RT_OK) return r; }
+    for (int i = 1; i < N; i++) { // the pushes: each on its device's stream, behind that device's last slice
+        if (!a->shard[i]) continue;
+        MHIP(hipSetDevice(m->dev[i].device));
+        MHIP(hipMemcpyPeerAsync(m->land_state[i], dev0, a->shard[i]->d_state, m->dev[i].device, (size_t)a->shard[i]->n_pixslots * ACCUM_SLOT_BYTES, m->dev[i].stream));
+        MHIP(hipEventRecord(m->dev[i].done, m->dev[i].stream));
+    }
+    MHIP(hipSetDevice(dev0));
+    for (int i = 0; i < N; i++) {
+        if (!a->shard[i]) continue;
+        if (i > 0) MHIP(hipStreamWaitEvent(s0, m->dev[i].done, 0));
+        const Regroup G = regroup_of(a, i);
+        hipLaunchKernelGGL(shard_to_frame_kernel, dim3(regroup_blocks(G.n_slots)), dim3(256), 0, s0, i ? m->land_state[i] : a->shard[0]->d_state, m->frame_state, G);
+    }
+    MHIP(hipGetLastError());
+    uint32_t h[ACCUM_HEADER_BYTES / 4];
+    accum_header(m->dev[0].scene, a->params.integrator, a->frame, a->frame_slots, a->samples, h);
+    memcpy(blob, h, ACCUM_HEADER_BYTES);
+    MHIP(hipMemcpyAsync((uint8_t *)blob + ACCUM_HEADER_BYTES, m->frame_state, state, hipMemcpyDeviceToHost, s0));
+    MHIP(hipStreamSynchronize(s0));
+    return RT_OK;
+}
+
+// Load: the reverse.  The blob goes to device 0, which gathers every shard's slots out of the frame order (its own shard in place,
+// the others into their landing areas); every other device then pulls its state over on its own stream.
+int rt_multi_accum_load(rt_multi_accum *a, const void *blob, size_t size) {
+    MA_ENTER("rt_multi_accum_load");
+    if (!blob) return fail(RT_ERR_INVALID_ARG, "rt_multi_accum_load: null argument");
+    if (size < ACCUM_HEADER_BYTES) return fail(RT_ERR_INVALID_ARG, "rt_multi_accum_load: truncated blob (shorter than its header)");
+    rt_multi *m = a->multi;
+    const int N = (int)a->shard.size();
+    uint32_t want[ACCUM_HEADER_BYTES / 4], got[ACCUM_HEADER_BYTES / 4];
+    accum_header(m->dev[0].scene, a->params.integrator, a->frame, a->frame_slots, a->samples, want);
+    memcpy(got, blob, ACCUM_HEADER_BYTES);
+    for (int f = 0; f < AH_WORDS; f++)
+        if (f != AH_SAMPLES && got[f] != want[f])
+            return fail(RT_ERR_INVALID_ARG, std::string("rt_multi_accum_load: the blob does not belong to this frame: ") + accum_field_names[f] + " is " + std::to_string(got[f]) +
+                                                ", expected " + std::to_string(want[f]));
+    if (got[AH_SAMPLES] >= (uint32_t)a->sample_limit) return fail(RT_ERR_INVALID_ARG, "rt_multi_accum_load: samples beyond the path records' sample index");
+    const size_t state = (size_t)a->frame_slots * ACCUM_SLOT_BYTES;
+    if (size < ACCUM_HEADER_BYTES + state) return fail(RT_ERR_INVALID_ARG, "rt_multi_accum_load: truncated blob (" + std::to_string(size) + " bytes, " + std::to_string(ACCUM_HEADER_BYTES + state) + " expected)");
+    if (N == 1) { // the unsharded rt_accum itself
+        MHIP(hipSetDevice(m->dev[0].device));
+        const int rc = rt_accum_load(a->shard[0], blob, size);
+        if (rc != RT_OK) return fail(rc, std::string("rt_multi_accum_load: ") + rt_last_error());
+        a->samples = (int32_t)got[AH_SAMPLES];
+        return RT_OK;
+    }
+    const int dev0 = m->dev[0].device;
+    hipStream_t s0 = m->dev[0].stream;
+    MHIP(hipSetDevice(dev0));
+    { int r = grow(m->frame_state, m->frame_cap_state, (size_t)a->frame_slots * (ACCUM_SLOT_BYTES / 4)); if (r != RT_OK) return r; }
+    for (int i = 1; i < N; i++)
+        if (a->shard[i]) { int r = grow(m->land_state[i], m->land_cap_state[i], (size_t)a->shard[i]->n_pixslots * (ACCUM_SLOT_BYTES / 4)); if (r != RT_OK) return r; }
+    // from here on the devices' states are being overwritten: a failure leaves the object broken
+    hipError_t e = hipMemcpyAsync(m->frame_state, (const uint8_t *)blob + ACCUM_HEADER_BYTES, state, hipMemcpyHostToDevice, s0);
+    for (int i = 0; i < N && e == hipSuccess; i++) {
+        if (!a->shard[i]) continue;
+        const Regroup G = regroup_of(a, i);
+        hipLaunchKernelGGL(frame_to_shard_kernel, dim3(regroup_blocks(G.n_slots)), dim3(256), 0, s0, m->frame_state, i ? m->land_state[i] : a->shard[0]->d_state, G);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipEventRecord(m->state_ready, s0);
+    for (int i = 1; i < N && e == hipSuccess; i++) {
+        if (!a->shard[i]) continue;
+        e = hipSetDevice(m->dev[i].device);
+        if (e == hipSuccess) e = hipStreamWaitEvent(m->dev[i].stream, m->state_ready, 0);
+        if (e == hipSuccess) e = hipMemcpyPeerAsync(a->shard[i]->d_state, m->dev[i].device, m->land_state[i], dev0, (size_t)a->shard[i]->n_pixslots * ACCUM_SLOT_BYTES, m->dev[i].stream);
+    }
+    for (int i = N - 1; i >= 0 && e == hipSuccess; i--) { // device 0 last: it becomes the current device again
+        if (!a->shard[i]) continue;
+        e = hipSetDevice(m->dev[i].device);
+        if (e == hipSuccess) e = hipStreamSynchronize(m->dev[i].stream);
+    }
+    if (e != hipSuccess) {
+        (void)hipSetDevice(dev0);
+        fail(RT_ERR_HIP, std::string("rt_multi_accum_load: ") + hipGetErrorString(e));
+        MA_BREAK(RT_ERR_HIP);
+    }
+    for (int i = 0; i < N; i++) if (a->shard[i]) a->shard[i]->samples = (int32_t)got[AH_SAMPLES];
+    a->samples = (int32_t)got[AH_SAMPLES];
+    return RT_OK;
 }
 
 } // extern "C"

@@ -104,6 +104,14 @@ int rtt_fold_nodes(const void *nodes, uint32_t n, const float *grid_box, void *o
         return (int)wide.size();
     } catch (...) { return -1; }
 }
+// shard_slot_to_frame_slot (rt_device.h) on the host (no GPU needed) for the n_slots slots of shard `shard` of `count` of a width x height frame
+// in square tiles: frame_slot[s] = the slot in frame order, in_frame[s] = 0 for a slot in a padding sub-tile.
+int rtt_shard_to_frame_slots(int width, int height, int tile, uint32_t shard, uint32_t count, uint32_t n_slots, uint32_t *frame_slot, uint8_t *in_frame) {
+    if (width <= 0 || height <= 0 || tile <= 0 || (tile & 7) || count == 0) return -1;
+    const int tiles_x = (width + tile - 1) / tile, sub_w = (width + 7) / 8, sub_h = (height + 7) / 8;
+    for (uint32_t s = 0; s < n_slots; s++) in_frame[s] = shard_slot_to_frame_slot(tile, tiles_x, sub_w, sub_h, shard, count, s, frame_slot[s]) ? 1 : 0;
+    return 0;
+}
 // grid_box: lo.xyz hi.xyz of what the grid must hold.  out bits: 1 float box entered, 2 grid box entered, 4 the box fits the grid, 8 grid entry <= float entry
 int rtt_slab_q(const float *cases, const float *grid_box, uint32_t *out, size_t n) {
     const rtamd::NodeGrid G = rtamd::make_node_grid(grid_box, grid_box + 3);

@@ -3,6 +3,8 @@
 #   hw8/run.sh:2-9   ./run.sh <scene.gltf> <width> <height> <samples> <out.ppm> [<envmap.png>]
 #   hw1/run.sh:2     ./run.sh <scene.txt> <out.ppm>
 # RTAMD_SNAPSHOT=hw1|hw3|hw6|hw8 picks which snapshot's integrator replays the scene (default hw8 / hw3).
+# RTAMD_SLICE=n / RTAMD_CHECKPOINT=path render the glTF surface in slices with a checkpoint, on every visible GPU;
+# RTAMD_DEVICE_LIST=0,1,3 names the HIP devices to use (the environment goes through to build/main as it is).
 if [ $# -eq 2 ]
 then
     ./build/main "$1" "$2"
