@@ -38,6 +38,7 @@
 // pt_tripwire: the leaf box of a triangle whose test accepts points far away from it) never go to the walkers at all.
 #pragma once
 #include "rt_wavefront.h"
+#include "rt_pt_queue.h" // the queues: pt_count, pt_ballot, pt_rank_below, pt_prefix, pt_pop, pt_push; PT_NONE
 
 namespace rtamd {
 namespace dev {
@@ -53,7 +54,6 @@ namespace dev {
 #define PT_NW (PT_MAX_PATHS / 32)
 #define PT_BIT_T 1u                   // pending: closest-hit walk outstanding
 #define PT_BIT_L 2u                   // pending: light-pdf sum outstanding
-#define PT_NONE 0xFFFFFFFFu
 // indices into PtShared::need / PtShared::cnt
 #define PT_Q_TRACE 0
 #define PT_Q_LIGHT 1
@@ -202,6 +202,7 @@ struct PtProf {
     unsigned long long t_part[2][3] = {{0, 0, 0}, {0, 0, 0}}, leaf_iters[2] = {0, 0}, leaf_lane_iters[2] = {0, 0}, light_hits = 0, light_tests = 0; // the last two per lane
     unsigned long long t_sub[2][3] = {{0, 0, 0}, {0, 0, 0}}, refills[2] = {0, 0}; // of [0]: publish finished walks | take new ones from the bitmap | read their rays
     unsigned long long light_reach[2] = {0, 0}; // light sums whose walk ends at the light tree's root / one level below it (pt_light_reach), per lane
+    PtPopStat pops[3];                          // what pt_pop handed out, by queue (PT_Q_TRACE, PT_Q_LIGHT, PT_Q_SHADE); flushed by the hw8 kernel only (CNT_P8_POPS)
 };
 template <bool COUNT> struct PtLap { // s_memtime laps of the counting build
     unsigned long long t;
@@ -219,108 +220,11 @@ struct PtWave {
 // A workgroup's paths come in groups of 2^shift consecutive slots (PtParams::group_shift: 6 = an 8x8 sub-tile, 4 = two rows of one): the unit of the deal.
 template <class SH> RT_DEV uint32_t pt_gshift(const SH &sh) { return (uint32_t)__builtin_amdgcn_readfirstlane(__hip_atomic_load(&sh.cnt[PT_GSHIFT], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)); }
 template <class SH> RT_DEV uint32_t pt_slot(const SH &sh, uint32_t l) { const uint32_t g = pt_gshift(sh); return (sh.groups[l >> g] << g) | (l & ((1u << g) - 1u)); }
-// A fresh LDS read each time; every lane reads the same word, and readfirstlane makes that explicit: the scheduler's decisions are
-// taken on SGPRs (scalar branches, wave-uniform by construction — the code under them uses __ballot / __shfl / lane-0 atomics).
-RT_DEV int pt_count(const int *p) { return __builtin_amdgcn_readfirstlane(__hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)); }
-
 // Lanes that must wait at a leaf before the wave runs its triangle tests: a share (leaf_batch >> 16, in 1/256) of the active lanes, at most
 // leaf_batch & 255.  Plain integer arithmetic on purpose: min() of an int and __popcll's result picks the double overload.
 RT_DEV int pt_leaf_batch(int leaf_batch, unsigned long long m_active) {
     const int cap = leaf_batch & 255, share = ((int)__popcll(m_active) * (leaf_batch >> 16) + 255) >> 8;
     return share < cap ? share : cap;
-}
-
-// The wave's mask of a predicate, straight from the compare (HIP's __ballot takes an int: a select and a second compare per call).
-RT_DEV unsigned long long pt_ballot(bool p) { return __builtin_amdgcn_ballot_w64(p); }
-// Number of set bits of a wave mask below this lane (v_mbcnt: no 64-bit lane mask in registers).
-RT_DEV uint32_t pt_rank_below(unsigned long long m) {
-    return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-}
-
-// Exclusive prefix sum over the wave of a small count per lane (0..63), without LDS: one ballot per bit of the counts.  `total` is wave-uniform.
-RT_DEV int pt_prefix(int x, int &total) {
-    int before = 0;
-    total = 0;
-    for (int b = 0; b < 6; b++) {
-        if (!pt_ballot((x >> b) != 0)) break;      // no lane has a bit at or above b (sparse queues: one or two rounds)
-        const unsigned long long m = pt_ballot((x >> b) & 1);
-        before += (int)pt_rank_below(m) << b;
-        total += __popcll(m) << b;
-    }
-    return before;
-}
-
-// Hands paths to the lanes that want one.  The wave reads 64 bitmap words at once (lane i: word cursor + i), then the words
-// claim for themselves — one LDS atomic instruction for all of them — and the claimed bits are dealt to the wanting lanes by rank, so a wave that
-// wants 64 paths from a dense queue gets the two words of one 8x8 sub-tile (coherent rays) for two LDS atomics.  A word that
-// holds more paths than are wanted keeps its upper bits and the cursor stays on it, so the next request starts there (no
-// path is passed over).  Returns the local path index or PT_NONE.
-// from_start: every request sweeps from word 0 — the paths at the front of the workgroup's list (its most expensive sub-tiles after a
-// re-deal) are always served first, so the longest serial chains (a pixel's samples are serial) never wait behind cheap work.
-RT_DEV uint32_t pt_pop(uint32_t *bm, int *cnt, const uint32_t nw, uint32_t &cursor, bool want, bool from_start = false) {
-    const uint32_t lane = threadIdx.x & 63u;
-    if (from_start) cursor = 0u;
-    const unsigned long long wantmask = pt_ballot(want);
-    const int need = __popcll(wantmask);
-    const int my_rank = (int)pt_rank_below(wantmask);
-    uint32_t got = PT_NONE;
-    int have = 0;                                                 // wave-uniform, like everything below that is not per word (= per lane) or `got`
-    for (uint32_t swept = 0; swept < nw && have < need; swept += 64u) {
-        uint32_t w = cursor + lane;
-        const bool valid = lane < nw;                                 // fewer than 64 words: the wave sees the whole ring at once
-        if (w >= nw) w -= nw;                                         // cursor < nw, and lane < nw where the word is read: no division
-        const uint32_t v = valid ? bm[w] : 0u;
-        // Every word claims for itself, all in ONE LDS atomic of the wave: word i may take what the words before it leave of the request
-        // (a prefix sum of the words' bit counts).  A claim can come back short (another wave was faster); the sweep then goes on.
-        const int pc = __popc(v);
-        int in_sight;
-        const int before = pt_prefix(pc, in_sight);
-        uint32_t next_cursor = cursor + 64u;
-        if (in_sight) {
-            const int room = need - have - before;
-            uint32_t take = 0u;
-            if (pc > 0 && room > 0) {
-                take = v;
-                if (room < pc) {                                  // the one word that is cut: its lowest `room` set bits
-                    uint32_t rest = v;
-                    for (int n = room; n > 0; n--) rest &= rest - 1u;
-                    take = v & ~rest;
-                }
-            }
-            uint32_t old = 0u;
-            if (take) old = atomicAnd(&bm[w], ~take) & take;     // the bits this word really gave
-            int claimed;
-            const int first = pt_prefix(__popc(old), claimed);   // this word's paths go to the wanting lanes of ranks have + first, ...
-            for (unsigned long long cm = pt_ballot(old != 0u); cm; cm &= cm - 1ull) {
-                const int j = __ffsll((long long)cm) - 1;
-                const uint32_t oj = (uint32_t)__builtin_amdgcn_readlane((int)old, j), wj = (uint32_t)__builtin_amdgcn_readlane((int)w, j);
-                const int fj = have + __builtin_amdgcn_readlane(first, j);
-                if (want && my_rank >= fj && my_rank < fj + __popc(oj)) {
-                    uint32_t bits = oj;
-                    for (int k = my_rank - fj; k > 0; k--) bits &= bits - 1u;
-                    got = wj * 32u + (uint32_t)__ffs((int)bits) - 1u;
-                }
-            }
-            have += claimed;
-            const unsigned long long tm = pt_ballot(take != 0u);
-            if (tm && have >= need) {                             // done: the next request starts at the last word touched if it kept paths, else behind it
-                const int jl = 63 - __clzll((long long)tm);
-                const uint32_t wl = (uint32_t)__builtin_amdgcn_readlane((int)w, jl), left = (uint32_t)__builtin_amdgcn_readlane((int)(v & ~take), jl);
-                next_cursor = left ? wl : wl + 1u;
-            }
-        }
-        cursor = (uint32_t)__builtin_amdgcn_readfirstlane((int)next_cursor);
-        while (cursor >= nw) cursor -= nw;                            // cursor % nw on SGPRs; one round, but for a ring of under 64 words swept without finding enough
-    }
-    if (have && lane == 0) atomicSub(cnt, have);
-    return got;
-}
-
-// Sets the bit of path l in queue q for the lanes with `doit` (wave-uniform call).
-template <class SH> RT_DEV void pt_push(SH &sh, int q, uint32_t l, bool doit) {
-    if (doit) atomicOr(&sh.need[q][l >> 5], 1u << (l & 31u));
-    const unsigned long long m = pt_ballot(doit);
-    if (m && (threadIdx.x & 63u) == 0) atomicAdd(&sh.cnt[q], (int)__popcll(m));
 }
 
 // One of the two walks of path l is done (its results are in HBM, ordered before this call by the caller's release fence):
@@ -408,7 +312,7 @@ RT_DEV void pt_walk_stint(WK &w, SH &sh, const PtParams &P, PtWave &wv, uint32_t
             if (!refill_ok) {}
             else if (pt_count(&sh.cnt[PT_Q_SHADE]) >= shade_thr) refill_ok = false;      // shaders are behind: drain, then help them
             else if (pt_count(&sh.cnt[Q::ID]) > 0) {
-                const uint32_t got = pt_pop(sh.need[Q::ID], &sh.cnt[Q::ID], wv.nw, wv.cur[Q::ID], !active, wv.front_first);
+                const uint32_t got = pt_pop(sh.need[Q::ID], &sh.cnt[Q::ID], wv.nw, wv.cur[Q::ID], !active, wv.front_first, COUNT ? &prof.pops[K] : nullptr);
                 __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
                 sub.lap(prof.t_sub[K][1]);
                 n_queries += __popcll(pt_ballot(got != PT_NONE));
@@ -946,7 +850,7 @@ RT_DEV void pt_run(RL &rl) {
         }
         // shaders first when a full wave of paths waits (or when it is all there is to do)
         if (ns >= P.shade_min || (ns > 0 && nt + nl == 0)) {
-            const uint32_t got = pt_pop(sh.need[PT_Q_SHADE], &sh.cnt[PT_Q_SHADE], wv.nw, wv.cur[PT_Q_SHADE], true, wv.front_first);
+            const uint32_t got = pt_pop(sh.need[PT_Q_SHADE], &sh.cnt[PT_Q_SHADE], wv.nw, wv.cur[PT_Q_SHADE], true, wv.front_first, COUNT ? &prof.pops[PT_Q_SHADE] : nullptr);
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
             if (pt_here(P.prio) == 2) __builtin_amdgcn_s_setprio(2);
             const PtShaded s = rl.shade(got, n_light, n_nodes, prof);
@@ -1102,6 +1006,10 @@ struct PtRoles {
             atomicAdd(&P.counters[CNT_P8_STINTS], prof.stints); atomicAdd(&P.counters[CNT_P8_SHADE_BATCHES], prof.shade_batches); atomicAdd(&P.counters[CNT_P8_SHADE_ITEMS], prof.shade_items);
             for (int k = 0; k < 3; k++) atomicAdd(&P.counters[CNT_P8_HANDOFF_TIME + k], prof.t_sub[0][k]);
             atomicAdd(&P.counters[CNT_P8_HANDOFFS], prof.refills[0]);
+            for (int q = 0; q < 3; q++) {
+                atomicAdd(&P.counters[CNT_P8_POPS + 3 * q], prof.pops[q].pops); atomicAdd(&P.counters[CNT_P8_POPS + 3 * q + 1], prof.pops[q].paths);
+                atomicAdd(&P.counters[CNT_P8_POPS + 3 * q + 2], prof.pops[q].words);
+            }
             for (int w = 0; w < 2; w++) {
                 for (int k = 0; k < 3; k++) atomicAdd(&P.counters[CNT_P8_WALK_TIME + 3 * w + k], prof.t_part[w][k]);
                 atomicAdd(&P.counters[CNT_P8_LEAF_ITERS + 2 * w], prof.leaf_iters[w]); atomicAdd(&P.counters[CNT_P8_LEAF_ITERS + 2 * w + 1], prof.leaf_lane_iters[w]);

@@ -44,6 +44,7 @@ enum CounterSlot {
     CNT_P8_LIGHT_REACH = 30,    // P8, 2 slots: light sums whose walk ends at the light tree's root / one level below it (pt_light_reach)
     CNT_WF_HIST_LIGHT = 32,     // WF, 16 slots: light queries by in-flight wave iterations / 32
     CNT_P6_SLOW_HITS = 32,      // P6, 16 slots: light sums in the slow role by number of hits
+    CNT_P8_POPS = 32,           // P8, 3 slots per queue (trace, light, shade): pt_pop calls, paths they handed out, bitmap words those came from
     CNT_P8_WALK_TIME = 48,      // P8, 3 slots per walker: hand-off and refill, inner nodes, leaves
     CNT_P8_LEAF_ITERS = 54,     // P8, 2 slots per walker: leaf passes, their lanes
     CNT_P8_LIGHT_HITS = 58,

@@ -539,6 +539,11 @@ static void report_persistent(rt_scene *scene, bool hw6, const char *kernel, boo
         const unsigned long long *handoff = h_cnt + CNT_P8_HANDOFF_TIME, tests = h_cnt[CNT_P8_LIGHT_TESTS], hits = h_cnt[CNT_P8_LIGHT_HITS], *reach = h_cnt + CNT_P8_LIGHT_REACH;
         fprintf(stderr, "[rtamd]   closest-hit walker's hand-off points: %llu; of their time: publishing finished walks %.1f %%, taking new ones from the bitmap %.1f %%, reading their rays %.1f %% (the rest: the test itself)\n",
                 h_cnt[CNT_P8_HANDOFFS], 100.0 * handoff[0] / nz(h_cnt[CNT_P8_WALK_TIME]), 100.0 * handoff[1] / nz(h_cnt[CNT_P8_WALK_TIME]), 100.0 * handoff[2] / nz(h_cnt[CNT_P8_WALK_TIME]));
+        for (int q = 0; q < 3; q++) {
+            const unsigned long long *pop = h_cnt + CNT_P8_POPS + 3 * q;
+            fprintf(stderr, "[rtamd]   pops of the %s queue: %llu, %.1f paths from %.2f claimed words each\n", q == 0 ? "closest-hit" : q == 1 ? "light" : "shade",
+                    pop[0], (double)pop[1] / nz(pop[0]), (double)pop[2] / nz(pop[0]));
+        }
         fprintf(stderr, "[rtamd]   light tests %llu (%.2f per light sum), hits %llu (%.2f per light sum); triangle tests of closest-hit walks %llu (%.2f per query)\n",
                 tests, (double)tests / nz(n_light), hits, (double)hits / nz(n_light), h_cnt[CNT_TRI_TESTS] - tests, (double)(h_cnt[CNT_TRI_TESTS] - tests) / nz(h_cnt[CNT_CLOSEST]));
         fprintf(stderr, "[rtamd]   light sums whose walk ends at the light tree's root %llu (%.1f %%), one level below it %llu (%.1f %%); settled by the shader: level %d\n",
@@ -766,7 +771,7 @@ static int collect_frame(rt_scene *scene, const Frame &F, hipStream_t stream, rt
         h_cnt[CNT_EXACT_LIGHT] = h_cnt[CNT_WF_SLOW_LIGHT]; // light sums finished by the exact kernel
     }
     // The two histograms are the round pipeline's (CNT_WF_HIST_*).  After a persistent hw8 render the same lines print what that kernel
-    // keeps in those slots (CNT_ROLE_TIME .. CNT_P8_LIGHT_REACH, then zeros), and the last line's CNT_WF_* slots are the round pipeline's
+    // keeps in those slots (CNT_ROLE_TIME .. CNT_P8_LIGHT_REACH, then CNT_P8_POPS and zeros), and the last line's CNT_WF_* slots are the round pipeline's
     // too (after a persistent hw6 render slot 11 is CNT_P6_EXACT_LIGHT): kept as they are, see profiles/r08_api_split.txt.
     if (count && debug && (pipe == Pipeline::Persistent8 || pipe == Pipeline::Rounds)) { // wave iterations a query stays in flight, buckets of 32
         fprintf(stderr, "[rtamd] closest-hit queries by in-flight wave iterations (x32):");

@@ -5,6 +5,7 @@
 #include "device/rt_exact.h"
 #include "device/rt_kernels_hw8.h"
 #include "device/rt_node_grid.h"
+#include "device/rt_pt_queue.h"
 #include "host/fold_nodes.h"
 #include <cstring>
 #include <vector>
@@ -87,7 +88,53 @@ __global__ void k_slab_q_entry(const float *in, rtamd::NodeGrid G, float *rcp, f
     entry[i] = tq;
 }
 
+// rt_pt_queue.h pt_pop on a bitmap of the test's own: every wave of the one workgroup makes n_calls calls, call c with the lanes of
+// want[c] wanting a path.  got: [wave][call][64] results; cursor_out, count_out: [wave][call] the wave's cursor and the queue's count after the call.
+#define HOOK_POP_NW 160
+__global__ void k_pt_pop(uint32_t *bitmap, int *count, uint32_t nw, uint32_t cursor0, const unsigned long long *want, int n_calls, int from_start,
+                         uint32_t *got, uint32_t *cursor_out, int *count_out) {
+    __shared__ uint32_t bm[HOOK_POP_NW];
+    __shared__ int cnt;
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    for (uint32_t i = threadIdx.x; i < nw; i += blockDim.x) bm[i] = bitmap[i];
+    if (threadIdx.x == 0) cnt = *count;
+    __syncthreads();
+    uint32_t cursor = cursor0;
+    for (int c = 0; c < n_calls; c++) {
+        const uint32_t g = pt_pop(bm, &cnt, nw, cursor, ((want[c] >> lane) & 1ull) != 0ull, from_start != 0);
+        got[((size_t)wave * n_calls + c) * 64 + lane] = g;
+        const int left = pt_count(&cnt);
+        if (lane == 0) { cursor_out[wave * n_calls + c] = cursor; count_out[wave * n_calls + c] = left; }
+    }
+    __syncthreads();
+    for (uint32_t i = threadIdx.x; i < nw; i += blockDim.x) bitmap[i] = bm[i];
+    if (threadIdx.x == 0) *count = cnt;
+}
+
 extern "C" {
+// rt_pt_queue.h bit helpers on the host (no GPU needed): out[i] = pt_nth_bit(v[i], n[i]) / pt_low_bits(v[i], n[i])
+void rtt_pt_nth_bit(const uint32_t *v, const int *n, int *out, size_t count) { for (size_t i = 0; i < count; i++) out[i] = pt_nth_bit(v[i], n[i]); }
+void rtt_pt_low_bits(const uint32_t *v, const int *n, uint32_t *out, size_t count) { for (size_t i = 0; i < count; i++) out[i] = pt_low_bits(v[i], n[i]); }
+// k_pt_pop with `waves` (1..4) waves on a bitmap of nw <= 160 words; bitmap and count are updated in place.  got: waves x n_calls x 64,
+// cursor_out and count_out: waves x n_calls.
+int rtt_pt_pop(uint32_t *bitmap, uint32_t nw, int *count, uint32_t cursor, const unsigned long long *want, int n_calls, int from_start, int waves,
+               uint32_t *got, uint32_t *cursor_out, int *count_out) {
+    if (nw == 0 || nw > HOOK_POP_NW || cursor >= nw || n_calls <= 0 || waves < 1 || waves > 4) return -1;
+    const size_t n_res = (size_t)waves * n_calls;
+    uint32_t *d_bm = nullptr, *d_got = nullptr, *d_cur = nullptr; int *d_cnt = nullptr, *d_left = nullptr; unsigned long long *d_want = nullptr;
+    int rc = -2;
+    if (hipMalloc((void **)&d_bm, nw * 4) == hipSuccess && hipMalloc((void **)&d_cnt, 4) == hipSuccess && hipMalloc((void **)&d_want, (size_t)n_calls * 8) == hipSuccess &&
+        hipMalloc((void **)&d_got, n_res * 256) == hipSuccess && hipMalloc((void **)&d_cur, n_res * 4) == hipSuccess && hipMalloc((void **)&d_left, n_res * 4) == hipSuccess &&
+        hipMemcpy(d_bm, bitmap, nw * 4, hipMemcpyHostToDevice) == hipSuccess && hipMemcpy(d_cnt, count, 4, hipMemcpyHostToDevice) == hipSuccess &&
+        hipMemcpy(d_want, want, (size_t)n_calls * 8, hipMemcpyHostToDevice) == hipSuccess) {
+        hipLaunchKernelGGL(k_pt_pop, dim3(1), dim3(64 * waves), 0, 0, d_bm, d_cnt, nw, cursor, d_want, n_calls, from_start, d_got, d_cur, d_left);
+        if (hipDeviceSynchronize() == hipSuccess && hipMemcpy(bitmap, d_bm, nw * 4, hipMemcpyDeviceToHost) == hipSuccess && hipMemcpy(count, d_cnt, 4, hipMemcpyDeviceToHost) == hipSuccess &&
+            hipMemcpy(got, d_got, n_res * 256, hipMemcpyDeviceToHost) == hipSuccess && hipMemcpy(cursor_out, d_cur, n_res * 4, hipMemcpyDeviceToHost) == hipSuccess &&
+            hipMemcpy(count_out, d_left, n_res * 4, hipMemcpyDeviceToHost) == hipSuccess) rc = 0;
+    }
+    (void)hipFree(d_bm); (void)hipFree(d_cnt); (void)hipFree(d_want); (void)hipFree(d_got); (void)hipFree(d_cur); (void)hipFree(d_left);
+    return rc;
+}
 // host/fold_nodes.h on host memory (no GPU needed): nodes = n two-box nodes of 64 bytes, grid_box = lo.xyz hi.xyz of what the grid must hold,
 // out = room for cap wide nodes of 64 bytes, grid_out = the grid's lo[3], step[3], istep[3].  Returns the number of wide nodes, -1 on error.
 int rtt_fold_nodes(const void *nodes, uint32_t n, const float *grid_box, void *out, uint32_t cap, uint32_t *depth_out, float *grid_out) {
