@@ -211,6 +211,28 @@ RT_DEV float rng_n01(Rng &r) {
     r.has_saved = true;
     return y * mult;
 }
+// One polar round of rng_n01: the value it returns (y * mult) and the one it saves (x * mult).
+RT_DEV void rng_polar(Rng &r, float &ret, float &keep) {
+    float x, y, r2;
+    do {
+        x = 2.0f * rng_u01(r) - 1.0f;
+        y = 2.0f * rng_u01(r) - 1.0f;
+        r2 = x * x + y * y;
+    } while (r2 > 1.0f || r2 == 0.0f);
+    float mult = sqrtf(-2 * rt_logf(r2) / r2);
+    keep = x * mult;
+    ret = y * mult;
+}
+// a = rng_n01(r), b = rng_n01(r), c = rng_n01(r): the same engine calls, values and state afterwards.  A lane that enters with a saved value
+// needs one polar round (saved, ret, keep), one without needs two (ret, keep, ret2; keep2 saved).  Three inlined rng_n01 make a wave that
+// holds both kinds run three rejection loops with the logarithm, root and division after each; here it runs one round for every lane and
+// a second for the lanes that entered without a saved value.
+RT_DEV void rng_n01x3(Rng &r, float &a, float &b, float &c) {
+    float p, q;
+    rng_polar(r, p, q);
+    if (r.has_saved) { a = r.saved; b = p; c = q; r.saved = q; r.has_saved = false; }
+    else { a = p; b = q; rng_polar(r, c, r.saved); r.has_saved = true; }
+}
 
 // ---- quaternion (quaternion.h:36-46) ------------------------------------------------------------
 struct Quat { F3 v; float w; };
@@ -631,7 +653,8 @@ RT_DEV F3 material_brdf_hw7(F3 base_color, float base_metallic, F3 l, F3 v, F3 n
 
 // ---- samplers (distributions.h) --------------------------------------------------------------------
 RT_DEV F3 cosine_sample(Rng &rng, F3 n) { // :42-52
-    float a = rng_n01(rng), b = rng_n01(rng), c = rng_n01(rng);
+    float a, b, c;
+    rng_n01x3(rng, a, b, c);
     F3 d = normalize(f3(a, b, c));
     d = d + n;
     float l = len(d);
@@ -702,6 +725,17 @@ RT_DEV float vndf_pdf(F3 n, F3 d, F3 v, float alpha) { // :239-245
     v = neg(v);
     Quat q = vndf_getq(n);
     return vndf_pdf_local(qtransform(q, d), qtransform(q, v), alpha);
+}
+// The same two with the frame given: q = vndf_getq(n) and vT = qtransform(q, -v), which both build from the same normal and direction.
+// A caller that needs the sample and the pdf forms the frame once.
+RT_DEV F3 vndf_sample(Rng &rng, Quat q, F3 vT, float alpha) {
+    float t1, t2;
+    vndf_disk_point(rng, t1, t2);
+    F3 dT = vndf_sample_local(t1, t2, vT, alpha);
+    return qtransform(qconj(q), dT);
+}
+RT_DEV float vndf_pdf(Quat q, F3 vT, F3 d, float alpha) {
+    return vndf_pdf_local(qtransform(q, d), vT, alpha);
 }
 RT_DEV F3 light_sample(const SceneView &S, Rng &rng, F3 x) { // :117-120, :81-94
     int k = (int)(rng_u01(rng) * S.n_lights_f);

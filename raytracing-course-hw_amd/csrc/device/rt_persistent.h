@@ -203,11 +203,32 @@ struct PtProf {
     unsigned long long t_sub[2][3] = {{0, 0, 0}, {0, 0, 0}}, refills[2] = {0, 0}; // of [0]: publish finished walks | take new ones from the bitmap | read their rays
     unsigned long long light_reach[2] = {0, 0}; // light sums whose walk ends at the light tree's root / one level below it (pt_light_reach), per lane
     PtPopStat pops[3];                          // what pt_pop handed out, by queue (PT_Q_TRACE, PT_Q_LIGHT, PT_Q_SHADE); flushed by the hw8 kernel only (CNT_P8_POPS)
+    // the hw8 shader's wave time by section (PtShadeLap: [0] record load, gate and pending bounce, [1] attributes and textures, [2] Mix::sample,
+    // [3] BRDF and pdf, [4] path end), the lanes that ran each section, and the hits at the deepest level among them (CNT_P8_SHADE_*)
+    unsigned long long t_shade[5] = {0, 0, 0, 0, 0}, shade_lanes[5] = {0, 0, 0, 0, 0}, shade_last = 0;
 };
 template <bool COUNT> struct PtLap { // s_memtime laps of the counting build
     unsigned long long t;
     RT_DEV PtLap() : t(COUNT ? __builtin_amdgcn_s_memtime() : 0ull) {}
     RT_DEV void lap(unsigned long long &acc) { if (COUNT) { const unsigned long long n = __builtin_amdgcn_s_memtime(); acc += n - t; t = n; } }
+};
+
+// The shader's laps (counting build): a lane carries the cycles of the sections it ran through one batch; the sections are divergent, so
+// the clock is read where a section ends for its lanes (s_memtime is scalar: all lanes of a section take the same two readings), and
+// PtRoles::shade books each section once per batch with the number of lanes that hold a time for it.
+template <bool COUNT> struct PtShadeLap {
+    unsigned long long t;
+    uint32_t d[5] = {0, 0, 0, 0, 0};
+    bool last = false;                // the lane shades a hit at the deepest level
+    RT_DEV PtShadeLap() : t(__builtin_amdgcn_s_memtime()) {}
+    RT_DEV void start() { t = __builtin_amdgcn_s_memtime(); } // a section that begins where lanes of different sections meet again
+    RT_DEV void lap(int k) { const unsigned long long n = __builtin_amdgcn_s_memtime(); d[k] += (uint32_t)(n - t); t = n; }
+    RT_DEV void at_last_level() { last = true; }
+};
+template <> struct PtShadeLap<false> { // the plain kernels carry nothing
+    RT_DEV void start() {}
+    RT_DEV void lap(int) {}
+    RT_DEV void at_last_level() {}
 };
 
 // wave-uniform state
@@ -527,12 +548,18 @@ template <bool COUNT> struct PtLightWalk {
 // section needs — the incoming direction, the random engine, base colour x texture colour, the metallic product, a path's tail —
 // is parked in this lane's column of the wave's LDS stack area (idle while the wave shades; volatile accesses, so the compiler neither
 // forwards a parked value through a register nor moves other memory operations across a park / unpark).
+// Each section runs once per batch.  A batch mixes depths, so a hit at the deepest level, of which getColor keeps only the emission, has no
+// branch of its own (the round pipeline's wf_shade_item has one: its launches are of one depth): it takes the common sections and ends
+// with the lanes whose BRDF is black, untraced.  The three normal draws of the cosine sampler are one call (rng_n01x3: two polar loops
+// for the wave, not three), and the VNDF frame that its sampler and its pdf both need is formed once, before the components part, and parked.
 #define PK_TAIL 0                     // 3 words: value the innermost call returns (paths that end)
 #define PK_LEVELS 3                   // bounces below which it returns
 #define PK_RNG 4                      // engine state, saved normal (has_saved travels in the packed word)
 #define PK_D 6                        // incoming direction (3)
 #define PK_BC 9                       // base_color * texture colour (3), metallic * baseMetallic
-#define PK_WORDS 13
+#define PK_Q 13                       // the VNDF frame of the hit, shared by vndf_sample and vndf_pdf: the rotation vndf_getq(sn) (4) ...
+#define PK_VT 17                      // ... and the outgoing direction in it, qtransform(q, -d) (3)
+#define PK_WORDS 20
 static_assert(PK_WORDS <= P8_STACK, "the shader parks its values in the lane's stack column");
 typedef __attribute__((address_space(3))) volatile uint32_t *PtLdsWord; // an LDS pointer that stays one (32-bit base + immediate offsets)
 struct PtPark {
@@ -546,10 +573,12 @@ struct PtPark {
     RT_DEV Rng rng(uint32_t packed) const { Rng g; g.x = getu(PK_RNG); g.saved = get(PK_RNG + 1); g.has_saved = (packed & 16u) != 0; return g; }
     RT_DEV void keep(const Rng &g, uint32_t &packed) const { putu(PK_RNG, g.x); put(PK_RNG + 1, g.saved); packed = g.has_saved ? (packed | 16u) : (packed & ~16u); }
     RT_DEV void end(F3 tail, int levels) const { put3(PK_TAIL, tail); putu(PK_LEVELS, (uint32_t)levels); }
+    RT_DEV void frame(Quat q, F3 vT) const { put3(PK_Q, q.v); put(PK_Q + 3, q.w); put3(PK_VT, vT); }
+    RT_DEV Quat q() const { Quat g; g.v = get3(PK_Q); g.w = get(PK_Q + 3); return g; }
 };
 
-template <int FEAT>
-RT_DEV int pt_shade_lean(const SceneView &S, const RenderView &R, const WfView &W, const uint32_t slot, const PtPark pk, bool &discarded) {
+template <int FEAT, bool COUNT>
+RT_DEV int pt_shade_lean(const SceneView &S, const RenderView &R, const WfView &W, const uint32_t slot, const PtPark pk, bool &discarded, PtShadeLap<COUNT> &lp) {
     float4 *r = wf_rec(W, slot);
     uint32_t packed = __float_as_uint(reinterpret_cast<const float *>(r + 3)[3]);
     int depth = (int)(packed & 15u);
@@ -602,22 +631,17 @@ RT_DEV int pt_shade_lean(const SceneView &S, const RenderView &R, const WfView &
             else { discarded = true; ended = true; pk.end(f3(0.f, 0.f, 0.f), depth + 1); }
         }
     }
+    lp.lap(0);
     if (!ended) {
         HitRec h;
         h.idx = (int)(hit & WF_INDEX_MASK); h.inside = (hit & WF_INSIDE_BIT) != 0; h.t = q2.x; h.u = q2.y; h.v = q2.z;
         if (hit == WF_MISS) { ended = true; pk.end(miss_color<(FEAT & WF_FEAT_ENV) != 0>(S, pk.get3(PK_D)), depth); }
-        else if (S.last_level_emission_only && depth + 1 >= R.ray_depth) {
-            // Deepest level: getColor returns its emission whatever Mix::sample / brdf / pdf produce (SceneView::last_level_emission_only);
-            // only the random draws must still happen, in order (distributions.h:257, then 3 normals | u1,u2 | index,u,v).
-            pk.end(emission_fetch(S, h), depth);
-            Rng rng = pk.rng(packed);
-            const int comp = (int)(rng_u01(rng) * S.n_components_f);
-            if (comp == 0) { rng_n01(rng); rng_n01(rng); rng_n01(rng); }
-            else if (comp == 2) { rng_u01(rng); rng_u01(rng); rng_u01(rng); }
-            else { rng_u01(rng); rng_u01(rng); }
-            pk.keep(rng, packed);
-            ended = true;
-        } else {
+        else {
+            // A hit at the deepest level (SceneView::last_level_emission_only: getColor returns its emission whatever Mix::sample / brdf /
+            // pdf produce) takes the same sections as every other hit, so that a batch of mixed depths runs each of them once: its draws are
+            // Mix::sample's, in order, and it leaves where a black BRDF leaves, with the level's emission and no new ray to trace.
+            const bool last = S.last_level_emission_only && depth + 1 >= R.ray_depth;
+            if (last) lp.at_last_level();
             const bool hw7 = (FEAT & WF_FEAT_HW7) && S.hw7;
             float4 *e = wf_entry(W, slot, depth);
             {   // the next ray's origin goes to the path's record at once (its final place): x + eps * geomNorma, scene.cpp:104
@@ -637,15 +661,19 @@ RT_DEV int pt_shade_lean(const SceneView &S, const RenderView &R, const WfView &
                 pk.put(PK_BC + 3, sh.metallic * base_metallic);
                 alpha = sh.alpha; sn = sh.sn;
             }
+            lp.lap(1);
             F3 nd;
             {   // Mix::sample (distributions.h:256-265)
+                // the VNDF frame once per hit, for the sampler (component 1) and for the pdf (every lane): both would build it from sn and d
+                { const Quat q = vndf_getq(sn); pk.frame(q, qtransform(q, neg(pk.get3(PK_D)))); }
                 Rng rng = pk.rng(packed);
                 const int comp = (int)(rng_u01(rng) * S.n_components_f);         // :257
                 if (comp == 0) nd = cosine_sample(rng, sn);
                 else if (comp == 2) { const float4 xq = r[0]; nd = light_sample(S, rng, f3(xq.x, xq.y, xq.z)); }
-                else nd = vndf_sample(rng, sn, pk.get3(PK_D), alpha);
+                else nd = vndf_sample(rng, pk.q(), pk.get3(PK_VT), alpha);
                 pk.keep(rng, packed);
             }
+            lp.lap(2);
             // the record and entry addresses are formed again from the slot number after the sampling code (an opaque copy, so that the
             // two 64-bit pointers do not sit in registers across it)
             uint32_t slot_again = slot;
@@ -661,26 +689,30 @@ RT_DEV int pt_shade_lean(const SceneView &S, const RenderView &R, const WfView &
                            : material_brdf_pre(bc, metallic_eff, nd, neg(d), sn, alpha);
             }
             const float epsf = 9.99999974737875163555e-05f;
-            if (brdf.x <= epsf && brdf.y <= epsf && brdf.z <= epsf) {                 // scene.cpp:154-156
+            if (last || (brdf.x <= epsf && brdf.y <= epsf && brdf.z <= epsf)) {       // scene.cpp:154-156
                 const float4 e0 = e[0];
                 ended = true; pk.end(f3(e0.x, e0.y, e0.z), depth);
+                lp.lap(3);
             } else {
                 e[1] = make_float4(brdf.x, brdf.y, brdf.z, dot(nd, sn));
-                asm volatile("" : "+v"(sn.x), "+v"(sn.y), "+v"(sn.z)); // the pdf terms start from the normal again: nothing derived from it for the sampling code (its rotation) waits in registers
                 float pdf = 0.f;                                                       // distributions.h:268-276, first two terms
                 pdf += cosine_pdf(sn, nd);
-                pdf += vndf_pdf(sn, nd, pk.get3(PK_D), alpha);
+                pdf += vndf_pdf(pk.q(), pk.get3(PK_VT), nd, alpha);
                 reinterpret_cast<float *>(e)[3] = pdf;
                 reinterpret_cast<float *>(r)[3] = nd.x;
                 r[1] = make_float4(nd.y, nd.z, __uint_as_float(pk.getu(PK_RNG)), pk.get(PK_RNG + 1));
                 const uint32_t sample = (packed >> 6) & WF_SAMPLE_MASK;
                 reinterpret_cast<float *>(r + 3)[3] = __uint_as_float(wf_pack(depth, (packed & 16u) != 0, sample, true));
+                lp.lap(3);
                 return WF_NEXT_TRACE | (S.n_lights ? WF_NEXT_LIGHT : 0);               // traced speculatively beside its own light-pdf sum
             }
         }
     }
+    lp.start();
     Rng rng = pk.rng(packed);
-    return wf_finish_path(S, R, W, slot, (int)pk.getu(PK_LEVELS), pk.get3(PK_TAIL), rng, (packed >> 6) & WF_SAMPLE_MASK);
+    const int todo = wf_finish_path(S, R, W, slot, (int)pk.getu(PK_LEVELS), pk.get3(PK_TAIL), rng, (packed >> 6) & WF_SAMPLE_MASK);
+    lp.lap(4);
+    return todo;
 }
 
 // ---- the exact role: one lane per query, the reference's own box arithmetic over the reference trees (rt_exact.h) -------------------
@@ -959,7 +991,15 @@ struct PtRoles {
                 if (4u * k + 5u <= P.trace_cap) for (int q = 0; q < 4; q++) P.trace_buf[1 + 4 * k + q] = tr[q];
             }
         }
-        if (got != PT_NONE) { PtPark pk; pk.p = (PtLdsWord)&stack[0][lane]; todo = pt_shade_lean<FEAT>(S, R, W, pt_slot(sh, got), pk, discarded); }
+        PtShadeLap<COUNT> lp;
+        if (got != PT_NONE) { PtPark pk; pk.p = (PtLdsWord)&stack[0][lane]; todo = pt_shade_lean<FEAT>(S, R, W, pt_slot(sh, got), pk, discarded, lp); }
+        if constexpr (COUNT) { // each section once per batch: its lanes all hold the same time
+            for (int k = 0; k < 5; k++) {
+                const unsigned long long m = pt_ballot(lp.d[k] != 0u);
+                if (m) { prof.t_shade[k] += (uint32_t)__builtin_amdgcn_readlane((int)lp.d[k], __builtin_ctzll(m)); prof.shade_lanes[k] += __popcll(m); }
+            }
+            prof.shade_last += __popcll(pt_ballot(lp.last));
+        }
         n_discarded += __popcll(pt_ballot(discarded));
         const bool next = got != PT_NONE && todo != PT_SHADE_EXACT && (todo & WF_NEXT_TRACE), with_light = next && (todo & WF_NEXT_LIGHT);
         bool wire = false;    // the new ray pierces a tripwire (rt_exact.h): its closest hit is the exact role's
@@ -1006,6 +1046,8 @@ struct PtRoles {
             atomicAdd(&P.counters[CNT_P8_STINTS], prof.stints); atomicAdd(&P.counters[CNT_P8_SHADE_BATCHES], prof.shade_batches); atomicAdd(&P.counters[CNT_P8_SHADE_ITEMS], prof.shade_items);
             for (int k = 0; k < 3; k++) atomicAdd(&P.counters[CNT_P8_HANDOFF_TIME + k], prof.t_sub[0][k]);
             atomicAdd(&P.counters[CNT_P8_HANDOFFS], prof.refills[0]);
+            for (int k = 0; k < 5; k++) { atomicAdd(&P.counters[CNT_P8_SHADE_TIME + k], prof.t_shade[k]); atomicAdd(&P.counters[CNT_P8_SHADE_LANES + k], prof.shade_lanes[k]); }
+            atomicAdd(&P.counters[CNT_P8_SHADE_LAST], prof.shade_last);
             for (int q = 0; q < 3; q++) {
                 atomicAdd(&P.counters[CNT_P8_POPS + 3 * q], prof.pops[q].pops); atomicAdd(&P.counters[CNT_P8_POPS + 3 * q + 1], prof.pops[q].paths);
                 atomicAdd(&P.counters[CNT_P8_POPS + 3 * q + 2], prof.pops[q].words);

@@ -11,7 +11,7 @@ namespace rtamd {
 #define RT_STACK_SIZE 64              // private traversal stack of the megakernel and of the exact walks over the reference's own tree
 #define P8_STACK 24                   // rt_persistent.h: LDS traversal stack entries per lane; the walkers' tree is built at most this deep (rt_bvh_build.h)
 
-// The 64 counters of a render (8 bytes each; RenderView::counters / PtParams::counters), zeroed before every frame and read back after
+// The 80 counters of a render (8 bytes each; RenderView::counters / PtParams::counters), zeroed before every frame and read back after
 // it for rt_stats, the error checks and the RTAMD_DEBUG_COUNTERS report (render_frame, report_persistent).  One name per meaning: where
 // two kernels use a slot differently it has two names, and the comment says who writes it (P8 = pt_persistent_kernel, P6 =
 // p6_persistent_kernel, WF = the round pipeline's kernels, mega = render_hw8_kernel / render_hw6_kernel).
@@ -51,9 +51,12 @@ enum CounterSlot {
     CNT_P8_LIGHT_TESTS = 59,
     CNT_P8_HANDOFF_TIME = 60,   // P8, 3 slots: the closest-hit walker's hand-off time by part (publish, take, read rays)
     CNT_P8_HANDOFFS = 63,       // P8: the closest-hit walker's hand-off points
-    CNT_SLOTS = 64
+    CNT_P8_SHADE_TIME = 64,     // P8, 5 slots: the shader's wave time by section (record load, gate and pending bounce; attributes and textures; Mix::sample; BRDF and pdf; path end)
+    CNT_P8_SHADE_LANES = 69,    // P8, 5 slots: the lanes that ran each section, summed over the batches
+    CNT_P8_SHADE_LAST = 74,     // P8: shaded hits at the deepest level (lanes, summed over the batches)
+    CNT_SLOTS = 80
 };
-#define CNT_BYTES (CNT_SLOTS * sizeof(unsigned long long)) // the 512-byte block
+#define CNT_BYTES (CNT_SLOTS * sizeof(unsigned long long)) // the 640-byte block
 
 // Binary BVH node with BOTH child boxes inline (one 64-byte fetch decides both children).
 // child = index of an inner node, or 0x80000000|first for a leaf whose primitives run from `first`

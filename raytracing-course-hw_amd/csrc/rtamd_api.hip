@@ -536,6 +536,14 @@ static void report_persistent(rt_scene *scene, bool hw6, const char *kernel, boo
             fprintf(stderr, "[rtamd]   %s walker's wave time: hand-off and refill %.1f %%, inner nodes %.1f %%, leaves %.1f %%; leaf passes %llu with %.1f of 64 lanes\n",
                     w ? "light" : "closest-hit", 100 * part[0] / tw, 100 * part[1] / tw, 100 * part[2] / tw, leaf[0], (double)leaf[1] / nz(leaf[0]));
         }
+        {
+            const unsigned long long *ts = h_cnt + CNT_P8_SHADE_TIME, *ls = h_cnt + CNT_P8_SHADE_LANES, nb = h_cnt[CNT_P8_SHADE_BATCHES];
+            static const char *const section[5] = {"record load, gate and pending bounce", "attributes and textures", "Mix::sample", "BRDF and pdf", "path end"};
+            fprintf(stderr, "[rtamd]   shader's wave time (%.0f cycles per batch):", (double)role[2] / nz(nb));
+            for (int k = 0; k < 5; k++) fprintf(stderr, " %s %.1f %% (%.0f cycles, %.1f lanes per batch)%s", section[k], 100.0 * ts[k] / nz(role[2]), (double)ts[k] / nz(nb), (double)ls[k] / nz(nb), k < 4 ? "," : "");
+            fprintf(stderr, "; the rest (%.1f %%): pop, settled light sums, pushes; hits at the deepest level: %.2f lanes per batch\n",
+                    100.0 * (1.0 - (double)(ts[0] + ts[1] + ts[2] + ts[3] + ts[4]) / nz(role[2])), (double)h_cnt[CNT_P8_SHADE_LAST] / nz(nb));
+        }
         const unsigned long long *handoff = h_cnt + CNT_P8_HANDOFF_TIME, tests = h_cnt[CNT_P8_LIGHT_TESTS], hits = h_cnt[CNT_P8_LIGHT_HITS], *reach = h_cnt + CNT_P8_LIGHT_REACH;
         fprintf(stderr, "[rtamd]   closest-hit walker's hand-off points: %llu; of their time: publishing finished walks %.1f %%, taking new ones from the bitmap %.1f %%, reading their rays %.1f %% (the rest: the test itself)\n",
                 h_cnt[CNT_P8_HANDOFFS], 100.0 * handoff[0] / nz(h_cnt[CNT_P8_WALK_TIME]), 100.0 * handoff[1] / nz(h_cnt[CNT_P8_WALK_TIME]), 100.0 * handoff[2] / nz(h_cnt[CNT_P8_WALK_TIME]));

@@ -37,6 +37,30 @@ __global__ void k_rng(uint32_t seed0, int n_seeds, int n_u, int n_n, float *out)
     for (int i = 0; i < n_u; i++) o[i] = rng_u01(r);
     for (int i = 0; i < n_n; i++) o[n_u + i] = rng_n01(r);
 }
+// rng_n01x3 against three rng_n01 calls, after `prior` (0 or 1) rng_n01 calls on the stream of seed0 + s.  Per seed and side (0: three
+// rng_n01, 1: rng_n01x3) eight words: the three values' bits, x, the bits of saved, has_saved, has_saved on entry, engine steps of the triple.
+RT_DEV uint32_t hook_rng_steps(uint32_t from, uint32_t to) { // steps of the engine from state `from` to state `to` (a triple makes a few)
+    Rng g; g.x = from; g.saved = 0.f; g.has_saved = false;
+    uint32_t n = 0;
+    while (g.x != to && n < 4096u) { (void)rng_u01(g); n++; }
+    return n;
+}
+__global__ void k_rng_triple(uint32_t seed0, int n_seeds, int prior, uint32_t *out) {
+    int s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= n_seeds) return;
+    for (int side = 0; side < 2; side++) {
+        Rng r;
+        rng_seed(r, seed0 + (uint32_t)s);
+        for (int i = 0; i < prior; i++) (void)rng_n01(r);
+        const uint32_t entered = r.has_saved ? 1u : 0u, x0 = r.x;
+        float a, b, c;
+        if (side == 0) { a = rng_n01(r); b = rng_n01(r); c = rng_n01(r); }
+        else rng_n01x3(r, a, b, c);
+        uint32_t *o = out + ((size_t)s * 2 + side) * 8;
+        o[0] = __float_as_uint(a); o[1] = __float_as_uint(b); o[2] = __float_as_uint(c);
+        o[3] = r.x; o[4] = __float_as_uint(r.saved); o[5] = r.has_saved ? 1u : 0u; o[6] = entered; o[7] = hook_rng_steps(x0, r.x);
+    }
+}
 
 // rt_exact.h: the runner-up's distance as it travels in the hit word, and the gate's decision on a box / ray / hit / gap
 __global__ void k_gap(const float *t, const float *t2, float *floor_out, uint32_t *code_out, size_t n) {
@@ -242,6 +266,17 @@ int rtt_env_uv(const float *d, float *uv, size_t n) {
     hipLaunchKernelGGL(k_env_uv, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, d_d, d_uv, n);
     int rc = hipMemcpy(uv, d_uv, n * 8, hipMemcpyDeviceToHost) == hipSuccess ? 0 : -2;
     (void)hipFree(d_d); (void)hipFree(d_uv);
+    return rc;
+}
+// k_rng_triple: out = n_seeds x 2 x 8 words
+int rtt_rng_triple(uint32_t seed0, int n_seeds, int prior, uint32_t *out) {
+    if (n_seeds <= 0 || prior < 0 || prior > 1) return -1;
+    uint32_t *d_out = nullptr;
+    const size_t n = (size_t)n_seeds * 16;
+    if (hipMalloc((void **)&d_out, n * 4) != hipSuccess) return -1;
+    hipLaunchKernelGGL(k_rng_triple, dim3((n_seeds + 63) / 64), dim3(64), 0, 0, seed0, n_seeds, prior, d_out);
+    int rc = (hipDeviceSynchronize() == hipSuccess && hipMemcpy(out, d_out, n * 4, hipMemcpyDeviceToHost) == hipSuccess) ? 0 : -2;
+    (void)hipFree(d_out);
     return rc;
 }
 // streams for seeds seed0 .. seed0+n_seeds-1: n_u uniforms then n_n normals each
