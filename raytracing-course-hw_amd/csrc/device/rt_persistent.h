@@ -241,13 +241,6 @@ struct PtWave {
 // A workgroup's paths come in groups of 2^shift consecutive slots (PtParams::group_shift: 6 = an 8x8 sub-tile, 4 = two rows of one): the unit of the deal.
 template <class SH> RT_DEV uint32_t pt_gshift(const SH &sh) { return (uint32_t)__builtin_amdgcn_readfirstlane(__hip_atomic_load(&sh.cnt[PT_GSHIFT], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)); }
 template <class SH> RT_DEV uint32_t pt_slot(const SH &sh, uint32_t l) { const uint32_t g = pt_gshift(sh); return (sh.groups[l >> g] << g) | (l & ((1u << g) - 1u)); }
-// Lanes that must wait at a leaf before the wave runs its triangle tests: a share (leaf_batch >> 16, in 1/256) of the active lanes, at most
-// leaf_batch & 255.  Plain integer arithmetic on purpose: min() of an int and __popcll's result picks the double overload.
-RT_DEV int pt_leaf_batch(int leaf_batch, unsigned long long m_active) {
-    const int cap = leaf_batch & 255, share = ((int)__popcll(m_active) * (leaf_batch >> 16) + 255) >> 8;
-    return share < cap ? share : cap;
-}
-
 // One of the two walks of path l is done (its results are in HBM, ordered before this call by the caller's release fence):
 // clear its pending bit; whoever clears the last one hands the path to the shaders.  Wave-uniform call.
 template <class SH> RT_DEV void pt_complete(SH &sh, uint32_t l, uint32_t bit, bool doit) {
@@ -261,7 +254,7 @@ template <class SH> RT_DEV void pt_complete(SH &sh, uint32_t l, uint32_t bit, bo
 }
 
 // ---- the walker loop -----------------------------------------------------------------------------------------------------------
-// The traversal loop of rt_wavefront.h (while-while) with its lanes refilled from a `need` bitmap: the one loop of the closest-hit and
+// The walker loop of rt_wavefront.h (wf_walk_loop, while-while) with its lanes refilled from a `need` bitmap: the one loop of the closest-hit and
 // the light-sum walkers of this file and of rt_persistent_hw6.h.  A walker is a policy WK, a struct that holds the per-walk state of a
 // lane and says what differs between the four:
 //   Queue                           which queue it serves and how a finished lane is published (PtTraceQueue, PtLightQueue)
@@ -453,7 +446,7 @@ struct PtTraceWalk {
     }
 };
 
-// ---- light-sum walker (wf_light_loop_lean of rt_wavefront.h): every light on the ray, the hits kept sorted at the top of the lane's column --
+// ---- light-sum walker (WfLightWalk of rt_wavefront.h): every light on the ray, the hits kept sorted at the top of the lane's column --
 template <bool COUNT> struct PtLightWalk {
     typedef PtLightQueue<PT_Q_XLIGHT> Queue;
     static constexpr uint32_t COST_NODE = PT_COST_LIGHT_NODE, COST_TEST = PT_COST_LIGHT_TEST;
@@ -512,7 +505,7 @@ template <bool COUNT> struct PtLightWalk {
         float v = 0.f;
         if (k == 1) v = __uint_as_float(stack[P8_STACK - 2][lane]);
         else if (k == 2) v = __uint_as_float(stack[P8_STACK - 2][lane]) + __uint_as_float(stack[P8_STACK - 4][lane]);
-        else if (k > 2) { // the reference's association of the additions, see wf_light_loop_lean
+        else if (k > 2) { // the reference's association of the additions: wf_merge_light_hits of rt_wavefront.h, for this kernel's columns
             const uint32_t nl = S.n_lights;
             for (int j = 1; j < k; j++) {
                 uint32_t a0 = stack[P8_STACK - 1 - 2 * (j - 1)][lane], b0 = stack[P8_STACK - 1 - 2 * j][lane];

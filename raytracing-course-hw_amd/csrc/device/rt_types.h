@@ -20,7 +20,7 @@ enum CounterSlot {
     CNT_LIGHT = 1,              // light-pdf queries: likewise
     CNT_NODE_VISITS = 2,        // counting variants of P8, P6, WF, render_hw8_kernel
     CNT_TRI_TESTS = 3,
-    CNT_WF_NODE_ITERS = 4,      // WF wf_trace_loop: wave node-iterations, ...
+    CNT_WF_NODE_ITERS = 4,      // WF closest-hit walker (WfTraceWalk): wave node-iterations, ...
     CNT_WF_LEAF_PHASES = 5,
     CNT_WF_LEAF_LANES = 6,
     CNT_WF_REFILLS = 7,

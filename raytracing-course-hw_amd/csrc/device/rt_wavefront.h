@@ -18,7 +18,7 @@
 //                attribute/texture fetch, Mix::sample, BRDF for the new hit; ends paths that miss / clamp /
 //                early-out (backward fold, next camera ray or pixel write) and queues the next ray.
 //
-// A pixel advances one bounce per round; spp * ray_depth rounds finish every pixel.  The traversal loops are
+// A pixel advances one bounce per round; spp * ray_depth rounds finish every pixel.  The walkers are
 // lean (few VGPRs, LDS stacks, all 64 lanes doing the same kind of work) and keep their lanes busy by pulling
 // the next ray as soon as one finishes.  Arithmetic is the same bit-exact code as the single-kernel path.
 //
@@ -241,11 +241,11 @@ __global__ __launch_bounds__(256) void wf_init_kernel(SceneView S, RenderView R,
     wf_flush(q, W.q_trace[0], W.ctr + 0, &gbase);
 }
 
-// ---- traversal kernels: persistent waves, per-lane LDS stacks ---------------------------------------------------
+// ---- traversal: persistent waves, per-lane LDS stacks, one loop (wf_walk_loop) for the three walkers ---------------------
 // Every wave owns a contiguous slice of the queue (no atomics: the work per ray is statistically uniform and a
 // slice keeps neighbouring pixels together).  Lanes pull the next ray of the slice as soon as >= WF_REFILL lanes are
-// idle.  Control flow is "while-while": lanes walk inner nodes until >= WF_LEAF_BATCH of them wait at a leaf,
-// then the (expensive, division-heavy) triangle tests run for all waiting lanes together.
+// idle.  Control flow is "while-while": lanes walk inner nodes until pt_leaf_batch of them (WF_LEAF_BATCH in a full wave)
+// wait at a leaf, then the (expensive, division-heavy) triangle tests run for all waiting lanes together.
 #define WF_REFILL 16
 #define WF_LEAF_BATCH 20
 #define WF_STEAL_CHUNK 64u
@@ -297,209 +297,241 @@ RT_DEV bool wf_take(WfSlice &s, bool want, uint32_t &item) {
     return got;
 }
 
-// Stack access.  The regular kernels index the LDS stack directly; the SPILL variant (selected on the host for trees deeper
-// than WF_STACK) pays a bounds check per access and keeps the deep entries in a per-thread global area.
-template <bool SPILL>
-RT_DEV void wf_spush(uint32_t (*stack)[64], uint32_t *ovf, int lds_limit, int lane, int &sp, uint32_t v) {
-    if (!SPILL || sp < lds_limit) stack[sp][lane] = v; else ovf[sp - lds_limit] = v;
-    sp++;
-}
-template <bool SPILL>
-RT_DEV uint32_t wf_spop(uint32_t (*stack)[64], const uint32_t *ovf, int lds_limit, int lane, int &sp) {
-    --sp;
-    return (!SPILL || sp < lds_limit) ? stack[sp][lane] : ovf[sp - lds_limit];
+// Lanes that must wait at a leaf before the wave runs its triangle tests: a share (leaf_batch >> 16, in 1/256) of the active lanes, at most
+// leaf_batch & 255, so that a thinly populated wave (the drain of a launch, small frames) does not make leaf lanes wait for 20 companions.
+// Plain integer arithmetic on purpose: min() of an int and __popcll's result picks the double overload.
+RT_DEV int pt_leaf_batch(int leaf_batch, unsigned long long m_active) {
+    const int cap = leaf_batch & 255, share = ((int)__popcll(m_active) * (leaf_batch >> 16) + 255) >> 8;
+    return share < cap ? share : cap;
 }
 
-template <bool COUNT, bool SPILL>
-RT_DEV void wf_trace_loop(const SceneView &S, const WfView &W, uint32_t (*stack)[64], const uint32_t *queue, WfSlice slice,
-                          unsigned long long *counters, int refill, int leaf_batch, int lds_limit) {
-    const int lane = threadIdx.x & 63;
-    uint32_t *ovf = SPILL ? W.ovf + ((size_t)blockIdx.x * 256u + threadIdx.x) * WF_OVF : nullptr;
-    bool active = false;
-    uint32_t slot = 0, cur = 0, hit = WF_MISS;
-    int sp = 0;
-    F3 o = f3(0.f, 0.f, 0.f), d = f3(0.f, 0.f, 1.f);
-    RayInv ray = make_ray_inv(o, d);
-    float best_t = RT_T_MAX, best_u = 0.f, best_v = 0.f;
-    // Boxes are pruned, and farther hits dropped, only beyond cull_t = best_t + the look-behind of rt_exact.h: the runner-up of the
-    // best hit must be SEEN, whatever tree the walk uses, to decide at the end of the walk whether the exact walk is needed.
-    float cull_t = RT_T_MAX, t2 = 2.f * RT_T_MAX, h_ray = 0.f; // h_ray: absolute part of the look-behind (pt_look_behind)
-    auto store_hit = [&]() { // the gate (pt_shade_item) decides with the runner-up's t whether this hit needs the exact walk
-        wf_rec(W, slot)[2] = make_float4(best_t, best_u, best_v, __uint_as_float(S.exact_boxes && hit != WF_MISS ? hit | pt_gap_code(best_t, t2) : hit));
+// A round walker's stack: the lane's LDS column, indexed directly.  The SPILL variant (selected on the host for trees deeper than
+// WF_STACK) pays a bounds check per access and keeps the entries beyond lds_limit in a per-thread global area.
+template <bool SPILL> struct WfStack {
+    uint32_t (*lds)[64]; uint32_t *ovf; int lds_limit, lane;
+    RT_DEV WfStack(const WfView &W, uint32_t (*stack)[64], int limit)
+        : lds(stack), ovf(SPILL ? W.ovf + ((size_t)blockIdx.x * 256u + threadIdx.x) * WF_OVF : nullptr), lds_limit(limit), lane(threadIdx.x & 63) {}
+    RT_DEV void push(int &sp, uint32_t v) { if (!SPILL || sp < lds_limit) lds[sp][lane] = v; else ovf[sp - lds_limit] = v; sp++; }
+    RT_DEV uint32_t pop(int &sp) { --sp; return (!SPILL || sp < lds_limit) ? lds[sp][lane] : ovf[sp - lds_limit]; }
+};
+
+// What a walk counts (counting build): node visits and triangle tests per lane, the rest per wave (lane 0 reports).
+template <bool COUNT> struct WfWalkStat {
+    unsigned long long n_nodes = 0, n_tris = 0, node_iters = 0, leaf_phases = 0, leaf_lanes = 0, refills = 0;
+    RT_DEV void node() { if (COUNT) n_nodes++; }
+    RT_DEV void tri() { if (COUNT) n_tris++; }
+};
+
+// ---- the round walker loop -----------------------------------------------------------------------------------------------------
+// The one traversal loop of the round pipeline: refill from the wave's slice, inner nodes until enough lanes wait at a leaf, then the leaf
+// phase of every waiting lane; in the counting build the in-flight histogram and the counter flush.  A walker is a policy WK, a struct
+// that holds the per-walk state of a lane and says what differs between the three (WfTraceWalk, WfLightFrameWalk, WfLightWalk):
+//   begin(slot)      read the ray from the path's record, reset the walk's state
+//   at_leaf()        the lane waits for the leaf phase
+//   step(stat)       one phase-1 step of a lane that does not wait; returns true when the walk ended (its result is written)
+//   leaf(stat)       the lane's leaf phase, with the same return
+//   HIST             first counter slot of its histogram of in-flight wave iterations per query (buckets of 32; filled when the host sets
+//                    CNT_WANT_HISTOGRAMS: one global atomic per query), or -1 for none
+//   WAVE_STATS       it reports refills, wave node-iterations, leaf phases and lanes, and its own share of the node visits / triangle tests
+//                    (CNT_WF_NODE_ITERS .. CNT_WF_LANE_TRIS): the closest-hit walker only
+// A walker is constructed in the branch that runs it: one that lives across another walker's loop keeps its registers there (24 VGPRs).
+// `active` is a word, not a bool, and is cleared in a branch of its own: as a bool assigned from the step's result the compiler carries it as
+// a lane mask through every merge of the step's branches, about fifteen scalar instructions per node step (profiles/r13_round_walk_loop.txt).
+template <bool COUNT, class WK>
+RT_DEV void wf_walk_loop(WK &w, const uint32_t *queue, WfSlice slice, unsigned long long *counters, int refill, int leaf_batch) {
+    uint32_t active = 0u;
+    WfWalkStat<COUNT> st;
+    uint32_t w_iter = 0, ray_start = 0; // COUNT: the wave iterations a query stays in flight -> counters[WK::HIST + min(15, iterations / 32)]
+    const bool hist = COUNT && WK::HIST >= 0 && counters && counters[CNT_WANT_HISTOGRAMS] != 0;
+    auto went = [&](bool over) { // after a lane's step or leaf phase: whether its walk ended there
+        if (over) active = 0u;
+        if (COUNT && hist && over) { uint32_t b = (w_iter - ray_start) >> 5; atomicAdd(&counters[WK::HIST + (b > 15u ? 15u : b)], 1ull); }
     };
-    unsigned long long n_nodes = 0, n_tris = 0;
-    unsigned long long w_node_iters = 0, w_leaf_phases = 0, w_leaf_lanes = 0, w_refills = 0; // wave-level (lane 0 reports)
-    uint32_t w_iter = 0, ray_start = 0; // COUNT: wave iterations a ray stays in flight -> histogram counters[CNT_WF_HIST_CLOSEST + min(15, iterations / 32)]
-    const bool hist = COUNT && counters && counters[CNT_WANT_HISTOGRAMS] != 0; // the host sets it when the histogram is wanted (one global atomic per query)
     for (;;) {
-        unsigned long long idle = __ballot(!active);
+        unsigned long long idle = __ballot(active == 0u);
         if (idle && (slice.pos < slice.end || !slice.done) && (__popcll(idle) >= refill || idle == ~0ull)) {
             if (slice.pos >= slice.end) wf_steal(slice);
             uint32_t item = 0;
-            if (COUNT) w_refills++;
-            if (wf_take(slice, !active, item)) {
-                slot = queue[item];
-                const float4 *r = wf_rec(W, slot);
-                float4 q0 = r[0], q1 = r[1];
-                o = f3(q0.x, q0.y, q0.z); d = f3(q0.w, q1.x, q1.y);
-                ray = make_ray_inv(o, d);
-                h_ray = S.exact_boxes ? pt_look_behind_abs(d, S.box_c2x) : 0.f;
-                cur = 0; sp = 0; hit = WF_MISS; best_t = RT_T_MAX; cull_t = RT_T_MAX; t2 = 2.f * RT_T_MAX; best_u = 0.f; best_v = 0.f;
-                active = true;
+            if (COUNT) st.refills++;
+            if (wf_take(slice, active == 0u, item)) {
+                w.begin(queue[item]);
+                active = 1u;
                 if (COUNT) ray_start = w_iter;
             }
         }
-        const unsigned long long m_active = __ballot(active);
+        const unsigned long long m_active = __ballot(active != 0u);
         if (!m_active) break;
-        // A thinly populated wave (the drain of a launch, small frames) does not make leaf lanes wait for 20 companions.
-        const int lb = min(leaf_batch & 255, (__popcll(m_active) * (leaf_batch >> 16) + 255) >> 8); // a share of the active lanes, in 1/256
-        // phase 1: inner nodes
-        for (;;) {
-            bool inner = active && !(cur & RT_LEAF_BIT);
-            unsigned long long m_inner = __ballot(inner);
-            unsigned long long m_leaf = __ballot(active && (cur & RT_LEAF_BIT));
-            if (!m_inner || __popcll(m_leaf) >= lb) break;
-            if (COUNT) { w_node_iters++; w_iter++; }
-            if (inner) {
-                const float4 *q = reinterpret_cast<const float4 *>(S.nodes + cur);
-                float4 lo0 = q[0], hi0 = q[1], lo1 = q[2], hi1 = q[3];
-                if (COUNT) n_nodes++;
-                float n0, n1;
-                bool h0 = slab_test(lo0, hi0, ray, cull_t, n0);
-                bool h1 = slab_test(lo1, hi1, ray, cull_t, n1);
-                uint32_t c0 = __float_as_uint(lo0.w), c1 = __float_as_uint(lo1.w);
-                if (h0 & h1) {
-                    bool swap = n1 < n0;
-                    wf_spush<SPILL>(stack, ovf, lds_limit, lane, sp, swap ? c0 : c1);
-                    cur = swap ? c1 : c0;
-                } else if (h0) cur = c0;
-                else if (h1) cur = c1;
-                else if (sp == 0) { // traversal finished: publish the hit
-                    store_hit();
-                    active = false;
-                    if (COUNT && hist) { uint32_t b = (w_iter - ray_start) >> 5; atomicAdd(&counters[CNT_WF_HIST_CLOSEST + (b > 15u ? 15u : b)], 1ull); }
-                } else cur = wf_spop<SPILL>(stack, ovf, lds_limit, lane, sp);
-            }
+        const int lb = pt_leaf_batch(leaf_batch, m_active);
+        for (;;) { // phase 1: inner nodes (the frame walk: and its cheap return steps)
+            const bool at_leaf = active != 0u && w.at_leaf(), busy = active != 0u && !at_leaf;
+            unsigned long long m_busy = __ballot(busy), m_leaf = __ballot(at_leaf);
+            if (!m_busy || __popcll(m_leaf) >= lb) break;
+            if (COUNT) { st.node_iters++; w_iter++; }
+            if (busy) went(w.step(st));
         }
         if (COUNT) w_iter++;
-        // phase 2: every lane waiting at a leaf tests its triangles
-        if (COUNT) { unsigned long long ml = __ballot(active && (cur & RT_LEAF_BIT)); if (ml) { w_leaf_phases++; w_leaf_lanes += __popcll(ml); } }
-        if (active && (cur & RT_LEAF_BIT)) {
-            if (cur != RT_EMPTY_LEAF) {
-                uint32_t i = cur & ~RT_LEAF_BIT;
-                for (;;) {
-                    TriIsect T = load_isect(S.tri_walk + i);
-                    if (COUNT) n_tris++;
-                    float t, u, v; bool inside;
-                    const uint32_t fi = T.pad >> 1; // index in the figure order
-                    if (tri_test_closer(T, o, d, cull_t, t, u, v, inside)) {
-                        const uint32_t best_i = hit & WF_INDEX_MASK;
-                        if (t < best_t || (t == best_t && fi < best_i)) { // reference tie rule: smallest t, equal t -> lowest figure index
-                            t2 = fminf(t2, best_t);
-                            best_t = t; best_u = u; best_v = v; hit = fi | (inside ? WF_INSIDE_BIT : 0u);
-                            cull_t = t + fmaxf(S.cull_k * t, h_ray);
-                        } else t2 = fminf(t2, t);
-                    }
-                    if (T.pad & 1u) break;
-                    i++;
-                }
-            }
-            if (sp == 0) {
-                store_hit();
-                active = false;
-                if (COUNT && hist) { uint32_t b = (w_iter - ray_start) >> 5; atomicAdd(&counters[CNT_WF_HIST_CLOSEST + (b > 15u ? 15u : b)], 1ull); }
-            } else cur = wf_spop<SPILL>(stack, ovf, lds_limit, lane, sp);
-        }
+        // phase 2: every lane waiting at a leaf runs its (expensive, division-heavy) tests
+        const bool at_leaf = active != 0u && w.at_leaf();
+        if (COUNT) { unsigned long long ml = __ballot(at_leaf); if (ml) { st.leaf_phases++; st.leaf_lanes += __popcll(ml); } }
+        if (at_leaf) went(w.leaf(st));
     }
     if (COUNT && counters) {
-        atomicAdd(&counters[CNT_NODE_VISITS], n_nodes); atomicAdd(&counters[CNT_TRI_TESTS], n_tris);
-        atomicAdd(&counters[CNT_WF_LANE_NODES], n_nodes); atomicAdd(&counters[CNT_WF_LANE_TRIS], n_tris);
-        if (lane == 0) { atomicAdd(&counters[CNT_WF_NODE_ITERS], w_node_iters); atomicAdd(&counters[CNT_WF_LEAF_PHASES], w_leaf_phases); atomicAdd(&counters[CNT_WF_LEAF_LANES], w_leaf_lanes); atomicAdd(&counters[CNT_WF_REFILLS], w_refills); }
+        atomicAdd(&counters[CNT_NODE_VISITS], st.n_nodes); atomicAdd(&counters[CNT_TRI_TESTS], st.n_tris);
+        if (WK::WAVE_STATS) {
+            atomicAdd(&counters[CNT_WF_LANE_NODES], st.n_nodes); atomicAdd(&counters[CNT_WF_LANE_TRIS], st.n_tris);
+            if ((threadIdx.x & 63) == 0) { atomicAdd(&counters[CNT_WF_NODE_ITERS], st.node_iters); atomicAdd(&counters[CNT_WF_LEAF_PHASES], st.leaf_phases); atomicAdd(&counters[CNT_WF_LEAF_LANES], st.leaf_lanes); atomicAdd(&counters[CNT_WF_REFILLS], st.refills); }
+        }
     }
 }
 
-// All-hits light sum (FiguresMix::getTotalPdf, distributions.h:148-165) with the reference's addition tree.
-// The finished sum goes straight into the pending bounce's pdf: E0.w += sum / n_lights (distributions.h:123,273).
-template <bool COUNT, bool SPILL>
-RT_DEV void wf_light_loop(const SceneView &S, const WfView &W, uint32_t (*stack)[64], const uint32_t *queue, WfSlice slice,
-                          unsigned long long *counters, int refill, int leaf_batch, int lds_limit) {
-    const int lane = threadIdx.x & 63;
-    uint32_t *ovf = SPILL ? W.ovf + ((size_t)blockIdx.x * 256u + threadIdx.x) * WF_OVF : nullptr;
-    bool active = false, descending = true;
+// What every round walker keeps of its query: the path's slot, the ray read from its record, and its place in the two-box tree.
+struct WfWalkRay {
     uint32_t slot = 0, cur = 0;
     int sp = 0;
-    unsigned long long addmask = 0;
-    float v = 0.f;
     F3 o = f3(0.f, 0.f, 0.f), d = f3(0.f, 0.f, 1.f);
     RayInv ray = make_ray_inv(o, d);
-    unsigned long long n_nodes = 0, n_tris = 0;
-    for (;;) {
-        unsigned long long idle = __ballot(!active);
-        if (idle && (slice.pos < slice.end || !slice.done) && (__popcll(idle) >= refill || idle == ~0ull)) {
-            if (slice.pos >= slice.end) wf_steal(slice);
-            uint32_t item = 0;
-            if (wf_take(slice, !active, item)) {
-                slot = queue[item];
-                const float4 *r = wf_rec(W, slot);
-                float4 q0 = r[0], q1 = r[1];
-                o = f3(q0.x, q0.y, q0.z); d = f3(q0.w, q1.x, q1.y);
-                ray = make_ray_inv(o, d);
-                cur = 0; sp = 0; addmask = 0; v = 0.f; descending = true;
-                active = true;
-            }
-        }
-        const unsigned long long m_active = __ballot(active);
-        if (!m_active) break;
-        const int lb = min(leaf_batch & 255, (__popcll(m_active) * (leaf_batch >> 16) + 255) >> 8);
-        // phase 1: node steps and (cheap) return steps, until enough lanes wait at a leaf
-        for (;;) {
-            bool at_leaf = active && descending && (cur & RT_LEAF_BIT);
-            bool busy = active && !at_leaf;
-            if (!__ballot(busy) || __popcll(__ballot(at_leaf)) >= lb) break;
-            if (busy) {
-                if (descending) {
-                    const float4 *q = reinterpret_cast<const float4 *>(S.light_nodes + cur);
-                    float4 lo0 = q[0], hi0 = q[1], lo1 = q[2], hi1 = q[3];
-                    if (COUNT) n_nodes++;
-                    float n0, n1;
-                    bool h0 = slab_test(lo0, hi0, ray, RT_T_MAX, n0);
-                    bool h1 = slab_test(lo1, hi1, ray, RT_T_MAX, n1);
-                    uint32_t c0 = __float_as_uint(lo0.w), c1 = __float_as_uint(lo1.w);
-                    if (h0 & h1) { addmask &= ~(1ull << sp); wf_spush<SPILL>(stack, ovf, lds_limit, lane, sp, c1); cur = c0; }
-                    else if (h0) cur = c0;
-                    else if (h1) cur = c1;
-                    else { v = 0.f; descending = false; }
-                } else if (sp == 0) { // sum complete
-                    int depth = (int)(__float_as_uint(reinterpret_cast<const float *>(wf_rec(W, slot) + 3)[3]) & 15u);
-                    float *pdf = reinterpret_cast<float *>(wf_entry(W, slot, depth)) + 3;
-                    *pdf = *pdf + v / S.n_lights_f;
-                    active = false;
-                } else {
-                    uint32_t f = wf_spop<SPILL>(stack, ovf, lds_limit, lane, sp);
-                    if ((addmask >> sp) & 1ull) v = __uint_as_float(f) + v;       // left total + right total
-                    else { addmask |= 1ull << sp; wf_spush<SPILL>(stack, ovf, lds_limit, lane, sp, __float_as_uint(v)); cur = f; descending = true; }
-                }
-            }
-        }
-        // phase 2: leaves
-        if (active && descending && (cur & RT_LEAF_BIT)) {
-            float result = 0.f;
-            if (cur != RT_EMPTY_LEAF) {
-                uint32_t i = cur & ~RT_LEAF_BIT;
-                for (;;) {
-                    bool last;
-                    if (COUNT) n_tris++;
-                    result += light_pdf_one(S.lights + i, o, d, last, S.hw7 != 0);
-                    if (last) break;
-                    i++;
-                }
-            }
-            v = result;
-            descending = false;
-        }
+    RT_DEV void read(const WfView &W, uint32_t s) {
+        slot = s;
+        const float4 *r = wf_rec(W, slot);
+        float4 q0 = r[0], q1 = r[1];
+        o = f3(q0.x, q0.y, q0.z); d = f3(q0.w, q1.x, q1.y);
+        ray = make_ray_inv(o, d);
+        cur = 0; sp = 0;
     }
-    if (COUNT && counters) { atomicAdd(&counters[CNT_NODE_VISITS], n_nodes); atomicAdd(&counters[CNT_TRI_TESTS], n_tris); }
+    RT_DEV bool at_leaf() const { return (cur & RT_LEAF_BIT) != 0u; }
+};
+
+// The best hit of a closest-hit walk so far: the reference's tie rule, and what the exactness gate needs.  PtTraceWalk of rt_persistent.h keeps the same
+// lines as members of its own: through this struct two of its kernels grew by 265 instructions (profiles/r13_round_walk_loop.txt).
+// Boxes are pruned, and farther hits dropped, only beyond cull_t = best_t + the look-behind of rt_exact.h: the runner-up of the
+// best hit must be SEEN, whatever tree the walk uses, to decide at the end of the walk whether the exact walk is needed.
+struct WfClosest {
+    uint32_t hit = WF_MISS;
+    float best_t = RT_T_MAX, best_u = 0.f, best_v = 0.f;
+    float cull_t = RT_T_MAX, t2 = 2.f * RT_T_MAX, h_ray = 0.f; // t2: the runner-up's t; h_ray: absolute part of the look-behind (pt_look_behind)
+    RT_DEV void reset(const SceneView &S, F3 d) {
+        h_ray = S.exact_boxes ? pt_look_behind_abs(d, S.box_c2x) : 0.f;
+        hit = WF_MISS; best_t = RT_T_MAX; cull_t = RT_T_MAX; t2 = 2.f * RT_T_MAX; best_u = 0.f; best_v = 0.f;
+    }
+    RT_DEV void offer(const SceneView &S, uint32_t fi, float t, float u, float v, bool inside) { // fi: index in the figure order
+        const uint32_t best_i = hit & WF_INDEX_MASK;
+        if (t < best_t || (t == best_t && fi < best_i)) { // reference tie rule: smallest t, equal t -> lowest figure index
+            t2 = fminf(t2, best_t);
+            best_t = t; best_u = u; best_v = v; hit = fi | (inside ? WF_INSIDE_BIT : 0u);
+            cull_t = t + fmaxf(S.cull_k * t, h_ray);
+        } else t2 = fminf(t2, t);
+    }
+    RT_DEV void store(const SceneView &S, const WfView &W, uint32_t slot) const { // the gate (pt_shade_item) decides with the runner-up's t whether this hit needs the exact walk
+        wf_rec(W, slot)[2] = make_float4(best_t, best_u, best_v, __uint_as_float(S.exact_boxes && hit != WF_MISS ? hit | pt_gap_code(best_t, t2) : hit));
+    }
+};
+
+// ---- closest hit: near child first, the other on the stack -------------------------------------------------------------------------
+template <bool SPILL> struct WfTraceWalk : WfWalkRay {
+    static constexpr int HIST = CNT_WF_HIST_CLOSEST;
+    static constexpr bool WAVE_STATS = true;
+    const SceneView &S; const WfView &W; WfStack<SPILL> stk;
+    WfClosest best;
+    RT_DEV WfTraceWalk(const SceneView &S_, const WfView &W_, uint32_t (*stack)[64], int lds_limit) : S(S_), W(W_), stk(W_, stack, lds_limit) {}
+    RT_DEV void begin(uint32_t s) { read(W, s); best.reset(S, d); }
+    RT_DEV bool next() { // the walk goes on with what its stack holds, or publishes the hit
+        if (sp == 0) { best.store(S, W, slot); return true; }
+        cur = stk.pop(sp);
+        return false;
+    }
+    template <bool COUNT> RT_DEV bool step(WfWalkStat<COUNT> &n) {
+        const float4 *q = reinterpret_cast<const float4 *>(S.nodes + cur);
+        float4 lo0 = q[0], hi0 = q[1], lo1 = q[2], hi1 = q[3];
+        n.node();
+        float n0, n1;
+        bool h0 = slab_test(lo0, hi0, ray, best.cull_t, n0);
+        bool h1 = slab_test(lo1, hi1, ray, best.cull_t, n1);
+        uint32_t c0 = __float_as_uint(lo0.w), c1 = __float_as_uint(lo1.w);
+        if (h0 & h1) {
+            bool swap = n1 < n0;
+            stk.push(sp, swap ? c0 : c1);
+            cur = swap ? c1 : c0;
+        } else {
+            cur = h0 ? c0 : c1;                      // one select, then one branch for the lanes that hit neither box
+            if (!(h0 | h1)) return next();
+        }
+        return false;
+    }
+    template <bool COUNT> RT_DEV bool leaf(WfWalkStat<COUNT> &n) {
+        if (cur != RT_EMPTY_LEAF) {
+            uint32_t i = cur & ~RT_LEAF_BIT;
+            for (;;) {
+                TriIsect T = load_isect(S.tri_walk + i);
+                n.tri();
+                float t, u, v; bool inside;
+                if (tri_test_closer(T, o, d, best.cull_t, t, u, v, inside)) best.offer(S, T.pad >> 1, t, u, v, inside);
+                if (T.pad & 1u) break;
+                i++;
+            }
+        }
+        return next();
+    }
+};
+
+// The write-back of a finished light sum v (FiguresMix::getTotalPdf) into the pending bounce's pdf: E0.w += v / n_lights (distributions.h:123,273).
+RT_DEV void wf_add_light_pdf(const SceneView &S, const WfView &W, uint32_t slot, float v) {
+    int depth = (int)(__float_as_uint(reinterpret_cast<const float *>(wf_rec(W, slot) + 3)[3]) & 15u);
+    float *pdf = reinterpret_cast<float *>(wf_entry(W, slot, depth)) + 3;
+    *pdf = *pdf + v / S.n_lights_f;
 }
+
+// ---- all-hits light sum (FiguresMix::getTotalPdf, distributions.h:148-165) with the reference's addition tree, as a frame walk ----------
+// The walk of the SPILL variant (trees deeper than WF_STACK), so its stack always spills.  A lane descends to a leaf, then returns: the
+// stack holds the right child of a node whose left side is being summed, then (addmask) the left side's total while the right side is.
+// n_nodes counts the descending steps only; the leaf phase never ends the walk, a return step at an empty stack does.
+struct WfLightFrameWalk : WfWalkRay {
+    static constexpr int HIST = -1;
+    static constexpr bool WAVE_STATS = false;
+    const SceneView &S; const WfView &W; WfStack<true> stk;
+    bool descending = true;
+    unsigned long long addmask = 0;
+    float v = 0.f;
+    RT_DEV WfLightFrameWalk(const SceneView &S_, const WfView &W_, uint32_t (*stack)[64], int lds_limit) : S(S_), W(W_), stk(W_, stack, lds_limit) {}
+    RT_DEV void begin(uint32_t s) { read(W, s); addmask = 0; v = 0.f; descending = true; }
+    RT_DEV bool at_leaf() const { return descending && (cur & RT_LEAF_BIT); }
+    template <bool COUNT> RT_DEV bool step(WfWalkStat<COUNT> &n) {
+        if (descending) {
+            const float4 *q = reinterpret_cast<const float4 *>(S.light_nodes + cur);
+            float4 lo0 = q[0], hi0 = q[1], lo1 = q[2], hi1 = q[3];
+            n.node();
+            float n0, n1;
+            bool h0 = slab_test(lo0, hi0, ray, RT_T_MAX, n0);
+            bool h1 = slab_test(lo1, hi1, ray, RT_T_MAX, n1);
+            uint32_t c0 = __float_as_uint(lo0.w), c1 = __float_as_uint(lo1.w);
+            if (h0 & h1) { addmask &= ~(1ull << sp); stk.push(sp, c1); cur = c0; }
+            else if (h0) cur = c0;
+            else if (h1) cur = c1;
+            else { v = 0.f; descending = false; }
+        } else if (sp == 0) { wf_add_light_pdf(S, W, slot, v); return true; } // sum complete
+        else {
+            uint32_t f = stk.pop(sp);
+            if ((addmask >> sp) & 1ull) v = __uint_as_float(f) + v;       // left total + right total
+            else { addmask |= 1ull << sp; stk.push(sp, __float_as_uint(v)); cur = f; descending = true; }
+        }
+        return false;
+    }
+    template <bool COUNT> RT_DEV bool leaf(WfWalkStat<COUNT> &n) {
+        float result = 0.f;
+        if (cur != RT_EMPTY_LEAF) {
+            uint32_t i = cur & ~RT_LEAF_BIT;
+            for (;;) {
+                bool last;
+                n.tri();
+                result += light_pdf_one(S.lights + i, o, d, last, S.hw7 != 0);
+                if (last) break;
+                i++;
+            }
+        }
+        v = result;
+        descending = false;
+        return false;
+    }
+};
 
 // The same sum, decoupled: WHICH lights the ray hits is found by a plain all-hits walk (no frames, left child first, so the
 // hits come out in the reference's light order); in WHAT ORDER their terms are added matters only for three or more hits
@@ -509,118 +541,87 @@ RT_DEV void wf_light_loop(const SceneView &S, const WfView &W, uint32_t (*stack)
 // Hits are kept in the top of the lane's LDS stack column ({index, term} pairs growing downwards); a query whose hits would
 // run into its stack, or with more than WF_MAX_LIGHT_HITS of them, is handed to wf_light_exact_kernel (frame walk of rt_device.h).
 #define WF_MAX_LIGHT_HITS 5
-template <bool COUNT>
-RT_DEV void wf_light_loop_lean(const SceneView &S, const WfView &W, uint32_t (*stack)[64], const uint32_t *queue, WfSlice slice,
-                               unsigned long long *counters, int refill, int leaf_batch, uint32_t *slow_count) {
-    const int lane = threadIdx.x & 63;
-    bool active = false, overflow = false;
-    uint32_t slot = 0, cur = 0;
-    int sp = 0, k = 0;
-    F3 o = f3(0.f, 0.f, 0.f), d = f3(0.f, 0.f, 1.f);
-    RayInv ray = make_ray_inv(o, d);
-    unsigned long long n_nodes = 0, n_tris = 0;
-    uint32_t w_iter = 0, ray_start = 0; // COUNT: histogram of in-flight wave iterations per query, counters[CNT_WF_HIST_LIGHT + ...]
-    const bool hist = COUNT && counters && counters[CNT_WANT_HISTOGRAMS] != 0;
-    // Hit j of the finished walk: light index in stack[31-2j], term in stack[30-2j] (ascending indices); the bottom of the
-    // column is free by then and holds the separation depths while the terms are merged.
-    auto finish = [&]() {
-        active = false;
-        if (overflow) { W.q_slow[atomicAdd(slow_count, 1u)] = slot; return; }
-        float v = 0.f;
-        if (k == 1) v = __uint_as_float(stack[WF_STACK - 2][lane]);
-        else if (k == 2) v = __uint_as_float(stack[WF_STACK - 2][lane]) + __uint_as_float(stack[WF_STACK - 4][lane]);
-        else if (k > 2) {
-            // Separation depth of each pair of neighbouring hits (two independent table reads each), then merge the pair that
-            // separates DEEPEST first: the node where they separate has exactly these two groups under its left and right
-            // child, so this rebuilds sum(node) = sum(left) + sum(right) bottom-up; inside a leaf the pseudo depths make it
-            // ((a + b) + c).  Terms live in column words 30-2j, depths in words 0..k-2.
-            const uint32_t nl = S.n_lights;
-            for (int j = 1; j < k; j++) {
-                uint32_t a0 = stack[WF_STACK - 1 - 2 * (j - 1)][lane], b0 = stack[WF_STACK - 1 - 2 * j][lane]; // boundaries a0 .. b0-1
-                uint32_t len = b0 - a0;
-                uint32_t lv = 31u - (uint32_t)__clz((int)len);
-                uint16_t m0 = S.light_sep[(size_t)lv * nl + a0], m1 = S.light_sep[(size_t)lv * nl + (b0 - (1u << lv))];
-                stack[j - 1][lane] = m0 < m1 ? m0 : m1;
-            }
-            for (int n = k; n > 1; n--) {
-                int best = 1;
-                uint32_t bd = stack[0][lane];
-                for (int i = 2; i < n; i++) { uint32_t di = stack[i - 1][lane]; if (di > bd) { bd = di; best = i; } }
-                float merged = __uint_as_float(stack[WF_STACK - 2 - 2 * (best - 1)][lane]) + __uint_as_float(stack[WF_STACK - 2 - 2 * best][lane]);
-                stack[WF_STACK - 2 - 2 * (best - 1)][lane] = __float_as_uint(merged);
-                for (int i = best; i < n - 1; i++) {
-                    stack[WF_STACK - 2 - 2 * i][lane] = stack[WF_STACK - 2 - 2 * (i + 1)][lane];
-                    stack[i - 1][lane] = stack[i][lane];
-                }
-            }
-            v = __uint_as_float(stack[WF_STACK - 2][lane]);
-        }
-        int depth = (int)(__float_as_uint(reinterpret_cast<const float *>(wf_rec(W, slot) + 3)[3]) & 15u);
-        float *pdf = reinterpret_cast<float *>(wf_entry(W, slot, depth)) + 3;
-        *pdf = *pdf + v / S.n_lights_f;                                  // distributions.h:123,273
-    };
-    for (;;) {
-        unsigned long long idle = __ballot(!active);
-        if (idle && (slice.pos < slice.end || !slice.done) && (__popcll(idle) >= refill || idle == ~0ull)) {
-            if (slice.pos >= slice.end) wf_steal(slice);
-            uint32_t item = 0;
-            if (wf_take(slice, !active, item)) {
-                slot = queue[item];
-                const float4 *r = wf_rec(W, slot);
-                float4 q0 = r[0], q1 = r[1];
-                o = f3(q0.x, q0.y, q0.z); d = f3(q0.w, q1.x, q1.y);
-                ray = make_ray_inv(o, d);
-                cur = 0; sp = 0; k = 0; overflow = false;
-                active = true;
-                if (COUNT) ray_start = w_iter;
-            }
-        }
-        const unsigned long long m_active = __ballot(active);
-        if (!m_active) break;
-        const int lb = min(leaf_batch & 255, (__popcll(m_active) * (leaf_batch >> 16) + 255) >> 8); // a share of the active lanes, in 1/256
-        for (;;) { // phase 1: inner nodes
-            bool inner = active && !(cur & RT_LEAF_BIT);
-            if (!__ballot(inner) || __popcll(__ballot(active && (cur & RT_LEAF_BIT))) >= lb) break;
-            if (COUNT) w_iter++;
-            if (inner) {
-                const float4 *q = reinterpret_cast<const float4 *>(S.light_nodes + cur);
-                float4 lo0 = q[0], hi0 = q[1], lo1 = q[2], hi1 = q[3];
-                if (COUNT) n_nodes++;
-                float n0, n1;
-                bool h0 = slab_test(lo0, hi0, ray, RT_T_MAX, n0);
-                bool h1 = slab_test(lo1, hi1, ray, RT_T_MAX, n1);
-                uint32_t c0 = __float_as_uint(lo0.w), c1 = __float_as_uint(lo1.w);
-                if (h0 & h1) { stack[sp++][lane] = c1; cur = c0; if (sp + 2 * k >= WF_STACK) overflow = true; }
-                else if (h0) cur = c0;
-                else if (h1) cur = c1;
-                else if (sp == 0) { finish(); if (COUNT && hist) { uint32_t b = (w_iter - ray_start) >> 5; atomicAdd(&counters[CNT_WF_HIST_LIGHT + (b > 15u ? 15u : b)], 1ull); } }
-                else cur = stack[--sp][lane];
-            }
-        }
-        if (COUNT) w_iter++;
-        if (active && (cur & RT_LEAF_BIT)) { // phase 2: leaves
-            if (cur != RT_EMPTY_LEAF) {
-                uint32_t i = cur & ~RT_LEAF_BIT;
-                for (;;) {
-                    bool last, robust; uint32_t li;
-                    if (COUNT) n_tris++;
-                    float term = pt_light_pdf_one(S, S.lights + i, o, d, last, robust, li); // the reference topology over `lights`: the position i IS the light index (li is not used)
-                    if (term != 0.f) { // a hit (a miss contributes exactly 0, and adding 0 changes nothing)
-                        if (!robust || k >= WF_MAX_LIGHT_HITS || sp + 2 * k + 2 >= WF_STACK) overflow = true; // not robust against the reference's box tests: exact walk
-                        else { stack[WF_STACK - 1 - 2 * k][lane] = i; stack[WF_STACK - 2 - 2 * k][lane] = __float_as_uint(term); k++; }
-                    }
-                    if (last) break;
-                    i++;
-                }
-            }
-            if (sp == 0) { finish(); if (COUNT && hist) { uint32_t b = (w_iter - ray_start) >> 5; atomicAdd(&counters[CNT_WF_HIST_LIGHT + (b > 15u ? 15u : b)], 1ull); } }
-            else cur = stack[--sp][lane];
+// The sum of the k hits of a finished walk in the reference's association.  Hit j: light index in stack[WF_STACK-1-2j], term in
+// stack[WF_STACK-2-2j], ascending indices; the bottom of the column is free by then and holds the separation depths while the terms
+// are merged.  (PtLightWalk::end of rt_persistent.h keeps its own copy for its P8_STACK columns, see profiles/r13_round_walk_loop.txt.)
+RT_DEV float wf_merge_light_hits(const SceneView &S, uint32_t (*stack)[64], int lane, int k) {
+    if (k == 0) return 0.f;
+    if (k == 1) return __uint_as_float(stack[WF_STACK - 2][lane]);
+    if (k == 2) return __uint_as_float(stack[WF_STACK - 2][lane]) + __uint_as_float(stack[WF_STACK - 4][lane]);
+    // Separation depth of each pair of neighbouring hits (two independent table reads each), then merge the pair that
+    // separates DEEPEST first: the node where they separate has exactly these two groups under its left and right
+    // child, so this rebuilds sum(node) = sum(left) + sum(right) bottom-up; inside a leaf the pseudo depths make it
+    // ((a + b) + c).  Terms live in column words WF_STACK-2-2j, depths in words 0..k-2.
+    const uint32_t nl = S.n_lights;
+    for (int j = 1; j < k; j++) {
+        uint32_t a0 = stack[WF_STACK - 1 - 2 * (j - 1)][lane], b0 = stack[WF_STACK - 1 - 2 * j][lane]; // boundaries a0 .. b0-1
+        uint32_t len = b0 - a0;
+        uint32_t lv = 31u - (uint32_t)__clz((int)len);
+        uint16_t m0 = S.light_sep[(size_t)lv * nl + a0], m1 = S.light_sep[(size_t)lv * nl + (b0 - (1u << lv))];
+        stack[j - 1][lane] = m0 < m1 ? m0 : m1;
+    }
+    for (int n = k; n > 1; n--) {
+        int best = 1;
+        uint32_t bd = stack[0][lane];
+        for (int i = 2; i < n; i++) { uint32_t di = stack[i - 1][lane]; if (di > bd) { bd = di; best = i; } }
+        float merged = __uint_as_float(stack[WF_STACK - 2 - 2 * (best - 1)][lane]) + __uint_as_float(stack[WF_STACK - 2 - 2 * best][lane]);
+        stack[WF_STACK - 2 - 2 * (best - 1)][lane] = __float_as_uint(merged);
+        for (int i = best; i < n - 1; i++) {
+            stack[WF_STACK - 2 - 2 * i][lane] = stack[WF_STACK - 2 - 2 * (i + 1)][lane];
+            stack[i - 1][lane] = stack[i][lane];
         }
     }
-    if (COUNT && counters) { atomicAdd(&counters[CNT_NODE_VISITS], n_nodes); atomicAdd(&counters[CNT_TRI_TESTS], n_tris); }
+    return __uint_as_float(stack[WF_STACK - 2][lane]);
 }
 
-// ---- traverse: both loops in one persistent launch -------------------------------------------------------------------
+struct WfLightWalk : WfWalkRay {
+    static constexpr int HIST = CNT_WF_HIST_LIGHT;
+    static constexpr bool WAVE_STATS = false;
+    const SceneView &S; const WfView &W; uint32_t (*stack)[64]; uint32_t *slow_count;
+    const int lane = threadIdx.x & 63;
+    bool overflow = false; // wf_light_exact_kernel sums this query
+    int k = 0;             // hits so far
+    RT_DEV WfLightWalk(const SceneView &S_, const WfView &W_, uint32_t (*stack_)[64], uint32_t *slow) : S(S_), W(W_), stack(stack_), slow_count(slow) {}
+    RT_DEV void begin(uint32_t s) { read(W, s); k = 0; overflow = false; }
+    RT_DEV bool next() { // the walk goes on with what its stack holds, or ends: to q_slow, or with its sum
+        if (sp != 0) { cur = stack[--sp][lane]; return false; }
+        if (overflow) W.q_slow[atomicAdd(slow_count, 1u)] = slot;
+        else wf_add_light_pdf(S, W, slot, wf_merge_light_hits(S, stack, lane, k));
+        return true;
+    }
+    template <bool COUNT> RT_DEV bool step(WfWalkStat<COUNT> &n) {
+        const float4 *q = reinterpret_cast<const float4 *>(S.light_nodes + cur);
+        float4 lo0 = q[0], hi0 = q[1], lo1 = q[2], hi1 = q[3];
+        n.node();
+        float n0, n1;
+        bool h0 = slab_test(lo0, hi0, ray, RT_T_MAX, n0);
+        bool h1 = slab_test(lo1, hi1, ray, RT_T_MAX, n1);
+        uint32_t c0 = __float_as_uint(lo0.w), c1 = __float_as_uint(lo1.w);
+        if (h0 & h1) { stack[sp++][lane] = c1; cur = c0; if (sp + 2 * k >= WF_STACK) overflow = true; }
+        else if (h0 | h1) cur = h0 ? c0 : c1;
+        else return next();
+        return false;
+    }
+    template <bool COUNT> RT_DEV bool leaf(WfWalkStat<COUNT> &n) {
+        if (cur != RT_EMPTY_LEAF) {
+            uint32_t i = cur & ~RT_LEAF_BIT;
+            for (;;) {
+                bool last, robust; uint32_t li;
+                n.tri();
+                float term = pt_light_pdf_one(S, S.lights + i, o, d, last, robust, li); // the reference topology over `lights`: the position i IS the light index (li is not used)
+                if (term != 0.f) { // a hit (a miss contributes exactly 0, and adding 0 changes nothing)
+                    if (!robust || k >= WF_MAX_LIGHT_HITS || sp + 2 * k + 2 >= WF_STACK) overflow = true; // not robust against the reference's box tests: exact walk
+                    else { stack[WF_STACK - 1 - 2 * k][lane] = i; stack[WF_STACK - 2 - 2 * k][lane] = __float_as_uint(term); k++; }
+                }
+                if (last) break;
+                i++;
+            }
+        }
+        return next();
+    }
+};
+
+// ---- traverse: both walks in one persistent launch -------------------------------------------------------------------
 // Blocks [0, nb_t) own the trace queue, the rest own the light queue; nb_t follows the queue lengths weighted by the
 // measured cost of one query of each kind (about equal on the benchmark scene since the light loop became frame-free).
 // After its own queue a block helps with the other one's dynamic tail, so a wrong split only costs a few chunks.
@@ -643,15 +644,20 @@ __global__ __launch_bounds__(256) void wf_traverse_kernel(SceneView S, WfView W,
     const uint32_t *q_t = W.q_trace[round & 1], *q_l = W.q_light;
     uint32_t *head_t = W.ctr + WF_CTR * round + 2, *head_l = W.ctr + WF_CTR * round + 3;
     const bool tracer = blockIdx.x < nb_t;
-    if (tracer) wf_trace_loop<COUNT, SPILL>(S, W, stack, q_t, wf_slice(ct, head_t, dyn, 0u, nb_t, true), counters, t_refill, t_batch, lds_limit);
+    auto trace = [&](bool owner) {
+        WfTraceWalk<SPILL> w(S, W, stack, lds_limit);
+        wf_walk_loop<COUNT>(w, q_t, wf_slice(ct, head_t, dyn, 0u, nb_t, owner), counters, t_refill, t_batch);
+    };
+    if (tracer) trace(true);
     if (cl) {
-        if (SPILL) wf_light_loop<COUNT, true>(S, W, stack, q_l, wf_slice(cl, head_l, dyn, nb_t, nb - nb_t, !tracer), counters, l_refill, l_batch, lds_limit);
-        else wf_light_loop_lean<COUNT>(S, W, stack, q_l, wf_slice(cl, head_l, dyn, nb_t, nb - nb_t, !tracer), counters, l_refill, l_batch, W.ctr + WF_CTR * round + 4);
+        const WfSlice slice = wf_slice(cl, head_l, dyn, nb_t, nb - nb_t, !tracer);
+        if (SPILL) { WfLightFrameWalk w(S, W, stack, lds_limit); wf_walk_loop<COUNT>(w, q_l, slice, counters, l_refill, l_batch); }
+        else { WfLightWalk w(S, W, stack, W.ctr + WF_CTR * round + 4); wf_walk_loop<COUNT>(w, q_l, slice, counters, l_refill, l_batch); }
     }
-    if (!tracer) wf_trace_loop<COUNT, SPILL>(S, W, stack, q_t, wf_slice(ct, head_t, dyn, 0u, nb_t, false), counters, t_refill, t_batch, lds_limit);
+    if (!tracer) trace(false);
 }
 
-// The few light queries the lean loop could not finish: the plain reference-order frame walk (light_pdf_sum), one lane each.
+// The few light queries the lean walker (WfLightWalk) could not finish: the plain reference-order frame walk (light_pdf_sum), one lane each.
 __global__ __launch_bounds__(64) void wf_light_exact_kernel(SceneView S, WfView W, uint32_t round) {
     const uint32_t count = W.ctr[WF_CTR * round + 4];
     uint32_t stack[RT_STACK_SIZE];
@@ -662,9 +668,7 @@ __global__ __launch_bounds__(64) void wf_light_exact_kernel(SceneView S, WfView 
         Counters cnt; cnt.closest = cnt.lightq = cnt.nodes = cnt.tris = 0;
         const F3 x = f3(q0.x, q0.y, q0.z), dir = f3(q0.w, q1.x, q1.y);
         float v = S.exact_boxes ? ref_light_pdf_sum(S, x, dir, stack) : light_pdf_sum<false>(S, x, dir, stack, cnt);
-        int depth = (int)(__float_as_uint(r[3].w) & 15u);
-        float *pdf = reinterpret_cast<float *>(wf_entry(W, slot, depth)) + 3;
-        *pdf = *pdf + v / S.n_lights_f;
+        wf_add_light_pdf(S, W, slot, v);
     }
 }
 

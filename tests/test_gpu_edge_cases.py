@@ -346,3 +346,41 @@ def test_counting_render_equals_the_plain_render(rt, sphere_scene, integrator):
     assert np.array_equal(cnt, plain, equal_nan=True) and np.array_equal(cnt8, plain8)
     assert (stc.closest_hit_queries, stc.light_pdf_queries) == (st.closest_hit_queries, st.light_pdf_queries)
     assert st.closest_hit_queries > 64 * 48 * 4 and stc.node_visits > 0
+
+
+# (node_visits, triangle_tests, closest_hit_queries, light_pdf_queries, exact_light_sums) of the counting renders below, recorded on an MI355X
+# with the library of commit 22b16d5 (the last one with three hand-copied traversal loops); three renders gave the same numbers each time.
+ROUND_COUNTERS_22b16d5 = {
+    ("sphere", "plain"): (966360, 228998, 46971, 31611, 0),
+    ("sphere", "spill"): (966360, 228998, 46971, 31611, 0),
+    ("soup", "plain"): (1681766, 282930, 41230, 23950, 249),
+    ("soup", "spill"): (1681766, 282930, 41230, 23950, 0),
+}
+
+
+@pytest.mark.parametrize("name", ["sphere", "soup"])
+def test_counting_render_of_the_round_pipeline(rt, sphere_scene, monkeypatch, name):
+    """The round pipeline's counting kernels (wf_traverse_kernel<true, *>), with the LDS stacks and with the spill variant on nearly every
+    ray (RTAMD_WF_LDS_STACK=3): the frame is the plain render's and the oracle's, and the counters are the parent's.  A round walk depends
+    only on its own ray, so node visits and triangle tests repeat exactly.  The soup (230 emissive triangles; about 6 % of the rays started
+    inside it cross three or more lights, 0.1 % six or more) reaches the merge of three and more light hits and the lean walker's overflow
+    queue; the spill variant sums with the frame walk and hands nothing to the exact kernel."""
+    sd, (w, h, spp) = (sphere_scene, (64, 48, 5)) if name == "sphere" else (pin_cases.random_triangle_scene(n=700, seed=21), (72, 48, 5))
+    orc, _, _ = oracle_lib.Hw8Oracle(sd).render(w, h, spp)
+    monkeypatch.setenv("RTAMD_KERNEL", "wavefront")
+    scene = rt.Scene(sd)
+    queries = []
+    for variant in ("plain", "spill"):
+        if variant == "spill": monkeypatch.setenv("RTAMD_WF_LDS_STACK", "3")
+        plain, plain8, st = scene.render(w, h, spp)
+        cnt, cnt8, stc = scene.render(w, h, spp, counters=True)
+        got = (stc.node_visits, stc.triangle_tests, stc.closest_hit_queries, stc.light_pdf_queries, stc.exact_light_sums)
+        print(f"{name} {variant}: node visits, triangle tests, closest-hit queries, light queries, exact light sums = {got}")
+        assert st.pipeline == rt.RT_PIPELINE_ROUNDS and stc.pipeline == rt.RT_PIPELINE_ROUNDS and stc.launches == st.launches > 1
+        assert np.array_equal(cnt, plain) and np.array_equal(cnt8, plain8) and np.array_equal(cnt, orc)
+        if (name, variant) == ("soup", "plain"): assert stc.exact_light_sums > 0   # the lean walker's overflow queue was used
+        assert got == ROUND_COUNTERS_22b16d5[(name, variant)]
+        queries.append(got[2:4])
+    monkeypatch.delenv("RTAMD_WF_LDS_STACK")
+    scene.close()
+    assert queries[0] == queries[1]
