@@ -772,6 +772,14 @@ RT_DEV uint32_t udiv24(uint32_t n, uint32_t d, float rcp_d, uint32_t &rem) {
     rem = (uint32_t)r;
     return q;
 }
+// The end of the mapping, shared with for_each_pixel: shard-local tile st at (gtx, gty) of the tile grid, 8x8 sub-tile (sx, sy) in it, pixel `lane` of that.
+RT_DEV void subtile_to_pixel(const RenderView &R, uint32_t st, uint32_t gtx, uint32_t gty, uint32_t sx, uint32_t sy, uint32_t lane, int &x, int &y, bool &inside, size_t &out_index) {
+    int tx0 = (int)gtx * R.tile_w, ty0 = (int)gty * R.tile_h;
+    int lx = (int)sx * 8 + (int)(lane & 7), ly = (int)sy * 8 + (int)(lane >> 3);
+    x = tx0 + lx; y = ty0 + ly;
+    inside = x < R.width && y < R.height;
+    out_index = R.shard_count > 1 ? ((size_t)st * R.tile_h + ly) * R.tile_w + lx : (size_t)y * R.width + x;
+}
 RT_DEV void slot_to_pixel(const RenderView &R, uint32_t slot, int &x, int &y, bool &inside, size_t &out_index) {
     const int sub_x = R.tile_w >> 3, sub_per_tile = sub_x * (R.tile_h >> 3);
     uint32_t w = slot >> 6, lane = slot & 63u; // w < 2^24: a launch holds fewer than 2^30 slots
@@ -781,11 +789,57 @@ RT_DEV void slot_to_pixel(const RenderView &R, uint32_t slot, int &x, int &y, bo
     if (gt < (1u << 24)) gty = udiv24(gt, (uint32_t)R.tiles_x, __builtin_amdgcn_rcpf((float)R.tiles_x), gtx);
     else { gty = gt / (uint32_t)R.tiles_x; gtx = gt % (uint32_t)R.tiles_x; }
     sy = udiv24(sub, (uint32_t)sub_x, __builtin_amdgcn_rcpf((float)sub_x), sx);
-    int tx0 = (int)gtx * R.tile_w, ty0 = (int)gty * R.tile_h;
-    int lx = (int)sx * 8 + (int)(lane & 7), ly = (int)sy * 8 + (int)(lane >> 3);
-    x = tx0 + lx; y = ty0 + ly;
-    inside = x < R.width && y < R.height;
-    out_index = R.shard_count > 1 ? ((size_t)st * R.tile_h + ly) * R.tile_w + lx : (size_t)y * R.width + x;
+    subtile_to_pixel(R, st, gtx, gty, sx, sy, lane, x, y, inside, out_index);
+}
+
+// One finished pixel: the float radiance and its tonemapped bytes (sceneio.cpp:393-395), whichever buffers the caller asked for; and the black
+// pixel that pads a border tile in the compact shard layout.  `lit` = false is the black pixel: the bytes are then 0 and the caller passes px = 0 too,
+// since the floats are always written from px.  The shell stores both kinds through this one block (a branch per kind cost hw2-hw4 up to 21 more SGPR spills).
+RT_DEV void store_pixel(const RenderView &R, size_t out_index, F3 px, bool lit = true) {
+    if (R.out_rgb) { R.out_rgb[3 * out_index] = px.x; R.out_rgb[3 * out_index + 1] = px.y; R.out_rgb[3 * out_index + 2] = px.z; }
+    if (R.out_rgb8) {
+        R.out_rgb8[3 * out_index] = lit ? tonemap1(px.x) : 0;
+        R.out_rgb8[3 * out_index + 1] = lit ? tonemap1(px.y) : 0;
+        R.out_rgb8[3 * out_index + 2] = lit ? tonemap1(px.z) : 0;
+    }
+}
+RT_DEV void store_pixel_zero(const RenderView &R, size_t out_index) { store_pixel(R, out_index, f3(0.f, 0.f, 0.f), false); }
+
+// The shell of the per-pixel kernels hw2-hw5 (the hw8 megakernel spells the same loop out, rt_kernels_hw8.h), one wave per block: waves are persistent and pull work items from a
+// global queue (the GPU form of `#pragma omp parallel for schedule(dynamic,8)`, hw8/src/sceneio.cpp:387).  A work item is one 8x8 sub-tile of
+// a shard tile (tile_w x tile_h, multiples of 8), one lane per pixel.  body(x, y) -> F3 runs for the pixels inside the image; the padding of a
+// border tile is written black in the compact shard layout and not at all in a whole frame.
+template <class BODY>
+RT_DEV void for_each_pixel(const RenderView &R, uint32_t n_work, const BODY &body) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const int sub_x = R.tile_w >> 3, sub_per_tile = sub_x * (R.tile_h >> 3);
+    for (;;) {
+        uint32_t w = 0;
+        if (lane == 0) w = atomicAdd(R.work_counter, 1u);
+        w = __shfl(w, 0);
+        if (w >= n_work) break;
+        uint32_t st = w / sub_per_tile, sub = w % sub_per_tile; // shard-local tile, 8x8 block inside it: plain divisions, w is wave-uniform
+        uint32_t gt = R.shard_count > 1 ? (uint32_t)R.shard_index + st * (uint32_t)R.shard_count : st;
+        int x, y; bool inside; size_t out_index;
+        subtile_to_pixel(R, st, gt % (uint32_t)R.tiles_x, gt / (uint32_t)R.tiles_x, sub % sub_x, sub / sub_x, lane, x, y, inside, out_index);
+        F3 px = f3(0.f, 0.f, 0.f);
+        if (inside) px = body(x, y);
+        if (inside || R.shard_count > 1) store_pixel(R, out_index, px, inside);
+    }
+}
+// The pixel's mean over R.samples camera samples: its own minstd_rand(y*W+x) (sceneio.cpp:389-391), two jitter draws per sample, then
+// sample(rng, fx, fy) -> F3 with the jittered pixel coordinates; scaled by the float 1/spp (scene.cpp:171-176).
+template <class SAMPLE>
+RT_DEV F3 average_samples(const RenderView &R, int x, int y, const SAMPLE &sample) {
+    Rng rng;
+    rng_seed(rng, (uint32_t)(y * R.width + x));
+    F3 color = f3(0.f, 0.f, 0.f);
+    for (int s = 0; s < R.samples; s++) {
+        float fx = (float)x + rng_u01(rng);
+        float fy = (float)y + rng_u01(rng);
+        color = color + sample(rng, fx, fy);
+    }
+    return R.inv_samples * color;
 }
 
 // Pixel slot of a shard -> pixel slot of the unsharded frame (its "frame order": the 8x8 sub-tiles of the image row-major, 64 slots each),

@@ -24,17 +24,7 @@ RT_DEV LightRegs load_light(const GpuLight *p) {
     return L;
 }
 
-// Scene::intersect (hw2/src/scene.cpp:8-28): first strictly-nearest figure with t <= tmax.
-RT_DEV int closest_prim2(const SceneViewTxt &S, F3 o, F3 d, float &bt, F3 &bn, bool &bin) {
-    int pos = -1;
-    for (uint32_t k = 0; k < S.n_prims; k++) {
-        PrimRegs P = load_prim(S.prims + k);
-        float t; F3 n; bool inside;
-        if (prim_hit<true>(P, o, d, t, n, inside) && t <= __builtin_inff() && (pos == -1 || t < bt)) { pos = (int)k; bt = t; bn = n; bin = inside; }
-    }
-    return pos;
-}
-// The same query used as a shadow test: only whether anything lies within tmax matters.
+// Scene::intersect (hw2/src/scene.cpp:8-28) used as a shadow test: only whether anything lies within tmax matters.
 RT_DEV bool occluded2(const SceneViewTxt &S, F3 o, F3 d, float tmax) {
     for (uint32_t k = 0; k < S.n_prims; k++) {
         PrimRegs P = load_prim(S.prims + k);
@@ -56,8 +46,8 @@ RT_DEV F3 trace_tree2(const SceneViewTxt &S, int ray_depth, F3 o, F3 d) {
         if (evaluating) {
             evaluating = false;
             if (fp >= ray_depth) { ret = f3(0.f, 0.f, 0.f); continue; }
-            float t = 0; F3 norma = f3(0.f, 0.f, 0.f); bool inside = false;
-            int pos = closest_prim2(S, o, d, t, norma, inside);
+            float t; F3 norma; bool inside;
+            int pos = closest_prim<true>(S, o, d, t, norma, inside);
             if (pos < 0) { ret = f3(S.bg); continue; }
             PrimRegs P = load_prim(S.prims + pos);
             if (P.kind == RT_MAT_DIFFUSE) {                              // :43-52
@@ -120,35 +110,11 @@ RT_DEV F3 trace_tree2(const SceneViewTxt &S, int ray_depth, F3 o, F3 d) {
 }
 
 __global__ __launch_bounds__(64) void render_hw2_kernel(SceneViewTxt S, RenderView R, float tan_fov_y, uint32_t n_work) {
-    const int lane = threadIdx.x & 63;
-    const int sub_x = R.tile_w >> 3, sub_per_tile = sub_x * (R.tile_h >> 3);
-    for (;;) {
-        uint32_t w = 0;
-        if (lane == 0) w = atomicAdd(R.work_counter, 1u);
-        w = __shfl(w, 0);
-        if (w >= n_work) break;
-        uint32_t st = w / sub_per_tile, sub = w % sub_per_tile;
-        uint32_t gt = R.shard_count > 1 ? (uint32_t)R.shard_index + st * (uint32_t)R.shard_count : st;
-        int tx0 = (int)(gt % (uint32_t)R.tiles_x) * R.tile_w, ty0 = (int)(gt / (uint32_t)R.tiles_x) * R.tile_h;
-        int lx = (int)(sub % sub_x) * 8 + (lane & 7), ly = (int)(sub / sub_x) * 8 + (lane >> 3);
-        int x = tx0 + lx, y = ty0 + ly;
-        bool inside = x < R.width && y < R.height;
-        size_t out_index = R.shard_count > 1 ? ((size_t)st * R.tile_h + ly) * R.tile_w + lx : (size_t)y * R.width + x;
-        F3 px = f3(0.f, 0.f, 0.f);
-        if (inside) {
-            F3 o, d;
-            camera_ray_txt(S, S.tan_fov_x_f, tan_fov_y, R.width, R.height, (float)x, (float)y, o, d); // hw2/src/scene.cpp:90-98
-            px = trace_tree2(S, R.ray_depth, o, d);
-        }
-        if (inside || R.shard_count > 1) {
-            if (R.out_rgb) { R.out_rgb[3 * out_index] = px.x; R.out_rgb[3 * out_index + 1] = px.y; R.out_rgb[3 * out_index + 2] = px.z; }
-            if (R.out_rgb8) {
-                R.out_rgb8[3 * out_index] = inside ? tonemap1(px.x) : 0;
-                R.out_rgb8[3 * out_index + 1] = inside ? tonemap1(px.y) : 0;
-                R.out_rgb8[3 * out_index + 2] = inside ? tonemap1(px.z) : 0;
-            }
-        }
-    }
+    for_each_pixel(R, n_work, [&](int x, int y) {
+        F3 o, d;
+        camera_ray_txt(S, S.tan_fov_x_f, tan_fov_y, R.width, R.height, (float)x, (float)y, o, d); // hw2/src/scene.cpp:90-98
+        return trace_tree2(S, R.ray_depth, o, d);
+    });
 }
 
 } // namespace dev

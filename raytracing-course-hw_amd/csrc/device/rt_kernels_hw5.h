@@ -151,13 +151,7 @@ RT_DEV float light_pdf_sum5(const SceneView5 &S, F3 x, F3 d, uint32_t *stack) {
 RT_DEV F3 mix_sample5(const SceneView5 &S, Rng &rng, F3 x, F3 n) {
     float comps = S.n_lights ? 2.f : 1.f;
     int distNum = (int)(rng_u01(rng) * comps);
-    if (distNum == 0) {
-        float a = rng_n01(rng), b = rng_n01(rng), c = rng_n01(rng);
-        F3 d = normalize(f3(a, b, c)) + n;
-        float l = len(d);
-        if (l <= 1e-9f || dot(d, n) <= 1e-9f || l != l) return n;
-        return (float)(1. / (double)l) * d;
-    }
+    if (distNum == 0) return cosine_sample_txt(rng, n);
     int li = (int)(rng_u01(rng) * (float)S.n_lights);
     FigRegs F = load_fig5(S.lights + li);
     if (F.P.type == RT_PRIM_TRIANGLE) {                                        // TriangleLight::sample :129-142
@@ -168,27 +162,11 @@ RT_DEV F3 mix_sample5(const SceneView5 &S, Rng &rng, F3 x, F3 n) {
         F3 point = F.P.position + qtransform(qconj(F.P.rot), a + u * b + v * c);
         return normalize(point - x);
     }
-    F3 dir = f3(0.f, 1.f, 0.f);
-    for (int attempt = 0; attempt < RT4_MAX_REJECTIONS; attempt++) {
-        F3 point;
-        if (F.P.type == RT_PRIM_BOX) {                                         // BoxLight::sample :84-105 (constructor arguments right to left)
-            float sx = F.P.data.x, sy = F.P.data.y, sz = F.P.data.z;
-            float wx = sy * sz, wy = sx * sz, wz = sx * sy;
-            float u = rng_u01(rng) * (wx + wy + wz);
-            float flip = (double)rng_u01(rng) > 0.5 ? 1.f : -1.f;
-            if (u < wx) { float c = (2 * rng_u01(rng) - 1) * sz; float b = (2 * rng_u01(rng) - 1) * sy; point = f3(flip * sx, b, c); }
-            else if (u < wx + wy) { float c = (2 * rng_u01(rng) - 1) * sz; float a = (2 * rng_u01(rng) - 1) * sx; point = f3(a, flip * sy, c); }
-            else { float b = (2 * rng_u01(rng) - 1) * sy; float a = (2 * rng_u01(rng) - 1) * sx; point = f3(a, b, flip * sz); }
-        } else {                                                               // EllipsoidLight::sample :160-171 (the pixel's shared n01)
-            float a = rng_n01(rng), b = rng_n01(rng), c = rng_n01(rng);
-            point = F.P.data * normalize(f3(a, b, c));
-        }
-        F3 actual = qtransform(qconj(F.P.rot), point) + F.P.position;
-        dir = normalize(actual - x);
-        float t; F3 nn; bool inside;
-        if (fig_hit5(F, x, dir, t, nn, inside)) break;
-    }
-    return dir;
+    return light_sample_reject(F.P, x, [&]() {                                 // BoxLight::sample :84-105, EllipsoidLight::sample :160-171 (the pixel's shared n01)
+        if (F.P.type == RT_PRIM_BOX) return box_face_point(rng, F.P.data);
+        float a = rng_n01(rng), b = rng_n01(rng), c = rng_n01(rng);
+        return F.P.data * normalize(f3(a, b, c));
+    }, [&](F3 dir) { float t; F3 nn; bool inside; return fig_hit5(F, x, dir, t, nn, inside); });
 }
 // Mix::pdf :292-302 with FiguresMix::pdf :211-213
 RT_DEV float mix_pdf5(const SceneView5 &S, F3 x, F3 n, F3 d, uint32_t *stack) {
@@ -199,110 +177,31 @@ RT_DEV float mix_pdf5(const SceneView5 &S, F3 x, F3 n, F3 d, uint32_t *stack) {
     return ans / 2.f;
 }
 
-// Scene::getColor, hw5/src/scene.cpp:47-103
-RT_DEV F3 trace_tree5(const SceneView5 &S, int ray_depth, Rng &rng, uint32_t *stack, F3 o, F3 d) {
-    Frame3 frames[RT4_MAX_DEPTH];
-    int fp = 0;
-    const float epsf = 9.99999974737875163555e-05f; // (float)eps, eps = 1e-4L (same float as (float)1e-4)
-    F3 ret = f3(0.f, 0.f, 0.f);
-    bool evaluating = true;
-    for (;;) {
-        if (evaluating) {
-            if (fp >= ray_depth) { ret = f3(0.f, 0.f, 0.f); evaluating = false; continue; }
-            Hit5 h = closest_hit5(S, o, d, stack);
-            if (h.idx < 0) { ret = f3(S.bg); evaluating = false; continue; }
-            FigRegs F = load_fig5(S.figs + h.idx);
-            F3 x = o + h.t * d;
-            if (F.P.kind == RT_MAT_DIFFUSE) {
-                F3 xs = x + epsf * h.n;
-                F3 w = mix_sample5(S, rng, xs, h.n);
-                if (dot(w, h.n) < 0) { ret = F.P.emission; evaluating = false; continue; }
-                float pdf = mix_pdf5(S, xs, h.n, w, stack);
-                Frame3 &f = frames[fp++];
-                f.kind = F3_MUL; f.emission = F.P.emission;
-                f.mult = (float)(1. / (double)(RT4_PI * pdf) * (double)dot(w, h.n)) * F.P.color;
-                o = x + epsf * w; d = w;
-                continue;
-            }
-            F3 dn = normalize(d);
-            F3 refl = dn - (float)(2. * (double)dot(h.n, dn)) * h.n;
-            Frame3 &f = frames[fp++];
-            f.emission = F.P.emission; f.mult = F.P.color; f.x = x; f.dn = dn; f.norma = h.n; f.inside = h.inside; f.ior = F.P.ior;
-            f.kind = F.P.kind == RT_MAT_METALLIC ? F3_MUL : F3_DIEL_REFLECT;
-            o = x + epsf * refl; d = refl;
-        } else {
-            if (fp == 0) break;
-            Frame3 &f = frames[--fp];
-            if (f.kind == F3_MUL) { ret = f.emission + f.mult * ret; continue; }
-            if (f.kind == F3_DIEL_REFRACT) {
-                F3 refracted = ret;
-                if (!f.inside) refracted = refracted * f.mult;
-                ret = f.emission + refracted;
-                continue;
-            }
-            float eta1 = 1.f, eta2 = f.ior;
-            if (f.inside) { float tmp = eta1; eta1 = eta2; eta2 = tmp; }
-            F3 l = neg(f.dn);
-            float nl = dot(f.norma, l);
-            float sinTheta2 = (float)((double)(eta1 / eta2) * sqrt((double)(1 - nl * nl)));
-            if (fabs((double)sinTheta2) > 1.) { ret = f.emission + ret; continue; }
-            float rr = (eta1 - eta2) / (eta1 + eta2);
-            float r0 = rr * rr;
-            double om = (double)(1 - nl), om2 = om * om;
-            float r = (float)((double)r0 + (double)(1 - r0) * (om2 * om2 * om));
-            if (rng_u01(rng) < r) { ret = f.emission + ret; continue; }
-            float cosTheta2 = sqrtf(1 - sinTheta2 * sinTheta2);
-            F3 refr = (eta1 / eta2) * neg(l) + (eta1 / eta2 * nl - cosTheta2) * f.norma;
-            f.kind = F3_DIEL_REFRACT;
-            fp++;
-            o = f.x + epsf * refr; d = refr;
-            evaluating = true;
-        }
+// Scene::getColor, hw5/src/scene.cpp:47-103: trace_tree over the planes and the BVH, with this snapshot's Mix
+struct TreePolicy5 {
+    const SceneView5 &S;
+    uint32_t *stack;
+    RT_DEV int closest(F3 o, F3 d, float &t, F3 &n, bool &inside) const {
+        Hit5 c = closest_hit5(S, o, d, stack);
+        t = c.t; n = c.n; inside = c.inside;
+        return c.idx;
     }
-    return ret;
-}
+    RT_DEV PrimRegs material(int idx) const { return load_fig5(S.figs + idx).P; }
+    RT_DEV bool diffuse(const Hit3 &h, F3 x, Rng &rng, Frame3 &f, F3 &o, F3 &d) const {
+        return mix_diffuse(h, x, f, o, d, [&](F3 xs, F3 n) { return mix_sample5(S, rng, xs, n); }, [&](F3 xs, F3 n, F3 w) { return mix_pdf5(S, xs, n, w, stack); });
+    }
+};
 
 __global__ __launch_bounds__(64) void render_hw5_kernel(SceneView5 S, RenderView R, float tan_fov_y, uint32_t n_work) {
-    const int lane = threadIdx.x & 63;
-    const int sub_x = R.tile_w >> 3, sub_per_tile = sub_x * (R.tile_h >> 3);
     uint32_t stack[RT5_STACK];
-    for (;;) {
-        uint32_t w = 0;
-        if (lane == 0) w = atomicAdd(R.work_counter, 1u);
-        w = __shfl(w, 0);
-        if (w >= n_work) break;
-        uint32_t st = w / sub_per_tile, sub = w % sub_per_tile;
-        uint32_t gt = R.shard_count > 1 ? (uint32_t)R.shard_index + st * (uint32_t)R.shard_count : st;
-        int tx0 = (int)(gt % (uint32_t)R.tiles_x) * R.tile_w, ty0 = (int)(gt / (uint32_t)R.tiles_x) * R.tile_h;
-        int lx = (int)(sub % sub_x) * 8 + (lane & 7), ly = (int)(sub / sub_x) * 8 + (lane >> 3);
-        int x = tx0 + lx, y = ty0 + ly;
-        bool inside = x < R.width && y < R.height;
-        size_t out_index = R.shard_count > 1 ? ((size_t)st * R.tile_h + ly) * R.tile_w + lx : (size_t)y * R.width + x;
-        F3 px = f3(0.f, 0.f, 0.f);
-        if (inside) {
-            Rng rng;
-            rng_seed(rng, (uint32_t)(y * R.width + x));                 // hw5/src/sceneio.cpp:110
-            F3 color = f3(0.f, 0.f, 0.f);
-            for (int s = 0; s < R.samples; s++) {                       // scene.cpp:105-126: all-float camera ray, no half-pixel offset
-                float fx = (float)x + rng_u01(rng);
-                float fy = (float)y + rng_u01(rng);
-                float nx = S.tan_fov_x * (2 * fx / (float)R.width - 1);
-                float ny = tan_fov_y * (2 * fy / (float)R.height - 1);
-                F3 o = f3(S.cam_pos);
-                F3 d = nx * f3(S.cam_right) - ny * f3(S.cam_up) + f3(S.cam_fwd);
-                color = color + trace_tree5(S, R.ray_depth, rng, stack, o, d);
-            }
-            px = R.inv_samples * color;
-        }
-        if (inside || R.shard_count > 1) {
-            if (R.out_rgb) { R.out_rgb[3 * out_index] = px.x; R.out_rgb[3 * out_index + 1] = px.y; R.out_rgb[3 * out_index + 2] = px.z; }
-            if (R.out_rgb8) {
-                R.out_rgb8[3 * out_index] = inside ? tonemap1(px.x) : 0;
-                R.out_rgb8[3 * out_index + 1] = inside ? tonemap1(px.y) : 0;
-                R.out_rgb8[3 * out_index + 2] = inside ? tonemap1(px.z) : 0;
-            }
-        }
-    }
+    for_each_pixel(R, n_work, [&](int x, int y) {
+        return average_samples(R, x, y, [&](Rng &rng, float fx, float fy) { // seed: hw5/src/sceneio.cpp:110
+            F3 o, d;
+            camera_ray_float(S, tan_fov_y, R.width, R.height, fx, fy, o, d);
+            TreePolicy5 policy{S, stack};
+            return trace_tree(policy, S.bg, R.ray_depth, rng, o, d);
+        });
+    });
 }
 
 } // namespace dev

@@ -426,10 +426,7 @@ __global__ __launch_bounds__(64, RT6_MIN_WAVES) void render_hw6_kernel(SceneView
                         color = f3(0.f, 0.f, 0.f); s = 0;
                         camera_ray();
                         have_pixel = true;
-                    } else if (R.shard_count > 1) {                                              // padding of a border tile in the compact shard layout
-                        if (R.out_rgb) { R.out_rgb[3 * out_index] = 0.f; R.out_rgb[3 * out_index + 1] = 0.f; R.out_rgb[3 * out_index + 2] = 0.f; }
-                        if (R.out_rgb8) { R.out_rgb8[3 * out_index] = 0; R.out_rgb8[3 * out_index + 1] = 0; R.out_rgb8[3 * out_index + 2] = 0; }
-                    }
+                    } else if (R.shard_count > 1) store_pixel_zero(R, out_index);                // padding of a border tile in the compact shard layout
                 }
             }
         }
@@ -438,9 +435,7 @@ __global__ __launch_bounds__(64, RT6_MIN_WAVES) void render_hw6_kernel(SceneView
             color = color + M.ret;                                                               // scene.cpp:113
             if (++s < R.samples) camera_ray();
             else {
-                F3 px = R.inv_samples * color;                                                   // scene.cpp:115
-                if (R.out_rgb) { R.out_rgb[3 * out_index] = px.x; R.out_rgb[3 * out_index + 1] = px.y; R.out_rgb[3 * out_index + 2] = px.z; }
-                if (R.out_rgb8) { R.out_rgb8[3 * out_index] = tonemap1(px.x); R.out_rgb8[3 * out_index + 1] = tonemap1(px.y); R.out_rgb8[3 * out_index + 2] = tonemap1(px.z); }
+                store_pixel(R, out_index, R.inv_samples * color);                                // scene.cpp:115
                 have_pixel = false;
             }
         }

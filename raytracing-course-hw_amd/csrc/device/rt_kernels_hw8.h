@@ -179,7 +179,9 @@ RT_DEV F3 trace_path(const SceneView &S, int ray_depth, Rng &rng, F3 o, F3 d, ui
 }
 
 // work item -> pixel.  Shard tiles are tile_w x tile_h (multiples of 8); a work item is one 8x8
-// sub-tile of a shard tile, one lane per pixel.
+// sub-tile of a shard tile, one lane per pixel.  This is for_each_pixel + average_samples of rt_device.h written out: the
+// counting instantiation loses a wave of occupancy (121 -> 129 or 130 VGPRs) in every form that shares the loop, with or
+// without a lambda (profiles/r14_pixel_shell.txt), so the megakernel keeps its own copy and shares only store_pixel.
 template <bool COUNT>
 __global__ __launch_bounds__(64) void render_hw8_kernel(SceneView S, RenderView R, uint32_t n_work) {
     uint32_t stack[RT_STACK_SIZE];
@@ -213,14 +215,7 @@ __global__ __launch_bounds__(64) void render_hw8_kernel(SceneView S, RenderView 
             }
             px = R.inv_samples * color;                                       // scene.cpp:176
         }
-        if (inside || R.shard_count > 1) {
-            if (R.out_rgb) { R.out_rgb[3 * out_index] = px.x; R.out_rgb[3 * out_index + 1] = px.y; R.out_rgb[3 * out_index + 2] = px.z; }
-            if (R.out_rgb8) {                                                 // sceneio.cpp:393-395
-                R.out_rgb8[3 * out_index] = inside ? tonemap1(px.x) : 0;
-                R.out_rgb8[3 * out_index + 1] = inside ? tonemap1(px.y) : 0;
-                R.out_rgb8[3 * out_index + 2] = inside ? tonemap1(px.z) : 0;
-            }
-        }
+        if (inside || R.shard_count > 1) store_pixel(R, out_index, px, inside);
     }
     if (COUNT && R.counters) {
         atomicAdd(&R.counters[CNT_CLOSEST], cnt.closest); atomicAdd(&R.counters[CNT_LIGHT], cnt.lightq);

@@ -101,7 +101,19 @@ RT_DEV bool prim_hit(const PrimRegs &P, F3 o, F3 d, float &t, F3 &norma, bool &i
     return true;
 }
 
-RT_DEV bool prim_hit3(const PrimRegs &P, F3 o, F3 d, float &t, F3 &norma, bool &inside) { return prim_hit<false>(P, o, d, t, norma, inside); }
+// Scene::intersect of hw2-hw4 (hw2/src/scene.cpp:8-28, hw3/src/scene.cpp:11-29): every figure of the flat list; strict '<' keeps the first of equals.
+// Returns its index (-1: none) and its t, normal and side.
+template <bool FLOAT_ROOTS, bool PLANE_TMAX = false>
+RT_DEV int closest_prim(const SceneViewTxt &S, F3 o, F3 d, float &bt, F3 &bn, bool &bin) {
+    int pos = -1;
+    bt = 0; bn = f3(0.f, 0.f, 0.f); bin = false;
+    for (uint32_t k = 0; k < S.n_prims; k++) {
+        PrimRegs P = load_prim(S.prims + k);
+        float t; F3 n; bool inside;
+        if (prim_hit<FLOAT_ROOTS, PLANE_TMAX>(P, o, d, t, n, inside) && t <= __builtin_inff() && (pos == -1 || t < bt)) { pos = (int)k; bt = t; bn = n; bin = inside; }
+    }
+    return pos;
+}
 
 // hw3/src/scene.cpp:99-107 (shared by hw1/src/scene.cpp:22-30): pixel centre +0.5 on top of the jitter, FOV_X based.
 RT_DEV void camera_ray_txt(const SceneViewTxt &S, float tan_fov_x, float tan_fov_y, int width, int height, float x, float y, F3 &o, F3 &d) {
@@ -145,11 +157,15 @@ __global__ __launch_bounds__(256) void render_hw1_kernel(SceneViewTxt S, int wid
     }
 }
 
-// ---- hw3 --------------------------------------------------------------------------------------------------------
+// ---- hw3 (Frame3 and RT3_EPS also serve trace_tree, the frame machine of hw4 and hw5 in rt_kernels_hw4.h) ------------------
 #define RT3_MAX_DEPTH 8
+#define RT3_EPS ((float)0.0001) // hw5's (float)eps with eps = 1e-4L is the same float
 enum { F3_MUL = 0, F3_DIEL_REFLECT = 1, F3_DIEL_REFRACT = 2 };
 struct Frame3 { F3 emission, mult, x, dn, norma; int kind; bool inside; float ior; };
 
+// Scene::getColor of hw3 (hw3/src/scene.cpp:31-87) as an explicit frame machine.  hw4 and hw5 run the same machine as policies of trace_tree
+// (rt_kernels_hw4.h); hw3 keeps this copy of its own: as a third policy (flat list, prim_hit<false>, uniform hemisphere, weight 2 cos) config 2 took 13.2 ms
+// against 11.9 ms with the same registers and fewer instructions, and the cause was not found (profiles/r14_pixel_shell.txt).
 RT_DEV F3 trace_tree3(const SceneViewTxt &S, int ray_depth, Rng &rng, F3 o, F3 d) {
     Frame3 frames[RT3_MAX_DEPTH];
     int fp = 0;
@@ -163,7 +179,7 @@ RT_DEV F3 trace_tree3(const SceneViewTxt &S, int ray_depth, Rng &rng, F3 o, F3 d
             for (uint32_t k = 0; k < S.n_prims; k++) {                  // hw3/src/scene.cpp:14-23: strict '<' keeps the first
                 PrimRegs P = load_prim(S.prims + k);
                 float t; F3 n; bool inside;
-                if (prim_hit3(P, o, d, t, n, inside) && t <= __builtin_inff() && (pos == -1 || t < bt)) { pos = (int)k; bt = t; bn = n; bin = inside; }
+                if (prim_hit<false>(P, o, d, t, n, inside) && t <= __builtin_inff() && (pos == -1 || t < bt)) { pos = (int)k; bt = t; bn = n; bin = inside; }
             }
             if (pos < 0) { ret = f3(S.bg); evaluating = false; continue; }
             PrimRegs P = load_prim(S.prims + pos);
@@ -220,43 +236,13 @@ RT_DEV F3 trace_tree3(const SceneViewTxt &S, int ray_depth, Rng &rng, F3 o, F3 d
 #define RT3_MIN_WAVES 4 // waves per SIMD the register allocation aims at; config 2: 1 -> 14.1 ms, 3 -> 14.3, 4 -> 11.9, 5 -> 12.0, 6 -> 12.2, 8 -> 17.6
 #endif
 __global__ __launch_bounds__(64, RT3_MIN_WAVES) void render_hw3_kernel(SceneViewTxt S, RenderView R, float tan_fov_y, uint32_t n_work) {
-    const int lane = threadIdx.x & 63;
-    const int sub_x = R.tile_w >> 3, sub_per_tile = sub_x * (R.tile_h >> 3);
-    for (;;) {
-        uint32_t w = 0;
-        if (lane == 0) w = atomicAdd(R.work_counter, 1u);
-        w = __shfl(w, 0);
-        if (w >= n_work) break;
-        uint32_t st = w / sub_per_tile, sub = w % sub_per_tile;
-        uint32_t gt = R.shard_count > 1 ? (uint32_t)R.shard_index + st * (uint32_t)R.shard_count : st;
-        int tx0 = (int)(gt % (uint32_t)R.tiles_x) * R.tile_w, ty0 = (int)(gt / (uint32_t)R.tiles_x) * R.tile_h;
-        int lx = (int)(sub % sub_x) * 8 + (lane & 7), ly = (int)(sub / sub_x) * 8 + (lane >> 3);
-        int x = tx0 + lx, y = ty0 + ly;
-        bool inside = x < R.width && y < R.height;
-        size_t out_index = R.shard_count > 1 ? ((size_t)st * R.tile_h + ly) * R.tile_w + lx : (size_t)y * R.width + x;
-        F3 px = f3(0.f, 0.f, 0.f);
-        if (inside) {
-            Rng rng;
-            rng_seed(rng, (uint32_t)(y * R.width + x));
-            F3 color = f3(0.f, 0.f, 0.f);
-            for (int s = 0; s < R.samples; s++) {                       // hw3/src/scene.cpp:89-97
-                float nx = (float)x + rng_u01(rng);
-                float ny = (float)y + rng_u01(rng);
-                F3 o, d;
-                camera_ray_txt(S, S.tan_fov_x, tan_fov_y, R.width, R.height, nx, ny, o, d);
-                color = color + trace_tree3(S, R.ray_depth, rng, o, d);
-            }
-            px = R.inv_samples * color;
-        }
-        if (inside || R.shard_count > 1) {
-            if (R.out_rgb) { R.out_rgb[3 * out_index] = px.x; R.out_rgb[3 * out_index + 1] = px.y; R.out_rgb[3 * out_index + 2] = px.z; }
-            if (R.out_rgb8) {
-                R.out_rgb8[3 * out_index] = inside ? tonemap1(px.x) : 0;
-                R.out_rgb8[3 * out_index + 1] = inside ? tonemap1(px.y) : 0;
-                R.out_rgb8[3 * out_index + 2] = inside ? tonemap1(px.z) : 0;
-            }
-        }
-    }
+    for_each_pixel(R, n_work, [&](int x, int y) {
+        return average_samples(R, x, y, [&](Rng &rng, float nx, float ny) {                   // hw3/src/scene.cpp:89-97
+            F3 o, d;
+            camera_ray_txt(S, S.tan_fov_x, tan_fov_y, R.width, R.height, nx, ny, o, d);
+            return trace_tree3(S, R.ray_depth, rng, o, d);
+        });
+    });
 }
 
 } // namespace dev

@@ -162,11 +162,7 @@ RT_DEV int wf_end_sample(const RenderView &R, float4 *r, uint32_t gslot, F3 L, R
         float *o = R.partial + 3 * (size_t)gslot;
         o[0] = accum.x; o[1] = accum.y; o[2] = accum.z;
     } else {
-        F3 px = R.inv_samples * accum;                               // scene.cpp:176
-        if (R.out_rgb) { R.out_rgb[3 * out_index] = px.x; R.out_rgb[3 * out_index + 1] = px.y; R.out_rgb[3 * out_index + 2] = px.z; }
-        if (R.out_rgb8) {                                            // sceneio.cpp:393-395
-            R.out_rgb8[3 * out_index] = tonemap1(px.x); R.out_rgb8[3 * out_index + 1] = tonemap1(px.y); R.out_rgb8[3 * out_index + 2] = tonemap1(px.z);
-        }
+        store_pixel(R, out_index, R.inv_samples * accum);            // scene.cpp:176
     }
     return 0;
 }
@@ -179,10 +175,7 @@ RT_DEV bool wf_seed_record(const RenderView &R, uint32_t gslot, bool fresh, int 
     bool inside; size_t out_index;
     wf_slot_to_pixel(R, gslot, x, y, inside, out_index);
     if (!inside) {
-        if (R.shard_count > 1 && (R.streams <= 1 || gslot < R.n_pixslots)) {
-            if (R.out_rgb) { R.out_rgb[3 * out_index] = 0.f; R.out_rgb[3 * out_index + 1] = 0.f; R.out_rgb[3 * out_index + 2] = 0.f; }
-            if (R.out_rgb8) { R.out_rgb8[3 * out_index] = 0; R.out_rgb8[3 * out_index + 1] = 0; R.out_rgb8[3 * out_index + 2] = 0; }
-        }
+        if (R.shard_count > 1 && (R.streams <= 1 || gslot < R.n_pixslots)) store_pixel_zero(R, out_index);
         return false;
     }
     if (fresh) {
@@ -829,9 +822,7 @@ __global__ __launch_bounds__(256) void wf_reduce_streams_kernel(RenderView R) {
             const float *q = R.partial + 3 * ((size_t)k * R.n_pixslots + p);
             sum = sum + f3(q[0], q[1], q[2]);
         }
-        F3 px = R.inv_samples * sum;
-        if (R.out_rgb) { R.out_rgb[3 * out_index] = px.x; R.out_rgb[3 * out_index + 1] = px.y; R.out_rgb[3 * out_index + 2] = px.z; }
-        if (R.out_rgb8) { R.out_rgb8[3 * out_index] = tonemap1(px.x); R.out_rgb8[3 * out_index + 1] = tonemap1(px.y); R.out_rgb8[3 * out_index + 2] = tonemap1(px.z); }
+        store_pixel(R, out_index, R.inv_samples * sum);
     }
 }
 
