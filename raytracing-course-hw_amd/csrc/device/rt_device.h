@@ -415,7 +415,7 @@ struct Counters { unsigned long long closest, lightq, nodes, tris; };
 
 // Closest hit with the reference's tie rule: smallest t, equal t -> lowest figure index
 // (bvh.h:111-142 visits figures in increasing index order and replaces only on strict '<').
-// STRIDE: distance in words between consecutive stack entries (1 = a private array; see ref_closest_hit, rt_exact.h)
+// STRIDE: distance in words between consecutive stack entries (1 = a private array; the persistent kernel's exact role interleaves its lanes' stacks in LDS)
 template <bool COUNT, int STRIDE = 1>
 RT_DEV HitRec closest_hit(const SceneView &S, F3 o, F3 d, uint32_t *stack, Counters &cnt) {
     HitRec best;
@@ -461,11 +461,7 @@ RT_DEV HitRec closest_hit(const SceneView &S, F3 o, F3 d, uint32_t *stack, Count
     return best;
 }
 
-// ---- light pdf: all-hits sum over the light BVH in the reference's association -------------------
-// FiguresMix::getTotalPdf (distributions.h:148-165) returns total(left) + total(right) recursively and
-// a sequential sum inside a leaf; float addition is not associative, so the same tree of additions
-// is replayed with an explicit frame stack: TODO(child) frames and ADD(partial) frames (tag bit in
-// `addmask`).  Misses contribute +0, which is the additive identity here (no term is -0).
+// ---- light pdf: one light's term of the all-hits sum (FiguresMix::getTotalPdf; the sum itself: light_pdf_sum, rt_kernels_hw8.h) ----
 RT_DEV float light_pdf_one(const LightRec *L, F3 x, F3 d, bool &last, bool geometric_normal = false) {
     TriIsect T = load_isect(&L->isect);
     last = T.pad != 0;
@@ -483,55 +479,6 @@ RT_DEV float light_pdf_one(const LightRec *L, F3 x, F3 d, bool &last, bool geome
     if (geometric_normal) { F3 n = f3(T.nx, T.ny, T.nz); sn = normalize(inside ? neg(n) : n); } // hw7: yn of the intersection
     F3 y = x + t * d;                          // distributions.h:144
     return point_prob * len2(x - y) / fabsf(dot(d, sn)); // :68-70 (pdfOne, shading normal in hw8)
-}
-
-template <bool COUNT, int STRIDE = 1>
-RT_DEV float light_pdf_sum(const SceneView &S, F3 x, F3 d, uint32_t *stack, Counters &cnt) {
-    if (COUNT) cnt.lightq++;
-    RayInv ray = make_ray_inv(x, d);
-    int sp = 0;
-    unsigned long long addmask = 0;
-    uint32_t cur = 0;
-    bool descending = true;
-    float v = 0.f;
-    for (;;) {
-        if (descending) {
-            if (cur & RT_LEAF_BIT) {
-                float result = 0.f;
-                if (cur != RT_EMPTY_LEAF) {
-                    uint32_t i = cur & ~RT_LEAF_BIT;
-                    for (;;) {
-                        bool last;
-                        if (COUNT) cnt.tris++;
-                        result += light_pdf_one(S.lights + i, x, d, last, S.hw7 != 0);
-                        if (last) break;
-                        i++;
-                    }
-                }
-                v = result;
-                descending = false;
-                continue;
-            }
-            const float4 *q = reinterpret_cast<const float4 *>(S.light_nodes + cur);
-            float4 lo0 = q[0], hi0 = q[1], lo1 = q[2], hi1 = q[3];
-            if (COUNT) cnt.nodes++;
-            float n0, n1;
-            bool h0 = slab_test(lo0, hi0, ray, RT_T_MAX, n0);
-            bool h1 = slab_test(lo1, hi1, ray, RT_T_MAX, n1);
-            uint32_t c0 = __float_as_uint(lo0.w), c1 = __float_as_uint(lo1.w);
-            if (h0 & h1) { addmask &= ~(1ull << sp); stack[STRIDE * sp++] = c1; cur = c0; }
-            else if (h0) cur = c0;
-            else if (h1) cur = c1;
-            else { v = 0.f; descending = false; }
-        } else {
-            if (sp == 0) break;
-            --sp;
-            uint32_t f = stack[STRIDE * sp];
-            if ((addmask >> sp) & 1ull) v = __uint_as_float(f) + v;       // left total + right total
-            else { addmask |= 1ull << sp; stack[STRIDE * sp++] = __float_as_uint(v); cur = f; descending = true; }
-        }
-    }
-    return v;
 }
 
 // ---- textures (scene.cpp:9-53) --------------------------------------------------------------------

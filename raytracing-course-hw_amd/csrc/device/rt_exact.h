@@ -27,98 +27,40 @@ namespace dev {
 #define WF_SAMPLE_MASK 0x01FFFFFFu    // 25 bits of sample index in the packed word
 #define WF_VERIFIED_BIT 0x80000000u   // packed word: the hit in q2 comes from the reference-exact walk
 
-// AABB::intersect -> intersectBoxAndRay(0.5 * (max - min), ray - 0.5 * (min + max), false), primitives.cpp:163-165,29-53.
-RT_DEV bool ref_box_test(F3 mn, F3 mx, F3 o, F3 d, float &t, bool &inside) {
-    const F3 s = 0.5f * (mx - mn);
-    const F3 oc = o - 0.5f * (mn + mx);
-    const F3 a = neg(s) - oc, b = s - oc;
-    const float a1x = a.x / d.x, a1y = a.y / d.y, a1z = a.z / d.z;
-    const float a2x = b.x / d.x, a2y = b.y / d.y, a2z = b.z / d.z;
-    const float t1x = smin(a1x, a2x), t2x = smax(a1x, a2x);
-    const float t1y = smin(a1y, a2y), t2y = smax(a1y, a2y);
-    const float t1z = smin(a1z, a2z), t2z = smax(a1z, a2z);
-    const float t1 = smax(smax(t1x, t1y), t1z);
-    const float t2 = smin(smin(t2x, t2y), t2z);
-    if (t1 > t2 || t2 < 0) return false;
-    if (t1 < 0) { inside = true; t = t2; }
-    else { inside = false; t = t1; }
-    return true;
-}
-
-struct RefNodeView { F3 mn, mx; uint32_t left, right, first, last; };
-RT_DEV RefNodeView load_ref_node(const GpuRefNode *p) {
-    const float4 *q = reinterpret_cast<const float4 *>(p);
-    const float4 a = q[0], b = q[1], c = q[2];
-    RefNodeView n;
-    n.mn = f3(a.x, a.y, a.z); n.left = __float_as_uint(a.w);
-    n.mx = f3(b.x, b.y, b.z); n.right = __float_as_uint(b.w);
-    n.first = __float_as_uint(c.x); n.last = __float_as_uint(c.y);
-    return n;
-}
-
-// BVH::intersect_ (bvh.h:111-142) as an iterative depth-first walk, left child first: the recursion's `curBest` is the running
-// best of all hits found so far, a leaf keeps its first triangle on equal t, and a later subtree replaces the best only when
-// strictly closer — so one running best with strict '<' reproduces the result.  `stack` holds up to RT_STACK_SIZE node indices.
-// STRIDE: distance in words between consecutive stack entries (1 = a private array; the persistent kernel keeps the stacks of its exact
-// role in LDS, interleaved over the lanes of the batch).
-template <int STRIDE = 1>
-RT_DEV void ref_closest_hit(const SceneView &S, F3 o, F3 d, uint32_t *stack, float &best_t, float &best_u, float &best_v, uint32_t &hit) {
+// BVH::intersect_ (bvh.h:111-142) over the reference's own tree: ref_left_first of rt_ref_walk.h with hw8's triangle test in the leaves.
+// `stack`: anything indexable that holds RT_STACK_SIZE node indices (a private array; the persistent kernel keeps the stacks of its exact
+// role in LDS, interleaved over the lanes of the batch: StridedStack).
+template <class A>
+RT_DEV void ref_closest_hit(const SceneView &S, F3 o, F3 d, A &&stack, float &best_t, float &best_u, float &best_v, uint32_t &hit) {
     best_t = RT_T_MAX; best_u = 0.f; best_v = 0.f; hit = WF_MISS;
     if (S.n_tris == 0) return;
-    int sp = 0;
-    uint32_t cur = 0;
-    for (;;) {
-        const RefNodeView n = load_ref_node(S.ref_nodes + cur);
-        float tb; bool inside;
-        if (ref_box_test(n.mn, n.mx, o, d, tb, inside) && !(hit != WF_MISS && best_t < tb && !inside)) {
-            if (n.left == 0) {
-                for (uint32_t i = n.first; i < n.last; i++) {
-                    const TriIsect T = load_isect(S.tri_isect + i);
-                    float t, u, v; bool in;
-                    if (tri_test(T, o, d, t, u, v, in) && (hit == WF_MISS || t < best_t)) {
-                        best_t = t; best_u = u; best_v = v; hit = i | (in ? WF_INSIDE_BIT : 0u);
-                    }
-                }
-            } else if (sp < RT_STACK_SIZE) { stack[STRIDE * sp++] = n.right; cur = n.left; continue; }
+    RefBest best = {false, RT_T_MAX};
+    ref_left_first<RT_STACK_SIZE>(S.ref_nodes, o, d, stack, best, [&](uint32_t first, uint32_t last) {
+        for (uint32_t i = first; i < last; i++) {
+            const TriIsect T = load_isect(S.tri_isect + i);
+            float t, u, v; bool in;
+            if (tri_test(T, o, d, t, u, v, in) && (!best.have || t < best.t)) {
+                best.have = true; best.t = t; best_u = u; best_v = v; hit = i | (in ? WF_INSIDE_BIT : 0u);
+            }
         }
-        if (sp == 0) break;
-        cur = stack[STRIDE * --sp];
-    }
+    });
+    best_t = best.t;
 }
 
 // FiguresMix::getTotalPdf (distributions.h:148-165) over the reference light tree with the reference's box test and its
-// association of the additions (TODO / ADD frames as in light_pdf_sum, rt_device.h).
-template <int STRIDE = 1>
-RT_DEV float ref_light_pdf_sum(const SceneView &S, F3 x, F3 d, uint32_t *stack) {
-    int sp = 0;
-    unsigned long long addmask = 0;
-    uint32_t cur = 0;
-    bool descending = true;
-    float v = 0.f;
-    for (;;) {
-        if (descending) {
-            const RefNodeView n = load_ref_node(S.ref_light_nodes + cur);
-            float tb; bool inside;
-            if (!ref_box_test(n.mn, n.mx, x, d, tb, inside)) { v = 0.f; descending = false; }
-            else if (n.left == 0) {
-                float result = 0.f;
-                for (uint32_t i = n.first; i < n.last; i++) {
-                    bool last;
-                    result += light_pdf_one(S.lights + i, x, d, last, S.hw7 != 0);
-                }
-                v = result;
-                descending = false;
-            } else if (sp < RT_STACK_SIZE) { addmask &= ~(1ull << sp); stack[STRIDE * sp++] = n.right; cur = n.left; }
-            else { v = 0.f; descending = false; } // deeper than the host admits (checked there)
-        } else {
-            if (sp == 0) break;
-            --sp;
-            const uint32_t f = stack[STRIDE * sp];
-            if ((addmask >> sp) & 1ull) v = __uint_as_float(f) + v;                  // left total + right total
-            else { addmask |= 1ull << sp; stack[STRIDE * sp++] = __float_as_uint(v); cur = f; descending = true; }
-        }
-    }
-    return v;
+// association of the additions (frame_sum of rt_ref_walk.h over the reference's nodes).
+template <class A>
+RT_DEV float ref_light_pdf_sum(const SceneView &S, F3 x, F3 d, A &&stack) {
+    return frame_sum<RT_STACK_SIZE>(stack, [&](uint32_t cur, uint32_t &l, uint32_t &r, float &v) {
+        return ref_node(S.ref_light_nodes, x, d, cur, l, r, v, [&](uint32_t first, uint32_t last) {
+            float result = 0.f;
+            for (uint32_t i = first; i < last; i++) {
+                bool last_one;
+                result += light_pdf_one(S.lights + i, x, d, last_one, S.hw7 != 0);
+            }
+            return result;
+        });
+    });
 }
 
 // The gate's own arithmetic is not replay arithmetic: it only has to err on the cautious side, and its thresholds carry 4x the rounding

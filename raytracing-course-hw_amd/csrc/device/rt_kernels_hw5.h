@@ -10,7 +10,7 @@
 #pragma once
 #include "rt_types_hw5.h"
 #include "rt_kernels_hw4.h"
-#include "rt_exact.h"
+#include "rt_ref_walk.h"
 
 namespace rtamd {
 namespace dev {
@@ -63,7 +63,7 @@ RT_DEV Hit5 closest_hit5(const SceneView5 &S, F3 o, F3 d, uint32_t *stack) {
     }
     if (S.n_nonplanes == 0) return best;
     // BVH::intersect_ (bvh.h:111-141) with the reference's own box test on its unpadded boxes (AABB::intersect, primitives.cpp:221-223 ->
-    // intersectBoxAndRay, :92-116: ref_box_test of rt_exact.h is the same code), as an iterative left-first walk.  The recursion's
+    // intersectBoxAndRay, :92-116: ref_box_test of rt_ref_walk.h is the same code), as an iterative left-first walk.  The recursion's
     // `curBest` at a node is the smallest t of the plane hit and of everything found before the node in this order (every level hands
     // its left result on to its right child), so one running value prunes (`curBest < t_box && !inside`); the result is the first
     // figure with the smallest t (a leaf and a parent both replace on strict '<' only), and it replaces the plane hit when strictly nearer.
@@ -112,39 +112,19 @@ RT_DEV float light_pdf_one5(const FigRegs &F, F3 x, F3 d) {
     F3 y2 = x + (float)((double)t1 + 1e-4 + (double)t2) * d;
     return ans + pdf_one5(F, x, d, y2, n2);
 }
-// FiguresMix::getTotalPdf, distributions.h:256-274: total(left) + total(right), sequential sum inside a leaf — the same
-// tree of float additions replayed with TODO(child) / ADD(partial) frames (see light_pdf_sum in rt_device.h).
+// FiguresMix::getTotalPdf, distributions.h:256-274: total(left) + total(right), sequential sum inside a leaf, the reference's own box
+// test at every node — frame_sum of rt_ref_walk.h over the reference's nodes.
 RT_DEV float light_pdf_sum5(const SceneView5 &S, F3 x, F3 d, uint32_t *stack) {
-    // the reference's own box test at every node (distributions.h:256-262): a failed box contributes 0 whatever lies below it
-    int sp = 0;
-    unsigned long long addmask = 0;
-    uint32_t cur = 0;
-    bool descending = true;
-    float v = 0.f;
-    for (;;) {
-        if (descending) {
-            const RefNodeView n = load_ref_node(S.ref_light_nodes + cur);
-            float tb; bool inside_box;
-            if (!ref_box_test(n.mn, n.mx, x, d, tb, inside_box)) { v = 0.f; descending = false; }
-            else if (n.left == 0) {
-                float result = 0.f;
-                for (uint32_t i = n.first; i < n.last; i++) {
-                    FigRegs F = load_fig5(S.lights + i);
-                    result += light_pdf_one5(F, x, d);
-                }
-                v = result;
-                descending = false;
-            } else if (sp < RT5_STACK) { addmask &= ~(1ull << sp); stack[sp++] = n.right; cur = n.left; }
-            else { v = 0.f; descending = false; } // deeper than the host admits (checked there)
-        } else {
-            if (sp == 0) break;
-            --sp;
-            uint32_t f = stack[sp];
-            if ((addmask >> sp) & 1ull) v = __uint_as_float(f) + v;
-            else { addmask |= 1ull << sp; stack[sp++] = __float_as_uint(v); cur = f; descending = true; }
-        }
-    }
-    return v;
+    return frame_sum<RT5_STACK>(stack, [&](uint32_t cur, uint32_t &l, uint32_t &r, float &v) {
+        return ref_node(S.ref_light_nodes, x, d, cur, l, r, v, [&](uint32_t first, uint32_t last) {
+            float result = 0.f;
+            for (uint32_t i = first; i < last; i++) {
+                FigRegs F = load_fig5(S.lights + i);
+                result += light_pdf_one5(F, x, d);
+            }
+            return result;
+        });
+    });
 }
 
 // Mix::sample (distributions.h:283-290) -> Cosine::sample (:43-53) or FiguresMix::sample (:200-209) -> one light's sample

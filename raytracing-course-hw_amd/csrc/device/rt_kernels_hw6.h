@@ -8,7 +8,7 @@
 // degenerates the tree); figures keep their index in the reference's order for the tie rule, the light BVH
 // keeps the reference's topology because its shape fixes the order of the float additions.
 #pragma once
-#include "rt_device.h"
+#include "rt_ref_walk.h"
 #include "rt_types_hw6.h"
 
 namespace rtamd {
@@ -116,63 +116,40 @@ RT_DEV Hit6 closest_hit6(const SceneView6 &S, F3 o, F3 d, uint32_t *stack) {
     return best;
 }
 
-// FiguresMix::getTotalPdf for triangle lights (hw6/src/include/distributions.h:212-256), reference addition tree.
+// One light's term of FiguresMix::getTotalPdf: pdfOne of a triangle light the ray hits (distributions.h:116-118), 0 on a miss.
+RT_DEV float light_term6_at(const Tri6Regs &T, F3 x, F3 d, float t, bool inside) { // the hit (t, inside) is known
+    F3 yn = normalize(inside ? neg(T.n) : T.n);                // primitives.cpp:31
+    F3 y = x + t * d;
+    return T.point_prob * len2(x - y) / fabsf(dot(d, yn));
+}
+RT_DEV bool light_term6(const Tri6Regs &T, F3 x, F3 d, float &term) {
+    float t; bool inside;
+    term = 0.f;
+    if (!tri6_test(T, x, d, t, inside)) return false;
+    term = light_term6_at(T, x, d, t, inside);
+    return true;
+}
+
+// FiguresMix::getTotalPdf for triangle lights (hw6/src/include/distributions.h:212-256), reference addition tree: frame_sum of
+// rt_ref_walk.h over the two-box nodes.
 // `stack`: anything indexable that holds RT6_STACK_SIZE words (a private array here; a strided slice of LDS in rt_persistent_hw6.h).
 template <class A>
-RT_DEV float light_pdf_sum6(const SceneView6 &S, F3 x, F3 d, A stack) {
-    RayInv ray = make_ray_inv(x, d);
-    int sp = 0;
-    unsigned long long mask_lo = 0, mask_hi = 0; // frame kind per stack slot: 1 = ADD(partial sum), 0 = TODO(child)
-    uint32_t cur = 0;
-    bool descending = true;
-    float v = 0.f;
-    for (;;) {
-        if (descending) {
-            if (cur & RT_LEAF_BIT) {
-                float result = 0.f;
-                if (cur != RT_EMPTY_LEAF) {
-                    uint32_t i = cur & ~RT_LEAF_BIT;
-                    for (;;) {
-                        Tri6Regs T = load_tri6(S.lights + i);
-                        float t; bool inside; float term = 0.f;
-                        if (tri6_test(T, x, d, t, inside)) {
-                            F3 yn = normalize(inside ? neg(T.n) : T.n);            // primitives.cpp:31
-                            F3 y = x + t * d;
-                            term = T.point_prob * len2(x - y) / fabsf(dot(d, yn)); // distributions.h:116-118
-                        }
-                        result += term;
-                        if (T.last) break;
-                        i++;
-                    }
-                }
-                v = result; descending = false; continue;
+RT_DEV float light_pdf_sum6(const SceneView6 &S, F3 x, F3 d, A &&stack) {
+    const RayInv ray = make_ray_inv(x, d);
+    return frame_sum<RT6_STACK_SIZE>(stack, [&](uint32_t cur, uint32_t &l, uint32_t &r, float &v) {
+        return two_box_node(S.light_nodes, ray, cur, l, r, v, [&](uint32_t i) {
+            float result = 0.f;
+            for (;;) {
+                Tri6Regs T = load_tri6(S.lights + i);
+                float term;
+                light_term6(T, x, d, term);
+                result += term;
+                if (T.last) break;
+                i++;
             }
-            const float4 *q = reinterpret_cast<const float4 *>(S.light_nodes + cur);
-            float4 lo0 = q[0], hi0 = q[1], lo1 = q[2], hi1 = q[3];
-            float n0, n1;
-            bool h0 = slab_test(lo0, hi0, ray, RT_T_MAX, n0);
-            bool h1 = slab_test(lo1, hi1, ray, RT_T_MAX, n1);
-            uint32_t c0 = __float_as_uint(lo0.w), c1 = __float_as_uint(lo1.w);
-            if (h0 & h1) {
-                if (sp < 64) mask_lo &= ~(1ull << sp); else mask_hi &= ~(1ull << (sp - 64));
-                stack[sp++] = c1; cur = c0;
-            }
-            else if (h0) cur = c0;
-            else if (h1) cur = c1;
-            else { v = 0.f; descending = false; }
-        } else {
-            if (sp == 0) break;
-            --sp;
-            uint32_t f = stack[sp];
-            bool is_add = sp < 64 ? ((mask_lo >> sp) & 1ull) != 0 : ((mask_hi >> (sp - 64)) & 1ull) != 0;
-            if (is_add) v = __uint_as_float(f) + v;
-            else {
-                if (sp < 64) mask_lo |= 1ull << sp; else mask_hi |= 1ull << (sp - 64);
-                stack[sp++] = __float_as_uint(v); cur = f; descending = true;
-            }
-        }
-    }
-    return v;
+            return result;
+        });
+    });
 }
 
 // The same sum without the reference tree's boxes.  The reference's light tree (constant sort key) costs thousands of box
@@ -251,13 +228,11 @@ RT_DEV float light_pdf_sum6_fast(const SceneView6 &S, F3 x, F3 d, uint32_t *stac
                 uint32_t i = cur & ~RT_LEAF_BIT;
                 for (;;) {
                     Tri6Regs T = load_tri6(S.fast_lights + i);
-                    float t; bool inside;
-                    if (tri6_test(T, x, d, t, inside)) {
+                    float term;
+                    if (light_term6(T, x, d, term)) {
                         if (k == RT6_MAX_LIGHT_HITS) { too_many = true; break; }
-                        F3 yn = normalize(inside ? neg(T.n) : T.n);                  // primitives.cpp:31
-                        F3 y = x + t * d;
                         hit_idx[k] = T.ref_index;
-                        hit_term[k] = T.point_prob * len2(x - y) / fabsf(dot(d, yn)); // distributions.h:116-118
+                        hit_term[k] = term;
                         k++;
                     }
                     if (T.last) break;

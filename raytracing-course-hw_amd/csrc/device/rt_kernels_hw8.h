@@ -4,7 +4,7 @@
 // tiles from a global queue (the GPU form of `#pragma omp parallel for schedule(dynamic,8)`,
 // hw8/src/sceneio.cpp:387).
 #pragma once
-#include "rt_device.h"
+#include "rt_ref_walk.h"
 
 namespace rtamd {
 namespace dev {
@@ -132,6 +132,28 @@ RT_DEV F3 miss_color(const SceneView &S, F3 d) { // scene.cpp:90-97
     float tx, ty;
     env_uv(d, tx, ty);
     return sample_texture(S, S.env_image, tx, ty, true);
+}
+
+// FiguresMix::getTotalPdf (distributions.h:148-165): the all-hits sum over the light tree in the reference's association of the additions
+// (frame_sum of rt_ref_walk.h over the two-box nodes).  `stack`: anything indexable that holds RT_STACK_SIZE words.
+template <bool COUNT, class A>
+RT_DEV float light_pdf_sum(const SceneView &S, F3 x, F3 d, A &&stack, Counters &cnt) {
+    if (COUNT) cnt.lightq++;
+    const RayInv ray = make_ray_inv(x, d);
+    return frame_sum<RT_STACK_SIZE>(stack, [&](uint32_t cur, uint32_t &l, uint32_t &r, float &v) {
+        if (COUNT && !(cur & RT_LEAF_BIT)) cnt.nodes++;
+        return two_box_node(S.light_nodes, ray, cur, l, r, v, [&](uint32_t i) {
+            float result = 0.f;
+            for (;;) {
+                bool last;
+                if (COUNT) cnt.tris++;
+                result += light_pdf_one(S.lights + i, x, d, last, S.hw7 != 0);
+                if (last) break;
+                i++;
+            }
+            return result;
+        });
+    });
 }
 
 // One camera sample: Scene::getColor unrolled into a loop; the nested e + m*(inner) of

@@ -714,7 +714,7 @@ RT_DEV int pt_shade_lean(const SceneView &S, const RenderView &R, const WfView &
 template <class SH>
 RT_DEV void pt_exact_batch(const SceneView &S, const WfView &W, SH &sh, PtWave &wv, uint32_t *area, uint32_t &n_xlight, uint32_t &n_xtrace) {
     const uint32_t lane = threadIdx.x & 63u;
-    uint32_t *xstack = area + (lane & (PT_EXACT_BATCH - 1u));
+    const StridedStack<PT_EXACT_BATCH> xview = {area + (lane & (PT_EXACT_BATCH - 1u))};
     uint32_t got = pt_pop(sh.need[PT_Q_XLIGHT], &sh.cnt[PT_Q_XLIGHT], wv.nw, wv.cur[PT_Q_XLIGHT], lane < PT_EXACT_BATCH);
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
     if (got != PT_NONE) {
@@ -723,11 +723,9 @@ RT_DEV void pt_exact_batch(const SceneView &S, const WfView &W, SH &sh, PtWave &
         float4 q0 = r[0], q1 = r[1];
         const F3 x = f3(q0.x, q0.y, q0.z), d = f3(q0.w, q1.x, q1.y);
         float v;
-        if (S.exact_boxes) v = ref_light_pdf_sum<PT_EXACT_BATCH>(S, x, d, xstack);
-        else { Counters c; c.closest = c.lightq = c.nodes = c.tris = 0; v = light_pdf_sum<false, PT_EXACT_BATCH>(S, x, d, xstack, c); }
-        int depth = (int)(__float_as_uint(r[3].w) & 15u);
-        float *pdf = reinterpret_cast<float *>(wf_entry(W, slot, depth)) + 3;
-        *pdf = *pdf + v / S.n_lights_f;
+        if (S.exact_boxes) v = ref_light_pdf_sum(S, x, d, xview);
+        else { Counters c; c.closest = c.lightq = c.nodes = c.tris = 0; v = light_pdf_sum<false>(S, x, d, xview, c); }
+        wf_add_light_pdf(S, W, slot, v);
     }
     n_xlight += __popcll(pt_ballot(got != PT_NONE));
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
@@ -739,10 +737,10 @@ RT_DEV void pt_exact_batch(const SceneView &S, const WfView &W, SH &sh, PtWave &
         float4 *r = wf_rec(W, slot);
         float4 q0 = r[0], q1 = r[1];
         float bt, bu, bv; uint32_t hit;
-        if (S.exact_boxes == 1u) ref_closest_hit<PT_EXACT_BATCH>(S, f3(q0.x, q0.y, q0.z), f3(q0.w, q1.x, q1.y), xstack, bt, bu, bv, hit);
+        if (S.exact_boxes == 1u) ref_closest_hit(S, f3(q0.x, q0.y, q0.z), f3(q0.w, q1.x, q1.y), xview, bt, bu, bv, hit);
         else { // no reference boxes to be exact about (a walk that ran out of stack): the padded float boxes of the two-box tree decide, as for every other hit
             Counters c; c.closest = c.lightq = c.nodes = c.tris = 0;
-            const HitRec h = closest_hit<false, PT_EXACT_BATCH>(S, f3(q0.x, q0.y, q0.z), f3(q0.w, q1.x, q1.y), xstack, c);
+            const HitRec h = closest_hit<false, PT_EXACT_BATCH>(S, f3(q0.x, q0.y, q0.z), f3(q0.w, q1.x, q1.y), xview.p, c);
             bt = h.t; bu = h.u; bv = h.v; hit = h.idx < 0 ? WF_MISS : ((uint32_t)h.idx | (h.inside ? WF_INSIDE_BIT : 0u));
         }
         r[2] = make_float4(bt, bu, bv, __uint_as_float(hit));

@@ -344,9 +344,8 @@ struct P6LightWalk {
     RT_DEV void take(Leaf &lf) { // the held hit's pdf term, robustness test and bookkeeping
         const Tri6Regs T = load_tri6(S.fast_lights + lf.h_i);
         const float t = lf.h_t; const bool inside = lf.h_in;
-        F3 yn = normalize(inside ? neg(T.n) : T.n);                          // primitives.cpp:31
-        F3 y = o + t * d;
-        const float term = T.point_prob * len2(o - y) / fabsf(dot(d, yn));    // distributions.h:116-118
+        const F3 y = o + t * d;
+        const float term = light_term6_at(T, o, d, t, inside);
         if (S.exact_boxes) { // is every box of the reference's light tree above this hit passed whatever the rounding? (rt_exact.h)
             const F3 pb = T.a + T.b, pc = T.a + T.c;
             const F3 blo = f3(fminf(T.a.x, fminf(pb.x, pc.x)), fminf(T.a.y, fminf(pb.y, pc.y)), fminf(T.a.z, fminf(pb.z, pc.z)));
@@ -475,29 +474,21 @@ RT_DEV float p6_merge_hits(const SceneView6 &S, const float2 *h, int k, uint32_t
     return p6_merge_hits_in(S, h, k, vals, ids);
 }
 
-// ---- exact role: BVH::intersect_ of hw6 (bvh.h, identical to hw8's) over the reference's own tree with the reference's box test, as an
-// iterative depth-first walk, left child first, one running best with strict '<' (ref_closest_hit of rt_exact.h with hw6's figures) ----
+// ---- exact role: BVH::intersect_ of hw6 (bvh.h, identical to hw8's) over the reference's own tree with the reference's box test:
+// ref_left_first of rt_ref_walk.h with hw6's figures in the leaves ----
 template <class A>
 RT_DEV void ref_closest_hit6(const SceneView6 &S, F3 o, F3 d, A stack, float &best_t, bool &best_inside, uint32_t &hit) {
     best_t = RT_T_MAX; best_inside = false; hit = 0xFFFFFFFFu;
     if (S.n_tris == 0) return;
-    int sp = 0;
-    uint32_t cur = 0;
-    for (;;) {
-        const RefNodeView n = load_ref_node(S.ref_nodes + cur);
-        float tb; bool inside;
-        if (ref_box_test(n.mn, n.mx, o, d, tb, inside) && !(hit != 0xFFFFFFFFu && best_t < tb && !inside)) {
-            if (n.left == 0) {
-                for (uint32_t i = n.first; i < n.last; i++) {
-                    const Tri6Regs T = load_tri6(S.ref_tris + i);
-                    float t; bool in;
-                    if (tri6_test(T, o, d, t, in) && (hit == 0xFFFFFFFFu || t < best_t)) { best_t = t; best_inside = in; hit = i; }
-                }
-            } else if (sp < RT6_STACK_SIZE) { stack[sp++] = n.right; cur = n.left; continue; }
+    RefBest best = {false, RT_T_MAX};
+    ref_left_first<RT6_STACK_SIZE>(S.ref_nodes, o, d, stack, best, [&](uint32_t first, uint32_t last) {
+        for (uint32_t i = first; i < last; i++) {
+            const Tri6Regs T = load_tri6(S.ref_tris + i);
+            float t; bool in;
+            if (tri6_test(T, o, d, t, in) && (!best.have || t < best.t)) { best.have = true; best.t = t; best_inside = in; hit = i; }
         }
-        if (sp == 0) break;
-        cur = stack[--sp];
-    }
+    });
+    best_t = best.t;
 }
 
 // The reference's trees are degenerate here (built on a constant sort key: 59 and 85 levels, tens of thousands of box tests per query),
@@ -619,51 +610,22 @@ RT_DEV float ref_light_pdf_sum6_along(const SceneView6 &S, F3 x, F3 d, A hit_idx
 }
 
 // FiguresMix::getTotalPdf of hw6 (distributions.h:212-256) over the reference's own light tree with the reference's box test and its
-// association of the additions (ref_light_pdf_sum of rt_exact.h with hw6's term).  The tree is degenerate (85 levels on practice6_2):
+// association of the additions: frame_sum of rt_ref_walk.h over the reference's nodes.  The tree is degenerate (85 levels on practice6_2):
 // thousands of box tests per query, which is why only light sums with a hit at a box boundary come here.
 template <class A>
 RT_DEV float ref_light_pdf_sum6(const SceneView6 &S, F3 x, F3 d, A stack) {
-    int sp = 0;
-    unsigned long long mask_lo = 0, mask_hi = 0;
-    uint32_t cur = 0;
-    bool descending = true;
-    float v = 0.f;
     if (S.n_lights == 0) return 0.f;
-    for (;;) {
-        if (descending) {
-            const RefNodeView n = load_ref_node(S.ref_light_nodes + cur);
-            float tb; bool inside;
-            if (!ref_box_test(n.mn, n.mx, x, d, tb, inside)) { v = 0.f; descending = false; }
-            else if (n.left == 0) {
-                float result = 0.f;
-                for (uint32_t i = n.first; i < n.last; i++) {
-                    const Tri6Regs T = load_tri6(S.lights + i);
-                    float t; bool in; float term = 0.f;
-                    if (tri6_test(T, x, d, t, in)) {
-                        const F3 yn = normalize(in ? neg(T.n) : T.n);
-                        const F3 y = x + t * d;
-                        term = T.point_prob * len2(x - y) / fabsf(dot(d, yn));
-                    }
-                    result += term;
-                }
-                v = result; descending = false;
-            } else if (sp < RT6_STACK_SIZE) {
-                if (sp < 64) mask_lo &= ~(1ull << sp); else mask_hi &= ~(1ull << (sp - 64));
-                stack[sp++] = n.right; cur = n.left;
-            } else { v = 0.f; descending = false; }
-        } else {
-            if (sp == 0) break;
-            --sp;
-            const uint32_t f = stack[sp];
-            const bool is_add = sp < 64 ? ((mask_lo >> sp) & 1ull) != 0 : ((mask_hi >> (sp - 64)) & 1ull) != 0;
-            if (is_add) v = __uint_as_float(f) + v;
-            else {
-                if (sp < 64) mask_lo |= 1ull << sp; else mask_hi |= 1ull << (sp - 64);
-                stack[sp++] = __float_as_uint(v); cur = f; descending = true;
+    return frame_sum<RT6_STACK_SIZE>(stack, [&](uint32_t cur, uint32_t &l, uint32_t &r, float &v) {
+        return ref_node(S.ref_light_nodes, x, d, cur, l, r, v, [&](uint32_t first, uint32_t last) {
+            float result = 0.f;
+            for (uint32_t i = first; i < last; i++) {
+                float term;
+                light_term6(load_tri6(S.lights + i), x, d, term);
+                result += term;
             }
-        }
-    }
-    return v;
+            return result;
+        });
+    });
 }
 
 // ---- the rare roles, P6_XBATCH queries at a time, work arrays in the wave's LDS stack area (P6Slice) ----------------------------------

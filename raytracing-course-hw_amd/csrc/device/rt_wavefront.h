@@ -477,6 +477,7 @@ RT_DEV void wf_add_light_pdf(const SceneView &S, const WfView &W, uint32_t slot,
 // The walk of the SPILL variant (trees deeper than WF_STACK), so its stack always spills.  A lane descends to a leaf, then returns: the
 // stack holds the right child of a node whose left side is being summed, then (addmask) the left side's total while the right side is.
 // n_nodes counts the descending steps only; the leaf phase never ends the walk, a return step at an empty stack does.
+// The frames are FrameWalk's (rt_ref_walk.h) written out: on the machine's two moves the spill variant was 1.4 % slower (profiles/r15_ref_walk.txt).
 struct WfLightFrameWalk : WfWalkRay {
     static constexpr int HIST = -1;
     static constexpr bool WAVE_STATS = false;
@@ -532,7 +533,7 @@ struct WfLightFrameWalk : WfWalkRay {
 // (SceneView::light_sep): sum(node) = sum(left) + sum(right), a side without hits is the additive identity, a leaf adds its
 // hits in index order.
 // Hits are kept in the top of the lane's LDS stack column ({index, term} pairs growing downwards); a query whose hits would
-// run into its stack, or with more than WF_MAX_LIGHT_HITS of them, is handed to wf_light_exact_kernel (frame walk of rt_device.h).
+// run into its stack, or with more than WF_MAX_LIGHT_HITS of them, is handed to wf_light_exact_kernel (frame_sum of rt_ref_walk.h).
 #define WF_MAX_LIGHT_HITS 5
 // The sum of the k hits of a finished walk in the reference's association.  Hit j: light index in stack[WF_STACK-1-2j], term in
 // stack[WF_STACK-2-2j], ascending indices; the bottom of the column is free by then and holds the separation depths while the terms

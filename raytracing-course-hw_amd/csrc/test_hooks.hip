@@ -6,6 +6,7 @@
 #include "device/rt_kernels_hw8.h"
 #include "device/rt_node_grid.h"
 #include "device/rt_pt_queue.h"
+#include "device/rt_ref_walk.h"
 #include "host/fold_nodes.h"
 #include <cstring>
 #include <vector>
@@ -133,6 +134,27 @@ __global__ void k_pt_pop(uint32_t *bitmap, int *count, uint32_t nw, uint32_t cur
     __syncthreads();
     for (uint32_t i = threadIdx.x; i < nw; i += blockDim.x) bitmap[i] = bm[i];
     if (threadIdx.x == 0) *count = cnt;
+}
+
+// rt_ref_walk.h frame_sum on a node table of the test's own, one tree per thread (workgroups of FS_BATCH threads).  A node is four words
+// {kind (FRAME_TOTAL / FRAME_ONE / FRAME_BOTH), left, right, value bits}; a node number beyond the table counts as a total of 0.
+// LDS_VIEW: the stack is a StridedStack<FS_BATCH> over LDS, the layout of the persistent kernel's exact role; else a private array.
+#define FS_BATCH 16
+template <int MAXDEPTH, bool LDS_VIEW>
+__global__ void k_frame_sum(const uint4 *nodes, uint32_t n_nodes, const uint32_t *roots, int n_roots, float *out) {
+    __shared__ uint32_t area[LDS_VIEW ? MAXDEPTH * FS_BATCH : 1];
+    uint32_t own[LDS_VIEW ? 1 : MAXDEPTH];
+    const int i = blockIdx.x * FS_BATCH + threadIdx.x;
+    if (i >= n_roots) return;
+    auto node = [&](uint32_t cur, uint32_t &l, uint32_t &r, float &v) {
+        if (cur >= n_nodes) { v = 0.f; return (int)FRAME_TOTAL; }
+        const uint4 n = nodes[cur];
+        l = n.y; r = n.z;
+        if (n.x == FRAME_TOTAL) v = __uint_as_float(n.w);
+        return (int)n.x;
+    };
+    if (LDS_VIEW) { const StridedStack<FS_BATCH> view = {area + threadIdx.x}; out[i] = frame_sum<MAXDEPTH>(view, node, roots[i]); }
+    else out[i] = frame_sum<MAXDEPTH>(own, node, roots[i]);
 }
 
 extern "C" {
@@ -287,6 +309,25 @@ int rtt_rng_streams(uint32_t seed0, int n_seeds, int n_u, int n_n, float *out) {
     hipLaunchKernelGGL(k_rng, dim3((n_seeds + 63) / 64), dim3(64), 0, 0, seed0, n_seeds, n_u, n_n, d_out);
     int rc = hipMemcpy(out, d_out, n * 4, hipMemcpyDeviceToHost) == hipSuccess ? 0 : -2;
     (void)hipFree(d_out);
+    return rc;
+}
+// k_frame_sum for n_roots trees of a table of n_nodes nodes (4 words each).  variant 0: depth 64, private stack; 1: depth 64, strided LDS view;
+// 2: depth 128, private stack.  out: n_roots floats.
+int rtt_frame_sum(const uint32_t *nodes, uint32_t n_nodes, const uint32_t *roots, int n_roots, int variant, float *out) {
+    if (n_roots <= 0 || n_nodes == 0 || variant < 0 || variant > 2) return -1;
+    uint4 *d_nodes = nullptr; uint32_t *d_roots = nullptr; float *d_out = nullptr;
+    int rc = -2;
+    if (hipMalloc((void **)&d_nodes, (size_t)n_nodes * 16) == hipSuccess && hipMalloc((void **)&d_roots, (size_t)n_roots * 4) == hipSuccess &&
+        hipMalloc((void **)&d_out, (size_t)n_roots * 4) == hipSuccess &&
+        hipMemcpy(d_nodes, nodes, (size_t)n_nodes * 16, hipMemcpyHostToDevice) == hipSuccess &&
+        hipMemcpy(d_roots, roots, (size_t)n_roots * 4, hipMemcpyHostToDevice) == hipSuccess) {
+        const dim3 grid((unsigned)((n_roots + FS_BATCH - 1) / FS_BATCH)), block(FS_BATCH);
+        if (variant == 0) hipLaunchKernelGGL((k_frame_sum<64, false>), grid, block, 0, 0, d_nodes, n_nodes, d_roots, n_roots, d_out);
+        else if (variant == 1) hipLaunchKernelGGL((k_frame_sum<64, true>), grid, block, 0, 0, d_nodes, n_nodes, d_roots, n_roots, d_out);
+        else hipLaunchKernelGGL((k_frame_sum<128, false>), grid, block, 0, 0, d_nodes, n_nodes, d_roots, n_roots, d_out);
+        rc = (hipDeviceSynchronize() == hipSuccess && hipMemcpy(out, d_out, (size_t)n_roots * 4, hipMemcpyDeviceToHost) == hipSuccess) ? 0 : -3;
+    }
+    (void)hipFree(d_nodes); (void)hipFree(d_roots); (void)hipFree(d_out);
     return rc;
 }
 }
