@@ -80,7 +80,6 @@ struct Scene2 {
     std::vector<Light> lights;
     V3 camPos, camRight, camUp, camFwd, bg, ambient;
     float fovX = 0;
-    int width = 0, height = 0, rayDepth = 1;
 
     // hw2/src/scene.cpp:8-28
     bool intersect(V3 o, V3 d, float tmax, Hit &best, int &pos) const {
@@ -139,11 +138,11 @@ struct Scene2 {
         return r * reflected + (1 - r) * refracted;
     }
     // hw2/src/scene.cpp:90-98 — tan on a float is tanf here
-    void camera_ray(int x, int y, V3 &o, V3 &d) const {
+    void camera_ray(const Frame &fr, int x, int y, V3 &o, V3 &d) const {
         float tanFovX = tanf(fovX / 2);
-        float tanFovY = tanFovX * height / width;
-        float nx = tanFovX * (2 * (x + 0.5) / width - 1);
-        float ny = tanFovY * (2 * (y + 0.5) / height - 1);
+        float tanFovY = tanFovX * fr.height / fr.width;
+        float nx = tanFovX * (2 * (x + 0.5) / fr.width - 1);
+        float ny = tanFovY * (2 * (y + 0.5) / fr.height - 1);
         o = camPos;
         d = nx * camRight - ny * camUp + camFwd;
     }
@@ -154,7 +153,6 @@ static inline V3 gamma_corrected_f(V3 x) {
     float gamma = 1. / 2.2;
     return {powf(x.x, gamma), powf(x.y, gamma), powf(x.z, gamma)};
 }
-static V3 v3(const float *p) { return {p[0], p[1], p[2]}; }
 } // namespace rto2
 
 using namespace rto2;
@@ -178,15 +176,15 @@ void rto_hw2_destroy(void *p) { delete (Scene2 *)p; }
 // Rectangle [x0,x0+w) x [y0,y0+h) of the width x height frame; out_rgb = linear radiance, out8 = the program's bytes
 // (hw2/src/sceneio.cpp:150-162: aces, gamma, round(255 x)).
 int rto_hw2_render(void *p, int width, int height, int ray_depth, int x0, int y0, int w, int h, float *out_rgb, uint8_t *out8, int nthreads) {
-    Scene2 *s = (Scene2 *)p;
-    s->width = width; s->height = height; s->rayDepth = ray_depth;
+    const Scene2 *s = (const Scene2 *)p;
+    const Frame fr{width, height, 1, ray_depth};
     if (nthreads <= 0) nthreads = omp_get_max_threads();
 #pragma omp parallel for schedule(dynamic, 8) num_threads(nthreads)
     for (int j = 0; j < w * h; j++) {
         int x = x0 + j % w, y = y0 + j / w;
         V3 o, d;
-        s->camera_ray(x, y, o, d);
-        V3 px = s->get_color(o, d, s->rayDepth);
+        s->camera_ray(fr, x, y, o, d);
+        V3 px = s->get_color(o, d, fr.ray_depth);
         if (out_rgb) { out_rgb[3 * j] = px.x; out_rgb[3 * j + 1] = px.y; out_rgb[3 * j + 2] = px.z; }
         if (out8) to_extern(gamma_corrected_f(aces_tonemap(px)), out8 + 3 * j);
     }

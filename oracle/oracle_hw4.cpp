@@ -9,15 +9,9 @@
 // (pinned bit for bit against the compiled hw4 sources); seed_mode 1 gives every pixel a fresh engine(y*W+x) and fresh
 // distribution objects — the form a parallel machine can run, used to check the GPU.
 #include "oracle_txt_prims.h"
-#include <memory>
-#include <omp.h>
 
 namespace rto4 {
 using namespace rtot;
-
-typedef std::uniform_real_distribution<float> U01;
-typedef std::normal_distribution<float> N01;
-static const float PI = std::acos(-1); // distributions.h:9
 
 struct Sampler { // all mutable sampling state of one replay stream
     rng_t rng;
@@ -31,7 +25,6 @@ struct Scene4 {
     std::vector<int> lights; // indices of emissive BOX / ELLIPSOID figures in figure order (scene.cpp:12-21)
     V3 camPos, camRight, camUp, camFwd, bg;
     float fovX = 0;
-    int width = 0, height = 0, samples = 1, rayDepth = 1;
 
     bool intersect(V3 o, V3 d, Hit &best, int &pos) const { // scene.cpp:31-49
         pos = -1;
@@ -43,25 +36,9 @@ struct Scene4 {
     }
 
     // ---- distributions.h ---------------------------------------------------------------------------------------
-    V3 cosine_sample(Sampler &S, V3 n) const { // :55-67
-        float a = S.cosine_n01(S.rng), b = S.cosine_n01(S.rng), c = S.cosine_n01(S.rng);
-        V3 d = normalize(V3{a, b, c});
-        d = d + n;
-        float l = len(d);
-        if (l <= 1e-9f || dot(d, n) <= 1e-9f || std::isnan(l)) return n;
-        return (float)(1. / (double)l) * d;
-    }
-    float cosine_pdf(V3 n, V3 d) const { return smax(0.f, dot(d, n) / PI); } // :69-72
+    struct Ray { bool operator()(const Prim &f, V3 o, V3 d, Hit &h) const { return prim_ray3(f, o, d, h, true); } };
     float pdf_one(const Prim &f, V3 x, V3 d, V3 y, V3 yn) const {
-        if (f.type == RT_PRIM_BOX) {                                         // :115-118
-            float sx = f.data.x, sy = f.data.y, sz = f.data.z;
-            float sTotal = 8 * (sy * sz + sx * sz + sx * sy);
-            return (double)len2(x - y) / ((double)sTotal * std::fabs((double)dot(d, yn)));
-        }
-        V3 r = f.data;                                                       // :159-164
-        V3 n = qtransform(f.rotation, y - f.position) / r;
-        float pointProb = 1. / (double)(4 * PI * len(V3{n.x * r.y * r.z, r.x * n.y * r.z, r.x * r.y * n.z}));
-        return (double)(pointProb * len2(x - y)) / std::fabs((double)dot(d, yn));
+        return f.type == RT_PRIM_BOX ? box_emitter_pdf_one(f, x, d, y, yn) : ellipsoid_emitter_pdf_one(f, x, d, y, yn);
     }
     float light_pdf(const Prim &f, V3 x, V3 d) const { // FigureLight::pdf :85-107
         Hit h1;
@@ -74,39 +51,15 @@ struct Scene4 {
         V3 y2 = x + (float)((double)h1.t + 0.0001 + (double)h2.t) * d;
         return ans + pdf_one(f, x, d, y2, h2.norma);
     }
-    V3 light_sample(Sampler &S, int li, V3 x) const {
+    V3 light_sample(Sampler &S, int li, V3 x) const { // each EllipsoidLight draws from its own normal_distribution
         const Prim &f = figs[lights[li]];
-        if (f.type == RT_PRIM_BOX) {                                         // :125-151
-            float sx = f.data.x, sy = f.data.y, sz = f.data.z;
-            float wx = sy * sz, wy = sx * sz, wz = sx * sy;
-            for (;;) {
-                float u = S.u01(S.rng) * (wx + wy + wz);
-                float flipSign = (double)S.u01(S.rng) > 0.5 ? 1 : -1;
-                // Vec3(a, b, c) is a constructor call: g++ evaluates its arguments right to left, so the LAST
-                // coordinate's random number is drawn first (pinned against the compiled reference).
-                V3 point;
-                if (u < wx) { float c = (2 * S.u01(S.rng) - 1) * sz; float b = (2 * S.u01(S.rng) - 1) * sy; point = V3{flipSign * sx, b, c}; }
-                else if (u < wx + wy) { float c = (2 * S.u01(S.rng) - 1) * sz; float a = (2 * S.u01(S.rng) - 1) * sx; point = V3{a, flipSign * sy, c}; }
-                else { float b = (2 * S.u01(S.rng) - 1) * sy; float a = (2 * S.u01(S.rng) - 1) * sx; point = V3{a, b, flipSign * sz}; }
-                V3 actual = qtransform(qconj(f.rotation), point) + f.position;
-                Hit h;
-                if (prim_ray3(f, x, normalize(actual - x), h, true)) return normalize(actual - x);
-            }
-        }
-        V3 r = f.data;                                                       // :169-180
-        N01 &n01 = S.light_n01[li];
-        for (;;) {
-            float a = n01(S.rng), b = n01(S.rng), c = n01(S.rng);
-            V3 point = r * normalize(V3{a, b, c});
-            V3 actual = qtransform(qconj(f.rotation), point) + f.position;
-            Hit h;
-            if (prim_ray3(f, x, normalize(actual - x), h, true)) return normalize(actual - x);
-        }
+        if (f.type == RT_PRIM_BOX) return box_emitter_sample(f, S.u01, S.rng, x, Ray());
+        return ellipsoid_emitter_sample(f, S.light_n01[li], S.rng, x, Ray());
     }
     V3 mix_sample(Sampler &S, V3 x, V3 n) const { // Mix::sample :194-197, outer then inner
         size_t comps = lights.empty() ? 1 : 2;
         int distNum = S.u01(S.rng) * comps;
-        if (distNum == 0) return cosine_sample(S, n);
+        if (distNum == 0) return cosine_sample(S.cosine_n01, S.rng, n);
         int li = S.u01(S.rng) * lights.size();
         return light_sample(S, li, x);
     }
@@ -135,43 +88,27 @@ struct Scene4 {
             V3 inner = get_color(S, x + (float)0.0001 * d, d, recLimit - 1);
             return f.emission + (float)(1. / (double)(PI * pdf) * (double)dot(d, norma)) * f.color * inner;
         }
-        V3 dn = normalize(rd);
-        V3 refl = dn - (float)(2. * dot(norma, dn)) * norma;
-        V3 o = ro + t * rd + (float)0.0001 * refl;
-        if (f.kind == RT_MAT_METALLIC) return f.emission + f.color * get_color(S, o, refl, recLimit - 1);
-        V3 reflected = get_color(S, o, refl, recLimit - 1);
-        float eta1 = 1., eta2 = f.ior;
-        if (h.inside) std::swap(eta1, eta2);
-        V3 l = neg1(normalize(rd));
-        float sinTheta2 = eta1 / eta2 * std::sqrt((double)(1 - dot(norma, l) * dot(norma, l)));
-        if (std::fabs((double)sinTheta2) > 1.) return f.emission + reflected;
-        float r0 = std::pow((double)((eta1 - eta2) / (eta1 + eta2)), 2.);
-        float r = r0 + (1 - r0) * std::pow((double)(1 - dot(norma, l)), 5.);
-        if (S.u01(S.rng) < r) return f.emission + reflected;
-        float cosTheta2 = std::sqrt((double)(1 - sinTheta2 * sinTheta2));
-        V3 refr = (eta1 / eta2) * neg1(l) + (eta1 / eta2 * dot(norma, l) - cosTheta2) * norma;
-        V3 refracted = get_color(S, ro + t * rd + (float)0.0001 * refr, refr, recLimit - 1);
-        if (!h.inside) refracted = refracted * f.color;
-        return f.emission + refracted;
+        return specular_tail(t, norma, h.inside, ro, rd, f.color, f.emission, f.kind, f.ior, (float)0.0001, [&] { return S.u01(S.rng); },
+                             [&](V3 o, V3 d) { return get_color(S, o, d, recLimit - 1); });
     }
-    void camera_ray(float x, float y, V3 &o, V3 &d) const { // scene.cpp:124-132: all float, no half-pixel offset
+    void camera_ray(const Frame &fr, float x, float y, V3 &o, V3 &d) const { // scene.cpp:124-132: all float, no half-pixel offset
         float tanFovX = std::tan((double)(fovX / 2));
-        float tanFovY = tanFovX * height / width;
-        float nx = tanFovX * (2 * x / width - 1);
-        float ny = tanFovY * (2 * y / height - 1);
+        float tanFovY = tanFovX * fr.height / fr.width;
+        float nx = tanFovX * (2 * x / fr.width - 1);
+        float ny = tanFovY * (2 * y / fr.height - 1);
         o = camPos;
         d = nx * camRight - ny * camUp + camFwd;
     }
-    V3 get_pixel(Sampler &S, int x, int y) const { // scene.cpp:114-122
+    V3 get_pixel(const Frame &fr, Sampler &S, int x, int y) const { // scene.cpp:114-122
         V3 color{0, 0, 0};
-        for (int s = 0; s < samples; s++) {
+        for (int s = 0; s < fr.samples; s++) {
             float nx = x + S.u01(S.rng);
             float ny = y + S.u01(S.rng);
             V3 o, d;
-            camera_ray(nx, ny, o, d);
-            color = color + get_color(S, o, d, rayDepth);
+            camera_ray(fr, nx, ny, o, d);
+            color = color + get_color(S, o, d, fr.ray_depth);
         }
-        return (float)(1.0 / samples) * color;
+        return (float)(1.0 / fr.samples) * color;
     }
 };
 } // namespace rto4
@@ -196,27 +133,13 @@ int rto_hw4_num_lights(void *p) { return (int)((Scene4 *)p)->lights.size(); }
 // seed_mode 1: fresh engine(y*W+x) and fresh distribution objects per pixel (parallel).
 int rto_hw4_render(void *p, int width, int height, int samples, int ray_depth, int seed_mode, int x0, int y0, int w, int h,
                    float *out_rgb, uint8_t *out8, int nthreads) {
-    Scene4 *s = (Scene4 *)p;
-    s->width = width; s->height = height; s->samples = samples; s->rayDepth = ray_depth;
-    auto store = [&](int j, V3 px) {
-        if (out_rgb) { out_rgb[3 * j] = px.x; out_rgb[3 * j + 1] = px.y; out_rgb[3 * j + 2] = px.z; }
-        if (out8) to_extern(gamma_corrected(aces_tonemap(px)), out8 + 3 * j);
-    };
-    if (seed_mode == 0) {
-        Sampler S;
-        S.light_n01.assign(s->lights.size(), N01(0.f, 1.f));
-        for (int j = 0; j < w * h; j++) store(j, s->get_pixel(S, x0 + j % w, y0 + j / w));
-        return 0;
-    }
-    if (nthreads <= 0) nthreads = omp_get_max_threads();
-#pragma omp parallel for schedule(dynamic, 8) num_threads(nthreads)
-    for (int j = 0; j < w * h; j++) {
-        int x = x0 + j % w, y = y0 + j / w;
-        Sampler S;
-        S.rng.seed(y * width + x);
-        S.light_n01.assign(s->lights.size(), N01(0.f, 1.f));
-        store(j, s->get_pixel(S, x, y));
-    }
+    const Scene4 *s = (const Scene4 *)p;
+    const Frame fr{width, height, samples, ray_depth};
+    auto pixel = [&](Sampler &S, int x, int y) { return s->get_pixel(fr, S, x, y); };
+    auto fresh = [&](int seed) { Sampler S; S.rng.seed(seed); S.light_n01.assign(s->lights.size(), N01(0.f, 1.f)); return S; };
+    Sampler whole = fresh(rng_t::default_seed);             // scene.cpp:5: a default-constructed engine
+    if (seed_mode == 0) render_rect(true, 1, x0, y0, w, h, out_rgb, out8, [&](int, int) -> Sampler & { return whole; }, pixel);
+    else render_rect(false, nthreads, x0, y0, w, h, out_rgb, out8, [&](int x, int y) { return fresh(y * width + x); }, pixel);
     return 0;
 }
 }

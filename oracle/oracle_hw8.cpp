@@ -6,11 +6,10 @@
 // reference lines it follows.  Pinned against the compiled reference by tests/test_oracle_ref.py
 // (oracle/_ref harnesses, fixtures in tests/golden/); see DESIGN.md "Oracle pinning" for what is
 // pinned by which fixture and the two glue functions that are "parity unpinned".
-#include "oracle_common.h"
+#include "oracle_bvh.h"
 #include <optional>
 #include <utility>
 #include <atomic>
-#include <omp.h>
 #include <cstdio>
 
 namespace rto {
@@ -40,9 +39,6 @@ struct Hit {                                   // primitives.h:48-55
     float tanw;
     bool inside;
 };
-struct Box { V3 mn, mx; };
-
-struct Counters { uint64_t closest = 0, lightq = 0, boxes = 0, tris = 0; };
 static thread_local Counters tl_cnt;
 static thread_local std::vector<float> *tl_trace = nullptr; // diagnostic query log of one pixel (rto_hw8_trace_pixel)
 static bool g_debug_bruteforce = false;
@@ -57,25 +53,6 @@ static inline bool plane_ray(V3 n, V3 o, V3 d, float &t, V3 &ng, bool &inside) {
         return true;
     }
     return false;
-}
-// primitives.cpp:29-53 with require_norma == false (the only form on the hw8 hot path)
-static inline bool box_ray(V3 s, V3 o, V3 d, float &t, bool &inside) {
-    V3 ts1 = (neg1(s) - o) / d;
-    V3 ts2 = (s - o) / d;
-    float t1x = smin(ts1.x, ts2.x), t2x = smax(ts1.x, ts2.x);
-    float t1y = smin(ts1.y, ts2.y), t2y = smax(ts1.y, ts2.y);
-    float t1z = smin(ts1.z, ts2.z), t2z = smax(ts1.z, ts2.z);
-    float t1 = smax(smax(t1x, t1y), t1z);
-    float t2 = smin(smin(t2x, t2y), t2z);
-    if (t1 > t2 || t2 < 0) return false;
-    if (t1 < 0) { inside = true; t = t2; }
-    else { inside = false; t = t1; }
-    return true;
-}
-// primitives.cpp:163-165
-static inline bool aabb_ray(const Box &b, V3 o, V3 d, float &t, bool &inside) {
-    tl_cnt.boxes++;
-    return box_ray(0.5f * (b.mx - b.mn), o - 0.5f * (b.mn + b.mx), d, t, inside);
 }
 // primitives.cpp:76-80
 static inline void solve2(float a1, float b1, float c1, float a2, float b2, float c2, float &x, float &y) {
@@ -116,108 +93,23 @@ static bool tri_ray(const Fig &f, V3 o, V3 d, Hit &h) {
     return true;
 }
 
-// primitives.cpp:130-141
-static Box box_of(const Fig &f) {
-    Box b;
-    b.mn = {smin(f.d3.coords.x, smin(f.d.coords.x, f.d2.coords.x)), smin(f.d3.coords.y, smin(f.d.coords.y, f.d2.coords.y)),
-            smin(f.d3.coords.z, smin(f.d.coords.z, f.d2.coords.z))};
-    b.mx = {smax(f.d3.coords.x, smax(f.d.coords.x, f.d2.coords.x)), smax(f.d3.coords.y, smax(f.d.coords.y, f.d2.coords.y)),
-            smax(f.d3.coords.z, smax(f.d.coords.z, f.d2.coords.z))};
-    return b;
-}
-// primitives.cpp:144-156
-static void extend(Box &b, V3 p) {
-    b.mx.x = smax(b.mx.x, p.x); b.mx.y = smax(b.mx.y, p.y); b.mx.z = smax(b.mx.z, p.z);
-    b.mn.x = smin(b.mn.x, p.x); b.mn.y = smin(b.mn.y, p.y); b.mn.z = smin(b.mn.z, p.z);
-}
-static void extend(Box &b, const Box &o) { extend(b, o.mn); extend(b, o.mx); }
-// primitives.cpp:158-161
-static float surf(const Box &b) {
-    V3 d = b.mx - b.mn;
-    return 2 * (d.x * d.y + d.x * d.z + d.y * d.z);
-}
-
-// ---- bvh.h --------------------------------------------------------------------------------------
-struct Node { Box aabb; uint32_t left = 0, right = 0, first = 0, last = 0; }; // bvh.h:9-16
-struct Bvh {
-    std::vector<Node> nodes;
-    uint32_t root = 0;
-    uint32_t depth = 0;
-
-    // bvh.h:34-54
-    static std::pair<float, uint32_t> best_split(std::vector<Fig> &figs, uint32_t first, uint32_t last) {
-        std::vector<float> scores(last - first, 0);
-        Box pre = box_of(figs[first]);
-        for (size_t i = 1; i < last - first; i++) {
-            scores[i] = surf(pre) * i;
-            extend(pre, box_of(figs[first + i]));
-        }
-        Box suf = box_of(figs[last - 1]);
-        for (size_t i = last - first - 1; i >= 1; i--) {
-            scores[i] += surf(suf) * ((last - first) - i);
-            extend(suf, box_of(figs[first + i - 1]));
-        }
-        std::pair<float, uint32_t> ans = {scores[1], first + 1};
-        for (size_t i = 2; i < last - first; i++)
-            if (scores[i] < ans.first) ans = {scores[i], (uint32_t)(first + i)};
-        return ans;
+// ---- bvh.h: the shared builder, sorted on the third corner (bvh.h:60-65) ------------------------
+struct Tree8 {
+    typedef rto::Hit Hit;
+    // primitives.cpp:130-141
+    static Box box_of(const Fig &f) {
+        Box b;
+        b.mn = {smin(f.d3.coords.x, smin(f.d.coords.x, f.d2.coords.x)), smin(f.d3.coords.y, smin(f.d.coords.y, f.d2.coords.y)),
+                smin(f.d3.coords.z, smin(f.d.coords.z, f.d2.coords.z))};
+        b.mx = {smax(f.d3.coords.x, smax(f.d.coords.x, f.d2.coords.x)), smax(f.d3.coords.y, smax(f.d.coords.y, f.d2.coords.y)),
+                smax(f.d3.coords.z, smax(f.d.coords.z, f.d2.coords.z))};
+        return b;
     }
-    // bvh.h:60-65
-    static void half_split(std::vector<Fig> &figs, uint32_t first, uint32_t last, int axis) {
-        if (axis == 0) std::sort(figs.begin() + first, figs.begin() + last, [](const Fig &l, const Fig &r) { return l.d3.coords.x < r.d3.coords.x; });
-        else if (axis == 1) std::sort(figs.begin() + first, figs.begin() + last, [](const Fig &l, const Fig &r) { return l.d3.coords.y < r.d3.coords.y; });
-        else std::sort(figs.begin() + first, figs.begin() + last, [](const Fig &l, const Fig &r) { return l.d3.coords.z < r.d3.coords.z; });
-    }
-    // bvh.h:67-109
-    uint32_t build(std::vector<Fig> &figs, uint32_t first, uint32_t last, uint32_t d = 1) {
-        if (d > depth) depth = d;
-        Node cur; cur.first = first; cur.last = last;
-        Box aabb;
-        if (first < last) aabb = box_of(figs[first]);
-        for (uint32_t i = first + 1; i < last; i++) extend(aabb, box_of(figs[i]));
-        cur.aabb = aabb;
-        uint32_t pos = (uint32_t)nodes.size();
-        nodes.push_back(cur);
-        if (last - first <= 1) return pos;
-        half_split(figs, first, last, 0); auto sx = best_split(figs, first, last);
-        half_split(figs, first, last, 1); auto sy = best_split(figs, first, last);
-        half_split(figs, first, last, 2); auto sz = best_split(figs, first, last);
-        float best = smin(sx.first, smin(sy.first, sz.first));
-        if (best >= surf(aabb) * (last - first)) return pos;
-        uint32_t mid;
-        if (best == sx.first) { mid = sx.second; half_split(figs, first, last, 0); }
-        else if (best == sy.first) { mid = sy.second; half_split(figs, first, last, 1); }
-        else { mid = sz.second; half_split(figs, first, last, 2); }
-        uint32_t l = build(figs, first, mid, d + 1); nodes[pos].left = l;
-        uint32_t r = build(figs, mid, last, d + 1); nodes[pos].right = r;
-        return pos;
-    }
-    void init(std::vector<Fig> &figs, uint32_t n) { nodes.clear(); depth = 0; root = build(figs, 0, n); }
-
-    // bvh.h:111-142 — recursive closest hit, left child first, strict '<' keeps the first found.
-    bool intersect(const std::vector<Fig> &figs, uint32_t pos, V3 o, V3 d, bool have_best, float cur_best, Hit &out, int &idx) const {
-        const Node &cur = nodes[pos];
-        float t; bool inside;
-        if (!aabb_ray(cur.aabb, o, d, t, inside)) return false;
-        if (have_best && cur_best < t && !inside) return false;
-        bool found = false;
-        if (cur.left == 0) {
-            for (uint32_t i = cur.first; i < cur.last; i++) {
-                Hit h;
-                if (tri_ray(figs[i], o, d, h) && (!found || h.t < out.t)) { out = h; idx = (int)i; found = true; }
-            }
-            return found;
-        }
-        Hit lh; int li = -1;
-        bool lf = intersect(figs, cur.left, o, d, have_best, cur_best, lh, li);
-        if (lf) { out = lh; idx = li; found = true; }
-        if (lf && (!have_best || lh.t < cur_best)) { cur_best = lh.t; have_best = true; }
-        Hit rh; int ri = -1;
-        bool rf = intersect(figs, cur.right, o, d, have_best, cur_best, rh, ri);
-        if (rf && (!found || rh.t < out.t)) { out = rh; idx = ri; found = true; }
-        return found;
-    }
+    static V3 key(const Fig &f) { return f.d3.coords; }
+    static bool hit(const Fig &f, V3 o, V3 d, Hit &h) { return tri_ray(f, o, d, h); }
+    static void count_box() { tl_cnt.boxes++; }
 };
+typedef Bvh<Fig, Tree8> Bvh8;
 
 // ---- material.h ---------------------------------------------------------------------------------
 struct MaterialModel {
@@ -283,22 +175,6 @@ struct MaterialModel {
 };
 
 // ---- distributions.h ----------------------------------------------------------------------------
-typedef std::uniform_real_distribution<float> U01;
-typedef std::normal_distribution<float> N01;
-
-// distributions.h:42-52
-static V3 cosine_sample(N01 &n01, rng_t &rng, V3 n) {
-    float a = n01(rng), b = n01(rng), c = n01(rng); // braced init: left to right
-    V3 d = normalize(V3{a, b, c});
-    d = d + n;
-    float l = len(d);
-    const float ceps = 1e-9;
-    if (l <= ceps || dot(d, n) <= ceps || std::isnan(l)) return n;
-    return (float)(1. / l) * d;
-}
-// distributions.h:54-57
-static float cosine_pdf(V3 n, V3 d) { return smax(0.f, dot(d, n) / (float)M_PI); }
-
 struct TriLight {                              // distributions.h:60-95
     float pointProb;
     Fig fig;
@@ -320,7 +196,7 @@ struct TriLight {                              // distributions.h:60-95
 
 struct FiguresMix {                            // distributions.h:97-166
     std::vector<TriLight> lights;
-    Bvh bvh;
+    Bvh8 bvh;
     bool hw7_geom_normal = false;              // hw7/src/include/distributions.h:140-145 uses yn (geometric)
     float pdf_one(const TriLight &tl, V3 x, V3 d) const { // distributions.h:131-146
         Hit h;
@@ -329,22 +205,9 @@ struct FiguresMix {                            // distributions.h:97-166
         V3 y = x + h.t * d;
         return tl.pdfOne(x, d, y, hw7_geom_normal ? h.ng : h.ns);
     }
-    float total_pdf(uint32_t pos, V3 x, V3 d) const { // distributions.h:148-165
-        const Node &cur = bvh.nodes[pos];
-        float t; bool inside;
-        if (!aabb_ray(cur.aabb, x, d, t, inside)) return 0;
-        if (cur.left == 0) {
-            float result = 0;
-            for (uint32_t i = cur.first; i < cur.last; i++) result += pdf_one(lights[i], x, d);
-            return result;
-        }
-        float l = total_pdf(cur.left, x, d);
-        float r = total_pdf(cur.right, x, d);
-        return l + r;
-    }
     float pdf(V3 x, V3 d) const { // :122-124
         tl_cnt.lightq++;
-        float r = total_pdf(0, x, d) / lights.size();
+        float r = bvh.total_pdf(0, x, d, [&](uint32_t i) { return pdf_one(lights[i], x, d); }) / lights.size(); // getTotalPdf :148-165
         if (g_debug_bruteforce) { // diagnostic: lights whose triangle test hits but whose BVH boxes the reference's slab test rejects
             float brute = 0; int nh = 0;
             for (const TriLight &tl : lights) { float p = pdf_one(tl, x, d); if (p != 0) nh++; brute += p; }
@@ -357,6 +220,7 @@ struct FiguresMix {                            // distributions.h:97-166
                     for (;;) {
                         const Node &n = bvh.nodes[pos];
                         float t; bool inside;
+                        Tree8::count_box();
                         bool ok = aabb_ray(n.aabb, x, d, t, inside);
                         if (!ok) {
                             V3 s = 0.5f * (n.aabb.mx - n.aabb.mn), o = x - 0.5f * (n.aabb.mn + n.aabb.mx);
@@ -488,10 +352,9 @@ struct Scene {
     bool has_env = false; Tex env;
     V3 camPos, camRight, camUp, camFwd; float fovY = 0;
     V3 bg;
-    Bvh bvh;
+    Bvh8 bvh;
     FiguresMix lightmix;
     int n_components = 2;
-    int width = 0, height = 0, samples = 1, rayDepth = 6;
     bool hw7 = false; // replay hw7/src/scene.cpp:29-61 instead of hw8/src/scene.cpp:84-165
 
     bool emissive(const Fig &f) const {     // distributions.h:104-109 (factor, not texture)
@@ -525,11 +388,11 @@ struct Scene {
         return ans / (size_t)n_components;
     }
     // scene.cpp:179-186
-    void camera_ray(float x, float y, V3 &o, V3 &d) const {
+    void camera_ray(const Frame &fr, float x, float y, V3 &o, V3 &d) const {
         float tanFovY = std::tan((double)(fovY / 2));
-        float tanFovX = tanFovY * width / height;
-        float nx = tanFovX * (2 * x / width - 1);
-        float ny = tanFovY * (2 * y / height - 1);
+        float tanFovX = tanFovY * fr.width / fr.height;
+        float nx = tanFovX * (2 * x / fr.width - 1);
+        float ny = tanFovY * (2 * y / fr.height - 1);
         o = camPos;
         d = normalize(nx * camRight - ny * camUp + camFwd);
     }
@@ -579,30 +442,26 @@ struct Scene {
         return emission + mult * get_color(u01, n01, rng, xo, d, recLimit - 1);
     }
     // scene.cpp:167-177
-    V3 get_pixel(rng_t &rng, int x, int y) const {
+    V3 get_pixel(const Frame &fr, rng_t &rng, int x, int y) const {
         U01 u01(0.0, 1.0);
         N01 n01(0.0, 1.0);
         V3 color{0, 0, 0};
-        for (int s = 0; s < samples; s++) {
+        for (int s = 0; s < fr.samples; s++) {
             float nx = x + u01(rng);
             float ny = y + u01(rng);
             V3 o, d;
-            camera_ray(nx, ny, o, d);
-            color = color + get_color(u01, n01, rng, o, d, rayDepth);
+            camera_ray(fr, nx, ny, o, d);
+            color = color + get_color(u01, n01, rng, o, d, fr.ray_depth);
         }
-        return (float)(1.0 / samples) * color;
+        return (float)(1.0 / fr.samples) * color;
     }
 };
-
-static V3 v3(const float *p) { return {p[0], p[1], p[2]}; }
 
 } // namespace rto
 
 using namespace rto;
 
 extern "C" {
-
-struct rto_counters { uint64_t closest, lightq, boxes, tris; };
 
 static void *create_common(const rt_scene_desc *d, bool hw7) {
     Scene *s = new Scene();
@@ -671,12 +530,12 @@ void rto_hw8_set_seed_offset(uint32_t off) { g_seed_offset = off; }
 // Diagnostic: the closest-hit queries of one pixel's replay, 12 floats each (origin, direction, t or -1, figure index or -1, inside,
 // texture u, v, remaining depth); returns the number of floats written (at most cap).
 int rto_hw8_trace_pixel(void *p, int width, int height, int samples, int ray_depth, int x, int y, float *out, int cap) {
-    Scene *s = (Scene *)p;
-    s->width = width; s->height = height; s->samples = samples; s->rayDepth = ray_depth > 0 ? ray_depth : 6;
+    const Scene *s = (const Scene *)p;
+    const Frame fr{width, height, samples, ray_depth > 0 ? ray_depth : 6};
     std::vector<float> log;
     tl_trace = &log;
     rng_t rng((uint32_t)(y * width + x) + g_seed_offset);
-    (void)s->get_pixel(rng, x, y);
+    (void)s->get_pixel(fr, rng, x, y);
     tl_trace = nullptr;
     int n = (int)log.size() < cap ? (int)log.size() : cap;
     memcpy(out, log.data(), (size_t)n * sizeof(float));
@@ -687,23 +546,13 @@ int rto_hw8_trace_pixel(void *p, int width, int height, int samples, int ray_dep
 // out_rgb: w*h*3 linear float radiance (nullable); out8: w*h*3 tonemapped bytes (nullable).
 // Mirrors the loop body of sceneio.cpp:387-396 (seed = y*width + x of the FULL image).
 int rto_hw8_render(void *p, int width, int height, int samples, int ray_depth, int x0, int y0, int w, int h,
-                   float *out_rgb, uint8_t *out8, int nthreads, rto_counters *cnt) {
-    Scene *s = (Scene *)p;
-    s->width = width; s->height = height; s->samples = samples; s->rayDepth = ray_depth > 0 ? ray_depth : 6;
-    if (nthreads <= 0) nthreads = omp_get_max_threads();
-    uint64_t c0 = 0, c1 = 0, c2 = 0, c3 = 0;
-#pragma omp parallel for schedule(dynamic, 8) num_threads(nthreads) reduction(+ : c0, c1, c2, c3)
-    for (int j = 0; j < w * h; j++) {
-        tl_cnt = Counters{};
-        int x = x0 + j % w, y = y0 + j / w;
-        int i = y * width + x;
-        rng_t rng((uint32_t)i + g_seed_offset);
-        V3 px = s->get_pixel(rng, x, y);
-        if (out_rgb) { out_rgb[3 * j] = px.x; out_rgb[3 * j + 1] = px.y; out_rgb[3 * j + 2] = px.z; }
-        if (out8) to_extern(gamma_corrected(aces_tonemap(px)), out8 + 3 * j);
-        c0 += tl_cnt.closest; c1 += tl_cnt.lightq; c2 += tl_cnt.boxes; c3 += tl_cnt.tris;
-    }
-    if (cnt) { cnt->closest = c0; cnt->lightq = c1; cnt->boxes = c2; cnt->tris = c3; }
+                   float *out_rgb, uint8_t *out8, int nthreads, Counters *cnt) {
+    const Scene *s = (const Scene *)p;
+    const Frame fr{width, height, samples, ray_depth > 0 ? ray_depth : 6};
+    Counters total = render_rect(false, nthreads, x0, y0, w, h, out_rgb, out8,
+                                 [&](int x, int y) { return rng_t((uint32_t)(y * width + x) + g_seed_offset); },
+                                 [&](rng_t &rng, int x, int y) { return s->get_pixel(fr, rng, x, y); }, [] { return &tl_cnt; });
+    if (cnt) *cnt = total;
     return 0;
 }
 

@@ -8,7 +8,6 @@
 // exactly that (pinned byte-for-byte against the compiled hw3 program), `seed_mode` 1 seeds one engine per
 // pixel with y*W+x like hw5+ do — the only form a parallel machine can run, used to check the GPU.
 #include "oracle_txt_prims.h"
-#include <omp.h>
 
 namespace rtot {
 
@@ -16,7 +15,6 @@ struct Scene3 {
     std::vector<Prim> figs;
     V3 camPos, camRight, camUp, camFwd, bg;
     float fovX = 0;
-    int width = 0, height = 0, samples = 1, rayDepth = 1;
 
     // hw3/src/scene.cpp:11-29 (tmax = +inf)
     bool intersect(V3 o, V3 d, Hit &best, int &pos) const {
@@ -40,52 +38,30 @@ struct Scene3 {
             if (dot(w, norma) < 0) w = neg1(w);
             V3 o = ro + t * rd + (float)0.0001 * w;
             return f.emission + (2 * dot(w, norma)) * f.color * get_color(rnd, u01, n01, o, w, recLimit - 1);
-        } else if (f.kind == RT_MAT_METALLIC) {
-            V3 dn = normalize(rd);
-            V3 refl = dn - (float)(2. * dot(norma, dn)) * norma;
-            V3 o = ro + t * rd + (float)0.0001 * refl;
-            return f.emission + f.color * get_color(rnd, u01, n01, o, refl, recLimit - 1);
-        } else {
-            V3 dn = normalize(rd);
-            V3 refl = dn - (float)(2. * dot(norma, dn)) * norma;
-            V3 o = ro + t * rd + (float)0.0001 * refl;
-            V3 reflected = get_color(rnd, u01, n01, o, refl, recLimit - 1);
-            float eta1 = 1., eta2 = f.ior;
-            if (h.inside) std::swap(eta1, eta2);
-            V3 l = neg1(normalize(rd));
-            float sinTheta2 = eta1 / eta2 * std::sqrt((double)(1 - dot(norma, l) * dot(norma, l)));
-            if (std::fabs((double)sinTheta2) > 1.) return f.emission + reflected;
-            float r0 = std::pow((double)((eta1 - eta2) / (eta1 + eta2)), 2.);
-            float r = r0 + (1 - r0) * std::pow((double)(1 - dot(norma, l)), 5.);
-            if (u01(rnd) < r) return f.emission + reflected;
-            float cosTheta2 = std::sqrt((double)(1 - sinTheta2 * sinTheta2));
-            V3 refr = (eta1 / eta2) * neg1(l) + (eta1 / eta2 * dot(norma, l) - cosTheta2) * norma;
-            V3 fo = ro + t * rd + (float)0.0001 * refr;
-            V3 refracted = get_color(rnd, u01, n01, fo, refr, recLimit - 1);
-            if (!h.inside) refracted = refracted * f.color;
-            return f.emission + refracted;
         }
+        return specular_tail(t, norma, h.inside, ro, rd, f.color, f.emission, f.kind, f.ior, (float)0.0001, [&] { return u01(rnd); },
+                             [&](V3 o, V3 d) { return get_color(rnd, u01, n01, o, d, recLimit - 1); });
     }
     // hw3/src/scene.cpp:99-107
-    void camera_ray(float x, float y, V3 &o, V3 &d, bool float_tan = false) const {
+    void camera_ray(const Frame &fr, float x, float y, V3 &o, V3 &d, bool float_tan = false) const {
         float tanFovX = float_tan ? tanf(fovX / 2) : (float)std::tan((double)(fovX / 2)); // hw1: <math.h> => tanf
-        float tanFovY = tanFovX * height / width;
-        float nx = tanFovX * (2 * (x + 0.5) / width - 1);
-        float ny = tanFovY * (2 * (y + 0.5) / height - 1);
+        float tanFovY = tanFovX * fr.height / fr.width;
+        float nx = tanFovX * (2 * (x + 0.5) / fr.width - 1);
+        float ny = tanFovY * (2 * (y + 0.5) / fr.height - 1);
         o = camPos;
         d = nx * camRight - ny * camUp + camFwd;
     }
     // hw3/src/scene.cpp:89-97
-    V3 get_pixel(rng_t &rnd, U01 &u01, N01 &n01, int x, int y) const {
+    V3 get_pixel(const Frame &fr, rng_t &rnd, U01 &u01, N01 &n01, int x, int y) const {
         V3 color{0, 0, 0};
-        for (int s = 0; s < samples; s++) {
+        for (int s = 0; s < fr.samples; s++) {
             float nx = x + u01(rnd);
             float ny = y + u01(rnd);
             V3 o, d;
-            camera_ray(nx, ny, o, d);
-            color = color + get_color(rnd, u01, n01, o, d, rayDepth);
+            camera_ray(fr, nx, ny, o, d);
+            color = color + get_color(rnd, u01, n01, o, d, fr.ray_depth);
         }
-        return (float)(1.0 / samples) * color;
+        return (float)(1.0 / fr.samples) * color;
     }
 };
 
@@ -140,12 +116,12 @@ void rto_txt_destroy(void *p) { delete (Scene3 *)p; }
 
 // hw1: out8 = round(255*colour) bytes (hw1/src/color.cpp:13-19), out_rgb = the colour itself.
 int rto_hw1_render(void *p, int width, int height, float *out_rgb, uint8_t *out8) {
-    Scene3 *s = (Scene3 *)p;
-    s->width = width; s->height = height;
+    const Scene3 *s = (const Scene3 *)p;
+    const Frame fr{width, height, 1, 1};
     for (int y = 0; y < height; y++)
         for (int x = 0; x < width; x++) {
             V3 o, d;
-            s->camera_ray((float)x, (float)y, o, d, true); // hw1/src/scene.cpp:22-30 takes ints; (x + 0.5) is the same double either way
+            s->camera_ray(fr, (float)x, (float)y, o, d, true); // hw1/src/scene.cpp:22-30 takes ints; (x + 0.5) is the same double either way
             V3 ans = s->bg;
             float best = -1;
             for (const Prim &f : s->figs) {
@@ -161,29 +137,15 @@ int rto_hw1_render(void *p, int width, int height, float *out_rgb, uint8_t *out8
 
 // hw3.  seed_mode 0: one engine for the whole frame, pixels in row-major order (the reference, single thread);
 //       seed_mode 1: engine(y*W+x) per pixel (parallel).
+struct Stream3 { rng_t rnd; U01 u01{0.0, 1.0}; N01 n01{0.0, 1.0}; }; // hw3/src/scene.cpp:5-7: default-seeded, shared by everything
 int rto_hw3_render(void *p, int width, int height, int samples, int ray_depth, int seed_mode, int x0, int y0, int w, int h,
                    float *out_rgb, uint8_t *out8, int nthreads) {
-    Scene3 *s = (Scene3 *)p;
-    s->width = width; s->height = height; s->samples = samples; s->rayDepth = ray_depth;
-    if (seed_mode == 0) {
-        rng_t rnd; U01 u01(0.0, 1.0); N01 n01(0.0, 1.0);   // hw3/src/scene.cpp:5-7: default-seeded, shared by everything
-        for (int j = 0; j < w * h; j++) {
-            int x = x0 + j % w, y = y0 + j / w;
-            V3 px = s->get_pixel(rnd, u01, n01, x, y);
-            if (out_rgb) { out_rgb[3 * j] = px.x; out_rgb[3 * j + 1] = px.y; out_rgb[3 * j + 2] = px.z; }
-            if (out8) to_extern(gamma_corrected(aces_tonemap(px)), out8 + 3 * j);
-        }
-        return 0;
-    }
-    if (nthreads <= 0) nthreads = omp_get_max_threads();
-#pragma omp parallel for schedule(dynamic, 8) num_threads(nthreads)
-    for (int j = 0; j < w * h; j++) {
-        int x = x0 + j % w, y = y0 + j / w;
-        rng_t rnd(y * width + x); U01 u01(0.0, 1.0); N01 n01(0.0, 1.0);
-        V3 px = s->get_pixel(rnd, u01, n01, x, y);
-        if (out_rgb) { out_rgb[3 * j] = px.x; out_rgb[3 * j + 1] = px.y; out_rgb[3 * j + 2] = px.z; }
-        if (out8) to_extern(gamma_corrected(aces_tonemap(px)), out8 + 3 * j);
-    }
+    const Scene3 *s = (const Scene3 *)p;
+    const Frame fr{width, height, samples, ray_depth};
+    auto pixel = [&](Stream3 &S, int x, int y) { return s->get_pixel(fr, S.rnd, S.u01, S.n01, x, y); };
+    Stream3 whole;
+    if (seed_mode == 0) render_rect(true, 1, x0, y0, w, h, out_rgb, out8, [&](int, int) -> Stream3 & { return whole; }, pixel);
+    else render_rect(false, nthreads, x0, y0, w, h, out_rgb, out8, [&](int x, int y) { Stream3 S; S.rnd.seed(y * width + x); return S; }, pixel);
     return 0;
 }
 }

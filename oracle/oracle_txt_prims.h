@@ -1,6 +1,7 @@
 // ORACLE — TEST INFRASTRUCTURE ONLY (see oracle_common.h).
 // Analytic primitives of the hw3 / hw4 / hw5 snapshots (<cmath> flavour: unqualified sqrt/fabs on floats are the double
-// C functions, results narrowed) shared by oracle_txt.cpp (hw3), oracle_hw4.cpp and oracle_hw5.cpp.
+// C functions, results narrowed) shared by oracle_txt.cpp (hw3), oracle_hw4.cpp and oracle_hw5.cpp,
+// and the box / ellipsoid light emitters that hw4 and hw5 share.
 #pragma once
 #include "oracle_common.h"
 
@@ -11,9 +12,6 @@ struct Prim {
     int type; V3 data, position; Quat rotation; V3 color, emission; int kind; float ior;
 };
 struct Hit { float t; V3 norma; bool inside; };
-
-typedef std::uniform_real_distribution<float> U01;
-typedef std::normal_distribution<float> N01;
 
 // hw3/src/primitives.cpp:28-47 (hw1: :33-52 without the inside flag)
 static inline bool smallest_root(float a, float b, float c, float &t, bool &inside) {
@@ -75,8 +73,54 @@ static inline bool prim_ray3(const Prim &f, V3 o, V3 d, Hit &h, bool plane_tmax 
     return true;
 }
 
+// ---- the box and ellipsoid emitters of hw4 and hw5 (hw4/src/include/distributions.h:115-180, hw5 :69-171) ------------------------
+// Templated on the figure type (Prim / rto5::Fig: type, data, position, rotation) and on the figure's ray test
+// ray(fig, o, d, Hit &) — prim_ray3(.., true) in hw4, fig_ray in hw5.  The light pdf's second-hit term stays with each snapshot.
+// The two samplers are rejection loops: kept out of line, as they were, because inlined into getColor they slow its recursion down
+// (hw5 render +10 %, profiles/r16_oracle_shared.txt).
 
-static inline V3 v3(const float *p) { return {p[0], p[1], p[2]}; }
+// BoxLight::pdfOne — hw4 :115-118, hw5 :69-71 (sTotal as the constructor computes it, hw5 :74-82)
+template <class Fig> static inline float box_emitter_pdf_one(const Fig &f, V3 x, V3 d, V3 y, V3 yn) {
+    float sx = f.data.x, sy = f.data.y, sz = f.data.z;
+    float sTotal = 8 * (sy * sz + sx * sz + sx * sy);
+    return (double)len2(x - y) / ((double)sTotal * std::fabs((double)dot(d, yn)));
+}
+// EllipsoidLight::pdfOne — hw4 :159-164, hw5 :150-155
+template <class Fig> static inline float ellipsoid_emitter_pdf_one(const Fig &f, V3 x, V3 d, V3 y, V3 yn) {
+    V3 r = f.data;
+    V3 n = qtransform(f.rotation, y - f.position) / r;
+    float pointProb = 1. / (double)(4 * PI * len(V3{n.x * r.y * r.z, r.x * n.y * r.z, r.x * r.y * n.z}));
+    return (double)(pointProb * len2(x - y)) / std::fabs((double)dot(d, yn));
+}
+// BoxLight::sample — hw4 :125-151, hw5 :84-105: face pick by area, sign flip, rejection until the figure is hit from x.
+template <class Fig, class Ray> static __attribute__((noinline)) V3 box_emitter_sample(const Fig &f, U01 &u01, rng_t &rng, V3 x, Ray &&ray) {
+    float sx = f.data.x, sy = f.data.y, sz = f.data.z;
+    float wx = sy * sz, wy = sx * sz, wz = sx * sy;
+    for (;;) {
+        float u = u01(rng) * (wx + wy + wz);
+        float flipSign = (double)u01(rng) > 0.5 ? 1 : -1;
+        // Vec3(a, b, c) is a constructor call: g++ evaluates its arguments right to left, so the LAST
+        // coordinate's random number is drawn first (pinned against the compiled reference).
+        V3 point;
+        if (u < wx) { float c = (2 * u01(rng) - 1) * sz; float b = (2 * u01(rng) - 1) * sy; point = V3{flipSign * sx, b, c}; }
+        else if (u < wx + wy) { float c = (2 * u01(rng) - 1) * sz; float a = (2 * u01(rng) - 1) * sx; point = V3{a, flipSign * sy, c}; }
+        else { float b = (2 * u01(rng) - 1) * sy; float a = (2 * u01(rng) - 1) * sx; point = V3{a, b, flipSign * sz}; }
+        V3 actual = qtransform(qconj(f.rotation), point) + f.position;
+        Hit h;
+        if (ray(f, x, normalize(actual - x), h)) return normalize(actual - x);
+    }
+}
+// EllipsoidLight::sample — hw4 :169-180 (one normal_distribution per light object), hw5 :160-171 (the pixel's): the caller's n01.
+template <class Fig, class Ray> static __attribute__((noinline)) V3 ellipsoid_emitter_sample(const Fig &f, N01 &n01, rng_t &rng, V3 x, Ray &&ray) {
+    for (;;) {
+        float a = n01(rng), b = n01(rng), c = n01(rng);
+        V3 point = f.data * normalize(V3{a, b, c});
+        V3 actual = qtransform(qconj(f.rotation), point) + f.position;
+        Hit h;
+        if (ray(f, x, normalize(actual - x), h)) return normalize(actual - x);
+    }
+}
+
 static inline Prim prim_from_abi(const rt_primitive &p) {
     Prim f;
     f.type = p.type; f.data = v3(p.data); f.position = v3(p.position);

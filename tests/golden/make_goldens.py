@@ -1,5 +1,6 @@
 """Regenerates tests/golden/pins_*.npz from the compiled reference (oracle/_ref, built where the reference's sources are).
-Run:  python tests/golden/make_goldens.py      (after `make -C oracle`)"""
+Run:  python tests/golden/make_goldens.py      (after `make -C oracle`)
+      python tests/golden/make_goldens.py orders      only pins_oracle_orders.npz, which comes from the oracle itself"""
 import ctypes as C
 import os
 import sys
@@ -120,6 +121,15 @@ def save_env_uv():
     print("env uv", d.shape)
 
 
+def save_oracle_orders():
+    """Figure order, light order and tree statistics the ORACLE's builder leaves on the cases of tests/test_oracle_orders.py.  A pin of
+    the oracle to itself: write it only from an oracle that passes tests/test_oracle_pins.py against the reference."""
+    import test_oracle_orders
+    out = {f"{case}/{k}": v for case in test_oracle_orders.CASES for k, v in test_oracle_orders.orders(case).items()}
+    np.savez_compressed(os.path.join(HERE, "pins_oracle_orders.npz"), **out)
+    print("oracle orders", {k: v.shape for k, v in out.items()})
+
+
 def save_function_inputs():
     """The soup case's queries, so that tests can tell the goldens still answer the questions pin_cases asks today."""
     out = pin_cases.function_inputs(pin_cases.random_triangle_scene(), 23)
@@ -143,4 +153,4 @@ def save_reference_crops():
 
 
 if __name__ == "__main__":
-    main()
+    save_oracle_orders() if sys.argv[1:] == ["orders"] else main()
