@@ -95,6 +95,12 @@ class rt_scene_info(C.Structure):
                 ("bvh_build_ms", C.c_double), ("bvh_on_device", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class rt_noise_summary(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("batches", C.c_int32), ("samples_observed", C.c_int32), ("samples_total", C.c_int32),
+                ("pixels", C.c_uint64), ("nonfinite_pixels", C.c_uint64), ("mean_luminance", C.c_double), ("rms_error", C.c_double),
+                ("noise", C.c_double), ("worst_tile_noise", C.c_double)]
+
+
 # Every symbol include/rtamd.h declares; tests/test_abi.py checks the library exports them all.
 ABI_SYMBOLS = ["rt_abi_version", "rt_last_error", "rt_scene_create", "rt_scene_destroy", "rt_output_elems", "rt_render",
                "rt_unshard", "rt_scene_get_info", "rt_scene_get_light_order", "rt_load_gltf", "rt_load_txt",
@@ -103,7 +109,9 @@ ABI_SYMBOLS = ["rt_abi_version", "rt_last_error", "rt_scene_create", "rt_scene_d
                "rt_multi_destroy", "rt_accum_create", "rt_accum_render", "rt_accum_samples", "rt_accum_resolve",
                "rt_accum_state_bytes", "rt_accum_save", "rt_accum_load", "rt_accum_destroy", "rt_multi_accum_create",
                "rt_multi_accum_render", "rt_multi_accum_samples", "rt_multi_accum_resolve", "rt_multi_accum_save",
-               "rt_multi_accum_load", "rt_multi_accum_destroy"]
+               "rt_multi_accum_load", "rt_multi_accum_destroy", "rt_noise_create", "rt_noise_update", "rt_noise_reset",
+               "rt_noise_batches", "rt_noise_estimate", "rt_noise_destroy", "rt_multi_noise_create", "rt_multi_noise_update",
+               "rt_multi_noise_reset", "rt_multi_noise_batches", "rt_multi_noise_estimate", "rt_multi_noise_destroy"]
 
 if not os.path.exists(LIB_PATH):
     raise ImportError(f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
@@ -153,6 +161,12 @@ lib.rt_multi_accum_save.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
 lib.rt_multi_accum_load.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
 lib.rt_multi_accum_destroy.argtypes = [C.c_void_p]
 lib.rt_multi_accum_destroy.restype = None
+for _family in ("rt_noise", "rt_multi_noise"):
+    getattr(lib, _family + "_create").argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
+    for _name in ("_update", "_reset", "_batches", "_destroy"):
+        getattr(lib, _family + _name).argtypes = [C.c_void_p]
+    getattr(lib, _family + "_estimate").argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(rt_noise_summary)]
+    getattr(lib, _family + "_destroy").restype = None
 
 
 def _check(code):
@@ -355,6 +369,74 @@ class MultiScene:
         return MultiAccumulator(self, width, height, **kw)
 
 
+class NoiseMonitor:
+    """Noise of a frame in progress (rt_noise on an Accumulator): update() after every render(n) makes those n samples one batch;
+    estimate() gives the per-pixel standard error of the picture's luminance and the figures of the frame.  It only reads the
+    accumulator; close it before the accumulator (Accumulator.close() does)."""
+    _family = "rt_noise"
+
+    def __init__(self, accumulator):
+        self.accumulator = accumulator  # keeps it alive: a monitor is destroyed before its accumulator
+        self._h = C.c_void_p()
+        _check(getattr(lib, self._family + "_create")(accumulator._h, C.byref(self._h)))
+        accumulator._monitors.add(self)
+
+    def close(self):
+        if self._h:
+            getattr(lib, self._family + "_destroy")(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def update(self):
+        _check(getattr(lib, self._family + "_update")(self._h))
+
+    def reset(self):
+        _check(getattr(lib, self._family + "_reset")(self._h))
+
+    @property
+    def batches(self):
+        return _check(getattr(lib, self._family + "_batches")(self._h))
+
+    def _map(self):
+        p = rt_render_params.from_buffer_copy(self.accumulator.params)
+        p.samples = 1
+        if p.shard_count <= 1:
+            return np.zeros((p.height, p.width), dtype=np.float32)
+        return np.zeros(lib.rt_output_elems(C.byref(p)) // 3, dtype=np.float32)
+
+    def estimate(self, want_map=True):
+        """(standard error per pixel as float32 or None, rt_noise_summary): the map is (H, W), or the compact shard tiles."""
+        se = self._map() if want_map else None
+        summary = rt_noise_summary()
+        summary.struct_size = C.sizeof(rt_noise_summary)
+        _check(getattr(lib, self._family + "_estimate")(self._h, 0, se.ctypes.data if want_map else None, C.byref(summary)))
+        return se, summary
+
+    def estimate_device(self, out_se_ptr):
+        """The map into device memory on the scene's GPU (a raw pointer, e.g. a torch tensor's data_ptr()); returns the summary."""
+        summary = rt_noise_summary()
+        summary.struct_size = C.sizeof(rt_noise_summary)
+        _check(getattr(lib, self._family + "_estimate")(self._h, RT_FLAG_OUT_DEVICE, out_se_ptr, C.byref(summary)))
+        return summary
+
+
+class MultiNoiseMonitor(NoiseMonitor):
+    """The same on a MultiAccumulator (rt_multi_noise): the map is the whole (H, W) frame, and the summary equals the unsharded
+    single-device monitor's of the same slicing in every field."""
+    _family = "rt_multi_noise"
+
+    def _map(self):
+        return np.zeros((self.accumulator.params.height, self.accumulator.params.width), dtype=np.float32)
+
+    def estimate_device(self, out_se_ptr):
+        raise RtError(RT_ERR_INVALID_ARG, "rt_multi_noise_estimate writes host memory only")
+
+
 class MultiAccumulator:
     """A frame in progress on every device of a MultiScene (rt_multi_accum), the counterpart of Accumulator: render(n) draws n more
     samples per pixel on all devices, resolve() is the whole picture so far, bit for bit Scene.render(width, height, samples);
@@ -366,10 +448,13 @@ class MultiAccumulator:
         if "shard_count" not in kw:
             self.params.shard_count, self.params.shard_index = 0, 0
         self._h = C.c_void_p()
+        self._monitors = weakref.WeakSet()
         _check(lib.rt_multi_accum_create(multi._h, C.byref(self.params), C.byref(self._h)))
         multi._accums.add(self)
 
     def close(self):
+        for m in list(self._monitors):  # an rt_multi_noise goes before its rt_multi_accum
+            m.close()
         if self._h:
             lib.rt_multi_accum_destroy(self._h)
             self._h = C.c_void_p()
@@ -407,6 +492,10 @@ class MultiAccumulator:
     def load(self, blob):
         _check(lib.rt_multi_accum_load(self._h, blob, len(blob)))
 
+    def noise_monitor(self):
+        """A MultiNoiseMonitor of this frame."""
+        return MultiNoiseMonitor(self)
+
 
 class Accumulator:
     """A frame in progress on a Scene (rt_accum): render(n) draws n more samples per pixel, resolve() is the picture so far,
@@ -416,10 +505,13 @@ class Accumulator:
         self.scene = scene  # keeps the scene alive: an rt_accum is destroyed before its scene
         self.params = make_params(width, height, 0, **kw)
         self._h = C.c_void_p()
+        self._monitors = weakref.WeakSet()
         _check(lib.rt_accum_create(scene._h, C.byref(self.params), C.byref(self._h)))
         scene._accums.add(self)
 
     def close(self):
+        for m in list(self._monitors):  # an rt_noise goes before its rt_accum
+            m.close()
         if self._h:
             lib.rt_accum_destroy(self._h)
             self._h = C.c_void_p()
@@ -459,6 +551,10 @@ class Accumulator:
 
     def load(self, blob):
         _check(lib.rt_accum_load(self._h, blob, len(blob)))
+
+    def noise_monitor(self):
+        """A NoiseMonitor of this frame."""
+        return NoiseMonitor(self)
 
 
 class Scene:

@@ -11,7 +11,13 @@
 // either way, so a frame begun on eight GPUs can be finished on one): RTAMD_SLICE=n renders in slices of n samples and rewrites the PPM
 // after every slice; RTAMD_CHECKPOINT=path carries on from that file when it exists and writes it after every slice (both files are
 // written under a temporary name and renamed, so a reader never sees half a file); RTAMD_SLICE_LIMIT=k stops after k slices.
+// Stopping at a noise target (rt_noise_* / rt_multi_noise_*, which only read the frame in progress): RTAMD_TARGET_NOISE=x renders in slices
+// (of RTAMD_SLICE samples, else a sixteenth of the samples asked for), prints the estimated noise of the picture (RMS error of its luminance
+// over its mean luminance) after every slice from the second on and ends the run at the first slice where it is at most x, once
+// RTAMD_NOISE_MIN_BATCHES slices (default 4, at least 2) have been observed: the file is then the plain run's at that many samples.
+// RTAMD_NOISE_MAP=path writes the last per-pixel standard error as a grayscale PFM ("Pf", little-endian, bottom row first as PFM has it).
 #include "../../../include/rtamd.h"
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -44,9 +50,37 @@ struct Progress {
     void destroy() { if (all) rt_multi_accum_destroy(all); else rt_accum_destroy(one); all = nullptr; one = nullptr; }
 };
 
+// The noise monitor of a frame in progress, on whichever of the two it is.
+struct Monitor {
+    rt_noise *one = nullptr;
+    rt_multi_noise *all = nullptr;
+    int create(Progress &acc) { return acc.all ? rt_multi_noise_create(acc.all, &all) : rt_noise_create(acc.one, &one); }
+    int update() { return all ? rt_multi_noise_update(all) : rt_noise_update(one); }
+    int batches() const { return all ? rt_multi_noise_batches(all) : rt_noise_batches(one); }
+    int estimate(float *se, rt_noise_summary *s) { return all ? rt_multi_noise_estimate(all, 0, se, s) : rt_noise_estimate(one, 0, se, s); }
+    void destroy() { if (all) rt_multi_noise_destroy(all); else if (one) rt_noise_destroy(one); all = nullptr; one = nullptr; }
+};
+struct NoiseTarget {
+    double target = 0;           // RTAMD_TARGET_NOISE, 0 = none
+    int min_batches = 4;         // RTAMD_NOISE_MIN_BATCHES
+    const char *map = nullptr;   // RTAMD_NOISE_MAP
+    bool active() const { return target > 0 || map; }
+};
+
+// The standard error per pixel as a grayscale PFM: "Pf", a negative scale = little-endian floats, rows from the bottom up.
+static bool write_noise_map(const char *path, int width, int height, const std::vector<float> &se) {
+    char head[64];
+    const int n = snprintf(head, sizeof head, "Pf\n%d %d\n-1.0\n", width, height);
+    std::vector<uint8_t> file((size_t)n + se.size() * sizeof(float));
+    memcpy(file.data(), head, (size_t)n);
+    for (int y = 0; y < height; y++) memcpy(file.data() + n + (size_t)y * width * sizeof(float), se.data() + (size_t)(height - 1 - y) * width, (size_t)width * sizeof(float));
+    return write_file_atomically(path, file.data(), file.size());
+}
+
 // The frame in slices: the picture after every slice is the frame of that many samples, the last one the frame of the plain run.
 // `p` are the params of the unsharded frame, whose rt_accum_state_bytes is the size of the checkpoint on any number of devices.
-static int render_in_slices(Progress &acc, const rt_render_params &p, int slice, const char *checkpoint, const char *out_path, std::vector<uint8_t> &rgb8) {
+// With a noise target the run ends at the first slice whose picture is quiet enough: that picture is the plain run's at that many samples.
+static int render_in_slices(Progress &acc, const rt_render_params &p, int slice, const char *checkpoint, const char *out_path, std::vector<uint8_t> &rgb8, const NoiseTarget &noise) {
     std::vector<uint8_t> blob(checkpoint ? rt_accum_state_bytes(&p) : 0);
     if (checkpoint) {
         if (FILE *f = fopen(checkpoint, "rb")) {
@@ -59,11 +93,27 @@ static int render_in_slices(Progress &acc, const rt_render_params &p, int slice,
             fprintf(stderr, "checkpoint: %s loaded, %d of %d samples done\n", checkpoint, acc.samples(), p.samples);
         }
     }
+    Monitor mon; // after the checkpoint: its batches start at the state that was loaded
+    if (noise.active() && mon.create(acc) != RT_OK) return die();
+    // the monitor goes before the frame it watches; with RTAMD_NOISE_MAP its last map is written first
+    auto end_monitor = [&]() -> int {
+        int rc = 0;
+        if (noise.map && mon.batches() >= 2) {
+            std::vector<float> se((size_t)p.width * p.height);
+            if (mon.estimate(se.data(), nullptr) != RT_OK) rc = die();
+            else if (!write_noise_map(noise.map, p.width, p.height, se)) { fprintf(stderr, "error: cannot write noise map %s\n", noise.map); rc = 1; }
+        } else if (noise.map) {
+            fprintf(stderr, "note: no noise map written: the estimate needs two slices of this run\n");
+        }
+        mon.destroy();
+        return rc;
+    };
     const int limit = getenv("RTAMD_SLICE_LIMIT") ? atoi(getenv("RTAMD_SLICE_LIMIT")) : 0;
     const std::string tmp_ppm = std::string(out_path) + ".part";
     double kernel_ms = 0;
     uint64_t samples = 0;
     uint32_t exact = 1;
+    bool converged = false;
     for (int k = 0;; k++) {
         const int done = acc.samples();
         if (k > 0 || done == p.samples) { // the picture so far (a checkpoint that already holds the frame just resolves)
@@ -71,17 +121,31 @@ static int render_in_slices(Progress &acc, const rt_render_params &p, int slice,
             if (rt_write_ppm(tmp_ppm.c_str(), p.width, p.height, rgb8.data()) != RT_OK) return die();
             if (rename(tmp_ppm.c_str(), out_path) != 0) { fprintf(stderr, "error: cannot rename %s to %s\n", tmp_ppm.c_str(), out_path); return 1; }
         }
-        if (done == p.samples) break;
+        if (converged) fprintf(stderr, "CONVERGED after %d slices at %d of %d samples\n", k, done, p.samples);
+        if (done == p.samples || converged) break;
         if (limit > 0 && k >= limit) {
             fprintf(stderr, "STOPPED after %d slices at %d of %d samples\n", k, done, p.samples);
+            const int rc = end_monitor();
             acc.destroy();
-            return -1;
+            return rc ? rc : -1;
         }
         const int n = slice > 0 && slice < p.samples - done ? slice : p.samples - done;
         rt_stats st;
         if (acc.render(n, &st) != RT_OK) return die();
         kernel_ms += st.kernel_ms; samples += st.samples; exact &= st.reference_exact;
-        fprintf(stderr, "slice %d: %d samples (%d of %d), %.3f ms on the GPU\n", k + 1, n, done + n, p.samples, st.kernel_ms);
+        fprintf(stderr, "slice %d: %d samples (%d of %d), %.3f ms on the GPU", k + 1, n, done + n, p.samples, st.kernel_ms);
+        if (noise.active()) {
+            if (mon.update() != RT_OK) { fprintf(stderr, "\n"); return die(); }
+            if (mon.batches() >= 2) {
+                rt_noise_summary ns;
+                memset(&ns, 0, sizeof ns);
+                ns.struct_size = sizeof ns;
+                if (mon.estimate(nullptr, &ns) != RT_OK) { fprintf(stderr, "\n"); return die(); }
+                fprintf(stderr, ", noise %.9g worst tile %.9g", ns.noise, ns.worst_tile_noise);
+                converged = noise.target > 0 && mon.batches() >= noise.min_batches && ns.noise <= noise.target;
+            }
+        }
+        fprintf(stderr, "\n");
         if (checkpoint) {
             if (acc.save(blob.data(), blob.size()) != RT_OK) return die();
             if (!write_file_atomically(checkpoint, blob.data(), blob.size())) { fprintf(stderr, "error: cannot write checkpoint %s\n", checkpoint); return 1; }
@@ -90,8 +154,9 @@ static int render_in_slices(Progress &acc, const rt_render_params &p, int slice,
     if (samples) fprintf(stderr, "render: %.3f ms on the GPU, %.2f Msamples/s\n", kernel_ms, samples / (kernel_ms * 1e3));
     if (samples && !exact)
         fprintf(stderr, "note: this render kept the answers of the walkers' padded boxes (no exactness gate on this path: see rt_stats.reference_exact in rtamd.h); about one pixel in 1e5 may differ from the reference's\n");
+    const int rc = end_monitor();
     acc.destroy();
-    return 0;
+    return rc;
 }
 
 int main(int argc, const char *argv[]) {
@@ -132,10 +197,21 @@ int main(int argc, const char *argv[]) {
     rt_stats st;
     int n_dev = rt_device_count();
     if (const char *e = getenv("RTAMD_DEVICES")) { int v = atoi(e); if (v >= 1 && v < n_dev) n_dev = v; }
-    const int slice = getenv("RTAMD_SLICE") ? atoi(getenv("RTAMD_SLICE")) : 0;
+    int slice = getenv("RTAMD_SLICE") ? atoi(getenv("RTAMD_SLICE")) : 0;
     const char *checkpoint = getenv("RTAMD_CHECKPOINT");
-    const bool sliced = argc >= 6 && (getenv("RTAMD_SLICE") || checkpoint);
+    NoiseTarget noise;
+    if (argc >= 6) {
+        if (const char *e = getenv("RTAMD_TARGET_NOISE")) {
+            char *end = nullptr;
+            noise.target = strtod(e, &end);
+            if (end == e || *end != 0 || !std::isfinite(noise.target) || !(noise.target > 0)) { fprintf(stderr, "error: RTAMD_TARGET_NOISE must be a positive finite number (got \"%s\")\n", e); return 1; }
+        }
+        if (const char *e = getenv("RTAMD_NOISE_MIN_BATCHES")) { noise.min_batches = atoi(e); if (noise.min_batches < 2) noise.min_batches = 2; }
+        noise.map = getenv("RTAMD_NOISE_MAP");
+    }
+    const bool sliced = argc >= 6 && (getenv("RTAMD_SLICE") || checkpoint || noise.active());
     if (sliced && slice <= 0 && getenv("RTAMD_SLICE")) { fprintf(stderr, "error: RTAMD_SLICE must be a positive number of samples\n"); return 1; }
+    if (noise.active() && !getenv("RTAMD_SLICE")) slice = p.samples / 16 > 1 ? p.samples / 16 : 1; // watching the noise implies slices
     std::vector<int> list; // RTAMD_DEVICE_LIST: the devices of rt_multi_create, as given
     if (const char *e = getenv("RTAMD_DEVICE_LIST")) {
         const int visible = rt_device_count();
@@ -158,7 +234,7 @@ int main(int argc, const char *argv[]) {
         if (sliced) {
             Progress acc;
             if (rt_multi_accum_create(multi, &p, &acc.all) != RT_OK) return die();
-            const int rc = render_in_slices(acc, p, slice, checkpoint, out_path, rgb8);
+            const int rc = render_in_slices(acc, p, slice, checkpoint, out_path, rgb8, noise);
             acc.destroy(); // before its rt_multi
             rt_multi_destroy(multi);
             rt_host_scene_free(hs);
@@ -174,7 +250,7 @@ int main(int argc, const char *argv[]) {
         if (sliced) {
             Progress acc;
             if (rt_accum_create(scene, &p, &acc.one) != RT_OK) return die();
-            const int rc = render_in_slices(acc, p, slice, checkpoint, out_path, rgb8);
+            const int rc = render_in_slices(acc, p, slice, checkpoint, out_path, rgb8, noise);
             acc.destroy(); // before its scene
             rt_scene_destroy(scene);
             rt_host_scene_free(hs);

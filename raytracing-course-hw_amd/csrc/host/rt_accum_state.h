@@ -1,9 +1,11 @@
-// struct rt_accum and the header of its checkpoint, shared by the two translation units that keep resumable state:
-// rtamd_api.hip (rt_accum_*: one frame or one shard on one device) and rtamd_multi.hip (rt_multi_accum_*: one sharded rt_accum
-// per device and the checkpoint of the whole frame, which is the unsharded rt_accum's blob byte for byte).
+// struct rt_accum, struct rt_multi_accum and the header of the checkpoint, shared by the translation units that keep or read resumable
+// state: rtamd_api.hip (rt_accum_*: one frame or one shard on one device), rtamd_multi.hip (rt_multi_accum_*: one sharded rt_accum
+// per device and the checkpoint of the whole frame, which is the unsharded rt_accum's blob byte for byte) and rtamd_noise.hip
+// (rt_noise_* / rt_multi_noise_*: the noise monitors, which only read the state between slices).
 #pragma once
 #include <cstring>
 #include <string>
+#include <vector>
 #include "rt_scene.h"
 
 #define ACCUM_MAGIC 0x43415452u   // "RTAC" read as a little-endian word
@@ -25,7 +27,25 @@ struct rt_accum {
     int32_t samples = 0;            // per pixel so far
     int32_t sample_limit = 0;       // the path records' sample index field (choose_pipeline)
     std::string broken;             // first error of a slice that failed under way: the state is half advanced
+    uint64_t loads = 0;             // how often rt_accum_load has replaced the state (a noise monitor's batches end there)
     ~rt_accum() { if (d_state) (void)hipFree(d_state); }
+};
+
+// One sharded rt_accum per device entry of an rt_multi (shard i of N on that entry's stream; none for an entry that gets no tile).
+// With one entry the rt_accum IS the unsharded one.
+struct rt_multi;
+struct rt_multi_accum {
+    rt_multi *multi = nullptr;
+    rt_render_params params{};       // of the unsharded frame, as given
+    int tile = 32;
+    rtamd::RenderView frame{};       // geometry of the unsharded frame: 8x8 tiles, shard 0 of 1
+    uint32_t frame_slots = 0;        // ceil(W/8) * ceil(H/8) * 64
+    std::vector<rt_accum *> shard;   // per device entry; null = an empty shard
+    std::vector<size_t> elems;       // floats (or bytes) of each shard's compact picture
+    int32_t samples = 0, sample_limit = 0;
+    std::string broken;              // first error of a call that failed under way on some device
+    uint64_t loads = 0;              // how often rt_multi_accum_load has replaced the shards' states
+    ~rt_multi_accum() { for (rt_accum *a : shard) if (a) rt_accum_destroy(a); }
 };
 
 // The 128-byte header of the checkpoint of a frame (or shard) of geometry `R` with `n_pixslots` pixel slots after `samples` samples.

@@ -1041,6 +1041,7 @@ int rt_accum_load(rt_accum *a, const void *blob, size_t size) {
     try {
         HIP_CHECK(hipSetDevice(a->scene->device));
         hipStream_t stream = (hipStream_t)a->params.stream;
+        a->loads++; // from here on the state is being replaced: the batches of a noise monitor end here
         if (state) HIP_CHECK(hipMemcpyAsync(a->d_state, (const uint8_t *)blob + ACCUM_HEADER_BYTES, state, hipMemcpyHostToDevice, stream));
         HIP_CHECK(hipStreamSynchronize(stream));
         a->samples = (int32_t)got[AH_SAMPLES];

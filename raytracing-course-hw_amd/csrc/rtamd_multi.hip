@@ -341,22 +341,9 @@ int rt_multi_render(rt_multi *m, const rt_render_params *params, float *out_rgb,
 }
 
 // ---- resumable renders on all devices (include/rtamd.h: rt_multi_accum_*) ---------------------------------------------------
-// One sharded rt_accum per device entry (shard i of N on that entry's stream; none for an entry that gets no tile), advanced side
+// One sharded rt_accum per device entry (struct rt_multi_accum, host/rt_accum_state.h), advanced side
 // by side; the picture goes through the exchange of rt_multi_render; the checkpoint is regrouped on device 0 into the frame order,
 // where it is the blob of the unsharded single-device rt_accum.  With one entry the rt_accum IS that unsharded one.
-struct rt_multi_accum {
-    rt_multi *multi = nullptr;
-    rt_render_params params{};       // of the unsharded frame, as given
-    int tile = 32;
-    rtamd::RenderView frame{};       // geometry of the unsharded frame: 8x8 tiles, shard 0 of 1
-    uint32_t frame_slots = 0;        // ceil(W/8) * ceil(H/8) * 64
-    std::vector<rt_accum *> shard;   // per device entry; null = an empty shard
-    std::vector<size_t> elems;       // floats (or bytes) of each shard's compact picture
-    int32_t samples = 0, sample_limit = 0;
-    std::string broken;              // first error of a call that failed under way on some device
-    ~rt_multi_accum() { for (rt_accum *a : shard) if (a) rt_accum_destroy(a); }
-};
-
 static Regroup regroup_of(const rt_multi_accum *a, int i) {
     Regroup G;
     G.tile = a->tile; G.tiles_x = (a->params.width + a->tile - 1) / a->tile; G.sub_w = a->frame.tiles_x; G.sub_h = a->frame.tiles_y;
@@ -545,6 +532,7 @@ int rt_multi_accum_load(rt_multi_accum *a, const void *blob, size_t size) {
         const int rc = rt_accum_load(a->shard[0], blob, size);
         if (rc != RT_OK) return fail(rc, std::string("rt_multi_accum_load: ") + rt_last_error());
         a->samples = (int32_t)got[AH_SAMPLES];
+        a->loads++;
         return RT_OK;
     }
     const int dev0 = m->dev[0].device;
@@ -554,6 +542,7 @@ int rt_multi_accum_load(rt_multi_accum *a, const void *blob, size_t size) {
     for (int i = 1; i < N; i++)
         if (a->shard[i]) { int r = grow(m->land_state[i], m->land_cap_state[i], (size_t)a->shard[i]->n_pixslots * (ACCUM_SLOT_BYTES / 4)); if (r != RT_OK) return r; }
     // from here on the devices' states are being overwritten: a failure leaves the object broken
+    a->loads++;
     hipError_t e = hipMemcpyAsync(m->frame_state, (const uint8_t *)blob + ACCUM_HEADER_BYTES, state, hipMemcpyHostToDevice, s0);
     for (int i = 0; i < N && e == hipSuccess; i++) {
         if (!a->shard[i]) continue;

@@ -4,6 +4,8 @@
 #   hw1/run.sh:2     ./run.sh <scene.txt> <out.ppm>
 # RTAMD_SNAPSHOT=hw1|hw3|hw6|hw8 picks which snapshot's integrator replays the scene (default hw8 / hw3).
 # RTAMD_SLICE=n / RTAMD_CHECKPOINT=path render the glTF surface in slices with a checkpoint, on every visible GPU;
+# RTAMD_TARGET_NOISE=x ends such a run at the first slice whose estimated noise is at most x (RTAMD_NOISE_MIN_BATCHES slices at least,
+# default 4; RTAMD_NOISE_MAP=path writes the per-pixel standard error as a PFM);
 # RTAMD_DEVICE_LIST=0,1,3 names the HIP devices to use (the environment goes through to build/main as it is).
 if [ $# -eq 2 ]
 then

@@ -2,10 +2,11 @@
 """Cost of rendering the headline frame (synth_room_v1, 1920x1080x256) in slices: wall time of the whole sequence, one resolve to the
 host per slice included, against the one-shot render of the same frame.
 
-usage: sliced_render.py [--workload NAME] [--repeats R] [--oneshot] [--slices N ...]
+usage: sliced_render.py [--workload NAME] [--repeats R] [--oneshot] [--slices N ...] [--monitor]
   --oneshot    time Scene.render (works with a library that has no rt_accum_*: point RTAMD_LIB at it, or run a copy of this script
                inside a checkout of the commit to compare with)
   --slices N   time an Accumulator advanced in slices of N samples (several N: one after the other)
+  --monitor    with a NoiseMonitor updated and estimated (summary only) after every slice; its share of the wall time is printed
 Every configuration is rendered once untimed first (allocations, code objects), then R times; all R times are printed."""
 import argparse
 import importlib
@@ -23,6 +24,7 @@ ap.add_argument("--workload", default="synth_room_v1_1920x1080x256", choices=sor
 ap.add_argument("--repeats", type=int, default=3)
 ap.add_argument("--oneshot", action="store_true")
 ap.add_argument("--slices", type=int, nargs="*", default=[])
+ap.add_argument("--monitor", action="store_true")
 a = ap.parse_args()
 rt = importlib.import_module("raytracing-course-hw_amd")
 import gen_synth_room
@@ -42,18 +44,27 @@ if a.oneshot:
 for n in a.slices:
     for rep in range(a.repeats + 1):
         acc = scene.accumulator(W, H)
-        per_slice, resolve_ms = [], 0.0
+        mon = acc.noise_monitor() if a.monitor else None
+        per_slice, resolve_ms, monitor_ms, noise = [], 0.0, 0.0, None
         t0 = time.perf_counter()
         while acc.samples < SPP:
             st = acc.render(min(n, SPP - acc.samples))
             per_slice.append(st.kernel_ms)
             t1 = time.perf_counter()
+            if mon:
+                mon.update()
+                if mon.batches >= 2:
+                    noise = mon.estimate(want_map=False)[1].noise
+                monitor_ms += (time.perf_counter() - t1) * 1e3
+                t1 = time.perf_counter()
             acc.resolve()
             resolve_ms += (time.perf_counter() - t1) * 1e3
         wall = (time.perf_counter() - t0) * 1e3
         acc.close()
         if rep:
-            print(f"slices of {n} run {rep}: wall {wall:.1f} ms ({len(per_slice)} slices, resolves {resolve_ms:.1f} ms of it), kernel_ms per slice: "
+            if mon:
+                print(f"slices of {n} run {rep}: monitor {monitor_ms:.2f} ms of the wall time ({monitor_ms / len(per_slice):.3f} ms per slice: one update, one estimate), last noise {noise!r}", flush=True)
+            print(f"slices of {n}{' monitored' if mon else ''} run {rep}: wall {wall:.1f} ms ({len(per_slice)} slices, resolves {resolve_ms:.1f} ms of it), kernel_ms per slice: "
                   + " ".join(f"{k:.1f}" for k in per_slice) + f" (sum {sum(per_slice):.1f}), {st.launches} launches per slice", flush=True)
     p = rt.make_params(W, H, 0)
     state = rt.lib.rt_accum_state_bytes(p)
