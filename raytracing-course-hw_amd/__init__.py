@@ -331,21 +331,22 @@ def unshard(params, buf):
     return full
 
 
-class MultiScene:
-    """One scene replica per listed HIP device (rt_multi); render() shards the frame over them and returns the whole frame."""
+class _Handle:
+    """One object of the library: `_h` is its handle, `_destroy` names the C function that frees it.  close() closes the children
+    first -- an rt_noise goes before its rt_accum, an rt_accum before its scene, and the same for the rt_multi_* family."""
+    _destroy = None
 
-    def __init__(self, data, devices):
-        self.data = data
+    def _open(self, parent=None):
         self._h = C.c_void_p()
-        self._accums = weakref.WeakSet()
-        arr = (C.c_int * len(devices))(*devices)
-        _check(lib.rt_multi_create(C.byref(data.desc), arr, len(devices), C.byref(self._h)))
+        self._children = weakref.WeakSet()
+        if parent is not None:
+            parent._children.add(self)
 
     def close(self):
-        for a in list(self._accums):  # an rt_multi_accum goes before its rt_multi
-            a.close()
+        for child in list(self._children):
+            child.close()
         if self._h:
-            lib.rt_multi_destroy(self._h)
+            getattr(lib, self._destroy)(self._h)
             self._h = C.c_void_p()
 
     def __del__(self):
@@ -353,6 +354,17 @@ class MultiScene:
             self.close()
         except Exception:
             pass
+
+
+class MultiScene(_Handle):
+    """One scene replica per listed HIP device (rt_multi); render() shards the frame over them and returns the whole frame."""
+    _destroy = "rt_multi_destroy"
+
+    def __init__(self, data, devices):
+        self.data = data
+        self._open()
+        arr = (C.c_int * len(devices))(*devices)
+        _check(lib.rt_multi_create(C.byref(data.desc), arr, len(devices), C.byref(self._h)))
 
     def render(self, width, height, samples, want_float=True, want_rgb8=True, **kw):
         p = make_params(width, height, samples, **kw)
@@ -369,28 +381,17 @@ class MultiScene:
         return MultiAccumulator(self, width, height, **kw)
 
 
-class NoiseMonitor:
+class NoiseMonitor(_Handle):
     """Noise of a frame in progress (rt_noise on an Accumulator): update() after every render(n) makes those n samples one batch;
     estimate() gives the per-pixel standard error of the picture's luminance and the figures of the frame.  It only reads the
     accumulator; close it before the accumulator (Accumulator.close() does)."""
     _family = "rt_noise"
+    _destroy = "rt_noise_destroy"
 
     def __init__(self, accumulator):
         self.accumulator = accumulator  # keeps it alive: a monitor is destroyed before its accumulator
-        self._h = C.c_void_p()
+        self._open(accumulator)
         _check(getattr(lib, self._family + "_create")(accumulator._h, C.byref(self._h)))
-        accumulator._monitors.add(self)
-
-    def close(self):
-        if self._h:
-            getattr(lib, self._family + "_destroy")(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def update(self):
         _check(getattr(lib, self._family + "_update")(self._h))
@@ -429,6 +430,7 @@ class MultiNoiseMonitor(NoiseMonitor):
     """The same on a MultiAccumulator (rt_multi_noise): the map is the whole (H, W) frame, and the summary equals the unsharded
     single-device monitor's of the same slicing in every field."""
     _family = "rt_multi_noise"
+    _destroy = "rt_multi_noise_destroy"
 
     def _map(self):
         return np.zeros((self.accumulator.params.height, self.accumulator.params.width), dtype=np.float32)
@@ -437,42 +439,53 @@ class MultiNoiseMonitor(NoiseMonitor):
         raise RtError(RT_ERR_INVALID_ARG, "rt_multi_noise_estimate writes host memory only")
 
 
-class MultiAccumulator:
-    """A frame in progress on every device of a MultiScene (rt_multi_accum), the counterpart of Accumulator: render(n) draws n more
-    samples per pixel on all devices, resolve() is the whole picture so far, bit for bit Scene.render(width, height, samples);
-    save() / load() exchange the portable checkpoint, byte for byte the blob of an unsharded Accumulator of the same frame."""
+class _AccumulatorBase(_Handle):
+    """What Accumulator (`_family` rt_accum, on a Scene) and MultiAccumulator (rt_multi_accum, on a MultiScene) share: the handle on
+    its parent, samples, render(n), load(blob) and the monitor."""
+    _family = None
+    _monitor = None
 
-    def __init__(self, multi, width, height, **kw):
-        self.multi = multi  # keeps the rt_multi alive: an rt_multi_accum is destroyed before it
-        self.params = make_params(width, height, 0, **kw)
-        if "shard_count" not in kw:
-            self.params.shard_count, self.params.shard_index = 0, 0
-        self._h = C.c_void_p()
-        self._monitors = weakref.WeakSet()
-        _check(lib.rt_multi_accum_create(multi._h, C.byref(self.params), C.byref(self._h)))
-        multi._accums.add(self)
-
-    def close(self):
-        for m in list(self._monitors):  # an rt_multi_noise goes before its rt_multi_accum
-            m.close()
-        if self._h:
-            lib.rt_multi_accum_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    def _create(self, parent, params):
+        self.params = params
+        self._open(parent)
+        _check(getattr(lib, self._family + "_create")(parent._h, C.byref(self.params), C.byref(self._h)))
 
     @property
     def samples(self):
-        return _check(lib.rt_multi_accum_samples(self._h))
+        return _check(getattr(lib, self._family + "_samples")(self._h))
 
     def render(self, n_samples):
         st = rt_stats()
-        _check(lib.rt_multi_accum_render(self._h, n_samples, C.byref(st)))
+        _check(getattr(lib, self._family + "_render")(self._h, n_samples, C.byref(st)))
         return st
+
+    def _save(self, params):
+        buf = C.create_string_buffer(lib.rt_accum_state_bytes(C.byref(params)))
+        _check(getattr(lib, self._family + "_save")(self._h, buf, len(buf)))
+        return buf.raw
+
+    def load(self, blob):
+        _check(getattr(lib, self._family + "_load")(self._h, blob, len(blob)))
+
+    def noise_monitor(self):
+        """A monitor of this frame: NoiseMonitor, or MultiNoiseMonitor on a MultiAccumulator."""
+        return self._monitor(self)
+
+
+class MultiAccumulator(_AccumulatorBase):
+    """A frame in progress on every device of a MultiScene (rt_multi_accum), the counterpart of Accumulator: render(n) draws n more
+    samples per pixel on all devices, resolve() is the whole picture so far, bit for bit Scene.render(width, height, samples);
+    save() / load() exchange the portable checkpoint, byte for byte the blob of an unsharded Accumulator of the same frame."""
+    _family = "rt_multi_accum"
+    _destroy = "rt_multi_accum_destroy"
+    _monitor = MultiNoiseMonitor
+
+    def __init__(self, multi, width, height, **kw):
+        self.multi = multi  # keeps the rt_multi alive: an rt_multi_accum is destroyed before it
+        params = make_params(width, height, 0, **kw)
+        if "shard_count" not in kw:
+            params.shard_count, params.shard_index = 0, 0
+        self._create(multi, params)
 
     def resolve(self, want_float=True, want_rgb8=True):
         """(rgb float32, rgb8) of the whole frame, (H, W, 3) each."""
@@ -485,51 +498,19 @@ class MultiAccumulator:
     def save(self):
         p = rt_render_params.from_buffer_copy(self.params)
         p.shard_count, p.shard_index = 0, 0   # the checkpoint is the unsharded frame's
-        buf = C.create_string_buffer(lib.rt_accum_state_bytes(C.byref(p)))
-        _check(lib.rt_multi_accum_save(self._h, buf, len(buf)))
-        return buf.raw
-
-    def load(self, blob):
-        _check(lib.rt_multi_accum_load(self._h, blob, len(blob)))
-
-    def noise_monitor(self):
-        """A MultiNoiseMonitor of this frame."""
-        return MultiNoiseMonitor(self)
+        return self._save(p)
 
 
-class Accumulator:
+class Accumulator(_AccumulatorBase):
     """A frame in progress on a Scene (rt_accum): render(n) draws n more samples per pixel, resolve() is the picture so far,
     bit for bit Scene.render(width, height, samples); save() / load() move the state through host memory."""
+    _family = "rt_accum"
+    _destroy = "rt_accum_destroy"
+    _monitor = NoiseMonitor
 
     def __init__(self, scene, width, height, **kw):
         self.scene = scene  # keeps the scene alive: an rt_accum is destroyed before its scene
-        self.params = make_params(width, height, 0, **kw)
-        self._h = C.c_void_p()
-        self._monitors = weakref.WeakSet()
-        _check(lib.rt_accum_create(scene._h, C.byref(self.params), C.byref(self._h)))
-        scene._accums.add(self)
-
-    def close(self):
-        for m in list(self._monitors):  # an rt_noise goes before its rt_accum
-            m.close()
-        if self._h:
-            lib.rt_accum_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    @property
-    def samples(self):
-        return _check(lib.rt_accum_samples(self._h))
-
-    def render(self, n_samples):
-        st = rt_stats()
-        _check(lib.rt_accum_render(self._h, n_samples, C.byref(st)))
-        return st
+        self._create(scene, make_params(width, height, 0, **kw))
 
     def resolve(self, want_float=True, want_rgb8=True):
         """(rgb float32, rgb8) in Scene.render's layout: (H, W, 3), or the compact shard buffers."""
@@ -545,41 +526,19 @@ class Accumulator:
         return rgb, rgb8
 
     def save(self):
-        buf = C.create_string_buffer(lib.rt_accum_state_bytes(C.byref(self.params)))
-        _check(lib.rt_accum_save(self._h, buf, len(buf)))
-        return buf.raw
-
-    def load(self, blob):
-        _check(lib.rt_accum_load(self._h, blob, len(blob)))
-
-    def noise_monitor(self):
-        """A NoiseMonitor of this frame."""
-        return NoiseMonitor(self)
+        return self._save(self.params)
 
 
-class Scene:
+class Scene(_Handle):
     """A prepared scene resident in HBM on the current HIP device (rt_scene)."""
+    _destroy = "rt_scene_destroy"
 
     def __init__(self, data, build_flags=0):
         self.data = data
-        self._h = C.c_void_p()
-        self._accums = weakref.WeakSet()
+        self._open()
         desc = rt_scene_desc.from_buffer_copy(data.desc)   # the arrays stay owned by `data`
         desc.build_flags = build_flags
         _check(lib.rt_scene_create(C.byref(desc), C.byref(self._h)))
-
-    def close(self):
-        for a in list(self._accums):  # an rt_accum goes before its scene
-            a.close()
-        if self._h:
-            lib.rt_scene_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def info(self):
         i = rt_scene_info()

@@ -228,35 +228,27 @@ int main(int argc, const char *argv[]) {
         }
         n_dev = (int)list.size();
     }
+    rt_multi *multi = nullptr; // all devices, or ...
+    rt_scene *scene = nullptr; // ... one
     if ((!list.empty() || n_dev > 1) && p.integrator != RT_INTEGRATOR_HW1) {
-        rt_multi *multi = nullptr;
         if (rt_multi_create(&desc, list.empty() ? nullptr : list.data(), n_dev, &multi) != RT_OK) return die();
-        if (sliced) {
-            Progress acc;
-            if (rt_multi_accum_create(multi, &p, &acc.all) != RT_OK) return die();
-            const int rc = render_in_slices(acc, p, slice, checkpoint, out_path, rgb8, noise);
-            acc.destroy(); // before its rt_multi
-            rt_multi_destroy(multi);
-            rt_host_scene_free(hs);
-            if (rc == 0) fprintf(stderr, "FINISH\n");
-            return rc < 0 ? 0 : rc; // < 0: stopped by RTAMD_SLICE_LIMIT, the checkpoint and the picture so far are written
-        }
+    } else if (rt_scene_create(&desc, &scene) != RT_OK) return die();
+    if (sliced) {
+        Progress acc;
+        if ((multi ? rt_multi_accum_create(multi, &p, &acc.all) : rt_accum_create(scene, &p, &acc.one)) != RT_OK) return die();
+        const int rc = render_in_slices(acc, p, slice, checkpoint, out_path, rgb8, noise);
+        acc.destroy(); // before its rt_multi or its scene
+        rt_multi_destroy(multi);
+        rt_scene_destroy(scene);
+        rt_host_scene_free(hs);
+        if (rc == 0) fprintf(stderr, "FINISH\n");
+        return rc < 0 ? 0 : rc; // < 0: stopped by RTAMD_SLICE_LIMIT, the checkpoint and the picture so far are written
+    }
+    if (multi) {
         if (rt_multi_render(multi, &p, nullptr, rgb8.data(), &st) != RT_OK) return die();
         fprintf(stderr, "render: %d GPUs, slowest %.3f ms, %.2f Msamples/s over the whole call\n", n_dev, st.kernel_ms, st.samples / (st.total_ms * 1e3));
         rt_multi_destroy(multi);
     } else {
-        rt_scene *scene = nullptr;
-        if (rt_scene_create(&desc, &scene) != RT_OK) return die();
-        if (sliced) {
-            Progress acc;
-            if (rt_accum_create(scene, &p, &acc.one) != RT_OK) return die();
-            const int rc = render_in_slices(acc, p, slice, checkpoint, out_path, rgb8, noise);
-            acc.destroy(); // before its scene
-            rt_scene_destroy(scene);
-            rt_host_scene_free(hs);
-            if (rc == 0) fprintf(stderr, "FINISH\n");
-            return rc < 0 ? 0 : rc; // < 0: stopped by RTAMD_SLICE_LIMIT, the checkpoint and the picture so far are written
-        }
         if (rt_render(scene, &p, nullptr, rgb8.data(), &st) != RT_OK) return die();
         fprintf(stderr, "render: %.3f ms on the GPU, %.2f Msamples/s\n", st.kernel_ms, st.samples / (st.kernel_ms * 1e3));
         if ((p.integrator == RT_INTEGRATOR_HW8 || p.integrator == RT_INTEGRATOR_HW7 || p.integrator == RT_INTEGRATOR_HW6) && !st.reference_exact)

@@ -62,6 +62,34 @@ static inline void accum_header(const rt_scene *scene, int integrator, const rta
 }
 static inline void accum_header(const rt_accum *a, uint32_t *h) { accum_header(a->scene, a->params.integrator, a->view, a->n_pixslots, a->samples, h); }
 
+// What a loader refuses in a blob of `size` bytes, before any state is replaced: `want` is the header of the frame that loads it, `state`
+// the bytes of state behind the header.  Returns the blob's sample count, or the rt_status with `who` in front of the message.
+static inline int accum_check_blob(const uint32_t *want, const void *blob, size_t size, int32_t sample_limit, size_t state, const std::string &who) {
+    if (size < ACCUM_HEADER_BYTES) return rtamd::fail(RT_ERR_INVALID_ARG, who + "truncated blob (shorter than its header)");
+    uint32_t got[ACCUM_HEADER_BYTES / 4];
+    memcpy(got, blob, ACCUM_HEADER_BYTES);
+    for (int f = 0; f < AH_WORDS; f++)
+        if (f != AH_SAMPLES && got[f] != want[f])
+            return rtamd::fail(RT_ERR_INVALID_ARG, who + "the blob does not belong to this frame: " + accum_field_names[f] + " is " + std::to_string(got[f]) +
+                                                       ", expected " + std::to_string(want[f]));
+    if (got[AH_SAMPLES] >= (uint32_t)sample_limit) return rtamd::fail(RT_ERR_INVALID_ARG, who + "samples beyond the path records' sample index");
+    if (size < ACCUM_HEADER_BYTES + state) return rtamd::fail(RT_ERR_INVALID_ARG, who + "truncated blob (" + std::to_string(size) + " bytes, " + std::to_string(ACCUM_HEADER_BYTES + state) + " expected)");
+    return (int)got[AH_SAMPLES];
+}
+
+// fn(i), an rt_status, on the calling thread for every device entry i of n that has a device (device_of(i) >= 0), with that device
+// current: entries 1 .. n-1 first and entry 0 last, so that device 0 is the current device again afterwards.  Stops at the first
+// status that is not RT_OK and returns it.  The parallel sibling is rtamd_multi.hip's fan_out.
+template <class DeviceOf, class Fn> static inline int each_device(size_t n, DeviceOf device_of, Fn fn) {
+    for (size_t k = 1; k <= n; k++) {
+        const size_t i = k % n;
+        if (device_of(i) < 0) continue;
+        HIP_CHECK(hipSetDevice(device_of(i)));
+        if (const int rc = fn(i)) return rc;
+    }
+    return RT_OK;
+}
+
 namespace rtamd {
 // What rt_accum_render refuses before it launches anything (a broken state, n_samples, the sample-index limit, a pipeline without
 // resumable state); RT_OK = the slice would be launched.  Host only; `who` prefixes the message.

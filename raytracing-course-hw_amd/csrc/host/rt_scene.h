@@ -11,18 +11,10 @@
 #include "../device/rt_types_hw6.h"
 #include "../device/rt_types_txt.h"
 #include "../device/rt_types_wf.h"
-#include "hip_check.h"
+#include "rt_guard.h"
 
 namespace rtamd {
-
-void set_error(const std::string &msg); // what rt_last_error returns on this thread (rtamd_scene.hip)
-
 namespace { // internal linkage: the library exports none of these helpers
-
-inline int fail(int code, const std::string &msg) {
-    set_error(msg);
-    return code;
-}
 
 inline double now_ms() {
     return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
@@ -35,8 +27,36 @@ struct OwnedDev {
     explicit OwnedDev(void *q) : p(q) {}
     OwnedDev(const OwnedDev &) = delete;
     OwnedDev &operator=(const OwnedDev &) = delete;
+    OwnedDev(OwnedDev &&o) : p(o.release()) {}
     ~OwnedDev() { if (p) (void)hipFree(p); }
     void *release() { void *q = p; p = nullptr; return q; }
+};
+
+// A device buffer that a call needs `need` bytes of: kept when it is large enough, else freed and allocated anew.
+template <class T> void grow(T *&p, size_t &have, size_t need) {
+    if (have >= need) return;
+    if (p) (void)hipFree(p);
+    p = nullptr; have = 0;
+    HIP_CHECK(hipMalloc((void **)&p, need));
+    have = need;
+}
+
+// An output of `elems` elements that the caller wants at `out`: device memory with RT_FLAG_OUT_DEVICE, which the kernel then writes
+// itself, else host memory, which gets a device buffer of this call (dev), the copy back queued by copy_back(), freed on every way out.
+struct StagedOut {
+    void *dev;          // what the kernel writes; null = no such output
+    void *host = nullptr;
+    size_t bytes = 0;
+    OwnedDev buf;
+    StagedOut(void *out, uint32_t flags, size_t elems, size_t elem_size) : dev(out) {
+        if (!out || (flags & RT_FLAG_OUT_DEVICE)) return;
+        dev = nullptr;
+        if (!elems) return;
+        bytes = elems * elem_size;
+        HIP_CHECK(hipMalloc(&buf.p, bytes));
+        host = out; dev = buf.p;
+    }
+    void copy_back(hipStream_t stream) const { if (buf.p) HIP_CHECK(hipMemcpyAsync(host, buf.p, bytes, hipMemcpyDeviceToHost, stream)); }
 };
 
 template <class T> T *upload(const std::vector<T> &v, uint64_t &bytes) {

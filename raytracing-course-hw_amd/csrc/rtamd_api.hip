@@ -33,20 +33,14 @@ int rt_abi_version(void) { return RTAMD_ABI_VERSION; }
 
 size_t rt_output_elems(const rt_render_params *p) {
     if (!p) return 0;
-    RenderView R{};
-    std::string err;
-    if (!resolve_tiles(p, R, err)) return 0;
-    if (R.shard_count > 1) return (size_t)R.n_shard_tiles * R.tile_w * R.tile_h * 3;
-    return (size_t)R.width * R.height * 3;
-}
-
-// A buffer of the scene that a render needs `need` bytes of: kept when it is large enough, else freed and allocated anew.
-static void grow(void **p, size_t &have, size_t need) {
-    if (have >= need) return;
-    if (*p) (void)hipFree(*p);
-    *p = nullptr; have = 0;
-    HIP_CHECK(hipMalloc(p, need));
-    have = need;
+    size_t elems = 0; // what a refusal answers, without a message
+    guarded("rt_output_elems: ", [&]() -> int {
+        RenderView R{};
+        std::string err;
+        if (resolve_tiles(p, R, err)) elems = R.shard_count > 1 ? (size_t)R.n_shard_tiles * R.tile_w * R.tile_h * 3 : (size_t)R.width * R.height * 3;
+        return RT_OK;
+    });
+    return elems;
 }
 
 // Rounds a pixel needs per camera sample: one per bounce; without the deepest-level shortcut the last bounce's pdf / clamp
@@ -382,8 +376,8 @@ static void launch_persistent(rt_scene *scene, const PersistentKernel &k, const 
     uint32_t group_shift = (uint64_t)pass_groups < 16ull * n_blocks_max ? 4u : 6u;
     if (const int v = env_int("RTAMD_PT_GROUP_SHIFT", 0); v == 4 || v == 5 || v == 6) group_shift = (uint32_t)v;
     const uint32_t sub = 6u - group_shift, groups_per_block = k.max_paths >> group_shift;
-    grow(&scene->pt_records, scene->pt_record_bytes, (size_t)pass_groups * 64 * k.record_bytes);
-    grow((void **)&scene->pt_groups, scene->pt_group_bytes, (2 * ((size_t)pass_groups << sub) + n_blocks_max + 1) * 4);
+    grow(scene->pt_records, scene->pt_record_bytes, (size_t)pass_groups * 64 * k.record_bytes);
+    grow(scene->pt_groups, scene->pt_group_bytes, (2 * ((size_t)pass_groups << sub) + n_blocks_max + 1) * 4);
     uint32_t *d_cost = scene->pt_groups, *d_ofs = d_cost + ((size_t)pass_groups << sub), *d_ids = d_ofs + n_blocks_max + 1;
     dev::PtParams P{};
     const int leaf_share = env_positive("RTAMD_WF_LEAF_SHARE_256", 112) & 0x7fff;
@@ -694,7 +688,7 @@ static void launch_frame(rt_scene *scene, const rt_render_params *p, Frame &F, h
             R.rr_depth = (p->flags & RT_FLAG_RUSSIAN_ROULETTE) ? 2 : 0;
             R.samples /= streams;                           // per stream; inv_samples stays 1 / (all samples of the pixel)
             R.sample_stop = R.samples;
-            grow((void **)&scene->d_partial, scene->partial_bytes, (size_t)streams * R.n_pixslots * 3 * sizeof(float));
+            grow(scene->d_partial, scene->partial_bytes, (size_t)streams * R.n_pixslots * 3 * sizeof(float));
             R.partial = scene->d_partial;
         }
         const uint32_t n_slot_groups = n_work * (uint32_t)streams; // 64-slot groups of all streams
@@ -844,27 +838,20 @@ static int collect_frame(rt_scene *scene, const Frame &F, hipStream_t stream, rt
 // rt_render, and with `slice` rt_accum_render: the same checks, pipelines, launches and statistics.
 static int render_frame(rt_scene *scene, const rt_render_params *p, float *out_rgb, uint8_t *out_rgb8, rt_stats *stats, const AccumSlice *slice) {
     const std::string who = slice ? "rt_accum_render: " : "rt_render: ";
-    Frame F;
-    if (const int rc = check_frame(scene, p, slice, who, F)) return rc;
-    const double t0 = now_ms();
-    OwnedDev rgb_buf, rgb8_buf; // host-output renders: freed on every way out
-    try {
+    return guarded(who, [&]() -> int {
+        Frame F;
+        if (const int rc = check_frame(scene, p, slice, who, F)) return rc;
+        const double t0 = now_ms();
         HIP_CHECK(hipSetDevice(scene->device));
         hipStream_t stream = (hipStream_t)p->stream;
-        const bool out_dev = (p->flags & RT_FLAG_OUT_DEVICE) != 0;
         const size_t elems = rt_output_elems(p);
-        F.R.out_rgb = out_rgb; F.R.out_rgb8 = out_rgb8;
-        if (out_rgb && !out_dev) { HIP_CHECK(hipMalloc(&rgb_buf.p, elems * sizeof(float))); F.R.out_rgb = (float *)rgb_buf.p; }
-        if (out_rgb8 && !out_dev) { HIP_CHECK(hipMalloc(&rgb8_buf.p, elems)); F.R.out_rgb8 = (uint8_t *)rgb8_buf.p; }
+        StagedOut rgb(out_rgb, p->flags, elems, sizeof(float)), rgb8(out_rgb8, p->flags, elems, 1);
+        F.R.out_rgb = (float *)rgb.dev; F.R.out_rgb8 = (uint8_t *)rgb8.dev;
         launch_frame(scene, p, F, stream, stats != nullptr);
-        if (rgb_buf.p) HIP_CHECK(hipMemcpyAsync(out_rgb, rgb_buf.p, elems * sizeof(float), hipMemcpyDeviceToHost, stream));
-        if (rgb8_buf.p) HIP_CHECK(hipMemcpyAsync(out_rgb8, rgb8_buf.p, elems, hipMemcpyDeviceToHost, stream));
+        rgb.copy_back(stream);
+        rgb8.copy_back(stream);
         return collect_frame(scene, F, stream, stats, t0, who);
-    } catch (const HipError &e) {
-        return fail(RT_ERR_HIP, e.what());
-    } catch (const std::exception &e) { // e.g. std::bad_alloc from the host-side vectors: nothing crosses the C boundary
-        return fail(RT_ERR_INVALID_ARG, who + e.what());
-    }
+    });
 }
 
 int rt_render(rt_scene *scene, const rt_render_params *p, float *out_rgb, uint8_t *out_rgb8, rt_stats *stats) {
@@ -893,16 +880,22 @@ static bool accum_geometry(const rt_render_params *p, RenderView &R, uint32_t &n
 }
 
 size_t rt_accum_state_bytes(const rt_render_params *p) {
-    RenderView R{};
-    uint32_t n = 0;
-    std::string err;
-    if (!accum_geometry(p, R, n, err)) { set_error("rt_accum_state_bytes: " + err); return 0; }
-    return (size_t)ACCUM_HEADER_BYTES + (size_t)n * ACCUM_SLOT_BYTES;
+    size_t bytes = 0; // what a refusal answers
+    guarded("rt_accum_state_bytes: ", [&]() -> int {
+        RenderView R{};
+        uint32_t n = 0;
+        std::string err;
+        if (!accum_geometry(p, R, n, err)) return fail(RT_ERR_INVALID_ARG, "rt_accum_state_bytes: " + err);
+        bytes = (size_t)ACCUM_HEADER_BYTES + (size_t)n * ACCUM_SLOT_BYTES;
+        return RT_OK;
+    });
+    return bytes;
 }
 
 int rt_accum_create(rt_scene *scene, const rt_render_params *p, rt_accum **out) {
     if (!scene || !p || !out) return fail(RT_ERR_INVALID_ARG, "rt_accum_create: null argument");
     *out = nullptr;
+    return guarded("rt_accum_create: ", [&]() -> int {
     if (p->struct_size == sizeof(rt_render_params)) {
         if (p->sample_streams > 1) return fail(RT_ERR_UNSUPPORTED, std::string("rt_accum_create: ") + accum_unsupported(Pipeline::Persistent8, p));
         if (p->integrator >= RT_INTEGRATOR_HW1 && p->integrator <= RT_INTEGRATOR_HW5) return fail(RT_ERR_UNSUPPORTED, std::string("rt_accum_create: ") + accum_unsupported(Pipeline::Hw1, p));
@@ -919,22 +912,19 @@ int rt_accum_create(rt_scene *scene, const rt_render_params *p, rt_accum **out) 
     if (const char *why = accum_unsupported(pipe, p)) return fail(RT_ERR_UNSUPPORTED, std::string("rt_accum_create: ") + why);
     a->scene = scene; a->params = *p; a->params.samples = 0;
     a->sample_limit = pipe == Pipeline::Persistent6 ? 1 << 24 : 1 << 25; // sample index bits of p6_pack / wf_pack
-    try {
-        HIP_CHECK(hipSetDevice(scene->device));
-        hipStream_t stream = (hipStream_t)p->stream;
-        HIP_CHECK(hipMalloc((void **)&a->d_state, (size_t)(a->n_pixslots ? a->n_pixslots : 1u) * ACCUM_SLOT_BYTES));
-        if (a->n_pixslots) {
-            RenderView R = a->view;
-            R.accum = a->d_state; R.n_pixslots = a->n_pixslots;
-            hipLaunchKernelGGL(dev::accum_seed_kernel, dim3((a->n_pixslots + 255u) / 256u), dim3(256), 0, stream, R);
-            HIP_CHECK(hipGetLastError());
-            HIP_CHECK(hipStreamSynchronize(stream));
-        }
-    } catch (const HipError &e) {
-        return fail(RT_ERR_HIP, e.what());
+    HIP_CHECK(hipSetDevice(scene->device));
+    hipStream_t stream = (hipStream_t)p->stream;
+    HIP_CHECK(hipMalloc((void **)&a->d_state, (size_t)(a->n_pixslots ? a->n_pixslots : 1u) * ACCUM_SLOT_BYTES));
+    if (a->n_pixslots) {
+        RenderView R = a->view;
+        R.accum = a->d_state; R.n_pixslots = a->n_pixslots;
+        hipLaunchKernelGGL(dev::accum_seed_kernel, dim3((a->n_pixslots + 255u) / 256u), dim3(256), 0, stream, R);
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipStreamSynchronize(stream));
     }
     *out = a.release();
     return RT_OK;
+    });
 }
 
 void rt_accum_destroy(rt_accum *a) {
@@ -964,31 +954,30 @@ int rtamd::accum_check_slice(const rt_accum *a, int32_t n_samples, const std::st
 }
 
 int rt_accum_render(rt_accum *a, int32_t n_samples, rt_stats *stats) {
-    if (const int rc = accum_check_slice(a, n_samples, "rt_accum_render: ")) return rc;
-    rt_render_params p = a->params;
-    p.samples = n_samples;
-    const AccumSlice slice{a->d_state, a->samples};
-    const int rc = render_frame(a->scene, &p, nullptr, nullptr, stats, &slice);
-    if (rc != RT_OK) { a->broken = rt_last_error(); return rc; }
-    a->samples += n_samples;
-    return RT_OK;
+    return guarded("rt_accum_render: ", [&]() -> int {
+        if (const int rc = accum_check_slice(a, n_samples, "rt_accum_render: ")) return rc;
+        rt_render_params p = a->params;
+        p.samples = n_samples;
+        const AccumSlice slice{a->d_state, a->samples};
+        const int rc = render_frame(a->scene, &p, nullptr, nullptr, stats, &slice);
+        if (rc != RT_OK) { a->broken = rt_last_error(); return rc; } // the slice failed under way: the state is half advanced
+        a->samples += n_samples;
+        return RT_OK;
+    });
 }
 
 int rt_accum_resolve(rt_accum *a, uint32_t flags, float *out_rgb, uint8_t *out_rgb8) {
     if (!a) return fail(RT_ERR_INVALID_ARG, "rt_accum_resolve: null argument");
-    if (!a->broken.empty()) return fail(RT_ERR_INVALID_ARG, "rt_accum_resolve: an earlier slice failed and left the state half advanced (" + a->broken + ")");
-    if (flags & ~RT_FLAG_OUT_DEVICE) return fail(RT_ERR_INVALID_ARG, "rt_accum_resolve: flags other than RT_FLAG_OUT_DEVICE");
-    if (a->samples <= 0) return fail(RT_ERR_INVALID_ARG, "rt_accum_resolve: no samples yet (a picture needs at least one)");
-    OwnedDev rgb_buf, rgb8_buf;
-    try {
+    return guarded("rt_accum_resolve: ", [&]() -> int {
+        if (!a->broken.empty()) return fail(RT_ERR_INVALID_ARG, "rt_accum_resolve: an earlier slice failed and left the state half advanced (" + a->broken + ")");
+        if (flags & ~RT_FLAG_OUT_DEVICE) return fail(RT_ERR_INVALID_ARG, "rt_accum_resolve: flags other than RT_FLAG_OUT_DEVICE");
+        if (a->samples <= 0) return fail(RT_ERR_INVALID_ARG, "rt_accum_resolve: no samples yet (a picture needs at least one)");
         HIP_CHECK(hipSetDevice(a->scene->device));
         hipStream_t stream = (hipStream_t)a->params.stream;
-        const bool out_dev = (flags & RT_FLAG_OUT_DEVICE) != 0;
         RenderView R = a->view;
         const size_t elems = R.shard_count > 1 ? (size_t)R.n_shard_tiles * R.tile_w * R.tile_h * 3 : (size_t)R.width * R.height * 3;
-        R.out_rgb = out_rgb; R.out_rgb8 = out_rgb8;
-        if (out_rgb && !out_dev) { HIP_CHECK(hipMalloc(&rgb_buf.p, elems * sizeof(float))); R.out_rgb = (float *)rgb_buf.p; }
-        if (out_rgb8 && !out_dev) { HIP_CHECK(hipMalloc(&rgb8_buf.p, elems)); R.out_rgb8 = (uint8_t *)rgb8_buf.p; }
+        StagedOut rgb(out_rgb, flags, elems, sizeof(float)), rgb8(out_rgb8, flags, elems, 1);
+        R.out_rgb = (float *)rgb.dev; R.out_rgb8 = (uint8_t *)rgb8.dev;
         R.accum = a->d_state; R.n_pixslots = a->n_pixslots;
         R.samples = a->samples;
         R.inv_samples = (float)(1.0 / a->samples); // scene.cpp:176, as rt_render(samples = d) evaluates it
@@ -996,21 +985,19 @@ int rt_accum_resolve(rt_accum *a, uint32_t flags, float *out_rgb, uint8_t *out_r
             hipLaunchKernelGGL(dev::accum_resolve_kernel, dim3((a->n_pixslots + 255u) / 256u), dim3(256), 0, stream, R);
             HIP_CHECK(hipGetLastError());
         }
-        if (rgb_buf.p) HIP_CHECK(hipMemcpyAsync(out_rgb, rgb_buf.p, elems * sizeof(float), hipMemcpyDeviceToHost, stream));
-        if (rgb8_buf.p) HIP_CHECK(hipMemcpyAsync(out_rgb8, rgb8_buf.p, elems, hipMemcpyDeviceToHost, stream));
+        rgb.copy_back(stream);
+        rgb8.copy_back(stream);
         HIP_CHECK(hipStreamSynchronize(stream));
         return RT_OK;
-    } catch (const HipError &e) {
-        return fail(RT_ERR_HIP, e.what());
-    }
+    });
 }
 
 int rt_accum_save(rt_accum *a, void *blob, size_t capacity) {
     if (!a || !blob) return fail(RT_ERR_INVALID_ARG, "rt_accum_save: null argument");
-    if (!a->broken.empty()) return fail(RT_ERR_INVALID_ARG, "rt_accum_save: an earlier slice failed and left the state half advanced (" + a->broken + ")");
-    const size_t state = (size_t)a->n_pixslots * ACCUM_SLOT_BYTES;
-    if (capacity < ACCUM_HEADER_BYTES + state) return fail(RT_ERR_INVALID_ARG, "rt_accum_save: buffer smaller than rt_accum_state_bytes");
-    try {
+    return guarded("rt_accum_save: ", [&]() -> int {
+        if (!a->broken.empty()) return fail(RT_ERR_INVALID_ARG, "rt_accum_save: an earlier slice failed and left the state half advanced (" + a->broken + ")");
+        const size_t state = (size_t)a->n_pixslots * ACCUM_SLOT_BYTES;
+        if (capacity < ACCUM_HEADER_BYTES + state) return fail(RT_ERR_INVALID_ARG, "rt_accum_save: buffer smaller than rt_accum_state_bytes");
         HIP_CHECK(hipSetDevice(a->scene->device));
         hipStream_t stream = (hipStream_t)a->params.stream;
         uint32_t h[ACCUM_HEADER_BYTES / 4];
@@ -1019,36 +1006,26 @@ int rt_accum_save(rt_accum *a, void *blob, size_t capacity) {
         if (state) HIP_CHECK(hipMemcpyAsync((uint8_t *)blob + ACCUM_HEADER_BYTES, a->d_state, state, hipMemcpyDeviceToHost, stream));
         HIP_CHECK(hipStreamSynchronize(stream));
         return RT_OK;
-    } catch (const HipError &e) {
-        return fail(RT_ERR_HIP, e.what());
-    }
+    });
 }
 
 int rt_accum_load(rt_accum *a, const void *blob, size_t size) {
     if (!a || !blob) return fail(RT_ERR_INVALID_ARG, "rt_accum_load: null argument");
-    if (!a->broken.empty()) return fail(RT_ERR_INVALID_ARG, "rt_accum_load: an earlier slice failed and left the state half advanced (" + a->broken + ")");
-    if (size < ACCUM_HEADER_BYTES) return fail(RT_ERR_INVALID_ARG, "rt_accum_load: truncated blob (shorter than its header)");
-    uint32_t want[ACCUM_HEADER_BYTES / 4], got[ACCUM_HEADER_BYTES / 4];
-    accum_header(a, want);
-    memcpy(got, blob, ACCUM_HEADER_BYTES);
-    for (int f = 0; f < AH_WORDS; f++)
-        if (f != AH_SAMPLES && got[f] != want[f])
-            return fail(RT_ERR_INVALID_ARG, std::string("rt_accum_load: the blob does not belong to this frame: ") + accum_field_names[f] + " is " + std::to_string(got[f]) +
-                                                ", expected " + std::to_string(want[f]));
-    if (got[AH_SAMPLES] >= (uint32_t)a->sample_limit) return fail(RT_ERR_INVALID_ARG, "rt_accum_load: samples beyond the path records' sample index");
-    const size_t state = (size_t)a->n_pixslots * ACCUM_SLOT_BYTES;
-    if (size < ACCUM_HEADER_BYTES + state) return fail(RT_ERR_INVALID_ARG, "rt_accum_load: truncated blob (" + std::to_string(size) + " bytes, " + std::to_string(ACCUM_HEADER_BYTES + state) + " expected)");
-    try {
+    return guarded("rt_accum_load: ", [&]() -> int {
+        if (!a->broken.empty()) return fail(RT_ERR_INVALID_ARG, "rt_accum_load: an earlier slice failed and left the state half advanced (" + a->broken + ")");
+        uint32_t want[ACCUM_HEADER_BYTES / 4];
+        accum_header(a, want);
+        const size_t state = (size_t)a->n_pixslots * ACCUM_SLOT_BYTES;
+        const int samples = accum_check_blob(want, blob, size, a->sample_limit, state, "rt_accum_load: ");
+        if (samples < 0) return samples;
         HIP_CHECK(hipSetDevice(a->scene->device));
         hipStream_t stream = (hipStream_t)a->params.stream;
         a->loads++; // from here on the state is being replaced: the batches of a noise monitor end here
         if (state) HIP_CHECK(hipMemcpyAsync(a->d_state, (const uint8_t *)blob + ACCUM_HEADER_BYTES, state, hipMemcpyHostToDevice, stream));
         HIP_CHECK(hipStreamSynchronize(stream));
-        a->samples = (int32_t)got[AH_SAMPLES];
+        a->samples = samples;
         return RT_OK;
-    } catch (const HipError &e) {
-        return fail(RT_ERR_HIP, e.what());
-    }
+    });
 }
 
 } // extern "C"

@@ -10,7 +10,6 @@
 // Resumable renders on the same devices (rt_multi_accum_*, second half of this file): one sharded rt_accum per device, the picture through
 // the same exchange, and a checkpoint regrouped on device 0 into the unsharded rt_accum's own blob.
 #include <hip/hip_runtime.h>
-#include <chrono>
 #include <cstring>
 #include <memory>
 #include <string>
@@ -21,10 +20,9 @@
 #include "host/rt_accum_state.h"
 #include "host/shared_prep.h"
 
-namespace {
+using namespace rtamd;
 
-int fail(int code, const std::string &msg) { rtamd::set_error(msg); return code; }
-double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+namespace {
 
 // shard `shard` of `count` holds the tiles shard, shard + count, ... in order (layout of rt_render_params); one thread per element
 template <class T>
@@ -84,7 +82,7 @@ struct DeviceSlot {
     hipStream_t stream = nullptr;
     float *d_rgb = nullptr;       // this device's shard, float
     uint8_t *d_rgb8 = nullptr;    // this device's shard, u8
-    size_t cap_rgb = 0, cap_rgb8 = 0;
+    size_t cap_rgb = 0, cap_rgb8 = 0; // bytes (grow)
     hipEvent_t done = nullptr;    // recorded on `stream` after this device's shard has landed on device 0
 };
 
@@ -127,18 +125,29 @@ struct rt_multi {
     }
 };
 
-#define MHIP(expr)                                                                                                  \
-    do {                                                                                                            \
-        hipError_t e_ = (expr);                                                                                     \
-        if (e_ != hipSuccess) return fail(RT_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));           \
-    } while (0)
-
-template <class T> static int grow(T *&p, size_t &cap, size_t elems) {
-    if (cap >= elems) return RT_OK;
-    if (p) (void)hipFree(p);
-    p = nullptr; cap = 0;
-    MHIP(hipMalloc((void **)&p, elems * sizeof(T)));
-    cap = elems;
+// fn(i), an rt_status with its message in rt_last_error, for every device entry i of n that has a device (device_of(i) >= 0), each on
+// its own host thread with that device current; all threads are joined on every way out.  Returns the first failure in entry order:
+// its status, and `who` + "device N: " + its message.  The serial sibling is each_device (host/rt_accum_state.h).
+template <class DeviceOf, class Fn> static int fan_out(const std::string &who, int n, DeviceOf device_of, Fn fn) {
+    std::vector<int> rc((size_t)n, RT_OK);
+    std::vector<std::string> err((size_t)n);
+    {
+        Threads threads;
+        for (int i = 0; i < n; i++)
+            if (device_of(i) >= 0)
+                threads.th.emplace_back([&, i] {
+                    rc[i] = guarded("", [&]() -> int { // nothing leaves a thread either; the outer guard is for the copy of the message
+                        const int r = guarded("", [&]() -> int {
+                            if (hipSetDevice(device_of(i)) != hipSuccess) return fail(RT_ERR_HIP, "hipSetDevice failed");
+                            return fn(i);
+                        });
+                        if (r != RT_OK) err[i] = rt_last_error();
+                        return r;
+                    });
+                });
+    }
+    for (int i = 0; i < n; i++)
+        if (rc[i] != RT_OK) return fail(rc[i], who + "device " + std::to_string(device_of(i)) + ": " + err[i]);
     return RT_OK;
 }
 
@@ -153,47 +162,39 @@ static int exchange_frame(rt_multi *m, const std::string &who, int width, int he
     const int N = (int)m->dev.size();
     // landing areas on device 0 and the frame, before any thread starts (allocations on device 0 from this thread only)
     const int dev0 = m->dev[0].device;
-    MHIP(hipSetDevice(dev0));
+    HIP_CHECK(hipSetDevice(dev0));
     hipStream_t s0 = m->dev[0].stream;
     const size_t frame_elems = (size_t)width * height * 3;
     float *frame_rgb = nullptr;
     uint8_t *frame_rgb8 = nullptr;
     if (N > 1) {
-        if (out_rgb) { if (out_dev) frame_rgb = out_rgb; else { int r = grow(m->frame_rgb, m->frame_cap_rgb, frame_elems); if (r != RT_OK) return r; frame_rgb = m->frame_rgb; } }
-        if (out_rgb8) { if (out_dev) frame_rgb8 = out_rgb8; else { int r = grow(m->frame_rgb8, m->frame_cap_rgb8, frame_elems); if (r != RT_OK) return r; frame_rgb8 = m->frame_rgb8; } }
+        if (out_rgb) { if (out_dev) frame_rgb = out_rgb; else { grow(m->frame_rgb, m->frame_cap_rgb, frame_elems * sizeof(float)); frame_rgb = m->frame_rgb; } }
+        if (out_rgb8) { if (out_dev) frame_rgb8 = out_rgb8; else { grow(m->frame_rgb8, m->frame_cap_rgb8, frame_elems); frame_rgb8 = m->frame_rgb8; } }
         for (int i = 1; i < N; i++) {
             if (elems[i] == 0) continue;
-            if (out_rgb) { int r = grow(m->land_rgb[i], m->land_cap_rgb[i], elems[i]); if (r != RT_OK) return r; }
-            if (out_rgb8) { int r = grow(m->land_rgb8[i], m->land_cap_rgb8[i], elems[i]); if (r != RT_OK) return r; }
+            if (out_rgb) grow(m->land_rgb[i], m->land_cap_rgb[i], elems[i] * sizeof(float));
+            if (out_rgb8) grow(m->land_rgb8[i], m->land_cap_rgb8[i], elems[i]);
         }
     }
     // every device fills its shard from its own host thread and pushes it to device 0 as soon as it is done
-    std::vector<int> rc((size_t)N, RT_OK);
-    std::vector<std::string> err((size_t)N);
-    {
-        Threads threads;
-        for (int i = 0; i < N; i++)
-            threads.th.emplace_back([&, i] {
-                DeviceSlot &d = m->dev[i];
-                if (hipSetDevice(d.device) != hipSuccess) { rc[i] = RT_ERR_HIP; err[i] = "hipSetDevice failed"; return; }
-                if (elems[i] == 0) return; // more devices than tiles
-                if (out_rgb && (rc[i] = grow(d.d_rgb, d.cap_rgb, elems[i])) != RT_OK) { err[i] = rt_last_error(); return; }
-                if (out_rgb8 && (rc[i] = grow(d.d_rgb8, d.cap_rgb8, elems[i])) != RT_OK) { err[i] = rt_last_error(); return; }
-                rc[i] = produce(i, out_rgb ? d.d_rgb : nullptr, out_rgb8 ? d.d_rgb8 : nullptr);
-                if (rc[i] != RT_OK) { err[i] = rt_last_error(); return; }
-                if (i > 0 && N > 1) { // the push: this device's stream, this device's link
-                    hipError_t e = hipSuccess;
-                    if (out_rgb) e = hipMemcpyPeerAsync(m->land_rgb[i], dev0, d.d_rgb, d.device, elems[i] * sizeof(float), d.stream);
-                    if (e == hipSuccess && out_rgb8) e = hipMemcpyPeerAsync(m->land_rgb8[i], dev0, d.d_rgb8, d.device, elems[i], d.stream);
-                    if (e == hipSuccess) e = hipEventRecord(d.done, d.stream);
-                    if (e != hipSuccess) { rc[i] = RT_ERR_HIP; err[i] = std::string("shard push: ") + hipGetErrorString(e); }
-                }
-            });
-    }
-    for (int i = 0; i < N; i++)
-        if (rc[i] != RT_OK) return fail(rc[i], who + "device " + std::to_string(m->dev[i].device) + ": " + err[i]);
+    const int rc = fan_out(who, N, [&](int i) { return m->dev[i].device; }, [&](int i) -> int {
+        DeviceSlot &d = m->dev[i];
+        if (elems[i] == 0) return RT_OK; // more devices than tiles
+        if (out_rgb) grow(d.d_rgb, d.cap_rgb, elems[i] * sizeof(float));
+        if (out_rgb8) grow(d.d_rgb8, d.cap_rgb8, elems[i]);
+        if (const int r = produce(i, out_rgb ? d.d_rgb : nullptr, out_rgb8 ? d.d_rgb8 : nullptr)) return r;
+        if (i > 0 && N > 1) { // the push: this device's stream, this device's link
+            hipError_t e = hipSuccess;
+            if (out_rgb) e = hipMemcpyPeerAsync(m->land_rgb[i], dev0, d.d_rgb, d.device, elems[i] * sizeof(float), d.stream);
+            if (e == hipSuccess && out_rgb8) e = hipMemcpyPeerAsync(m->land_rgb8[i], dev0, d.d_rgb8, d.device, elems[i], d.stream);
+            if (e == hipSuccess) e = hipEventRecord(d.done, d.stream);
+            if (e != hipSuccess) return fail(RT_ERR_HIP, std::string("shard push: ") + hipGetErrorString(e));
+        }
+        return RT_OK;
+    });
+    if (rc != RT_OK) return rc;
     // tiles -> frame on device 0, each shard as soon as its push has landed
-    MHIP(hipSetDevice(dev0));
+    HIP_CHECK(hipSetDevice(dev0));
     if (N == 1) { frame_rgb = m->dev[0].d_rgb; frame_rgb8 = m->dev[0].d_rgb8; }
     else {
         const int tiles_x = (width + tile - 1) / tile, tiles_y = (height + tile - 1) / tile;
@@ -203,21 +204,49 @@ static int exchange_frame(rt_multi *m, const std::string &who, int width, int he
             const uint32_t n_tiles = (total_tiles - (uint32_t)i + (uint32_t)N - 1) / (uint32_t)N;
             const float *src_rgb = i ? m->land_rgb[i] : m->dev[0].d_rgb;
             const uint8_t *src_rgb8 = i ? m->land_rgb8[i] : m->dev[0].d_rgb8;
-            if (i > 0) MHIP(hipStreamWaitEvent(s0, m->dev[i].done, 0));
+            if (i > 0) HIP_CHECK(hipStreamWaitEvent(s0, m->dev[i].done, 0));
             const unsigned blocks = (unsigned)((elems[i] + 255) / 256 < 65535 ? (elems[i] + 255) / 256 : 65535);
             if (out_rgb) hipLaunchKernelGGL(assemble_tiles_kernel<float>, dim3(blocks), dim3(256), 0, s0, src_rgb, frame_rgb, width, height, tile, tiles_x, i, N, n_tiles);
             if (out_rgb8) hipLaunchKernelGGL(assemble_tiles_kernel<uint8_t>, dim3(blocks), dim3(256), 0, s0, src_rgb8, frame_rgb8, width, height, tile, tiles_x, i, N, n_tiles);
         }
-        MHIP(hipGetLastError());
+        HIP_CHECK(hipGetLastError());
     }
     if (!out_dev) {
-        if (out_rgb) MHIP(hipMemcpyAsync(out_rgb, frame_rgb, frame_elems * sizeof(float), hipMemcpyDeviceToHost, s0));
-        if (out_rgb8) MHIP(hipMemcpyAsync(out_rgb8, frame_rgb8, frame_elems, hipMemcpyDeviceToHost, s0));
+        if (out_rgb) HIP_CHECK(hipMemcpyAsync(out_rgb, frame_rgb, frame_elems * sizeof(float), hipMemcpyDeviceToHost, s0));
+        if (out_rgb8) HIP_CHECK(hipMemcpyAsync(out_rgb8, frame_rgb8, frame_elems, hipMemcpyDeviceToHost, s0));
     } else if (N == 1) {
-        if (out_rgb) MHIP(hipMemcpyAsync(out_rgb, frame_rgb, frame_elems * sizeof(float), hipMemcpyDeviceToDevice, s0));
-        if (out_rgb8) MHIP(hipMemcpyAsync(out_rgb8, frame_rgb8, frame_elems, hipMemcpyDeviceToDevice, s0));
+        if (out_rgb) HIP_CHECK(hipMemcpyAsync(out_rgb, frame_rgb, frame_elems * sizeof(float), hipMemcpyDeviceToDevice, s0));
+        if (out_rgb8) HIP_CHECK(hipMemcpyAsync(out_rgb8, frame_rgb8, frame_elems, hipMemcpyDeviceToDevice, s0));
     }
-    MHIP(hipStreamSynchronize(s0));
+    HIP_CHECK(hipStreamSynchronize(s0));
+    return RT_OK;
+}
+
+// What a frame on all devices of `m` needs settled before anything runs, for rt_multi_render (`render`) and rt_multi_accum_create: the
+// refusals the two share, the square tile, and per device entry the rt_render_params of its shard (shard i of N on that entry's
+// stream; with one entry the unsharded frame) and the elements of its compact picture (0: more entries than tiles).
+struct FramePlan {
+    int tile = 32;
+    std::vector<rt_render_params> p;
+    std::vector<size_t> elems;
+};
+static int plan_frame(const rt_multi *m, const rt_render_params *params, const std::string &who, bool render, FramePlan &P) {
+    if (params->struct_size != sizeof(rt_render_params)) return fail(RT_ERR_INVALID_ARG, who + "struct_size mismatch (ABI skew)");
+    if (params->shard_count > 1) return fail(RT_ERR_INVALID_ARG, who + "the frame is sharded over the devices here; shard_count must be 0 or 1");
+    if (render && params->integrator == RT_INTEGRATOR_HW1) return fail(RT_ERR_UNSUPPORTED, who + "the hw1 caster renders unsharded frames only"); // an rt_accum refuses hw1 itself
+    P.tile = params->tile_w > 0 ? params->tile_w : 32;
+    if (params->tile_h > 0 && params->tile_h != P.tile) return fail(RT_ERR_INVALID_ARG, who + "square tiles only");
+    const int N = (int)m->dev.size();
+    P.p.assign((size_t)N, *params);
+    P.elems.assign((size_t)N, 0);
+    for (int i = 0; i < N; i++) {
+        rt_render_params &p = P.p[i];
+        p.shard_index = N > 1 ? i : 0; p.shard_count = N > 1 ? N : 1; p.tile_w = p.tile_h = P.tile;
+        p.stream = m->dev[i].stream;
+        rt_render_params q = p;
+        q.samples = 1; // rt_output_elems looks at it; whether the frame has samples is the caller's business
+        P.elems[i] = N > 1 ? rt_output_elems(&q) : (size_t)(params->width > 0 && params->height > 0 ? (size_t)params->width * params->height * 3 : 0);
+    }
     return RT_OK;
 }
 
@@ -250,94 +279,64 @@ int rt_multi_create(const rt_scene_desc *desc, const int *devices, int n_devices
     *out = nullptr;
     const int visible = rt_device_count();
     if (visible == 0) return fail(RT_ERR_NO_DEVICE, "rt_multi_create: no HIP device available (this library has no CPU fallback)");
-    try {
-    std::unique_ptr<rt_multi> m(new rt_multi());
-    rtamd::SharedPrep prep; // one host-side preparation for all devices
-    m->dev.resize((size_t)n_devices);
-    for (int i = 0; i < n_devices; i++) {
-        m->dev[i].device = devices ? devices[i] : i;
-        if (m->dev[i].device < 0 || m->dev[i].device >= visible) return fail(RT_ERR_INVALID_ARG, "rt_multi_create: device index out of range");
-    }
-    // one scene per device; the host-side preparation (BVH replay) of each runs on its own thread
-    std::vector<int> rc((size_t)n_devices, RT_OK);
-    std::vector<std::string> err((size_t)n_devices);
-    Threads threads;
-    for (int i = 0; i < n_devices; i++)
-        threads.th.emplace_back([&, i] {
-            if (hipSetDevice(m->dev[i].device) != hipSuccess) { rc[i] = RT_ERR_HIP; err[i] = "hipSetDevice failed"; return; }
-            rc[i] = rtamd::scene_create_shared(desc, &m->dev[i].scene, &prep);
-            if (rc[i] != RT_OK) { err[i] = rt_last_error(); return; }
-            if (hipStreamCreateWithFlags(&m->dev[i].stream, hipStreamNonBlocking) != hipSuccess || hipEventCreateWithFlags(&m->dev[i].done, hipEventDisableTiming) != hipSuccess) {
-                rc[i] = RT_ERR_HIP; err[i] = "stream / event creation failed";
-            }
-        });
-    threads.join();
-    for (int i = 0; i < n_devices; i++)
-        if (rc[i] != RT_OK) return fail(rc[i], "rt_multi_create: device " + std::to_string(m->dev[i].device) + ": " + err[i]);
-    // peer access from every sender towards device 0 — the direction of its push — where the hardware offers it (hipMemcpyPeerAsync
-    // stages through the host otherwise)
-    for (int i = 1; i < n_devices; i++) {
-        if (m->dev[i].device == m->dev[0].device) continue;
-        int can = 0;
-        if (hipDeviceCanAccessPeer(&can, m->dev[i].device, m->dev[0].device) == hipSuccess && can) {
-            (void)hipSetDevice(m->dev[i].device);
-            hipError_t e = hipDeviceEnablePeerAccess(m->dev[0].device, 0);
-            if (e != hipSuccess && e != hipErrorPeerAccessAlreadyEnabled) (void)hipGetLastError();
+    return guarded("rt_multi_create: ", [&]() -> int { // also std::bad_alloc and the std::system_error of a thread that could not start
+        std::unique_ptr<rt_multi> m(new rt_multi());
+        rtamd::SharedPrep prep; // one host-side preparation for all devices
+        m->dev.resize((size_t)n_devices);
+        for (int i = 0; i < n_devices; i++) {
+            m->dev[i].device = devices ? devices[i] : i;
+            if (m->dev[i].device < 0 || m->dev[i].device >= visible) return fail(RT_ERR_INVALID_ARG, "rt_multi_create: device index out of range");
         }
-    }
-    (void)hipSetDevice(m->dev[0].device);
-    m->land_rgb.assign((size_t)n_devices, nullptr); m->land_rgb8.assign((size_t)n_devices, nullptr);
-    m->land_cap_rgb.assign((size_t)n_devices, 0); m->land_cap_rgb8.assign((size_t)n_devices, 0);
-    m->land_state.assign((size_t)n_devices, nullptr); m->land_cap_state.assign((size_t)n_devices, 0);
-    MHIP(hipEventCreateWithFlags(&m->state_ready, hipEventDisableTiming));
-    *out = m.release();
-    return RT_OK;
-    } catch (const std::exception &e) { // std::bad_alloc, std::system_error of a thread: nothing may cross the C boundary
-        return fail(RT_ERR_INVALID_ARG, std::string("rt_multi_create: ") + e.what());
-    } catch (...) {
-        return fail(RT_ERR_INVALID_ARG, "rt_multi_create: unknown exception");
-    }
+        // one scene per device; the host-side preparation (BVH replay) of each runs on its own thread
+        const int rc = fan_out("rt_multi_create: ", n_devices, [&](int i) { return m->dev[i].device; }, [&](int i) -> int {
+            if (const int r = rtamd::scene_create_shared(desc, &m->dev[i].scene, &prep)) return r;
+            if (hipStreamCreateWithFlags(&m->dev[i].stream, hipStreamNonBlocking) != hipSuccess || hipEventCreateWithFlags(&m->dev[i].done, hipEventDisableTiming) != hipSuccess)
+                return fail(RT_ERR_HIP, "stream / event creation failed");
+            return RT_OK;
+        });
+        if (rc != RT_OK) return rc;
+        // peer access from every sender towards device 0 — the direction of its push — where the hardware offers it (hipMemcpyPeerAsync
+        // stages through the host otherwise)
+        for (int i = 1; i < n_devices; i++) {
+            if (m->dev[i].device == m->dev[0].device) continue;
+            int can = 0;
+            if (hipDeviceCanAccessPeer(&can, m->dev[i].device, m->dev[0].device) == hipSuccess && can) {
+                (void)hipSetDevice(m->dev[i].device);
+                hipError_t e = hipDeviceEnablePeerAccess(m->dev[0].device, 0);
+                if (e != hipSuccess && e != hipErrorPeerAccessAlreadyEnabled) (void)hipGetLastError();
+            }
+        }
+        (void)hipSetDevice(m->dev[0].device);
+        m->land_rgb.assign((size_t)n_devices, nullptr); m->land_rgb8.assign((size_t)n_devices, nullptr);
+        m->land_cap_rgb.assign((size_t)n_devices, 0); m->land_cap_rgb8.assign((size_t)n_devices, 0);
+        m->land_state.assign((size_t)n_devices, nullptr); m->land_cap_state.assign((size_t)n_devices, 0);
+        HIP_CHECK(hipEventCreateWithFlags(&m->state_ready, hipEventDisableTiming));
+        *out = m.release();
+        return RT_OK;
+    });
 }
 
 void rt_multi_destroy(rt_multi *m) { delete m; }
 
 int rt_multi_render(rt_multi *m, const rt_render_params *params, float *out_rgb, uint8_t *out_rgb8, rt_stats *stats) {
     if (!m || !params) return fail(RT_ERR_INVALID_ARG, "rt_multi_render: null argument");
-    if (params->struct_size != sizeof(rt_render_params)) return fail(RT_ERR_INVALID_ARG, "rt_multi_render: struct_size mismatch (ABI skew)");
-    if (params->shard_count > 1) return fail(RT_ERR_INVALID_ARG, "rt_multi_render: the frame is sharded over the devices here; shard_count must be 0 or 1");
-    if (params->integrator == RT_INTEGRATOR_HW1) return fail(RT_ERR_UNSUPPORTED, "rt_multi_render: the hw1 caster renders unsharded frames only");
-    const int N = (int)m->dev.size();
-    const double t0 = now_ms();
-    const bool out_dev = (params->flags & RT_FLAG_OUT_DEVICE) != 0;
-    const int tile = params->tile_w > 0 ? params->tile_w : 32;
-    if (params->tile_h > 0 && params->tile_h != tile) return fail(RT_ERR_INVALID_ARG, "rt_multi_render: square tiles only");
-    std::vector<rt_render_params> p((size_t)N, *params);
-    std::vector<size_t> elems((size_t)N);
-    for (int i = 0; i < N; i++) {
-        p[i].shard_index = i; p[i].shard_count = N; p[i].tile_w = p[i].tile_h = tile;
-        p[i].flags = params->flags | RT_FLAG_OUT_DEVICE;
-        p[i].stream = m->dev[i].stream;
-        elems[i] = N > 1 ? rt_output_elems(&p[i]) : (size_t)params->width * params->height * 3;
-        if (N == 1) { p[i].shard_count = 1; p[i].shard_index = 0; }
-        if (elems[i] == 0 && params->width > 0 && params->height > 0 && N == 1) return fail(RT_ERR_INVALID_ARG, "rt_multi_render: bad render parameters");
-    }
-    if (params->width <= 0 || params->height <= 0 || params->samples <= 0) return fail(RT_ERR_INVALID_ARG, "rt_multi_render: width, height and samples must be positive");
-    try {
-    std::vector<rt_stats> st((size_t)N);
-    for (auto &x : st) memset(&x, 0, sizeof x);
-    const int rc = exchange_frame(m, "rt_multi_render: ", params->width, params->height, tile, out_dev, out_rgb, out_rgb8, elems,
-                                  [&](int i, float *d_rgb, uint8_t *d_rgb8) { return rt_render(m->dev[i].scene, &p[i], d_rgb, d_rgb8, &st[i]); });
-    if (rc != RT_OK) return rc;
-    if (stats) {
-        sum_stats(st, elems, stats);
-        stats->total_ms = now_ms() - t0; // host wall time of the whole call: renders, exchange, read-back
-    }
-    return RT_OK;
-    } catch (const std::exception &e) { // std::bad_alloc, std::system_error of a thread: nothing may cross the C boundary
-        return fail(RT_ERR_INVALID_ARG, std::string("rt_multi_render: ") + e.what());
-    } catch (...) {
-        return fail(RT_ERR_INVALID_ARG, "rt_multi_render: unknown exception");
-    }
+    return guarded("rt_multi_render: ", [&]() -> int {
+        const double t0 = now_ms();
+        FramePlan P;
+        if (const int rc = plan_frame(m, params, "rt_multi_render: ", true, P)) return rc;
+        for (rt_render_params &p : P.p) p.flags = params->flags | RT_FLAG_OUT_DEVICE;
+        if (params->width <= 0 || params->height <= 0 || params->samples <= 0) return fail(RT_ERR_INVALID_ARG, "rt_multi_render: width, height and samples must be positive");
+        std::vector<rt_stats> st(P.p.size());
+        for (auto &x : st) memset(&x, 0, sizeof x);
+        const int rc = exchange_frame(m, "rt_multi_render: ", params->width, params->height, P.tile, (params->flags & RT_FLAG_OUT_DEVICE) != 0, out_rgb, out_rgb8, P.elems,
+                                      [&](int i, float *d_rgb, uint8_t *d_rgb8) { return rt_render(m->dev[i].scene, &P.p[i], d_rgb, d_rgb8, &st[i]); });
+        if (rc != RT_OK) return rc;
+        if (stats) {
+            sum_stats(st, P.elems, stats);
+            stats->total_ms = now_ms() - t0; // host wall time of the whole call: renders, exchange, read-back
+        }
+        return RT_OK;
+    });
 }
 
 // ---- resumable renders on all devices (include/rtamd.h: rt_multi_accum_*) ---------------------------------------------------
@@ -355,41 +354,30 @@ static unsigned regroup_blocks(uint32_t n_slots) { return (n_slots + 255u) / 256
 int rt_multi_accum_create(rt_multi *m, const rt_render_params *params, rt_multi_accum **out) {
     if (!m || !params || !out) return fail(RT_ERR_INVALID_ARG, "rt_multi_accum_create: null argument");
     *out = nullptr;
-    if (params->struct_size != sizeof(rt_render_params)) return fail(RT_ERR_INVALID_ARG, "rt_multi_accum_create: struct_size mismatch (ABI skew)");
-    if (params->shard_count > 1) return fail(RT_ERR_INVALID_ARG, "rt_multi_accum_create: the frame is sharded over the devices here; shard_count must be 0 or 1");
-    const int tile = params->tile_w > 0 ? params->tile_w : 32;
-    if (params->tile_h > 0 && params->tile_h != tile) return fail(RT_ERR_INVALID_ARG, "rt_multi_accum_create: square tiles only");
-    try {
-    const int N = (int)m->dev.size();
-    std::unique_ptr<rt_multi_accum> a(new rt_multi_accum());
-    a->multi = m; a->params = *params; a->params.samples = 0; a->params.shard_index = 0; a->params.shard_count = 1; a->tile = tile;
-    a->shard.assign((size_t)N, nullptr); a->elems.assign((size_t)N, 0);
-    a->sample_limit = 0;
-    for (int i = 0; i < N; i++) {
-        rt_render_params p = a->params;
-        p.stream = m->dev[i].stream;
-        if (N > 1) { p.shard_index = i; p.shard_count = N; p.tile_w = p.tile_h = tile; }
-        p.samples = 1; // ignored by rt_accum_create, looked at by rt_output_elems
-        a->elems[i] = N > 1 ? rt_output_elems(&p) : (size_t)(params->width > 0 && params->height > 0 ? (size_t)params->width * params->height * 3 : 0);
-        if (i > 0 && a->elems[i] == 0) continue; // more devices than tiles; the first entry always has a tile, and makes every refusal
-        MHIP(hipSetDevice(m->dev[i].device));
-        const int rc = rt_accum_create(m->dev[i].scene, &p, &a->shard[i]);
-        if (rc != RT_OK) return fail(rc, "rt_multi_accum_create: device " + std::to_string(m->dev[i].device) + ": " + rt_last_error());
-        if (a->sample_limit == 0 || a->shard[i]->sample_limit < a->sample_limit) a->sample_limit = a->shard[i]->sample_limit;
-    }
-    std::string err;
-    rt_render_params q = a->params;
-    q.samples = 1;
-    if (!rtamd::resolve_tiles(&q, a->frame, err)) return fail(RT_ERR_INVALID_ARG, "rt_multi_accum_create: " + err);
-    a->frame_slots = (uint32_t)a->frame.tiles_x * (uint32_t)a->frame.tiles_y * 64u; // below 2^30: rt_accum_create has taken shard 0 of this frame
-    MHIP(hipSetDevice(m->dev[0].device));
-    *out = a.release();
-    return RT_OK;
-    } catch (const std::exception &e) {
-        return fail(RT_ERR_INVALID_ARG, std::string("rt_multi_accum_create: ") + e.what());
-    } catch (...) {
-        return fail(RT_ERR_INVALID_ARG, "rt_multi_accum_create: unknown exception");
-    }
+    return guarded("rt_multi_accum_create: ", [&]() -> int {
+        FramePlan P;
+        if (const int rc = plan_frame(m, params, "rt_multi_accum_create: ", false, P)) return rc;
+        const int N = (int)m->dev.size();
+        std::unique_ptr<rt_multi_accum> a(new rt_multi_accum());
+        a->multi = m; a->params = *params; a->params.samples = 0; a->params.shard_index = 0; a->params.shard_count = 1; a->tile = P.tile;
+        a->shard.assign((size_t)N, nullptr); a->elems = P.elems;
+        a->sample_limit = 0;
+        for (int i = 0; i < N; i++) {
+            if (i > 0 && a->elems[i] == 0) continue; // more devices than tiles; the first entry always has a tile, and makes every refusal
+            HIP_CHECK(hipSetDevice(m->dev[i].device));
+            const int rc = rt_accum_create(m->dev[i].scene, &P.p[i], &a->shard[i]); // its samples field is ignored there
+            if (rc != RT_OK) return fail(rc, "rt_multi_accum_create: device " + std::to_string(m->dev[i].device) + ": " + rt_last_error());
+            if (a->sample_limit == 0 || a->shard[i]->sample_limit < a->sample_limit) a->sample_limit = a->shard[i]->sample_limit;
+        }
+        std::string err;
+        rt_render_params q = a->params;
+        q.samples = 1;
+        if (!rtamd::resolve_tiles(&q, a->frame, err)) return fail(RT_ERR_INVALID_ARG, "rt_multi_accum_create: " + err);
+        a->frame_slots = (uint32_t)a->frame.tiles_x * (uint32_t)a->frame.tiles_y * 64u; // below 2^30: rt_accum_create has taken shard 0 of this frame
+        HIP_CHECK(hipSetDevice(m->dev[0].device));
+        *out = a.release();
+        return RT_OK;
+    });
 }
 
 void rt_multi_accum_destroy(rt_multi_accum *a) { delete a; }
@@ -405,171 +393,149 @@ int rt_multi_accum_samples(const rt_multi_accum *a) {
 // a failure after the devices have started: the object is broken from here on
 #define MA_BREAK(rc_) do { a->broken = rt_last_error(); return (rc_); } while (0)
 
+// the HIP device of entry i's shard, -1 for an empty shard (fan_out, each_device)
+static int shard_device(const rt_multi_accum *a, size_t i) { return a->shard[i] ? a->multi->dev[i].device : -1; }
+
 int rt_multi_accum_render(rt_multi_accum *a, int32_t n_samples, rt_stats *stats) {
-    MA_ENTER("rt_multi_accum_render");
-    rt_multi *m = a->multi;
-    const int N = (int)a->shard.size();
-    const double t0 = now_ms();
-    if (n_samples <= 0) return fail(RT_ERR_INVALID_ARG, "rt_multi_accum_render: n_samples must be positive");
-    if ((int64_t)a->samples + n_samples >= (int64_t)a->sample_limit)
-        return fail(RT_ERR_LIMIT, "rt_multi_accum_render: " + std::to_string(a->samples) + " + " + std::to_string(n_samples) + " samples per pixel do not fit the path records' sample index (below " + std::to_string(a->sample_limit) + " on some device)");
-    for (int i = 0; i < N; i++) // every refusal before any device launches: the state stays as it was
-        if (a->shard[i]) if (const int rc = rtamd::accum_check_slice(a->shard[i], n_samples, "rt_multi_accum_render: device " + std::to_string(m->dev[i].device) + ": ")) return rc;
-    try {
-    std::vector<int> rc((size_t)N, RT_OK);
-    std::vector<std::string> err((size_t)N);
-    std::vector<rt_stats> st((size_t)N);
-    for (auto &x : st) memset(&x, 0, sizeof x);
-    {
-        Threads threads;
-        for (int i = 0; i < N; i++)
-            if (a->shard[i])
-                threads.th.emplace_back([&, i] {
-                    if (hipSetDevice(m->dev[i].device) != hipSuccess) { rc[i] = RT_ERR_HIP; err[i] = "hipSetDevice failed"; return; }
-                    rc[i] = rt_accum_render(a->shard[i], n_samples, &st[i]);
-                    if (rc[i] != RT_OK) err[i] = rt_last_error();
-                });
-    }
-    (void)hipSetDevice(m->dev[0].device);
-    for (int i = 0; i < N; i++)
-        if (rc[i] != RT_OK) { fail(rc[i], "rt_multi_accum_render: device " + std::to_string(m->dev[i].device) + ": " + err[i]); MA_BREAK(rc[i]); }
-    a->samples += n_samples;
-    if (stats) {
-        sum_stats(st, a->elems, stats);
-        stats->samples = (uint64_t)a->params.width * (uint64_t)a->params.height * (uint64_t)n_samples;
-        stats->reference_exact = 1;
-        for (int i = 0; i < N; i++) if (a->shard[i]) stats->reference_exact &= st[i].reference_exact;
-        stats->total_ms = now_ms() - t0;
-    }
-    return RT_OK;
-    } catch (const std::exception &e) { // a thread that could not be started: the others have run
-        fail(RT_ERR_INVALID_ARG, std::string("rt_multi_accum_render: ") + e.what());
-        MA_BREAK(RT_ERR_INVALID_ARG);
-    } catch (...) {
-        fail(RT_ERR_INVALID_ARG, "rt_multi_accum_render: unknown exception");
-        MA_BREAK(RT_ERR_INVALID_ARG);
-    }
+    return guarded("rt_multi_accum_render: ", [&]() -> int {
+        MA_ENTER("rt_multi_accum_render");
+        rt_multi *m = a->multi;
+        const int N = (int)a->shard.size();
+        const double t0 = now_ms();
+        if (n_samples <= 0) return fail(RT_ERR_INVALID_ARG, "rt_multi_accum_render: n_samples must be positive");
+        if ((int64_t)a->samples + n_samples >= (int64_t)a->sample_limit)
+            return fail(RT_ERR_LIMIT, "rt_multi_accum_render: " + std::to_string(a->samples) + " + " + std::to_string(n_samples) + " samples per pixel do not fit the path records' sample index (below " + std::to_string(a->sample_limit) + " on some device)");
+        for (int i = 0; i < N; i++) // every refusal before any device launches: the state stays as it was
+            if (a->shard[i]) if (const int rc = rtamd::accum_check_slice(a->shard[i], n_samples, "rt_multi_accum_render: device " + std::to_string(m->dev[i].device) + ": ")) return rc;
+        std::vector<rt_stats> st((size_t)N);
+        for (auto &x : st) memset(&x, 0, sizeof x);
+        const int rc = guarded("rt_multi_accum_render: ", [&]() -> int { // a thread that could not be started: the others have run
+            return fan_out("rt_multi_accum_render: ", N, [&](int i) { return shard_device(a, (size_t)i); }, [&](int i) { return rt_accum_render(a->shard[i], n_samples, &st[i]); });
+        });
+        (void)hipSetDevice(m->dev[0].device);
+        if (rc != RT_OK) MA_BREAK(rc);
+        a->samples += n_samples;
+        if (stats) {
+            sum_stats(st, a->elems, stats);
+            stats->samples = (uint64_t)a->params.width * (uint64_t)a->params.height * (uint64_t)n_samples;
+            stats->reference_exact = 1;
+            for (int i = 0; i < N; i++) if (a->shard[i]) stats->reference_exact &= st[i].reference_exact;
+            stats->total_ms = now_ms() - t0;
+        }
+        return RT_OK;
+    });
 }
 
 int rt_multi_accum_resolve(rt_multi_accum *a, uint32_t flags, float *out_rgb, uint8_t *out_rgb8) {
-    MA_ENTER("rt_multi_accum_resolve");
-    if (flags & ~RT_FLAG_OUT_DEVICE) return fail(RT_ERR_INVALID_ARG, "rt_multi_accum_resolve: flags other than RT_FLAG_OUT_DEVICE");
-    if (a->samples <= 0) return fail(RT_ERR_INVALID_ARG, "rt_multi_accum_resolve: no samples yet (a picture needs at least one)");
-    if (!out_rgb && !out_rgb8) return RT_OK;
-    try {
+    return guarded("rt_multi_accum_resolve: ", [&]() -> int {
+        MA_ENTER("rt_multi_accum_resolve");
+        if (flags & ~RT_FLAG_OUT_DEVICE) return fail(RT_ERR_INVALID_ARG, "rt_multi_accum_resolve: flags other than RT_FLAG_OUT_DEVICE");
+        if (a->samples <= 0) return fail(RT_ERR_INVALID_ARG, "rt_multi_accum_resolve: no samples yet (a picture needs at least one)");
+        if (!out_rgb && !out_rgb8) return RT_OK;
         // the state is only read; each device resolves its shard on device in the compact layout (accum_resolve_kernel)
         return exchange_frame(a->multi, "rt_multi_accum_resolve: ", a->params.width, a->params.height, a->tile, (flags & RT_FLAG_OUT_DEVICE) != 0, out_rgb, out_rgb8, a->elems,
                               [&](int i, float *d_rgb, uint8_t *d_rgb8) { return rt_accum_resolve(a->shard[i], RT_FLAG_OUT_DEVICE, d_rgb, d_rgb8); });
-    } catch (const std::exception &e) {
-        return fail(RT_ERR_INVALID_ARG, std::string("rt_multi_accum_resolve: ") + e.what());
-    } catch (...) {
-        return fail(RT_ERR_INVALID_ARG, "rt_multi_accum_resolve: unknown exception");
-    }
+    });
+}
+
+// The buffers on device 0 that a checkpoint passes through: the state in frame order and the landing areas of the other devices' states.
+static void grow_state_buffers(rt_multi_accum *a) {
+    rt_multi *m = a->multi;
+    grow(m->frame_state, m->frame_cap_state, (size_t)a->frame_slots * ACCUM_SLOT_BYTES);
+    for (size_t i = 1; i < a->shard.size(); i++)
+        if (a->shard[i]) grow(m->land_state[i], m->land_cap_state[i], (size_t)a->shard[i]->n_pixslots * ACCUM_SLOT_BYTES);
 }
 
 // Save: every device pushes its shard's state to its landing area on device 0 (its own stream, an event), device 0 scatters each
 // landed shard into the frame-order buffer and copies header + buffer to the host once.
 int rt_multi_accum_save(rt_multi_accum *a, void *blob, size_t capacity) {
-    MA_ENTER("rt_multi_accum_save");
-    if (!blob) return fail(RT_ERR_INVALID_ARG, "rt_multi_accum_save: null argument");
-    const size_t state = (size_t)a->frame_slots * ACCUM_SLOT_BYTES;
-    if (capacity < ACCUM_HEADER_BYTES + state) return fail(RT_ERR_INVALID_ARG, "rt_multi_accum_save: buffer smaller than rt_accum_state_bytes of the unsharded frame");
-    rt_multi *m = a->multi;
-    const int N = (int)a->shard.size();
-    if (N == 1) { // the unsharded rt_accum itself
-        MHIP(hipSetDevice(m->dev[0].device));
-        const int rc = rt_accum_save(a->shard[0], blob, capacity);
-        return rc == RT_OK ? rc : fail(rc, std::string("rt_multi_accum_save: ") + rt_last_error());
-    }
-    const int dev0 = m->dev[0].device;
-    hipStream_t s0 = m->dev[0].stream;
-    MHIP(hipSetDevice(dev0));
-    { int r = grow(m->frame_state, m->frame_cap_state, (size_t)a->frame_slots * (ACCUM_SLOT_BYTES / 4)); if (r != RT_OK) return r; }
-    for (int i = 1; i < N; i++)
-        if (a->shard[i]) { int r = grow(m->land_state[i], m->land_cap_state[i], (size_t)a->shard[i]->n_pixslots * (ACCUM_SLOT_BYTES / 4)); if (r != RT_OK) return r; }
-    for (int i = 1; i < N; i++) { // the pushes: each on its device's stream, behind that device's last slice
-        if (!a->shard[i]) continue;
-        MHIP(hipSetDevice(m->dev[i].device));
-        MHIP(hipMemcpyPeerAsync(m->land_state[i], dev0, a->shard[i]->d_state, m->dev[i].device, (size_t)a->shard[i]->n_pixslots * ACCUM_SLOT_BYTES, m->dev[i].stream));
-        MHIP(hipEventRecord(m->dev[i].done, m->dev[i].stream));
-    }
-    MHIP(hipSetDevice(dev0));
-    for (int i = 0; i < N; i++) {
-        if (!a->shard[i]) continue;
-        if (i > 0) MHIP(hipStreamWaitEvent(s0, m->dev[i].done, 0));
-        const Regroup G = regroup_of(a, i);
-        hipLaunchKernelGGL(shard_to_frame_kernel, dim3(regroup_blocks(G.n_slots)), dim3(256), 0, s0, i ? m->land_state[i] : a->shard[0]->d_state, m->frame_state, G);
-    }
-    MHIP(hipGetLastError());
-    uint32_t h[ACCUM_HEADER_BYTES / 4];
-    accum_header(m->dev[0].scene, a->params.integrator, a->frame, a->frame_slots, a->samples, h);
-    memcpy(blob, h, ACCUM_HEADER_BYTES);
-    MHIP(hipMemcpyAsync((uint8_t *)blob + ACCUM_HEADER_BYTES, m->frame_state, state, hipMemcpyDeviceToHost, s0));
-    MHIP(hipStreamSynchronize(s0));
-    return RT_OK;
+    return guarded("rt_multi_accum_save: ", [&]() -> int {
+        MA_ENTER("rt_multi_accum_save");
+        if (!blob) return fail(RT_ERR_INVALID_ARG, "rt_multi_accum_save: null argument");
+        const size_t state = (size_t)a->frame_slots * ACCUM_SLOT_BYTES;
+        if (capacity < ACCUM_HEADER_BYTES + state) return fail(RT_ERR_INVALID_ARG, "rt_multi_accum_save: buffer smaller than rt_accum_state_bytes of the unsharded frame");
+        rt_multi *m = a->multi;
+        const int N = (int)a->shard.size();
+        const int dev0 = m->dev[0].device;
+        HIP_CHECK(hipSetDevice(dev0));
+        if (N == 1) { // the unsharded rt_accum itself
+            const int rc = rt_accum_save(a->shard[0], blob, capacity);
+            return rc == RT_OK ? rc : fail(rc, std::string("rt_multi_accum_save: ") + rt_last_error());
+        }
+        hipStream_t s0 = m->dev[0].stream;
+        grow_state_buffers(a);
+        each_device((size_t)N, [&](size_t i) { return i ? shard_device(a, i) : -1; }, [&](size_t i) { // the pushes: each on its device's stream, behind that device's last slice
+            HIP_CHECK(hipMemcpyPeerAsync(m->land_state[i], dev0, a->shard[i]->d_state, m->dev[i].device, (size_t)a->shard[i]->n_pixslots * ACCUM_SLOT_BYTES, m->dev[i].stream));
+            HIP_CHECK(hipEventRecord(m->dev[i].done, m->dev[i].stream));
+            return RT_OK;
+        });
+        HIP_CHECK(hipSetDevice(dev0));
+        for (int i = 0; i < N; i++) {
+            if (!a->shard[i]) continue;
+            if (i > 0) HIP_CHECK(hipStreamWaitEvent(s0, m->dev[i].done, 0));
+            const Regroup G = regroup_of(a, i);
+            hipLaunchKernelGGL(shard_to_frame_kernel, dim3(regroup_blocks(G.n_slots)), dim3(256), 0, s0, i ? m->land_state[i] : a->shard[0]->d_state, m->frame_state, G);
+        }
+        HIP_CHECK(hipGetLastError());
+        uint32_t h[ACCUM_HEADER_BYTES / 4];
+        accum_header(m->dev[0].scene, a->params.integrator, a->frame, a->frame_slots, a->samples, h);
+        memcpy(blob, h, ACCUM_HEADER_BYTES);
+        HIP_CHECK(hipMemcpyAsync((uint8_t *)blob + ACCUM_HEADER_BYTES, m->frame_state, state, hipMemcpyDeviceToHost, s0));
+        HIP_CHECK(hipStreamSynchronize(s0));
+        return RT_OK;
+    });
 }
 
 // Load: the reverse.  The blob goes to device 0, which gathers every shard's slots out of the frame order (its own shard in place,
 // the others into their landing areas); every other device then pulls its state over on its own stream.
 int rt_multi_accum_load(rt_multi_accum *a, const void *blob, size_t size) {
-    MA_ENTER("rt_multi_accum_load");
-    if (!blob) return fail(RT_ERR_INVALID_ARG, "rt_multi_accum_load: null argument");
-    if (size < ACCUM_HEADER_BYTES) return fail(RT_ERR_INVALID_ARG, "rt_multi_accum_load: truncated blob (shorter than its header)");
-    rt_multi *m = a->multi;
-    const int N = (int)a->shard.size();
-    uint32_t want[ACCUM_HEADER_BYTES / 4], got[ACCUM_HEADER_BYTES / 4];
-    accum_header(m->dev[0].scene, a->params.integrator, a->frame, a->frame_slots, a->samples, want);
-    memcpy(got, blob, ACCUM_HEADER_BYTES);
-    for (int f = 0; f < AH_WORDS; f++)
-        if (f != AH_SAMPLES && got[f] != want[f])
-            return fail(RT_ERR_INVALID_ARG, std::string("rt_multi_accum_load: the blob does not belong to this frame: ") + accum_field_names[f] + " is " + std::to_string(got[f]) +
-                                                ", expected " + std::to_string(want[f]));
-    if (got[AH_SAMPLES] >= (uint32_t)a->sample_limit) return fail(RT_ERR_INVALID_ARG, "rt_multi_accum_load: samples beyond the path records' sample index");
-    const size_t state = (size_t)a->frame_slots * ACCUM_SLOT_BYTES;
-    if (size < ACCUM_HEADER_BYTES + state) return fail(RT_ERR_INVALID_ARG, "rt_multi_accum_load: truncated blob (" + std::to_string(size) + " bytes, " + std::to_string(ACCUM_HEADER_BYTES + state) + " expected)");
-    if (N == 1) { // the unsharded rt_accum itself
-        MHIP(hipSetDevice(m->dev[0].device));
-        const int rc = rt_accum_load(a->shard[0], blob, size);
-        if (rc != RT_OK) return fail(rc, std::string("rt_multi_accum_load: ") + rt_last_error());
-        a->samples = (int32_t)got[AH_SAMPLES];
+    return guarded("rt_multi_accum_load: ", [&]() -> int {
+        MA_ENTER("rt_multi_accum_load");
+        if (!blob) return fail(RT_ERR_INVALID_ARG, "rt_multi_accum_load: null argument");
+        rt_multi *m = a->multi;
+        const int N = (int)a->shard.size();
+        uint32_t want[ACCUM_HEADER_BYTES / 4];
+        accum_header(m->dev[0].scene, a->params.integrator, a->frame, a->frame_slots, a->samples, want);
+        const size_t state = (size_t)a->frame_slots * ACCUM_SLOT_BYTES;
+        const int samples = accum_check_blob(want, blob, size, a->sample_limit, state, "rt_multi_accum_load: ");
+        if (samples < 0) return samples;
+        const int dev0 = m->dev[0].device;
+        HIP_CHECK(hipSetDevice(dev0));
+        if (N == 1) { // the unsharded rt_accum itself
+            const int rc = rt_accum_load(a->shard[0], blob, size);
+            if (rc != RT_OK) return fail(rc, std::string("rt_multi_accum_load: ") + rt_last_error());
+            a->samples = samples;
+            a->loads++;
+            return RT_OK;
+        }
+        hipStream_t s0 = m->dev[0].stream;
+        grow_state_buffers(a);
+        // from here on the devices' states are being overwritten: a failure leaves the object broken
         a->loads++;
+        const int rc = guarded("rt_multi_accum_load: ", [&]() -> int {
+            HIP_CHECK(hipMemcpyAsync(m->frame_state, (const uint8_t *)blob + ACCUM_HEADER_BYTES, state, hipMemcpyHostToDevice, s0));
+            for (int i = 0; i < N; i++) {
+                if (!a->shard[i]) continue;
+                const Regroup G = regroup_of(a, i);
+                hipLaunchKernelGGL(frame_to_shard_kernel, dim3(regroup_blocks(G.n_slots)), dim3(256), 0, s0, m->frame_state, i ? m->land_state[i] : a->shard[0]->d_state, G);
+                HIP_CHECK(hipGetLastError());
+            }
+            HIP_CHECK(hipEventRecord(m->state_ready, s0));
+            each_device((size_t)N, [&](size_t i) { return i ? shard_device(a, i) : -1; }, [&](size_t i) { // the pulls, each on its device's stream
+                HIP_CHECK(hipStreamWaitEvent(m->dev[i].stream, m->state_ready, 0));
+                HIP_CHECK(hipMemcpyPeerAsync(a->shard[i]->d_state, m->dev[i].device, m->land_state[i], dev0, (size_t)a->shard[i]->n_pixslots * ACCUM_SLOT_BYTES, m->dev[i].stream));
+                return RT_OK;
+            });
+            return each_device((size_t)N, [&](size_t i) { return shard_device(a, i); }, [&](size_t i) { HIP_CHECK(hipStreamSynchronize(m->dev[i].stream)); return RT_OK; });
+        });
+        if (rc != RT_OK) {
+            (void)hipSetDevice(dev0);
+            MA_BREAK(rc);
+        }
+        for (int i = 0; i < N; i++) if (a->shard[i]) a->shard[i]->samples = samples;
+        a->samples = samples;
         return RT_OK;
-    }
-    const int dev0 = m->dev[0].device;
-    hipStream_t s0 = m->dev[0].stream;
-    MHIP(hipSetDevice(dev0));
-    { int r = grow(m->frame_state, m->frame_cap_state, (size_t)a->frame_slots * (ACCUM_SLOT_BYTES / 4)); if (r != RT_OK) return r; }
-    for (int i = 1; i < N; i++)
-        if (a->shard[i]) { int r = grow(m->land_state[i], m->land_cap_state[i], (size_t)a->shard[i]->n_pixslots * (ACCUM_SLOT_BYTES / 4)); if (r != RT_OK) return r; }
-    // from here on the devices' states are being overwritten: a failure leaves the object broken
-    a->loads++;
-    hipError_t e = hipMemcpyAsync(m->frame_state, (const uint8_t *)blob + ACCUM_HEADER_BYTES, state, hipMemcpyHostToDevice, s0);
-    for (int i = 0; i < N && e == hipSuccess; i++) {
-        if (!a->shard[i]) continue;
-        const Regroup G = regroup_of(a, i);
-        hipLaunchKernelGGL(frame_to_shard_kernel, dim3(regroup_blocks(G.n_slots)), dim3(256), 0, s0, m->frame_state, i ? m->land_state[i] : a->shard[0]->d_state, G);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipEventRecord(m->state_ready, s0);
-    for (int i = 1; i < N && e == hipSuccess; i++) {
-        if (!a->shard[i]) continue;
-        e = hipSetDevice(m->dev[i].device);
-        if (e == hipSuccess) e = hipStreamWaitEvent(m->dev[i].stream, m->state_ready, 0);
-        if (e == hipSuccess) e = hipMemcpyPeerAsync(a->shard[i]->d_state, m->dev[i].device, m->land_state[i], dev0, (size_t)a->shard[i]->n_pixslots * ACCUM_SLOT_BYTES, m->dev[i].stream);
-    }
-    for (int i = N - 1; i >= 0 && e == hipSuccess; i--) { // device 0 last: it becomes the current device again
-        if (!a->shard[i]) continue;
-        e = hipSetDevice(m->dev[i].device);
-        if (e == hipSuccess) e = hipStreamSynchronize(m->dev[i].stream);
-    }
-    if (e != hipSuccess) {
-        (void)hipSetDevice(dev0);
-        fail(RT_ERR_HIP, std::string("rt_multi_accum_load: ") + hipGetErrorString(e));
-        MA_BREAK(RT_ERR_HIP);
-    }
-    for (int i = 0; i < N; i++) if (a->shard[i]) a->shard[i]->samples = (int32_t)got[AH_SAMPLES];
-    a->samples = (int32_t)got[AH_SAMPLES];
-    return RT_OK;
+    });
 }
 
 } // extern "C"

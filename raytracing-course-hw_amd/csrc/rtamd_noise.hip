@@ -52,20 +52,22 @@ RenderView noise_frame(const rt_noise *n) {
     return R;
 }
 
+// The refusal every call makes of a monitor whose accumulator is broken.
+int noise_usable(const rt_accum *a, const std::string &who) {
+    if (!a->broken.empty()) return fail(RT_ERR_INVALID_ARG, who + "the accumulator is broken: an earlier slice failed and left the state half advanced (" + a->broken + ")");
+    return RT_OK;
+}
+
+// The launches below run on the accumulator's stream; its device is the current one (the entry points and each_device see to that).
 // create / reset: the sums as they are, no batch yet
 int noise_snapshot(rt_noise *n, const std::string &who) {
     rt_accum *a = n->accum;
-    if (!a->broken.empty()) return fail(RT_ERR_INVALID_ARG, who + "the accumulator is broken: an earlier slice failed and left the state half advanced (" + a->broken + ")");
-    try {
-        HIP_CHECK(hipSetDevice(a->scene->device));
-        hipStream_t stream = (hipStream_t)a->params.stream;
-        if (a->n_pixslots) {
-            hipLaunchKernelGGL(dev::noise_snapshot_kernel, dim3(noise_blocks(a->n_pixslots)), dim3(256), 0, stream, noise_frame(n), noise_view(n));
-            HIP_CHECK(hipGetLastError());
-            HIP_CHECK(hipStreamSynchronize(stream));
-        }
-    } catch (const HipError &e) {
-        return fail(RT_ERR_HIP, who + e.what());
+    if (const int rc = noise_usable(a, who)) return rc;
+    hipStream_t stream = (hipStream_t)a->params.stream;
+    if (a->n_pixslots) {
+        hipLaunchKernelGGL(dev::noise_snapshot_kernel, dim3(noise_blocks(a->n_pixslots)), dim3(256), 0, stream, noise_frame(n), noise_view(n));
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipStreamSynchronize(stream));
     }
     n->batches = 0; n->observed = 0;
     n->samples_seen = a->samples; n->loads_seen = a->loads;
@@ -75,35 +77,29 @@ int noise_snapshot(rt_noise *n, const std::string &who) {
 // what rt_noise_update refuses, before anything is launched: the statistics stay as they were
 int noise_update_check(const rt_noise *n, const std::string &who) {
     const rt_accum *a = n->accum;
-    if (!a->broken.empty()) return fail(RT_ERR_INVALID_ARG, who + "the accumulator is broken: an earlier slice failed and left the state half advanced (" + a->broken + ")");
+    if (const int rc = noise_usable(a, who)) return rc;
     if (a->loads != n->loads_seen) return fail(RT_ERR_INVALID_ARG, who + "rt_accum_load has replaced the state since the monitor's last snapshot: its batches do not continue, call rt_noise_reset");
     if (a->samples <= n->samples_seen) return fail(RT_ERR_INVALID_ARG, who + "no samples since the last update (a batch needs at least one)");
     return RT_OK;
 }
 
-int noise_update(rt_noise *n, const std::string &who) {
+void noise_update(rt_noise *n) {
     rt_accum *a = n->accum;
     const int32_t batch = a->samples - n->samples_seen;
-    try {
-        HIP_CHECK(hipSetDevice(a->scene->device));
-        hipStream_t stream = (hipStream_t)a->params.stream;
-        if (a->n_pixslots) {
-            NoiseView V = noise_view(n);
-            V.n = (float)batch; V.N = (float)n->observed; V.N1 = (float)(n->observed + batch); V.first = n->observed == 0;
-            hipLaunchKernelGGL(dev::noise_update_kernel, dim3(noise_blocks(a->n_pixslots)), dim3(256), 0, stream, noise_frame(n), V);
-            HIP_CHECK(hipGetLastError());
-            HIP_CHECK(hipStreamSynchronize(stream));
-        }
-    } catch (const HipError &e) {
-        return fail(RT_ERR_HIP, who + e.what());
+    hipStream_t stream = (hipStream_t)a->params.stream;
+    if (a->n_pixslots) {
+        NoiseView V = noise_view(n);
+        V.n = (float)batch; V.N = (float)n->observed; V.N1 = (float)(n->observed + batch); V.first = n->observed == 0;
+        hipLaunchKernelGGL(dev::noise_update_kernel, dim3(noise_blocks(a->n_pixslots)), dim3(256), 0, stream, noise_frame(n), V);
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipStreamSynchronize(stream));
     }
     n->batches += 1; n->observed += batch; n->samples_seen = a->samples;
-    return RT_OK;
 }
 
 int noise_estimate_check(const rt_noise *n, const std::string &who) {
     const rt_accum *a = n->accum;
-    if (!a->broken.empty()) return fail(RT_ERR_INVALID_ARG, who + "the accumulator is broken: an earlier slice failed and left the state half advanced (" + a->broken + ")");
+    if (const int rc = noise_usable(a, who)) return rc;
     if (a->loads != n->loads_seen) return fail(RT_ERR_INVALID_ARG, who + "rt_accum_load has replaced the state since the monitor's last snapshot: call rt_noise_reset");
     if (n->batches < 2) return fail(RT_ERR_INVALID_ARG, who + std::to_string(n->batches) + " batches so far: the scatter of batch means needs at least 2");
     return RT_OK;
@@ -115,11 +111,10 @@ size_t noise_map_elems(const rt_noise *n) {
     return R.shard_count > 1 ? (size_t)n->accum->n_pixslots : (size_t)R.width * R.height;
 }
 
-// Launches the estimate on the monitor's device and stream: the map to `d_se` (device memory, nullable), the sub-tile entries to `tiles`
+// Launches the estimate on the monitor's stream: the map to `d_se` (device memory, nullable), the sub-tile entries to `tiles`
 // (host, n_pixslots / 64).  Returns with the copies queued; the caller synchronises the stream.
 void noise_estimate_launch(rt_noise *n, float *d_se, NoiseTile *tiles) {
     rt_accum *a = n->accum;
-    HIP_CHECK(hipSetDevice(a->scene->device));
     hipStream_t stream = (hipStream_t)a->params.stream;
     if (!a->n_pixslots) return;
     NoiseView V = noise_view(n);
@@ -177,20 +172,18 @@ extern "C" {
 int rt_noise_create(rt_accum *a, rt_noise **out) {
     if (!a || !out) return fail(RT_ERR_INVALID_ARG, "rt_noise_create: null argument");
     *out = nullptr;
-    std::unique_ptr<rt_noise> n(new rt_noise);
-    n->accum = a;
-    try {
+    return guarded("rt_noise_create: ", [&]() -> int {
+        std::unique_ptr<rt_noise> n(new rt_noise);
+        n->accum = a;
         HIP_CHECK(hipSetDevice(a->scene->device));
         const size_t slots = a->n_pixslots ? a->n_pixslots : 64u;
         HIP_CHECK(hipMalloc((void **)&n->d_stats, 3 * slots * sizeof(float)));
         HIP_CHECK(hipMalloc((void **)&n->d_tiles, (slots / 64u) * sizeof(NoiseTile)));
         HIP_CHECK(hipMemsetAsync(n->d_stats, 0, 3 * slots * sizeof(float), (hipStream_t)a->params.stream)); // padding slots are never written again
-    } catch (const HipError &e) {
-        return fail(RT_ERR_HIP, std::string("rt_noise_create: ") + e.what());
-    }
-    if (const int rc = noise_snapshot(n.get(), "rt_noise_create: ")) return rc;
-    *out = n.release();
-    return RT_OK;
+        if (const int rc = noise_snapshot(n.get(), "rt_noise_create: ")) return rc;
+        *out = n.release();
+        return RT_OK;
+    });
 }
 
 void rt_noise_destroy(rt_noise *n) {
@@ -200,7 +193,10 @@ void rt_noise_destroy(rt_noise *n) {
 
 int rt_noise_reset(rt_noise *n) {
     if (!n) return fail(RT_ERR_INVALID_ARG, "rt_noise_reset: null argument");
-    return noise_snapshot(n, "rt_noise_reset: ");
+    return guarded("rt_noise_reset: ", [&]() -> int {
+        HIP_CHECK(hipSetDevice(n->accum->scene->device));
+        return noise_snapshot(n, "rt_noise_reset: ");
+    });
 }
 
 int rt_noise_batches(const rt_noise *n) {
@@ -210,28 +206,28 @@ int rt_noise_batches(const rt_noise *n) {
 
 int rt_noise_update(rt_noise *n) {
     if (!n) return fail(RT_ERR_INVALID_ARG, "rt_noise_update: null argument");
-    if (const int rc = noise_update_check(n, "rt_noise_update: ")) return rc;
-    return noise_update(n, "rt_noise_update: ");
+    return guarded("rt_noise_update: ", [&]() -> int {
+        if (const int rc = noise_update_check(n, "rt_noise_update: ")) return rc;
+        HIP_CHECK(hipSetDevice(n->accum->scene->device));
+        noise_update(n);
+        return RT_OK;
+    });
 }
 
 int rt_noise_estimate(rt_noise *n, uint32_t flags, float *out_se, rt_noise_summary *summary) {
     if (summary && summary->struct_size != sizeof(rt_noise_summary)) return fail(RT_ERR_INVALID_ARG, "rt_noise_estimate: struct_size mismatch (ABI skew)");
     if (!n) return fail(RT_ERR_INVALID_ARG, "rt_noise_estimate: null argument");
     if (flags & ~RT_FLAG_OUT_DEVICE) return fail(RT_ERR_INVALID_ARG, "rt_noise_estimate: flags other than RT_FLAG_OUT_DEVICE");
-    if (const int rc = noise_estimate_check(n, "rt_noise_estimate: ")) return rc;
-    if (!out_se && !summary) return RT_OK;
-    rt_accum *a = n->accum;
-    OwnedDev se_buf;
-    try {
+    return guarded("rt_noise_estimate: ", [&]() -> int {
+        if (const int rc = noise_estimate_check(n, "rt_noise_estimate: ")) return rc;
+        if (!out_se && !summary) return RT_OK;
+        rt_accum *a = n->accum;
         HIP_CHECK(hipSetDevice(a->scene->device));
         hipStream_t stream = (hipStream_t)a->params.stream;
-        const bool out_dev = (flags & RT_FLAG_OUT_DEVICE) != 0;
-        const size_t elems = noise_map_elems(n);
-        float *d_se = out_se;
-        if (out_se && !out_dev) { HIP_CHECK(hipMalloc(&se_buf.p, (elems ? elems : 1) * sizeof(float))); d_se = (float *)se_buf.p; }
+        StagedOut se(out_se, flags, noise_map_elems(n), sizeof(float));
         std::vector<NoiseTile> tiles(a->n_pixslots / 64u);
-        noise_estimate_launch(n, d_se, tiles.data());
-        if (se_buf.p && elems) HIP_CHECK(hipMemcpyAsync(out_se, se_buf.p, elems * sizeof(float), hipMemcpyDeviceToHost, stream));
+        noise_estimate_launch(n, (float *)se.dev, tiles.data());
+        se.copy_back(stream);
         HIP_CHECK(hipStreamSynchronize(stream));
         if (summary) {
             std::vector<NoiseTile> frame(noise_frame_subtiles(a->view), NoiseTile{0.f, 0.f, 0u, 0u});
@@ -239,11 +235,7 @@ int rt_noise_estimate(rt_noise *n, uint32_t flags, float *out_se, rt_noise_summa
             noise_summarise(frame, n, summary);
         }
         return RT_OK;
-    } catch (const HipError &e) {
-        return fail(RT_ERR_HIP, std::string("rt_noise_estimate: ") + e.what());
-    } catch (const std::exception &e) { // std::bad_alloc: nothing may cross the C boundary
-        return fail(RT_ERR_INVALID_ARG, std::string("rt_noise_estimate: ") + e.what());
-    }
+    });
 }
 
 // ---- the same on an rt_multi_accum: one rt_noise per non-empty shard, each on that shard's device and stream ----------------------------
@@ -252,11 +244,14 @@ int rt_noise_estimate(rt_noise *n, uint32_t flags, float *out_se, rt_noise_summa
     if (!n) return fail(RT_ERR_INVALID_ARG, name ": null argument");                                                                          \
     if (!n->accum->broken.empty()) return fail(RT_ERR_INVALID_ARG, name ": the accumulator is broken: an earlier call failed under way and left the state half advanced (" + n->accum->broken + ")")
 
+// the HIP device of shard i's monitor, -1 for an empty shard (each_device)
+static int noise_device(const rt_multi_noise *n, size_t i) { return n->shard[i] ? n->shard[i]->accum->scene->device : -1; }
+
 int rt_multi_noise_create(rt_multi_accum *a, rt_multi_noise **out) {
     if (!a || !out) return fail(RT_ERR_INVALID_ARG, "rt_multi_noise_create: null argument");
     *out = nullptr;
-    if (!a->broken.empty()) return fail(RT_ERR_INVALID_ARG, "rt_multi_noise_create: the accumulator is broken: an earlier call failed under way and left the state half advanced (" + a->broken + ")");
-    try {
+    return guarded("rt_multi_noise_create: ", [&]() -> int {
+        if (!a->broken.empty()) return fail(RT_ERR_INVALID_ARG, "rt_multi_noise_create: the accumulator is broken: an earlier call failed under way and left the state half advanced (" + a->broken + ")");
         std::unique_ptr<rt_multi_noise> n(new rt_multi_noise);
         n->accum = a;
         n->shard.assign(a->shard.size(), nullptr);
@@ -267,21 +262,21 @@ int rt_multi_noise_create(rt_multi_accum *a, rt_multi_noise **out) {
         (void)hipSetDevice(a->shard[0]->scene->device);
         *out = n.release();
         return RT_OK;
-    } catch (const std::exception &e) {
-        return fail(RT_ERR_INVALID_ARG, std::string("rt_multi_noise_create: ") + e.what());
-    }
+    });
 }
 
 void rt_multi_noise_destroy(rt_multi_noise *n) { delete n; }
 
 int rt_multi_noise_reset(rt_multi_noise *n) {
-    MN_ENTER("rt_multi_noise_reset");
-    for (size_t i = 0; i < n->shard.size(); i++)
-        if (n->shard[i])
-            if (const int rc = noise_snapshot(n->shard[i], "rt_multi_noise_reset: shard " + std::to_string(i) + ": ")) return rc;
-    n->loads_seen = n->accum->loads;
-    (void)hipSetDevice(n->accum->shard[0]->scene->device);
-    return RT_OK;
+    return guarded("rt_multi_noise_reset: ", [&]() -> int {
+        MN_ENTER("rt_multi_noise_reset");
+        const int rc = each_device(n->shard.size(), [&](size_t i) { return noise_device(n, i); }, [&](size_t i) {
+            const std::string who = "rt_multi_noise_reset: shard " + std::to_string(i) + ": ";
+            return guarded(who, [&]() -> int { return noise_snapshot(n->shard[i], who); });
+        });
+        if (rc == RT_OK) n->loads_seen = n->accum->loads;
+        return rc;
+    });
 }
 
 int rt_multi_noise_batches(const rt_multi_noise *n) {
@@ -290,47 +285,43 @@ int rt_multi_noise_batches(const rt_multi_noise *n) {
 }
 
 int rt_multi_noise_update(rt_multi_noise *n) {
-    MN_ENTER("rt_multi_noise_update");
-    if (n->accum->loads != n->loads_seen) return fail(RT_ERR_INVALID_ARG, "rt_multi_noise_update: rt_multi_accum_load has replaced the state since the monitor's last snapshot: its batches do not continue, call rt_multi_noise_reset");
-    for (rt_noise *s : n->shard) // every refusal before any device launches
-        if (s) if (const int rc = noise_update_check(s, "rt_multi_noise_update: ")) return rc;
-    for (size_t i = 0; i < n->shard.size(); i++)
-        if (n->shard[i])
-            if (const int rc = noise_update(n->shard[i], "rt_multi_noise_update: shard " + std::to_string(i) + ": ")) return rc;
-    (void)hipSetDevice(n->accum->shard[0]->scene->device);
-    return RT_OK;
+    return guarded("rt_multi_noise_update: ", [&]() -> int {
+        MN_ENTER("rt_multi_noise_update");
+        if (n->accum->loads != n->loads_seen) return fail(RT_ERR_INVALID_ARG, "rt_multi_noise_update: rt_multi_accum_load has replaced the state since the monitor's last snapshot: its batches do not continue, call rt_multi_noise_reset");
+        for (rt_noise *s : n->shard) // every refusal before any device launches
+            if (s) if (const int rc = noise_update_check(s, "rt_multi_noise_update: ")) return rc;
+        return each_device(n->shard.size(), [&](size_t i) { return noise_device(n, i); }, [&](size_t i) {
+            return guarded("rt_multi_noise_update: shard " + std::to_string(i) + ": ", [&]() -> int { noise_update(n->shard[i]); return RT_OK; });
+        });
+    });
 }
 
 int rt_multi_noise_estimate(rt_multi_noise *n, uint32_t flags, float *out_se, rt_noise_summary *summary) {
     if (summary && summary->struct_size != sizeof(rt_noise_summary)) return fail(RT_ERR_INVALID_ARG, "rt_multi_noise_estimate: struct_size mismatch (ABI skew)");
-    MN_ENTER("rt_multi_noise_estimate");
-    if (flags) return fail(RT_ERR_INVALID_ARG, "rt_multi_noise_estimate: flags must be 0 (the outputs are host memory)");
-    if (n->accum->loads != n->loads_seen) return fail(RT_ERR_INVALID_ARG, "rt_multi_noise_estimate: rt_multi_accum_load has replaced the state since the monitor's last snapshot: call rt_multi_noise_reset");
-    for (rt_noise *s : n->shard)
-        if (s) if (const int rc = noise_estimate_check(s, "rt_multi_noise_estimate: ")) return rc;
-    if (!out_se && !summary) return RT_OK;
-    const size_t N = n->shard.size();
-    const int width = n->accum->params.width, height = n->accum->params.height;
-    std::vector<OwnedDev> se_buf(N);
-    try {
+    return guarded("rt_multi_noise_estimate: ", [&]() -> int {
+        MN_ENTER("rt_multi_noise_estimate");
+        if (flags) return fail(RT_ERR_INVALID_ARG, "rt_multi_noise_estimate: flags must be 0 (the outputs are host memory)");
+        if (n->accum->loads != n->loads_seen) return fail(RT_ERR_INVALID_ARG, "rt_multi_noise_estimate: rt_multi_accum_load has replaced the state since the monitor's last snapshot: call rt_multi_noise_reset");
+        for (rt_noise *s : n->shard)
+            if (s) if (const int rc = noise_estimate_check(s, "rt_multi_noise_estimate: ")) return rc;
+        if (!out_se && !summary) return RT_OK;
+        const size_t N = n->shard.size();
+        const int width = n->accum->params.width, height = n->accum->params.height;
+        const auto device_of = [&](size_t i) { return noise_device(n, i); };
         std::vector<std::vector<NoiseTile>> tiles(N);
         std::vector<std::vector<float>> se(N);
-        for (size_t i = 0; i < N; i++) { // every device works on its own stream; the waits come after the last launch
+        std::vector<StagedOut> staged; // one per shard, freed on every way out
+        staged.reserve(N);
+        each_device(N, device_of, [&](size_t i) { // every device works on its own stream; the waits come after the last launch
             rt_noise *s = n->shard[i];
-            if (!s) continue;
-            HIP_CHECK(hipSetDevice(s->accum->scene->device));
-            const size_t elems = noise_map_elems(s);
-            if (out_se) { HIP_CHECK(hipMalloc(&se_buf[i].p, (elems ? elems : 1) * sizeof(float))); se[i].resize(elems); }
+            if (out_se) se[i].resize(noise_map_elems(s));
+            staged.emplace_back(se[i].data(), 0u, se[i].size(), sizeof(float));
             tiles[i].resize(s->accum->n_pixslots / 64u);
-            noise_estimate_launch(s, (float *)se_buf[i].p, tiles[i].data());
-            if (out_se && elems) HIP_CHECK(hipMemcpyAsync(se[i].data(), se_buf[i].p, elems * sizeof(float), hipMemcpyDeviceToHost, (hipStream_t)s->accum->params.stream));
-        }
-        for (size_t i = N; i-- > 0;) { // device 0 last: it becomes the current device again
-            rt_noise *s = n->shard[i];
-            if (!s) continue;
-            HIP_CHECK(hipSetDevice(s->accum->scene->device));
-            HIP_CHECK(hipStreamSynchronize((hipStream_t)s->accum->params.stream));
-        }
+            noise_estimate_launch(s, (float *)staged.back().dev, tiles[i].data());
+            staged.back().copy_back((hipStream_t)s->accum->params.stream);
+            return RT_OK;
+        });
+        each_device(N, device_of, [&](size_t i) { HIP_CHECK(hipStreamSynchronize((hipStream_t)n->shard[i]->accum->params.stream)); return RT_OK; });
         if (out_se) { // the shards' compact maps -> the frame, on the host
             for (size_t i = 0; i < N; i++) {
                 if (!n->shard[i]) continue;
@@ -353,12 +344,7 @@ int rt_multi_noise_estimate(rt_multi_noise *n, uint32_t flags, float *out_se, rt
             noise_summarise(frame, n->shard[0], summary);
         }
         return RT_OK;
-    } catch (const HipError &e) {
-        (void)hipSetDevice(n->accum->shard[0]->scene->device);
-        return fail(RT_ERR_HIP, std::string("rt_multi_noise_estimate: ") + e.what());
-    } catch (const std::exception &e) {
-        return fail(RT_ERR_INVALID_ARG, std::string("rt_multi_noise_estimate: ") + e.what());
-    }
+    });
 }
 
 } // extern "C"

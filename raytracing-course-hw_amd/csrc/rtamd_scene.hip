@@ -337,7 +337,7 @@ int rtamd::scene_create_shared(const rt_scene_desc *desc, rt_scene **out, rtamd:
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
         return fail(RT_ERR_NO_DEVICE, "rt_scene_create: no HIP device available (this library has no CPU fallback)");
-    try {
+    return guarded("", [&]() -> int { // the preparation's refusals and HIP's failures name themselves
         std::unique_ptr<rt_scene> s(new rt_scene());
         HIP_CHECK(hipGetDevice(&s->device));
         hipDeviceProp_t prop;
@@ -349,11 +349,7 @@ int rtamd::scene_create_shared(const rt_scene_desc *desc, rt_scene **out, rtamd:
         // A scene without per-vertex normals can only be an hw6 scene.
         if (desc->n_triangles && !desc->normals) return create_hw6(desc, s, out, t0);
         return create_hw8(desc, s, out, t0, shared);
-    } catch (const HipError &e) {
-        return fail(RT_ERR_HIP, e.what());
-    } catch (const std::exception &e) {
-        return fail(RT_ERR_INVALID_ARG, e.what());
-    }
+    });
 }
 
 extern "C" {
@@ -380,7 +376,7 @@ int rt_scene_get_light_order(const rt_scene *scene, uint32_t *out, uint32_t capa
 int rt_host_prepare_orders(const rt_scene_desc *desc, int integrator, uint32_t *figure_order, uint32_t figure_capacity,
                            uint32_t *light_order, uint32_t light_capacity) {
     if (!desc || desc->struct_size != sizeof(rt_scene_desc)) return fail(RT_ERR_INVALID_ARG, "rt_host_prepare_orders: bad desc");
-    try {
+    return guarded("rt_host_prepare_orders: ", [&]() -> int {
         std::vector<uint32_t> fo, lo;
         if (integrator == RT_INTEGRATOR_HW8 || integrator == RT_INTEGRATOR_HW7) { PreparedScene P; prepare_scene(*desc, P); fo = P.figure_order; lo = P.light_order; }
         else if (integrator == RT_INTEGRATOR_HW6) { PreparedScene6 P; prepare_scene_hw6(*desc, P); fo = P.figure_order; lo = P.light_order; }
@@ -390,13 +386,12 @@ int rt_host_prepare_orders(const rt_scene_desc *desc, int integrator, uint32_t *
         if (figure_order) memcpy(figure_order, fo.data(), fo.size() * sizeof(uint32_t));
         if (light_order) memcpy(light_order, lo.data(), lo.size() * sizeof(uint32_t));
         return (int)lo.size();
-    } catch (const std::exception &e) {
-        return fail(RT_ERR_INVALID_ARG, std::string("rt_host_prepare_orders: ") + e.what());
-    }
+    });
 }
 
 int rt_unshard(const rt_render_params *p, const void *shard_buf, size_t elem_size, void *full_image) {
     if (!p || !shard_buf || !full_image || (elem_size != 1 && elem_size != 4)) return fail(RT_ERR_INVALID_ARG, "rt_unshard: bad argument");
+    return guarded("rt_unshard: ", [&]() -> int {
     RenderView R{};
     std::string err;
     if (!resolve_tiles(p, R, err)) return fail(RT_ERR_INVALID_ARG, "rt_unshard: " + err);
@@ -411,41 +406,30 @@ int rt_unshard(const rt_render_params *p, const void *shard_buf, size_t elem_siz
             memcpy(dst + ((size_t)(ty0 + ly) * R.width + tx0) * px, src + (((size_t)st * R.tile_h + ly) * R.tile_w) * px, (size_t)w * px);
     }
     return RT_OK;
+    });
 }
 
 // ---- host-side front-end ---------------------------------------------------------------------------
 int rt_load_gltf(const char *path, int flavor, rt_host_scene **out) {
     if (!path || !out) return fail(RT_ERR_INVALID_ARG, "rt_load_gltf: null argument");
     *out = nullptr;
-    try {
-        *out = load_gltf(path, flavor);
-        return RT_OK;
-    } catch (const std::exception &e) {
-        return fail(RT_ERR_PARSE, std::string("rt_load_gltf(") + path + "): " + e.what());
-    }
+    return guarded(std::string("rt_load_gltf(") + path + "): ", [&]() -> int { *out = load_gltf(path, flavor); return RT_OK; }, RT_ERR_PARSE);
 }
 int rt_load_txt(const char *path, int flavor, rt_host_scene **out, int32_t *w, int32_t *h, int32_t *samples, int32_t *depth) {
     if (!path || !out) return fail(RT_ERR_INVALID_ARG, "rt_load_txt: null argument");
     *out = nullptr;
-    try {
-        *out = load_txt(path, flavor, w, h, samples, depth);
-        return RT_OK;
-    } catch (const std::exception &e) {
-        return fail(RT_ERR_PARSE, std::string("rt_load_txt(") + path + "): " + e.what());
-    }
+    return guarded(std::string("rt_load_txt(") + path + "): ", [&]() -> int { *out = load_txt(path, flavor, w, h, samples, depth); return RT_OK; }, RT_ERR_PARSE);
 }
 int rt_host_scene_set_environment(rt_host_scene *hs, const char *image_path) {
     if (!hs || !image_path) return fail(RT_ERR_INVALID_ARG, "rt_host_scene_set_environment: null argument");
-    try {
+    return guarded("", [&]() -> int {
         int w, h;
         load_image_rgb8(image_path, w, h, hs->env_data);
         hs->env = rt_image{w, h, nullptr};
         hs->has_env = true;
         hs->finalize();
         return RT_OK;
-    } catch (const std::exception &e) {
-        return fail(RT_ERR_IO, e.what());
-    }
+    }, RT_ERR_IO);
 }
 const rt_scene_desc *rt_host_scene_desc(const rt_host_scene *hs) { return hs ? &hs->desc : nullptr; }
 void rt_host_scene_free(rt_host_scene *hs) { delete hs; }
@@ -462,7 +446,7 @@ int rt_write_ppm(const char *path, int32_t width, int32_t height, const uint8_t 
 }
 int rt_decode_png(const char *path, int32_t *width, int32_t *height, uint8_t **rgb) {
     if (!path || !width || !height || !rgb) return fail(RT_ERR_INVALID_ARG, "rt_decode_png: null argument");
-    try {
+    return guarded("", [&]() -> int {
         std::vector<uint8_t> px;
         int w, h;
         load_image_rgb8(path, w, h, px);
@@ -471,9 +455,7 @@ int rt_decode_png(const char *path, int32_t *width, int32_t *height, uint8_t **r
         memcpy(*rgb, px.data(), px.size());
         *width = w; *height = h;
         return RT_OK;
-    } catch (const std::exception &e) {
-        return fail(RT_ERR_IO, e.what());
-    }
+    }, RT_ERR_IO);
 }
 void rt_free(void *p) { free(p); }
 

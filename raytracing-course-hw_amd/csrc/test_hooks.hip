@@ -8,7 +8,9 @@
 #include "device/rt_pt_queue.h"
 #include "device/rt_ref_walk.h"
 #include "host/fold_nodes.h"
+#include "host/rt_guard.h"
 #include <cstring>
+#include <new>
 #include <vector>
 
 using namespace rtamd::dev;
@@ -329,5 +331,16 @@ int rtt_frame_sum(const uint32_t *nodes, uint32_t n_nodes, const uint32_t *roots
     }
     (void)hipFree(d_nodes); (void)hipFree(d_roots); (void)hipFree(d_out);
     return rc;
+}
+// The guard of the C boundary (host/rt_guard.h) around a body that throws a HipError (kind 0), a std::bad_alloc (1), a std::runtime_error (2)
+// or an int (3), or returns 5 (anything else): the guard's answer; the message is in the library's rt_last_error().  Host only.
+int rtt_guard_probe(int kind) {
+    return rtamd::guarded("rtt_guard_probe: ", [&]() -> int {
+        if (kind == 0) throw rtamd::HipError("hipProbe(): failed");
+        if (kind == 1) throw std::bad_alloc();
+        if (kind == 2) throw std::runtime_error("a runtime error");
+        if (kind == 3) throw 7;
+        return 5;
+    });
 }
 }
