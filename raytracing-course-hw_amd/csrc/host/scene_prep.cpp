@@ -12,6 +12,14 @@
 //                      that order (rt_types.h); boxes are padded so the kernel's fast slab test is
 //                      conservative, triangle records carry host-evaluated reference sub-expressions.
 //
+// The stages, each written once for the flavours (prepare_scene: hw8 / hw7, _hw6, _hw5, _txt: hw1 .. hw4):
+//   triangle_stage    the refusals, the sort keys (data3), the boxes and the largest coordinate of the triangles
+//   RefTree           the reference's builder over a prefix of an order -> nodes + depth; build_light_tree: "partition a
+//                     copy, build over the front" for the three light lists
+//   encode_both       a RefTree as padded GpuNodes and as GpuRefNodes; put_box8, put_leaf_boxes (boxes as 8 floats), mark_leaf_ends
+//   tri_frame         a, b, c, n of a triangle, for make_isect, Tri6, LightRec and point_prob
+//   build_tripwires   the tripwire records from the TriIsect records, walk_box and the largest coordinate
+//
 // Build with -ffp-contract=off (reference float semantics for the precomputed sub-expressions).
 #include "scene_prep.h"
 #include "knobs.h"
@@ -21,6 +29,7 @@
 #include <cstring>
 #include <cstdlib>
 #include <limits>
+#include <numeric>
 #include <stdexcept>
 #include <thread>
 
@@ -42,20 +51,15 @@ inline void grow(Box3 &b, const Box3 &o) {
 
 // Reference-topology builder over an index permutation.
 struct RefNode { Box3 box; uint32_t left = 0, right = 0, first = 0, last = 0; };
-
-class RefBuilder {
+// The reference's tree over the first n entries of `order`, built on construction: `nodes` in the builder's preorder numbering (left == 0
+// marks a leaf) and `depth`.  The builder's scratch lives as long as the tree.
+class RefTree {
 public:
     // keys[axis][tri] = data3 coordinate, boxes[tri] = triangle AABB; `order` is permuted in place.
-    RefBuilder(const std::vector<float> *keys, const std::vector<Box3> &boxes, std::vector<uint32_t> &order)
-        : keys_(keys), boxes_(boxes), order_(order), pairs_(order.size()), scores_(order.size()), suffix_(order.size()) {}
-
+    RefTree(const std::vector<float> *keys, const std::vector<Box3> &boxes, std::vector<uint32_t> &order, uint32_t n)
+        : keys_(keys), boxes_(boxes), order_(order), pairs_(order.size()), scores_(order.size()) { depth = build(0, n, 1, nodes, 0); }
     std::vector<RefNode> nodes;
     uint32_t depth = 0;
-
-    // The two subtrees of a node work on disjoint ranges of every array, so the large ones near the root are built on
-    // separate threads into their own node lists and spliced in afterwards in the reference's (preorder) numbering.
-    void run(uint32_t n) { nodes.clear(); depth = 0; depth = build(0, n, 1, nodes, 0); }
-
 private:
     struct KI { float k; uint32_t i; };
     const std::vector<float> *keys_;
@@ -63,7 +67,6 @@ private:
     std::vector<uint32_t> &order_;
     std::vector<KI> pairs_;
     std::vector<float> scores_;
-    std::vector<float> suffix_;
 
     void sort_axis(uint32_t first, uint32_t last, int axis) { // bvh.h:60-65
         const std::vector<float> &key = keys_[axis];
@@ -90,7 +93,8 @@ private:
             if (sc[i] < ans.first) ans = {sc[i], (uint32_t)(first + i)};
         return ans;
     }
-    // Builds the subtree over [first,last) into `out` (indices relative to `out`); returns its depth.
+    // Builds the subtree over [first,last) into `out` (indices relative to `out`); returns its depth.  The two subtrees of a node work on disjoint ranges
+    // of every array, so the large ones near the root are built on separate threads into their own node lists and spliced in afterwards (preorder).
     uint32_t build(uint32_t first, uint32_t last, uint32_t d, std::vector<RefNode> &out, int fork_level) { // bvh.h:67-109
         uint32_t deepest = d;
         RefNode cur;
@@ -136,6 +140,22 @@ private:
     }
 };
 
+std::vector<uint32_t> identity_order(uint32_t n) { std::vector<uint32_t> order(n); std::iota(order.begin(), order.end(), 0u); return order; }
+// FiguresMix receives the reordered figure list BY VALUE, moves the lights to its front with std::partition and builds its tree over
+// them (hw8 and hw6 distributions.h:103-115, hw5 distributions.h:180-198); the front of that copy is the light order.
+template <class IsLight>
+RefTree build_light_tree(const std::vector<float> *keys, const std::vector<Box3> &boxes, const std::vector<uint32_t> &figure_order, IsLight is_light, std::vector<uint32_t> &light_order) {
+    std::vector<uint32_t> lorder = figure_order;
+    const uint32_t n_lights = (uint32_t)(std::partition(lorder.begin(), lorder.end(), is_light) - lorder.begin());
+    RefTree tree(keys, boxes, lorder, n_lights);
+    light_order.assign(lorder.begin(), lorder.begin() + n_lights);
+    return tree;
+}
+inline bool emissive_triangle(const rt_scene_desc &d, uint32_t tri) { // hw8 and hw6, distributions.h:104-109: the emission FACTOR decides, not the texture
+    const rt_material &m = d.materials[d.material_index[tri]];
+    return !(m.emission[0] == 0 && m.emission[1] == 0 && m.emission[2] == 0);
+}
+
 // Conservative padding for the kernels' reciprocal-multiply slab test: 2^-17 relative to the coordinate magnitude (64 ulp) on every
 // face, plus abs_pad = 2^-18 x the largest |coordinate| of scene and camera.  The absolute part is what makes the walk independent of
 // the tree: a triangle test accepts points up to a few ulp OF THE LARGEST COORDINATES INVOLVED outside the true triangle (p = o + t d),
@@ -149,20 +169,15 @@ inline void pad_box(const Box3 &b, float lo[3], float hi[3], float abs_pad) {
         hi[k] = b.hi[k] + pad;
     }
 }
-inline float scene_abs_pad(const std::vector<Box3> &boxes, const rt_camera &cam) {
-    float m = 0.f;
-    for (int k = 0; k < 3; k++) m = smax(m, std::fabs(cam.position[k]));
-    for (const Box3 &b : boxes) for (int k = 0; k < 3; k++) m = smax(m, smax(std::fabs(b.lo[k]), std::fabs(b.hi[k])));
-    const float scale = (float)env_float("RTAMD_BOX_PAD_SCALE", 1.0); // experiments
-    return m * 3.814697265625e-06f * scale; // 2^-18
-}
+// 2^-18 x the largest |coordinate|; the scale: experiments
+inline float scene_abs_pad(float max_coord) { return max_coord * 3.814697265625e-06f * (float)env_float("RTAMD_BOX_PAD_SCALE", 1.0); }
 
 // Re-encode a reference tree as two-box GpuNodes (child reference: inner node index, or
-// 0x80000000|first for a leaf, 0xFFFFFFFF for an empty leaf).  `leaf_last` receives the index of
-// the last primitive of every leaf; the kernels walk a leaf until they meet that mark.
-void encode_tree(const std::vector<RefNode> &ref, std::vector<GpuNode> &out, std::vector<uint32_t> &leaf_last, float abs_pad = 0.f) {
+// 0x80000000|first for a leaf, 0xFFFFFFFF for an empty leaf).  Returns the index of
+// the last primitive of every leaf: the kernels walk a leaf until they meet that mark.
+std::vector<uint32_t> encode_tree(const std::vector<RefNode> &ref, std::vector<GpuNode> &out, float abs_pad) {
     out.clear();
-    leaf_last.clear();
+    std::vector<uint32_t> leaf_last;
     auto empty_child = [](float lo[3], float hi[3], int32_t &child, int32_t &cnt) {
         for (int k = 0; k < 3; k++) { lo[k] = 3.0e38f; hi[k] = 3.0e38f; }
         child = (int32_t)0xFFFFFFFFu; cnt = 0;
@@ -176,7 +191,7 @@ void encode_tree(const std::vector<RefNode> &ref, std::vector<GpuNode> &out, std
         empty_child(g.lo0, g.hi0, g.child0, g.cnt0);
         empty_child(g.lo1, g.hi1, g.child1, g.cnt1);
         out.push_back(g);
-        return;
+        return leaf_last;
     }
     if (ref[0].left == 0) { // root is a leaf: wrap it
         GpuNode g;
@@ -184,7 +199,7 @@ void encode_tree(const std::vector<RefNode> &ref, std::vector<GpuNode> &out, std
         leaf_ref(ref[0], g.child0, g.cnt0);
         empty_child(g.lo1, g.hi1, g.child1, g.cnt1);
         out.push_back(g);
-        return;
+        return leaf_last;
     }
     // Inner reference nodes get GPU indices in DFS preorder (root = 0).
     std::vector<int32_t> gpu_index(ref.size(), -1);
@@ -203,6 +218,7 @@ void encode_tree(const std::vector<RefNode> &ref, std::vector<GpuNode> &out, std
         if (r.left == 0) leaf_ref(r, g.child1, g.cnt1);
         else { g.child1 = gpu_index[ref[i].right]; g.cnt1 = 0; }
     }
+    return leaf_last;
 }
 
 // The reference tree as the exact walks read it (unpadded boxes, preorder numbering of the builder).
@@ -215,6 +231,34 @@ void encode_ref_tree(const std::vector<RefNode> &ref, std::vector<GpuRefNode> &o
         g.left = ref[i].left; g.right = ref[i].right; g.first = ref[i].first; g.last = ref[i].last;
         g.pad0 = g.pad1 = 0;
     }
+}
+// A tree both ways, and its depth; returns the last record of every leaf.
+std::vector<uint32_t> encode_both(const RefTree &tree, float abs_pad, std::vector<GpuNode> &nodes, std::vector<GpuRefNode> &ref_nodes, uint32_t &depth) {
+    std::vector<uint32_t> leaf_last = encode_tree(tree.nodes, nodes, abs_pad);
+    encode_ref_tree(tree.nodes, ref_nodes);
+    depth = tree.depth;
+    return leaf_last;
+}
+// n records of an order: out[i] = make(i).
+template <class Rec, class Make> void fill_records(std::vector<Rec> &out, uint32_t n, Make make) { out.resize(n); for (uint32_t i = 0; i < n; i++) out[i] = make(i); }
+// mark(i) is the word of record i that tells the kernels where a leaf ends.
+template <class Mark> void mark_leaf_ends(const std::vector<uint32_t> &leaf_last, Mark mark) { for (uint32_t i : leaf_last) mark(i) |= 1u; }
+
+// A box as record i of 8 floats: lo.xyz, -, hi.xyz, -.
+inline void put_box8(std::vector<float> &out, size_t i, const Box3 &b) { for (int k = 0; k < 3; k++) { out[8 * i + k] = b.lo[k]; out[8 * i + 4 + k] = b.hi[k]; } }
+// n zeroed box records; one when there is none, which a device pointer can stand on.
+inline std::vector<float> box8_records(uint32_t n) { return std::vector<float>((size_t)(n ? n : 1) * 8, 0.f); }
+// Every figure's own box, in the order given.
+std::vector<float> own_boxes8(const std::vector<Box3> &boxes, const std::vector<uint32_t> &order) {
+    std::vector<float> out = box8_records((uint32_t)order.size());
+    for (size_t i = 0; i < order.size(); i++) put_box8(out, i, boxes[order[i]]);
+    return out;
+}
+// Per member of the tree's order the (unpadded) box of its reference leaf: member i is record i, or slot[i].
+void put_leaf_boxes(const RefTree &tree, std::vector<float> &out, const uint32_t *slot = nullptr) {
+    for (const RefNode &rn : tree.nodes)
+        if (rn.left == 0)
+            for (uint32_t i = rn.first; i < rn.last; i++) put_box8(out, slot ? slot[i] : i, rn.box);
 }
 
 // Renumber the inner nodes so that the first `top` of them are the top of the tree in breadth-first order (root = 0 stays):
@@ -252,13 +296,29 @@ inline V3 crossr(V3 a, V3 o) { return {a.z * o.y - a.y * o.z, a.x * o.z - a.z * 
 const float magic1[] = {0.239, 0.419, 0.533};       // primitives.cpp:82
 const float magic2[] = {0.35743, 0.66682, 0.69695}; // primitives.cpp:83
 
-TriIsect make_isect(const float *p /* data, data2, data3 */) {
-    V3 d0{p[0], p[1], p[2]}, d1{p[3], p[4], p[5]}, a{p[6], p[7], p[8]};
-    V3 b = sub(d0, a), c = sub(d1, a);
-    V3 n = crossr(b, c);
+// A triangle as every record holds it: a = data3, b = data - a, c = data2 - a, n = b.cross(c) (primitives.cpp:85-90).
+struct TriFrame { V3 a, b, c, n; };
+inline TriFrame tri_frame(const float *p /* data, data2, data3 */) {
+    const V3 a{p[6], p[7], p[8]}, b = sub(V3{p[0], p[1], p[2]}, a), c = sub(V3{p[3], p[4], p[5]}, a);
+    return {a, b, c, crossr(b, c)};
+}
+inline void put3(float out[3], V3 v) { out[0] = v.x; out[1] = v.y; out[2] = v.z; }
+// Shading normals of a triangle as base and deltas (primitives.cpp:110-117); left as they are without normals.
+inline void put_normals(const float *normals, uint32_t src, float n3[3], float dn1[3], float dn2[3]) {
+    const float *q = normals ? normals + 9 * (size_t)src : nullptr;
+    for (int k = 0; q && k < 3; k++) { n3[k] = q[6 + k]; dn1[k] = q[k] - q[6 + k]; dn2[k] = q[3 + k] - q[6 + k]; }
+}
+// TriangleLight's pointProb = 1 / area (hw8 distributions.h:78, hw6 distributions.h:126): |n| in float, its root and the quotient in double
+inline float point_prob(const TriFrame &f) {
+    const float nl = (float)std::sqrt((double)(f.n.x * f.n.x + f.n.y * f.n.y + f.n.z * f.n.z));
+    return (float)(1.0 / (0.5 * (double)nl));
+}
+
+TriIsect make_isect(const TriFrame &f) {
+    const V3 &b = f.b, &c = f.c;
     TriIsect t;
-    t.ax = a.x; t.ay = a.y; t.az = a.z;
-    t.nx = n.x; t.ny = n.y; t.nz = n.z;
+    t.ax = f.a.x; t.ay = f.a.y; t.az = f.a.z;
+    t.nx = f.n.x; t.ny = f.n.y; t.nz = f.n.z;
     t.a1 = magic1[0] * b.x + magic1[1] * b.y + magic1[2] * b.z;
     t.b1 = magic1[0] * c.x + magic1[1] * c.y + magic1[2] * c.z;
     t.a2 = magic2[0] * b.x + magic2[1] * b.y + magic2[2] * b.z;
@@ -266,6 +326,99 @@ TriIsect make_isect(const float *p /* data, data2, data3 */) {
     t.den = t.b1 * t.a2 - t.a1 * t.b2;
     t.pad = 0;
     return t;
+}
+
+// What hw8 and hw6 form from the nine floats of every triangle, after the refusals they share: the sort keys (the data3 vertex), the
+// boxes (primitives.cpp:130-141, hw6 primitives.cpp:173-183) and the largest |coordinate| of boxes and camera, which box_pad, box_c2 and
+// the tripwires' padding are multiples of.  `limit`, `too_many`: the flavour's own triangle limit and its refusal.
+struct TriStage { std::vector<float> keys[3]; std::vector<Box3> boxes; float max_coord = 0.f; };
+void triangle_stage(const rt_scene_desc &d, uint32_t limit, const char *too_many, TriStage &out) {
+    const uint32_t n = d.n_triangles;
+    if (n >= limit) throw std::runtime_error(too_many);
+    if (n && (!d.positions || !d.material_index)) throw std::runtime_error("scene has triangles but no positions/material_index");
+    for (uint32_t i = 0; i < n; i++)
+        if (d.material_index[i] >= d.n_materials) throw std::runtime_error("triangle material index out of range");
+    out.boxes.resize(n);
+    for (int k = 0; k < 3; k++) { out.keys[k].resize(n); out.max_coord = smax(out.max_coord, std::fabs(d.camera.position[k])); }
+    for (uint32_t i = 0; i < n; i++) {
+        const float *p = d.positions + 9 * (size_t)i;
+        for (int k = 0; k < 3; k++) {
+            out.keys[k][i] = p[6 + k]; // data3
+            out.boxes[i].lo[k] = smin(p[6 + k], smin(p[k], p[3 + k]));
+            out.boxes[i].hi[k] = smax(p[6 + k], smax(p[k], p[3 + k]));
+            out.max_coord = smax(out.max_coord, smax(std::fabs(out.boxes[i].lo[k]), std::fabs(out.boxes[i].hi[k])));
+        }
+    }
+}
+
+// The tripwires of scene_prep.h, from the TriIsect records and their reference leaf boxes (walk_box), both in figure order, and the
+// largest |coordinate| of scene and camera; returns the number of groups.
+uint32_t build_tripwires(const std::vector<TriIsect> &isect, const std::vector<float> &walk_box, float max_coord, std::vector<float> &tripwires) {
+    // |den| / (|n| |k|) = |cos| of the angle between the triangle's normal and the projection's kernel k = magic1 x magic2: how far
+    // outside the triangle the test can still accept a point grows like (rounding of the hit point) / cos.  Below 2^-14 (20 triangles of the
+    // benchmark scene; 8 lie below 1e-5, one at 4e-8: its test accepted a point 16 units away) the walkers' look-behind and the gate's
+    // window (rt_exact.h) no longer cover it; every ray pays for the test, so the list is kept short.
+    const uint32_t n = (uint32_t)isect.size();
+    const double m1[3] = {magic1[0], magic1[1], magic1[2]}, m2[3] = {magic2[0], magic2[1], magic2[2]}; // double arithmetic on the float values
+    const double kx = m1[1] * m2[2] - m1[2] * m2[1], ky = m1[2] * m2[0] - m1[0] * m2[2], kz = m1[0] * m2[1] - m1[1] * m2[0];
+    const double kn = std::sqrt(kx * kx + ky * ky + kz * kz);
+    const double tripwire_cos = env_float("RTAMD_TRIPWIRE_COS", 6.103515625e-05); // 2^-14
+    struct Wire { uint64_t key; Box3 box; uint32_t figure; };
+    std::vector<Wire> wires;
+    float slo[3] = {3e38f, 3e38f, 3e38f}, shi[3] = {-3e38f, -3e38f, -3e38f};
+    for (uint32_t i = 0; i < n; i++) for (int k = 0; k < 3; k++) { slo[k] = smin(slo[k], walk_box[8 * (size_t)i + k]); shi[k] = smax(shi[k], walk_box[8 * (size_t)i + 4 + k]); }
+    for (uint32_t i = 0; i < n; i++) {
+        const TriIsect &T = isect[i];
+        const double nn = std::sqrt((double)T.nx * T.nx + (double)T.ny * T.ny + (double)T.nz * T.nz);
+        if (!(nn > 0.0)) continue;                                       // no plane: its test never passes (t is NaN or infinite)
+        if (std::fabs((double)T.den) >= tripwire_cos * nn * kn) continue;
+        Wire w;
+        const float pad = 1e-4f * max_coord + 1e-30f;                    // far more than any rounding of the reference's box test
+        uint64_t key = 0;
+        for (int k = 0; k < 3; k++) {
+            w.box.lo[k] = walk_box[8 * (size_t)i + k] - pad; w.box.hi[k] = walk_box[8 * (size_t)i + 4 + k] + pad;
+            const double c = 0.5 * ((double)w.box.lo[k] + w.box.hi[k]), e = (double)shi[k] - slo[k];
+            const uint64_t q = e > 0 ? (uint64_t)std::fmin(1023.0, std::fmax(0.0, (c - slo[k]) / e * 1024.0)) : 0;
+            for (int b = 0; b < 10; b++) key |= ((q >> b) & 1ull) << (3 * b + k);       // Morton code: neighbours end up in one group
+        }
+        w.key = key;
+        w.figure = i;
+        wires.push_back(w);
+    }
+    std::sort(wires.begin(), wires.end(), [](const Wire &a, const Wire &b) { return a.key < b.key; });
+    // Groups: the wires lie in a few far-apart families (the band of a sphere's triangles whose normals are perpendicular to k), and a group's
+    // box must stay small — a ray that pierces it pays for its members.  Neighbouring runs of the Morton order are merged, cheapest union
+    // (by surface area) first, until at most four are left.
+    struct Run { size_t first, last; Box3 box; };
+    std::vector<Run> runs;
+    for (size_t m = 0; m < wires.size(); m++) runs.push_back(Run{m, m + 1, wires[m].box});
+    auto area_of_union = [](const Run &a, const Run &b) {
+        double e[3];
+        for (int k = 0; k < 3; k++) e[k] = (double)smax(a.box.hi[k], b.box.hi[k]) - (double)smin(a.box.lo[k], b.box.lo[k]);
+        return e[0] * e[1] + e[1] * e[2] + e[2] * e[0];
+    };
+    while (runs.size() > 4) {
+        size_t best = 0; double best_area = 1e300;
+        for (size_t j = 0; j + 1 < runs.size(); j++) { const double ar = area_of_union(runs[j], runs[j + 1]); if (ar < best_area) { best_area = ar; best = j; } }
+        runs[best].last = runs[best + 1].last;
+        grow(runs[best].box, runs[best + 1].box);
+        runs.erase(runs.begin() + (long)best + 1);
+    }
+    const size_t n_groups = runs.size();
+    if (env_flag("RTAMD_DUMP_TRIPWIRES")) // diagnostic
+        for (const Run &r : runs) fprintf(stderr, "[rtamd] tripwire group: %zu wires, box %.3f %.3f %.3f .. %.3f %.3f %.3f\n", r.last - r.first, r.box.lo[0], r.box.lo[1], r.box.lo[2], r.box.hi[0], r.box.hi[1], r.box.hi[2]);
+    tripwires.assign((n_groups + wires.size()) * 8, 0.f);
+    for (size_t g = 0; g < n_groups; g++) {
+        const size_t first = runs[g].first, last = runs[g].last;
+        put_box8(tripwires, g, runs[g].box);
+        for (size_t m = first; m < last; m++) {
+            put_box8(tripwires, n_groups + m, wires[m].box);
+            memcpy(&tripwires[8 * (n_groups + m) + 3], &wires[m].figure, 4);
+        }
+        const uint32_t first_rec = (uint32_t)(n_groups + first), count = (uint32_t)(last - first);
+        memcpy(&tripwires[8 * g + 3], &first_rec, 4); memcpy(&tripwires[8 * g + 7], &count, 4);
+    }
+    return (uint32_t)n_groups;
 }
 
 } // namespace
@@ -305,92 +458,54 @@ static void build_light_sep(const std::vector<RefNode> &rn, uint32_t nl, std::ve
 
 void prepare_scene(const rt_scene_desc &d, PreparedScene &out, bool tree_on_device) {
     const uint32_t n = d.n_triangles;
-    if (n >= 0x00FFFFFFu) throw std::runtime_error("too many triangles (limit 2^24-2: the hit word keeps 24 bits of figure index, device/rt_exact.h)");
-    if (n && (!d.positions || !d.material_index)) throw std::runtime_error("scene has triangles but no positions/material_index");
-    for (uint32_t i = 0; i < n; i++)
-        if (d.material_index[i] >= d.n_materials) throw std::runtime_error("triangle material index out of range");
+    TriStage tri;
+    triangle_stage(d, 0x00FFFFFFu, "too many triangles (limit 2^24-2: the hit word keeps 24 bits of figure index, device/rt_exact.h)", tri);
+    out.box_pad = scene_abs_pad(tri.max_coord);
+    out.box_c2 = tri.max_coord * 9.5367431640625e-07f; // 2^-20, whatever RTAMD_BOX_PAD_SCALE says
 
     // ---- 1. figure order (scene BVH) --------------------------------------------------------------
-    std::vector<float> keys[3];
-    std::vector<Box3> boxes(n);
-    for (int k = 0; k < 3; k++) keys[k].resize(n);
-    for (uint32_t i = 0; i < n; i++) {
-        const float *p = d.positions + 9 * (size_t)i;
-        for (int k = 0; k < 3; k++) {
-            keys[k][i] = p[6 + k]; // data3
-            boxes[i].lo[k] = smin(p[6 + k], smin(p[k], p[3 + k])); // primitives.cpp:130-141
-            boxes[i].hi[k] = smax(p[6 + k], smax(p[k], p[3 + k]));
-        }
-    }
-    out.figure_order.resize(n);
-    for (uint32_t i = 0; i < n; i++) out.figure_order[i] = i;
-    std::vector<uint32_t> scene_leaf_last, light_leaf_last;
-    out.box_pad = scene_abs_pad(boxes, d.camera);
+    out.figure_order = identity_order(n);
+    std::vector<uint32_t> scene_leaf_last;
     if (tree_on_device) {
         // RT_BUILD_DEVICE_BVH: no replay of the reference's builder -- the figure order is the LOAD order, the records below stay in
         // it (tri_box doubles as the builder's input) and rtamd_build.hip makes the tree and the leaf order on the GPU
         out.nodes.clear();
         encode_ref_tree(std::vector<RefNode>(), out.ref_nodes);
     } else {
-        RefBuilder scene_builder(keys, boxes, out.figure_order);
-        scene_builder.run(n);
-        out.bvh_depth = scene_builder.depth;
-        out.n_ref_nodes = (uint32_t)scene_builder.nodes.size();
-        encode_tree(scene_builder.nodes, out.nodes, scene_leaf_last, out.box_pad);
+        const RefTree scene_tree(tri.keys, tri.boxes, out.figure_order, n);
+        scene_leaf_last = encode_tree(scene_tree.nodes, out.nodes, out.box_pad);
+        out.bvh_depth = scene_tree.depth;
         bfs_top_first(out.nodes, 512);
         // Walk boxes: the box of the figure's reference leaf (a few leaves hold several triangles): whatever the reference can reach
         // through its leaf box is then inside a box of ours.  (Widening each box by how far outside the triangle the reference's test
         // can still report a hit -- delta cot(phi), rt_exact.h -- was tried: the few triangles whose plane contains the projection's
         // kernel get scene-sized boxes, their test accepts a sliver of every ray, and 12 % of the queries end in the exact walk.)
-        out.walk_box.assign((size_t)(n ? n : 1) * 8, 0.f);
-        for (const RefNode &rn : scene_builder.nodes)
-            if (rn.left == 0)
-                for (uint32_t i = rn.first; i < rn.last; i++)
-                    for (int k = 0; k < 3; k++) { out.walk_box[8 * (size_t)i + k] = rn.box.lo[k]; out.walk_box[8 * (size_t)i + 4 + k] = rn.box.hi[k]; }
-        encode_ref_tree(scene_builder.nodes, out.ref_nodes);
+        out.walk_box = box8_records(n);
+        put_leaf_boxes(scene_tree, out.walk_box);
+        // not encode_both: allocated in front of the walk boxes, the reference's nodes (26 MB for the benchmark scene) leave glibc's heap so
+        // that it is trimmed after every scene, and a third of the pages fault in again at the next
+        encode_ref_tree(scene_tree.nodes, out.ref_nodes);
     }
 
     // ---- 2. light order ---------------------------------------------------------------------------
-    auto emissive = [&](uint32_t tri) { // distributions.h:104-109: the FACTOR decides, not the texture
-        const rt_material &m = d.materials[d.material_index[tri]];
-        return !(m.emission[0] == 0 && m.emission[1] == 0 && m.emission[2] == 0);
-    };
-    std::vector<uint32_t> lorder = out.figure_order; // the copy FiguresMix receives by value
-    uint32_t n_lights = (uint32_t)(std::partition(lorder.begin(), lorder.end(), emissive) - lorder.begin());
-    RefBuilder light_builder(keys, boxes, lorder);
-    light_builder.run(n_lights);
-    out.light_bvh_depth = light_builder.depth;
-    encode_tree(light_builder.nodes, out.light_nodes, light_leaf_last, out.box_pad);
-    encode_ref_tree(light_builder.nodes, out.ref_light_nodes);
-    build_light_sep(light_builder.nodes, n_lights, out.light_sep, out.light_sep_levels);
-    out.light_walk_box.assign((size_t)(n_lights ? n_lights : 1) * 8, 0.f);
-    for (const RefNode &rn : light_builder.nodes)
-        if (rn.left == 0)
-            for (uint32_t i = rn.first; i < rn.last; i++)
-                for (int k = 0; k < 3; k++) { out.light_walk_box[8 * (size_t)i + k] = rn.box.lo[k]; out.light_walk_box[8 * (size_t)i + 4 + k] = rn.box.hi[k]; }
-    out.light_order.assign(lorder.begin(), lorder.begin() + n_lights);
+    const RefTree light_tree = build_light_tree(tri.keys, tri.boxes, out.figure_order, [&](uint32_t t) { return emissive_triangle(d, t); }, out.light_order);
+    const uint32_t n_lights = (uint32_t)out.light_order.size();
+    const std::vector<uint32_t> light_leaf_last = encode_both(light_tree, out.box_pad, out.light_nodes, out.ref_light_nodes, out.light_bvh_depth);
+    build_light_sep(light_tree.nodes, n_lights, out.light_sep, out.light_sep_levels);
+    out.light_walk_box = box8_records(n_lights);
+    put_leaf_boxes(light_tree, out.light_walk_box);
 
     // ---- 3. records ---------------------------------------------------------------------------------
     out.isect.resize(n);
     out.shade.resize(n);
-    out.tri_box.assign((size_t)(n ? n : 1) * 8, 0.f);
-    float max_coord = 0.f;
-    for (int k = 0; k < 3; k++) max_coord = smax(max_coord, std::fabs(d.camera.position[k]));
+    out.tri_box = own_boxes8(tri.boxes, out.figure_order);
     for (uint32_t i = 0; i < n; i++) {
         uint32_t src = out.figure_order[i];
-        for (int k = 0; k < 3; k++) {
-            out.tri_box[8 * (size_t)i + k] = boxes[src].lo[k];
-            out.tri_box[8 * (size_t)i + 4 + k] = boxes[src].hi[k];
-            max_coord = smax(max_coord, smax(std::fabs(boxes[src].lo[k]), std::fabs(boxes[src].hi[k])));
-        }
-        out.isect[i] = make_isect(d.positions + 9 * (size_t)src);
+        out.isect[i] = make_isect(tri_frame(d.positions + 9 * (size_t)src));
         out.isect[i].pad = i << 1; // figure index; bit 0 (last of its leaf) is set below / by the GPU builder's gather
         TriShade &s = out.shade[i];
         memset(&s, 0, sizeof s);
-        if (d.normals) {
-            const float *q = d.normals + 9 * (size_t)src;
-            for (int k = 0; k < 3; k++) { s.n3[k] = q[6 + k]; s.dn1[k] = q[k] - q[6 + k]; s.dn2[k] = q[3 + k] - q[6 + k]; }
-        }
+        put_normals(d.normals, src, s.n3, s.dn1, s.dn2);
         if (d.tangents) {
             const float *q = d.tangents + 12 * (size_t)src;
             for (int k = 0; k < 3; k++) { s.t3[k] = q[8 + k]; s.dt1[k] = q[k] - q[8 + k]; s.dt2[k] = q[4 + k] - q[8 + k]; }
@@ -403,89 +518,18 @@ void prepare_scene(const rt_scene_desc &d, PreparedScene &out, bool tree_on_devi
         s.material = d.material_index[src];
         s.orig = src;
     }
-    out.box_c2 = max_coord * 9.5367431640625e-07f; // 2^-20
-    for (uint32_t i : scene_leaf_last) out.isect[i].pad |= 1u;
-    out.tripwires.clear(); out.n_tripwire_groups = 0;
-    if (!out.walk_box.empty()) { // replay mode: the tripwires of scene_prep.h
-        // |den| / (|n| |k|) = |cos| of the angle between the triangle's normal and the projection's kernel k = magic1 x magic2: how far
-        // outside the triangle the test can still accept a point grows like (rounding of the hit point) / cos.  Below 2^-14 (20 triangles of the
-        // benchmark scene; 8 lie below 1e-5, one at 4e-8: its test accepted a point 16 units away) the walkers' look-behind and the gate's
-        // window (rt_exact.h) no longer cover it; every ray pays for the test, so the list is kept short.
-        const double m1[3] = {0.239f, 0.419f, 0.533f}, m2[3] = {0.35743f, 0.66682f, 0.69695f};
-        const double kx = m1[1] * m2[2] - m1[2] * m2[1], ky = m1[2] * m2[0] - m1[0] * m2[2], kz = m1[0] * m2[1] - m1[1] * m2[0];
-        const double kn = std::sqrt(kx * kx + ky * ky + kz * kz);
-        const double tripwire_cos = env_float("RTAMD_TRIPWIRE_COS", 6.103515625e-05); // 2^-14
-        struct Wire { uint64_t key; float lo[3], hi[3]; uint32_t figure; };
-        std::vector<Wire> wires;
-        float slo[3] = {3e38f, 3e38f, 3e38f}, shi[3] = {-3e38f, -3e38f, -3e38f};
-        for (uint32_t i = 0; i < n; i++) for (int k = 0; k < 3; k++) { slo[k] = smin(slo[k], out.walk_box[8 * (size_t)i + k]); shi[k] = smax(shi[k], out.walk_box[8 * (size_t)i + 4 + k]); }
-        for (uint32_t i = 0; i < n; i++) {
-            const TriIsect &T = out.isect[i];
-            const double nn = std::sqrt((double)T.nx * T.nx + (double)T.ny * T.ny + (double)T.nz * T.nz);
-            if (!(nn > 0.0)) continue;                                       // no plane: its test never passes (t is NaN or infinite)
-            if (std::fabs((double)T.den) >= tripwire_cos * nn * kn) continue;
-            Wire w;
-            const float pad = 1e-4f * max_coord + 1e-30f;                    // far more than any rounding of the reference's box test
-            uint64_t key = 0;
-            for (int k = 0; k < 3; k++) {
-                w.lo[k] = out.walk_box[8 * (size_t)i + k] - pad; w.hi[k] = out.walk_box[8 * (size_t)i + 4 + k] + pad;
-                const double c = 0.5 * ((double)w.lo[k] + w.hi[k]), e = (double)shi[k] - slo[k];
-                const uint64_t q = e > 0 ? (uint64_t)std::fmin(1023.0, std::fmax(0.0, (c - slo[k]) / e * 1024.0)) : 0;
-                for (int b = 0; b < 10; b++) key |= ((q >> b) & 1ull) << (3 * b + k);       // Morton code: neighbours end up in one group
-            }
-            w.key = key;
-            w.figure = i;
-            wires.push_back(w);
-        }
-        std::sort(wires.begin(), wires.end(), [](const Wire &a, const Wire &b) { return a.key < b.key; });
-        // Groups: the wires lie in a few far-apart families (the band of a sphere's triangles whose normals are perpendicular to k), and a group's
-        // box must stay small — a ray that pierces it pays for its members.  Neighbouring runs of the Morton order are merged, cheapest union
-        // (by surface area) first, until at most four are left.
-        struct Run { size_t first, last; float lo[3], hi[3]; };
-        std::vector<Run> runs;
-        for (size_t m = 0; m < wires.size(); m++) { Run r; r.first = m; r.last = m + 1; for (int k = 0; k < 3; k++) { r.lo[k] = wires[m].lo[k]; r.hi[k] = wires[m].hi[k]; } runs.push_back(r); }
-        auto area_of_union = [](const Run &a, const Run &b) {
-            double e[3];
-            for (int k = 0; k < 3; k++) e[k] = (double)smax(a.hi[k], b.hi[k]) - (double)smin(a.lo[k], b.lo[k]);
-            return e[0] * e[1] + e[1] * e[2] + e[2] * e[0];
-        };
-        while (runs.size() > 4) {
-            size_t best = 0; double best_area = 1e300;
-            for (size_t j = 0; j + 1 < runs.size(); j++) { const double ar = area_of_union(runs[j], runs[j + 1]); if (ar < best_area) { best_area = ar; best = j; } }
-            Run &a = runs[best]; const Run &b2 = runs[best + 1];
-            a.last = b2.last;
-            for (int k = 0; k < 3; k++) { a.lo[k] = smin(a.lo[k], b2.lo[k]); a.hi[k] = smax(a.hi[k], b2.hi[k]); }
-            runs.erase(runs.begin() + (long)best + 1);
-        }
-        const size_t n_groups = runs.size();
-        out.n_tripwire_groups = (uint32_t)n_groups;
-        if (env_flag("RTAMD_DUMP_TRIPWIRES")) // diagnostic
-            for (const Run &r : runs) fprintf(stderr, "[rtamd] tripwire group: %zu wires, box %.3f %.3f %.3f .. %.3f %.3f %.3f\n", r.last - r.first, r.lo[0], r.lo[1], r.lo[2], r.hi[0], r.hi[1], r.hi[2]);
-        out.tripwires.assign((n_groups + wires.size()) * 8, 0.f);
-        for (size_t g = 0; g < n_groups; g++) {
-            const size_t first = runs[g].first, last = runs[g].last;
-            float *rec = &out.tripwires[8 * g];
-            for (int k = 0; k < 3; k++) { rec[k] = runs[g].lo[k]; rec[4 + k] = runs[g].hi[k]; }
-            for (size_t m = first; m < last; m++) {
-                float *mr = &out.tripwires[8 * (n_groups + m)];
-                for (int k = 0; k < 3; k++) { mr[k] = wires[m].lo[k]; mr[4 + k] = wires[m].hi[k]; }
-                memcpy(&mr[3], &wires[m].figure, 4);
-            }
-            const uint32_t first_rec = (uint32_t)(n_groups + first), count = (uint32_t)(last - first);
-            memcpy(&rec[3], &first_rec, 4); memcpy(&rec[7], &count, 4);
-        }
-    }
+    mark_leaf_ends(scene_leaf_last, [&](uint32_t i) -> uint32_t & { return out.isect[i].pad; });
+    out.tripwires.clear();
+    out.n_tripwire_groups = out.walk_box.empty() ? 0u : build_tripwires(out.isect, out.walk_box, tri.max_coord, out.tripwires); // replay mode only
     out.lights.resize(n_lights);
     for (uint32_t i = 0; i < n_lights; i++) {
         uint32_t src = out.light_order[i];
-        const float *p = d.positions + 9 * (size_t)src;
+        const TriFrame f = tri_frame(d.positions + 9 * (size_t)src);
         LightRec &L = out.lights[i];
         memset(&L, 0, sizeof L);
-        L.isect = make_isect(p);
-        for (int k = 0; k < 3; k++) { L.b[k] = p[k] - p[6 + k]; L.c[k] = p[3 + k] - p[6 + k]; }
-        float nl2 = L.isect.nx * L.isect.nx + L.isect.ny * L.isect.ny + L.isect.nz * L.isect.nz;
-        float nl = (float)std::sqrt((double)nl2);
-        L.point_prob = (float)(1.0 / (0.5 * (double)nl)); // distributions.h:78
+        L.isect = make_isect(f);
+        put3(L.b, f.b); put3(L.c, f.c);
+        L.point_prob = point_prob(f);
         { // the box the kernel used to form per hit: a, a + b, a + c in float (not the original vertices)
             const float av[3] = {L.isect.ax, L.isect.ay, L.isect.az};
             for (int k = 0; k < 3; k++) {
@@ -494,13 +538,9 @@ void prepare_scene(const rt_scene_desc &d, PreparedScene &out, bool tree_on_devi
                 L.box_hi[k] = std::fmax(av[k], std::fmax(pb, pc));
             }
         }
-        if (d.normals) {
-            const float *q = d.normals + 9 * (size_t)src;
-            for (int k = 0; k < 3; k++) { L.n3[k] = q[6 + k]; L.dn1[k] = q[k] - q[6 + k]; L.dn2[k] = q[3 + k] - q[6 + k]; }
-        }
+        put_normals(d.normals, src, L.n3, L.dn1, L.dn2);
     }
-
-    for (uint32_t i : light_leaf_last) out.lights[i].isect.pad = 1;
+    mark_leaf_ends(light_leaf_last, [&](uint32_t i) -> uint32_t & { return out.lights[i].isect.pad; });
 
     // ---- materials, images ------------------------------------------------------------------------
     out.images.clear();
@@ -542,113 +582,68 @@ void prepare_scene(const rt_scene_desc &d, PreparedScene &out, bool tree_on_devi
     for (int b = 0; b < 256; b++) out.srgb_lut[b] = std::pow((float)(1. / 255) * (1.f * (float)b), 2.2f);
 }
 
-
 void prepare_scene_hw6(const rt_scene_desc &d, PreparedScene6 &out, bool tree_on_device) {
     const uint32_t n = d.n_triangles;
-    if (n >= 0x7FFFFFFFu) throw std::runtime_error("too many triangles (limit 2^31-2)");
-    if (n && (!d.positions || !d.material_index)) throw std::runtime_error("scene has triangles but no positions/material_index");
-    for (uint32_t i = 0; i < n; i++)
-        if (d.material_index[i] >= d.n_materials) throw std::runtime_error("triangle material index out of range");
-    std::vector<float> zero_keys[3], keys[3];
-    std::vector<Box3> boxes(n);
-    for (int k = 0; k < 3; k++) { zero_keys[k].assign(n, 0.f); keys[k].resize(n); }
-    for (uint32_t i = 0; i < n; i++) {
-        const float *p = d.positions + 9 * (size_t)i;
-        for (int k = 0; k < 3; k++) {
-            keys[k][i] = p[6 + k];
-            boxes[i].lo[k] = smin(p[6 + k], smin(p[k], p[3 + k])); // hw6/src/primitives.cpp:173-183
-            boxes[i].hi[k] = smax(p[6 + k], smax(p[k], p[3 + k]));
-        }
-    }
+    TriStage tri;
+    triangle_stage(d, 0x7FFFFFFFu, "too many triangles (limit 2^31-2)", tri);
+    std::vector<float> zero_keys[3];
+    for (int k = 0; k < 3; k++) zero_keys[k].assign(n, 0.f);
+    out.box_pad = scene_abs_pad(tri.max_coord);
+    out.box_c2 = out.box_pad * 0.25f; // 2^-20 x the largest |coordinate|, and RTAMD_BOX_PAD_SCALE with it
     // 1. the reference's figure order: hw6's BVH sorts on Figure::position == (0,0,0) for every triangle
     //    (hw6/src/include/bvh.h:61-63); the resulting permutation is what introsort does with all-equal keys.
-    out.figure_order.resize(n);
-    for (uint32_t i = 0; i < n; i++) out.figure_order[i] = i;
-    RefBuilder ref(zero_keys, boxes, out.figure_order);
-    ref.run(n);
-    out.ref_bvh_depth = ref.depth;
+    out.figure_order = identity_order(n);
+    const RefTree ref(zero_keys, tri.boxes, out.figure_order, n);
     encode_ref_tree(ref.nodes, out.ref_nodes);
     std::vector<uint32_t> ref_pos(n);
     for (uint32_t i = 0; i < n; i++) ref_pos[out.figure_order[i]] = i;
-    // the reference leaf box of every triangle (LOAD order): what the walkers' own tree is built over (see PreparedScene::walk_box)
-    std::vector<Box3> leaf_box = boxes;
-    for (const RefNode &rn : ref.nodes)
-        if (rn.left == 0)
-            for (uint32_t i = rn.first; i < rn.last; i++) leaf_box[out.figure_order[i]] = rn.box;
     // 2. light order + light tree (reference topology: it fixes the order of the float additions)
-    auto emissive = [&](uint32_t tri) {
-        const rt_material &m = d.materials[d.material_index[tri]];
-        return !(m.emission[0] == 0 && m.emission[1] == 0 && m.emission[2] == 0);
-    };
-    std::vector<uint32_t> lorder = out.figure_order;
-    uint32_t n_lights = (uint32_t)(std::partition(lorder.begin(), lorder.end(), emissive) - lorder.begin());
-    RefBuilder light_builder(zero_keys, boxes, lorder);
-    light_builder.run(n_lights);
-    out.light_bvh_depth = light_builder.depth;
-    std::vector<uint32_t> light_leaf_last, scene_leaf_last;
-    out.box_pad = scene_abs_pad(boxes, d.camera);
-    encode_tree(light_builder.nodes, out.light_nodes, light_leaf_last, out.box_pad);
-    encode_ref_tree(light_builder.nodes, out.ref_light_nodes);
-    out.light_order.assign(lorder.begin(), lorder.begin() + n_lights);
+    const RefTree light_tree = build_light_tree(zero_keys, tri.boxes, out.figure_order, [&](uint32_t t) { return emissive_triangle(d, t); }, out.light_order);
+    const uint32_t n_lights = (uint32_t)out.light_order.size();
+    const std::vector<uint32_t> light_leaf_last = encode_both(light_tree, out.box_pad, out.light_nodes, out.ref_light_nodes, out.light_bvh_depth);
     // 3. own scene tree: the same full-sweep SAH builder keyed on the data3 vertex (as hw8 does) -- or, when the caller builds the
-    //    tree on the GPU (device/rt_bvh_build.h), the records stay in LOAD order and the boxes go along
-    std::vector<uint32_t> my_order(n);
-    for (uint32_t i = 0; i < n; i++) my_order[i] = i;
+    //    tree on the GPU (device/rt_bvh_build.h), the records stay in LOAD order and the reference leaf box of every triangle goes
+    //    along (LOAD order: what the walkers' own tree is built over, see PreparedScene::walk_box)
+    std::vector<uint32_t> my_order = identity_order(n), scene_leaf_last;
     if (tree_on_device) {
         out.boxes8.assign((size_t)n * 8, 0.f);
-        for (uint32_t i = 0; i < n; i++)
-            for (int k = 0; k < 3; k++) { out.boxes8[8 * (size_t)i + k] = leaf_box[i].lo[k]; out.boxes8[8 * (size_t)i + 4 + k] = leaf_box[i].hi[k]; }
+        put_leaf_boxes(ref, out.boxes8, out.figure_order.data());
     } else {
-        RefBuilder mine(keys, boxes, my_order);
-        mine.run(n);
+        const RefTree mine(tri.keys, tri.boxes, my_order, n);
         out.bvh_depth = mine.depth;
-        encode_tree(mine.nodes, out.nodes, scene_leaf_last, out.box_pad);
+        scene_leaf_last = encode_tree(mine.nodes, out.nodes, out.box_pad);
     }
-    auto make = [&](uint32_t src) {
-        const float *p = d.positions + 9 * (size_t)src;
+    auto make = [&](uint32_t src, uint32_t ref_index) {
+        const TriFrame f = tri_frame(d.positions + 9 * (size_t)src);
         Tri6 t;
         memset(&t, 0, sizeof t);
-        V3 a{p[6], p[7], p[8]}, b = sub(V3{p[0], p[1], p[2]}, a), c = sub(V3{p[3], p[4], p[5]}, a);
-        V3 nn = crossr(b, c);
-        t.a[0] = a.x; t.a[1] = a.y; t.a[2] = a.z; t.b[0] = b.x; t.b[1] = b.y; t.b[2] = b.z;
-        t.c[0] = c.x; t.c[1] = c.y; t.c[2] = c.z; t.n[0] = nn.x; t.n[1] = nn.y; t.n[2] = nn.z;
+        put3(t.a, f.a); put3(t.b, f.b); put3(t.c, f.c); put3(t.n, f.n);
+        t.ref_index = ref_index;
         t.material = d.material_index[src];
-        float nl = (float)std::sqrt((double)(nn.x * nn.x + nn.y * nn.y + nn.z * nn.z));
-        t.point_prob = (float)(1.0 / (0.5 * (double)nl)); // hw6/src/include/distributions.h:126
+        t.point_prob = point_prob(f);
         return t;
     };
-    out.tris.resize(n);
-    for (uint32_t i = 0; i < n; i++) { out.tris[i] = make(my_order[i]); out.tris[i].ref_index = ref_pos[my_order[i]]; }
-    for (uint32_t i : scene_leaf_last) out.tris[i].last = 1;
-    out.ref_tris.resize(n);
-    out.tri_box.assign((size_t)(n ? n : 1) * 8, 0.f);
-    for (uint32_t i = 0; i < n; i++) {
-        const uint32_t src = out.figure_order[i];
-        out.ref_tris[i] = make(src); out.ref_tris[i].ref_index = i;
-        for (int k = 0; k < 3; k++) { out.tri_box[8 * (size_t)i + k] = boxes[src].lo[k]; out.tri_box[8 * (size_t)i + 4 + k] = boxes[src].hi[k]; }
-    }
-    out.box_c2 = out.box_pad * 0.25f; // 2^-20 x the largest |coordinate|
-    out.lights.resize(n_lights);
-    for (uint32_t i = 0; i < n_lights; i++) { out.lights[i] = make(out.light_order[i]); out.lights[i].ref_index = i; }
-    for (uint32_t i : light_leaf_last) out.lights[i].last = 1;
+    fill_records(out.tris, n, [&](uint32_t i) { return make(my_order[i], ref_pos[my_order[i]]); });
+    mark_leaf_ends(scene_leaf_last, [&](uint32_t i) -> uint32_t & { return out.tris[i].last; });
+    fill_records(out.ref_tris, n, [&](uint32_t i) { return make(out.figure_order[i], i); });
+    out.tri_box = own_boxes8(tri.boxes, out.figure_order);
+    fill_records(out.lights, n_lights, [&](uint32_t i) { return make(out.light_order[i], i); });
+    mark_leaf_ends(light_leaf_last, [&](uint32_t i) -> uint32_t & { return out.lights[i].last; });
     // The reference's light tree (constant sort key) is degenerate — thousands of box tests per query — and only the ORDER
     // of its additions matters, which is irrelevant when at most two lights are hit.  A second, properly keyed tree over the
     // same lights serves those queries; three or more hits fall back to the reference-order walk.
     {
         std::vector<uint32_t> forder = out.light_order;
-        RefBuilder fast(keys, boxes, forder);
-        fast.run(n_lights);
+        const RefTree fast(tri.keys, tri.boxes, forder, n_lights);
         out.fast_light_bvh_depth = fast.depth;
-        std::vector<uint32_t> fast_leaf_last;
-        encode_tree(fast.nodes, out.fast_light_nodes, fast_leaf_last, out.box_pad);
-        out.fast_lights.resize(n_lights);
+        const std::vector<uint32_t> fast_leaf_last = encode_tree(fast.nodes, out.fast_light_nodes, out.box_pad);
         std::vector<uint32_t> light_pos(n, 0);
         for (uint32_t i = 0; i < n_lights; i++) light_pos[out.light_order[i]] = i;
-        for (uint32_t i = 0; i < n_lights; i++) { out.fast_lights[i] = make(forder[i]); out.fast_lights[i].ref_index = light_pos[forder[i]]; }
-        build_light_sep(light_builder.nodes, n_lights, out.light_sep, out.light_sep_levels);
-        for (const RefNode &rn : light_builder.nodes) { out.light_ref.push_back(rn.left); out.light_ref.push_back(rn.right); out.light_ref.push_back(rn.first); out.light_ref.push_back(rn.last); }
+        fill_records(out.fast_lights, n_lights, [&](uint32_t i) { return make(forder[i], light_pos[forder[i]]); });
+        mark_leaf_ends(fast_leaf_last, [&](uint32_t i) -> uint32_t & { return out.fast_lights[i].last; });
+        build_light_sep(light_tree.nodes, n_lights, out.light_sep, out.light_sep_levels);
+        for (const RefNode &rn : light_tree.nodes) { out.light_ref.push_back(rn.left); out.light_ref.push_back(rn.right); out.light_ref.push_back(rn.first); out.light_ref.push_back(rn.last); }
         if (out.light_ref.empty()) out.light_ref.assign(4, 0);
-        for (uint32_t i : fast_leaf_last) out.fast_lights[i].last = 1;
     }
     out.materials.resize(d.n_materials);
     for (uint32_t i = 0; i < d.n_materials; i++) {
@@ -713,28 +708,18 @@ void prepare_scene_hw5(const rt_scene_desc &d, PreparedScene5 &out) {
     }
     // Scene::initBVH, hw5/src/scene.cpp:18-23: planes to the back, BVH (which reorders) over the front
     std::vector<uint32_t> &order = out.figure_order;
-    order.resize(n);
-    for (uint32_t i = 0; i < n; i++) order[i] = i;
+    order = identity_order(n);
     out.n_nonplanes = (uint32_t)(std::partition(order.begin(), order.end(), [&](uint32_t i) { return d.primitives[i].type != RT_PRIM_PLANE; }) - order.begin());
-    RefBuilder scene_builder(keys, boxes, order);
-    scene_builder.run(out.n_nonplanes);
-    out.bvh_depth = scene_builder.depth;
+    const RefTree scene_tree(keys, boxes, order, out.n_nonplanes);
     // FiguresMix::FiguresMix on a copy of the reordered list, hw5/src/include/distributions.h:180-198
-    std::vector<uint32_t> lorder = order;
-    uint32_t n_lights = (uint32_t)(std::partition(lorder.begin(), lorder.end(), [&](uint32_t i) {
+    const RefTree light_tree = build_light_tree(keys, boxes, order, [&](uint32_t i) {
         const rt_primitive &f = d.primitives[i];
         if (f.emission[0] == 0 && f.emission[1] == 0 && f.emission[2] == 0) return false;
         return f.type == RT_PRIM_BOX || f.type == RT_PRIM_ELLIPSOID || f.type == RT_PRIM_TRIANGLE;
-    }) - lorder.begin());
-    RefBuilder light_builder(keys, boxes, lorder);
-    light_builder.run(n_lights);
-    out.light_bvh_depth = light_builder.depth;
-    out.light_order.assign(lorder.begin(), lorder.begin() + n_lights);
-    std::vector<uint32_t> scene_leaf_last, light_leaf_last;
-    encode_tree(scene_builder.nodes, out.nodes, scene_leaf_last);
-    encode_tree(light_builder.nodes, out.light_nodes, light_leaf_last);
-    encode_ref_tree(scene_builder.nodes, out.ref_nodes);
-    encode_ref_tree(light_builder.nodes, out.ref_light_nodes);
+    }, out.light_order);
+    const uint32_t n_lights = (uint32_t)out.light_order.size();
+    const std::vector<uint32_t> scene_leaf_last = encode_both(scene_tree, 0.f, out.nodes, out.ref_nodes, out.bvh_depth);
+    const std::vector<uint32_t> light_leaf_last = encode_both(light_tree, 0.f, out.light_nodes, out.ref_light_nodes, out.light_bvh_depth);
     auto make = [&](uint32_t src) {
         const rt_primitive &f = d.primitives[src];
         GpuFig5 g;
@@ -747,12 +732,33 @@ void prepare_scene_hw5(const rt_scene_desc &d, PreparedScene5 &out) {
         g.type = f.type; g.kind = f.kind; g.ior = f.ior;
         return g;
     };
-    out.figs.resize(n);
-    for (uint32_t i = 0; i < n; i++) out.figs[i] = make(order[i]);
-    for (uint32_t i : scene_leaf_last) out.figs[i].last = 1;
-    out.lights.resize(n_lights);
-    for (uint32_t i = 0; i < n_lights; i++) out.lights[i] = make(lorder[i]);
-    for (uint32_t i : light_leaf_last) out.lights[i].last = 1;
+    fill_records(out.figs, n, [&](uint32_t i) { return make(order[i]); });
+    mark_leaf_ends(scene_leaf_last, [&](uint32_t i) -> uint32_t & { return out.figs[i].last; });
+    fill_records(out.lights, n_lights, [&](uint32_t i) { return make(out.light_order[i]); });
+    mark_leaf_ends(light_leaf_last, [&](uint32_t i) -> uint32_t & { return out.lights[i].last; });
+}
+
+// ---- hw1 .. hw4 -------------------------------------------------------------------------------------------------
+void prepare_scene_txt(const rt_scene_desc &d, PreparedSceneTxt &out) {
+    out.prims.resize(d.n_primitives);
+    for (uint32_t i = 0; i < d.n_primitives; i++) {
+        const rt_primitive &p = d.primitives[i];
+        GpuPrim &g = out.prims[i];
+        if (p.type < RT_PRIM_ELLIPSOID || p.type > RT_PRIM_TRIANGLE) throw std::runtime_error("rt_scene_create: bad primitive type");
+        if (p.type == RT_PRIM_TRIANGLE) out.has_triangles = true;
+        for (int k = 0; k < 3; k++) { g.data[k] = p.data[k]; g.position[k] = p.position[k]; g.color[k] = p.color[k]; g.emission[k] = p.emission[k]; }
+        for (int k = 0; k < 4; k++) g.rotation[k] = p.rotation[k];
+        g.type = p.type; g.kind = p.kind; g.ior = p.ior;
+        if ((p.emission[0] > 0 || p.emission[1] > 0 || p.emission[2] > 0) && (p.type == RT_PRIM_BOX || p.type == RT_PRIM_ELLIPSOID)) out.light_prims.push_back(i);
+    }
+    out.lights.resize(d.n_lights);
+    for (uint32_t i = 0; i < d.n_lights; i++) {
+        const rt_light &L = d.lights[i];
+        GpuLight &g = out.lights[i];
+        if (L.type != RT_LIGHT_POINT && L.type != RT_LIGHT_DIRECTIONAL) throw std::runtime_error("rt_scene_create: bad light type");
+        g.type = L.type;
+        for (int k = 0; k < 3; k++) { g.intensity[k] = L.intensity[k]; g.position[k] = L.position[k]; g.attenuation[k] = L.attenuation[k]; g.direction[k] = L.direction[k]; }
+    }
 }
 
 } // namespace rtamd

@@ -94,63 +94,65 @@ int finish_scene(std::unique_ptr<rt_scene> &s, rt_scene **out, uint64_t bytes, d
     return RT_OK;
 }
 
+// Uploads a prepared array, hands it to the scene (which frees it) and counts its bytes.
+struct Uploader {
+    rt_scene *s;
+    uint64_t bytes = 0;
+    template <class T> const T *operator()(const std::vector<T> &v) { s->allocations.push_back((void *)upload(v, bytes)); return (const T *)s->allocations.back(); }
+};
+// What the three flavours upload and report alike: the reference's own two trees, for the exact walks, and the light order and
+// rt_scene_info; n_nodes, bvh_depth: of the scene tree the kernels walk, the prepared one or one built on the device.
+template <class View> void upload_ref_trees(View &V, const PreparedTrees &P, Uploader &up) { V.ref_nodes = up(P.ref_nodes); V.ref_light_nodes = up(P.ref_light_nodes); }
+void report_trees(rt_scene *s, const rt_scene_desc *desc, const PreparedTrees &P, uint32_t n_lights, uint32_t n_nodes, uint32_t bvh_depth) {
+    s->light_order = P.light_order;
+    s->info.n_triangles = desc->n_triangles; s->info.n_lights = n_lights;
+    s->info.n_bvh_nodes = n_nodes; s->info.n_light_bvh_nodes = (uint32_t)P.light_nodes.size();
+    s->info.bvh_depth = bvh_depth; s->info.light_bvh_depth = P.light_bvh_depth;
+}
+
+// What the views of the two triangle flavours are told alike; components: of the reference's mix without lights (hw6 scene.cpp:8-16, hw8 scene.cpp:65-74).
+template <class View> void set_triangle_view(View &V, const rt_scene_desc &desc, const PreparedTriangles &P, uint32_t components) {
+    V.box_c2 = P.box_c2; V.box_c2x = 1.25f * P.box_c2;
+    V.cull_k = (float)env_float("RTAMD_CULL_K", 0.0078125); // how far behind the best hit the walkers still look, relative to t (rt_exact.h)
+    V.n_tris = desc.n_triangles;
+    V.n_lights = (uint32_t)P.light_order.size();
+    V.n_components = components + (V.n_lights ? 1u : 0u);
+    V.n_lights_f = (float)V.n_lights; V.n_components_f = (float)V.n_components;
+    set_camera(V, desc);
+    V.tan_fov_y = (float)std::tan((double)(desc.camera.fov_y / 2)); // scene.cpp:180 (host libm, like the reference)
+}
+
 // Analytic primitives only: a .txt scene (hw1 .. hw5).
 int create_txt(const rt_scene_desc *desc, std::unique_ptr<rt_scene> &s, rt_scene **out, double t0) {
-    std::vector<GpuPrim> prims(desc->n_primitives);
-    for (uint32_t i = 0; i < desc->n_primitives; i++) {
-        const rt_primitive &p = desc->primitives[i];
-        GpuPrim &g = prims[i];
-        if (p.type < RT_PRIM_ELLIPSOID || p.type > RT_PRIM_TRIANGLE) return fail(RT_ERR_INVALID_ARG, "rt_scene_create: bad primitive type");
-        if (p.type == RT_PRIM_TRIANGLE) s->txt_has_triangles = true;
-        for (int k = 0; k < 3; k++) { g.data[k] = p.data[k]; g.position[k] = p.position[k]; g.color[k] = p.color[k]; g.emission[k] = p.emission[k]; }
-        for (int k = 0; k < 4; k++) g.rotation[k] = p.rotation[k];
-        g.type = p.type; g.kind = p.kind; g.ior = p.ior;
-    }
-    uint64_t bytes = 0;
-    auto keep = [&](auto *p) { s->allocations.push_back((void *)p); return p; };
+    PreparedSceneTxt T;
+    prepare_scene_txt(*desc, T);
+    PreparedScene5 P5; // hw5 structures: reference figure order, BVH over the non-planes, light list + light BVH
+    prepare_scene_hw5(*desc, P5);
+    Uploader up{s.get()};
+    s->txt_has_triangles = T.has_triangles;
     SceneViewTxt &V = s->viewt;
-    V.prims = keep(upload(prims, bytes));
+    V.prims = up(T.prims);
     V.n_prims = desc->n_primitives;
     set_camera(V, *desc);
     V.tan_fov_x = (float)std::tan((double)(desc->camera.fov_x / 2)); // hw3/src/scene.cpp:100
     V.tan_fov_x_f = tanf(desc->camera.fov_x / 2);                    // hw1/src/scene.cpp:23, hw2/src/scene.cpp:91 (<math.h>: float overload)
-    std::vector<GpuLight> lights(desc->n_lights);
-    for (uint32_t i = 0; i < desc->n_lights; i++) {
-        const rt_light &L = desc->lights[i];
-        GpuLight &g = lights[i];
-        if (L.type != RT_LIGHT_POINT && L.type != RT_LIGHT_DIRECTIONAL) return fail(RT_ERR_INVALID_ARG, "rt_scene_create: bad light type");
-        g.type = L.type;
-        for (int k = 0; k < 3; k++) { g.intensity[k] = L.intensity[k]; g.position[k] = L.position[k]; g.attenuation[k] = L.attenuation[k]; g.direction[k] = L.direction[k]; }
-    }
     V.n_lights = desc->n_lights;
-    if (desc->n_lights) V.lights = keep(upload(lights, bytes));
+    if (desc->n_lights) V.lights = up(T.lights);
     for (int k = 0; k < 3; k++) V.ambient[k] = desc->ambient_light[k];
-    std::vector<uint32_t> light_prims; // hw4/src/scene.cpp:12-21
-    for (uint32_t i = 0; i < desc->n_primitives; i++) {
-        const rt_primitive &p = desc->primitives[i];
-        if ((p.emission[0] > 0 || p.emission[1] > 0 || p.emission[2] > 0) && (p.type == RT_PRIM_BOX || p.type == RT_PRIM_ELLIPSOID)) light_prims.push_back(i);
-    }
-    V.n_light_prims = (uint32_t)light_prims.size();
-    if (!light_prims.empty()) V.light_prims = keep(upload(light_prims, bytes));
-    { // hw5 structures: reference figure order, BVH over the non-planes, light list + light BVH
-        PreparedScene5 P5;
-        prepare_scene_hw5(*desc, P5);
-        SceneView5 &V5 = s->view5;
-        V5.nodes = keep(upload(P5.nodes, bytes));
-        V5.figs = keep(upload(P5.figs, bytes));
-        V5.light_nodes = keep(upload(P5.light_nodes, bytes));
-        V5.ref_nodes = keep(upload(P5.ref_nodes, bytes));
-        V5.ref_light_nodes = keep(upload(P5.ref_light_nodes, bytes));
-        if (!P5.lights.empty()) V5.lights = keep(upload(P5.lights, bytes));
-        V5.n_figs = (uint32_t)P5.figs.size(); V5.n_nonplanes = P5.n_nonplanes; V5.n_lights = (uint32_t)P5.lights.size();
-        set_camera(V5, *desc);
-        V5.tan_fov_x = V.tan_fov_x;
-        s->light_order = P5.light_order;
-        s->info.n_lights = V5.n_lights; s->info.n_bvh_nodes = (uint32_t)P5.nodes.size(); s->info.n_light_bvh_nodes = (uint32_t)P5.light_nodes.size();
-        s->info.bvh_depth = P5.bvh_depth; s->info.light_bvh_depth = P5.light_bvh_depth;
-    }
+    V.n_light_prims = (uint32_t)T.light_prims.size();
+    if (!T.light_prims.empty()) V.light_prims = up(T.light_prims);
+    SceneView5 &V5 = s->view5;
+    V5.nodes = up(P5.nodes);
+    V5.figs = up(P5.figs);
+    V5.light_nodes = up(P5.light_nodes);
+    upload_ref_trees(V5, P5, up);
+    if (!P5.lights.empty()) V5.lights = up(P5.lights);
+    V5.n_figs = (uint32_t)P5.figs.size(); V5.n_nonplanes = P5.n_nonplanes; V5.n_lights = (uint32_t)P5.lights.size();
+    set_camera(V5, *desc);
+    V5.tan_fov_x = V.tan_fov_x;
+    report_trees(s.get(), desc, P5, V5.n_lights, (uint32_t)P5.nodes.size(), P5.bvh_depth);
     s->flavor = RT_INTEGRATOR_HW3;
-    return finish_scene(s, out, bytes, t0, t0); // no preparation to speak of: all of it counts as upload
+    return finish_scene(s, out, up.bytes, t0, t0); // the preparation is no work to speak of: all of it counts as upload
 }
 
 // hw6: flat shading, no per-vertex normals (hw6/src/sceneio.cpp:186-225).
@@ -160,59 +162,48 @@ int create_hw6(const rt_scene_desc *desc, std::unique_ptr<rt_scene> &s, rt_scene
     const bool tree_on_device = desc->n_triangles >= 64 && !env_flag("RTAMD_HOST_BVH");
     PreparedScene6 P6;
     prepare_scene_hw6(*desc, P6, tree_on_device);
+    uint32_t bvh_depth = P6.bvh_depth, n_nodes = (uint32_t)P6.nodes.size();
     double t1 = now_ms();
-    uint64_t bytes = 0;
+    Uploader up{s.get()};
     SceneView6 &V = s->view6;
-    auto keep = [&](auto *p) { s->allocations.push_back((void *)p); return p; };
     if (tree_on_device) {
         uint64_t scratch = 0;
-        OwnedDev d_load(upload(P6.tris, bytes)); // device_bytes: stands for the gathered copy of the same size, which the scene keeps
+        OwnedDev d_load(upload(P6.tris, up.bytes)); // device_bytes: stands for the gathered copy of the same size, which the scene keeps
         OwnedDev d_boxes(upload(P6.boxes8, scratch));
         const DeviceTree t = build_leaf_ordered(s.get(), (const float *)d_boxes.p, (const Tri6 *)d_load.p, desc->n_triangles, P6.box_pad, 28, // hw6 walkers: 36-entry stack columns
                                                 13, false, V.tris);                                                                         // word 13 = Tri6::last
         V.nodes = t.nodes;
-        bytes += (uint64_t)t.n_nodes * sizeof(GpuNode);
-        P6.bvh_depth = t.depth;
-        P6.nodes.resize(t.n_nodes); // node count for rt_scene_info
+        up.bytes += (uint64_t)t.n_nodes * sizeof(GpuNode);
+        bvh_depth = t.depth;
+        n_nodes = t.n_nodes;
         s->info.bvh_build_ms = t.build_ms; s->info.bvh_on_device = 1;
     } else {
-        V.nodes = keep(upload(P6.nodes, bytes));
-        V.tris = keep(upload(P6.tris, bytes));
+        V.nodes = up(P6.nodes);
+        V.tris = up(P6.tris);
     }
-    if (P6.bvh_depth > RT6_STACK_SIZE - 2 || P6.light_bvh_depth > RT6_STACK_SIZE - 2 || P6.fast_light_bvh_depth > RT6_STACK_SIZE - 2)
-        return fail(RT_ERR_LIMIT, "scene BVH deeper than the kernel's traversal stack (" + std::to_string(P6.bvh_depth) + "/" +
+    if (bvh_depth > RT6_STACK_SIZE - 2 || P6.light_bvh_depth > RT6_STACK_SIZE - 2 || P6.fast_light_bvh_depth > RT6_STACK_SIZE - 2)
+        return fail(RT_ERR_LIMIT, "scene BVH deeper than the kernel's traversal stack (" + std::to_string(bvh_depth) + "/" +
                                       std::to_string(P6.light_bvh_depth) + ")");
-    s->hw6_lds_stack = P6.bvh_depth <= RT6_LDS_STACK && P6.fast_light_bvh_depth <= RT6_LDS_STACK; // both own trees fit the LDS stack columns
-    s->hw6_pt_stack = P6.bvh_depth <= P6_STACK && P6.fast_light_bvh_depth <= P6_STACK;           // ... of the persistent pipeline
-    V.light_nodes = keep(upload(P6.light_nodes, bytes));
-    V.lights = keep(upload(P6.lights, bytes));
-    V.fast_light_nodes = keep(upload(P6.fast_light_nodes, bytes));
-    V.fast_lights = keep(upload(P6.fast_lights, bytes));
-    V.light_ref = keep(upload(P6.light_ref, bytes));
-    V.ref_nodes = keep(upload(P6.ref_nodes, bytes));
-    V.ref_light_nodes = keep(upload(P6.ref_light_nodes, bytes));
-    V.ref_tris = keep(upload(P6.ref_tris, bytes));
-    V.tri_box = keep(upload(P6.tri_box, bytes));
-    V.box_c2 = P6.box_c2; V.box_c2x = 1.25f * P6.box_c2;
-    V.cull_k = (float)env_float("RTAMD_CULL_K", 0.0078125);
+    s->hw6_lds_stack = bvh_depth <= RT6_LDS_STACK && P6.fast_light_bvh_depth <= RT6_LDS_STACK; // both own trees fit the LDS stack columns
+    s->hw6_pt_stack = bvh_depth <= P6_STACK && P6.fast_light_bvh_depth <= P6_STACK;           // ... of the persistent pipeline
+    V.light_nodes = up(P6.light_nodes);
+    V.lights = up(P6.lights);
+    V.fast_light_nodes = up(P6.fast_light_nodes);
+    V.fast_lights = up(P6.fast_lights);
+    V.light_ref = up(P6.light_ref);
+    upload_ref_trees(V, P6, up);
+    V.ref_tris = up(P6.ref_tris);
+    V.tri_box = up(P6.tri_box);
+    set_triangle_view(V, *desc, P6, 1u);
     V.exact_boxes = env_flag("RTAMD_NO_EXACT_BOXES") ? 0u : 1u;
-    V.light_sep = keep(upload(P6.light_sep, bytes));
-    V.materials = keep(upload(P6.materials, bytes));
-    V.n_tris = desc->n_triangles;
-    V.n_lights = (uint32_t)P6.lights.size();
-    V.n_components = P6.lights.empty() ? 1u : 2u; // hw6/src/scene.cpp:8-16
-    V.n_lights_f = (float)V.n_lights; V.n_components_f = (float)V.n_components;
-    set_camera(V, *desc);
-    V.tan_fov_y = (float)std::tan((double)(desc->camera.fov_y / 2));
+    V.light_sep = up(P6.light_sep);
+    V.materials = up(P6.materials);
     s->view.tan_fov_y = V.tan_fov_y;
     s->flavor = RT_INTEGRATOR_HW6;
-    make_walk_nodes(s.get(), V.cam_pos, V.nodes, (uint32_t)P6.nodes.size(), V.fast_light_nodes, (uint32_t)P6.fast_light_nodes.size(), true,
-                    V.grid, V.nodes4, V.fast_light_nodes4, bytes);
-    s->light_order = P6.light_order;
-    s->info.n_triangles = desc->n_triangles; s->info.n_lights = V.n_lights;
-    s->info.n_bvh_nodes = (uint32_t)P6.nodes.size(); s->info.n_light_bvh_nodes = (uint32_t)P6.light_nodes.size();
-    s->info.bvh_depth = P6.bvh_depth; s->info.light_bvh_depth = P6.light_bvh_depth;
-    return finish_scene(s, out, bytes, t0, t1);
+    make_walk_nodes(s.get(), V.cam_pos, V.nodes, n_nodes, V.fast_light_nodes, (uint32_t)P6.fast_light_nodes.size(), true,
+                    V.grid, V.nodes4, V.fast_light_nodes4, up.bytes);
+    report_trees(s.get(), desc, P6, V.n_lights, n_nodes, bvh_depth);
+    return finish_scene(s, out, up.bytes, t0, t1);
 }
 
 // hw8 / hw7.  The host-side preparation (the replay of the reference's figure and light order: ~0.4 s for the benchmark scene) is
@@ -233,12 +224,11 @@ int create_hw8(const rt_scene_desc *desc, std::unique_ptr<rt_scene> &s, rt_scene
     const PreparedScene &P = shared ? shared->P : P_local; // read-only from here on (several devices may be uploading from it)
     uint32_t bvh_depth = P.bvh_depth, n_nodes = (uint32_t)P.nodes.size();
     double t1 = now_ms();
-    uint64_t bytes = 0;
+    Uploader up{s.get()};
     SceneView &V = s->view;
-    auto keep = [&](auto *p) { s->allocations.push_back((void *)p); return p; };
-    V.tri_isect = keep(upload(P.isect, bytes));
-    V.tri_shade = keep(upload(P.shade, bytes));
-    V.tri_box = keep(upload(P.tri_box, bytes));
+    V.tri_isect = up(P.isect);
+    V.tri_shade = up(P.shade);
+    V.tri_box = up(P.tri_box);
     if (walk_tree_on_device) {
         const uint32_t n = desc->n_triangles;
         uint64_t scratch = 0;
@@ -249,12 +239,12 @@ int create_hw8(const rt_scene_desc *desc, std::unique_ptr<rt_scene> &s, rt_scene
         const DeviceTree t = build_leaf_ordered(s.get(), d_walk_box.p ? (const float *)d_walk_box.p : V.tri_box, V.tri_isect, n, P.box_pad, P8_STACK,
                                                 11, true, V.tri_walk); // word 11 = TriIsect::pad: figure index << 1 | leaf mark
         V.nodes = t.nodes;
-        bytes += (uint64_t)t.n_nodes * sizeof(GpuNode) + (uint64_t)n * sizeof(TriIsect);
+        up.bytes += (uint64_t)t.n_nodes * sizeof(GpuNode) + (uint64_t)n * sizeof(TriIsect);
         bvh_depth = t.depth;
         n_nodes = t.n_nodes;
         s->info.bvh_build_ms = t.build_ms; s->info.bvh_on_device = 1;
     } else {
-        V.nodes = keep(upload(P.nodes, bytes));
+        V.nodes = up(P.nodes);
         V.tri_walk = V.tri_isect;
     }
     if (P.bvh_depth > RT_STACK_SIZE - 2) // the exact walks keep a private stack over the reference's own tree
@@ -262,19 +252,16 @@ int create_hw8(const rt_scene_desc *desc, std::unique_ptr<rt_scene> &s, rt_scene
     if (bvh_depth > RT_STACK_SIZE - 2 || P.light_bvh_depth > RT_STACK_SIZE - 2)
         return fail(RT_ERR_LIMIT, "scene BVH deeper than the kernel's traversal stack (" + std::to_string(bvh_depth) + "/" +
                                       std::to_string(P.light_bvh_depth) + ")");
-    V.light_nodes = keep(upload(P.light_nodes, bytes));
-    V.light_sep = keep(upload(P.light_sep, bytes));
-    V.ref_nodes = keep(upload(P.ref_nodes, bytes));
-    V.ref_light_nodes = keep(upload(P.ref_light_nodes, bytes));
-    V.box_c2 = P.box_c2; V.box_c2x = 1.25f * P.box_c2;
+    V.light_nodes = up(P.light_nodes);
+    V.light_sep = up(P.light_sep);
+    upload_ref_trees(V, P, up);
+    set_triangle_view(V, *desc, P, 2u);
     V.box_c2x *= (float)env_float("RTAMD_C2X_SCALE", 1.0); // experiment: the walkers' absolute look-behind (the gate's `seen` follows)
-    // how far behind the best hit the walkers still look, relative to t (rt_exact.h)
-    V.cull_k = (float)env_float("RTAMD_CULL_K", 0.0078125);
     V.exact_boxes = (env_flag("RTAMD_NO_EXACT_BOXES") || fast_build) ? 0u : 1u; // RT_BUILD_DEVICE_BVH: there is no reference tree to be exact about
     if (env_flag("RTAMD_DIAG_LOOKBEHIND_ONLY")) V.exact_boxes = 2u; // diagnostic (timing only, pixels NOT exact): the walkers look behind as with the gate, every hit stands
     V.n_tripwire_groups = (V.exact_boxes != 1u || env_flag("RTAMD_NO_TRIPWIRES")) ? 0u : P.n_tripwire_groups; // part of the exactness machinery
-    V.tripwires = V.n_tripwire_groups ? keep(upload(P.tripwires, bytes)) : nullptr;
-    V.lights = keep(upload(P.lights, bytes));
+    V.tripwires = V.n_tripwire_groups ? up(P.tripwires) : nullptr;
+    V.lights = up(P.lights);
     uint32_t n_light_walk_nodes = 0;
     {   // the light walker's own tree (rt_types.h: light_walk_nodes / lights_walk)
         const uint32_t nl = (uint32_t)P.lights.size();
@@ -282,31 +269,26 @@ int create_hw8(const rt_scene_desc *desc, std::unique_ptr<rt_scene> &s, rt_scene
         for (uint32_t i = 0; i < nl; i++) tagged[i].isect.pad = (i << 1) | (tagged[i].isect.pad ? 1u : 0u);
         if (nl >= 64 && !env_flag("RTAMD_HOST_LIGHT_BVH")) {
             uint64_t scratch = 0;
-            OwnedDev d_tagged(upload(tagged, bytes)); // device_bytes: stands for the gathered copy of the same size, which the scene keeps
+            OwnedDev d_tagged(upload(tagged, up.bytes)); // device_bytes: stands for the gathered copy of the same size, which the scene keeps
             OwnedDev d_lbox(upload(P.light_walk_box, scratch));
             const DeviceTree lt = build_leaf_ordered(s.get(), (const float *)d_lbox.p, (const LightRec *)d_tagged.p, nl, P.box_pad, 16, // the hits of a walk share its 24-entry column with the node stack
                                                      11, true, V.lights_walk);                                                        // word 11 = TriIsect::pad
             V.light_walk_nodes = lt.nodes;
-            bytes += (uint64_t)lt.n_nodes * sizeof(GpuNode);
+            up.bytes += (uint64_t)lt.n_nodes * sizeof(GpuNode);
             s->light_walk_depth = lt.depth;
             n_light_walk_nodes = lt.n_nodes;
         } else {
             V.light_walk_nodes = V.light_nodes;
             n_light_walk_nodes = (uint32_t)P.light_nodes.size();
-            V.lights_walk = keep(upload(tagged, bytes));
+            V.lights_walk = up(tagged);
             s->light_walk_depth = P.light_bvh_depth;
         }
     }
-    V.materials = keep(upload(P.materials, bytes));
-    V.images = keep(upload(P.images, bytes));
-    V.texels = keep(upload(P.texels, bytes));
-    std::vector<float> lut(P.srgb_lut, P.srgb_lut + 256);
-    V.srgb_lut = keep(upload(lut, bytes));
-    V.n_tris = desc->n_triangles;
+    V.materials = up(P.materials);
+    V.images = up(P.images);
+    V.texels = up(P.texels);
+    V.srgb_lut = up(std::vector<float>(P.srgb_lut, P.srgb_lut + 256));
     V.n_nodes = n_nodes;
-    V.n_lights = (uint32_t)P.lights.size();
-    V.n_components = P.lights.empty() ? 2u : 3u; // scene.cpp:65-74
-    V.n_lights_f = (float)V.n_lights; V.n_components_f = (float)V.n_components;
     V.last_level_emission_only = 1;
     for (uint32_t i = 0; i < desc->n_materials; i++) {
         const rt_material &m = desc->materials[i];
@@ -315,15 +297,10 @@ int create_hw8(const rt_scene_desc *desc, std::unique_ptr<rt_scene> &s, rt_scene
     }
     if (env_flag("RTAMD_NO_LAST_LEVEL_SHORTCUT")) V.last_level_emission_only = 0;
     V.env_image = P.env_image;
-    set_camera(V, *desc);
-    V.tan_fov_y = (float)std::tan((double)(desc->camera.fov_y / 2)); // scene.cpp:180 (host libm, like the reference)
     make_walk_nodes(s.get(), V.cam_pos, V.nodes, n_nodes, V.light_walk_nodes, n_light_walk_nodes, n_light_walk_nodes != 0,
-                    V.grid, V.nodes4, V.light_walk_nodes4, bytes);
-    s->light_order = P.light_order;
-    s->info.n_triangles = desc->n_triangles; s->info.n_lights = V.n_lights;
-    s->info.n_bvh_nodes = n_nodes; s->info.n_light_bvh_nodes = (uint32_t)P.light_nodes.size();
-    s->info.bvh_depth = bvh_depth; s->info.light_bvh_depth = P.light_bvh_depth;
-    return finish_scene(s, out, bytes, t0, t1);
+                    V.grid, V.nodes4, V.light_walk_nodes4, up.bytes);
+    report_trees(s.get(), desc, P, V.n_lights, n_nodes, bvh_depth);
+    return finish_scene(s, out, up.bytes, t0, t1);
 }
 
 } // namespace
@@ -377,15 +354,16 @@ int rt_host_prepare_orders(const rt_scene_desc *desc, int integrator, uint32_t *
                            uint32_t *light_order, uint32_t light_capacity) {
     if (!desc || desc->struct_size != sizeof(rt_scene_desc)) return fail(RT_ERR_INVALID_ARG, "rt_host_prepare_orders: bad desc");
     return guarded("rt_host_prepare_orders: ", [&]() -> int {
-        std::vector<uint32_t> fo, lo;
-        if (integrator == RT_INTEGRATOR_HW8 || integrator == RT_INTEGRATOR_HW7) { PreparedScene P; prepare_scene(*desc, P); fo = P.figure_order; lo = P.light_order; }
-        else if (integrator == RT_INTEGRATOR_HW6) { PreparedScene6 P; prepare_scene_hw6(*desc, P); fo = P.figure_order; lo = P.light_order; }
-        else if (integrator == RT_INTEGRATOR_HW5) { PreparedScene5 P; prepare_scene_hw5(*desc, P); fo = P.figure_order; lo = P.light_order; }
-        else return fail(RT_ERR_UNSUPPORTED, "rt_host_prepare_orders: integrator must be HW5, HW6, HW7 or HW8");
-        if ((figure_order && figure_capacity < fo.size()) || (light_order && light_capacity < lo.size())) return fail(RT_ERR_INVALID_ARG, "rt_host_prepare_orders: buffer too small");
-        if (figure_order) memcpy(figure_order, fo.data(), fo.size() * sizeof(uint32_t));
-        if (light_order) memcpy(light_order, lo.data(), lo.size() * sizeof(uint32_t));
-        return (int)lo.size();
+        auto answer = [&](const PreparedTrees &P) -> int {
+            if ((figure_order && figure_capacity < P.figure_order.size()) || (light_order && light_capacity < P.light_order.size())) return fail(RT_ERR_INVALID_ARG, "rt_host_prepare_orders: buffer too small");
+            if (figure_order) memcpy(figure_order, P.figure_order.data(), P.figure_order.size() * sizeof(uint32_t));
+            if (light_order) memcpy(light_order, P.light_order.data(), P.light_order.size() * sizeof(uint32_t));
+            return (int)P.light_order.size();
+        };
+        if (integrator == RT_INTEGRATOR_HW8 || integrator == RT_INTEGRATOR_HW7) { PreparedScene P; prepare_scene(*desc, P); return answer(P); }
+        if (integrator == RT_INTEGRATOR_HW6) { PreparedScene6 P; prepare_scene_hw6(*desc, P); return answer(P); }
+        if (integrator == RT_INTEGRATOR_HW5) { PreparedScene5 P; prepare_scene_hw5(*desc, P); return answer(P); }
+        return fail(RT_ERR_UNSUPPORTED, "rt_host_prepare_orders: integrator must be HW5, HW6, HW7 or HW8");
     });
 }
 

@@ -9,8 +9,11 @@
 #include "device/rt_ref_walk.h"
 #include "host/fold_nodes.h"
 #include "host/rt_guard.h"
+#include "host/scene_prep.h"
+#include <cstdio>
 #include <cstring>
 #include <new>
+#include <string>
 #include <vector>
 
 using namespace rtamd::dev;
@@ -158,6 +161,57 @@ __global__ void k_frame_sum(const uint4 *nodes, uint32_t n_nodes, const uint32_t
     if (LDS_VIEW) { const StridedStack<FS_BATCH> view = {area + threadIdx.x}; out[i] = frame_sum<MAXDEPTH>(view, node, roots[i]); }
     else out[i] = frame_sum<MAXDEPTH>(own, node, roots[i]);
 }
+
+// The host-side preparation (host/scene_prep.h) as text, one line per member of the prepared struct: `name element_count hash`, the
+// hash FNV-1a (64 bit) over the member's raw bytes; a scalar is `name 1 bits`, its value's bits in hex.
+namespace {
+struct PreparedDigest {
+    std::string text;
+    void line(const char *name, size_t count, unsigned long long word, int digits) {
+        char buf[160];
+        snprintf(buf, sizeof buf, "%s %zu %0*llx\n", name, count, digits, word);
+        text += buf;
+    }
+    void bytes(const char *name, size_t count, const void *p, size_t n) {
+        unsigned long long h = 0xcbf29ce484222325ull;
+        for (size_t i = 0; i < n; i++) h = (h ^ ((const unsigned char *)p)[i]) * 0x100000001b3ull;
+        line(name, count, h, 16);
+    }
+    template <class T> void vec(const char *name, const std::vector<T> &v) { bytes(name, v.size(), v.data(), v.size() * sizeof(T)); }
+    template <class T> void scalar(const char *name, const T &v) {
+        static_assert(sizeof(T) <= 4, "scalars of the prepared structs are 32 bits at the most");
+        uint32_t bits = 0;
+        memcpy(&bits, &v, sizeof(T));
+        line(name, 1, bits, 8);
+    }
+};
+#define PD_VEC(m) D.vec(#m, P.m)
+#define PD_SCALAR(m) D.scalar(#m, P.m)
+void digest_of(PreparedDigest &D, const rtamd::PreparedScene &P) {
+    PD_VEC(nodes); PD_VEC(light_nodes); PD_VEC(ref_nodes); PD_VEC(ref_light_nodes); PD_VEC(tri_box); PD_VEC(walk_box); PD_VEC(light_walk_box);
+    PD_VEC(tripwires); PD_SCALAR(n_tripwire_groups); PD_SCALAR(box_c2); PD_SCALAR(box_pad); PD_VEC(light_sep); PD_SCALAR(light_sep_levels);
+    PD_VEC(isect); PD_VEC(shade); PD_VEC(lights); PD_VEC(materials); PD_VEC(images); PD_VEC(texels);
+    D.bytes("srgb_lut", 256, P.srgb_lut, sizeof P.srgb_lut);
+    PD_SCALAR(env_image); PD_VEC(figure_order); PD_VEC(light_order); PD_SCALAR(bvh_depth); PD_SCALAR(light_bvh_depth);
+}
+void digest_of(PreparedDigest &D, const rtamd::PreparedScene6 &P) {
+    PD_VEC(nodes); PD_VEC(light_nodes); PD_VEC(fast_light_nodes); PD_VEC(tris); PD_VEC(lights); PD_VEC(fast_lights); PD_SCALAR(fast_light_bvh_depth);
+    PD_VEC(light_ref); PD_VEC(light_sep); PD_VEC(ref_nodes); PD_VEC(ref_light_nodes); PD_VEC(ref_tris); PD_VEC(tri_box); PD_SCALAR(box_c2);
+    PD_VEC(boxes8); PD_SCALAR(box_pad); PD_SCALAR(light_sep_levels); PD_VEC(materials); PD_VEC(figure_order); PD_VEC(light_order);
+    PD_SCALAR(bvh_depth); PD_SCALAR(light_bvh_depth);
+}
+void digest_of(PreparedDigest &D, const rtamd::PreparedScene5 &P) {
+    PD_VEC(nodes); PD_VEC(light_nodes); PD_VEC(ref_nodes); PD_VEC(ref_light_nodes); PD_VEC(figs); PD_VEC(lights); PD_VEC(figure_order);
+    PD_VEC(light_order); PD_SCALAR(n_nonplanes); PD_SCALAR(bvh_depth); PD_SCALAR(light_bvh_depth);
+}
+void digest_of(PreparedDigest &D, const rtamd::PreparedSceneTxt &P) { // listed behind the hw5 members of the same scene
+    D.vec("txt.prims", P.prims); D.vec("txt.lights", P.lights); D.vec("txt.light_prims", P.light_prims);
+    const uint32_t has_triangles = P.has_triangles ? 1u : 0u;
+    D.scalar("txt.has_triangles", has_triangles);
+}
+#undef PD_VEC
+#undef PD_SCALAR
+} // namespace
 
 extern "C" {
 // rt_pt_queue.h bit helpers on the host (no GPU needed): out[i] = pt_nth_bit(v[i], n[i]) / pt_low_bits(v[i], n[i])
@@ -341,6 +395,23 @@ int rtt_guard_probe(int kind) {
         if (kind == 2) throw std::runtime_error("a runtime error");
         if (kind == 3) throw 7;
         return 5;
+    });
+}
+// The preparation of `desc` as the integrator's flavour sees it (HW8 / HW7: prepare_scene, HW6: prepare_scene_hw6, HW5: prepare_scene_hw5 and
+// then prepare_scene_txt), digested into `out` (PreparedDigest above).  Returns the text's length (the terminator not counted; nothing is
+// written when it exceeds capacity - 1), or the guard's code with the preparation's refusal in rt_last_error().  Host only.
+int rtt_prepared_digest(const rt_scene_desc *desc, int integrator, int tree_on_device, char *out, size_t capacity) {
+    if (!desc || !out) return RT_ERR_INVALID_ARG;
+    return rtamd::guarded("rtt_prepared_digest: ", [&]() -> int {
+        PreparedDigest D;
+        if (integrator == RT_INTEGRATOR_HW8 || integrator == RT_INTEGRATOR_HW7) { rtamd::PreparedScene P; rtamd::prepare_scene(*desc, P, tree_on_device != 0); digest_of(D, P); }
+        else if (integrator == RT_INTEGRATOR_HW6) { rtamd::PreparedScene6 P; rtamd::prepare_scene_hw6(*desc, P, tree_on_device != 0); digest_of(D, P); }
+        else if (integrator == RT_INTEGRATOR_HW5) {
+            rtamd::PreparedScene5 P; rtamd::prepare_scene_hw5(*desc, P); digest_of(D, P);
+            rtamd::PreparedSceneTxt T; rtamd::prepare_scene_txt(*desc, T); digest_of(D, T);
+        } else return RT_ERR_UNSUPPORTED;
+        if (D.text.size() + 1 <= capacity) memcpy(out, D.text.c_str(), D.text.size() + 1);
+        return (int)D.text.size();
     });
 }
 }
