@@ -13,6 +13,9 @@
  *                     (hw8/src/sceneio.cpp:387-396): per-pixel minstd_rand(y*W+x) replay,
  *                     getPixel, aces_tonemap/gamma_corrected/toExternColorFormat.
  *   rt_scene_destroy  replaces  Scene::~Scene (hw8/src/scene.cpp:56-63).
+ * Below that seam, for a caller with a render loop of its own:
+ *   rt_query_closest    answers  BVH::intersect (hw8/src/include/bvh.h:111-142) for a batch of rays,
+ *   rt_query_light_pdf  answers  FiguresMix::pdf (hw8/src/include/distributions.h:122-124).
  *
  * Conventions: plain C, plain pointers and sizes, no exceptions cross the boundary.
  * Every function returns 0 on success and a negative rt_status on failure;
@@ -422,6 +425,60 @@ int  rt_multi_noise_reset(rt_multi_noise *n);
 int  rt_multi_noise_batches(const rt_multi_noise *n);
 int  rt_multi_noise_estimate(rt_multi_noise *n, uint32_t flags, float *out_se /* nullable */, rt_noise_summary *summary /* nullable */);
 void rt_multi_noise_destroy(rt_multi_noise *n);
+
+/* ---- batched ray queries: below the render loop ----------------------------------------------------------------------------
+ * The two functions the render loop spends its time in, for rays of the caller's own (an integrator, a picker, a visibility or
+ * baking pass, a debugger): the closest hit, BVH::intersect (hw8/src/include/bvh.h:111-142) with Figure::intersectAsTriangle's
+ * attributes (hw8/src/primitives.cpp:85-125), and the light pdf, FiguresMix::pdf (hw8/src/include/distributions.h:122-124: the
+ * all-hits sum getTotalPdf, :148-165, divided by the light count).  Both answer bit for bit what the reference computes, over the
+ * trees and with the walkers the renders use (device/rt_query.h).  ABI version 6 still: the additions change nothing that existed.
+ *
+ * Scenes created for hw8 / hw7 are served (hw6 and .txt scenes: RT_ERR_UNSUPPORTED).  The light pdf is hw8's, with the shading
+ * normal (hw7's own uses the geometric normal, hw7/src/include/distributions.h:140-145: not offered); on a scene without lights
+ * rt_query_light_pdf is RT_ERR_INVALID_ARG.  n == 0 is RT_OK and launches nothing.
+ *
+ * rt_ray   d as the reference takes it: any length, t is in units of d (the reference reports hits with 0 < t < 1e4).
+ * rt_hit   64 bytes.  triangle: index in LOAD order (the order of rt_scene_desc's arrays), 0xFFFFFFFF = miss, and then every other
+ *          field but flags is 0.  ng: the geometric normal, normalised, flipped against the ray when it hits the back
+ *          (RT_HIT_INSIDE); texcoord, ns (normalised, flipped likewise) and tangent (xyz normalised, w of the first vertex) are
+ *          interpolated as the shader does.  flags: RT_HIT_INSIDE, RT_HIT_EXACT_WALK (the answer came from the reference-order walk,
+ *          not from the fast walk: informative, it changes no other field), RT_HIT_INVALID_RAY.
+ * Invalid rays: a ray with a NaN or an infinity in o or d, or with d == 0, is never walked; it is answered as a miss with
+ *          RT_HIT_INVALID_RAY (light pdf: 0) and counted in rt_query_stats.invalid_rays.
+ * flags    RT_QUERY_DEVICE_POINTERS: rays and out are device memory on the scene's GPU (out of rt_query_closest 16-byte aligned),
+ *          read and written in place; the work is ordered on the null stream and has finished when the call returns.
+ *          RT_QUERY_REFERENCE_WALK: every valid ray takes the reference-order walk, one lane per ray -- the referee of the fast path;
+ *          the answers are the same bits.
+ * Memory   rays are processed in chunks of 262,144, so the staging (29 MB per scene, allocated by the first query, freed with the
+ *          scene) does not grow with n.  Queries are serialised with the scene's other calls by the caller, like every call; they
+ *          only read the scene and disturb no rt_accum.
+ * stats    struct_size in: sizeof(rt_query_stats).  exact_walks: valid rays answered by the reference-order walk -- those the gate
+ *          (device/rt_exact.h) sent there, and those outside what the gate was derived for: an origin coordinate beyond the largest
+ *          |coordinate| of scene and camera, a direction with a zero component or a length outside [1/16, 16], all rays under
+ *          RT_QUERY_REFERENCE_WALK.  kernel_ms: HIP-event time of the kernels; total_ms: host wall time of the call.
+ *          reference_exact: 1 = every answer of this call is the reference's own.  0 on RT_BUILD_DEVICE_BVH scenes and under
+ *          RTAMD_NO_EXACT_BOXES: the answers are then the closest triangles of the padded boxes' walk, with the tie rule (equal t: the
+ *          lowest index) in load order on RT_BUILD_DEVICE_BVH scenes, and the light sums add in that order. */
+typedef struct rt_ray { float o[3]; float d[3]; } rt_ray;
+typedef struct rt_hit {
+    float t; uint32_t triangle;
+    float ng[3]; float texcoord[2]; float ns[3]; float tangent[4];
+    uint32_t flags;
+    uint32_t reserved;
+} rt_hit;
+#define RT_HIT_INSIDE      1u
+#define RT_HIT_EXACT_WALK  2u
+#define RT_HIT_INVALID_RAY 4u
+typedef struct rt_query_stats {
+    uint32_t struct_size; uint32_t reference_exact;
+    uint64_t rays, exact_walks, invalid_rays;
+    double kernel_ms, total_ms;
+    uint32_t launches, reserved;
+} rt_query_stats;
+#define RT_QUERY_DEVICE_POINTERS 1u
+#define RT_QUERY_REFERENCE_WALK  2u
+int rt_query_closest(rt_scene *scene, const rt_ray *rays, size_t n, uint32_t flags, rt_hit *out, rt_query_stats *stats /* nullable */);
+int rt_query_light_pdf(rt_scene *scene, const rt_ray *rays, size_t n, uint32_t flags, float *out, rt_query_stats *stats /* nullable */);
 
 /* Scene info the host side needs after preparation. */
 typedef struct rt_scene_info {

@@ -20,6 +20,9 @@ RT_INTEGRATOR_HW1, RT_INTEGRATOR_HW2, RT_INTEGRATOR_HW3, RT_INTEGRATOR_HW4, RT_I
 RT_INTEGRATOR_HW6, RT_INTEGRATOR_HW7, RT_INTEGRATOR_HW8 = 6, 7, 8
 RT_FLAG_OUT_DEVICE, RT_FLAG_COUNTERS, RT_FLAG_SAMPLE_SEEDS, RT_FLAG_RUSSIAN_ROULETTE = 1, 2, 4, 8
 RT_BUILD_DEVICE_BVH = 1
+RT_QUERY_DEVICE_POINTERS, RT_QUERY_REFERENCE_WALK = 1, 2
+RT_HIT_INSIDE, RT_HIT_EXACT_WALK, RT_HIT_INVALID_RAY = 1, 2, 4
+RT_HIT_MISS = 0xFFFFFFFF
 RT_PIPELINE_SINGLE, RT_PIPELINE_ROUNDS, RT_PIPELINE_PERSISTENT = 0, 1, 2
 RT_OK = 0
 RT_ERR_INVALID_ARG, RT_ERR_NO_DEVICE, RT_ERR_HIP, RT_ERR_UNSUPPORTED, RT_ERR_LIMIT = -1, -2, -3, -4, -7
@@ -101,6 +104,26 @@ class rt_noise_summary(C.Structure):
                 ("noise", C.c_double), ("worst_tile_noise", C.c_double)]
 
 
+class rt_ray(C.Structure):
+    _fields_ = [("o", C.c_float * 3), ("d", C.c_float * 3)]
+
+
+class rt_hit(C.Structure):
+    _fields_ = [("t", C.c_float), ("triangle", C.c_uint32), ("ng", C.c_float * 3), ("texcoord", C.c_float * 2), ("ns", C.c_float * 3),
+                ("tangent", C.c_float * 4), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class rt_query_stats(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("reference_exact", C.c_uint32), ("rays", C.c_uint64), ("exact_walks", C.c_uint64),
+                ("invalid_rays", C.c_uint64), ("kernel_ms", C.c_double), ("total_ms", C.c_double), ("launches", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
+# rt_ray / rt_hit as numpy records: what Scene.query_* take and return
+RAY_DTYPE = np.dtype([("o", np.float32, 3), ("d", np.float32, 3)])
+HIT_DTYPE = np.dtype([("t", np.float32), ("triangle", np.uint32), ("ng", np.float32, 3), ("texcoord", np.float32, 2), ("ns", np.float32, 3),
+                      ("tangent", np.float32, 4), ("flags", np.uint32), ("reserved", np.uint32)])
+
 # Every symbol include/rtamd.h declares; tests/test_abi.py checks the library exports them all.
 ABI_SYMBOLS = ["rt_abi_version", "rt_last_error", "rt_scene_create", "rt_scene_destroy", "rt_output_elems", "rt_render",
                "rt_unshard", "rt_scene_get_info", "rt_scene_get_light_order", "rt_load_gltf", "rt_load_txt",
@@ -111,7 +134,8 @@ ABI_SYMBOLS = ["rt_abi_version", "rt_last_error", "rt_scene_create", "rt_scene_d
                "rt_multi_accum_render", "rt_multi_accum_samples", "rt_multi_accum_resolve", "rt_multi_accum_save",
                "rt_multi_accum_load", "rt_multi_accum_destroy", "rt_noise_create", "rt_noise_update", "rt_noise_reset",
                "rt_noise_batches", "rt_noise_estimate", "rt_noise_destroy", "rt_multi_noise_create", "rt_multi_noise_update",
-               "rt_multi_noise_reset", "rt_multi_noise_batches", "rt_multi_noise_estimate", "rt_multi_noise_destroy"]
+               "rt_multi_noise_reset", "rt_multi_noise_batches", "rt_multi_noise_estimate", "rt_multi_noise_destroy", "rt_query_closest",
+               "rt_query_light_pdf"]
 
 if not os.path.exists(LIB_PATH):
     raise ImportError(f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
@@ -167,6 +191,8 @@ for _family in ("rt_noise", "rt_multi_noise"):
         getattr(lib, _family + _name).argtypes = [C.c_void_p]
     getattr(lib, _family + "_estimate").argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(rt_noise_summary)]
     getattr(lib, _family + "_destroy").restype = None
+for _name in ("rt_query_closest", "rt_query_light_pdf"):
+    getattr(lib, _name).argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.POINTER(rt_query_stats)]
 
 
 def _check(code):
@@ -310,6 +336,19 @@ def write_ppm(path, rgb8):
 def dominant_kernel_name(st):
     """Name of the kernel rt_stats.dominant_kernel_ms / _launches refer to (for the hw8 / hw7 integrators)."""
     return {RT_PIPELINE_ROUNDS: "wf_traverse_kernel", RT_PIPELINE_PERSISTENT: "pt_persistent_kernel"}.get(st.pipeline, "render_hw8_kernel")
+
+
+def pack_rays(o, d):
+    """Origins and directions, (n, 3) each (or one (3,) vector), as one contiguous array of rt_ray records.  Refuses anything else
+    before the library is called: the C side only sees a pointer and a count."""
+    o, d = np.asarray(o, dtype=np.float32), np.asarray(d, dtype=np.float32)
+    if o.ndim == 1 and d.ndim == 1:
+        o, d = o[None, :], d[None, :]
+    if o.ndim != 2 or o.shape[1] != 3 or d.shape != o.shape:
+        raise ValueError(f"ray origins and directions must both be (n, 3), got {o.shape} and {d.shape}")
+    rays = np.zeros(o.shape[0], dtype=RAY_DTYPE)
+    rays["o"], rays["d"] = o, d
+    return rays
 
 
 def make_params(width, height, samples, integrator=RT_INTEGRATOR_HW8, ray_depth=0, shard_index=0, shard_count=1,
@@ -577,3 +616,32 @@ class Scene(_Handle):
         params.flags |= RT_FLAG_OUT_DEVICE
         _check(lib.rt_render(self._h, C.byref(params), out_rgb_ptr, out_rgb8_ptr, C.byref(st)))
         return st
+
+    def _query(self, fn, rays_ptr, n, flags, out_ptr):
+        st = rt_query_stats()
+        st.struct_size = C.sizeof(rt_query_stats)
+        _check(fn(self._h, rays_ptr, n, flags, out_ptr, C.byref(st)))
+        return st
+
+    def query_closest(self, o, d, flags=0):
+        """Closest hits of the rays (o[i], d[i]) (rt_query_closest): (array of HIT_DTYPE records, rt_query_stats)."""
+        if flags & RT_QUERY_DEVICE_POINTERS:
+            raise ValueError("query_closest takes host arrays; device memory goes through query_closest_device")
+        rays = pack_rays(o, d)
+        hits = np.zeros(rays.shape[0], dtype=HIT_DTYPE)
+        return hits, self._query(lib.rt_query_closest, rays.ctypes.data, rays.shape[0], flags, hits.ctypes.data)
+
+    def query_light_pdf(self, x, d, flags=0):
+        """Light pdf of the directions d[i] seen from x[i] (rt_query_light_pdf): (float32 array, rt_query_stats)."""
+        if flags & RT_QUERY_DEVICE_POINTERS:
+            raise ValueError("query_light_pdf takes host arrays; device memory goes through query_light_pdf_device")
+        rays = pack_rays(x, d)
+        pdf = np.zeros(rays.shape[0], dtype=np.float32)
+        return pdf, self._query(lib.rt_query_light_pdf, rays.ctypes.data, rays.shape[0], flags, pdf.ctypes.data)
+
+    def query_closest_device(self, rays_ptr, n, out_ptr, flags=0):
+        """The same on device memory of the scene's GPU (raw pointers, e.g. torch tensor data_ptr()): n rt_ray in, n rt_hit out."""
+        return self._query(lib.rt_query_closest, rays_ptr, n, flags | RT_QUERY_DEVICE_POINTERS, out_ptr)
+
+    def query_light_pdf_device(self, rays_ptr, n, out_ptr, flags=0):
+        return self._query(lib.rt_query_light_pdf, rays_ptr, n, flags | RT_QUERY_DEVICE_POINTERS, out_ptr)

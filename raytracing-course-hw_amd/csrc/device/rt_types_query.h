@@ -1,0 +1,39 @@
+// One chunk of a batched ray query as its kernels see it (rt_query.h), and what the host side (rtamd_query.hip) asks of the translation
+// unit that holds them (rtamd_api.hip: every __global__ keeps one definition there).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+struct rt_scene;
+
+namespace rtamd {
+
+// Counter words of a chunk (QueryView::ctr; zeroed before every chunk) and of a call (QueryView::totals; zeroed once per call).
+enum { RQ_CTR_FAST = 0,      // rays on the fast list (q_fast)
+       RQ_CTR_EXACT = 1,     // rays on the exact list (q_exact)
+       RQ_CTR_HEAD = 2,      // dynamic tail of the fast list (wf_steal)
+       RQ_CTR_WORDS = 4 };
+enum { RQ_TOTAL_EXACT = 0, RQ_TOTAL_INVALID = 1, RQ_TOTAL_WORDS = 2 };
+
+struct QueryView {
+    const float *rays;            // n x {o.xyz, d.xyz} (rt_ray): the chunk's rays, staged or the caller's own device memory
+    uint32_t n;
+    uint32_t reference_walk;      // RT_QUERY_REFERENCE_WALK: every valid ray goes on the exact list
+    float origin_bound;           // max |coordinate| of scene and camera: what the gate's margin box_c2 was derived for (rt_query.h)
+    float4 *rec;                  // closest hit, per ray: t, u, v, hit word with the gap code (what WfClosest::store leaves in a path record)
+    uint32_t *q_fast, *q_exact;   // ray indices, n words each
+    uint32_t *ctr;                // RQ_CTR_*
+    unsigned long long *totals;   // RQ_TOTAL_*
+    uint4 *hits;                  // closest hit: 4 per ray (rt_hit), 16-byte aligned
+    float *pdf;                   // light pdf: 1 per ray
+    uint32_t *ovf;                // SPILL variant: WF_OVF words per persistent thread
+};
+
+// Launch geometry of the persistent walk (the round pipeline's traverse launch) as the host side sizes its overflow area by it.
+#define RQ_BLOCKS_PER_CU 5u
+size_t query_ovf_words(const rt_scene *scene);                        // 0 when neither tree needs the SPILL variant
+// The launches of one chunk on `stream`; both return the number of launches.  The scene is only read.
+uint32_t query_launch_closest(const rt_scene *scene, const QueryView &Q, hipStream_t stream);
+uint32_t query_launch_light_pdf(const rt_scene *scene, const QueryView &Q, hipStream_t stream);
+
+} // namespace rtamd

@@ -141,6 +141,8 @@ struct rt_scene {
     size_t pt_record_bytes = 0, pt_group_bytes = 0;
     uint32_t pt_blocks = 0, pt_launches = 0;
     double pt_rebalance_ms = 0, pt_imbalance = 0;
+    uint8_t *query_stage = nullptr;  // batched ray queries (rtamd_query.hip): the staging of one chunk, allocated by the first query
+    size_t query_stage_bytes = 0;
     void free_wf() {
         for (void *p : wf_allocs) (void)hipFree(p);
         wf_allocs.clear();
@@ -153,6 +155,7 @@ struct rt_scene {
         if (pt_records) (void)hipFree(pt_records);
         if (pt_groups) (void)hipFree(pt_groups);
         if (d_pt_debug) (void)hipFree(d_pt_debug);
+        if (query_stage) (void)hipFree(query_stage);
         for (void *p : allocations) (void)hipFree(p);
         if (ev_start) (void)hipEventDestroy(ev_start);
         if (ev_stop) (void)hipEventDestroy(ev_stop);

@@ -17,6 +17,7 @@
 #include "host/rt_accum_state.h"
 #include "device/rt_kernels_hw8.h"
 #include "device/rt_wavefront.h"
+#include "device/rt_query.h"
 #include "device/rt_persistent.h"
 #include "device/rt_kernels_hw6.h"
 #include "device/rt_persistent_hw6.h"
@@ -1029,3 +1030,57 @@ int rt_accum_load(rt_accum *a, const void *blob, size_t size) {
 }
 
 } // extern "C"
+
+// ---- batched ray queries: the launches of one chunk (device/rt_query.h; the host side is rtamd_query.hip) -------------------------------
+// The geometry of the round pipeline's traverse launch at its defaults: RQ_BLOCKS_PER_CU blocks of 256 per CU with 30 KB of stack columns
+// each, refill at 16 idle lanes, leaf batch 20 or 112/256 of the active lanes, a quarter of the list handed out dynamically; fewer blocks
+// when the chunk has fewer rays than their lanes.  Not tuned for the queries (profiles/r20_ray_queries.txt).
+namespace {
+
+struct QueryGeometry { SceneView V; int lds_limit; bool spill_scene, deep_lights; unsigned walk_blocks, flat_blocks, exact_blocks; };
+
+QueryGeometry query_geometry(const rt_scene *scene, uint32_t n) {
+    QueryGeometry G;
+    G.V = scene->view;
+    if (G.V.exact_boxes != 1u) { G.V.exact_boxes = 0u; G.V.n_tripwire_groups = 0u; G.V.cull_k = 4.8e-7f; } // no gate: the tie tolerance only, as check_frame sets it
+    G.lds_limit = WF_STACK;
+    G.spill_scene = scene->info.bvh_depth > (uint32_t)WF_STACK;
+    G.deep_lights = scene->info.light_bvh_depth > (uint32_t)WF_STACK;
+    const unsigned need = (n + 255u) / 256u;
+    G.walk_blocks = std::max(1u, std::min((unsigned)scene->n_cus * RQ_BLOCKS_PER_CU, need));
+    G.flat_blocks = std::max(1u, std::min((unsigned)scene->n_cus * 16u, need));
+    G.exact_blocks = std::max(1u, std::min((unsigned)scene->n_cus, (n + 63u) / 64u));
+    return G;
+}
+const int rq_refill = WF_REFILL, rq_leaf_batch = WF_LEAF_BATCH | (112 << 16), rq_dyn = 64;
+
+} // namespace
+
+size_t rtamd::query_ovf_words(const rt_scene *scene) {
+    return scene->info.bvh_depth > (uint32_t)WF_STACK ? (size_t)scene->n_cus * RQ_BLOCKS_PER_CU * 256u * WF_OVF : 0u;
+}
+
+uint32_t rtamd::query_launch_closest(const rt_scene *scene, const QueryView &Q, hipStream_t stream) {
+    const QueryGeometry G = query_geometry(scene, Q.n);
+    hipLaunchKernelGGL(dev::rq_classify_kernel<false>, dim3(G.flat_blocks), dim3(256), 0, stream, G.V, Q, 0u);
+    uint32_t launches = 2;
+    if (!Q.reference_walk) {
+        if (G.spill_scene) hipLaunchKernelGGL(dev::rq_closest_kernel<true>, dim3(G.walk_blocks), dim3(256), 0, stream, G.V, Q, rq_refill, rq_leaf_batch, rq_dyn, G.lds_limit);
+        else hipLaunchKernelGGL(dev::rq_closest_kernel<false>, dim3(G.walk_blocks), dim3(256), 0, stream, G.V, Q, rq_refill, rq_leaf_batch, rq_dyn, G.lds_limit);
+        hipLaunchKernelGGL(dev::rq_resolve_kernel, dim3(G.flat_blocks), dim3(256), 0, stream, G.V, Q);
+        launches += 2;
+    }
+    hipLaunchKernelGGL(dev::rq_closest_exact_kernel, dim3(G.exact_blocks), dim3(64), 0, stream, G.V, Q);
+    HIP_CHECK(hipGetLastError());
+    return launches;
+}
+
+uint32_t rtamd::query_launch_light_pdf(const rt_scene *scene, const QueryView &Q, hipStream_t stream) {
+    const QueryGeometry G = query_geometry(scene, Q.n);
+    const bool lean = !Q.reference_walk && !G.deep_lights;
+    hipLaunchKernelGGL(dev::rq_classify_kernel<true>, dim3(G.flat_blocks), dim3(256), 0, stream, G.V, Q, lean ? 0u : 1u);
+    if (lean) hipLaunchKernelGGL(dev::rq_light_kernel, dim3(G.walk_blocks), dim3(256), 0, stream, G.V, Q, rq_refill, rq_leaf_batch, rq_dyn);
+    hipLaunchKernelGGL(dev::rq_light_exact_kernel, dim3(G.exact_blocks), dim3(64), 0, stream, G.V, Q);
+    HIP_CHECK(hipGetLastError());
+    return lean ? 3u : 2u;
+}
