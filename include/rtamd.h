@@ -15,7 +15,9 @@
  *   rt_scene_destroy  replaces  Scene::~Scene (hw8/src/scene.cpp:56-63).
  * Below that seam, for a caller with a render loop of its own:
  *   rt_query_closest    answers  BVH::intersect (hw8/src/include/bvh.h:111-142) for a batch of rays,
- *   rt_query_light_pdf  answers  FiguresMix::pdf (hw8/src/include/distributions.h:122-124).
+ *   rt_query_light_pdf  answers  FiguresMix::pdf (hw8/src/include/distributions.h:122-124),
+ *   rt_query_surface / rt_query_environment / rt_camera_rays  answer  the material fetch, the miss colour and getCameraRay of
+ *                     Scene::getColor / getPixel (hw8/src/scene.cpp:90-149,179-186); rt_render_guides composes them per pixel.
  *
  * Conventions: plain C, plain pointers and sizes, no exceptions cross the boundary.
  * Every function returns 0 on success and a negative rt_status on failure;
@@ -450,7 +452,7 @@ void rt_multi_noise_destroy(rt_multi_noise *n);
  *          RT_QUERY_REFERENCE_WALK: every valid ray takes the reference-order walk, one lane per ray -- the referee of the fast path;
  *          the answers are the same bits.
  * Memory   rays are processed in chunks of 262,144, so the staging (29 MB per scene, allocated by the first query, freed with the
- *          scene) does not grow with n.  Queries are serialised with the scene's other calls by the caller, like every call; they
+ *          scene; 57 MB once a surface query or a guide pass has run) does not grow with n.  Queries are serialised with the scene's other calls by the caller, like every call; they
  *          only read the scene and disturb no rt_accum.
  * stats    struct_size in: sizeof(rt_query_stats).  exact_walks: valid rays answered by the reference-order walk -- those the gate
  *          (device/rt_exact.h) sent there, and those outside what the gate was derived for: an origin coordinate beyond the largest
@@ -479,6 +481,49 @@ typedef struct rt_query_stats {
 #define RT_QUERY_REFERENCE_WALK  2u
 int rt_query_closest(rt_scene *scene, const rt_ray *rays, size_t n, uint32_t flags, rt_hit *out, rt_query_stats *stats /* nullable */);
 int rt_query_light_pdf(rt_scene *scene, const rt_ray *rays, size_t n, uint32_t flags, float *out, rt_query_stats *stats /* nullable */);
+
+/* ---- the first-hit layer: surface, environment, camera rays, guide images ---------------------------------------------------
+ * What a caller with a render loop of its own needs next to the closest hit, each the reference's own arithmetic bit for bit and
+ * with the device functions the renders use (device/rt_query_surface.h).  Same scenes, same refusals, same chunks of 262,144 and
+ * the same staging as the two queries above; flags takes RT_QUERY_DEVICE_POINTERS only.  ABI version 6 still.
+ *
+ * rt_query_surface      what Scene::getColor knows about a hit before it samples a direction (hw8/src/scene.cpp:99-149), with hw8's
+ *          material rule (textures, normal map, roughness floor 0.08; hw7's own is not offered).  In: the rt_hit records that
+ *          rt_query_closest wrote, or records of the caller's own: only triangle (LOAD order), texcoord, ns and tangent (xyz, w) are
+ *          read, the ray is not needed.  Out, 64 bytes per hit: color = the base-colour texture tap (sRGB decoded) or 1,1,1;
+ *          alpha = max(0.08, roughnessFactor * mr.y)^2; emission = emissiveFactor (* the emissive tap); metallic = mr.z of the
+ *          metallic-roughness tap (1 without one); sn = the shading normal after the normal map; material = the material's index;
+ *          base_color, base_metallic = the material's factors (the other two arguments of the reference's brdf).
+ *          A miss (triangle 0xFFFFFFFF) answers zeros with material = 0xFFFFFFFF.  So does a record with triangle >= n_triangles
+ *          or with a NaN or an infinity in texcoord, ns or tangent; those are counted in rt_query_stats.invalid_rays and lead to
+ *          no read of the scene.  exact_walks is 0.  With RT_QUERY_DEVICE_POINTERS both arrays are 16-byte aligned.
+ *          The first call grows the scene's staging to 57 MB and makes a table of 4 bytes per triangle; neither is part of
+ *          rt_scene_info.device_bytes, both go with the scene.
+ * rt_query_environment  what a ray that misses sees (scene.cpp:90-97) in its direction d as given: the background colour, or the
+ *          equirect lookup of the environment map (a d.y beyond +-1 gives the reference's NaN).  n x 3 floats.  Invalid rays (the
+ *          rule of rt_query_closest) answer 0,0,0 and are counted.
+ * rt_camera_rays        Scene::getCameraRay (scene.cpp:179-186) for a frame of width x height and n points (nx, ny) of its image
+ *          plane in pixel units: the renderer's sample is nx = x + u1, ny = y + u2 with its two random draws, a pixel's centre
+ *          x + 0.5, y + 0.5.  width or height < 1 is RT_ERR_INVALID_ARG, and so is a NaN or an infinity in a host xy array; from a
+ *          device array such a point comes out as a NaN direction, which every query then answers as an invalid ray.
+ * rt_render_guides      the guide images a denoiser takes next to a noisy frame, row-major, row 0 first, every plane nullable: per
+ *          pixel the camera ray through its centre, rt_query_closest, then on a hit albedo = base_color * color (one float product
+ *          per channel), normal = sn, depth = t and the surface's emission, on a miss albedo = rt_query_environment's answer and
+ *          0 elsewhere.  No plane depends on a random number, a sample count or the pipeline.  The rays are made, walked and
+ *          shaded on the device chunk by chunk, so the memory is the staging whatever the frame's size; stats are those of the
+ *          closest-hit query over width * height rays, with every launch counted.  One GPU, unsharded frames. */
+typedef struct rt_surface {
+    float color[3];      float alpha;
+    float emission[3];   float metallic;
+    float sn[3];         uint32_t material;
+    float base_color[3]; float base_metallic;
+} rt_surface;
+int rt_query_surface(rt_scene *scene, const rt_hit *hits, size_t n, uint32_t flags, rt_surface *out, rt_query_stats *stats /* nullable */);
+int rt_query_environment(rt_scene *scene, const rt_ray *rays, size_t n, uint32_t flags, float *out_rgb /* n*3 */, rt_query_stats *stats /* nullable */);
+int rt_camera_rays(rt_scene *scene, int32_t width, int32_t height, const float *xy /* n*2 */, size_t n, uint32_t flags, rt_ray *out);
+int rt_render_guides(rt_scene *scene, int32_t width, int32_t height, uint32_t flags,
+                     float *albedo /* W*H*3 */, float *normal /* W*H*3 */, float *depth /* W*H */, float *emission /* W*H*3 */,
+                     rt_query_stats *stats /* nullable */);
 
 /* Scene info the host side needs after preparation. */
 typedef struct rt_scene_info {

@@ -123,6 +123,8 @@ class rt_query_stats(C.Structure):
 RAY_DTYPE = np.dtype([("o", np.float32, 3), ("d", np.float32, 3)])
 HIT_DTYPE = np.dtype([("t", np.float32), ("triangle", np.uint32), ("ng", np.float32, 3), ("texcoord", np.float32, 2), ("ns", np.float32, 3),
                       ("tangent", np.float32, 4), ("flags", np.uint32), ("reserved", np.uint32)])
+SURFACE_DTYPE = np.dtype([("color", np.float32, 3), ("alpha", np.float32), ("emission", np.float32, 3), ("metallic", np.float32),
+                          ("sn", np.float32, 3), ("material", np.uint32), ("base_color", np.float32, 3), ("base_metallic", np.float32)])
 
 # Every symbol include/rtamd.h declares; tests/test_abi.py checks the library exports them all.
 ABI_SYMBOLS = ["rt_abi_version", "rt_last_error", "rt_scene_create", "rt_scene_destroy", "rt_output_elems", "rt_render",
@@ -135,7 +137,7 @@ ABI_SYMBOLS = ["rt_abi_version", "rt_last_error", "rt_scene_create", "rt_scene_d
                "rt_multi_accum_load", "rt_multi_accum_destroy", "rt_noise_create", "rt_noise_update", "rt_noise_reset",
                "rt_noise_batches", "rt_noise_estimate", "rt_noise_destroy", "rt_multi_noise_create", "rt_multi_noise_update",
                "rt_multi_noise_reset", "rt_multi_noise_batches", "rt_multi_noise_estimate", "rt_multi_noise_destroy", "rt_query_closest",
-               "rt_query_light_pdf"]
+               "rt_query_light_pdf", "rt_query_surface", "rt_query_environment", "rt_camera_rays", "rt_render_guides"]
 
 if not os.path.exists(LIB_PATH):
     raise ImportError(f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
@@ -191,8 +193,10 @@ for _family in ("rt_noise", "rt_multi_noise"):
         getattr(lib, _family + _name).argtypes = [C.c_void_p]
     getattr(lib, _family + "_estimate").argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(rt_noise_summary)]
     getattr(lib, _family + "_destroy").restype = None
-for _name in ("rt_query_closest", "rt_query_light_pdf"):
+for _name in ("rt_query_closest", "rt_query_light_pdf", "rt_query_surface", "rt_query_environment"):
     getattr(lib, _name).argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.POINTER(rt_query_stats)]
+lib.rt_camera_rays.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p]
+lib.rt_render_guides.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_uint32] + [C.c_void_p] * 4 + [C.POINTER(rt_query_stats)]
 
 
 def _check(code):
@@ -645,3 +649,53 @@ class Scene(_Handle):
 
     def query_light_pdf_device(self, rays_ptr, n, out_ptr, flags=0):
         return self._query(lib.rt_query_light_pdf, rays_ptr, n, flags | RT_QUERY_DEVICE_POINTERS, out_ptr)
+
+    def query_surface(self, hits):
+        """What the shader knows about each hit before it samples a direction (rt_query_surface): (array of SURFACE_DTYPE records,
+        rt_query_stats).  hits: HIT_DTYPE records, as query_closest returns them or altered."""
+        hits = np.ascontiguousarray(hits, dtype=HIT_DTYPE).reshape(-1)
+        out = np.zeros(hits.shape[0], dtype=SURFACE_DTYPE)
+        return out, self._query(lib.rt_query_surface, hits.ctypes.data, hits.shape[0], 0, out.ctypes.data)
+
+    def query_environment(self, o, d):
+        """What the rays (o[i], d[i]) see where they miss (rt_query_environment): ((n, 3) float32 array, rt_query_stats)."""
+        rays = pack_rays(o, d)
+        rgb = np.zeros((rays.shape[0], 3), dtype=np.float32)
+        return rgb, self._query(lib.rt_query_environment, rays.ctypes.data, rays.shape[0], 0, rgb.ctypes.data)
+
+    def camera_rays(self, width, height, xy):
+        """The camera rays of a width x height frame through the points xy (n, 2) of its image plane, in pixel units
+        (rt_camera_rays): (o, d), (n, 3) float32 each."""
+        xy = np.ascontiguousarray(xy, dtype=np.float32)
+        if xy.ndim != 2 or xy.shape[1] != 2:
+            raise ValueError(f"xy must be (n, 2), got {xy.shape}")
+        rays = np.zeros(xy.shape[0], dtype=RAY_DTYPE)
+        _check(lib.rt_camera_rays(self._h, width, height, xy.ctypes.data, xy.shape[0], 0, rays.ctypes.data))
+        return rays["o"].copy(), rays["d"].copy()
+
+    def render_guides(self, width, height, albedo=True, normal=True, depth=True, emission=True):
+        """First-hit guide images of a width x height frame (rt_render_guides): (dict of the planes asked for -- albedo, normal,
+        emission (H, W, 3), depth (H, W), float32 --, rt_query_stats)."""
+        want = {"albedo": albedo, "normal": normal, "depth": depth, "emission": emission}
+        planes = {k: np.zeros((height, width) if k == "depth" else (height, width, 3), dtype=np.float32) for k, v in want.items() if v}
+        ptr = [planes[k].ctypes.data if k in planes else None for k in want]
+        st = rt_query_stats()
+        st.struct_size = C.sizeof(rt_query_stats)
+        _check(lib.rt_render_guides(self._h, width, height, 0, *ptr, C.byref(st)))
+        return planes, st
+
+    def query_surface_device(self, hits_ptr, n, out_ptr):
+        """The same on device memory of the scene's GPU: n rt_hit in, n rt_surface out, both 16-byte aligned."""
+        return self._query(lib.rt_query_surface, hits_ptr, n, RT_QUERY_DEVICE_POINTERS, out_ptr)
+
+    def query_environment_device(self, rays_ptr, n, out_ptr):
+        return self._query(lib.rt_query_environment, rays_ptr, n, RT_QUERY_DEVICE_POINTERS, out_ptr)
+
+    def camera_rays_device(self, width, height, xy_ptr, n, out_ptr):
+        _check(lib.rt_camera_rays(self._h, width, height, xy_ptr, n, RT_QUERY_DEVICE_POINTERS, out_ptr))
+
+    def render_guides_device(self, width, height, albedo_ptr=None, normal_ptr=None, depth_ptr=None, emission_ptr=None):
+        st = rt_query_stats()
+        st.struct_size = C.sizeof(rt_query_stats)
+        _check(lib.rt_render_guides(self._h, width, height, RT_QUERY_DEVICE_POINTERS, albedo_ptr, normal_ptr, depth_ptr, emission_ptr, C.byref(st)))
+        return st

@@ -16,6 +16,8 @@
 // over its mean luminance) after every slice from the second on and ends the run at the first slice where it is at most x, once
 // RTAMD_NOISE_MIN_BATCHES slices (default 4, at least 2) have been observed: the file is then the plain run's at that many samples.
 // RTAMD_NOISE_MAP=path writes the last per-pixel standard error as a grayscale PFM ("Pf", little-endian, bottom row first as PFM has it).
+// First-hit guide images for a denoiser (rt_render_guides, glTF surface, hw8 / hw7): RTAMD_GUIDES=prefix writes prefix_albedo.pfm and
+// prefix_normal.pfm ("PF") and prefix_depth.pfm ("Pf") at the frame's size before the frame is rendered; out.ppm is the run's without it.
 #include "../../../include/rtamd.h"
 #include <cmath>
 #include <cstdio>
@@ -67,14 +69,30 @@ struct NoiseTarget {
     bool active() const { return target > 0 || map; }
 };
 
-// The standard error per pixel as a grayscale PFM: "Pf", a negative scale = little-endian floats, rows from the bottom up.
-static bool write_noise_map(const char *path, int width, int height, const std::vector<float> &se) {
+// A float image (row 0 first) as a PFM: "Pf" for one channel, "PF" for three; a negative scale = little-endian floats, rows from the bottom up.
+static bool write_pfm(const std::string &path, int width, int height, int channels, const std::vector<float> &image) {
     char head[64];
-    const int n = snprintf(head, sizeof head, "Pf\n%d %d\n-1.0\n", width, height);
-    std::vector<uint8_t> file((size_t)n + se.size() * sizeof(float));
+    const int n = snprintf(head, sizeof head, "%s\n%d %d\n-1.0\n", channels == 3 ? "PF" : "Pf", width, height);
+    const size_t row = (size_t)width * channels;
+    std::vector<uint8_t> file((size_t)n + image.size() * sizeof(float));
     memcpy(file.data(), head, (size_t)n);
-    for (int y = 0; y < height; y++) memcpy(file.data() + n + (size_t)y * width * sizeof(float), se.data() + (size_t)(height - 1 - y) * width, (size_t)width * sizeof(float));
+    for (int y = 0; y < height; y++) memcpy(file.data() + n + (size_t)y * row * sizeof(float), image.data() + (size_t)(height - 1 - y) * row, row * sizeof(float));
     return write_file_atomically(path, file.data(), file.size());
+}
+
+// RTAMD_GUIDES=prefix: the first-hit guide images of the frame (rt_render_guides) as prefix_albedo.pfm, prefix_normal.pfm, prefix_depth.pfm.
+static int write_guides(rt_scene *scene, const rt_render_params &p, const std::string &prefix) {
+    const size_t px = (size_t)p.width * p.height;
+    std::vector<float> albedo(px * 3), normal(px * 3), depth(px);
+    rt_query_stats st;
+    memset(&st, 0, sizeof st);
+    st.struct_size = sizeof st;
+    if (rt_render_guides(scene, p.width, p.height, 0, albedo.data(), normal.data(), depth.data(), nullptr, &st) != RT_OK) return die();
+    fprintf(stderr, "guides: %.3f ms on the GPU in %u launches\n", st.kernel_ms, st.launches);
+    const struct { const char *name; int channels; const std::vector<float> &image; } planes[] = {{"_albedo.pfm", 3, albedo}, {"_normal.pfm", 3, normal}, {"_depth.pfm", 1, depth}};
+    for (const auto &pl : planes)
+        if (!write_pfm(prefix + pl.name, p.width, p.height, pl.channels, pl.image)) { fprintf(stderr, "error: cannot write guide image %s%s\n", prefix.c_str(), pl.name); return 1; }
+    return 0;
 }
 
 // The frame in slices: the picture after every slice is the frame of that many samples, the last one the frame of the plain run.
@@ -101,7 +119,7 @@ static int render_in_slices(Progress &acc, const rt_render_params &p, int slice,
         if (noise.map && mon.batches() >= 2) {
             std::vector<float> se((size_t)p.width * p.height);
             if (mon.estimate(se.data(), nullptr) != RT_OK) rc = die();
-            else if (!write_noise_map(noise.map, p.width, p.height, se)) { fprintf(stderr, "error: cannot write noise map %s\n", noise.map); rc = 1; }
+            else if (!write_pfm(noise.map, p.width, p.height, 1, se)) { fprintf(stderr, "error: cannot write noise map %s\n", noise.map); rc = 1; }
         } else if (noise.map) {
             fprintf(stderr, "note: no noise map written: the estimate needs two slices of this run\n");
         }
@@ -233,6 +251,13 @@ int main(int argc, const char *argv[]) {
     if ((!list.empty() || n_dev > 1) && p.integrator != RT_INTEGRATOR_HW1) {
         if (rt_multi_create(&desc, list.empty() ? nullptr : list.data(), n_dev, &multi) != RT_OK) return die();
     } else if (rt_scene_create(&desc, &scene) != RT_OK) return die();
+    if (const char *prefix = argc >= 6 ? getenv("RTAMD_GUIDES") : nullptr) { // before the frame, which they do not touch
+        rt_scene *own = nullptr; // a guide pass runs on one device: with several, on a scene of its own on the current one
+        if (!scene && rt_scene_create(&desc, &own) != RT_OK) return die();
+        const int rc = write_guides(scene ? scene : own, p, prefix);
+        rt_scene_destroy(own);
+        if (rc) return rc;
+    }
     if (sliced) {
         Progress acc;
         if ((multi ? rt_multi_accum_create(multi, &p, &acc.all) : rt_accum_create(scene, &p, &acc.one)) != RT_OK) return die();

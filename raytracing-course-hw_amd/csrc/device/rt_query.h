@@ -53,10 +53,13 @@ RT_DEV void rq_load_ray(const QueryView &Q, uint32_t i, F3 &o, F3 &d) { // rt_ra
     o = f3(p[0], p[1], p[2]); d = f3(p[3], p[4], p[5]);
 }
 RT_DEV bool rq_finite(float x) { return (__float_as_uint(x) & 0x7f800000u) != 0x7f800000u; }
+RT_DEV bool rq_valid_ray(F3 o, F3 d) { // every query's rule: finite, and d != 0
+    if (!(rq_finite(o.x) && rq_finite(o.y) && rq_finite(o.z) && rq_finite(d.x) && rq_finite(d.y) && rq_finite(d.z))) return false;
+    return fmaxf(fmaxf(fabsf(d.x), fabsf(d.y)), fabsf(d.z)) > 0.f;
+}
 RT_DEV int rq_classify(const QueryView &Q, F3 o, F3 d) {
-    if (!(rq_finite(o.x) && rq_finite(o.y) && rq_finite(o.z) && rq_finite(d.x) && rq_finite(d.y) && rq_finite(d.z))) return RQ_INVALID;
-    const float dmax = fmaxf(fmaxf(fabsf(d.x), fabsf(d.y)), fabsf(d.z)), dmin = fminf(fminf(fabsf(d.x), fabsf(d.y)), fabsf(d.z));
-    if (!(dmax > 0.f)) return RQ_INVALID;
+    if (!rq_valid_ray(o, d)) return RQ_INVALID;
+    const float dmin = fminf(fminf(fabsf(d.x), fabsf(d.y)), fabsf(d.z));
     if (Q.reference_walk) return RQ_EXACT;
     const float omax = fmaxf(fmaxf(fabsf(o.x), fabsf(o.y)), fabsf(o.z)), l2 = len2(d);
     return omax <= Q.origin_bound && dmin >= 1e-30f && l2 >= 0.00390625f && l2 <= 256.f ? RQ_FAST : RQ_EXACT;

@@ -29,11 +29,44 @@ struct QueryView {
     uint32_t *ovf;                // SPILL variant: WF_OVF words per persistent thread
 };
 
+// The first-hit layer (rt_query_surface.h): one chunk of each call as its kernel sees it.
+struct SurfaceView {
+    const uint4 *hits;            // n x 4 (rt_hit), 16-byte aligned: what rt_query_closest wrote, or the caller's own
+    uint4 *out;                   // n x 4 (rt_surface), 16-byte aligned
+    uint32_t n, n_tris;
+    const uint32_t *tri_material; // n_tris words: material index by LOAD-order triangle (rt_scene::query_materials)
+    unsigned long long *totals;   // RQ_TOTAL_*
+};
+struct EnvironmentView {
+    const float *rays;            // n x {o.xyz, d.xyz}
+    float *rgb;                   // n x 3
+    uint32_t n;
+    unsigned long long *totals;
+};
+struct CameraView {
+    const float *xy;              // n x {nx, ny} in pixel units; null = the centres of the pixels first_pixel .. first_pixel + n in frame order
+    float *rays;                  // n x {o.xyz, d.xyz}
+    uint32_t n, first_pixel;
+    int32_t width, height;
+    float tan_fov_x;              // set by query_launch_camera_rays, as the render launch sets RenderView::tan_fov_x
+};
+struct GuidesView {
+    const uint4 *hits, *surfaces; // the chunk's rt_hit and rt_surface records
+    const float *rays;            // and its camera rays
+    float *albedo, *normal, *depth, *emission; // the chunk's part of each plane; null = not wanted
+    uint32_t n;
+};
+
 // Launch geometry of the persistent walk (the round pipeline's traverse launch) as the host side sizes its overflow area by it.
 #define RQ_BLOCKS_PER_CU 5u
 size_t query_ovf_words(const rt_scene *scene);                        // 0 when neither tree needs the SPILL variant
 // The launches of one chunk on `stream`; both return the number of launches.  The scene is only read.
 uint32_t query_launch_closest(const rt_scene *scene, const QueryView &Q, hipStream_t stream);
 uint32_t query_launch_light_pdf(const rt_scene *scene, const QueryView &Q, hipStream_t stream);
+uint32_t query_launch_material_table(const rt_scene *scene, uint32_t *table, hipStream_t stream); // fills n_triangles words
+uint32_t query_launch_surface(const rt_scene *scene, const SurfaceView &V, hipStream_t stream);
+uint32_t query_launch_environment(const rt_scene *scene, const EnvironmentView &V, hipStream_t stream);
+uint32_t query_launch_camera_rays(const rt_scene *scene, const CameraView &V, hipStream_t stream);
+uint32_t query_launch_guides(const rt_scene *scene, const GuidesView &V, hipStream_t stream);
 
 } // namespace rtamd

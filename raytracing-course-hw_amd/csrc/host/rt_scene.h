@@ -143,6 +143,7 @@ struct rt_scene {
     double pt_rebalance_ms = 0, pt_imbalance = 0;
     uint8_t *query_stage = nullptr;  // batched ray queries (rtamd_query.hip): the staging of one chunk, allocated by the first query
     size_t query_stage_bytes = 0;
+    uint32_t *query_materials = nullptr; // material index by LOAD-order triangle, made by the first surface query (not part of info.device_bytes)
     void free_wf() {
         for (void *p : wf_allocs) (void)hipFree(p);
         wf_allocs.clear();
@@ -156,6 +157,7 @@ struct rt_scene {
         if (pt_groups) (void)hipFree(pt_groups);
         if (d_pt_debug) (void)hipFree(d_pt_debug);
         if (query_stage) (void)hipFree(query_stage);
+        if (query_materials) (void)hipFree(query_materials);
         for (void *p : allocations) (void)hipFree(p);
         if (ev_start) (void)hipEventDestroy(ev_start);
         if (ev_stop) (void)hipEventDestroy(ev_stop);

@@ -18,6 +18,7 @@
 #include "device/rt_kernels_hw8.h"
 #include "device/rt_wavefront.h"
 #include "device/rt_query.h"
+#include "device/rt_query_surface.h"
 #include "device/rt_persistent.h"
 #include "device/rt_kernels_hw6.h"
 #include "device/rt_persistent_hw6.h"
@@ -607,6 +608,9 @@ struct Frame {
 static const int max_ray_depth[RT_INTEGRATOR_HW8 + 1] = {0, RT_MAX_DEPTH, RT2_MAX_DEPTH, RT3_MAX_DEPTH, RT4_MAX_DEPTH, RT4_MAX_DEPTH, RT6_MAX_DEPTH, RT_MAX_DEPTH, RT_MAX_DEPTH};
 
 // Part one of a render: argument and limit checks, in the order in which each error has always won; fills `F`.  Host only.
+// scene.cpp:181 — evaluated on the host in float exactly like the reference; for the render launch and for rt_camera_rays
+static float frame_tan_fov_x(const SceneView &V, int32_t width, int32_t height) { return V.tan_fov_y * width / height; }
+
 static int check_frame(const rt_scene *scene, const rt_render_params *p, const AccumSlice *slice, const std::string &who, Frame &F) {
     if (!scene || !p) return fail(RT_ERR_INVALID_ARG, who + "null argument");
     if (p->struct_size != sizeof(rt_render_params)) return fail(RT_ERR_INVALID_ARG, who + "struct_size mismatch (ABI skew)");
@@ -623,8 +627,8 @@ static int check_frame(const rt_scene *scene, const rt_render_params *p, const A
     F.count = (p->flags & RT_FLAG_COUNTERS) != 0;
     R.work_counter = scene->d_work_counter;
     R.counters = F.count ? scene->d_counters : nullptr;
-    // scene.cpp:181,176 — evaluated on the host in float exactly like the reference
-    R.tan_fov_x = scene->view.tan_fov_y * R.width / R.height;
+    R.tan_fov_x = frame_tan_fov_x(scene->view, R.width, R.height);
+    // scene.cpp:176 — evaluated on the host in float exactly like the reference
     R.inv_samples = (float)(1.0 / R.samples);
     const uint32_t n_work = F.n_work = R.n_shard_tiles * (uint32_t)((R.tile_w >> 3) * (R.tile_h >> 3));
     const int streams = F.streams = p->sample_streams > 1 ? p->sample_streams : 1;
@@ -1083,4 +1087,39 @@ uint32_t rtamd::query_launch_light_pdf(const rt_scene *scene, const QueryView &Q
     hipLaunchKernelGGL(dev::rq_light_exact_kernel, dim3(G.exact_blocks), dim3(64), 0, stream, G.V, Q);
     HIP_CHECK(hipGetLastError());
     return lean ? 3u : 2u;
+}
+
+// The first-hit layer (device/rt_query_surface.h): flat launches, one lane per record.
+uint32_t rtamd::query_launch_material_table(const rt_scene *scene, uint32_t *table, hipStream_t stream) {
+    const uint32_t n = scene->view.n_tris;
+    if (!n) return 0u;
+    hipLaunchKernelGGL(dev::rq_material_table_kernel, dim3((n + 255u) / 256u), dim3(256), 0, stream, scene->view, table);
+    HIP_CHECK(hipGetLastError());
+    return 1u;
+}
+
+uint32_t rtamd::query_launch_surface(const rt_scene *scene, const SurfaceView &V, hipStream_t stream) {
+    hipLaunchKernelGGL(dev::rq_surface_kernel, dim3(query_geometry(scene, V.n).flat_blocks), dim3(256), 0, stream, scene->view, V);
+    HIP_CHECK(hipGetLastError());
+    return 1u;
+}
+
+uint32_t rtamd::query_launch_environment(const rt_scene *scene, const EnvironmentView &V, hipStream_t stream) {
+    hipLaunchKernelGGL(dev::rq_environment_kernel, dim3(query_geometry(scene, V.n).flat_blocks), dim3(256), 0, stream, scene->view, V);
+    HIP_CHECK(hipGetLastError());
+    return 1u;
+}
+
+uint32_t rtamd::query_launch_camera_rays(const rt_scene *scene, const CameraView &V, hipStream_t stream) {
+    CameraView C = V;
+    C.tan_fov_x = frame_tan_fov_x(scene->view, V.width, V.height);
+    hipLaunchKernelGGL(dev::rq_camera_rays_kernel, dim3(query_geometry(scene, V.n).flat_blocks), dim3(256), 0, stream, scene->view, C);
+    HIP_CHECK(hipGetLastError());
+    return 1u;
+}
+
+uint32_t rtamd::query_launch_guides(const rt_scene *scene, const GuidesView &V, hipStream_t stream) {
+    hipLaunchKernelGGL(dev::rq_guides_kernel, dim3(query_geometry(scene, V.n).flat_blocks), dim3(256), 0, stream, scene->view, V);
+    HIP_CHECK(hipGetLastError());
+    return 1u;
 }

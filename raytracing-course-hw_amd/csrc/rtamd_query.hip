@@ -1,8 +1,10 @@
-// Batched ray queries through the C-ABI (include/rtamd.h: rt_query_closest, rt_query_light_pdf): argument checks, the chunking, the
-// staging and the statistics.  No kernel and no kernel header here: the kernels (device/rt_query.h) live in rtamd_api.hip, where every
-// __global__ keeps one definition, and are launched through query_launch_* (device/rt_types_query.h).
+// Batched ray queries through the C-ABI (include/rtamd.h: rt_query_closest, rt_query_light_pdf) and the first-hit layer over them
+// (rt_query_surface, rt_query_environment, rt_camera_rays, rt_render_guides): argument checks, the chunking, the staging and the
+// statistics.  No kernel and no kernel header here: the kernels (device/rt_query.h, device/rt_query_surface.h) live in rtamd_api.hip,
+// where every __global__ keeps one definition, and are launched through query_launch_* (device/rt_types_query.h).
 #include <hip/hip_runtime.h>
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <string>
 #include "../../include/rtamd.h"
@@ -14,7 +16,8 @@ using namespace rtamd;
 
 namespace {
 
-static_assert(sizeof(rt_ray) == 24 && sizeof(rt_hit) == 64, "rt_ray is 24 bytes and rt_hit 64: the kernels read and write them as words");
+static_assert(sizeof(rt_ray) == 24 && sizeof(rt_hit) == 64 && sizeof(rt_surface) == 64,
+              "rt_ray is 24 bytes, rt_hit and rt_surface 64: the kernels read and write them as words");
 
 // Rays per chunk: what the staging is sized for.  RTAMD_QUERY_CHUNK (testing) lowers it, so that a small call crosses chunk seams; it
 // changes no answer, a ray's answer does not depend on its neighbours.
@@ -22,16 +25,21 @@ const size_t QUERY_CHUNK = 262144;
 size_t query_chunk() { return std::min(QUERY_CHUNK, (size_t)std::max(64, env_positive("RTAMD_QUERY_CHUNK", (int)QUERY_CHUNK))); }
 
 // The staging of one chunk, carved out of one allocation that the scene keeps: counters first, then the arrays in 256-byte steps.
+// The two ray queries need the first eight parts; a surface query or a guide pass (`first_hit`) grows the allocation by the last two.
+const size_t PLANE_FLOATS = 10; // albedo 3, normal 3, depth 1, emission 3
 struct QueryStage {
     uint32_t *ctr; unsigned long long *totals;
     float *rays; uint8_t *out; float4 *rec; uint32_t *q_fast, *q_exact, *ovf;
+    uint8_t *surf; float *planes;
 };
-QueryStage query_stage(rt_scene *scene) {
+QueryStage query_stage(rt_scene *scene, bool first_hit) {
     const size_t C = QUERY_CHUNK, ovf_words = query_ovf_words(scene);
     size_t at = 0;
     auto take = [&](size_t bytes) { const size_t here = at; at += (bytes + 255u) & ~(size_t)255u; return here; };
     const size_t o_ctr = take(RQ_CTR_WORDS * 4), o_tot = take(RQ_TOTAL_WORDS * 8), o_rays = take(C * sizeof(rt_ray)), o_out = take(C * sizeof(rt_hit)),
                  o_rec = take(C * 16), o_fast = take(C * 4), o_exact = take(C * 4), o_ovf = take(ovf_words * 4);
+    size_t o_surf = 0, o_planes = 0;
+    if (first_hit) { o_surf = take(C * sizeof(rt_surface)); o_planes = take(C * PLANE_FLOATS * 4); }
     grow(scene->query_stage, scene->query_stage_bytes, at);
     uint8_t *b = scene->query_stage;
     QueryStage s;
@@ -39,19 +47,24 @@ QueryStage query_stage(rt_scene *scene) {
     s.rays = (float *)(b + o_rays); s.out = b + o_out; s.rec = (float4 *)(b + o_rec);
     s.q_fast = (uint32_t *)(b + o_fast); s.q_exact = (uint32_t *)(b + o_exact);
     s.ovf = ovf_words ? (uint32_t *)(b + o_ovf) : nullptr;
+    s.surf = first_hit ? b + o_surf : nullptr; s.planes = first_hit ? (float *)(b + o_planes) : nullptr;
     return s;
 }
 
-// Both queries: `light` answers one float per ray, else one rt_hit.
-int query(rt_scene *scene, const rt_ray *rays, size_t n, uint32_t flags, void *out, rt_query_stats *stats, bool light, const std::string &who) {
+// What every call here checks first.  `allowed`: the flags the function takes, `allowed_names` their names for the message.
+int check_call(const rt_scene *scene, const rt_query_stats *stats, uint32_t flags, uint32_t allowed, const char *allowed_names, const std::string &who) {
     if (stats && stats->struct_size != sizeof(rt_query_stats)) return fail(RT_ERR_INVALID_ARG, who + "struct_size mismatch (ABI skew)");
     if (!scene) return fail(RT_ERR_INVALID_ARG, who + "null argument");
-    if (flags & ~(RT_QUERY_DEVICE_POINTERS | RT_QUERY_REFERENCE_WALK)) return fail(RT_ERR_INVALID_ARG, who + "flags other than RT_QUERY_DEVICE_POINTERS | RT_QUERY_REFERENCE_WALK");
+    if (flags & ~allowed) return fail(RT_ERR_INVALID_ARG, who + "flags other than " + allowed_names);
     if (scene->flavor != RT_INTEGRATOR_HW8) return fail(RT_ERR_UNSUPPORTED, who + "ray queries serve scenes created for hw8 / hw7 (this one was prepared for integrator " + std::to_string(scene->flavor) + ")");
-    if (light && scene->view.n_lights == 0) return fail(RT_ERR_INVALID_ARG, who + "the scene has no lights: there is no light pdf to ask for");
-    if (n && (!rays || !out)) return fail(RT_ERR_INVALID_ARG, who + "null argument");
-    const bool on_device = (flags & RT_QUERY_DEVICE_POINTERS) != 0;
-    if (n && on_device && !light && ((uintptr_t)out & 15u)) return fail(RT_ERR_INVALID_ARG, who + "with RT_QUERY_DEVICE_POINTERS the rt_hit array must be 16-byte aligned");
+    return RT_OK;
+}
+
+// One call over n items in chunks.  Per chunk: before(S, first, m, stream) queues the copies in, launch(...) the kernels (between the
+// scene's two events) and returns their number, after(...) queues the copies out; the next chunk reuses the staging, so each ends with
+// a synchronisation.  n == 0 launches nothing.
+template <class Before, class Launch, class After>
+int answer(rt_scene *scene, size_t n, rt_query_stats *stats, const std::string &who, bool first_hit, Before before, Launch launch, After after) {
     return guarded(who, [&]() -> int {
         const double t0 = now_ms();
         rt_query_stats st{};
@@ -61,27 +74,18 @@ int query(rt_scene *scene, const rt_ray *rays, size_t n, uint32_t flags, void *o
         if (n) {
             HIP_CHECK(hipSetDevice(scene->device));
             hipStream_t stream = nullptr;
-            const QueryStage S = query_stage(scene);
-            const size_t out_size = light ? sizeof(float) : sizeof(rt_hit), chunk = query_chunk();
+            const QueryStage S = query_stage(scene, first_hit);
+            const size_t chunk = query_chunk();
             HIP_CHECK(hipMemsetAsync(S.totals, 0, RQ_TOTAL_WORDS * 8, stream));
             float ms_sum = 0.f;
             for (size_t first = 0; first < n; first += chunk) {
                 const size_t m = std::min(chunk, n - first);
-                uint8_t *out_here = (uint8_t *)out + first * out_size;
-                QueryView Q{};
-                Q.n = (uint32_t)m;
-                Q.reference_walk = (flags & RT_QUERY_REFERENCE_WALK) ? 1u : 0u;
-                Q.origin_bound = scene->view.box_c2 * 1048576.f; // box_c2 = 2^-20 max|coordinate| of scene and camera
-                Q.rec = S.rec; Q.q_fast = S.q_fast; Q.q_exact = S.q_exact; Q.ctr = S.ctr; Q.totals = S.totals; Q.ovf = S.ovf;
-                if (on_device) Q.rays = (const float *)(rays + first);
-                else { HIP_CHECK(hipMemcpyAsync(S.rays, rays + first, m * sizeof(rt_ray), hipMemcpyHostToDevice, stream)); Q.rays = S.rays; }
-                uint8_t *dev_out = on_device ? out_here : S.out;
-                if (light) Q.pdf = (float *)dev_out; else Q.hits = (uint4 *)dev_out;
+                before(S, first, m, stream);
                 HIP_CHECK(hipMemsetAsync(S.ctr, 0, RQ_CTR_WORDS * 4, stream));
                 HIP_CHECK(hipEventRecord(scene->ev_start, stream));
-                st.launches += light ? query_launch_light_pdf(scene, Q, stream) : query_launch_closest(scene, Q, stream);
+                st.launches += launch(S, first, m, stream);
                 HIP_CHECK(hipEventRecord(scene->ev_stop, stream));
-                if (!on_device) HIP_CHECK(hipMemcpyAsync(out_here, S.out, m * out_size, hipMemcpyDeviceToHost, stream));
+                after(S, first, m, stream);
                 HIP_CHECK(hipStreamSynchronize(stream)); // the next chunk reuses the staging
                 float ms = 0.f;
                 HIP_CHECK(hipEventElapsedTime(&ms, scene->ev_start, scene->ev_stop));
@@ -98,6 +102,57 @@ int query(rt_scene *scene, const rt_ray *rays, size_t n, uint32_t flags, void *o
     });
 }
 
+// The closest-hit and light-pdf launches' view of a chunk of m rays at `rays`.
+QueryView walk_view(const rt_scene *scene, const QueryStage &S, size_t m, uint32_t flags, const float *rays) {
+    QueryView Q{};
+    Q.n = (uint32_t)m;
+    Q.reference_walk = (flags & RT_QUERY_REFERENCE_WALK) ? 1u : 0u;
+    Q.origin_bound = scene->view.box_c2 * 1048576.f; // box_c2 = 2^-20 max|coordinate| of scene and camera
+    Q.rec = S.rec; Q.q_fast = S.q_fast; Q.q_exact = S.q_exact; Q.ctr = S.ctr; Q.totals = S.totals; Q.ovf = S.ovf;
+    Q.rays = rays;
+    return Q;
+}
+
+// Both ray queries: `light` answers one float per ray, else one rt_hit.
+int query(rt_scene *scene, const rt_ray *rays, size_t n, uint32_t flags, void *out, rt_query_stats *stats, bool light, const std::string &who) {
+    if (const int rc = check_call(scene, stats, flags, RT_QUERY_DEVICE_POINTERS | RT_QUERY_REFERENCE_WALK, "RT_QUERY_DEVICE_POINTERS | RT_QUERY_REFERENCE_WALK", who)) return rc;
+    if (light && scene->view.n_lights == 0) return fail(RT_ERR_INVALID_ARG, who + "the scene has no lights: there is no light pdf to ask for");
+    if (n && (!rays || !out)) return fail(RT_ERR_INVALID_ARG, who + "null argument");
+    const bool on_device = (flags & RT_QUERY_DEVICE_POINTERS) != 0;
+    if (n && on_device && !light && ((uintptr_t)out & 15u)) return fail(RT_ERR_INVALID_ARG, who + "with RT_QUERY_DEVICE_POINTERS the rt_hit array must be 16-byte aligned");
+    const size_t out_size = light ? sizeof(float) : sizeof(rt_hit);
+    return answer(scene, n, stats, who, false,
+        [&](const QueryStage &S, size_t first, size_t m, hipStream_t stream) {
+            if (!on_device) HIP_CHECK(hipMemcpyAsync(S.rays, rays + first, m * sizeof(rt_ray), hipMemcpyHostToDevice, stream));
+        },
+        [&](const QueryStage &S, size_t first, size_t m, hipStream_t stream) {
+            QueryView Q = walk_view(scene, S, m, flags, on_device ? (const float *)(rays + first) : S.rays);
+            uint8_t *dev_out = on_device ? (uint8_t *)out + first * out_size : S.out;
+            if (light) Q.pdf = (float *)dev_out; else Q.hits = (uint4 *)dev_out;
+            return light ? query_launch_light_pdf(scene, Q, stream) : query_launch_closest(scene, Q, stream);
+        },
+        [&](const QueryStage &S, size_t first, size_t m, hipStream_t stream) {
+            if (!on_device) HIP_CHECK(hipMemcpyAsync((uint8_t *)out + first * out_size, S.out, m * out_size, hipMemcpyDeviceToHost, stream));
+        });
+}
+
+// The material index of every LOAD-order triangle, made on the device from the shading records the first time a surface is asked for.
+void ensure_materials(rt_scene *scene, hipStream_t stream) {
+    if (scene->query_materials) return;
+    OwnedDev table;
+    HIP_CHECK(hipMalloc(&table.p, std::max<size_t>(scene->view.n_tris, 4u) * sizeof(uint32_t)));
+    query_launch_material_table(scene, (uint32_t *)table.p, stream);
+    scene->query_materials = (uint32_t *)table.release();
+}
+
+SurfaceView surface_view(const rt_scene *scene, const QueryStage &S, size_t m, const void *hits, void *out) {
+    SurfaceView V{};
+    V.hits = (const uint4 *)hits; V.out = (uint4 *)out;
+    V.n = (uint32_t)m; V.n_tris = scene->view.n_tris;
+    V.tri_material = scene->query_materials; V.totals = S.totals;
+    return V;
+}
+
 } // namespace
 
 extern "C" {
@@ -108,6 +163,105 @@ int rt_query_closest(rt_scene *scene, const rt_ray *rays, size_t n, uint32_t fla
 
 int rt_query_light_pdf(rt_scene *scene, const rt_ray *rays, size_t n, uint32_t flags, float *out, rt_query_stats *stats) {
     return query(scene, rays, n, flags, out, stats, true, "rt_query_light_pdf: ");
+}
+
+int rt_query_surface(rt_scene *scene, const rt_hit *hits, size_t n, uint32_t flags, rt_surface *out, rt_query_stats *stats) {
+    const std::string who = "rt_query_surface: ";
+    if (const int rc = check_call(scene, stats, flags, RT_QUERY_DEVICE_POINTERS, "RT_QUERY_DEVICE_POINTERS", who)) return rc;
+    if (n && (!hits || !out)) return fail(RT_ERR_INVALID_ARG, who + "null argument");
+    const bool on_device = (flags & RT_QUERY_DEVICE_POINTERS) != 0;
+    if (n && on_device && (((uintptr_t)hits | (uintptr_t)out) & 15u))
+        return fail(RT_ERR_INVALID_ARG, who + "with RT_QUERY_DEVICE_POINTERS the rt_hit and rt_surface arrays must be 16-byte aligned");
+    return answer(scene, n, stats, who, true,
+        [&](const QueryStage &S, size_t first, size_t m, hipStream_t stream) {
+            ensure_materials(scene, stream);
+            if (!on_device) HIP_CHECK(hipMemcpyAsync(S.out, hits + first, m * sizeof(rt_hit), hipMemcpyHostToDevice, stream));
+        },
+        [&](const QueryStage &S, size_t first, size_t m, hipStream_t stream) {
+            return query_launch_surface(scene, on_device ? surface_view(scene, S, m, hits + first, out + first) : surface_view(scene, S, m, S.out, S.surf), stream);
+        },
+        [&](const QueryStage &S, size_t first, size_t m, hipStream_t stream) {
+            if (!on_device) HIP_CHECK(hipMemcpyAsync(out + first, S.surf, m * sizeof(rt_surface), hipMemcpyDeviceToHost, stream));
+        });
+}
+
+int rt_query_environment(rt_scene *scene, const rt_ray *rays, size_t n, uint32_t flags, float *out_rgb, rt_query_stats *stats) {
+    const std::string who = "rt_query_environment: ";
+    if (const int rc = check_call(scene, stats, flags, RT_QUERY_DEVICE_POINTERS, "RT_QUERY_DEVICE_POINTERS", who)) return rc;
+    if (n && (!rays || !out_rgb)) return fail(RT_ERR_INVALID_ARG, who + "null argument");
+    const bool on_device = (flags & RT_QUERY_DEVICE_POINTERS) != 0;
+    return answer(scene, n, stats, who, false, // the colours of a chunk are staged where a closest-hit query keeps its 16-byte records
+        [&](const QueryStage &S, size_t first, size_t m, hipStream_t stream) {
+            if (!on_device) HIP_CHECK(hipMemcpyAsync(S.rays, rays + first, m * sizeof(rt_ray), hipMemcpyHostToDevice, stream));
+        },
+        [&](const QueryStage &S, size_t first, size_t m, hipStream_t stream) {
+            EnvironmentView V{};
+            V.rays = on_device ? (const float *)(rays + first) : S.rays;
+            V.rgb = on_device ? out_rgb + 3 * first : (float *)S.rec;
+            V.n = (uint32_t)m; V.totals = S.totals;
+            return query_launch_environment(scene, V, stream);
+        },
+        [&](const QueryStage &S, size_t first, size_t m, hipStream_t stream) {
+            if (!on_device) HIP_CHECK(hipMemcpyAsync(out_rgb + 3 * first, S.rec, m * 3 * sizeof(float), hipMemcpyDeviceToHost, stream));
+        });
+}
+
+int rt_camera_rays(rt_scene *scene, int32_t width, int32_t height, const float *xy, size_t n, uint32_t flags, rt_ray *out) {
+    const std::string who = "rt_camera_rays: ";
+    if (const int rc = check_call(scene, nullptr, flags, RT_QUERY_DEVICE_POINTERS, "RT_QUERY_DEVICE_POINTERS", who)) return rc;
+    if (width < 1 || height < 1) return fail(RT_ERR_INVALID_ARG, who + "width and height must be positive");
+    if (n && (!xy || !out)) return fail(RT_ERR_INVALID_ARG, who + "null argument");
+    const bool on_device = (flags & RT_QUERY_DEVICE_POINTERS) != 0;
+    if (!on_device)
+        for (size_t i = 0; i < 2 * n; i++)
+            if (!std::isfinite(xy[i])) return fail(RT_ERR_INVALID_ARG, who + "xy holds a NaN or an infinity (point " + std::to_string(i / 2) + ")");
+    return answer(scene, n, nullptr, who, false, // the points of a chunk are staged where a closest-hit query keeps its 16-byte records
+        [&](const QueryStage &S, size_t first, size_t m, hipStream_t stream) {
+            if (!on_device) HIP_CHECK(hipMemcpyAsync(S.rec, xy + 2 * first, m * 2 * sizeof(float), hipMemcpyHostToDevice, stream));
+        },
+        [&](const QueryStage &S, size_t first, size_t m, hipStream_t stream) {
+            CameraView V{};
+            V.xy = on_device ? xy + 2 * first : (const float *)S.rec;
+            V.rays = on_device ? (float *)(out + first) : S.rays;
+            V.n = (uint32_t)m; V.width = width; V.height = height;
+            return query_launch_camera_rays(scene, V, stream);
+        },
+        [&](const QueryStage &S, size_t first, size_t m, hipStream_t stream) {
+            if (!on_device) HIP_CHECK(hipMemcpyAsync(out + first, S.rays, m * sizeof(rt_ray), hipMemcpyDeviceToHost, stream));
+        });
+}
+
+int rt_render_guides(rt_scene *scene, int32_t width, int32_t height, uint32_t flags, float *albedo, float *normal, float *depth, float *emission,
+                     rt_query_stats *stats) {
+    const std::string who = "rt_render_guides: ";
+    if (const int rc = check_call(scene, stats, flags, RT_QUERY_DEVICE_POINTERS, "RT_QUERY_DEVICE_POINTERS", who)) return rc;
+    if (width < 1 || height < 1) return fail(RT_ERR_INVALID_ARG, who + "width and height must be positive");
+    if ((int64_t)width * height >= 2147483647LL) return fail(RT_ERR_INVALID_ARG, who + "image too large (width * height must stay below 2^31-1)");
+    const bool on_device = (flags & RT_QUERY_DEVICE_POINTERS) != 0;
+    // the planes of a chunk in the staging, in this order: {plane, floats per pixel, offset in floats per pixel of the chunk}
+    struct Plane { float *p; size_t k, at; } planes[4] = {{albedo, 3, 0}, {normal, 3, 3}, {depth, 1, 6}, {emission, 3, 7}};
+    return answer(scene, (size_t)width * height, stats, who, true,
+        [&](const QueryStage &, size_t, size_t, hipStream_t stream) { ensure_materials(scene, stream); },
+        [&](const QueryStage &S, size_t first, size_t m, hipStream_t stream) {
+            CameraView C{};
+            C.rays = S.rays; C.n = (uint32_t)m; C.first_pixel = (uint32_t)first; C.width = width; C.height = height;
+            uint32_t launches = query_launch_camera_rays(scene, C, stream);
+            QueryView Q = walk_view(scene, S, m, 0u, S.rays);
+            Q.hits = (uint4 *)S.out;
+            launches += query_launch_closest(scene, Q, stream);
+            launches += query_launch_surface(scene, surface_view(scene, S, m, S.out, S.surf), stream);
+            GuidesView G{};
+            G.hits = (const uint4 *)S.out; G.surfaces = (const uint4 *)S.surf; G.rays = S.rays; G.n = (uint32_t)m;
+            float **to[4] = {&G.albedo, &G.normal, &G.depth, &G.emission};
+            for (int k = 0; k < 4; k++)
+                if (planes[k].p) *to[k] = on_device ? planes[k].p + planes[k].k * first : S.planes + planes[k].at * QUERY_CHUNK;
+            return launches + query_launch_guides(scene, G, stream);
+        },
+        [&](const QueryStage &S, size_t first, size_t m, hipStream_t stream) {
+            if (on_device) return;
+            for (const Plane &pl : planes)
+                if (pl.p) HIP_CHECK(hipMemcpyAsync(pl.p + pl.k * first, S.planes + pl.at * QUERY_CHUNK, m * pl.k * sizeof(float), hipMemcpyDeviceToHost, stream));
+        });
 }
 
 } // extern "C"

@@ -6,6 +6,7 @@
 # RTAMD_SLICE=n / RTAMD_CHECKPOINT=path render the glTF surface in slices with a checkpoint, on every visible GPU;
 # RTAMD_TARGET_NOISE=x ends such a run at the first slice whose estimated noise is at most x (RTAMD_NOISE_MIN_BATCHES slices at least,
 # default 4; RTAMD_NOISE_MAP=path writes the per-pixel standard error as a PFM);
+# RTAMD_GUIDES=prefix writes the first-hit guide images prefix_albedo.pfm, prefix_normal.pfm and prefix_depth.pfm before the frame;
 # RTAMD_DEVICE_LIST=0,1,3 names the HIP devices to use (the environment goes through to build/main as it is).
 if [ $# -eq 2 ]
 then
