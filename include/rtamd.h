@@ -525,6 +525,88 @@ int rt_render_guides(rt_scene *scene, int32_t width, int32_t height, uint32_t fl
                      float *albedo /* W*H*3 */, float *normal /* W*H*3 */, float *depth /* W*H */, float *emission /* W*H*3 */,
                      rt_query_stats *stats /* nullable */);
 
+/* ---- denoised previews: a variance-guided edge-avoiding filter on the guide images -------------------------------------------
+ * What consumes rt_render_guides' planes: a noisy frame of few samples in, a usable preview out.  An a-trous wavelet filter (five
+ * taps per axis, stride doubling per level) whose weights stop at normal, depth and -- with rt_noise_estimate's map -- luminance edges
+ * as wide as the pixel's own noise.  rt_denoise is an image filter: the scene only names the GPU, owns the working set and serialises the
+ * call, so it works on a scene of any kind and on frames of rt_multi_*; no render kernel knows of it and no picture changes because
+ * of it.  ABI version 6 still.
+ *
+ * rt_denoise        planes row-major, row 0 first: rgb, normal W*H*3, depth W*H (rt_render_guides' normal and depth), albedo and
+ *                   emission W*H*3 or NULL, se W*H (rt_noise_estimate's map) or NULL; out_rgb W*H*3 floats and / or out_rgb8 their
+ *                   tonemapped bytes.  Host memory, or with RT_DENOISE_DEVICE_POINTERS memory on the scene's GPU, read and written in
+ *                   place; out_rgb may be rgb.  The work is ordered on the null stream and has finished when the call returns.
+ *                   albedo NULL = no demodulation.  Demodulating by the pixel-centre albedo is opt-in: at preview sizes textures are
+ *                   undersampled and the centre tap is not the albedo of the pixel's footprint.
+ * rt_accum_denoise  the preview of a frame in progress, composed on the device with no trip to the host: the outputs equal, bit for
+ *                   bit, rt_denoise applied to what rt_accum_resolve, rt_render_guides (device path, made by the first call and kept
+ *                   until the rt_accum is destroyed: 40 bytes per pixel) and, if `noise` is given, rt_noise_estimate return.  The
+ *                   emission plane is always passed, the albedo plane only with RT_DENOISE_ALBEDO, no error map when noise is NULL.
+ *                   width and height of the params must be 0 or the accumulator's.  Outputs are host memory, or device memory with
+ *                   RT_DENOISE_DEVICE_POINTERS.  It only reads: the checkpoint and the monitor's figures are the same bytes afterwards.
+ * Refused before any device work, with a message naming the field: a null scene / accum, params, rgb, normal or depth, a wrong
+ * struct_size (params, stats), reserved != 0, unknown flags, iterations outside 0 .. 8, a negative or non-finite sigma, both outputs
+ * null, width or height < 1 (RT_ERR_INVALID_ARG); width * height > 2^26 (RT_ERR_LIMIT).  rt_accum_denoise: a sharded accumulator or
+ * one of an hw6 scene is RT_ERR_UNSUPPORTED (what rt_render_guides refuses); no samples yet, a monitor of another accumulator or
+ * with fewer than 2 batches, and a broken accumulator (its first error in the message) are RT_ERR_INVALID_ARG.
+ *
+ * Arithmetic (float32, one rounding per operation, no transcendental function; tests/denoise_model.py restates it in numpy bit for bit).
+ *   Y(r, g, b) = ((0.2126f*r) + (0.7152f*g)) + (0.0722f*b);  max(a, b) = (a < b) ? b : a (a NaN b gives a)
+ *   e16(x): t = max(0, 1 - x*0.0625f), squared four times: about exp(-x), zero from x = 16 and for a NaN.
+ *   fixed   a pixel with depth not > 0 (a miss), with an emission channel != 0, or with a NaN / inf in its rgb, normal, depth,
+ *           albedo or se.  Its output is its input bit for bit, it is no neighbour of any pixel, and rt_denoise_stats.fixed_pixels
+ *           counts it: directly seen lights and the environment pass through unchanged.
+ *   pack    a = max(1/64, albedo) per channel, 1 without the plane; irr = rgb / a; with se: s = se / Y(a), v = s*s, else v = 0.
+ *           gx = (z(xr, y) - z(xl, y)) / (float)(xr - xl), xr = min(x+1, W-1), xl = max(x-1, 0), 0 when xr == xl; gy likewise
+ *           (z the depth plane as given).
+ *   level i = 0 .. iterations-1, step = 1 << i, for every pixel p that is not fixed:
+ *           with se: pv = the 3x3 Gaussian of v around p (weights 1/2, 1/4 per axis, dy outer, dx inner) over the neighbours in the
+ *           image that are not fixed, divided by the sum of the weights used; sd = sqrt(max(0, pv)).
+ *           The 25 taps q = p + step*(dx, dy), dy outer, dx inner, both -2 .. 2; taps outside the image and fixed taps are skipped:
+ *             h  = k[|dy|] * k[|dx|], k = (3/8, 1/4, 1/16)
+ *             wn = max(0, (n_p.x*n_q.x + n_p.y*n_q.y) + n_p.z*n_q.z), squared six times
+ *             xz = |z_p - z_q| / (((sigma_depth * |gx_p*(float)(dx*step) + gy_p*(float)(dy*step)|) + 1e-3f*z_p) + 1e-12f)
+ *             xl = |Y(irr_p) - Y(irr_q)| / ((sigma_luminance * sd) + 1e-6f), with se only
+ *             w  = (h * e16(xz + xl)) * wn        (without se: e16(xz))
+ *             acc += w*irr_q;  accw += w;  accv += (w*w)*v_q
+ *           irr' = acc / accw, v' = accv / (accw*accw); a pixel whose accw is not > 0 keeps irr and v.  Levels ping-pong between
+ *           two buffers; one lane sums a pixel in that order, so the bits depend on nothing but the planes.
+ *   end     out = irr * a (a fixed pixel: its rgb as given); the bytes are rt_render's tonemap chain of those floats.
+ * Working set: 56 bytes per pixel (116 MB at 1920x1080) plus the staging of host planes, a buffer of the scene grown on demand and
+ * freed with it, not part of rt_scene_info.device_bytes.  One launch packs the planes, one per level follows.
+ *
+ * Measured on one MI355X (profiles/r22_denoise.txt): rt_denoise on a 1920x1080 frame with device planes, five
+ * levels, takes 0.88 ms of kernels with the error map and 0.71 ms without (0.08 - 0.14 ms per level), 0.91 / 0.74 ms for the call with its
+ * launches and its synchronisation, next to 72 ms of render kernels per slice of 16 samples.  On the sphere scene at 64x48 the filtered
+ * frame of 16 samples has a third of the noisy frame's luminance RMSE against the 1,024-sample frame (0.041 against 0.129, on the CPU).
+ *
+ * What the filter does not do: no temporal reuse (every call stands alone), no supersampled albedo, and nothing to fixed pixels. */
+typedef struct rt_denoise_params {
+    uint32_t struct_size;      /* = sizeof(rt_denoise_params) */
+    int32_t  width, height;    /* >= 1, width*height <= 2^26 (else RT_ERR_LIMIT); rt_accum_denoise: 0 or the accumulator's */
+    int32_t  iterations;       /* 0 = default 5; 1 .. 8; level i taps at stride 2^i */
+    float    sigma_depth;      /* 0 = default 1 */
+    float    sigma_luminance;  /* 0 = default 4 */
+    uint32_t flags;            /* RT_DENOISE_DEVICE_POINTERS, RT_DENOISE_ALBEDO (rt_accum_denoise only) */
+    uint32_t reserved;         /* must be 0 */
+} rt_denoise_params;
+typedef struct rt_denoise_stats {
+    uint32_t struct_size;      /* in: sizeof(rt_denoise_stats) */
+    uint32_t launches;         /* 1 + iterations */
+    uint64_t fixed_pixels;
+    double   kernel_ms;        /* HIP-event time from the pack kernel to the last level */
+    double   total_ms;         /* host wall time of the call (rt_accum_denoise: resolve, guides and estimate included) */
+} rt_denoise_stats;
+#define RT_DENOISE_DEVICE_POINTERS 1u /* rt_denoise: every plane and output is device memory; rt_accum_denoise: the outputs are */
+#define RT_DENOISE_ALBEDO          2u /* rt_accum_denoise: demodulate by the albedo plane */
+extern int rt_denoise(rt_scene *scene, const rt_denoise_params *params,
+                      const float *rgb /* W*H*3 */, const float *normal /* W*H*3 */, const float *depth /* W*H */,
+                      const float *albedo /* nullable: NULL = no demodulation */, const float *emission /* nullable */,
+                      const float *se /* nullable: W*H, rt_noise_estimate's map */,
+                      float *out_rgb /* nullable */, uint8_t *out_rgb8 /* nullable */, rt_denoise_stats *stats /* nullable */);
+extern int rt_accum_denoise(rt_accum *accum, rt_noise *noise /* nullable */, const rt_denoise_params *params,
+                            float *out_rgb /* nullable */, uint8_t *out_rgb8 /* nullable */, rt_denoise_stats *stats /* nullable */);
+
 /* Scene info the host side needs after preparation. */
 typedef struct rt_scene_info {
     uint32_t n_triangles, n_lights, n_bvh_nodes, n_light_bvh_nodes;

@@ -23,6 +23,7 @@ RT_BUILD_DEVICE_BVH = 1
 RT_QUERY_DEVICE_POINTERS, RT_QUERY_REFERENCE_WALK = 1, 2
 RT_HIT_INSIDE, RT_HIT_EXACT_WALK, RT_HIT_INVALID_RAY = 1, 2, 4
 RT_HIT_MISS = 0xFFFFFFFF
+RT_DENOISE_DEVICE_POINTERS, RT_DENOISE_ALBEDO = 1, 2
 RT_PIPELINE_SINGLE, RT_PIPELINE_ROUNDS, RT_PIPELINE_PERSISTENT = 0, 1, 2
 RT_OK = 0
 RT_ERR_INVALID_ARG, RT_ERR_NO_DEVICE, RT_ERR_HIP, RT_ERR_UNSUPPORTED, RT_ERR_LIMIT = -1, -2, -3, -4, -7
@@ -119,6 +120,16 @@ class rt_query_stats(C.Structure):
                 ("reserved", C.c_uint32)]
 
 
+class rt_denoise_params(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("width", C.c_int32), ("height", C.c_int32), ("iterations", C.c_int32),
+                ("sigma_depth", C.c_float), ("sigma_luminance", C.c_float), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class rt_denoise_stats(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("launches", C.c_uint32), ("fixed_pixels", C.c_uint64), ("kernel_ms", C.c_double),
+                ("total_ms", C.c_double)]
+
+
 # rt_ray / rt_hit as numpy records: what Scene.query_* take and return
 RAY_DTYPE = np.dtype([("o", np.float32, 3), ("d", np.float32, 3)])
 HIT_DTYPE = np.dtype([("t", np.float32), ("triangle", np.uint32), ("ng", np.float32, 3), ("texcoord", np.float32, 2), ("ns", np.float32, 3),
@@ -138,6 +149,9 @@ ABI_SYMBOLS = ["rt_abi_version", "rt_last_error", "rt_scene_create", "rt_scene_d
                "rt_noise_batches", "rt_noise_estimate", "rt_noise_destroy", "rt_multi_noise_create", "rt_multi_noise_update",
                "rt_multi_noise_reset", "rt_multi_noise_batches", "rt_multi_noise_estimate", "rt_multi_noise_destroy", "rt_query_closest",
                "rt_query_light_pdf", "rt_query_surface", "rt_query_environment", "rt_camera_rays", "rt_render_guides"]
+# The preview filter's two, which the header declares `extern int`: the list above and the family lists of the tests are closed sets
+# of the header's plain prototypes (tests/test_abi_and_host.py, tests/test_accum_host.py), and rt_accum_denoise is no rt_accum_* of theirs.
+DENOISE_SYMBOLS = ["rt_denoise", "rt_accum_denoise"]
 
 if not os.path.exists(LIB_PATH):
     raise ImportError(f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
@@ -197,6 +211,8 @@ for _name in ("rt_query_closest", "rt_query_light_pdf", "rt_query_surface", "rt_
     getattr(lib, _name).argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.POINTER(rt_query_stats)]
 lib.rt_camera_rays.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p]
 lib.rt_render_guides.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_uint32] + [C.c_void_p] * 4 + [C.POINTER(rt_query_stats)]
+lib.rt_denoise.argtypes = [C.c_void_p, C.POINTER(rt_denoise_params)] + [C.c_void_p] * 8 + [C.POINTER(rt_denoise_stats)]
+lib.rt_accum_denoise.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(rt_denoise_params), C.c_void_p, C.c_void_p, C.POINTER(rt_denoise_stats)]
 
 
 def _check(code):
@@ -365,6 +381,21 @@ def make_params(width, height, samples, integrator=RT_INTEGRATOR_HW8, ray_depth=
     p.stream = stream
     p.sample_streams = sample_streams  # 0/1 = replay mode (reference pixels); K > 1 = throughput mode, statistical parity only
     return p
+
+
+def make_denoise_params(width, height, iterations=0, sigma_depth=0.0, sigma_luminance=0.0, flags=0):
+    """rt_denoise_params; 0 selects the default of iterations and of either sigma."""
+    p = rt_denoise_params()
+    p.struct_size = C.sizeof(rt_denoise_params)
+    p.width, p.height, p.iterations = width, height, iterations
+    p.sigma_depth, p.sigma_luminance, p.flags = sigma_depth, sigma_luminance, flags
+    return p
+
+
+def _denoise_stats():
+    st = rt_denoise_stats()
+    st.struct_size = C.sizeof(rt_denoise_stats)
+    return st
 
 
 def unshard(params, buf):
@@ -571,6 +602,20 @@ class Accumulator(_AccumulatorBase):
     def save(self):
         return self._save(self.params)
 
+    def denoise(self, monitor=None, albedo=False, want_float=True, want_rgb8=True, **kw):
+        """The filtered preview of the picture so far (rt_accum_denoise): (rgb float32 (H, W, 3), rgb8, rt_denoise_stats).  monitor: a
+        NoiseMonitor of this accumulator with two batches, whose error map steers the filter; albedo=True demodulates by the albedo
+        plane; keywords as make_denoise_params."""
+        h, w = self.params.height, self.params.width
+        p = make_denoise_params(0, 0, **kw)
+        p.flags |= RT_DENOISE_ALBEDO if albedo else 0
+        rgb = np.zeros((h, w, 3), dtype=np.float32) if want_float else None
+        rgb8 = np.zeros((h, w, 3), dtype=np.uint8) if want_rgb8 else None
+        st = _denoise_stats()
+        _check(lib.rt_accum_denoise(self._h, monitor._h if monitor is not None else None, C.byref(p), rgb.ctypes.data if want_float else None,
+                                    rgb8.ctypes.data if want_rgb8 else None, C.byref(st)))
+        return rgb, rgb8, st
+
 
 class Scene(_Handle):
     """A prepared scene resident in HBM on the current HIP device (rt_scene)."""
@@ -683,6 +728,37 @@ class Scene(_Handle):
         st.struct_size = C.sizeof(rt_query_stats)
         _check(lib.rt_render_guides(self._h, width, height, 0, *ptr, C.byref(st)))
         return planes, st
+
+    def denoise(self, rgb, normal, depth, albedo=None, emission=None, se=None, want_float=True, want_rgb8=True, **kw):
+        """The preview filter on host planes (rt_denoise): rgb, normal (H, W, 3), depth (H, W), optionally albedo, emission (H, W, 3) and
+        se (H, W), float32; keywords as make_denoise_params.  Returns (rgb float32 (H, W, 3), rgb8, rt_denoise_stats)."""
+        depth = np.ascontiguousarray(depth, dtype=np.float32)
+        if depth.ndim != 2:
+            raise ValueError(f"depth must be (H, W), got {depth.shape}")
+        h, w = depth.shape
+        planes = []
+        for name, a, shape in (("rgb", rgb, (h, w, 3)), ("normal", normal, (h, w, 3)), ("depth", depth, (h, w)), ("albedo", albedo, (h, w, 3)),
+                               ("emission", emission, (h, w, 3)), ("se", se, (h, w))):
+            a = None if a is None else np.ascontiguousarray(a, dtype=np.float32)
+            if a is not None and a.shape != shape:
+                raise ValueError(f"{name} must be {shape}, got {a.shape}")
+            planes.append(a)
+        out = np.zeros((h, w, 3), dtype=np.float32) if want_float else None
+        out8 = np.zeros((h, w, 3), dtype=np.uint8) if want_rgb8 else None
+        p = make_denoise_params(w, h, **kw)
+        st = _denoise_stats()
+        _check(lib.rt_denoise(self._h, C.byref(p), *[None if a is None else a.ctypes.data for a in planes],
+                              out.ctypes.data if want_float else None, out8.ctypes.data if want_rgb8 else None, C.byref(st)))
+        return out, out8, st
+
+    def denoise_device(self, width, height, rgb_ptr, normal_ptr, depth_ptr, albedo_ptr=None, emission_ptr=None, se_ptr=None,
+                       out_rgb_ptr=None, out_rgb8_ptr=None, **kw):
+        """The same on device memory of the scene's GPU (raw pointers, e.g. torch tensor data_ptr()); out_rgb_ptr may be rgb_ptr."""
+        p = make_denoise_params(width, height, **kw)
+        p.flags |= RT_DENOISE_DEVICE_POINTERS
+        st = _denoise_stats()
+        _check(lib.rt_denoise(self._h, C.byref(p), rgb_ptr, normal_ptr, depth_ptr, albedo_ptr, emission_ptr, se_ptr, out_rgb_ptr, out_rgb8_ptr, C.byref(st)))
+        return st
 
     def query_surface_device(self, hits_ptr, n, out_ptr):
         """The same on device memory of the scene's GPU: n rt_hit in, n rt_surface out, both 16-byte aligned."""

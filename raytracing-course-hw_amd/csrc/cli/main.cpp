@@ -18,6 +18,10 @@
 // RTAMD_NOISE_MAP=path writes the last per-pixel standard error as a grayscale PFM ("Pf", little-endian, bottom row first as PFM has it).
 // First-hit guide images for a denoiser (rt_render_guides, glTF surface, hw8 / hw7): RTAMD_GUIDES=prefix writes prefix_albedo.pfm and
 // prefix_normal.pfm ("PF") and prefix_depth.pfm ("Pf") at the frame's size before the frame is rendered; out.ppm is the run's without it.
+// Denoised previews (rt_accum_denoise, glTF surface, hw8 / hw7): RTAMD_DENOISE=path.ppm writes the filtered picture next to out.ppm, in a
+// sliced run after every slice, steered by the noise monitor's error map whenever a monitor runs (RTAMD_TARGET_NOISE, RTAMD_NOISE_MAP) and
+// has two batches; RTAMD_DENOISE_ALBEDO=1 demodulates by the albedo plane.  out.ppm is the run's without it.  With several devices the
+// frame and the map come to the host (rt_multi_accum_resolve, rt_multi_noise_estimate) and rt_denoise filters them on a scene of its own.
 #include "../../../include/rtamd.h"
 #include <cmath>
 #include <cstdio>
@@ -95,10 +99,47 @@ static int write_guides(rt_scene *scene, const rt_render_params &p, const std::s
     return 0;
 }
 
+// RTAMD_DENOISE=path: the filtered preview of the picture so far.  On one device rt_accum_denoise composes it on the GPU; on several the
+// frame and the error map come to the host and rt_denoise filters them on `scene`, a scene of the preview's own on the current device,
+// with the frame's guide planes made there once.
+struct Preview {
+    const char *path = nullptr;  // RTAMD_DENOISE
+    bool albedo = false;         // RTAMD_DENOISE_ALBEDO=1
+    rt_scene *scene = nullptr;   // several devices only
+    std::vector<float> guides;   // several devices only: albedo, normal, depth, emission
+};
+static int write_preview(Preview &pv, Progress &acc, Monitor &mon, bool monitored, const rt_render_params &p, std::vector<uint8_t> &rgb8) {
+    rt_denoise_params dp;
+    memset(&dp, 0, sizeof dp);
+    dp.struct_size = sizeof dp;
+    const bool with_map = monitored && mon.batches() >= 2;
+    const size_t px = (size_t)p.width * p.height;
+    if (acc.one) {
+        dp.flags = pv.albedo ? RT_DENOISE_ALBEDO : 0u;
+        if (rt_accum_denoise(acc.one, with_map ? mon.one : nullptr, &dp, nullptr, rgb8.data(), nullptr) != RT_OK) return die();
+    } else {
+        if (pv.guides.empty()) {
+            pv.guides.resize(px * 10);
+            float *g = pv.guides.data();
+            if (rt_render_guides(pv.scene, p.width, p.height, 0, g, g + 3 * px, g + 6 * px, g + 7 * px, nullptr) != RT_OK) return die();
+        }
+        std::vector<float> rgb(px * 3), se(with_map ? px : 0);
+        if (rt_multi_accum_resolve(acc.all, 0, rgb.data(), nullptr) != RT_OK) return die();
+        if (with_map && rt_multi_noise_estimate(mon.all, 0, se.data(), nullptr) != RT_OK) return die();
+        const float *g = pv.guides.data();
+        dp.width = p.width; dp.height = p.height;
+        if (rt_denoise(pv.scene, &dp, rgb.data(), g + 3 * px, g + 6 * px, pv.albedo ? g : nullptr, g + 7 * px, with_map ? se.data() : nullptr, nullptr, rgb8.data(), nullptr) != RT_OK) return die();
+    }
+    const std::string tmp = std::string(pv.path) + ".part";
+    if (rt_write_ppm(tmp.c_str(), p.width, p.height, rgb8.data()) != RT_OK) return die();
+    if (rename(tmp.c_str(), pv.path) != 0) { fprintf(stderr, "error: cannot rename %s to %s\n", tmp.c_str(), pv.path); return 1; }
+    return 0;
+}
+
 // The frame in slices: the picture after every slice is the frame of that many samples, the last one the frame of the plain run.
 // `p` are the params of the unsharded frame, whose rt_accum_state_bytes is the size of the checkpoint on any number of devices.
 // With a noise target the run ends at the first slice whose picture is quiet enough: that picture is the plain run's at that many samples.
-static int render_in_slices(Progress &acc, const rt_render_params &p, int slice, const char *checkpoint, const char *out_path, std::vector<uint8_t> &rgb8, const NoiseTarget &noise) {
+static int render_in_slices(Progress &acc, const rt_render_params &p, int slice, const char *checkpoint, const char *out_path, std::vector<uint8_t> &rgb8, const NoiseTarget &noise, Preview &preview) {
     std::vector<uint8_t> blob(checkpoint ? rt_accum_state_bytes(&p) : 0);
     if (checkpoint) {
         if (FILE *f = fopen(checkpoint, "rb")) {
@@ -138,6 +179,7 @@ static int render_in_slices(Progress &acc, const rt_render_params &p, int slice,
             if (acc.resolve(rgb8.data()) != RT_OK) return die();
             if (rt_write_ppm(tmp_ppm.c_str(), p.width, p.height, rgb8.data()) != RT_OK) return die();
             if (rename(tmp_ppm.c_str(), out_path) != 0) { fprintf(stderr, "error: cannot rename %s to %s\n", tmp_ppm.c_str(), out_path); return 1; }
+            if (preview.path) if (const int rc = write_preview(preview, acc, mon, noise.active(), p, rgb8)) return rc;
         }
         if (converged) fprintf(stderr, "CONVERGED after %d slices at %d of %d samples\n", k, done, p.samples);
         if (done == p.samples || converged) break;
@@ -227,7 +269,13 @@ int main(int argc, const char *argv[]) {
         if (const char *e = getenv("RTAMD_NOISE_MIN_BATCHES")) { noise.min_batches = atoi(e); if (noise.min_batches < 2) noise.min_batches = 2; }
         noise.map = getenv("RTAMD_NOISE_MAP");
     }
-    const bool sliced = argc >= 6 && (getenv("RTAMD_SLICE") || checkpoint || noise.active());
+    Preview preview;
+    if (const char *e = getenv("RTAMD_DENOISE")) {
+        if (argc < 6 || p.integrator == RT_INTEGRATOR_HW6) fprintf(stderr, "note: RTAMD_DENOISE serves the glTF surface with hw8 / hw7 (guide images are made for those scenes): no preview is written\n");
+        else if (p.sample_streams > 1) fprintf(stderr, "note: RTAMD_DENOISE previews a resumable render, which throughput mode (RTAMD_STREAMS) is not: no preview is written\n");
+        else { preview.path = e; preview.albedo = getenv("RTAMD_DENOISE_ALBEDO") && atoi(getenv("RTAMD_DENOISE_ALBEDO")) != 0; }
+    }
+    const bool sliced = argc >= 6 && (getenv("RTAMD_SLICE") || checkpoint || noise.active() || preview.path);
     if (sliced && slice <= 0 && getenv("RTAMD_SLICE")) { fprintf(stderr, "error: RTAMD_SLICE must be a positive number of samples\n"); return 1; }
     if (noise.active() && !getenv("RTAMD_SLICE")) slice = p.samples / 16 > 1 ? p.samples / 16 : 1; // watching the noise implies slices
     std::vector<int> list; // RTAMD_DEVICE_LIST: the devices of rt_multi_create, as given
@@ -261,8 +309,10 @@ int main(int argc, const char *argv[]) {
     if (sliced) {
         Progress acc;
         if ((multi ? rt_multi_accum_create(multi, &p, &acc.all) : rt_accum_create(scene, &p, &acc.one)) != RT_OK) return die();
-        const int rc = render_in_slices(acc, p, slice, checkpoint, out_path, rgb8, noise);
+        if (preview.path && multi && rt_scene_create(&desc, &preview.scene) != RT_OK) return die();
+        const int rc = render_in_slices(acc, p, slice, checkpoint, out_path, rgb8, noise, preview);
         acc.destroy(); // before its rt_multi or its scene
+        rt_scene_destroy(preview.scene);
         rt_multi_destroy(multi);
         rt_scene_destroy(scene);
         rt_host_scene_free(hs);

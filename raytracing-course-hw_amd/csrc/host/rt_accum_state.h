@@ -1,7 +1,8 @@
 // struct rt_accum, struct rt_multi_accum and the header of the checkpoint, shared by the translation units that keep or read resumable
 // state: rtamd_api.hip (rt_accum_*: one frame or one shard on one device), rtamd_multi.hip (rt_multi_accum_*: one sharded rt_accum
 // per device and the checkpoint of the whole frame, which is the unsharded rt_accum's blob byte for byte) and rtamd_noise.hip
-// (rt_noise_* / rt_multi_noise_*: the noise monitors, which only read the state between slices).
+// (rt_noise_* / rt_multi_noise_*: the noise monitors, which only read the state between slices) and rtamd_denoise.hip (rt_accum_denoise:
+// the preview filter, which only reads it too and keeps the frame's guide planes here).
 #pragma once
 #include <cstring>
 #include <string>
@@ -28,7 +29,8 @@ struct rt_accum {
     int32_t sample_limit = 0;       // the path records' sample index field (choose_pipeline)
     std::string broken;             // first error of a slice that failed under way: the state is half advanced
     uint64_t loads = 0;             // how often rt_accum_load has replaced the state (a noise monitor's batches end there)
-    ~rt_accum() { if (d_state) (void)hipFree(d_state); }
+    float *d_guides = nullptr;      // rt_accum_denoise: albedo, normal, depth, emission of the frame (10 floats per pixel), made by its first call
+    ~rt_accum() { if (d_state) (void)hipFree(d_state); if (d_guides) (void)hipFree(d_guides); }
 };
 
 // One sharded rt_accum per device entry of an rt_multi (shard i of N on that entry's stream; none for an entry that gets no tile).
@@ -94,4 +96,6 @@ namespace rtamd {
 // What rt_accum_render refuses before it launches anything (a broken state, n_samples, the sample-index limit, a pipeline without
 // resumable state); RT_OK = the slice would be launched.  Host only; `who` prefixes the message.
 int accum_check_slice(const rt_accum *a, int32_t n_samples, const std::string &who);
+// What rt_noise_estimate would refuse of monitor `n`, and that it watches `a` (rtamd_noise.hip); RT_OK = an estimate can be taken.  Host only.
+int noise_estimate_ready(const rt_noise *n, const rt_accum *a, const std::string &who);
 } // namespace rtamd

@@ -167,6 +167,11 @@ size_t noise_frame_subtiles(const RenderView &R) { return (size_t)(((uint32_t)R.
 
 } // namespace
 
+int rtamd::noise_estimate_ready(const rt_noise *n, const rt_accum *a, const std::string &who) {
+    if (n->accum != a) return fail(RT_ERR_INVALID_ARG, who + "the monitor watches another accumulator");
+    return noise_estimate_check(n, who);
+}
+
 extern "C" {
 
 int rt_noise_create(rt_accum *a, rt_noise **out) {
