@@ -1,5 +1,6 @@
 // Test-only entry points (NOT part of include/rtamd.h, built into librtamd_testhooks.so): run individual
-// device functions of rt_device.h on the GPU so tests can compare them with the host libm / libstdc++.
+// device functions of rt_device.h on the GPU so tests can compare them with the host libm / libstdc++, and the on-device tree builder
+// on boxes of the test's own so its tree can be read back.
 #include <hip/hip_runtime.h>
 #include "device/rt_device.h"
 #include "device/rt_exact.h"
@@ -7,7 +8,9 @@
 #include "device/rt_node_grid.h"
 #include "device/rt_pt_queue.h"
 #include "device/rt_ref_walk.h"
+#include "host/device_build.h"
 #include "host/fold_nodes.h"
+#include "host/hip_check.h"
 #include "host/rt_guard.h"
 #include "host/scene_prep.h"
 #include <cstdio>
@@ -384,6 +387,60 @@ int rtt_frame_sum(const uint32_t *nodes, uint32_t n_nodes, const uint32_t *roots
         rc = (hipDeviceSynchronize() == hipSuccess && hipMemcpy(out, d_out, (size_t)n_roots * 4, hipMemcpyDeviceToHost) == hipSuccess) ? 0 : -3;
     }
     (void)hipFree(d_nodes); (void)hipFree(d_roots); (void)hipFree(d_out);
+    return rc;
+}
+// The on-device tree builder (host/device_build.h build_tree_on_device, the function rtamd_scene.hip calls) on n host boxes of 8 floats
+// (lo.xyz, -, hi.xyz, -): nodes_out = room for node_cap two-box nodes of 64 bytes, order_out = n words, last_out = n bytes, depth_out = the
+// deepest leaf.  Returns the number of nodes; -1 when the builder refuses or a HIP call fails, -2 for any other exception, -3 when the
+// tree has more than node_cap nodes (nothing is written then).
+int rtt_build_tree(const float *boxes8, uint32_t n, float abs_pad, uint32_t max_depth, void *nodes_out, uint32_t node_cap, uint32_t *order_out,
+                   uint8_t *last_out, uint32_t *depth_out) {
+    float *d_boxes = nullptr;
+    rtamd::DeviceTree t;
+    int rc;
+    try {
+        if (n) {
+            HIP_CHECK(hipMalloc((void **)&d_boxes, (size_t)n * 32));
+            HIP_CHECK(hipMemcpy(d_boxes, boxes8, (size_t)n * 32, hipMemcpyHostToDevice));
+        }
+        t = rtamd::build_tree_on_device(d_boxes, n, abs_pad, max_depth);
+        if (t.n_nodes > node_cap) rc = -3;
+        else {
+            HIP_CHECK(hipMemcpy(nodes_out, t.nodes, (size_t)t.n_nodes * sizeof(rtamd::GpuNode), hipMemcpyDeviceToHost));
+            HIP_CHECK(hipMemcpy(order_out, t.order, (size_t)n * 4, hipMemcpyDeviceToHost));
+            HIP_CHECK(hipMemcpy(last_out, t.last, (size_t)n, hipMemcpyDeviceToHost));
+            *depth_out = t.depth;
+            rc = (int)t.n_nodes;
+        }
+    } catch (const std::exception &) { rc = -1; } catch (...) { rc = -2; }
+    rtamd::free_device_tree(t);
+    (void)hipFree(d_boxes);
+    return rc;
+}
+// gather_records (host/device_build.h) on n host records of elem_bytes with a leaf order and leaf marks of the test's own: out = n records.
+// mark_word: the index of the records' mark word, -1 for none.  Returns 0; -1 when gather_records refuses (a size that is no multiple of
+// 16) or a HIP call fails, -2 for any other exception, -4 for an order entry or a mark word outside the records (not run).
+int rtt_gather_records(const void *records, uint32_t n, uint32_t elem_bytes, const uint32_t *order, const uint8_t *last, int mark_word, int or_into_word, void *out) {
+    if (n == 0 || elem_bytes == 0 || mark_word < -1 || (mark_word >= 0 && (uint32_t)mark_word >= elem_bytes / 4)) return -4;
+    for (uint32_t i = 0; i < n; i++) if (order[i] >= n) return -4;
+    void *d_in = nullptr, *d_out = nullptr;
+    rtamd::DeviceTree t;
+    int rc;
+    try {
+        const size_t bytes = (size_t)n * elem_bytes;
+        HIP_CHECK(hipMalloc(&d_in, bytes)); HIP_CHECK(hipMalloc(&d_out, bytes));
+        HIP_CHECK(hipMalloc((void **)&t.order, (size_t)n * 4)); HIP_CHECK(hipMalloc((void **)&t.last, n));
+        HIP_CHECK(hipMemcpy(d_in, records, bytes, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemset(d_out, 0, bytes));
+        HIP_CHECK(hipMemcpy(t.order, order, (size_t)n * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(t.last, last, n, hipMemcpyHostToDevice));
+        rtamd::gather_records(d_in, d_out, t, n, elem_bytes, mark_word, or_into_word != 0);
+        HIP_CHECK(hipDeviceSynchronize());
+        HIP_CHECK(hipMemcpy(out, d_out, bytes, hipMemcpyDeviceToHost));
+        rc = 0;
+    } catch (const std::exception &) { rc = -1; } catch (...) { rc = -2; }
+    rtamd::free_device_tree(t);
+    (void)hipFree(d_in); (void)hipFree(d_out);
     return rc;
 }
 // The guard of the C boundary (host/rt_guard.h) around a body that throws a HipError (kind 0), a std::bad_alloc (1), a std::runtime_error (2)
