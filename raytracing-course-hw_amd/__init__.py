@@ -23,6 +23,7 @@ RT_BUILD_DEVICE_BVH = 1
 RT_QUERY_DEVICE_POINTERS, RT_QUERY_REFERENCE_WALK = 1, 2
 RT_HIT_INSIDE, RT_HIT_EXACT_WALK, RT_HIT_INVALID_RAY = 1, 2, 4
 RT_HIT_MISS = 0xFFFFFFFF
+RT_OCCLUSION_OCCLUDED, RT_OCCLUSION_EXACT_WALK, RT_OCCLUSION_INVALID_RAY = 1, 2, 4
 RT_DENOISE_DEVICE_POINTERS, RT_DENOISE_ALBEDO = 1, 2
 RT_PIPELINE_SINGLE, RT_PIPELINE_ROUNDS, RT_PIPELINE_PERSISTENT = 0, 1, 2
 RT_OK = 0
@@ -148,7 +149,8 @@ ABI_SYMBOLS = ["rt_abi_version", "rt_last_error", "rt_scene_create", "rt_scene_d
                "rt_multi_accum_load", "rt_multi_accum_destroy", "rt_noise_create", "rt_noise_update", "rt_noise_reset",
                "rt_noise_batches", "rt_noise_estimate", "rt_noise_destroy", "rt_multi_noise_create", "rt_multi_noise_update",
                "rt_multi_noise_reset", "rt_multi_noise_batches", "rt_multi_noise_estimate", "rt_multi_noise_destroy", "rt_query_closest",
-               "rt_query_light_pdf", "rt_query_surface", "rt_query_environment", "rt_camera_rays", "rt_render_guides"]
+               "rt_query_light_pdf", "rt_query_surface", "rt_query_environment", "rt_camera_rays", "rt_render_guides",
+               "rt_query_occluded"]
 # The preview filter's two, which the header declares `extern int`: the list above and the family lists of the tests are closed sets
 # of the header's plain prototypes (tests/test_abi_and_host.py, tests/test_accum_host.py), and rt_accum_denoise is no rt_accum_* of theirs.
 DENOISE_SYMBOLS = ["rt_denoise", "rt_accum_denoise"]
@@ -209,6 +211,7 @@ for _family in ("rt_noise", "rt_multi_noise"):
     getattr(lib, _family + "_destroy").restype = None
 for _name in ("rt_query_closest", "rt_query_light_pdf", "rt_query_surface", "rt_query_environment"):
     getattr(lib, _name).argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.POINTER(rt_query_stats)]
+lib.rt_query_occluded.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.POINTER(rt_query_stats)]
 lib.rt_camera_rays.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p]
 lib.rt_render_guides.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_uint32] + [C.c_void_p] * 4 + [C.POINTER(rt_query_stats)]
 lib.rt_denoise.argtypes = [C.c_void_p, C.POINTER(rt_denoise_params)] + [C.c_void_p] * 8 + [C.POINTER(rt_denoise_stats)]
@@ -687,6 +690,30 @@ class Scene(_Handle):
         rays = pack_rays(x, d)
         pdf = np.zeros(rays.shape[0], dtype=np.float32)
         return pdf, self._query(lib.rt_query_light_pdf, rays.ctypes.data, rays.shape[0], flags, pdf.ctypes.data)
+
+    def query_occluded(self, o, d, tmax=None, flags=0):
+        """Is anything in front of tmax[i] on the ray (o[i], d[i]) (rt_query_occluded; tmax None: does the ray hit anything):
+        (uint8 array of RT_OCCLUSION_* bits, rt_query_stats)."""
+        if flags & RT_QUERY_DEVICE_POINTERS:
+            raise ValueError("query_occluded takes host arrays; device memory goes through query_occluded_device")
+        rays = pack_rays(o, d)
+        n = rays.shape[0]
+        if tmax is not None:
+            tmax = np.ascontiguousarray(tmax, dtype=np.float32)
+            if tmax.shape != (n,):
+                raise ValueError(f"tmax must have shape ({n},), one bound per ray; got {tmax.shape}")
+        out = np.zeros(n, dtype=np.uint8)
+        st = rt_query_stats()
+        st.struct_size = C.sizeof(rt_query_stats)
+        _check(lib.rt_query_occluded(self._h, rays.ctypes.data, None if tmax is None else tmax.ctypes.data, n, flags, out.ctypes.data, C.byref(st)))
+        return out, st
+
+    def query_occluded_device(self, rays_ptr, tmax_ptr, n, out_ptr, flags=0):
+        """The same on device memory: n rt_ray and n floats (or None) in, n bytes out, no alignment demand on out."""
+        st = rt_query_stats()
+        st.struct_size = C.sizeof(rt_query_stats)
+        _check(lib.rt_query_occluded(self._h, rays_ptr, tmax_ptr, n, flags | RT_QUERY_DEVICE_POINTERS, out_ptr, C.byref(st)))
+        return st
 
     def query_closest_device(self, rays_ptr, n, out_ptr, flags=0):
         """The same on device memory of the scene's GPU (raw pointers, e.g. torch tensor data_ptr()): n rt_ray in, n rt_hit out."""

@@ -11,6 +11,8 @@
 //   rq_closest_exact_kernel  ref_closest_hit, one lane per ray of the exact list (RT_HIT_EXACT_WALK), as wf_trace_exact_kernel does
 //   rq_light_kernel          wf_walk_loop with RqLightWalk (WfLightWalk's walk and merge); what it cannot finish goes on the exact list
 //   rq_light_exact_kernel    the reference-order frame walk, as wf_light_exact_kernel does
+// and for rt_query_occluded (the last section of this file): rq_classify_occluded_kernel, rq_any_kernel (wf_walk_loop with RqAnyWalk, a
+// walk that ends at the first hit below the ray's bound), rq_any_resolve_kernel (the any-hit gate), rq_any_exact_kernel.
 //
 // What the gate covers, and the rule of the fast list.  The gate's margins (rt_exact.h) bound the rounding of the reference's slab test by
 // 2^-23 |t| + 2^-24 |o - centre|_j / |d_j| per term, with c2 = 2^-20 max|coordinate| of scene and camera standing for |o - centre|: the ray
@@ -326,6 +328,200 @@ __global__ __launch_bounds__(64) void rq_light_exact_kernel(SceneView S, QueryVi
         Counters cnt; cnt.closest = cnt.lightq = cnt.nodes = cnt.tris = 0;
         const float v = S.exact_boxes == 1u ? ref_light_pdf_sum(S, x, d, stack) : light_pdf_sum<false>(S, x, d, stack, cnt);
         Q.pdf[ray] = rq_x86_nan(v / S.n_lights_f);
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(Q.totals + RQ_TOTAL_EXACT, (unsigned long long)count);
+}
+
+// ---- occlusion: is anything in front of tmax? (rt_query_occluded) --------------------------------------------------------------------------
+// Bit 0 of a ray's byte: the reference's BVH::intersect reports a hit with t < tmax (strict, float32).  The walk ends at the first
+// triangle below the bound instead of looking for the closest, and the gate asks a smaller question than pt_hit_stands:
+//   a miss stands     the walkers see a superset of what the reference's box test lets through (padded boxes, pruned only beyond the
+//                     bound plus WfClosest's look-behind, so a reference hit in a face of a flat box stays in view); the triangles whose
+//                     test accepts points far outside their box are the tripwires', and a ray that crosses one is walked exactly;
+//   a hit X stands    when (a) every box above it passes the reference's slab test whatever the rounding (the `worst` and `exit_` terms
+//                     of pt_hit_stands), so the reference reaches X unless it pruned X's leaf behind an earlier hit Y, and (b) such a
+//                     Y is itself below the bound: the reference prunes only when t_Y < the rounded entry of X's box <= t_X + window
+//                     (window = need - min a, rt_exact.h), so tmax - t_X > window puts t_Y < tmax.  Either way the reference ends
+//                     with a hit below tmax.  A deep-inside hit has window <= 0 and stands at once.
+// The runner-up, the tie tolerance and the `window <= seen` term belong to "which triangle is closest" and play no part.
+// Every other ray goes on the exact list: the full closest walk of rq_closest_exact_kernel, compared with tmax (RQ_OCC_EXACT_WALK).
+// A ray's tmax: Q.tmax[i], or +inf without the array.  NaN: the ray is invalid.  tmax <= 0: valid, not occluded, never walked.
+#define RQ_OCC_OCCLUDED 1u
+#define RQ_OCC_EXACT_WALK 2u
+#define RQ_OCC_INVALID_RAY 4u
+
+RT_DEV float rq_load_tmax(const QueryView &Q, uint32_t i) { return Q.tmax ? Q.tmax[i] : __uint_as_float(0x7f800000u); }
+
+__global__ __launch_bounds__(256) void rq_classify_occluded_kernel(SceneView S, QueryView Q) {
+    __shared__ uint32_t buf_f[WF_BUF], buf_e[WF_BUF];
+    __shared__ uint32_t cnt_f, cnt_e, gbase;
+    if (threadIdx.x == 0) { cnt_f = 0; cnt_e = 0; }
+    __syncthreads();
+    Pusher fast; fast.buf = buf_f; fast.cnt = &cnt_f;
+    Pusher exact; exact.buf = buf_e; exact.cnt = &cnt_e;
+    for (uint32_t base = blockIdx.x * 256u; base < Q.n; base += gridDim.x * 256u) {
+        const uint32_t i = base + threadIdx.x;
+        if (i < Q.n) {
+            F3 o, d;
+            rq_load_ray(Q, i, o, d);
+            const float tmax = rq_load_tmax(Q, i);
+            const int kind = tmax != tmax ? RQ_INVALID : rq_classify(Q, o, d);
+            if (kind == RQ_INVALID) {
+                Q.occ[i] = (uint8_t)RQ_OCC_INVALID_RAY;
+                atomicAdd(Q.totals + RQ_TOTAL_INVALID, 1ull);
+            } else if (!(tmax > 0.f) || S.n_tris == 0u) Q.occ[i] = 0;
+            else if (kind == RQ_FAST) wf_push(fast, i);
+            else wf_push(exact, i);
+        }
+        __syncthreads();
+        if (cnt_f > WF_BUF - 256) wf_flush(fast, Q.q_fast, Q.ctr + RQ_CTR_FAST, &gbase);
+        if (cnt_e > WF_BUF - 256) wf_flush(exact, Q.q_exact, Q.ctr + RQ_CTR_EXACT, &gbase);
+    }
+    __syncthreads();
+    wf_flush(fast, Q.q_fast, Q.ctr + RQ_CTR_FAST, &gbase);
+    wf_flush(exact, Q.q_exact, Q.ctr + RQ_CTR_EXACT, &gbase);
+}
+
+// RqTraceWalk's node step and stack; no best hit is kept, so the pruning bound is fixed for the walk: lim = min(tmax, RT_T_MAX) plus the
+// look-behind WfClosest gives a best hit at lim.  The record per ray is 8 bytes of Q.rec: t and the hit word, or a miss.
+template <bool SPILL> struct RqAnyWalk : WfWalkRay {
+    static constexpr int HIST = -1;
+    static constexpr bool WAVE_STATS = false;
+    const SceneView &S; const QueryView &Q; WfStack<SPILL> stk;
+    float tmax = 0.f, lim = 0.f, cull_t = 0.f;
+    RT_DEV RqAnyWalk(const SceneView &S_, const QueryView &Q_, const WfView &W_, uint32_t (*stack)[64], int lds_limit) : S(S_), Q(Q_), stk(W_, stack, lds_limit) {}
+    RT_DEV void begin(uint32_t item) {
+        slot = item;
+        rq_load_ray(Q, item, o, d);
+        ray = make_ray_inv(o, d);
+        cur = 0; sp = 0;
+        tmax = rq_load_tmax(Q, item);
+        lim = fminf(tmax, RT_T_MAX);
+        cull_t = lim + fmaxf(S.cull_k * lim, S.exact_boxes ? pt_look_behind_abs(d, S.box_c2x) : 0.f);
+    }
+    // One 64-bit store.  As two words the compiler sinks the miss record's second word and next()'s `cur = pop` into one store through a
+    // phi of the two addresses, which takes this walker's address: walker and both views then live in scratch (552 B/lane).
+    RT_DEV void leave(float t, uint32_t hit) { reinterpret_cast<unsigned long long *>(Q.rec)[slot] = (unsigned long long)hit << 32 | __float_as_uint(t); }
+    RT_DEV bool next() {
+        if (sp == 0) { leave(0.f, WF_MISS); return true; }
+        cur = stk.pop(sp);
+        return false;
+    }
+    template <bool COUNT> RT_DEV bool step(WfWalkStat<COUNT> &n) {
+        const float4 *q = reinterpret_cast<const float4 *>(S.nodes + cur);
+        float4 lo0 = q[0], hi0 = q[1], lo1 = q[2], hi1 = q[3];
+        n.node();
+        float n0, n1;
+        bool h0 = slab_test(lo0, hi0, ray, cull_t, n0);
+        bool h1 = slab_test(lo1, hi1, ray, cull_t, n1);
+        uint32_t c0 = __float_as_uint(lo0.w), c1 = __float_as_uint(lo1.w);
+        if (h0 & h1) {
+            bool swap = n1 < n0;
+            stk.push(sp, swap ? c0 : c1);
+            cur = swap ? c1 : c0;
+        } else {
+            cur = h0 ? c0 : c1;
+            if (!(h0 | h1)) return next();
+        }
+        return false;
+    }
+    template <bool COUNT> RT_DEV bool leaf(WfWalkStat<COUNT> &n) {
+        if (cur != RT_EMPTY_LEAF) {
+            uint32_t i = cur & ~RT_LEAF_BIT;
+            for (;;) {
+                TriIsect T = load_isect(S.tri_walk + i);
+                n.tri();
+                float t, u, v; bool inside;
+                if (tri_test_closer(T, o, d, lim, t, u, v, inside) && t < tmax) { // the walk ends here, whatever its stack still holds
+                    leave(t, (T.pad >> 1) | (inside ? WF_INSIDE_BIT : 0u));
+                    return true;
+                }
+                if (T.pad & 1u) break;
+                i++;
+            }
+        }
+        return next();
+    }
+};
+
+template <bool SPILL>
+__global__ __launch_bounds__(256) void rq_any_kernel(SceneView S, QueryView Q, int refill, int leaf_batch, int dyn, int lds_limit) {
+    __shared__ uint32_t lds_stack[4][WF_STACK][64];
+    WfView W{};
+    W.ovf = Q.ovf;
+    RqAnyWalk<SPILL> w(S, Q, W, lds_stack[threadIdx.x >> 6], lds_limit);
+    wf_walk_loop<false>(w, Q.q_fast, wf_slice(Q.ctr[RQ_CTR_FAST], Q.ctr + RQ_CTR_HEAD, dyn, 0u, gridDim.x, true), nullptr, refill, leaf_batch);
+}
+
+// Does the any-hit walk's hit at t on the triangle whose box is [lo, hi] stand as "the reference reports a hit below tmax"?  The
+// arithmetic of pt_hit_stands with the any-hit conditions (a) and (b) above.  NaN compares false: exact walk.
+RT_DEV bool rq_any_hit_stands(F3 lo, F3 hi, F3 o, F3 d, float t, float tmax, float c2) {
+    const F3 P = o + t * d;
+    if (pt_deep_inside(lo, hi, P, d, t, c2)) return true;
+    const float ix = pt_rcp(fmaxf(fabsf(d.x), 1e-30f)), iy = pt_rcp(fmaxf(fabsf(d.y), 1e-30f)), iz = pt_rcp(fmaxf(fabsf(d.z), 1e-30f));
+    const float inx = d.x > 0 ? P.x - lo.x : hi.x - P.x, outx = d.x > 0 ? hi.x - P.x : P.x - lo.x;
+    const float iny = d.y > 0 ? P.y - lo.y : hi.y - P.y, outy = d.y > 0 ? hi.y - P.y : P.y - lo.y;
+    const float inz = d.z > 0 ? P.z - lo.z : hi.z - P.z, outz = d.z > 0 ? hi.z - P.z : P.z - lo.z;
+    const float ax = (inx - c2) * ix, ay = (iny - c2) * iy, az = (inz - c2) * iz;
+    const float bx = (outx - c2) * ix, by = (outy - c2) * iy, bz = (outz - c2) * iz;
+    const float need = 1.9073486328125e-06f * t;
+    const float worst = fminf(fminf(fminf(ax + by, ax + bz), fminf(ay + bx, ay + bz)), fminf(az + bx, az + by));
+    const float exit_ = t + fminf(fminf(bx, by), bz);
+    const float window = need - fminf(fminf(ax, ay), az);
+    return worst >= need && exit_ >= need && tmax - t > window;
+}
+
+__global__ __launch_bounds__(256) void rq_any_resolve_kernel(SceneView S, QueryView Q) {
+    __shared__ uint32_t buf[WF_BUF];
+    __shared__ uint32_t cnt, gbase;
+    if (threadIdx.x == 0) cnt = 0;
+    __syncthreads();
+    Pusher exact; exact.buf = buf; exact.cnt = &cnt;
+    const uint32_t count = Q.ctr[RQ_CTR_FAST];
+    for (uint32_t base = blockIdx.x * 256u; base < count; base += gridDim.x * 256u) {
+        const uint32_t i = base + threadIdx.x;
+        if (i < count) {
+            const uint32_t ray = Q.q_fast[i];
+            const float2 r = reinterpret_cast<const float2 *>(Q.rec)[ray];
+            const uint32_t hit = __float_as_uint(r.y);
+            bool stands = true;
+            if (S.exact_boxes) {
+                F3 o, d;
+                rq_load_ray(Q, ray, o, d);
+                if (S.n_tripwire_groups && pt_tripwire(S, o, d)) stands = false;
+                else if (hit != WF_MISS) {
+                    const float4 *bx = reinterpret_cast<const float4 *>(S.tri_box) + 2 * (size_t)(hit & WF_INDEX_MASK);
+                    const float4 lo = bx[0], hi = bx[1];
+                    stands = rq_any_hit_stands(f3(lo.x, lo.y, lo.z), f3(hi.x, hi.y, hi.z), o, d, r.x, rq_load_tmax(Q, ray), S.box_c2);
+                }
+            }
+            if (stands) Q.occ[ray] = (uint8_t)(hit != WF_MISS ? RQ_OCC_OCCLUDED : 0u);
+            else wf_push(exact, ray);
+        }
+        __syncthreads();
+        if (cnt > WF_BUF - 256) wf_flush(exact, Q.q_exact, Q.ctr + RQ_CTR_EXACT, &gbase);
+    }
+    __syncthreads();
+    wf_flush(exact, Q.q_exact, Q.ctr + RQ_CTR_EXACT, &gbase);
+}
+
+// The exact list: rq_closest_exact_kernel's walk, left as the full closest walk (it is the referee, and rare), its t compared with tmax.
+__global__ __launch_bounds__(64) void rq_any_exact_kernel(SceneView S, QueryView Q) {
+    const uint32_t count = Q.ctr[RQ_CTR_EXACT];
+    uint32_t stack[RT_STACK_SIZE];
+    for (uint32_t i = blockIdx.x * 64u + threadIdx.x; i < count; i += gridDim.x * 64u) {
+        const uint32_t ray = Q.q_exact[i];
+        F3 o, d;
+        rq_load_ray(Q, ray, o, d);
+        float bt, bu, bv; uint32_t hit;
+        if (S.exact_boxes == 1u) ref_closest_hit(S, o, d, stack, bt, bu, bv, hit);
+        else {
+            Counters cnt; cnt.closest = cnt.lightq = cnt.nodes = cnt.tris = 0;
+            const HitRec h = closest_hit<false>(S, o, d, stack, cnt);
+            bt = h.t;
+            hit = h.idx < 0 ? WF_MISS : (uint32_t)h.idx;
+        }
+        Q.occ[ray] = (uint8_t)(RQ_OCC_EXACT_WALK | (hit != WF_MISS && bt < rq_load_tmax(Q, ray) ? RQ_OCC_OCCLUDED : 0u));
     }
     if (blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(Q.totals + RQ_TOTAL_EXACT, (unsigned long long)count);
 }

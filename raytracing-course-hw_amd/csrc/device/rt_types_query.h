@@ -26,6 +26,8 @@ struct QueryView {
     unsigned long long *totals;   // RQ_TOTAL_*
     uint4 *hits;                  // closest hit: 4 per ray (rt_hit), 16-byte aligned
     float *pdf;                   // light pdf: 1 per ray
+    const float *tmax;            // occlusion: the bound per ray, 4-byte aligned; null = +inf for every ray
+    uint8_t *occ;                 // occlusion: 1 byte per ray (RT_OCCLUSION_*), no alignment
     uint32_t *ovf;                // SPILL variant: WF_OVF words per persistent thread
 };
 
@@ -63,6 +65,7 @@ size_t query_ovf_words(const rt_scene *scene);                        // 0 when 
 // The launches of one chunk on `stream`; both return the number of launches.  The scene is only read.
 uint32_t query_launch_closest(const rt_scene *scene, const QueryView &Q, hipStream_t stream);
 uint32_t query_launch_light_pdf(const rt_scene *scene, const QueryView &Q, hipStream_t stream);
+uint32_t query_launch_occluded(const rt_scene *scene, const QueryView &Q, hipStream_t stream);
 uint32_t query_launch_material_table(const rt_scene *scene, uint32_t *table, hipStream_t stream); // fills n_triangles words
 uint32_t query_launch_surface(const rt_scene *scene, const SurfaceView &V, hipStream_t stream);
 uint32_t query_launch_environment(const rt_scene *scene, const EnvironmentView &V, hipStream_t stream);

@@ -1058,10 +1058,17 @@ QueryGeometry query_geometry(const rt_scene *scene, uint32_t n) {
 }
 const int rq_refill = WF_REFILL, rq_leaf_batch = WF_LEAF_BATCH | (112 << 16), rq_dyn = 64;
 
+// RTAMD_WF_LDS_STACK=n (testing), as the round pipeline takes it: the occlusion walk pretends its LDS stacks hold only n entries, so an
+// ordinary scene runs the SPILL variant.  The closest-hit and light-pdf launches keep WF_STACK.
+int query_lds_limit() {
+    const int limit = env_int("RTAMD_WF_LDS_STACK", WF_STACK);
+    return limit < 1 || limit >= WF_STACK ? WF_STACK : limit;
+}
+
 } // namespace
 
 size_t rtamd::query_ovf_words(const rt_scene *scene) {
-    return scene->info.bvh_depth > (uint32_t)WF_STACK ? (size_t)scene->n_cus * RQ_BLOCKS_PER_CU * 256u * WF_OVF : 0u;
+    return scene->info.bvh_depth > (uint32_t)query_lds_limit() ? (size_t)scene->n_cus * RQ_BLOCKS_PER_CU * 256u * WF_OVF : 0u;
 }
 
 uint32_t rtamd::query_launch_closest(const rt_scene *scene, const QueryView &Q, hipStream_t stream) {
@@ -1087,6 +1094,23 @@ uint32_t rtamd::query_launch_light_pdf(const rt_scene *scene, const QueryView &Q
     hipLaunchKernelGGL(dev::rq_light_exact_kernel, dim3(G.exact_blocks), dim3(64), 0, stream, G.V, Q);
     HIP_CHECK(hipGetLastError());
     return lean ? 3u : 2u;
+}
+
+uint32_t rtamd::query_launch_occluded(const rt_scene *scene, const QueryView &Q, hipStream_t stream) {
+    QueryGeometry G = query_geometry(scene, Q.n);
+    G.lds_limit = query_lds_limit();
+    G.spill_scene = scene->info.bvh_depth > (uint32_t)G.lds_limit;
+    hipLaunchKernelGGL(dev::rq_classify_occluded_kernel, dim3(G.flat_blocks), dim3(256), 0, stream, G.V, Q);
+    uint32_t launches = 2;
+    if (!Q.reference_walk) {
+        if (G.spill_scene) hipLaunchKernelGGL(dev::rq_any_kernel<true>, dim3(G.walk_blocks), dim3(256), 0, stream, G.V, Q, rq_refill, rq_leaf_batch, rq_dyn, G.lds_limit);
+        else hipLaunchKernelGGL(dev::rq_any_kernel<false>, dim3(G.walk_blocks), dim3(256), 0, stream, G.V, Q, rq_refill, rq_leaf_batch, rq_dyn, G.lds_limit);
+        hipLaunchKernelGGL(dev::rq_any_resolve_kernel, dim3(G.flat_blocks), dim3(256), 0, stream, G.V, Q);
+        launches += 2;
+    }
+    hipLaunchKernelGGL(dev::rq_any_exact_kernel, dim3(G.exact_blocks), dim3(64), 0, stream, G.V, Q);
+    HIP_CHECK(hipGetLastError());
+    return launches;
 }
 
 // The first-hit layer (device/rt_query_surface.h): flat launches, one lane per record.

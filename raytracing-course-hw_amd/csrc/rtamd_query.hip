@@ -1,4 +1,4 @@
-// Batched ray queries through the C-ABI (include/rtamd.h: rt_query_closest, rt_query_light_pdf) and the first-hit layer over them
+// Batched ray queries through the C-ABI (include/rtamd.h: rt_query_closest, rt_query_light_pdf, rt_query_occluded) and the first-hit layer over them
 // (rt_query_surface, rt_query_environment, rt_camera_rays, rt_render_guides): argument checks, the chunking, the staging and the
 // statistics.  No kernel and no kernel header here: the kernels (device/rt_query.h, device/rt_query_surface.h) live in rtamd_api.hip,
 // where every __global__ keeps one definition, and are launched through query_launch_* (device/rt_types_query.h).
@@ -25,14 +25,18 @@ const size_t QUERY_CHUNK = 262144;
 size_t query_chunk() { return std::min(QUERY_CHUNK, (size_t)std::max(64, env_positive("RTAMD_QUERY_CHUNK", (int)QUERY_CHUNK))); }
 
 // The staging of one chunk, carved out of one allocation that the scene keeps: counters first, then the arrays in 256-byte steps.
-// The two ray queries need the first eight parts; a surface query or a guide pass (`first_hit`) grows the allocation by the last two.
+// The two ray queries need the first eight parts; a surface query or a guide pass (STAGE_FIRST_HIT) grows the allocation by the next
+// two, an occlusion query (STAGE_OCCLUSION) by the last two: a bound and an answer byte per ray.
 const size_t PLANE_FLOATS = 10; // albedo 3, normal 3, depth 1, emission 3
+enum StageParts { STAGE_WALK, STAGE_FIRST_HIT, STAGE_OCCLUSION };
 struct QueryStage {
     uint32_t *ctr; unsigned long long *totals;
     float *rays; uint8_t *out; float4 *rec; uint32_t *q_fast, *q_exact, *ovf;
     uint8_t *surf; float *planes;
+    float *tmax; uint8_t *occ;
 };
-QueryStage query_stage(rt_scene *scene, bool first_hit) {
+QueryStage query_stage(rt_scene *scene, StageParts parts) {
+    const bool first_hit = parts == STAGE_FIRST_HIT, occlusion = parts == STAGE_OCCLUSION;
     const size_t C = QUERY_CHUNK, ovf_words = query_ovf_words(scene);
     size_t at = 0;
     auto take = [&](size_t bytes) { const size_t here = at; at += (bytes + 255u) & ~(size_t)255u; return here; };
@@ -40,6 +44,8 @@ QueryStage query_stage(rt_scene *scene, bool first_hit) {
                  o_rec = take(C * 16), o_fast = take(C * 4), o_exact = take(C * 4), o_ovf = take(ovf_words * 4);
     size_t o_surf = 0, o_planes = 0;
     if (first_hit) { o_surf = take(C * sizeof(rt_surface)); o_planes = take(C * PLANE_FLOATS * 4); }
+    size_t o_tmax = 0, o_occ = 0;
+    if (occlusion) { o_tmax = take(C * sizeof(float)); o_occ = take(C); }
     grow(scene->query_stage, scene->query_stage_bytes, at);
     uint8_t *b = scene->query_stage;
     QueryStage s;
@@ -48,6 +54,7 @@ QueryStage query_stage(rt_scene *scene, bool first_hit) {
     s.q_fast = (uint32_t *)(b + o_fast); s.q_exact = (uint32_t *)(b + o_exact);
     s.ovf = ovf_words ? (uint32_t *)(b + o_ovf) : nullptr;
     s.surf = first_hit ? b + o_surf : nullptr; s.planes = first_hit ? (float *)(b + o_planes) : nullptr;
+    s.tmax = occlusion ? (float *)(b + o_tmax) : nullptr; s.occ = occlusion ? b + o_occ : nullptr;
     return s;
 }
 
@@ -64,7 +71,7 @@ int check_call(const rt_scene *scene, const rt_query_stats *stats, uint32_t flag
 // scene's two events) and returns their number, after(...) queues the copies out; the next chunk reuses the staging, so each ends with
 // a synchronisation.  n == 0 launches nothing.
 template <class Before, class Launch, class After>
-int answer(rt_scene *scene, size_t n, rt_query_stats *stats, const std::string &who, bool first_hit, Before before, Launch launch, After after) {
+int answer(rt_scene *scene, size_t n, rt_query_stats *stats, const std::string &who, StageParts parts, Before before, Launch launch, After after) {
     return guarded(who, [&]() -> int {
         const double t0 = now_ms();
         rt_query_stats st{};
@@ -74,7 +81,7 @@ int answer(rt_scene *scene, size_t n, rt_query_stats *stats, const std::string &
         if (n) {
             HIP_CHECK(hipSetDevice(scene->device));
             hipStream_t stream = nullptr;
-            const QueryStage S = query_stage(scene, first_hit);
+            const QueryStage S = query_stage(scene, parts);
             const size_t chunk = query_chunk();
             HIP_CHECK(hipMemsetAsync(S.totals, 0, RQ_TOTAL_WORDS * 8, stream));
             float ms_sum = 0.f;
@@ -121,7 +128,7 @@ int query(rt_scene *scene, const rt_ray *rays, size_t n, uint32_t flags, void *o
     const bool on_device = (flags & RT_QUERY_DEVICE_POINTERS) != 0;
     if (n && on_device && !light && ((uintptr_t)out & 15u)) return fail(RT_ERR_INVALID_ARG, who + "with RT_QUERY_DEVICE_POINTERS the rt_hit array must be 16-byte aligned");
     const size_t out_size = light ? sizeof(float) : sizeof(rt_hit);
-    return answer(scene, n, stats, who, false,
+    return answer(scene, n, stats, who, STAGE_WALK,
         [&](const QueryStage &S, size_t first, size_t m, hipStream_t stream) {
             if (!on_device) HIP_CHECK(hipMemcpyAsync(S.rays, rays + first, m * sizeof(rt_ray), hipMemcpyHostToDevice, stream));
         },
@@ -165,6 +172,35 @@ int rt_query_light_pdf(rt_scene *scene, const rt_ray *rays, size_t n, uint32_t f
     return query(scene, rays, n, flags, out, stats, true, "rt_query_light_pdf: ");
 }
 
+int rt_query_occluded(rt_scene *scene, const rt_ray *rays, const float *tmax, size_t n, uint32_t flags, uint8_t *out, rt_query_stats *stats) {
+    const std::string who = "rt_query_occluded: ";
+    // what can be judged without the scene first, each refusal naming its argument; check_call repeats the first two and adds the scene's
+    const uint32_t allowed = RT_QUERY_DEVICE_POINTERS | RT_QUERY_REFERENCE_WALK;
+    if (stats && stats->struct_size != sizeof(rt_query_stats)) return fail(RT_ERR_INVALID_ARG, who + "struct_size mismatch (ABI skew)");
+    if (flags & ~allowed) return fail(RT_ERR_INVALID_ARG, who + "flags other than RT_QUERY_DEVICE_POINTERS | RT_QUERY_REFERENCE_WALK");
+    if (n && !rays) return fail(RT_ERR_INVALID_ARG, who + "null argument (rays)");
+    if (n && !out) return fail(RT_ERR_INVALID_ARG, who + "null argument (out)");
+    if (!scene) return fail(RT_ERR_INVALID_ARG, who + "null argument (scene)");
+    if (const int rc = check_call(scene, stats, flags, allowed, "RT_QUERY_DEVICE_POINTERS | RT_QUERY_REFERENCE_WALK", who)) return rc;
+    const bool on_device = (flags & RT_QUERY_DEVICE_POINTERS) != 0;
+    if (n && on_device && ((uintptr_t)tmax & 3u)) return fail(RT_ERR_INVALID_ARG, who + "with RT_QUERY_DEVICE_POINTERS the tmax array must be 4-byte aligned");
+    return answer(scene, n, stats, who, STAGE_OCCLUSION,
+        [&](const QueryStage &S, size_t first, size_t m, hipStream_t stream) {
+            if (on_device) return;
+            HIP_CHECK(hipMemcpyAsync(S.rays, rays + first, m * sizeof(rt_ray), hipMemcpyHostToDevice, stream));
+            if (tmax) HIP_CHECK(hipMemcpyAsync(S.tmax, tmax + first, m * sizeof(float), hipMemcpyHostToDevice, stream));
+        },
+        [&](const QueryStage &S, size_t first, size_t m, hipStream_t stream) {
+            QueryView Q = walk_view(scene, S, m, flags, on_device ? (const float *)(rays + first) : S.rays);
+            Q.tmax = !tmax ? nullptr : on_device ? tmax + first : S.tmax;
+            Q.occ = on_device ? out + first : S.occ;
+            return query_launch_occluded(scene, Q, stream);
+        },
+        [&](const QueryStage &S, size_t first, size_t m, hipStream_t stream) {
+            if (!on_device) HIP_CHECK(hipMemcpyAsync(out + first, S.occ, m, hipMemcpyDeviceToHost, stream));
+        });
+}
+
 int rt_query_surface(rt_scene *scene, const rt_hit *hits, size_t n, uint32_t flags, rt_surface *out, rt_query_stats *stats) {
     const std::string who = "rt_query_surface: ";
     if (const int rc = check_call(scene, stats, flags, RT_QUERY_DEVICE_POINTERS, "RT_QUERY_DEVICE_POINTERS", who)) return rc;
@@ -172,7 +208,7 @@ int rt_query_surface(rt_scene *scene, const rt_hit *hits, size_t n, uint32_t fla
     const bool on_device = (flags & RT_QUERY_DEVICE_POINTERS) != 0;
     if (n && on_device && (((uintptr_t)hits | (uintptr_t)out) & 15u))
         return fail(RT_ERR_INVALID_ARG, who + "with RT_QUERY_DEVICE_POINTERS the rt_hit and rt_surface arrays must be 16-byte aligned");
-    return answer(scene, n, stats, who, true,
+    return answer(scene, n, stats, who, STAGE_FIRST_HIT,
         [&](const QueryStage &S, size_t first, size_t m, hipStream_t stream) {
             ensure_materials(scene, stream);
             if (!on_device) HIP_CHECK(hipMemcpyAsync(S.out, hits + first, m * sizeof(rt_hit), hipMemcpyHostToDevice, stream));
@@ -190,7 +226,7 @@ int rt_query_environment(rt_scene *scene, const rt_ray *rays, size_t n, uint32_t
     if (const int rc = check_call(scene, stats, flags, RT_QUERY_DEVICE_POINTERS, "RT_QUERY_DEVICE_POINTERS", who)) return rc;
     if (n && (!rays || !out_rgb)) return fail(RT_ERR_INVALID_ARG, who + "null argument");
     const bool on_device = (flags & RT_QUERY_DEVICE_POINTERS) != 0;
-    return answer(scene, n, stats, who, false, // the colours of a chunk are staged where a closest-hit query keeps its 16-byte records
+    return answer(scene, n, stats, who, STAGE_WALK, // the colours of a chunk are staged where a closest-hit query keeps its 16-byte records
         [&](const QueryStage &S, size_t first, size_t m, hipStream_t stream) {
             if (!on_device) HIP_CHECK(hipMemcpyAsync(S.rays, rays + first, m * sizeof(rt_ray), hipMemcpyHostToDevice, stream));
         },
@@ -215,7 +251,7 @@ int rt_camera_rays(rt_scene *scene, int32_t width, int32_t height, const float *
     if (!on_device)
         for (size_t i = 0; i < 2 * n; i++)
             if (!std::isfinite(xy[i])) return fail(RT_ERR_INVALID_ARG, who + "xy holds a NaN or an infinity (point " + std::to_string(i / 2) + ")");
-    return answer(scene, n, nullptr, who, false, // the points of a chunk are staged where a closest-hit query keeps its 16-byte records
+    return answer(scene, n, nullptr, who, STAGE_WALK, // the points of a chunk are staged where a closest-hit query keeps its 16-byte records
         [&](const QueryStage &S, size_t first, size_t m, hipStream_t stream) {
             if (!on_device) HIP_CHECK(hipMemcpyAsync(S.rec, xy + 2 * first, m * 2 * sizeof(float), hipMemcpyHostToDevice, stream));
         },
@@ -240,7 +276,7 @@ int rt_render_guides(rt_scene *scene, int32_t width, int32_t height, uint32_t fl
     const bool on_device = (flags & RT_QUERY_DEVICE_POINTERS) != 0;
     // the planes of a chunk in the staging, in this order: {plane, floats per pixel, offset in floats per pixel of the chunk}
     struct Plane { float *p; size_t k, at; } planes[4] = {{albedo, 3, 0}, {normal, 3, 3}, {depth, 1, 6}, {emission, 3, 7}};
-    return answer(scene, (size_t)width * height, stats, who, true,
+    return answer(scene, (size_t)width * height, stats, who, STAGE_FIRST_HIT,
         [&](const QueryStage &, size_t, size_t, hipStream_t stream) { ensure_materials(scene, stream); },
         [&](const QueryStage &S, size_t first, size_t m, hipStream_t stream) {
             CameraView C{};
