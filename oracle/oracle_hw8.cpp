@@ -246,16 +246,25 @@ struct FiguresMix {                            // distributions.h:97-166
 
 // distributions.h:168-246
 struct Vndf {
+    // :180-184, the two draws and the point on the disk; nothing before them in sample_ draws or depends on them
+    static void disk_point(U01 &u01, rng_t &rng, float &t1, float &t2) {
+        float u1 = u01(rng), u2 = u01(rng);
+        float r = std::sqrt((double)u1);
+        float phi = 2.0 * M_PI * u2;
+        t1 = r * std::cos((double)phi);
+        t2 = r * std::sin((double)phi);
+    }
     static V3 sample_(U01 &u01, rng_t &rng, V3 v, float alpha) {
+        float t1, t2;
+        disk_point(u01, rng, t1, t2);
+        return sample_local(t1, t2, v, alpha);
+    }
+    // :170-194 without the draws
+    static V3 sample_local(float t1, float t2, V3 v, float alpha) {
         V3 vh = normalize(V3{alpha * v.x, alpha * v.y, v.z});
         float lensq = vh.x * vh.x + vh.y * vh.y;
         V3 T1 = lensq > 0 ? (float)(1. / std::sqrt((double)lensq)) * V3{-vh.y, vh.x, 0} : V3{1, 0, 0};
         V3 T2 = crossr(T1, vh);
-        float u1 = u01(rng), u2 = u01(rng);
-        float r = std::sqrt((double)u1);
-        float phi = 2.0 * M_PI * u2;
-        float t1 = r * std::cos((double)phi);
-        float t2 = r * std::sin((double)phi);
         float s = 0.5 * (1.0 + vh.z);
         t2 = (1.0 - s) * std::sqrt((double)(1.f - t1 * t1)) + s * t2;
         V3 nh = t1 * T1 + t2 * T2 + (float)std::sqrt((double)std::max<float>(0.f, 1.0 - t1 * t1 - t2 * t2)) * vh;
@@ -582,7 +591,46 @@ void rto_hw8_brdf(float base_metallic, const float *base_color, const float *l, 
     V3 r = m.brdf(v3(l), v3(v), v3(n), v3(color), metallic, alpha);
     out3[0] = r.x; out3[1] = r.y; out3[2] = r.z;
 }
+// ---- the shading layer's functions on their own (tests/shading_cases.py).  The samplers return the sample, the pdf of that sample
+// and the next uniform draw of the engine (the stream position), as rto_hw8_mix_sample_pdf does.
+void rto_hw8_vndf_sample_pdf(uint32_t seed, const float *n, const float *v, float alpha, float *out5) {
+    rng_t rng(seed); U01 u01(0.0, 1.0);
+    V3 d = Vndf::sample(u01, rng, v3(n), v3(v), alpha);
+    float pdf = Vndf::pdf(v3(n), d, v3(v), alpha);
+    out5[0] = d.x; out5[1] = d.y; out5[2] = d.z; out5[3] = pdf; out5[4] = u01(rng);
+}
+float rto_hw8_vndf_pdf(const float *n, const float *d, const float *v, float alpha) { return Vndf::pdf(v3(n), v3(d), v3(v), alpha); }
+// Vndf::sample_ behind its two draws: (t1, t2) is the point on the disk, vT the view direction in the local frame
+void rto_hw8_vndf_sample_local(float t1, float t2, const float *vT, float alpha, float *out3) {
+    V3 r = Vndf::sample_local(t1, t2, v3(vT), alpha);
+    out3[0] = r.x; out3[1] = r.y; out3[2] = r.z;
+}
+void rto_hw8_cosine_sample_pdf(uint32_t seed, const float *n, float *out5) {
+    rng_t rng(seed); U01 u01(0.0, 1.0); N01 n01(0.0, 1.0);
+    V3 d = cosine_sample(n01, rng, v3(n));
+    float pdf = cosine_pdf(v3(n), d);
+    out5[0] = d.x; out5[1] = d.y; out5[2] = d.z; out5[3] = pdf; out5[4] = u01(rng);
+}
+float rto_hw8_cosine_pdf(const float *n, const float *d) { return cosine_pdf(v3(n), v3(d)); }
+// hw7's MaterialModel(alpha, metallic, baseColor): the constructor squares alpha (hw7/src/include/material.h:42)
+void rto_hw7_brdf(float alpha, float metallic, const float *base_color, const float *l, const float *v, const float *n, float *out3) {
+    MaterialModel m{metallic, v3(base_color)};
+    V3 r = m.brdf_hw7(v3(l), v3(v), v3(n), alpha * alpha);
+    out3[0] = r.x; out3[1] = r.y; out3[2] = r.z;
+}
+// dot(h, l) and dot(h, v) of specularBrdf (material.h:24-25) for n pairs (l, v: n x 3; out: n x 2): what its 1e-4 gate compares, so
+// that the cases can be put on the gate's threshold to the bit
+void rto_hw8_half_dots(const float *l, const float *v, float *out, size_t n) {
+    for (size_t i = 0; i < n; i++) {
+        V3 h = normalize(v3(l + 3 * i) + v3(v + 3 * i));
+        out[2 * i] = dot(h, v3(l + 3 * i)); out[2 * i + 1] = dot(h, v3(v + 3 * i));
+    }
+}
 void rto_tonemap(const float *rgb, uint8_t *out3) { to_extern(gamma_corrected(aces_tonemap(v3(rgb))), out3); }
+// Host libm cos / sin on doubles (what the reference's Vndf::sample_ calls, distributions.h:183-184).  numpy's own may be a SIMD
+// implementation that is not glibc's.
+void rto_cos_array(const double *in, double *out, size_t n) { for (size_t i = 0; i < n; i++) out[i] = std::cos(in[i]); }
+void rto_sin_array(const double *in, double *out, size_t n) { for (size_t i = 0; i < n; i++) out[i] = std::sin(in[i]); }
 void rto_sample_texture(int w, int h, const uint8_t *data, float tx, float ty, int srgb, float *out3) {
     V3 r = sample_texture(tx, ty, Tex{w, h, data}, srgb != 0);
     out3[0] = r.x; out3[1] = r.y; out3[2] = r.z;

@@ -88,6 +88,26 @@ void ref8_brdf(float base_metallic, const float *base_color, const float *l, con
     Vec3 r = m.brdf(v3(l), v3(v), v3(n), v3(color), metallic, alpha);
     out3[0] = r.x; out3[1] = r.y; out3[2] = r.z;
 }
+// The shading layer's samplers on their own (tests/shading_cases.py).  Each: the sample, the pdf of that sample and the next uniform
+// draw of the engine (the stream position), as ref8_mix_sample_pdf above.  Vndf and Cosine ignore their x argument.
+void ref8_vndf_sample_pdf(uint32_t seed, const float *n, const float *v, float alpha, float *out5) {
+    rng_type rng(seed);
+    std::uniform_real_distribution<float> u01(0.0, 1.0);
+    Vndf vndf;
+    Vec3 d = vndf.sample(u01, rng, Vec3(0, 0, 0), v3(n), v3(v), alpha);
+    float pdf = vndf.pdf(Vec3(0, 0, 0), v3(n), d, v3(v), alpha);
+    out5[0] = d.x; out5[1] = d.y; out5[2] = d.z; out5[3] = pdf; out5[4] = u01(rng);
+}
+float ref8_vndf_pdf(const float *n, const float *d, const float *v, float alpha) { return Vndf().pdf(Vec3(0, 0, 0), v3(n), v3(d), v3(v), alpha); }
+void ref8_cosine_sample_pdf(uint32_t seed, const float *n, float *out5) {
+    rng_type rng(seed);
+    std::uniform_real_distribution<float> u01(0.0, 1.0);
+    std::normal_distribution<float> n01(0.0, 1.0);
+    Cosine cosine;
+    Vec3 d = cosine.sample(n01, rng, Vec3(0, 0, 0), v3(n));
+    float pdf = cosine.pdf(Vec3(0, 0, 0), v3(n), d);
+    out5[0] = d.x; out5[1] = d.y; out5[2] = d.z; out5[3] = pdf; out5[4] = u01(rng);
+}
 // Node transform chain exactly as hw8/src/sceneio.cpp:125-134 (calculateTransitions) and :247-293 (loadFigures) apply it:
 // chain = n_levels x {t3, q4(x,y,z,w), s3}, outermost parent first; if matrix16 != NULL the innermost node uses that
 // column-major matrix instead (sceneio.cpp:67-74).

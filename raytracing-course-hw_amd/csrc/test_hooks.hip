@@ -71,6 +71,90 @@ __global__ void k_rng_triple(uint32_t seed0, int n_seeds, int prior, uint32_t *o
     }
 }
 
+// The shading layer of rt_device.h, one lane per case (tests/shading_cases.py has the cases and the row layouts).
+// in: 18 floats (base_metallic, base_color 3, l 3, v 3, n 3, color 3, metallic, alpha), out: 3.  variant 0: material_brdf; 1: material_brdf_pre on
+// the two products the shader forms (rt_persistent.h, shade_fetch_attr's results); 2: material_brdf_hw7 with alpha2 = alpha * alpha as there
+__global__ void k_brdf(int variant, const float *in, float *out, size_t n) {
+    size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float *p = in + 18 * i;
+    const float base_metallic = p[0], metallic = p[16], alpha = p[17];
+    const F3 base_color = f3(p + 1), l = f3(p + 4), v = f3(p + 7), nn = f3(p + 10), color = f3(p + 13);
+    F3 r;
+    if (variant == 0) r = material_brdf(base_color, base_metallic, l, v, nn, color, metallic, alpha);
+    else if (variant == 1) r = material_brdf_pre(base_color * color, metallic * base_metallic, l, v, nn, alpha);
+    else r = material_brdf_hw7(base_color, base_metallic, l, v, nn, alpha * alpha);
+    out[3 * i] = r.x; out[3 * i + 1] = r.y; out[3 * i + 2] = r.z;
+}
+// in: 7 floats (n 3, v 3, alpha), out: 5 (d 3, pdf of d, the next rng_u01), state: the engine after the sample.  form 0: the plain pair;
+// 1: the frame-given pair on a frame built as the persistent shader builds it
+__global__ void k_vndf(int form, const uint32_t *seed, const float *in, float *out, uint32_t *state, size_t n) {
+    size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float *p = in + 7 * i;
+    const F3 nn = f3(p), v = f3(p + 3);
+    const float alpha = p[6];
+    Rng rng;
+    rng_seed(rng, seed[i]);
+    F3 d; float pdf;
+    if (form == 0) { d = vndf_sample(rng, nn, v, alpha); pdf = vndf_pdf(nn, d, v, alpha); }
+    else {
+        const Quat q = vndf_getq(nn);
+        const F3 vT = qtransform(q, neg(v));
+        d = vndf_sample(rng, q, vT, alpha);
+        pdf = vndf_pdf(q, vT, d, alpha);
+    }
+    state[i] = rng.x;
+    out[5 * i] = d.x; out[5 * i + 1] = d.y; out[5 * i + 2] = d.z; out[5 * i + 3] = pdf; out[5 * i + 4] = rng_u01(rng);
+}
+__global__ void k_vndf_local(const float *in, float *out, size_t n) { // in: t1, t2, vT 3, alpha
+    size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float *p = in + 6 * i;
+    const F3 r = vndf_sample_local(p[0], p[1], f3(p + 2), p[5]);
+    out[3 * i] = r.x; out[3 * i + 1] = r.y; out[3 * i + 2] = r.z;
+}
+__global__ void k_vndf_pdf(const float *in, float *out, size_t n) { // in: n 3, d 3, v 3, alpha
+    size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float *p = in + 10 * i;
+    out[i] = vndf_pdf(f3(p), f3(p + 3), f3(p + 6), p[9]);
+}
+__global__ void k_cosine(const uint32_t *seed, const float *in, float *out, uint32_t *state, size_t n) { // in: n 3; out as k_vndf
+    size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const F3 nn = f3(in + 3 * i);
+    Rng rng;
+    rng_seed(rng, seed[i]);
+    const F3 d = cosine_sample(rng, nn);
+    state[i] = rng.x;
+    out[5 * i] = d.x; out[5 * i + 1] = d.y; out[5 * i + 2] = d.z; out[5 * i + 3] = cosine_pdf(nn, d); out[5 * i + 4] = rng_u01(rng);
+}
+__global__ void k_cosine_pdf(const float *in, float *out, size_t n) { // in: n 3, d 3
+    size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (i < n) out[i] = cosine_pdf(f3(in + 6 * i), f3(in + 6 * i + 3));
+}
+__global__ void k_tonemap(const float *in, uint8_t *out, size_t n) {
+    size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (i < n) out[i] = tonemap1(in[i]);
+}
+// vndf_disk_point on the stream of seed0 + i: u = the two uniforms the call consumed (from a copy of the engine), t = (t1, t2), cs = the
+// device libm's cos and sin of the angle in double, which the call narrows (for the census of the test)
+__global__ void k_disk_point(uint32_t seed0, float *u, float *t, double *cs, size_t n) {
+    size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    Rng rng;
+    rng_seed(rng, seed0 + (uint32_t)i);
+    Rng copy = rng;
+    const float u1 = rng_u01(copy), u2 = rng_u01(copy);
+    float t1, t2;
+    vndf_disk_point(rng, t1, t2);
+    const float phi = (float)(2.0 * RT_PI * (double)u2);
+    u[2 * i] = u1; u[2 * i + 1] = u2;
+    t[2 * i] = t1; t[2 * i + 1] = t2;
+    cs[2 * i] = cos((double)phi); cs[2 * i + 1] = sin((double)phi);
+}
+
 // rt_exact.h: the runner-up's distance as it travels in the hit word, and the gate's decision on a box / ray / hit / gap
 __global__ void k_gap(const float *t, const float *t2, float *floor_out, uint32_t *code_out, size_t n) {
     size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
@@ -214,6 +298,23 @@ void digest_of(PreparedDigest &D, const rtamd::PreparedSceneTxt &P) { // listed 
 }
 #undef PD_VEC
 #undef PD_SCALAR
+
+// A device buffer of the shading hooks: filled from `src` when there is one; ok() says whether every step so far succeeded.
+struct HookBuf {
+    void *d = nullptr;
+    size_t bytes;
+    bool good;
+    HookBuf(const void *src, size_t bytes_) : bytes(bytes_) {
+        good = hipMalloc(&d, bytes ? bytes : 1) == hipSuccess;
+        if (good && src) good = hipMemcpy(d, src, bytes, hipMemcpyHostToDevice) == hipSuccess;
+    }
+    ~HookBuf() { (void)hipFree(d); }
+    HookBuf(const HookBuf &) = delete;
+    HookBuf &operator=(const HookBuf &) = delete;
+    template <class T> T *as() const { return (T *)d; }
+    bool back(void *dst) const { return hipMemcpy(dst, d, bytes, hipMemcpyDeviceToHost) == hipSuccess; }
+};
+inline dim3 hook_grid(size_t n) { return dim3((unsigned)((n + 255) / 256)); }
 } // namespace
 
 extern "C" {
@@ -348,6 +449,64 @@ int rtt_env_uv(const float *d, float *uv, size_t n) {
     int rc = hipMemcpy(uv, d_uv, n * 8, hipMemcpyDeviceToHost) == hipSuccess ? 0 : -2;
     (void)hipFree(d_d); (void)hipFree(d_uv);
     return rc;
+}
+// The shading layer (k_brdf .. k_disk_point above; rows as documented there).  0, or -1 for a refused argument, -2 when a HIP call fails.
+int rtt_brdf(int variant, const float *in, float *out, size_t n) {
+    if (variant < 0 || variant > 2 || n == 0) return -1;
+    HookBuf b_in(in, n * 18 * 4), b_out(nullptr, n * 3 * 4);
+    if (!b_in.good || !b_out.good) return -2;
+    hipLaunchKernelGGL(k_brdf, hook_grid(n), dim3(256), 0, 0, variant, b_in.as<float>(), b_out.as<float>(), n);
+    return hipDeviceSynchronize() == hipSuccess && b_out.back(out) ? 0 : -2;
+}
+int rtt_vndf(int form, const uint32_t *seed, const float *in, float *out, uint32_t *state, size_t n) {
+    if (form < 0 || form > 1 || n == 0) return -1;
+    HookBuf b_seed(seed, n * 4), b_in(in, n * 7 * 4), b_out(nullptr, n * 5 * 4), b_state(nullptr, n * 4);
+    if (!b_seed.good || !b_in.good || !b_out.good || !b_state.good) return -2;
+    hipLaunchKernelGGL(k_vndf, hook_grid(n), dim3(256), 0, 0, form, b_seed.as<uint32_t>(), b_in.as<float>(), b_out.as<float>(), b_state.as<uint32_t>(), n);
+    return hipDeviceSynchronize() == hipSuccess && b_out.back(out) && b_state.back(state) ? 0 : -2;
+}
+int rtt_vndf_local(const float *in, float *out, size_t n) {
+    if (n == 0) return -1;
+    HookBuf b_in(in, n * 6 * 4), b_out(nullptr, n * 3 * 4);
+    if (!b_in.good || !b_out.good) return -2;
+    hipLaunchKernelGGL(k_vndf_local, hook_grid(n), dim3(256), 0, 0, b_in.as<float>(), b_out.as<float>(), n);
+    return hipDeviceSynchronize() == hipSuccess && b_out.back(out) ? 0 : -2;
+}
+int rtt_vndf_pdf(const float *in, float *out, size_t n) {
+    if (n == 0) return -1;
+    HookBuf b_in(in, n * 10 * 4), b_out(nullptr, n * 4);
+    if (!b_in.good || !b_out.good) return -2;
+    hipLaunchKernelGGL(k_vndf_pdf, hook_grid(n), dim3(256), 0, 0, b_in.as<float>(), b_out.as<float>(), n);
+    return hipDeviceSynchronize() == hipSuccess && b_out.back(out) ? 0 : -2;
+}
+int rtt_cosine(const uint32_t *seed, const float *in, float *out, uint32_t *state, size_t n) {
+    if (n == 0) return -1;
+    HookBuf b_seed(seed, n * 4), b_in(in, n * 3 * 4), b_out(nullptr, n * 5 * 4), b_state(nullptr, n * 4);
+    if (!b_seed.good || !b_in.good || !b_out.good || !b_state.good) return -2;
+    hipLaunchKernelGGL(k_cosine, hook_grid(n), dim3(256), 0, 0, b_seed.as<uint32_t>(), b_in.as<float>(), b_out.as<float>(), b_state.as<uint32_t>(), n);
+    return hipDeviceSynchronize() == hipSuccess && b_out.back(out) && b_state.back(state) ? 0 : -2;
+}
+int rtt_cosine_pdf(const float *in, float *out, size_t n) {
+    if (n == 0) return -1;
+    HookBuf b_in(in, n * 6 * 4), b_out(nullptr, n * 4);
+    if (!b_in.good || !b_out.good) return -2;
+    hipLaunchKernelGGL(k_cosine_pdf, hook_grid(n), dim3(256), 0, 0, b_in.as<float>(), b_out.as<float>(), n);
+    return hipDeviceSynchronize() == hipSuccess && b_out.back(out) ? 0 : -2;
+}
+int rtt_tonemap(const float *in, uint8_t *out, size_t n) {
+    if (n == 0) return -1;
+    HookBuf b_in(in, n * 4), b_out(nullptr, n);
+    if (!b_in.good || !b_out.good) return -2;
+    hipLaunchKernelGGL(k_tonemap, hook_grid(n), dim3(256), 0, 0, b_in.as<float>(), b_out.as<uint8_t>(), n);
+    return hipDeviceSynchronize() == hipSuccess && b_out.back(out) ? 0 : -2;
+}
+// seeds seed0 .. seed0 + n - 1 (n < 2^31): u and t n x 2 floats, cs n x 2 doubles
+int rtt_disk_point(uint32_t seed0, size_t n, float *u, float *t, double *cs) {
+    if (n == 0 || n >= (1u << 31)) return -1;
+    HookBuf b_u(nullptr, n * 8), b_t(nullptr, n * 8), b_cs(nullptr, n * 16);
+    if (!b_u.good || !b_t.good || !b_cs.good) return -2;
+    hipLaunchKernelGGL(k_disk_point, hook_grid(n), dim3(256), 0, 0, seed0, b_u.as<float>(), b_t.as<float>(), b_cs.as<double>(), n);
+    return hipDeviceSynchronize() == hipSuccess && b_u.back(u) && b_t.back(t) && b_cs.back(cs) ? 0 : -2;
 }
 // k_rng_triple: out = n_seeds x 2 x 8 words
 int rtt_rng_triple(uint32_t seed0, int n_seeds, int prior, uint32_t *out) {

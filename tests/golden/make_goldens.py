@@ -1,6 +1,7 @@
 """Regenerates tests/golden/pins_*.npz from the compiled reference (oracle/_ref, built where the reference's sources are).
 Run:  python tests/golden/make_goldens.py      (after `make -C oracle`)
-      python tests/golden/make_goldens.py orders      only pins_oracle_orders.npz, which comes from the oracle itself"""
+      python tests/golden/make_goldens.py orders      only pins_oracle_orders.npz, which comes from the oracle itself
+      python tests/golden/make_goldens.py shading     only pins_shading_edges.npz"""
 import ctypes as C
 import os
 import sys
@@ -111,6 +112,16 @@ def main():
     np.savez_compressed(os.path.join(HERE, "pins_hw5_render.npz"), **out)
     save_reference_crops()
     save_env_uv()
+    save_shading_edges()
+
+
+def save_shading_edges():
+    """The shading layer at its branch points (tests/shading_cases.py) through the reference's own MaterialModel (hw8 and hw7), Vndf, Cosine
+    and tone-mapping.  Outputs only: the inputs are the case table's."""
+    import shading_cases
+    out = shading_cases.evaluate("reference")
+    np.savez_compressed(os.path.join(HERE, "pins_shading_edges.npz"), **{k: out[k] for k in shading_cases.REFERENCE_FAMILIES})
+    print("shading edges", {k: v.shape for k, v in out.items()})
 
 
 def save_env_uv():
@@ -153,4 +164,9 @@ def save_reference_crops():
 
 
 if __name__ == "__main__":
-    save_oracle_orders() if sys.argv[1:] == ["orders"] else main()
+    if sys.argv[1:] == ["orders"]:
+        save_oracle_orders()
+    elif sys.argv[1:] == ["shading"]:
+        save_shading_edges()
+    else:
+        main()
