@@ -576,6 +576,31 @@ int rto_hw8_closest_hit(void *p, const float *o, const float *d, float *out14) {
     return idx;
 }
 float rto_hw8_light_pdf(void *p, const float *x, const float *d) { return ((Scene *)p)->lightmix.pdf(v3(x), v3(d)); }
+// ---- the intersection layer's two tests on their own (tests/intersection_cases.py), n rows each.
+// rows12: mn, mx, o, d -> aabb_ray (oracle_bvh.h).  flags: 1 accepted | 2 inside; t: 0 for a rejected box.
+void rto_box_test(const float *rows12, size_t n, uint32_t *flags, float *t) {
+    for (size_t i = 0; i < n; i++) {
+        const float *p = rows12 + 12 * i;
+        float tt = 0; bool inside = false;
+        const bool ok = aabb_ray(Box{v3(p), v3(p + 3)}, v3(p + 6), v3(p + 9), tt, inside);
+        flags[i] = ok ? (1u | (inside ? 2u : 0u)) : 0u;
+        t[i] = ok ? tt : 0.f;
+    }
+}
+// rows15: the positions of data, data2, data3, then o, d -> tri_ray on a figure with texcoords (1,0), (0,1), (0,0), so that the hit's
+// texcoords are 0 + u * 1 + v * 0 and 0 + u * 0 + v * 1.  flags: 1 hit | 2 inside; out3: t and the two texcoords (0 for a miss).
+void rto_tri_test(const float *rows15, size_t n, uint32_t *flags, float *out3) {
+    for (size_t i = 0; i < n; i++) {
+        const float *p = rows15 + 15 * i;
+        Fig f;
+        f.d.coords = v3(p); f.d2.coords = v3(p + 3); f.d3.coords = v3(p + 6);
+        f.d.tu = 1; f.d2.tv = 1;
+        Hit h;
+        const bool hit = tri_ray(f, v3(p + 9), v3(p + 12), h);
+        flags[i] = hit ? (1u | (h.inside ? 2u : 0u)) : 0u;
+        out3[3 * i] = hit ? h.t : 0.f; out3[3 * i + 1] = hit ? h.tu : 0.f; out3[3 * i + 2] = hit ? h.tv : 0.f;
+    }
+}
 // Mix::sample then Mix::pdf with a fresh engine seeded `seed` after `burn` discarded uniform draws.
 void rto_hw8_mix_sample_pdf(void *p, uint32_t seed, const float *x, const float *n, const float *v, float alpha, float *out_d3_pdf) {
     Scene *s = (Scene *)p;

@@ -108,6 +108,32 @@ void ref8_cosine_sample_pdf(uint32_t seed, const float *n, float *out5) {
     float pdf = cosine.pdf(Vec3(0, 0, 0), v3(n), d);
     out5[0] = d.x; out5[1] = d.y; out5[2] = d.z; out5[3] = pdf; out5[4] = u01(rng);
 }
+// The intersection layer's two tests on their own (tests/intersection_cases.py), n rows each.
+// rows12: mn, mx, o, d -> AABB::intersect.  flags: 1 accepted | 2 is_inside; t: the intersection's t (0 for a rejected box).
+void ref8_box_test(const float *rows12, size_t n, uint32_t *flags, float *t) {
+    for (size_t i = 0; i < n; i++) {
+        const float *p = rows12 + 12 * i;
+        auto r = AABB(v3(p), v3(p + 3)).intersect(Ray(v3(p + 6), v3(p + 9)));
+        flags[i] = r.has_value() ? (1u | (r.value().is_inside ? 2u : 0u)) : 0u;
+        t[i] = r.has_value() ? r.value().t : 0.f;
+    }
+}
+// rows15: the positions of data, data2, data3, then o, d -> Figure::intersect of one Figure with those corners, texcoords (1,0), (0,1),
+// (0,0) (so that the interpolated texcoords are 0 + u * 1 + v * 0 and 0 + u * 0 + v * 1), normals (0,0,1) and tangents (1,0,0,1).
+// flags: 1 hit | 2 is_inside; out3: t and the two texcoords (0 for a miss).
+void ref8_tri_test(const float *rows15, size_t n, uint32_t *flags, float *out3) {
+    for (size_t i = 0; i < n; i++) {
+        const float *p = rows15 + 15 * i;
+        const Vec4 tangent(Vec3(1, 0, 0), 1);
+        Figure f(Vertex(v3(p), Vec2(1, 0), Vec3(0, 0, 1), tangent), Vertex(v3(p + 3), Vec2(0, 1), Vec3(0, 0, 1), tangent),
+                 Vertex(v3(p + 6), Vec2(0, 0), Vec3(0, 0, 1), tangent));
+        auto r = f.intersect(Ray(v3(p + 9), v3(p + 12)));
+        flags[i] = r.has_value() ? (1u | (r.value().is_inside ? 2u : 0u)) : 0u;
+        out3[3 * i] = r.has_value() ? r.value().t : 0.f;
+        out3[3 * i + 1] = r.has_value() ? r.value().texcoords.value().x : 0.f;
+        out3[3 * i + 2] = r.has_value() ? r.value().texcoords.value().y : 0.f;
+    }
+}
 // Node transform chain exactly as hw8/src/sceneio.cpp:125-134 (calculateTransitions) and :247-293 (loadFigures) apply it:
 // chain = n_levels x {t3, q4(x,y,z,w), s3}, outermost parent first; if matrix16 != NULL the innermost node uses that
 // column-major matrix instead (sceneio.cpp:67-74).

@@ -150,6 +150,24 @@ RT_DEV bool pt_hit_stands(F3 lo, F3 hi, F3 o, F3 d, float t, float gap, float c2
     return worst >= need && exit_ >= need && gap > window && gap > 4.8e-7f * (t + gap) && window <= seen; // NaN compares false: exact walk
 }
 
+// Does the any-hit walk's hit at t on the triangle whose box is [lo, hi] stand as "the reference reports a hit below tmax"?  The
+// arithmetic of pt_hit_stands with the any-hit conditions (a) and (b) of rt_query.h's occlusion walk.  NaN compares false: exact walk.
+RT_DEV bool rq_any_hit_stands(F3 lo, F3 hi, F3 o, F3 d, float t, float tmax, float c2) {
+    const F3 P = o + t * d;
+    if (pt_deep_inside(lo, hi, P, d, t, c2)) return true;
+    const float ix = pt_rcp(fmaxf(fabsf(d.x), 1e-30f)), iy = pt_rcp(fmaxf(fabsf(d.y), 1e-30f)), iz = pt_rcp(fmaxf(fabsf(d.z), 1e-30f));
+    const float inx = d.x > 0 ? P.x - lo.x : hi.x - P.x, outx = d.x > 0 ? hi.x - P.x : P.x - lo.x;
+    const float iny = d.y > 0 ? P.y - lo.y : hi.y - P.y, outy = d.y > 0 ? hi.y - P.y : P.y - lo.y;
+    const float inz = d.z > 0 ? P.z - lo.z : hi.z - P.z, outz = d.z > 0 ? hi.z - P.z : P.z - lo.z;
+    const float ax = (inx - c2) * ix, ay = (iny - c2) * iy, az = (inz - c2) * iz;
+    const float bx = (outx - c2) * ix, by = (outy - c2) * iy, bz = (outz - c2) * iz;
+    const float need = 1.9073486328125e-06f * t;
+    const float worst = fminf(fminf(fminf(ax + by, ax + bz), fminf(ay + bx, ay + bz)), fminf(az + bx, az + by));
+    const float exit_ = t + fminf(fminf(bx, by), bz);
+    const float window = need - fminf(fminf(ax, ay), az);
+    return worst >= need && exit_ >= need && tmax - t > window;
+}
+
 // Does the ray pierce one of the scene's tripwires (host/scene_prep.h: the leaf boxes of the triangles whose test accepts points far from the
 // triangle) and pass that triangle's test?  Such a ray's closest hit goes straight to the exact walk.  Conservative: the boxes carry a generous pad, the reciprocals are
 // v_rcp_f32, the interval is widened like slab_test's.  Two levels: up to four groups (wave-uniform records: scalar loads), members on a hit.

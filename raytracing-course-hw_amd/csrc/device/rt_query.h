@@ -69,6 +69,11 @@ RT_DEV int rq_classify(const QueryView &Q, F3 o, F3 d) {
 
 RT_DEV float rq_x86_nan(float v) { return v != v ? __uint_as_float(__float_as_uint(v) | 0x80000000u) : v; }
 RT_DEV uint32_t rq_bits(float v) { return __float_as_uint(rq_x86_nan(v)); }
+// -1. * v where the reference's build negates by flipping the sign bit, a NaN's included: x86's NaN first, then the flip.
+RT_DEV uint32_t rq_bits_negated(float v) { return rq_bits(v) ^ 0x80000000u; }
+// A light pdf that is a NaN became one in a term's fabs(d . normal) (distributions.h:68-70), which clears the sign; the additions and the
+// division after it hand that NaN on as it is.
+RT_DEV float rq_pdf_nan(float v) { return v != v ? __uint_as_float(0x7FC00000u) : v; }
 
 // One rt_hit: t | triangle | ng.xyz | texcoord.xy | ns.xyz | tangent.xyzw | flags | reserved.
 RT_DEV void rq_write_hit(const SceneView &S, const QueryView &Q, uint32_t ray, float t, float u, float v, uint32_t hit, uint32_t flags) {
@@ -88,14 +93,13 @@ RT_DEV void rq_write_hit(const SceneView &S, const QueryView &Q, uint32_t ray, f
     const float4 s0 = q[0], s1 = q[1], s2 = q[2], s3 = q[3];
     const F3 n3 = f3(s0.x, s0.y, s0.z), dn1 = f3(s0.w, s1.x, s1.y), dn2 = f3(s1.z, s1.w, s2.x);
     F3 sn = n3 + u * dn1 + v * dn2;                                               // :110
-    sn = normalize(sn);                                                           // :117
-    if (inside) sn = neg(sn);                                                     // :118-119
+    sn = normalize(sn);                                                           // :117; the flip of :118-119 is made on the bits below
     const F3 t3 = f3(s2.y, s2.z, s2.w), dt1 = f3(s3.x, s3.y, s3.z), dt2 = f3(s3.w, H.s4.x, H.s4.y);
     F3 tg = t3 + u * dt1 + v * dt2;                                               // :115
     tg = normalize(tg);                                                           // :116
     out[0] = make_uint4(rq_bits(t), __float_as_uint(H.s6.z), rq_bits(ng.x), rq_bits(ng.y)); // TriShade::orig: figure order -> LOAD order
-    out[1] = make_uint4(rq_bits(ng.z), rq_bits(tu), rq_bits(tv), rq_bits(sn.x));
-    out[2] = make_uint4(rq_bits(sn.y), rq_bits(sn.z), rq_bits(tg.x), rq_bits(tg.y));
+    out[1] = make_uint4(rq_bits(ng.z), rq_bits(tu), rq_bits(tv), inside ? rq_bits_negated(sn.x) : rq_bits(sn.x));
+    out[2] = make_uint4(inside ? rq_bits_negated(sn.y) : rq_bits(sn.y), inside ? rq_bits_negated(sn.z) : rq_bits(sn.z), rq_bits(tg.x), rq_bits(tg.y));
     out[3] = make_uint4(rq_bits(tg.z), __float_as_uint(H.s6.x), flags | (inside ? RQ_HIT_INSIDE : 0u), 0u);
 }
 
@@ -277,7 +281,7 @@ struct RqLightWalk : WfWalkRay {
     RT_DEV bool next() {
         if (sp != 0) { cur = stack[--sp][lane]; return false; }
         if (overflow) Q.q_exact[atomicAdd(Q.ctr + RQ_CTR_EXACT, 1u)] = slot;
-        else Q.pdf[slot] = rq_x86_nan(wf_merge_light_hits(S, stack, lane, k) / S.n_lights_f);
+        else Q.pdf[slot] = rq_pdf_nan(wf_merge_light_hits(S, stack, lane, k) / S.n_lights_f);
         return true;
     }
     template <bool COUNT> RT_DEV bool step(WfWalkStat<COUNT> &n) {
@@ -327,7 +331,7 @@ __global__ __launch_bounds__(64) void rq_light_exact_kernel(SceneView S, QueryVi
         rq_load_ray(Q, ray, x, d);
         Counters cnt; cnt.closest = cnt.lightq = cnt.nodes = cnt.tris = 0;
         const float v = S.exact_boxes == 1u ? ref_light_pdf_sum(S, x, d, stack) : light_pdf_sum<false>(S, x, d, stack, cnt);
-        Q.pdf[ray] = rq_x86_nan(v / S.n_lights_f);
+        Q.pdf[ray] = rq_pdf_nan(v / S.n_lights_f);
     }
     if (blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(Q.totals + RQ_TOTAL_EXACT, (unsigned long long)count);
 }
@@ -451,24 +455,6 @@ __global__ __launch_bounds__(256) void rq_any_kernel(SceneView S, QueryView Q, i
     W.ovf = Q.ovf;
     RqAnyWalk<SPILL> w(S, Q, W, lds_stack[threadIdx.x >> 6], lds_limit);
     wf_walk_loop<false>(w, Q.q_fast, wf_slice(Q.ctr[RQ_CTR_FAST], Q.ctr + RQ_CTR_HEAD, dyn, 0u, gridDim.x, true), nullptr, refill, leaf_batch);
-}
-
-// Does the any-hit walk's hit at t on the triangle whose box is [lo, hi] stand as "the reference reports a hit below tmax"?  The
-// arithmetic of pt_hit_stands with the any-hit conditions (a) and (b) above.  NaN compares false: exact walk.
-RT_DEV bool rq_any_hit_stands(F3 lo, F3 hi, F3 o, F3 d, float t, float tmax, float c2) {
-    const F3 P = o + t * d;
-    if (pt_deep_inside(lo, hi, P, d, t, c2)) return true;
-    const float ix = pt_rcp(fmaxf(fabsf(d.x), 1e-30f)), iy = pt_rcp(fmaxf(fabsf(d.y), 1e-30f)), iz = pt_rcp(fmaxf(fabsf(d.z), 1e-30f));
-    const float inx = d.x > 0 ? P.x - lo.x : hi.x - P.x, outx = d.x > 0 ? hi.x - P.x : P.x - lo.x;
-    const float iny = d.y > 0 ? P.y - lo.y : hi.y - P.y, outy = d.y > 0 ? hi.y - P.y : P.y - lo.y;
-    const float inz = d.z > 0 ? P.z - lo.z : hi.z - P.z, outz = d.z > 0 ? hi.z - P.z : P.z - lo.z;
-    const float ax = (inx - c2) * ix, ay = (iny - c2) * iy, az = (inz - c2) * iz;
-    const float bx = (outx - c2) * ix, by = (outy - c2) * iy, bz = (outz - c2) * iz;
-    const float need = 1.9073486328125e-06f * t;
-    const float worst = fminf(fminf(fminf(ax + by, ax + bz), fminf(ay + bx, ay + bz)), fminf(az + bx, az + by));
-    const float exit_ = t + fminf(fminf(bx, by), bz);
-    const float window = need - fminf(fminf(ax, ay), az);
-    return worst >= need && exit_ >= need && tmax - t > window;
 }
 
 __global__ __launch_bounds__(256) void rq_any_resolve_kernel(SceneView S, QueryView Q) {

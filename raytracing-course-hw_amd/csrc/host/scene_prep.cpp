@@ -423,6 +423,13 @@ uint32_t build_tripwires(const std::vector<TriIsect> &isect, const std::vector<f
 
 } // namespace
 
+TriIsect isect_of_positions(const float *positions9) { return make_isect(tri_frame(positions9)); }
+void walk_box_of(const float lo[3], const float hi[3], float max_coord, float out_lo[3], float out_hi[3]) {
+    Box3 b;
+    for (int k = 0; k < 3; k++) { b.lo[k] = lo[k]; b.hi[k] = hi[k]; }
+    pad_box(b, out_lo, out_hi, scene_abs_pad(max_coord));
+}
+
 // Separation depths of neighbouring lights in a reference light tree + sparse table for range minima (see scene_prep.h).
 static void build_light_sep(const std::vector<RefNode> &rn, uint32_t nl, std::vector<uint16_t> &table, uint32_t &table_levels) {
     std::vector<uint16_t> sep(nl ? nl : 1, 0);

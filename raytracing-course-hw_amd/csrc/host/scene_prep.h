@@ -103,4 +103,9 @@ struct PreparedSceneTxt {
 };
 void prepare_scene_txt(const rt_scene_desc &desc, PreparedSceneTxt &out);
 
+// Two steps of the preparation on their own, for the test hooks: the intersection record of one triangle (data, data2, data3 as nine
+// floats; make_isect) and a box as the walkers' two-box nodes hold it (pad_box with scene_abs_pad of the scene's largest |coordinate|).
+TriIsect isect_of_positions(const float *positions9);
+void walk_box_of(const float lo[3], const float hi[3], float max_coord, float out_lo[3], float out_hi[3]);
+
 } // namespace rtamd

@@ -170,6 +170,53 @@ __global__ void k_stands(const float *in, uint32_t *out, size_t n) { // per case
     out[i] = pt_hit_stands(f3(p[0], p[1], p[2]), f3(p[3], p[4], p[5]), f3(p[6], p[7], p[8]), f3(p[9], p[10], p[11]), p[12], p[13], p[14], 1.25f * p[14], p[15]) ? 1u : 0u;
 }
 
+// The intersection layer, one lane per case (tests/intersection_cases.py has the cases and the row layouts).
+// rt_ref_walk.h ref_box_test.  in: 12 floats (mn, mx, o, d); out: 2 words (1 accepted | 2 inside, the bits of t; 0 for a rejected box)
+__global__ void k_ref_box(const float *in, uint32_t *out, size_t n) {
+    size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float *p = in + 12 * i;
+    float t = 0.f; bool inside = false;
+    const bool ok = ref_box_test(f3(p), f3(p + 3), f3(p + 6), f3(p + 9), t, inside);
+    out[2 * i] = ok ? (1u | (inside ? 2u : 0u)) : 0u;
+    out[2 * i + 1] = ok ? __float_as_uint(t) : 0u;
+}
+// rt_device.h tri_test and tri_test_closer on the host's record of the triangle.  rays: 6 floats (o, d); out: 8 words, for each of the
+// two tests (1 hit | 2 inside) and the bits of t, u, v (0 for a miss)
+__global__ void k_tri(const rtamd::TriIsect *isect, const float *rays, const float *keep_t, uint32_t *out, size_t n) {
+    size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const rtamd::TriIsect T = load_isect(isect + i);
+    const F3 o = f3(rays + 6 * i), d = f3(rays + 6 * i + 3);
+    for (int side = 0; side < 2; side++) {
+        float t = 0.f, u = 0.f, v = 0.f; bool inside = false;
+        const bool hit = side == 0 ? tri_test(T, o, d, t, u, v, inside) : tri_test_closer(T, o, d, keep_t[i], t, u, v, inside);
+        uint32_t *q = out + 8 * i + 4 * side;
+        q[0] = hit ? (1u | (inside ? 2u : 0u)) : 0u;
+        q[1] = hit ? __float_as_uint(t) : 0u; q[2] = hit ? __float_as_uint(u) : 0u; q[3] = hit ? __float_as_uint(v) : 0u;
+    }
+}
+// rt_exact.h pt_box_robust with and without its pretest (bits 1 and 2) and rq_any_hit_stands (bit 4, with tmax in the gap's place), on
+// k_stands's 16 floats
+__global__ void k_robust(const float *in, uint32_t *out, size_t n) {
+    size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float *p = in + 16 * i;
+    const F3 lo = f3(p), hi = f3(p + 3), o = f3(p + 6), d = f3(p + 9);
+    const F3 P = o + p[12] * d;
+    out[i] = (pt_box_robust<true>(lo, hi, P, d, p[12], p[14]) ? 1u : 0u) | (pt_box_robust<false>(lo, hi, P, d, p[12], p[14]) ? 2u : 0u) |
+             (rq_any_hit_stands(lo, hi, o, d, p[12], p[13], p[14]) ? 4u : 0u);
+}
+// rt_device.h slab_test on boxes the host has padded.  boxes: 6 floats (lo, hi), rays: 12 floats, of which o and d are read
+__global__ void k_slab_padded(const float *boxes, const float *in, float tbest, uint32_t *flag, float *tnear, size_t n) {
+    size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float *b = boxes + 6 * i, *p = in + 12 * i;
+    float tn = 0.f;
+    flag[i] = slab_test(make_float4(b[0], b[1], b[2], 0.f), make_float4(b[3], b[4], b[5], 0.f), make_ray_inv(f3(p + 6), f3(p + 9)), tbest, tn) ? 1u : 0u;
+    tnear[i] = tn;
+}
+
 // rt_device.h slab_test_q against slab_test: a box on the walkers' 16-bit grid must be entered by every ray that enters the float box
 __global__ void k_slab_q(const float *in, rtamd::NodeGrid G, uint32_t *out, size_t n) { // per case 13 floats: lo.xyz hi.xyz o.xyz d.xyz tbest
     size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
@@ -409,6 +456,52 @@ int rtt_hit_stands(const float *cases16, uint32_t *out, size_t n) {
     int rc = hipMemcpy(out, d_out, n * 4, hipMemcpyDeviceToHost) == hipSuccess ? 0 : -2;
     (void)hipFree(d_in); (void)hipFree(d_out);
     return rc;
+}
+// The intersection layer (k_ref_box .. k_slab_padded above; rows as documented there).  0, or -1 for a refused argument, -2 when a HIP call fails.
+int rtt_ref_box_test(const float *rows12, uint32_t *out2, size_t n) {
+    if (n == 0) return -1;
+    HookBuf b_in(rows12, n * 12 * 4), b_out(nullptr, n * 2 * 4);
+    if (!b_in.good || !b_out.good) return -2;
+    hipLaunchKernelGGL(k_ref_box, hook_grid(n), dim3(256), 0, 0, b_in.as<float>(), b_out.as<uint32_t>(), n);
+    return hipDeviceSynchronize() == hipSuccess && b_out.back(out2) ? 0 : -2;
+}
+// rows15: positions (data, data2, data3), o, d.  The triangle's record is the host's own (scene_prep.cpp make_isect).
+int rtt_tri_test(const float *rows15, const float *keep_t, uint32_t *out8, size_t n) {
+    if (n == 0) return -1;
+    std::vector<rtamd::TriIsect> isect(n);
+    std::vector<float> rays(n * 6);
+    for (size_t i = 0; i < n; i++) {
+        isect[i] = rtamd::isect_of_positions(rows15 + 15 * i);
+        memcpy(&rays[6 * i], rows15 + 15 * i + 9, 6 * sizeof(float));
+    }
+    HookBuf b_isect(isect.data(), n * sizeof(rtamd::TriIsect)), b_rays(rays.data(), n * 6 * 4), b_keep(keep_t, n * 4), b_out(nullptr, n * 8 * 4);
+    if (!b_isect.good || !b_rays.good || !b_keep.good || !b_out.good) return -2;
+    hipLaunchKernelGGL(k_tri, hook_grid(n), dim3(256), 0, 0, b_isect.as<rtamd::TriIsect>(), b_rays.as<float>(), b_keep.as<float>(), b_out.as<uint32_t>(), n);
+    return hipDeviceSynchronize() == hipSuccess && b_out.back(out8) ? 0 : -2;
+}
+// cases16 as rtt_hit_stands takes them.  rtt_box_robust: bit 1 pt_box_robust<true>, bit 2 pt_box_robust<false> at P = o + t d;
+// rtt_any_hit_stands: rq_any_hit_stands with the row's gap read as tmax.
+static int run_robust(const float *cases16, uint32_t *out, size_t n, uint32_t mask, int shift) {
+    if (n == 0) return -1;
+    HookBuf b_in(cases16, n * 64), b_out(nullptr, n * 4);
+    if (!b_in.good || !b_out.good) return -2;
+    hipLaunchKernelGGL(k_robust, hook_grid(n), dim3(256), 0, 0, b_in.as<float>(), b_out.as<uint32_t>(), n);
+    if (hipDeviceSynchronize() != hipSuccess || !b_out.back(out)) return -2;
+    for (size_t i = 0; i < n; i++) out[i] = (out[i] & mask) >> shift;
+    return 0;
+}
+int rtt_box_robust(const float *cases16, uint32_t *out, size_t n) { return run_robust(cases16, out, n, 3u, 0); }
+int rtt_any_hit_stands(const float *cases16, uint32_t *out, size_t n) { return run_robust(cases16, out, n, 4u, 2); }
+// rows12 as rtt_ref_box_test takes them; every box is padded as a scene whose largest |coordinate| is max_coord pads its walkers' boxes
+// (host/scene_prep.h walk_box_of).  flag: slab_test's answer at tbest (the walkers' RT_T_MAX when it is negative), tnear: its entry distance.
+int rtt_slab_padded(const float *rows12, float max_coord, float tbest, uint32_t *flag, float *tnear, size_t n) {
+    if (n == 0) return -1;
+    std::vector<float> boxes(n * 6);
+    for (size_t i = 0; i < n; i++) rtamd::walk_box_of(rows12 + 12 * i, rows12 + 12 * i + 3, max_coord, &boxes[6 * i], &boxes[6 * i + 3]);
+    HookBuf b_box(boxes.data(), n * 6 * 4), b_in(rows12, n * 12 * 4), b_flag(nullptr, n * 4), b_near(nullptr, n * 4);
+    if (!b_box.good || !b_in.good || !b_flag.good || !b_near.good) return -2;
+    hipLaunchKernelGGL(k_slab_padded, hook_grid(n), dim3(256), 0, 0, b_box.as<float>(), b_in.as<float>(), tbest < 0.f ? RT_T_MAX : tbest, b_flag.as<uint32_t>(), b_near.as<float>(), n);
+    return hipDeviceSynchronize() == hipSuccess && b_flag.back(flag) && b_near.back(tnear) ? 0 : -2;
 }
 int rtt_logf(const float *in, float *out, size_t n) {
     float *d_in = nullptr, *d_out = nullptr;

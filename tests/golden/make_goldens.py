@@ -1,7 +1,8 @@
 """Regenerates tests/golden/pins_*.npz from the compiled reference (oracle/_ref, built where the reference's sources are).
 Run:  python tests/golden/make_goldens.py      (after `make -C oracle`)
       python tests/golden/make_goldens.py orders      only pins_oracle_orders.npz, which comes from the oracle itself
-      python tests/golden/make_goldens.py shading     only pins_shading_edges.npz"""
+      python tests/golden/make_goldens.py shading     only pins_shading_edges.npz
+      python tests/golden/make_goldens.py intersection     only pins_intersection_edges.npz"""
 import ctypes as C
 import os
 import sys
@@ -113,6 +114,16 @@ def main():
     save_reference_crops()
     save_env_uv()
     save_shading_edges()
+    save_intersection_edges()
+
+
+def save_intersection_edges():
+    """The box test and the triangle test at their branch points (tests/intersection_cases.py) through the reference's own AABB::intersect
+    and Figure::intersect.  Outputs only: the inputs are the case table's."""
+    import intersection_cases
+    out = intersection_cases.evaluate("reference")
+    np.savez_compressed(os.path.join(HERE, "pins_intersection_edges.npz"), **{k: out[k] for k in intersection_cases.FAMILIES})
+    print("intersection edges", {k: v.shape for k, v in out.items()})
 
 
 def save_shading_edges():
@@ -168,5 +179,7 @@ if __name__ == "__main__":
         save_oracle_orders()
     elif sys.argv[1:] == ["shading"]:
         save_shading_edges()
+    elif sys.argv[1:] == ["intersection"]:
+        save_intersection_edges()
     else:
         main()

@@ -209,6 +209,18 @@ def env_uv(impl_lib, name, d):
     return uv
 
 
+def intersection_test(impl_lib, name, rows, width):
+    """The box test or the triangle test on its own through impl_lib's `name`(rows, n, flags, out): rto_box_test / rto_tri_test (the
+    oracle) or ref8_box_test / ref8_tri_test (the reference's AABB::intersect / Figure::intersect).  rows: n x 12 (mn, mx, o, d) or n x 15
+    (positions, o, d) float32; returns flags (1 accepted | 2 inside, uint32) and the n x width float32 answers (t; t, tu, tv)."""
+    rows = np.ascontiguousarray(rows, np.float32)
+    flags, out = np.zeros(len(rows), np.uint32), np.zeros((len(rows), width), np.float32)
+    fn = getattr(impl_lib, name)
+    fn.argtypes, fn.restype = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p], None
+    fn(rows.ctypes.data, len(rows), flags.ctypes.data, out.ctypes.data)
+    return flags, out
+
+
 def _setup_hw6(L):
     if getattr(L, "_hw6_ready", False):
         return
