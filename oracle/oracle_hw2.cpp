@@ -190,4 +190,24 @@ int rto_hw2_render(void *p, int width, int height, int ray_depth, int x0, int y0
     }
     return 0;
 }
+
+// Function-level entry points (rows and answers as oracle_txt_prims.h describes them; tests/analytic_cases.py).
+static inline uint32_t word2(float f) { uint32_t u; memcpy(&u, &f, 4); return u; }
+void rto_hw2_quad(const float *abc, size_t n, uint32_t *out) {
+    for (size_t i = 0; i < n; i++) {
+        float t = 0; bool inside = false;
+        const bool ok = smallest_root(abc[3 * i], abc[3 * i + 1], abc[3 * i + 2], t, inside);
+        out[2 * i] = ok ? (1u | (inside ? 2u : 0u)) : 0u; out[2 * i + 1] = ok ? word2(t) : 0u;
+    }
+}
+void rto_hw2_fig(const float *rows, size_t n, uint32_t *out) {
+    for (size_t i = 0; i < n; i++) {
+        const float *r = rows + 24 * i;
+        uint32_t *o = out + 5 * i;
+        const Prim f{(int)r[0], v3(r + 1), v3(r + 10), Quat{v3(r + 13), r[16]}, V3{1, 1, 1}, RT_MAT_DIFFUSE, 1.f};
+        Hit h;
+        memset(o, 0, 20);
+        if (prim_ray(f, v3(r + 17), v3(r + 20), h)) { o[0] = 1u | (h.inside ? 2u : 0u); o[1] = word2(h.t); o[2] = word2(h.norma.x); o[3] = word2(h.norma.y); o[4] = word2(h.norma.z); }
+    }
+}
 }

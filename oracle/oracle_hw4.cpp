@@ -51,10 +51,10 @@ struct Scene4 {
         V3 y2 = x + (float)((double)h1.t + 0.0001 + (double)h2.t) * d;
         return ans + pdf_one(f, x, d, y2, h2.norma);
     }
-    V3 light_sample(Sampler &S, int li, V3 x) const { // each EllipsoidLight draws from its own normal_distribution
+    template <class R = Ray> V3 light_sample(Sampler &S, int li, V3 x, R &&ray = R()) const { // each EllipsoidLight draws from its own normal_distribution
         const Prim &f = figs[lights[li]];
-        if (f.type == RT_PRIM_BOX) return box_emitter_sample(f, S.u01, S.rng, x, Ray());
-        return ellipsoid_emitter_sample(f, S.light_n01[li], S.rng, x, Ray());
+        if (f.type == RT_PRIM_BOX) return box_emitter_sample(f, S.u01, S.rng, x, ray);
+        return ellipsoid_emitter_sample(f, S.light_n01[li], S.rng, x, ray);
     }
     V3 mix_sample(Sampler &S, V3 x, V3 n) const { // Mix::sample :194-197, outer then inner
         size_t comps = lights.empty() ? 1 : 2;
@@ -128,6 +128,73 @@ void *rto_hw4_create(const rt_scene_desc *d) {
 }
 void rto_hw4_destroy(void *p) { delete (Scene4 *)p; }
 int rto_hw4_num_lights(void *p) { return (int)((Scene4 *)p)->lights.size(); }
+
+// Function-level entry points (rows and answers as oracle_txt_prims.h describes them; tests/analytic_cases.py).
+void rto_hw4_fig(const float *rows, size_t n, uint32_t *out) {
+    for (size_t i = 0; i < n; i++) {
+        const float *r = rows + ROW * i;
+        Hit h;
+        put_hit(prim_ray3(prim_of_row(r), v3(r + R_O), v3(r + R_D), h, true), h, out + 5 * i);
+    }
+}
+// FigureLight::pdf of the row's figure as a light, x = o.  out: 1 word
+void rto_hw4_lpdf(const float *rows, size_t n, uint32_t *out) {
+    Scene4 s;
+    for (size_t i = 0; i < n; i++) {
+        const float *r = rows + ROW * i;
+        out[i] = word(s.light_pdf(prim_of_row(r), v3(r + R_O), v3(r + R_D)));
+    }
+}
+// pdfOne(x, d, y, yn) of the row's figure as a light on a y and yn of the row's own (30 floats: the figure row, y 3, yn 3).  out: 1 word
+void rto_hw4_pdf_one(const float *rows30, size_t n, uint32_t *out) {
+    Scene4 s;
+    for (size_t i = 0; i < n; i++) {
+        const float *r = rows30 + 30 * i;
+        out[i] = word(s.pdf_one(prim_of_row(r), v3(r + R_O), v3(r + R_D), v3(r + 24), v3(r + 27)));
+    }
+}
+// One round's point of BoxLight::sample (box_emitter_point, the same lines in hw4 and hw5) for half-sizes s3 and an engine seeded seeds[i].
+// out: 4 words (the point in the box's frame, engine state after)
+void rto_box_face_point(const float *s3, const uint32_t *seeds, size_t n, uint32_t *out) {
+    for (size_t i = 0; i < n; i++) {
+        rng_t rng(seeds[i]);
+        U01 u01(0.0, 1.0);
+        const V3 p = box_emitter_point(v3(s3 + 3 * i), u01, rng);
+        out[4 * i] = word(p.x); out[4 * i + 1] = word(p.y); out[4 * i + 2] = word(p.z); out[4 * i + 3] = state_of(rng);
+    }
+}
+// The light's sample(x), engine seeded aux[0], the light's own normal_distribution primed by aux[1].  out: 8 words (put_sample).  A row
+// that asks the figure more than max_attempts times gets zeros; returns the number of such rows.  attempts (may be null): the figure tests per row.
+int rto_hw4_lsample(const float *rows, const uint32_t *aux, size_t n, uint32_t max_attempts, uint32_t *out, uint32_t *attempts) {
+    int over = 0;
+    for (size_t i = 0; i < n; i++) {
+        const float *r = rows + ROW * i;
+        Scene4 s;
+        s.figs.push_back(prim_of_row(r));
+        s.lights.push_back(0);
+        Sampler S;
+        S.rng.seed(aux[2 * i]);
+        const N01 before = primed(aux[2 * i + 1]);
+        S.light_n01.assign(1, before);
+        CountedRay<Scene4::Ray> ray{Scene4::Ray(), max_attempts};
+        try {
+            const V3 d = s.light_sample(S, 0, v3(r + R_O), ray);
+            put_sample(d, S.rng, S.light_n01[0], before, out + 8 * i);
+        } catch (const TooManyAttempts &) { memset(out + 8 * i, 0, 32); over++; }
+        if (attempts) attempts[i] = max_attempts - ray.left;
+    }
+    return over;
+}
+// Cosine::sample(n), engine seeded aux[0], the Cosine object's normal_distribution primed by aux[1].  out: 8 words (put_sample)
+void rto_hw4_cosine(const float *normals, const uint32_t *aux, size_t n, uint32_t *out) {
+    for (size_t i = 0; i < n; i++) {
+        rng_t rng(aux[2 * i]);
+        const N01 before = primed(aux[2 * i + 1]);
+        N01 n01 = before;
+        const V3 d = cosine_sample(n01, rng, v3(normals + 3 * i));
+        put_sample(d, rng, n01, before, out + 8 * i);
+    }
+}
 
 // seed_mode 0: one engine + one set of distribution objects for the whole call, pixels in row-major order (the reference);
 // seed_mode 1: fresh engine(y*W+x) and fresh distribution objects per pixel (parallel).

@@ -111,8 +111,9 @@ struct Light {
         if (fig.type == RT_PRIM_TRIANGLE) return (double)(pointProb * len2(x - y)) / std::fabs((double)dot(d, yn)); // :117-119
         return ellipsoid_emitter_pdf_one(fig, x, d, y, yn);
     }
-    V3 sample(U01 &u01, N01 &n01, rng_t &rng, V3 x) const {
-        if (fig.type == RT_PRIM_TRIANGLE) {                                  // :129-142
+    typedef bool (*RayFn)(const Fig &, V3, V3, Hit &);
+    template <class R = RayFn> V3 sample(U01 &u01, N01 &n01, rng_t &rng, V3 x, R &&ray = Tree5::hit) const {
+        if (fig.type == RT_PRIM_TRIANGLE) {                                // :129-142
             V3 a = fig.data3, b = fig.data - a, c = fig.data2 - a;
             float u = u01(rng);
             float v = u01(rng);
@@ -120,8 +121,8 @@ struct Light {
             V3 point = fig.position + qtransform(qconj(fig.rotation), a + u * b + v * c);
             return normalize(point - x);
         }
-        if (fig.type == RT_PRIM_BOX) return box_emitter_sample(fig, u01, rng, x, Tree5::hit);
-        return ellipsoid_emitter_sample(fig, n01, rng, x, Tree5::hit);
+        if (fig.type == RT_PRIM_BOX) return box_emitter_sample(fig, u01, rng, x, ray);
+        return ellipsoid_emitter_sample(fig, n01, rng, x, ray);
     }
 };
 
@@ -246,6 +247,66 @@ void rto_hw5_orders(void *p, uint32_t *figure_order, uint32_t *light_order) {
     Scene5 *s = (Scene5 *)p;
     for (size_t i = 0; i < s->figs.size(); i++) figure_order[i] = s->figs[i].load_index;
     for (size_t i = 0; i < s->lights.size(); i++) light_order[i] = s->lights[i].fig.load_index;
+}
+// Function-level entry points (rows and answers as oracle_txt_prims.h describes them; tests/analytic_cases.py).
+static Fig fig_of_row(const float *r) {
+    Fig f;
+    f.type = (int)r[R_TYPE]; f.data = v3(r + R_DATA); f.data2 = v3(r + R_DATA2); f.data3 = v3(r + R_DATA3); f.position = v3(r + R_POS);
+    f.rotation = Quat{v3(r + R_ROT), r[R_ROT + 3]};
+    f.color = V3{1, 1, 1}; f.emission = V3{1, 1, 1}; f.kind = RT_MAT_DIFFUSE; f.ior = 1; f.load_index = 0;
+    return f;
+}
+void rto_hw5_fig(const float *rows, size_t n, uint32_t *out) {
+    for (size_t i = 0; i < n; i++) {
+        const float *r = rows + ROW * i;
+        Hit h;
+        put_hit(fig_ray(fig_of_row(r), v3(r + R_O), v3(r + R_D), h), h, out + 5 * i);
+    }
+}
+// FiguresMix::pdfOneFigureLight of the row's figure as a light, x = o.  out: 1 word
+void rto_hw5_lpdf(const float *rows, size_t n, uint32_t *out) {
+    Scene5 s;
+    for (size_t i = 0; i < n; i++) {
+        const float *r = rows + ROW * i;
+        out[i] = word(s.light_pdf_one(Light(fig_of_row(r)), v3(r + R_O), v3(r + R_D)));
+    }
+}
+// pdfOne(x, d, y, yn) of the row's figure as a light on a y and yn of the row's own (30 floats: the figure row, y 3, yn 3).  out: 1 word
+void rto_hw5_pdf_one(const float *rows30, size_t n, uint32_t *out) {
+    for (size_t i = 0; i < n; i++) {
+        const float *r = rows30 + 30 * i;
+        out[i] = word(Light(fig_of_row(r)).pdf_one(v3(r + R_O), v3(r + R_D), v3(r + 24), v3(r + 27)));
+    }
+}
+// The light's sample(x), engine seeded aux[0], the caller's normal_distribution primed by aux[1].  out: 8 words (put_sample).  A row that
+// asks the figure more than max_attempts times gets zeros; returns the number of such rows.  attempts (may be null): the figure tests per row.
+int rto_hw5_lsample(const float *rows, const uint32_t *aux, size_t n, uint32_t max_attempts, uint32_t *out, uint32_t *attempts) {
+    int over = 0;
+    for (size_t i = 0; i < n; i++) {
+        const float *r = rows + ROW * i;
+        const Light L(fig_of_row(r));
+        rng_t rng(aux[2 * i]);
+        U01 u01(0.0, 1.0);
+        const N01 before = primed(aux[2 * i + 1]);
+        N01 n01 = before;
+        CountedRay<Light::RayFn> ray{Tree5::hit, max_attempts};
+        try {
+            const V3 d = L.sample(u01, n01, rng, v3(r + R_O), ray);
+            put_sample(d, rng, n01, before, out + 8 * i);
+        } catch (const TooManyAttempts &) { memset(out + 8 * i, 0, 32); over++; }
+        if (attempts) attempts[i] = max_attempts - ray.left;
+    }
+    return over;
+}
+// Cosine::sample(n), engine seeded aux[0], the pixel's normal_distribution primed by aux[1].  out: 8 words (put_sample)
+void rto_hw5_cosine(const float *normals, const uint32_t *aux, size_t n, uint32_t *out) {
+    for (size_t i = 0; i < n; i++) {
+        rng_t rng(aux[2 * i]);
+        const N01 before = primed(aux[2 * i + 1]);
+        N01 n01 = before;
+        const V3 d = cosine_sample(n01, rng, v3(normals + 3 * i));
+        put_sample(d, rng, n01, before, out + 8 * i);
+    }
 }
 int rto_hw5_render(void *p, int width, int height, int samples, int ray_depth, int x0, int y0, int w, int h, float *out_rgb, uint8_t *out8, int nthreads) {
     const Scene5 *s = (const Scene5 *)p;

@@ -135,6 +135,34 @@ int rto_hw1_render(void *p, int width, int height, float *out_rgb, uint8_t *out8
     return 0;
 }
 
+// Function-level entry points (rows and answers as oracle_txt_prims.h describes them; tests/analytic_cases.py).
+void rto_hw1_fig(const float *rows, size_t n, uint32_t *out) { // hw1 has no side and no normal: flags 1, t, zeros
+    for (size_t i = 0; i < n; i++) {
+        const float *r = rows + ROW * i;
+        float t = 0;
+        Hit h{0, V3{0, 0, 0}, false};
+        const bool ok = prim_ray1(prim_of_row(r), v3(r + R_O), v3(r + R_D), t);
+        h.t = t;
+        put_hit(ok, h, out + 5 * i);
+    }
+}
+void rto_hw3_quad(const float *abc, size_t n, uint32_t *out) { quad_rows(abc, n, out, smallest_root); }
+void rto_hw3_slabs(const float *rows9, size_t n, uint32_t *out) { // box_local's slab test: s, o, d -> flags, t
+    for (size_t i = 0; i < n; i++) {
+        const float *p = rows9 + 9 * i;
+        Hit h;
+        const bool ok = box_local(v3(p), v3(p + 3), v3(p + 6), h);
+        out[2 * i] = ok ? (1u | (h.inside ? 2u : 0u)) : 0u; out[2 * i + 1] = ok ? word(h.t) : 0u;
+    }
+}
+void rto_hw3_fig(const float *rows, size_t n, uint32_t *out) {
+    for (size_t i = 0; i < n; i++) {
+        const float *r = rows + ROW * i;
+        Hit h;
+        put_hit(prim_ray3(prim_of_row(r), v3(r + R_O), v3(r + R_D), h), h, out + 5 * i);
+    }
+}
+
 // hw3.  seed_mode 0: one engine for the whole frame, pixels in row-major order (the reference, single thread);
 //       seed_mode 1: engine(y*W+x) per pixel (parallel).
 struct Stream3 { rng_t rnd; U01 u01{0.0, 1.0}; N01 n01{0.0, 1.0}; }; // hw3/src/scene.cpp:5-7: default-seeded, shared by everything

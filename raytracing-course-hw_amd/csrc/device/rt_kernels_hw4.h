@@ -82,6 +82,14 @@ RT_DEV F3 cosine_sample_txt(Rng &rng, F3 n) {
     if (l <= 1e-9f || dot(d, n) <= 1e-9f || l != l) return n;
     return (float)(1. / (double)l) * d;
 }
+// BoxLight::sample :125-151 and EllipsoidLight::sample :169-180 of light li, the figure P
+RT_DEV F3 light_sample4(const PrimRegs &P, Rng &rng, LightNormals &N, int li, F3 x) {
+    return light_sample_reject(P, x, [&]() {
+        if (P.type == RT_PRIM_BOX) return box_face_point(rng, P.data);
+        float a = rng_n01_slot(rng, N, li), b = rng_n01_slot(rng, N, li), c = rng_n01_slot(rng, N, li); // each EllipsoidLight its own normal_distribution
+        return P.data * normalize(f3(a, b, c));
+    }, [&](F3 dir) { float t; F3 nn; bool inside; return prim_hit<false, true>(P, x, dir, t, nn, inside); });
+}
 // Mix::sample :194-197 (outer {Cosine, lights}, then the inner light choice)
 RT_DEV F3 mix_sample4(const SceneViewTxt &S, Rng &rng, LightNormals &N, F3 x, F3 n) {
     float comps = S.n_light_prims ? 2.f : 1.f;
@@ -89,11 +97,7 @@ RT_DEV F3 mix_sample4(const SceneViewTxt &S, Rng &rng, LightNormals &N, F3 x, F3
     if (distNum == 0) return cosine_sample_txt(rng, n);
     int li = (int)(rng_u01(rng) * (float)S.n_light_prims);
     PrimRegs P = load_prim(S.prims + S.light_prims[li]);
-    return light_sample_reject(P, x, [&]() {
-        if (P.type == RT_PRIM_BOX) return box_face_point(rng, P.data);
-        float a = rng_n01_slot(rng, N, li), b = rng_n01_slot(rng, N, li), c = rng_n01_slot(rng, N, li); // each EllipsoidLight its own normal_distribution
-        return P.data * normalize(f3(a, b, c));
-    }, [&](F3 dir) { float t; F3 nn; bool inside; return prim_hit<false, true>(P, x, dir, t, nn, inside); });
+    return light_sample4(P, rng, N, li, x);
 }
 // Mix::pdf :199-205
 RT_DEV float mix_pdf4(const SceneViewTxt &S, F3 x, F3 n, F3 d) {
@@ -205,6 +209,7 @@ RT_DEV void camera_ray_float(const SCENE &S, float tan_fov_y, int width, int hei
     d = nx * f3(S.cam_right) - ny * f3(S.cam_up) + f3(S.cam_fwd);
 }
 
+#ifndef RT_DEVICE_FUNCTIONS_ONLY // set by a translation unit that wants the RT_DEV functions above without a second copy of the kernel
 __global__ __launch_bounds__(64) void render_hw4_kernel(SceneViewTxt S, RenderView R, float tan_fov_y, uint32_t n_work) {
     for_each_pixel(R, n_work, [&](int x, int y) {
         LightNormals N;
@@ -217,6 +222,7 @@ __global__ __launch_bounds__(64) void render_hw4_kernel(SceneViewTxt S, RenderVi
         });
     });
 }
+#endif
 
 } // namespace dev
 } // namespace rtamd

@@ -127,13 +127,8 @@ RT_DEV float light_pdf_sum5(const SceneView5 &S, F3 x, F3 d, uint32_t *stack) {
     });
 }
 
-// Mix::sample (distributions.h:283-290) -> Cosine::sample (:43-53) or FiguresMix::sample (:200-209) -> one light's sample
-RT_DEV F3 mix_sample5(const SceneView5 &S, Rng &rng, F3 x, F3 n) {
-    float comps = S.n_lights ? 2.f : 1.f;
-    int distNum = (int)(rng_u01(rng) * comps);
-    if (distNum == 0) return cosine_sample_txt(rng, n);
-    int li = (int)(rng_u01(rng) * (float)S.n_lights);
-    FigRegs F = load_fig5(S.lights + li);
+// One light's sample: TriangleLight, BoxLight or EllipsoidLight of the figure F
+RT_DEV F3 light_sample5(const FigRegs &F, Rng &rng, F3 x) {
     if (F.P.type == RT_PRIM_TRIANGLE) {                                        // TriangleLight::sample :129-142
         F3 a = F.data3, b = F.P.data - a, c = F.data2 - a;
         float u = rng_u01(rng);
@@ -147,6 +142,15 @@ RT_DEV F3 mix_sample5(const SceneView5 &S, Rng &rng, F3 x, F3 n) {
         float a = rng_n01(rng), b = rng_n01(rng), c = rng_n01(rng);
         return F.P.data * normalize(f3(a, b, c));
     }, [&](F3 dir) { float t; F3 nn; bool inside; return fig_hit5(F, x, dir, t, nn, inside); });
+}
+// Mix::sample (distributions.h:283-290) -> Cosine::sample (:43-53) or FiguresMix::sample (:200-209) -> one light's sample
+RT_DEV F3 mix_sample5(const SceneView5 &S, Rng &rng, F3 x, F3 n) {
+    float comps = S.n_lights ? 2.f : 1.f;
+    int distNum = (int)(rng_u01(rng) * comps);
+    if (distNum == 0) return cosine_sample_txt(rng, n);
+    int li = (int)(rng_u01(rng) * (float)S.n_lights);
+    FigRegs F = load_fig5(S.lights + li);
+    return light_sample5(F, rng, x);
 }
 // Mix::pdf :292-302 with FiguresMix::pdf :211-213
 RT_DEV float mix_pdf5(const SceneView5 &S, F3 x, F3 n, F3 d, uint32_t *stack) {
@@ -172,6 +176,7 @@ struct TreePolicy5 {
     }
 };
 
+#ifndef RT_DEVICE_FUNCTIONS_ONLY // set by a translation unit that wants the RT_DEV functions above without a second copy of the kernel
 __global__ __launch_bounds__(64) void render_hw5_kernel(SceneView5 S, RenderView R, float tan_fov_y, uint32_t n_work) {
     uint32_t stack[RT5_STACK];
     for_each_pixel(R, n_work, [&](int x, int y) {
@@ -183,6 +188,7 @@ __global__ __launch_bounds__(64) void render_hw5_kernel(SceneView5 S, RenderView
         });
     });
 }
+#endif
 
 } // namespace dev
 } // namespace rtamd

@@ -124,6 +124,26 @@ RT_DEV void camera_ray_txt(const SceneViewTxt &S, float tan_fov_x, float tan_fov
 }
 
 // ---- hw1 --------------------------------------------------------------------------------------------------------
+// Figure::intersect of hw1 (hw1/src/primitives.cpp:24-91): the distance alone, no side and no normal.
+RT_DEV bool prim_hit1(const PrimRegs &P, F3 o, F3 d, float &t) {
+    F3 to = qtransform(P.rot, o - P.position), td = qtransform(P.rot, d);
+    if (P.type == RT_PRIM_ELLIPSOID) {                                 // hw1/src/primitives.cpp:54-59: b = (2*(o/r)) . (d/r)
+        F3 orr = div3(to, P.data), drr = div3(td, P.data);
+        float c = len2(orr) - 1;
+        float b = dot(2 * orr, drr);
+        float a = len2(drr);
+        bool inside;
+        return smallest_root<true>(a, b, c, t, inside);               // hw1/src/primitives.cpp:33-52, float sqrt
+    }
+    if (P.type == RT_PRIM_PLANE) {                                     // :64-70 (normal not normalised in hw1)
+        t = -dot(to, P.data) / dot(td, P.data);
+        return t > 0;
+    }
+    bool inside;
+    return box_slabs(P.data, to, td, t, inside);
+}
+
+#ifndef RT_DEVICE_FUNCTIONS_ONLY // set by a translation unit that wants the RT_DEV functions above without a second copy of the kernel
 __global__ __launch_bounds__(256) void render_hw1_kernel(SceneViewTxt S, int width, int height, float tan_fov_y, float *out_rgb, uint8_t *out_rgb8) {
     int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= width * height) return;
@@ -134,19 +154,8 @@ __global__ __launch_bounds__(256) void render_hw1_kernel(SceneViewTxt S, int wid
     float best = -1;
     for (uint32_t k = 0; k < S.n_prims; k++) {                         // hw1/src/scene.cpp:10-18
         PrimRegs P = load_prim(S.prims + k);
-        F3 to = qtransform(P.rot, o - P.position), td = qtransform(P.rot, d);
-        float t = 0; bool hit = false;
-        if (P.type == RT_PRIM_ELLIPSOID) {                             // hw1/src/primitives.cpp:54-59: b = (2*(o/r)) . (d/r)
-            F3 orr = div3(to, P.data), drr = div3(td, P.data);
-            float c = len2(orr) - 1;
-            float b = dot(2 * orr, drr);
-            float a = len2(drr);
-            bool inside;
-            hit = smallest_root<true>(a, b, c, t, inside);           // hw1/src/primitives.cpp:33-52, float sqrt
-        } else if (P.type == RT_PRIM_PLANE) {                          // :64-70 (normal not normalised in hw1)
-            t = -dot(to, P.data) / dot(td, P.data);
-            hit = t > 0;
-        } else { bool inside; hit = box_slabs(P.data, to, td, t, inside); }
+        float t = 0;
+        bool hit = prim_hit1(P, o, d, t);
         if (hit && (best == -1 || t < best)) { best = t; ans = P.color; }
     }
     if (out_rgb) { out_rgb[3 * i] = ans.x; out_rgb[3 * i + 1] = ans.y; out_rgb[3 * i + 2] = ans.z; }
@@ -156,6 +165,7 @@ __global__ __launch_bounds__(256) void render_hw1_kernel(SceneViewTxt S, int wid
         out_rgb8[3 * i + 2] = (uint8_t)(int)round((double)(255 * ans.z));
     }
 }
+#endif
 
 // ---- hw3 (Frame3 and RT3_EPS also serve trace_tree, the frame machine of hw4 and hw5 in rt_kernels_hw4.h) ------------------
 #define RT3_MAX_DEPTH 8
@@ -235,6 +245,7 @@ RT_DEV F3 trace_tree3(const SceneViewTxt &S, int ray_depth, Rng &rng, F3 o, F3 d
 #ifndef RT3_MIN_WAVES
 #define RT3_MIN_WAVES 4 // waves per SIMD the register allocation aims at; config 2: 1 -> 14.1 ms, 3 -> 14.3, 4 -> 11.9, 5 -> 12.0, 6 -> 12.2, 8 -> 17.6
 #endif
+#ifndef RT_DEVICE_FUNCTIONS_ONLY // set by a translation unit that wants the RT_DEV functions above without a second copy of the kernel
 __global__ __launch_bounds__(64, RT3_MIN_WAVES) void render_hw3_kernel(SceneViewTxt S, RenderView R, float tan_fov_y, uint32_t n_work) {
     for_each_pixel(R, n_work, [&](int x, int y) {
         return average_samples(R, x, y, [&](Rng &rng, float nx, float ny) {                   // hw3/src/scene.cpp:89-97
@@ -244,6 +255,7 @@ __global__ __launch_bounds__(64, RT3_MIN_WAVES) void render_hw3_kernel(SceneView
         });
     });
 }
+#endif
 
 } // namespace dev
 } // namespace rtamd

@@ -700,6 +700,26 @@ Box3 figure_box5(const rt_primitive &f) {
 }
 } // namespace
 
+GpuFig5 pack_fig5(const rt_primitive &f) {
+    GpuFig5 g;
+    memset(&g, 0, sizeof g);
+    for (int k = 0; k < 3; k++) {
+        g.data[k] = f.data[k]; g.data2[k] = f.data2[k]; g.data3[k] = f.data3[k]; g.position[k] = f.position[k];
+        g.color[k] = f.color[k]; g.emission[k] = f.emission[k];
+    }
+    for (int k = 0; k < 4; k++) g.rotation[k] = f.rotation[k];
+    g.type = f.type; g.kind = f.kind; g.ior = f.ior;
+    return g;
+}
+GpuPrim pack_prim(const rt_primitive &p) {
+    GpuPrim g;
+    memset(&g, 0, sizeof g);
+    for (int k = 0; k < 3; k++) { g.data[k] = p.data[k]; g.position[k] = p.position[k]; g.color[k] = p.color[k]; g.emission[k] = p.emission[k]; }
+    for (int k = 0; k < 4; k++) g.rotation[k] = p.rotation[k];
+    g.type = p.type; g.kind = p.kind; g.ior = p.ior;
+    return g;
+}
+
 void prepare_scene_hw5(const rt_scene_desc &d, PreparedScene5 &out) {
     const uint32_t n = d.n_primitives;
     if (n >= 0x7FFFFFFFu) throw std::runtime_error("too many primitives");
@@ -727,18 +747,7 @@ void prepare_scene_hw5(const rt_scene_desc &d, PreparedScene5 &out) {
     const uint32_t n_lights = (uint32_t)out.light_order.size();
     const std::vector<uint32_t> scene_leaf_last = encode_both(scene_tree, 0.f, out.nodes, out.ref_nodes, out.bvh_depth);
     const std::vector<uint32_t> light_leaf_last = encode_both(light_tree, 0.f, out.light_nodes, out.ref_light_nodes, out.light_bvh_depth);
-    auto make = [&](uint32_t src) {
-        const rt_primitive &f = d.primitives[src];
-        GpuFig5 g;
-        memset(&g, 0, sizeof g);
-        for (int k = 0; k < 3; k++) {
-            g.data[k] = f.data[k]; g.data2[k] = f.data2[k]; g.data3[k] = f.data3[k]; g.position[k] = f.position[k];
-            g.color[k] = f.color[k]; g.emission[k] = f.emission[k];
-        }
-        for (int k = 0; k < 4; k++) g.rotation[k] = f.rotation[k];
-        g.type = f.type; g.kind = f.kind; g.ior = f.ior;
-        return g;
-    };
+    auto make = [&](uint32_t src) { return pack_fig5(d.primitives[src]); };
     fill_records(out.figs, n, [&](uint32_t i) { return make(order[i]); });
     mark_leaf_ends(scene_leaf_last, [&](uint32_t i) -> uint32_t & { return out.figs[i].last; });
     fill_records(out.lights, n_lights, [&](uint32_t i) { return make(out.light_order[i]); });
@@ -750,12 +759,9 @@ void prepare_scene_txt(const rt_scene_desc &d, PreparedSceneTxt &out) {
     out.prims.resize(d.n_primitives);
     for (uint32_t i = 0; i < d.n_primitives; i++) {
         const rt_primitive &p = d.primitives[i];
-        GpuPrim &g = out.prims[i];
         if (p.type < RT_PRIM_ELLIPSOID || p.type > RT_PRIM_TRIANGLE) throw std::runtime_error("rt_scene_create: bad primitive type");
         if (p.type == RT_PRIM_TRIANGLE) out.has_triangles = true;
-        for (int k = 0; k < 3; k++) { g.data[k] = p.data[k]; g.position[k] = p.position[k]; g.color[k] = p.color[k]; g.emission[k] = p.emission[k]; }
-        for (int k = 0; k < 4; k++) g.rotation[k] = p.rotation[k];
-        g.type = p.type; g.kind = p.kind; g.ior = p.ior;
+        out.prims[i] = pack_prim(p);
         if ((p.emission[0] > 0 || p.emission[1] > 0 || p.emission[2] > 0) && (p.type == RT_PRIM_BOX || p.type == RT_PRIM_ELLIPSOID)) out.light_prims.push_back(i);
     }
     out.lights.resize(d.n_lights);

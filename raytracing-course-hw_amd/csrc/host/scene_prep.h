@@ -105,7 +105,10 @@ void prepare_scene_txt(const rt_scene_desc &desc, PreparedSceneTxt &out);
 
 // Two steps of the preparation on their own, for the test hooks: the intersection record of one triangle (data, data2, data3 as nine
 // floats; make_isect) and a box as the walkers' two-box nodes hold it (pad_box with scene_abs_pad of the scene's largest |coordinate|).
+// Also the records of one .txt figure as prepare_scene_txt and prepare_scene_hw5 pack them (material and leaf mark aside).
 TriIsect isect_of_positions(const float *positions9);
+GpuPrim pack_prim(const rt_primitive &p);
+GpuFig5 pack_fig5(const rt_primitive &p);
 void walk_box_of(const float lo[3], const float hi[3], float max_coord, float out_lo[3], float out_hi[3]);
 
 } // namespace rtamd

@@ -2,8 +2,11 @@
 // device functions of rt_device.h on the GPU so tests can compare them with the host libm / libstdc++, and the on-device tree builder
 // on boxes of the test's own so its tree can be read back.
 #include <hip/hip_runtime.h>
+#include "../../include/rtamd.h"
 #include "device/rt_device.h"
 #include "device/rt_exact.h"
+#define RT_DEVICE_FUNCTIONS_ONLY // the hooks call the device functions of the .txt kernels; the kernels themselves stay the library's alone
+#include "device/rt_kernels_hw5.h"
 #include "device/rt_kernels_hw8.h"
 #include "device/rt_node_grid.h"
 #include "device/rt_pt_queue.h"
@@ -215,6 +218,134 @@ __global__ void k_slab_padded(const float *boxes, const float *in, float tbest, 
     float tn = 0.f;
     flag[i] = slab_test(make_float4(b[0], b[1], b[2], 0.f), make_float4(b[3], b[4], b[5], 0.f), make_ray_inv(f3(p + 6), f3(p + 9)), tbest, tn) ? 1u : 0u;
     tnear[i] = tn;
+}
+
+// The analytic layer of the .txt snapshots, one lane per case (tests/analytic_cases.py has the cases and the row layouts).  A hit is 5 words:
+// 1 hit | 2 inside, the bits of t and of the normal; all 0 for a miss.
+__device__ inline void put_hit(bool ok, bool inside, float t, F3 n, uint32_t *o) {
+    o[0] = ok ? (1u | (inside ? 2u : 0u)) : 0u;
+    o[1] = ok ? __float_as_uint(t) : 0u; o[2] = ok ? __float_as_uint(n.x) : 0u; o[3] = ok ? __float_as_uint(n.y) : 0u; o[4] = ok ? __float_as_uint(n.z) : 0u;
+}
+// rt_kernels_txt.h smallest_root<true> (hw1 / hw2) and <false> (hw3+).  in: a, b, c; out: 2 words each (flags, t)
+__global__ void k_quad(const float *in, uint32_t *out, size_t n) {
+    size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float *p = in + 3 * i;
+    float t = 0.f; bool inside = false;
+    bool ok = smallest_root<true>(p[0], p[1], p[2], t, inside);
+    out[4 * i] = ok ? (1u | (inside ? 2u : 0u)) : 0u; out[4 * i + 1] = ok ? __float_as_uint(t) : 0u;
+    t = 0.f; inside = false;
+    ok = smallest_root<false>(p[0], p[1], p[2], t, inside);
+    out[4 * i + 2] = ok ? (1u | (inside ? 2u : 0u)) : 0u; out[4 * i + 3] = ok ? __float_as_uint(t) : 0u;
+}
+// box_slabs.  in: s, o, d; out: 2 words (flags, t)
+__global__ void k_slabs(const float *in, uint32_t *out, size_t n) {
+    size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float *p = in + 9 * i;
+    float t = 0.f; bool inside = false;
+    const bool ok = box_slabs(f3(p), f3(p + 3), f3(p + 6), t, inside);
+    out[2 * i] = ok ? (1u | (inside ? 2u : 0u)) : 0u; out[2 * i + 1] = ok ? __float_as_uint(t) : 0u;
+}
+// The figure test of each snapshot on the host's own records: prim_hit1 (hw1; no side, no normal), prim_hit<true> (hw2), prim_hit<false> (hw3),
+// prim_hit<false, true> (hw4) on the GpuPrim, fig_hit5 (hw5) on the GpuFig5.  rays: o, d; out: 5 hits
+__global__ void k_fig(const rtamd::GpuPrim *prims, const rtamd::GpuFig5 *figs, const float *rays, uint32_t *out, size_t n) {
+    size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const PrimRegs P = load_prim(prims + i);
+    const FigRegs F = load_fig5(figs + i);
+    const F3 o = f3(rays + 6 * i), d = f3(rays + 6 * i + 3), zero = f3(0.f, 0.f, 0.f);
+    uint32_t *q = out + 25 * i;
+    float t = 0.f; F3 nn = zero; bool inside = false;
+    bool ok = prim_hit1(P, o, d, t);
+    put_hit(ok, false, t, zero, q);
+    t = 0.f; nn = zero; inside = false;
+    ok = prim_hit<true>(P, o, d, t, nn, inside); put_hit(ok, inside, t, nn, q + 5);
+    t = 0.f; nn = zero; inside = false;
+    ok = prim_hit<false>(P, o, d, t, nn, inside); put_hit(ok, inside, t, nn, q + 10);
+    t = 0.f; nn = zero; inside = false;
+    ok = prim_hit<false, true>(P, o, d, t, nn, inside); put_hit(ok, inside, t, nn, q + 15);
+    t = 0.f; nn = zero; inside = false;
+    ok = fig_hit5(F, o, d, t, nn, inside); put_hit(ok, inside, t, nn, q + 20);
+}
+// light_pdf4 (box and ellipsoid figures) and light_pdf_one5.  rays: x, d; out: 2 words
+__global__ void k_lpdf(const rtamd::GpuPrim *prims, const rtamd::GpuFig5 *figs, const float *rays, uint32_t *out, size_t n) {
+    size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const PrimRegs P = load_prim(prims + i);
+    const FigRegs F = load_fig5(figs + i);
+    const F3 x = f3(rays + 6 * i), d = f3(rays + 6 * i + 3);
+    out[2 * i] = P.type == RT_PRIM_TRIANGLE ? 0u : __float_as_uint(light_pdf4(P, x, d));
+    out[2 * i + 1] = __float_as_uint(light_pdf_one5(F, x, d));
+}
+// pdf_one4 (box and ellipsoid figures) and pdf_one5 on a y and yn of the case's own.  pts: x, d, y, yn; out: 2 words
+__global__ void k_pdf_one(const rtamd::GpuPrim *prims, const rtamd::GpuFig5 *figs, const float *pts, uint32_t *out, size_t n) {
+    size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const PrimRegs P = load_prim(prims + i);
+    const FigRegs F = load_fig5(figs + i);
+    const float *p = pts + 12 * i;
+    const F3 x = f3(p), d = f3(p + 3), y = f3(p + 6), yn = f3(p + 9);
+    out[2 * i] = P.type == RT_PRIM_TRIANGLE ? 0u : __float_as_uint(pdf_one4(P, x, d, y, yn));
+    out[2 * i + 1] = __float_as_uint(pdf_one5(F, x, d, y, yn));
+}
+// box_face_point.  in: the half-sizes; out: 4 words (the point in the box's frame, engine state after); the normal cache must stay as it was
+__global__ void k_face_point(const float *in, const uint32_t *seeds, uint32_t *out, size_t n) {
+    size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    Rng rng;
+    rng_seed(rng, seeds[i]);
+    const F3 p = box_face_point(rng, f3(in + 3 * i));
+    out[4 * i] = __float_as_uint(p.x); out[4 * i + 1] = __float_as_uint(p.y); out[4 * i + 2] = __float_as_uint(p.z); out[4 * i + 3] = rng.x;
+}
+#define HOOK_SENTINEL 12345.f
+// light_sample4 as light number i % 32 of a pixel whose other normal caches (Cosine's and the other lights') all hold a sentinel, and
+// light_sample5 with the pixel's one cache.  aux: seed, whether the cache holds a value, its bits.  out: 13 words: hw4 direction 3, engine
+// state, the light's cache 2, 1 when every other cache still holds the sentinel; hw5 direction 3, engine state, cache 2
+__global__ void k_lsample(const rtamd::GpuPrim *prims, const rtamd::GpuFig5 *figs, const float *xs, const uint32_t *aux, uint32_t *out, size_t n) {
+    size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const PrimRegs P = load_prim(prims + i);
+    const FigRegs F = load_fig5(figs + i);
+    const F3 x = f3(xs + 3 * i);
+    const uint32_t seed = aux[3 * i], has = aux[3 * i + 1];
+    const float saved = __uint_as_float(aux[3 * i + 2]);
+    uint32_t *q = out + 13 * i;
+    for (int k = 0; k < 13; k++) q[k] = 0u;
+    Rng rng;
+    if (P.type != RT_PRIM_TRIANGLE) {
+        const int li = (int)(i % RT4_MAX_LIGHTS);
+        LightNormals N;
+        for (int k = 0; k < RT4_MAX_LIGHTS; k++) N.saved[k] = HOOK_SENTINEL;
+        N.has = 0xffffffffu;
+        N.saved[li] = saved;
+        if (!has) N.has &= ~(1u << li);
+        rng_seed(rng, seed);
+        rng.saved = HOOK_SENTINEL; rng.has_saved = true;
+        const F3 d = light_sample4(P, rng, N, li, x);
+        q[0] = __float_as_uint(d.x); q[1] = __float_as_uint(d.y); q[2] = __float_as_uint(d.z); q[3] = rng.x;
+        q[4] = (N.has >> li) & 1u; q[5] = q[4] ? __float_as_uint(N.saved[li]) : 0u;
+        bool intact = rng.has_saved && rng.saved == HOOK_SENTINEL;
+        for (int k = 0; k < RT4_MAX_LIGHTS; k++) if (k != li) intact = intact && ((N.has >> k) & 1u) && N.saved[k] == HOOK_SENTINEL;
+        q[6] = intact ? 1u : 0u;
+    }
+    rng_seed(rng, seed);
+    rng.saved = saved; rng.has_saved = has != 0u;
+    const F3 d = light_sample5(F, rng, x);
+    q[7] = __float_as_uint(d.x); q[8] = __float_as_uint(d.y); q[9] = __float_as_uint(d.z); q[10] = rng.x;
+    q[11] = rng.has_saved ? 1u : 0u; q[12] = rng.has_saved ? __float_as_uint(rng.saved) : 0u;
+}
+// cosine_sample_txt.  in: the normal; aux as k_lsample; out: 6 words (direction 3, engine state, cache 2)
+__global__ void k_cosine_txt(const float *in, const uint32_t *aux, uint32_t *out, size_t n) {
+    size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    Rng rng;
+    rng_seed(rng, aux[3 * i]);
+    rng.saved = __uint_as_float(aux[3 * i + 2]); rng.has_saved = aux[3 * i + 1] != 0u;
+    const F3 d = cosine_sample_txt(rng, f3(in + 3 * i));
+    uint32_t *q = out + 6 * i;
+    q[0] = __float_as_uint(d.x); q[1] = __float_as_uint(d.y); q[2] = __float_as_uint(d.z); q[3] = rng.x;
+    q[4] = rng.has_saved ? 1u : 0u; q[5] = rng.has_saved ? __float_as_uint(rng.saved) : 0u;
 }
 
 // rt_device.h slab_test_q against slab_test: a box on the walkers' 16-bit grid must be entered by every ray that enters the float box
@@ -502,6 +633,96 @@ int rtt_slab_padded(const float *rows12, float max_coord, float tbest, uint32_t 
     if (!b_box.good || !b_in.good || !b_flag.good || !b_near.good) return -2;
     hipLaunchKernelGGL(k_slab_padded, hook_grid(n), dim3(256), 0, 0, b_box.as<float>(), b_in.as<float>(), tbest < 0.f ? RT_T_MAX : tbest, b_flag.as<uint32_t>(), b_near.as<float>(), n);
     return hipDeviceSynchronize() == hipSuccess && b_flag.back(flag) && b_near.back(tnear) ? 0 : -2;
+}
+// The analytic layer (k_quad .. k_cosine_txt above).  rows24: type, data, data2, data3, position, rotation (x y z w), o, d, one unused; the
+// device records are the host's own (scene_prep.cpp pack_prim / pack_fig5), so load_prim / load_fig5 and the layouts are under test too.
+int rtt_quad(const float *abc, uint32_t *out4, size_t n) {
+    if (n == 0) return -1;
+    HookBuf b_in(abc, n * 3 * 4), b_out(nullptr, n * 4 * 4);
+    if (!b_in.good || !b_out.good) return -2;
+    hipLaunchKernelGGL(k_quad, hook_grid(n), dim3(256), 0, 0, b_in.as<float>(), b_out.as<uint32_t>(), n);
+    return hipDeviceSynchronize() == hipSuccess && b_out.back(out4) ? 0 : -2;
+}
+int rtt_slabs(const float *rows9, uint32_t *out2, size_t n) {
+    if (n == 0) return -1;
+    HookBuf b_in(rows9, n * 9 * 4), b_out(nullptr, n * 2 * 4);
+    if (!b_in.good || !b_out.good) return -2;
+    hipLaunchKernelGGL(k_slabs, hook_grid(n), dim3(256), 0, 0, b_in.as<float>(), b_out.as<uint32_t>(), n);
+    return hipDeviceSynchronize() == hipSuccess && b_out.back(out2) ? 0 : -2;
+}
+namespace {
+struct FigureRows {
+    std::vector<rtamd::GpuPrim> prims;
+    std::vector<rtamd::GpuFig5> figs;
+    std::vector<float> rays, xs;
+    bool ok = true;
+    FigureRows(const float *rows, size_t n, size_t stride = 24) : prims(n), figs(n), rays(n * 6), xs(n * 3) {
+        for (size_t i = 0; i < n; i++) {
+            const float *r = rows + stride * i;
+            rt_primitive p;
+            memset(&p, 0, sizeof p);
+            p.type = (int32_t)r[0];
+            if (p.type < RT_PRIM_ELLIPSOID || p.type > RT_PRIM_TRIANGLE) { ok = false; return; }
+            for (int k = 0; k < 3; k++) { p.data[k] = r[1 + k]; p.data2[k] = r[4 + k]; p.data3[k] = r[7 + k]; p.position[k] = r[10 + k]; p.color[k] = 1.f; p.emission[k] = 1.f; }
+            for (int k = 0; k < 4; k++) p.rotation[k] = r[13 + k];
+            p.kind = RT_MAT_DIFFUSE; p.ior = 1.f;
+            prims[i] = rtamd::pack_prim(p);
+            figs[i] = rtamd::pack_fig5(p);
+            memcpy(&rays[6 * i], r + 17, 6 * sizeof(float));
+            memcpy(&xs[3 * i], r + 17, 3 * sizeof(float));
+        }
+    }
+};
+}
+// which: 0 k_fig (out: 25 words per row), 1 k_lpdf (2 words)
+static int run_figure_rows(int which, const float *rows24, uint32_t *out, size_t n) {
+    if (n == 0) return -1;
+    const FigureRows R(rows24, n);
+    if (!R.ok) return -1;
+    const size_t width = which == 0 ? 25 : 2;
+    HookBuf b_prims(R.prims.data(), n * sizeof(rtamd::GpuPrim)), b_figs(R.figs.data(), n * sizeof(rtamd::GpuFig5)), b_rays(R.rays.data(), n * 6 * 4), b_out(nullptr, n * width * 4);
+    if (!b_prims.good || !b_figs.good || !b_rays.good || !b_out.good) return -2;
+    if (which == 0) hipLaunchKernelGGL(k_fig, hook_grid(n), dim3(256), 0, 0, b_prims.as<rtamd::GpuPrim>(), b_figs.as<rtamd::GpuFig5>(), b_rays.as<float>(), b_out.as<uint32_t>(), n);
+    else hipLaunchKernelGGL(k_lpdf, hook_grid(n), dim3(256), 0, 0, b_prims.as<rtamd::GpuPrim>(), b_figs.as<rtamd::GpuFig5>(), b_rays.as<float>(), b_out.as<uint32_t>(), n);
+    return hipDeviceSynchronize() == hipSuccess && b_out.back(out) ? 0 : -2;
+}
+int rtt_fig(const float *rows24, uint32_t *out25, size_t n) { return run_figure_rows(0, rows24, out25, n); }
+int rtt_lpdf(const float *rows24, uint32_t *out2, size_t n) { return run_figure_rows(1, rows24, out2, n); }
+// rows30: a figure row with x = o and d, then y 3, yn 3
+int rtt_pdf_one(const float *rows30, uint32_t *out2, size_t n) {
+    if (n == 0) return -1;
+    const FigureRows R(rows30, n, 30);
+    if (!R.ok) return -1;
+    std::vector<float> pts(n * 12);
+    for (size_t i = 0; i < n; i++) { memcpy(&pts[12 * i], rows30 + 30 * i + 17, 6 * sizeof(float)); memcpy(&pts[12 * i + 6], rows30 + 30 * i + 24, 6 * sizeof(float)); }
+    HookBuf b_prims(R.prims.data(), n * sizeof(rtamd::GpuPrim)), b_figs(R.figs.data(), n * sizeof(rtamd::GpuFig5)), b_pts(pts.data(), n * 12 * 4), b_out(nullptr, n * 2 * 4);
+    if (!b_prims.good || !b_figs.good || !b_pts.good || !b_out.good) return -2;
+    hipLaunchKernelGGL(k_pdf_one, hook_grid(n), dim3(256), 0, 0, b_prims.as<rtamd::GpuPrim>(), b_figs.as<rtamd::GpuFig5>(), b_pts.as<float>(), b_out.as<uint32_t>(), n);
+    return hipDeviceSynchronize() == hipSuccess && b_out.back(out2) ? 0 : -2;
+}
+// aux3: seed, whether the normal cache holds a value, its bits.  x = the row's o.
+int rtt_lsample(const float *rows24, const uint32_t *aux3, uint32_t *out13, size_t n) {
+    if (n == 0) return -1;
+    const FigureRows R(rows24, n);
+    if (!R.ok) return -1;
+    HookBuf b_prims(R.prims.data(), n * sizeof(rtamd::GpuPrim)), b_figs(R.figs.data(), n * sizeof(rtamd::GpuFig5)), b_xs(R.xs.data(), n * 3 * 4), b_aux(aux3, n * 3 * 4), b_out(nullptr, n * 13 * 4);
+    if (!b_prims.good || !b_figs.good || !b_xs.good || !b_aux.good || !b_out.good) return -2;
+    hipLaunchKernelGGL(k_lsample, hook_grid(n), dim3(256), 0, 0, b_prims.as<rtamd::GpuPrim>(), b_figs.as<rtamd::GpuFig5>(), b_xs.as<float>(), b_aux.as<uint32_t>(), b_out.as<uint32_t>(), n);
+    return hipDeviceSynchronize() == hipSuccess && b_out.back(out13) ? 0 : -2;
+}
+int rtt_face_point(const float *s3, const uint32_t *seeds, uint32_t *out4, size_t n) {
+    if (n == 0) return -1;
+    HookBuf b_in(s3, n * 3 * 4), b_seed(seeds, n * 4), b_out(nullptr, n * 4 * 4);
+    if (!b_in.good || !b_seed.good || !b_out.good) return -2;
+    hipLaunchKernelGGL(k_face_point, hook_grid(n), dim3(256), 0, 0, b_in.as<float>(), b_seed.as<uint32_t>(), b_out.as<uint32_t>(), n);
+    return hipDeviceSynchronize() == hipSuccess && b_out.back(out4) ? 0 : -2;
+}
+int rtt_cosine_txt(const float *normals, const uint32_t *aux3, uint32_t *out6, size_t n) {
+    if (n == 0) return -1;
+    HookBuf b_in(normals, n * 3 * 4), b_aux(aux3, n * 3 * 4), b_out(nullptr, n * 6 * 4);
+    if (!b_in.good || !b_aux.good || !b_out.good) return -2;
+    hipLaunchKernelGGL(k_cosine_txt, hook_grid(n), dim3(256), 0, 0, b_in.as<float>(), b_aux.as<uint32_t>(), b_out.as<uint32_t>(), n);
+    return hipDeviceSynchronize() == hipSuccess && b_out.back(out6) ? 0 : -2;
 }
 int rtt_logf(const float *in, float *out, size_t n) {
     float *d_in = nullptr, *d_out = nullptr;

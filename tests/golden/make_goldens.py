@@ -2,7 +2,8 @@
 Run:  python tests/golden/make_goldens.py      (after `make -C oracle`)
       python tests/golden/make_goldens.py orders      only pins_oracle_orders.npz, which comes from the oracle itself
       python tests/golden/make_goldens.py shading     only pins_shading_edges.npz
-      python tests/golden/make_goldens.py intersection     only pins_intersection_edges.npz"""
+      python tests/golden/make_goldens.py intersection     only pins_intersection_edges.npz
+      python tests/golden/make_goldens.py analytic     only pins_analytic_edges.npz"""
 import ctypes as C
 import os
 import sys
@@ -115,6 +116,16 @@ def main():
     save_env_uv()
     save_shading_edges()
     save_intersection_edges()
+    save_analytic_edges()
+
+
+def save_analytic_edges():
+    """The analytic figures, the light pdf and the samplers of hw1 .. hw5 at their branch points (tests/analytic_cases.py) through each
+    snapshot's own Figure::intersect, root function, FigureLight::pdf and sample().  Outputs only: the inputs are the case table's."""
+    import analytic_cases
+    out = analytic_cases.evaluate("reference")
+    np.savez_compressed(os.path.join(HERE, "pins_analytic_edges.npz"), **{k: out[k] for k in analytic_cases.FAMILIES})
+    print("analytic edges", {k: v.shape for k, v in out.items()})
 
 
 def save_intersection_edges():
@@ -181,5 +192,7 @@ if __name__ == "__main__":
         save_shading_edges()
     elif sys.argv[1:] == ["intersection"]:
         save_intersection_edges()
+    elif sys.argv[1:] == ["analytic"]:
+        save_analytic_edges()
     else:
         main()

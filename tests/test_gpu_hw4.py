@@ -10,20 +10,20 @@ import pin_cases
 pytestmark = pytest.mark.gpu
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 TXT = os.path.join(GOLD, "scenes", "txt")
-RMSE_TOL = 1e-3
 
 
 @pytest.mark.parametrize("name", pin_cases.HW4_CASES)
 def test_hw4_matches_oracle_with_per_pixel_seeds(rt, name):
     """Same per-pixel minstd_rand(y*W+x) streams and per-object normal caches on both sides: cosine / box-light /
-    ellipsoid-light sampling, the two-hit light pdf, dielectric recursion.  Tolerance 1e-3 RMSE; in practice bit-exact."""
+    ellipsoid-light sampling, the two-hit light pdf, dielectric recursion.  Bit for bit: every function beneath is pinned to the
+    reference at its edges (test_gpu_analytic.py), and the frame is the same arithmetic in the same order."""
     sd, w, h, spp, depth = rt.load_txt(os.path.join(TXT, name + ".txt"), rt.RT_INTEGRATOR_HW4)
     scene = rt.Scene(sd)
     rgb, rgb8, _ = scene.render(w, h, spp, integrator=rt.RT_INTEGRATOR_HW4, ray_depth=depth)
     ref, ref8 = oracle_lib.Hw4Oracle(sd).render(w, h, spp, depth, per_pixel_seed=True)
     rmse = float(np.sqrt(np.mean((rgb.astype(np.float64) - ref) ** 2)))
     print(f"hw4 {name}: rmse {rmse:.3e} bit_exact {np.array_equal(rgb, ref)} byte_mismatch {(rgb8 != ref8).sum()}")
-    assert ref.mean() > 0.01 and rmse < RMSE_TOL
+    assert ref.mean() > 0.01 and np.array_equal(rgb, ref) and np.array_equal(rgb8, ref8)
     scene.close()
 
 
