@@ -556,6 +556,83 @@ int rt_render_guides(rt_scene *scene, int32_t width, int32_t height, uint32_t fl
                      float *albedo /* W*H*3 */, float *normal /* W*H*3 */, float *depth /* W*H */, float *emission /* W*H*3 */,
                      rt_query_stats *stats /* nullable */);
 
+/* ---- the bounce step: scatter queries and rt_trace_paths ---------------------------------------------------------------------
+ * What Scene::getColor DECIDES at a hit (hw8/src/scene.cpp:151-164), for a caller with an integrator of its own -- a light-map or
+ * probe baker, another camera model, a path debugger, next-event estimation: Mix::sample, MaterialModel::brdf, Mix::pdf, the weight
+ * and the two early returns, with the device functions the renders use (device/rt_query_scatter.h) and bit for bit the reference's
+ * answers.  With the queries above, a frame folded from public calls only -- camera ray, closest, surface / environment, scatter,
+ * repeated -- is rt_render's frame word for word.  Same scenes, refusals, chunks (RTAMD_QUERY_CHUNK) and n == 0 as
+ * rt_query_surface.  Offered: hw8's rules only.  Not offered: hw7's brdf and light pdf, the throughput-mode options (sample streams,
+ * Russian roulette).  ABI version 6 still.
+ *
+ * rt_rng   the engine of a path as a record: x the state of std::minstd_rand, saved / has_saved the second value of
+ *          std::normal_distribution<float> -- what an rt_accum checkpoint stores per pixel slot.  rt_rng_seed is minstd_rand::seed
+ *          (seed mod (2^31-1), 0 -> 1, no saved value), rt_rng_uniform one draw of uniform_real_distribution<float>(0, 1) on it
+ *          (float(x' - 1) * 2^-31, kept below 1); both run on the host and need no GPU: a caller replays getPixel's two jitter draws
+ *          with them before rt_camera_rays.  A state with x == 0 or x >= 2147483647 is one the engine never has, and the normal
+ *          distribution's rejection loop would never leave it: host arrays are checked before any launch (RT_ERR_INVALID_ARG, the
+ *          message names the record), a record from device memory is marked RT_SCATTER_INVALID and never sampled.  A record comes
+ *          back with saved = 0 whenever has_saved is 0; reserved is handed through.
+ *
+ * rt_query_scatter   one bounce, per record i from rays[i] (the ray that hit), hits[i] (t and ng are read, triangle only compared
+ *          with 0xFFFFFFFF), surfaces[i] (every field but material, which is only compared with 0xFFFFFFFF) and rng[i].  No index of
+ *          a caller's record is dereferenced; the scene is read at the light the engine picks and in the light tree, nowhere else.
+ *            x = o + t*d;  out.o = x + eps*ng, eps = (float)1e-4L                                           scene.cpp:104, :151
+ *            component = (int)(u01 * (2 + (lights ? 1 : 0)));  out.d = cosine (0), vndf (1) or light (2) sample   distributions.h:256-265
+ *            brdf = MaterialModel(base_metallic, base_color).brdf(out.d, -d, sn, color, metallic, alpha)     :153
+ *            every brdf channel < eps: RT_SCATTER_END_BRDF                                                    :154-156
+ *            pdf = (cosine pdf + vndf pdf (+ light pdf of (out.o, out.d))) / components                        distributions.h:267-279
+ *            weight = (float)(1. / pdf * fabs(out.d . sn)) * brdf                                             :159
+ *            a weight channel > 6 or a NaN: RT_SCATTER_END_CLAMP                                              :161-163
+ *          A path that ends returns the surface's emission; one that goes on has L = emission + weight * L(out.o, out.d)  (:164).
+ *          NaNs in a record flow through the arithmetic as in the reference and normally end in RT_SCATTER_END_CLAMP.  The engine is
+ *          written back after its draws, for an ended record too: it has drawn.  A record is judged in this order: no surface
+ *          (RT_SCATTER_NO_SURFACE), then invalid (RT_SCATTER_INVALID); both answer zeros and leave the engine as it was.
+ *          Launches per chunk: the sample kernel, on a scene with lights rt_query_light_pdf's launches over (out.o, out.d) -- records
+ *          that need no walk ride along as invalid rays, which no walker touches and invalid_rays does not count --, the finish kernel.
+ *          flags: RT_QUERY_DEVICE_POINTERS (all five arrays are device memory; rt_hit, rt_surface, rt_rng and rt_scatter 16-byte
+ *          aligned, rays 4-byte) and RT_QUERY_REFERENCE_WALK (handed to the light walk; the same bits).  stats.exact_walks: light walks
+ *          answered by the reference-order walk; invalid_rays: RT_SCATTER_INVALID records.
+ * rt_query_bsdf      the two evaluations for directions of the caller's own: out_brdf = brdf(dirs[i], -d, sn, ...), out_pdf = the full
+ *          Mix::pdf of dirs[i] at out.o; the pdf is always evaluated.  It is rt_query_scatter's finish kernel: on a scatter's own d
+ *          both equal the scatter's words wherever it evaluated them.  No-surface and invalid records (also: a non-finite or zero
+ *          dirs[i]) answer zeros.  With RT_QUERY_DEVICE_POINTERS dirs, out_brdf and out_pdf are 4-byte aligned.
+ * rt_trace_paths     Scene::getColor(ray, ray_depth) for rays and engines of the caller's own.  Per bounce, on the device, chunk by
+ *          chunk: rt_query_closest; a miss ends the path with rt_query_environment's colour; rt_query_surface; rt_query_scatter; an
+ *          RT_SCATTER_END_* ends it with the emission; else e[b] = emission, m[b] = weight and the ray becomes (o, d).  After
+ *          ray_depth bounces (0 = 6; above 16: RT_ERR_LIMIT, as rt_render) the tail is 0; then L = e[b] + m[b] * L backwards, two
+ *          roundings per channel.  Radiance and engine afterwards equal that composition of the public calls bit for bit, hence
+ *          rt_render's sample.  An invalid ray answers 0, 0, 0 with its engine untouched and is counted.  Ended paths ride along as
+ *          invalid rays until the depth is spent: nothing is compacted.  The per-bounce stack is 24 bytes x depth + 16 bytes per
+ *          path of a chunk (37 MB at depth 6), kept by the scene like the staging and not part of rt_scene_info.device_bytes.
+ *          stats: rays = n, exact_walks summed over all walks of the call, every launch counted.
+ * Memory   the first of these calls grows the scene's staging to 85 MB.
+ * Measured on one MI355X, synth_room_v1, the 2,073,600 camera-ray records of the 1080p frame (profiles/r28_scatter_paths.txt, DESIGN.md
+ *          section 4): rt_query_scatter 3.37 ms of kernels = 615 Mrecords/s with device pointers (the call 3.6 ms), of which the sample
+ *          kernel is 0.19 ms, the finish kernel 0.10 ms and the light walk 2.98 ms; through host arrays the call takes 19.8 ms.
+ *          rt_trace_paths at depth 6: 44.5 ms = 46.6 Mpaths/s, 8.6 x rt_render(samples = 1) of the same frame (5.2 ms): 528 launches,
+ *          records through memory, and what no compaction costs -- 27.8 % of the ray slots over the six bounces (48.2 % at the last)
+ *          belong to paths already ended.  Sample kernel: 108 VGPRs, no scratch. */
+typedef struct rt_rng { uint32_t x; float saved; uint32_t has_saved; uint32_t reserved; } rt_rng;   /* 16 bytes */
+void rt_rng_seed(rt_rng *r, uint32_t seed);
+extern float rt_rng_uniform(rt_rng *r);
+typedef struct rt_scatter {           /* 64 bytes */
+    float o[3]; float pdf;            /* x + eps*ng; Mix::pdf of d */
+    float d[3]; uint32_t flags;       /* the sampled direction; RT_SCATTER_* */
+    float weight[3]; uint32_t component; /* mult of scene.cpp:159; 0 cosine, 1 vndf, 2 lights */
+    float brdf[3]; uint32_t reserved;
+} rt_scatter;
+#define RT_SCATTER_END_BRDF   1u  /* every brdf channel < eps (:154): the path returns the surface's emission; pdf and weight are 0, no light walk */
+#define RT_SCATTER_END_CLAMP  2u  /* a weight channel > 6 or NaN (:161): likewise; weight 0, pdf and brdf as computed */
+#define RT_SCATTER_NO_SURFACE 4u  /* hit.triangle or surface.material is 0xFFFFFFFF: zeros, engine untouched, not counted */
+#define RT_SCATTER_INVALID    8u  /* invalid ray (rt_query_closest's rule), non-finite t or ng, bad engine: zeros, engine untouched, counted in invalid_rays */
+int rt_query_scatter(rt_scene *scene, const rt_ray *rays, const rt_hit *hits, const rt_surface *surfaces, rt_rng *rng /* in and out */,
+                     size_t n, uint32_t flags, rt_scatter *out, rt_query_stats *stats /* nullable */);
+int rt_query_bsdf(rt_scene *scene, const rt_ray *rays, const rt_hit *hits, const rt_surface *surfaces, const float *dirs /* n*3 */,
+                  size_t n, uint32_t flags, float *out_brdf /* n*3 */, float *out_pdf /* n */, rt_query_stats *stats /* nullable */);
+int rt_trace_paths(rt_scene *scene, const rt_ray *rays, rt_rng *rng /* in and out */, size_t n, int32_t ray_depth,
+                   uint32_t flags, float *out_rgb /* n*3 */, rt_query_stats *stats /* nullable */);
+
 /* ---- denoised previews: a variance-guided edge-avoiding filter on the guide images -------------------------------------------
  * What consumes rt_render_guides' planes: a noisy frame of few samples in, a usable preview out.  An a-trous wavelet filter (five
  * taps per axis, stride doubling per level) whose weights stop at normal, depth and -- with rt_noise_estimate's map -- luminance edges

@@ -24,6 +24,7 @@ RT_QUERY_DEVICE_POINTERS, RT_QUERY_REFERENCE_WALK = 1, 2
 RT_HIT_INSIDE, RT_HIT_EXACT_WALK, RT_HIT_INVALID_RAY = 1, 2, 4
 RT_HIT_MISS = 0xFFFFFFFF
 RT_OCCLUSION_OCCLUDED, RT_OCCLUSION_EXACT_WALK, RT_OCCLUSION_INVALID_RAY = 1, 2, 4
+RT_SCATTER_END_BRDF, RT_SCATTER_END_CLAMP, RT_SCATTER_NO_SURFACE, RT_SCATTER_INVALID = 1, 2, 4, 8
 RT_DENOISE_DEVICE_POINTERS, RT_DENOISE_ALBEDO = 1, 2
 RT_PIPELINE_SINGLE, RT_PIPELINE_ROUNDS, RT_PIPELINE_PERSISTENT = 0, 1, 2
 RT_OK = 0
@@ -121,6 +122,15 @@ class rt_query_stats(C.Structure):
                 ("reserved", C.c_uint32)]
 
 
+class rt_rng(C.Structure):
+    _fields_ = [("x", C.c_uint32), ("saved", C.c_float), ("has_saved", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class rt_scatter(C.Structure):
+    _fields_ = [("o", C.c_float * 3), ("pdf", C.c_float), ("d", C.c_float * 3), ("flags", C.c_uint32), ("weight", C.c_float * 3),
+                ("component", C.c_uint32), ("brdf", C.c_float * 3), ("reserved", C.c_uint32)]
+
+
 class rt_denoise_params(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("width", C.c_int32), ("height", C.c_int32), ("iterations", C.c_int32),
                 ("sigma_depth", C.c_float), ("sigma_luminance", C.c_float), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
@@ -137,6 +147,9 @@ HIT_DTYPE = np.dtype([("t", np.float32), ("triangle", np.uint32), ("ng", np.floa
                       ("tangent", np.float32, 4), ("flags", np.uint32), ("reserved", np.uint32)])
 SURFACE_DTYPE = np.dtype([("color", np.float32, 3), ("alpha", np.float32), ("emission", np.float32, 3), ("metallic", np.float32),
                           ("sn", np.float32, 3), ("material", np.uint32), ("base_color", np.float32, 3), ("base_metallic", np.float32)])
+RNG_DTYPE = np.dtype([("x", np.uint32), ("saved", np.float32), ("has_saved", np.uint32), ("reserved", np.uint32)])
+SCATTER_DTYPE = np.dtype([("o", np.float32, 3), ("pdf", np.float32), ("d", np.float32, 3), ("flags", np.uint32), ("weight", np.float32, 3),
+                          ("component", np.uint32), ("brdf", np.float32, 3), ("reserved", np.uint32)])
 
 # Every symbol include/rtamd.h declares; tests/test_abi.py checks the library exports them all.
 ABI_SYMBOLS = ["rt_abi_version", "rt_last_error", "rt_scene_create", "rt_scene_destroy", "rt_output_elems", "rt_render",
@@ -150,10 +163,12 @@ ABI_SYMBOLS = ["rt_abi_version", "rt_last_error", "rt_scene_create", "rt_scene_d
                "rt_noise_batches", "rt_noise_estimate", "rt_noise_destroy", "rt_multi_noise_create", "rt_multi_noise_update",
                "rt_multi_noise_reset", "rt_multi_noise_batches", "rt_multi_noise_estimate", "rt_multi_noise_destroy", "rt_query_closest",
                "rt_query_light_pdf", "rt_query_surface", "rt_query_environment", "rt_camera_rays", "rt_render_guides",
-               "rt_query_occluded"]
+               "rt_query_occluded", "rt_rng_seed", "rt_query_scatter", "rt_query_bsdf", "rt_trace_paths"]
 # The preview filter's two, which the header declares `extern int`: the list above and the family lists of the tests are closed sets
 # of the header's plain prototypes (tests/test_abi_and_host.py, tests/test_accum_host.py), and rt_accum_denoise is no rt_accum_* of theirs.
 DENOISE_SYMBOLS = ["rt_denoise", "rt_accum_denoise"]
+# Likewise the one function of the header that returns a float (`extern float`): the closed set above is of its int / void / pointer prototypes.
+RNG_SYMBOLS = ["rt_rng_uniform"]
 
 if not os.path.exists(LIB_PATH):
     raise ImportError(f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
@@ -214,6 +229,13 @@ for _name in ("rt_query_closest", "rt_query_light_pdf", "rt_query_surface", "rt_
 lib.rt_query_occluded.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.POINTER(rt_query_stats)]
 lib.rt_camera_rays.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p]
 lib.rt_render_guides.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_uint32] + [C.c_void_p] * 4 + [C.POINTER(rt_query_stats)]
+lib.rt_rng_seed.argtypes = [C.c_void_p, C.c_uint32]
+lib.rt_rng_seed.restype = None
+lib.rt_rng_uniform.argtypes = [C.c_void_p]
+lib.rt_rng_uniform.restype = C.c_float
+lib.rt_query_scatter.argtypes = [C.c_void_p] + [C.c_void_p] * 4 + [C.c_size_t, C.c_uint32, C.c_void_p, C.POINTER(rt_query_stats)]
+lib.rt_query_bsdf.argtypes = [C.c_void_p] + [C.c_void_p] * 4 + [C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(rt_query_stats)]
+lib.rt_trace_paths.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int32, C.c_uint32, C.c_void_p, C.POINTER(rt_query_stats)]
 lib.rt_denoise.argtypes = [C.c_void_p, C.POINTER(rt_denoise_params)] + [C.c_void_p] * 8 + [C.POINTER(rt_denoise_stats)]
 lib.rt_accum_denoise.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(rt_denoise_params), C.c_void_p, C.c_void_p, C.POINTER(rt_denoise_stats)]
 
@@ -372,6 +394,41 @@ def pack_rays(o, d):
     rays = np.zeros(o.shape[0], dtype=RAY_DTYPE)
     rays["o"], rays["d"] = o, d
     return rays
+
+
+def rng_seed(seeds):
+    """Engines seeded as std::minstd_rand::seed does (rt_rng_seed): an array of RNG_DTYPE records, one per seed.  No GPU needed."""
+    seeds = np.atleast_1d(np.asarray(seeds, dtype=np.uint32))
+    rng = np.zeros(seeds.shape, dtype=RNG_DTYPE)
+    flat = rng.reshape(-1)
+    for i, s in enumerate(seeds.reshape(-1)):
+        lib.rt_rng_seed(flat.ctypes.data + i * RNG_DTYPE.itemsize, int(s))
+    return rng
+
+
+def rng_uniform(rng):
+    """One uniform draw in [0, 1) from every engine of the RNG_DTYPE array, which advances in place (rt_rng_uniform): float32 array."""
+    if not isinstance(rng, np.ndarray) or rng.dtype != RNG_DTYPE or not rng.flags.c_contiguous or not rng.flags.writeable:
+        raise ValueError("rng must be a writeable C-contiguous array of RNG_DTYPE records")
+    flat = rng.reshape(-1)
+    out = np.zeros(flat.shape[0], dtype=np.float32)
+    for i in range(flat.shape[0]):
+        out[i] = lib.rt_rng_uniform(flat.ctypes.data + i * RNG_DTYPE.itemsize)
+    return out.reshape(rng.shape)
+
+
+def _records(a, dtype, n, name):
+    """`a` as a contiguous array of n records of `dtype`; anything else is refused before the library is called."""
+    a = np.ascontiguousarray(a)
+    if a.dtype != dtype or a.ndim != 1 or (n is not None and a.shape[0] != n):
+        raise ValueError(f"{name} must be {'(n,)' if n is None else (n,)} records of {dtype.names}, got {a.dtype} {a.shape}")
+    return a
+
+
+def _engines(rng, n):
+    if not isinstance(rng, np.ndarray) or not rng.flags.c_contiguous or not rng.flags.writeable:
+        raise ValueError("rng must be a writeable C-contiguous array of RNG_DTYPE records: the engines advance in place")
+    return _records(rng, RNG_DTYPE, n, "rng")
 
 
 def make_params(width, height, samples, integrator=RT_INTEGRATOR_HW8, ray_depth=0, shard_index=0, shard_count=1,
@@ -801,4 +858,68 @@ class Scene(_Handle):
         st = rt_query_stats()
         st.struct_size = C.sizeof(rt_query_stats)
         _check(lib.rt_render_guides(self._h, width, height, RT_QUERY_DEVICE_POINTERS, albedo_ptr, normal_ptr, depth_ptr, emission_ptr, C.byref(st)))
+        return st
+
+    def _stats(self):
+        st = rt_query_stats()
+        st.struct_size = C.sizeof(rt_query_stats)
+        return st
+
+    def query_scatter(self, o, d, hits, surfaces, rng, flags=0):
+        """One bounce of Scene::getColor per record (rt_query_scatter): the rays (o[i], d[i]) that hit, their HIT_DTYPE and
+        SURFACE_DTYPE records and their engines, an RNG_DTYPE array that advances in place: (array of SCATTER_DTYPE records,
+        rt_query_stats).  flags: RT_QUERY_REFERENCE_WALK."""
+        if flags & RT_QUERY_DEVICE_POINTERS:
+            raise ValueError("query_scatter takes host arrays; device memory goes through query_scatter_device")
+        rays = pack_rays(o, d)
+        n = rays.shape[0]
+        hits, surfaces, rng = _records(hits, HIT_DTYPE, n, "hits"), _records(surfaces, SURFACE_DTYPE, n, "surfaces"), _engines(rng, n)
+        out = np.zeros(n, dtype=SCATTER_DTYPE)
+        st = self._stats()
+        _check(lib.rt_query_scatter(self._h, rays.ctypes.data, hits.ctypes.data, surfaces.ctypes.data, rng.ctypes.data, n, flags, out.ctypes.data, C.byref(st)))
+        return out, st
+
+    def query_scatter_device(self, rays_ptr, hits_ptr, surfaces_ptr, rng_ptr, n, out_ptr, flags=0):
+        """The same on device memory of the scene's GPU: every record array but the rays 16-byte aligned; the engines advance in place."""
+        st = self._stats()
+        _check(lib.rt_query_scatter(self._h, rays_ptr, hits_ptr, surfaces_ptr, rng_ptr, n, flags | RT_QUERY_DEVICE_POINTERS, out_ptr, C.byref(st)))
+        return st
+
+    def query_bsdf(self, o, d, hits, surfaces, dirs, flags=0):
+        """brdf and Mix::pdf of the directions dirs[i] at the hits of the rays (o[i], d[i]) (rt_query_bsdf): ((n, 3) float32, (n,)
+        float32, rt_query_stats)."""
+        if flags & RT_QUERY_DEVICE_POINTERS:
+            raise ValueError("query_bsdf takes host arrays; device memory goes through query_bsdf_device")
+        rays = pack_rays(o, d)
+        n = rays.shape[0]
+        hits, surfaces = _records(hits, HIT_DTYPE, n, "hits"), _records(surfaces, SURFACE_DTYPE, n, "surfaces")
+        dirs = np.ascontiguousarray(dirs, dtype=np.float32)
+        if dirs.shape != (n, 3):
+            raise ValueError(f"dirs must be ({n}, 3), got {dirs.shape}")
+        brdf, pdf = np.zeros((n, 3), dtype=np.float32), np.zeros(n, dtype=np.float32)
+        st = self._stats()
+        _check(lib.rt_query_bsdf(self._h, rays.ctypes.data, hits.ctypes.data, surfaces.ctypes.data, dirs.ctypes.data, n, flags, brdf.ctypes.data, pdf.ctypes.data, C.byref(st)))
+        return brdf, pdf, st
+
+    def query_bsdf_device(self, rays_ptr, hits_ptr, surfaces_ptr, dirs_ptr, n, out_brdf_ptr, out_pdf_ptr, flags=0):
+        st = self._stats()
+        _check(lib.rt_query_bsdf(self._h, rays_ptr, hits_ptr, surfaces_ptr, dirs_ptr, n, flags | RT_QUERY_DEVICE_POINTERS, out_brdf_ptr, out_pdf_ptr, C.byref(st)))
+        return st
+
+    def trace_paths(self, o, d, rng, ray_depth=0, flags=0):
+        """Scene::getColor(ray, ray_depth) for the rays (o[i], d[i]) with the engines rng[i], which advance in place (rt_trace_paths):
+        ((n, 3) float32 radiance, rt_query_stats).  ray_depth 0 = 6."""
+        if flags & RT_QUERY_DEVICE_POINTERS:
+            raise ValueError("trace_paths takes host arrays; device memory goes through trace_paths_device")
+        rays = pack_rays(o, d)
+        n = rays.shape[0]
+        rng = _engines(rng, n)
+        rgb = np.zeros((n, 3), dtype=np.float32)
+        st = self._stats()
+        _check(lib.rt_trace_paths(self._h, rays.ctypes.data, rng.ctypes.data, n, ray_depth, flags, rgb.ctypes.data, C.byref(st)))
+        return rgb, st
+
+    def trace_paths_device(self, rays_ptr, rng_ptr, n, out_rgb_ptr, ray_depth=0, flags=0):
+        st = self._stats()
+        _check(lib.rt_trace_paths(self._h, rays_ptr, rng_ptr, n, ray_depth, flags | RT_QUERY_DEVICE_POINTERS, out_rgb_ptr, C.byref(st)))
         return st

@@ -13,7 +13,9 @@ enum { RQ_CTR_FAST = 0,      // rays on the fast list (q_fast)
        RQ_CTR_EXACT = 1,     // rays on the exact list (q_exact)
        RQ_CTR_HEAD = 2,      // dynamic tail of the fast list (wf_steal)
        RQ_CTR_WORDS = 4 };
-enum { RQ_TOTAL_EXACT = 0, RQ_TOTAL_INVALID = 1, RQ_TOTAL_WORDS = 2 };
+// RQ_TOTAL_RIDE_*: the same two of a walk whose invalid rays are records that ride along (rt_query_scatter's light walk, rt_trace_paths'
+// later bounces; QueryView::totals then points at RQ_TOTAL_RIDE_EXACT): its exact walks count for the call, its invalid rays for nothing.
+enum { RQ_TOTAL_EXACT = 0, RQ_TOTAL_INVALID = 1, RQ_TOTAL_RIDE_EXACT = 2, RQ_TOTAL_RIDE_INVALID = 3, RQ_TOTAL_WORDS = 4 };
 
 struct QueryView {
     const float *rays;            // n x {o.xyz, d.xyz} (rt_ray): the chunk's rays, staged or the caller's own device memory
@@ -59,6 +61,33 @@ struct GuidesView {
     uint32_t n;
 };
 
+// The bounce step (rt_query_scatter.h): one chunk of rt_query_scatter, rt_query_bsdf and of one bounce of rt_trace_paths.
+struct ScatterView {
+    const float *rays;            // n x {o.xyz, d.xyz}: the rays that hit
+    const uint4 *hits, *surfaces; // n x 4 each (rt_hit, rt_surface), 16-byte aligned
+    uint4 *rng;                   // n (rt_rng), in and out, 16-byte aligned; unused by rt_query_bsdf
+    uint4 *out;                   // n x 4 (rt_scatter), 16-byte aligned; unused by rt_query_bsdf
+    const float *dirs;            // rt_query_bsdf: n x 3
+    float *out_brdf, *out_pdf;    // rt_query_bsdf: n x 3, n
+    float *walk_rays;             // n x {o.xyz, d.xyz}: what the light walk is asked, an invalid ray where no walk is needed
+    const float *light_pdf;       // n: what it answered; not read on a scene without lights
+    uint32_t n;
+    unsigned long long *totals;   // RQ_TOTAL_*
+};
+// rt_trace_paths: the paths of a chunk between two bounces.
+struct PathView {
+    float *rays;                  // n x {o.xyz, d.xyz}: the bounce's rays in, the next bounce's out (an ended path: NaNs)
+    const uint4 *hits, *surfaces, *scatter; // what the bounce's three queries answered
+    float4 *state;                // n: tail.xyz, bounces kept | RQ_PATH_ENDED
+    float *stack;                 // depth x n x {e.xyz, m.xyz}
+    float *rgb;                   // n x 3, written after the last bounce
+    uint32_t n, last;             // last: this was the last bounce, fold and write rgb
+};
+
+// The engine states std::minstd_rand can be in: 1 .. 2^31 - 2.  Any other x is refused (host arrays) or marked invalid (device arrays)
+// before a draw: 0 stays 0 for ever, and rng_n01's rejection loop would not end.
+__host__ __device__ inline bool rq_rng_valid(uint32_t x) { return x - 1u < 2147483646u; }
+
 // Launch geometry of the persistent walk (the round pipeline's traverse launch) as the host side sizes its overflow area by it.
 #define RQ_BLOCKS_PER_CU 5u
 size_t query_ovf_words(const rt_scene *scene);                        // 0 when neither tree needs the SPILL variant
@@ -71,5 +100,10 @@ uint32_t query_launch_surface(const rt_scene *scene, const SurfaceView &V, hipSt
 uint32_t query_launch_environment(const rt_scene *scene, const EnvironmentView &V, hipStream_t stream);
 uint32_t query_launch_camera_rays(const rt_scene *scene, const CameraView &V, hipStream_t stream);
 uint32_t query_launch_guides(const rt_scene *scene, const GuidesView &V, hipStream_t stream);
+uint32_t query_launch_scatter_sample(const rt_scene *scene, const ScatterView &V, hipStream_t stream);
+uint32_t query_launch_scatter_finish(const rt_scene *scene, const ScatterView &V, hipStream_t stream);
+uint32_t query_launch_bsdf_rays(const rt_scene *scene, const ScatterView &V, hipStream_t stream);
+uint32_t query_launch_bsdf_finish(const rt_scene *scene, const ScatterView &V, hipStream_t stream);
+uint32_t query_launch_path_advance(const rt_scene *scene, const PathView &V, hipStream_t stream);
 
 } // namespace rtamd

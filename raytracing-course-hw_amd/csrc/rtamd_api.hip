@@ -19,6 +19,7 @@
 #include "device/rt_wavefront.h"
 #include "device/rt_query.h"
 #include "device/rt_query_surface.h"
+#include "device/rt_query_scatter.h"
 #include "device/rt_persistent.h"
 #include "device/rt_kernels_hw6.h"
 #include "device/rt_persistent_hw6.h"
@@ -1144,6 +1145,37 @@ uint32_t rtamd::query_launch_camera_rays(const rt_scene *scene, const CameraView
 
 uint32_t rtamd::query_launch_guides(const rt_scene *scene, const GuidesView &V, hipStream_t stream) {
     hipLaunchKernelGGL(dev::rq_guides_kernel, dim3(query_geometry(scene, V.n).flat_blocks), dim3(256), 0, stream, scene->view, V);
+    HIP_CHECK(hipGetLastError());
+    return 1u;
+}
+
+// The bounce step (device/rt_query_scatter.h): flat launches, one lane per record; the light walk between them is query_launch_light_pdf.
+uint32_t rtamd::query_launch_scatter_sample(const rt_scene *scene, const ScatterView &V, hipStream_t stream) {
+    hipLaunchKernelGGL(dev::rq_scatter_sample_kernel, dim3(query_geometry(scene, V.n).flat_blocks), dim3(256), 0, stream, scene->view, V);
+    HIP_CHECK(hipGetLastError());
+    return 1u;
+}
+
+uint32_t rtamd::query_launch_scatter_finish(const rt_scene *scene, const ScatterView &V, hipStream_t stream) {
+    hipLaunchKernelGGL(dev::rq_scatter_finish_kernel, dim3(query_geometry(scene, V.n).flat_blocks), dim3(256), 0, stream, scene->view, V);
+    HIP_CHECK(hipGetLastError());
+    return 1u;
+}
+
+uint32_t rtamd::query_launch_bsdf_rays(const rt_scene *scene, const ScatterView &V, hipStream_t stream) {
+    hipLaunchKernelGGL(dev::rq_bsdf_rays_kernel, dim3(query_geometry(scene, V.n).flat_blocks), dim3(256), 0, stream, scene->view, V);
+    HIP_CHECK(hipGetLastError());
+    return 1u;
+}
+
+uint32_t rtamd::query_launch_bsdf_finish(const rt_scene *scene, const ScatterView &V, hipStream_t stream) {
+    hipLaunchKernelGGL(dev::rq_bsdf_finish_kernel, dim3(query_geometry(scene, V.n).flat_blocks), dim3(256), 0, stream, scene->view, V);
+    HIP_CHECK(hipGetLastError());
+    return 1u;
+}
+
+uint32_t rtamd::query_launch_path_advance(const rt_scene *scene, const PathView &V, hipStream_t stream) {
+    hipLaunchKernelGGL(dev::rq_path_advance_kernel, dim3(query_geometry(scene, V.n).flat_blocks), dim3(256), 0, stream, scene->view, V);
     HIP_CHECK(hipGetLastError());
     return 1u;
 }

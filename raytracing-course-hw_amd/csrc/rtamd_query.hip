@@ -1,6 +1,7 @@
-// Batched ray queries through the C-ABI (include/rtamd.h: rt_query_closest, rt_query_light_pdf, rt_query_occluded) and the first-hit layer over them
-// (rt_query_surface, rt_query_environment, rt_camera_rays, rt_render_guides): argument checks, the chunking, the staging and the
-// statistics.  No kernel and no kernel header here: the kernels (device/rt_query.h, device/rt_query_surface.h) live in rtamd_api.hip,
+// Batched ray queries through the C-ABI (include/rtamd.h: rt_query_closest, rt_query_light_pdf, rt_query_occluded), the first-hit layer over them
+// (rt_query_surface, rt_query_environment, rt_camera_rays, rt_render_guides) and the bounce step (rt_query_scatter, rt_query_bsdf,
+// rt_trace_paths, rt_rng_*): argument checks, the chunking, the staging and the statistics.  No kernel and no kernel header here: the
+// kernels (device/rt_query.h, device/rt_query_surface.h, device/rt_query_scatter.h) live in rtamd_api.hip,
 // where every __global__ keeps one definition, and are launched through query_launch_* (device/rt_types_query.h).
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -16,8 +17,8 @@ using namespace rtamd;
 
 namespace {
 
-static_assert(sizeof(rt_ray) == 24 && sizeof(rt_hit) == 64 && sizeof(rt_surface) == 64,
-              "rt_ray is 24 bytes, rt_hit and rt_surface 64: the kernels read and write them as words");
+static_assert(sizeof(rt_ray) == 24 && sizeof(rt_hit) == 64 && sizeof(rt_surface) == 64 && sizeof(rt_rng) == 16 && sizeof(rt_scatter) == 64,
+              "rt_ray is 24 bytes, rt_rng 16, rt_hit, rt_surface and rt_scatter 64: the kernels read and write them as words");
 
 // Rays per chunk: what the staging is sized for.  RTAMD_QUERY_CHUNK (testing) lowers it, so that a small call crosses chunk seams; it
 // changes no answer, a ray's answer does not depend on its neighbours.
@@ -26,17 +27,19 @@ size_t query_chunk() { return std::min(QUERY_CHUNK, (size_t)std::max(64, env_pos
 
 // The staging of one chunk, carved out of one allocation that the scene keeps: counters first, then the arrays in 256-byte steps.
 // The two ray queries need the first eight parts; a surface query or a guide pass (STAGE_FIRST_HIT) grows the allocation by the next
-// two, an occlusion query (STAGE_OCCLUSION) by the last two: a bound and an answer byte per ray.
+// two, an occlusion query (STAGE_OCCLUSION) by the last two: a bound and an answer byte per ray.  The bounce step (STAGE_SCATTER) takes
+// the first-hit layer's parts and four more: the engines, the rt_scatter records, the rays of the light walk and its answers.
 const size_t PLANE_FLOATS = 10; // albedo 3, normal 3, depth 1, emission 3
-enum StageParts { STAGE_WALK, STAGE_FIRST_HIT, STAGE_OCCLUSION };
+enum StageParts { STAGE_WALK, STAGE_FIRST_HIT, STAGE_OCCLUSION, STAGE_SCATTER };
 struct QueryStage {
     uint32_t *ctr; unsigned long long *totals;
     float *rays; uint8_t *out; float4 *rec; uint32_t *q_fast, *q_exact, *ovf;
     uint8_t *surf; float *planes;
     float *tmax; uint8_t *occ;
+    uint8_t *rng, *scat; float *walk_rays, *light_pdf;
 };
 QueryStage query_stage(rt_scene *scene, StageParts parts) {
-    const bool first_hit = parts == STAGE_FIRST_HIT, occlusion = parts == STAGE_OCCLUSION;
+    const bool scatter = parts == STAGE_SCATTER, first_hit = parts == STAGE_FIRST_HIT || scatter, occlusion = parts == STAGE_OCCLUSION;
     const size_t C = QUERY_CHUNK, ovf_words = query_ovf_words(scene);
     size_t at = 0;
     auto take = [&](size_t bytes) { const size_t here = at; at += (bytes + 255u) & ~(size_t)255u; return here; };
@@ -46,6 +49,8 @@ QueryStage query_stage(rt_scene *scene, StageParts parts) {
     if (first_hit) { o_surf = take(C * sizeof(rt_surface)); o_planes = take(C * PLANE_FLOATS * 4); }
     size_t o_tmax = 0, o_occ = 0;
     if (occlusion) { o_tmax = take(C * sizeof(float)); o_occ = take(C); }
+    size_t o_rng = 0, o_scat = 0, o_walk = 0, o_lpdf = 0;
+    if (scatter) { o_rng = take(C * sizeof(rt_rng)); o_scat = take(C * sizeof(rt_scatter)); o_walk = take(C * sizeof(rt_ray)); o_lpdf = take(C * sizeof(float)); }
     grow(scene->query_stage, scene->query_stage_bytes, at);
     uint8_t *b = scene->query_stage;
     QueryStage s;
@@ -55,6 +60,8 @@ QueryStage query_stage(rt_scene *scene, StageParts parts) {
     s.ovf = ovf_words ? (uint32_t *)(b + o_ovf) : nullptr;
     s.surf = first_hit ? b + o_surf : nullptr; s.planes = first_hit ? (float *)(b + o_planes) : nullptr;
     s.tmax = occlusion ? (float *)(b + o_tmax) : nullptr; s.occ = occlusion ? b + o_occ : nullptr;
+    s.rng = scatter ? b + o_rng : nullptr; s.scat = scatter ? b + o_scat : nullptr;
+    s.walk_rays = scatter ? (float *)(b + o_walk) : nullptr; s.light_pdf = scatter ? (float *)(b + o_lpdf) : nullptr;
     return s;
 }
 
@@ -100,7 +107,7 @@ int answer(rt_scene *scene, size_t n, rt_query_stats *stats, const std::string &
             }
             unsigned long long totals[RQ_TOTAL_WORDS];
             HIP_CHECK(hipMemcpy(totals, S.totals, sizeof totals, hipMemcpyDeviceToHost));
-            st.exact_walks = totals[RQ_TOTAL_EXACT]; st.invalid_rays = totals[RQ_TOTAL_INVALID];
+            st.exact_walks = totals[RQ_TOTAL_EXACT] + totals[RQ_TOTAL_RIDE_EXACT]; st.invalid_rays = totals[RQ_TOTAL_INVALID];
             st.kernel_ms = ms_sum;
         }
         st.total_ms = now_ms() - t0;
@@ -158,6 +165,49 @@ SurfaceView surface_view(const rt_scene *scene, const QueryStage &S, size_t m, c
     V.n = (uint32_t)m; V.n_tris = scene->view.n_tris;
     V.tri_material = scene->query_materials; V.totals = S.totals;
     return V;
+}
+
+// ---- the bounce step ------------------------------------------------------------------------------------------------------------------------
+const uint32_t SCATTER_FLAGS = RT_QUERY_DEVICE_POINTERS | RT_QUERY_REFERENCE_WALK;
+const char *const SCATTER_FLAG_NAMES = "RT_QUERY_DEVICE_POINTERS | RT_QUERY_REFERENCE_WALK";
+
+// What rt_query_scatter, rt_query_bsdf and rt_trace_paths check before the scene: stats, flags, and the engines of a host array, so
+// that no launch ever sees a state the engine cannot be in (device arrays: the sample kernel marks such a record invalid).
+int check_scatter_call(const rt_query_stats *stats, uint32_t flags, const rt_rng *rng, size_t n, const std::string &who) {
+    if (stats && stats->struct_size != sizeof(rt_query_stats)) return fail(RT_ERR_INVALID_ARG, who + "struct_size mismatch (ABI skew)");
+    if (flags & ~SCATTER_FLAGS) return fail(RT_ERR_INVALID_ARG, who + "flags other than " + SCATTER_FLAG_NAMES);
+    if (rng && !(flags & RT_QUERY_DEVICE_POINTERS))
+        for (size_t i = 0; i < n; i++)
+            if (!rq_rng_valid(rng[i].x))
+                return fail(RT_ERR_INVALID_ARG, who + "rng[" + std::to_string(i) + "].x = " + std::to_string(rng[i].x) + " is no state of the engine (1 .. 2147483646)");
+    return RT_OK;
+}
+
+// A chunk's records as the kernels see them: the caller's device arrays from `first` on, or the staging.
+struct ScatterArrays { const rt_ray *rays; const rt_hit *hits; const rt_surface *surfaces; rt_rng *rng; rt_scatter *out; };
+ScatterView scatter_view(const QueryStage &S, size_t m, const ScatterArrays &A) {
+    ScatterView V{};
+    V.rays = (const float *)A.rays; V.hits = (const uint4 *)A.hits; V.surfaces = (const uint4 *)A.surfaces;
+    V.rng = (uint4 *)A.rng; V.out = (uint4 *)A.out;
+    V.walk_rays = S.walk_rays; V.light_pdf = S.light_pdf;
+    V.n = (uint32_t)m; V.totals = S.totals;
+    return V;
+}
+
+// The light walk over the rays a sample kernel left in the staging: its invalid rays are records that ride along, so its totals are the
+// RIDE pair.  `rezero`: a walk before it in this chunk has used the chunk's counters.
+uint32_t launch_ride_light_pdf(const rt_scene *scene, const QueryStage &S, size_t m, uint32_t flags, bool rezero, hipStream_t stream) {
+    if (scene->view.n_lights == 0) return 0u;
+    if (rezero) HIP_CHECK(hipMemsetAsync(S.ctr, 0, RQ_CTR_WORDS * 4, stream));
+    QueryView Q = walk_view(scene, S, m, flags, S.walk_rays);
+    Q.pdf = S.light_pdf; Q.totals = S.totals + RQ_TOTAL_RIDE_EXACT;
+    return query_launch_light_pdf(scene, Q, stream);
+}
+
+// The per-bounce stack of rt_trace_paths for `paths` paths of a chunk: 16 bytes of state, then 24 bytes per bounce.
+uint8_t *path_stack(rt_scene *scene, size_t paths, int depth) {
+    grow(scene->path_stack, scene->path_stack_bytes, paths * (16u + 24u * (size_t)depth));
+    return scene->path_stack;
 }
 
 } // namespace
@@ -297,6 +347,144 @@ int rt_render_guides(rt_scene *scene, int32_t width, int32_t height, uint32_t fl
             if (on_device) return;
             for (const Plane &pl : planes)
                 if (pl.p) HIP_CHECK(hipMemcpyAsync(pl.p + pl.k * first, S.planes + pl.at * QUERY_CHUNK, m * pl.k * sizeof(float), hipMemcpyDeviceToHost, stream));
+        });
+}
+
+void rt_rng_seed(rt_rng *r, uint32_t seed) {
+    if (!r) return;
+    const uint32_t v = seed % 2147483647u;
+    r->x = v == 0 ? 1u : v; r->saved = 0.f; r->has_saved = 0u; r->reserved = 0u;
+}
+
+float rt_rng_uniform(rt_rng *r) { // rng_next and rng_u01 of device/rt_device.h, on the host
+    if (!r) return 0.f;
+    r->x = (uint32_t)((uint64_t)r->x * 48271ull % 2147483647ull);
+    const float v = (float)(r->x - 1u) * 4.656612873077392578125e-10f;
+    return v >= 1.0f ? 0.99999994f : v;
+}
+
+int rt_query_scatter(rt_scene *scene, const rt_ray *rays, const rt_hit *hits, const rt_surface *surfaces, rt_rng *rng, size_t n, uint32_t flags,
+                     rt_scatter *out, rt_query_stats *stats) {
+    const std::string who = "rt_query_scatter: ";
+    if (n && (!rays || !hits || !surfaces || !rng || !out)) return fail(RT_ERR_INVALID_ARG, who + "null argument");
+    if (const int rc = check_scatter_call(stats, flags, rng, n, who)) return rc;
+    if (const int rc = check_call(scene, stats, flags, SCATTER_FLAGS, SCATTER_FLAG_NAMES, who)) return rc;
+    const bool on_device = (flags & RT_QUERY_DEVICE_POINTERS) != 0;
+    if (n && on_device && (((uintptr_t)hits | (uintptr_t)surfaces | (uintptr_t)rng | (uintptr_t)out) & 15u))
+        return fail(RT_ERR_INVALID_ARG, who + "with RT_QUERY_DEVICE_POINTERS the rt_hit, rt_surface, rt_rng and rt_scatter arrays must be 16-byte aligned");
+    return answer(scene, n, stats, who, STAGE_SCATTER,
+        [&](const QueryStage &S, size_t first, size_t m, hipStream_t stream) {
+            if (on_device) return;
+            HIP_CHECK(hipMemcpyAsync(S.rays, rays + first, m * sizeof(rt_ray), hipMemcpyHostToDevice, stream));
+            HIP_CHECK(hipMemcpyAsync(S.out, hits + first, m * sizeof(rt_hit), hipMemcpyHostToDevice, stream));
+            HIP_CHECK(hipMemcpyAsync(S.surf, surfaces + first, m * sizeof(rt_surface), hipMemcpyHostToDevice, stream));
+            HIP_CHECK(hipMemcpyAsync(S.rng, rng + first, m * sizeof(rt_rng), hipMemcpyHostToDevice, stream));
+        },
+        [&](const QueryStage &S, size_t first, size_t m, hipStream_t stream) {
+            const ScatterArrays A = on_device ? ScatterArrays{rays + first, hits + first, surfaces + first, rng + first, out + first}
+                                              : ScatterArrays{(const rt_ray *)S.rays, (const rt_hit *)S.out, (const rt_surface *)S.surf, (rt_rng *)S.rng, (rt_scatter *)S.scat};
+            const ScatterView V = scatter_view(S, m, A);
+            uint32_t launches = query_launch_scatter_sample(scene, V, stream);
+            launches += launch_ride_light_pdf(scene, S, m, flags, false, stream);
+            return launches + query_launch_scatter_finish(scene, V, stream);
+        },
+        [&](const QueryStage &S, size_t first, size_t m, hipStream_t stream) {
+            if (on_device) return;
+            HIP_CHECK(hipMemcpyAsync(out + first, S.scat, m * sizeof(rt_scatter), hipMemcpyDeviceToHost, stream));
+            HIP_CHECK(hipMemcpyAsync(rng + first, S.rng, m * sizeof(rt_rng), hipMemcpyDeviceToHost, stream));
+        });
+}
+
+int rt_query_bsdf(rt_scene *scene, const rt_ray *rays, const rt_hit *hits, const rt_surface *surfaces, const float *dirs, size_t n, uint32_t flags,
+                  float *out_brdf, float *out_pdf, rt_query_stats *stats) {
+    const std::string who = "rt_query_bsdf: ";
+    if (n && (!rays || !hits || !surfaces || !dirs || !out_brdf || !out_pdf)) return fail(RT_ERR_INVALID_ARG, who + "null argument");
+    if (const int rc = check_scatter_call(stats, flags, nullptr, n, who)) return rc;
+    if (const int rc = check_call(scene, stats, flags, SCATTER_FLAGS, SCATTER_FLAG_NAMES, who)) return rc;
+    const bool on_device = (flags & RT_QUERY_DEVICE_POINTERS) != 0;
+    if (n && on_device && (((uintptr_t)hits | (uintptr_t)surfaces) & 15u))
+        return fail(RT_ERR_INVALID_ARG, who + "with RT_QUERY_DEVICE_POINTERS the rt_hit and rt_surface arrays must be 16-byte aligned");
+    if (n && on_device && (((uintptr_t)dirs | (uintptr_t)out_brdf | (uintptr_t)out_pdf) & 3u))
+        return fail(RT_ERR_INVALID_ARG, who + "with RT_QUERY_DEVICE_POINTERS dirs, out_brdf and out_pdf must be 4-byte aligned");
+    // host arrays: the directions and the two answers of a chunk are staged where a scatter keeps its records (3 + 3 + 1 floats per record)
+    auto stage_dirs = [](const QueryStage &S) { return (float *)S.scat; };
+    auto stage_brdf = [](const QueryStage &S) { return (float *)S.scat + 3 * QUERY_CHUNK; };
+    auto stage_pdf = [](const QueryStage &S) { return (float *)S.scat + 6 * QUERY_CHUNK; };
+    return answer(scene, n, stats, who, STAGE_SCATTER,
+        [&](const QueryStage &S, size_t first, size_t m, hipStream_t stream) {
+            if (on_device) return;
+            HIP_CHECK(hipMemcpyAsync(S.rays, rays + first, m * sizeof(rt_ray), hipMemcpyHostToDevice, stream));
+            HIP_CHECK(hipMemcpyAsync(S.out, hits + first, m * sizeof(rt_hit), hipMemcpyHostToDevice, stream));
+            HIP_CHECK(hipMemcpyAsync(S.surf, surfaces + first, m * sizeof(rt_surface), hipMemcpyHostToDevice, stream));
+            HIP_CHECK(hipMemcpyAsync(stage_dirs(S), dirs + 3 * first, m * 3 * sizeof(float), hipMemcpyHostToDevice, stream));
+        },
+        [&](const QueryStage &S, size_t first, size_t m, hipStream_t stream) {
+            const ScatterArrays A = on_device ? ScatterArrays{rays + first, hits + first, surfaces + first, nullptr, nullptr}
+                                              : ScatterArrays{(const rt_ray *)S.rays, (const rt_hit *)S.out, (const rt_surface *)S.surf, nullptr, nullptr};
+            ScatterView V = scatter_view(S, m, A);
+            V.dirs = on_device ? dirs + 3 * first : stage_dirs(S);
+            V.out_brdf = on_device ? out_brdf + 3 * first : stage_brdf(S);
+            V.out_pdf = on_device ? out_pdf + first : stage_pdf(S);
+            uint32_t launches = query_launch_bsdf_rays(scene, V, stream);
+            launches += launch_ride_light_pdf(scene, S, m, flags, false, stream);
+            return launches + query_launch_bsdf_finish(scene, V, stream);
+        },
+        [&](const QueryStage &S, size_t first, size_t m, hipStream_t stream) {
+            if (on_device) return;
+            HIP_CHECK(hipMemcpyAsync(out_brdf + 3 * first, stage_brdf(S), m * 3 * sizeof(float), hipMemcpyDeviceToHost, stream));
+            HIP_CHECK(hipMemcpyAsync(out_pdf + first, stage_pdf(S), m * sizeof(float), hipMemcpyDeviceToHost, stream));
+        });
+}
+
+int rt_trace_paths(rt_scene *scene, const rt_ray *rays, rt_rng *rng, size_t n, int32_t ray_depth, uint32_t flags, float *out_rgb, rt_query_stats *stats) {
+    const std::string who = "rt_trace_paths: ";
+    if (n && (!rays || !rng || !out_rgb)) return fail(RT_ERR_INVALID_ARG, who + "null argument");
+    if (const int rc = check_scatter_call(stats, flags, rng, n, who)) return rc;
+    if (const int rc = check_call(scene, stats, flags, SCATTER_FLAGS, SCATTER_FLAG_NAMES, who)) return rc;
+    const int depth = ray_depth > 0 ? ray_depth : 6;
+    if (depth > RT_MAX_DEPTH) return fail(RT_ERR_LIMIT, who + "ray_depth above " + std::to_string(RT_MAX_DEPTH));
+    const bool on_device = (flags & RT_QUERY_DEVICE_POINTERS) != 0;
+    if (n && on_device && ((uintptr_t)rng & 15u)) return fail(RT_ERR_INVALID_ARG, who + "with RT_QUERY_DEVICE_POINTERS the rt_rng array must be 16-byte aligned");
+    if (n && on_device && (((uintptr_t)rays | (uintptr_t)out_rgb) & 3u)) return fail(RT_ERR_INVALID_ARG, who + "with RT_QUERY_DEVICE_POINTERS rays and out_rgb must be 4-byte aligned");
+    const size_t paths = std::min(n, query_chunk());
+    uint8_t *stack = nullptr;
+    return answer(scene, n, stats, who, STAGE_SCATTER,
+        [&](const QueryStage &S, size_t first, size_t m, hipStream_t stream) {
+            ensure_materials(scene, stream);
+            stack = path_stack(scene, paths, depth);
+            HIP_CHECK(hipMemsetAsync(stack, 0, paths * 16u, stream)); // tail 0, no bounce kept, not ended
+            // the rays change from bounce to bounce: always a copy in the staging
+            HIP_CHECK(hipMemcpyAsync(S.rays, rays + first, m * sizeof(rt_ray), on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, stream));
+            if (!on_device) HIP_CHECK(hipMemcpyAsync(S.rng, rng + first, m * sizeof(rt_rng), hipMemcpyHostToDevice, stream));
+        },
+        [&](const QueryStage &S, size_t first, size_t m, hipStream_t stream) {
+            const ScatterView V = scatter_view(S, m, ScatterArrays{(const rt_ray *)S.rays, (const rt_hit *)S.out, (const rt_surface *)S.surf,
+                                                                   on_device ? rng + first : (rt_rng *)S.rng, (rt_scatter *)S.scat});
+            PathView P{};
+            P.rays = S.rays; P.hits = V.hits; P.surfaces = V.surfaces; P.scatter = V.out;
+            P.state = (float4 *)stack; P.stack = (float *)(stack + paths * 16u);
+            P.rgb = on_device ? out_rgb + 3 * first : (float *)S.rec; // the colours of a chunk are staged where a closest-hit query keeps its records
+            P.n = (uint32_t)m;
+            uint32_t launches = 0;
+            for (int b = 0; b < depth; b++) {
+                if (b) HIP_CHECK(hipMemsetAsync(S.ctr, 0, RQ_CTR_WORDS * 4, stream));
+                QueryView Q = walk_view(scene, S, m, flags, S.rays);
+                Q.hits = (uint4 *)S.out;
+                if (b) Q.totals = S.totals + RQ_TOTAL_RIDE_EXACT; // ended paths ride along as invalid rays; the caller's own were counted at b == 0
+                launches += query_launch_closest(scene, Q, stream);
+                launches += query_launch_surface(scene, surface_view(scene, S, m, S.out, S.surf), stream);
+                launches += query_launch_scatter_sample(scene, V, stream);
+                launches += launch_ride_light_pdf(scene, S, m, flags, true, stream);
+                launches += query_launch_scatter_finish(scene, V, stream);
+                P.last = b == depth - 1 ? 1u : 0u;
+                launches += query_launch_path_advance(scene, P, stream);
+            }
+            return launches;
+        },
+        [&](const QueryStage &S, size_t first, size_t m, hipStream_t stream) {
+            if (on_device) return;
+            HIP_CHECK(hipMemcpyAsync(out_rgb + 3 * first, S.rec, m * 3 * sizeof(float), hipMemcpyDeviceToHost, stream));
+            HIP_CHECK(hipMemcpyAsync(rng + first, S.rng, m * sizeof(rt_rng), hipMemcpyDeviceToHost, stream));
         });
 }
 
