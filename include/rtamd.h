@@ -633,6 +633,70 @@ int rt_query_bsdf(rt_scene *scene, const rt_ray *rays, const rt_hit *hits, const
 int rt_trace_paths(rt_scene *scene, const rt_ray *rays, rt_rng *rng /* in and out */, size_t n, int32_t ray_depth,
                    uint32_t flags, float *out_rgb /* n*3 */, rt_query_stats *stats /* nullable */);
 
+/* ---- the baker: irradiance and SH probes at points of the caller's, paths restarted in place ----------------------------------
+ * The first caller of the query layer above, kept a composition of its public calls: per sample a ray from the engine (rt_bake_rays),
+ * rt_trace_paths over it, and a float32 sum.  Same scenes, refusals and chunks (RTAMD_QUERY_CHUNK) as rt_trace_paths; hw8's rules
+ * only.  New on the device are the ray maker and the advance / fold / accumulate / restart step (device/rt_bake.h); the walks are
+ * the launches of the queries above, untouched.  ABI version 6 still.
+ *
+ * rt_bake_rays   the rt_camera_rays of a baker: one ray per record from the record's engine, which advances in place.
+ *            RT_BAKE_IRRADIANCE:  o = p + eps*n, eps = (float)1e-4L, n used as given (a unit normal: rt_hit.ng, rt_surface.sn);
+ *                                 d = the cosine-distributed direction around n that rt_query_scatter's component 0 draws.
+ *            RT_BAKE_SH9:         o = p, n is not read;  d = normalize(a, b, c) of three normal draws: a uniform direction.
+ *          A record with a NaN or an infinity in p, (irradiance) a NaN or an infinity in n or n == 0, or an engine state outside
+ *          1 .. 2^31-2 is invalid: it gets an invalid ray (o = 0, d = NaN), keeps its engine and is counted in invalid_rays.  Host
+ *          engine arrays are checked before any launch, as rt_query_scatter's.  flags: RT_QUERY_DEVICE_POINTERS (points and rays
+ *          4-byte aligned, rt_rng 16-byte).
+ * rt_bake        per point i and stream k (params.streams = K, 1 .. 64, 0 = 1; samples >= 1 and a multiple of K) the engine
+ *          rng[i*K+k] draws q = samples / K samples back to back: rt_bake_rays, rt_trace_paths(ray, engine, ray_depth), then
+ *            irradiance:  acc_k = acc_k + L                           per channel, in sample order
+ *            SH9:         acc_k[m][c] = acc_k[m][c] + (Y_m(d) * L[c])    d the sample's first direction, and
+ *                         Y_0 = 0.282095f, Y_1 = 0.488603f*y, Y_2 = 0.488603f*z, Y_3 = 0.488603f*x, Y_4 = 1.092548f*(x*y),
+ *                         Y_5 = 1.092548f*(y*z), Y_6 = 0.315392f*((3.0f*(z*z)) - 1.0f), Y_7 = 1.092548f*(x*z),
+ *                         Y_8 = 0.546274f*((x*x) - (y*y))
+ *          in float32 with one rounding per operation.  out = scale * (((acc_0 + acc_1) + acc_2) ...), scale =
+ *          (float)(pi / (double)samples) for the irradiance (3 floats per point), (float)(4 * pi / (double)samples) for SH9 (27
+ *          floats per point, [m][c]).  Streams exist so that a few thousand probes with thousands of samples fill the GPU; the
+ *          caller seeds the engines (rt_rng_seed) and may carry them into a later call.  A point with an invalid record (the rule
+ *          of rt_bake_rays, over all K of its engines) answers zeros, leaves all its engines untouched and is counted once in
+ *          invalid_points.  ray_depth: 0 = 6, above 16 RT_ERR_LIMIT; streams > 64 or n_points * streams >= 2^31: RT_ERR_LIMIT; a bad
+ *          mode, flags, struct_size or a non-zero reserved word: RT_ERR_INVALID_ARG, the message names the field.
+ * Scheduling  a slot (i, k) owns its engine, so it runs its q paths back to back: in the round (closest hit, surface, scatter,
+ *          light walk, advance) in which its path ends -- a miss, an RT_SCATTER_END_*, or ray_depth bounces spent -- the advance
+ *          step folds L = e[b] + m[b]*L, accumulates, makes the slot's next ray from the engine as the scatter left it and resets the
+ *          path; a slot without a sample left parks as an invalid ray.  The host reads a live-slot count after every round and
+ *          stops at 0.  No compaction, no sort, no change to a walker.  RT_BAKE_LOCKSTEP: every slot starts sample j in the same
+ *          round and every sample takes ray_depth rounds -- the plain composition, the referee: outputs and engines are the same
+ *          bits, since a slot's samples come from its one engine in the same order whatever the schedule.
+ * flags    RT_QUERY_DEVICE_POINTERS (points and out 4-byte aligned, rt_rng 16-byte), RT_QUERY_REFERENCE_WALK, RT_BAKE_LOCKSTEP.
+ * stats    points = n_points; paths = valid slots * q; rounds = rounds launched, summed over chunks; ray_slots = rounds * slots of
+ *          the chunk, summed; live_ray_slots = closest-hit queries made for live paths; exact_walks over all walks of the call.
+ * Memory   a chunk holds floor(chunk / K) whole points, so the stream sum never crosses a seam.  The bake grows the scene's staging
+ *          by 24 (the point) + 12 (the first direction) + 12 or 108 (the accumulator) + 4 (the samples left) bytes per slot of a
+ *          chunk (13.6 or 38.8 MB), with host arrays by the chunk's answer too, and uses rt_trace_paths' per-bounce stack.
+ * Measured on one MI355X, synth_room_v1, device pointers, depth 6, kernel time (profiles/r29_bake.txt):
+ *          2,073,600 texels x 16 samples, K = 1: 749 ms = 44.3 Mpaths/s; RT_BAKE_LOCKSTEP 759 ms; the loop of rt_bake_rays +
+ *          rt_trace_paths from outside 736 ms; 768 rounds either way, 76.1 % of the ray slots live.  4,096 SH9 probes x 4,096
+ *          samples, K = 64: 362 ms = 46.3 Mpaths/s in 366 rounds (83.0 % live); lockstep 382 ms in 384; outside loop 363 ms.
+ *          Restarting in place does not shorten a chunk whose slowest slot runs q * ray_depth rounds, and among 262,144 slots
+ *          one does; the bits of all three are the same.  The per-round poll costs 19 us a round.  rq_bake_advance_kernel: 45 VGPRs,
+ *          28 bytes of scratch per lane (rq_path_advance_kernel's), no LDS; rq_bake_rays_kernel 34 VGPRs, rq_bake_resolve_kernel 12. */
+typedef struct rt_bake_point { float p[3]; float n[3]; } rt_bake_point;   /* 24 bytes */
+#define RT_BAKE_IRRADIANCE 0   /* out: 3 floats per point  */
+#define RT_BAKE_SH9        1   /* out: 27 floats per point, [m][c], m = 0..8, c = r,g,b */
+#define RT_BAKE_LOCKSTEP   4u  /* flag, next to RT_QUERY_DEVICE_POINTERS (1) and RT_QUERY_REFERENCE_WALK (2) */
+typedef struct rt_bake_params {
+    uint32_t struct_size; int32_t mode; int32_t samples; int32_t streams; int32_t ray_depth; uint32_t flags; uint32_t reserved[2];
+} rt_bake_params;
+typedef struct rt_bake_stats {
+    uint32_t struct_size, reference_exact; uint64_t points, invalid_points, paths, exact_walks;
+    uint64_t rounds, ray_slots, live_ray_slots; double kernel_ms, total_ms; uint32_t launches, reserved;
+} rt_bake_stats;
+int rt_bake_rays(rt_scene *scene, const rt_bake_point *points, rt_rng *rng /* in and out */, size_t n, int32_t mode, uint32_t flags,
+                 rt_ray *out, rt_query_stats *stats /* nullable */);
+int rt_bake(rt_scene *scene, const rt_bake_point *points, size_t n_points, const rt_bake_params *params,
+            rt_rng *rng /* n_points*streams, [i*streams+k], in and out */, float *out, rt_bake_stats *stats /* nullable */);
+
 /* ---- denoised previews: a variance-guided edge-avoiding filter on the guide images -------------------------------------------
  * What consumes rt_render_guides' planes: a noisy frame of few samples in, a usable preview out.  An a-trous wavelet filter (five
  * taps per axis, stride doubling per level) whose weights stop at normal, depth and -- with rt_noise_estimate's map -- luminance edges

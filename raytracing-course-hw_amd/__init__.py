@@ -131,6 +131,22 @@ class rt_scatter(C.Structure):
                 ("component", C.c_uint32), ("brdf", C.c_float * 3), ("reserved", C.c_uint32)]
 
 
+class rt_bake_point(C.Structure):
+    _fields_ = [("p", C.c_float * 3), ("n", C.c_float * 3)]
+
+
+class rt_bake_params(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("mode", C.c_int32), ("samples", C.c_int32), ("streams", C.c_int32), ("ray_depth", C.c_int32),
+                ("flags", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+class rt_bake_stats(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("reference_exact", C.c_uint32), ("points", C.c_uint64), ("invalid_points", C.c_uint64),
+                ("paths", C.c_uint64), ("exact_walks", C.c_uint64), ("rounds", C.c_uint64), ("ray_slots", C.c_uint64),
+                ("live_ray_slots", C.c_uint64), ("kernel_ms", C.c_double), ("total_ms", C.c_double), ("launches", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
 class rt_denoise_params(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("width", C.c_int32), ("height", C.c_int32), ("iterations", C.c_int32),
                 ("sigma_depth", C.c_float), ("sigma_luminance", C.c_float), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
@@ -150,6 +166,10 @@ SURFACE_DTYPE = np.dtype([("color", np.float32, 3), ("alpha", np.float32), ("emi
 RNG_DTYPE = np.dtype([("x", np.uint32), ("saved", np.float32), ("has_saved", np.uint32), ("reserved", np.uint32)])
 SCATTER_DTYPE = np.dtype([("o", np.float32, 3), ("pdf", np.float32), ("d", np.float32, 3), ("flags", np.uint32), ("weight", np.float32, 3),
                           ("component", np.uint32), ("brdf", np.float32, 3), ("reserved", np.uint32)])
+BAKE_POINT_DTYPE = np.dtype([("p", np.float32, 3), ("n", np.float32, 3)])
+RT_BAKE_IRRADIANCE, RT_BAKE_SH9 = 0, 1
+RT_BAKE_LOCKSTEP = 4
+BAKE_FLOATS = {RT_BAKE_IRRADIANCE: 3, RT_BAKE_SH9: 27}
 
 # Every symbol include/rtamd.h declares; tests/test_abi.py checks the library exports them all.
 ABI_SYMBOLS = ["rt_abi_version", "rt_last_error", "rt_scene_create", "rt_scene_destroy", "rt_output_elems", "rt_render",
@@ -163,7 +183,7 @@ ABI_SYMBOLS = ["rt_abi_version", "rt_last_error", "rt_scene_create", "rt_scene_d
                "rt_noise_batches", "rt_noise_estimate", "rt_noise_destroy", "rt_multi_noise_create", "rt_multi_noise_update",
                "rt_multi_noise_reset", "rt_multi_noise_batches", "rt_multi_noise_estimate", "rt_multi_noise_destroy", "rt_query_closest",
                "rt_query_light_pdf", "rt_query_surface", "rt_query_environment", "rt_camera_rays", "rt_render_guides",
-               "rt_query_occluded", "rt_rng_seed", "rt_query_scatter", "rt_query_bsdf", "rt_trace_paths"]
+               "rt_query_occluded", "rt_rng_seed", "rt_query_scatter", "rt_query_bsdf", "rt_trace_paths", "rt_bake_rays", "rt_bake"]
 # The preview filter's two, which the header declares `extern int`: the list above and the family lists of the tests are closed sets
 # of the header's plain prototypes (tests/test_abi_and_host.py, tests/test_accum_host.py), and rt_accum_denoise is no rt_accum_* of theirs.
 DENOISE_SYMBOLS = ["rt_denoise", "rt_accum_denoise"]
@@ -236,6 +256,8 @@ lib.rt_rng_uniform.restype = C.c_float
 lib.rt_query_scatter.argtypes = [C.c_void_p] + [C.c_void_p] * 4 + [C.c_size_t, C.c_uint32, C.c_void_p, C.POINTER(rt_query_stats)]
 lib.rt_query_bsdf.argtypes = [C.c_void_p] + [C.c_void_p] * 4 + [C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(rt_query_stats)]
 lib.rt_trace_paths.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int32, C.c_uint32, C.c_void_p, C.POINTER(rt_query_stats)]
+lib.rt_bake_rays.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int32, C.c_uint32, C.c_void_p, C.POINTER(rt_query_stats)]
+lib.rt_bake.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(rt_bake_params), C.c_void_p, C.c_void_p, C.POINTER(rt_bake_stats)]
 lib.rt_denoise.argtypes = [C.c_void_p, C.POINTER(rt_denoise_params)] + [C.c_void_p] * 8 + [C.POINTER(rt_denoise_stats)]
 lib.rt_accum_denoise.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(rt_denoise_params), C.c_void_p, C.c_void_p, C.POINTER(rt_denoise_stats)]
 
@@ -441,6 +463,25 @@ def make_params(width, height, samples, integrator=RT_INTEGRATOR_HW8, ray_depth=
     p.stream = stream
     p.sample_streams = sample_streams  # 0/1 = replay mode (reference pixels); K > 1 = throughput mode, statistical parity only
     return p
+
+
+def pack_bake_points(p, n=None):
+    """Points (n, 3) and their normals (n, 3; None: zeros, which RT_BAKE_SH9 does not read) as one contiguous array of rt_bake_point
+    records.  Refuses anything else before the library is called."""
+    p = np.asarray(p, dtype=np.float32)
+    n = np.zeros_like(p) if n is None else np.asarray(n, dtype=np.float32)
+    if p.ndim != 2 or p.shape[1] != 3 or n.shape != p.shape:
+        raise ValueError(f"points and normals must both be (n, 3), got {p.shape} and {n.shape}")
+    points = np.zeros(p.shape[0], dtype=BAKE_POINT_DTYPE)
+    points["p"], points["n"] = p, n
+    return points
+
+
+def make_bake_params(samples, streams=1, mode=RT_BAKE_IRRADIANCE, ray_depth=0, flags=0):
+    params = rt_bake_params()
+    params.struct_size = C.sizeof(rt_bake_params)
+    params.mode, params.samples, params.streams, params.ray_depth, params.flags = mode, samples, streams, ray_depth, flags
+    return params
 
 
 def make_denoise_params(width, height, iterations=0, sigma_depth=0.0, sigma_luminance=0.0, flags=0):
@@ -922,4 +963,50 @@ class Scene(_Handle):
     def trace_paths_device(self, rays_ptr, rng_ptr, n, out_rgb_ptr, ray_depth=0, flags=0):
         st = self._stats()
         _check(lib.rt_trace_paths(self._h, rays_ptr, rng_ptr, n, ray_depth, flags | RT_QUERY_DEVICE_POINTERS, out_rgb_ptr, C.byref(st)))
+        return st
+
+    def _bake_stats(self):
+        st = rt_bake_stats()
+        st.struct_size = C.sizeof(rt_bake_stats)
+        return st
+
+    def bake_rays(self, points, rng, mode=RT_BAKE_IRRADIANCE):
+        """One ray per BAKE_POINT_DTYPE record from the record's engine (rt_bake_rays): o = p + eps * n with a cosine-distributed d
+        (RT_BAKE_IRRADIANCE) or o = p with a uniform d (RT_BAKE_SH9).  rng: an RNG_DTYPE array that advances in place.  Returns
+        (array of RAY_DTYPE records, rt_query_stats)."""
+        points = _records(points, BAKE_POINT_DTYPE, None, "points")
+        n = points.shape[0]
+        rng = _engines(rng, n)
+        rays = np.zeros(n, dtype=RAY_DTYPE)
+        st = self._stats()
+        _check(lib.rt_bake_rays(self._h, points.ctypes.data, rng.ctypes.data, n, mode, 0, rays.ctypes.data, C.byref(st)))
+        return rays, st
+
+    def bake_rays_device(self, points_ptr, rng_ptr, n, out_ptr, mode=RT_BAKE_IRRADIANCE):
+        """The same on device memory of the scene's GPU: rt_rng 16-byte aligned, points and rays 4-byte."""
+        st = self._stats()
+        _check(lib.rt_bake_rays(self._h, points_ptr, rng_ptr, n, mode, RT_QUERY_DEVICE_POINTERS, out_ptr, C.byref(st)))
+        return st
+
+    def bake(self, points, rng, samples, streams=1, mode=RT_BAKE_IRRADIANCE, ray_depth=0, flags=0):
+        """Irradiance (n, 3) or SH9 coefficients (n, 9, 3) at the BAKE_POINT_DTYPE records (rt_bake): per point `streams` engines,
+        rng[i * streams + k], which advance in place and draw samples / streams paths each.  flags: RT_QUERY_REFERENCE_WALK,
+        RT_BAKE_LOCKSTEP.  Returns (float32 array, rt_bake_stats)."""
+        if flags & RT_QUERY_DEVICE_POINTERS:
+            raise ValueError("bake takes host arrays; device memory goes through bake_device")
+        if mode not in BAKE_FLOATS:
+            raise ValueError(f"mode must be RT_BAKE_IRRADIANCE or RT_BAKE_SH9, got {mode}")
+        points = _records(points, BAKE_POINT_DTYPE, None, "points")
+        n = points.shape[0]
+        rng = _engines(rng, n * max(1, streams))
+        out = np.zeros((n, 3) if mode == RT_BAKE_IRRADIANCE else (n, 9, 3), dtype=np.float32)
+        st = self._bake_stats()
+        params = make_bake_params(samples, streams, mode, ray_depth, flags)
+        _check(lib.rt_bake(self._h, points.ctypes.data, n, C.byref(params), rng.ctypes.data, out.ctypes.data, C.byref(st)))
+        return out, st
+
+    def bake_device(self, points_ptr, rng_ptr, n_points, out_ptr, samples, streams=1, mode=RT_BAKE_IRRADIANCE, ray_depth=0, flags=0):
+        st = self._bake_stats()
+        params = make_bake_params(samples, streams, mode, ray_depth, flags | RT_QUERY_DEVICE_POINTERS)
+        _check(lib.rt_bake(self._h, points_ptr, n_points, C.byref(params), rng_ptr, out_ptr, C.byref(st)))
         return st

@@ -9,7 +9,7 @@
 //                             k * brdf, the clamp return
 //   rq_bsdf_rays_kernel       rt_query_bsdf: classify and the ray of the light walk for a direction of the caller's
 //   rq_bsdf_finish_kernel     rt_query_bsdf: material_brdf and the finish kernel's pdf for that direction
-//   rq_path_advance_kernel    rt_trace_paths: after a bounce's queries, end a path (miss: rq_environment; END_*: the emission) or keep
+//   rq_path_advance_kernel    rt_trace_paths: after a bounce's queries (rq_path_end_or_keep, which rt_bake.h shares), end a path (miss: rq_environment; END_*: the emission) or keep
 //                             e[b], m[b] and make (o, d) its ray; after the last bounce fold L = e[b] + m[b] * L backwards
 //
 // A record is classified before any dependent work, as rq_surface_kernel does: no surface (hit.triangle or surface.material 0xFFFFFFFF)
@@ -162,43 +162,55 @@ __global__ __launch_bounds__(256) void rq_bsdf_finish_kernel(SceneView S, Scatte
 
 // ---- rt_trace_paths ------------------------------------------------------------------------------------------------------------------------
 // A chunk's state starts as zeros (the host clears it): tail 0, no bounce kept, not ended.
+// The end-or-keep step of a live path after a bounce's queries, shared with the baker (rt_bake.h): end it (miss: rq_environment; END_*:
+// the emission) with `tail`, RQ_PATH_ENDED in `word` and an invalid ray, or keep e[b], m[b], count the bounce in `word` and make (o, d) its ray.
+RT_DEV bool rq_path_end_or_keep(const SceneView &S, const PathView &V, uint32_t i, float *ray, uint32_t &word, F3 &tail) {
+    const uint32_t tri = V.hits[4 * (size_t)i].y;
+    tail = f3(0.f, 0.f, 0.f);
+    bool ended = true;
+    if (tri == RQ_NO_TRIANGLE) {                             // scene.cpp:90-97; an invalid ray sees 0, 0, 0
+        bool valid;
+        tail = rq_environment(S, f3(ray[0], ray[1], ray[2]), f3(ray[3], ray[4], ray[5]), valid);
+    } else {
+        const uint4 *sc = V.scatter + 4 * (size_t)i;
+        const uint4 c0 = sc[0], c1 = sc[1], c2 = sc[2];
+        const uint4 s1 = V.surfaces[4 * (size_t)i + 1];
+        const F3 emission = rq_f3(s1.x, s1.y, s1.z);
+        if (c1.w) tail = (c1.w & RQ_SCATTER_NO_SURFACE) ? tail : emission;                                    // :154-156, :161-163
+        else {
+            float *e = V.stack + 6 * ((size_t)(word & 0xFFu) * V.n + i);
+            e[0] = emission.x; e[1] = emission.y; e[2] = emission.z;
+            e[3] = __uint_as_float(c2.x); e[4] = __uint_as_float(c2.y); e[5] = __uint_as_float(c2.z);
+            word++;
+            rq_store_ray(ray, rq_f3(c0.x, c0.y, c0.z), rq_f3(c1.x, c1.y, c1.z));
+            ended = false;
+        }
+    }
+    if (ended) { word |= RQ_PATH_ENDED; rq_store_no_ray(ray); }
+    return ended;
+}
+// L = e[b] + m[b] * L backwards from the tail over the bounces kept.
+RT_DEV F3 rq_path_fold(const PathView &V, uint32_t i, uint32_t word, F3 tail) {
+    F3 L = tail;                                             // recLimit == 0 -> 0: a path that never ended keeps the tail 0
+    for (int b = (int)(word & 0xFFu) - 1; b >= 0; b--) {
+        const float *e = V.stack + 6 * ((size_t)b * V.n + i);
+        L = f3(e[0], e[1], e[2]) + f3(e[3], e[4], e[5]) * L;                                                  // :164
+    }
+    return L;
+}
+
 __global__ __launch_bounds__(256) void rq_path_advance_kernel(SceneView S, PathView V) {
     for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < V.n; i += gridDim.x * 256u) {
         float4 st = V.state[i];
         uint32_t word = __float_as_uint(st.w);
-        float *ray = V.rays + 6 * (size_t)i;
         if (!(word & RQ_PATH_ENDED)) {
-            const uint32_t tri = V.hits[4 * (size_t)i].y;
-            F3 tail = f3(0.f, 0.f, 0.f);
-            bool ended = true;
-            if (tri == RQ_NO_TRIANGLE) {                     // scene.cpp:90-97; an invalid ray sees 0, 0, 0
-                bool valid;
-                tail = rq_environment(S, f3(ray[0], ray[1], ray[2]), f3(ray[3], ray[4], ray[5]), valid);
-            } else {
-                const uint4 *sc = V.scatter + 4 * (size_t)i;
-                const uint4 c0 = sc[0], c1 = sc[1], c2 = sc[2];
-                const uint4 s1 = V.surfaces[4 * (size_t)i + 1];
-                const F3 emission = rq_f3(s1.x, s1.y, s1.z);
-                if (c1.w) tail = (c1.w & RQ_SCATTER_NO_SURFACE) ? tail : emission;                            // :154-156, :161-163
-                else {
-                    float *e = V.stack + 6 * ((size_t)(word & 0xFFu) * V.n + i);
-                    e[0] = emission.x; e[1] = emission.y; e[2] = emission.z;
-                    e[3] = __uint_as_float(c2.x); e[4] = __uint_as_float(c2.y); e[5] = __uint_as_float(c2.z);
-                    word++;
-                    rq_store_ray(ray, rq_f3(c0.x, c0.y, c0.z), rq_f3(c1.x, c1.y, c1.z));
-                    ended = false;
-                }
-            }
-            if (ended) { word |= RQ_PATH_ENDED; rq_store_no_ray(ray); }
+            F3 tail;
+            rq_path_end_or_keep(S, V, i, V.rays + 6 * (size_t)i, word, tail);
             st = make_float4(tail.x, tail.y, tail.z, __uint_as_float(word));
             if (!V.last) V.state[i] = st;
         }
         if (V.last) {
-            F3 L = f3(st.x, st.y, st.z);                     // recLimit == 0 -> 0: a path that never ended keeps the tail 0
-            for (int b = (int)(word & 0xFFu) - 1; b >= 0; b--) {
-                const float *e = V.stack + 6 * ((size_t)b * V.n + i);
-                L = f3(e[0], e[1], e[2]) + f3(e[3], e[4], e[5]) * L;                                          // :164
-            }
+            const F3 L = rq_path_fold(V, i, word, f3(st.x, st.y, st.z));
             float *out = V.rgb + 3 * (size_t)i;
             out[0] = L.x; out[1] = L.y; out[2] = L.z;
         }

@@ -84,6 +84,31 @@ struct PathView {
     uint32_t n, last;             // last: this was the last bounce, fold and write rgb
 };
 
+// The baker (rt_bake.h): the records of rt_bake_rays, or the slots of one chunk of rt_bake.  Slot s = point * streams + stream.
+enum { RQ_BAKE_CTR_SLOTS = 0,          // valid slots of the chunk (the start launch)
+       RQ_BAKE_CTR_PARKED = 1,         // of which every sample is in: the chunk is done when the two are equal
+       RQ_BAKE_CTR_LIVE_RAY_SLOTS = 2, // closest-hit queries made for live paths
+       RQ_BAKE_CTR_INVALID_POINTS = 3,
+       RQ_BAKE_CTR_WORDS = 4 };
+struct BakeView {
+    const float *points;          // n / streams x {p.xyz, n.xyz} (rt_bake_point), 4-byte aligned
+    uint4 *rng;                   // n (rt_rng), in and out, 16-byte aligned
+    float *rays;                  // n x {o.xyz, d.xyz}: the ray of a record or of a slot's sample; an invalid ray for an invalid or parked one
+    float *dir0;                  // rt_bake: n x 3, the first direction of the slot's sample in flight; null in rt_bake_rays
+    float *acc;                   // rt_bake: floats x n, [j][slot]
+    uint32_t *left;               // rt_bake: n, the slot's samples not yet in; null in rt_bake_rays
+    float *out;                   // the resolve launch: n floats, [point][j]
+    unsigned long long *ctr;      // RQ_BAKE_CTR_*
+    unsigned long long *totals;   // RQ_TOTAL_* (rt_bake_rays counts its invalid records there)
+    uint32_t n;                   // records or slots; in the resolve launch the floats of the chunk's answer
+    uint32_t streams;             // K; 1 in rt_bake_rays
+    uint32_t per_stream;          // q = samples / K
+    uint32_t depth, lockstep, last; // the advance launch: ray_depth, RT_BAKE_LOCKSTEP, this round spends the depth
+    int32_t mode;                 // RT_BAKE_IRRADIANCE or RT_BAKE_SH9
+    uint32_t floats;              // 3 or 27
+    float scale;
+};
+
 // The engine states std::minstd_rand can be in: 1 .. 2^31 - 2.  Any other x is refused (host arrays) or marked invalid (device arrays)
 // before a draw: 0 stays 0 for ever, and rng_n01's rejection loop would not end.
 __host__ __device__ inline bool rq_rng_valid(uint32_t x) { return x - 1u < 2147483646u; }
@@ -105,5 +130,8 @@ uint32_t query_launch_scatter_finish(const rt_scene *scene, const ScatterView &V
 uint32_t query_launch_bsdf_rays(const rt_scene *scene, const ScatterView &V, hipStream_t stream);
 uint32_t query_launch_bsdf_finish(const rt_scene *scene, const ScatterView &V, hipStream_t stream);
 uint32_t query_launch_path_advance(const rt_scene *scene, const PathView &V, hipStream_t stream);
+uint32_t query_launch_bake_rays(const rt_scene *scene, const BakeView &B, hipStream_t stream);
+uint32_t query_launch_bake_advance(const rt_scene *scene, const PathView &V, const BakeView &B, hipStream_t stream);
+uint32_t query_launch_bake_resolve(const rt_scene *scene, const BakeView &B, hipStream_t stream);
 
 } // namespace rtamd

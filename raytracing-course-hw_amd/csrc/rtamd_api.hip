@@ -20,6 +20,7 @@
 #include "device/rt_query.h"
 #include "device/rt_query_surface.h"
 #include "device/rt_query_scatter.h"
+#include "device/rt_bake.h"
 #include "device/rt_persistent.h"
 #include "device/rt_kernels_hw6.h"
 #include "device/rt_persistent_hw6.h"
@@ -1176,6 +1177,25 @@ uint32_t rtamd::query_launch_bsdf_finish(const rt_scene *scene, const ScatterVie
 
 uint32_t rtamd::query_launch_path_advance(const rt_scene *scene, const PathView &V, hipStream_t stream) {
     hipLaunchKernelGGL(dev::rq_path_advance_kernel, dim3(query_geometry(scene, V.n).flat_blocks), dim3(256), 0, stream, scene->view, V);
+    HIP_CHECK(hipGetLastError());
+    return 1u;
+}
+
+// The baker (device/rt_bake.h): flat launches, one lane per record, per slot, per float of the answer.
+uint32_t rtamd::query_launch_bake_rays(const rt_scene *scene, const BakeView &B, hipStream_t stream) {
+    hipLaunchKernelGGL(dev::rq_bake_rays_kernel, dim3(query_geometry(scene, B.n).flat_blocks), dim3(256), 0, stream, scene->view, B);
+    HIP_CHECK(hipGetLastError());
+    return 1u;
+}
+
+uint32_t rtamd::query_launch_bake_advance(const rt_scene *scene, const PathView &V, const BakeView &B, hipStream_t stream) {
+    hipLaunchKernelGGL(dev::rq_bake_advance_kernel, dim3(query_geometry(scene, V.n).flat_blocks), dim3(256), 0, stream, scene->view, V, B);
+    HIP_CHECK(hipGetLastError());
+    return 1u;
+}
+
+uint32_t rtamd::query_launch_bake_resolve(const rt_scene *scene, const BakeView &B, hipStream_t stream) {
+    hipLaunchKernelGGL(dev::rq_bake_resolve_kernel, dim3(query_geometry(scene, B.n).flat_blocks), dim3(256), 0, stream, scene->view, B);
     HIP_CHECK(hipGetLastError());
     return 1u;
 }

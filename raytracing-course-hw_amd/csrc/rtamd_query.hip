@@ -1,7 +1,8 @@
 // Batched ray queries through the C-ABI (include/rtamd.h: rt_query_closest, rt_query_light_pdf, rt_query_occluded), the first-hit layer over them
 // (rt_query_surface, rt_query_environment, rt_camera_rays, rt_render_guides) and the bounce step (rt_query_scatter, rt_query_bsdf,
-// rt_trace_paths, rt_rng_*): argument checks, the chunking, the staging and the statistics.  No kernel and no kernel header here: the
-// kernels (device/rt_query.h, device/rt_query_surface.h, device/rt_query_scatter.h) live in rtamd_api.hip,
+// rt_trace_paths, rt_rng_*) and its first caller, the baker (rt_bake_rays, rt_bake): argument checks, the chunking, the staging, the
+// rounds and the statistics.  No kernel and no kernel header here: the
+// kernels (device/rt_query.h, device/rt_query_surface.h, device/rt_query_scatter.h, device/rt_bake.h) live in rtamd_api.hip,
 // where every __global__ keeps one definition, and are launched through query_launch_* (device/rt_types_query.h).
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -17,6 +18,7 @@ using namespace rtamd;
 
 namespace {
 
+static_assert(sizeof(rt_bake_point) == 24 && sizeof(rt_bake_params) == 32 && sizeof(rt_bake_stats) == 88, "the baker's records as include/rtamd.h lays them out");
 static_assert(sizeof(rt_ray) == 24 && sizeof(rt_hit) == 64 && sizeof(rt_surface) == 64 && sizeof(rt_rng) == 16 && sizeof(rt_scatter) == 64,
               "rt_ray is 24 bytes, rt_rng 16, rt_hit, rt_surface and rt_scatter 64: the kernels read and write them as words");
 
@@ -28,18 +30,21 @@ size_t query_chunk() { return std::min(QUERY_CHUNK, (size_t)std::max(64, env_pos
 // The staging of one chunk, carved out of one allocation that the scene keeps: counters first, then the arrays in 256-byte steps.
 // The two ray queries need the first eight parts; a surface query or a guide pass (STAGE_FIRST_HIT) grows the allocation by the next
 // two, an occlusion query (STAGE_OCCLUSION) by the last two: a bound and an answer byte per ray.  The bounce step (STAGE_SCATTER) takes
-// the first-hit layer's parts and four more: the engines, the rt_scatter records, the rays of the light walk and its answers.
+// the first-hit layer's parts and four more: the engines, the rt_scatter records, the rays of the light walk and its answers.  The
+// baker (STAGE_BAKE) takes the bounce step's parts and its per-slot state: the points, the first directions, `bake_floats` accumulator
+// floats, the samples left, its counters and, with host arrays, the chunk's answer.
 const size_t PLANE_FLOATS = 10; // albedo 3, normal 3, depth 1, emission 3
-enum StageParts { STAGE_WALK, STAGE_FIRST_HIT, STAGE_OCCLUSION, STAGE_SCATTER };
+enum StageParts { STAGE_WALK, STAGE_FIRST_HIT, STAGE_OCCLUSION, STAGE_SCATTER, STAGE_BAKE };
 struct QueryStage {
     uint32_t *ctr; unsigned long long *totals;
     float *rays; uint8_t *out; float4 *rec; uint32_t *q_fast, *q_exact, *ovf;
     uint8_t *surf; float *planes;
     float *tmax; uint8_t *occ;
     uint8_t *rng, *scat; float *walk_rays, *light_pdf;
+    float *bake_points, *bake_dir0, *bake_acc, *bake_out; uint32_t *bake_left; unsigned long long *bake_ctr;
 };
-QueryStage query_stage(rt_scene *scene, StageParts parts) {
-    const bool scatter = parts == STAGE_SCATTER, first_hit = parts == STAGE_FIRST_HIT || scatter, occlusion = parts == STAGE_OCCLUSION;
+QueryStage query_stage(rt_scene *scene, StageParts parts, size_t bake_floats = 0, bool bake_out = false) {
+    const bool bake = parts == STAGE_BAKE, scatter = parts == STAGE_SCATTER || bake, first_hit = parts == STAGE_FIRST_HIT || scatter, occlusion = parts == STAGE_OCCLUSION;
     const size_t C = QUERY_CHUNK, ovf_words = query_ovf_words(scene);
     size_t at = 0;
     auto take = [&](size_t bytes) { const size_t here = at; at += (bytes + 255u) & ~(size_t)255u; return here; };
@@ -51,6 +56,11 @@ QueryStage query_stage(rt_scene *scene, StageParts parts) {
     if (occlusion) { o_tmax = take(C * sizeof(float)); o_occ = take(C); }
     size_t o_rng = 0, o_scat = 0, o_walk = 0, o_lpdf = 0;
     if (scatter) { o_rng = take(C * sizeof(rt_rng)); o_scat = take(C * sizeof(rt_scatter)); o_walk = take(C * sizeof(rt_ray)); o_lpdf = take(C * sizeof(float)); }
+    size_t o_bpts = 0, o_bdir = 0, o_bacc = 0, o_bleft = 0, o_bctr = 0, o_bout = 0;
+    if (bake) {
+        o_bpts = take(C * sizeof(rt_bake_point)); o_bdir = take(C * 12); o_bacc = take(C * bake_floats * 4); o_bleft = take(C * 4);
+        o_bctr = take(RQ_BAKE_CTR_WORDS * 8); o_bout = take(bake_out ? C * bake_floats * 4 : 0);
+    }
     grow(scene->query_stage, scene->query_stage_bytes, at);
     uint8_t *b = scene->query_stage;
     QueryStage s;
@@ -62,6 +72,9 @@ QueryStage query_stage(rt_scene *scene, StageParts parts) {
     s.tmax = occlusion ? (float *)(b + o_tmax) : nullptr; s.occ = occlusion ? b + o_occ : nullptr;
     s.rng = scatter ? b + o_rng : nullptr; s.scat = scatter ? b + o_scat : nullptr;
     s.walk_rays = scatter ? (float *)(b + o_walk) : nullptr; s.light_pdf = scatter ? (float *)(b + o_lpdf) : nullptr;
+    s.bake_points = bake ? (float *)(b + o_bpts) : nullptr; s.bake_dir0 = bake ? (float *)(b + o_bdir) : nullptr;
+    s.bake_acc = bake ? (float *)(b + o_bacc) : nullptr; s.bake_left = bake ? (uint32_t *)(b + o_bleft) : nullptr;
+    s.bake_ctr = bake ? (unsigned long long *)(b + o_bctr) : nullptr; s.bake_out = bake && bake_out ? (float *)(b + o_bout) : nullptr;
     return s;
 }
 
@@ -208,6 +221,36 @@ uint32_t launch_ride_light_pdf(const rt_scene *scene, const QueryStage &S, size_
 uint8_t *path_stack(rt_scene *scene, size_t paths, int depth) {
     grow(scene->path_stack, scene->path_stack_bytes, paths * (16u + 24u * (size_t)depth));
     return scene->path_stack;
+}
+
+// One round of a chunk's m paths, for rt_trace_paths and rt_bake: closest hit, surface, scatter sample, light walk, scatter finish over
+// the rays in the staging.  `later`: not the chunk's first round -- the counters have been used, and paths that have ended (or slots
+// that are parked) ride along as invalid rays, so the closest-hit walk counts into the RIDE pair.
+uint32_t launch_round(rt_scene *scene, const QueryStage &S, const ScatterView &V, size_t m, uint32_t flags, bool later, hipStream_t stream) {
+    if (later) HIP_CHECK(hipMemsetAsync(S.ctr, 0, RQ_CTR_WORDS * 4, stream));
+    QueryView Q = walk_view(scene, S, m, flags, S.rays);
+    Q.hits = (uint4 *)S.out;
+    if (later) Q.totals = S.totals + RQ_TOTAL_RIDE_EXACT; // the caller's own invalid rays were counted in the first round
+    uint32_t launches = query_launch_closest(scene, Q, stream);
+    launches += query_launch_surface(scene, surface_view(scene, S, m, S.out, S.surf), stream);
+    launches += query_launch_scatter_sample(scene, V, stream);
+    launches += launch_ride_light_pdf(scene, S, m, flags, true, stream);
+    return launches + query_launch_scatter_finish(scene, V, stream);
+}
+
+// What rt_bake_rays and rt_bake refuse alike.
+const uint32_t BAKE_RAYS_FLAGS = RT_QUERY_DEVICE_POINTERS;
+const uint32_t BAKE_FLAGS = RT_QUERY_DEVICE_POINTERS | RT_QUERY_REFERENCE_WALK | RT_BAKE_LOCKSTEP;
+int check_bake_mode(int32_t mode, const std::string &who, const char *field) {
+    if (mode != RT_BAKE_IRRADIANCE && mode != RT_BAKE_SH9)
+        return fail(RT_ERR_INVALID_ARG, who + field + " = " + std::to_string(mode) + " is neither RT_BAKE_IRRADIANCE nor RT_BAKE_SH9");
+    return RT_OK;
+}
+int check_bake_engines(const rt_rng *rng, size_t n, const std::string &who) {
+    for (size_t i = 0; i < n; i++)
+        if (!rq_rng_valid(rng[i].x))
+            return fail(RT_ERR_INVALID_ARG, who + "rng[" + std::to_string(i) + "].x = " + std::to_string(rng[i].x) + " is no state of the engine (1 .. 2147483646)");
+    return RT_OK;
 }
 
 } // namespace
@@ -467,15 +510,7 @@ int rt_trace_paths(rt_scene *scene, const rt_ray *rays, rt_rng *rng, size_t n, i
             P.n = (uint32_t)m;
             uint32_t launches = 0;
             for (int b = 0; b < depth; b++) {
-                if (b) HIP_CHECK(hipMemsetAsync(S.ctr, 0, RQ_CTR_WORDS * 4, stream));
-                QueryView Q = walk_view(scene, S, m, flags, S.rays);
-                Q.hits = (uint4 *)S.out;
-                if (b) Q.totals = S.totals + RQ_TOTAL_RIDE_EXACT; // ended paths ride along as invalid rays; the caller's own were counted at b == 0
-                launches += query_launch_closest(scene, Q, stream);
-                launches += query_launch_surface(scene, surface_view(scene, S, m, S.out, S.surf), stream);
-                launches += query_launch_scatter_sample(scene, V, stream);
-                launches += launch_ride_light_pdf(scene, S, m, flags, true, stream);
-                launches += query_launch_scatter_finish(scene, V, stream);
+                launches += launch_round(scene, S, V, m, flags, b != 0, stream);
                 P.last = b == depth - 1 ? 1u : 0u;
                 launches += query_launch_path_advance(scene, P, stream);
             }
@@ -486,6 +521,165 @@ int rt_trace_paths(rt_scene *scene, const rt_ray *rays, rt_rng *rng, size_t n, i
             HIP_CHECK(hipMemcpyAsync(out_rgb + 3 * first, S.rec, m * 3 * sizeof(float), hipMemcpyDeviceToHost, stream));
             HIP_CHECK(hipMemcpyAsync(rng + first, S.rng, m * sizeof(rt_rng), hipMemcpyDeviceToHost, stream));
         });
+}
+
+int rt_bake_rays(rt_scene *scene, const rt_bake_point *points, rt_rng *rng, size_t n, int32_t mode, uint32_t flags, rt_ray *out, rt_query_stats *stats) {
+    const std::string who = "rt_bake_rays: ";
+    if (stats && stats->struct_size != sizeof(rt_query_stats)) return fail(RT_ERR_INVALID_ARG, who + "struct_size mismatch (ABI skew)");
+    if (const int rc = check_bake_mode(mode, who, "mode")) return rc;
+    if (flags & ~BAKE_RAYS_FLAGS) return fail(RT_ERR_INVALID_ARG, who + "flags other than RT_QUERY_DEVICE_POINTERS");
+    if (n && (!points || !rng || !out)) return fail(RT_ERR_INVALID_ARG, who + "null argument");
+    const bool on_device = (flags & RT_QUERY_DEVICE_POINTERS) != 0;
+    if (!on_device)
+        if (const int rc = check_bake_engines(rng, n, who)) return rc;
+    if (const int rc = check_call(scene, stats, flags, BAKE_RAYS_FLAGS, "RT_QUERY_DEVICE_POINTERS", who)) return rc;
+    if (n && on_device && ((uintptr_t)rng & 15u)) return fail(RT_ERR_INVALID_ARG, who + "with RT_QUERY_DEVICE_POINTERS the rt_rng array must be 16-byte aligned");
+    if (n && on_device && (((uintptr_t)points | (uintptr_t)out) & 3u)) return fail(RT_ERR_INVALID_ARG, who + "with RT_QUERY_DEVICE_POINTERS points and out must be 4-byte aligned");
+    return answer(scene, n, stats, who, STAGE_BAKE, // the points of a chunk are staged with the baker's state
+        [&](const QueryStage &S, size_t first, size_t m, hipStream_t stream) {
+            if (on_device) return;
+            HIP_CHECK(hipMemcpyAsync(S.bake_points, points + first, m * sizeof(rt_bake_point), hipMemcpyHostToDevice, stream));
+            HIP_CHECK(hipMemcpyAsync(S.rng, rng + first, m * sizeof(rt_rng), hipMemcpyHostToDevice, stream));
+        },
+        [&](const QueryStage &S, size_t first, size_t m, hipStream_t stream) {
+            BakeView B{};
+            B.points = on_device ? (const float *)(points + first) : S.bake_points;
+            B.rng = (uint4 *)(on_device ? rng + first : (rt_rng *)S.rng);
+            B.rays = on_device ? (float *)(out + first) : S.rays;
+            B.totals = S.totals; B.n = (uint32_t)m; B.streams = 1u; B.mode = mode;
+            return query_launch_bake_rays(scene, B, stream);
+        },
+        [&](const QueryStage &S, size_t first, size_t m, hipStream_t stream) {
+            if (on_device) return;
+            HIP_CHECK(hipMemcpyAsync(out + first, S.rays, m * sizeof(rt_ray), hipMemcpyDeviceToHost, stream));
+            HIP_CHECK(hipMemcpyAsync(rng + first, S.rng, m * sizeof(rt_rng), hipMemcpyDeviceToHost, stream));
+        });
+}
+
+int rt_bake(rt_scene *scene, const rt_bake_point *points, size_t n_points, const rt_bake_params *params, rt_rng *rng, float *out, rt_bake_stats *stats) {
+    const std::string who = "rt_bake: ";
+    if (!params) return fail(RT_ERR_INVALID_ARG, who + "null argument (params)");
+    if (params->struct_size != sizeof(rt_bake_params)) return fail(RT_ERR_INVALID_ARG, who + "params.struct_size mismatch (ABI skew)");
+    if (stats && stats->struct_size != sizeof(rt_bake_stats)) return fail(RT_ERR_INVALID_ARG, who + "stats.struct_size mismatch (ABI skew)");
+    if (const int rc = check_bake_mode(params->mode, who, "params.mode")) return rc;
+    const uint32_t flags = params->flags;
+    if (flags & ~BAKE_FLAGS) return fail(RT_ERR_INVALID_ARG, who + "params.flags other than RT_QUERY_DEVICE_POINTERS | RT_QUERY_REFERENCE_WALK | RT_BAKE_LOCKSTEP");
+    if (params->reserved[0] || params->reserved[1]) return fail(RT_ERR_INVALID_ARG, who + "params.reserved must be zero");
+    if (params->streams < 0) return fail(RT_ERR_INVALID_ARG, who + "params.streams must not be negative");
+    if (params->streams > 64) return fail(RT_ERR_LIMIT, who + "params.streams above 64");
+    const size_t K = params->streams ? (size_t)params->streams : 1u;
+    if (params->samples < 1) return fail(RT_ERR_INVALID_ARG, who + "params.samples must be at least 1");
+    if ((size_t)params->samples % K) return fail(RT_ERR_INVALID_ARG, who + "params.samples = " + std::to_string(params->samples) + " is no multiple of params.streams = " + std::to_string(K));
+    const int depth = params->ray_depth > 0 ? params->ray_depth : 6;
+    if (depth > RT_MAX_DEPTH) return fail(RT_ERR_LIMIT, who + "params.ray_depth above " + std::to_string(RT_MAX_DEPTH));
+    if (n_points > (((size_t)1 << 31) - 1u) / K) return fail(RT_ERR_LIMIT, who + "n_points * params.streams must stay below 2^31");
+    if (n_points && (!points || !rng || !out)) return fail(RT_ERR_INVALID_ARG, who + "null argument");
+    const bool on_device = (flags & RT_QUERY_DEVICE_POINTERS) != 0, lockstep = (flags & RT_BAKE_LOCKSTEP) != 0;
+    if (!on_device)
+        if (const int rc = check_bake_engines(rng, n_points * K, who)) return rc;
+    if (!scene) return fail(RT_ERR_INVALID_ARG, who + "null argument (scene)");
+    if (const int rc = check_call(scene, nullptr, 0u, 0u, "", who)) return rc;
+    if (n_points && on_device && ((uintptr_t)rng & 15u)) return fail(RT_ERR_INVALID_ARG, who + "with RT_QUERY_DEVICE_POINTERS the rt_rng array must be 16-byte aligned");
+    if (n_points && on_device && (((uintptr_t)points | (uintptr_t)out) & 3u)) return fail(RT_ERR_INVALID_ARG, who + "with RT_QUERY_DEVICE_POINTERS points and out must be 4-byte aligned");
+    const uint32_t walk_flags = flags & (RT_QUERY_DEVICE_POINTERS | RT_QUERY_REFERENCE_WALK);
+    const size_t floats = params->mode == RT_BAKE_SH9 ? 27u : 3u;
+    const uint32_t q = (uint32_t)((size_t)params->samples / K);
+    const double pi = 3.14159265358979323846;
+    const float scale = params->mode == RT_BAKE_SH9 ? (float)(4.0 * pi / (double)params->samples) : (float)(pi / (double)params->samples);
+    return guarded(who, [&]() -> int {
+        const double t0 = now_ms();
+        rt_bake_stats st{};
+        st.struct_size = sizeof(rt_bake_stats);
+        st.reference_exact = scene->view.exact_boxes == 1u ? 1u : 0u;
+        st.points = n_points;
+        if (n_points) {
+            HIP_CHECK(hipSetDevice(scene->device));
+            hipStream_t stream = nullptr;
+            const QueryStage S = query_stage(scene, STAGE_BAKE, floats, !on_device);
+            const size_t chunk_points = query_chunk() / K; // whole points: the stream sum never crosses a seam (the chunk's minimum of 64 covers K <= 64)
+            const size_t slots_max = std::min(n_points, chunk_points) * K;
+            ensure_materials(scene, stream);
+            uint8_t *stack = path_stack(scene, slots_max, depth);
+            HIP_CHECK(hipMemsetAsync(S.totals, 0, RQ_TOTAL_WORDS * 8, stream));
+            float ms_sum = 0.f;
+            auto mark = [&](bool stop) { // the scene's two events around a stretch of launches; add_ms reads them once the stream has been waited for
+                HIP_CHECK(hipEventRecord(stop ? scene->ev_stop : scene->ev_start, stream));
+            };
+            auto add_ms = [&]() { float ms = 0.f; HIP_CHECK(hipEventElapsedTime(&ms, scene->ev_start, scene->ev_stop)); ms_sum += ms; };
+            for (size_t first = 0; first < n_points; first += chunk_points) {
+                const size_t pts = std::min(chunk_points, n_points - first), m = pts * K;
+                if (!on_device) {
+                    HIP_CHECK(hipMemcpyAsync(S.bake_points, points + first, pts * sizeof(rt_bake_point), hipMemcpyHostToDevice, stream));
+                    HIP_CHECK(hipMemcpyAsync(S.rng, rng + first * K, m * sizeof(rt_rng), hipMemcpyHostToDevice, stream));
+                }
+                HIP_CHECK(hipMemsetAsync(stack, 0, slots_max * 16u, stream)); // tail 0, no bounce kept, not ended
+                HIP_CHECK(hipMemsetAsync(S.ctr, 0, RQ_CTR_WORDS * 4, stream));
+                HIP_CHECK(hipMemsetAsync(S.bake_ctr, 0, RQ_BAKE_CTR_WORDS * 8, stream));
+                const ScatterView V = scatter_view(S, m, ScatterArrays{(const rt_ray *)S.rays, (const rt_hit *)S.out, (const rt_surface *)S.surf,
+                                                                       on_device ? rng + first * K : (rt_rng *)S.rng, (rt_scatter *)S.scat});
+                PathView P{};
+                P.rays = S.rays; P.hits = V.hits; P.surfaces = V.surfaces; P.scatter = V.out;
+                P.state = (float4 *)stack; P.stack = (float *)(stack + slots_max * 16u);
+                P.n = (uint32_t)m;
+                BakeView B{};
+                B.points = on_device ? (const float *)(points + first) : S.bake_points;
+                B.rng = V.rng; B.rays = S.rays; B.dir0 = params->mode == RT_BAKE_SH9 ? S.bake_dir0 : nullptr; B.acc = S.bake_acc; B.left = S.bake_left;
+                B.out = on_device ? out + first * floats : S.bake_out;
+                B.ctr = S.bake_ctr; B.totals = S.totals;
+                B.n = (uint32_t)m; B.streams = (uint32_t)K; B.per_stream = q; B.depth = (uint32_t)depth; B.lockstep = lockstep ? 1u : 0u;
+                B.mode = params->mode; B.floats = (uint32_t)floats; B.scale = scale;
+                unsigned long long ctr[RQ_BAKE_CTR_WORDS] = {};
+                auto poll = [&]() { HIP_CHECK(hipMemcpy(ctr, S.bake_ctr, sizeof ctr, hipMemcpyDeviceToHost)); add_ms(); }; // waits for the stream
+                uint64_t rounds = 0;
+                auto round = [&](bool last) {
+                    st.launches += launch_round(scene, S, V, m, walk_flags, rounds != 0, stream);
+                    B.last = last ? 1u : 0u;
+                    st.launches += query_launch_bake_advance(scene, P, B, stream);
+                    rounds++;
+                };
+                mark(false);
+                st.launches += query_launch_bake_rays(scene, B, stream);
+                if (lockstep) { // the plain composition: every slot starts sample j in the same round, every sample takes `depth` rounds
+                    for (uint32_t j = 0; j < q; j++)
+                        for (int b = 0; b < depth; b++) round(b == depth - 1);
+                    mark(true);
+                    poll();
+                } else {        // regeneration: a round at a time, until every valid slot is parked
+                    mark(true);
+                    poll();
+                    while (ctr[RQ_BAKE_CTR_PARKED] < ctr[RQ_BAKE_CTR_SLOTS]) {
+                        mark(false);
+                        round(false);
+                        mark(true);
+                        poll();
+                    }
+                }
+                BakeView R = B;
+                R.n = (uint32_t)(pts * floats);
+                mark(false);
+                st.launches += query_launch_bake_resolve(scene, R, stream);
+                mark(true);
+                if (!on_device) {
+                    HIP_CHECK(hipMemcpyAsync(out + first * floats, S.bake_out, pts * floats * sizeof(float), hipMemcpyDeviceToHost, stream));
+                    HIP_CHECK(hipMemcpyAsync(rng + first * K, S.rng, m * sizeof(rt_rng), hipMemcpyDeviceToHost, stream));
+                }
+                HIP_CHECK(hipStreamSynchronize(stream)); // the next chunk reuses the staging
+                add_ms();
+                st.invalid_points += ctr[RQ_BAKE_CTR_INVALID_POINTS];
+                st.paths += ctr[RQ_BAKE_CTR_SLOTS] * q;
+                st.live_ray_slots += ctr[RQ_BAKE_CTR_LIVE_RAY_SLOTS];
+                st.rounds += rounds;
+                st.ray_slots += rounds * m;
+            }
+            unsigned long long totals[RQ_TOTAL_WORDS];
+            HIP_CHECK(hipMemcpy(totals, S.totals, sizeof totals, hipMemcpyDeviceToHost));
+            st.exact_walks = totals[RQ_TOTAL_EXACT] + totals[RQ_TOTAL_RIDE_EXACT];
+            st.kernel_ms = ms_sum;
+        }
+        st.total_ms = now_ms() - t0;
+        if (stats) *stats = st;
+        return RT_OK;
+    });
 }
 
 } // extern "C"
