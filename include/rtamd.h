@@ -697,6 +697,46 @@ int rt_bake_rays(rt_scene *scene, const rt_bake_point *points, rt_rng *rng /* in
 int rt_bake(rt_scene *scene, const rt_bake_point *points, size_t n_points, const rt_bake_params *params,
             rt_rng *rng /* n_points*streams, [i*streams+k], in and out */, float *out, rt_bake_stats *stats /* nullable */);
 
+/* ---- rt_render_paths, rt_render_bake: a caller's paths at render speed -----------------------------------------------------------
+ * rt_trace_paths and rt_bake (RT_BAKE_IRRADIANCE) through the persistent render kernel: one launch per chunk instead of a round of
+ * launches per bounce, no record through memory between the stages, no dead ray slots.  The kernel is rt_render's, compiled with a
+ * path source (device/rt_path_source.h): a slot's first ray comes from the caller's array, or from rt_bake_rays' expressions on the
+ * slot's point, instead of the camera; sum, engine and end of slot are a resumable render's (rt_accum_*) over 24 bytes per slot.  The
+ * frame is an unsharded strip 8 pixels wide and 8 * ceil(n / 64) high, whose pixel slots are the record indices.  ABI version 6 still.
+ *
+ * Contract   on a scene whose renders and queries report reference_exact = 1, out and rng are bit for bit rt_trace_paths' / rt_bake's
+ *          for the same arguments; the composed calls are the referees (tests/test_gpu_render_paths.py).  Floats leave through the
+ *          queries' rule: a NaN has its sign bit set.  An engine leaves with saved = 0 whenever has_saved is 0.  Invalid records (the
+ *          referees' rules) answer zeros, keep their engines and are counted.  On a scene with reference_exact = 0
+ *          (RT_BUILD_DEVICE_BVH, RTAMD_NO_EXACT_BOXES) the calls are served, the stats say reference_exact = 0, the answers are the
+ *          persistent walkers' padded-box answers, and equality with the composed calls is NOT promised.
+ * First rays the walkers were not derived for -- an origin outside the walkers' node grid, a ray off rt_query_closest's fast list
+ *          (|o| beyond scene and camera, a zero direction component, |d| outside 1/16 .. 16), one that pierces a tripwire -- are
+ *          walked by the exact role from the start and counted in exact_walks.
+ * Refusals   before any device work.  RT_ERR_INVALID_ARG: null arguments, struct_size, reserved words, flags other than
+ *          RT_QUERY_DEVICE_POINTERS (alignments as rt_trace_paths / rt_bake), a host engine outside 1 .. 2^31-2 (the record is named).
+ *          RT_ERR_LIMIT: ray_depth > 16, streams > 64, n_points * streams >= 2^31, samples / streams >= 2^25.  RT_ERR_UNSUPPORTED:
+ *          RT_BAKE_SH9 (rt_bake serves it), hw6 and .txt scenes, and whatever keeps the persistent hw8 kernel from the scene
+ *          (RTAMD_KERNEL=wavefront|mega, trees beyond its stack columns): there is no fallback, as with rt_accum_create.  n = 0: RT_OK.
+ * stats    rt_query_stats: rays = n, invalid_rays, exact_walks = exact closest hits + exact light sums of the launches, kernel_ms =
+ *          the render launches' (the pack and unpack launches are in total_ms), launches, reference_exact.  rt_bake_stats: points,
+ *          invalid_points, paths, exact_walks, times, launches; rounds = ray_slots = live_ray_slots = 0: there are no rounds.
+ * Memory   a chunk holds 2,073,600 slots (whole points: floor(chunk / K)), the pixel slots of a 1080p frame, so the kernel's path
+ *          records never exceed what rt_render of that frame allocates (256 bytes per slot at depth 6).  The state (24 bytes per slot
+ *          of a chunk, 50 MB) and, with host arrays, the chunk's records (52 bytes per slot) are kept by the scene, not part of
+ *          rt_scene_info.device_bytes, freed with it.  RTAMD_QUERY_CHUNK lowers the chunk.  The calls only read the scene: an
+ *          rt_accum of it and the next rt_render see nothing of them.
+ * Measured on one MI355X, synth_room_v1, device pointers, depth 6, kernel time, alternating with the referee in one process
+ *          (profiles/r30_render_paths.txt): the 2,073,600 camera-ray records of the 1080p frame 5.52 ms = 376
+ *          Mpaths/s against rt_trace_paths' 44.55 ms, rt_render(samples = 1) of that frame 5.22 ms; 2,073,600 texels x 16 samples,
+ *          K = 1: 79.9 ms = 415 Mpaths/s against rt_bake's 745 ms; 4,096 points x 4,096 samples, K = 64: 62.9 ms = 267 Mpaths/s
+ *          against 368 ms.  The chunk: 262,144 slots 8.55 and 123.4 ms, 1,048,576 5.66 and 94.8 ms, 2,073,600 5.52 and 79.9 ms.  The
+ *          two kernels: 87 VGPRs, no scratch, five waves per SIMD, 31,680 bytes of LDS; the renderer's own kernels are unchanged. */
+int rt_render_paths(rt_scene *scene, const rt_ray *rays, rt_rng *rng /* in and out */, size_t n, int32_t ray_depth,
+                    uint32_t flags, float *out_rgb /* n*3 */, rt_query_stats *stats /* nullable */);
+int rt_render_bake(rt_scene *scene, const rt_bake_point *points, size_t n_points, const rt_bake_params *params,
+                   rt_rng *rng /* n_points*streams, [i*streams+k], in and out */, float *out /* n_points*3 */, rt_bake_stats *stats /* nullable */);
+
 /* ---- denoised previews: a variance-guided edge-avoiding filter on the guide images -------------------------------------------
  * What consumes rt_render_guides' planes: a noisy frame of few samples in, a usable preview out.  An a-trous wavelet filter (five
  * taps per axis, stride doubling per level) whose weights stop at normal, depth and -- with rt_noise_estimate's map -- luminance edges

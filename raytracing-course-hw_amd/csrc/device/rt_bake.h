@@ -29,28 +29,32 @@ RT_DEV void rq_bake_count(unsigned long long *ctr, int which, bool flag) {
     if (flag && (uint32_t)(__ffsll((long long)mask) - 1) == (threadIdx.x & 63u)) atomicAdd(ctr + which, (unsigned long long)__popcll(mask));
 }
 
-// The point of record i and whether it is valid; n is read in irradiance mode only.
-RT_DEV bool rq_bake_point(const BakeView &B, uint32_t i, F3 &p, F3 &n) {
-    const uint32_t point = i / B.streams;
-    const float *q = B.points + 6 * (size_t)point;
+// Point `point` of `points` and whether its numbers are valid (its engines: rq_bake_point); n is read in irradiance mode only.  Shared with
+// the path source of the persistent kernel (rt_path_source.h).
+RT_DEV bool rq_bake_point_read(const float *points, uint32_t point, int32_t mode, F3 &p, F3 &n) {
+    const float *q = points + 6 * (size_t)point;
     p = f3(q[0], q[1], q[2]);
     n = f3(0.f, 0.f, 0.f);
     bool ok = rq_finite(p.x) && rq_finite(p.y) && rq_finite(p.z);
-    if (B.mode == RQ_BAKE_IRRADIANCE) {
+    if (mode == RQ_BAKE_IRRADIANCE) {
         n = f3(q[3], q[4], q[5]);
         ok = ok && rq_valid_ray(p, n);                       // finite, and n != 0
     }
+    return ok;
+}
+// The point of record i and whether it is valid.
+RT_DEV bool rq_bake_point(const BakeView &B, uint32_t i, F3 &p, F3 &n) {
+    const uint32_t point = i / B.streams;
+    bool ok = rq_bake_point_read(B.points, point, B.mode, p, n);
     const uint4 *e = B.rng + (size_t)point * B.streams;
     for (uint32_t k = 0; k < B.streams; k++) ok = ok && rq_rng_valid(e[k].x);
     return ok;
 }
 
-// The ray of one sample from the slot's engine, which advances; the engine's record is written back as the scatter writes it.
-RT_DEV void rq_bake_make_ray(const BakeView &B, uint32_t i, F3 p, F3 n, float *ray) {
-    const uint4 e = B.rng[i];                                // x saved has_saved reserved
-    Rng rng; rng.x = e.x; rng.saved = __uint_as_float(e.y); rng.has_saved = e.z != 0u;
-    F3 o, d;
-    if (B.mode == RQ_BAKE_IRRADIANCE) {
+// The ray (o, d) of one sample at a point, drawn from `rng`, which advances: the one place these expressions stand (rq_bake_make_ray below,
+// PtSource of rt_path_source.h).
+RT_DEV void rq_bake_ray(int32_t mode, Rng &rng, F3 p, F3 n, F3 &o, F3 &d) {
+    if (mode == RQ_BAKE_IRRADIANCE) {
         o = p + RQ_EPS * n;
         d = cosine_sample(rng, n);
     } else {
@@ -59,6 +63,13 @@ RT_DEV void rq_bake_make_ray(const BakeView &B, uint32_t i, F3 p, F3 n, float *r
         o = p;
         d = normalize(f3(a, b, c));
     }
+}
+// ... from the slot's engine record, which is written back as the scatter writes it.
+RT_DEV void rq_bake_make_ray(const BakeView &B, uint32_t i, F3 p, F3 n, float *ray) {
+    const uint4 e = B.rng[i];                                // x saved has_saved reserved
+    Rng rng; rng.x = e.x; rng.saved = __uint_as_float(e.y); rng.has_saved = e.z != 0u;
+    F3 o, d;
+    rq_bake_ray(B.mode, rng, p, n, o, d);
     B.rng[i] = make_uint4(rng.x, rng.has_saved ? __float_as_uint(rng.saved) : 0u, rng.has_saved ? 1u : 0u, e.w);
     rq_store_ray(ray, o, d);
     if (B.dir0) { float *q = B.dir0 + 3 * (size_t)i; q[0] = d.x; q[1] = d.y; q[2] = d.z; }
@@ -132,6 +143,13 @@ __global__ __launch_bounds__(256) void rq_bake_advance_kernel(SceneView S, PathV
     }
 }
 
+// scale * (((a_0 + a_1) + a_2) ...) over the `streams` sums of a point, `stride` floats apart; the bits as the answer keeps them.  Shared with
+// rq_source_unpack_kernel (rt_path_source.h), whose sums lie in the slots' state.
+RT_DEV uint32_t rq_bake_stream_sum(const float *a, size_t stride, uint32_t streams, float scale) {
+    float sum = a[0];
+    for (uint32_t k = 1; k < streams; k++) sum = sum + a[k * stride];
+    return rq_bits(scale * sum);
+}
 // out[point][j] = scale * (((acc_0 + acc_1) + acc_2) ...) over the point's streams; B.n counts the floats of the chunk's answer.
 __global__ __launch_bounds__(256) void rq_bake_resolve_kernel(SceneView S, BakeView B) {
     const uint32_t slots = B.n / B.floats * B.streams;
@@ -141,9 +159,7 @@ __global__ __launch_bounds__(256) void rq_bake_resolve_kernel(SceneView S, BakeV
         F3 p, n;
         if (!rq_bake_point(B, point * B.streams, p, n)) { *out = 0u; continue; }
         const float *a = B.acc + (size_t)j * slots + (size_t)point * B.streams;
-        float sum = a[0];
-        for (uint32_t k = 1; k < B.streams; k++) sum = sum + a[k];
-        *out = rq_bits(B.scale * sum);
+        *out = rq_bake_stream_sum(a, 1u, B.streams, B.scale);
     }
 }
 

@@ -1,0 +1,124 @@
+// The path source of the persistent hw8 kernel (include/rtamd.h: rt_render_paths, rt_render_bake): rt_render, rt_trace_paths and rt_bake
+// differ in where a sample's first ray comes from and where a slot's sum and engine go when it has no sample left.  A kernel compiled
+// with WF_FEAT_SOURCE takes the first ray from RenderView::src_* instead of the camera,
+//   src_mode 1   the caller's ray src_rays[gslot], used as given (not normalised); the engine does not advance for it; one sample per slot
+//   src_mode 2   rq_bake_ray (rt_bake.h) on point gslot / src_streams, drawn from the slot's engine; `samples` samples per slot
+// and keeps sum, engine and end of slot as a resumable render has them (RenderView::accum, 24 bytes per slot): the slice of a resumable
+// frame whose pixel slots are the record indices.  A kernel with the bit is only ever launched with src_mode 1 or 2.
+//
+// The frame.  An unsharded strip 8 pixels wide and 8 * ceil(n / 64) high: its tiles are the 8x8 sub-tiles themselves, one per row of the
+// tile grid, so slot_to_pixel (rt_device.h) maps sub-tile s, pixel (x, y) of it to slot 64 s + 8 y + x -- gslot IS the record index.  The
+// pixel coordinates are never used (no camera ray, no pixel store).
+//
+// A slot with no path: gslot >= src_n, or a record the composed calls refuse (rt_trace_paths: rq_valid_ray, rq_rng_valid; rt_bake:
+// rq_bake_point -- a point's numbers and ALL of its streams' engines).  It starts no path, its state is not touched, and it is counted
+// in CNT_SRC_NO_PATH (mode 1: every such record below src_n; mode 2: once per point, by its first slot).
+//
+// First rays the walkers were not derived for (pt_source_exact) belong to the exact role from the start: an origin outside the 16-bit
+// node grid (rt_device.h RayGrid: its error budget holds for |o'| <= 65,536 cells), a ray off the fast list of rt_query.h (rq_classify),
+// or one that pierces a tripwire.  Bounce rays start on surfaces and are the render's own.
+//
+//   rq_source_pack_kernel    one lane per slot: the caller's rt_rng -> the slot's state, sum 0 (a slot beyond n: zeros, which is no engine)
+//   rq_source_unpack_kernel  one lane per slot: state -> rt_rng (saved = 0 whenever has_saved is 0, `reserved` handed through; an invalid
+//                            record's engine is not written) and the answer: the slot's sum (mode 1) or rq_bake_stream_sum over the
+//                            point's slots (mode 2, by the point's first slot), through rq_bits; an invalid record answers zeros
+#pragma once
+#include "rt_bake.h"
+
+namespace rtamd {
+namespace dev {
+
+#define PT_SRC_CAMERA 0u
+#define PT_SRC_RAYS 1u
+#define PT_SRC_BAKE 2u
+
+RT_DEV void pt_source_load_ray(const float *rays, uint32_t i, F3 &o, F3 &d) { // rt_ray is only 4-byte aligned
+    const float *p = rays + 6 * (size_t)i;
+    o = f3(p[0], p[1], p[2]); d = f3(p[3], p[4], p[5]);
+}
+// The engine word of slot j in the state of a resumable render (accum_enter's layout).
+RT_DEV uint32_t pt_source_engine(const uint32_t *state, uint32_t j) { return state[4 * (size_t)j + 3]; }
+// Mode 2: the point of slot `gslot` and whether it is valid.  The engines of the point's other slots are read from the state while those
+// slots may be running: a valid engine stays one however far it has advanced, and an invalid one is never written.
+RT_DEV bool pt_source_point(const RenderView &R, uint32_t gslot, F3 &p, F3 &n) {
+    const uint32_t point = gslot / R.src_streams;
+    bool ok = rq_bake_point_read(R.src_points, point, RQ_BAKE_IRRADIANCE, p, n);
+    for (uint32_t k = 0; k < R.src_streams; k++) ok = ok && rq_rng_valid(pt_source_engine(R.accum, point * R.src_streams + k));
+    return ok;
+}
+// Whether a slot without a path counts (once per invalid record / point; the padding of the last 64-slot group does not).
+RT_DEV bool pt_source_counts(const RenderView &R, uint32_t gslot) {
+    return gslot < R.src_n && (R.src_mode != PT_SRC_BAKE || gslot % R.src_streams == 0u);
+}
+// Whether the first ray (o, d) of a sample goes to the exact role (PT_Q_XTRACE) instead of the walkers.  Too cautious costs speed only.
+RT_DEV bool pt_source_exact(const SceneView &S, F3 o, F3 d) {
+    QueryView Q{};
+    Q.origin_bound = S.box_c2 * 1048576.f;                  // as rtamd_query.hip's walk_view sets it
+    if (rq_classify(Q, o, d) != RQ_FAST) return true;
+    const NodeGrid &G = S.grid;
+    const float cx = (o.x - G.lo[0]) * G.istep[0], cy = (o.y - G.lo[1]) * G.istep[1], cz = (o.z - G.lo[2]) * G.istep[2];
+    if (!(cx >= 0.f && cx <= 65536.f && cy >= 0.f && cy <= 65536.f && cz >= 0.f && cz <= 65536.f)) return true;
+    return pt_tripwire(S, o, d);
+}
+
+template <int FEAT> struct PtSource {
+    // The first ray of slot `gslot`, whose engine `rng` comes from the state; false: the slot has no path.
+    static RT_DEV bool first(const SceneView &, const RenderView &R, uint32_t gslot, Rng &rng, F3 &o, F3 &d) {
+        if (gslot >= R.src_n) return false;
+        if (R.src_mode == PT_SRC_BAKE) {
+            F3 p, n;
+            if (!pt_source_point(R, gslot, p, n)) return false;
+            rq_bake_ray(RQ_BAKE_IRRADIANCE, rng, p, n, o, d);
+            return true;
+        }
+        pt_source_load_ray(R.src_rays, gslot, o, d);
+        return rq_valid_ray(o, d) && rq_rng_valid(rng.x);
+    }
+    // The first ray of the slot's sample `next` (wf_finish_path): the slot has a path, so its record is valid.
+    static RT_DEV void ray(const SceneView &S, const RenderView &R, Rng &rng, uint32_t gslot, int x, int y, uint32_t next, F3 &o, F3 &d) {
+        if constexpr ((FEAT & WF_FEAT_SOURCE) != 0) {
+            if (R.src_mode == PT_SRC_BAKE) {
+                F3 p, n;
+                rq_bake_point_read(R.src_points, gslot / R.src_streams, RQ_BAKE_IRRADIANCE, p, n);
+                rq_bake_ray(RQ_BAKE_IRRADIANCE, rng, p, n, o, d);
+            } else pt_source_load_ray(R.src_rays, gslot, o, d); // (mode 1 has one sample per slot: never reached)
+        } else WfCameraSource::ray(S, R, rng, gslot, x, y, next, o, d);
+    }
+};
+
+__global__ __launch_bounds__(256) void rq_source_pack_kernel(SourceView V) {
+    for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < V.n_pixslots; i += gridDim.x * 256u) {
+        const uint4 e = i < V.n ? V.rng[i] : make_uint4(0u, 0u, 0u, 0u); // x saved has_saved reserved
+        reinterpret_cast<uint4 *>(V.state)[i] = make_uint4(0u, 0u, 0u, e.x);
+        reinterpret_cast<uint2 *>(V.state + 4 * (size_t)V.n_pixslots)[i] = make_uint2(e.y, e.z != 0u ? 1u : 0u);
+    }
+}
+
+__global__ __launch_bounds__(256) void rq_source_unpack_kernel(SourceView V) {
+    for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < V.n; i += gridDim.x * 256u) {
+        const uint4 a = reinterpret_cast<const uint4 *>(V.state)[i];
+        const uint2 b = reinterpret_cast<const uint2 *>(V.state + 4 * (size_t)V.n_pixslots)[i];
+        bool ok;
+        if (V.mode == PT_SRC_BAKE) {
+            BakeView B{};
+            B.points = V.points; B.rng = V.rng; B.streams = V.streams; B.mode = RQ_BAKE_IRRADIANCE;
+            F3 p, n;
+            ok = rq_bake_point(B, i, p, n);                  // the caller's engines: written below by other lanes, valid before and after
+            if (i % V.streams == 0u) {
+                uint32_t *out = reinterpret_cast<uint32_t *>(V.out) + 3 * (size_t)(i / V.streams);
+                const float *sums = reinterpret_cast<const float *>(V.state) + 4 * (size_t)i;
+                for (int j = 0; j < 3; j++) out[j] = ok ? rq_bake_stream_sum(sums + j, 4u, V.streams, V.scale) : 0u;
+            }
+        } else {
+            F3 o, d;
+            pt_source_load_ray(V.rays, i, o, d);
+            ok = rq_valid_ray(o, d) && rq_rng_valid(a.w);
+            uint32_t *out = reinterpret_cast<uint32_t *>(V.out) + 3 * (size_t)i;
+            out[0] = rq_bits(__uint_as_float(a.x)); out[1] = rq_bits(__uint_as_float(a.y)); out[2] = rq_bits(__uint_as_float(a.z)); // an invalid record's sum is the 0 it was packed with
+        }
+        if (ok) V.rng[i] = make_uint4(a.w, b.y ? b.x : 0u, b.y ? 1u : 0u, V.rng[i].w);
+    }
+}
+
+} // namespace dev
+} // namespace rtamd

@@ -37,7 +37,7 @@
 // ref_light_pdf_sum).  Pixels then match the reference's also where a ray grazes a box corner.  Rays that cross a tripwire (rt_exact.h
 // pt_tripwire: the leaf box of a triangle whose test accepts points far away from it) never go to the walkers at all.
 #pragma once
-#include "rt_wavefront.h"
+#include "rt_path_source.h" // the first ray of a sample under WF_FEAT_SOURCE; brings rt_wavefront.h
 #include "rt_pt_queue.h" // the queues: pt_count, pt_ballot, pt_rank_below, pt_prefix, pt_pop, pt_push; PT_NONE
 
 namespace rtamd {
@@ -703,7 +703,7 @@ RT_DEV int pt_shade_lean(const SceneView &S, const RenderView &R, const WfView &
     }
     lp.start();
     Rng rng = pk.rng(packed);
-    const int todo = wf_finish_path(S, R, W, slot, (int)pk.getu(PK_LEVELS), pk.get3(PK_TAIL), rng, (packed >> 6) & WF_SAMPLE_MASK);
+    const int todo = wf_finish_path<PtSource<FEAT>>(S, R, W, slot, (int)pk.getu(PK_LEVELS), pk.get3(PK_TAIL), rng, (packed >> 6) & WF_SAMPLE_MASK);
     lp.lap(4);
     return todo;
 }
@@ -810,7 +810,8 @@ struct PtShaded {
 // holds the kernel's arguments (S, R, W, P), its LDS block `sh`, the wave's stack area `stack`, its own query counts, and says
 //   THREADS, COUNT, SLOTS, DEFER    the workgroup's size; the counting build; the two measured choices of pt_walk_stint
 //   trace_walk(), light_walk(prof)  the kernel's two walker policies
-//   seed(slot, gslot, x, y, rng, sum)  writes r0..r3 of a fresh path: its first camera ray, drawn from `rng`, and the pixel sum
+//   seed(slot, gslot, x, y, rng, sum)  writes r0..r3 of a fresh path: its first camera ray, drawn from `rng`, and the pixel sum; false: the slot starts no
+//                                   path (a path source without a record for it, rt_path_source.h; the camera always has one)
 //   resumed_sample(slot)            the sample count in the packed word of a record that carries on (PtParams::resume)
 //   seed_wire(slot)                 whether the record's camera ray belongs to the exact role from the start (a tripwire)
 //   rare(wv)                        runs one batch of the kernel's rare roles if any is queued, and says whether it did
@@ -837,7 +838,7 @@ RT_DEV void pt_run(RL &rl) {
             if (wf_seed_record(R, gslot, !P.resume, x, y, rng, sum)) {
                 // a later phase of the frame: the record holds the pixel sum, the random stream and the parked camera ray
                 if (P.resume) started = rl.resumed_sample(slot) < (uint32_t)R.samples;
-                else { rl.seed(slot, gslot, x, y, rng, sum); started = true; }
+                else started = rl.seed(slot, gslot, x, y, rng, sum);
                 if (started) {
                     atomicOr(&sh.pending[l >> 4], PT_BIT_T << ((l & 15u) * 2u));
                     wire = rl.seed_wire(slot);
@@ -946,18 +947,33 @@ struct PtRoles {
     uint32_t n_xtrace = 0, n_xlight = 0, n_discarded = 0; // per wave and launch: well below 2^32
     RT_DEV PtTraceWalk trace_walk() { return PtTraceWalk{S, W, sh, P, stack}; }
     RT_DEV PtLightWalk<COUNT> light_walk(PtProf &prof) { return PtLightWalk<COUNT>{S, W, sh, P, stack, prof}; }
-    RT_DEV void seed(uint32_t slot, uint32_t gslot, int x, int y, Rng &rng, F3 sum) {
-        if (R.sample_seeds) wf_sample_seed(R, rng, gslot, x, y, 0u);
+    RT_DEV bool seed(uint32_t slot, uint32_t gslot, int x, int y, Rng &rng, F3 sum) {
         F3 o, d;
-        wf_camera_ray(S, R, rng, x, y, o, d);
         float4 *r = wf_rec(W, slot);
+        if constexpr ((FEAT & WF_FEAT_SOURCE) != 0) {
+            if (!PtSource<FEAT>::first(S, R, gslot, rng, o, d)) {
+                // no path: the state stays as it is, and the record says "every sample is in" to a later phase of the launch (resumed_sample)
+                r[3] = make_float4(0.f, 0.f, 0.f, __uint_as_float(wf_pack(0, false, (uint32_t)R.samples)));
+                if (P.counters && pt_source_counts(R, gslot)) atomicAdd(&P.counters[CNT_SRC_NO_PATH], 1ull);
+                return false;
+            }
+        } else {
+            if (R.sample_seeds) wf_sample_seed(R, rng, gslot, x, y, 0u);
+            wf_camera_ray(S, R, rng, x, y, o, d);
+        }
         r[0] = make_float4(o.x, o.y, o.z, d.x);
         r[1] = make_float4(d.y, d.z, __uint_as_float(rng.x), rng.saved);
         r[2] = make_float4(0.f, 0.f, 0.f, 0.f);
         r[3] = make_float4(sum.x, sum.y, sum.z, __uint_as_float(wf_pack(0, rng.has_saved, R.accum ? (uint32_t)R.sample_first : 0u)));
+        return true;
     }
     RT_DEV uint32_t resumed_sample(uint32_t slot) { return (__float_as_uint(reinterpret_cast<const float *>(wf_rec(W, slot) + 3)[3]) >> 6) & WF_SAMPLE_MASK; }
     RT_DEV bool seed_wire(uint32_t slot) { // the record's ray pierces a tripwire (rt_exact.h): its closest hit is the exact role's
+        if constexpr ((FEAT & WF_FEAT_SOURCE) != 0) { // ... or it is a first ray the walkers were not derived for (pt_source_exact, which looks at the tripwires too)
+            const float4 *nr = wf_rec(W, slot);
+            const float4 n0 = nr[0], n1 = nr[1];
+            return pt_source_exact(S, f3(n0.x, n0.y, n0.z), f3(n0.w, n1.x, n1.y));
+        }
         if (!S.n_tripwire_groups) return false;
         const float4 *nr = wf_rec(W, slot);
         const float4 n0 = nr[0], n1 = nr[1];
@@ -1009,6 +1025,15 @@ struct PtRoles {
                     const int depth = (int)(__float_as_uint(reinterpret_cast<const float *>(nr + 3)[3]) & 15u);
                     float *pdf = reinterpret_cast<float *>(wf_entry(W, pt_slot(sh, got), depth)) + 3;
                     *pdf = *pdf + 0.f / S.n_lights_f;                      // distributions.h:123,273 (+0.f: a -0 sum becomes +0)
+                }
+            }
+        }
+        if constexpr ((FEAT & WF_FEAT_SOURCE) != 0) { // the next sample's first ray (depth 0, no bounce pending) gets the treatment of the slot's first
+            if (next && !wire) {
+                const float4 *nr = wf_rec(W, pt_slot(sh, got));
+                if ((__float_as_uint(reinterpret_cast<const float *>(nr + 3)[3]) & (15u | WF_PENDING_BIT)) == 0u) {
+                    const float4 n0 = nr[0], n1 = nr[1];
+                    wire = pt_source_exact(S, f3(n0.x, n0.y, n0.z), f3(n0.w, n1.x, n1.y));
                 }
             }
         }

@@ -707,7 +707,7 @@ struct P6Roles {
     uint32_t n_slow = 0, n_exact = 0, n_xlight = 0;
     RT_DEV P6TraceWalk trace_walk() { return P6TraceWalk{S, W, sh, P, stack}; }
     RT_DEV P6LightWalk light_walk(PtProf &) { return P6LightWalk{S, W, sh, P, stack}; }
-    RT_DEV void seed(uint32_t slot, uint32_t, int x, int y, Rng &rng, F3 sum) { // first camera ray (hw6/src/sceneio.cpp:281-284)
+    RT_DEV bool seed(uint32_t slot, uint32_t, int x, int y, Rng &rng, F3 sum) { // first camera ray (hw6/src/sceneio.cpp:281-284); every slot starts a path
         F3 o, d;
         p6_camera_ray(S, R, rng, x, y, o, d);
         float4 *r = p6_rec(W, slot);
@@ -715,6 +715,7 @@ struct P6Roles {
         r[1] = make_float4(d.y, d.z, __uint_as_float(rng.x), rng.saved);
         r[2] = make_float4(0.f, 0.f, 0.f, 0.f);
         r[3] = make_float4(sum.x, sum.y, sum.z, __uint_as_float(p6_pack(0, rng.has_saved, R.accum ? (uint32_t)R.sample_first : 0u, 0u)));
+        return true;
     }
     RT_DEV uint32_t resumed_sample(uint32_t slot) { return __float_as_uint(reinterpret_cast<const float *>(p6_rec(W, slot) + 3)[3]) >> 8; }
     RT_DEV bool seed_wire(uint32_t) { return false; }

@@ -40,6 +40,7 @@ enum CounterSlot {
     CNT_P8_STINTS = 25,
     CNT_P8_SHADE_BATCHES = 26,
     CNT_P8_SHADE_ITEMS = 27,
+    CNT_SRC_NO_PATH = 28,       // P8 with a path source (rt_path_source.h): records that started no path (rays: invalid records; bake: invalid points)
     CNT_DEADLINE = 29,          // P8, P6: waves that ran into the launch deadline (an error)
     CNT_P8_LIGHT_REACH = 30,    // P8, 2 slots: light sums whose walk ends at the light tree's root / one level below it (pt_light_reach)
     CNT_WF_HIST_LIGHT = 32,     // WF, 16 slots: light queries by in-flight wave iterations / 32
@@ -216,6 +217,13 @@ struct RenderView {
     // accum_enter / accum_leave): n_pixslots x {sum.x, sum.y, sum.z, Rng::x}, then n_pixslots x {Rng::saved, Rng::has_saved}.
     uint32_t *accum;               // nullable: null = a one-shot frame
     int32_t sample_first;
+    // The path source of the persistent hw8 kernel (rt_path_source.h, kernels compiled with WF_FEAT_SOURCE): where a sample's first ray comes
+    // from.  Every other launch leaves these zero.  Indexed by the record index, which is the pixel slot (frame geometry: rt_path_source.h).
+    uint32_t src_mode;             // 0 = the camera, 1 = the caller's rays, 2 = bake irradiance
+    uint32_t src_n;                // records (mode 2: points x streams); a slot at or beyond it starts no path
+    const float *src_rays;         // mode 1: src_n x {o.xyz, d.xyz} (rt_ray), used as given
+    const float *src_points;       // mode 2: src_n / src_streams x {p.xyz, n.xyz} (rt_bake_point)
+    uint32_t src_streams;          // mode 2: slots per point
 };
 
 } // namespace rtamd

@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <string>
 
 struct rt_scene;
 
@@ -109,6 +110,29 @@ struct BakeView {
     float scale;
 };
 
+// rt_render_paths / rt_render_bake (rt_path_source.h): one chunk's slots between the caller's records and the state the persistent
+// kernel runs over (RenderView::accum's layout: n_pixslots x {sum.xyz, Rng::x}, then n_pixslots x {Rng::saved, Rng::has_saved}).
+struct SourceView {
+    uint32_t *state;
+    uint32_t n_pixslots;          // slots of the chunk's frame: n rounded up to whole 64-slot groups
+    uint32_t n;                   // records (bake: points x streams)
+    uint32_t mode;                // RenderView::src_mode: 1 = rays, 2 = bake irradiance
+    uint4 *rng;                   // n (rt_rng), in (pack) and out (unpack), 16-byte aligned
+    const float *rays;            // mode 1: n x {o.xyz, d.xyz}
+    const float *points;          // mode 2: n / streams x {p.xyz, n.xyz}
+    uint32_t streams;             // mode 2: K
+    float scale;                  // mode 2: pi / samples
+    float *out;                   // unpack: n x 3 (mode 1) or n / streams x 3 (mode 2)
+};
+// One chunk through the persistent hw8 kernel with a path source: a slice of `samples` samples per slot of the strip frame over `state`.
+struct SourceChunk {
+    uint32_t mode, n, streams;    // as in SourceView
+    const float *rays, *points;
+    int32_t ray_depth, samples;
+    uint32_t *state;
+};
+struct SourceResult { float kernel_ms; uint32_t launches, reference_exact; uint64_t exact_walks, no_path; };
+
 // The engine states std::minstd_rand can be in: 1 .. 2^31 - 2.  Any other x is refused (host arrays) or marked invalid (device arrays)
 // before a draw: 0 stays 0 for ever, and rng_n01's rejection loop would not end.
 __host__ __device__ inline bool rq_rng_valid(uint32_t x) { return x - 1u < 2147483646u; }
@@ -133,5 +157,12 @@ uint32_t query_launch_path_advance(const rt_scene *scene, const PathView &V, hip
 uint32_t query_launch_bake_rays(const rt_scene *scene, const BakeView &B, hipStream_t stream);
 uint32_t query_launch_bake_advance(const rt_scene *scene, const PathView &V, const BakeView &B, hipStream_t stream);
 uint32_t query_launch_bake_resolve(const rt_scene *scene, const BakeView &B, hipStream_t stream);
+uint32_t query_launch_source_pack(const rt_scene *scene, const SourceView &V, hipStream_t stream);
+uint32_t query_launch_source_unpack(const rt_scene *scene, const SourceView &V, hipStream_t stream);
+// rt_render_paths / rt_render_bake.  source_check: what stands in the way of a chunk of `slots` slots (host only; RT_OK, or the refusal
+// with `who` in front).  source_render: the chunk's launches through the renders' own driver (check_frame, launch_frame, collect_frame
+// of rtamd_api.hip), synchronous; the chunk's state is advanced in place.
+int source_check(const rt_scene *scene, uint32_t slots, int32_t ray_depth, int32_t samples, const std::string &who);
+int source_render(rt_scene *scene, const SourceChunk &C, hipStream_t stream, SourceResult &res, const std::string &who);
 
 } // namespace rtamd

@@ -186,7 +186,16 @@ RT_DEV bool wf_seed_record(const RenderView &R, uint32_t gslot, bool fresh, int 
     return true;
 }
 
+// Where the next sample's first ray comes from: the camera, for every kernel but the persistent hw8 kernel with a path source
+// (rt_path_source.h PtSource).
+struct WfCameraSource {
+    static RT_DEV void ray(const SceneView &S, const RenderView &R, Rng &rng, uint32_t gslot, int x, int y, uint32_t next, F3 &o, F3 &d) {
+        if (R.sample_seeds) wf_sample_seed(R, rng, gslot, x, y, next);
+        wf_camera_ray(S, R, rng, x, y, o, d);
+    }
+};
 // End of one camera sample: fold e + m*(inner) backwards (scene.cpp:164), then wf_end_sample.
+template <class SRC = WfCameraSource>
 RT_DEV int wf_finish_path(const SceneView &S, const RenderView &R, const WfView &W, uint32_t slot, int depth, F3 tail,
                            Rng &rng, uint32_t sample) {
     F3 L = tail;
@@ -196,10 +205,7 @@ RT_DEV int wf_finish_path(const SceneView &S, const RenderView &R, const WfView 
         L = f3(e0.x, e0.y, e0.z) + f3(e1.x, e1.y, e1.z) * L;
     }
     return wf_end_sample(R, wf_rec(W, slot), slot + W.slot_base, L, rng, sample,
-                         [&](int x, int y, uint32_t next, F3 &o, F3 &d) {
-                             if (R.sample_seeds) wf_sample_seed(R, rng, slot + W.slot_base, x, y, next);
-                             wf_camera_ray(S, R, rng, x, y, o, d);
-                         },
+                         [&](int x, int y, uint32_t next, F3 &o, F3 &d) { SRC::ray(S, R, rng, slot + W.slot_base, x, y, next, o, d); },
                          [](bool has_saved, uint32_t next) { return wf_pack(0, has_saved, next); });
 }
 
@@ -675,6 +681,7 @@ __global__ __launch_bounds__(64) void wf_light_exact_kernel(SceneView S, WfView 
 // environment lookup inlines float atan2f / asinf (rt_device.h) and a texture fetch.
 #define WF_FEAT_ENV 1
 #define WF_FEAT_HW7 2
+#define WF_FEAT_SOURCE 4 // rt_persistent.h only: a sample's first ray comes from a path source (rt_path_source.h); no hw7 and no counting variant
 template <int FEAT = WF_FEAT_ENV | WF_FEAT_HW7>
 RT_DEV int wf_shade_item(const SceneView &S, const RenderView &R, const WfView &W, uint32_t slot, unsigned long long *counters, bool *discarded = nullptr) {
     float4 *r = wf_rec(W, slot);

@@ -146,6 +146,8 @@ struct rt_scene {
     uint32_t *query_materials = nullptr; // material index by LOAD-order triangle, made by the first surface query (not part of info.device_bytes)
     uint8_t *path_stack = nullptr;   // rt_trace_paths: state and per-bounce stack of a chunk's paths, grown on demand (not part of info.device_bytes)
     size_t path_stack_bytes = 0;
+    uint8_t *source_stage = nullptr; // rt_render_paths / rt_render_bake: the slots' state and, with host arrays, the staging of one chunk (not part of info.device_bytes)
+    size_t source_stage_bytes = 0;
     uint8_t *denoise_stage = nullptr; // preview filter (rtamd_denoise.hip): the working set of one frame, grown on demand (not part of info.device_bytes)
     size_t denoise_stage_bytes = 0;
     void free_wf() {
@@ -163,6 +165,7 @@ struct rt_scene {
         if (query_stage) (void)hipFree(query_stage);
         if (query_materials) (void)hipFree(query_materials);
         if (path_stack) (void)hipFree(path_stack);
+        if (source_stage) (void)hipFree(source_stage);
         if (denoise_stage) (void)hipFree(denoise_stage);
         for (void *p : allocations) (void)hipFree(p);
         if (ev_start) (void)hipEventDestroy(ev_start);

@@ -347,7 +347,10 @@ static PersistentKernel hw8_persistent(const SceneView &V, int ray_depth, hipStr
                 dev::WfView W{};
                 W.r0 = records; W.stride = stride; W.n_slots = n_slots; W.slot_base = slot_base;
                 const dim3 grid(blocks), block(P8_THREADS);
-                if (count) {
+                if (R.src_mode) { // a path source (device/rt_path_source.h; source_render below): hw8 only, no counting variant
+                    if (feat == WF_FEAT_ENV) hipLaunchKernelGGL((dev::pt_persistent_kernel<false, WF_FEAT_SOURCE | WF_FEAT_ENV>), grid, block, 0, stream, V, R, W, P);
+                    else hipLaunchKernelGGL((dev::pt_persistent_kernel<false, WF_FEAT_SOURCE>), grid, block, 0, stream, V, R, W, P);
+                } else if (count) {
                     if (feat == WF_FEAT_HW7) hipLaunchKernelGGL((dev::pt_persistent_kernel<true, WF_FEAT_HW7>), grid, block, 0, stream, V, R, W, P);
                     else if (feat == WF_FEAT_ENV) hipLaunchKernelGGL((dev::pt_persistent_kernel<true, WF_FEAT_ENV>), grid, block, 0, stream, V, R, W, P);
                     else hipLaunchKernelGGL((dev::pt_persistent_kernel<true, 0>), grid, block, 0, stream, V, R, W, P);
@@ -1198,4 +1201,57 @@ uint32_t rtamd::query_launch_bake_resolve(const rt_scene *scene, const BakeView 
     hipLaunchKernelGGL(dev::rq_bake_resolve_kernel, dim3(query_geometry(scene, B.n).flat_blocks), dim3(256), 0, stream, scene->view, B);
     HIP_CHECK(hipGetLastError());
     return 1u;
+}
+
+// ---- rt_render_paths / rt_render_bake: a caller's paths through the persistent hw8 kernel (device/rt_path_source.h) --------------------------
+uint32_t rtamd::query_launch_source_pack(const rt_scene *scene, const SourceView &V, hipStream_t stream) {
+    hipLaunchKernelGGL(dev::rq_source_pack_kernel, dim3(query_geometry(scene, V.n_pixslots).flat_blocks), dim3(256), 0, stream, V);
+    HIP_CHECK(hipGetLastError());
+    return 1u;
+}
+
+uint32_t rtamd::query_launch_source_unpack(const rt_scene *scene, const SourceView &V, hipStream_t stream) {
+    hipLaunchKernelGGL(dev::rq_source_unpack_kernel, dim3(query_geometry(scene, V.n).flat_blocks), dim3(256), 0, stream, V);
+    HIP_CHECK(hipGetLastError());
+    return 1u;
+}
+
+namespace {
+// The strip frame of `slots` record indices (device/rt_path_source.h): 8 pixels wide, one 8x8 sub-tile per 64 slots, unsharded.
+rt_render_params source_params(uint32_t slots, int32_t ray_depth, int32_t samples) {
+    rt_render_params p{};
+    p.struct_size = sizeof(rt_render_params);
+    p.width = 8; p.height = 8 * (int32_t)((slots + 63u) / 64u);
+    p.samples = samples; p.ray_depth = ray_depth;
+    p.integrator = RT_INTEGRATOR_HW8;
+    return p;
+}
+int source_frame(const rt_scene *scene, const rt_render_params &p, const AccumSlice &slice, const std::string &who, Frame &F) {
+    if (const int rc = check_frame(scene, &p, &slice, who, F)) return rc;
+    if (F.pipe != Pipeline::Persistent8)
+        return fail(RT_ERR_UNSUPPORTED, who + "the persistent hw8 kernel does not take this scene or environment (RTAMD_KERNEL=wavefront|mega, or a tree beyond its stack columns): there is no fallback, rt_trace_paths / rt_bake serve it");
+    return RT_OK;
+}
+} // namespace
+
+int rtamd::source_check(const rt_scene *scene, uint32_t slots, int32_t ray_depth, int32_t samples, const std::string &who) {
+    Frame F;
+    return source_frame(scene, source_params(slots, ray_depth, samples), AccumSlice{nullptr, 0}, who, F);
+}
+
+int rtamd::source_render(rt_scene *scene, const SourceChunk &C, hipStream_t stream, SourceResult &res, const std::string &who) {
+    const rt_render_params p = source_params(C.n, C.ray_depth, C.samples);
+    const AccumSlice slice{C.state, 0};
+    Frame F;
+    if (const int rc = source_frame(scene, p, slice, who, F)) return rc;
+    const double t0 = now_ms();
+    F.R.src_mode = C.mode; F.R.src_n = C.n; F.R.src_rays = C.rays; F.R.src_points = C.points; F.R.src_streams = C.streams;
+    launch_frame(scene, &p, F, stream, true);
+    rt_stats st{};
+    if (const int rc = collect_frame(scene, F, stream, &st, t0, who)) return rc;
+    unsigned long long no_path = 0;
+    HIP_CHECK(hipMemcpy(&no_path, scene->d_counters + CNT_SRC_NO_PATH, sizeof no_path, hipMemcpyDeviceToHost)); // the launch is over (collect_frame waited)
+    res.kernel_ms = st.kernel_ms; res.launches = st.launches; res.reference_exact = st.reference_exact;
+    res.exact_walks = st.exact_closest_hits + st.exact_light_sums; res.no_path = no_path;
+    return RT_OK;
 }

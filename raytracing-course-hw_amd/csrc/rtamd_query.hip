@@ -1,7 +1,8 @@
 // Batched ray queries through the C-ABI (include/rtamd.h: rt_query_closest, rt_query_light_pdf, rt_query_occluded), the first-hit layer over them
 // (rt_query_surface, rt_query_environment, rt_camera_rays, rt_render_guides) and the bounce step (rt_query_scatter, rt_query_bsdf,
 // rt_trace_paths, rt_rng_*) and its first caller, the baker (rt_bake_rays, rt_bake): argument checks, the chunking, the staging, the
-// rounds and the statistics.  No kernel and no kernel header here: the
+// rounds and the statistics; and rt_render_paths / rt_render_bake, the same answers through the persistent render kernel
+// (device/rt_path_source.h; the launches are rtamd_api.hip's frame driver, source_render).  No kernel and no kernel header here: the
 // kernels (device/rt_query.h, device/rt_query_surface.h, device/rt_query_scatter.h, device/rt_bake.h) live in rtamd_api.hip,
 // where every __global__ keeps one definition, and are launched through query_launch_* (device/rt_types_query.h).
 #include <hip/hip_runtime.h>
@@ -250,6 +251,65 @@ int check_bake_engines(const rt_rng *rng, size_t n, const std::string &who) {
     for (size_t i = 0; i < n; i++)
         if (!rq_rng_valid(rng[i].x))
             return fail(RT_ERR_INVALID_ARG, who + "rng[" + std::to_string(i) + "].x = " + std::to_string(rng[i].x) + " is no state of the engine (1 .. 2147483646)");
+    return RT_OK;
+}
+
+
+// ---- rt_render_paths / rt_render_bake: the caller's paths through the persistent kernel (device/rt_path_source.h) ----------------------------
+// Slots per chunk: the pixel slots of a 1080p frame, so the persistent kernel's path records (256 bytes per slot at depth 6) never grow
+// beyond what rt_render of that frame allocates, and workload A of profiles/r30_render_paths.txt is one launch.  RTAMD_QUERY_CHUNK
+// lowers it as it does for the composed calls.
+const size_t SOURCE_CHUNK = 2073600;
+size_t source_chunk() { return std::min(SOURCE_CHUNK, (size_t)std::max(64, env_positive("RTAMD_QUERY_CHUNK", (int)SOURCE_CHUNK))); }
+
+// One call: `items` rays (K = 1) or points of K slots each.  `in`: the rays or the points, 24 bytes an item.
+struct SourceCall {
+    uint32_t mode; size_t K; int32_t depth, samples; float scale; // samples: per slot
+    const void *in; rt_rng *rng; float *out; bool on_device;
+};
+struct SourceTotals { double kernel_ms = 0; uint32_t launches = 0, reference_exact = 0; uint64_t exact_walks = 0, no_path = 0; };
+
+int source_run(rt_scene *scene, const SourceCall &c, size_t items, const std::string &who, SourceTotals &T) {
+    HIP_CHECK(hipSetDevice(scene->device));
+    hipStream_t stream = nullptr;
+    const size_t chunk_items = source_chunk() / c.K; // whole points: the stream sum never crosses a seam (the chunk's minimum of 64 covers K <= 64)
+    const size_t cap_items = std::min(items, chunk_items), cap = (cap_items * c.K + 63u) & ~(size_t)63u;
+    size_t at = 0;
+    auto take = [&](size_t bytes) { const size_t here = at; at += (bytes + 255u) & ~(size_t)255u; return here; };
+    const size_t o_state = take(cap * 24u), o_in = take(c.on_device ? 0 : cap_items * 24u), o_rng = take(c.on_device ? 0 : cap * sizeof(rt_rng)),
+                 o_out = take(c.on_device ? 0 : cap_items * 12u);
+    grow(scene->source_stage, scene->source_stage_bytes, at);
+    uint8_t *b = scene->source_stage;
+    for (size_t first = 0; first < items; first += chunk_items) {
+        const size_t m_items = std::min(chunk_items, items - first), m = m_items * c.K;
+        const uint8_t *in = (const uint8_t *)c.in + first * 24u;
+        rt_rng *rng = c.rng + first * c.K;
+        float *out = c.out + first * 3u;
+        if (!c.on_device) {
+            HIP_CHECK(hipMemcpyAsync(b + o_in, in, m_items * 24u, hipMemcpyHostToDevice, stream));
+            HIP_CHECK(hipMemcpyAsync(b + o_rng, rng, m * sizeof(rt_rng), hipMemcpyHostToDevice, stream));
+        }
+        SourceView V{};
+        V.state = (uint32_t *)(b + o_state); V.n_pixslots = (uint32_t)((m + 63u) & ~(size_t)63u); V.n = (uint32_t)m; V.mode = c.mode;
+        V.rng = (uint4 *)(c.on_device ? (uint8_t *)rng : b + o_rng);
+        const float *records = (const float *)(c.on_device ? in : b + o_in);
+        if (c.mode == 1u) V.rays = records; else V.points = records;
+        V.streams = (uint32_t)c.K; V.scale = c.scale;
+        V.out = c.on_device ? out : (float *)(b + o_out);
+        T.launches += query_launch_source_pack(scene, V, stream);
+        SourceChunk C{};
+        C.mode = c.mode; C.n = V.n; C.streams = V.streams; C.rays = V.rays; C.points = V.points;
+        C.ray_depth = c.depth; C.samples = c.samples; C.state = V.state;
+        SourceResult res{};
+        if (const int rc = source_render(scene, C, stream, res, who)) return rc;
+        T.launches += res.launches + query_launch_source_unpack(scene, V, stream);
+        if (!c.on_device) {
+            HIP_CHECK(hipMemcpyAsync(out, b + o_out, m_items * 12u, hipMemcpyDeviceToHost, stream));
+            HIP_CHECK(hipMemcpyAsync(rng, b + o_rng, m * sizeof(rt_rng), hipMemcpyDeviceToHost, stream));
+        }
+        HIP_CHECK(hipStreamSynchronize(stream)); // the next chunk reuses the state and the staging
+        T.kernel_ms += res.kernel_ms; T.exact_walks += res.exact_walks; T.no_path += res.no_path; T.reference_exact = res.reference_exact;
+    }
     return RT_OK;
 }
 
@@ -675,6 +735,88 @@ int rt_bake(rt_scene *scene, const rt_bake_point *points, size_t n_points, const
             HIP_CHECK(hipMemcpy(totals, S.totals, sizeof totals, hipMemcpyDeviceToHost));
             st.exact_walks = totals[RQ_TOTAL_EXACT] + totals[RQ_TOTAL_RIDE_EXACT];
             st.kernel_ms = ms_sum;
+        }
+        st.total_ms = now_ms() - t0;
+        if (stats) *stats = st;
+        return RT_OK;
+    });
+}
+
+int rt_render_paths(rt_scene *scene, const rt_ray *rays, rt_rng *rng, size_t n, int32_t ray_depth, uint32_t flags, float *out_rgb, rt_query_stats *stats) {
+    const std::string who = "rt_render_paths: ";
+    if (n && (!rays || !rng || !out_rgb)) return fail(RT_ERR_INVALID_ARG, who + "null argument");
+    if (stats && stats->struct_size != sizeof(rt_query_stats)) return fail(RT_ERR_INVALID_ARG, who + "struct_size mismatch (ABI skew)");
+    if (flags & ~RT_QUERY_DEVICE_POINTERS) return fail(RT_ERR_INVALID_ARG, who + "flags other than RT_QUERY_DEVICE_POINTERS");
+    const bool on_device = (flags & RT_QUERY_DEVICE_POINTERS) != 0;
+    if (!on_device)
+        if (const int rc = check_bake_engines(rng, n, who)) return rc;
+    const int depth = ray_depth > 0 ? ray_depth : 6;
+    if (depth > RT_MAX_DEPTH) return fail(RT_ERR_LIMIT, who + "ray_depth above " + std::to_string(RT_MAX_DEPTH));
+    if (const int rc = check_call(scene, stats, flags, RT_QUERY_DEVICE_POINTERS, "RT_QUERY_DEVICE_POINTERS", who)) return rc;
+    if (n && on_device && ((uintptr_t)rng & 15u)) return fail(RT_ERR_INVALID_ARG, who + "with RT_QUERY_DEVICE_POINTERS the rt_rng array must be 16-byte aligned");
+    if (n && on_device && (((uintptr_t)rays | (uintptr_t)out_rgb) & 3u)) return fail(RT_ERR_INVALID_ARG, who + "with RT_QUERY_DEVICE_POINTERS rays and out_rgb must be 4-byte aligned");
+    if (const int rc = source_check(scene, (uint32_t)std::min(std::max<size_t>(n, 1u), source_chunk()), depth, 1, who)) return rc;
+    return guarded(who, [&]() -> int {
+        const double t0 = now_ms();
+        rt_query_stats st{};
+        st.struct_size = sizeof(rt_query_stats);
+        st.reference_exact = scene->view.exact_boxes == 1u ? 1u : 0u;
+        st.rays = n;
+        if (n) {
+            SourceTotals T;
+            if (const int rc = source_run(scene, SourceCall{1u, 1u, depth, 1, 0.f, rays, rng, out_rgb, on_device}, n, who, T)) return rc;
+            st.exact_walks = T.exact_walks; st.invalid_rays = T.no_path; st.kernel_ms = T.kernel_ms; st.launches = T.launches;
+            st.reference_exact = T.reference_exact;
+        }
+        st.total_ms = now_ms() - t0;
+        if (stats) *stats = st;
+        return RT_OK;
+    });
+}
+
+int rt_render_bake(rt_scene *scene, const rt_bake_point *points, size_t n_points, const rt_bake_params *params, rt_rng *rng, float *out, rt_bake_stats *stats) {
+    const std::string who = "rt_render_bake: ";
+    if (!params) return fail(RT_ERR_INVALID_ARG, who + "null argument (params)");
+    if (params->struct_size != sizeof(rt_bake_params)) return fail(RT_ERR_INVALID_ARG, who + "params.struct_size mismatch (ABI skew)");
+    if (stats && stats->struct_size != sizeof(rt_bake_stats)) return fail(RT_ERR_INVALID_ARG, who + "stats.struct_size mismatch (ABI skew)");
+    if (const int rc = check_bake_mode(params->mode, who, "params.mode")) return rc;
+    const uint32_t flags = params->flags;
+    if (flags & ~RT_QUERY_DEVICE_POINTERS) return fail(RT_ERR_INVALID_ARG, who + "params.flags other than RT_QUERY_DEVICE_POINTERS");
+    if (params->reserved[0] || params->reserved[1]) return fail(RT_ERR_INVALID_ARG, who + "params.reserved must be zero");
+    if (params->streams < 0) return fail(RT_ERR_INVALID_ARG, who + "params.streams must not be negative");
+    if (params->streams > 64) return fail(RT_ERR_LIMIT, who + "params.streams above 64");
+    const size_t K = params->streams ? (size_t)params->streams : 1u;
+    if (params->samples < 1) return fail(RT_ERR_INVALID_ARG, who + "params.samples must be at least 1");
+    if ((size_t)params->samples % K) return fail(RT_ERR_INVALID_ARG, who + "params.samples = " + std::to_string(params->samples) + " is no multiple of params.streams = " + std::to_string(K));
+    const int depth = params->ray_depth > 0 ? params->ray_depth : 6;
+    if (depth > RT_MAX_DEPTH) return fail(RT_ERR_LIMIT, who + "params.ray_depth above " + std::to_string(RT_MAX_DEPTH));
+    if (n_points > (((size_t)1 << 31) - 1u) / K) return fail(RT_ERR_LIMIT, who + "n_points * params.streams must stay below 2^31");
+    const size_t q = (size_t)params->samples / K;
+    if (q >= ((size_t)1 << 25)) return fail(RT_ERR_LIMIT, who + "params.samples / params.streams must stay below 2^25 (the path record's sample index)");
+    if (params->mode == RT_BAKE_SH9)
+        return fail(RT_ERR_UNSUPPORTED, who + "RT_BAKE_SH9 does not fit the persistent kernel's path record (27 accumulators and the first direction): rt_bake serves it");
+    if (n_points && (!points || !rng || !out)) return fail(RT_ERR_INVALID_ARG, who + "null argument");
+    const bool on_device = (flags & RT_QUERY_DEVICE_POINTERS) != 0;
+    if (!on_device)
+        if (const int rc = check_bake_engines(rng, n_points * K, who)) return rc;
+    if (!scene) return fail(RT_ERR_INVALID_ARG, who + "null argument (scene)");
+    if (const int rc = check_call(scene, nullptr, 0u, 0u, "", who)) return rc;
+    if (n_points && on_device && ((uintptr_t)rng & 15u)) return fail(RT_ERR_INVALID_ARG, who + "with RT_QUERY_DEVICE_POINTERS the rt_rng array must be 16-byte aligned");
+    if (n_points && on_device && (((uintptr_t)points | (uintptr_t)out) & 3u)) return fail(RT_ERR_INVALID_ARG, who + "with RT_QUERY_DEVICE_POINTERS points and out must be 4-byte aligned");
+    if (const int rc = source_check(scene, (uint32_t)std::min(std::max<size_t>(n_points, 1u) * K, source_chunk()), depth, (int32_t)q, who)) return rc;
+    const double pi = 3.14159265358979323846;
+    const float scale = (float)(pi / (double)params->samples);
+    return guarded(who, [&]() -> int {
+        const double t0 = now_ms();
+        rt_bake_stats st{};
+        st.struct_size = sizeof(rt_bake_stats);
+        st.reference_exact = scene->view.exact_boxes == 1u ? 1u : 0u;
+        st.points = n_points;
+        if (n_points) {
+            SourceTotals T;
+            if (const int rc = source_run(scene, SourceCall{2u, K, depth, (int32_t)q, scale, points, rng, out, on_device}, n_points, who, T)) return rc;
+            st.invalid_points = T.no_path; st.paths = (n_points - T.no_path) * K * q; st.exact_walks = T.exact_walks;
+            st.kernel_ms = T.kernel_ms; st.launches = T.launches; st.reference_exact = T.reference_exact;
         }
         st.total_ms = now_ms() - t0;
         if (stats) *stats = st;
