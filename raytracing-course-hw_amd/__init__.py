@@ -502,6 +502,24 @@ def _denoise_stats():
     return st
 
 
+def _query_stats():
+    st = rt_query_stats()
+    st.struct_size = C.sizeof(rt_query_stats)
+    return st
+
+
+def _bake_stats():
+    st = rt_bake_stats()
+    st.struct_size = C.sizeof(rt_bake_stats)
+    return st
+
+
+def _host_arrays_only(name, flags):
+    """The host-array wrappers refuse RT_QUERY_DEVICE_POINTERS: their arrays are numpy's."""
+    if flags & RT_QUERY_DEVICE_POINTERS:
+        raise ValueError(f"{name} takes host arrays; device memory goes through {name}_device")
+
+
 def unshard(params, buf):
     buf = np.ascontiguousarray(buf)
     full = np.zeros((params.height, params.width, 3), dtype=buf.dtype)
@@ -771,23 +789,20 @@ class Scene(_Handle):
         return st
 
     def _query(self, fn, rays_ptr, n, flags, out_ptr):
-        st = rt_query_stats()
-        st.struct_size = C.sizeof(rt_query_stats)
+        st = _query_stats()
         _check(fn(self._h, rays_ptr, n, flags, out_ptr, C.byref(st)))
         return st
 
     def query_closest(self, o, d, flags=0):
         """Closest hits of the rays (o[i], d[i]) (rt_query_closest): (array of HIT_DTYPE records, rt_query_stats)."""
-        if flags & RT_QUERY_DEVICE_POINTERS:
-            raise ValueError("query_closest takes host arrays; device memory goes through query_closest_device")
+        _host_arrays_only("query_closest", flags)
         rays = pack_rays(o, d)
         hits = np.zeros(rays.shape[0], dtype=HIT_DTYPE)
         return hits, self._query(lib.rt_query_closest, rays.ctypes.data, rays.shape[0], flags, hits.ctypes.data)
 
     def query_light_pdf(self, x, d, flags=0):
         """Light pdf of the directions d[i] seen from x[i] (rt_query_light_pdf): (float32 array, rt_query_stats)."""
-        if flags & RT_QUERY_DEVICE_POINTERS:
-            raise ValueError("query_light_pdf takes host arrays; device memory goes through query_light_pdf_device")
+        _host_arrays_only("query_light_pdf", flags)
         rays = pack_rays(x, d)
         pdf = np.zeros(rays.shape[0], dtype=np.float32)
         return pdf, self._query(lib.rt_query_light_pdf, rays.ctypes.data, rays.shape[0], flags, pdf.ctypes.data)
@@ -795,8 +810,7 @@ class Scene(_Handle):
     def query_occluded(self, o, d, tmax=None, flags=0):
         """Is anything in front of tmax[i] on the ray (o[i], d[i]) (rt_query_occluded; tmax None: does the ray hit anything):
         (uint8 array of RT_OCCLUSION_* bits, rt_query_stats)."""
-        if flags & RT_QUERY_DEVICE_POINTERS:
-            raise ValueError("query_occluded takes host arrays; device memory goes through query_occluded_device")
+        _host_arrays_only("query_occluded", flags)
         rays = pack_rays(o, d)
         n = rays.shape[0]
         if tmax is not None:
@@ -804,15 +818,13 @@ class Scene(_Handle):
             if tmax.shape != (n,):
                 raise ValueError(f"tmax must have shape ({n},), one bound per ray; got {tmax.shape}")
         out = np.zeros(n, dtype=np.uint8)
-        st = rt_query_stats()
-        st.struct_size = C.sizeof(rt_query_stats)
+        st = _query_stats()
         _check(lib.rt_query_occluded(self._h, rays.ctypes.data, None if tmax is None else tmax.ctypes.data, n, flags, out.ctypes.data, C.byref(st)))
         return out, st
 
     def query_occluded_device(self, rays_ptr, tmax_ptr, n, out_ptr, flags=0):
         """The same on device memory: n rt_ray and n floats (or None) in, n bytes out, no alignment demand on out."""
-        st = rt_query_stats()
-        st.struct_size = C.sizeof(rt_query_stats)
+        st = _query_stats()
         _check(lib.rt_query_occluded(self._h, rays_ptr, tmax_ptr, n, flags | RT_QUERY_DEVICE_POINTERS, out_ptr, C.byref(st)))
         return st
 
@@ -852,8 +864,7 @@ class Scene(_Handle):
         want = {"albedo": albedo, "normal": normal, "depth": depth, "emission": emission}
         planes = {k: np.zeros((height, width) if k == "depth" else (height, width, 3), dtype=np.float32) for k, v in want.items() if v}
         ptr = [planes[k].ctypes.data if k in planes else None for k in want]
-        st = rt_query_stats()
-        st.struct_size = C.sizeof(rt_query_stats)
+        st = _query_stats()
         _check(lib.rt_render_guides(self._h, width, height, 0, *ptr, C.byref(st)))
         return planes, st
 
@@ -899,41 +910,33 @@ class Scene(_Handle):
         _check(lib.rt_camera_rays(self._h, width, height, xy_ptr, n, RT_QUERY_DEVICE_POINTERS, out_ptr))
 
     def render_guides_device(self, width, height, albedo_ptr=None, normal_ptr=None, depth_ptr=None, emission_ptr=None):
-        st = rt_query_stats()
-        st.struct_size = C.sizeof(rt_query_stats)
+        st = _query_stats()
         _check(lib.rt_render_guides(self._h, width, height, RT_QUERY_DEVICE_POINTERS, albedo_ptr, normal_ptr, depth_ptr, emission_ptr, C.byref(st)))
-        return st
-
-    def _stats(self):
-        st = rt_query_stats()
-        st.struct_size = C.sizeof(rt_query_stats)
         return st
 
     def query_scatter(self, o, d, hits, surfaces, rng, flags=0):
         """One bounce of Scene::getColor per record (rt_query_scatter): the rays (o[i], d[i]) that hit, their HIT_DTYPE and
         SURFACE_DTYPE records and their engines, an RNG_DTYPE array that advances in place: (array of SCATTER_DTYPE records,
         rt_query_stats).  flags: RT_QUERY_REFERENCE_WALK."""
-        if flags & RT_QUERY_DEVICE_POINTERS:
-            raise ValueError("query_scatter takes host arrays; device memory goes through query_scatter_device")
+        _host_arrays_only("query_scatter", flags)
         rays = pack_rays(o, d)
         n = rays.shape[0]
         hits, surfaces, rng = _records(hits, HIT_DTYPE, n, "hits"), _records(surfaces, SURFACE_DTYPE, n, "surfaces"), _engines(rng, n)
         out = np.zeros(n, dtype=SCATTER_DTYPE)
-        st = self._stats()
+        st = _query_stats()
         _check(lib.rt_query_scatter(self._h, rays.ctypes.data, hits.ctypes.data, surfaces.ctypes.data, rng.ctypes.data, n, flags, out.ctypes.data, C.byref(st)))
         return out, st
 
     def query_scatter_device(self, rays_ptr, hits_ptr, surfaces_ptr, rng_ptr, n, out_ptr, flags=0):
         """The same on device memory of the scene's GPU: every record array but the rays 16-byte aligned; the engines advance in place."""
-        st = self._stats()
+        st = _query_stats()
         _check(lib.rt_query_scatter(self._h, rays_ptr, hits_ptr, surfaces_ptr, rng_ptr, n, flags | RT_QUERY_DEVICE_POINTERS, out_ptr, C.byref(st)))
         return st
 
     def query_bsdf(self, o, d, hits, surfaces, dirs, flags=0):
         """brdf and Mix::pdf of the directions dirs[i] at the hits of the rays (o[i], d[i]) (rt_query_bsdf): ((n, 3) float32, (n,)
         float32, rt_query_stats)."""
-        if flags & RT_QUERY_DEVICE_POINTERS:
-            raise ValueError("query_bsdf takes host arrays; device memory goes through query_bsdf_device")
+        _host_arrays_only("query_bsdf", flags)
         rays = pack_rays(o, d)
         n = rays.shape[0]
         hits, surfaces = _records(hits, HIT_DTYPE, n, "hits"), _records(surfaces, SURFACE_DTYPE, n, "surfaces")
@@ -941,36 +944,30 @@ class Scene(_Handle):
         if dirs.shape != (n, 3):
             raise ValueError(f"dirs must be ({n}, 3), got {dirs.shape}")
         brdf, pdf = np.zeros((n, 3), dtype=np.float32), np.zeros(n, dtype=np.float32)
-        st = self._stats()
+        st = _query_stats()
         _check(lib.rt_query_bsdf(self._h, rays.ctypes.data, hits.ctypes.data, surfaces.ctypes.data, dirs.ctypes.data, n, flags, brdf.ctypes.data, pdf.ctypes.data, C.byref(st)))
         return brdf, pdf, st
 
     def query_bsdf_device(self, rays_ptr, hits_ptr, surfaces_ptr, dirs_ptr, n, out_brdf_ptr, out_pdf_ptr, flags=0):
-        st = self._stats()
+        st = _query_stats()
         _check(lib.rt_query_bsdf(self._h, rays_ptr, hits_ptr, surfaces_ptr, dirs_ptr, n, flags | RT_QUERY_DEVICE_POINTERS, out_brdf_ptr, out_pdf_ptr, C.byref(st)))
         return st
 
     def trace_paths(self, o, d, rng, ray_depth=0, flags=0):
         """Scene::getColor(ray, ray_depth) for the rays (o[i], d[i]) with the engines rng[i], which advance in place (rt_trace_paths):
         ((n, 3) float32 radiance, rt_query_stats).  ray_depth 0 = 6."""
-        if flags & RT_QUERY_DEVICE_POINTERS:
-            raise ValueError("trace_paths takes host arrays; device memory goes through trace_paths_device")
+        _host_arrays_only("trace_paths", flags)
         rays = pack_rays(o, d)
         n = rays.shape[0]
         rng = _engines(rng, n)
         rgb = np.zeros((n, 3), dtype=np.float32)
-        st = self._stats()
+        st = _query_stats()
         _check(lib.rt_trace_paths(self._h, rays.ctypes.data, rng.ctypes.data, n, ray_depth, flags, rgb.ctypes.data, C.byref(st)))
         return rgb, st
 
     def trace_paths_device(self, rays_ptr, rng_ptr, n, out_rgb_ptr, ray_depth=0, flags=0):
-        st = self._stats()
+        st = _query_stats()
         _check(lib.rt_trace_paths(self._h, rays_ptr, rng_ptr, n, ray_depth, flags | RT_QUERY_DEVICE_POINTERS, out_rgb_ptr, C.byref(st)))
-        return st
-
-    def _bake_stats(self):
-        st = rt_bake_stats()
-        st.struct_size = C.sizeof(rt_bake_stats)
         return st
 
     def bake_rays(self, points, rng, mode=RT_BAKE_IRRADIANCE):
@@ -981,13 +978,13 @@ class Scene(_Handle):
         n = points.shape[0]
         rng = _engines(rng, n)
         rays = np.zeros(n, dtype=RAY_DTYPE)
-        st = self._stats()
+        st = _query_stats()
         _check(lib.rt_bake_rays(self._h, points.ctypes.data, rng.ctypes.data, n, mode, 0, rays.ctypes.data, C.byref(st)))
         return rays, st
 
     def bake_rays_device(self, points_ptr, rng_ptr, n, out_ptr, mode=RT_BAKE_IRRADIANCE):
         """The same on device memory of the scene's GPU: rt_rng 16-byte aligned, points and rays 4-byte."""
-        st = self._stats()
+        st = _query_stats()
         _check(lib.rt_bake_rays(self._h, points_ptr, rng_ptr, n, mode, RT_QUERY_DEVICE_POINTERS, out_ptr, C.byref(st)))
         return st
 
@@ -995,21 +992,20 @@ class Scene(_Handle):
         """Irradiance (n, 3) or SH9 coefficients (n, 9, 3) at the BAKE_POINT_DTYPE records (rt_bake): per point `streams` engines,
         rng[i * streams + k], which advance in place and draw samples / streams paths each.  flags: RT_QUERY_REFERENCE_WALK,
         RT_BAKE_LOCKSTEP.  Returns (float32 array, rt_bake_stats)."""
-        if flags & RT_QUERY_DEVICE_POINTERS:
-            raise ValueError("bake takes host arrays; device memory goes through bake_device")
+        _host_arrays_only("bake", flags)
         if mode not in BAKE_FLOATS:
             raise ValueError(f"mode must be RT_BAKE_IRRADIANCE or RT_BAKE_SH9, got {mode}")
         points = _records(points, BAKE_POINT_DTYPE, None, "points")
         n = points.shape[0]
         rng = _engines(rng, n * max(1, streams))
         out = np.zeros((n, 3) if mode == RT_BAKE_IRRADIANCE else (n, 9, 3), dtype=np.float32)
-        st = self._bake_stats()
+        st = _bake_stats()
         params = make_bake_params(samples, streams, mode, ray_depth, flags)
         _check(lib.rt_bake(self._h, points.ctypes.data, n, C.byref(params), rng.ctypes.data, out.ctypes.data, C.byref(st)))
         return out, st
 
     def bake_device(self, points_ptr, rng_ptr, n_points, out_ptr, samples, streams=1, mode=RT_BAKE_IRRADIANCE, ray_depth=0, flags=0):
-        st = self._bake_stats()
+        st = _bake_stats()
         params = make_bake_params(samples, streams, mode, ray_depth, flags | RT_QUERY_DEVICE_POINTERS)
         _check(lib.rt_bake(self._h, points_ptr, n_points, C.byref(params), rng_ptr, out_ptr, C.byref(st)))
         return st
@@ -1021,12 +1017,12 @@ class Scene(_Handle):
         n = rays.shape[0]
         rng = _engines(rng, n)
         rgb = np.zeros((n, 3), dtype=np.float32)
-        st = self._stats()
+        st = _query_stats()
         _check(lib.rt_render_paths(self._h, rays.ctypes.data, rng.ctypes.data, n, ray_depth, 0, rgb.ctypes.data, C.byref(st)))
         return rgb, st
 
     def render_paths_device(self, rays_ptr, rng_ptr, n, out_rgb_ptr, ray_depth=0):
-        st = self._stats()
+        st = _query_stats()
         _check(lib.rt_render_paths(self._h, rays_ptr, rng_ptr, n, ray_depth, RT_QUERY_DEVICE_POINTERS, out_rgb_ptr, C.byref(st)))
         return st
 
@@ -1037,13 +1033,13 @@ class Scene(_Handle):
         n = points.shape[0]
         rng = _engines(rng, n * max(1, streams))
         out = np.zeros((n, 3), dtype=np.float32)
-        st = self._bake_stats()
+        st = _bake_stats()
         params = make_bake_params(samples, streams, mode, ray_depth, 0)
         _check(lib.rt_render_bake(self._h, points.ctypes.data, n, C.byref(params), rng.ctypes.data, out.ctypes.data, C.byref(st)))
         return out, st
 
     def render_bake_device(self, points_ptr, rng_ptr, n_points, out_ptr, samples, streams=1, mode=RT_BAKE_IRRADIANCE, ray_depth=0):
-        st = self._bake_stats()
+        st = _bake_stats()
         params = make_bake_params(samples, streams, mode, ray_depth, RT_QUERY_DEVICE_POINTERS)
         _check(lib.rt_render_bake(self._h, points_ptr, n_points, C.byref(params), rng_ptr, out_ptr, C.byref(st)))
         return st

@@ -1,15 +1,18 @@
 // Batched ray queries through the C-ABI (include/rtamd.h: rt_query_closest, rt_query_light_pdf, rt_query_occluded), the first-hit layer over them
 // (rt_query_surface, rt_query_environment, rt_camera_rays, rt_render_guides) and the bounce step (rt_query_scatter, rt_query_bsdf,
-// rt_trace_paths, rt_rng_*) and its first caller, the baker (rt_bake_rays, rt_bake): argument checks, the chunking, the staging, the
-// rounds and the statistics; and rt_render_paths / rt_render_bake, the same answers through the persistent render kernel
-// (device/rt_path_source.h; the launches are rtamd_api.hip's frame driver, source_render).  No kernel and no kernel header here: the
-// kernels (device/rt_query.h, device/rt_query_surface.h, device/rt_query_scatter.h, device/rt_bake.h) live in rtamd_api.hip,
-// where every __global__ keeps one definition, and are launched through query_launch_* (device/rt_types_query.h).
+// rt_trace_paths, rt_rng_*) and its first caller, the baker (rt_bake_rays, rt_bake); and rt_render_paths / rt_render_bake, the same
+// answers through the persistent render kernel (device/rt_path_source.h; the launches are rtamd_api.hip's frame driver, source_render).
+// Host side only, each thing once: the argument predicates, the staging map, the chunk loop over a call's declared arrays, the stats
+// shell; then the entry points, which check in their own order, declare their arrays and build their views.  No kernel and no kernel
+// header here: the kernels (device/rt_query.h, device/rt_query_surface.h, device/rt_query_scatter.h, device/rt_bake.h) live in
+// rtamd_api.hip, where every __global__ keeps one definition, and are launched through query_launch_* (device/rt_types_query.h).
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <initializer_list>
 #include <string>
+#include <type_traits>
 #include "../../include/rtamd.h"
 #include "host/knobs.h"
 #include "host/rt_scene.h"
@@ -23,19 +26,120 @@ static_assert(sizeof(rt_bake_point) == 24 && sizeof(rt_bake_params) == 32 && siz
 static_assert(sizeof(rt_ray) == 24 && sizeof(rt_hit) == 64 && sizeof(rt_surface) == 64 && sizeof(rt_rng) == 16 && sizeof(rt_scatter) == 64,
               "rt_ray is 24 bytes, rt_rng 16, rt_hit, rt_surface and rt_scatter 64: the kernels read and write them as words");
 
+// ---- the argument predicates: each refusal's text once; every entry point asks them in its own order, which is part of the ABI ------------
+const uint32_t WALK_FLAGS = RT_QUERY_DEVICE_POINTERS | RT_QUERY_REFERENCE_WALK;
+bool device_pointers(uint32_t flags) { return (flags & RT_QUERY_DEVICE_POINTERS) != 0; }
+
+int null_arg(const std::string &who, const char *name = nullptr) {
+    return fail(RT_ERR_INVALID_ARG, who + "null argument" + (name ? " (" + std::string(name) + ")" : std::string()));
+}
+// A struct that carries its size: a stats record (null: not wanted) or rt_bake_params.  `field`: "", "stats." or "params.".
+template <class T> int check_struct_size(const T *s, const std::string &who, const char *field = "") {
+    if (s && s->struct_size != sizeof(T)) return fail(RT_ERR_INVALID_ARG, who + field + "struct_size mismatch (ABI skew)");
+    return RT_OK;
+}
+int check_flags(uint32_t flags, uint32_t allowed, const std::string &who, const char *field = "") {
+    if (!(flags & ~allowed)) return RT_OK;
+    const struct { uint32_t bit; const char *name; } known[] = {{RT_QUERY_DEVICE_POINTERS, "RT_QUERY_DEVICE_POINTERS"}, {RT_QUERY_REFERENCE_WALK, "RT_QUERY_REFERENCE_WALK"},
+                                                                {RT_BAKE_LOCKSTEP, "RT_BAKE_LOCKSTEP"}};
+    std::string names;
+    for (const auto &k : known)
+        if (allowed & k.bit) names += (names.empty() ? "" : " | ") + std::string(k.name);
+    return fail(RT_ERR_INVALID_ARG, who + field + "flags other than " + names);
+}
+// The scene's part of every check: there is one, and it was created for hw8 / hw7.
+int check_scene(const rt_scene *scene, const std::string &who, const char *name = nullptr) {
+    if (!scene) return null_arg(who, name);
+    if (scene->flavor != RT_INTEGRATOR_HW8) return fail(RT_ERR_UNSUPPORTED, who + "ray queries serve scenes created for hw8 / hw7 (this one was prepared for integrator " + std::to_string(scene->flavor) + ")");
+    return RT_OK;
+}
+// What the ray queries and the first-hit layer check first: the stats, that there is a scene, the flags, the scene's flavor.
+int check_walk_call(const rt_scene *scene, const rt_query_stats *stats, uint32_t flags, uint32_t allowed, const std::string &who) {
+    if (const int rc = check_struct_size(stats, who)) return rc;
+    if (!scene) return null_arg(who);
+    if (const int rc = check_flags(flags, allowed, who)) return rc;
+    return check_scene(scene, who);
+}
+// The engines of a host array, so that no launch ever sees a state the engine cannot be in (device arrays: the kernels mark such a record invalid).
+int check_engines(const rt_rng *rng, size_t n, bool on_device, const std::string &who) {
+    if (rng && !on_device)
+        for (size_t i = 0; i < n; i++)
+            if (!rq_rng_valid(rng[i].x))
+                return fail(RT_ERR_INVALID_ARG, who + "rng[" + std::to_string(i) + "].x = " + std::to_string(rng[i].x) + " is no state of the engine (1 .. 2147483646)");
+    return RT_OK;
+}
+int check_depth(int32_t ray_depth, const std::string &who, const char *field, int &depth) {
+    depth = ray_depth > 0 ? ray_depth : 6;
+    if (depth > RT_MAX_DEPTH) return fail(RT_ERR_LIMIT, who + field + "ray_depth above " + std::to_string(RT_MAX_DEPTH));
+    return RT_OK;
+}
+// `device`: the call has records and they are device arrays.
+int check_aligned(bool device, std::initializer_list<const void *> arrays, unsigned bytes, const char *what, const std::string &who) {
+    uintptr_t bits = 0;
+    for (const void *p : arrays) bits |= (uintptr_t)p;
+    if (device && (bits & (bytes - 1u))) return fail(RT_ERR_INVALID_ARG, who + "with RT_QUERY_DEVICE_POINTERS " + what + " must be " + std::to_string(bytes) + "-byte aligned");
+    return RT_OK;
+}
+// The device arrays of a call with engines: the rt_rng records by 16 bytes, its two float arrays `names` by 4.
+int check_engine_arrays(bool device, const void *rng, const void *a, const void *b, const char *names, const std::string &who) {
+    if (const int rc = check_aligned(device, {rng}, 16, "the rt_rng array", who)) return rc;
+    return check_aligned(device, {a, b}, 4, names, who);
+}
+int check_bake_mode(int32_t mode, const std::string &who, const char *field) {
+    if (mode != RT_BAKE_IRRADIANCE && mode != RT_BAKE_SH9)
+        return fail(RT_ERR_INVALID_ARG, who + field + " = " + std::to_string(mode) + " is neither RT_BAKE_IRRADIANCE nor RT_BAKE_SH9");
+    return RT_OK;
+}
+// The block rt_bake and rt_render_bake share, up to the slot limit; K and depth: the streams and the ray depth with their defaults filled in.
+int check_bake_params(const rt_bake_params *params, const rt_bake_stats *stats, size_t n_points, uint32_t allowed, const std::string &who, size_t &K, int &depth) {
+    if (!params) return null_arg(who, "params");
+    if (const int rc = check_struct_size(params, who, "params.")) return rc;
+    if (const int rc = check_struct_size(stats, who, "stats.")) return rc;
+    if (const int rc = check_bake_mode(params->mode, who, "params.mode")) return rc;
+    if (const int rc = check_flags(params->flags, allowed, who, "params.")) return rc;
+    if (params->reserved[0] || params->reserved[1]) return fail(RT_ERR_INVALID_ARG, who + "params.reserved must be zero");
+    if (params->streams < 0) return fail(RT_ERR_INVALID_ARG, who + "params.streams must not be negative");
+    if (params->streams > 64) return fail(RT_ERR_LIMIT, who + "params.streams above 64");
+    K = params->streams ? (size_t)params->streams : 1u;
+    if (params->samples < 1) return fail(RT_ERR_INVALID_ARG, who + "params.samples must be at least 1");
+    if ((size_t)params->samples % K) return fail(RT_ERR_INVALID_ARG, who + "params.samples = " + std::to_string(params->samples) + " is no multiple of params.streams = " + std::to_string(K));
+    if (const int rc = check_depth(params->ray_depth, who, "params.", depth)) return rc;
+    if (n_points > (((size_t)1 << 31) - 1u) / K) return fail(RT_ERR_LIMIT, who + "n_points * params.streams must stay below 2^31");
+    return RT_OK;
+}
+// What the three bake calls check last: their arrays, the engines of host arrays, the scene (`scene_name`: how a null one is reported), the alignment.
+int check_bake_arrays(const rt_scene *scene, const char *scene_name, const void *points, const rt_rng *rng, const void *out, size_t n, size_t K, bool on_device, const std::string &who) {
+    if (n && (!points || !rng || !out)) return null_arg(who);
+    if (const int rc = check_engines(rng, n * K, on_device, who)) return rc;
+    if (const int rc = check_scene(scene, who, scene_name)) return rc;
+    return check_engine_arrays(n && on_device, rng, points, out, "points and out", who);
+}
+
+// ---- the staging map ------------------------------------------------------------------------------------------------------------------------
 // Rays per chunk: what the staging is sized for.  RTAMD_QUERY_CHUNK (testing) lowers it, so that a small call crosses chunk seams; it
 // changes no answer, a ray's answer does not depend on its neighbours.
 const size_t QUERY_CHUNK = 262144;
 size_t query_chunk() { return std::min(QUERY_CHUNK, (size_t)std::max(64, env_positive("RTAMD_QUERY_CHUNK", (int)QUERY_CHUNK))); }
 
-// The staging of one chunk, carved out of one allocation that the scene keeps: counters first, then the arrays in 256-byte steps.
-// The two ray queries need the first eight parts; a surface query or a guide pass (STAGE_FIRST_HIT) grows the allocation by the next
-// two, an occlusion query (STAGE_OCCLUSION) by the last two: a bound and an answer byte per ray.  The bounce step (STAGE_SCATTER) takes
-// the first-hit layer's parts and four more: the engines, the rt_scatter records, the rays of the light walk and its answers.  The
-// baker (STAGE_BAKE) takes the bounce step's parts and its per-slot state: the points, the first directions, `bake_floats` accumulator
-// floats, the samples left, its counters and, with host arrays, the chunk's answer.
+// Both stagings (rt_scene::query_stage, source_stage) are one allocation carved in 256-byte steps: a pass over a null base measures, a
+// pass over the allocation binds.  A part of no bytes takes no room and stays null.
+struct Carver {
+    uint8_t *base; size_t at = 0;
+    template <class T> void operator()(T *&part, size_t bytes) {
+        part = base && bytes ? (T *)(base + at) : nullptr;
+        at += (bytes + 255u) & ~(size_t)255u;
+    }
+};
+
+// The staging of one chunk of the composed calls: counters first, then the arrays.  The two ray queries need the first eight parts; a
+// surface query or a guide pass (STAGE_FIRST_HIT) grows the allocation by the next two, an occlusion query (STAGE_OCCLUSION) by a bound
+// and an answer byte per ray.  The bounce step (STAGE_SCATTER) takes the first-hit layer's parts and four more: the engines, the
+// rt_scatter records, the rays of the light walk and its answers.  The baker (STAGE_BAKE) takes the bounce step's parts and its per-slot
+// state: the points, the first directions, `bake_floats` accumulator floats, the samples left, its counters and, with host arrays
+// (`bake_out`), the chunk's answer.
 const size_t PLANE_FLOATS = 10; // albedo 3, normal 3, depth 1, emission 3
 enum StageParts { STAGE_WALK, STAGE_FIRST_HIT, STAGE_OCCLUSION, STAGE_SCATTER, STAGE_BAKE };
+struct StageSpec { StageParts parts; size_t bake_floats = 0; bool bake_out = false; };
 struct QueryStage {
     uint32_t *ctr; unsigned long long *totals;
     float *rays; uint8_t *out; float4 *rec; uint32_t *q_fast, *q_exact, *ovf;
@@ -44,92 +148,133 @@ struct QueryStage {
     uint8_t *rng, *scat; float *walk_rays, *light_pdf;
     float *bake_points, *bake_dir0, *bake_acc, *bake_out; uint32_t *bake_left; unsigned long long *bake_ctr;
 };
-QueryStage query_stage(rt_scene *scene, StageParts parts, size_t bake_floats = 0, bool bake_out = false) {
-    const bool bake = parts == STAGE_BAKE, scatter = parts == STAGE_SCATTER || bake, first_hit = parts == STAGE_FIRST_HIT || scatter, occlusion = parts == STAGE_OCCLUSION;
+QueryStage query_stage(rt_scene *scene, const StageSpec &spec) {
+    const bool bake = spec.parts == STAGE_BAKE, scatter = spec.parts == STAGE_SCATTER || bake, first_hit = spec.parts == STAGE_FIRST_HIT || scatter;
     const size_t C = QUERY_CHUNK, ovf_words = query_ovf_words(scene);
-    size_t at = 0;
-    auto take = [&](size_t bytes) { const size_t here = at; at += (bytes + 255u) & ~(size_t)255u; return here; };
-    const size_t o_ctr = take(RQ_CTR_WORDS * 4), o_tot = take(RQ_TOTAL_WORDS * 8), o_rays = take(C * sizeof(rt_ray)), o_out = take(C * sizeof(rt_hit)),
-                 o_rec = take(C * 16), o_fast = take(C * 4), o_exact = take(C * 4), o_ovf = take(ovf_words * 4);
-    size_t o_surf = 0, o_planes = 0;
-    if (first_hit) { o_surf = take(C * sizeof(rt_surface)); o_planes = take(C * PLANE_FLOATS * 4); }
-    size_t o_tmax = 0, o_occ = 0;
-    if (occlusion) { o_tmax = take(C * sizeof(float)); o_occ = take(C); }
-    size_t o_rng = 0, o_scat = 0, o_walk = 0, o_lpdf = 0;
-    if (scatter) { o_rng = take(C * sizeof(rt_rng)); o_scat = take(C * sizeof(rt_scatter)); o_walk = take(C * sizeof(rt_ray)); o_lpdf = take(C * sizeof(float)); }
-    size_t o_bpts = 0, o_bdir = 0, o_bacc = 0, o_bleft = 0, o_bctr = 0, o_bout = 0;
-    if (bake) {
-        o_bpts = take(C * sizeof(rt_bake_point)); o_bdir = take(C * 12); o_bacc = take(C * bake_floats * 4); o_bleft = take(C * 4);
-        o_bctr = take(RQ_BAKE_CTR_WORDS * 8); o_bout = take(bake_out ? C * bake_floats * 4 : 0);
-    }
-    grow(scene->query_stage, scene->query_stage_bytes, at);
-    uint8_t *b = scene->query_stage;
-    QueryStage s;
-    s.ctr = (uint32_t *)(b + o_ctr); s.totals = (unsigned long long *)(b + o_tot);
-    s.rays = (float *)(b + o_rays); s.out = b + o_out; s.rec = (float4 *)(b + o_rec);
-    s.q_fast = (uint32_t *)(b + o_fast); s.q_exact = (uint32_t *)(b + o_exact);
-    s.ovf = ovf_words ? (uint32_t *)(b + o_ovf) : nullptr;
-    s.surf = first_hit ? b + o_surf : nullptr; s.planes = first_hit ? (float *)(b + o_planes) : nullptr;
-    s.tmax = occlusion ? (float *)(b + o_tmax) : nullptr; s.occ = occlusion ? b + o_occ : nullptr;
-    s.rng = scatter ? b + o_rng : nullptr; s.scat = scatter ? b + o_scat : nullptr;
-    s.walk_rays = scatter ? (float *)(b + o_walk) : nullptr; s.light_pdf = scatter ? (float *)(b + o_lpdf) : nullptr;
-    s.bake_points = bake ? (float *)(b + o_bpts) : nullptr; s.bake_dir0 = bake ? (float *)(b + o_bdir) : nullptr;
-    s.bake_acc = bake ? (float *)(b + o_bacc) : nullptr; s.bake_left = bake ? (uint32_t *)(b + o_bleft) : nullptr;
-    s.bake_ctr = bake ? (unsigned long long *)(b + o_bctr) : nullptr; s.bake_out = bake && bake_out ? (float *)(b + o_bout) : nullptr;
+    QueryStage s{};
+    auto carve = [&](uint8_t *base) {
+        Carver take{base};
+        take(s.ctr, RQ_CTR_WORDS * 4); take(s.totals, RQ_TOTAL_WORDS * 8); take(s.rays, C * sizeof(rt_ray)); take(s.out, C * sizeof(rt_hit));
+        take(s.rec, C * 16); take(s.q_fast, C * 4); take(s.q_exact, C * 4); take(s.ovf, ovf_words * 4);
+        if (first_hit) { take(s.surf, C * sizeof(rt_surface)); take(s.planes, C * PLANE_FLOATS * 4); }
+        if (spec.parts == STAGE_OCCLUSION) { take(s.tmax, C * sizeof(float)); take(s.occ, C); }
+        if (scatter) { take(s.rng, C * sizeof(rt_rng)); take(s.scat, C * sizeof(rt_scatter)); take(s.walk_rays, C * sizeof(rt_ray)); take(s.light_pdf, C * sizeof(float)); }
+        if (bake) {
+            take(s.bake_points, C * sizeof(rt_bake_point)); take(s.bake_dir0, C * 12); take(s.bake_acc, C * spec.bake_floats * 4); take(s.bake_left, C * 4);
+            take(s.bake_ctr, RQ_BAKE_CTR_WORDS * 8); take(s.bake_out, spec.bake_out ? C * spec.bake_floats * 4 : 0);
+        }
+        return take.at;
+    };
+    grow(scene->query_stage, scene->query_stage_bytes, carve(nullptr));
+    carve(scene->query_stage);
     return s;
 }
 
-// What every call here checks first.  `allowed`: the flags the function takes, `allowed_names` their names for the message.
-int check_call(const rt_scene *scene, const rt_query_stats *stats, uint32_t flags, uint32_t allowed, const char *allowed_names, const std::string &who) {
-    if (stats && stats->struct_size != sizeof(rt_query_stats)) return fail(RT_ERR_INVALID_ARG, who + "struct_size mismatch (ABI skew)");
-    if (!scene) return fail(RT_ERR_INVALID_ARG, who + "null argument");
-    if (flags & ~allowed) return fail(RT_ERR_INVALID_ARG, who + "flags other than " + allowed_names);
-    if (scene->flavor != RT_INTEGRATOR_HW8) return fail(RT_ERR_UNSUPPORTED, who + "ray queries serve scenes created for hw8 / hw7 (this one was prepared for integrator " + std::to_string(scene->flavor) + ")");
+// ---- the chunk loop -------------------------------------------------------------------------------------------------------------------------
+// A caller's array as a call declares it, once: the caller's pointer (null: not given), the bytes per item, its slot in the staging, and
+// whether the kernels read it (IN), write it (OUT) or both.  `at`: the chunk's part as the kernels see it, set by chunks().
+enum { IN = 1, OUT = 2 };
+struct Arr {
+    void *caller; size_t stride; void *stage; int dir;
+    uint8_t *at = nullptr;
+    template <class T> T *as() const { return (T *)at; }
+};
+Arr arr_in(const void *caller, size_t stride, void *stage) { return Arr{(void *)caller, stride, stage, IN}; }
+Arr arr_out(void *caller, size_t stride, void *stage) { return Arr{caller, stride, stage, OUT}; }
+Arr arr_inout(void *caller, size_t stride, void *stage) { return Arr{caller, stride, stage, IN | OUT}; }
+
+// The scene's two events around a stretch of launches; add() reads them once the stream has been waited for.
+struct Timer {
+    rt_scene *scene; hipStream_t stream; float ms = 0.f;
+    void start() { HIP_CHECK(hipEventRecord(scene->ev_start, stream)); }
+    void stop() { HIP_CHECK(hipEventRecord(scene->ev_stop, stream)); }
+    void add() { float t = 0.f; HIP_CHECK(hipEventElapsedTime(&t, scene->ev_start, scene->ev_stop)); ms += t; }
+};
+
+// One call over `items` items in chunks.  Host arrays: the in-arrays of a chunk are copied to the staging, body(first, m) finds the
+// staging in Arr::at, the out-arrays are copied back.  Device pointers: body finds the caller's own memory from `first` on and nothing
+// is copied.  Either way a chunk ends with one synchronisation, the next reuses the staging; `timer` (nullable) then reads its events.
+// body returns RT_OK or the refusal that ends the call.  `arrays`: the call's own struct of nothing but Arr members, so that the call
+// names each array where it declares it and where it builds its view, and the loop sees them all.
+template <class Arrays, class Body>
+int chunks(size_t items, size_t chunk_items, bool on_device, Arrays &arrays, hipStream_t stream, Timer *timer, Body body) {
+    static_assert(std::is_standard_layout<Arrays>::value && sizeof(Arrays) % sizeof(Arr) == 0, "a struct of Arr members and nothing else");
+    Arr *const A = reinterpret_cast<Arr *>(&arrays), *const A_end = A + sizeof(Arrays) / sizeof(Arr);
+    for (size_t first = 0; first < items; first += chunk_items) {
+        const size_t m = std::min(chunk_items, items - first);
+        for (Arr *a = A; a != A_end; a++) {
+            uint8_t *own = a->caller ? (uint8_t *)a->caller + first * a->stride : nullptr;
+            a->at = !own ? nullptr : on_device ? own : (uint8_t *)a->stage;
+            if (own && !on_device && (a->dir & IN)) HIP_CHECK(hipMemcpyAsync(a->stage, own, m * a->stride, hipMemcpyHostToDevice, stream));
+        }
+        if (const int rc = body(first, m)) return rc;
+        for (const Arr *a = A; a != A_end; a++)
+            if (a->caller && !on_device && (a->dir & OUT)) HIP_CHECK(hipMemcpyAsync((uint8_t *)a->caller + first * a->stride, a->stage, m * a->stride, hipMemcpyDeviceToHost, stream));
+        HIP_CHECK(hipStreamSynchronize(stream));
+        if (timer) timer->add();
+    }
     return RT_OK;
 }
 
-// One call over n items in chunks.  Per chunk: before(S, first, m, stream) queues the copies in, launch(...) the kernels (between the
-// scene's two events) and returns their number, after(...) queues the copies out; the next chunk reuses the staging, so each ends with
-// a synchronisation.  n == 0 launches nothing.
-template <class Before, class Launch, class After>
-int answer(rt_scene *scene, size_t n, rt_query_stats *stats, const std::string &who, StageParts parts, Before before, Launch launch, After after) {
+// ---- the stats shell ------------------------------------------------------------------------------------------------------------------------
+uint64_t &items_of(rt_query_stats &st) { return st.rays; }
+uint64_t &items_of(rt_bake_stats &st) { return st.points; }
+void invalid_total(rt_query_stats &st, uint64_t invalid) { st.invalid_rays = invalid; }
+void invalid_total(rt_bake_stats &, uint64_t) {} // the baker counts its invalid points itself
+
+// A call over n items under the guard: work(st) fills in what it did (n == 0: nothing to do) and returns RT_OK or its refusal.
+template <class Stats, class Work>
+int with_stats(const rt_scene *scene, size_t n, Stats *stats, const std::string &who, Work work) {
     return guarded(who, [&]() -> int {
         const double t0 = now_ms();
-        rt_query_stats st{};
-        st.struct_size = sizeof(rt_query_stats);
+        Stats st{};
+        st.struct_size = sizeof(Stats);
         st.reference_exact = scene->view.exact_boxes == 1u ? 1u : 0u;
-        st.rays = n;
-        if (n) {
-            HIP_CHECK(hipSetDevice(scene->device));
-            hipStream_t stream = nullptr;
-            const QueryStage S = query_stage(scene, parts);
-            const size_t chunk = query_chunk();
-            HIP_CHECK(hipMemsetAsync(S.totals, 0, RQ_TOTAL_WORDS * 8, stream));
-            float ms_sum = 0.f;
-            for (size_t first = 0; first < n; first += chunk) {
-                const size_t m = std::min(chunk, n - first);
-                before(S, first, m, stream);
-                HIP_CHECK(hipMemsetAsync(S.ctr, 0, RQ_CTR_WORDS * 4, stream));
-                HIP_CHECK(hipEventRecord(scene->ev_start, stream));
-                st.launches += launch(S, first, m, stream);
-                HIP_CHECK(hipEventRecord(scene->ev_stop, stream));
-                after(S, first, m, stream);
-                HIP_CHECK(hipStreamSynchronize(stream)); // the next chunk reuses the staging
-                float ms = 0.f;
-                HIP_CHECK(hipEventElapsedTime(&ms, scene->ev_start, scene->ev_stop));
-                ms_sum += ms;
-            }
-            unsigned long long totals[RQ_TOTAL_WORDS];
-            HIP_CHECK(hipMemcpy(totals, S.totals, sizeof totals, hipMemcpyDeviceToHost));
-            st.exact_walks = totals[RQ_TOTAL_EXACT] + totals[RQ_TOTAL_RIDE_EXACT]; st.invalid_rays = totals[RQ_TOTAL_INVALID];
-            st.kernel_ms = ms_sum;
-        }
+        items_of(st) = n;
+        if (n)
+            if (const int rc = work(st)) return rc;
         st.total_ms = now_ms() - t0;
         if (stats) *stats = st;
         return RT_OK;
     });
 }
 
+// A chunk of a composed call as its launch body sees it: m slots (items x K) from item `first` on.
+struct Chunk { const QueryStage &S; size_t first, m; hipStream_t stream; Timer &T; };
+const auto no_prepare = [](const Chunk &, const auto &) {};
+
+// The composed calls: n items of K slots through the scene's staging.  declare(S) names the caller's arrays; per chunk prepare(chunk, arrays)
+// runs before the counters are zeroed and the clock starts, body(chunk, arrays, st) builds its views, launches and returns the number
+// of launches.  The totals of all walks are read once, after the last chunk.
+template <class Stats, class Declare, class Prepare, class Body>
+int answer(rt_scene *scene, size_t n, size_t K, Stats *stats, const std::string &who, const StageSpec &spec, bool on_device, Declare declare, Prepare prepare, Body body) {
+    return with_stats(scene, n, stats, who, [&](Stats &st) -> int {
+        HIP_CHECK(hipSetDevice(scene->device));
+        hipStream_t stream = nullptr;
+        const QueryStage S = query_stage(scene, spec);
+        auto A = declare(S);
+        Timer T{scene, stream};
+        HIP_CHECK(hipMemsetAsync(S.totals, 0, RQ_TOTAL_WORDS * 8, stream));
+        const int rc = chunks(n, query_chunk() / K, on_device, A, stream, &T, [&](size_t first, size_t items) -> int { // whole items: K <= 64, the chunk's minimum
+            const Chunk c{S, first, items * K, stream, T};
+            prepare(c, A);
+            HIP_CHECK(hipMemsetAsync(S.ctr, 0, RQ_CTR_WORDS * 4, stream));
+            T.start();
+            st.launches += body(c, A, st);
+            T.stop();
+            return RT_OK;
+        });
+        if (rc) return rc;
+        unsigned long long totals[RQ_TOTAL_WORDS];
+        HIP_CHECK(hipMemcpy(totals, S.totals, sizeof totals, hipMemcpyDeviceToHost));
+        st.exact_walks = totals[RQ_TOTAL_EXACT] + totals[RQ_TOTAL_RIDE_EXACT];
+        invalid_total(st, totals[RQ_TOTAL_INVALID]);
+        st.kernel_ms = T.ms;
+        return RT_OK;
+    });
+}
+
+// ---- views and launches that several calls share --------------------------------------------------------------------------------------------
 // The closest-hit and light-pdf launches' view of a chunk of m rays at `rays`.
 QueryView walk_view(const rt_scene *scene, const QueryStage &S, size_t m, uint32_t flags, const float *rays) {
     QueryView Q{};
@@ -143,24 +288,18 @@ QueryView walk_view(const rt_scene *scene, const QueryStage &S, size_t m, uint32
 
 // Both ray queries: `light` answers one float per ray, else one rt_hit.
 int query(rt_scene *scene, const rt_ray *rays, size_t n, uint32_t flags, void *out, rt_query_stats *stats, bool light, const std::string &who) {
-    if (const int rc = check_call(scene, stats, flags, RT_QUERY_DEVICE_POINTERS | RT_QUERY_REFERENCE_WALK, "RT_QUERY_DEVICE_POINTERS | RT_QUERY_REFERENCE_WALK", who)) return rc;
+    if (const int rc = check_walk_call(scene, stats, flags, WALK_FLAGS, who)) return rc;
     if (light && scene->view.n_lights == 0) return fail(RT_ERR_INVALID_ARG, who + "the scene has no lights: there is no light pdf to ask for");
-    if (n && (!rays || !out)) return fail(RT_ERR_INVALID_ARG, who + "null argument");
-    const bool on_device = (flags & RT_QUERY_DEVICE_POINTERS) != 0;
-    if (n && on_device && !light && ((uintptr_t)out & 15u)) return fail(RT_ERR_INVALID_ARG, who + "with RT_QUERY_DEVICE_POINTERS the rt_hit array must be 16-byte aligned");
-    const size_t out_size = light ? sizeof(float) : sizeof(rt_hit);
-    return answer(scene, n, stats, who, STAGE_WALK,
-        [&](const QueryStage &S, size_t first, size_t m, hipStream_t stream) {
-            if (!on_device) HIP_CHECK(hipMemcpyAsync(S.rays, rays + first, m * sizeof(rt_ray), hipMemcpyHostToDevice, stream));
-        },
-        [&](const QueryStage &S, size_t first, size_t m, hipStream_t stream) {
-            QueryView Q = walk_view(scene, S, m, flags, on_device ? (const float *)(rays + first) : S.rays);
-            uint8_t *dev_out = on_device ? (uint8_t *)out + first * out_size : S.out;
-            if (light) Q.pdf = (float *)dev_out; else Q.hits = (uint4 *)dev_out;
-            return light ? query_launch_light_pdf(scene, Q, stream) : query_launch_closest(scene, Q, stream);
-        },
-        [&](const QueryStage &S, size_t first, size_t m, hipStream_t stream) {
-            if (!on_device) HIP_CHECK(hipMemcpyAsync((uint8_t *)out + first * out_size, S.out, m * out_size, hipMemcpyDeviceToHost, stream));
+    if (n && (!rays || !out)) return null_arg(who);
+    const bool on_device = device_pointers(flags);
+    if (const int rc = check_aligned(n && on_device && !light, {out}, 16, "the rt_hit array", who)) return rc;
+    struct A { Arr rays, out; };
+    return answer(scene, n, 1, stats, who, {STAGE_WALK}, on_device,
+        [&](const QueryStage &S) { return A{arr_in(rays, sizeof(rt_ray), S.rays), arr_out(out, light ? sizeof(float) : sizeof(rt_hit), S.out)}; }, no_prepare,
+        [&](const Chunk &c, const A &a, rt_query_stats &) {
+            QueryView Q = walk_view(scene, c.S, c.m, flags, a.rays.as<float>());
+            if (light) Q.pdf = a.out.as<float>(); else Q.hits = a.out.as<uint4>();
+            return light ? query_launch_light_pdf(scene, Q, c.stream) : query_launch_closest(scene, Q, c.stream);
         });
 }
 
@@ -181,28 +320,11 @@ SurfaceView surface_view(const rt_scene *scene, const QueryStage &S, size_t m, c
     return V;
 }
 
-// ---- the bounce step ------------------------------------------------------------------------------------------------------------------------
-const uint32_t SCATTER_FLAGS = RT_QUERY_DEVICE_POINTERS | RT_QUERY_REFERENCE_WALK;
-const char *const SCATTER_FLAG_NAMES = "RT_QUERY_DEVICE_POINTERS | RT_QUERY_REFERENCE_WALK";
-
-// What rt_query_scatter, rt_query_bsdf and rt_trace_paths check before the scene: stats, flags, and the engines of a host array, so
-// that no launch ever sees a state the engine cannot be in (device arrays: the sample kernel marks such a record invalid).
-int check_scatter_call(const rt_query_stats *stats, uint32_t flags, const rt_rng *rng, size_t n, const std::string &who) {
-    if (stats && stats->struct_size != sizeof(rt_query_stats)) return fail(RT_ERR_INVALID_ARG, who + "struct_size mismatch (ABI skew)");
-    if (flags & ~SCATTER_FLAGS) return fail(RT_ERR_INVALID_ARG, who + "flags other than " + SCATTER_FLAG_NAMES);
-    if (rng && !(flags & RT_QUERY_DEVICE_POINTERS))
-        for (size_t i = 0; i < n; i++)
-            if (!rq_rng_valid(rng[i].x))
-                return fail(RT_ERR_INVALID_ARG, who + "rng[" + std::to_string(i) + "].x = " + std::to_string(rng[i].x) + " is no state of the engine (1 .. 2147483646)");
-    return RT_OK;
-}
-
-// A chunk's records as the kernels see them: the caller's device arrays from `first` on, or the staging.
-struct ScatterArrays { const rt_ray *rays; const rt_hit *hits; const rt_surface *surfaces; rt_rng *rng; rt_scatter *out; };
-ScatterView scatter_view(const QueryStage &S, size_t m, const ScatterArrays &A) {
+// A chunk's records as the bounce step's kernels see them: the caller's device arrays from the chunk's first on, or the staging.
+ScatterView scatter_view(const QueryStage &S, size_t m, const void *rays, const void *hits, const void *surfaces, void *rng, void *out) {
     ScatterView V{};
-    V.rays = (const float *)A.rays; V.hits = (const uint4 *)A.hits; V.surfaces = (const uint4 *)A.surfaces;
-    V.rng = (uint4 *)A.rng; V.out = (uint4 *)A.out;
+    V.rays = (const float *)rays; V.hits = (const uint4 *)hits; V.surfaces = (const uint4 *)surfaces;
+    V.rng = (uint4 *)rng; V.out = (uint4 *)out;
     V.walk_rays = S.walk_rays; V.light_pdf = S.light_pdf;
     V.n = (uint32_t)m; V.totals = S.totals;
     return V;
@@ -218,10 +340,22 @@ uint32_t launch_ride_light_pdf(const rt_scene *scene, const QueryStage &S, size_
     return query_launch_light_pdf(scene, Q, stream);
 }
 
-// The per-bounce stack of rt_trace_paths for `paths` paths of a chunk: 16 bytes of state, then 24 bytes per bounce.
-uint8_t *path_stack(rt_scene *scene, size_t paths, int depth) {
+// The paths of rt_trace_paths and rt_bake run over the staging: rays, hits, surfaces and scatter records there, the engines at `rng`.
+// Their per-bounce stack for `paths` paths of a chunk: 16 bytes of state (zeroed per chunk: tail 0, no bounce kept, not ended), then
+// 24 bytes per bounce.
+struct Paths { ScatterView V; PathView P; };
+void prepare_paths(rt_scene *scene, size_t paths, int depth, hipStream_t stream) {
+    ensure_materials(scene, stream);
     grow(scene->path_stack, scene->path_stack_bytes, paths * (16u + 24u * (size_t)depth));
-    return scene->path_stack;
+    HIP_CHECK(hipMemsetAsync(scene->path_stack, 0, paths * 16u, stream));
+}
+Paths paths_view(const rt_scene *scene, const Chunk &c, void *rng, size_t paths) {
+    const QueryStage &S = c.S;
+    Paths p{scatter_view(S, c.m, S.rays, S.out, S.surf, rng, S.scat), PathView{}};
+    p.P.rays = S.rays; p.P.hits = p.V.hits; p.P.surfaces = p.V.surfaces; p.P.scatter = p.V.out;
+    p.P.state = (float4 *)scene->path_stack; p.P.stack = (float *)(scene->path_stack + paths * 16u);
+    p.P.n = (uint32_t)c.m;
+    return p;
 }
 
 // One round of a chunk's m paths, for rt_trace_paths and rt_bake: closest hit, surface, scatter sample, light walk, scatter finish over
@@ -238,22 +372,6 @@ uint32_t launch_round(rt_scene *scene, const QueryStage &S, const ScatterView &V
     launches += launch_ride_light_pdf(scene, S, m, flags, true, stream);
     return launches + query_launch_scatter_finish(scene, V, stream);
 }
-
-// What rt_bake_rays and rt_bake refuse alike.
-const uint32_t BAKE_RAYS_FLAGS = RT_QUERY_DEVICE_POINTERS;
-const uint32_t BAKE_FLAGS = RT_QUERY_DEVICE_POINTERS | RT_QUERY_REFERENCE_WALK | RT_BAKE_LOCKSTEP;
-int check_bake_mode(int32_t mode, const std::string &who, const char *field) {
-    if (mode != RT_BAKE_IRRADIANCE && mode != RT_BAKE_SH9)
-        return fail(RT_ERR_INVALID_ARG, who + field + " = " + std::to_string(mode) + " is neither RT_BAKE_IRRADIANCE nor RT_BAKE_SH9");
-    return RT_OK;
-}
-int check_bake_engines(const rt_rng *rng, size_t n, const std::string &who) {
-    for (size_t i = 0; i < n; i++)
-        if (!rq_rng_valid(rng[i].x))
-            return fail(RT_ERR_INVALID_ARG, who + "rng[" + std::to_string(i) + "].x = " + std::to_string(rng[i].x) + " is no state of the engine (1 .. 2147483646)");
-    return RT_OK;
-}
-
 
 // ---- rt_render_paths / rt_render_bake: the caller's paths through the persistent kernel (device/rt_path_source.h) ----------------------------
 // Slots per chunk: the pixel slots of a 1080p frame, so the persistent kernel's path records (256 bytes per slot at depth 6) never grow
@@ -274,28 +392,23 @@ int source_run(rt_scene *scene, const SourceCall &c, size_t items, const std::st
     hipStream_t stream = nullptr;
     const size_t chunk_items = source_chunk() / c.K; // whole points: the stream sum never crosses a seam (the chunk's minimum of 64 covers K <= 64)
     const size_t cap_items = std::min(items, chunk_items), cap = (cap_items * c.K + 63u) & ~(size_t)63u;
-    size_t at = 0;
-    auto take = [&](size_t bytes) { const size_t here = at; at += (bytes + 255u) & ~(size_t)255u; return here; };
-    const size_t o_state = take(cap * 24u), o_in = take(c.on_device ? 0 : cap_items * 24u), o_rng = take(c.on_device ? 0 : cap * sizeof(rt_rng)),
-                 o_out = take(c.on_device ? 0 : cap_items * 12u);
-    grow(scene->source_stage, scene->source_stage_bytes, at);
-    uint8_t *b = scene->source_stage;
-    for (size_t first = 0; first < items; first += chunk_items) {
-        const size_t m_items = std::min(chunk_items, items - first), m = m_items * c.K;
-        const uint8_t *in = (const uint8_t *)c.in + first * 24u;
-        rt_rng *rng = c.rng + first * c.K;
-        float *out = c.out + first * 3u;
-        if (!c.on_device) {
-            HIP_CHECK(hipMemcpyAsync(b + o_in, in, m_items * 24u, hipMemcpyHostToDevice, stream));
-            HIP_CHECK(hipMemcpyAsync(b + o_rng, rng, m * sizeof(rt_rng), hipMemcpyHostToDevice, stream));
-        }
+    struct { uint32_t *state; uint8_t *in, *rng; float *out; } S{}; // the kernel's state; host arrays: the records, the engines, the answer
+    auto carve = [&](uint8_t *base) {
+        Carver take{base};
+        take(S.state, cap * 24u);
+        if (!c.on_device) { take(S.in, cap_items * 24u); take(S.rng, cap * sizeof(rt_rng)); take(S.out, cap_items * 12u); }
+        return take.at;
+    };
+    grow(scene->source_stage, scene->source_stage_bytes, carve(nullptr));
+    carve(scene->source_stage);
+    struct { Arr in, rng, out; } A{arr_in(c.in, 24u, S.in), arr_inout(c.rng, c.K * sizeof(rt_rng), S.rng), arr_out(c.out, 12u, S.out)};
+    return chunks(items, chunk_items, c.on_device, A, stream, nullptr, [&](size_t, size_t m_items) -> int {
         SourceView V{};
-        V.state = (uint32_t *)(b + o_state); V.n_pixslots = (uint32_t)((m + 63u) & ~(size_t)63u); V.n = (uint32_t)m; V.mode = c.mode;
-        V.rng = (uint4 *)(c.on_device ? (uint8_t *)rng : b + o_rng);
-        const float *records = (const float *)(c.on_device ? in : b + o_in);
-        if (c.mode == 1u) V.rays = records; else V.points = records;
+        V.state = S.state; V.n = (uint32_t)(m_items * c.K); V.n_pixslots = (V.n + 63u) & ~63u; V.mode = c.mode;
+        V.rng = A.rng.as<uint4>();
+        if (c.mode == 1u) V.rays = A.in.as<float>(); else V.points = A.in.as<float>();
         V.streams = (uint32_t)c.K; V.scale = c.scale;
-        V.out = c.on_device ? out : (float *)(b + o_out);
+        V.out = A.out.as<float>();
         T.launches += query_launch_source_pack(scene, V, stream);
         SourceChunk C{};
         C.mode = c.mode; C.n = V.n; C.streams = V.streams; C.rays = V.rays; C.points = V.points;
@@ -303,14 +416,9 @@ int source_run(rt_scene *scene, const SourceCall &c, size_t items, const std::st
         SourceResult res{};
         if (const int rc = source_render(scene, C, stream, res, who)) return rc;
         T.launches += res.launches + query_launch_source_unpack(scene, V, stream);
-        if (!c.on_device) {
-            HIP_CHECK(hipMemcpyAsync(out, b + o_out, m_items * 12u, hipMemcpyDeviceToHost, stream));
-            HIP_CHECK(hipMemcpyAsync(rng, b + o_rng, m * sizeof(rt_rng), hipMemcpyDeviceToHost, stream));
-        }
-        HIP_CHECK(hipStreamSynchronize(stream)); // the next chunk reuses the state and the staging
         T.kernel_ms += res.kernel_ms; T.exact_walks += res.exact_walks; T.no_path += res.no_path; T.reference_exact = res.reference_exact;
-    }
-    return RT_OK;
+        return RT_OK;
+    });
 }
 
 } // namespace
@@ -327,129 +435,98 @@ int rt_query_light_pdf(rt_scene *scene, const rt_ray *rays, size_t n, uint32_t f
 
 int rt_query_occluded(rt_scene *scene, const rt_ray *rays, const float *tmax, size_t n, uint32_t flags, uint8_t *out, rt_query_stats *stats) {
     const std::string who = "rt_query_occluded: ";
-    // what can be judged without the scene first, each refusal naming its argument; check_call repeats the first two and adds the scene's
-    const uint32_t allowed = RT_QUERY_DEVICE_POINTERS | RT_QUERY_REFERENCE_WALK;
-    if (stats && stats->struct_size != sizeof(rt_query_stats)) return fail(RT_ERR_INVALID_ARG, who + "struct_size mismatch (ABI skew)");
-    if (flags & ~allowed) return fail(RT_ERR_INVALID_ARG, who + "flags other than RT_QUERY_DEVICE_POINTERS | RT_QUERY_REFERENCE_WALK");
-    if (n && !rays) return fail(RT_ERR_INVALID_ARG, who + "null argument (rays)");
-    if (n && !out) return fail(RT_ERR_INVALID_ARG, who + "null argument (out)");
-    if (!scene) return fail(RT_ERR_INVALID_ARG, who + "null argument (scene)");
-    if (const int rc = check_call(scene, stats, flags, allowed, "RT_QUERY_DEVICE_POINTERS | RT_QUERY_REFERENCE_WALK", who)) return rc;
-    const bool on_device = (flags & RT_QUERY_DEVICE_POINTERS) != 0;
-    if (n && on_device && ((uintptr_t)tmax & 3u)) return fail(RT_ERR_INVALID_ARG, who + "with RT_QUERY_DEVICE_POINTERS the tmax array must be 4-byte aligned");
-    return answer(scene, n, stats, who, STAGE_OCCLUSION,
-        [&](const QueryStage &S, size_t first, size_t m, hipStream_t stream) {
-            if (on_device) return;
-            HIP_CHECK(hipMemcpyAsync(S.rays, rays + first, m * sizeof(rt_ray), hipMemcpyHostToDevice, stream));
-            if (tmax) HIP_CHECK(hipMemcpyAsync(S.tmax, tmax + first, m * sizeof(float), hipMemcpyHostToDevice, stream));
-        },
-        [&](const QueryStage &S, size_t first, size_t m, hipStream_t stream) {
-            QueryView Q = walk_view(scene, S, m, flags, on_device ? (const float *)(rays + first) : S.rays);
-            Q.tmax = !tmax ? nullptr : on_device ? tmax + first : S.tmax;
-            Q.occ = on_device ? out + first : S.occ;
-            return query_launch_occluded(scene, Q, stream);
-        },
-        [&](const QueryStage &S, size_t first, size_t m, hipStream_t stream) {
-            if (!on_device) HIP_CHECK(hipMemcpyAsync(out + first, S.occ, m, hipMemcpyDeviceToHost, stream));
+    // what can be judged without the scene first, each refusal naming its argument
+    if (const int rc = check_struct_size(stats, who)) return rc;
+    if (const int rc = check_flags(flags, WALK_FLAGS, who)) return rc;
+    if (n && !rays) return null_arg(who, "rays");
+    if (n && !out) return null_arg(who, "out");
+    if (const int rc = check_scene(scene, who, "scene")) return rc;
+    const bool on_device = device_pointers(flags);
+    if (const int rc = check_aligned(n && on_device, {tmax}, 4, "the tmax array", who)) return rc;
+    struct A { Arr rays, tmax, out; };
+    return answer(scene, n, 1, stats, who, {STAGE_OCCLUSION}, on_device,
+        [&](const QueryStage &S) { return A{arr_in(rays, sizeof(rt_ray), S.rays), arr_in(tmax, sizeof(float), S.tmax), arr_out(out, 1, S.occ)}; }, no_prepare,
+        [&](const Chunk &c, const A &a, rt_query_stats &) {
+            QueryView Q = walk_view(scene, c.S, c.m, flags, a.rays.as<float>());
+            Q.tmax = a.tmax.as<float>(); Q.occ = a.out.at;
+            return query_launch_occluded(scene, Q, c.stream);
         });
 }
 
 int rt_query_surface(rt_scene *scene, const rt_hit *hits, size_t n, uint32_t flags, rt_surface *out, rt_query_stats *stats) {
     const std::string who = "rt_query_surface: ";
-    if (const int rc = check_call(scene, stats, flags, RT_QUERY_DEVICE_POINTERS, "RT_QUERY_DEVICE_POINTERS", who)) return rc;
-    if (n && (!hits || !out)) return fail(RT_ERR_INVALID_ARG, who + "null argument");
-    const bool on_device = (flags & RT_QUERY_DEVICE_POINTERS) != 0;
-    if (n && on_device && (((uintptr_t)hits | (uintptr_t)out) & 15u))
-        return fail(RT_ERR_INVALID_ARG, who + "with RT_QUERY_DEVICE_POINTERS the rt_hit and rt_surface arrays must be 16-byte aligned");
-    return answer(scene, n, stats, who, STAGE_FIRST_HIT,
-        [&](const QueryStage &S, size_t first, size_t m, hipStream_t stream) {
-            ensure_materials(scene, stream);
-            if (!on_device) HIP_CHECK(hipMemcpyAsync(S.out, hits + first, m * sizeof(rt_hit), hipMemcpyHostToDevice, stream));
-        },
-        [&](const QueryStage &S, size_t first, size_t m, hipStream_t stream) {
-            return query_launch_surface(scene, on_device ? surface_view(scene, S, m, hits + first, out + first) : surface_view(scene, S, m, S.out, S.surf), stream);
-        },
-        [&](const QueryStage &S, size_t first, size_t m, hipStream_t stream) {
-            if (!on_device) HIP_CHECK(hipMemcpyAsync(out + first, S.surf, m * sizeof(rt_surface), hipMemcpyDeviceToHost, stream));
-        });
+    if (const int rc = check_walk_call(scene, stats, flags, RT_QUERY_DEVICE_POINTERS, who)) return rc;
+    if (n && (!hits || !out)) return null_arg(who);
+    const bool on_device = device_pointers(flags);
+    if (const int rc = check_aligned(n && on_device, {hits, out}, 16, "the rt_hit and rt_surface arrays", who)) return rc;
+    struct A { Arr hits, out; };
+    return answer(scene, n, 1, stats, who, {STAGE_FIRST_HIT}, on_device,
+        [&](const QueryStage &S) { return A{arr_in(hits, sizeof(rt_hit), S.out), arr_out(out, sizeof(rt_surface), S.surf)}; },
+        [&](const Chunk &c, const A &) { ensure_materials(scene, c.stream); },
+        [&](const Chunk &c, const A &a, rt_query_stats &) { return query_launch_surface(scene, surface_view(scene, c.S, c.m, a.hits.at, a.out.at), c.stream); });
 }
 
 int rt_query_environment(rt_scene *scene, const rt_ray *rays, size_t n, uint32_t flags, float *out_rgb, rt_query_stats *stats) {
     const std::string who = "rt_query_environment: ";
-    if (const int rc = check_call(scene, stats, flags, RT_QUERY_DEVICE_POINTERS, "RT_QUERY_DEVICE_POINTERS", who)) return rc;
-    if (n && (!rays || !out_rgb)) return fail(RT_ERR_INVALID_ARG, who + "null argument");
-    const bool on_device = (flags & RT_QUERY_DEVICE_POINTERS) != 0;
-    return answer(scene, n, stats, who, STAGE_WALK, // the colours of a chunk are staged where a closest-hit query keeps its 16-byte records
-        [&](const QueryStage &S, size_t first, size_t m, hipStream_t stream) {
-            if (!on_device) HIP_CHECK(hipMemcpyAsync(S.rays, rays + first, m * sizeof(rt_ray), hipMemcpyHostToDevice, stream));
-        },
-        [&](const QueryStage &S, size_t first, size_t m, hipStream_t stream) {
+    if (const int rc = check_walk_call(scene, stats, flags, RT_QUERY_DEVICE_POINTERS, who)) return rc;
+    if (n && (!rays || !out_rgb)) return null_arg(who);
+    struct A { Arr rays, rgb; };
+    return answer(scene, n, 1, stats, who, {STAGE_WALK}, device_pointers(flags), // the colours of a chunk are staged where a closest-hit query keeps its 16-byte records
+        [&](const QueryStage &S) { return A{arr_in(rays, sizeof(rt_ray), S.rays), arr_out(out_rgb, 3 * sizeof(float), S.rec)}; }, no_prepare,
+        [&](const Chunk &c, const A &a, rt_query_stats &) {
             EnvironmentView V{};
-            V.rays = on_device ? (const float *)(rays + first) : S.rays;
-            V.rgb = on_device ? out_rgb + 3 * first : (float *)S.rec;
-            V.n = (uint32_t)m; V.totals = S.totals;
-            return query_launch_environment(scene, V, stream);
-        },
-        [&](const QueryStage &S, size_t first, size_t m, hipStream_t stream) {
-            if (!on_device) HIP_CHECK(hipMemcpyAsync(out_rgb + 3 * first, S.rec, m * 3 * sizeof(float), hipMemcpyDeviceToHost, stream));
+            V.rays = a.rays.as<float>(); V.rgb = a.rgb.as<float>();
+            V.n = (uint32_t)c.m; V.totals = c.S.totals;
+            return query_launch_environment(scene, V, c.stream);
         });
 }
 
 int rt_camera_rays(rt_scene *scene, int32_t width, int32_t height, const float *xy, size_t n, uint32_t flags, rt_ray *out) {
     const std::string who = "rt_camera_rays: ";
-    if (const int rc = check_call(scene, nullptr, flags, RT_QUERY_DEVICE_POINTERS, "RT_QUERY_DEVICE_POINTERS", who)) return rc;
+    if (const int rc = check_walk_call(scene, nullptr, flags, RT_QUERY_DEVICE_POINTERS, who)) return rc;
     if (width < 1 || height < 1) return fail(RT_ERR_INVALID_ARG, who + "width and height must be positive");
-    if (n && (!xy || !out)) return fail(RT_ERR_INVALID_ARG, who + "null argument");
-    const bool on_device = (flags & RT_QUERY_DEVICE_POINTERS) != 0;
+    if (n && (!xy || !out)) return null_arg(who);
+    const bool on_device = device_pointers(flags);
     if (!on_device)
         for (size_t i = 0; i < 2 * n; i++)
             if (!std::isfinite(xy[i])) return fail(RT_ERR_INVALID_ARG, who + "xy holds a NaN or an infinity (point " + std::to_string(i / 2) + ")");
-    return answer(scene, n, nullptr, who, STAGE_WALK, // the points of a chunk are staged where a closest-hit query keeps its 16-byte records
-        [&](const QueryStage &S, size_t first, size_t m, hipStream_t stream) {
-            if (!on_device) HIP_CHECK(hipMemcpyAsync(S.rec, xy + 2 * first, m * 2 * sizeof(float), hipMemcpyHostToDevice, stream));
-        },
-        [&](const QueryStage &S, size_t first, size_t m, hipStream_t stream) {
+    struct A { Arr xy, rays; };
+    return answer(scene, n, 1, (rt_query_stats *)nullptr, who, {STAGE_WALK}, on_device, // the points of a chunk are staged where a closest-hit query keeps its 16-byte records
+        [&](const QueryStage &S) { return A{arr_in(xy, 2 * sizeof(float), S.rec), arr_out(out, sizeof(rt_ray), S.rays)}; }, no_prepare,
+        [&](const Chunk &c, const A &a, rt_query_stats &) {
             CameraView V{};
-            V.xy = on_device ? xy + 2 * first : (const float *)S.rec;
-            V.rays = on_device ? (float *)(out + first) : S.rays;
-            V.n = (uint32_t)m; V.width = width; V.height = height;
-            return query_launch_camera_rays(scene, V, stream);
-        },
-        [&](const QueryStage &S, size_t first, size_t m, hipStream_t stream) {
-            if (!on_device) HIP_CHECK(hipMemcpyAsync(out + first, S.rays, m * sizeof(rt_ray), hipMemcpyDeviceToHost, stream));
+            V.xy = a.xy.as<float>(); V.rays = a.rays.as<float>();
+            V.n = (uint32_t)c.m; V.width = width; V.height = height;
+            return query_launch_camera_rays(scene, V, c.stream);
         });
 }
 
 int rt_render_guides(rt_scene *scene, int32_t width, int32_t height, uint32_t flags, float *albedo, float *normal, float *depth, float *emission,
                      rt_query_stats *stats) {
     const std::string who = "rt_render_guides: ";
-    if (const int rc = check_call(scene, stats, flags, RT_QUERY_DEVICE_POINTERS, "RT_QUERY_DEVICE_POINTERS", who)) return rc;
+    if (const int rc = check_walk_call(scene, stats, flags, RT_QUERY_DEVICE_POINTERS, who)) return rc;
     if (width < 1 || height < 1) return fail(RT_ERR_INVALID_ARG, who + "width and height must be positive");
     if ((int64_t)width * height >= 2147483647LL) return fail(RT_ERR_INVALID_ARG, who + "image too large (width * height must stay below 2^31-1)");
-    const bool on_device = (flags & RT_QUERY_DEVICE_POINTERS) != 0;
-    // the planes of a chunk in the staging, in this order: {plane, floats per pixel, offset in floats per pixel of the chunk}
-    struct Plane { float *p; size_t k, at; } planes[4] = {{albedo, 3, 0}, {normal, 3, 3}, {depth, 1, 6}, {emission, 3, 7}};
-    return answer(scene, (size_t)width * height, stats, who, STAGE_FIRST_HIT,
-        [&](const QueryStage &, size_t, size_t, hipStream_t stream) { ensure_materials(scene, stream); },
-        [&](const QueryStage &S, size_t first, size_t m, hipStream_t stream) {
-            CameraView C{};
-            C.rays = S.rays; C.n = (uint32_t)m; C.first_pixel = (uint32_t)first; C.width = width; C.height = height;
-            uint32_t launches = query_launch_camera_rays(scene, C, stream);
-            QueryView Q = walk_view(scene, S, m, 0u, S.rays);
-            Q.hits = (uint4 *)S.out;
-            launches += query_launch_closest(scene, Q, stream);
-            launches += query_launch_surface(scene, surface_view(scene, S, m, S.out, S.surf), stream);
-            GuidesView G{};
-            G.hits = (const uint4 *)S.out; G.surfaces = (const uint4 *)S.surf; G.rays = S.rays; G.n = (uint32_t)m;
-            float **to[4] = {&G.albedo, &G.normal, &G.depth, &G.emission};
-            for (int k = 0; k < 4; k++)
-                if (planes[k].p) *to[k] = on_device ? planes[k].p + planes[k].k * first : S.planes + planes[k].at * QUERY_CHUNK;
-            return launches + query_launch_guides(scene, G, stream);
+    struct A { Arr albedo, normal, depth, emission; };
+    return answer(scene, (size_t)width * height, 1, stats, who, {STAGE_FIRST_HIT}, device_pointers(flags),
+        [&](const QueryStage &S) { // the planes of a chunk in the staging: 3 + 3 + 1 + 3 floats per pixel of a whole chunk, in this order
+            float *const p = S.planes;
+            return A{arr_out(albedo, 12, p), arr_out(normal, 12, p + 3 * QUERY_CHUNK), arr_out(depth, 4, p + 6 * QUERY_CHUNK), arr_out(emission, 12, p + 7 * QUERY_CHUNK)};
         },
-        [&](const QueryStage &S, size_t first, size_t m, hipStream_t stream) {
-            if (on_device) return;
-            for (const Plane &pl : planes)
-                if (pl.p) HIP_CHECK(hipMemcpyAsync(pl.p + pl.k * first, S.planes + pl.at * QUERY_CHUNK, m * pl.k * sizeof(float), hipMemcpyDeviceToHost, stream));
+        [&](const Chunk &c, const A &) { ensure_materials(scene, c.stream); },
+        [&](const Chunk &c, const A &a, rt_query_stats &) {
+            const QueryStage &S = c.S;
+            CameraView C{};
+            C.rays = S.rays; C.n = (uint32_t)c.m; C.first_pixel = (uint32_t)c.first; C.width = width; C.height = height;
+            uint32_t launches = query_launch_camera_rays(scene, C, c.stream);
+            QueryView Q = walk_view(scene, S, c.m, 0u, S.rays);
+            Q.hits = (uint4 *)S.out;
+            launches += query_launch_closest(scene, Q, c.stream);
+            launches += query_launch_surface(scene, surface_view(scene, S, c.m, S.out, S.surf), c.stream);
+            GuidesView G{};
+            G.hits = (const uint4 *)S.out; G.surfaces = (const uint4 *)S.surf; G.rays = S.rays; G.n = (uint32_t)c.m;
+            G.albedo = a.albedo.as<float>(); G.normal = a.normal.as<float>(); G.depth = a.depth.as<float>(); G.emission = a.emission.as<float>(); // null: not wanted
+            return launches + query_launch_guides(scene, G, c.stream);
         });
 }
 
@@ -466,360 +543,211 @@ float rt_rng_uniform(rt_rng *r) { // rng_next and rng_u01 of device/rt_device.h,
     return v >= 1.0f ? 0.99999994f : v;
 }
 
+// rt_query_scatter, rt_query_bsdf and rt_trace_paths judge everything that needs no scene first.
 int rt_query_scatter(rt_scene *scene, const rt_ray *rays, const rt_hit *hits, const rt_surface *surfaces, rt_rng *rng, size_t n, uint32_t flags,
                      rt_scatter *out, rt_query_stats *stats) {
     const std::string who = "rt_query_scatter: ";
-    if (n && (!rays || !hits || !surfaces || !rng || !out)) return fail(RT_ERR_INVALID_ARG, who + "null argument");
-    if (const int rc = check_scatter_call(stats, flags, rng, n, who)) return rc;
-    if (const int rc = check_call(scene, stats, flags, SCATTER_FLAGS, SCATTER_FLAG_NAMES, who)) return rc;
-    const bool on_device = (flags & RT_QUERY_DEVICE_POINTERS) != 0;
-    if (n && on_device && (((uintptr_t)hits | (uintptr_t)surfaces | (uintptr_t)rng | (uintptr_t)out) & 15u))
-        return fail(RT_ERR_INVALID_ARG, who + "with RT_QUERY_DEVICE_POINTERS the rt_hit, rt_surface, rt_rng and rt_scatter arrays must be 16-byte aligned");
-    return answer(scene, n, stats, who, STAGE_SCATTER,
-        [&](const QueryStage &S, size_t first, size_t m, hipStream_t stream) {
-            if (on_device) return;
-            HIP_CHECK(hipMemcpyAsync(S.rays, rays + first, m * sizeof(rt_ray), hipMemcpyHostToDevice, stream));
-            HIP_CHECK(hipMemcpyAsync(S.out, hits + first, m * sizeof(rt_hit), hipMemcpyHostToDevice, stream));
-            HIP_CHECK(hipMemcpyAsync(S.surf, surfaces + first, m * sizeof(rt_surface), hipMemcpyHostToDevice, stream));
-            HIP_CHECK(hipMemcpyAsync(S.rng, rng + first, m * sizeof(rt_rng), hipMemcpyHostToDevice, stream));
-        },
-        [&](const QueryStage &S, size_t first, size_t m, hipStream_t stream) {
-            const ScatterArrays A = on_device ? ScatterArrays{rays + first, hits + first, surfaces + first, rng + first, out + first}
-                                              : ScatterArrays{(const rt_ray *)S.rays, (const rt_hit *)S.out, (const rt_surface *)S.surf, (rt_rng *)S.rng, (rt_scatter *)S.scat};
-            const ScatterView V = scatter_view(S, m, A);
-            uint32_t launches = query_launch_scatter_sample(scene, V, stream);
-            launches += launch_ride_light_pdf(scene, S, m, flags, false, stream);
-            return launches + query_launch_scatter_finish(scene, V, stream);
-        },
-        [&](const QueryStage &S, size_t first, size_t m, hipStream_t stream) {
-            if (on_device) return;
-            HIP_CHECK(hipMemcpyAsync(out + first, S.scat, m * sizeof(rt_scatter), hipMemcpyDeviceToHost, stream));
-            HIP_CHECK(hipMemcpyAsync(rng + first, S.rng, m * sizeof(rt_rng), hipMemcpyDeviceToHost, stream));
+    const bool on_device = device_pointers(flags);
+    if (n && (!rays || !hits || !surfaces || !rng || !out)) return null_arg(who);
+    if (const int rc = check_struct_size(stats, who)) return rc;
+    if (const int rc = check_flags(flags, WALK_FLAGS, who)) return rc;
+    if (const int rc = check_engines(rng, n, on_device, who)) return rc;
+    if (const int rc = check_scene(scene, who)) return rc;
+    if (const int rc = check_aligned(n && on_device, {hits, surfaces, rng, out}, 16, "the rt_hit, rt_surface, rt_rng and rt_scatter arrays", who)) return rc;
+    struct A { Arr rays, hits, surfaces, rng, out; };
+    return answer(scene, n, 1, stats, who, {STAGE_SCATTER}, on_device,
+        [&](const QueryStage &S) {
+            return A{arr_in(rays, sizeof(rt_ray), S.rays), arr_in(hits, sizeof(rt_hit), S.out), arr_in(surfaces, sizeof(rt_surface), S.surf),
+                     arr_inout(rng, sizeof(rt_rng), S.rng), arr_out(out, sizeof(rt_scatter), S.scat)};
+        }, no_prepare,
+        [&](const Chunk &c, const A &a, rt_query_stats &) {
+            const ScatterView V = scatter_view(c.S, c.m, a.rays.at, a.hits.at, a.surfaces.at, a.rng.at, a.out.at);
+            uint32_t launches = query_launch_scatter_sample(scene, V, c.stream);
+            launches += launch_ride_light_pdf(scene, c.S, c.m, flags, false, c.stream);
+            return launches + query_launch_scatter_finish(scene, V, c.stream);
         });
 }
 
 int rt_query_bsdf(rt_scene *scene, const rt_ray *rays, const rt_hit *hits, const rt_surface *surfaces, const float *dirs, size_t n, uint32_t flags,
                   float *out_brdf, float *out_pdf, rt_query_stats *stats) {
     const std::string who = "rt_query_bsdf: ";
-    if (n && (!rays || !hits || !surfaces || !dirs || !out_brdf || !out_pdf)) return fail(RT_ERR_INVALID_ARG, who + "null argument");
-    if (const int rc = check_scatter_call(stats, flags, nullptr, n, who)) return rc;
-    if (const int rc = check_call(scene, stats, flags, SCATTER_FLAGS, SCATTER_FLAG_NAMES, who)) return rc;
-    const bool on_device = (flags & RT_QUERY_DEVICE_POINTERS) != 0;
-    if (n && on_device && (((uintptr_t)hits | (uintptr_t)surfaces) & 15u))
-        return fail(RT_ERR_INVALID_ARG, who + "with RT_QUERY_DEVICE_POINTERS the rt_hit and rt_surface arrays must be 16-byte aligned");
-    if (n && on_device && (((uintptr_t)dirs | (uintptr_t)out_brdf | (uintptr_t)out_pdf) & 3u))
-        return fail(RT_ERR_INVALID_ARG, who + "with RT_QUERY_DEVICE_POINTERS dirs, out_brdf and out_pdf must be 4-byte aligned");
-    // host arrays: the directions and the two answers of a chunk are staged where a scatter keeps its records (3 + 3 + 1 floats per record)
-    auto stage_dirs = [](const QueryStage &S) { return (float *)S.scat; };
-    auto stage_brdf = [](const QueryStage &S) { return (float *)S.scat + 3 * QUERY_CHUNK; };
-    auto stage_pdf = [](const QueryStage &S) { return (float *)S.scat + 6 * QUERY_CHUNK; };
-    return answer(scene, n, stats, who, STAGE_SCATTER,
-        [&](const QueryStage &S, size_t first, size_t m, hipStream_t stream) {
-            if (on_device) return;
-            HIP_CHECK(hipMemcpyAsync(S.rays, rays + first, m * sizeof(rt_ray), hipMemcpyHostToDevice, stream));
-            HIP_CHECK(hipMemcpyAsync(S.out, hits + first, m * sizeof(rt_hit), hipMemcpyHostToDevice, stream));
-            HIP_CHECK(hipMemcpyAsync(S.surf, surfaces + first, m * sizeof(rt_surface), hipMemcpyHostToDevice, stream));
-            HIP_CHECK(hipMemcpyAsync(stage_dirs(S), dirs + 3 * first, m * 3 * sizeof(float), hipMemcpyHostToDevice, stream));
-        },
-        [&](const QueryStage &S, size_t first, size_t m, hipStream_t stream) {
-            const ScatterArrays A = on_device ? ScatterArrays{rays + first, hits + first, surfaces + first, nullptr, nullptr}
-                                              : ScatterArrays{(const rt_ray *)S.rays, (const rt_hit *)S.out, (const rt_surface *)S.surf, nullptr, nullptr};
-            ScatterView V = scatter_view(S, m, A);
-            V.dirs = on_device ? dirs + 3 * first : stage_dirs(S);
-            V.out_brdf = on_device ? out_brdf + 3 * first : stage_brdf(S);
-            V.out_pdf = on_device ? out_pdf + first : stage_pdf(S);
-            uint32_t launches = query_launch_bsdf_rays(scene, V, stream);
-            launches += launch_ride_light_pdf(scene, S, m, flags, false, stream);
-            return launches + query_launch_bsdf_finish(scene, V, stream);
-        },
-        [&](const QueryStage &S, size_t first, size_t m, hipStream_t stream) {
-            if (on_device) return;
-            HIP_CHECK(hipMemcpyAsync(out_brdf + 3 * first, stage_brdf(S), m * 3 * sizeof(float), hipMemcpyDeviceToHost, stream));
-            HIP_CHECK(hipMemcpyAsync(out_pdf + first, stage_pdf(S), m * sizeof(float), hipMemcpyDeviceToHost, stream));
+    const bool on_device = device_pointers(flags);
+    if (n && (!rays || !hits || !surfaces || !dirs || !out_brdf || !out_pdf)) return null_arg(who);
+    if (const int rc = check_struct_size(stats, who)) return rc;
+    if (const int rc = check_flags(flags, WALK_FLAGS, who)) return rc;
+    if (const int rc = check_scene(scene, who)) return rc;
+    if (const int rc = check_aligned(n && on_device, {hits, surfaces}, 16, "the rt_hit and rt_surface arrays", who)) return rc;
+    if (const int rc = check_aligned(n && on_device, {dirs, out_brdf, out_pdf}, 4, "dirs, out_brdf and out_pdf", who)) return rc;
+    struct A { Arr rays, hits, surfaces, dirs, brdf, pdf; };
+    return answer(scene, n, 1, stats, who, {STAGE_SCATTER}, on_device,
+        [&](const QueryStage &S) { // host arrays: the directions and the two answers of a chunk are staged where a scatter keeps its records (3 + 3 + 1 floats per record)
+            float *const f = (float *)S.scat;
+            return A{arr_in(rays, sizeof(rt_ray), S.rays), arr_in(hits, sizeof(rt_hit), S.out), arr_in(surfaces, sizeof(rt_surface), S.surf),
+                     arr_in(dirs, 12, f), arr_out(out_brdf, 12, f + 3 * QUERY_CHUNK), arr_out(out_pdf, 4, f + 6 * QUERY_CHUNK)};
+        }, no_prepare,
+        [&](const Chunk &c, const A &a, rt_query_stats &) {
+            ScatterView V = scatter_view(c.S, c.m, a.rays.at, a.hits.at, a.surfaces.at, nullptr, nullptr);
+            V.dirs = a.dirs.as<float>(); V.out_brdf = a.brdf.as<float>(); V.out_pdf = a.pdf.as<float>();
+            uint32_t launches = query_launch_bsdf_rays(scene, V, c.stream);
+            launches += launch_ride_light_pdf(scene, c.S, c.m, flags, false, c.stream);
+            return launches + query_launch_bsdf_finish(scene, V, c.stream);
         });
 }
 
 int rt_trace_paths(rt_scene *scene, const rt_ray *rays, rt_rng *rng, size_t n, int32_t ray_depth, uint32_t flags, float *out_rgb, rt_query_stats *stats) {
     const std::string who = "rt_trace_paths: ";
-    if (n && (!rays || !rng || !out_rgb)) return fail(RT_ERR_INVALID_ARG, who + "null argument");
-    if (const int rc = check_scatter_call(stats, flags, rng, n, who)) return rc;
-    if (const int rc = check_call(scene, stats, flags, SCATTER_FLAGS, SCATTER_FLAG_NAMES, who)) return rc;
-    const int depth = ray_depth > 0 ? ray_depth : 6;
-    if (depth > RT_MAX_DEPTH) return fail(RT_ERR_LIMIT, who + "ray_depth above " + std::to_string(RT_MAX_DEPTH));
-    const bool on_device = (flags & RT_QUERY_DEVICE_POINTERS) != 0;
-    if (n && on_device && ((uintptr_t)rng & 15u)) return fail(RT_ERR_INVALID_ARG, who + "with RT_QUERY_DEVICE_POINTERS the rt_rng array must be 16-byte aligned");
-    if (n && on_device && (((uintptr_t)rays | (uintptr_t)out_rgb) & 3u)) return fail(RT_ERR_INVALID_ARG, who + "with RT_QUERY_DEVICE_POINTERS rays and out_rgb must be 4-byte aligned");
+    const bool on_device = device_pointers(flags);
+    int depth = 0;
+    if (n && (!rays || !rng || !out_rgb)) return null_arg(who);
+    if (const int rc = check_struct_size(stats, who)) return rc;
+    if (const int rc = check_flags(flags, WALK_FLAGS, who)) return rc;
+    if (const int rc = check_engines(rng, n, on_device, who)) return rc;
+    if (const int rc = check_scene(scene, who)) return rc;
+    if (const int rc = check_depth(ray_depth, who, "", depth)) return rc;
+    if (const int rc = check_engine_arrays(n && on_device, rng, rays, out_rgb, "rays and out_rgb", who)) return rc;
     const size_t paths = std::min(n, query_chunk());
-    uint8_t *stack = nullptr;
-    return answer(scene, n, stats, who, STAGE_SCATTER,
-        [&](const QueryStage &S, size_t first, size_t m, hipStream_t stream) {
-            ensure_materials(scene, stream);
-            stack = path_stack(scene, paths, depth);
-            HIP_CHECK(hipMemsetAsync(stack, 0, paths * 16u, stream)); // tail 0, no bounce kept, not ended
+    struct A { Arr rays, rng, rgb; };
+    return answer(scene, n, 1, stats, who, {STAGE_SCATTER}, on_device, // the colours of a chunk are staged where a closest-hit query keeps its records
+        [&](const QueryStage &S) { return A{arr_in(rays, sizeof(rt_ray), S.rays), arr_inout(rng, sizeof(rt_rng), S.rng), arr_out(out_rgb, 12, S.rec)}; },
+        [&](const Chunk &c, const A &a) {
+            prepare_paths(scene, paths, depth, c.stream);
             // the rays change from bounce to bounce: always a copy in the staging
-            HIP_CHECK(hipMemcpyAsync(S.rays, rays + first, m * sizeof(rt_ray), on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, stream));
-            if (!on_device) HIP_CHECK(hipMemcpyAsync(S.rng, rng + first, m * sizeof(rt_rng), hipMemcpyHostToDevice, stream));
+            if (on_device) HIP_CHECK(hipMemcpyAsync(c.S.rays, a.rays.at, c.m * sizeof(rt_ray), hipMemcpyDeviceToDevice, c.stream));
         },
-        [&](const QueryStage &S, size_t first, size_t m, hipStream_t stream) {
-            const ScatterView V = scatter_view(S, m, ScatterArrays{(const rt_ray *)S.rays, (const rt_hit *)S.out, (const rt_surface *)S.surf,
-                                                                   on_device ? rng + first : (rt_rng *)S.rng, (rt_scatter *)S.scat});
-            PathView P{};
-            P.rays = S.rays; P.hits = V.hits; P.surfaces = V.surfaces; P.scatter = V.out;
-            P.state = (float4 *)stack; P.stack = (float *)(stack + paths * 16u);
-            P.rgb = on_device ? out_rgb + 3 * first : (float *)S.rec; // the colours of a chunk are staged where a closest-hit query keeps its records
-            P.n = (uint32_t)m;
+        [&](const Chunk &c, const A &a, rt_query_stats &) {
+            Paths p = paths_view(scene, c, a.rng.at, paths);
+            p.P.rgb = a.rgb.as<float>();
             uint32_t launches = 0;
             for (int b = 0; b < depth; b++) {
-                launches += launch_round(scene, S, V, m, flags, b != 0, stream);
-                P.last = b == depth - 1 ? 1u : 0u;
-                launches += query_launch_path_advance(scene, P, stream);
+                launches += launch_round(scene, c.S, p.V, c.m, flags, b != 0, c.stream);
+                p.P.last = b == depth - 1 ? 1u : 0u;
+                launches += query_launch_path_advance(scene, p.P, c.stream);
             }
             return launches;
-        },
-        [&](const QueryStage &S, size_t first, size_t m, hipStream_t stream) {
-            if (on_device) return;
-            HIP_CHECK(hipMemcpyAsync(out_rgb + 3 * first, S.rec, m * 3 * sizeof(float), hipMemcpyDeviceToHost, stream));
-            HIP_CHECK(hipMemcpyAsync(rng + first, S.rng, m * sizeof(rt_rng), hipMemcpyDeviceToHost, stream));
         });
 }
 
+// The bake calls judge everything that needs no scene first, too.
 int rt_bake_rays(rt_scene *scene, const rt_bake_point *points, rt_rng *rng, size_t n, int32_t mode, uint32_t flags, rt_ray *out, rt_query_stats *stats) {
     const std::string who = "rt_bake_rays: ";
-    if (stats && stats->struct_size != sizeof(rt_query_stats)) return fail(RT_ERR_INVALID_ARG, who + "struct_size mismatch (ABI skew)");
+    const bool on_device = device_pointers(flags);
+    if (const int rc = check_struct_size(stats, who)) return rc;
     if (const int rc = check_bake_mode(mode, who, "mode")) return rc;
-    if (flags & ~BAKE_RAYS_FLAGS) return fail(RT_ERR_INVALID_ARG, who + "flags other than RT_QUERY_DEVICE_POINTERS");
-    if (n && (!points || !rng || !out)) return fail(RT_ERR_INVALID_ARG, who + "null argument");
-    const bool on_device = (flags & RT_QUERY_DEVICE_POINTERS) != 0;
-    if (!on_device)
-        if (const int rc = check_bake_engines(rng, n, who)) return rc;
-    if (const int rc = check_call(scene, stats, flags, BAKE_RAYS_FLAGS, "RT_QUERY_DEVICE_POINTERS", who)) return rc;
-    if (n && on_device && ((uintptr_t)rng & 15u)) return fail(RT_ERR_INVALID_ARG, who + "with RT_QUERY_DEVICE_POINTERS the rt_rng array must be 16-byte aligned");
-    if (n && on_device && (((uintptr_t)points | (uintptr_t)out) & 3u)) return fail(RT_ERR_INVALID_ARG, who + "with RT_QUERY_DEVICE_POINTERS points and out must be 4-byte aligned");
-    return answer(scene, n, stats, who, STAGE_BAKE, // the points of a chunk are staged with the baker's state
-        [&](const QueryStage &S, size_t first, size_t m, hipStream_t stream) {
-            if (on_device) return;
-            HIP_CHECK(hipMemcpyAsync(S.bake_points, points + first, m * sizeof(rt_bake_point), hipMemcpyHostToDevice, stream));
-            HIP_CHECK(hipMemcpyAsync(S.rng, rng + first, m * sizeof(rt_rng), hipMemcpyHostToDevice, stream));
-        },
-        [&](const QueryStage &S, size_t first, size_t m, hipStream_t stream) {
+    if (const int rc = check_flags(flags, RT_QUERY_DEVICE_POINTERS, who)) return rc;
+    if (const int rc = check_bake_arrays(scene, nullptr, points, rng, out, n, 1, on_device, who)) return rc;
+    struct A { Arr points, rng, out; };
+    return answer(scene, n, 1, stats, who, {STAGE_BAKE}, on_device, // the points of a chunk are staged with the baker's state
+        [&](const QueryStage &S) { return A{arr_in(points, sizeof(rt_bake_point), S.bake_points), arr_inout(rng, sizeof(rt_rng), S.rng), arr_out(out, sizeof(rt_ray), S.rays)}; },
+        no_prepare,
+        [&](const Chunk &c, const A &a, rt_query_stats &) {
             BakeView B{};
-            B.points = on_device ? (const float *)(points + first) : S.bake_points;
-            B.rng = (uint4 *)(on_device ? rng + first : (rt_rng *)S.rng);
-            B.rays = on_device ? (float *)(out + first) : S.rays;
-            B.totals = S.totals; B.n = (uint32_t)m; B.streams = 1u; B.mode = mode;
-            return query_launch_bake_rays(scene, B, stream);
-        },
-        [&](const QueryStage &S, size_t first, size_t m, hipStream_t stream) {
-            if (on_device) return;
-            HIP_CHECK(hipMemcpyAsync(out + first, S.rays, m * sizeof(rt_ray), hipMemcpyDeviceToHost, stream));
-            HIP_CHECK(hipMemcpyAsync(rng + first, S.rng, m * sizeof(rt_rng), hipMemcpyDeviceToHost, stream));
+            B.points = a.points.as<float>(); B.rng = a.rng.as<uint4>(); B.rays = a.out.as<float>();
+            B.totals = c.S.totals; B.n = (uint32_t)c.m; B.streams = 1u; B.mode = mode;
+            return query_launch_bake_rays(scene, B, c.stream);
         });
 }
 
 int rt_bake(rt_scene *scene, const rt_bake_point *points, size_t n_points, const rt_bake_params *params, rt_rng *rng, float *out, rt_bake_stats *stats) {
     const std::string who = "rt_bake: ";
-    if (!params) return fail(RT_ERR_INVALID_ARG, who + "null argument (params)");
-    if (params->struct_size != sizeof(rt_bake_params)) return fail(RT_ERR_INVALID_ARG, who + "params.struct_size mismatch (ABI skew)");
-    if (stats && stats->struct_size != sizeof(rt_bake_stats)) return fail(RT_ERR_INVALID_ARG, who + "stats.struct_size mismatch (ABI skew)");
-    if (const int rc = check_bake_mode(params->mode, who, "params.mode")) return rc;
-    const uint32_t flags = params->flags;
-    if (flags & ~BAKE_FLAGS) return fail(RT_ERR_INVALID_ARG, who + "params.flags other than RT_QUERY_DEVICE_POINTERS | RT_QUERY_REFERENCE_WALK | RT_BAKE_LOCKSTEP");
-    if (params->reserved[0] || params->reserved[1]) return fail(RT_ERR_INVALID_ARG, who + "params.reserved must be zero");
-    if (params->streams < 0) return fail(RT_ERR_INVALID_ARG, who + "params.streams must not be negative");
-    if (params->streams > 64) return fail(RT_ERR_LIMIT, who + "params.streams above 64");
-    const size_t K = params->streams ? (size_t)params->streams : 1u;
-    if (params->samples < 1) return fail(RT_ERR_INVALID_ARG, who + "params.samples must be at least 1");
-    if ((size_t)params->samples % K) return fail(RT_ERR_INVALID_ARG, who + "params.samples = " + std::to_string(params->samples) + " is no multiple of params.streams = " + std::to_string(K));
-    const int depth = params->ray_depth > 0 ? params->ray_depth : 6;
-    if (depth > RT_MAX_DEPTH) return fail(RT_ERR_LIMIT, who + "params.ray_depth above " + std::to_string(RT_MAX_DEPTH));
-    if (n_points > (((size_t)1 << 31) - 1u) / K) return fail(RT_ERR_LIMIT, who + "n_points * params.streams must stay below 2^31");
-    if (n_points && (!points || !rng || !out)) return fail(RT_ERR_INVALID_ARG, who + "null argument");
-    const bool on_device = (flags & RT_QUERY_DEVICE_POINTERS) != 0, lockstep = (flags & RT_BAKE_LOCKSTEP) != 0;
-    if (!on_device)
-        if (const int rc = check_bake_engines(rng, n_points * K, who)) return rc;
-    if (!scene) return fail(RT_ERR_INVALID_ARG, who + "null argument (scene)");
-    if (const int rc = check_call(scene, nullptr, 0u, 0u, "", who)) return rc;
-    if (n_points && on_device && ((uintptr_t)rng & 15u)) return fail(RT_ERR_INVALID_ARG, who + "with RT_QUERY_DEVICE_POINTERS the rt_rng array must be 16-byte aligned");
-    if (n_points && on_device && (((uintptr_t)points | (uintptr_t)out) & 3u)) return fail(RT_ERR_INVALID_ARG, who + "with RT_QUERY_DEVICE_POINTERS points and out must be 4-byte aligned");
-    const uint32_t walk_flags = flags & (RT_QUERY_DEVICE_POINTERS | RT_QUERY_REFERENCE_WALK);
+    size_t K = 1;
+    int depth = 0;
+    if (const int rc = check_bake_params(params, stats, n_points, WALK_FLAGS | RT_BAKE_LOCKSTEP, who, K, depth)) return rc;
+    const uint32_t flags = params->flags, walk_flags = flags & WALK_FLAGS;
+    const bool on_device = device_pointers(flags), lockstep = (flags & RT_BAKE_LOCKSTEP) != 0;
+    if (const int rc = check_bake_arrays(scene, "scene", points, rng, out, n_points, K, on_device, who)) return rc;
     const size_t floats = params->mode == RT_BAKE_SH9 ? 27u : 3u;
     const uint32_t q = (uint32_t)((size_t)params->samples / K);
     const double pi = 3.14159265358979323846;
     const float scale = params->mode == RT_BAKE_SH9 ? (float)(4.0 * pi / (double)params->samples) : (float)(pi / (double)params->samples);
-    return guarded(who, [&]() -> int {
-        const double t0 = now_ms();
-        rt_bake_stats st{};
-        st.struct_size = sizeof(rt_bake_stats);
-        st.reference_exact = scene->view.exact_boxes == 1u ? 1u : 0u;
-        st.points = n_points;
-        if (n_points) {
-            HIP_CHECK(hipSetDevice(scene->device));
-            hipStream_t stream = nullptr;
-            const QueryStage S = query_stage(scene, STAGE_BAKE, floats, !on_device);
-            const size_t chunk_points = query_chunk() / K; // whole points: the stream sum never crosses a seam (the chunk's minimum of 64 covers K <= 64)
-            const size_t slots_max = std::min(n_points, chunk_points) * K;
-            ensure_materials(scene, stream);
-            uint8_t *stack = path_stack(scene, slots_max, depth);
-            HIP_CHECK(hipMemsetAsync(S.totals, 0, RQ_TOTAL_WORDS * 8, stream));
-            float ms_sum = 0.f;
-            auto mark = [&](bool stop) { // the scene's two events around a stretch of launches; add_ms reads them once the stream has been waited for
-                HIP_CHECK(hipEventRecord(stop ? scene->ev_stop : scene->ev_start, stream));
+    const size_t slots_max = std::min(n_points, query_chunk() / K) * K; // a chunk holds whole points: the stream sum never crosses a seam
+    struct A { Arr points, rng, out; };
+    return answer(scene, n_points, K, stats, who, StageSpec{STAGE_BAKE, floats, !on_device}, on_device,
+        [&](const QueryStage &S) { return A{arr_in(points, sizeof(rt_bake_point), S.bake_points), arr_inout(rng, K * sizeof(rt_rng), S.rng), arr_out(out, floats * sizeof(float), S.bake_out)}; },
+        [&](const Chunk &c, const A &) {
+            prepare_paths(scene, slots_max, depth, c.stream);
+            HIP_CHECK(hipMemsetAsync(c.S.bake_ctr, 0, RQ_BAKE_CTR_WORDS * 8, c.stream));
+        },
+        [&](const Chunk &c, const A &a, rt_bake_stats &st) {
+            const QueryStage &S = c.S;
+            const Paths p = paths_view(scene, c, a.rng.at, slots_max);
+            BakeView B{};
+            B.points = a.points.as<float>(); B.out = a.out.as<float>();
+            B.rng = p.V.rng; B.rays = S.rays; B.dir0 = params->mode == RT_BAKE_SH9 ? S.bake_dir0 : nullptr; B.acc = S.bake_acc; B.left = S.bake_left;
+            B.ctr = S.bake_ctr; B.totals = S.totals;
+            B.n = (uint32_t)c.m; B.streams = (uint32_t)K; B.per_stream = q; B.depth = (uint32_t)depth; B.lockstep = lockstep ? 1u : 0u;
+            B.mode = params->mode; B.floats = (uint32_t)floats; B.scale = scale;
+            unsigned long long ctr[RQ_BAKE_CTR_WORDS] = {};
+            auto poll = [&]() { c.T.stop(); HIP_CHECK(hipMemcpy(ctr, S.bake_ctr, sizeof ctr, hipMemcpyDeviceToHost)); c.T.add(); }; // waits for the stream
+            uint64_t rounds = 0;
+            uint32_t launches = query_launch_bake_rays(scene, B, c.stream);
+            auto round = [&](bool last) {
+                launches += launch_round(scene, S, p.V, c.m, walk_flags, rounds != 0, c.stream);
+                B.last = last ? 1u : 0u;
+                launches += query_launch_bake_advance(scene, p.P, B, c.stream);
+                rounds++;
             };
-            auto add_ms = [&]() { float ms = 0.f; HIP_CHECK(hipEventElapsedTime(&ms, scene->ev_start, scene->ev_stop)); ms_sum += ms; };
-            for (size_t first = 0; first < n_points; first += chunk_points) {
-                const size_t pts = std::min(chunk_points, n_points - first), m = pts * K;
-                if (!on_device) {
-                    HIP_CHECK(hipMemcpyAsync(S.bake_points, points + first, pts * sizeof(rt_bake_point), hipMemcpyHostToDevice, stream));
-                    HIP_CHECK(hipMemcpyAsync(S.rng, rng + first * K, m * sizeof(rt_rng), hipMemcpyHostToDevice, stream));
+            if (lockstep) { // the plain composition: every slot starts sample j in the same round, every sample takes `depth` rounds
+                for (uint32_t j = 0; j < q; j++)
+                    for (int b = 0; b < depth; b++) round(b == depth - 1);
+                poll();
+            } else {        // regeneration: a round at a time, until every valid slot is parked
+                for (poll(); ctr[RQ_BAKE_CTR_PARKED] < ctr[RQ_BAKE_CTR_SLOTS]; poll()) {
+                    c.T.start();
+                    round(false);
                 }
-                HIP_CHECK(hipMemsetAsync(stack, 0, slots_max * 16u, stream)); // tail 0, no bounce kept, not ended
-                HIP_CHECK(hipMemsetAsync(S.ctr, 0, RQ_CTR_WORDS * 4, stream));
-                HIP_CHECK(hipMemsetAsync(S.bake_ctr, 0, RQ_BAKE_CTR_WORDS * 8, stream));
-                const ScatterView V = scatter_view(S, m, ScatterArrays{(const rt_ray *)S.rays, (const rt_hit *)S.out, (const rt_surface *)S.surf,
-                                                                       on_device ? rng + first * K : (rt_rng *)S.rng, (rt_scatter *)S.scat});
-                PathView P{};
-                P.rays = S.rays; P.hits = V.hits; P.surfaces = V.surfaces; P.scatter = V.out;
-                P.state = (float4 *)stack; P.stack = (float *)(stack + slots_max * 16u);
-                P.n = (uint32_t)m;
-                BakeView B{};
-                B.points = on_device ? (const float *)(points + first) : S.bake_points;
-                B.rng = V.rng; B.rays = S.rays; B.dir0 = params->mode == RT_BAKE_SH9 ? S.bake_dir0 : nullptr; B.acc = S.bake_acc; B.left = S.bake_left;
-                B.out = on_device ? out + first * floats : S.bake_out;
-                B.ctr = S.bake_ctr; B.totals = S.totals;
-                B.n = (uint32_t)m; B.streams = (uint32_t)K; B.per_stream = q; B.depth = (uint32_t)depth; B.lockstep = lockstep ? 1u : 0u;
-                B.mode = params->mode; B.floats = (uint32_t)floats; B.scale = scale;
-                unsigned long long ctr[RQ_BAKE_CTR_WORDS] = {};
-                auto poll = [&]() { HIP_CHECK(hipMemcpy(ctr, S.bake_ctr, sizeof ctr, hipMemcpyDeviceToHost)); add_ms(); }; // waits for the stream
-                uint64_t rounds = 0;
-                auto round = [&](bool last) {
-                    st.launches += launch_round(scene, S, V, m, walk_flags, rounds != 0, stream);
-                    B.last = last ? 1u : 0u;
-                    st.launches += query_launch_bake_advance(scene, P, B, stream);
-                    rounds++;
-                };
-                mark(false);
-                st.launches += query_launch_bake_rays(scene, B, stream);
-                if (lockstep) { // the plain composition: every slot starts sample j in the same round, every sample takes `depth` rounds
-                    for (uint32_t j = 0; j < q; j++)
-                        for (int b = 0; b < depth; b++) round(b == depth - 1);
-                    mark(true);
-                    poll();
-                } else {        // regeneration: a round at a time, until every valid slot is parked
-                    mark(true);
-                    poll();
-                    while (ctr[RQ_BAKE_CTR_PARKED] < ctr[RQ_BAKE_CTR_SLOTS]) {
-                        mark(false);
-                        round(false);
-                        mark(true);
-                        poll();
-                    }
-                }
-                BakeView R = B;
-                R.n = (uint32_t)(pts * floats);
-                mark(false);
-                st.launches += query_launch_bake_resolve(scene, R, stream);
-                mark(true);
-                if (!on_device) {
-                    HIP_CHECK(hipMemcpyAsync(out + first * floats, S.bake_out, pts * floats * sizeof(float), hipMemcpyDeviceToHost, stream));
-                    HIP_CHECK(hipMemcpyAsync(rng + first * K, S.rng, m * sizeof(rt_rng), hipMemcpyDeviceToHost, stream));
-                }
-                HIP_CHECK(hipStreamSynchronize(stream)); // the next chunk reuses the staging
-                add_ms();
-                st.invalid_points += ctr[RQ_BAKE_CTR_INVALID_POINTS];
-                st.paths += ctr[RQ_BAKE_CTR_SLOTS] * q;
-                st.live_ray_slots += ctr[RQ_BAKE_CTR_LIVE_RAY_SLOTS];
-                st.rounds += rounds;
-                st.ray_slots += rounds * m;
             }
-            unsigned long long totals[RQ_TOTAL_WORDS];
-            HIP_CHECK(hipMemcpy(totals, S.totals, sizeof totals, hipMemcpyDeviceToHost));
-            st.exact_walks = totals[RQ_TOTAL_EXACT] + totals[RQ_TOTAL_RIDE_EXACT];
-            st.kernel_ms = ms_sum;
-        }
-        st.total_ms = now_ms() - t0;
-        if (stats) *stats = st;
-        return RT_OK;
-    });
+            c.T.start();
+            BakeView R = B;
+            R.n = (uint32_t)(c.m / K * floats);
+            st.invalid_points += ctr[RQ_BAKE_CTR_INVALID_POINTS];
+            st.paths += ctr[RQ_BAKE_CTR_SLOTS] * q;
+            st.live_ray_slots += ctr[RQ_BAKE_CTR_LIVE_RAY_SLOTS];
+            st.rounds += rounds;
+            st.ray_slots += rounds * c.m;
+            return launches + query_launch_bake_resolve(scene, R, c.stream);
+        });
 }
 
 int rt_render_paths(rt_scene *scene, const rt_ray *rays, rt_rng *rng, size_t n, int32_t ray_depth, uint32_t flags, float *out_rgb, rt_query_stats *stats) {
     const std::string who = "rt_render_paths: ";
-    if (n && (!rays || !rng || !out_rgb)) return fail(RT_ERR_INVALID_ARG, who + "null argument");
-    if (stats && stats->struct_size != sizeof(rt_query_stats)) return fail(RT_ERR_INVALID_ARG, who + "struct_size mismatch (ABI skew)");
-    if (flags & ~RT_QUERY_DEVICE_POINTERS) return fail(RT_ERR_INVALID_ARG, who + "flags other than RT_QUERY_DEVICE_POINTERS");
-    const bool on_device = (flags & RT_QUERY_DEVICE_POINTERS) != 0;
-    if (!on_device)
-        if (const int rc = check_bake_engines(rng, n, who)) return rc;
-    const int depth = ray_depth > 0 ? ray_depth : 6;
-    if (depth > RT_MAX_DEPTH) return fail(RT_ERR_LIMIT, who + "ray_depth above " + std::to_string(RT_MAX_DEPTH));
-    if (const int rc = check_call(scene, stats, flags, RT_QUERY_DEVICE_POINTERS, "RT_QUERY_DEVICE_POINTERS", who)) return rc;
-    if (n && on_device && ((uintptr_t)rng & 15u)) return fail(RT_ERR_INVALID_ARG, who + "with RT_QUERY_DEVICE_POINTERS the rt_rng array must be 16-byte aligned");
-    if (n && on_device && (((uintptr_t)rays | (uintptr_t)out_rgb) & 3u)) return fail(RT_ERR_INVALID_ARG, who + "with RT_QUERY_DEVICE_POINTERS rays and out_rgb must be 4-byte aligned");
+    const bool on_device = device_pointers(flags);
+    int depth = 0;
+    if (n && (!rays || !rng || !out_rgb)) return null_arg(who);
+    if (const int rc = check_struct_size(stats, who)) return rc;
+    if (const int rc = check_flags(flags, RT_QUERY_DEVICE_POINTERS, who)) return rc;
+    if (const int rc = check_engines(rng, n, on_device, who)) return rc;
+    if (const int rc = check_depth(ray_depth, who, "", depth)) return rc;
+    if (const int rc = check_scene(scene, who)) return rc;
+    if (const int rc = check_engine_arrays(n && on_device, rng, rays, out_rgb, "rays and out_rgb", who)) return rc;
     if (const int rc = source_check(scene, (uint32_t)std::min(std::max<size_t>(n, 1u), source_chunk()), depth, 1, who)) return rc;
-    return guarded(who, [&]() -> int {
-        const double t0 = now_ms();
-        rt_query_stats st{};
-        st.struct_size = sizeof(rt_query_stats);
-        st.reference_exact = scene->view.exact_boxes == 1u ? 1u : 0u;
-        st.rays = n;
-        if (n) {
-            SourceTotals T;
-            if (const int rc = source_run(scene, SourceCall{1u, 1u, depth, 1, 0.f, rays, rng, out_rgb, on_device}, n, who, T)) return rc;
-            st.exact_walks = T.exact_walks; st.invalid_rays = T.no_path; st.kernel_ms = T.kernel_ms; st.launches = T.launches;
-            st.reference_exact = T.reference_exact;
-        }
-        st.total_ms = now_ms() - t0;
-        if (stats) *stats = st;
+    return with_stats(scene, n, stats, who, [&](rt_query_stats &st) -> int {
+        SourceTotals T;
+        if (const int rc = source_run(scene, SourceCall{1u, 1u, depth, 1, 0.f, rays, rng, out_rgb, on_device}, n, who, T)) return rc;
+        st.exact_walks = T.exact_walks; st.invalid_rays = T.no_path; st.kernel_ms = T.kernel_ms; st.launches = T.launches;
+        st.reference_exact = T.reference_exact;
         return RT_OK;
     });
 }
 
 int rt_render_bake(rt_scene *scene, const rt_bake_point *points, size_t n_points, const rt_bake_params *params, rt_rng *rng, float *out, rt_bake_stats *stats) {
     const std::string who = "rt_render_bake: ";
-    if (!params) return fail(RT_ERR_INVALID_ARG, who + "null argument (params)");
-    if (params->struct_size != sizeof(rt_bake_params)) return fail(RT_ERR_INVALID_ARG, who + "params.struct_size mismatch (ABI skew)");
-    if (stats && stats->struct_size != sizeof(rt_bake_stats)) return fail(RT_ERR_INVALID_ARG, who + "stats.struct_size mismatch (ABI skew)");
-    if (const int rc = check_bake_mode(params->mode, who, "params.mode")) return rc;
-    const uint32_t flags = params->flags;
-    if (flags & ~RT_QUERY_DEVICE_POINTERS) return fail(RT_ERR_INVALID_ARG, who + "params.flags other than RT_QUERY_DEVICE_POINTERS");
-    if (params->reserved[0] || params->reserved[1]) return fail(RT_ERR_INVALID_ARG, who + "params.reserved must be zero");
-    if (params->streams < 0) return fail(RT_ERR_INVALID_ARG, who + "params.streams must not be negative");
-    if (params->streams > 64) return fail(RT_ERR_LIMIT, who + "params.streams above 64");
-    const size_t K = params->streams ? (size_t)params->streams : 1u;
-    if (params->samples < 1) return fail(RT_ERR_INVALID_ARG, who + "params.samples must be at least 1");
-    if ((size_t)params->samples % K) return fail(RT_ERR_INVALID_ARG, who + "params.samples = " + std::to_string(params->samples) + " is no multiple of params.streams = " + std::to_string(K));
-    const int depth = params->ray_depth > 0 ? params->ray_depth : 6;
-    if (depth > RT_MAX_DEPTH) return fail(RT_ERR_LIMIT, who + "params.ray_depth above " + std::to_string(RT_MAX_DEPTH));
-    if (n_points > (((size_t)1 << 31) - 1u) / K) return fail(RT_ERR_LIMIT, who + "n_points * params.streams must stay below 2^31");
+    size_t K = 1;
+    int depth = 0;
+    if (const int rc = check_bake_params(params, stats, n_points, RT_QUERY_DEVICE_POINTERS, who, K, depth)) return rc;
     const size_t q = (size_t)params->samples / K;
     if (q >= ((size_t)1 << 25)) return fail(RT_ERR_LIMIT, who + "params.samples / params.streams must stay below 2^25 (the path record's sample index)");
     if (params->mode == RT_BAKE_SH9)
         return fail(RT_ERR_UNSUPPORTED, who + "RT_BAKE_SH9 does not fit the persistent kernel's path record (27 accumulators and the first direction): rt_bake serves it");
-    if (n_points && (!points || !rng || !out)) return fail(RT_ERR_INVALID_ARG, who + "null argument");
-    const bool on_device = (flags & RT_QUERY_DEVICE_POINTERS) != 0;
-    if (!on_device)
-        if (const int rc = check_bake_engines(rng, n_points * K, who)) return rc;
-    if (!scene) return fail(RT_ERR_INVALID_ARG, who + "null argument (scene)");
-    if (const int rc = check_call(scene, nullptr, 0u, 0u, "", who)) return rc;
-    if (n_points && on_device && ((uintptr_t)rng & 15u)) return fail(RT_ERR_INVALID_ARG, who + "with RT_QUERY_DEVICE_POINTERS the rt_rng array must be 16-byte aligned");
-    if (n_points && on_device && (((uintptr_t)points | (uintptr_t)out) & 3u)) return fail(RT_ERR_INVALID_ARG, who + "with RT_QUERY_DEVICE_POINTERS points and out must be 4-byte aligned");
+    const bool on_device = device_pointers(params->flags);
+    if (const int rc = check_bake_arrays(scene, "scene", points, rng, out, n_points, K, on_device, who)) return rc;
     if (const int rc = source_check(scene, (uint32_t)std::min(std::max<size_t>(n_points, 1u) * K, source_chunk()), depth, (int32_t)q, who)) return rc;
     const double pi = 3.14159265358979323846;
     const float scale = (float)(pi / (double)params->samples);
-    return guarded(who, [&]() -> int {
-        const double t0 = now_ms();
-        rt_bake_stats st{};
-        st.struct_size = sizeof(rt_bake_stats);
-        st.reference_exact = scene->view.exact_boxes == 1u ? 1u : 0u;
-        st.points = n_points;
-        if (n_points) {
-            SourceTotals T;
-            if (const int rc = source_run(scene, SourceCall{2u, K, depth, (int32_t)q, scale, points, rng, out, on_device}, n_points, who, T)) return rc;
-            st.invalid_points = T.no_path; st.paths = (n_points - T.no_path) * K * q; st.exact_walks = T.exact_walks;
-            st.kernel_ms = T.kernel_ms; st.launches = T.launches; st.reference_exact = T.reference_exact;
-        }
-        st.total_ms = now_ms() - t0;
-        if (stats) *stats = st;
+    return with_stats(scene, n_points, stats, who, [&](rt_bake_stats &st) -> int {
+        SourceTotals T;
+        if (const int rc = source_run(scene, SourceCall{2u, K, depth, (int32_t)q, scale, points, rng, out, on_device}, n_points, who, T)) return rc;
+        st.invalid_points = T.no_path; st.paths = (n_points - T.no_path) * K * q; st.exact_walks = T.exact_walks;
+        st.kernel_ms = T.kernel_ms; st.launches = T.launches; st.reference_exact = T.reference_exact;
         return RT_OK;
     });
 }

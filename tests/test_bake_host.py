@@ -3,7 +3,7 @@ package binds it; the three records have the sizes the C compiler sees; every re
 arrives on a null scene with a message naming the field; the wrapper refuses mismatched shapes; and tests/bake_model.py is checked
 against the oracle before it judges the GPU (tests/test_gpu_bake.py): its cosine direction and stream position are the oracle's,
 its SH polynomials are the real ones to float32 rounding, and its loop over the oracle's calls folds what scatter_model.trace folds.
-The same refusals run under the host sanitizers in tools/sanitize/bake_sanitize.cpp, stand-alone."""
+The same refusals run under the host sanitizers in tools/sanitize/query_sanitize.cpp, stand-alone."""
 import ctypes as C
 import os
 import re
