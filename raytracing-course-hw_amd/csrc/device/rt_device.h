@@ -297,14 +297,45 @@ RT_DEV bool tri_test_closer(const TriIsect &T, F3 o, F3 d, float keep_t, float &
     return true;
 }
 
-RT_DEV TriIsect load_isect(const TriIsect *p) {
-    const float4 *q = reinterpret_cast<const float4 *>(p);
-    float4 a = q[0], b = q[1], c = q[2];
+RT_DEV TriIsect isect_of(float4 a, float4 b, float4 c) { // a record from its three 16-byte words
     TriIsect T;
     T.ax = a.x; T.ay = a.y; T.az = a.z; T.nx = a.w;
     T.ny = b.x; T.nz = b.y; T.a1 = b.z; T.b1 = b.w;
     T.a2 = c.x; T.b2 = c.y; T.den = c.z; T.pad = __float_as_uint(c.w);
     return T;
+}
+RT_DEV TriIsect load_isect(const TriIsect *p) {
+    const float4 *q = reinterpret_cast<const float4 *>(p);
+    const float4 a = q[0], b = q[1], c = q[2];
+    return isect_of(a, b, c);
+}
+
+// A wave-uniform array that a walker reads in its innermost loops, as the loads want it: the base in a scalar register pair of its own, known to
+// the compiler to point into global memory, and every record at a 32-bit byte offset from it.  That is the `global_load v, v_off, s[base]` form:
+// no 64-bit address arithmetic per fetch, and no flat access, which would count on the LDS counter as well and make a fetch wait for the lane's
+// stack traffic.  The arrays read this way hold at most RT_WALK_MAX_RECORDS records and stay below 4 GiB (rt_types.h; checked at scene creation).
+// Why a pair of its own: taken straight from the kernel arguments the pointer sits in a group of four registers that the allocator keeps or spills
+// as a whole.  Without the copy (profiles/r09_scheduler_refactor.txt) the hw8 node loops reload the pointer with 4 v_readlane per step and the light
+// leaf loop reloads 30 SGPRs per iteration instead of 15.
+#define RT_GLOBAL __attribute__((address_space(1)))
+struct GlobalBytes {
+    const RT_GLOBAL char *base;
+    // A plain vector: HIP's uint4 is a class, which no address space but the generic one can copy.  Loaded this way a record's three words come as
+    // three 16-byte loads ahead of the test; through a uint4 pointer the compiler cut them up and sank 20 bytes of a triangle behind its plane test,
+    // a second round trip for every lane that passed it (profiles/r32_walker_loads.txt).
+    typedef uint32_t Word4 __attribute__((ext_vector_type(4)));
+    // 16-byte word k of the record at byte `ofs`: base + ofs is the load's scalar base and 32-bit offset, 16 k its immediate
+    RT_DEV uint4 u4(uint32_t ofs, uint32_t k = 0u) const { const Word4 w = reinterpret_cast<const RT_GLOBAL Word4 *>(base + ofs)[k]; return make_uint4(w.x, w.y, w.z, w.w); }
+    RT_DEV float4 f4(uint32_t ofs, uint32_t k = 0u) const { const uint4 w = u4(ofs, k); return make_float4(__uint_as_float(w.x), __uint_as_float(w.y), __uint_as_float(w.z), __uint_as_float(w.w)); }
+};
+RT_DEV GlobalBytes global_bytes(const void *p) { return GlobalBytes{(const RT_GLOBAL char *)p}; }                    // the address space alone
+RT_DEV GlobalBytes global_bytes_own(const void *p) { asm volatile("" : "+s"(p)); return global_bytes(p); }           // ... and the register pair
+// byte offset of record i < 2^24 of `stride` bytes each: one full-rate 24-bit multiply
+RT_DEV uint32_t record_ofs(uint32_t i, uint32_t stride) { return __umul24(i, stride); }
+// the TriIsect at the head of the record at byte `ofs`
+RT_DEV TriIsect load_isect(const GlobalBytes &g, uint32_t ofs) {
+    const float4 a = g.f4(ofs, 0u), b = g.f4(ofs, 1u), c = g.f4(ofs, 2u);
+    return isect_of(a, b, c);
 }
 
 // ---- my BVH: conservative two-box slab test -------------------------------------------------------

@@ -205,28 +205,30 @@ RT_DEV bool pt_tripwire(const SceneView &S, F3 o, F3 d) {
 // light_pdf_one (rt_device.h) that also says whether the hit is robust against the reference's box tests (pt_box_robust on
 // the light triangle's own box: a, a + b, a + c).
 // `index`: the light's position in the reference's light order — carried by the record itself (pad >> 1) in the persistent kernel's own light
-// tree (SceneView::lights_walk), whose leaf order is not the light order.
+// tree (SceneView::lights_walk_test / lights_walk_rest), whose leaf order is not the light order.
 // The same in two steps, for a leaf loop that tests several lights and leaves the (rarer, longer) work on a hit for after the loop:
 // pt_light_test is the triangle test alone, pt_light_pdf_hit what light_pdf_one computes once the test has passed.
-RT_DEV bool pt_light_test(const LightRec *L, F3 x, F3 d, bool &last, uint32_t &index, float &t, float &u, float &v, bool &inside) {
-    const TriIsect T = load_isect(&L->isect);
+// `tests`, `rests`: the walker's light records (SceneView::lights_walk_test / lights_walk_rest), `i`: the record.
+RT_DEV bool pt_light_test(const GlobalBytes &tests, uint32_t i, F3 x, F3 d, bool &last, uint32_t &index, float &t, float &u, float &v, bool &inside) {
+    const TriIsect T = load_isect(tests, record_ofs(i, (uint32_t)sizeof(TriIsect)));
     last = (T.pad & 1u) != 0;
     index = T.pad >> 1;
     return tri_test(T, x, d, t, u, v, inside);
 }
-RT_DEV float pt_light_pdf_hit(const SceneView &S, const LightRec *L, F3 x, F3 d, float t, float u, float v, bool inside, bool &robust) {
+RT_DEV float pt_light_pdf_hit(const SceneView &S, const GlobalBytes &tests, const GlobalBytes &rests, uint32_t i, F3 x, F3 d, float t, float u, float v, bool inside, bool &robust) {
     robust = true;
-    const float4 *q = reinterpret_cast<const float4 *>(L) + 3;
-    float4 q1 = q[1], q2 = q[2], q3 = q[3];
+    uint32_t q = record_ofs(i, (uint32_t)sizeof(LightRest)); // 16-byte words: 0 b, c.xy; 1 c.z, point_prob, n3.xy; 2 n3.z, dn1; 3 dn2 .. 4, 5 the box
+    const float4 q1 = rests.f4(q, 1u), q2 = rests.f4(q, 2u), q3 = rests.f4(q, 3u);
     float point_prob = q1.z;
     F3 n3 = f3(q1.w, q2.x, q2.y), dn1 = f3(q2.z, q2.w, q3.x), dn2 = f3(q3.y, q3.z, q3.w);
     F3 sn = n3 + u * dn1 + v * dn2;           // primitives.cpp:110
     sn = normalize(sn);                        // :117
     if (inside) sn = neg(sn);                  // :118-119
-    if (S.hw7) { const TriIsect T = load_isect(&L->isect); F3 n = f3(T.nx, T.ny, T.nz); sn = normalize(inside ? neg(n) : n); }
+    if (S.hw7) { const TriIsect T = load_isect(tests, record_ofs(i, (uint32_t)sizeof(TriIsect))); F3 n = f3(T.nx, T.ny, T.nz); sn = normalize(inside ? neg(n) : n); }
     F3 y = x + t * d;                          // distributions.h:144
     if (S.exact_boxes == 1u) {
-        const float4 blo = q[4], bhi = q[5];   // the light's own box (LightRec::box_lo / box_hi)
+        asm volatile("" : "+v"(q)); // the offset as a value of THIS block: one carried in arrives 64 bits wide and is added to the base in the VALU
+        const float4 blo = rests.f4(q, 4u), bhi = rests.f4(q, 5u); // the light's own box (LightRest::box_lo / box_hi)
         robust = pt_box_robust(f3(blo.x, blo.y, blo.z), f3(bhi.x, bhi.y, bhi.z), y, d, t, S.box_c2);
     }
     return point_prob * len2(x - y) / fabsf(dot(d, sn)); // :68-70 (pdfOne, shading normal in hw8)

@@ -87,11 +87,22 @@ RT_DEV void pt_order(uint32_t &ka, uint32_t &ca, uint32_t &kb, uint32_t &cb) {
     kb = s ? ka : kb; cb = s ? ca : cb;
     ka = k; ca = c;
 }
+// The four records of wide node `cur`.  NODES: the node array as the kernel holds it, a plain pointer (rt_persistent_hw6.h) or a GlobalBytes
+// (this file's walkers: one 64-byte node at byte cur << 6 of an array below 4 GiB).
+RT_DEV void pt_node_records(const GpuNode4Q *nodes, uint32_t cur, uint4 &b0, uint4 &b1, uint4 &b2, uint4 &b3) {
+    const uint4 *q = reinterpret_cast<const uint4 *>(nodes + cur);
+    b0 = q[0]; b1 = q[1]; b2 = q[2]; b3 = q[3];
+}
+RT_DEV void pt_node_records(const GlobalBytes nodes, uint32_t cur, uint4 &b0, uint4 &b1, uint4 &b2, uint4 &b3) {
+    const uint32_t ofs = cur << 6;
+    b0 = nodes.u4(ofs, 0u); b1 = nodes.u4(ofs, 1u); b2 = nodes.u4(ofs, 2u); b3 = nodes.u4(ofs, 3u);
+}
 // Closest-hit walks: the entered children nearest first — the nearest becomes `cur`, the others are pushed farthest first.
 // `cap`: entries the column may hold.
-RT_DEV int pt_wide_step_nearest(const GpuNode4Q *nodes, const RayGrid &ray, float cull_t, uint32_t (*stack)[64], int lane, int &sp, int cap, uint32_t &cur) {
-    const uint4 *q = reinterpret_cast<const uint4 *>(nodes + cur);
-    const uint4 b0 = q[0], b1 = q[1], b2 = q[2], b3 = q[3];
+template <class NODES>
+RT_DEV int pt_wide_step_nearest(const NODES nodes, const RayGrid &ray, float cull_t, uint32_t (*stack)[64], int lane, int &sp, int cap, uint32_t &cur) {
+    uint4 b0, b1, b2, b3;
+    pt_node_records(nodes, cur, b0, b1, b2, b3);
     uint32_t k0, k1, k2, k3;
     const bool h0 = slab_enter_q(b0, ray, cull_t, k0), h1 = slab_enter_q(b1, ray, cull_t, k1);
     const bool h2 = slab_enter_q(b2, ray, cull_t, k2), h3 = slab_enter_q(b3, ray, cull_t, k3);
@@ -109,14 +120,23 @@ RT_DEV int pt_wide_step_nearest(const GpuNode4Q *nodes, const RayGrid &ray, floa
 }
 // Which records of wide node `cur` a light sum enters: the one decision of the light walker (pt_wide_step_all) and of the shader's
 // settling of light sums (pt_light_reach), so that both take it with the same code.
-RT_DEV void pt_wide_enter_all(const GpuNode4Q *nodes, uint32_t cur, const RayGrid &ray, uint4 &b0, uint4 &b1, uint4 &b2, uint4 &b3,
+template <class NODES>
+RT_DEV void pt_wide_enter_all(const NODES nodes, uint32_t cur, const RayGrid &ray, uint4 &b0, uint4 &b1, uint4 &b2, uint4 &b3,
                               bool &h0, bool &h1, bool &h2, bool &h3) {
-    const uint4 *q = reinterpret_cast<const uint4 *>(nodes + cur);
-    b0 = q[0]; b1 = q[1]; b2 = q[2]; b3 = q[3];
+    pt_node_records(nodes, cur, b0, b1, b2, b3);
     h0 = slab_test_q(b0, ray); h1 = slab_test_q(b1, ray); h2 = slab_test_q(b2, ray); h3 = slab_test_q(b3, ray); // no entry distance: every entered child is walked
 }
+// The root of a tree is the same 64 bytes for every lane: read through the constant address space, i.e. by scalar loads, once for the wave.
+struct PtRootNode { const GpuNode4Q *nodes; };
+RT_DEV void pt_node_records(const PtRootNode root, uint32_t, uint4 &b0, uint4 &b1, uint4 &b2, uint4 &b3) {
+    typedef const __attribute__((address_space(4))) GlobalBytes::Word4 *Q;
+    const Q q = (Q)root.nodes;
+    const GlobalBytes::Word4 w0 = q[0], w1 = q[1], w2 = q[2], w3 = q[3];
+    b0 = make_uint4(w0.x, w0.y, w0.z, w0.w); b1 = make_uint4(w1.x, w1.y, w1.z, w1.w); b2 = make_uint4(w2.x, w2.y, w2.z, w2.w); b3 = make_uint4(w3.x, w3.y, w3.z, w3.w);
+}
 // Light sums: every entered child is walked, in any order (the callers keep their hits sorted): the first one now, the others wait.
-RT_DEV int pt_wide_step_all(const GpuNode4Q *nodes, const RayGrid &ray, uint32_t (*stack)[64], int lane, int &sp, int cap, uint32_t &cur) {
+template <class NODES>
+RT_DEV int pt_wide_step_all(const NODES nodes, const RayGrid &ray, uint32_t (*stack)[64], int lane, int &sp, int cap, uint32_t &cur) {
     uint4 b0, b1, b2, b3;
     bool h0, h1, h2, h3;
     pt_wide_enter_all(nodes, cur, ray, b0, b1, b2, b3, h0, h1, h2, h3);
@@ -141,7 +161,8 @@ template <int LEVELS>
 RT_DEV int pt_light_reach(const SceneView &S, const RayGrid &ray, int &steps) {
     uint4 b[4];
     bool h[4];
-    pt_wide_enter_all(S.light_walk_nodes4, 0u, ray, b[0], b[1], b[2], b[3], h[0], h[1], h[2], h[3]);
+    const GlobalBytes nodes = global_bytes(S.light_walk_nodes4);
+    pt_wide_enter_all(PtRootNode{S.light_walk_nodes4}, 0u, ray, b[0], b[1], b[2], b[3], h[0], h[1], h[2], h[3]);
     steps = 1;
     if (!(h[0] | h[1] | h[2] | h[3])) return 0;
     if (LEVELS < 2) return 2;
@@ -150,7 +171,7 @@ RT_DEV int pt_light_reach(const SceneView &S, const RayGrid &ray, int &steps) {
         if (b[c].w & RT_LEAF_BIT) return 2;                      // a leaf (or an unused record): the walker tests lights there
         uint4 g0, g1, g2, g3;
         bool e0, e1, e2, e3;
-        pt_wide_enter_all(S.light_walk_nodes4, b[c].w, ray, g0, g1, g2, g3, e0, e1, e2, e3);
+        pt_wide_enter_all(nodes, b[c].w, ray, g0, g1, g2, g3, e0, e1, e2, e3);
         steps++;
         if (e0 | e1 | e2 | e3) return 2;
     }
@@ -392,16 +413,13 @@ RT_DEV void pt_walk_stint(WK &w, SH &sh, const PtParams &P, PtWave &wv, uint32_t
     }
 }
 
-// A wave-uniform pointer in a scalar register pair of its own, for what a walker reads in its innermost loops: taken straight from the kernel arguments it
-// sits in a group of four registers that the allocator keeps or spills as a whole.  Without the copies (profiles/r09_scheduler_refactor.txt) the hw8 node
-// loops reload the pointer with 4 v_readlane per step and the light leaf loop reloads 30 SGPRs per iteration instead of 15.
-template <class T> RT_DEV const T *pt_own_pointer(const T *p) { asm volatile("" : "+s"(p)); return p; }
+// What a walker reads in its innermost loops it reads through a GlobalBytes of its own (rt_device.h global_bytes_own): a scalar base, 32-bit offsets.
 // ---- closest-hit walker: near-first, tie -> lowest figure index ---------------------------------------------------------------------
 struct PtTraceWalk {
     typedef PtTraceQueue Queue;
     static constexpr uint32_t COST_NODE = PT_COST_TRACE_NODE, COST_TEST = PT_COST_TRACE_TRI;
     const SceneView &S; const WfView &W; PtShared &sh; const PtParams &P; uint32_t (*stack)[64];
-    const GpuNode4Q *nodes = pt_own_pointer(S.nodes4);
+    const GlobalBytes nodes = global_bytes_own(S.nodes4), tris = global_bytes(S.tri_walk);
     const int lane = threadIdx.x & 63;
     F3 o = f3(0.f, 0.f, 0.f), d = f3(0.f, 0.f, 1.f);
     RayGrid ray = RT_GRID_RAY_IDLE; // idle lanes: never used
@@ -425,7 +443,7 @@ struct PtTraceWalk {
     // stack of its own (pt_exact_batch).
     RT_DEV void full() { best_t = PT_T_OVERFLOW; best_u = 0.f; best_v = 0.f; hit = 0u; t2 = PT_T_OVERFLOW; }
     RT_DEV bool test(uint32_t i, int, Leaf &) {
-        TriIsect T = load_isect(S.tri_walk + i);
+        TriIsect T = load_isect(tris, record_ofs(i, (uint32_t)sizeof(TriIsect)));
         float t, u, v; bool inside;
         const uint32_t fi = T.pad >> 1; // index in the figure order
         if (tri_test_closer(T, o, d, cull_t, t, u, v, inside)) {
@@ -451,8 +469,7 @@ template <bool COUNT> struct PtLightWalk {
     typedef PtLightQueue<PT_Q_XLIGHT> Queue;
     static constexpr uint32_t COST_NODE = PT_COST_LIGHT_NODE, COST_TEST = PT_COST_LIGHT_TEST;
     const SceneView &S; const WfView &W; PtShared &sh; const PtParams &P; uint32_t (*stack)[64]; PtProf &prof;
-    const GpuNode4Q *nodes = pt_own_pointer(S.light_walk_nodes4);
-    const LightRec *lights = pt_own_pointer(S.lights_walk);
+    const GlobalBytes nodes = global_bytes_own(S.light_walk_nodes4), tests = global_bytes_own(S.lights_walk_test), rests = global_bytes(S.lights_walk_rest);
     const int lane = threadIdx.x & 63;
     bool overflow = false; // the exact role sums this query
     int k = 0;             // hits so far
@@ -473,7 +490,7 @@ template <bool COUNT> struct PtLightWalk {
     RT_DEV void full() { overflow = true; } // no room beside the hits
     RT_DEV void take(Leaf &lf, int sp) { // the held hit joins the lane's hits
         bool robust;
-        const float term = pt_light_pdf_hit(S, lights + lf.h_i, o, d, lf.h_t, lf.h_u, lf.h_v, lf.h_in, robust);
+        const float term = pt_light_pdf_hit(S, tests, rests, lf.h_i, o, d, lf.h_t, lf.h_u, lf.h_v, lf.h_in, robust);
         if (COUNT && term != 0.f) prof.light_hits++;
         if (term != 0.f) { // (a hit whose term is exactly 0 adds nothing, like a miss)
             if (!robust || k >= WF_MAX_LIGHT_HITS || sp + 2 * k + 2 >= P8_STACK) overflow = true;
@@ -492,7 +509,7 @@ template <bool COUNT> struct PtLightWalk {
     RT_DEV bool test(uint32_t i, int sp, Leaf &lf) {
         bool last, inside; uint32_t li; float t, u, v;
         if (COUNT) prof.light_tests++;
-        if (pt_light_test(lights + i, o, d, last, li, t, u, v, inside)) {
+        if (pt_light_test(tests, i, o, d, last, li, t, u, v, inside)) {
             if (lf.held) take(lf, sp); // a second hit in this phase
             lf.held = true; lf.h_i = i; lf.h_li = li; lf.h_t = t; lf.h_u = u; lf.h_v = v; lf.h_in = inside;
         }
@@ -986,10 +1003,11 @@ struct PtRoles {
     }
     RT_DEV PtShaded shade(uint32_t got, uint32_t &n_light, unsigned long long &n_nodes, PtProf &prof) {
         const uint32_t lane = threadIdx.x & 63u;
+        const uint32_t slot = got != PT_NONE ? pt_slot(sh, got) : 0u; // once: an LDS read and a readfirstlane each time
         int todo = 0;
         bool discarded = false;
         if (COUNT && P.trace_buf && got != PT_NONE) {
-            const uint32_t tslot = pt_slot(sh, got);
+            const uint32_t tslot = slot;
             int tx, ty; bool tin; size_t toi;
             wf_slot_to_pixel(R, tslot + W.slot_base, tx, ty, tin, toi);
             if (tin && ty * R.width + tx == P.trace_pixel) {
@@ -999,7 +1017,7 @@ struct PtRoles {
             }
         }
         PtShadeLap<COUNT> lp;
-        if (got != PT_NONE) { PtPark pk; pk.p = (PtLdsWord)&stack[0][lane]; todo = pt_shade_lean<FEAT>(S, R, W, pt_slot(sh, got), pk, discarded, lp); }
+        if (got != PT_NONE) { PtPark pk; pk.p = (PtLdsWord)&stack[0][lane]; todo = pt_shade_lean<FEAT>(S, R, W, slot, pk, discarded, lp); }
         if constexpr (COUNT) { // each section once per batch: its lanes all hold the same time
             for (int k = 0; k < 5; k++) {
                 const unsigned long long m = pt_ballot(lp.d[k] != 0u);
@@ -1013,7 +1031,7 @@ struct PtRoles {
         bool settled = false; // its light sum is settled here (PT_LIGHT_SETTLE): the walk would test no light
         int settle_steps = 0; // the node steps that decision took (the cost the light walker would have booked)
         if (next && (S.n_tripwire_groups || ((COUNT || PT_LIGHT_SETTLE) && with_light))) {
-            const float4 *nr = wf_rec(W, pt_slot(sh, got));
+            const float4 *nr = wf_rec(W, slot);
             const float4 n0 = nr[0], n1 = nr[1];
             const F3 o = f3(n0.x, n0.y, n0.z), d = f3(n0.w, n1.x, n1.y);
             if (S.n_tripwire_groups) wire = pt_tripwire(S, o, d);
@@ -1023,14 +1041,14 @@ struct PtRoles {
                 settled = reach < PT_LIGHT_SETTLE;
                 if (settled) { // what the walker's end() does with no hit, before the loop's release publishes the path
                     const int depth = (int)(__float_as_uint(reinterpret_cast<const float *>(nr + 3)[3]) & 15u);
-                    float *pdf = reinterpret_cast<float *>(wf_entry(W, pt_slot(sh, got), depth)) + 3;
+                    float *pdf = reinterpret_cast<float *>(wf_entry(W, slot, depth)) + 3;
                     *pdf = *pdf + 0.f / S.n_lights_f;                      // distributions.h:123,273 (+0.f: a -0 sum becomes +0)
                 }
             }
         }
         if constexpr ((FEAT & WF_FEAT_SOURCE) != 0) { // the next sample's first ray (depth 0, no bounce pending) gets the treatment of the slot's first
             if (next && !wire) {
-                const float4 *nr = wf_rec(W, pt_slot(sh, got));
+                const float4 *nr = wf_rec(W, slot);
                 if ((__float_as_uint(reinterpret_cast<const float *>(nr + 3)[3]) & (15u | WF_PENDING_BIT)) == 0u) {
                     const float4 n0 = nr[0], n1 = nr[1];
                     wire = pt_source_exact(S, f3(n0.x, n0.y, n0.z), f3(n0.w, n1.x, n1.y));

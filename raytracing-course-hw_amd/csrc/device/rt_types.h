@@ -119,6 +119,27 @@ struct LightRec {
     float box_hi[3], pad1;         // point with; formed on the host instead of 24 instructions per light hit)
 };
 static_assert(sizeof(LightRec) == 48 + 64 + 32, "LightRec must be 144 bytes");
+// What a LightRec holds after its TriIsect.  The persistent kernel's light walker keeps its own copy of the lights as a pair of arrays, the TriIsect
+// of every light packed (what a light test reads: 48-byte records share no 64-byte line with anything a test does not read) and the LightRest of
+// every light (what a hit reads): record k of the pair is LightRec k of the walker's leaf order, byte for byte.
+struct LightRest {
+    float b[3], c[3];
+    float point_prob;
+    float n3[3], dn1[3], dn2[3];
+    float box_lo[3], pad0;
+    float box_hi[3], pad1;
+};
+static_assert(sizeof(LightRest) == sizeof(LightRec) - sizeof(TriIsect) && sizeof(LightRest) == 96, "LightRest must be the 96 bytes of a LightRec after its TriIsect");
+
+// The persistent pipeline's walkers read their arrays (nodes4, light_walk_nodes4, tri_walk, lights_walk_test / lights_walk_rest) at 32-bit byte offsets from a scalar
+// base, a record's offset formed by a 24-bit multiply (rt_device.h GlobalBytes, record_ofs): at most 2^24 records each — the 24-bit figure index
+// bounds the triangles, hence the lights and the nodes — and every array below 4 GiB (2^24 LightRest are 1.6 GB).  Scene creation checks it.
+#define RT_WALK_MAX_RECORDS (1u << 24)
+inline bool walk_arrays_fit(uint64_t n_tris, uint64_t n_lights, uint64_t n_nodes, uint64_t n_light_nodes) {
+    const uint64_t lim = 1ull << 32;
+    return n_tris <= RT_WALK_MAX_RECORDS && n_lights <= RT_WALK_MAX_RECORDS && n_tris * sizeof(TriIsect) < lim && n_lights * sizeof(LightRest) < lim &&
+           n_nodes * sizeof(GpuNode4Q) < lim && n_light_nodes * sizeof(GpuNode4Q) < lim;
+}
 
 // Node of the reference's own tree with its UNPADDED box (hw8/src/include/bvh.h:9-16), for the reference-exact walks of
 // rt_persistent.h: left == 0 marks a leaf holding the figures (lights) [first, last) of the reference order.
@@ -151,14 +172,15 @@ struct SceneView {
     const GpuNode *light_nodes;    // light BVH in the reference's topology, root = 0
     const LightRec *lights;
     // The persistent kernel's light walker: a tree of the library's own over the lights (GPU-built over their reference leaf boxes) and the light
-    // records in ITS leaf order, pad = light index (position in `lights`) << 1 | last-of-leaf.  == light_nodes / lights with pads rewritten when the
-    // scene has too few lights to bother (then the index is the position).
+    // records in ITS leaf order (lights_walk_test / lights_walk_rest), pad = light index (position in `lights`) << 1 | last-of-leaf.  == light_nodes /
+    // lights with pads rewritten when the scene has too few lights to bother (then the index is the position).
     const GpuNode *light_walk_nodes;
     const float *tripwires;        // host/scene_prep.h: boxes a ray must not pierce unnoticed (8 floats per record: groups, then members); rt_exact.h pt_tripwire
     uint32_t n_tripwire_groups;
     const GpuNode4Q *nodes4, *light_walk_nodes4;  // `nodes` / `light_walk_nodes` four wide on the 16-bit grid: what the persistent pipeline's walkers read
     NodeGrid grid;                 // covers both trees' root boxes and the camera (every ray origin lies inside it)
-    const LightRec *lights_walk;
+    const TriIsect *lights_walk_test;   // the walker's light records as a pair of arrays (LightRest above): what a test reads ...
+    const LightRest *lights_walk_rest;  // ... and what a hit reads
     const uint16_t *light_sep;     // range-minimum table of the separation depths of neighbouring lights (scene_prep.h)
     const GpuMaterial *materials;
     const GpuImage *images;

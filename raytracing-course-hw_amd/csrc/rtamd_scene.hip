@@ -263,8 +263,9 @@ int create_hw8(const rt_scene_desc *desc, std::unique_ptr<rt_scene> &s, rt_scene
     V.tripwires = V.n_tripwire_groups ? up(P.tripwires) : nullptr;
     V.lights = up(P.lights);
     uint32_t n_light_walk_nodes = 0;
-    {   // the light walker's own tree (rt_types.h: light_walk_nodes / lights_walk)
+    {   // the light walker's own tree (rt_types.h: light_walk_nodes / lights_walk_test, lights_walk_rest)
         const uint32_t nl = (uint32_t)P.lights.size();
+        const LightRec *ordered = nullptr;       // the records in the walker's leaf order
         std::vector<LightRec> tagged = P.lights; // pad = light index << 1 | last-of-leaf (of the REFERENCE topology for now)
         for (uint32_t i = 0; i < nl; i++) tagged[i].isect.pad = (i << 1) | (tagged[i].isect.pad ? 1u : 0u);
         if (nl >= 64 && !env_flag("RTAMD_HOST_LIGHT_BVH")) {
@@ -272,7 +273,7 @@ int create_hw8(const rt_scene_desc *desc, std::unique_ptr<rt_scene> &s, rt_scene
             OwnedDev d_tagged(upload(tagged, up.bytes)); // device_bytes: stands for the gathered copy of the same size, which the scene keeps
             OwnedDev d_lbox(upload(P.light_walk_box, scratch));
             const DeviceTree lt = build_leaf_ordered(s.get(), (const float *)d_lbox.p, (const LightRec *)d_tagged.p, nl, P.box_pad, 16, // the hits of a walk share its 24-entry column with the node stack
-                                                     11, true, V.lights_walk);                                                        // word 11 = TriIsect::pad
+                                                     11, true, ordered);                                                        // word 11 = TriIsect::pad
             V.light_walk_nodes = lt.nodes;
             up.bytes += (uint64_t)lt.n_nodes * sizeof(GpuNode);
             s->light_walk_depth = lt.depth;
@@ -280,9 +281,22 @@ int create_hw8(const rt_scene_desc *desc, std::unique_ptr<rt_scene> &s, rt_scene
         } else {
             V.light_walk_nodes = V.light_nodes;
             n_light_walk_nodes = (uint32_t)P.light_nodes.size();
-            V.lights_walk = up(tagged);
+            ordered = up(tagged);
             s->light_walk_depth = P.light_bvh_depth;
         }
+        // The walker reads the records as a pair of arrays (rt_types.h LightRest), which together are the bytes of the one: the leaf-ordered records
+        // of either branch, the scene's newest allocation, make way for them.
+        OwnedDev whole(s->allocations.back());
+        s->allocations.pop_back();
+        const size_t n_rec = nl ? nl : 1u; // (no lights: the one zeroed dummy record of the upload)
+        char *pair = nullptr;
+        HIP_CHECK(hipMalloc((void **)&pair, n_rec * sizeof(LightRec)));
+        s->allocations.push_back(pair);
+        char *rest = pair + n_rec * sizeof(TriIsect);
+        HIP_CHECK(hipMemcpy2D(pair, sizeof(TriIsect), ordered, sizeof(LightRec), sizeof(TriIsect), n_rec, hipMemcpyDeviceToDevice));
+        HIP_CHECK(hipMemcpy2D(rest, sizeof(LightRest), (const char *)ordered + sizeof(TriIsect), sizeof(LightRec), sizeof(LightRest), n_rec, hipMemcpyDeviceToDevice));
+        V.lights_walk_test = (const TriIsect *)pair;
+        V.lights_walk_rest = (const LightRest *)rest;
     }
     V.materials = up(P.materials);
     V.images = up(P.images);
@@ -297,6 +311,8 @@ int create_hw8(const rt_scene_desc *desc, std::unique_ptr<rt_scene> &s, rt_scene
     }
     if (env_flag("RTAMD_NO_LAST_LEVEL_SHORTCUT")) V.last_level_emission_only = 0;
     V.env_image = P.env_image;
+    if (!walk_arrays_fit(desc->n_triangles, V.n_lights, n_nodes, n_light_walk_nodes)) // (a tree has no more wide nodes than two-box nodes)
+        return fail(RT_ERR_LIMIT, "the scene's triangles, lights or tree nodes do not fit the walkers' 32-bit offsets (2^24 records, 4 GiB per array)");
     make_walk_nodes(s.get(), V.cam_pos, V.nodes, n_nodes, V.light_walk_nodes, n_light_walk_nodes, n_light_walk_nodes != 0,
                     V.grid, V.nodes4, V.light_walk_nodes4, up.bytes);
     report_trees(s.get(), desc, P, V.n_lights, n_nodes, bvh_depth);

@@ -15,6 +15,7 @@
 #include "host/fold_nodes.h"
 #include "host/hip_check.h"
 #include "host/rt_guard.h"
+#include "host/rt_scene.h"
 #include "host/scene_prep.h"
 #include <cstdio>
 #include <cstring>
@@ -534,6 +535,21 @@ int rtt_fold_nodes(const void *nodes, uint32_t n, const float *grid_box, void *o
         for (int k = 0; k < 3; k++) { grid_out[k] = G.lo[k]; grid_out[3 + k] = G.step[k]; grid_out[6 + k] = G.istep[k]; }
         return (int)wide.size();
     } catch (...) { return -1; }
+}
+// walk_arrays_fit (rt_types.h), the bound that scene creation answers RT_ERR_LIMIT for, on counts of the test's own (no GPU needed): 1 = they fit
+int rtt_walk_arrays_fit(uint64_t n_tris, uint64_t n_lights, uint64_t n_nodes, uint64_t n_light_nodes) { return rtamd::walk_arrays_fit(n_tris, n_lights, n_nodes, n_light_nodes) ? 1 : 0; }
+// The light records of an hw8 scene as its persistent light walker reads them, the pair of arrays of rt_types.h LightRest, and the lights in the
+// reference's order: n_lights records each into test_out (48 bytes each), rest_out (96) and lights_out (144), room for `cap` of them.
+// Returns n_lights, -1 on error.
+int rtt_light_walk_arrays(const rt_scene *scene, void *test_out, void *rest_out, void *lights_out, uint32_t cap) {
+    if (!scene || scene->flavor != RT_INTEGRATOR_HW8) return -1;
+    const rtamd::SceneView &V = scene->view;
+    const size_t n = V.n_lights;
+    if (n > cap) return -1;
+    if (n && (hipMemcpy(test_out, V.lights_walk_test, n * sizeof(rtamd::TriIsect), hipMemcpyDeviceToHost) != hipSuccess ||
+              hipMemcpy(rest_out, V.lights_walk_rest, n * sizeof(rtamd::LightRest), hipMemcpyDeviceToHost) != hipSuccess ||
+              hipMemcpy(lights_out, V.lights, n * sizeof(rtamd::LightRec), hipMemcpyDeviceToHost) != hipSuccess)) return -1;
+    return (int)n;
 }
 // shard_slot_to_frame_slot (rt_device.h) on the host (no GPU needed) for the n_slots slots of shard `shard` of `count` of a width x height frame
 // in square tiles: frame_slot[s] = the slot in frame order, in_frame[s] = 0 for a slot in a padding sub-tile.
