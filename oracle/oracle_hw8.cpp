@@ -660,6 +660,10 @@ void rto_sample_texture(int w, int h, const uint8_t *data, float tx, float ty, i
     V3 r = sample_texture(tx, ty, Tex{w, h, data}, srgb != 0);
     out3[0] = r.x; out3[1] = r.y; out3[2] = r.z;
 }
+void rto_apply_normal_map(const float *sn3, const float *tan4, const float *sample3, float *out3) {
+    V3 r = apply_normal_map(v3(sn3), v3(tan4), tan4[3], v3(sample3));
+    out3[0] = r.x; out3[1] = r.y; out3[2] = r.z;
+}
 // RNG known-answer helper: seed, then n_u uniforms followed by n_n normals.
 void rto_rng_kat(uint32_t seed, int n_u, int n_n, float *out) {
     rng_t rng(seed); U01 u01(0.0, 1.0); N01 n01(0.0, 1.0);

@@ -1,9 +1,9 @@
 // ORACLE TOOLING — builds ONLY in a container that has /root/reference; output goes to oracle/_ref/.
 // Harness around the reference's own hw8 sources (compiled where they lie, nothing copied):
 //   /root/reference/hw8/src/primitives.cpp, color.cpp and the header-only bvh.h, distributions.h,
-//   material.h.  hw8/src/scene.cpp and sceneio.cpp are NOT buildable here (they include the absent
-//   stb_image.h / rapidjson headers), so getColor/getPixel of hw8 are pinned through the hw7
-//   harness (ref_hw7_scene.cpp) plus the per-function entry points below.
+//   material.h.  hw8/src/sceneio.cpp is NOT buildable here (it needs the absent rapidjson headers and image decoders).
+//   hw8/src/scene.cpp is: ref_hw8_scene.cpp builds it, and pins getColor / getPixel of hw8 with its texture layer.  The
+//   per-function entry points of the layers below scene.cpp are here.
 #include "bvh.h"
 #include "distributions.h"
 #include "material.h"

@@ -142,6 +142,24 @@ __global__ void k_tonemap(const float *in, uint8_t *out, size_t n) {
     size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
     if (i < n) out[i] = tonemap1(in[i]);
 }
+// The texture layer (rt_device.h sample_texture / load_texel / apply_normal_map), one lane per case.  k_sample_texture taps the images of a
+// scene made through the public API, so the texel array, the descriptors and the sRGB table are scene preparation's: slot = an image slot,
+// -1 = the environment map; form 0 = the overload that loads the descriptor by slot, 1 = the one that is handed the descriptor.
+__global__ void k_sample_texture(rtamd::SceneView S, int form, const int32_t *slot, const float *uv, const int32_t *srgb, float *out, size_t n) {
+    size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int s = slot[i] < 0 ? S.env_image : slot[i];
+    const F3 r = form == 0 ? sample_texture(S, s, uv[2 * i], uv[2 * i + 1], srgb[i] != 0)
+                           : sample_texture(S, S.images[s], uv[2 * i], uv[2 * i + 1], srgb[i] != 0);
+    out[3 * i] = r.x; out[3 * i + 1] = r.y; out[3 * i + 2] = r.z;
+}
+__global__ void k_apply_normal_map(const float *in, float *out, size_t n) { // in: sn 3, tangent 3, tanw, sample 3
+    size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float *p = in + 10 * i;
+    const F3 r = apply_normal_map(f3(p), f3(p + 3), p[6], f3(p + 7));
+    out[3 * i] = r.x; out[3 * i + 1] = r.y; out[3 * i + 2] = r.z;
+}
 // vndf_disk_point on the stream of seed0 + i: u = the two uniforms the call consumed (from a copy of the engine), t = (t1, t2), cs = the
 // device libm's cos and sin of the angle in double, which the call narrows (for the census of the test)
 __global__ void k_disk_point(uint32_t seed0, float *u, float *t, double *cs, size_t n) {
@@ -831,6 +849,23 @@ int rtt_tonemap(const float *in, uint8_t *out, size_t n) {
     return hipDeviceSynchronize() == hipSuccess && b_out.back(out) ? 0 : -2;
 }
 // seeds seed0 .. seed0 + n - 1 (n < 2^31): u and t n x 2 floats, cs n x 2 doubles
+// The texture layer (k_sample_texture, k_apply_normal_map above).  The scene is an hw8 scene WITH an environment map, which scene
+// preparation puts behind the images: its slot is the number of images, and every slot[i] must lie in [-1, that number).
+int rtt_sample_texture(const rt_scene *scene, int form, const int32_t *slot, const float *uv2, const int32_t *srgb, float *out3, size_t n) {
+    if (!scene || scene->flavor != RT_INTEGRATOR_HW8 || scene->view.env_image < 0 || form < 0 || form > 1 || n == 0) return -1;
+    for (size_t i = 0; i < n; i++) if (slot[i] < -1 || slot[i] >= scene->view.env_image) return -1;
+    HookBuf b_slot(slot, n * 4), b_uv(uv2, n * 8), b_srgb(srgb, n * 4), b_out(nullptr, n * 12);
+    if (!b_slot.good || !b_uv.good || !b_srgb.good || !b_out.good) return -2;
+    hipLaunchKernelGGL(k_sample_texture, hook_grid(n), dim3(256), 0, 0, scene->view, form, b_slot.as<int32_t>(), b_uv.as<float>(), b_srgb.as<int32_t>(), b_out.as<float>(), n);
+    return hipDeviceSynchronize() == hipSuccess && b_out.back(out3) ? 0 : -2;
+}
+int rtt_apply_normal_map(const float *in10, float *out3, size_t n) {
+    if (n == 0) return -1;
+    HookBuf b_in(in10, n * 40), b_out(nullptr, n * 12);
+    if (!b_in.good || !b_out.good) return -2;
+    hipLaunchKernelGGL(k_apply_normal_map, hook_grid(n), dim3(256), 0, 0, b_in.as<float>(), b_out.as<float>(), n);
+    return hipDeviceSynchronize() == hipSuccess && b_out.back(out3) ? 0 : -2;
+}
 int rtt_disk_point(uint32_t seed0, size_t n, float *u, float *t, double *cs) {
     if (n == 0 || n >= (1u << 31)) return -1;
     HookBuf b_u(nullptr, n * 8), b_t(nullptr, n * 8), b_cs(nullptr, n * 16);

@@ -3,7 +3,8 @@ Run:  python tests/golden/make_goldens.py      (after `make -C oracle`)
       python tests/golden/make_goldens.py orders      only pins_oracle_orders.npz, which comes from the oracle itself
       python tests/golden/make_goldens.py shading     only pins_shading_edges.npz
       python tests/golden/make_goldens.py intersection     only pins_intersection_edges.npz
-      python tests/golden/make_goldens.py analytic     only pins_analytic_edges.npz"""
+      python tests/golden/make_goldens.py analytic     only pins_analytic_edges.npz
+      python tests/golden/make_goldens.py texture     only pins_texture_edges.npz and pins_hw8_paths.npz"""
 import ctypes as C
 import os
 import sys
@@ -117,6 +118,33 @@ def main():
     save_shading_edges()
     save_intersection_edges()
     save_analytic_edges()
+    save_texture_edges()
+    save_hw8_paths()
+
+
+def save_texture_edges():
+    """The texture layer at its edges (tests/texture_cases.py) through the static sampleTexture and applyNormalMaps of the reference's own
+    hw8 scene.cpp, and the reference's taps at the camera set's hits on the scene texture_edges.  Outputs only, but for the texcoords of those
+    hits, which say which question each of those taps answers."""
+    import texture_cases
+    out = texture_cases.evaluate("reference")
+    hits = texture_cases.edge_hits()
+    out["edge_hit_uv"] = np.ascontiguousarray(hits["texcoord"]).view(np.uint32)
+    out["edge_hit_taps"] = texture_cases.edge_taps(texture_cases.ref_scene_lib().ref8_sample_texture, hits)
+    np.savez_compressed(os.path.join(HERE, "pins_texture_edges.npz"), **out)
+    print("texture edges", {k: v.shape for k, v in out.items()})
+
+
+def save_hw8_paths():
+    """Float radiance of the reference's own hw8 Scene::getPixel (scene.cpp with its textures, normal maps and environment map) on the
+    scenes of tests/test_texture_pins.py PATH_CASES."""
+    import surface_cases
+    import test_texture_pins
+    out = {}
+    for key, (name, depth) in test_texture_pins.PATH_CASES.items():
+        out[key], _, _ = oracle_lib.Ref8Scene(surface_cases.scene_data(name)).render(*test_texture_pins.FRAME, ray_depth=depth)
+        print(key, out[key].shape, float(np.nanmean(out[key])))
+    np.savez_compressed(os.path.join(HERE, "pins_hw8_paths.npz"), **out)
 
 
 def save_analytic_edges():
@@ -194,5 +222,8 @@ if __name__ == "__main__":
         save_intersection_edges()
     elif sys.argv[1:] == ["analytic"]:
         save_analytic_edges()
+    elif sys.argv[1:] == ["texture"]:
+        save_texture_edges()
+        save_hw8_paths()
     else:
         main()

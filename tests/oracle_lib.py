@@ -48,6 +48,7 @@ def lib():
         L.rto_hw8_brdf.argtypes = [C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_void_p]
         L.rto_tonemap.argtypes = [C.c_void_p, C.c_void_p]
         L.rto_sample_texture.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_float, C.c_float, C.c_int, C.c_void_p]
+        L.rto_apply_normal_map.argtypes = [C.c_void_p] * 4
         L.rto_rng_kat.argtypes = [C.c_uint32, C.c_int, C.c_int, C.c_void_p]
         L.rto_rng_kat_normals_first.argtypes = [C.c_uint32, C.c_int, C.c_int, C.c_void_p]
         _lib = L
@@ -180,6 +181,34 @@ class Ref7:
         rgb = np.zeros((h, w, 3), np.float32)
         rgb8 = np.zeros((h, w, 3), np.uint8)
         self.L.ref7_render(self._h, width, height, samples, ray_depth, x0, y0, w, h, rgb.ctypes.data, rgb8.ctypes.data, threads)
+        return rgb, rgb8, None
+
+
+class Ref8Scene:
+    """The reference's own hw8 integrator with its texture layer (oracle/_ref/libref_hw8_scene.so: hw8 scene.cpp/primitives.cpp/color.cpp)."""
+
+    def __init__(self, scene_data):
+        p = ref_path("libref_hw8_scene.so")
+        if p is None:
+            raise FileNotFoundError("oracle/_ref/libref_hw8_scene.so not built")
+        L = C.CDLL(p)
+        L.ref8s_create.restype = C.c_void_p
+        L.ref8s_create.argtypes = [C.POINTER(rt.rt_scene_desc)]
+        L.ref8s_destroy.argtypes = [C.c_void_p]
+        L.ref8s_render.argtypes = [C.c_void_p] + [C.c_int] * 8 + [C.c_void_p, C.c_void_p, C.c_int]
+        self.L, self.data = L, scene_data
+        self._h = L.ref8s_create(C.byref(scene_data.desc))
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            self.L.ref8s_destroy(self._h)
+            self._h = None
+
+    def render(self, width, height, samples, ray_depth=0, rect=None, threads=0):
+        x0, y0, w, h = rect if rect else (0, 0, width, height)
+        rgb = np.zeros((h, w, 3), np.float32)
+        rgb8 = np.zeros((h, w, 3), np.uint8)
+        self.L.ref8s_render(self._h, width, height, samples, ray_depth, x0, y0, w, h, rgb.ctypes.data, rgb8.ctypes.data, threads)
         return rgb, rgb8, None
 
 

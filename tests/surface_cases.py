@@ -56,12 +56,91 @@ def _soup(name):
                         tsrc, images, sd.camera, (0.05, 0.07, 0.1), None)
 
 
+# ---- texture_edges: camera-facing quads, one material and one uv layout each, dealt by this table ---------------------------------
+# name: (uv of the quad's four corners (x0y0, x1y0, x1y1, x0y1), or one uv per triangle when "constant"; {kind: image}; tangent w;
+# "parallel" = the tangent is the normal; emission factor).  Images are named: a texture_cases size, or a constant colour.
+def _uv_box(u0, v0, u1, v1):
+    return ((u0, v0), (u1, v0), (u1, v1), (u0, v1))
+
+
+EDGE_ROWS = (
+    ("uv_on_0_and_1", _uv_box(0, 0, 1, 1), {"base_color_texture": (3, 5)}, 1, False, 0),
+    ("uv_negative", _uv_box(-3, -3, -2, -2), {"base_color_texture": (17, 13), "metallic_roughness_texture": (2, 2)}, 1, False, 0),
+    ("uv_times_1e4", _uv_box(0, 0, 1e4, 1e4), {"base_color_texture": (32, 32), "metallic_roughness_texture": (3, 5)}, 1, False, 0),
+    ("uv_constant", "constant", {"base_color_texture": (2, 2), "emissive_texture": (3, 5)}, 1, False, 0.5),
+    ("image_1x1", _uv_box(-0.5, -0.5, 1.5, 1.5), {"base_color_texture": (1, 1), "metallic_roughness_texture": (1, 1)}, 1, False, 0),
+    ("image_1x7", _uv_box(0, 0, 1, 1), {"base_color_texture": (1, 7)}, 1, False, 0),
+    ("image_7x3", _uv_box(0, 0, 2, 2), {"base_color_texture": (7, 3), "normal_texture": "up"}, 1, False, 0),
+    ("image_255x3", _uv_box(0, 0, 1, 1), {"base_color_texture": (255, 3), "metallic_roughness_texture": (255, 3)}, 1, False, 0),
+    ("normal_128_128_255", _uv_box(0, 0, 1, 1), {"normal_texture": (128, 128, 255)}, 1, False, 0),
+    ("normal_grey", _uv_box(0, 0, 3, 3), {"normal_texture": "grey"}, 1, False, 0),
+    ("tangent_w_minus_1", _uv_box(0, 0, 1, 1), {"normal_texture": "up", "base_color_texture": (7, 1)}, -1, False, 0),
+    ("tangent_parallel", _uv_box(0, 0, 1, 1), {"normal_texture": "up"}, 1, True, 0),
+    ("emitter", _uv_box(0, 0, 1, 1), {"emissive_texture": (7, 1)}, 1, False, 6),
+    ("plain", _uv_box(0, 0, 1, 1), {}, 1, False, 0),
+    ("plain_emitter", _uv_box(0, 0, 1, 1), {}, 1, False, 3),
+    ("all_four", _uv_box(-1, -1, 2, 2), {"base_color_texture": (17, 13), "emissive_texture": (32, 32), "metallic_roughness_texture": (7, 3),
+                                         "normal_texture": "up"}, 1, False, 1),
+)
+
+
+def _edge_image(name, rng):
+    import texture_cases
+    if name == "up":                        # a normal map that mostly points up, as _soup's
+        return np.clip(rng.integers(0, 256, (5, 5, 3)) // 4 + np.array([96, 96, 180]), 0, 255).astype(np.uint8)
+    if name == "grey":                      # 127 and 128 in turn: 2 * sample - 1 is about +-0.004 per channel, and crosses 0 between texels
+        g = np.where((np.arange(16).reshape(4, 4) + np.arange(4)[:, None]) % 2, 127, 128)
+        return np.repeat(g[:, :, None], 3, axis=2).astype(np.uint8)
+    if len(name) == 3:
+        return np.tile(np.array(name, np.uint8), (2, 2, 1))
+    return texture_cases.images()[1 + texture_cases.IMAGE_SIZES.index(name)]
+
+
+def _texture_edges():
+    """A 4 x 4 grid of quads that fills the 48 x 32 frame, each a little tilted and offset in depth so that bounces meet other quads."""
+    rng = np.random.default_rng(213)
+    cam = rt.rt_camera()
+    cam.position, cam.right, cam.up, cam.forward, cam.fov_y = (0, 0, 6), (1, 0, 0), (0, 1, 0), (0, 0, -1), 0.9
+    pos, uvs, nrm, tan, mat_idx, mats, images, tsrc = [], [], [], [], [], [], [], []
+    for q, (name, uv, kinds, tanw, parallel, emit) in enumerate(EDGE_ROWS):
+        cx, cy = -3.3 + 2.2 * (q % 4), -2.1 + 1.4 * (q // 4)
+        ax, ay = rng.uniform(-0.35, 0.35, 2)
+        rot = np.array([[np.cos(ay), 0, np.sin(ay)], [0, 1, 0], [-np.sin(ay), 0, np.cos(ay)]]) @ \
+            np.array([[1, 0, 0], [0, np.cos(ax), -np.sin(ax)], [0, np.sin(ax), np.cos(ax)]])
+        centre = np.array([cx, cy, rng.uniform(-0.6, 0.6)])
+        corner = [centre + rot @ np.array([sx * 1.08, sy * 0.68, 0]) for sx, sy in ((-1, -1), (1, -1), (1, 1), (-1, 1))]
+        n, t = np.float32(rot @ np.array([0, 0, 1.0])), np.float32(rot @ np.array([1.0, 0, 0]))
+        if parallel:
+            t = n
+        for tri, const in (((0, 1, 2), (0.25, 0.75)), ((0, 2, 3), (-1.5, 3.0))):
+            pos.append(np.concatenate([corner[k] for k in tri]))
+            uvs.append(np.tile(const, 3) if uv == "constant" else np.concatenate([uv[k] for k in tri]))
+            nrm.append(np.tile(n, 3))
+            tan.append(np.tile(np.append(t, tanw), 3))
+            mat_idx.append(q)
+        m = rt.rt_material()
+        m.base_color = tuple(rng.uniform(0.3, 1, 3).astype(np.float32))
+        m.emission = (emit, emit * 0.8, emit * 0.6)
+        m.metallic_factor, m.roughness_factor = float(np.float32(rng.uniform(0, 1))), float(np.float32(rng.uniform(0.1, 1)))
+        for kind in KINDS:
+            setattr(m, kind, -1)
+            if kind in kinds:
+                images.append(_edge_image(kinds[kind], rng))
+                tsrc.append(len(images) - 1)
+                setattr(m, kind, len(tsrc) - 1)
+        mats.append(m)
+    return rt.SceneData(np.float32(pos), np.float32(uvs), np.float32(nrm), np.float32(tan), np.uint32(mat_idx), mats, tsrc, images, cam,
+                        (0.3, 0.35, 0.4), None)
+
+
 _gltf = lambda name: rt.load_gltf(os.path.join(pin_cases.SCENES, "hw8_sphere", name + ".gltf"))
 BUILDERS = {"sphere": lambda: _gltf("sphere"), "sphere_emissive": lambda: _gltf("sphere_emissive"), "sphere_roughness": lambda: _gltf("sphere_roughness"),
             "soup_a": lambda: _soup("soup_a"), "soup_b": lambda: _soup("soup_b"),
             "sphere_emissive_env": lambda: _with(_gltf("sphere_emissive"), env_map()),
             "sphere_env": lambda: _with(_gltf("sphere"), env_map()),
-            "soup_a_env": lambda: _with(_soup("soup_a"), env_map())}
+            "soup_a_env": lambda: _with(_soup("soup_a"), env_map()),
+            "sphere_roughness_env": lambda: _with(_gltf("sphere_roughness"), env_map()), "soup_b_env": lambda: _with(_soup("soup_b"), env_map()),
+            "texture_edges": _texture_edges}
 
 
 @functools.lru_cache(maxsize=None)
