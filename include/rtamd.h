@@ -716,7 +716,7 @@ int rt_bake(rt_scene *scene, const rt_bake_point *points, size_t n_points, const
  * Refusals   before any device work.  RT_ERR_INVALID_ARG: null arguments, struct_size, reserved words, flags other than
  *          RT_QUERY_DEVICE_POINTERS (alignments as rt_trace_paths / rt_bake), a host engine outside 1 .. 2^31-2 (the record is named).
  *          RT_ERR_LIMIT: ray_depth > 16, streams > 64, n_points * streams >= 2^31, samples / streams >= 2^25.  RT_ERR_UNSUPPORTED:
- *          RT_BAKE_SH9 (rt_bake serves it), hw6 and .txt scenes, and whatever keeps the persistent hw8 kernel from the scene
+ *          RT_BAKE_SH9 (rt_bake serves it, and rt_render_probes below at this speed), hw6 and .txt scenes, and whatever keeps the persistent hw8 kernel from the scene
  *          (RTAMD_KERNEL=wavefront|mega, trees beyond its stack columns): there is no fallback, as with rt_accum_create.  n = 0: RT_OK.
  * stats    rt_query_stats: rays = n, invalid_rays, exact_walks = exact closest hits + exact light sums of the launches, kernel_ms =
  *          the render launches' (the pack and unpack launches are in total_ms), launches, reference_exact.  rt_bake_stats: points,
@@ -736,6 +736,49 @@ int rt_render_paths(rt_scene *scene, const rt_ray *rays, rt_rng *rng /* in and o
                     uint32_t flags, float *out_rgb /* n*3 */, rt_query_stats *stats /* nullable */);
 int rt_render_bake(rt_scene *scene, const rt_bake_point *points, size_t n_points, const rt_bake_params *params,
                    rt_rng *rng /* n_points*streams, [i*streams+k], in and out */, float *out /* n_points*3 */, rt_bake_stats *stats /* nullable */);
+
+/* ---- rt_render_probes: SH9 probe bakes at render speed ---------------------------------------------------------------------------
+ * rt_bake (RT_BAKE_SH9) through the persistent render kernel, the way rt_render_bake serves irradiance.  What does not fit the
+ * kernel's path record -- 27 accumulators and the sample's first direction -- lives beside the slots' state, 120 bytes per slot
+ * (device/rt_path_source.h), and the kernel is a third source kernel of its own: rt_render_paths' and rt_render_bake's are the code
+ * they were, and rt_render_bake keeps refusing RT_BAKE_SH9.  ABI version 6 still.
+ *
+ * Contract   on a scene whose renders and queries report reference_exact = 1, out and rng are bit for bit rt_bake's for the same
+ *          arguments with mode = RT_BAKE_SH9 (the referee, tests/test_gpu_render_probes.py).  The same expressions: o = p, d =
+ *          normalize of three normal draws, acc[m][c] = acc[m][c] + (Y_m(d) * L[c]) with the nine Y_m as rt_bake spells them, one
+ *          rounding per operation, d the sample's first direction; out = (float)(4 pi / (double)samples) * (((acc_0 + acc_1) + acc_2)
+ *          ...) over the point's streams, through the queries' rule for floats (a NaN leaves with its sign bit set).  An engine leaves
+ *          with saved = 0 whenever has_saved is 0, `reserved` is handed through.  On a scene with reference_exact = 0 the call is
+ *          served, the stats say 0 and equality with rt_bake is NOT promised (as rt_render_bake).
+ * Invalid points   rt_bake's SH9 rule: a NaN or an infinity in p, or any of the point's K engines outside 1 .. 2^31-2.  n is not read:
+ *          n == 0 or a NaN n is a valid point.  An invalid point answers 27 zeros, keeps all its engines and is counted once in
+ *          invalid_points.  Host engine arrays are checked before any launch (RT_ERR_INVALID_ARG, the record named); device arrays are
+ *          judged on the device.
+ * First rays   a probe's ray starts at p itself, no epsilon offset, and p may lie anywhere: every sample's first ray is classified
+ *          as rt_render_paths classifies a caller's ray, and what the walkers were not derived for (an origin outside their node
+ *          grid, ...) is walked by the exact role and counted in exact_walks.  Too cautious costs speed only.
+ * Refusals   before any device work, each naming its field: rt_render_bake's (null arguments, struct_size, reserved words, flags
+ *          other than RT_QUERY_DEVICE_POINTERS, alignments, host engines; RT_ERR_LIMIT: ray_depth > 16, streams > 64, n_points *
+ *          streams >= 2^31, samples / streams >= 2^25); RT_ERR_INVALID_ARG: mode = RT_BAKE_IRRADIANCE (rt_render_bake serves it);
+ *          RT_ERR_UNSUPPORTED: hw6 and .txt scenes and whatever keeps the persistent hw8 kernel from the scene
+ *          (RTAMD_KERNEL=wavefront|mega, trees beyond its stack columns): no fallback.  n_points = 0: RT_OK, no launch.
+ * stats    as rt_render_bake: points, invalid_points, paths, exact_walks, times, launches (three per chunk and phase: pack, render,
+ *          unpack), reference_exact; rounds = ray_slots = live_ray_slots = 0.
+ * Memory   chunks as rt_render_bake's (2,073,600 slots, whole points; RTAMD_QUERY_CHUNK lowers it).  Per slot of a chunk 24 bytes of
+ *          state and 120 bytes of accumulators and first direction: 144 bytes, 299 MB for a full chunk, 38 MB for 4,096 probes of 64
+ *          streams; with host arrays 40 bytes per slot (engines, points) and 108 bytes of answer per point beside them.  Kept in the
+ *          scene's source staging: not part of rt_scene_info.device_bytes, freed with the scene.  The call only reads the scene.
+ * Measured on one MI355X, synth_room_v1, device pointers, depth 6, kernel time, five repeats alternating with the referee in one
+ *          process (profiles/r34_render_probes.txt): 4,096 probes x 4,096 samples, K = 64: 63.4 ms (62.8 .. 63.4)
+ *          = 265 Mpaths/s against rt_bake's 365.1 ms (364.9 .. 365.4), 5.8 x, the referee's bits; rt_render_bake irradiance on the
+ *          same points 62.2 ms: the SH mode costs 1.2 ms.  2,073,600 texels x 16 samples, K = 1 (one full chunk): 79.3 ms (78.4 .. 81.1)
+ *          = 419 Mpaths/s against 747.0 ms (745.0 .. 748.2), 9.4 x; irradiance 78.8 ms.  In that run ONE of the 2,073,600 points
+ *          differs from rt_bake: a path on which the persistent kernel itself (rt_render_paths, too) parts from the reference on its
+ *          sixth ray, 1 in 33 million, located in the profile file and not fixed.  The kernel: 89 VGPRs, no scratch, five waves per
+ *          SIMD, 31,680 bytes of LDS; every other kernel is, instruction for instruction, the one it was. */
+int rt_render_probes(rt_scene *scene, const rt_bake_point *points, size_t n_points, const rt_bake_params *params,
+                     rt_rng *rng /* n_points*streams, [i*streams+k], in and out */, float *out /* n_points*27, [m][c] */,
+                     rt_bake_stats *stats /* nullable */);
 
 /* ---- denoised previews: a variance-guided edge-avoiding filter on the guide images -------------------------------------------
  * What consumes rt_render_guides' planes: a noisy frame of few samples in, a usable preview out.  An a-trous wavelet filter (five

@@ -184,7 +184,7 @@ ABI_SYMBOLS = ["rt_abi_version", "rt_last_error", "rt_scene_create", "rt_scene_d
                "rt_multi_noise_reset", "rt_multi_noise_batches", "rt_multi_noise_estimate", "rt_multi_noise_destroy", "rt_query_closest",
                "rt_query_light_pdf", "rt_query_surface", "rt_query_environment", "rt_camera_rays", "rt_render_guides",
                "rt_query_occluded", "rt_rng_seed", "rt_query_scatter", "rt_query_bsdf", "rt_trace_paths", "rt_bake_rays", "rt_bake",
-               "rt_render_paths", "rt_render_bake"]
+               "rt_render_paths", "rt_render_bake", "rt_render_probes"]
 # The preview filter's two, which the header declares `extern int`: the list above and the family lists of the tests are closed sets
 # of the header's plain prototypes (tests/test_abi_and_host.py, tests/test_accum_host.py), and rt_accum_denoise is no rt_accum_* of theirs.
 DENOISE_SYMBOLS = ["rt_denoise", "rt_accum_denoise"]
@@ -261,6 +261,7 @@ lib.rt_bake_rays.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c
 lib.rt_bake.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(rt_bake_params), C.c_void_p, C.c_void_p, C.POINTER(rt_bake_stats)]
 lib.rt_render_paths.argtypes = lib.rt_trace_paths.argtypes
 lib.rt_render_bake.argtypes = lib.rt_bake.argtypes
+lib.rt_render_probes.argtypes = lib.rt_bake.argtypes
 lib.rt_denoise.argtypes = [C.c_void_p, C.POINTER(rt_denoise_params)] + [C.c_void_p] * 8 + [C.POINTER(rt_denoise_stats)]
 lib.rt_accum_denoise.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(rt_denoise_params), C.c_void_p, C.c_void_p, C.POINTER(rt_denoise_stats)]
 
@@ -1042,4 +1043,22 @@ class Scene(_Handle):
         st = _bake_stats()
         params = make_bake_params(samples, streams, mode, ray_depth, RT_QUERY_DEVICE_POINTERS)
         _check(lib.rt_render_bake(self._h, points_ptr, n_points, C.byref(params), rng_ptr, out_ptr, C.byref(st)))
+        return st
+
+    def render_probes(self, points, rng, samples, streams=1, ray_depth=0):
+        """bake in RT_BAKE_SH9 through the persistent render kernel (rt_render_probes): the same coefficients and engines as bake on a
+        scene whose renders report reference_exact = 1.  Returns ((n, 9, 3) float32, rt_bake_stats)."""
+        points = _records(points, BAKE_POINT_DTYPE, None, "points")
+        n = points.shape[0]
+        rng = _engines(rng, n * max(1, streams))
+        out = np.zeros((n, 9, 3), dtype=np.float32)
+        st = _bake_stats()
+        params = make_bake_params(samples, streams, RT_BAKE_SH9, ray_depth, 0)
+        _check(lib.rt_render_probes(self._h, points.ctypes.data, n, C.byref(params), rng.ctypes.data, out.ctypes.data, C.byref(st)))
+        return out, st
+
+    def render_probes_device(self, points_ptr, rng_ptr, n_points, out_ptr, samples, streams=1, ray_depth=0):
+        st = _bake_stats()
+        params = make_bake_params(samples, streams, RT_BAKE_SH9, ray_depth, RT_QUERY_DEVICE_POINTERS)
+        _check(lib.rt_render_probes(self._h, points_ptr, n_points, C.byref(params), rng_ptr, out_ptr, C.byref(st)))
         return st

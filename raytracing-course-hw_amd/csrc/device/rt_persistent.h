@@ -971,7 +971,7 @@ struct PtRoles {
             if (!PtSource<FEAT>::first(S, R, gslot, rng, o, d)) {
                 // no path: the state stays as it is, and the record says "every sample is in" to a later phase of the launch (resumed_sample)
                 r[3] = make_float4(0.f, 0.f, 0.f, __uint_as_float(wf_pack(0, false, (uint32_t)R.samples)));
-                if (P.counters && pt_source_counts(R, gslot)) atomicAdd(&P.counters[CNT_SRC_NO_PATH], 1ull);
+                if (P.counters && pt_source_counts<FEAT>(R, gslot)) atomicAdd(&P.counters[CNT_SRC_NO_PATH], 1ull);
                 return false;
             }
         } else {

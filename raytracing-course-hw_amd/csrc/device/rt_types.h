@@ -241,11 +241,14 @@ struct RenderView {
     int32_t sample_first;
     // The path source of the persistent hw8 kernel (rt_path_source.h, kernels compiled with WF_FEAT_SOURCE): where a sample's first ray comes
     // from.  Every other launch leaves these zero.  Indexed by the record index, which is the pixel slot (frame geometry: rt_path_source.h).
-    uint32_t src_mode;             // 0 = the camera, 1 = the caller's rays, 2 = bake irradiance
+    uint32_t src_mode;             // 0 = the camera, 1 = the caller's rays, 2 = bake irradiance, 3 = SH9 probes
     uint32_t src_n;                // records (mode 2: points x streams); a slot at or beyond it starts no path
-    const float *src_rays;         // mode 1: src_n x {o.xyz, d.xyz} (rt_ray), used as given
-    const float *src_points;       // mode 2: src_n / src_streams x {p.xyz, n.xyz} (rt_bake_point)
-    uint32_t src_streams;          // mode 2: slots per point
+    union {                        // one pointer's room: the struct, and with it every kernel's argument block, is laid out as before mode 3
+        const float *src_rays;     // mode 1: src_n x {o.xyz, d.xyz} (rt_ray), used as given
+        float *src_sh;             // mode 3: src_n rounded up to 64 x {first direction xyz, 27 accumulators [m][c]}, slot-major, 8-byte aligned
+    };
+    const float *src_points;       // mode 2 and 3: src_n / src_streams x {p.xyz, n.xyz} (rt_bake_point)
+    uint32_t src_streams;          // mode 2 and 3: slots per point
 };
 
 } // namespace rtamd

@@ -110,19 +110,22 @@ struct BakeView {
     float scale;
 };
 
-// rt_render_paths / rt_render_bake (rt_path_source.h): one chunk's slots between the caller's records and the state the persistent
+// rt_render_paths / rt_render_bake / rt_render_probes (rt_path_source.h): one chunk's slots between the caller's records and the state the persistent
 // kernel runs over (RenderView::accum's layout: n_pixslots x {sum.xyz, Rng::x}, then n_pixslots x {Rng::saved, Rng::has_saved}).
 struct SourceView {
     uint32_t *state;
     uint32_t n_pixslots;          // slots of the chunk's frame: n rounded up to whole 64-slot groups
     uint32_t n;                   // records (bake: points x streams)
-    uint32_t mode;                // RenderView::src_mode: 1 = rays, 2 = bake irradiance
+    uint32_t mode;                // RenderView::src_mode: 1 = rays, 2 = bake irradiance, 3 = SH9 probes
     uint4 *rng;                   // n (rt_rng), in (pack) and out (unpack), 16-byte aligned
-    const float *rays;            // mode 1: n x {o.xyz, d.xyz}
-    const float *points;          // mode 2: n / streams x {p.xyz, n.xyz}
-    uint32_t streams;             // mode 2: K
-    float scale;                  // mode 2: pi / samples
-    float *out;                   // unpack: n x 3 (mode 1) or n / streams x 3 (mode 2)
+    union {                       // one pointer's room, as in RenderView: the two older kernels' argument block is laid out as before mode 3
+        const float *rays;        // mode 1: n x {o.xyz, d.xyz}
+        float *sh;                // mode 3: RenderView::src_sh, n_pixslots x 30 floats
+    };
+    const float *points;          // mode 2 and 3: n / streams x {p.xyz, n.xyz}
+    uint32_t streams;             // mode 2 and 3: K
+    float scale;                  // mode 2: pi / samples; mode 3: 4 pi / samples
+    float *out;                   // unpack: n x 3 (mode 1), n / streams x 3 (mode 2) or n / streams x 27 (mode 3)
 };
 // One chunk through the persistent hw8 kernel with a path source: a slice of `samples` samples per slot of the strip frame over `state`.
 struct SourceChunk {
@@ -130,6 +133,7 @@ struct SourceChunk {
     const float *rays, *points;
     int32_t ray_depth, samples;
     uint32_t *state;
+    float *sh;                    // mode 3
 };
 struct SourceResult { float kernel_ms; uint32_t launches, reference_exact; uint64_t exact_walks, no_path; };
 
@@ -159,7 +163,7 @@ uint32_t query_launch_bake_advance(const rt_scene *scene, const PathView &V, con
 uint32_t query_launch_bake_resolve(const rt_scene *scene, const BakeView &B, hipStream_t stream);
 uint32_t query_launch_source_pack(const rt_scene *scene, const SourceView &V, hipStream_t stream);
 uint32_t query_launch_source_unpack(const rt_scene *scene, const SourceView &V, hipStream_t stream);
-// rt_render_paths / rt_render_bake.  source_check: what stands in the way of a chunk of `slots` slots (host only; RT_OK, or the refusal
+// rt_render_paths / rt_render_bake / rt_render_probes.  source_check: what stands in the way of a chunk of `slots` slots (host only; RT_OK, or the refusal
 // with `who` in front).  source_render: the chunk's launches through the renders' own driver (check_frame, launch_frame, collect_frame
 // of rtamd_api.hip), synchronous; the chunk's state is advanced in place.
 int source_check(const rt_scene *scene, uint32_t slots, int32_t ray_depth, int32_t samples, const std::string &who);

@@ -193,6 +193,7 @@ struct WfCameraSource {
         if (R.sample_seeds) wf_sample_seed(R, rng, gslot, x, y, next);
         wf_camera_ray(S, R, rng, x, y, o, d);
     }
+    static RT_DEV void sample(const RenderView &, uint32_t, F3) {} // a finished sample's value goes nowhere but the slot's sum
 };
 // End of one camera sample: fold e + m*(inner) backwards (scene.cpp:164), then wf_end_sample.
 template <class SRC = WfCameraSource>
@@ -204,6 +205,7 @@ RT_DEV int wf_finish_path(const SceneView &S, const RenderView &R, const WfView 
         float4 e0 = e[0], e1 = e[1];
         L = f3(e0.x, e0.y, e0.z) + f3(e1.x, e1.y, e1.z) * L;
     }
+    SRC::sample(R, slot + W.slot_base, L);                           // before wf_end_sample draws the next sample's ray
     return wf_end_sample(R, wf_rec(W, slot), slot + W.slot_base, L, rng, sample,
                          [&](int x, int y, uint32_t next, F3 &o, F3 &d) { SRC::ray(S, R, rng, slot + W.slot_base, x, y, next, o, d); },
                          [](bool has_saved, uint32_t next) { return wf_pack(0, has_saved, next); });
@@ -682,6 +684,7 @@ __global__ __launch_bounds__(64) void wf_light_exact_kernel(SceneView S, WfView 
 #define WF_FEAT_ENV 1
 #define WF_FEAT_HW7 2
 #define WF_FEAT_SOURCE 4 // rt_persistent.h only: a sample's first ray comes from a path source (rt_path_source.h); no hw7 and no counting variant
+#define WF_FEAT_PROBES 8 // with WF_FEAT_SOURCE only: the source is SH9 probes (src_mode 3), a finished sample is projected into RenderView::src_sh
 template <int FEAT = WF_FEAT_ENV | WF_FEAT_HW7>
 RT_DEV int wf_shade_item(const SceneView &S, const RenderView &R, const WfView &W, uint32_t slot, unsigned long long *counters, bool *discarded = nullptr) {
     float4 *r = wf_rec(W, slot);

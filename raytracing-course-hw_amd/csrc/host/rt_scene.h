@@ -146,7 +146,7 @@ struct rt_scene {
     uint32_t *query_materials = nullptr; // material index by LOAD-order triangle, made by the first surface query (not part of info.device_bytes)
     uint8_t *path_stack = nullptr;   // rt_trace_paths: state and per-bounce stack of a chunk's paths, grown on demand (not part of info.device_bytes)
     size_t path_stack_bytes = 0;
-    uint8_t *source_stage = nullptr; // rt_render_paths / rt_render_bake: the slots' state and, with host arrays, the staging of one chunk (not part of info.device_bytes)
+    uint8_t *source_stage = nullptr; // rt_render_paths / rt_render_bake / rt_render_probes: the slots' state (probes: with their accumulators) and, with host arrays, the staging of one chunk (not part of info.device_bytes)
     size_t source_stage_bytes = 0;
     uint8_t *denoise_stage = nullptr; // preview filter (rtamd_denoise.hip): the working set of one frame, grown on demand (not part of info.device_bytes)
     size_t denoise_stage_bytes = 0;

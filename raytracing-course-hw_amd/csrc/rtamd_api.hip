@@ -347,7 +347,10 @@ static PersistentKernel hw8_persistent(const SceneView &V, int ray_depth, hipStr
                 dev::WfView W{};
                 W.r0 = records; W.stride = stride; W.n_slots = n_slots; W.slot_base = slot_base;
                 const dim3 grid(blocks), block(P8_THREADS);
-                if (R.src_mode) { // a path source (device/rt_path_source.h; source_render below): hw8 only, no counting variant
+                if (R.src_mode == PT_SRC_PROBES) { // SH9 probes: the source kernel compiled with the side arrays (WF_FEAT_PROBES)
+                    if (feat == WF_FEAT_ENV) hipLaunchKernelGGL((dev::pt_persistent_kernel<false, WF_FEAT_SOURCE | WF_FEAT_PROBES | WF_FEAT_ENV>), grid, block, 0, stream, V, R, W, P);
+                    else hipLaunchKernelGGL((dev::pt_persistent_kernel<false, WF_FEAT_SOURCE | WF_FEAT_PROBES>), grid, block, 0, stream, V, R, W, P);
+                } else if (R.src_mode) { // a path source (device/rt_path_source.h; source_render below): hw8 only, no counting variant
                     if (feat == WF_FEAT_ENV) hipLaunchKernelGGL((dev::pt_persistent_kernel<false, WF_FEAT_SOURCE | WF_FEAT_ENV>), grid, block, 0, stream, V, R, W, P);
                     else hipLaunchKernelGGL((dev::pt_persistent_kernel<false, WF_FEAT_SOURCE>), grid, block, 0, stream, V, R, W, P);
                 } else if (count) {
@@ -1203,15 +1206,15 @@ uint32_t rtamd::query_launch_bake_resolve(const rt_scene *scene, const BakeView 
     return 1u;
 }
 
-// ---- rt_render_paths / rt_render_bake: a caller's paths through the persistent hw8 kernel (device/rt_path_source.h) --------------------------
+// ---- rt_render_paths / rt_render_bake / rt_render_probes: a caller's paths through the persistent hw8 kernel (device/rt_path_source.h) -------
 uint32_t rtamd::query_launch_source_pack(const rt_scene *scene, const SourceView &V, hipStream_t stream) {
-    hipLaunchKernelGGL(dev::rq_source_pack_kernel, dim3(query_geometry(scene, V.n_pixslots).flat_blocks), dim3(256), 0, stream, V);
+    hipLaunchKernelGGL(V.mode == PT_SRC_PROBES ? dev::rq_probes_pack_kernel : dev::rq_source_pack_kernel, dim3(query_geometry(scene, V.n_pixslots).flat_blocks), dim3(256), 0, stream, V);
     HIP_CHECK(hipGetLastError());
     return 1u;
 }
 
 uint32_t rtamd::query_launch_source_unpack(const rt_scene *scene, const SourceView &V, hipStream_t stream) {
-    hipLaunchKernelGGL(dev::rq_source_unpack_kernel, dim3(query_geometry(scene, V.n).flat_blocks), dim3(256), 0, stream, V);
+    hipLaunchKernelGGL(V.mode == PT_SRC_PROBES ? dev::rq_probes_unpack_kernel : dev::rq_source_unpack_kernel, dim3(query_geometry(scene, V.n).flat_blocks), dim3(256), 0, stream, V);
     HIP_CHECK(hipGetLastError());
     return 1u;
 }
@@ -1246,6 +1249,7 @@ int rtamd::source_render(rt_scene *scene, const SourceChunk &C, hipStream_t stre
     if (const int rc = source_frame(scene, p, slice, who, F)) return rc;
     const double t0 = now_ms();
     F.R.src_mode = C.mode; F.R.src_n = C.n; F.R.src_rays = C.rays; F.R.src_points = C.points; F.R.src_streams = C.streams;
+    if (C.mode == PT_SRC_PROBES) F.R.src_sh = C.sh; // shares its room with src_rays (RenderView), which mode 3 has none of
     launch_frame(scene, &p, F, stream, true);
     rt_stats st{};
     if (const int rc = collect_frame(scene, F, stream, &st, t0, who)) return rc;

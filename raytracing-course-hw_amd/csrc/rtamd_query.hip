@@ -373,16 +373,18 @@ uint32_t launch_round(rt_scene *scene, const QueryStage &S, const ScatterView &V
     return launches + query_launch_scatter_finish(scene, V, stream);
 }
 
-// ---- rt_render_paths / rt_render_bake: the caller's paths through the persistent kernel (device/rt_path_source.h) ----------------------------
+// ---- rt_render_paths / rt_render_bake / rt_render_probes: the caller's paths through the persistent kernel (device/rt_path_source.h) ---------
 // Slots per chunk: the pixel slots of a 1080p frame, so the persistent kernel's path records (256 bytes per slot at depth 6) never grow
 // beyond what rt_render of that frame allocates, and workload A of profiles/r30_render_paths.txt is one launch.  RTAMD_QUERY_CHUNK
 // lowers it as it does for the composed calls.
 const size_t SOURCE_CHUNK = 2073600;
 size_t source_chunk() { return std::min(SOURCE_CHUNK, (size_t)std::max(64, env_positive("RTAMD_QUERY_CHUNK", (int)SOURCE_CHUNK))); }
 
-// One call: `items` rays (K = 1) or points of K slots each.  `in`: the rays or the points, 24 bytes an item.
+// One call: `items` rays (K = 1) or points of K slots each.  `in`: the rays or the points, 24 bytes an item.  `floats`: the answer per item,
+// 3, or 27 for SH9 probes (mode 3), whose slots also keep 120 bytes each beside the state: the first direction and the 27 accumulators.
 struct SourceCall {
     uint32_t mode; size_t K; int32_t depth, samples; float scale; // samples: per slot
+    size_t floats;
     const void *in; rt_rng *rng; float *out; bool on_device;
 };
 struct SourceTotals { double kernel_ms = 0; uint32_t launches = 0, reference_exact = 0; uint64_t exact_walks = 0, no_path = 0; };
@@ -392,27 +394,30 @@ int source_run(rt_scene *scene, const SourceCall &c, size_t items, const std::st
     hipStream_t stream = nullptr;
     const size_t chunk_items = source_chunk() / c.K; // whole points: the stream sum never crosses a seam (the chunk's minimum of 64 covers K <= 64)
     const size_t cap_items = std::min(items, chunk_items), cap = (cap_items * c.K + 63u) & ~(size_t)63u;
-    struct { uint32_t *state; uint8_t *in, *rng; float *out; } S{}; // the kernel's state; host arrays: the records, the engines, the answer
+    const bool probes = c.mode == 3u;
+    struct { uint32_t *state; float *sh; uint8_t *in, *rng; float *out; } S{}; // the kernel's state; host arrays: the records, the engines, the answer
     auto carve = [&](uint8_t *base) {
         Carver take{base};
         take(S.state, cap * 24u);
-        if (!c.on_device) { take(S.in, cap_items * 24u); take(S.rng, cap * sizeof(rt_rng)); take(S.out, cap_items * 12u); }
+        take(S.sh, probes ? cap * 120u : 0u);
+        if (!c.on_device) { take(S.in, cap_items * 24u); take(S.rng, cap * sizeof(rt_rng)); take(S.out, cap_items * c.floats * 4u); }
         return take.at;
     };
     grow(scene->source_stage, scene->source_stage_bytes, carve(nullptr));
     carve(scene->source_stage);
-    struct { Arr in, rng, out; } A{arr_in(c.in, 24u, S.in), arr_inout(c.rng, c.K * sizeof(rt_rng), S.rng), arr_out(c.out, 12u, S.out)};
+    struct { Arr in, rng, out; } A{arr_in(c.in, 24u, S.in), arr_inout(c.rng, c.K * sizeof(rt_rng), S.rng), arr_out(c.out, c.floats * 4u, S.out)};
     return chunks(items, chunk_items, c.on_device, A, stream, nullptr, [&](size_t, size_t m_items) -> int {
         SourceView V{};
         V.state = S.state; V.n = (uint32_t)(m_items * c.K); V.n_pixslots = (V.n + 63u) & ~63u; V.mode = c.mode;
         V.rng = A.rng.as<uint4>();
         if (c.mode == 1u) V.rays = A.in.as<float>(); else V.points = A.in.as<float>();
+        if (probes) V.sh = S.sh; // shares its room with `rays`, which probes have none of
         V.streams = (uint32_t)c.K; V.scale = c.scale;
         V.out = A.out.as<float>();
         T.launches += query_launch_source_pack(scene, V, stream);
         SourceChunk C{};
-        C.mode = c.mode; C.n = V.n; C.streams = V.streams; C.rays = V.rays; C.points = V.points;
-        C.ray_depth = c.depth; C.samples = c.samples; C.state = V.state;
+        C.mode = c.mode; C.n = V.n; C.streams = V.streams; C.rays = c.mode == 1u ? V.rays : nullptr; C.points = V.points;
+        C.ray_depth = c.depth; C.samples = c.samples; C.state = V.state; C.sh = S.sh;
         SourceResult res{};
         if (const int rc = source_render(scene, C, stream, res, who)) return rc;
         T.launches += res.launches + query_launch_source_unpack(scene, V, stream);
@@ -722,7 +727,7 @@ int rt_render_paths(rt_scene *scene, const rt_ray *rays, rt_rng *rng, size_t n, 
     if (const int rc = source_check(scene, (uint32_t)std::min(std::max<size_t>(n, 1u), source_chunk()), depth, 1, who)) return rc;
     return with_stats(scene, n, stats, who, [&](rt_query_stats &st) -> int {
         SourceTotals T;
-        if (const int rc = source_run(scene, SourceCall{1u, 1u, depth, 1, 0.f, rays, rng, out_rgb, on_device}, n, who, T)) return rc;
+        if (const int rc = source_run(scene, SourceCall{1u, 1u, depth, 1, 0.f, 3u, rays, rng, out_rgb, on_device}, n, who, T)) return rc;
         st.exact_walks = T.exact_walks; st.invalid_rays = T.no_path; st.kernel_ms = T.kernel_ms; st.launches = T.launches;
         st.reference_exact = T.reference_exact;
         return RT_OK;
@@ -745,7 +750,30 @@ int rt_render_bake(rt_scene *scene, const rt_bake_point *points, size_t n_points
     const float scale = (float)(pi / (double)params->samples);
     return with_stats(scene, n_points, stats, who, [&](rt_bake_stats &st) -> int {
         SourceTotals T;
-        if (const int rc = source_run(scene, SourceCall{2u, K, depth, (int32_t)q, scale, points, rng, out, on_device}, n_points, who, T)) return rc;
+        if (const int rc = source_run(scene, SourceCall{2u, K, depth, (int32_t)q, scale, 3u, points, rng, out, on_device}, n_points, who, T)) return rc;
+        st.invalid_points = T.no_path; st.paths = (n_points - T.no_path) * K * q; st.exact_walks = T.exact_walks;
+        st.kernel_ms = T.kernel_ms; st.launches = T.launches; st.reference_exact = T.reference_exact;
+        return RT_OK;
+    });
+}
+
+int rt_render_probes(rt_scene *scene, const rt_bake_point *points, size_t n_points, const rt_bake_params *params, rt_rng *rng, float *out, rt_bake_stats *stats) {
+    const std::string who = "rt_render_probes: ";
+    size_t K = 1;
+    int depth = 0;
+    if (const int rc = check_bake_params(params, stats, n_points, RT_QUERY_DEVICE_POINTERS, who, K, depth)) return rc;
+    const size_t q = (size_t)params->samples / K;
+    if (q >= ((size_t)1 << 25)) return fail(RT_ERR_LIMIT, who + "params.samples / params.streams must stay below 2^25 (the path record's sample index)");
+    if (params->mode == RT_BAKE_IRRADIANCE)
+        return fail(RT_ERR_INVALID_ARG, who + "params.mode = RT_BAKE_IRRADIANCE: this call bakes RT_BAKE_SH9 probes, rt_render_bake serves irradiance");
+    const bool on_device = device_pointers(params->flags);
+    if (const int rc = check_bake_arrays(scene, "scene", points, rng, out, n_points, K, on_device, who)) return rc;
+    if (const int rc = source_check(scene, (uint32_t)std::min(std::max<size_t>(n_points, 1u) * K, source_chunk()), depth, (int32_t)q, who)) return rc;
+    const double pi = 3.14159265358979323846;
+    const float scale = (float)(4.0 * pi / (double)params->samples);
+    return with_stats(scene, n_points, stats, who, [&](rt_bake_stats &st) -> int {
+        SourceTotals T;
+        if (const int rc = source_run(scene, SourceCall{3u, K, depth, (int32_t)q, scale, 27u, points, rng, out, on_device}, n_points, who, T)) return rc;
         st.invalid_points = T.no_path; st.paths = (n_points - T.no_path) * K * q; st.exact_walks = T.exact_walks;
         st.kernel_ms = T.kernel_ms; st.launches = T.launches; st.reference_exact = T.reference_exact;
         return RT_OK;
