@@ -862,6 +862,93 @@ extern int rt_denoise(rt_scene *scene, const rt_denoise_params *params,
 extern int rt_accum_denoise(rt_accum *accum, rt_noise *noise /* nullable */, const rt_denoise_params *params,
                             float *out_rgb /* nullable */, uint8_t *out_rgb8 /* nullable */, rt_denoise_stats *stats /* nullable */);
 
+/* ---- adaptive sampling: freeze converged 8x8 sub-tiles -------------------------------------------------------------------------
+ * What rt_accum, rt_noise and RTAMD_TARGET_NOISE lead up to: a resumable render that stops drawing samples where the picture is done.
+ * An rt_adaptive owns its state -- it is NOT a mode of rt_accum, whose checkpoints, monitors, previews and multi-GPU frames all assume
+ * one sample count per frame.  The state is rt_accum's (24 bytes per pixel slot) plus, per 8x8 sub-tile, its sample count, its
+ * batches and observed samples, its flags and the noise monitor's three planes y0 / yp / m2 (12 bytes per pixel slot).  ABI version 6
+ * still: additions only.
+ *
+ * Contract   pixels are independent and a camera ray depends only on the pixel and its engine, so a sub-tile that has drawn d samples
+ *          holds exactly rt_render(samples = d)'s pixels, floats and bytes, whatever its neighbours drew (tests/test_gpu_adaptive.py:
+ *          np.array_equal per distinct count).  With every sub-tile active in every slice the picture is rt_accum_resolve's and the
+ *          map and summary are rt_noise_estimate's for the same slicing, bit for bit.
+ * A slice    the state of the active sub-tiles is gathered into a compact strip (8 pixels wide, one sub-tile per 64 slots), the
+ *          persistent hw8 kernel runs a slice of a resumable render over it with a path source of its own (src_mode 4, device/
+ *          rt_path_source.h: the REAL frame's camera ray for the pixel behind each slot, the same code as the renders'), and the
+ *          state is scattered back.  Every kernel that existed before is, instruction for instruction, the one it was.  Frames with
+ *          more active pixel slots than one path-source chunk (2,073,600; RTAMD_QUERY_CHUNK lowers it) run the list in chunks.
+ * Arithmetic the noise monitor's (rt_noise above), with n, N, B and d per sub-tile: a slice is one batch of the sub-tiles it drew
+ *          for, the statistics of a frozen sub-tile do not move.  A sub-tile with fewer than 2 batches has no estimate: 0 in the map,
+ *          RT_ADAPTIVE_NO_ESTIMATE in its entry, part of no frame figure.  rt_adaptive_resolve: pixel = (float)(1.0 / d_s) * sum as
+ *          rt_accum_resolve, d_s the sub-tile's count; a sub-tile with d_s = 0 is zeros.
+ * Decision (rt_adaptive_render; on the host, in double, in the frame's sub-tile order, after the slice's update and estimate).
+ *          L = the frame's mean luminance as rt_noise_estimate sums it, over the sub-tiles that have an estimate.  A sub-tile with
+ *          an estimate, batches >= min_batches and pixels > 0 becomes CONVERGED when sqrt(sum_se2 / pixels) <= target_noise * L; one
+ *          with an estimate and pixels == 0 (every pixel non-finite) at once.  CONVERGED is sticky.  CAPPED: samples + n_samples >
+ *          max_samples, n_samples the slice length of the call that decides.  ACTIVE = not CAPPED and (not CONVERGED, or
+ *          RT_ADAPTIVE_DILATE and some 8-neighbour is neither CONVERGED nor CAPPED: no seams one sub-tile wide).  A fresh object has
+ *          every sub-tile ACTIVE | NO_ESTIMATE.  rt_adaptive_render decides once more before it launches (the cap depends on this
+ *          call's n_samples), draws n_samples for the ACTIVE sub-tiles, updates, estimates and decides.  With no active sub-tile it
+ *          is RT_OK, launches nothing and reports samples = 0: the caller's stop condition.
+ * rt_adaptive_render_tiles   the mechanism without the policy: mask[t] != 0 draws n_samples for sub-tile t (one byte per sub-tile,
+ *          row-major over ceil(W/8) x ceil(H/8)); update and estimate as above, ACTIVE / CONVERGED / CAPPED are left as they were.
+ * rt_adaptive_tiles   the sub-tiles' entries, host memory, ceil(W/8) * ceil(H/8) of them.
+ * rt_adaptive_noise   the map (W*H floats, host memory or with RT_FLAG_OUT_DEVICE memory on the scene's GPU) and the frame figures
+ *          as rt_noise_estimate adds them; batches, samples_observed and samples_total are the largest over the sub-tiles.
+ *          RT_ERR_INVALID_ARG while no sub-tile has 2 batches.
+ * rt_adaptive_sample_map   W*H counts, host memory.
+ * stats    active_tiles: sub-tiles this call drew for; converged_tiles / capped_tiles: as flagged when it returns; samples: camera
+ *          samples drawn (pixels inside the image x n_samples); min_samples / max_samples per pixel over the frame; kernel_ms: the
+ *          persistent kernel's launches; gather_ms / scatter_ms: the two kernels around it; total_ms: host wall time of the call.
+ * Refusals   before anything is launched, the state untouched.  RT_ERR_UNSUPPORTED, no fallback: integrators other than
+ *          RT_INTEGRATOR_HW8, shard_count > 1, sample_streams > 1, render flags other than 0, and whatever keeps the persistent hw8
+ *          kernel from the scene (RTAMD_KERNEL=wavefront|mega, a tree beyond its stack columns).  RT_ERR_INVALID_ARG: null arguments,
+ *          struct_size, reserved words, target_noise not finite or <= 0, min_batches < 0 or 1, max_samples < 0, unknown flags,
+ *          n_samples <= 0, a broken object.  RT_ERR_LIMIT: width or height above 65,535 (the slot's pixel is one packed word), and a
+ *          slice that would take an active sub-tile's count to the path records' sample index limit (2^25).  A slice that fails
+ *          under way leaves the object broken, as with rt_accum.
+ * Out of scope   checkpoints of an rt_adaptive, rt_multi_*, hw7 / hw6, rt_accum_denoise on it.
+ * Measured on one MI355X: profiles/r35_adaptive.txt. */
+typedef struct rt_adaptive_params {
+    uint32_t struct_size;
+    float    target_noise;   /* a sub-tile converges when sqrt(its mean se^2) <= target_noise * frame mean luminance; > 0, finite */
+    int32_t  min_batches;    /* never judged before this many slices of its own; >= 2; 0 = 4 (RTAMD_NOISE_MIN_BATCHES' default) */
+    int32_t  max_samples;    /* a sub-tile whose next slice would pass this stops ("capped"); 0 = the sample-index limit */
+    uint32_t flags;          /* RT_ADAPTIVE_DILATE */
+    int32_t  reserved;       /* 0 */
+} rt_adaptive_params;
+#define RT_ADAPTIVE_DILATE 1u
+typedef struct rt_adaptive_tile {   /* 32 bytes, one per 8x8 sub-tile, row-major over ceil(W/8) x ceil(H/8) */
+    int32_t  samples, batches;
+    uint32_t pixels, nonfinite;     /* of the last estimate: pixels with a finite estimate, pixels inside the image without */
+    float    sum_se2, sum_luminance;
+    uint32_t flags;                 /* RT_ADAPTIVE_ACTIVE, _CONVERGED, _CAPPED, _NO_ESTIMATE */
+    uint32_t reserved;
+} rt_adaptive_tile;
+#define RT_ADAPTIVE_ACTIVE      1u
+#define RT_ADAPTIVE_CONVERGED   2u
+#define RT_ADAPTIVE_CAPPED      4u
+#define RT_ADAPTIVE_NO_ESTIMATE 8u
+typedef struct rt_adaptive_stats {
+    uint32_t struct_size;           /* in: sizeof(rt_adaptive_stats) */
+    uint32_t active_tiles, converged_tiles, capped_tiles;
+    uint64_t samples;
+    int32_t  min_samples, max_samples;
+    double   kernel_ms, gather_ms, scatter_ms, total_ms;
+    uint32_t launches, reference_exact;
+    uint64_t exact_walks;
+} rt_adaptive_stats;
+typedef struct rt_adaptive rt_adaptive;
+int  rt_adaptive_create(rt_scene *scene, const rt_render_params *params, const rt_adaptive_params *adaptive, rt_adaptive **out);
+int  rt_adaptive_render(rt_adaptive *a, int32_t n_samples, rt_adaptive_stats *stats /* nullable */);
+int  rt_adaptive_render_tiles(rt_adaptive *a, int32_t n_samples, const uint8_t *mask, rt_adaptive_stats *stats /* nullable */);
+int  rt_adaptive_tiles(rt_adaptive *a, rt_adaptive_tile *out);
+int  rt_adaptive_resolve(rt_adaptive *a, uint32_t flags, float *out_rgb /* nullable */, uint8_t *out_rgb8 /* nullable */);
+int  rt_adaptive_noise(rt_adaptive *a, uint32_t flags, float *out_se /* nullable */, rt_noise_summary *summary /* nullable */);
+int  rt_adaptive_sample_map(rt_adaptive *a, int32_t *out /* W*H */);
+void rt_adaptive_destroy(rt_adaptive *a);
+
 /* Scene info the host side needs after preparation. */
 typedef struct rt_scene_info {
     uint32_t n_triangles, n_lights, n_bvh_nodes, n_light_bvh_nodes;

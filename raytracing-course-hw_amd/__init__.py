@@ -26,6 +26,8 @@ RT_HIT_MISS = 0xFFFFFFFF
 RT_OCCLUSION_OCCLUDED, RT_OCCLUSION_EXACT_WALK, RT_OCCLUSION_INVALID_RAY = 1, 2, 4
 RT_SCATTER_END_BRDF, RT_SCATTER_END_CLAMP, RT_SCATTER_NO_SURFACE, RT_SCATTER_INVALID = 1, 2, 4, 8
 RT_DENOISE_DEVICE_POINTERS, RT_DENOISE_ALBEDO = 1, 2
+RT_ADAPTIVE_DILATE = 1
+RT_ADAPTIVE_ACTIVE, RT_ADAPTIVE_CONVERGED, RT_ADAPTIVE_CAPPED, RT_ADAPTIVE_NO_ESTIMATE = 1, 2, 4, 8
 RT_PIPELINE_SINGLE, RT_PIPELINE_ROUNDS, RT_PIPELINE_PERSISTENT = 0, 1, 2
 RT_OK = 0
 RT_ERR_INVALID_ARG, RT_ERR_NO_DEVICE, RT_ERR_HIP, RT_ERR_UNSUPPORTED, RT_ERR_LIMIT = -1, -2, -3, -4, -7
@@ -157,6 +159,22 @@ class rt_denoise_stats(C.Structure):
                 ("total_ms", C.c_double)]
 
 
+class rt_adaptive_params(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("target_noise", C.c_float), ("min_batches", C.c_int32), ("max_samples", C.c_int32),
+                ("flags", C.c_uint32), ("reserved", C.c_int32)]
+
+
+class rt_adaptive_stats(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("active_tiles", C.c_uint32), ("converged_tiles", C.c_uint32), ("capped_tiles", C.c_uint32),
+                ("samples", C.c_uint64), ("min_samples", C.c_int32), ("max_samples", C.c_int32), ("kernel_ms", C.c_double),
+                ("gather_ms", C.c_double), ("scatter_ms", C.c_double), ("total_ms", C.c_double), ("launches", C.c_uint32),
+                ("reference_exact", C.c_uint32), ("exact_walks", C.c_uint64)]
+
+
+# rt_adaptive_tile as a numpy record: what AdaptiveRender.tiles() returns, one per 8x8 sub-tile
+ADAPTIVE_TILE_DTYPE = np.dtype([("samples", np.int32), ("batches", np.int32), ("pixels", np.uint32), ("nonfinite", np.uint32),
+                                ("sum_se2", np.float32), ("sum_luminance", np.float32), ("flags", np.uint32), ("reserved", np.uint32)])
+
 # rt_ray / rt_hit as numpy records: what Scene.query_* take and return
 RAY_DTYPE = np.dtype([("o", np.float32, 3), ("d", np.float32, 3)])
 HIT_DTYPE = np.dtype([("t", np.float32), ("triangle", np.uint32), ("ng", np.float32, 3), ("texcoord", np.float32, 2), ("ns", np.float32, 3),
@@ -184,7 +202,9 @@ ABI_SYMBOLS = ["rt_abi_version", "rt_last_error", "rt_scene_create", "rt_scene_d
                "rt_multi_noise_reset", "rt_multi_noise_batches", "rt_multi_noise_estimate", "rt_multi_noise_destroy", "rt_query_closest",
                "rt_query_light_pdf", "rt_query_surface", "rt_query_environment", "rt_camera_rays", "rt_render_guides",
                "rt_query_occluded", "rt_rng_seed", "rt_query_scatter", "rt_query_bsdf", "rt_trace_paths", "rt_bake_rays", "rt_bake",
-               "rt_render_paths", "rt_render_bake", "rt_render_probes"]
+               "rt_render_paths", "rt_render_bake", "rt_render_probes", "rt_adaptive_create", "rt_adaptive_render",
+               "rt_adaptive_render_tiles", "rt_adaptive_tiles", "rt_adaptive_resolve", "rt_adaptive_noise", "rt_adaptive_sample_map",
+               "rt_adaptive_destroy"]
 # The preview filter's two, which the header declares `extern int`: the list above and the family lists of the tests are closed sets
 # of the header's plain prototypes (tests/test_abi_and_host.py, tests/test_accum_host.py), and rt_accum_denoise is no rt_accum_* of theirs.
 DENOISE_SYMBOLS = ["rt_denoise", "rt_accum_denoise"]
@@ -262,6 +282,15 @@ lib.rt_bake.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(rt_bake_pa
 lib.rt_render_paths.argtypes = lib.rt_trace_paths.argtypes
 lib.rt_render_bake.argtypes = lib.rt_bake.argtypes
 lib.rt_render_probes.argtypes = lib.rt_bake.argtypes
+lib.rt_adaptive_create.argtypes = [C.c_void_p, C.POINTER(rt_render_params), C.POINTER(rt_adaptive_params), C.POINTER(C.c_void_p)]
+lib.rt_adaptive_render.argtypes = [C.c_void_p, C.c_int32, C.POINTER(rt_adaptive_stats)]
+lib.rt_adaptive_render_tiles.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(rt_adaptive_stats)]
+lib.rt_adaptive_tiles.argtypes = [C.c_void_p, C.c_void_p]
+lib.rt_adaptive_resolve.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
+lib.rt_adaptive_noise.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(rt_noise_summary)]
+lib.rt_adaptive_sample_map.argtypes = [C.c_void_p, C.c_void_p]
+lib.rt_adaptive_destroy.argtypes = [C.c_void_p]
+lib.rt_adaptive_destroy.restype = None
 lib.rt_denoise.argtypes = [C.c_void_p, C.POINTER(rt_denoise_params)] + [C.c_void_p] * 8 + [C.POINTER(rt_denoise_stats)]
 lib.rt_accum_denoise.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(rt_denoise_params), C.c_void_p, C.c_void_p, C.POINTER(rt_denoise_stats)]
 
@@ -486,6 +515,20 @@ def make_bake_params(samples, streams=1, mode=RT_BAKE_IRRADIANCE, ray_depth=0, f
     params.struct_size = C.sizeof(rt_bake_params)
     params.mode, params.samples, params.streams, params.ray_depth, params.flags = mode, samples, streams, ray_depth, flags
     return params
+
+
+def make_adaptive_params(target_noise, min_batches=0, max_samples=0, flags=0):
+    """rt_adaptive_params; 0 selects the default of min_batches (4) and of max_samples (the sample-index limit)."""
+    p = rt_adaptive_params()
+    p.struct_size = C.sizeof(rt_adaptive_params)
+    p.target_noise, p.min_batches, p.max_samples, p.flags = target_noise, min_batches, max_samples, flags
+    return p
+
+
+def _adaptive_stats():
+    st = rt_adaptive_stats()
+    st.struct_size = C.sizeof(rt_adaptive_stats)
+    return st
 
 
 def make_denoise_params(width, height, iterations=0, sigma_depth=0.0, sigma_luminance=0.0, flags=0):
@@ -740,6 +783,67 @@ class Accumulator(_AccumulatorBase):
         return rgb, rgb8, st
 
 
+class AdaptiveRender(_Handle):
+    """A frame in progress whose converged 8x8 sub-tiles stop drawing samples (rt_adaptive on a Scene): render(n) is one slice of the
+    policy, render_tiles(n, mask) one of the caller's own mask; a sub-tile that has drawn d samples holds Scene.render(samples = d)'s
+    pixels.  Keywords: target_noise, min_batches, max_samples, dilate, then make_params'."""
+    _destroy = "rt_adaptive_destroy"
+
+    def __init__(self, scene, width, height, target_noise, min_batches=0, max_samples=0, dilate=False, **kw):
+        self.scene = scene  # keeps the scene alive: an rt_adaptive is destroyed before its scene
+        self.params = make_params(width, height, 0, **kw)
+        self.adaptive = make_adaptive_params(target_noise, min_batches, max_samples, RT_ADAPTIVE_DILATE if dilate else 0)
+        self._open(scene)
+        _check(lib.rt_adaptive_create(scene._h, C.byref(self.params), C.byref(self.adaptive), C.byref(self._h)))
+
+    @property
+    def grid(self):
+        """(rows, columns) of the frame's 8x8 sub-tiles."""
+        return (self.params.height + 7) // 8, (self.params.width + 7) // 8
+
+    def render(self, n_samples):
+        st = _adaptive_stats()
+        _check(lib.rt_adaptive_render(self._h, n_samples, C.byref(st)))
+        return st
+
+    def render_tiles(self, n_samples, mask):
+        """One slice for the sub-tiles whose byte of `mask` (rows x columns, or flat) is not 0."""
+        mask = np.ascontiguousarray(np.asarray(mask).astype(np.uint8).reshape(-1))
+        if mask.size != self.grid[0] * self.grid[1]:
+            raise ValueError(f"mask must hold one byte per sub-tile ({self.grid[0]} x {self.grid[1]}), got {mask.size}")
+        st = _adaptive_stats()
+        _check(lib.rt_adaptive_render_tiles(self._h, n_samples, mask.ctypes.data, C.byref(st)))
+        return st
+
+    def tiles(self):
+        """The sub-tiles' entries, ADAPTIVE_TILE_DTYPE records of shape (rows, columns)."""
+        out = np.zeros(self.grid, dtype=ADAPTIVE_TILE_DTYPE)
+        _check(lib.rt_adaptive_tiles(self._h, out.ctypes.data))
+        return out
+
+    def resolve(self, want_float=True, want_rgb8=True):
+        """(rgb float32, rgb8), (H, W, 3) each: every sub-tile's pixels are Scene.render's at that sub-tile's sample count."""
+        h, w = self.params.height, self.params.width
+        rgb = np.zeros((h, w, 3), dtype=np.float32) if want_float else None
+        rgb8 = np.zeros((h, w, 3), dtype=np.uint8) if want_rgb8 else None
+        _check(lib.rt_adaptive_resolve(self._h, 0, rgb.ctypes.data if want_float else None, rgb8.ctypes.data if want_rgb8 else None))
+        return rgb, rgb8
+
+    def noise(self, want_map=True):
+        """(standard error per pixel (H, W) or None, rt_noise_summary), the sample count read per sub-tile."""
+        se = np.zeros((self.params.height, self.params.width), dtype=np.float32) if want_map else None
+        summary = rt_noise_summary()
+        summary.struct_size = C.sizeof(rt_noise_summary)
+        _check(lib.rt_adaptive_noise(self._h, 0, se.ctypes.data if want_map else None, C.byref(summary)))
+        return se, summary
+
+    def sample_map(self):
+        """Samples drawn per pixel, int32 (H, W)."""
+        out = np.zeros((self.params.height, self.params.width), dtype=np.int32)
+        _check(lib.rt_adaptive_sample_map(self._h, out.ctypes.data))
+        return out
+
+
 class Scene(_Handle):
     """A prepared scene resident in HBM on the current HIP device (rt_scene)."""
     _destroy = "rt_scene_destroy"
@@ -781,6 +885,10 @@ class Scene(_Handle):
     def accumulator(self, width, height, **kw):
         """A resumable render of this scene (Accumulator); keywords as make_params."""
         return Accumulator(self, width, height, **kw)
+
+    def adaptive(self, width, height, target_noise, **kw):
+        """An adaptive render of this scene (AdaptiveRender)."""
+        return AdaptiveRender(self, width, height, target_noise, **kw)
 
     def render_device(self, params, out_rgb_ptr, out_rgb8_ptr):
         """Render into device buffers (raw pointers, e.g. torch tensor data_ptr())."""

@@ -22,6 +22,13 @@
 // sliced run after every slice, steered by the noise monitor's error map whenever a monitor runs (RTAMD_TARGET_NOISE, RTAMD_NOISE_MAP) and
 // has two batches; RTAMD_DENOISE_ALBEDO=1 demodulates by the albedo plane.  out.ppm is the run's without it.  With several devices the
 // frame and the map come to the host (rt_multi_accum_resolve, rt_multi_noise_estimate) and rt_denoise filters them on a scene of its own.
+// Adaptive sampling (rt_adaptive_*, glTF surface, hw8, one GPU): RTAMD_ADAPTIVE=1 together with RTAMD_TARGET_NOISE=x renders in slices of
+// RTAMD_SLICE samples (else a sixteenth of the samples asked for) and stops drawing samples for every 8x8 sub-tile whose own noise is at
+// most x times the frame's mean luminance, once RTAMD_NOISE_MIN_BATCHES slices of it have been observed; the samples asked for are the
+// most any sub-tile draws.  RTAMD_ADAPTIVE_DILATE=1 keeps the neighbours of an unfinished sub-tile drawing.  After every slice one line
+// on stderr: the sub-tiles that drew, the converged and the capped ones, the frame's noise.  RTAMD_SAMPLE_MAP=path writes the samples per
+// pixel as a grayscale PFM.  out.ppm is rt_adaptive_resolve's bytes: every sub-tile the plain run's picture at that sub-tile's count.
+// On several GPUs, with another snapshot or with a checkpoint the run ends with an error that names the reason.
 #include "../../../include/rtamd.h"
 #include <cmath>
 #include <cstdio>
@@ -219,6 +226,52 @@ static int render_in_slices(Progress &acc, const rt_render_params &p, int slice,
     return rc;
 }
 
+// RTAMD_ADAPTIVE=1: slices of the policy until no sub-tile is active.
+static int render_adaptive(rt_scene *scene, const rt_render_params &p, int slice, const NoiseTarget &noise, const char *out_path, std::vector<uint8_t> &rgb8) {
+    rt_adaptive_params ap;
+    memset(&ap, 0, sizeof ap);
+    ap.struct_size = sizeof ap;
+    ap.target_noise = (float)noise.target; ap.min_batches = noise.min_batches; ap.max_samples = p.samples;
+    if (const char *e = getenv("RTAMD_ADAPTIVE_DILATE")) if (atoi(e) != 0) ap.flags |= RT_ADAPTIVE_DILATE;
+    rt_render_params q = p;
+    q.samples = 0;
+    rt_adaptive *ad = nullptr;
+    if (rt_adaptive_create(scene, &q, &ap, &ad) != RT_OK) return die();
+    auto fail = [&]() { const int rc = die(); rt_adaptive_destroy(ad); return rc; };
+    double kernel_ms = 0;
+    uint64_t samples = 0;
+    for (int k = 1;; k++) {
+        rt_adaptive_stats st;
+        memset(&st, 0, sizeof st);
+        st.struct_size = sizeof st;
+        if (rt_adaptive_render(ad, slice, &st) != RT_OK) return fail();
+        if (st.samples == 0) break;
+        kernel_ms += st.kernel_ms; samples += st.samples;
+        fprintf(stderr, "slice %d: %u sub-tiles drew %d samples, %u converged, %u capped, %d .. %d samples per pixel, %.3f ms on the GPU", k, st.active_tiles, slice,
+                st.converged_tiles, st.capped_tiles, st.min_samples, st.max_samples, st.kernel_ms);
+        if (k >= 2) {
+            rt_noise_summary ns;
+            memset(&ns, 0, sizeof ns);
+            ns.struct_size = sizeof ns;
+            if (rt_adaptive_noise(ad, 0, nullptr, &ns) != RT_OK) { fprintf(stderr, "\n"); return fail(); }
+            fprintf(stderr, ", noise %.9g worst tile %.9g", ns.noise, ns.worst_tile_noise);
+        }
+        fprintf(stderr, "\n");
+    }
+    if (samples) fprintf(stderr, "render: %.3f ms on the GPU, %.2f Msamples/s, %llu camera samples of the %llu a uniform run draws\n", kernel_ms, samples / (kernel_ms * 1e3),
+                         (unsigned long long)samples, (unsigned long long)p.width * p.height * p.samples);
+    if (rt_adaptive_resolve(ad, 0, nullptr, rgb8.data()) != RT_OK) return fail();
+    if (const char *path = getenv("RTAMD_SAMPLE_MAP")) {
+        std::vector<int32_t> spp((size_t)p.width * p.height);
+        if (rt_adaptive_sample_map(ad, spp.data()) != RT_OK) return fail();
+        const std::vector<float> image(spp.begin(), spp.end());
+        if (!write_pfm(path, p.width, p.height, 1, image)) { fprintf(stderr, "error: cannot write sample map %s\n", path); rt_adaptive_destroy(ad); return 1; }
+    }
+    rt_adaptive_destroy(ad);
+    if (rt_write_ppm(out_path, p.width, p.height, rgb8.data()) != RT_OK) return die();
+    return 0;
+}
+
 int main(int argc, const char *argv[]) {
     const char *snap = getenv("RTAMD_SNAPSHOT");
     rt_host_scene *hs = nullptr;
@@ -294,6 +347,15 @@ int main(int argc, const char *argv[]) {
         }
         n_dev = (int)list.size();
     }
+    const bool adaptive = argc >= 6 && getenv("RTAMD_ADAPTIVE") && atoi(getenv("RTAMD_ADAPTIVE")) != 0;
+    if (adaptive) { // one GPU and hw8 only; what else stands in the way is the library's to say (rt_adaptive_create)
+        const char *why = !(noise.target > 0) ? "it needs RTAMD_TARGET_NOISE=x, the noise at which a sub-tile stops"
+                          : p.integrator != RT_INTEGRATOR_HW8 ? "it runs the hw8 integrator only (RTAMD_SNAPSHOT=hw8, the default)"
+                          : (!list.empty() || n_dev > 1) ? "it runs on one GPU (RTAMD_DEVICES=1; no RTAMD_DEVICE_LIST)"
+                          : checkpoint ? "an adaptive render has no checkpoint (RTAMD_CHECKPOINT)"
+                          : preview.path ? "an adaptive render has no denoised preview (RTAMD_DENOISE)" : nullptr;
+        if (why) { fprintf(stderr, "error: RTAMD_ADAPTIVE: %s\n", why); return 1; }
+    }
     rt_multi *multi = nullptr; // all devices, or ...
     rt_scene *scene = nullptr; // ... one
     if ((!list.empty() || n_dev > 1) && p.integrator != RT_INTEGRATOR_HW1) {
@@ -305,6 +367,13 @@ int main(int argc, const char *argv[]) {
         const int rc = write_guides(scene ? scene : own, p, prefix);
         rt_scene_destroy(own);
         if (rc) return rc;
+    }
+    if (adaptive) {
+        const int rc = render_adaptive(scene, p, slice, noise, out_path, rgb8);
+        rt_scene_destroy(scene);
+        rt_host_scene_free(hs);
+        if (rc == 0) fprintf(stderr, "FINISH\n");
+        return rc;
     }
     if (sliced) {
         Progress acc;

@@ -49,6 +49,7 @@ RT_DEV float noise_wave_sum(float v) {
     return v;
 }
 
+#ifndef RT_NOISE_FUNCTIONS_ONLY // set by rt_adaptive.h, which wants the three functions above in rtamd_api.hip without a second copy of the kernels
 // create / reset: y0 = yp = Y(sum), m2 = 0
 __global__ __launch_bounds__(256) void noise_snapshot_kernel(RenderView R, NoiseView V) {
     for (uint32_t p = blockIdx.x * 256u + threadIdx.x; p < R.n_pixslots; p += gridDim.x * 256u) {
@@ -107,6 +108,8 @@ __global__ __launch_bounds__(256) void noise_estimate_kernel(RenderView R, Noise
         }
     }
 }
+
+#endif // RT_NOISE_FUNCTIONS_ONLY
 
 } // namespace dev
 } // namespace rtamd

@@ -19,6 +19,17 @@
 // contiguous: slot-major keeps a lane's 120 bytes within two 128-byte lines where plane-major would touch 30.  120 is a multiple of 8,
 // so the lane moves them as fifteen 8-byte words.  One lane owns a slot from its first ray to its last sample: no atomics.
 //
+// The pixels of another frame (include/rtamd.h: rt_adaptive_*) are a kernel of their own too, compiled with WF_FEAT_SOURCE |
+// WF_FEAT_PIXELS and only ever launched with
+//   src_mode 4   wf_camera_ray's expressions for pixel src_pixels[gslot] = x | y << 16 of the frame src_frame[0] x src_frame[1] with
+//                src_tan_fov_x, drawn from the slot's engine; `samples` samples per slot
+// The strip's slots are the pixel slots of the active 8x8 sub-tiles of that frame, gathered by ad_gather_kernel (rt_adaptive.h), which
+// also works the pixel out, so that no division on the real geometry runs here.  A slot whose engine word is 0 is the padding of a
+// border sub-tile (accum_seed_kernel) or lies beyond the list: it starts no path and is NOT counted, as padding never was.  Its rays
+// are camera rays, which the walkers were derived for: the shader looks at the tripwires only, as the camera kernels' seed_wire does
+// (rt_persistent.h), not at pt_source_exact.  The pixels are the same either way (the exact role and the walkers agree on every ray
+// the gate lets the walkers keep); the camera kernels' rule is the cheaper one and the one rt_render itself runs.
+//
 // The frame.  An unsharded strip 8 pixels wide and 8 * ceil(n / 64) high: its tiles are the 8x8 sub-tiles themselves, one per row of the
 // tile grid, so slot_to_pixel (rt_device.h) maps sub-tile s, pixel (x, y) of it to slot 64 s + 8 y + x -- gslot IS the record index.  The
 // pixel coordinates are never used (no camera ray, no pixel store).
@@ -45,6 +56,7 @@ namespace dev {
 #define PT_SRC_RAYS 1u
 #define PT_SRC_BAKE 2u
 #define PT_SRC_PROBES 3u
+#define PT_SRC_PIXELS 4u
 #define PT_SH_FLOATS 30u // per slot of RenderView::src_sh: d0.xyz, then acc[9][3]
 
 RT_DEV void pt_source_load_ray(const float *rays, uint32_t i, F3 &o, F3 &d) { // rt_ray is only 4-byte aligned
@@ -63,6 +75,7 @@ template <int32_t MODE> RT_DEV bool pt_source_point(const RenderView &R, uint32_
 }
 // Whether a slot without a path counts (once per invalid record / point; the padding of the last 64-slot group does not).
 template <int FEAT> RT_DEV bool pt_source_counts(const RenderView &R, uint32_t gslot) {
+    if constexpr ((FEAT & WF_FEAT_PIXELS) != 0) return false; // mode 4: a slot without a path is padding
     if constexpr ((FEAT & WF_FEAT_PROBES) != 0) return gslot < R.src_n && gslot % R.src_streams == 0u;
     else return gslot < R.src_n && (R.src_mode != PT_SRC_BAKE || gslot % R.src_streams == 0u);
 }
@@ -101,10 +114,21 @@ RT_DEV void pt_source_project(const RenderView &R, uint32_t gslot, F3 L) {
     for (int j = 1; j < (int)PT_SH_FLOATS / 2; j++) s[j] = make_float2(v[2 * j], v[2 * j + 1]); // word 1 holds d0.z next to acc[0][0]: rewritten as read
 }
 
+// Mode 4: the camera ray of the real frame's pixel behind strip slot `gslot`.
+RT_DEV void pt_source_pixel_ray(const SceneView &S, const RenderView &R, uint32_t gslot, Rng &rng, F3 &o, F3 &d) {
+    const uint32_t xy = R.src_pixels[gslot];
+    wf_camera_ray_of(S, R.src_tan_fov_x, R.src_frame[0], R.src_frame[1], rng, (int)(xy & 0xffffu), (int)(xy >> 16), o, d);
+}
+
 template <int FEAT> struct PtSource {
     // The first ray of slot `gslot`, whose engine `rng` comes from the state; false: the slot has no path.
-    static RT_DEV bool first(const SceneView &, const RenderView &R, uint32_t gslot, Rng &rng, F3 &o, F3 &d) {
+    static RT_DEV bool first(const SceneView &S, const RenderView &R, uint32_t gslot, Rng &rng, F3 &o, F3 &d) {
         if (gslot >= R.src_n) return false;
+        if constexpr ((FEAT & WF_FEAT_PIXELS) != 0) {
+            if (!rq_rng_valid(rng.x)) return false;          // engine word 0: padding of a border sub-tile
+            pt_source_pixel_ray(S, R, gslot, rng, o, d);
+            return true;
+        }
         if constexpr ((FEAT & WF_FEAT_PROBES) != 0) {
             F3 p, n;
             if (!pt_source_point<RQ_BAKE_SH9>(R, gslot, p, n)) return false;
@@ -123,7 +147,9 @@ template <int FEAT> struct PtSource {
     }
     // The first ray of the slot's sample `next` (wf_finish_path): the slot has a path, so its record is valid.
     static RT_DEV void ray(const SceneView &S, const RenderView &R, Rng &rng, uint32_t gslot, int x, int y, uint32_t next, F3 &o, F3 &d) {
-        if constexpr ((FEAT & WF_FEAT_PROBES) != 0) {
+        if constexpr ((FEAT & WF_FEAT_PIXELS) != 0) {
+            pt_source_pixel_ray(S, R, gslot, rng, o, d);
+        } else if constexpr ((FEAT & WF_FEAT_PROBES) != 0) {
             F3 p, n;
             rq_bake_point_read(R.src_points, gslot / R.src_streams, RQ_BAKE_SH9, p, n);
             rq_bake_ray(RQ_BAKE_SH9, rng, p, n, o, d);

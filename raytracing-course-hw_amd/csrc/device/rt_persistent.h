@@ -986,7 +986,8 @@ struct PtRoles {
     }
     RT_DEV uint32_t resumed_sample(uint32_t slot) { return (__float_as_uint(reinterpret_cast<const float *>(wf_rec(W, slot) + 3)[3]) >> 6) & WF_SAMPLE_MASK; }
     RT_DEV bool seed_wire(uint32_t slot) { // the record's ray pierces a tripwire (rt_exact.h): its closest hit is the exact role's
-        if constexpr ((FEAT & WF_FEAT_SOURCE) != 0) { // ... or it is a first ray the walkers were not derived for (pt_source_exact, which looks at the tripwires too)
+        // (a pixel source's ray is a camera ray, which the walkers were derived for: tripwires only, as the camera kernels)
+        if constexpr ((FEAT & WF_FEAT_SOURCE) != 0 && (FEAT & WF_FEAT_PIXELS) == 0) { // ... or it is a first ray the walkers were not derived for (pt_source_exact, which looks at the tripwires too)
             const float4 *nr = wf_rec(W, slot);
             const float4 n0 = nr[0], n1 = nr[1];
             return pt_source_exact(S, f3(n0.x, n0.y, n0.z), f3(n0.w, n1.x, n1.y));
@@ -1046,7 +1047,7 @@ struct PtRoles {
                 }
             }
         }
-        if constexpr ((FEAT & WF_FEAT_SOURCE) != 0) { // the next sample's first ray (depth 0, no bounce pending) gets the treatment of the slot's first
+        if constexpr ((FEAT & WF_FEAT_SOURCE) != 0 && (FEAT & WF_FEAT_PIXELS) == 0) { // the next sample's first ray (depth 0, no bounce pending) gets the treatment of the slot's first
             if (next && !wire) {
                 const float4 *nr = wf_rec(W, slot);
                 if ((__float_as_uint(reinterpret_cast<const float *>(nr + 3)[3]) & (15u | WF_PENDING_BIT)) == 0u) {

@@ -241,14 +241,21 @@ struct RenderView {
     int32_t sample_first;
     // The path source of the persistent hw8 kernel (rt_path_source.h, kernels compiled with WF_FEAT_SOURCE): where a sample's first ray comes
     // from.  Every other launch leaves these zero.  Indexed by the record index, which is the pixel slot (frame geometry: rt_path_source.h).
-    uint32_t src_mode;             // 0 = the camera, 1 = the caller's rays, 2 = bake irradiance, 3 = SH9 probes
+    uint32_t src_mode;             // 0 = the camera, 1 = the caller's rays, 2 = bake irradiance, 3 = SH9 probes, 4 = the pixels of another frame
     uint32_t src_n;                // records (mode 2: points x streams); a slot at or beyond it starts no path
     union {                        // one pointer's room: the struct, and with it every kernel's argument block, is laid out as before mode 3
         const float *src_rays;     // mode 1: src_n x {o.xyz, d.xyz} (rt_ray), used as given
         float *src_sh;             // mode 3: src_n rounded up to 64 x {first direction xyz, 27 accumulators [m][c]}, slot-major, 8-byte aligned
+        const uint32_t *src_pixels; // mode 4: src_n x (x | y << 16), the pixel of the real frame behind the strip slot (ad_gather_kernel, rt_adaptive.h)
     };
-    const float *src_points;       // mode 2 and 3: src_n / src_streams x {p.xyz, n.xyz} (rt_bake_point)
-    uint32_t src_streams;          // mode 2 and 3: slots per point
+    union {                        // again one pointer's room, for mode 4, which has no points
+        const float *src_points;   // mode 2 and 3: src_n / src_streams x {p.xyz, n.xyz} (rt_bake_point)
+        int32_t src_frame[2];      // mode 4: width and height of the real frame, which wf_camera_ray takes in place of the strip's
+    };
+    union {
+        uint32_t src_streams;      // mode 2 and 3: slots per point
+        float src_tan_fov_x;       // mode 4: the real frame's tan_fov_x
+    };
 };
 
 } // namespace rtamd

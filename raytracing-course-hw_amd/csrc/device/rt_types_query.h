@@ -134,6 +134,8 @@ struct SourceChunk {
     int32_t ray_depth, samples;
     uint32_t *state;
     float *sh;                    // mode 3
+    const uint32_t *pixels;       // mode 4: n x (x | y << 16) of the real frame (rt_adaptive.h)
+    int32_t frame_w, frame_h;     // mode 4: the real frame, whose camera the slots' rays come from
 };
 struct SourceResult { float kernel_ms; uint32_t launches, reference_exact; uint64_t exact_walks, no_path; };
 

@@ -22,6 +22,7 @@
 #include "device/rt_query_scatter.h"
 #include "device/rt_bake.h"
 #include "device/rt_persistent.h"
+#include "device/rt_adaptive.h"
 #include "device/rt_kernels_hw6.h"
 #include "device/rt_persistent_hw6.h"
 #include "device/rt_kernels_txt.h"
@@ -347,7 +348,10 @@ static PersistentKernel hw8_persistent(const SceneView &V, int ray_depth, hipStr
                 dev::WfView W{};
                 W.r0 = records; W.stride = stride; W.n_slots = n_slots; W.slot_base = slot_base;
                 const dim3 grid(blocks), block(P8_THREADS);
-                if (R.src_mode == PT_SRC_PROBES) { // SH9 probes: the source kernel compiled with the side arrays (WF_FEAT_PROBES)
+                if (R.src_mode == PT_SRC_PIXELS) { // the pixels of another frame (rt_adaptive_*): the source kernel compiled for them (WF_FEAT_PIXELS)
+                    if (feat == WF_FEAT_ENV) hipLaunchKernelGGL((dev::pt_persistent_kernel<false, WF_FEAT_SOURCE | WF_FEAT_PIXELS | WF_FEAT_ENV>), grid, block, 0, stream, V, R, W, P);
+                    else hipLaunchKernelGGL((dev::pt_persistent_kernel<false, WF_FEAT_SOURCE | WF_FEAT_PIXELS>), grid, block, 0, stream, V, R, W, P);
+                } else if (R.src_mode == PT_SRC_PROBES) { // SH9 probes: the source kernel compiled with the side arrays (WF_FEAT_PROBES)
                     if (feat == WF_FEAT_ENV) hipLaunchKernelGGL((dev::pt_persistent_kernel<false, WF_FEAT_SOURCE | WF_FEAT_PROBES | WF_FEAT_ENV>), grid, block, 0, stream, V, R, W, P);
                     else hipLaunchKernelGGL((dev::pt_persistent_kernel<false, WF_FEAT_SOURCE | WF_FEAT_PROBES>), grid, block, 0, stream, V, R, W, P);
                 } else if (R.src_mode) { // a path source (device/rt_path_source.h; source_render below): hw8 only, no counting variant
@@ -1250,6 +1254,11 @@ int rtamd::source_render(rt_scene *scene, const SourceChunk &C, hipStream_t stre
     const double t0 = now_ms();
     F.R.src_mode = C.mode; F.R.src_n = C.n; F.R.src_rays = C.rays; F.R.src_points = C.points; F.R.src_streams = C.streams;
     if (C.mode == PT_SRC_PROBES) F.R.src_sh = C.sh; // shares its room with src_rays (RenderView), which mode 3 has none of
+    if (C.mode == PT_SRC_PIXELS) { // likewise: the pixel words, and the real frame's constants where the points and streams of modes 2 and 3 are
+        F.R.src_pixels = C.pixels;
+        F.R.src_frame[0] = C.frame_w; F.R.src_frame[1] = C.frame_h;
+        F.R.src_tan_fov_x = frame_tan_fov_x(scene->view, C.frame_w, C.frame_h);
+    }
     launch_frame(scene, &p, F, stream, true);
     rt_stats st{};
     if (const int rc = collect_frame(scene, F, stream, &st, t0, who)) return rc;
@@ -1259,3 +1268,35 @@ int rtamd::source_render(rt_scene *scene, const SourceChunk &C, hipStream_t stre
     res.exact_walks = st.exact_closest_hits + st.exact_light_sums; res.no_path = no_path;
     return RT_OK;
 }
+
+// ---- rt_adaptive_*: the flat kernels around the pixel source (device/rt_adaptive.h; the host side is rtamd_adaptive.hip) ---------------------
+namespace {
+template <class K> uint32_t adaptive_launch(K kernel, const rt_scene *scene, uint32_t lanes, const RenderView &R, const AdaptiveView &V, hipStream_t stream) {
+    if (!lanes) return 0u;
+    hipLaunchKernelGGL(kernel, dim3(query_geometry(scene, lanes).flat_blocks), dim3(256), 0, stream, R, V);
+    HIP_CHECK(hipGetLastError());
+    return 1u;
+}
+} // namespace
+
+uint32_t rtamd::adaptive_launch_gather(const rt_scene *scene, const RenderView &R, const AdaptiveView &V, hipStream_t stream) {
+    return adaptive_launch(dev::ad_gather_kernel, scene, V.strip_slots, R, V, stream);
+}
+uint32_t rtamd::adaptive_launch_scatter(const rt_scene *scene, const RenderView &R, const AdaptiveView &V, hipStream_t stream) {
+    return adaptive_launch(dev::ad_scatter_kernel, scene, V.n_list * 64u, R, V, stream);
+}
+uint32_t rtamd::adaptive_launch_resolve(const rt_scene *scene, const RenderView &R, const AdaptiveView &V, hipStream_t stream) {
+    return adaptive_launch(dev::ad_resolve_kernel, scene, R.n_pixslots, R, V, stream);
+}
+uint32_t rtamd::adaptive_launch_update(const rt_scene *scene, const RenderView &R, const AdaptiveView &V, hipStream_t stream) {
+    return adaptive_launch(dev::ad_update_kernel, scene, V.n_list * 64u, R, V, stream);
+}
+uint32_t rtamd::adaptive_launch_estimate(const rt_scene *scene, const RenderView &R, const AdaptiveView &V, hipStream_t stream) {
+    return adaptive_launch(dev::ad_estimate_kernel, scene, R.n_pixslots, R, V, stream);
+}
+void rtamd::adaptive_launch_seed(const rt_scene *, const RenderView &R, hipStream_t stream) {
+    if (!R.n_pixslots) return;
+    hipLaunchKernelGGL(dev::accum_seed_kernel, dim3((R.n_pixslots + 255u) / 256u), dim3(256), 0, stream, R);
+    HIP_CHECK(hipGetLastError());
+}
+float rtamd::adaptive_tan_fov_x(const rt_scene *scene, int32_t width, int32_t height) { return frame_tan_fov_x(scene->view, width, height); }

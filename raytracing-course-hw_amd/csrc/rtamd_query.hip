@@ -17,6 +17,7 @@
 #include "host/knobs.h"
 #include "host/rt_scene.h"
 #include "device/rt_types_query.h"
+#include "device/rt_types_adaptive.h"
 
 using namespace rtamd;
 
@@ -379,6 +380,15 @@ uint32_t launch_round(rt_scene *scene, const QueryStage &S, const ScatterView &V
 // lowers it as it does for the composed calls.
 const size_t SOURCE_CHUNK = 2073600;
 size_t source_chunk() { return std::min(SOURCE_CHUNK, (size_t)std::max(64, env_positive("RTAMD_QUERY_CHUNK", (int)SOURCE_CHUNK))); }
+
+} // namespace
+// The same loop for rtamd_adaptive.hip, whose chunks are stretches of its list of active sub-tiles and carry no caller arrays.
+size_t rtamd::source_chunk_slots() { return source_chunk(); }
+int rtamd::source_chunks(size_t items, size_t chunk_items, hipStream_t stream, const std::function<int(size_t first, size_t m)> &body) {
+    struct { Arr none; } A{Arr{nullptr, 0u, nullptr, 0}};
+    return chunks(items, chunk_items, true, A, stream, nullptr, body);
+}
+namespace {
 
 // One call: `items` rays (K = 1) or points of K slots each.  `in`: the rays or the points, 24 bytes an item.  `floats`: the answer per item,
 // 3, or 27 for SH9 probes (mode 3), whose slots also keep 120 bytes each beside the state: the first direction and the 27 accumulators.

@@ -14,6 +14,7 @@
 #include "host/device_build.h"
 #include "host/fold_nodes.h"
 #include "host/hip_check.h"
+#include "host/rt_adaptive_decide.h"
 #include "host/rt_guard.h"
 #include "host/rt_scene.h"
 #include "host/scene_prep.h"
@@ -969,6 +970,13 @@ int rtt_gather_records(const void *records, uint32_t n, uint32_t elem_bytes, con
 }
 // The guard of the C boundary (host/rt_guard.h) around a body that throws a HipError (kind 0), a std::bad_alloc (1), a std::runtime_error (2)
 // or an int (3), or returns 5 (anything else): the guard's answer; the message is in the library's rt_last_error().  Host only.
+// The decision of an adaptive slice (host/rt_adaptive_decide.h) on a table of the test's own: sub_w * sub_h entries in, their new flags out.
+int rtt_adaptive_decide(const rt_adaptive_tile *tiles, const rt_adaptive_params *params, int32_t sub_w, int32_t sub_h, int32_t n_samples, uint32_t *flags) {
+    if (!tiles || !params || !flags || sub_w < 1 || sub_h < 1) return RT_ERR_INVALID_ARG;
+    rtamd::adaptive_decide(tiles, *params, sub_w, sub_h, n_samples, flags);
+    return RT_OK;
+}
+
 int rtt_guard_probe(int kind) {
     return rtamd::guarded("rtt_guard_probe: ", [&]() -> int {
         if (kind == 0) throw rtamd::HipError("hipProbe(): failed");
