@@ -949,6 +949,81 @@ int  rt_adaptive_noise(rt_adaptive *a, uint32_t flags, float *out_se /* nullable
 int  rt_adaptive_sample_map(rt_adaptive *a, int32_t *out /* W*H */);
 void rt_adaptive_destroy(rt_adaptive *a);
 
+/* ---- view sets: a batch of cameras over one live scene -------------------------------------------------------------------------
+ * A scene is bound to the one camera of its rt_scene_desc; a second viewpoint used to mean rt_scene_create again.  An rt_views renders
+ * n_views cameras of the caller's, one frame size for all, from the scene as it stands, many small views in one launch.  It owns its
+ * state -- rt_accum's, 24 bytes per pixel slot, per view -- and only READS the scene: the scene's own camera, its node grid, box_c2,
+ * every rt_accum and rt_adaptive on it and the next rt_render see nothing of a view set.  ABI version 6 still: additions only.
+ *
+ * Contract   on a scene whose renders report reference_exact = 1, view v after d samples holds, bit for bit, floats and bytes, what
+ *          rt_render(samples = d) returns on a scene created from the same rt_scene_desc with camera = cameras[v] -- whatever the other
+ *          views are, whatever they drew and however the samples were sliced (tests/test_gpu_views.py).  The engines are the
+ *          reference's: pixel (x, y) of every view starts from minstd_rand(y * W + x).  On a scene with reference_exact = 0 the calls
+ *          are served and the stats say 0; equality is then not promised, as with rt_render_bake.
+ * Cameras    position, right, up, forward and fov_y are used as given (not normalised, not orthogonalised, as the reference uses
+ *          them); tan_fov_y = (float)tan((double)(fov_y / 2)) by the host libm and tan_fov_x = tan_fov_y * width / height, the
+ *          expressions of the scene's own camera.  fov_x is ignored.
+ * A slice    (rt_views_render) every view with mask[v] != 0 -- a NULL mask: every view -- draws n_samples more samples; counts are
+ *          per view (rt_views_samples).  The state of the active views' 8x8 sub-tiles is gathered into a compact strip, the persistent
+ *          hw8 kernel runs a slice of a resumable render over it with a path source of its own (src_mode 5, device/rt_path_source.h:
+ *          the camera ray of the view behind each slot, from a device array of per-view camera records), and the state is scattered
+ *          back.  Every kernel that existed before is, instruction for instruction, the one it was.  More active pixel slots than one
+ *          path-source chunk (2,073,600; RTAMD_QUERY_CHUNK lowers it) run in chunks of whole sub-tiles.  With no active view the call
+ *          is RT_OK, launches nothing and reports samples = 0.
+ * First rays  the walkers' 16-bit node grid and the query layer's origin bound were derived for the SCENE's camera.  A view's first
+ *          ray whose origin lies outside the grid or beyond the bound, or that pierces a tripwire, is the exact role's from the start
+ *          (pt_source_exact, as rt_render_paths' rays): the pixels are the same, the speed is not.  Create the scene with a camera
+ *          that spans the volume the views will move in; profiles/r36_views.txt has the cost when every first ray is exact.
+ * rt_views_set_cameras   replaces the cameras of views first .. first + n - 1 and resets those views: sum 0, engines reseeded,
+ *          0 samples.  The other views are untouched.
+ * rt_views_resolve   view `view`: (float)(1.0 / d_v) * sum and the tonemapped bytes, W x H x 3 row-major, host memory or with
+ *          RT_FLAG_OUT_DEVICE memory on the scene's GPU, as rt_accum_resolve.  A view with 0 samples is RT_ERR_INVALID_ARG.  The state
+ *          is only read.
+ * stats    active_views: views this call drew for; samples: camera samples drawn (active views x W x H x n_samples); min_samples /
+ *          max_samples per pixel over all views when the call returns; kernel_ms: the persistent kernel's launches; gather_ms /
+ *          scatter_ms: the two kernels around it; total_ms: host wall time of the call; exact_walks: closest hits and light sums the
+ *          exact role answered.
+ * Refusals   before any device work, the state untouched; the message names the field and, where it applies, the view.
+ *          RT_ERR_INVALID_ARG: null arguments, struct_size of the params or the stats, reserved words or flags other than 0,
+ *          n_views < 1, width or height below 1, first / n / view out of range, n_samples <= 0, a broken object, and a bad camera: a
+ *          component that is not finite or above 2^40 in magnitude (with that bound no float expression of the camera ray overflows
+ *          at any frame size allowed here), fov_y outside (0, 3], or right, up and forward not linearly independent (the determinant
+ *          in double against the product of the three lengths; with independent vectors cx * right - cy * up + forward is never
+ *          zero, so no first direction is a NaN).  RT_ERR_LIMIT: width or height above 65,535 (a slot's pixel is one packed word),
+ *          ray_depth above 16, n_views x the pixel slots of a view (64 per 8x8 sub-tile) at or above 2^31, and a slice that would
+ *          take an active view's count to the path records' sample index limit (2^25).  RT_ERR_UNSUPPORTED, no fallback, as
+ *          rt_adaptive_create answers: scenes that are not hw8 scenes, and whatever keeps the persistent hw8 kernel from the scene
+ *          (RTAMD_KERNEL=wavefront|mega, a tree beyond its stack columns).  A slice that fails under way leaves the object broken,
+ *          as with rt_accum.
+ * Out of scope   checkpoints of a view set; rt_noise, rt_denoise, guide images and rt_camera_rays for a view's camera; rt_multi_*;
+ *          hw7 and hw6; adaptive sampling per view; views of different sizes.
+ * Measured on one MI355X: profiles/r36_views.txt. */
+typedef struct rt_views_params {
+    uint32_t struct_size;
+    int32_t  width, height;   /* one frame size for all views; 1 .. 65,535 each */
+    int32_t  ray_depth;       /* 0 = 6; > 16: RT_ERR_LIMIT */
+    int32_t  n_views;         /* >= 1; n_views * pixel slots of a view < 2^31 */
+    uint32_t flags;           /* 0 */
+    void    *stream;          /* hipStream_t of the set's launches and copies; NULL = the default stream */
+    uint32_t reserved[2];     /* 0 */
+} rt_views_params;
+typedef struct rt_views_stats {
+    uint32_t struct_size;                   /* in: sizeof(rt_views_stats) */
+    uint32_t active_views;
+    uint64_t samples;                       /* camera samples drawn by this call */
+    int32_t  min_samples, max_samples;      /* per pixel, over the views */
+    double   kernel_ms, gather_ms, scatter_ms, total_ms;
+    uint32_t launches, reference_exact;
+    uint64_t exact_walks;
+} rt_views_stats;
+typedef struct rt_views rt_views;
+int  rt_views_create(rt_scene *scene, const rt_views_params *params, const rt_camera *cameras /* n_views */, rt_views **out);
+int  rt_views_set_cameras(rt_views *v, int32_t first, int32_t n, const rt_camera *cameras /* n */);
+int  rt_views_render(rt_views *v, int32_t n_samples, const uint8_t *mask /* nullable: n_views bytes */, rt_views_stats *stats);
+int  rt_views_samples(const rt_views *v, int32_t *out /* n_views */);
+int  rt_views_resolve(rt_views *v, int32_t view, uint32_t flags /* RT_FLAG_OUT_DEVICE */, float *out_rgb /* nullable */, uint8_t *out_rgb8 /* nullable */);
+void rt_views_destroy(rt_views *v);
+
 /* Scene info the host side needs after preparation. */
 typedef struct rt_scene_info {
     uint32_t n_triangles, n_lights, n_bvh_nodes, n_light_bvh_nodes;

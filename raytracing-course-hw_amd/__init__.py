@@ -171,6 +171,17 @@ class rt_adaptive_stats(C.Structure):
                 ("reference_exact", C.c_uint32), ("exact_walks", C.c_uint64)]
 
 
+class rt_views_params(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("width", C.c_int32), ("height", C.c_int32), ("ray_depth", C.c_int32), ("n_views", C.c_int32),
+                ("flags", C.c_uint32), ("stream", C.c_void_p), ("reserved", C.c_uint32 * 2)]
+
+
+class rt_views_stats(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("active_views", C.c_uint32), ("samples", C.c_uint64), ("min_samples", C.c_int32),
+                ("max_samples", C.c_int32), ("kernel_ms", C.c_double), ("gather_ms", C.c_double), ("scatter_ms", C.c_double),
+                ("total_ms", C.c_double), ("launches", C.c_uint32), ("reference_exact", C.c_uint32), ("exact_walks", C.c_uint64)]
+
+
 # rt_adaptive_tile as a numpy record: what AdaptiveRender.tiles() returns, one per 8x8 sub-tile
 ADAPTIVE_TILE_DTYPE = np.dtype([("samples", np.int32), ("batches", np.int32), ("pixels", np.uint32), ("nonfinite", np.uint32),
                                 ("sum_se2", np.float32), ("sum_luminance", np.float32), ("flags", np.uint32), ("reserved", np.uint32)])
@@ -204,7 +215,8 @@ ABI_SYMBOLS = ["rt_abi_version", "rt_last_error", "rt_scene_create", "rt_scene_d
                "rt_query_occluded", "rt_rng_seed", "rt_query_scatter", "rt_query_bsdf", "rt_trace_paths", "rt_bake_rays", "rt_bake",
                "rt_render_paths", "rt_render_bake", "rt_render_probes", "rt_adaptive_create", "rt_adaptive_render",
                "rt_adaptive_render_tiles", "rt_adaptive_tiles", "rt_adaptive_resolve", "rt_adaptive_noise", "rt_adaptive_sample_map",
-               "rt_adaptive_destroy"]
+               "rt_adaptive_destroy", "rt_views_create", "rt_views_set_cameras", "rt_views_render", "rt_views_samples", "rt_views_resolve",
+               "rt_views_destroy"]
 # The preview filter's two, which the header declares `extern int`: the list above and the family lists of the tests are closed sets
 # of the header's plain prototypes (tests/test_abi_and_host.py, tests/test_accum_host.py), and rt_accum_denoise is no rt_accum_* of theirs.
 DENOISE_SYMBOLS = ["rt_denoise", "rt_accum_denoise"]
@@ -291,6 +303,13 @@ lib.rt_adaptive_noise.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(
 lib.rt_adaptive_sample_map.argtypes = [C.c_void_p, C.c_void_p]
 lib.rt_adaptive_destroy.argtypes = [C.c_void_p]
 lib.rt_adaptive_destroy.restype = None
+lib.rt_views_create.argtypes = [C.c_void_p, C.POINTER(rt_views_params), C.c_void_p, C.POINTER(C.c_void_p)]
+lib.rt_views_set_cameras.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
+lib.rt_views_render.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(rt_views_stats)]
+lib.rt_views_samples.argtypes = [C.c_void_p, C.c_void_p]
+lib.rt_views_resolve.argtypes = [C.c_void_p, C.c_int32, C.c_uint32, C.c_void_p, C.c_void_p]
+lib.rt_views_destroy.argtypes = [C.c_void_p]
+lib.rt_views_destroy.restype = None
 lib.rt_denoise.argtypes = [C.c_void_p, C.POINTER(rt_denoise_params)] + [C.c_void_p] * 8 + [C.POINTER(rt_denoise_stats)]
 lib.rt_accum_denoise.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(rt_denoise_params), C.c_void_p, C.c_void_p, C.POINTER(rt_denoise_stats)]
 
@@ -529,6 +548,23 @@ def _adaptive_stats():
     st = rt_adaptive_stats()
     st.struct_size = C.sizeof(rt_adaptive_stats)
     return st
+
+
+def make_views_params(width, height, n_views, ray_depth=0, stream=None):
+    """rt_views_params; ray_depth 0 selects the default (6)."""
+    p = rt_views_params()
+    p.struct_size = C.sizeof(rt_views_params)
+    p.width, p.height, p.n_views, p.ray_depth, p.stream = width, height, n_views, ray_depth, stream
+    return p
+
+
+def _camera_array(cameras):
+    """A contiguous array of rt_camera from a sequence of them (one rt_camera alone counts as a sequence of one)."""
+    cameras = [cameras] if isinstance(cameras, rt_camera) else list(cameras)
+    arr = (rt_camera * max(1, len(cameras)))()
+    for i, c in enumerate(cameras):
+        arr[i] = c
+    return arr, len(cameras)
 
 
 def make_denoise_params(width, height, iterations=0, sigma_depth=0.0, sigma_luminance=0.0, flags=0):
@@ -844,6 +880,49 @@ class AdaptiveRender(_Handle):
         return out
 
 
+class ViewSet(_Handle):
+    """A batch of cameras over one Scene (rt_views): render(n, mask) draws n more samples for the views whose byte of `mask` is not 0
+    (None: all); view v after d samples holds what a Scene created with cameras[v] renders with samples = d.  The scene is only read.
+    Keywords: ray_depth, stream."""
+    _destroy = "rt_views_destroy"
+
+    def __init__(self, scene, width, height, cameras, **kw):
+        self.scene = scene  # keeps the scene alive: an rt_views is destroyed before its scene
+        arr, n = _camera_array(cameras)
+        self.params = make_views_params(width, height, n, **kw)
+        self._open(scene)
+        _check(lib.rt_views_create(scene._h, C.byref(self.params), C.cast(arr, C.c_void_p), C.byref(self._h)))
+
+    def render(self, n_samples, mask=None):
+        if mask is not None:
+            mask = np.ascontiguousarray(np.asarray(mask).astype(np.uint8).reshape(-1))
+            if mask.size != self.params.n_views:
+                raise ValueError(f"mask must hold one byte per view ({self.params.n_views}), got {mask.size}")
+        st = rt_views_stats()
+        st.struct_size = C.sizeof(rt_views_stats)
+        _check(lib.rt_views_render(self._h, n_samples, mask.ctypes.data if mask is not None else None, C.byref(st)))
+        return st
+
+    def samples(self):
+        """Samples drawn per view, int32 (n_views,)."""
+        out = np.zeros(self.params.n_views, dtype=np.int32)
+        _check(lib.rt_views_samples(self._h, out.ctypes.data))
+        return out
+
+    def resolve(self, view, want_float=True, want_rgb8=True):
+        """(rgb float32, rgb8) of one view, (H, W, 3) each."""
+        h, w = self.params.height, self.params.width
+        rgb = np.zeros((h, w, 3), dtype=np.float32) if want_float else None
+        rgb8 = np.zeros((h, w, 3), dtype=np.uint8) if want_rgb8 else None
+        _check(lib.rt_views_resolve(self._h, view, 0, rgb.ctypes.data if want_float else None, rgb8.ctypes.data if want_rgb8 else None))
+        return rgb, rgb8
+
+    def set_cameras(self, first, cameras):
+        """New cameras for views first .. first + len(cameras) - 1, which start over at 0 samples."""
+        arr, n = _camera_array(cameras)
+        _check(lib.rt_views_set_cameras(self._h, first, n, C.cast(arr, C.c_void_p)))
+
+
 class Scene(_Handle):
     """A prepared scene resident in HBM on the current HIP device (rt_scene)."""
     _destroy = "rt_scene_destroy"
@@ -889,6 +968,10 @@ class Scene(_Handle):
     def adaptive(self, width, height, target_noise, **kw):
         """An adaptive render of this scene (AdaptiveRender)."""
         return AdaptiveRender(self, width, height, target_noise, **kw)
+
+    def views(self, width, height, cameras, **kw):
+        """A batch of cameras over this scene (ViewSet)."""
+        return ViewSet(self, width, height, cameras, **kw)
 
     def render_device(self, params, out_rgb_ptr, out_rgb8_ptr):
         """Render into device buffers (raw pointers, e.g. torch tensor data_ptr())."""

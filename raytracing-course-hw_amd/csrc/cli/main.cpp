@@ -29,7 +29,12 @@
 // on stderr: the sub-tiles that drew, the converged and the capped ones, the frame's noise.  RTAMD_SAMPLE_MAP=path writes the samples per
 // pixel as a grayscale PFM.  out.ppm is rt_adaptive_resolve's bytes: every sub-tile the plain run's picture at that sub-tile's count.
 // On several GPUs, with another snapshot or with a checkpoint the run ends with an error that names the reason.
+// A batch of cameras (rt_views_*, glTF surface, hw8, one GPU): RTAMD_CAMERAS=file gives one camera per line as 13 floats -- position,
+// right, up, forward, fov_y; empty lines and lines that begin with # are skipped.  The run renders all of them as one view set from the
+// one scene, in one slice or with RTAMD_SLICE in slices of that many samples, and writes out_000.ppm, out_001.ppm, ... beside the named
+// output (its name before the extension, then the camera's number).  A malformed line ends the run with RT_ERR_PARSE and names the line.
 #include "../../../include/rtamd.h"
+#include "../host/knobs.h"
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -272,6 +277,73 @@ static int render_adaptive(rt_scene *scene, const rt_render_params &p, int slice
     return 0;
 }
 
+// RTAMD_CAMERAS: the file's cameras, one per line; false (and the message printed) for a file that cannot be read or a malformed line.
+static bool read_cameras(const char *path, std::vector<rt_camera> &cameras) {
+    FILE *f = fopen(path, "r");
+    if (!f) { fprintf(stderr, "error: RTAMD_CAMERAS: cannot open %s\n", path); return false; }
+    char line[1024];
+    for (int number = 1; fgets(line, sizeof line, f); number++) {
+        const char *c = line + strspn(line, " \t\r\n");
+        if (*c == 0 || *c == '#') continue;
+        float v[13];
+        int n = 0;
+        for (; n < 13; n++) {
+            char *end = nullptr;
+            v[n] = strtof(c, &end);
+            if (end == c) break;
+            c = end;
+        }
+        if (n < 13 || c[strspn(c, " \t\r\n")] != 0) {
+            fprintf(stderr, "error: RTAMD_CAMERAS: %s line %d: a camera is 13 numbers (position, right, up, forward, fov_y) and nothing else (RT_ERR_PARSE, %d)\n", path, number, (int)RT_ERR_PARSE);
+            fclose(f);
+            return false;
+        }
+        rt_camera cam;
+        memset(&cam, 0, sizeof cam);
+        for (int k = 0; k < 3; k++) { cam.position[k] = v[k]; cam.right[k] = v[3 + k]; cam.up[k] = v[6 + k]; cam.forward[k] = v[9 + k]; }
+        cam.fov_y = v[12];
+        cameras.push_back(cam);
+    }
+    fclose(f);
+    if (cameras.empty()) { fprintf(stderr, "error: RTAMD_CAMERAS: %s holds no camera\n", path); return false; }
+    return true;
+}
+
+// RTAMD_CAMERAS=file: all cameras as one view set, p.samples samples each in slices of `slice` (0: one slice), one PPM per camera.
+static int render_views(rt_scene *scene, const rt_render_params &p, int slice, const std::vector<rt_camera> &cameras, const char *out_path, std::vector<uint8_t> &rgb8) {
+    rt_views_params vp;
+    memset(&vp, 0, sizeof vp);
+    vp.struct_size = sizeof vp;
+    vp.width = p.width; vp.height = p.height; vp.ray_depth = p.ray_depth; vp.n_views = (int32_t)cameras.size();
+    rt_views *views = nullptr;
+    if (rt_views_create(scene, &vp, cameras.data(), &views) != RT_OK) return die();
+    auto fail = [&]() { const int rc = die(); rt_views_destroy(views); return rc; };
+    double kernel_ms = 0;
+    uint64_t samples = 0;
+    for (int done = 0; done < p.samples;) {
+        const int n = slice > 0 && slice < p.samples - done ? slice : p.samples - done;
+        rt_views_stats st;
+        memset(&st, 0, sizeof st);
+        st.struct_size = sizeof st;
+        if (rt_views_render(views, n, nullptr, &st) != RT_OK) return fail();
+        done += n; kernel_ms += st.kernel_ms; samples += st.samples;
+        if (slice > 0) fprintf(stderr, "slice: %u views drew %d samples, %d of %d, %.3f ms on the GPU, %llu first rays and bounces by the exact role\n", st.active_views, n, done, p.samples,
+                               st.kernel_ms, (unsigned long long)st.exact_walks);
+    }
+    fprintf(stderr, "render: %zu views, %.3f ms on the GPU, %.2f Msamples/s\n", cameras.size(), kernel_ms, samples / (kernel_ms * 1e3));
+    std::string stem = out_path;
+    const size_t dot = stem.rfind('.'), slash = stem.find_last_of('/');
+    if (dot != std::string::npos && (slash == std::string::npos || dot > slash)) stem.resize(dot);
+    for (size_t v = 0; v < cameras.size(); v++) {
+        char tail[32];
+        snprintf(tail, sizeof tail, "_%03zu.ppm", v);
+        if (rt_views_resolve(views, (int32_t)v, 0, nullptr, rgb8.data()) != RT_OK) return fail();
+        if (rt_write_ppm((stem + tail).c_str(), p.width, p.height, rgb8.data()) != RT_OK) return fail();
+    }
+    rt_views_destroy(views);
+    return 0;
+}
+
 int main(int argc, const char *argv[]) {
     const char *snap = getenv("RTAMD_SNAPSHOT");
     rt_host_scene *hs = nullptr;
@@ -356,6 +428,16 @@ int main(int argc, const char *argv[]) {
                           : preview.path ? "an adaptive render has no denoised preview (RTAMD_DENOISE)" : nullptr;
         if (why) { fprintf(stderr, "error: RTAMD_ADAPTIVE: %s\n", why); return 1; }
     }
+    std::vector<rt_camera> cameras; // RTAMD_CAMERAS: one GPU and hw8 only; what else stands in the way is the library's to say (rt_views_create)
+    if (const char *path = argc >= 6 ? rtamd::env_str("RTAMD_CAMERAS") : nullptr) {
+        const char *why = p.integrator != RT_INTEGRATOR_HW8 ? "it runs the hw8 integrator only (RTAMD_SNAPSHOT=hw8, the default)"
+                          : (!list.empty() || n_dev > 1) ? "it runs on one GPU (RTAMD_DEVICES=1; no RTAMD_DEVICE_LIST)"
+                          : adaptive ? "a view set has no adaptive sampling (RTAMD_ADAPTIVE)"
+                          : (checkpoint || noise.active() || preview.path) ? "a view set has no checkpoint, noise monitor or denoised preview (RTAMD_CHECKPOINT, RTAMD_TARGET_NOISE, RTAMD_NOISE_MAP, RTAMD_DENOISE)"
+                          : p.sample_streams > 1 ? "a view set renders in replay mode (no RTAMD_STREAMS)" : nullptr;
+        if (why) { fprintf(stderr, "error: RTAMD_CAMERAS: %s\n", why); return 1; }
+        if (!read_cameras(path, cameras)) return 1;
+    }
     rt_multi *multi = nullptr; // all devices, or ...
     rt_scene *scene = nullptr; // ... one
     if ((!list.empty() || n_dev > 1) && p.integrator != RT_INTEGRATOR_HW1) {
@@ -367,6 +449,13 @@ int main(int argc, const char *argv[]) {
         const int rc = write_guides(scene ? scene : own, p, prefix);
         rt_scene_destroy(own);
         if (rc) return rc;
+    }
+    if (!cameras.empty()) {
+        const int rc = render_views(scene, p, slice, cameras, out_path, rgb8);
+        rt_scene_destroy(scene);
+        rt_host_scene_free(hs);
+        if (rc == 0) fprintf(stderr, "FINISH\n");
+        return rc;
     }
     if (adaptive) {
         const int rc = render_adaptive(scene, p, slice, noise, out_path, rgb8);

@@ -30,6 +30,17 @@
 // (rt_persistent.h), not at pt_source_exact.  The pixels are the same either way (the exact role and the walkers agree on every ray
 // the gate lets the walkers keep); the camera kernels' rule is the cheaper one and the one rt_render itself runs.
 //
+// A batch of cameras over one scene (include/rtamd.h: rt_views_*) is the fifth kernel, compiled with WF_FEAT_SOURCE | WF_FEAT_VIEWS and only
+// ever launched with
+//   src_mode 5   wf_camera_ray's expressions for pixel src_pixels[gslot] = x | y << 16 of a frame of src_wh = width | height << 16 pixels,
+//                the camera's values from record src_cameras[v], v = src_pixels[src_n + gslot / 64] the view behind the slot's 64-slot
+//                group (src_n is a multiple of 64); drawn from the slot's engine; `samples` samples per slot
+// The strip's slots are the pixel slots of the active views' 8x8 sub-tiles, gathered by vw_gather_kernel (rt_views.h), which works pixel
+// and view out.  Padding is an engine word of 0 as in mode 4.  The record is read for every first ray, 64 bytes as four 16-byte words,
+// and is dead once the ray is in the path record: no camera lives in registers across the path.  A view's camera may lie anywhere, so
+// UNLIKE mode 4 this source keeps pt_source_exact for every first ray: a camera outside the node grid or beyond the origin bound
+// sends its rays to the exact role, one inside both takes the walkers as the scene's own camera does.
+//
 // The frame.  An unsharded strip 8 pixels wide and 8 * ceil(n / 64) high: its tiles are the 8x8 sub-tiles themselves, one per row of the
 // tile grid, so slot_to_pixel (rt_device.h) maps sub-tile s, pixel (x, y) of it to slot 64 s + 8 y + x -- gslot IS the record index.  The
 // pixel coordinates are never used (no camera ray, no pixel store).
@@ -57,6 +68,7 @@ namespace dev {
 #define PT_SRC_BAKE 2u
 #define PT_SRC_PROBES 3u
 #define PT_SRC_PIXELS 4u
+#define PT_SRC_VIEWS 5u
 #define PT_SH_FLOATS 30u // per slot of RenderView::src_sh: d0.xyz, then acc[9][3]
 
 RT_DEV void pt_source_load_ray(const float *rays, uint32_t i, F3 &o, F3 &d) { // rt_ray is only 4-byte aligned
@@ -75,7 +87,7 @@ template <int32_t MODE> RT_DEV bool pt_source_point(const RenderView &R, uint32_
 }
 // Whether a slot without a path counts (once per invalid record / point; the padding of the last 64-slot group does not).
 template <int FEAT> RT_DEV bool pt_source_counts(const RenderView &R, uint32_t gslot) {
-    if constexpr ((FEAT & WF_FEAT_PIXELS) != 0) return false; // mode 4: a slot without a path is padding
+    if constexpr ((FEAT & (WF_FEAT_PIXELS | WF_FEAT_VIEWS)) != 0) return false; // mode 4 and 5: a slot without a path is padding
     if constexpr ((FEAT & WF_FEAT_PROBES) != 0) return gslot < R.src_n && gslot % R.src_streams == 0u;
     else return gslot < R.src_n && (R.src_mode != PT_SRC_BAKE || gslot % R.src_streams == 0u);
 }
@@ -120,10 +132,24 @@ RT_DEV void pt_source_pixel_ray(const SceneView &S, const RenderView &R, uint32_
     wf_camera_ray_of(S, R.src_tan_fov_x, R.src_frame[0], R.src_frame[1], rng, (int)(xy & 0xffffu), (int)(xy >> 16), o, d);
 }
 
+// Mode 5: the ray of the camera of the slot's view through the pixel behind strip slot `gslot`.
+RT_DEV void pt_source_view_ray(const RenderView &R, uint32_t gslot, Rng &rng, F3 &o, F3 &d) {
+    const uint32_t xy = R.src_pixels[gslot], view = R.src_pixels[R.src_n + (gslot >> 6)];
+    const float4 *c = reinterpret_cast<const float4 *>(R.src_cameras + view);
+    const float4 c0 = c[0], c1 = c[1], c2 = c[2], c3 = c[3]; // pos.xyz right.x | right.yz up.xy | up.z fwd.xyz | tan_fov_x tan_fov_y
+    wf_camera_ray_from(f3(c0.x, c0.y, c0.z), f3(c0.w, c1.x, c1.y), f3(c1.z, c1.w, c2.x), f3(c2.y, c2.z, c2.w), c3.x, c3.y,
+                       (int)(R.src_wh & 0xffffu), (int)(R.src_wh >> 16), rng, (int)(xy & 0xffffu), (int)(xy >> 16), o, d);
+}
+
 template <int FEAT> struct PtSource {
     // The first ray of slot `gslot`, whose engine `rng` comes from the state; false: the slot has no path.
     static RT_DEV bool first(const SceneView &S, const RenderView &R, uint32_t gslot, Rng &rng, F3 &o, F3 &d) {
         if (gslot >= R.src_n) return false;
+        if constexpr ((FEAT & WF_FEAT_VIEWS) != 0) {
+            if (!rq_rng_valid(rng.x)) return false;          // engine word 0: padding of a border sub-tile
+            pt_source_view_ray(R, gslot, rng, o, d);
+            return true;
+        }
         if constexpr ((FEAT & WF_FEAT_PIXELS) != 0) {
             if (!rq_rng_valid(rng.x)) return false;          // engine word 0: padding of a border sub-tile
             pt_source_pixel_ray(S, R, gslot, rng, o, d);
@@ -147,7 +173,9 @@ template <int FEAT> struct PtSource {
     }
     // The first ray of the slot's sample `next` (wf_finish_path): the slot has a path, so its record is valid.
     static RT_DEV void ray(const SceneView &S, const RenderView &R, Rng &rng, uint32_t gslot, int x, int y, uint32_t next, F3 &o, F3 &d) {
-        if constexpr ((FEAT & WF_FEAT_PIXELS) != 0) {
+        if constexpr ((FEAT & WF_FEAT_VIEWS) != 0) {
+            pt_source_view_ray(R, gslot, rng, o, d);
+        } else if constexpr ((FEAT & WF_FEAT_PIXELS) != 0) {
             pt_source_pixel_ray(S, R, gslot, rng, o, d);
         } else if constexpr ((FEAT & WF_FEAT_PROBES) != 0) {
             F3 p, n;

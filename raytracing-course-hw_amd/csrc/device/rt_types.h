@@ -210,6 +210,15 @@ struct SceneView {
     float tan_fov_y;               // (float)tan((double)(fovY / 2)), hw8/src/scene.cpp:180
 };
 
+// The camera of one view of a view set (include/rtamd.h: rt_views_*; rt_path_source.h, src_mode 5): what wf_camera_ray takes from the
+// scene and the frame, per view.  64 bytes, 16-byte aligned: a first ray reads it as four 16-byte words.
+struct alignas(16) ViewCamera {
+    float pos[3], right[3], up[3], fwd[3];
+    float tan_fov_x, tan_fov_y;    // (float)tan((double)(fov_y / 2)) * width / height and (float)tan((double)(fov_y / 2)), hw8/src/scene.cpp:180-181
+    float pad[2];
+};
+static_assert(sizeof(ViewCamera) == 64, "a view's camera is four 16-byte words");
+
 struct RenderView {
     int32_t width, height, samples, ray_depth;
     int32_t sample_stop;           // a path that reaches this sample index parks (its camera ray is in its record): the persistent
@@ -241,20 +250,23 @@ struct RenderView {
     int32_t sample_first;
     // The path source of the persistent hw8 kernel (rt_path_source.h, kernels compiled with WF_FEAT_SOURCE): where a sample's first ray comes
     // from.  Every other launch leaves these zero.  Indexed by the record index, which is the pixel slot (frame geometry: rt_path_source.h).
-    uint32_t src_mode;             // 0 = the camera, 1 = the caller's rays, 2 = bake irradiance, 3 = SH9 probes, 4 = the pixels of another frame
+    uint32_t src_mode;             // 0 = the camera, 1 = the caller's rays, 2 = bake irradiance, 3 = SH9 probes, 4 = the pixels of another frame, 5 = a batch of cameras
     uint32_t src_n;                // records (mode 2: points x streams); a slot at or beyond it starts no path
     union {                        // one pointer's room: the struct, and with it every kernel's argument block, is laid out as before mode 3
         const float *src_rays;     // mode 1: src_n x {o.xyz, d.xyz} (rt_ray), used as given
         float *src_sh;             // mode 3: src_n rounded up to 64 x {first direction xyz, 27 accumulators [m][c]}, slot-major, 8-byte aligned
         const uint32_t *src_pixels; // mode 4: src_n x (x | y << 16), the pixel of the real frame behind the strip slot (ad_gather_kernel, rt_adaptive.h)
+                                   // mode 5: the same (vw_gather_kernel, rt_views.h), then src_n / 64 x the view index of each 64-slot group
     };
     union {                        // again one pointer's room, for mode 4, which has no points
         const float *src_points;   // mode 2 and 3: src_n / src_streams x {p.xyz, n.xyz} (rt_bake_point)
         int32_t src_frame[2];      // mode 4: width and height of the real frame, which wf_camera_ray takes in place of the strip's
+        const ViewCamera *src_cameras; // mode 5: one record per view of the set, indexed by the group's view index
     };
     union {
         uint32_t src_streams;      // mode 2 and 3: slots per point
         float src_tan_fov_x;       // mode 4: the real frame's tan_fov_x
+        uint32_t src_wh;           // mode 5: width | height << 16 of the views' frame (both at most 65,535)
     };
 };
 

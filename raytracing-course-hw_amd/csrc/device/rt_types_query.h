@@ -128,6 +128,7 @@ struct SourceView {
     float *out;                   // unpack: n x 3 (mode 1), n / streams x 3 (mode 2) or n / streams x 27 (mode 3)
 };
 // One chunk through the persistent hw8 kernel with a path source: a slice of `samples` samples per slot of the strip frame over `state`.
+struct ViewCamera;                // rt_types.h, which this header does not need
 struct SourceChunk {
     uint32_t mode, n, streams;    // as in SourceView
     const float *rays, *points;
@@ -136,6 +137,7 @@ struct SourceChunk {
     float *sh;                    // mode 3
     const uint32_t *pixels;       // mode 4: n x (x | y << 16) of the real frame (rt_adaptive.h)
     int32_t frame_w, frame_h;     // mode 4: the real frame, whose camera the slots' rays come from
+    const ViewCamera *cameras;    // mode 5: `pixels` also holds n / 64 view indices, frame_w x frame_h is the views' frame (rt_views.h)
 };
 struct SourceResult { float kernel_ms; uint32_t launches, reference_exact; uint64_t exact_walks, no_path; };
 

@@ -99,15 +99,20 @@ RT_DEV void wf_sample_seed(const RenderView &R, Rng &rng, uint32_t gslot, int x,
     rng_seed(rng, h);
 }
 
-// The camera ray through pixel (x, y) of a frame of width x height pixels whose tan_fov_x is given: the frame being rendered
-// (wf_camera_ray), or the real frame behind the strip of a pixel source (rt_path_source.h, src_mode 4).
-RT_DEV void wf_camera_ray_of(const SceneView &S, float tan_fov_x, int width, int height, Rng &rng, int x, int y, F3 &o, F3 &d) {
+// The camera ray through pixel (x, y) of a frame of width x height pixels, the camera's values given: the scene's own (wf_camera_ray_of)
+// or those of a view's record (rt_path_source.h, src_mode 5).
+RT_DEV void wf_camera_ray_from(F3 pos, F3 right, F3 up, F3 fwd, float tan_fov_x, float tan_fov_y, int width, int height, Rng &rng, int x, int y, F3 &o, F3 &d) {
     float nx = (float)x + rng_u01(rng);                             // scene.cpp:172-173
     float ny = (float)y + rng_u01(rng);
     float cx = tan_fov_x * (2 * nx / (float)width - 1);             // scene.cpp:183-184
-    float cy = S.tan_fov_y * (2 * ny / (float)height - 1);
-    o = f3(S.cam_pos);
-    d = normalize(cx * f3(S.cam_right) - cy * f3(S.cam_up) + f3(S.cam_fwd));
+    float cy = tan_fov_y * (2 * ny / (float)height - 1);
+    o = pos;
+    d = normalize(cx * right - cy * up + fwd);
+}
+// The scene's camera and a frame of width x height pixels whose tan_fov_x is given: the frame being rendered (wf_camera_ray), or the
+// real frame behind the strip of a pixel source (rt_path_source.h, src_mode 4).
+RT_DEV void wf_camera_ray_of(const SceneView &S, float tan_fov_x, int width, int height, Rng &rng, int x, int y, F3 &o, F3 &d) {
+    wf_camera_ray_from(f3(S.cam_pos), f3(S.cam_right), f3(S.cam_up), f3(S.cam_fwd), tan_fov_x, S.tan_fov_y, width, height, rng, x, y, o, d);
 }
 RT_DEV void wf_camera_ray(const SceneView &S, const RenderView &R, Rng &rng, int x, int y, F3 &o, F3 &d) {
     wf_camera_ray_of(S, R.tan_fov_x, R.width, R.height, rng, x, y, o, d);
@@ -691,6 +696,7 @@ __global__ __launch_bounds__(64) void wf_light_exact_kernel(SceneView S, WfView 
 #define WF_FEAT_SOURCE 4 // rt_persistent.h only: a sample's first ray comes from a path source (rt_path_source.h); no hw7 and no counting variant
 #define WF_FEAT_PROBES 8 // with WF_FEAT_SOURCE only: the source is SH9 probes (src_mode 3), a finished sample is projected into RenderView::src_sh
 #define WF_FEAT_PIXELS 16 // with WF_FEAT_SOURCE only: the source is the camera of another frame (src_mode 4), the pixel behind a slot comes from RenderView::src_pixels
+#define WF_FEAT_VIEWS 32 // with WF_FEAT_SOURCE only: the source is a batch of cameras (src_mode 5), pixel and view behind a slot come from RenderView::src_pixels, the camera from src_cameras
 template <int FEAT = WF_FEAT_ENV | WF_FEAT_HW7>
 RT_DEV int wf_shade_item(const SceneView &S, const RenderView &R, const WfView &W, uint32_t slot, unsigned long long *counters, bool *discarded = nullptr) {
     float4 *r = wf_rec(W, slot);

@@ -23,6 +23,7 @@
 #include "device/rt_bake.h"
 #include "device/rt_persistent.h"
 #include "device/rt_adaptive.h"
+#include "device/rt_views.h"
 #include "device/rt_kernels_hw6.h"
 #include "device/rt_persistent_hw6.h"
 #include "device/rt_kernels_txt.h"
@@ -348,7 +349,10 @@ static PersistentKernel hw8_persistent(const SceneView &V, int ray_depth, hipStr
                 dev::WfView W{};
                 W.r0 = records; W.stride = stride; W.n_slots = n_slots; W.slot_base = slot_base;
                 const dim3 grid(blocks), block(P8_THREADS);
-                if (R.src_mode == PT_SRC_PIXELS) { // the pixels of another frame (rt_adaptive_*): the source kernel compiled for them (WF_FEAT_PIXELS)
+                if (R.src_mode == PT_SRC_VIEWS) { // a batch of cameras (rt_views_*): the source kernel compiled for them (WF_FEAT_VIEWS)
+                    if (feat == WF_FEAT_ENV) hipLaunchKernelGGL((dev::pt_persistent_kernel<false, WF_FEAT_SOURCE | WF_FEAT_VIEWS | WF_FEAT_ENV>), grid, block, 0, stream, V, R, W, P);
+                    else hipLaunchKernelGGL((dev::pt_persistent_kernel<false, WF_FEAT_SOURCE | WF_FEAT_VIEWS>), grid, block, 0, stream, V, R, W, P);
+                } else if (R.src_mode == PT_SRC_PIXELS) { // the pixels of another frame (rt_adaptive_*): the source kernel compiled for them (WF_FEAT_PIXELS)
                     if (feat == WF_FEAT_ENV) hipLaunchKernelGGL((dev::pt_persistent_kernel<false, WF_FEAT_SOURCE | WF_FEAT_PIXELS | WF_FEAT_ENV>), grid, block, 0, stream, V, R, W, P);
                     else hipLaunchKernelGGL((dev::pt_persistent_kernel<false, WF_FEAT_SOURCE | WF_FEAT_PIXELS>), grid, block, 0, stream, V, R, W, P);
                 } else if (R.src_mode == PT_SRC_PROBES) { // SH9 probes: the source kernel compiled with the side arrays (WF_FEAT_PROBES)
@@ -1259,6 +1263,11 @@ int rtamd::source_render(rt_scene *scene, const SourceChunk &C, hipStream_t stre
         F.R.src_frame[0] = C.frame_w; F.R.src_frame[1] = C.frame_h;
         F.R.src_tan_fov_x = frame_tan_fov_x(scene->view, C.frame_w, C.frame_h);
     }
+    if (C.mode == PT_SRC_VIEWS) { // the pixel and view words, the cameras where the points are, the views' frame where the streams are
+        F.R.src_pixels = C.pixels;
+        F.R.src_cameras = C.cameras;
+        F.R.src_wh = (uint32_t)C.frame_w | ((uint32_t)C.frame_h << 16);
+    }
     launch_frame(scene, &p, F, stream, true);
     rt_stats st{};
     if (const int rc = collect_frame(scene, F, stream, &st, t0, who)) return rc;
@@ -1300,3 +1309,23 @@ void rtamd::adaptive_launch_seed(const rt_scene *, const RenderView &R, hipStrea
     HIP_CHECK(hipGetLastError());
 }
 float rtamd::adaptive_tan_fov_x(const rt_scene *scene, int32_t width, int32_t height) { return frame_tan_fov_x(scene->view, width, height); }
+
+// ---- rt_views_*: the flat kernels around the view source (device/rt_views.h; the host side is rtamd_views.hip) -------------------------------
+uint32_t rtamd::views_launch_gather(const rt_scene *scene, const RenderView &R, const ViewsView &V, hipStream_t stream) {
+    hipLaunchKernelGGL(dev::vw_gather_kernel, dim3(query_geometry(scene, V.strip_slots).flat_blocks), dim3(256), 0, stream, R, V);
+    HIP_CHECK(hipGetLastError());
+    return 1u;
+}
+uint32_t rtamd::views_launch_scatter(const rt_scene *scene, const RenderView &R, const ViewsView &V, hipStream_t stream) {
+    hipLaunchKernelGGL(dev::vw_scatter_kernel, dim3(query_geometry(scene, V.strip_slots).flat_blocks), dim3(256), 0, stream, R, V);
+    HIP_CHECK(hipGetLastError());
+    return 1u;
+}
+void rtamd::views_launch_seed(const rt_scene *, const RenderView &R, hipStream_t stream) {
+    hipLaunchKernelGGL(dev::accum_seed_kernel, dim3((R.n_pixslots + 255u) / 256u), dim3(256), 0, stream, R);
+    HIP_CHECK(hipGetLastError());
+}
+void rtamd::views_launch_resolve(const rt_scene *, const RenderView &R, hipStream_t stream) {
+    hipLaunchKernelGGL(dev::accum_resolve_kernel, dim3((R.n_pixslots + 255u) / 256u), dim3(256), 0, stream, R);
+    HIP_CHECK(hipGetLastError());
+}

@@ -15,6 +15,7 @@
 #include "host/fold_nodes.h"
 #include "host/hip_check.h"
 #include "host/rt_adaptive_decide.h"
+#include "host/rt_views_camera.h"
 #include "host/rt_guard.h"
 #include "host/rt_scene.h"
 #include "host/scene_prep.h"
@@ -975,6 +976,14 @@ int rtt_adaptive_decide(const rt_adaptive_tile *tiles, const rt_adaptive_params 
     if (!tiles || !params || !flags || sub_w < 1 || sub_h < 1) return RT_ERR_INVALID_ARG;
     rtamd::adaptive_decide(tiles, *params, sub_w, sub_h, n_samples, flags);
     return RT_OK;
+}
+
+// The camera check of a view set (host/rt_views_camera.h): RT_OK, or RT_ERR_INVALID_ARG with the reason in `why` (cut to `capacity`).  Host only.
+int rtt_views_camera_check(const rt_camera *camera, char *why, size_t capacity) {
+    if (!camera) return RT_ERR_INVALID_ARG;
+    const std::string reason = rtamd::views_camera_check(*camera);
+    if (why && capacity) snprintf(why, capacity, "%s", reason.c_str());
+    return reason.empty() ? RT_OK : RT_ERR_INVALID_ARG;
 }
 
 int rtt_guard_probe(int kind) {

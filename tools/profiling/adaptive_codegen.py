@@ -91,6 +91,6 @@ for n in new:
     print("  new", n)
 print("resource usage (this tree), the persistent hw8 kernels and the new flat kernels:")
 for k in sorted(lines):
-    if "pt_persistent_kernel" in k or "ad_" in k:
+    if "pt_persistent_kernel" in k or "ad_" in k or "vw_" in k:
         print(f"  {k} {lines[k]}")
 sys.exit(1 if differ else 0)
