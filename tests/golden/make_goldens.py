@@ -4,7 +4,8 @@ Run:  python tests/golden/make_goldens.py      (after `make -C oracle`)
       python tests/golden/make_goldens.py shading     only pins_shading_edges.npz
       python tests/golden/make_goldens.py intersection     only pins_intersection_edges.npz
       python tests/golden/make_goldens.py analytic     only pins_analytic_edges.npz
-      python tests/golden/make_goldens.py texture     only pins_texture_edges.npz and pins_hw8_paths.npz"""
+      python tests/golden/make_goldens.py texture     only pins_texture_edges.npz and pins_hw8_paths.npz
+      python tests/golden/make_goldens.py light_sums     only pins_light_sums.npz"""
 import ctypes as C
 import os
 import sys
@@ -120,6 +121,27 @@ def main():
     save_analytic_edges()
     save_texture_edges()
     save_hw8_paths()
+    save_light_sums()
+
+
+def save_light_sums():
+    """Light-pdf sums by hit count (tests/light_sum_cases.py): the compiled reference's FiguresMix::pdf (Ref8.light_pdf) on every hw8 stack
+    scene and ray set, with the rays, and the reference's own pixels (hw8 scene.cpp, Ref8Scene) of the frames the GPU tests render."""
+    import light_sum_cases as lc
+    out = {}
+    for L in lc.HW8_LAYERS:
+        sd = lc.stack_scene(L)
+        ref = oracle_lib.Ref8(sd)
+        for which in lc.RAY_SETS:
+            o, d = lc.rays(L, which)
+            key = lc.fixture_key(L, which)
+            out[key + "_o"], out[key + "_d"], out[key + "_pdf"] = o, d, lc.light_pdfs(ref, o, d)
+        if L in lc.FRAME_LAYERS:
+            w, h, spp = lc.FRAME
+            out[f"L{L}_frame_rgb"], out[f"L{L}_frame_rgb8"], _ = oracle_lib.Ref8Scene(sd).render(w, h, spp)
+            print("light sums frame", L, float(out[f"L{L}_frame_rgb"].mean()))
+    np.savez_compressed(os.path.join(HERE, "pins_light_sums.npz"), **out)
+    print("light sums", {k: v.shape for k, v in out.items()})
 
 
 def save_texture_edges():
@@ -225,5 +247,7 @@ if __name__ == "__main__":
     elif sys.argv[1:] == ["texture"]:
         save_texture_edges()
         save_hw8_paths()
+    elif sys.argv[1:] == ["light_sums"]:
+        save_light_sums()
     else:
         main()
