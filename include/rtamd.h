@@ -995,8 +995,9 @@ void rt_adaptive_destroy(rt_adaptive *a);
  *          rt_adaptive_create answers: scenes that are not hw8 scenes, and whatever keeps the persistent hw8 kernel from the scene
  *          (RTAMD_KERNEL=wavefront|mega, a tree beyond its stack columns).  A slice that fails under way leaves the object broken,
  *          as with rt_accum.
- * Out of scope   checkpoints of a view set; rt_noise, rt_denoise, guide images and rt_camera_rays for a view's camera; rt_multi_*;
- *          hw7 and hw6; adaptive sampling per view; views of different sizes.
+ * Out of scope   an rt_views has no adaptive sampling per view: every pixel of a view draws what the view draws.  That lives in
+ *          rt_view_adaptive_* below, an object of its own over the same kind of state.  Out of scope for both: checkpoints of a view set;
+ *          rt_noise, rt_denoise, guide images and rt_camera_rays for a view's camera; rt_multi_*; hw7 and hw6; views of different sizes.
  * Measured on one MI355X: profiles/r36_views.txt. */
 typedef struct rt_views_params {
     uint32_t struct_size;
@@ -1023,6 +1024,76 @@ int  rt_views_render(rt_views *v, int32_t n_samples, const uint8_t *mask /* null
 int  rt_views_samples(const rt_views *v, int32_t *out /* n_views */);
 int  rt_views_resolve(rt_views *v, int32_t view, uint32_t flags /* RT_FLAG_OUT_DEVICE */, float *out_rgb /* nullable */, uint8_t *out_rgb8 /* nullable */);
 void rt_views_destroy(rt_views *v);
+
+/* ---- adaptive view sets: freeze converged 8x8 sub-tiles per camera -------------------------------------------------------------
+ * rt_adaptive stops drawing samples where ONE camera's picture is done; rt_views renders many cameras in one launch, every pixel the
+ * same count.  An rt_view_adaptive does both: the strip of a slice holds the ACTIVE sub-tiles of ALL views, in any mix, so a wall and
+ * a glossy object under an emitter each draw what they need and many small views still fill one launch.  The persistent kernel is
+ * the one rt_views runs (src_mode 5 reads the view per 64-slot group and the pixel per slot); no variant was added.  ABI version 6
+ * still: additions only.  rt_views_params, rt_adaptive_params, rt_adaptive_tile and rt_noise_summary are those above;
+ * rt_views_params.flags stays 0.
+ *
+ * State      per view one rt_accum block (24 bytes per pixel slot) plus the noise monitor's three planes y0 / yp / m2 (12 bytes per
+ *          slot); per (view, sub-tile) what rt_adaptive keeps per sub-tile: samples, batches, observed samples, flags and the last
+ *          estimate's entry.
+ * Contract   on a scene whose renders report reference_exact = 1: take view v of a set driven by rt_view_adaptive_render with v in the
+ *          mask for slices n_1, n_2, ..., and an rt_adaptive with the same rt_adaptive_params on a scene created from the same
+ *          rt_scene_desc with camera = cameras[v], driven by rt_adaptive_render with the same slice lengths.  The 32-byte tile
+ *          entries, the resolved floats and bytes, the noise map and every summary field, and the sample map are the same, bit for
+ *          bit -- whatever the other views are and whatever they drew (tests/test_gpu_view_adaptive.py).  Consequently a sub-tile
+ *          that has drawn d samples holds rt_render(samples = d)'s pixels on that scene.
+ * Decision   per view, the decision of rt_adaptive_render over that view's table with that view's own mean luminance L; dilation looks
+ *          at the 8 neighbours inside the view only.  A view whose view_mask byte is 0 (a NULL mask: every view takes part) draws
+ *          nothing in that call and keeps its entries and flags.  The call decides once more before it launches (the cap depends on
+ *          this call's n_samples), draws, updates, estimates and decides, as rt_adaptive_render does.  With no active sub-tile in any
+ *          masked view it is RT_OK, launches nothing and reports samples = 0: the caller's stop condition.
+ * A slice    per chunk one gather, the persistent kernel, one scatter; then ONE update launch over the list and ONE estimate launch
+ *          over all sub-tiles of all views: the launch count does not grow with n_views.  A strip entry is one word
+ *          view * tiles + sub-tile, the list ascending.  Chunks are RTAMD_QUERY_CHUNK-sized, made of whole sub-tiles, and may split
+ *          a view.  Cameras and first rays outside the node grid follow rt_views' rules above.
+ * rt_view_adaptive_render_tiles   the mechanism without the policy: one byte per (view, sub-tile), view-major; update and estimate as
+ *          above, ACTIVE / CONVERGED / CAPPED are left as they were.
+ * rt_view_adaptive_set_cameras   replaces the cameras of views first .. first + n - 1 and resets those views: sums 0, engines reseeded,
+ *          counts and batches 0, every sub-tile ACTIVE | NO_ESTIMATE.  The other views are untouched.
+ * rt_view_adaptive_tiles / _resolve / _noise / _sample_map   one view's, as the rt_adaptive_* calls of the same name.
+ *          rt_view_adaptive_noise is RT_ERR_INVALID_ARG while no sub-tile of that view has 2 batches; samples_total, batches and
+ *          samples_observed are the largest over the view's sub-tiles.
+ * stats    active_views: views for which at least one sub-tile drew in this call; active_tiles: (view, sub-tile) pairs it drew for;
+ *          converged_tiles / capped_tiles: over all views, as flagged when the call returns; samples: camera samples drawn (pixels
+ *          inside the image x n_samples); min_samples / max_samples per pixel over all views; noise_ms: the update and estimate
+ *          launches; the rest as rt_views_stats.
+ * Refusals   before any device work, the state untouched; the message names the field and, where it applies, the view or sub-tile.
+ *          What rt_views_create refuses (struct sizes, reserved words, flags, n_views, sizes, bad cameras, the limits, scenes that are
+ *          not hw8 scenes or that the persistent hw8 kernel cannot take), what rt_adaptive_create refuses (target_noise, min_batches,
+ *          max_samples, unknown adaptive flags), and what a slice refuses (n_samples <= 0, the 2^25 sample-index limit per active
+ *          sub-tile), each with that call's status.  A slice that fails under way leaves the object broken, as with rt_views.
+ * Out of scope   checkpoints of an adaptive view set; rt_multi_*; hw7 and hw6; rt_denoise and guide images for a view's camera; views
+ *          of different sizes.
+ * Measured on one MI355X, 64 views of 128x128 in slices of 16 (profiles/r38_view_adaptive.txt): an all-active
+ *          slice costs what rt_views_render's does (51.6 against 51.8 ms; update and estimate 0.021 ms); to the median of the views'
+ *          worst-sub-tile noise the set draws 0.512 of the uniform 64-sample set's camera samples in 0.587 x its wall time.  The target
+ *          is relative to each view's own mean luminance: a view with almost no light in it runs to max_samples, so set one.  Not
+ *          measured: RT_ADAPTIVE_DILATE on a set, sets beyond one chunk. */
+typedef struct rt_view_adaptive_stats {
+    uint32_t struct_size, active_views;                              /* in: sizeof(rt_view_adaptive_stats) */
+    uint32_t active_tiles, converged_tiles, capped_tiles, launches;
+    uint64_t samples;
+    int32_t  min_samples, max_samples;
+    double   kernel_ms, gather_ms, scatter_ms, noise_ms, total_ms;
+    uint32_t reference_exact, reserved;
+    uint64_t exact_walks;
+} rt_view_adaptive_stats;
+typedef struct rt_view_adaptive rt_view_adaptive;
+int  rt_view_adaptive_create(rt_scene *scene, const rt_views_params *params, const rt_adaptive_params *adaptive,
+                             const rt_camera *cameras /* n_views */, rt_view_adaptive **out);
+int  rt_view_adaptive_set_cameras(rt_view_adaptive *a, int32_t first, int32_t n, const rt_camera *cameras /* n */);
+int  rt_view_adaptive_render(rt_view_adaptive *a, int32_t n_samples, const uint8_t *view_mask /* nullable: n_views bytes */, rt_view_adaptive_stats *stats);
+int  rt_view_adaptive_render_tiles(rt_view_adaptive *a, int32_t n_samples, const uint8_t *tile_mask /* n_views * tiles bytes */, rt_view_adaptive_stats *stats);
+int  rt_view_adaptive_tiles(rt_view_adaptive *a, int32_t view, rt_adaptive_tile *out /* tiles */);
+int  rt_view_adaptive_resolve(rt_view_adaptive *a, int32_t view, uint32_t flags /* RT_FLAG_OUT_DEVICE */, float *out_rgb /* nullable */, uint8_t *out_rgb8 /* nullable */);
+int  rt_view_adaptive_noise(rt_view_adaptive *a, int32_t view, uint32_t flags, float *out_se /* nullable */, rt_noise_summary *summary /* nullable */);
+int  rt_view_adaptive_sample_map(rt_view_adaptive *a, int32_t view, int32_t *out /* W*H */);
+void rt_view_adaptive_destroy(rt_view_adaptive *a);
 
 /* Scene info the host side needs after preparation. */
 typedef struct rt_scene_info {

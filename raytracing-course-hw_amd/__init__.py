@@ -182,6 +182,14 @@ class rt_views_stats(C.Structure):
                 ("total_ms", C.c_double), ("launches", C.c_uint32), ("reference_exact", C.c_uint32), ("exact_walks", C.c_uint64)]
 
 
+class rt_view_adaptive_stats(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("active_views", C.c_uint32), ("active_tiles", C.c_uint32), ("converged_tiles", C.c_uint32),
+                ("capped_tiles", C.c_uint32), ("launches", C.c_uint32), ("samples", C.c_uint64), ("min_samples", C.c_int32),
+                ("max_samples", C.c_int32), ("kernel_ms", C.c_double), ("gather_ms", C.c_double), ("scatter_ms", C.c_double),
+                ("noise_ms", C.c_double), ("total_ms", C.c_double), ("reference_exact", C.c_uint32), ("reserved", C.c_uint32),
+                ("exact_walks", C.c_uint64)]
+
+
 # rt_adaptive_tile as a numpy record: what AdaptiveRender.tiles() returns, one per 8x8 sub-tile
 ADAPTIVE_TILE_DTYPE = np.dtype([("samples", np.int32), ("batches", np.int32), ("pixels", np.uint32), ("nonfinite", np.uint32),
                                 ("sum_se2", np.float32), ("sum_luminance", np.float32), ("flags", np.uint32), ("reserved", np.uint32)])
@@ -216,7 +224,9 @@ ABI_SYMBOLS = ["rt_abi_version", "rt_last_error", "rt_scene_create", "rt_scene_d
                "rt_render_paths", "rt_render_bake", "rt_render_probes", "rt_adaptive_create", "rt_adaptive_render",
                "rt_adaptive_render_tiles", "rt_adaptive_tiles", "rt_adaptive_resolve", "rt_adaptive_noise", "rt_adaptive_sample_map",
                "rt_adaptive_destroy", "rt_views_create", "rt_views_set_cameras", "rt_views_render", "rt_views_samples", "rt_views_resolve",
-               "rt_views_destroy"]
+               "rt_views_destroy", "rt_view_adaptive_create", "rt_view_adaptive_set_cameras", "rt_view_adaptive_render",
+               "rt_view_adaptive_render_tiles", "rt_view_adaptive_tiles", "rt_view_adaptive_resolve", "rt_view_adaptive_noise",
+               "rt_view_adaptive_sample_map", "rt_view_adaptive_destroy"]
 # The preview filter's two, which the header declares `extern int`: the list above and the family lists of the tests are closed sets
 # of the header's plain prototypes (tests/test_abi_and_host.py, tests/test_accum_host.py), and rt_accum_denoise is no rt_accum_* of theirs.
 DENOISE_SYMBOLS = ["rt_denoise", "rt_accum_denoise"]
@@ -310,6 +320,16 @@ lib.rt_views_samples.argtypes = [C.c_void_p, C.c_void_p]
 lib.rt_views_resolve.argtypes = [C.c_void_p, C.c_int32, C.c_uint32, C.c_void_p, C.c_void_p]
 lib.rt_views_destroy.argtypes = [C.c_void_p]
 lib.rt_views_destroy.restype = None
+lib.rt_view_adaptive_create.argtypes = [C.c_void_p, C.POINTER(rt_views_params), C.POINTER(rt_adaptive_params), C.c_void_p, C.POINTER(C.c_void_p)]
+lib.rt_view_adaptive_set_cameras.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
+lib.rt_view_adaptive_render.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(rt_view_adaptive_stats)]
+lib.rt_view_adaptive_render_tiles.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(rt_view_adaptive_stats)]
+lib.rt_view_adaptive_tiles.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
+lib.rt_view_adaptive_resolve.argtypes = [C.c_void_p, C.c_int32, C.c_uint32, C.c_void_p, C.c_void_p]
+lib.rt_view_adaptive_noise.argtypes = [C.c_void_p, C.c_int32, C.c_uint32, C.c_void_p, C.POINTER(rt_noise_summary)]
+lib.rt_view_adaptive_sample_map.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
+lib.rt_view_adaptive_destroy.argtypes = [C.c_void_p]
+lib.rt_view_adaptive_destroy.restype = None
 lib.rt_denoise.argtypes = [C.c_void_p, C.POINTER(rt_denoise_params)] + [C.c_void_p] * 8 + [C.POINTER(rt_denoise_stats)]
 lib.rt_accum_denoise.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(rt_denoise_params), C.c_void_p, C.c_void_p, C.POINTER(rt_denoise_stats)]
 
@@ -923,6 +943,84 @@ class ViewSet(_Handle):
         _check(lib.rt_views_set_cameras(self._h, first, n, C.cast(arr, C.c_void_p)))
 
 
+class AdaptiveViews(_Handle):
+    """A batch of cameras over one Scene whose converged 8x8 sub-tiles stop drawing samples, per view (rt_view_adaptive): render(n, mask)
+    is one slice of the policy for the views whose byte of `mask` is not 0 (None: all), render_tiles(n, mask) one of the caller's own
+    mask per (view, sub-tile).  View v is what an AdaptiveRender with the same parameters does on a Scene created with cameras[v].
+    Keywords: min_batches, max_samples, dilate, then make_views_params'."""
+    _destroy = "rt_view_adaptive_destroy"
+
+    def __init__(self, scene, width, height, cameras, target_noise, min_batches=0, max_samples=0, dilate=False, **kw):
+        self.scene = scene  # keeps the scene alive: an rt_view_adaptive is destroyed before its scene
+        arr, n = _camera_array(cameras)
+        self.params = make_views_params(width, height, n, **kw)
+        self.adaptive = make_adaptive_params(target_noise, min_batches, max_samples, RT_ADAPTIVE_DILATE if dilate else 0)
+        self._open(scene)
+        _check(lib.rt_view_adaptive_create(scene._h, C.byref(self.params), C.byref(self.adaptive), C.cast(arr, C.c_void_p), C.byref(self._h)))
+
+    @property
+    def grid(self):
+        """(rows, columns) of one view's 8x8 sub-tiles."""
+        return (self.params.height + 7) // 8, (self.params.width + 7) // 8
+
+    @staticmethod
+    def _stats():
+        st = rt_view_adaptive_stats()
+        st.struct_size = C.sizeof(rt_view_adaptive_stats)
+        return st
+
+    def render(self, n_samples, mask=None):
+        if mask is not None:
+            mask = np.ascontiguousarray(np.asarray(mask).astype(np.uint8).reshape(-1))
+            if mask.size != self.params.n_views:
+                raise ValueError(f"mask must hold one byte per view ({self.params.n_views}), got {mask.size}")
+        st = self._stats()
+        _check(lib.rt_view_adaptive_render(self._h, n_samples, mask.ctypes.data if mask is not None else None, C.byref(st)))
+        return st
+
+    def render_tiles(self, n_samples, mask):
+        """One slice for the (view, sub-tile) pairs whose byte of `mask` (views x rows x columns, or flat) is not 0."""
+        mask = np.ascontiguousarray(np.asarray(mask).astype(np.uint8).reshape(-1))
+        if mask.size != self.params.n_views * self.grid[0] * self.grid[1]:
+            raise ValueError(f"mask must hold one byte per view and sub-tile ({self.params.n_views} x {self.grid[0]} x {self.grid[1]}), got {mask.size}")
+        st = self._stats()
+        _check(lib.rt_view_adaptive_render_tiles(self._h, n_samples, mask.ctypes.data, C.byref(st)))
+        return st
+
+    def tiles(self, view):
+        """One view's entries, ADAPTIVE_TILE_DTYPE records of shape (rows, columns)."""
+        out = np.zeros(self.grid, dtype=ADAPTIVE_TILE_DTYPE)
+        _check(lib.rt_view_adaptive_tiles(self._h, view, out.ctypes.data))
+        return out
+
+    def resolve(self, view, want_float=True, want_rgb8=True):
+        """(rgb float32, rgb8) of one view, (H, W, 3) each."""
+        h, w = self.params.height, self.params.width
+        rgb = np.zeros((h, w, 3), dtype=np.float32) if want_float else None
+        rgb8 = np.zeros((h, w, 3), dtype=np.uint8) if want_rgb8 else None
+        _check(lib.rt_view_adaptive_resolve(self._h, view, 0, rgb.ctypes.data if want_float else None, rgb8.ctypes.data if want_rgb8 else None))
+        return rgb, rgb8
+
+    def noise(self, view, want_map=True):
+        """(standard error per pixel (H, W) or None, rt_noise_summary) of one view."""
+        se = np.zeros((self.params.height, self.params.width), dtype=np.float32) if want_map else None
+        summary = rt_noise_summary()
+        summary.struct_size = C.sizeof(rt_noise_summary)
+        _check(lib.rt_view_adaptive_noise(self._h, view, 0, se.ctypes.data if want_map else None, C.byref(summary)))
+        return se, summary
+
+    def sample_map(self, view):
+        """Samples drawn per pixel of one view, int32 (H, W)."""
+        out = np.zeros((self.params.height, self.params.width), dtype=np.int32)
+        _check(lib.rt_view_adaptive_sample_map(self._h, view, out.ctypes.data))
+        return out
+
+    def set_cameras(self, first, cameras):
+        """New cameras for views first .. first + len(cameras) - 1, which start over: no samples, every sub-tile active."""
+        arr, n = _camera_array(cameras)
+        _check(lib.rt_view_adaptive_set_cameras(self._h, first, n, C.cast(arr, C.c_void_p)))
+
+
 class Scene(_Handle):
     """A prepared scene resident in HBM on the current HIP device (rt_scene)."""
     _destroy = "rt_scene_destroy"
@@ -972,6 +1070,10 @@ class Scene(_Handle):
     def views(self, width, height, cameras, **kw):
         """A batch of cameras over this scene (ViewSet)."""
         return ViewSet(self, width, height, cameras, **kw)
+
+    def adaptive_views(self, width, height, cameras, target_noise, **kw):
+        """A batch of cameras over this scene with adaptive sampling per view (AdaptiveViews)."""
+        return AdaptiveViews(self, width, height, cameras, target_noise, **kw)
 
     def render_device(self, params, out_rgb_ptr, out_rgb8_ptr):
         """Render into device buffers (raw pointers, e.g. torch tensor data_ptr())."""

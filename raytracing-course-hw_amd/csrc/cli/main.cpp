@@ -33,6 +33,11 @@
 // right, up, forward, fov_y; empty lines and lines that begin with # are skipped.  The run renders all of them as one view set from the
 // one scene, in one slice or with RTAMD_SLICE in slices of that many samples, and writes out_000.ppm, out_001.ppm, ... beside the named
 // output (its name before the extension, then the camera's number).  A malformed line ends the run with RT_ERR_PARSE and names the line.
+// Both together (rt_view_adaptive_*): RTAMD_CAMERAS=file with RTAMD_ADAPTIVE=1 and RTAMD_TARGET_NOISE=x renders the file's cameras as one
+// adaptive set in slices of RTAMD_SLICE (else a sixteenth of the samples asked for, which are the most any sub-tile draws) until no
+// sub-tile of any view is active, each view judged by its own mean luminance.  After every slice one line on stderr: the views and
+// sub-tiles that drew, the converged and the capped sub-tiles.  It writes out_000.ppm, ... and, with RTAMD_SAMPLE_MAP=spp.pfm,
+// spp_000.pfm, ...; RTAMD_ADAPTIVE_DILATE is honoured.
 #include "../../../include/rtamd.h"
 #include "../host/knobs.h"
 #include <cmath>
@@ -309,6 +314,16 @@ static bool read_cameras(const char *path, std::vector<rt_camera> &cameras) {
     return true;
 }
 
+// The file of view v beside `path`: out.ppm -> out_007.ppm (the extension, if any, is replaced by `ext`).
+static std::string numbered(const char *path, size_t v, const char *ext) {
+    std::string stem = path;
+    const size_t dot = stem.rfind('.'), slash = stem.find_last_of('/');
+    if (dot != std::string::npos && (slash == std::string::npos || dot > slash)) stem.resize(dot);
+    char tail[32];
+    snprintf(tail, sizeof tail, "_%03zu", v);
+    return stem + tail + ext;
+}
+
 // RTAMD_CAMERAS=file: all cameras as one view set, p.samples samples each in slices of `slice` (0: one slice), one PPM per camera.
 static int render_views(rt_scene *scene, const rt_render_params &p, int slice, const std::vector<rt_camera> &cameras, const char *out_path, std::vector<uint8_t> &rgb8) {
     rt_views_params vp;
@@ -331,16 +346,56 @@ static int render_views(rt_scene *scene, const rt_render_params &p, int slice, c
                                st.kernel_ms, (unsigned long long)st.exact_walks);
     }
     fprintf(stderr, "render: %zu views, %.3f ms on the GPU, %.2f Msamples/s\n", cameras.size(), kernel_ms, samples / (kernel_ms * 1e3));
-    std::string stem = out_path;
-    const size_t dot = stem.rfind('.'), slash = stem.find_last_of('/');
-    if (dot != std::string::npos && (slash == std::string::npos || dot > slash)) stem.resize(dot);
     for (size_t v = 0; v < cameras.size(); v++) {
-        char tail[32];
-        snprintf(tail, sizeof tail, "_%03zu.ppm", v);
         if (rt_views_resolve(views, (int32_t)v, 0, nullptr, rgb8.data()) != RT_OK) return fail();
-        if (rt_write_ppm((stem + tail).c_str(), p.width, p.height, rgb8.data()) != RT_OK) return fail();
+        if (rt_write_ppm(numbered(out_path, v, ".ppm").c_str(), p.width, p.height, rgb8.data()) != RT_OK) return fail();
     }
     rt_views_destroy(views);
+    return 0;
+}
+
+// RTAMD_CAMERAS=file with RTAMD_ADAPTIVE=1: all cameras as one adaptive view set, slices of the policy until no sub-tile of any view is
+// active; one PPM per camera and, with RTAMD_SAMPLE_MAP=spp.pfm, spp_000.pfm, ... beside it.
+static int render_view_adaptive(rt_scene *scene, const rt_render_params &p, int slice, const NoiseTarget &noise, const std::vector<rt_camera> &cameras, const char *out_path,
+                                std::vector<uint8_t> &rgb8) {
+    rt_views_params vp;
+    memset(&vp, 0, sizeof vp);
+    vp.struct_size = sizeof vp;
+    vp.width = p.width; vp.height = p.height; vp.ray_depth = p.ray_depth; vp.n_views = (int32_t)cameras.size();
+    rt_adaptive_params ap;
+    memset(&ap, 0, sizeof ap);
+    ap.struct_size = sizeof ap;
+    ap.target_noise = (float)noise.target; ap.min_batches = noise.min_batches; ap.max_samples = p.samples;
+    if (const char *e = getenv("RTAMD_ADAPTIVE_DILATE")) if (atoi(e) != 0) ap.flags |= RT_ADAPTIVE_DILATE;
+    rt_view_adaptive *set = nullptr;
+    if (rt_view_adaptive_create(scene, &vp, &ap, cameras.data(), &set) != RT_OK) return die();
+    auto fail = [&]() { const int rc = die(); rt_view_adaptive_destroy(set); return rc; };
+    double kernel_ms = 0;
+    uint64_t samples = 0;
+    for (int k = 1;; k++) {
+        rt_view_adaptive_stats st;
+        memset(&st, 0, sizeof st);
+        st.struct_size = sizeof st;
+        if (rt_view_adaptive_render(set, slice, nullptr, &st) != RT_OK) return fail();
+        if (st.samples == 0) break;
+        kernel_ms += st.kernel_ms; samples += st.samples;
+        fprintf(stderr, "slice %d: %u views, %u sub-tiles drew %d samples, %u converged, %u capped, %d .. %d samples per pixel, %.3f ms on the GPU\n", k, st.active_views, st.active_tiles,
+                slice, st.converged_tiles, st.capped_tiles, st.min_samples, st.max_samples, st.kernel_ms);
+    }
+    if (samples) fprintf(stderr, "render: %zu views, %.3f ms on the GPU, %.2f Msamples/s, %llu camera samples of the %llu a uniform run draws\n", cameras.size(), kernel_ms,
+                         samples / (kernel_ms * 1e3), (unsigned long long)samples, (unsigned long long)cameras.size() * p.width * p.height * p.samples);
+    const char *map_path = getenv("RTAMD_SAMPLE_MAP");
+    std::vector<int32_t> spp((size_t)p.width * p.height);
+    for (size_t v = 0; v < cameras.size(); v++) {
+        if (rt_view_adaptive_resolve(set, (int32_t)v, 0, nullptr, rgb8.data()) != RT_OK) return fail();
+        if (rt_write_ppm(numbered(out_path, v, ".ppm").c_str(), p.width, p.height, rgb8.data()) != RT_OK) return fail();
+        if (!map_path) continue;
+        if (rt_view_adaptive_sample_map(set, (int32_t)v, spp.data()) != RT_OK) return fail();
+        const std::vector<float> image(spp.begin(), spp.end());
+        const std::string path = numbered(map_path, v, ".pfm");
+        if (!write_pfm(path.c_str(), p.width, p.height, 1, image)) { fprintf(stderr, "error: cannot write sample map %s\n", path.c_str()); rt_view_adaptive_destroy(set); return 1; }
+    }
+    rt_view_adaptive_destroy(set);
     return 0;
 }
 
@@ -432,8 +487,8 @@ int main(int argc, const char *argv[]) {
     if (const char *path = argc >= 6 ? rtamd::env_str("RTAMD_CAMERAS") : nullptr) {
         const char *why = p.integrator != RT_INTEGRATOR_HW8 ? "it runs the hw8 integrator only (RTAMD_SNAPSHOT=hw8, the default)"
                           : (!list.empty() || n_dev > 1) ? "it runs on one GPU (RTAMD_DEVICES=1; no RTAMD_DEVICE_LIST)"
-                          : adaptive ? "a view set has no adaptive sampling (RTAMD_ADAPTIVE)"
-                          : (checkpoint || noise.active() || preview.path) ? "a view set has no checkpoint, noise monitor or denoised preview (RTAMD_CHECKPOINT, RTAMD_TARGET_NOISE, RTAMD_NOISE_MAP, RTAMD_DENOISE)"
+                          : (checkpoint || preview.path || (adaptive ? noise.map != nullptr : noise.active())) ? // with RTAMD_ADAPTIVE the target is the sub-tiles'
+"a view set has no checkpoint, noise monitor or denoised preview (RTAMD_CHECKPOINT, RTAMD_TARGET_NOISE, RTAMD_NOISE_MAP, RTAMD_DENOISE)"
                           : p.sample_streams > 1 ? "a view set renders in replay mode (no RTAMD_STREAMS)" : nullptr;
         if (why) { fprintf(stderr, "error: RTAMD_CAMERAS: %s\n", why); return 1; }
         if (!read_cameras(path, cameras)) return 1;
@@ -451,7 +506,7 @@ int main(int argc, const char *argv[]) {
         if (rc) return rc;
     }
     if (!cameras.empty()) {
-        const int rc = render_views(scene, p, slice, cameras, out_path, rgb8);
+        const int rc = adaptive ? render_view_adaptive(scene, p, slice, noise, cameras, out_path, rgb8) : render_views(scene, p, slice, cameras, out_path, rgb8);
         rt_scene_destroy(scene);
         rt_host_scene_free(hs);
         if (rc == 0) fprintf(stderr, "FINISH\n");

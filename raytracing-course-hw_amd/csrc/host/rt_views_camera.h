@@ -1,9 +1,11 @@
-// The camera check of a view set (include/rtamd.h: rt_views_create, rt_views_set_cameras).  One host function with no GPU call in it,
-// shared by rtamd_views.hip and the test hook rtt_views_camera_check (test_hooks.hip).
+// The cameras of a view set (include/rtamd.h: rt_views_create, rt_views_set_cameras, and the same two of rt_view_adaptive_*): the check
+// and the record the kernel reads.  Host functions with no GPU call in them, shared by rtamd_views.hip, rtamd_view_adaptive.hip and the
+// test hook rtt_views_camera_check (test_hooks.hip).
 #pragma once
 #include <cmath>
 #include <string>
 #include "../../../include/rtamd.h"
+#include "../device/rt_types.h" // ViewCamera
 
 namespace rtamd {
 
@@ -25,6 +27,25 @@ inline std::string views_camera_check(const rt_camera &c) {
                        std::sqrt(f[0] * f[0] + f[1] * f[1] + f[2] * f[2]);
     if (!(std::fabs(det) > VIEWS_MIN_DET * len)) return "right, up and forward must be linearly independent (their determinant is 0 against their lengths)";
     return std::string();
+}
+
+// The refusal of a camera array, before anything is touched; `first`: the view of cameras[0].  Empty when every camera is usable.
+inline std::string views_cameras_check(const rt_camera *cameras, int32_t first, int32_t n) {
+    for (int32_t i = 0; i < n; i++) {
+        const std::string why = views_camera_check(cameras[i]);
+        if (!why.empty()) return "cameras: view " + std::to_string(first + i) + ": " + why;
+    }
+    return std::string();
+}
+
+// The record the kernel reads: the camera's vectors as given, the two tangents by the expressions of the scene's own camera
+// (set_triangle_view: host libm in double; frame_tan_fov_x).
+inline ViewCamera views_camera_record(const rt_camera &c, int32_t width, int32_t height) {
+    ViewCamera r{};
+    for (int k = 0; k < 3; k++) { r.pos[k] = c.position[k]; r.right[k] = c.right[k]; r.up[k] = c.up[k]; r.fwd[k] = c.forward[k]; }
+    r.tan_fov_y = (float)std::tan((double)(c.fov_y / 2)); // scene.cpp:180
+    r.tan_fov_x = r.tan_fov_y * width / height;           // scene.cpp:181
+    return r;
 }
 
 } // namespace rtamd

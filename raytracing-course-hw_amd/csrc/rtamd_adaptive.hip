@@ -56,25 +56,9 @@ AdaptiveView adaptive_view(const rt_adaptive *a) {
     return V;
 }
 
-// pixels of sub-tile t that lie inside the image
-uint32_t tile_pixels(const rt_adaptive *a, uint32_t t) {
-    const int32_t gx = (int32_t)(t % (uint32_t)a->sub_w), gy = (int32_t)(t / (uint32_t)a->sub_w);
-    return (uint32_t)(std::min(8, a->view.width - 8 * gx) * std::min(8, a->view.height - 8 * gy));
-}
-
 int usable(const rt_adaptive *a, const std::string &who) {
     if (!a->broken.empty()) return fail(RT_ERR_INVALID_ARG, who + "an earlier slice failed and left the state half advanced (" + a->broken + ")");
     return RT_OK;
-}
-
-void fill_counts(const rt_adaptive *a, rt_adaptive_stats &st) {
-    int32_t lo = 0x7fffffff, hi = 0;
-    for (const rt_adaptive_tile &t : a->tiles) {
-        if (t.flags & RT_ADAPTIVE_CONVERGED) st.converged_tiles++;
-        if (t.flags & RT_ADAPTIVE_CAPPED) st.capped_tiles++;
-        lo = std::min(lo, t.samples); hi = std::max(hi, t.samples);
-    }
-    st.min_samples = a->tiles.empty() ? 0 : lo; st.max_samples = hi;
 }
 
 void decide(rt_adaptive *a, int32_t n_samples) {
@@ -101,17 +85,10 @@ int slice(rt_adaptive *a, int32_t n_samples, const std::vector<uint32_t> &list, 
     hipStream_t stream = (hipStream_t)a->params.stream;
     st.active_tiles = (uint32_t)list.size();
     if (list.empty()) return RT_OK;
-    // the monitor's numbers per sub-tile: the update's from before the slice, the estimate's from after it
-    std::vector<AdTileArgs> args(a->n_tiles);
+    std::vector<AdTileArgs> args;
+    adaptive_slice_args(a->tiles.data(), a->observed.data(), a->n_tiles, n_samples, list, args);
     std::vector<bool> drawn(a->n_tiles, false);
     for (uint32_t t : list) drawn[t] = true;
-    for (uint32_t t = 0; t < a->n_tiles; t++) {
-        const rt_adaptive_tile &T = a->tiles[t];
-        const int32_t N = a->observed[t], n = drawn[t] ? n_samples : 0;
-        AdTileArgs &A = args[t];
-        A.n = (float)n_samples; A.N = (float)N; A.N1 = (float)(N + n_samples); A.first = N == 0;
-        A.dof = (float)(T.batches + (drawn[t] ? 1 : 0) - 1); A.d = (float)(T.samples + n);
-    }
     HIP_CHECK(hipMemcpyAsync(a->d_args, args.data(), args.size() * sizeof(AdTileArgs), hipMemcpyHostToDevice, stream));
     HIP_CHECK(hipMemcpyAsync(a->d_list, list.data(), list.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
     const size_t chunk_tiles = std::max<size_t>(1u, source_chunk_slots() / 64u);
@@ -155,14 +132,11 @@ int slice(rt_adaptive *a, int32_t n_samples, const std::vector<uint32_t> &list, 
     HIP_CHECK(hipMemcpyAsync(est.data(), a->d_tiles, est.size() * sizeof(AdTile), hipMemcpyDeviceToHost, stream));
     HIP_CHECK(hipStreamSynchronize(stream));
     for (uint32_t t = 0; t < a->n_tiles; t++) {
-        rt_adaptive_tile &T = a->tiles[t];
         if (drawn[t]) {
-            T.samples += n_samples; T.batches += 1; a->observed[t] += n_samples;
-            st.samples += (uint64_t)tile_pixels(a, t) * (uint64_t)n_samples;
+            adaptive_count_slice(a->tiles[t], a->observed[t], n_samples);
+            st.samples += (uint64_t)adaptive_tile_pixels(t, a->sub_w, a->view.width, a->view.height) * (uint64_t)n_samples;
         }
-        const bool none = est[t].nonfinite == AD_NO_ESTIMATE;
-        T.sum_se2 = est[t].sum_se2; T.sum_luminance = est[t].sum_luminance; T.pixels = est[t].pixels; T.nonfinite = none ? 0u : est[t].nonfinite;
-        T.flags = (T.flags & ~RT_ADAPTIVE_NO_ESTIMATE) | (none ? RT_ADAPTIVE_NO_ESTIMATE : 0u);
+        adaptive_take_estimate(a->tiles[t], est[t]);
     }
     return RT_OK;
 }
@@ -190,7 +164,7 @@ int render(rt_adaptive *a, int32_t n_samples, const uint8_t *mask, rt_adaptive_s
         const int rc = guarded(who, [&]() -> int { return slice(a, n_samples, list, st, who); });
         if (rc != RT_OK) { a->broken = rt_last_error(); return rc; } // the slice failed under way (a refusal or a HIP error): the state is half advanced
         if (!mask) decide(a, n_samples);
-        fill_counts(a, st);
+        adaptive_tile_counts(a->tiles.data(), a->tiles.size(), st.converged_tiles, st.capped_tiles, st.min_samples, st.max_samples);
         st.total_ms = now_ms() - t0;
         if (stats) *stats = st;
         return RT_OK;
@@ -209,10 +183,7 @@ int rt_adaptive_create(rt_scene *scene, const rt_render_params *p, const rt_adap
         if (p->struct_size != sizeof(rt_render_params)) return fail(RT_ERR_INVALID_ARG, who + "params.struct_size mismatch (ABI skew)");
         if (ap->struct_size != sizeof(rt_adaptive_params)) return fail(RT_ERR_INVALID_ARG, who + "adaptive.struct_size mismatch (ABI skew)");
         if (p->reserved != 0 || ap->reserved != 0) return fail(RT_ERR_INVALID_ARG, who + "reserved must be 0");
-        if (!(ap->target_noise > 0.f) || !std::isfinite(ap->target_noise)) return fail(RT_ERR_INVALID_ARG, who + "adaptive.target_noise must be positive and finite");
-        if (ap->min_batches < 0 || ap->min_batches == 1) return fail(RT_ERR_INVALID_ARG, who + "adaptive.min_batches must be at least 2 (0 = 4): the scatter of batch means needs 2");
-        if (ap->max_samples < 0) return fail(RT_ERR_INVALID_ARG, who + "adaptive.max_samples must not be negative (0 = the sample-index limit)");
-        if (ap->flags & ~RT_ADAPTIVE_DILATE) return fail(RT_ERR_INVALID_ARG, who + "adaptive.flags other than RT_ADAPTIVE_DILATE");
+        if (const std::string why = adaptive_params_refusal(*ap); !why.empty()) return fail(RT_ERR_INVALID_ARG, who + why);
         if (p->integrator != RT_INTEGRATOR_HW8 || scene->flavor != RT_INTEGRATOR_HW8)
             return fail(RT_ERR_UNSUPPORTED, who + "adaptive sampling runs the persistent hw8 kernel: RT_INTEGRATOR_HW8 on a scene created for it only (integrator " +
                                             std::to_string(p->integrator) + ", scene prepared for " + std::to_string(scene->flavor) + "); there is no fallback");
@@ -324,9 +295,7 @@ int rt_adaptive_noise(rt_adaptive *a, uint32_t flags, float *out_se, rt_noise_su
     return guarded(who, [&]() -> int {
         if (const int rc = usable(a, who)) return rc;
         int32_t batches = 0, observed = 0, total = 0;
-        for (uint32_t t = 0; t < a->n_tiles; t++) {
-            batches = std::max(batches, a->tiles[t].batches); observed = std::max(observed, a->observed[t]); total = std::max(total, a->tiles[t].samples);
-        }
+        adaptive_largest(a->tiles.data(), a->observed.data(), a->n_tiles, batches, observed, total);
         if (batches < 2) return fail(RT_ERR_INVALID_ARG, who + "no sub-tile has 2 batches yet (" + std::to_string(batches) + " at most): the scatter of batch means needs at least 2");
         if (out_se) { // the map: the estimate once more, with the numbers of the state as it stands
             HIP_CHECK(hipSetDevice(a->scene->device));
@@ -341,26 +310,9 @@ int rt_adaptive_noise(rt_adaptive *a, uint32_t flags, float *out_se, rt_noise_su
             se.copy_back(stream);
             HIP_CHECK(hipStreamSynchronize(stream));
         }
-        if (summary) { // noise_summarise's sums (rtamd_noise.hip), over the sub-tiles that have an estimate, in the frame's order
-            uint64_t pixels = 0, nonfinite = 0;
-            double se2 = 0, lum = 0, worst = 0;
-            for (const rt_adaptive_tile &t : a->tiles) {
-                if (t.flags & RT_ADAPTIVE_NO_ESTIMATE) continue;
-                nonfinite += t.nonfinite;
-                if (!t.pixels) continue;
-                pixels += t.pixels;
-                se2 += (double)t.sum_se2;
-                lum += (double)t.sum_luminance;
-                const double mean = (double)t.sum_se2 / (double)t.pixels;
-                if (mean > worst) worst = mean;
-            }
-            rt_noise_summary *s = summary;
-            s->batches = batches; s->samples_observed = observed; s->samples_total = total;
-            s->pixels = pixels; s->nonfinite_pixels = nonfinite;
-            s->mean_luminance = pixels ? lum / (double)pixels : 0.0;
-            s->rms_error = pixels ? std::sqrt(se2 / (double)pixels) : 0.0;
-            s->noise = s->mean_luminance != 0.0 ? s->rms_error / s->mean_luminance : 0.0;
-            s->worst_tile_noise = s->mean_luminance != 0.0 ? std::sqrt(worst) / s->mean_luminance : 0.0;
+        if (summary) {
+            summary->batches = batches; summary->samples_observed = observed; summary->samples_total = total;
+            adaptive_summarise(a->tiles.data(), a->tiles.size(), summary);
         }
         return RT_OK;
     });

@@ -24,6 +24,7 @@
 #include "device/rt_persistent.h"
 #include "device/rt_adaptive.h"
 #include "device/rt_views.h"
+#include "device/rt_view_adaptive.h"
 #include "device/rt_kernels_hw6.h"
 #include "device/rt_persistent_hw6.h"
 #include "device/rt_kernels_txt.h"
@@ -1328,4 +1329,31 @@ void rtamd::views_launch_seed(const rt_scene *, const RenderView &R, hipStream_t
 void rtamd::views_launch_resolve(const rt_scene *, const RenderView &R, hipStream_t stream) {
     hipLaunchKernelGGL(dev::accum_resolve_kernel, dim3((R.n_pixslots + 255u) / 256u), dim3(256), 0, stream, R);
     HIP_CHECK(hipGetLastError());
+}
+
+// ---- rt_view_adaptive_*: the flat kernels around the view source over a strip of sub-tiles (device/rt_view_adaptive.h; the host side is
+// rtamd_view_adaptive.hip) -------------------------------------------------------------------------------------------------------------
+namespace {
+template <class K> uint32_t view_adaptive_launch(K kernel, const rt_scene *scene, uint32_t lanes, const RenderView &R, const ViewAdaptiveView &V, hipStream_t stream) {
+    if (!lanes) return 0u;
+    hipLaunchKernelGGL(kernel, dim3(query_geometry(scene, lanes).flat_blocks), dim3(256), 0, stream, R, V);
+    HIP_CHECK(hipGetLastError());
+    return 1u;
+}
+} // namespace
+
+uint32_t rtamd::view_adaptive_launch_gather(const rt_scene *scene, const RenderView &R, const ViewAdaptiveView &V, hipStream_t stream) {
+    return view_adaptive_launch(dev::va_gather_kernel, scene, V.strip_slots, R, V, stream);
+}
+uint32_t rtamd::view_adaptive_launch_scatter(const rt_scene *scene, const RenderView &R, const ViewAdaptiveView &V, hipStream_t stream) {
+    return view_adaptive_launch(dev::va_scatter_kernel, scene, V.n_list * 64u, R, V, stream);
+}
+uint32_t rtamd::view_adaptive_launch_update(const rt_scene *scene, const RenderView &R, const ViewAdaptiveView &V, hipStream_t stream) {
+    return view_adaptive_launch(dev::va_update_kernel, scene, V.n_list * 64u, R, V, stream);
+}
+uint32_t rtamd::view_adaptive_launch_estimate(const rt_scene *scene, const RenderView &R, const ViewAdaptiveView &V, hipStream_t stream) {
+    return view_adaptive_launch(dev::va_estimate_kernel, scene, V.count * 64u, R, V, stream);
+}
+uint32_t rtamd::view_adaptive_launch_resolve(const rt_scene *scene, const RenderView &R, const ViewAdaptiveView &V, hipStream_t stream) {
+    return view_adaptive_launch(dev::va_resolve_kernel, scene, R.n_pixslots, R, V, stream);
 }

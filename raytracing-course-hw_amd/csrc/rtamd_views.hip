@@ -50,29 +50,16 @@ int usable(const rt_views *v, const std::string &who) {
     return RT_OK;
 }
 
-// The refusals of a camera array, before anything is touched; `first`: the view of cameras[0].
+// The refusals of a camera array (host/rt_views_camera.h), before anything is touched; `first`: the view of cameras[0].
 int check_cameras(const rt_camera *cameras, int32_t first, int32_t n, const std::string &who) {
-    for (int32_t i = 0; i < n; i++) {
-        const std::string why = views_camera_check(cameras[i]);
-        if (!why.empty()) return fail(RT_ERR_INVALID_ARG, who + "cameras: view " + std::to_string(first + i) + ": " + why);
-    }
-    return RT_OK;
-}
-
-// The record the kernel reads: the camera's vectors as given, the two tangents by the expressions of the scene's own camera
-// (set_triangle_view: host libm in double; frame_tan_fov_x).
-ViewCamera camera_record(const rt_camera &c, int32_t width, int32_t height) {
-    ViewCamera r{};
-    for (int k = 0; k < 3; k++) { r.pos[k] = c.position[k]; r.right[k] = c.right[k]; r.up[k] = c.up[k]; r.fwd[k] = c.forward[k]; }
-    r.tan_fov_y = (float)std::tan((double)(c.fov_y / 2)); // scene.cpp:180
-    r.tan_fov_x = r.tan_fov_y * width / height;           // scene.cpp:181
-    return r;
+    const std::string why = views_cameras_check(cameras, first, n);
+    return why.empty() ? RT_OK : fail(RT_ERR_INVALID_ARG, who + why);
 }
 
 // Views first .. first + n - 1 get `cameras` and a fresh state: sum 0, engines reseeded, 0 samples.
 void reset_views(rt_views *v, int32_t first, int32_t n, const rt_camera *cameras) {
     std::vector<ViewCamera> rec((size_t)n);
-    for (int32_t i = 0; i < n; i++) rec[(size_t)i] = camera_record(cameras[i], v->view.width, v->view.height);
+    for (int32_t i = 0; i < n; i++) rec[(size_t)i] = views_camera_record(cameras[i], v->view.width, v->view.height);
     HIP_CHECK(hipMemcpyAsync(v->d_cameras + first, rec.data(), rec.size() * sizeof(ViewCamera), hipMemcpyHostToDevice, v->stream));
     for (int32_t i = first; i < first + n; i++) {
         RenderView R = v->view;

@@ -15,6 +15,7 @@
 #include "host/fold_nodes.h"
 #include "host/hip_check.h"
 #include "host/rt_adaptive_decide.h"
+#include "host/rt_view_adaptive_plan.h"
 #include "host/rt_views_camera.h"
 #include "host/rt_guard.h"
 #include "host/rt_scene.h"
@@ -975,6 +976,30 @@ int rtt_gather_records(const void *records, uint32_t n, uint32_t elem_bytes, con
 int rtt_adaptive_decide(const rt_adaptive_tile *tiles, const rt_adaptive_params *params, int32_t sub_w, int32_t sub_h, int32_t n_samples, uint32_t *flags) {
     if (!tiles || !params || !flags || sub_w < 1 || sub_h < 1) return RT_ERR_INVALID_ARG;
     rtamd::adaptive_decide(tiles, *params, sub_w, sub_h, n_samples, flags);
+    return RT_OK;
+}
+
+// The planning step of an adaptive slice over a view set (host/rt_view_adaptive_plan.h) on tables of the test's own: n_views tables of
+// sub_w * sub_h entries and their observed samples in; out, for a slice of n_samples, the flags the call decides before it launches
+// (tile_mask: the stored flags), the ascending list of words view * tiles + sub-tile with its length, and the monitor's numbers per
+// (view, sub-tile), 24 bytes each.  tile_mask != NULL is rt_view_adaptive_render_tiles' plan, else view_mask (nullable) is the policy's.
+int rtt_view_adaptive_plan(const rt_adaptive_tile *tiles, const int32_t *observed, const rt_adaptive_params *params, int32_t sub_w, int32_t sub_h, int32_t n_views,
+                           int32_t n_samples, const uint8_t *view_mask, const uint8_t *tile_mask, uint32_t *flags, uint32_t *list, uint32_t *n_list, void *args) {
+    if (!tiles || !observed || !params || !flags || !list || !n_list || !args || sub_w < 1 || sub_h < 1 || n_views < 1) return RT_ERR_INVALID_ARG;
+    const size_t per_view = (size_t)sub_w * (size_t)sub_h, n = per_view * (size_t)n_views;
+    std::vector<uint32_t> l;
+    if (tile_mask) {
+        for (size_t G = 0; G < n; G++) flags[G] = tiles[G].flags;
+        rtamd::view_adaptive_list_tiles(tile_mask, n, l);
+    } else {
+        rtamd::view_adaptive_decide(tiles, *params, sub_w, sub_h, n_views, n_samples, view_mask, flags);
+        rtamd::view_adaptive_list_policy(flags, per_view, n_views, view_mask, l);
+    }
+    std::vector<rtamd::AdTileArgs> a;
+    rtamd::adaptive_slice_args(tiles, observed, n, n_samples, l, a);
+    memcpy(list, l.data(), l.size() * sizeof(uint32_t));
+    *n_list = (uint32_t)l.size();
+    memcpy(args, a.data(), a.size() * sizeof(rtamd::AdTileArgs));
     return RT_OK;
 }
 
