@@ -73,11 +73,24 @@ namespace dev {
 #define PT_COST_SHADE 14u
 #define PT_DEBUG_BLOCKS 2048           // RTAMD_DEBUG_COUNTERS: workgroups whose start / exit times are recorded (>= 256 CUs x 5)
 #define PT_DRAINED 0xFFFFFFFEu        // `cur` of a lane whose stack is empty and whose last leaf is still to be tested (reads as a leaf: the lane waits)
+// `cur` of a lane that walks nothing: just below the leaf bit and above every node index (an array of 64-byte nodes below 4 GiB has fewer than
+// 2^26), so that one compare tells an inner node from all the rest and the leaf bit alone tells who waits for a leaf phase.
+#define PT_IDLE 0x7FFFFFFDu           // no walk
+#define PT_FULL 0x7FFFFFFEu           // the walk is over, its stack column could not take a node's children: full() and end() are due
+#define PT_ENDED 0x7FFFFFFFu          // the walk is over: its end() is due
+RT_DEV bool pt_is_inner(uint32_t cur) { return cur < PT_IDLE; }
+RT_DEV bool pt_is_ending(uint32_t cur) { return (int32_t)cur > (int32_t)PT_IDLE; } // PT_FULL or PT_ENDED (leaves are negative)
 #define PT_T_OVERFLOW (-1.f)          // t of a closest-hit record whose walk ran out of stack: the exact role redoes the query
 // ---- one step of a walk over the four-wide grid nodes (rt_types.h GpuNode4Q), shared with rt_persistent_hw6.h ------------------------
-#define PT_WIDE_NONE 0                // no child entered: the caller pops its stack
-#define PT_WIDE_WENT 1                // `cur` is the child to visit next, the others wait in the lane's stack column
-#define PT_WIDE_FULL 2                // the column cannot take the children that would wait (nothing was pushed, `cur` unchanged)
+// A step yields the lane's next `cur`: the child to visit (the others wait in the lane's stack column), or, when no child is entered, what
+// pt_pop_or_end gives, or PT_FULL when the column cannot take the children that would wait (nothing is pushed then).
+//
+// pt_pop_or_end: what a lane with nothing at hand visits next — the top of its column; with an empty column the walk is over (PT_ENDED),
+// unless leaves are parked (`parked`): those are tested first (PT_DRAINED).
+RT_DEV uint32_t pt_pop_or_end(uint32_t (*stack)[64], int lane, int &sp, bool parked) {
+    if (sp != 0) return stack[--sp][lane];
+    return parked ? PT_DRAINED : PT_ENDED;
+}
 // sort key of a child: its entry distance's (rt_device.h slab_enter_q), or the last of all for one that is not entered
 RT_DEV uint32_t pt_near_key(bool entered, uint32_t key) { return entered ? key : 0xFFFFFFFFu; }
 // compare-exchange of (key, child word) pairs: the smaller key first
@@ -100,7 +113,7 @@ RT_DEV void pt_node_records(const GlobalBytes nodes, uint32_t cur, uint4 &b0, ui
 // Closest-hit walks: the entered children nearest first — the nearest becomes `cur`, the others are pushed farthest first.
 // `cap`: entries the column may hold.
 template <class NODES>
-RT_DEV int pt_wide_step_nearest(const NODES nodes, const RayGrid &ray, float cull_t, uint32_t (*stack)[64], int lane, int &sp, int cap, uint32_t &cur) {
+RT_DEV uint32_t pt_wide_step_nearest(const NODES nodes, const RayGrid &ray, float cull_t, uint32_t (*stack)[64], int lane, int &sp, int cap, uint32_t cur, bool parked) {
     uint4 b0, b1, b2, b3;
     pt_node_records(nodes, cur, b0, b1, b2, b3);
     uint32_t k0, k1, k2, k3;
@@ -110,13 +123,12 @@ RT_DEV int pt_wide_step_nearest(const NODES nodes, const RayGrid &ray, float cul
     uint32_t c0 = b0.w, c1 = b1.w, c2 = b2.w, c3 = b3.w;
     pt_order(k0, c0, k1, c1); pt_order(k2, c2, k3, c3); pt_order(k0, c0, k2, c2); pt_order(k1, c1, k3, c3); pt_order(k1, c1, k2, c2);
     const int nh = (int)h0 + (int)h1 + (int)h2 + (int)h3;
-    if (nh == 0) return PT_WIDE_NONE;
-    if (sp + nh - 1 > cap) return PT_WIDE_FULL;
+    if (nh == 0) return pt_pop_or_end(stack, lane, sp, parked);
+    if (sp + nh - 1 > cap) return PT_FULL;
     if (nh > 3) stack[sp++][lane] = c3;
     if (nh > 2) stack[sp++][lane] = c2;
     if (nh > 1) stack[sp++][lane] = c1;
-    cur = c0;
-    return PT_WIDE_WENT;
+    return c0;
 }
 // Which records of wide node `cur` a light sum enters: the one decision of the light walker (pt_wide_step_all) and of the shader's
 // settling of light sums (pt_light_reach), so that both take it with the same code.
@@ -136,19 +148,18 @@ RT_DEV void pt_node_records(const PtRootNode root, uint32_t, uint4 &b0, uint4 &b
 }
 // Light sums: every entered child is walked, in any order (the callers keep their hits sorted): the first one now, the others wait.
 template <class NODES>
-RT_DEV int pt_wide_step_all(const NODES nodes, const RayGrid &ray, uint32_t (*stack)[64], int lane, int &sp, int cap, uint32_t &cur) {
+RT_DEV uint32_t pt_wide_step_all(const NODES nodes, const RayGrid &ray, uint32_t (*stack)[64], int lane, int &sp, int cap, uint32_t cur, bool parked) {
     uint4 b0, b1, b2, b3;
     bool h0, h1, h2, h3;
     pt_wide_enter_all(nodes, cur, ray, b0, b1, b2, b3, h0, h1, h2, h3);
-    const int nh = (int)h0 + (int)h1 + (int)h2 + (int)h3;
-    if (nh == 0) return PT_WIDE_NONE;
-    if (sp + nh - 1 > cap) return PT_WIDE_FULL;
-    const int first = h0 ? 0 : h1 ? 1 : h2 ? 2 : 3;
-    if (h3 && first != 3) stack[sp++][lane] = b3.w;
-    if (h2 && first < 2) stack[sp++][lane] = b2.w;
-    if (h1 && first < 1) stack[sp++][lane] = b1.w;
-    cur = first == 0 ? b0.w : first == 1 ? b1.w : first == 2 ? b2.w : b3.w;
-    return PT_WIDE_WENT;
+    if (!(h0 || h1 || h2 || h3)) return pt_pop_or_end(stack, lane, sp, parked);
+    // an entered child waits when one before it is entered too: decided on the lane masks of the four tests, no counting of hits
+    const bool w3 = h3 && (h0 || h1 || h2), w2 = h2 && (h0 || h1), w1 = h1 && h0;
+    if (sp + (int)w3 + (int)w2 + (int)w1 > cap) return PT_FULL;
+    if (w3) stack[sp++][lane] = b3.w;
+    if (w2) stack[sp++][lane] = b2.w;
+    if (w1) stack[sp++][lane] = b1.w;
+    return h0 ? b0.w : h1 ? b1.w : h2 ? b2.w : b3.w;
 }
 // The shader settles the light sums whose walk enters no record of the light tree's root (pt_light_reach < PT_LIGHT_SETTLE) instead of
 // handing them to the light walker.
@@ -200,6 +211,7 @@ struct PtParams {
     const uint32_t *group_ofs, *group_ids;
     uint32_t *group_cost;
     uint32_t resume;
+    int stack_cap;                    // counting builds only: entries a walker's stack column may hold (the kernel's own, or RTAMD_PT_STACK_CAP); the plain kernels hold it as an immediate
     int refill, leaf_batch;           // as in rt_wavefront.h (refill = closest-hit walker's | light walker's << 16; leaf_batch = batch | share << 16)
     int shade_min;                    // a wave turns shader when this many paths wait for shading (64 = a full wave of them)
     int shade_thr0, shade_thr_step;   // wave w stops refilling its walkers when need_shade holds >= thr0 + w * step paths
@@ -281,7 +293,10 @@ template <class SH> RT_DEV void pt_complete(SH &sh, uint32_t l, uint32_t bit, bo
 //   Queue                           which queue it serves and how a finished lane is published (PtTraceQueue, PtLightQueue)
 //   COST_NODE, COST_TEST            what a node step / a leaf test adds to the walk's `steps`, the cost measure of the re-deal (PT_COST_*)
 //   begin(slot)                     read the ray from the path's record, reset the walk's state
-//   step(cur, sp)                   one wide step (PT_WIDE_*); full(): what a full stack column means for the walk
+//   step<COUNT>(cur, sp, parked)    one wide step: the lane's next `cur` (pt_wide_step_*); full(): what a full stack column means for the walk's result
+// The walk's place is `cur` and `sp` alone: a node or a leaf to visit, PT_DRAINED, or one of the marks PT_IDLE, PT_ENDED, PT_FULL.  The node loop
+// writes nothing but `cur`, `sp`, `steps` and the parked leaves; a walk that ends there, by an empty column or a full one, only leaves its mark in
+// `cur`, and full() and end() run outside the loop (DEFER) or right where the mark appears (immediate endings), through one `finish`.
 //   Leaf, test(i, sp, lf)           the state of one leaf phase and its per-triangle body: tests record i, returns whether it was its leaf's last
 //   leaves_done(lf, sp)             after a lane's leaf loop; returns whether the walk is over whatever its stack holds
 //   end(l, slot, steps)             the end of a walk: writes its result, returns the lane's `fin` word (path l, bit 31 for the queue's use)
@@ -316,23 +331,27 @@ RT_DEV void pt_walk_stint(WK &w, SH &sh, const PtParams &P, PtWave &wv, uint32_t
     typedef typename WK::Queue Q;
     constexpr int K = Q::ID; // PtProf's index of the walker
     const int lane = threadIdx.x & 63;
-    bool active = false, refill_ok = true, ending = false; // ending (DEFER): the walk is over, its end() runs at the top of the next pass
-    uint32_t l = 0, slot = 0, cur = 0, fin = PT_NONE;      // fin: the lane's finished, unpublished path
+    bool refill_ok = true;
+    uint32_t l = 0, slot = 0, cur = PT_IDLE, fin = PT_NONE; // fin: the lane's finished, unpublished path
     int sp = 0;
     uint32_t pend = RT_EMPTY_LEAF, pend2 = RT_EMPTY_LEAF, pend3 = RT_EMPTY_LEAF; // the leaves this lane has met and not yet tested (pend first)
     uint32_t steps = 0;   // node steps + leaf tests of the lane's current walk, weighted
-    auto end_walk = [&]() {
-        active = false;
-        if (DEFER) ending = true; else fin = w.end(l, slot, steps);
+    auto finish = [&]() { // of a lane whose `cur` is PT_ENDED or PT_FULL
+        if (cur == PT_FULL) { // the parked leaves stay untested: a rare role redoes the query
+            w.full();
+            pend = RT_EMPTY_LEAF; pend2 = RT_EMPTY_LEAF; pend3 = RT_EMPTY_LEAF;
+        }
+        fin = w.end(l, slot, steps);
+        cur = PT_IDLE;
     };
     PtLap<COUNT> clk;
     for (;;) {
         // Walks that ended since the last pass write their results here, together: in the loops below a lane only marks itself, so the
         // code of an ending (gap code or sum, record store, cost counter) runs once per pass and not in every step in which some lane ends.
-        if (DEFER && pt_ballot(ending)) {
-            if (ending) { fin = w.end(l, slot, steps); ending = false; }
+        if (DEFER && pt_ballot(pt_is_ending(cur))) {
+            if (pt_is_ending(cur)) finish();
         }
-        const unsigned long long idle = pt_ballot(!active);
+        const unsigned long long idle = pt_ballot(cur == PT_IDLE);
         if (idle && (__popcll(idle) >= Q::refill_at(P) || idle == ~0ull)) {
             // Hand-off point.  Finished lanes are published here and not the moment they finish: the release (a wait for the
             // wave's outstanding record stores) is paid once per refill, when the stores have long landed, not once per walk.
@@ -347,7 +366,7 @@ RT_DEV void pt_walk_stint(WK &w, SH &sh, const PtParams &P, PtWave &wv, uint32_t
             if (!refill_ok) {}
             else if (pt_count(&sh.cnt[PT_Q_SHADE]) >= shade_thr) refill_ok = false;      // shaders are behind: drain, then help them
             else if (pt_count(&sh.cnt[Q::ID]) > 0) {
-                const uint32_t got = pt_pop(sh.need[Q::ID], &sh.cnt[Q::ID], wv.nw, wv.cur[Q::ID], !active, wv.front_first, COUNT ? &prof.pops[K] : nullptr);
+                const uint32_t got = pt_pop(sh.need[Q::ID], &sh.cnt[Q::ID], wv.nw, wv.cur[Q::ID], cur == PT_IDLE, wv.front_first, COUNT ? &prof.pops[K] : nullptr);
                 __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
                 sub.lap(prof.t_sub[K][1]);
                 n_queries += __popcll(pt_ballot(got != PT_NONE));
@@ -356,43 +375,37 @@ RT_DEV void pt_walk_stint(WK &w, SH &sh, const PtParams &P, PtWave &wv, uint32_t
                     w.begin(slot);
                     steps = 0;
                     cur = 0; sp = 0; pend = RT_EMPTY_LEAF; pend2 = RT_EMPTY_LEAF; pend3 = RT_EMPTY_LEAF;
-                    active = true;
                 }
                 sub.lap(prof.t_sub[K][2]);
             }
         }
-        const unsigned long long m_active = pt_ballot(active);
+        const unsigned long long m_active = pt_ballot(cur != PT_IDLE);
         clk.lap(prof.t_part[K][0]);
         if (!m_active) break;
         const int lb = pt_leaf_batch(P.leaf_batch, m_active);
         for (;;) { // phase 1: inner nodes
             // A lane that meets a leaf keeps it for the next leaf phase and walks on with what its stack holds (a leaf beyond its slots stops
             // it): more lanes stay in the node loop, and more of them bring a leaf to each leaf phase.
-            if (active && (cur & RT_LEAF_BIT) && (SLOTS == 3 ? pend3 : pend2) == RT_EMPTY_LEAF && cur != PT_DRAINED) {
+            if ((cur & RT_LEAF_BIT) && (SLOTS == 3 ? pend3 : pend2) == RT_EMPTY_LEAF && cur != PT_DRAINED) {
                 if (pend == RT_EMPTY_LEAF) pend = cur; else if (SLOTS == 2 || pend2 == RT_EMPTY_LEAF) pend2 = cur; else pend3 = cur; // (an empty leaf leaves the slot as it was)
-                cur = sp == 0 ? PT_DRAINED : stack[--sp][lane];
-                if (cur == PT_DRAINED && pend == RT_EMPTY_LEAF) end_walk(); // an empty leaf was all that was left
+                cur = pt_pop_or_end(stack, lane, sp, pend != RT_EMPTY_LEAF); // (PT_ENDED: an empty leaf was all that was left)
+                if (!DEFER && cur == PT_ENDED) finish();
             }
-            const bool inner = active && !(cur & RT_LEAF_BIT);
-            if (!pt_ballot(inner) || __popcll(pt_ballot(active && (cur & RT_LEAF_BIT))) >= lb) break;
+            // The two ballots that end the phase: no lane is at an inner node, or at least `lb` lanes wait at a leaf (the marks are neither).
+            // One flag, not `||`: both conditions are wave-uniform, and two exits would be two branch targets at the loop's top.
+            const bool inner = pt_is_inner(cur);
+            const bool stop = (pt_ballot(inner) == 0ull) | (__popcll(pt_ballot((cur & RT_LEAF_BIT) != 0u)) >= lb);
+            if (stop) break;
             if (COUNT) { prof.iters[K]++; prof.lane_iters[K] += __popcll(pt_ballot(inner)); }
             if (inner) {
                 if (COUNT) n_nodes++;
                 steps += WK::COST_NODE;
-                const int went = w.step(cur, sp);
-                if (went == PT_WIDE_NONE) {
-                    if (sp != 0) cur = stack[--sp][lane];
-                    else if (pend != RT_EMPTY_LEAF) cur = PT_DRAINED;
-                    else end_walk();
-                } else if (went == PT_WIDE_FULL) { // the walk ends here, the parked leaves untested: a rare role redoes the query
-                    w.full();
-                    pend = RT_EMPTY_LEAF; pend2 = RT_EMPTY_LEAF; pend3 = RT_EMPTY_LEAF;
-                    end_walk();
-                }
+                cur = w.template step<COUNT>(cur, sp, pend != RT_EMPTY_LEAF);
+                if (!DEFER && pt_is_ending(cur)) finish();
             }
         }
         clk.lap(prof.t_part[K][1]);
-        const bool at_leaf = active && pend != RT_EMPTY_LEAF;
+        const bool at_leaf = pend != RT_EMPTY_LEAF && (!DEFER || cur != PT_FULL); // (idle lanes have nothing parked)
         if (COUNT) { prof.leaf_iters[K]++; prof.leaf_lane_iters[K] += __popcll(pt_ballot(at_leaf)); }
         if (at_leaf) { // phase 2: the lane's parked leaves, in the order it met them
             uint32_t i = pend & ~RT_LEAF_BIT, more = pend2, more2 = pend3;
@@ -407,7 +420,10 @@ RT_DEV void pt_walk_stint(WK &w, SH &sh, const PtParams &P, PtWave &wv, uint32_t
             }
             const bool over = w.leaves_done(lf, sp);
             pend = RT_EMPTY_LEAF; pend2 = RT_EMPTY_LEAF; pend3 = RT_EMPTY_LEAF;
-            if (cur == PT_DRAINED || over) end_walk(); // a lane that stopped at a leaf beyond its slots keeps that for the next round
+            if (cur == PT_DRAINED || over) { // a lane that stopped at a leaf beyond its slots keeps that for the next round
+                cur = PT_ENDED;
+                if (!DEFER) finish();
+            }
         }
         clk.lap(prof.t_part[K][2]);
     }
@@ -437,7 +453,10 @@ struct PtTraceWalk {
         h_ray = S.exact_boxes ? pt_look_behind_abs(d, S.box_c2x) : 0.f;
         hit = WF_MISS; best_t = RT_T_MAX; cull_t = RT_T_MAX; t2 = 2.f * RT_T_MAX; best_u = 0.f; best_v = 0.f;
     }
-    RT_DEV int step(uint32_t &cur, int &sp) { return pt_wide_step_nearest(nodes, ray, cull_t, stack, lane, sp, P8_STACK, cur); }
+    // (the cap of the column is an immediate but in the counting build, where RTAMD_PT_STACK_CAP may lower it)
+    template <bool COUNT> RT_DEV uint32_t step(uint32_t cur, int &sp, bool parked) {
+        return pt_wide_step_nearest(nodes, ray, cull_t, stack, lane, sp, COUNT ? P.stack_cap : P8_STACK, cur, parked);
+    }
     // The column is full (a walk holds up to three entries per level of a tree of up to P8_STACK / 2 levels; this takes a ray that
     // grazes many boxes: triangle soups).  The walk says so — no hit has a negative t — and the exact role walks the query with a
     // stack of its own (pt_exact_batch).
@@ -486,7 +505,9 @@ template <bool COUNT> struct PtLightWalk {
         ray = make_ray_grid(S.grid, o, d);
         k = 0; overflow = false;
     }
-    RT_DEV int step(uint32_t &cur, int &sp) { return pt_wide_step_all(nodes, ray, stack, lane, sp, P8_STACK - 2 * k - 1, cur); } // the hits sit at the column's top
+    template <bool> RT_DEV uint32_t step(uint32_t cur, int &sp, bool parked) { // the hits sit at the column's top
+        return pt_wide_step_all(nodes, ray, stack, lane, sp, (COUNT ? P.stack_cap : P8_STACK) - 2 * k - 1, cur, parked);
+    }
     RT_DEV void full() { overflow = true; } // no room beside the hits
     RT_DEV void take(Leaf &lf, int sp) { // the held hit joins the lane's hits
         bool robust;

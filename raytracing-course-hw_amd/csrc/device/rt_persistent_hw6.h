@@ -293,7 +293,9 @@ struct P6TraceWalk {
         h_ray = S.exact_boxes ? pt_look_behind_abs(d, S.box_c2x) : 0.f;
         hit = 0xFFFFFFFFu; best_ref = 0xFFFFFFFFu; best_t = RT_T_MAX; cull_t = RT_T_MAX; t2 = 2.f * RT_T_MAX; best_inside = false;
     }
-    RT_DEV int step(uint32_t &cur, int &sp) { return pt_wide_step_nearest(S.nodes4, ray, cull_t, stack, lane, sp, P6_STACK, cur); }
+    template <bool COUNT> RT_DEV uint32_t step(uint32_t cur, int &sp, bool parked) {
+        return pt_wide_step_nearest(S.nodes4, ray, cull_t, stack, lane, sp, COUNT ? P.stack_cap : P6_STACK, cur, parked);
+    }
     RT_DEV void full() { best_t = PT_T_OVERFLOW; hit = 0u; t2 = PT_T_OVERFLOW; best_inside = false; } // the exact role redoes the query (rt_persistent.h)
     RT_DEV bool test(uint32_t i, int, Leaf &) {
         Tri6Regs T = load_tri6(S.tris + i);
@@ -339,7 +341,9 @@ struct P6LightWalk {
         ray = make_ray_grid(S.grid, o, d);
         k = 0; many = false; fragile = false; term0 = 0.f; term1 = 0.f;
     }
-    RT_DEV int step(uint32_t &cur, int &sp) { return pt_wide_step_all(S.fast_light_nodes4, ray, stack, lane, sp, P6_STACK, cur); }
+    template <bool COUNT> RT_DEV uint32_t step(uint32_t cur, int &sp, bool parked) {
+        return pt_wide_step_all(S.fast_light_nodes4, ray, stack, lane, sp, COUNT ? P.stack_cap : P6_STACK, cur, parked);
+    }
     RT_DEV void full() { many = true; fragile = false; k = RT6_MAX_LIGHT_HITS + 1; } // the slow role walks the sum in the reference's order
     RT_DEV void take(Leaf &lf) { // the held hit's pdf term, robustness test and bookkeeping
         const Tri6Regs T = load_tri6(S.fast_lights + lf.h_i);

@@ -332,6 +332,7 @@ static void redeal_groups(rt_scene *scene, const uint32_t *d_cost, uint32_t *d_o
 struct PersistentKernel {
     uint32_t max_paths;               // paths per workgroup (its LDS bitmap)
     int per_cu;                       // workgroups per CU
+    int stack;                        // entries of a walker's stack column (P8_STACK, P6_STACK)
     size_t record_bytes;              // path record per slot
     int cost_t, cost_l;               // PtParams::cost_t / cost_l
     bool hw8_knobs;                   // RTAMD_WF_SPLIT, RTAMD_PT_PRIO and the RTAMD_TRACE_PIXEL dump apply
@@ -345,7 +346,7 @@ static PersistentKernel hw8_persistent(const SceneView &V, int ray_depth, hipStr
     // kernel variant by the features this render can reach (fewer features, fewer spilled registers): the hw7 integrator has no
     // environment map; an hw8 render needs the environment lookup only when the scene has a map
     const int feat = V.hw7 ? WF_FEAT_HW7 : (V.env_image >= 0 ? WF_FEAT_ENV : 0);
-    return {PT_MAX_PATHS, P8_PER_CU, 16u * stride, 7, 8, true, 2.0, 0.3,
+    return {PT_MAX_PATHS, P8_PER_CU, P8_STACK, 16u * stride, 7, 8, true, 2.0, 0.3,
             [=, &V](uint32_t blocks, const RenderView &R, const dev::PtParams &P, float4 *records, uint32_t slot_base, uint32_t n_slots) {
                 dev::WfView W{};
                 W.r0 = records; W.stride = stride; W.n_slots = n_slots; W.slot_base = slot_base;
@@ -375,7 +376,7 @@ static PersistentKernel hw8_persistent(const SceneView &V, int ray_depth, hipStr
 }
 
 static PersistentKernel hw6_persistent(const SceneView6 &V, hipStream_t stream, bool count) {
-    return {P6_MAX_PATHS, P6_PER_CU, (size_t)P6_REC * sizeof(float4), 1, 1, false, 1.5, 0.4, // the record holds the path's frames
+    return {P6_MAX_PATHS, P6_PER_CU, P6_STACK, (size_t)P6_REC * sizeof(float4), 1, 1, false, 1.5, 0.4, // the record holds the path's frames
             [=, &V](uint32_t blocks, const RenderView &R, const dev::PtParams &P, float4 *records, uint32_t slot_base, uint32_t) {
                 const dev::W6View W{records, slot_base};
                 if (count) hipLaunchKernelGGL(dev::p6_persistent_kernel<true>, dim3(blocks), dim3(P6_THREADS), 0, stream, V, R, W, P);
@@ -402,6 +403,10 @@ static void launch_persistent(rt_scene *scene, const PersistentKernel &k, const 
     const int leaf_share = env_positive("RTAMD_WF_LEAF_SHARE_256", 112) & 0x7fff;
     P.refill = env_positive("RTAMD_TRACE_REFILL", WF_REFILL) | (env_positive("RTAMD_LIGHT_REFILL", env_positive("RTAMD_TRACE_REFILL", WF_REFILL)) << 16);
     P.leaf_batch = (env_positive("RTAMD_TRACE_LEAF_BATCH", 28) & 255) | (leaf_share << 16); // lanes that hold two leaves (or have nothing else left) before a leaf phase starts
+    // RTAMD_PT_STACK_CAP=n (test knob): the walkers' columns count as full beyond n entries, so that a small scene reaches the endings of a
+    // full column (the exact role redoes those queries: same pixels).  Counting launches only: the plain kernels hold the cap as an immediate.
+    P.stack_cap = k.stack;
+    if (const int v = env_int("RTAMD_PT_STACK_CAP", 0); count && v >= 1 && v < k.stack) P.stack_cap = v;
     P.shade_min = 0; // set per pass below
     P.shade_thr0 = env_positive("RTAMD_PT_SHADE_THR0", 128);
     P.shade_thr_step = env_positive("RTAMD_PT_SHADE_STEP", 512);
